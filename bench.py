@@ -38,7 +38,7 @@ PEAK_HBM_GBS = 8000.0
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--d", type=int, default=16)
@@ -60,7 +60,55 @@ def parse():
     ap.add_argument("--driver", choices=["auto", "c", "python"], default="auto",
                     help="who drives the sharded path: the C entry point flgp_dev_heat_kernel_covariance_sharded with an RCCL "
                          "flgp_comm (default for N > 1), or flgp_amd/pipeline.py over torch.distributed (default for N = 1: it times the stages)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, < 64 MB in all): "
+                         "values (K,), and a fixed seeded sample of rows of H (n x m) and of the eigenvectors V (n x K); "
+                         "se_grid: values (10, K) and distances_mean (1,)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_ROWS = 3072          # sampled rows of H and V
+DUMP_COLS = 1024          # at most this many columns of each: 2 x 3072 x 1024 x 8 B = 50 MB, plus the values
+DUMP_SEED = 777
+
+
+def dump_sample(res, n, lo, n_loc, m, device, world):
+    """The last timed step's outputs as host float64 arrays: ``values`` in full, and the rows
+    ``random_anchor_rows(n, DUMP_ROWS, DUMP_SEED)`` (sorted) of H and V -- all m columns of H (a seeded
+    selection of DUMP_COLS when m is larger) and the leading DUMP_COLS columns of V.  Every rank fills the
+    sampled rows it owns and a sum over ranks assembles them (an entry has exactly one contributor)."""
+    rows = np.sort(synth.random_anchor_rows(n, min(n, DUMP_ROWS), seed=DUMP_SEED))
+    mine = (rows >= lo) & (rows < lo + n_loc)
+    loc = torch.from_numpy(rows[mine] - lo).to(device)
+    where = torch.from_numpy(np.nonzero(mine)[0]).to(device)
+    cols = np.arange(m) if m <= DUMP_COLS else np.sort(synth.random_anchor_rows(m, DUMP_COLS, seed=DUMP_SEED + 1))
+    out = {}
+    Hs = torch.zeros((rows.size, cols.size), dtype=torch.float64, device=device)
+    Hs[where] = res.H[:, loc][torch.from_numpy(cols).to(device)].t().to(torch.float64)    # H is (m, n_loc): column-major n_loc x m
+    parts = {"H_sample": Hs}
+    vectors = getattr(res, "vectors", None)
+    if vectors is not None:
+        kc = min(vectors.shape[0], DUMP_COLS)
+        Vs = torch.zeros((rows.size, kc), dtype=torch.float64, device=device)
+        Vs[where] = vectors[:kc][:, loc].t().to(torch.float64)                           # vectors is (K, n_loc)
+        parts["vectors_sample"] = Vs
+    for name, t_ in parts.items():
+        if world > 1:
+            torch.distributed.all_reduce(t_)
+        out[name] = t_.cpu().numpy()
+    values = getattr(res, "values", None)
+    if values is not None:
+        out["values"] = values.to(torch.float64).cpu().numpy()
+    return out
+
+
+def write_dump(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def prof_query(L, name):
@@ -233,6 +281,8 @@ def main():
                 grid(par)
             torch.cuda.synchronize(device)
             res_t[par] = (time.perf_counter() - t0) * 1e3 / args.steps
+        if args.dump_outputs:       # the last timed step is the max_parallel = 1 pass
+            write_dump(args.dump_outputs, {"values": vals.cpu().numpy(), "distances_mean": np.array([mean.value])})
         out = {
             "metric": "points/sec through k-NN(with distances) -> 10 x [SE weights -> Laplacian -> trunc-SVD -> U] (fit_se_* bandwidth grid), n=1e6 d=16 K=200",
             "value": n / (res_t[10] * 1e-3), "unit": "points/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -289,6 +339,11 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs:           # before the diagnostic step below replaces res
+        dumped = dump_sample(res, n, lo, n_loc, args.m, device, world)
+        if rank == 0:
+            write_dump(args.dump_outputs, dumped)
+        del dumped
 
     # ---- the dominant kernel, from the timed region (HIP events on the launch stream)
     roof = None
