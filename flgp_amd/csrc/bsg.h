@@ -64,6 +64,7 @@ struct BsG {
   int h_meta_own[BSG_META] = {0};
   int *h_meta = h_meta_own;       // host copy of meta
   int launches = 0;               // products issued
+  int verbose = 0;                // eig_verbose, read by bsg_setup
   std::vector<int> h_perm;        // source of an asynchronous upload: lives as long as the struct
   void *h_big = nullptr;          // caller-owned pinned memory for the set-up's larger exchange (bsg_host_slots), or null
   size_t h_big_bytes = 0;

@@ -892,6 +892,9 @@ void bsg_carve(BsG &g, char *&p, int s, int b) {
 
 int bsg_setup(hipStream_t st, const double *dG, int ldg, int s, BsG &g, hipStream_t side, hipEvent_t side_ev) {
   g.built = false; g.on = false; g.lanczos = false;
+  g.verbose = tuning("eig_verbose", 0);
+  const int part_knob = tuning("eig_bs_part_cap", 0);
+  const int part_cap = part_knob < 8 ? 0 : part_knob;                // (below 8: no cap)
   const int rows4 = ceil_div(s, 4);
   int *lab2 = g.rcnt;
   FLGP_HIP(hipMemsetAsync(g.meta, 0, sizeof(int) * BSG_META, st));
@@ -903,7 +906,7 @@ int bsg_setup(hipStream_t st, const double *dG, int ldg, int s, BsG &g, hipStrea
   FLGP_HIP(hipMemcpyAsync(g.h_bounds, g.bounds, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
   // (round 4: the ordering's launches are ENQUEUED before the Lanczos run's 41 -- the host needs 0.2-0.5 ms for those, and the
   //  ordering, which the host then waits for, used to sit behind them; the event that releases the second stream is recorded first)
-  const bool lz = side && side_ev && tuning("eig_lanczos_lo", 1);
+  const bool lz = side && side_ev;
   if (lz) FLGP_HIP(hipEventRecord(side_ev, st));
   // ordering
   hipLaunchKernelGGL(bsg_seed_gather_kernel, dim3(ceil_div((long)s * BSG_SEEDS, 256)), dim3(256), 0, st, dG, ldg, s, g.E0);
@@ -990,7 +993,6 @@ int bsg_setup(hipStream_t st, const double *dG, int ldg, int s, BsG &g, hipStrea
   hipLaunchKernelGGL(bsg_count_kernel, dim3(g.ntile), dim3(256), sizeof(int) * g.nstage, st, g.gptr, g.gcol, g.perm, g.iperm, s,
                      g.nstage, g.cnt);
   FLGP_HIP(hipMemsetAsync(g.tcnt, 0, sizeof(int) * ((size_t)g.ntile * g.nbt + 4), st));
-  const int part_cap = tuning("eig_bs_part_cap", 0) < 8 ? 0 : tuning("eig_bs_part_cap", 0);
   hipLaunchKernelGGL(bsg_lists_kernel, dim3(1), dim3(1024), 0, st, g.cnt, g.ntile, g.nstage, (long)g.pack_cap, g.blkpos,
                      g.nk, g.off, g.klist, g.order, g.meta, part_cap, (int)g.part_max, (int)g.slab_cap, (int4 *)g.parts_u,
                      (int4 *)g.parts, g.slab0);
@@ -1023,15 +1025,15 @@ void bsg_finish(BsG &g) {
       double lo = t20 - 3.0 * std::max(0.0, t15 - t20);
       lo = std::min(lo, 0.9 * t20);
       g.lambda_lo = lo > 0.0 ? lo : 0.0;
-      if (tuning("eig_verbose", 0)) fprintf(stderr, "[flgp eig] Lanczos lambda_min estimates: %.6g (15 steps), %.6g (20) -> lower end %.6g\n", t15, t20, g.lambda_lo);
+      if (g.verbose) fprintf(stderr, "[flgp eig] Lanczos lambda_min estimates: %.6g (15 steps), %.6g (20) -> lower end %.6g\n", t15, t20, g.lambda_lo);
     }
   }
   const double frac = (double)g.h_meta[BSG_M_TOTAL] / ((double)g.ntile * g.nstage);
-  if (tuning("eig_verbose", 0))
+  if (g.verbose)
     fprintf(stderr, "[flgp eig] block-sparse G: %d non-zeros, %.1f %% of the %dx%d blocks kept for the MFMA product (max %d of %d stages "
             "per tile), %d scattered non-zeros\n", g.h_meta[BSG_M_NNZ], 100.0 * frac, BSG_TM, BSG_SK, g.h_meta[BSG_M_MAXNK], g.nstage,
             g.h_meta[BSG_M_RNNZ]);
-  if (tuning("eig_verbose", 0) > 1) {     // the remainder: entries per row, and per tile
+  if (g.verbose > 1) {     // the remainder: entries per row, and per tile
     std::vector<int> rp(g.s + 1);
     if (hipMemcpy(rp.data(), g.rptr, sizeof(int) * (g.s + 1), hipMemcpyDeviceToHost) == hipSuccess) {
       int hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1044,7 +1046,7 @@ void bsg_finish(BsG &g) {
       fprintf(stderr, "\n");
     }
   }
-  if (tuning("eig_verbose", 0) > 1) {     // list lengths of the tiles, longest first
+  if (g.verbose > 1) {     // list lengths of the tiles, longest first
     std::vector<int> nk(g.ntile);
     if (hipMemcpy(nk.data(), g.nk, sizeof(int) * g.ntile, hipMemcpyDeviceToHost) == hipSuccess) {
       std::sort(nk.begin(), nk.end(), [](int a, int b) { return a > b; });
@@ -1053,7 +1055,7 @@ void bsg_finish(BsG &g) {
       fprintf(stderr, "\n");
     }
   }
-  g.on = frac <= 0.01 * std::min(50, tuning("eig_bs_max_pct", 50));
+  g.on = frac <= 0.5;   // (at most half the blocks kept)
 }
 
 static long long *g_bsg_trace = nullptr;     // diagnostic: 4 words per task of the product kernel (see flgp_dev_bsg_set_trace)
@@ -1074,13 +1076,10 @@ int bsg_product(hipStream_t st, BsG &g, const double *Xt, int b, double alpha, d
   if (nbt != g.nbt) { set_error("bsg_product: block width differs from the one the workspace was carved for"); return FLGP_ERR_INVALID; }
   const int npart = g.h_meta[BSG_M_NPART];
   const int ntask = npart * nbt;
-  int grid = std::max(64, tuning("eig_bs_wgs", 256));
-  int xmap = tuning("eig_bs_xmap", 1);
-  if (xmap) {                                       // the layout of the fixed tasks needs (grid / 8) % nbt == 0
-    const int unit = 8 * nbt;
-    if (grid >= unit) grid = grid / unit * unit; else xmap = 0;
-  }
-  if (!xmap) grid = std::min(grid, ntask);
+  // 256 workgroups; the layout of the fixed tasks (xmap) needs (grid / 8) % nbt == 0, else the plain one, one task per workgroup
+  const int unit = 8 * nbt;
+  const int xmap = 256 >= unit ? 1 : 0;
+  const int grid = xmap ? 256 / unit * unit : std::min(256, ntask);
   {
     const double fl = 2.0 * (double)BSG_BLK * (double)g.h_meta[BSG_M_TOTAL] * (double)b;
     ProfScope ps("bsg_gemm_kernel", st, fl);

@@ -121,6 +121,7 @@ struct GemmPair { const double *A2, *B2; double *C2; };
 int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, double *C, GemmFusedReduce *fused);
 // The eigensolver's b x b Gram product out = Xa^T Xb (Xa, Xb: s x b column-major) on its own kernel (rot.hip): split over the
 // rows, planes reduced by gemm.hip's reduction kernels (with the fused extras).  false: not this shape, nothing was launched.
+int gemm_split_limit(int Kd, int ntiles, int gk, bool tile64);
 bool gramk_applicable(int s, int b, const double *Xa, const double *Xb, size_t work_elems);
 int gramk_launch(hipStream_t st, int s, int b, const double *Xa, const double *Xb, double *out, double *work, size_t work_elems,
                  GemmFusedReduce *fused);

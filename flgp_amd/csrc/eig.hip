@@ -44,6 +44,8 @@ struct HostCtx {
   hipEvent_t side_ev = nullptr, mark_ev = nullptr, wait_ev = nullptr;
   void *pinned = nullptr;      // page-locked slots for the solve's small asynchronous read-backs (HOST_SLOT_BYTES)
   void *pinned_dev = nullptr;  // the same memory as the device addresses it (null: kernels cannot write it, copies are used)
+  long spin_us = 2000;         // the solve's EigParams::spin_us / spin_wait (see stream_mark)
+  bool spin_wait = true;
 };
 constexpr int DIST_SLOT_DOUBLES = 64;          // partial sums dist_to_identity_kernel writes straight into host memory
 constexpr int RT_SLOT_DOUBLES = 2 * 4096;      // residuals + sorted Ritz values of a Rayleigh-Ritz step (2 b doubles), likewise
@@ -99,10 +101,9 @@ struct HostCtxLease {
 // Rayleigh-Ritz step of ~1.2 ms); after that the thread blocks in hipEventSynchronize like any other HIP caller, so
 // a kernel that never finishes costs an idle thread, not a spinning one, and a device error surfaces as FLGP_ERR_HIP.
 static hipError_t event_wait(hipEvent_t ev) {
-  const long spin_us = tuning("eig_spin_us", 2000);
   const int rc = bounded_wait(
       [&]() -> int { const hipError_t e = hipEventQuery(ev); return e == hipSuccess ? 0 : (e == hipErrorNotReady ? 1 : 1000 + (int)e); },
-      [&]() -> int { const hipError_t e = hipEventSynchronize(ev); return e == hipSuccess ? 0 : 1000 + (int)e; }, spin_us);
+      [&]() -> int { const hipError_t e = hipEventSynchronize(ev); return e == hipSuccess ? 0 : 1000 + (int)e; }, g_ctx->spin_us);
   return rc == 0 ? hipSuccess : (hipError_t)(rc - 1000);
 }
 static hipError_t stream_mark(hipStream_t st) {
@@ -114,7 +115,7 @@ static hipError_t mark_wait() {
   return event_wait(g_ctx->mark_ev);
 }
 hipError_t stream_wait(hipStream_t st) {
-  if (!g_ctx || !g_ctx->wait_ev || tuning("eig_spin_wait", 1) == 0) return hipStreamSynchronize(st);
+  if (!g_ctx || !g_ctx->wait_ev || !g_ctx->spin_wait) return hipStreamSynchronize(st);
   const hipError_t e = hipEventRecord(g_ctx->wait_ev, st);
   if (e != hipSuccess) return e;
   return event_wait(g_ctx->wait_ev);
@@ -180,9 +181,8 @@ __device__ __forceinline__ double rsqrt_nr(double x) {
 // flags[1]: "converged" latch set by the host-side protocol (kernel exits early)
 __global__ __launch_bounds__(1024) void jac_round_kernel(double *__restrict__ B, double *__restrict__ V, int b,
                                                         int ldb, int w, int nbc, int round, double tol,
-                                                        int *__restrict__ flags, int local_sweeps) {
+                                                        int *__restrict__ flags) {
   extern __shared__ double sm[];
-  __shared__ int any_rot;
   if (flags[1]) return;
   const int tid = threadIdx.x, nt = blockDim.x;
   int I, J;
@@ -212,10 +212,6 @@ __global__ __launch_bounds__(1024) void jac_round_kernel(double *__restrict__ B,
     while (gs > 1 && gs * npair > nt) gs >>= 1;
     const int grp = tid / gs, gl = tid % gs;
     int rotations = 0;
-    for (int ls = 0; ls < local_sweeps; ++ls) {
-    if (tid == 0) any_rot = 0;
-    __syncthreads();
-    int rot_here = 0;
     for (int rr = 0; rr < m2 - 1; ++rr) {
       for (int k0 = 0; k0 < npair; k0 += nt / gs) {   // more pairs than groups: several passes
         const int k = k0 + grp;
@@ -270,16 +266,10 @@ __global__ __launch_bounds__(1024) void jac_round_kernel(double *__restrict__ B,
             const double u = vp_[i], v = vq_[i];
             vp_[i] = cs * u - sn * v; vq_[i] = sn * u + cs * v;
           }
-          if (gl == 0) ++rot_here;
+          if (gl == 0) ++rotations;
         }
       }
       __syncthreads();
-    }
-    rotations += rot_here;
-    if (rot_here) any_rot = 1;
-    __syncthreads();
-    if (!any_rot) break;           // this block of columns is orthogonal to working precision
-    __syncthreads();
     }
     if (rotations) atomicAdd(&flags[0], rotations);
   }
@@ -322,15 +312,15 @@ __device__ __forceinline__ void jac_stamp(long long *tr, int slot) {
 template <int NLOC>
 __global__ __launch_bounds__(1024) void jac_block_kernel(double *__restrict__ B, double *__restrict__ V, int b,
                                                          int ldb, int nbc, int round, double tol,
-                                                         int *__restrict__ flags, int local_sweeps,
-                                                         int cross_only, long long *__restrict__ trace, int batched_load) {
+                                                         int *__restrict__ flags, int cross_only,
+                                                         long long *__restrict__ trace) {
   constexpr int WB = NLOC / 2;        // block-column width
   constexpr int NP = NLOC / 2;        // pairs per local round
   constexpr int NT16 = NLOC / 16;     // 16-wide tiles per side
   constexpr int TILES = NT16 * NT16;
   constexpr int KP = 4;               // row parts of the Gram product
   extern __shared__ double sm[];
-  __shared__ int any_rot, visit_rot;
+  __shared__ int visit_rot;
   __shared__ int round_rot[3];
   if (flags[1]) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -359,7 +349,7 @@ __global__ __launch_bounds__(1024) void jac_block_kernel(double *__restrict__ B,
   //  panels were last written by other XCDs -- 3.4 of a visit's 26 us; now all of a wave's loads are issued, then stored)
   auto load_panel = [&](const double *M) {
     constexpr int CPW = NLOC / 16;      // columns per wave
-    if (b <= 512 && batched_load) {
+    if (b <= 512) {
       d2v tmp[CPW][4];
 #pragma unroll
       for (int cc = 0; cc < CPW; ++cc) {
@@ -482,75 +472,66 @@ __global__ __launch_bounds__(1024) void jac_block_kernel(double *__restrict__ B,
   double mx_num = 0.0, mx_den = 1.0;   // largest squared cosine between two columns rotated in this visit, as a fraction:
                                        // compared by cross-multiplication, divided once at the end (an fp64 division is ~25
                                        // dependent instructions on the round's critical chain; the value only feeds a log line)
-  for (int ls = 0; ls < local_sweeps; ++ls) {
-    if (tid == 0) any_rot = 0;
-    __syncthreads();
-    int rot_here = 0;
-    // cross_only: only the WB x WB pairs (p in block column I, q in block column J) are visited, in WB
-    // rounds; the pairs inside a block column are left to the one visit per sweep that runs the full
-    // round-robin (jacobi_run: round 0), so a sweep rotates every pair of the b columns exactly once
-    const int nrounds = cross_only ? NP : NLOC - 1;
-    for (int rr = 0; rr < nrounds; ++rr) {
-      if (tid < NP) {
-        int p, q;
-        if (cross_only) { p = tid; q = NP + ((tid + rr) & (NP - 1)); }
-        else rr_pair(NLOC, rr, tid, p, q);
-        const double al = Gc[p * NLOC + p], be = Gc[q * NLOC + q], ga = Gc[p * NLOC + q];
-        double cs = 1.0, sn = 0.0;
-        if (ga * ga > tol2 * (al * be) && al > 0.0 && be > 0.0) {
-          const double dl = be - al;
-          const double r1 = rsqrt_nr(dl * dl + 4.0 * (ga * ga));
-          const double x2 = 0.5 + 0.5 * (__builtin_fabs(dl) * r1);
-          const double r2 = rsqrt_nr(x2);
-          cs = x2 * r2;
-          sn = (dl >= 0.0 ? ga : -ga) * (r1 * r2);
-          ++rot_here;
-          round_rot[rr % 3] = 1;
-          if ((ga * ga) * mx_den > mx_num * (al * be)) { mx_num = ga * ga; mx_den = al * be; }
-        }
-        cc[p] = cs; dd[p] = -sn;              // new_p = c old_p - s old_q
-        cc[q] = cs; dd[q] = sn;               // new_q = s old_p + c old_q
-        pr[tid] = p | (q << 16);              // the round's pairs, by leader
+  // cross_only: only the WB x WB pairs (p in block column I, q in block column J) are visited, in WB
+  // rounds; the pairs inside a block column are left to the one visit per sweep that runs the full
+  // round-robin (jacobi_run: round 0), so a sweep rotates every pair of the b columns exactly once
+  const int nrounds = cross_only ? NP : NLOC - 1;
+  for (int rr = 0; rr < nrounds; ++rr) {
+    if (tid < NP) {
+      int p, q;
+      if (cross_only) { p = tid; q = NP + ((tid + rr) & (NP - 1)); }
+      else rr_pair(NLOC, rr, tid, p, q);
+      const double al = Gc[p * NLOC + p], be = Gc[q * NLOC + q], ga = Gc[p * NLOC + q];
+      double cs = 1.0, sn = 0.0;
+      if (ga * ga > tol2 * (al * be) && al > 0.0 && be > 0.0) {
+        const double dl = be - al;
+        const double r1 = rsqrt_nr(dl * dl + 4.0 * (ga * ga));
+        const double x2 = 0.5 + 0.5 * (__builtin_fabs(dl) * r1);
+        const double r2 = rsqrt_nr(x2);
+        cs = x2 * r2;
+        sn = (dl >= 0.0 ? ga : -ga) * (r1 * r2);
+        ++rotations;
+        round_rot[rr % 3] = 1;
+        if ((ga * ga) * mx_den > mx_num * (al * be)) { mx_num = ga * ga; mx_den = al * be; }
       }
-      if (tid == 0) round_rot[(rr + 2) % 3] = 0;   // last read two barriers ago, next set two barriers on
-      __syncthreads();
-      if (!round_rot[rr % 3]) continue;            // nobody rotates: both buffers stay as they are
-      // A rotation round acts on 2 x 2 blocks: the block (pair a, pair b) of the matrix and the entries (row i, pair b) of
-      // Wm are rebuilt by ONE thread each -- one LDS read per output instead of four (two for Wm): with sixteen waves
-      // queueing at the LDS pipe the rebuild is a matter of its LDS instructions, 224 per round element by element, 112
-      // this way.  Every output is the same expression, in the same operation order, as the element-wise form.
-      for (int item = tid; item < NP * NP + NLOC * NP; item += 1024) {
-        if (item < NP * NP) {
-          const int a = item / NP, bq = item % NP;
-          const int pqa = pr[a], pqb = pr[bq];
-          const int pa = pqa & 0xffff, qa = pqa >> 16, pb = pqb & 0xffff, qb = pqb >> 16;
-          const double ca = cc[pa], sa = dd[qa], cb = cc[pb], sb = dd[qb];
-          const double g00 = Gc[pa * NLOC + pb], g01 = Gc[pa * NLOC + qb], g10 = Gc[qa * NLOC + pb], g11 = Gc[qa * NLOC + qb];
-          Gn[pa * NLOC + pb] = ca * (cb * g00 + (-sb) * g01) + (-sa) * (cb * g10 + (-sb) * g11);
-          Gn[pa * NLOC + qb] = ca * (cb * g01 + sb * g00) + (-sa) * (cb * g11 + sb * g10);
-          Gn[qa * NLOC + pb] = ca * (cb * g10 + (-sb) * g11) + sa * (cb * g00 + (-sb) * g01);
-          Gn[qa * NLOC + qb] = ca * (cb * g11 + sb * g10) + sa * (cb * g01 + sb * g00);
-        } else {
-          const int v = item - NP * NP;
-          const int i = v / NP, bq = v % NP;
-          const int pqb = pr[bq];
-          const int pb = pqb & 0xffff, qb = pqb >> 16;
-          const double cb = cc[pb], sb = dd[qb];
-          const double w0 = Wc[i * NLOC + pb], w1 = Wc[i * NLOC + qb];
-          Wn[i * NLOC + pb] = cb * w0 + (-sb) * w1;
-          Wn[i * NLOC + qb] = cb * w1 + sb * w0;
-        }
-      }
-      __syncthreads();
-      double *t1 = Gc; Gc = Gn; Gn = t1;
-      double *t2 = Wc; Wc = Wn; Wn = t2;
+      cc[p] = cs; dd[p] = -sn;              // new_p = c old_p - s old_q
+      cc[q] = cs; dd[q] = sn;               // new_q = s old_p + c old_q
+      pr[tid] = p | (q << 16);              // the round's pairs, by leader
     }
-    rotations += rot_here;
-    if (rot_here) { any_rot = 1; visit_rot = 1; }
+    if (tid == 0) round_rot[(rr + 2) % 3] = 0;   // last read two barriers ago, next set two barriers on
     __syncthreads();
-    if (!any_rot) break;
+    if (!round_rot[rr % 3]) continue;            // nobody rotates: both buffers stay as they are
+    // A rotation round acts on 2 x 2 blocks: the block (pair a, pair b) of the matrix and the entries (row i, pair b) of
+    // Wm are rebuilt by ONE thread each -- one LDS read per output instead of four (two for Wm): with sixteen waves
+    // queueing at the LDS pipe the rebuild is a matter of its LDS instructions, 224 per round element by element, 112
+    // this way.  Every output is the same expression, in the same operation order, as the element-wise form.
+    for (int item = tid; item < NP * NP + NLOC * NP; item += 1024) {
+      if (item < NP * NP) {
+        const int a = item / NP, bq = item % NP;
+        const int pqa = pr[a], pqb = pr[bq];
+        const int pa = pqa & 0xffff, qa = pqa >> 16, pb = pqb & 0xffff, qb = pqb >> 16;
+        const double ca = cc[pa], sa = dd[qa], cb = cc[pb], sb = dd[qb];
+        const double g00 = Gc[pa * NLOC + pb], g01 = Gc[pa * NLOC + qb], g10 = Gc[qa * NLOC + pb], g11 = Gc[qa * NLOC + qb];
+        Gn[pa * NLOC + pb] = ca * (cb * g00 + (-sb) * g01) + (-sa) * (cb * g10 + (-sb) * g11);
+        Gn[pa * NLOC + qb] = ca * (cb * g01 + sb * g00) + (-sa) * (cb * g11 + sb * g10);
+        Gn[qa * NLOC + pb] = ca * (cb * g10 + (-sb) * g11) + sa * (cb * g00 + (-sb) * g01);
+        Gn[qa * NLOC + qb] = ca * (cb * g11 + sb * g10) + sa * (cb * g01 + sb * g00);
+      } else {
+        const int v = item - NP * NP;
+        const int i = v / NP, bq = v % NP;
+        const int pqb = pr[bq];
+        const int pb = pqb & 0xffff, qb = pqb >> 16;
+        const double cb = cc[pb], sb = dd[qb];
+        const double w0 = Wc[i * NLOC + pb], w1 = Wc[i * NLOC + qb];
+        Wn[i * NLOC + pb] = cb * w0 + (-sb) * w1;
+        Wn[i * NLOC + qb] = cb * w1 + sb * w0;
+      }
+    }
     __syncthreads();
+    double *t1 = Gc; Gc = Gn; Gn = t1;
+    double *t2 = Wc; Wc = Wn; Wn = t2;
   }
+  if (rotations) visit_rot = 1;
   __syncthreads();
   jac_stamp(tr, 3);
   if (tr && tid == 0) { tr[6] = cross_only; tr[7] = round; tr[4] = tr[5] = 0; trace[0] = trace[0] + 1; }
@@ -1090,7 +1071,63 @@ __global__ __launch_bounds__(256) void apriori_bounds_kernel(const double *__res
 // ------------------------------------------------------------------------------------------
 // host orchestration
 // ------------------------------------------------------------------------------------------
-struct JacobiPlan { int w, nbc, nt; size_t lds; int nloc; /* 32 / 16: MFMA block kernel, 0: scalar kernel */ };
+// The switches a solve reads (flgp_set_tuning), read once at its start: a solve never sees two values of one key even if
+// another thread sets it meanwhile.  Variants that were measured and dropped have no switch; their code is in the history
+// (NOTEBOOK.md).
+struct EigParams {
+  int spin_us, spin_wait;                      // host waits: see stream_mark
+  int guard_pct, guard_sweeps;                 // guard columns (percent of K, at least 24); sweeps on their block
+  int blocksparse, bs_min_s, host_slots;       // block-sparse products from s = bs_min_s on; pinned result slots
+  int start_stream;                            // start block: 0 = the documented one, others for robustness runs
+  int verbose;
+  int ns_plain_below_x10, ns_extra, ns_e0_pct; // plain Newton-Schulz: entry bound, extra steps, predicted error
+  int ns_ell0_exp, ns_tail;                    // scaled Newton-Schulz: l_0 = 10^-ell0_exp, plain steps after l = 1
+  int m0;                                      // filter degree of iteration 0 (a-priori bounds)
+  int amp_exp_early, amp_exp, cut_pct;         // amplification cap 10^amp_exp (before / from iteration 2); cut position
+  int landing_below_e8, landing_margin_pct, landing_boost;
+  int rr_every, rr_skip_below_e6;              // Rayleigh-Ritz on every rr_every-th late iteration
+  int overlap_from_it, overlap_below_e6;       // overlapped Rayleigh-Ritz
+  int sweeps_it1, sweeps_it2;                  // Jacobi sweeps of the early Rayleigh-Ritz steps (iteration 1; rmax > 5e-2)
+  int refine3_above_e4, refine2_above_e8, refine_minus, sweeps2_from_m;   // sweeps of the late ones
+};
+
+static EigParams eig_params() {
+  EigParams p;
+  p.spin_us = tuning("eig_spin_us", 2000);
+  p.spin_wait = tuning("eig_spin_wait", 1);
+  p.guard_pct = tuning("eig_guard_pct", 25);
+  p.guard_sweeps = tuning("eig_guard_sweeps", 1);
+  p.blocksparse = tuning("eig_blocksparse", 1);
+  p.bs_min_s = tuning("eig_bs_min_s", 1536);
+  p.host_slots = tuning("eig_host_slots", 1);
+  p.start_stream = tuning("eig_start_stream", 0);
+  p.verbose = tuning("eig_verbose", 0);
+  p.ns_plain_below_x10 = tuning("eig_ns_plain_below_x10", 45);
+  p.ns_extra = tuning("eig_ns_extra", 2);
+  p.ns_e0_pct = tuning("eig_ns_e0_pct", 30);
+  p.ns_ell0_exp = tuning("eig_ns_ell0_exp", 4);
+  p.ns_tail = tuning("eig_ns_tail", 2);
+  p.m0 = tuning("eig_m0", 8);
+  p.amp_exp_early = tuning("eig_amp_exp_early", 3);
+  p.amp_exp = tuning("eig_amp_exp", 8);
+  p.cut_pct = tuning("eig_cut_pct", 90);
+  p.landing_below_e8 = tuning("eig_landing_below_e8", 100);
+  p.landing_margin_pct = tuning("eig_landing_margin_pct", 40);
+  p.landing_boost = tuning("eig_landing_boost", 3);
+  p.rr_every = tuning("eig_rr_every", 3);
+  p.rr_skip_below_e6 = tuning("eig_rr_skip_below_e6", 1000);
+  p.overlap_from_it = tuning("eig_overlap_from_it", 3);
+  p.overlap_below_e6 = tuning("eig_overlap_below_e6", 10000);
+  p.sweeps_it1 = tuning("eig_sweeps_it1", 2);
+  p.sweeps_it2 = tuning("eig_sweeps_it2", 2);
+  p.refine3_above_e4 = tuning("eig_refine3_above_e4", 2000);
+  p.refine2_above_e8 = tuning("eig_refine2_above_e8", 100);
+  p.refine_minus = tuning("eig_refine_minus", 0);
+  p.sweeps2_from_m = tuning("eig_sweeps2_from_m", 11);
+  return p;
+}
+
+struct JacobiPlan { int w, nbc, nt; size_t lds; int nloc; /* 32 / 16: MFMA block kernel, -1: streamed, 0: scalar kernel */ };
 
 static size_t jac_block_lds(int b, int nloc) { return sizeof(double) * ((size_t)nloc * (b + 2) + 6 * (size_t)nloc * nloc); }
 static_assert(true, "part[] holds 4 Gram partials = 4 nloc^2 doubles; the local Jacobi reuses 2 nloc^2 + 3 nloc of them");
@@ -1098,9 +1135,8 @@ static_assert(true, "part[] holds 4 Gram partials = 4 nloc^2 doubles; the local 
 static JacobiPlan jacobi_plan(int b) {
   JacobiPlan p;
   p.nloc = 0;
-  if (b % 16 == 0 && b >= 32 && tuning("jacobi_scalar", 0) == 0) {
+  if (b % 16 == 0 && b >= 32) {
     for (int nloc : {32, 16}) {
-      if (nloc == 32 && tuning("jacobi_nloc", 32) == 16 && b >= 64) continue;      // (experiments: smaller column blocks, more of them)
       if (jac_block_lds(b, nloc) <= 150 * 1024) {
         p.nloc = nloc; p.w = nloc / 2; p.nbc = (b + p.w - 1) / p.w;
         if (p.nbc & 1) ++p.nbc;
@@ -1109,14 +1145,14 @@ static JacobiPlan jacobi_plan(int b) {
       }
     }
   }
-  if (b > tuning("jacobi_stream_above", 1024) && tuning("jacobi_scalar", 0) == 0) {
+  if (b > 1024) {
     // panels too long for LDS: streamed visits (jac_stream_kernel); any b (ragged rows and block columns are handled)
     p.nloc = -1; p.w = 16; p.nbc = (b + 15) / 16;
     if (p.nbc & 1) ++p.nbc;
     p.nt = 1024; p.lds = 0;
     return p;
   }
-  // 2w columns of B and of V, each b+16 doubles, must fit ~150 KB of LDS
+  // the scalar kernel (b not a multiple of 16, or b < 32): 2w columns of B and of V, each b+16 doubles, must fit ~150 KB of LDS
   int w = (int)((150 * 1024) / (sizeof(double) * 4 * (size_t)(b + 16)));
   int pw = 1;
   while (pw * 2 <= w && pw < 32) pw *= 2;
@@ -1144,8 +1180,8 @@ struct EigWork {
 
 static size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
 
-static int eig_block_size(int s, int K) {
-  int guard = K * tuning("eig_guard_pct", 25) / 100;
+static int eig_block_size(int s, int K, const EigParams &P) {
+  int guard = K * P.guard_pct / 100;
   if (guard < 24) guard = 24;
   int b = K + guard;
   b = (b + 15) / 16 * 16;
@@ -1153,8 +1189,8 @@ static int eig_block_size(int s, int K) {
   return b;
 }
 
-static bool eig_use_dense(int s, int K) {
-  const int b = eig_block_size(s, K);
+static bool eig_use_dense(int s, int K, const EigParams &P) {
+  const int b = eig_block_size(s, K, P);
   return K >= s || s <= 256 || 2 * b >= s;
 }
 
@@ -1191,9 +1227,9 @@ __global__ void bs_unpermute_kernel(const double *__restrict__ R, int s, int K, 
   V[(size_t)k * ldv + perm[ip]] = R[e];
 }
 
-static size_t eig_workspace_bytes(int s, int K) {
-  const bool dense = eig_use_dense(s, K);
-  const int b = dense ? s : eig_block_size(s, K);
+static size_t eig_workspace_bytes(int s, int K, const EigParams &P) {
+  const bool dense = eig_use_dense(s, K, P);
+  const int b = dense ? s : eig_block_size(s, K, P);
   size_t tot = 0;
   if (!dense) tot += 5 * align_up(sizeof(double) * (size_t)s * b);
   tot += 6 * align_up(sizeof(double) * (size_t)b * b);
@@ -1212,7 +1248,7 @@ static size_t eig_workspace_bytes(int s, int K) {
 // rounding threshold (at most 60 sweeps; `strict` turns a miss into FLGP_ERR_NOCONV);
 // sweep_limit = k > 0: exactly k sweeps, a refinement step on an already nearly diagonal T.
 // JV is a product of plane rotations, i.e. orthogonal to rounding, however early the loop stops.
-static int jacobi_run(hipStream_t st, int b, EigWork &w, std::vector<double> &h_lam, int *sweeps_out,
+static int jacobi_run(hipStream_t st, int b, EigWork &w, const EigParams &P, std::vector<double> &h_lam, int *sweeps_out,
                       int sweep_limit, double tol_scale, bool strict, double *JB = nullptr, double *JV = nullptr,
                       bool to_host = true) {
   if (!JB) JB = w.JB;
@@ -1229,21 +1265,20 @@ static int jacobi_run(hipStream_t st, int b, EigWork &w, std::vector<double> &h_
   // rounding noise, so a tighter threshold only chases noise (cf. LAPACK dgesvj: sqrt(m) eps)
   const double tol = tol_scale * 4.0 * std::sqrt((double)b) * 1.1102230246251565e-16;
   int h_flags[4] = {0, 0, 0, 0};
-  const int cross_from = tuning("jacobi_cross_from", 0);   // 1000 = never
   for (int sw = 0; sw < max_sweeps; ++sw) {
     for (int round = 0; round < p.nbc - 1; ++round) {
-      const int cross = (round > 0 && sw >= cross_from) ? 1 : 0;
+      const int cross = round > 0 ? 1 : 0;     // (jac_block_kernel: round 0 visits every pair of its columns, later rounds the cross pairs)
       if (p.nloc < 0)
         hipLaunchKernelGGL(jac_stream_kernel, dim3(p.nbc / 2), dim3(1024), 0, st, JB, JV, b, b, p.nbc, round, tol, w.flags);
       else if (p.nloc == 32)
         hipLaunchKernelGGL(jac_block_kernel<32>, dim3(p.nbc / 2), dim3(1024), p.lds, st, JB, JV, b, b, p.nbc, round,
-                           tol, w.flags, tuning("jacobi_local_sweeps", 1), cross, g_jac_trace, tuning("jacobi_batched_load", 1));
+                           tol, w.flags, cross, g_jac_trace);
       else if (p.nloc == 16)
         hipLaunchKernelGGL(jac_block_kernel<16>, dim3(p.nbc / 2), dim3(1024), p.lds, st, JB, JV, b, b, p.nbc, round,
-                           tol, w.flags, tuning("jacobi_local_sweeps", 1), cross, g_jac_trace, tuning("jacobi_batched_load", 1));
+                           tol, w.flags, cross, g_jac_trace);
       else
         hipLaunchKernelGGL(jac_round_kernel, dim3(p.nbc / 2), dim3(p.nt), p.lds, st, JB, JV, b, b, p.w, p.nbc,
-                           round, tol, w.flags, 1);
+                           round, tol, w.flags);
     }
     hipLaunchKernelGGL(jac_sweep_end_kernel, dim3(1), dim3(64), 0, st, w.flags);
     FLGP_TRY(check_launch("jac_round_kernel"));
@@ -1255,7 +1290,7 @@ static int jacobi_run(hipStream_t st, int b, EigWork &w, std::vector<double> &h_
   }
   hipLaunchKernelGGL(jac_values_kernel, dim3(b), dim3(256), 0, st, JB, JV, b, b, w.lam);
   FLGP_TRY(check_launch("jac_values_kernel"));
-  if (tuning("eig_verbose", 0) > 2) {
+  if (P.verbose > 2) {
     int hf[12];
     FLGP_HIP(hipMemcpyAsync(hf, w.flags, sizeof(hf), hipMemcpyDeviceToHost, st));
     FLGP_HIP(hipStreamSynchronize(st));
@@ -1278,14 +1313,14 @@ static int jacobi_run(hipStream_t st, int b, EigWork &w, std::vector<double> &h_
 
 // symmetric eigendecomposition of the b x b matrix T (device): on return JV holds eigenvectors,
 // h_lam the eigenvalues (unsorted, host copy).  Synchronises the stream.
-static int jacobi_eig(hipStream_t st, const double *T, int ldt, int b, EigWork &w, std::vector<double> &h_lam,
-                      int *sweeps_out, int sweep_limit = -1, double tol_scale = 1.0, bool strict = false,
-                      bool to_host = true) {
+static int jacobi_eig(hipStream_t st, const double *T, int ldt, int b, EigWork &w, const EigParams &P,
+                      std::vector<double> &h_lam, int *sweeps_out, int sweep_limit = -1, double tol_scale = 1.0,
+                      bool strict = false, bool to_host = true) {
   ProfScope ps("jacobi_eig", st, 8.0 * (double)b * b);
   hipLaunchKernelGGL(jac_init_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, T, ldt, b, w.JB, w.JV, b,
                      w.flags);
   FLGP_TRY(check_launch("jac_init_kernel"));
-  return jacobi_run(st, b, w, h_lam, sweeps_out, sweep_limit, tol_scale, strict, nullptr, nullptr, to_host || sweep_limit < 0);
+  return jacobi_run(st, b, w, P, h_lam, sweeps_out, sweep_limit, tol_scale, strict, nullptr, nullptr, to_host || sweep_limit < 0);
 }
 
 // Rayleigh-Ritz refinement for a T that is diagonal up to small couplings EXCEPT in its trailing
@@ -1293,11 +1328,11 @@ static int jacobi_eig(hipStream_t st, const double *T, int ldt, int b, EigWork &
 //   1. the g x g block is diagonalised completely by one workgroup inside LDS (one launch),
 //   2. with V0 = blockdiag(I, Vg), B0 = T V0, `sweeps` global sweeps finish the job
 //      (quadratic convergence: couplings eps -> eps^2 per sweep).
-static int jacobi_refine(hipStream_t st, const double *T, int b, int K, EigWork &w, std::vector<double> &h_lam,
-                         int *sweeps_out, int sweeps, bool to_host = true) {
+static int jacobi_refine(hipStream_t st, const double *T, int b, int K, EigWork &w, const EigParams &P,
+                         std::vector<double> &h_lam, int *sweeps_out, int sweeps, bool to_host = true) {
   const int g = b - K;
   if (g < 2 || 2 * (size_t)g * g > (size_t)b * b)
-    return jacobi_eig(st, T, b, b, w, h_lam, sweeps_out, -1, 1.0);
+    return jacobi_eig(st, T, b, b, w, P, h_lam, sweeps_out, -1, 1.0);
   ProfScope ps("jacobi_refine", st, 8.0 * (double)b * b);
   double *Vg = w.X2;
   if (g <= 64) {
@@ -1306,7 +1341,7 @@ static int jacobi_refine(hipStream_t st, const double *T, int b, int K, EigWork 
                                  (int)lds_small));
     const double tol_g = 4.0 * std::sqrt((double)g) * 1.1102230246251565e-16;
     hipLaunchKernelGGL(small_sym_eig_kernel<64>, dim3(1), dim3(1024), lds_small, st, T + (size_t)K * b + K, b, g, Vg,
-                       tol_g, tuning("eig_guard_sweeps", 1));
+                       tol_g, P.guard_sweeps);
     FLGP_TRY(check_launch("small_sym_eig_kernel"));
   } else {
     // a guard block too large for one workgroup's LDS: the block Jacobi on the g x g matrix itself
@@ -1316,7 +1351,7 @@ static int jacobi_refine(hipStream_t st, const double *T, int b, int K, EigWork 
                        Bg, Vg, g, w.flags);
     FLGP_TRY(check_launch("jac_init_kernel"));
     std::vector<double> tmp;
-    FLGP_TRY(jacobi_run(st, g, w, tmp, nullptr, 4, 1.0, false, Bg, Vg, false));
+    FLGP_TRY(jacobi_run(st, g, w, P, tmp, nullptr, 4, 1.0, false, Bg, Vg, false));
   }
   hipLaunchKernelGGL(embed_block_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, Vg, g, K, b, w.JV);
   FLGP_TRY(check_launch("embed_block_kernel"));
@@ -1331,7 +1366,7 @@ static int jacobi_refine(hipStream_t st, const double *T, int b, int K, EigWork 
     FLGP_TRY(gemm_launch(st, b, b, b, 1.0, T, 1, b, w.JV, 1, b, 0.0, nullptr, 0, 0, w.JB, 1, b, w.gemm_ws, w.gemm_ws_elems,
                          0.0, nullptr));
   }
-  return jacobi_run(st, b, w, h_lam, sweeps_out, sweeps, 1.0, false, nullptr, nullptr, to_host);
+  return jacobi_run(st, b, w, P, h_lam, sweeps_out, sweeps, 1.0, false, nullptr, nullptr, to_host);
 }
 
 // W = JV(:, order), order = the eigenvalues in w.lam descending, all on the device: w.perm = order, w.theta = sorted values
@@ -1357,13 +1392,778 @@ static int sorted_basis(hipStream_t st, const std::vector<double> &lam, const st
   return FLGP_OK;
 }
 
+// The buffers of set[0..n) other than `except`, in order, into out[0..n-1).
+static void others(double *const *set, int n, const double *except, double **out) {
+  int k = 0;
+  for (int q = 0; q < n; ++q)
+    if (set[q] != except) out[k++] = set[q];
+}
+
+// Chebyshev filter on [c - e, c + e], scaled by sigma1 = e / (top - c) so that it is 1 at the top Ritz value; degree m
+struct FilterPlan { double c, e, sigma1; int m; };
+
+// ------------------------------------------------------------------------------------------
+// The truncated solve (the file's header comment; K < s and s > 256): one object per solve, one method per step.
+// ------------------------------------------------------------------------------------------
+struct EigSolver {
+  hipStream_t st;
+  const double *dG;
+  int ldg, s, K, b;
+  long tot;                 // s * b
+  double tol;
+  const EigParams &P;
+  EigWork &w;
+  BsG bs;
+
+  // host-visible result slots (HostCtx::pinned): [bsg | a-priori bounds | dist partials | residuals + Ritz values]
+  double *dist_h = nullptr, *dist_d = nullptr, *rt_h = nullptr, *rt_d = nullptr;
+  double h_apriori_own[2 * APRIORI_BLOCKS];
+  double *h_apriori = h_apriori_own;
+  hipStream_t side_st = nullptr;   // second stream: late Rayleigh-Ritz refinements run beside the filter's GEMMs
+  hipEvent_t side_ev = nullptr;
+  bool use_rot = false;     // rotations on rot.hip's kernel; W is then kept k-major (`wt` = 1 tells its producers)
+  int wt = 0;
+  const double *t_q = nullptr, *t_z = nullptr;   // blocks whose transposes currently sit in bs.T[0], bs.T[1]
+
+  // Four s x b buffers take turns in the roles of an iteration: Q = the current orthonormal block, F[0] receives G Q,
+  // F[1] and F[2] are free.  An iteration leaves the new block in one of the four and the other three become F again.
+  double *Q = nullptr, *F[3] = {nullptr, nullptr, nullptr};
+  double *result = nullptr; // the converged Ritz vectors
+
+  std::vector<double> lam, theta, res, rt;
+  std::vector<int> order;
+  int sweeps = 0, ns_orths = 0, jac_orths = 0;
+  int it = 0, gprods = 0, last_m = 0, since_rr = 0, it_meas = 0;
+  double cond = 0.0, rmax_prev = 1.0, rate = 0.1, rmax_meas = 0.0;
+  double lambda_lo = 0.0;   // far end of the damped interval (bs.lambda_lo while the Ritz values allow it)
+
+  EigSolver(hipStream_t st_, const double *dG_, int ldg_, int s_, int K_, int b_, double tol_, const EigParams &P_, EigWork &w_)
+      : st(st_), dG(dG_), ldg(ldg_), s(s_), K(K_), b(b_), tot((long)s_ * b_), tol(tol_), P(P_), w(w_),
+        theta(b_), res(K_), rt(2 * (size_t)b_) {}
+
+
+  // ---- products ------------------------------------------------------------------------------
+  int gemmG(const double *Xin, double alpha, double beta, const double *E, double gamma, const double *E2,
+                       double *out) {  // out = alpha G Xin + beta E + gamma E2   (s x b)
+    return gemm_launch(st, s, b, s, alpha, dG, 1, ldg, Xin, 1, s, beta, E, 1, s, out, 1, s, w.gemm_ws,
+                       w.gemm_ws_elems, gamma, E2, w.tickets);
+  }
+  // ---- block-sparse products (bs.on): blocks live transposed (b x s, the b values of one row contiguous) while
+  //      the filter runs, so that both the tiled GEMM (over the listed k stages of P G P^T) and the CSR remainder
+  //      read and write whole 8b-byte rows
+  int to_t(const double *in, double *out_t) {     // s x b  ->  b x s
+    hipLaunchKernelGGL(bs_transpose_kernel, dim3(ceil_div(s, 32), ceil_div(b, 32)), dim3(256), 0, st, in, s, b, out_t);
+    return check_launch("bs_transpose_kernel");
+  }
+  int from_t(const double *in_t, double *out) {   // b x s  ->  s x b
+    hipLaunchKernelGGL(bs_transpose_kernel, dim3(ceil_div(b, 32), ceil_div(s, 32)), dim3(256), 0, st, in_t, b, s, out);
+    return check_launch("bs_transpose_kernel");
+  }
+  // out = G X, the product that opens an iteration
+  int apply_g(const double *X, double *out) {
+    if (bs.on) {
+      FLGP_TRY(to_t(X, bs.T[0]));
+      FLGP_TRY(bsg_product(st, bs, bs.T[0], b, 1.0, 0.0, nullptr, 0.0, nullptr, bs.T[1]));
+      FLGP_TRY(from_t(bs.T[1], out));
+      t_q = X; t_z = out;
+    } else {
+      FLGP_TRY(gemmG(X, 1.0, 0.0, nullptr, 0.0, nullptr, out));
+    }
+    ++gprods;
+    return FLGP_OK;
+  }
+  int gram_small(const double *Xa, const double *Xb, double *out, GemmFusedReduce *fr = nullptr) {  // out = Xa^T Xb   (b x b)
+    if (gramk_applicable(s, b, Xa, Xb, w.gemm_ws_elems)) return gramk_launch(st, s, b, Xa, Xb, out, w.gemm_ws, w.gemm_ws_elems, fr);
+    return gemm_launch(st, b, b, s, 1.0, Xa, s, 1, Xb, 1, s, 0.0, nullptr, 0, 0, out, 1, b, w.gemm_ws,
+                       w.gemm_ws_elems, 0.0, nullptr, w.tickets, fr);
+  }
+  int rotate(const double *Xin, const double *Wm, double *out) {  // out = Xin Wm   (s x b)(b x b)
+    if (use_rot) return rot_launch(st, s, b, 1.0, Xin, nullptr, Wm, 0.0, nullptr, nullptr, out, nullptr);
+    return gemm_launch(st, s, b, b, 1.0, Xin, 1, s, Wm, 1, b, 0.0, nullptr, 0, 0, out, 1, s, w.gemm_ws,
+                       w.gemm_ws_elems, 0.0, nullptr, w.tickets);
+  }
+  // two rotations by the same W in one launch (the Ritz vectors and G times them)
+  int rotate2(const double *X1, const double *X2, const double *Wm, double *out1, double *out2) {
+    if (use_rot) return rot_launch(st, s, b, 1.0, X1, X2, Wm, 0.0, nullptr, nullptr, out1, out2);
+    const GemmPair pr{X2, Wm, out2};
+    return gemm_launch(st, s, b, b, 1.0, X1, 1, s, Wm, 1, b, 0.0, nullptr, 0, 0, out1, 1, s, w.gemm_ws, w.gemm_ws_elems, 0.0,
+                       nullptr, nullptr, nullptr, &pr);
+  }
+  int small_gemm(const double *Am, const double *Bm, double alpha, double beta, const double *E,
+                            double *out) {  // out = alpha Am Bm + beta E   (b x b, column-major)
+    if (b % 16 == 0) {
+      SmallGemmPair pr;
+      pr.g[0] = SmallGemm{Am, Bm, E, out, alpha, beta};
+      pr.g[1] = pr.g[0];
+      ProfScope ps("small_gemm_kernel", st, 2.0 * (double)b * b * b);
+      hipLaunchKernelGGL(small_gemm_kernel, dim3(b / 16, b / 16, 1), dim3(64), 0, st, pr, b);
+      return check_launch("small_gemm_kernel");
+    }
+    return gemm_launch(st, b, b, b, alpha, Am, 1, b, Bm, 1, b, beta, E, 1, b, out, 1, b, w.gemm_ws, w.gemm_ws_elems,
+                       0.0, nullptr);
+  }
+  // two independent products in one launch: out0 = A0 B0, out1 = A1 B1
+  int small_gemm2(const double *A0, const double *B0, double *out0, const double *A1, const double *B1,
+                             double *out1) {
+    if (b % 16 == 0) {
+      SmallGemmPair pr;
+      pr.g[0] = SmallGemm{A0, B0, nullptr, out0, 1.0, 0.0};
+      pr.g[1] = SmallGemm{A1, B1, nullptr, out1, 1.0, 0.0};
+      ProfScope ps("small_gemm_kernel", st, 4.0 * (double)b * b * b);
+      hipLaunchKernelGGL(small_gemm_kernel, dim3(b / 16, b / 16, 2), dim3(64), 0, st, pr, b);
+      return check_launch("small_gemm_kernel");
+    }
+    FLGP_TRY(small_gemm(A0, B0, 1.0, 0.0, nullptr, out0));
+    return small_gemm(A1, B1, 1.0, 0.0, nullptr, out1);
+  }
+
+  // ---- host questions: |M - diag I|_F from the DIST_BLOCKS partial sums of dist_to_identity_kernel -------------------
+  static_assert(DIST_BLOCKS <= DIST_SLOT_DOUBLES, "slot of the distance partials");
+  double dist_sum(const double *part, int off = 0) const {
+    double sum = 0.0;
+    for (int q = 0; q < DIST_BLOCKS; ++q) sum += part[off + q];
+    return std::sqrt(sum);
+  }
+  int dist_to_identity(const double *M, double *out, double diag = 1.0) {
+    double part_own[DIST_BLOCKS];
+    const double *part = part_own;
+    if (dist_d) {
+      hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M, b, dist_d, diag);
+      FLGP_TRY(check_launch("dist_to_identity_kernel"));
+      part = dist_h;
+    } else {
+      hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M, b, w.res, diag);
+      FLGP_TRY(check_launch("dist_to_identity_kernel"));
+      FLGP_HIP(hipMemcpyAsync(part_own, w.res, sizeof(double) * DIST_BLOCKS, hipMemcpyDeviceToHost, st));
+    }
+    FLGP_HIP(stream_wait(st));
+    *out = dist_sum(part);
+    return FLGP_OK;
+  }
+  // two distances for one question to the host (the second lands in the upper half of the slot)
+  static_assert(2 * DIST_BLOCKS <= DIST_SLOT_DOUBLES, "two sets of distance partials share the slot");
+  int dist_to_identity2(const double *M1, const double *M2, double *out1, double *out2) {
+    if (!dist_d) { FLGP_TRY(dist_to_identity(M1, out1)); return dist_to_identity(M2, out2); }
+    hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M1, b, dist_d);
+    hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M2, b, dist_d + DIST_BLOCKS);
+    FLGP_TRY(check_launch("dist_to_identity_kernel"));
+    FLGP_HIP(stream_wait(st));
+    *out1 = dist_sum(dist_h); *out2 = dist_sum(dist_h, DIST_BLOCKS);
+    return FLGP_OK;
+  }
+
+  // ---- orthonormalisation ----------------------------------------------------------------------
+  // the first step of the coupled iteration, where Z = I:  M = beta I + alpha Y (into Zout: it IS the next Z),  Yout = Y M
+  // (Z_0 = I is never stored: the first step is one product instead of three)
+  int first_step(const double *Yc, double alpha, double beta, double *Zout, double *Yout) {
+    hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, alpha, Yc, beta, w.Id, Zout, (long)b * b);
+    FLGP_TRY(check_launch("eig_axpby_kernel"));
+    return small_gemm(Yc, Zout, 1.0, 0.0, nullptr, Yout);
+  }
+
+  // orthonormalise the columns of Yin into Qout ("SVQB" on the column-normalised block, so that the widely different column
+  // norms a Chebyshev filter leaves behind do not enter the conditioning of the Gram matrix); cond_out = the condition
+  // estimate of the scaled Gram matrix.  Three routes, cheapest first: plain Newton-Schulz, scaled Newton-Schulz, Jacobi.
+  static_assert(GEMM_DIST_PARTS == DIST_BLOCKS, "the fused reduction answers in the slots of dist_to_identity_kernel");
+  int orth(const double *Yin, double *Qout, double *cond_out) {
+    double delta = 0.0;
+    // S = D Y^T Y D and |I - S|_F: inside the reduction kernel of the split product (one launch instead of four)
+    GemmFusedReduce fr{1 | 4, w.dinv, dist_d ? dist_d : w.res, w.red, w.redcnt, false};
+    FLGP_TRY(gram_small(Yin, Yin, w.T, &fr));
+    if (fr.done) {
+      double part_own[DIST_BLOCKS];
+      const double *part = dist_d ? dist_h : part_own;
+      if (!dist_d) FLGP_HIP(hipMemcpyAsync(part_own, w.res, sizeof(double) * DIST_BLOCKS, hipMemcpyDeviceToHost, st));
+      FLGP_HIP(stream_wait(st));
+      delta = dist_sum(part);
+    } else {
+      hipLaunchKernelGGL(sym_scale_diag_kernel, dim3(ceil_div(b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
+      hipLaunchKernelGGL(sym_scale_apply_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
+      FLGP_TRY(check_launch("sym_scale_kernel"));
+      FLGP_TRY(dist_to_identity(w.T, &delta));
+    }
+    bool ok = false;
+    if (delta < 0.1 * P.ns_plain_below_x10) {  // |I - S|_F bounds the spectral norm from above, loosely: try, and watch it contract
+                                              // (measured at configs[2]: 3.6 contracted, 5.7 did not)
+      FLGP_TRY(orth_newton_schulz(Yin, Qout, delta, cond_out, &ok));
+      if (ok) return FLGP_OK;
+      // did not contract: rebuild S
+      FLGP_TRY(gram_small(Yin, Yin, w.T));
+      hipLaunchKernelGGL(sym_scale_apply_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
+      FLGP_TRY(check_launch("sym_scale_kernel"));
+    }
+    FLGP_TRY(orth_scaled(Yin, Qout, cond_out, &ok));
+    if (ok) return FLGP_OK;
+    FLGP_TRY(gram_small(Yin, Yin, w.T));
+    hipLaunchKernelGGL(sym_scale_apply_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
+    FLGP_TRY(check_launch("sym_scale_kernel"));
+    return orth_jacobi(Yin, Qout, cond_out);
+  }
+
+  // well-conditioned block (S = w.T): S^-1/2 by the coupled Newton-Schulz iteration -- b x b MFMA GEMMs only
+  //   M = (3 I - Z Y)/2,  Y <- Y M,  Z <- M Z ;  Y -> S^1/2, Z -> S^-1/2   (|I - S| < 1)
+  // *ok = false: the block did not contract (w.T is overwritten, Qout may be)
+  int orth_newton_schulz(const double *Yin, double *Qout, double delta, double *cond_out, bool *ok) {
+    double *Yc = w.T, *Zc = w.JV, *Mm = w.W, *Yn = w.JB, *Zn = w.X2;
+    // the error contracts quadratically, e <- (3/4) e^2 + O(e^3): run the predicted number of
+    // iterations without talking to the host, then check once (|I - S|_F over-estimates e, so
+    // the prediction errs on the safe side); a block that does not contract falls through to Jacobi
+    // (|I - S|_F over-estimates the spectral norm that contracts: the prediction starts from 0.3 |I - S|_F -- over eight start
+    //  blocks at configs[2] one to five steps fewer per orthonormalisation with the closing check still at rounding level,
+    //  13.84 -> 13.70 ms; a prediction that falls short fails that check and the block takes the scaled iteration below)
+    int kmax = P.ns_extra;   // steps beyond the predicted count (the closing check tests the LAST step's M, so one is inherent)
+    for (double e = std::min(delta * 0.01 * P.ns_e0_pct, 0.95); e > 1e-17 && kmax < 40; ++kmax) e = (e < 0.5) ? 0.8 * e * e : 0.5 * e + 0.4 * e * e;
+    for (int k = 0; k < kmax; ++k) {
+      if (k == 0) {
+        FLGP_TRY(first_step(Yc, -0.5, 1.5, Zn, Yn));
+        if (kmax == 1) FLGP_HIP(hipMemcpyAsync(Mm, Zn, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));   // (the closing check reads Mm)
+      } else {
+        FLGP_TRY(small_gemm(Zc, Yc, -0.5, 1.5, w.Id, Mm));
+        FLGP_TRY(small_gemm2(Yc, Mm, Yn, Mm, Zc, Zn));
+      }
+      std::swap(Yc, Yn);
+      std::swap(Zc, Zn);
+    }
+    // the last M must be the identity to rounding.  Its check is a host round trip: the rotation it would
+    // allow is enqueued behind the measurement first (a failed check just overwrites Qout later), so the
+    // GPU multiplies while the host reads the verdict
+    double part_own[DIST_BLOCKS];
+    const double *part = dist_d ? dist_h : part_own;
+    hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, Mm, b, dist_d ? dist_d : w.res);
+    FLGP_TRY(check_launch("dist_to_identity_kernel"));
+    if (!dist_d) FLGP_HIP(hipMemcpyAsync(part_own, w.res, sizeof(double) * DIST_BLOCKS, hipMemcpyDeviceToHost, st));
+    FLGP_HIP(stream_mark(st));
+    // Zc may live in JV or X2; the rotation needs diag(dinv) Z in W (Mm's buffer: read by the kernel above first)
+    hipLaunchKernelGGL(row_scale_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, Zc, b, w.dinv, w.W, 1.0, wt);
+    FLGP_TRY(check_launch("row_scale_kernel"));
+    FLGP_TRY(rotate(Yin, w.W, Qout));
+    FLGP_HIP(mark_wait());
+    const double dm = dist_sum(part);
+    *ok = dm < 1e-13 * std::sqrt((double)b);
+    if (P.verbose > 1) fprintf(stderr, "[flgp orth] delta=%.3e kmax=%d dm=%.2e %s\n", delta, kmax, dm, *ok ? "ok" : "FAILED");
+    if (*ok) {
+      if (cond_out) *cond_out = (1.0 + delta) / std::max(1.0 - delta, 1e-3);
+      ++ns_orths;
+    }
+    return FLGP_OK;
+  }
+
+  // ill-conditioned block (the first filters amplify by 1e3 and leave cond(S) ~ 1e5): the same
+  // Newton-Schulz iteration on S / sigma with sigma >= lambda_max.  Every eigenvalue x of Z Y obeys
+  // x <- x (3 - x)^2 / 4, which maps (0, 3) into (0, 1] and lifts a small x by 9/4 per step until
+  // the quadratic phase: ~log(cond)/log(2.25) + 5 iterations of three b x b GEMMs, against twenty
+  // Jacobi sweeps.  sigma = |S^2|_F^(1/2) over-estimates lambda_max by at most b^(1/4).
+  // *ok = false: no convergence (w.T is overwritten)
+  int orth_scaled(const double *Yin, double *Qout, double *cond_out, bool *ok) {
+    *ok = false;
+    double *Yc = w.T, *Zc = w.JV, *Mm = w.W, *Yn = w.JB, *Zn = w.X2;
+    FLGP_TRY(small_gemm(Yc, Yc, 1.0, 0.0, nullptr, Yn));
+    // (sigma computed on the device -- one question to the host less, one launch more -- measured: 14.90 ms either way)
+    double f2 = 0.0;
+    FLGP_TRY(dist_to_identity(Yn, &f2, 0.0));      // |S^2|_F
+    const double sigma = 1.02 * std::sqrt(f2);
+    if (!(sigma > 0.0 && std::isfinite(sigma))) return FLGP_OK;
+    hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, 1.0 / sigma, Yc, 0.0, w.Id,
+                       Yn, (long)b * b);
+    FLGP_TRY(check_launch("eig_axpby_kernel"));
+    std::swap(Yc, Yn);
+    bool z_is_identity = true;      // Z_0 = I not stored until a step needs it (see first_step)
+    double dm = 1.0;
+    double zn = 0.0;   // |Z - I|_F^2 + 1 >= 1/x_min: an upper bound of cond(S / sigma)
+    bool zn_valid = false;
+    // Dynamically scaled steps (Chen & Chow 2014): with every singular value x of the iterate in [l, 1],
+    //   x <- (a / 2) x (3 - a^2 x^2),  a = sqrt(3 / (1 + l + l^2)),
+    // is the cubic that lifts the lower end the most, l <- (a / 2) l (3 - a^2 l^2) (x 2.6 per step while l is small,
+    // against 1.5 unscaled), and keeps [l, 1] inside itself.  l_0 is a guess: one that is too low costs a few steps,
+    // one that is too high leaves singular values behind that the unscaled steps below then pick up at their own pace.
+    // The step count follows from l alone, so the host is not asked until the end.
+    int kdyn = 0;
+    {
+      double ell = std::pow(10.0, -(double)P.ns_ell0_exp);
+      int after = 0;
+      while (kdyn < 60) {
+        const bool plain = ell > 1.0 - 1e-9;
+        if (plain && after++ >= P.ns_tail) break;
+        const double a = plain ? 1.0 : std::sqrt(3.0 / (1.0 + ell + ell * ell));
+        if (z_is_identity) {
+          FLGP_TRY(first_step(Yc, -0.5 * a * a * a, 1.5 * a, Zn, Yn));
+          z_is_identity = false;
+        } else {
+          FLGP_TRY(small_gemm(Zc, Yc, -0.5 * a * a * a, 1.5 * a, w.Id, Mm));
+          FLGP_TRY(small_gemm2(Yc, Mm, Yn, Mm, Zc, Zn));
+        }
+        std::swap(Yc, Yn);
+        std::swap(Zc, Zn);
+        ell = std::min(1.0, 0.5 * a * ell * (3.0 - a * a * ell * ell));
+        ++kdyn;
+      }
+      if (kdyn == 1)   // (the only step was the first one: its M sits in Zc, not in Mm)
+        FLGP_HIP(hipMemcpyAsync(Mm, Zc, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));
+      if (kdyn) {
+        FLGP_TRY(dist_to_identity2(Mm, Zc, &dm, &zn));      // (zn is wanted only if dm passes: asked in the same breath)
+        *ok = std::isfinite(dm) && dm < 1e-9;
+        zn_valid = *ok;
+      }
+    }
+    if (z_is_identity) {   // (no scaled step ran)
+      FLGP_HIP(hipMemcpyAsync(Zc, w.Id, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));
+      z_is_identity = false;
+    }
+    for (int k = 0; k < 72 && !*ok && std::isfinite(dm); ++k) {
+      FLGP_TRY(small_gemm(Zc, Yc, -0.5, 1.5, w.Id, Mm));
+      FLGP_TRY(small_gemm2(Yc, Mm, Yn, Mm, Zc, Zn));
+      std::swap(Yc, Yn);
+      std::swap(Zc, Zn);
+      if ((kdyn || k >= 8) && k % 3 == 2) {
+        FLGP_TRY(dist_to_identity(Mm, &dm));
+        if (!std::isfinite(dm)) break;
+        *ok = dm < 1e-9;
+      }
+    }
+    if (P.verbose > 1) fprintf(stderr, "[flgp orth] scaled: sigma=%.3e scaled steps=%d dm=%.2e %s\n", sigma, kdyn, dm, *ok ? "ok" : "FAILED");
+    if (!*ok) return FLGP_OK;
+    if (!zn_valid) FLGP_TRY(dist_to_identity(Zc, &zn));
+    hipLaunchKernelGGL(row_scale_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, Zc, b, w.dinv, w.W,
+                       1.0 / std::sqrt(sigma), wt);  // W = D (Z / sqrt(sigma))
+    FLGP_TRY(check_launch("row_scale_kernel"));
+    if (cond_out) {
+      *cond_out = 1.0 + zn * zn;
+      if (dm > 1e-12) *cond_out = std::max(*cond_out, 2e8);   // ask for the second pass
+    }
+    ++ns_orths;
+    return rotate(Yin, w.W, Qout);
+  }
+
+  // the last resort (S = w.T): S = V L V^T by Jacobi, Qout = Yin D V L^-1/2
+  int orth_jacobi(const double *Yin, double *Qout, double *cond_out) {
+    ++jac_orths;
+    FLGP_TRY(jacobi_eig(st, w.T, b, b, w, P, lam, &sweeps));
+    double lmax = 0.0;
+    for (int j = 0; j < b; ++j) lmax = std::max(lmax, lam[j]);
+    std::vector<int> ord(b);
+    for (int j = 0; j < b; ++j) ord[j] = j;
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return lam[x] > lam[y]; });
+    std::vector<double> sc(b);
+    const double floor_ = lmax * 1e-28;
+    double lmin = lmax;
+    for (int j = 0; j < b; ++j) {
+      const double l = std::max(lam[ord[j]], floor_);
+      lmin = std::min(lmin, l);
+      sc[j] = 1.0 / std::sqrt(l);
+    }
+    if (cond_out) *cond_out = (lmin > 0.0) ? lmax / lmin : 1e300;
+    FLGP_TRY(sorted_basis(st, lam, &sc, b, b, w, order, w.dinv, wt));
+    return rotate(Yin, w.W, Qout);
+  }
+
+  // ---- set-up and start block ------------------------------------------------------------------
+  // p: the workspace behind EigWork (the block-sparse products carve theirs from it)
+  int setup(char *p) {
+    if (s >= std::max(1024, P.bs_min_s) && s <= 65536 && P.blocksparse) {   // (65536: bsg_lists_kernel keeps one int per 64-anchor tile in LDS)
+      bsg_carve(bs, p, s, b);
+      if (g_ctx && g_ctx->pinned) bsg_host_slots(bs, g_ctx->pinned, (char *)g_ctx->pinned + HOST_SMALL_BYTES, HOST_BIG_BYTES);
+      FLGP_TRY(bsg_setup(st, dG, ldg, s, bs, g_ctx ? g_ctx->side : nullptr, g_ctx ? g_ctx->side_ev : nullptr));
+    }
+    use_rot = rot_applicable(s, b, w.Q, w.Y, w.W, w.Yp, w.Z) && rot_applicable(s, b, w.Qold, nullptr, w.T, w.Z, nullptr);
+    wt = use_rot ? 1 : 0;
+    const bool host_slots = g_ctx && g_ctx->pinned && g_ctx->pinned_dev && P.host_slots;
+    const size_t dist_off = BSG_HOST_SLOT_BYTES + sizeof(double) * APRIORI_SLOT_DOUBLES;
+    const size_t rt_off = dist_off + sizeof(double) * DIST_SLOT_DOUBLES;
+    if (host_slots) {
+      dist_h = (double *)((char *)g_ctx->pinned + dist_off);
+      dist_d = (double *)((char *)g_ctx->pinned_dev + dist_off);
+      if (2 * b <= RT_SLOT_DOUBLES) {
+        rt_h = (double *)((char *)g_ctx->pinned + rt_off);
+        rt_d = (double *)((char *)g_ctx->pinned_dev + rt_off);
+      }
+    }
+    static_assert(2 * APRIORI_BLOCKS <= APRIORI_SLOT_DOUBLES, "the pinned slot of the a-priori bounds");
+    if (g_ctx && g_ctx->pinned) h_apriori = (double *)((char *)g_ctx->pinned + BSG_HOST_SLOT_BYTES);
+    side_st = g_ctx ? g_ctx->side : nullptr;
+    side_ev = g_ctx ? g_ctx->side_ev : nullptr;
+    hipLaunchKernelGGL(set_identity_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.Id, b);
+    return check_launch("set_identity_kernel");
+  }
+
+  // Start block: uniform random columns, orthonormalised once.  Iteration 0 forms no Rayleigh-Ritz matrix: Rayleigh-Ritz on
+  // a random block yields nothing but poor bounds (every Ritz value of a random subspace sits near the mean eigenvalue), and
+  // the span p(G) Q does not depend on the basis.  So the first filter runs straight on the start block with a-priori
+  // bounds -- damped interval [0, trace / s], scaled at the 1-norm -- and the first Rayleigh-Ritz step (two Jacobi sweeps,
+  // two rotations, a host round trip) is saved.  (Not orthonormalising the start block at all was measured no faster: the
+  // 0.33 ms it saves sat in the shadow of the set-up's host round trips.)
+  int start_block() {
+    Q = w.Q; F[0] = w.Y; F[1] = w.Yp; F[2] = w.Z;
+    hipLaunchKernelGGL(eig_init_q_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, st, F[0], s, b, s,
+                       (unsigned long long)P.start_stream);
+    FLGP_TRY(check_launch("eig_init_q_kernel"));
+    if (!bs.built) {
+      hipLaunchKernelGGL(apriori_bounds_kernel, dim3(APRIORI_BLOCKS), dim3(256), 0, st, dG, ldg, s, w.apriori);
+      FLGP_TRY(check_launch("apriori_bounds_kernel"));
+      FLGP_HIP(hipMemcpyAsync(h_apriori, w.apriori, sizeof(double) * 2 * APRIORI_BLOCKS, hipMemcpyDeviceToHost, st));
+    }
+    FLGP_TRY(orth(F[0], Q, &cond));
+    FLGP_HIP(stream_wait(st));   // the set-up's bookkeeping (and the a-priori bounds) have arrived on the host
+    bsg_finish(bs);
+    lambda_lo = bs.built ? bs.lambda_lo : 0.0;
+    return FLGP_OK;
+  }
+
+  // ---- filter ----------------------------------------------------------------------------------
+  // iteration 0: the filter on a-priori bounds (h_apriori, or the block-sparse set-up's pass over G): damped interval
+  // [0, trace / s], scaled at the 1-norm
+  int apriori_filter(FilterPlan *fp) const {
+    double n1 = 0.0, tr = 0.0;
+    if (bs.built) { n1 = bs.h_bounds[0]; tr = bs.h_bounds[1]; }
+    else for (int q = 0; q < APRIORI_BLOCKS; ++q) { n1 = std::max(n1, h_apriori[q]); tr += h_apriori[APRIORI_BLOCKS + q]; }
+    double cut0 = tr / (double)s;
+    if (!(n1 > 0.0) || !std::isfinite(n1)) { set_error("eigensolver: the matrix is zero or not finite"); return FLGP_ERR_INVALID; }
+    if (!(cut0 > 1e-3 * n1)) cut0 = 1e-3 * n1;
+    if (cut0 > 0.5 * n1) cut0 = 0.5 * n1;
+    fp->c = fp->e = 0.5 * cut0;
+    fp->sigma1 = fp->e / (n1 - fp->c);
+    fp->m = std::max(2, P.m0);
+    return FLGP_OK;
+  }
+
+  // later iterations: the filter on [lo, cut] from the Ritz values, scaled to 1 at the top one
+  FilterPlan plan_filter(double top) {
+    const int cut_pos = K + (b - K) * P.cut_pct / 100;
+    double cut = theta[std::min(b - 1, std::max(K, cut_pos - 1))];
+    if (!(cut > 0.0)) cut = 1e-3 * top;
+    if (cut > 0.999 * top) cut = 0.999 * top;   // degenerate block: keep a valid interval
+    FilterPlan fp;
+    // damped interval [lo, cut]: lo = 0 (G is PSD) unless the set-up's Lanczos run vouches for more -- at BASELINE
+    // configs[2] lambda_min = 0.113 and cut = 0.39: the interval shrinks by a quarter, the filter's growth per degree at the
+    // K-th eigenvalue rises from 1.38 to 1.46, 17 % fewer products
+    const double lo = (lambda_lo > 0.0 && lambda_lo < 0.5 * cut) ? lambda_lo : 0.0;
+    fp.e = 0.5 * (cut - lo); fp.c = 0.5 * (cut + lo);
+    const double g1 = (top - fp.c) / fp.e;      // >= 1
+    // degree: amplification T_m(g1) of the top direction capped per outer iteration
+    // (gentler while the block is still far from the invariant subspace)
+    const double amp = std::pow(10.0, (double)((it < 2) ? P.amp_exp_early : P.amp_exp));
+    int m = (int)std::floor(std::acosh(amp) / std::acosh(std::max(g1, 1.0 + 1e-12)));
+    const int m_cap = 40;
+    fp.m = std::max(2, std::min(m, m_cap));
+    // Landing.  A filter of degree m contracts the residual of the K-th pair -- the slowest -- by 1 / T_m(g_K) ~ 2 exp(-m a),
+    // a = acosh(g_K), g_K the K-th Ritz value on the filter's own scale (measured at configs[2]: 0.0526 per iteration
+    // against 1 / T_8(1.1055) = 0.0526).  With the last measured residual that gives the iterations still needed at the
+    // capped degree, n0.  If a few degrees more per iteration save a whole iteration (orthonormalisation, Rayleigh-Ritz
+    // and its wait: ~1 ms) they are spent; if n0 iterations overshoot, the degree is lowered to what the tolerance needs.
+    // Without this the iteration on which the residual test is first met moves by one with perturbations of rounding
+    // size (DESIGN section 4: 10 or 11 iterations at configs[2], depending on the start block).
+    if (it >= 3 && rmax_prev > 0.0 && rmax_prev < 1e-8 * (double)P.landing_below_e8) {
+      const double gK = (theta[K - 1] - fp.c) / fp.e;
+      if (gK > 1.0 + 1e-9) {
+        const double a = std::acosh(gK), ln2 = 0.6931471805599453;
+        const double target = tol * 0.01 * (double)P.landing_margin_pct;
+        const double L = std::log(rmax_prev / target);
+        const double per0 = fp.m * a - ln2;
+        if (L > 0.0 && per0 > 0.0) {
+          const int n0 = std::max(1, (int)std::ceil(L / per0));
+          auto degree_for = [&](int n) { return (int)std::ceil((L / n + ln2) / a); };
+          int mm = degree_for(n0);                                  // <= fp.m by construction of n0
+          // (one iteration fewer at most, and three degrees more at most: with five or eight more per iteration the block
+          //  loses accuracy faster than the filter gains -- 14 and 15 iterations instead of 10)
+          if (n0 >= 2 && degree_for(n0 - 1) <= fp.m + P.landing_boost) mm = degree_for(n0 - 1);
+          fp.m = std::max(2, std::min(mm, m_cap));
+          rate = std::min(0.5, std::max(1e-4, 2.0 * std::exp(-fp.m * a)));
+        }
+      }
+    }
+    fp.sigma1 = fp.e / (top - fp.c);
+    if (P.verbose) fprintf(stderr, "[flgp eig]   filter it=%d: top %.4f, cut %.4f, lo %.3f, degree %d\n", it, top, cut, lo, fp.m);
+    return fp;
+  }
+
+  // p(G) A given B = G A; A, f1, f2 are overwritten (B is not); returns the buffer with the result and
+  // one buffer that is free afterwards
+  int apply_filter(const FilterPlan &fp, double *A, const double *B, double *f1, double *f2, double **cur_out,
+                              double **spare_out) {
+    double sigma = fp.sigma1;
+    if (bs.on) {
+      // the recurrence on transposed blocks; A and B are left alone, the result lands in f1
+      if (!(t_q == A && t_z == B)) {
+        FLGP_TRY(to_t(A, bs.T[0]));
+        FLGP_TRY(to_t(B, bs.T[1]));
+      }
+      t_q = nullptr; t_z = nullptr;
+      double *prev = bs.T[0], *cur = bs.T[2], *next = bs.T[1];
+      hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, st, fp.sigma1 / fp.e, bs.T[1],
+                         -fp.sigma1 * fp.c / fp.e, bs.T[0], cur, tot);
+      FLGP_TRY(check_launch("eig_axpby_kernel"));
+      for (int deg = 2; deg <= fp.m; ++deg) {   // out_t = alpha X_t G' + beta E_t + gamma E2_t   (b x s)
+        const double sn = 1.0 / (2.0 / fp.sigma1 - sigma);
+        FLGP_TRY(bsg_product(st, bs, cur, b, 2.0 * sn / fp.e, -2.0 * sn * fp.c / fp.e, cur, -sigma * sn, prev, next));
+        ++gprods;
+        double *t3 = prev; prev = cur; cur = next; next = t3;
+        sigma = sn;
+      }
+      FLGP_TRY(from_t(cur, f1));
+      *cur_out = f1;
+      *spare_out = f2;
+      return FLGP_OK;
+    }
+    // degree 1: Y = (sigma1/e) (G A - c A) = (sigma1/e) (B - c A), into a free buffer
+    double *prev = A, *cur = f1, *next = f2;
+    hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, st, fp.sigma1 / fp.e, B,
+                       -fp.sigma1 * fp.c / fp.e, A, cur, tot);
+    FLGP_TRY(check_launch("eig_axpby_kernel"));
+    for (int deg = 2; deg <= fp.m; ++deg) {
+      const double sn = 1.0 / (2.0 / fp.sigma1 - sigma);
+      // next = (2 sn / e) (G cur - c cur) - sigma sn prev
+      FLGP_TRY(gemmG(cur, 2.0 * sn / fp.e, -2.0 * sn * fp.c / fp.e, cur, -sigma * sn, prev, next));
+      ++gprods;
+      double *t3 = prev; prev = cur; cur = next; next = t3;
+      sigma = sn;
+    }
+    *cur_out = cur;
+    *spare_out = prev;
+    return FLGP_OK;
+  }
+
+  // De-contaminate: a filtered column y_j = p(G) q_j carries its error components along the higher Ritz directions amplified
+  // by p(th_i)/p(th_j) (up to `amp`).  One Gram-Schmidt pass against the OLD Ritz vectors (w.Qold) in sorted order removes
+  // exactly those:
+  //     y_j <- y_j - sum_{i<j} q_i (q_i . y_j)
+  // (two GEMMs).  What is left is nearly orthogonal, so the symmetric orthonormalisation no longer mixes eigen-directions
+  // and the next T stays diagonal up to the guard block.
+  int decontaminate(double *cur) {
+    if (use_rot) {
+      // T^T = cur^T Qold, strictly lower: the same sums (products commute), laid out k-major as rot.hip reads W
+      GemmFusedReduce fr{8, nullptr, nullptr, w.red, w.redcnt, false};
+      FLGP_TRY(gram_small(cur, w.Qold, w.T, &fr));
+      if (!fr.done) {
+        hipLaunchKernelGGL(mask_strict_upper_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, 1);
+        FLGP_TRY(check_launch("mask_strict_upper_kernel"));
+      }
+      return rot_launch(st, s, b, -1.0, w.Qold, nullptr, w.T, 1.0, cur, nullptr, cur, nullptr);
+    }
+    GemmFusedReduce fr{2, nullptr, nullptr, w.red, w.redcnt, false};   // the strict upper triangle, by the reduction kernel
+    FLGP_TRY(gram_small(w.Qold, cur, w.T, &fr));
+    if (!fr.done) {
+      hipLaunchKernelGGL(mask_strict_upper_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b);
+      FLGP_TRY(check_launch("mask_strict_upper_kernel"));
+    }
+    return gemm_launch(st, s, b, b, -1.0, w.Qold, 1, s, w.T, 1, b, 1.0, cur, 1, s, cur, 1, s, w.gemm_ws, w.gemm_ws_elems,
+                       0.0, nullptr, w.tickets);
+  }
+
+  // ---- Rayleigh-Ritz and convergence -------------------------------------------------------------
+  // Jacobi sweeps of a late Rayleigh-Ritz step (jacobi_refine): more while the residual is large, and at least two after a
+  // strong filter, which leaves T further from diagonal than the residual says (measured: one sweep after degree 24
+  // un-converged the cluster pairs)
+  int refine_sweeps() const {
+    int nsw = std::max(1, (rmax_prev > 1e-4 * P.refine3_above_e4 ? 3 : (rmax_prev > 1e-8 * P.refine2_above_e8 ? 2 : 1)) - P.refine_minus);
+    if (last_m >= P.sweeps2_from_m) nsw = std::max(nsw, 2);
+    return nsw;
+  }
+
+  // residuals of the K wanted pairs (A = Ritz vectors, B = G A) with the Ritz values sorted_basis_dev left in w.theta;
+  // the ONE host round trip of a Rayleigh-Ritz step: brings the residuals and the sorted Ritz values over together
+  int residuals(const double *A, const double *B, double *rmax_out) {
+    hipLaunchKernelGGL(resid_kernel, dim3(K), dim3(256), 0, st, B, A, s, s, w.theta, w.res, rt_d, b, 1);
+    FLGP_TRY(check_launch("resid_kernel"));
+    const double *rtp = rt_h;
+    if (!rt_d) { FLGP_HIP(hipMemcpyAsync(rt.data(), w.res, sizeof(double) * 2 * b, hipMemcpyDeviceToHost, st)); rtp = rt.data(); }
+    FLGP_HIP(stream_wait(st));
+    double rmax = 0.0;
+    for (int j = 0; j < K; ++j) { res[j] = rtp[j]; rmax = std::max(rmax, res[j]); }
+    for (int j = 0; j < b; ++j) theta[j] = rtp[b + j];
+    *rmax_out = rmax;
+    return FLGP_OK;
+  }
+
+  // book-keeping after a Rayleigh-Ritz step, shared by both orders; true: converged
+  bool after_rr(double rmax, double top, bool overlapped) {
+    // the watch on the Lanczos bound: a direction below `lambda_lo` that the filter amplified instead of damping shows
+    // up as a Ritz value far below the guard block's (which sit just under the K-th); then the bound goes
+    if (lambda_lo > 0.0 && theta[b - 1] < lambda_lo + 0.5 * (theta[K - 1] - lambda_lo)) {
+      if (P.verbose) fprintf(stderr, "[flgp eig] smallest Ritz value %.4g: the lower bound %.4g is dropped\n", theta[b - 1], lambda_lo);
+      lambda_lo = 0.0;
+    }
+    if (P.verbose) {
+      int npre = 0, nconv = 0;
+      while (npre < K && res[npre] <= tol * top) ++npre;
+      for (int j = 0; j < K; ++j) nconv += res[j] <= tol * top;
+      fprintf(stderr, "[flgp eig] it=%d gprods=%d theta0=%.15g thetaK=%.6g cut=%.6g rmax=%.3e cond=%.2e sweeps=%d conv=%d prefix=%d%s\n",
+              it, gprods, theta[0], theta[K - 1], theta[b - 1], rmax, cond, sweeps, nconv, npre, overlapped ? " (overlapped)" : "");
+      if (P.verbose > 2) {
+        int shown = 0;
+        for (int j = 0; j < K && shown < 8; ++j) if (res[j] > tol * top) { fprintf(stderr, "    pair %d theta %.9f res %.2e\n", j, theta[j], res[j]); ++shown; }
+      }
+    }
+    if (rmax <= tol * top) return true;
+    if (it >= 3 && rmax_meas > 0.0 && rmax / top < rmax_meas) {
+      const double r = std::pow((rmax / top) / rmax_meas, 1.0 / (double)(it - it_meas));
+      rate = std::min(0.5, std::max(0.02, r));
+    }
+    rmax_meas = rmax / top; it_meas = it;
+    rmax_prev = rmax / top;
+    return false;
+  }
+
+  // ---- one outer iteration ---------------------------------------------------------------------
+  //   Z = G Q;  [Rayleigh-Ritz: A = Q W (Ritz vectors), B = Z W, residuals -> stop?];  Y = p(G) A;
+  //   de-contaminate Y against the old Ritz vectors;  Q = orth(Y)
+  // Rayleigh-Ritz is skipped on iteration 0 (a-priori bounds) and on some late iterations (rr_every > 1); late ones may
+  // overlap the filter (rr_overlapped below).
+  int iteration(bool *converged) {
+    double *Z = F[0];
+    double *A, *B, *free1, *free2;     // Ritz vectors, G * Ritz vectors, two free s x b buffers
+    double *cur = nullptr, *spare = nullptr;   // filtered block; a buffer that is free after the filter
+    FLGP_TRY(apply_g(Q, Z));
+    // Rayleigh-Ritz may be skipped on some late iterations (rr_every > 1): the block is then used as it
+    // is (its columns are the previous Ritz vectors, filtered, cleaned and orthonormalised: still ordered
+    // and nearly Ritz), bounds are reused, and no convergence test is made on that iteration
+    // (rmax_prev is then advanced by the measured per-iteration contraction `rate`, so that the Rayleigh-
+    //  Ritz step and its convergence test land on the iteration where the tolerance is expected to be met)
+    const bool near_done = rmax_prev * rate <= 4.0 * tol;
+    const bool do_rr = it > 0 && !(P.rr_every > 1 && it >= 3 && rmax_prev < 1e-6 * P.rr_skip_below_e6 && since_rr + 1 < P.rr_every && !near_done);
+    // Late Rayleigh-Ritz steps only refine a nearly diagonal T: the filter does not wait for them.  It is
+    // linear, p(G) (Q W) = (p(G) Q) W, so it runs on the block as it is, with the bounds of the previous
+    // step (once the residuals are below 1e-3 they move in the third digit: measured, earlier steps lose
+    // more to the stale interval than they gain), while the refinement runs on the second stream; the
+    // rotation W is applied to the filtered block afterwards.  Not on the step that is expected to
+    // converge: there the filter's products would be thrown away.
+    const bool overlap = side_st && side_ev && do_rr && it >= P.overlap_from_it && !near_done &&
+                         rmax_prev <= 1e-6 * (double)P.overlap_below_e6;
+    double rmax = 0.0, top = std::max(theta[0], 1e-300);
+    if (overlap) {
+      since_rr = 0;
+      FLGP_TRY(gram_small(Q, Z, w.T));
+      FLGP_HIP(hipEventRecord(side_ev, st));
+      // the other stream first (round 4: it used to be enqueued BEHIND the filter's launches, and the host needs ~0.4 ms to
+      // enqueue a filter of degree 24 -- the refinement, which is the longer of the two, started that much late): T = W Th W^T
+      FLGP_HIP(hipStreamWaitEvent(side_st, side_ev, 0));
+      const int nsw = refine_sweeps();
+      FLGP_TRY(jacobi_refine(side_st, w.T, b, K, w, P, lam, &sweeps, nsw, false));
+      sweeps = nsw;
+      FLGP_TRY(sorted_basis_dev(side_st, b, w, wt));   // order and W on the device: the host is not asked
+      FLGP_HIP(hipEventRecord(side_ev, side_st));
+      FLGP_HIP(hipMemcpyAsync(w.Qold, Q, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
+      const FilterPlan fp = plan_filter(top);
+      FLGP_TRY(apply_filter(fp, Q, Z, F[1], F[2], &cur, &spare));
+      FLGP_HIP(hipStreamWaitEvent(st, side_ev, 0));
+      double *const trio[3] = {Q, F[1], F[2]};
+      double *ab[2];
+      others(trio, 3, cur, ab);                  // the two buffers that do not hold the filtered block
+      A = ab[0]; B = ab[1];
+      FLGP_TRY(rotate2(w.Qold, Z, w.W, A, B));   // A = Ritz vectors, B = G * Ritz vectors
+      FLGP_TRY(residuals(A, B, &rmax));
+      top = std::max(theta[0], 1e-300);
+      if (after_rr(rmax, top, true)) { *converged = true; result = A; return FLGP_OK; }
+      last_m = fp.m;
+      FLGP_TRY(rotate(cur, w.W, Z));      // the filtered block in the new Ritz order (Z is free by now)
+      FLGP_HIP(hipMemcpyAsync(w.Qold, A, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
+      free1 = cur; free2 = Z;
+      spare = cur;
+      cur = Z;
+    } else {
+      if (do_rr) {
+        since_rr = 0;
+        A = F[1]; B = F[2]; free1 = Q; free2 = Z;
+        // ---- Rayleigh-Ritz on span(Q): Z = G Q, T = Q^T Z, T = W Th W^T
+        FLGP_TRY(gram_small(Q, Z, w.T));
+        // T is far from diagonal only while the block is far from invariant: full Jacobi for the first
+        // iterations, afterwards a single sweep refines the (already nearly diagonal) Ritz basis
+        // (a fixed small number of global sweeps alone is NOT enough, even late: the guard columns
+        //  never converge, so their diagonal block of T stays dense -- measured: 2 sweeps put rmax
+        //  back to 4e-2.  jacobi_refine diagonalises that block first.)
+        if (it == 1) {      // bounds and a rough Ritz basis are all that is needed yet: loose threshold, capped sweeps
+          sweeps = P.sweeps_it1;
+          FLGP_TRY(jacobi_eig(st, w.T, b, b, w, P, lam, nullptr, sweeps, 1e10, false, false));
+        } else if (rmax_prev > 5e-2) {
+          sweeps = P.sweeps_it2;
+          FLGP_TRY(jacobi_eig(st, w.T, b, b, w, P, lam, nullptr, sweeps, 1e6, false, false));
+        } else {
+          sweeps = refine_sweeps();
+          FLGP_TRY(jacobi_refine(st, w.T, b, K, w, P, lam, nullptr, sweeps, false));
+        }
+        FLGP_TRY(sorted_basis_dev(st, b, w, wt));
+        FLGP_TRY(rotate2(Q, Z, w.W, A, B));   // A = Ritz vectors, B = G * Ritz vectors
+        FLGP_TRY(residuals(A, B, &rmax));
+        top = std::max(theta[0], 1e-300);
+        if (after_rr(rmax, top, false)) { *converged = true; result = A; return FLGP_OK; }
+      } else {
+        ++since_rr;
+        A = Q; B = Z; free1 = F[1]; free2 = F[2];
+        if (it > 0) rmax_prev *= rate;
+      }
+      FilterPlan fp;
+      if (it == 0) FLGP_TRY(apriori_filter(&fp));   // (the start orthonormalisation has synchronised the stream: h_apriori is valid)
+      else fp = plan_filter(top);
+      // the Ritz vectors are needed again after the filter (decontaminate): keep a copy
+      FLGP_HIP(hipMemcpyAsync(w.Qold, A, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
+      FLGP_TRY(apply_filter(fp, A, B, free1, free2, &cur, &spare));
+      if (it > 0) last_m = fp.m;
+    }
+    // (not after the a-priori filter of iteration 0: the start block is no Ritz basis, and projecting along its columns
+    //  would take the block out of span p(G) Q)
+    if (it > 0) FLGP_TRY(decontaminate(cur));
+    // ---- orthonormalise the filtered block (B is free by now; twice if ill-conditioned)
+    FLGP_TRY(orth(cur, B, &cond));
+    double *R = B;
+    if (cond > 1e8) {
+      FLGP_TRY(orth(B, spare, &cond));
+      R = spare;
+    }
+    double *const pool[4] = {A, B, free1, free2};
+    others(pool, 4, R, F);
+    Q = R;
+    return FLGP_OK;
+  }
+
+  // ---- finish --------------------------------------------------------------------------------------
+  int finish(bool converged, void *stream, double *d_values, double *dV, int ldv, int *info) {
+    if (info) { info[0] = it; info[1] = gprods; info[2] = 0; info[3] = ns_orths * 1000 + jac_orths; }
+    if (!converged) {
+      // A spectrum the filter cannot split -- e.g. r = 1, where G is the identity up to the 1e-9 guards and the wanted
+      // and unwanted eigenvalues coincide -- never meets the residual test.  While the full decomposition is affordable
+      // (s <= 8192) it is taken instead, with its own workspace: any orthonormal basis of a degenerate eigenspace is a
+      // valid answer, and the Jacobi route always delivers one.
+      if (s <= 8192) {
+        DevBuf fw, fvals, fV;
+        const size_t fb = eig_workspace_bytes(s, s, P);
+        FLGP_TRY(fw.alloc(fb));
+        FLGP_TRY(fvals.alloc(sizeof(double) * (size_t)s));
+        FLGP_TRY(fV.alloc(sizeof(double) * (size_t)s * s));
+        if (P.verbose) fprintf(stderr, "[flgp eig] no convergence after %d outer iterations: full decomposition instead\n", it);
+        FLGP_TRY(flgp_dev_eig_topk(stream, dG, ldg, s, s, tol, fvals.as<double>(), fV.as<double>(), s, fw.p, fb, nullptr));
+        FLGP_HIP(hipMemcpyAsync(d_values, fvals.p, sizeof(double) * K, hipMemcpyDeviceToDevice, st));
+        FLGP_HIP(hipMemcpy2DAsync(dV, sizeof(double) * (size_t)ldv, fV.p, sizeof(double) * (size_t)s, sizeof(double) * (size_t)s, K,
+                                  hipMemcpyDeviceToDevice, st));
+        FLGP_HIP(stream_wait(st));
+        if (info) info[2] = 1;
+        return FLGP_OK;
+      }
+      set_error("eigensolver: %d of the residuals still above %.1e after %d outer iterations", K, tol, it);
+      return FLGP_ERR_NOCONV;
+    }
+    if (rt_h) {       // (through the pinned slot: an upload from pageable memory is staged by the runtime first)
+      memcpy(rt_h, theta.data(), sizeof(double) * K);
+      FLGP_HIP(hipMemcpyAsync(d_values, rt_h, sizeof(double) * K, hipMemcpyHostToDevice, st));
+    } else {
+      FLGP_HIP(hipMemcpyAsync(d_values, theta.data(), sizeof(double) * K, hipMemcpyHostToDevice, st));
+    }
+    if (bs.on) {   // the solver worked on P G P^T: rows back to the caller's anchor order
+      hipLaunchKernelGGL(bs_unpermute_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, result, s, K, bs.perm, dV, ldv);
+      FLGP_TRY(check_launch("bs_unpermute_kernel"));
+    } else {
+      FLGP_HIP(hipMemcpy2DAsync(dV, sizeof(double) * ldv, result, sizeof(double) * s, sizeof(double) * s, K,
+                                hipMemcpyDeviceToDevice, st));
+    }
+    FLGP_HIP(stream_wait(st));
+    return FLGP_OK;
+  }
+};
+
 }  // namespace flgp
 
 using namespace flgp;
 
 extern "C" size_t flgp_dev_eig_workspace(int s, int K) {
   if (K < 0 || K > s) K = s;
-  return eig_workspace_bytes(s, K);
+  return eig_workspace_bytes(s, K, eig_params());
 }
 
 static int eig_topk_impl(void *stream, const double *dG, int ldg, int s, int K, double tol, double *d_values, double *dV,
@@ -1387,12 +2187,14 @@ extern "C" int flgp_dev_eig_topk(void *stream, const double *dG, int ldg, int s,
 static int eig_topk_impl(void *stream, const double *dG, int ldg, int s, int K, double tol, double *d_values, double *dV,
                          int ldv, void *d_work, size_t work_bytes, int *info) {
   hipStream_t st = (hipStream_t)stream;
+  const EigParams P = eig_params();
+  if (g_ctx) { g_ctx->spin_us = P.spin_us; g_ctx->spin_wait = P.spin_wait != 0; }
   if (K < 0) K = s;
   FLGP_REQUIRE(K >= 1 && K <= s, "eig: need 1 <= K <= s (K=%d, s=%d)", K, s);
-  FLGP_REQUIRE(work_bytes >= eig_workspace_bytes(s, K), "eig: workspace too small");
+  FLGP_REQUIRE(work_bytes >= eig_workspace_bytes(s, K, P), "eig: workspace too small");
   if (tol <= 0.0) tol = 5e-11;   // relative residual of every wanted pair (Spectra's own tolerance is 1e-10)
-  const bool dense = eig_use_dense(s, K);
-  const int b = dense ? s : eig_block_size(s, K);
+  const bool dense = eig_use_dense(s, K, P);
+  const int b = dense ? s : eig_block_size(s, K, P);
   FLGP_REQUIRE(!dense || s <= 16384, "eig: the full decomposition (K == s, or K close to s) is built for s <= 16384");
 
   // carve the workspace
@@ -1422,22 +2224,14 @@ static int eig_topk_impl(void *stream, const double *dG, int ldg, int s, int K, 
     w.redcnt = (int *)(w.red + nt2);
     FLGP_HIP(hipMemsetAsync(w.redcnt, 0, sizeof(int), st));
   }
-  BsG bs;
-  if (!dense && s >= std::max(1024, tuning("eig_bs_min_s", 1536)) && s <= 65536 && tuning("eig_blocksparse", 1)) {   // (65536: bsg_lists_kernel keeps one int per 64-anchor tile in LDS)
-    bsg_carve(bs, p, s, b);
-    if (g_ctx && g_ctx->pinned && tuning("eig_pinned_slots", 1))
-      bsg_host_slots(bs, g_ctx->pinned, (char *)g_ctx->pinned + HOST_SMALL_BYTES, HOST_BIG_BYTES);
-    FLGP_TRY(bsg_setup(st, dG, ldg, s, bs, g_ctx ? g_ctx->side : nullptr, g_ctx ? g_ctx->side_ev : nullptr));
-  }
-
-  std::vector<double> lam;
-  std::vector<int> order;
-  int sweeps = 0;
   if (info) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
 
   if (dense) {
     // full symmetric eigendecomposition of G itself (the K == s branch, src/TruncatedSVD.cpp:17-20)
-    FLGP_TRY(jacobi_eig(st, dG, ldg, s, w, lam, &sweeps, -1, 1.0, true));
+    std::vector<double> lam;
+    std::vector<int> order;
+    int sweeps = 0;
+    FLGP_TRY(jacobi_eig(st, dG, ldg, s, w, P, lam, &sweeps, -1, 1.0, true));
     FLGP_TRY(sorted_basis(st, lam, nullptr, s, K, w, order));
     std::vector<double> vals(K);
     for (int j = 0; j < K; ++j) vals[j] = lam[order[j]];
@@ -1449,764 +2243,16 @@ static int eig_topk_impl(void *stream, const double *dG, int ldg, int s, int K, 
     return FLGP_OK;
   }
 
-  const long tot = (long)s * b;
-  auto gemmG = [&](const double *Xin, double alpha, double beta, const double *E, double gamma, const double *E2,
-                   double *out) {  // out = alpha G Xin + beta E + gamma E2   (s x b)
-    return gemm_launch(st, s, b, s, alpha, dG, 1, ldg, Xin, 1, s, beta, E, 1, s, out, 1, s, w.gemm_ws,
-                       w.gemm_ws_elems, gamma, E2, w.tickets);
-  };
-  // ---- block-sparse products (bs.on): blocks live transposed (b x s, the b values of one row contiguous) while
-  //      the filter runs, so that both the tiled GEMM (over the listed k stages of P G P^T) and the CSR remainder
-  //      read and write whole 8b-byte rows
-  auto to_t = [&](const double *in, double *out_t) {     // s x b  ->  b x s
-    hipLaunchKernelGGL(bs_transpose_kernel, dim3(ceil_div(s, 32), ceil_div(b, 32)), dim3(256), 0, st, in, s, b, out_t);
-    return check_launch("bs_transpose_kernel");
-  };
-  auto from_t = [&](const double *in_t, double *out) {   // b x s  ->  s x b
-    hipLaunchKernelGGL(bs_transpose_kernel, dim3(ceil_div(b, 32), ceil_div(s, 32)), dim3(256), 0, st, in_t, b, s, out);
-    return check_launch("bs_transpose_kernel");
-  };
-  auto gemmG_t = [&](const double *Xt, double alpha, double beta, const double *Et, double gamma, const double *E2t,
-                     double *out_t) -> int {   // out_t = alpha X_t G' + beta E_t + gamma E2_t   (b x s)
-    return bsg_product(st, bs, Xt, b, alpha, beta, Et, gamma, E2t, out_t);
-  };
-  const double *t_q = nullptr, *t_z = nullptr;   // blocks whose transposes currently sit in bs.T[0], bs.T[1]
-  auto gram_small = [&](const double *Xa, const double *Xb, double *out, GemmFusedReduce *fr = nullptr) {  // out = Xa^T Xb   (b x b)
-    if (gramk_applicable(s, b, Xa, Xb, w.gemm_ws_elems)) return gramk_launch(st, s, b, Xa, Xb, out, w.gemm_ws, w.gemm_ws_elems, fr);
-    return gemm_launch(st, b, b, s, 1.0, Xa, s, 1, Xb, 1, s, 0.0, nullptr, 0, 0, out, 1, b, w.gemm_ws,
-                       w.gemm_ws_elems, 0.0, nullptr, w.tickets, fr);
-  };
-  const bool fuse_reduce = tuning("eig_fused_reduce", 1) != 0;   // the small-matrix kernels behind a Gram product inside its reduction
-  // The rotations run on their own kernel (rot.hip) where the shape allows; W is then kept k-major (`wt` = 1 tells its producers)
-  const bool use_rot = rot_applicable(s, b, w.Q, w.Y, w.W, w.Yp, w.Z) && rot_applicable(s, b, w.Qold, nullptr, w.T, w.Z, nullptr);
-  const int wt = use_rot ? 1 : 0;
-  auto rotate = [&](const double *Xin, const double *Wm, double *out) {  // out = Xin Wm   (s x b)(b x b)
-    if (use_rot) return rot_launch(st, s, b, 1.0, Xin, nullptr, Wm, 0.0, nullptr, nullptr, out, nullptr);
-    return gemm_launch(st, s, b, b, 1.0, Xin, 1, s, Wm, 1, b, 0.0, nullptr, 0, 0, out, 1, s, w.gemm_ws,
-                       w.gemm_ws_elems, 0.0, nullptr, w.tickets);
-  };
-  // two rotations by the same W in one launch (the Ritz vectors and G times them)
-  const bool pair_rot = tuning("eig_pair_rotate", 1) != 0;
-  auto rotate2 = [&](const double *X1, const double *X2, const double *Wm, double *out1, double *out2) -> int {
-    if (!pair_rot) { FLGP_TRY(rotate(X1, Wm, out1)); return rotate(X2, Wm, out2); }
-    if (use_rot) return rot_launch(st, s, b, 1.0, X1, X2, Wm, 0.0, nullptr, nullptr, out1, out2);
-    const GemmPair pr{X2, Wm, out2};
-    return gemm_launch(st, s, b, b, 1.0, X1, 1, s, Wm, 1, b, 0.0, nullptr, 0, 0, out1, 1, s, w.gemm_ws, w.gemm_ws_elems, 0.0,
-                       nullptr, nullptr, nullptr, &pr);
-  };
-  // orthonormalise the columns of Yin into Qout ("SVQB" on the column-normalised block, so that
-  // the widely different column norms a Chebyshev filter leaves behind do not enter the
-  // conditioning of the Gram matrix); returns the condition estimate of the scaled Gram matrix
-  const bool tiny_ok = b % 16 == 0 && tuning("eig_small_gemm", 1);
-  auto small_gemm = [&](const double *Am, const double *Bm, double alpha, double beta, const double *E,
-                        double *out) -> int {  // out = alpha Am Bm + beta E   (b x b, column-major)
-    if (tiny_ok) {
-      SmallGemmPair pr;
-      pr.g[0] = SmallGemm{Am, Bm, E, out, alpha, beta};
-      pr.g[1] = pr.g[0];
-      ProfScope ps("small_gemm_kernel", st, 2.0 * (double)b * b * b);
-      hipLaunchKernelGGL(small_gemm_kernel, dim3(b / 16, b / 16, 1), dim3(64), 0, st, pr, b);
-      return check_launch("small_gemm_kernel");
-    }
-    return gemm_launch(st, b, b, b, alpha, Am, 1, b, Bm, 1, b, beta, E, 1, b, out, 1, b, w.gemm_ws, w.gemm_ws_elems,
-                       0.0, nullptr);
-  };
-  // two independent products in one launch: out0 = A0 B0, out1 = A1 B1
-  auto small_gemm2 = [&](const double *A0, const double *B0, double *out0, const double *A1, const double *B1,
-                         double *out1) -> int {
-    if (tiny_ok) {
-      SmallGemmPair pr;
-      pr.g[0] = SmallGemm{A0, B0, nullptr, out0, 1.0, 0.0};
-      pr.g[1] = SmallGemm{A1, B1, nullptr, out1, 1.0, 0.0};
-      ProfScope ps("small_gemm_kernel", st, 4.0 * (double)b * b * b);
-      hipLaunchKernelGGL(small_gemm_kernel, dim3(b / 16, b / 16, 2), dim3(64), 0, st, pr, b);
-      return check_launch("small_gemm_kernel");
-    }
-    FLGP_TRY(small_gemm(A0, B0, 1.0, 0.0, nullptr, out0));
-    return small_gemm(A1, B1, 1.0, 0.0, nullptr, out1);
-  };
-  // host-visible result slots (HostCtx::pinned): [bsg | a-priori bounds | dist partials | residuals + Ritz values]
-  static_assert(DIST_BLOCKS <= DIST_SLOT_DOUBLES, "slot of the distance partials");
-  const bool host_slots = g_ctx && g_ctx->pinned && g_ctx->pinned_dev && tuning("eig_host_slots", 1);
-  const size_t dist_off = BSG_HOST_SLOT_BYTES + sizeof(double) * APRIORI_SLOT_DOUBLES;
-  const size_t rt_off = dist_off + sizeof(double) * DIST_SLOT_DOUBLES;
-  double *dist_h = host_slots ? (double *)((char *)g_ctx->pinned + dist_off) : nullptr;
-  double *dist_d = host_slots ? (double *)((char *)g_ctx->pinned_dev + dist_off) : nullptr;
-  double *rt_h = (host_slots && 2 * b <= RT_SLOT_DOUBLES) ? (double *)((char *)g_ctx->pinned + rt_off) : nullptr;
-  double *rt_d = rt_h ? (double *)((char *)g_ctx->pinned_dev + rt_off) : nullptr;
-  auto dist_to_identity = [&](const double *M, double *out, double diag = 1.0) -> int {
-    double part_own[DIST_BLOCKS];
-    const double *part = part_own;
-    if (dist_d) {
-      hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M, b, dist_d, diag);
-      FLGP_TRY(check_launch("dist_to_identity_kernel"));
-      part = dist_h;
-    } else {
-      hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M, b, w.res, diag);
-      FLGP_TRY(check_launch("dist_to_identity_kernel"));
-      FLGP_HIP(hipMemcpyAsync(part_own, w.res, sizeof(double) * DIST_BLOCKS, hipMemcpyDeviceToHost, st));
-    }
-    FLGP_HIP(stream_wait(st));
-    double sum = 0.0;
-    for (int q = 0; q < DIST_BLOCKS; ++q) sum += part[q];
-    *out = std::sqrt(sum);
-    return FLGP_OK;
-  };
-  // two distances for one question to the host (the second lands in the upper half of the slot)
-  static_assert(2 * DIST_BLOCKS <= DIST_SLOT_DOUBLES, "two sets of distance partials share the slot");
-  auto dist_to_identity2 = [&](const double *M1, const double *M2, double *out1, double *out2) -> int {
-    if (!dist_d) { FLGP_TRY(dist_to_identity(M1, out1)); return dist_to_identity(M2, out2); }
-    hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M1, b, dist_d);
-    hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, M2, b, dist_d + DIST_BLOCKS);
-    FLGP_TRY(check_launch("dist_to_identity_kernel"));
-    FLGP_HIP(stream_wait(st));
-    double s1 = 0.0, s2 = 0.0;
-    for (int q = 0; q < DIST_BLOCKS; ++q) { s1 += dist_h[q]; s2 += dist_h[DIST_BLOCKS + q]; }
-    *out1 = std::sqrt(s1); *out2 = std::sqrt(s2);
-    return FLGP_OK;
-  };
-  hipLaunchKernelGGL(set_identity_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.Id, b);
-  FLGP_TRY(check_launch("set_identity_kernel"));
-  int ns_orths = 0, jac_orths = 0;
-  // the first step of the coupled iteration, where Z = I:  M = beta I + alpha Y (into Zout: it IS the next Z),  Yout = Y M
-  const bool ns_first = tuning("eig_ns_first_step", 1) != 0;
-  auto first_step = [&](const double *Yc_, double alpha, double beta, double *Zout, double *Yout) -> int {
-    hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, alpha, Yc_, beta, w.Id, Zout, (long)b * b);
-    FLGP_TRY(check_launch("eig_axpby_kernel"));
-    return small_gemm(Yc_, Zout, 1.0, 0.0, nullptr, Yout);
-  };
-  static_assert(GEMM_DIST_PARTS == DIST_BLOCKS, "the fused reduction answers in the slots of dist_to_identity_kernel");
-  auto orth = [&](const double *Yin, double *Qout, double *cond_out) -> int {
-    double delta = 0.0;
-    // S = D Y^T Y D and |I - S|_F: inside the reduction kernel of the split product (one launch instead of four)
-    GemmFusedReduce fr{1 | 4, w.dinv, dist_d ? dist_d : w.res, w.red, w.redcnt, false};
-    FLGP_TRY(gram_small(Yin, Yin, w.T, fuse_reduce ? &fr : nullptr));
-    if (fr.done) {
-      double part_own[DIST_BLOCKS];
-      const double *part = dist_d ? dist_h : part_own;
-      if (!dist_d) FLGP_HIP(hipMemcpyAsync(part_own, w.res, sizeof(double) * DIST_BLOCKS, hipMemcpyDeviceToHost, st));
-      FLGP_HIP(stream_wait(st));
-      double sum = 0.0;
-      for (int q = 0; q < DIST_BLOCKS; ++q) sum += part[q];
-      delta = std::sqrt(sum);
-    } else {
-      hipLaunchKernelGGL(sym_scale_diag_kernel, dim3(ceil_div(b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
-      hipLaunchKernelGGL(sym_scale_apply_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
-      FLGP_TRY(check_launch("sym_scale_kernel"));
-      FLGP_TRY(dist_to_identity(w.T, &delta));
-    }
-    if (delta < 0.1 * tuning("eig_ns_plain_below_x10", 45)) {  // |I - S|_F bounds the spectral norm from above, loosely: try, and watch it contract
-                                                              // (measured at configs[2]: 3.6 contracted, 5.7 did not)
-      // well-conditioned block: S^-1/2 by the coupled Newton-Schulz iteration -- b x b MFMA GEMMs only
-      //   M = (3 I - Z Y)/2,  Y <- Y M,  Z <- M Z ;  Y -> S^1/2, Z -> S^-1/2   (|I - S| < 1)
-      double *Yc = w.T, *Zc = w.JV, *Mm = w.W, *Yn = w.JB, *Zn = w.X2;
-      // (Z_0 = I is never stored: the first step is M = (3 I - Y)/2, Y <- Y M, Z <- M -- one product instead of three)
-      if (!ns_first) FLGP_HIP(hipMemcpyAsync(Zc, w.Id, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));
-      // the error contracts quadratically, e <- (3/4) e^2 + O(e^3): run the predicted number of
-      // iterations without talking to the host, then check once (|I - S|_F over-estimates e, so
-      // the prediction errs on the safe side); a block that does not contract falls through to Jacobi
-      // (|I - S|_F over-estimates the spectral norm that contracts: the prediction starts from 0.3 |I - S|_F -- over eight start
-      //  blocks at configs[2] one to five steps fewer per orthonormalisation with the closing check still at rounding level,
-      //  13.84 -> 13.70 ms; a prediction that falls short fails that check and the block takes the scaled iteration below)
-      int kmax = tuning("eig_ns_extra", 2);   // steps beyond the predicted count (the closing check tests the LAST step's M, so one is inherent)
-      for (double e = std::min(delta * 0.01 * tuning("eig_ns_e0_pct", 30), 0.95); e > 1e-17 && kmax < 40; ++kmax) e = (e < 0.5) ? 0.8 * e * e : 0.5 * e + 0.4 * e * e;
-      bool ok = false;
-      for (int k = 0; k < kmax; ++k) {
-        if (k == 0 && ns_first) {
-          FLGP_TRY(first_step(Yc, -0.5, 1.5, Zn, Yn));
-          if (kmax == 1) FLGP_HIP(hipMemcpyAsync(Mm, Zn, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));   // (the closing check reads Mm)
-        } else {
-          FLGP_TRY(small_gemm(Zc, Yc, -0.5, 1.5, w.Id, Mm));
-          FLGP_TRY(small_gemm2(Yc, Mm, Yn, Mm, Zc, Zn));
-        }
-        std::swap(Yc, Yn);
-        std::swap(Zc, Zn);
-      }
-      {
-        // the last M must be the identity to rounding.  Its check is a host round trip: the rotation it would
-        // allow is enqueued behind the measurement first (a failed check just overwrites Qout later), so the
-        // GPU multiplies while the host reads the verdict
-        double part_own[DIST_BLOCKS];
-        const double *part = dist_d ? dist_h : part_own;
-        hipLaunchKernelGGL(dist_to_identity_kernel, dim3(DIST_BLOCKS), dim3(256), 0, st, Mm, b, dist_d ? dist_d : w.res);
-        FLGP_TRY(check_launch("dist_to_identity_kernel"));
-        if (!dist_d) FLGP_HIP(hipMemcpyAsync(part_own, w.res, sizeof(double) * DIST_BLOCKS, hipMemcpyDeviceToHost, st));
-        FLGP_HIP(stream_mark(st));
-        // Zc may live in JV or X2; the rotation needs diag(dinv) Z in W (Mm's buffer: read by the kernel above first)
-        hipLaunchKernelGGL(row_scale_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, Zc, b, w.dinv, w.W, 1.0, wt);
-        FLGP_TRY(check_launch("row_scale_kernel"));
-        FLGP_TRY(rotate(Yin, w.W, Qout));
-        FLGP_HIP(mark_wait());
-        double dm = 0.0;
-        for (int q = 0; q < DIST_BLOCKS; ++q) dm += part[q];
-        dm = std::sqrt(dm);
-        ok = dm < 1e-13 * std::sqrt((double)b);
-        if (tuning("eig_verbose", 0) > 1) fprintf(stderr, "[flgp orth] delta=%.3e kmax=%d dm=%.2e %s\n", delta, kmax, dm, ok ? "ok" : "FAILED");
-      }
-      if (ok) {
-        if (cond_out) *cond_out = (1.0 + delta) / std::max(1.0 - delta, 1e-3);
-        ++ns_orths;
-        return FLGP_OK;
-      }
-      // did not contract: rebuild S and fall through to Jacobi
-      FLGP_TRY(gram_small(Yin, Yin, w.T));
-      hipLaunchKernelGGL(sym_scale_apply_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
-      FLGP_TRY(check_launch("sym_scale_kernel"));
-    }
-    if (tuning("eig_ns_scaled", 1)) {
-      // ill-conditioned block (the first filters amplify by 1e3 and leave cond(S) ~ 1e5): the same
-      // Newton-Schulz iteration on S / sigma with sigma >= lambda_max.  Every eigenvalue x of Z Y obeys
-      // x <- x (3 - x)^2 / 4, which maps (0, 3) into (0, 1] and lifts a small x by 9/4 per step until
-      // the quadratic phase: ~log(cond)/log(2.25) + 5 iterations of three b x b GEMMs, against twenty
-      // Jacobi sweeps.  sigma = |S^2|_F^(1/2) over-estimates lambda_max by at most b^(1/4).
-      double *Yc = w.T, *Zc = w.JV, *Mm = w.W, *Yn = w.JB, *Zn = w.X2;
-      FLGP_TRY(small_gemm(Yc, Yc, 1.0, 0.0, nullptr, Yn));
-      // (sigma computed on the device -- one question to the host less, one launch more -- measured: 14.90 ms either way)
-      double f2 = 0.0;
-      FLGP_TRY(dist_to_identity(Yn, &f2, 0.0));      // |S^2|_F
-      const double sigma = 1.02 * std::sqrt(f2);
-      if (sigma > 0.0 && std::isfinite(sigma)) {
-        hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, 1.0 / sigma, Yc, 0.0, w.Id,
-                           Yn, (long)b * b);
-        FLGP_TRY(check_launch("eig_axpby_kernel"));
-        std::swap(Yc, Yn);
-        bool z_is_identity = ns_first;      // Z_0 = I not stored until a step needs it (see first_step)
-        if (!z_is_identity) FLGP_HIP(hipMemcpyAsync(Zc, w.Id, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));
-        double dm = 1.0;
-        double zn = 0.0;   // |Z - I|_F^2 + 1 >= 1/x_min: an upper bound of cond(S / sigma)
-        bool zn_valid = false;
-        bool ok = false;
-        // Dynamically scaled steps (Chen & Chow 2014): with every singular value x of the iterate in [l, 1],
-        //   x <- (a / 2) x (3 - a^2 x^2),  a = sqrt(3 / (1 + l + l^2)),
-        // is the cubic that lifts the lower end the most, l <- (a / 2) l (3 - a^2 l^2) (x 2.6 per step while l is small,
-        // against 1.5 unscaled), and keeps [l, 1] inside itself.  l_0 is a guess: one that is too low costs a few steps,
-        // one that is too high leaves singular values behind that the unscaled steps below then pick up at their own pace.
-        // The step count follows from l alone, so the host is not asked until the end.
-        int kdyn = 0;
-        {
-          double ell = std::pow(10.0, -(double)tuning("eig_ns_ell0_exp", 4));
-          const int tail = tuning("eig_ns_tail", 2);
-          int after = 0;
-          while (kdyn < 60 && tuning("eig_ns_dynamic", 1)) {
-            const bool plain = ell > 1.0 - 1e-9;
-            if (plain && after++ >= tail) break;
-            const double a = plain ? 1.0 : std::sqrt(3.0 / (1.0 + ell + ell * ell));
-            if (z_is_identity) {
-              FLGP_TRY(first_step(Yc, -0.5 * a * a * a, 1.5 * a, Zn, Yn));
-              z_is_identity = false;
-            } else {
-              FLGP_TRY(small_gemm(Zc, Yc, -0.5 * a * a * a, 1.5 * a, w.Id, Mm));
-              FLGP_TRY(small_gemm2(Yc, Mm, Yn, Mm, Zc, Zn));
-            }
-            std::swap(Yc, Yn);
-            std::swap(Zc, Zn);
-            ell = std::min(1.0, 0.5 * a * ell * (3.0 - a * a * ell * ell));
-            ++kdyn;
-          }
-          if (kdyn == 1 && ns_first)   // (the only step was the first one: its M sits in Zc, not in Mm)
-            FLGP_HIP(hipMemcpyAsync(Mm, Zc, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));
-          if (kdyn) {
-            FLGP_TRY(dist_to_identity2(Mm, Zc, &dm, &zn));      // (zn is wanted only if dm passes: asked in the same breath)
-            ok = std::isfinite(dm) && dm < 1e-9;
-            zn_valid = ok;
-          }
-        }
-        if (z_is_identity) {   // (no scaled step ran)
-          FLGP_HIP(hipMemcpyAsync(Zc, w.Id, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToDevice, st));
-          z_is_identity = false;
-        }
-        for (int k = 0; k < 72 && !ok && std::isfinite(dm); ++k) {
-          FLGP_TRY(small_gemm(Zc, Yc, -0.5, 1.5, w.Id, Mm));
-          FLGP_TRY(small_gemm2(Yc, Mm, Yn, Mm, Zc, Zn));
-          std::swap(Yc, Yn);
-          std::swap(Zc, Zn);
-          if ((kdyn || k >= 8) && k % 3 == 2) {
-            FLGP_TRY(dist_to_identity(Mm, &dm));
-            if (!std::isfinite(dm)) break;
-            ok = dm < 1e-9;
-          }
-        }
-        if (tuning("eig_verbose", 0) > 1) fprintf(stderr, "[flgp orth] scaled: delta=%.3e sigma=%.3e scaled steps=%d dm=%.2e %s\n", delta, sigma, kdyn, dm, ok ? "ok" : "FAILED");
-        if (ok) {
-          if (!zn_valid) FLGP_TRY(dist_to_identity(Zc, &zn));
-          hipLaunchKernelGGL(row_scale_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, Zc, b, w.dinv, w.W,
-                             1.0 / std::sqrt(sigma), wt);  // W = D (Z / sqrt(sigma))
-          FLGP_TRY(check_launch("row_scale_kernel"));
-          if (cond_out) {
-            *cond_out = 1.0 + zn * zn;
-            if (dm > 1e-12) *cond_out = std::max(*cond_out, 2e8);   // ask for the second pass
-          }
-          ++ns_orths;
-          return rotate(Yin, w.W, Qout);
-        }
-      }
-      FLGP_TRY(gram_small(Yin, Yin, w.T));
-      hipLaunchKernelGGL(sym_scale_apply_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, w.dinv);
-      FLGP_TRY(check_launch("sym_scale_kernel"));
-    }
-    ++jac_orths;
-    FLGP_TRY(jacobi_eig(st, w.T, b, b, w, lam, &sweeps));
-    double lmax = 0.0;
-    for (int j = 0; j < b; ++j) lmax = std::max(lmax, lam[j]);
-    std::vector<int> ord(b);
-    for (int j = 0; j < b; ++j) ord[j] = j;
-    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return lam[x] > lam[y]; });
-    std::vector<double> sc(b);
-    const double floor_ = lmax * 1e-28;
-    double lmin = lmax;
-    for (int j = 0; j < b; ++j) {
-      const double l = std::max(lam[ord[j]], floor_);
-      lmin = std::min(lmin, l);
-      sc[j] = 1.0 / std::sqrt(l);
-    }
-    if (cond_out) *cond_out = (lmin > 0.0) ? lmax / lmin : 1e300;
-    FLGP_TRY(sorted_basis(st, lam, &sc, b, b, w, order, w.dinv, wt));
-    return rotate(Yin, w.W, Qout);
-  };
-
-  // ---- start block: uniform random columns.  NOT orthonormalised (round 3): iteration 0 forms no Rayleigh-Ritz
-  //      matrix -- it filters the block as it is on a-priori bounds, and a filter is linear -- and the block that comes out
-  //      of the filter is orthonormalised anyway; a uniform random s x b block has condition
-  //      ~ (sqrt s + sqrt b) / (sqrt s - sqrt b) (1.6 at BASELINE configs[2]), so nothing is lost but the 0.33 ms of a
-  //      Gram product, 24 Newton-Schulz launches and two host round trips.  (eig_start_orths = 1 / 2: the old behaviour.)
-  //      Four s x b buffers rotate through the roles Q (current block) and three free ones.
-  double *Q = w.Q, *F[3] = {w.Y, w.Yp, w.Z};
-  const int start_orths = tuning("eig_start_orths", 1);   // (0 was tried in round 3: the 0.33 ms it saves sat in the shadow of the set-up's host round trips -- mean over eight start blocks 15.97 vs 15.83 ms)
-  hipLaunchKernelGGL(eig_init_q_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, st, start_orths > 0 ? F[0] : Q, s, b, s,
-                     (unsigned long long)tuning("eig_start_stream", 0));   // 0 = the documented start block; others: robustness runs
-  FLGP_TRY(check_launch("eig_init_q_kernel"));
-  // Rayleigh-Ritz on the random start block yields nothing but bounds, and poor ones (every Ritz value of a random
-  // subspace sits near the mean eigenvalue); the span p(G) Q does not depend on the basis.  So the first filter runs
-  // straight on the start block with a-priori bounds -- damped interval [0, trace / s], scaled at the 1-norm -- and the
-  // first Rayleigh-Ritz step (two Jacobi sweeps, two rotations, a host round trip) is saved.
-  const int skip_rr_n = tuning("eig_skip_rr0", 1) ? std::max(1, tuning("eig_skip_rr_n", 1)) : 0;   // iterations without Rayleigh-Ritz
-  const bool skip_rr0 = skip_rr_n > 0;
-  static_assert(2 * APRIORI_BLOCKS <= APRIORI_SLOT_DOUBLES, "the pinned slot of the a-priori bounds");
-  double h_apriori_own[2 * APRIORI_BLOCKS];
-  double *h_apriori = (g_ctx && g_ctx->pinned && tuning("eig_pinned_slots", 1)) ? (double *)((char *)g_ctx->pinned + BSG_HOST_SLOT_BYTES) : h_apriori_own;
-  if (skip_rr0 && !bs.built) {
-    hipLaunchKernelGGL(apriori_bounds_kernel, dim3(APRIORI_BLOCKS), dim3(256), 0, st, dG, ldg, s, w.apriori);
-    FLGP_TRY(check_launch("apriori_bounds_kernel"));
-    FLGP_HIP(hipMemcpyAsync(h_apriori, w.apriori, sizeof(double) * 2 * APRIORI_BLOCKS, hipMemcpyDeviceToHost, st));
-  }
-  double cond = 0.0;
-  if (start_orths >= 2) {
-    FLGP_TRY(orth(F[0], F[1], &cond));
-    FLGP_TRY(orth(F[1], Q, &cond));
-  } else if (start_orths == 1) {
-    FLGP_TRY(orth(F[0], Q, &cond));
-  } else if (!skip_rr0) {
-    // an iteration 0 WITH Rayleigh-Ritz needs an orthonormal block
-    FLGP_TRY(orth(Q, F[0], &cond));
-    std::swap(Q, F[0]);
-  }
-  FLGP_HIP(stream_wait(st));   // the set-up's bookkeeping (and the a-priori bounds) have arrived on the host
-  bsg_finish(bs);
-
-  std::vector<double> theta(b), res(K), pred(K, 1.0);   // pred: see plan_filter (soft locking)
-  bool soft_on = tuning("eig_soft_lock", 0) != 0;   // (off by default: see NOTEBOOK r04-1 -- 8 iterations instead of 10.4, but every one waits for two Jacobi sweeps)
-  int last_m = 0;                                  // degree of the filter applied last
-  int gprods = 0, it = 0;
-  const int max_it = 80;
+  EigSolver S(st, dG, ldg, s, K, b, tol, P, w);
+  FLGP_TRY(S.setup(p));
+  FLGP_TRY(S.start_block());
+  constexpr int max_it = 80;
   bool converged = false;
-  double *result = nullptr;
-  double rmax_prev = 1.0;
-  const int rr_every = soft_on ? 1 : tuning("eig_rr_every", 3);   // (soft locking needs every step's residuals; skipped steps were a saving of the 10-iteration schedule)
-  int since_rr = 0, it_meas = 0;
-  double rate = 0.1, rmax_meas = 0.0;
-
-  // second stream: late Rayleigh-Ritz refinements (eight workgroups of Jacobi) run beside the filter's GEMMs
-  struct Side {
-    hipStream_t st;
-    hipEvent_t ev;
-  } side{g_ctx ? g_ctx->side : nullptr, g_ctx ? g_ctx->side_ev : nullptr};
-  const bool can_overlap = side.st && side.ev && tuning("eig_overlap", 1);
-
-  double lambda_lo = (bs.built && tuning("eig_lanczos_lo", 1)) ? bs.lambda_lo : 0.0;   // far end of the damped interval
-  // ---- Chebyshev filter on [lo, cut], scaled to 1 at the top Ritz value
-  struct FilterPlan { double c, e, sigma1; int m; };
-  auto plan_filter = [&](double top, int it_) {
-    const int cut_pos = K + (b - K) * tuning("eig_cut_pct", 90) / 100;
-    double cut = theta[std::min(b - 1, std::max(K, cut_pos - 1))];
-    if (!(cut > 0.0)) cut = 1e-3 * top;
-    if (cut > 0.999 * top) cut = 0.999 * top;   // degenerate block: keep a valid interval
-    FilterPlan fp;
-    // damped interval [lo, cut]: lo = 0 (G is PSD) unless the set-up's Lanczos run vouches for more -- at BASELINE
-    // configs[2] lambda_min = 0.113 and cut = 0.39: the interval shrinks by a quarter, the filter's growth per degree at the
-    // K-th eigenvalue rises from 1.38 to 1.46, 17 % fewer products
-    const double lo = (lambda_lo > 0.0 && lambda_lo < 0.5 * cut) ? lambda_lo : 0.0;
-    fp.e = 0.5 * (cut - lo); fp.c = 0.5 * (cut + lo);
-    // Soft locking (round 4).  The amplification cap exists for the columns that are still moving: a filtered column j
-    // carries the rounding noise of the recurrence along the higher directions amplified by p(th_i) / p(th_j).  Along a
-    // CONVERGED Ritz direction that noise is removed by the Gram-Schmidt pass below to the accuracy of the converged vector,
-    // however large it was; so the cap is taken at the first Ritz value whose pair has NOT met the tolerance, not at the
-    // top of the spectrum.  At BASELINE configs[2] the sixteen cluster eigenvalues (0.994..1, then a gap to 0.66) converge
-    // by iteration 3 and the prefix grows by ~50 pairs per iteration: degrees 8 8 13 22 12 instead of 8 each, 7 outer
-    // iterations instead of 10 with the same number of products (scripts/model_chfsi2.py soft=1; a cap of 1e9 still
-    // converges in the model, 1e10 does not, and degrees beyond ~24 stop paying -- mmax).  The polynomial is still scaled to 1
-    // at the true top (sigma1), so converged columns grow by up to T_m(g_top) ~ 1e23 per iteration and are renormalised by
-    // the orthonormalisation's column scaling.  `pred` = the residuals of the last Rayleigh-Ritz step, contracted by the
-    // filters applied since (overlapped iterations plan their filter before the step's own residuals are known).
-    int n_soft = 0;
-    if (it_ >= 2 && soft_on) {
-      const double lim = tol * std::max(theta[0], 1e-300);
-      while (n_soft < K - 1 && pred[n_soft] <= lim) ++n_soft;
-    }
-    const double top_act = std::max(theta[n_soft], 1e-300);
-    const double g1 = (std::min(top, top_act) - fp.c) / fp.e;      // >= 1
-    // degree: amplification T_m(g1) of the top direction capped per outer iteration
-    // (gentler while the block is still far from the invariant subspace)
-    const double amp = std::pow(10.0, (double)((it_ < 2) ? tuning("eig_amp_exp_early", 3) : tuning("eig_amp_exp", 8)));
-    int m = (int)std::floor(std::acosh(amp) / std::acosh(std::max(g1, 1.0 + 1e-12)));
-    const int m_cap = n_soft ? tuning("eig_soft_mmax", 24) : 40;
-    fp.m = std::max(2, std::min(m, m_cap));
-    // Landing.  A filter of degree m contracts the residual of the K-th pair -- the slowest -- by 1 / T_m(g_K) ~ 2 exp(-m a),
-    // a = acosh(g_K), g_K the K-th Ritz value on the filter's own scale (measured at configs[2]: 0.0526 per iteration
-    // against 1 / T_8(1.1055) = 0.0526).  With the last measured residual that gives the iterations still needed at the
-    // capped degree, n0.  If a few degrees more per iteration save a whole iteration (orthonormalisation, Rayleigh-Ritz
-    // and its wait: ~1 ms) they are spent; if n0 iterations overshoot, the degree is lowered to what the tolerance needs.
-    // Without this the iteration on which the residual test is first met moves by one with perturbations of rounding
-    // size (DESIGN section 4: 10 or 11 iterations at configs[2], depending on the start block).
-    if (it_ >= 3 && tuning("eig_landing", 1) && rmax_prev > 0.0 && rmax_prev < 1e-8 * (double)tuning("eig_landing_below_e8", 100)) {
-      const double gK = (theta[K - 1] - fp.c) / fp.e;
-      if (gK > 1.0 + 1e-9) {
-        const double a = std::acosh(gK), ln2 = 0.6931471805599453;
-        const double target = tol * 0.01 * (double)tuning("eig_landing_margin_pct", 40);
-        const double L = std::log(rmax_prev / target);
-        const double per0 = fp.m * a - ln2;
-        if (L > 0.0 && per0 > 0.0) {
-          const int n0 = std::max(1, (int)std::ceil(L / per0));
-          auto degree_for = [&](int n) { return (int)std::ceil((L / n + ln2) / a); };
-          int mm = degree_for(n0);                                  // <= fp.m by construction of n0
-          // (one iteration fewer at most, and three degrees more at most: with five or eight more per iteration the block
-          //  loses accuracy faster than the filter gains -- 14 and 15 iterations instead of 10)
-          if (n0 >= 2 && degree_for(n0 - 1) <= fp.m + tuning("eig_landing_boost", 3)) mm = degree_for(n0 - 1);
-          fp.m = std::max(2, std::min(mm, m_cap));
-          rate = std::min(0.5, std::max(1e-4, 2.0 * std::exp(-fp.m * a)));
-        }
-      }
-    }
-    fp.sigma1 = fp.e / (top - fp.c);
-    if (tuning("eig_verbose", 0)) fprintf(stderr, "[flgp eig]   filter it=%d: soft prefix %d, active top %.4f, cut %.4f, lo %.3f, degree %d\n", it_, n_soft, top_act, cut, lo, fp.m);
-    return fp;
-  };
-  // what a filter just applied does to the residual of pair j: 1 / T_m(g_j) ~ 2 exp(-m acosh g_j), times a safety factor
-  // (the model: measured contraction within 3x of this for every pair once the block is past its first two iterations)
-  auto contract_pred = [&](const FilterPlan &fp) {
-    last_m = fp.m;
-    const double safety = (double)tuning("eig_soft_safety", 10);
-    for (int j = 0; j < K; ++j) {
-      const double g = (theta[j] - fp.c) / fp.e;
-      if (g > 1.0) pred[j] *= std::min(1.0, safety * 2.0 * std::exp(-fp.m * std::acosh(g)));
-    }
-  };
-  // p(G) A given B = G A; A, f1, f2 are overwritten (B is not); returns the buffer with the result and
-  // one buffer that is free afterwards
-  auto apply_filter = [&](const FilterPlan &fp, double *A, const double *B, double *f1, double *f2, double **cur_out,
-                          double **spare_out) -> int {
-    double sigma = fp.sigma1;
-    if (bs.on) {
-      // the recurrence on transposed blocks; A and B are left alone, the result lands in f1
-      if (!(t_q == A && t_z == B)) {
-        FLGP_TRY(to_t(A, bs.T[0]));
-        FLGP_TRY(to_t(B, bs.T[1]));
-      }
-      t_q = nullptr; t_z = nullptr;
-      double *prev = bs.T[0], *cur = bs.T[2], *next = bs.T[1];
-      hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, st, fp.sigma1 / fp.e, bs.T[1],
-                         -fp.sigma1 * fp.c / fp.e, bs.T[0], cur, tot);
-      FLGP_TRY(check_launch("eig_axpby_kernel"));
-      for (int deg = 2; deg <= fp.m; ++deg) {
-        const double sn = 1.0 / (2.0 / fp.sigma1 - sigma);
-        FLGP_TRY(gemmG_t(cur, 2.0 * sn / fp.e, -2.0 * sn * fp.c / fp.e, cur, -sigma * sn, prev, next));
-        ++gprods;
-        double *t3 = prev; prev = cur; cur = next; next = t3;
-        sigma = sn;
-      }
-      FLGP_TRY(from_t(cur, f1));
-      *cur_out = f1;
-      *spare_out = f2;
-      return FLGP_OK;
-    }
-    // degree 1: Y = (sigma1/e) (G A - c A) = (sigma1/e) (B - c A), into a free buffer
-    double *prev = A, *cur = f1, *next = f2;
-    hipLaunchKernelGGL(eig_axpby_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, st, fp.sigma1 / fp.e, B,
-                       -fp.sigma1 * fp.c / fp.e, A, cur, tot);
-    FLGP_TRY(check_launch("eig_axpby_kernel"));
-    for (int deg = 2; deg <= fp.m; ++deg) {
-      const double sn = 1.0 / (2.0 / fp.sigma1 - sigma);
-      // next = (2 sn / e) (G cur - c cur) - sigma sn prev
-      FLGP_TRY(gemmG(cur, 2.0 * sn / fp.e, -2.0 * sn * fp.c / fp.e, cur, -sigma * sn, prev, next));
-      ++gprods;
-      double *t3 = prev; prev = cur; cur = next; next = t3;
-      sigma = sn;
-    }
-    *cur_out = cur;
-    *spare_out = prev;
-    return FLGP_OK;
-  };
-  // residuals of the K wanted pairs (A = Ritz vectors, B = G A) with the Ritz values sorted_basis_dev left in w.theta;
-  // the ONE host round trip of a Rayleigh-Ritz step: brings the residuals and the sorted Ritz values over together
-  std::vector<double> rt(2 * (size_t)b);
-  auto residuals = [&](const double *A, const double *B, double *rmax_out) -> int {
-    hipLaunchKernelGGL(resid_kernel, dim3(K), dim3(256), 0, st, B, A, s, s, w.theta, w.res, rt_d, b, 1);
-    FLGP_TRY(check_launch("resid_kernel"));
-    const double *rtp = rt_h;
-    if (!rt_d) { FLGP_HIP(hipMemcpyAsync(rt.data(), w.res, sizeof(double) * 2 * b, hipMemcpyDeviceToHost, st)); rtp = rt.data(); }
-    FLGP_HIP(stream_wait(st));
-    double rmax = 0.0;
-    for (int j = 0; j < K; ++j) { res[j] = rtp[j]; pred[j] = res[j]; rmax = std::max(rmax, res[j]); }
-    for (int j = 0; j < b; ++j) theta[j] = rtp[b + j];
-    *rmax_out = rmax;
-    return FLGP_OK;
-  };
-  // Overlapped iterations plan their filter before the Rayleigh-Ritz step has finished.  The columns of Q are last
-  // iteration's Ritz vectors, filtered, cleaned and orthonormalised -- nearly Ritz -- so | Z_j - Q_j T_jj | is a residual of
-  // an approximate pair in its own right, and an upper estimate of the Ritz pair's: a MEASURED prefix of converged pairs for
-  // the soft locking, one small kernel and one host round trip (~25 us) behind the Gram product that is waited for anyway.
-  auto residual_estimate = [&](const double *Qc, const double *Zc, const double *Tm) -> int {
-    hipLaunchKernelGGL(resid_kernel, dim3(K), dim3(256), 0, st, Zc, Qc, s, s, Tm, w.res, rt_d, b, b + 1);
-    FLGP_TRY(check_launch("resid_kernel"));
-    const double *rtp = rt_h;
-    if (!rt_d) { FLGP_HIP(hipMemcpyAsync(rt.data(), w.res, sizeof(double) * K, hipMemcpyDeviceToHost, st)); rtp = rt.data(); }
-    FLGP_HIP(stream_wait(st));
-    for (int j = 0; j < K; ++j) pred[j] = rtp[j];
-    return FLGP_OK;
-  };
-  auto after_rr = [&](double rmax, double top, bool overlapped) {   // book-keeping shared by both orders
-    // the watch on the Lanczos bound: a direction below `lambda_lo` that the filter amplified instead of damping shows
-    // up as a Ritz value far below the guard block's (which sit just under the K-th); then the bound goes
-    if (lambda_lo > 0.0 && theta[b - 1] < lambda_lo + 0.5 * (theta[K - 1] - lambda_lo)) {
-      if (tuning("eig_verbose", 0)) fprintf(stderr, "[flgp eig] smallest Ritz value %.4g: the lower bound %.4g is dropped\n", theta[b - 1], lambda_lo);
-      lambda_lo = 0.0;
-    }
-    if (tuning("eig_verbose", 0)) {
-      int npre = 0, nconv = 0;
-      while (npre < K && res[npre] <= tol * top) ++npre;
-      for (int j = 0; j < K; ++j) nconv += res[j] <= tol * top;
-      fprintf(stderr, "[flgp eig] it=%d gprods=%d theta0=%.15g thetaK=%.6g cut=%.6g rmax=%.3e cond=%.2e sweeps=%d conv=%d prefix=%d%s\n",
-              it, gprods, theta[0], theta[K - 1], theta[b - 1], rmax, cond, sweeps, nconv, npre, overlapped ? " (overlapped)" : "");
-      if (tuning("eig_verbose", 0) > 2) {
-        int shown = 0;
-        for (int j = 0; j < K && shown < 8; ++j) if (res[j] > tol * top) { fprintf(stderr, "    pair %d theta %.9f res %.2e\n", j, theta[j], res[j]); ++shown; }
-      }
-    }
-    if (rmax <= tol * top) return true;
-    // the soft locking's safeguard: residuals that GROW say a filter was stronger than the block could take (a pair counted
-    // as converged was not) -- back to the cap at the top of the spectrum for the rest of the solve
-    if (soft_on && it >= 3 && rmax_meas > 0.0 && rmax / top > 4.0 * rmax_meas) {
-      soft_on = false;
-      if (tuning("eig_verbose", 0)) fprintf(stderr, "[flgp eig] residual grew (%.2e -> %.2e): soft locking off\n", rmax_meas, rmax / top);
-    }
-    if (it >= 3 && rmax_meas > 0.0 && rmax / top < rmax_meas) {
-      const double rt = std::pow((rmax / top) / rmax_meas, 1.0 / (double)(it - it_meas));
-      rate = std::min(0.5, std::max(0.02, rt));
-    }
-    rmax_meas = rmax / top; it_meas = it;
-    rmax_prev = rmax / top;
-    return false;
-  };
-
-  for (it = 0; it < max_it; ++it) {
-    double *Z = F[0];
-    double *A, *B, *free1, *free2;     // Ritz vectors, G * Ritz vectors, two free s x b buffers
-    double *cur = nullptr, *spare = nullptr;   // filtered block; a buffer that is free after the filter
-    if (bs.on) {
-      FLGP_TRY(to_t(Q, bs.T[0]));
-      FLGP_TRY(gemmG_t(bs.T[0], 1.0, 0.0, nullptr, 0.0, nullptr, bs.T[1]));
-      FLGP_TRY(from_t(bs.T[1], Z));
-      t_q = Q; t_z = Z;
-    } else {
-      FLGP_TRY(gemmG(Q, 1.0, 0.0, nullptr, 0.0, nullptr, Z));
-    }
-    ++gprods;
-    // Rayleigh-Ritz may be skipped on some late iterations (rr_every > 1): the block is then used as it
-    // is (its columns are the previous Ritz vectors, filtered, cleaned and orthonormalised: still ordered
-    // and nearly Ritz), bounds are reused, and no convergence test is made on that iteration
-    // (rmax_prev is then advanced by the measured per-iteration contraction `rate`, so that the Rayleigh-
-    //  Ritz step and its convergence test land on the iteration where the tolerance is expected to be met)
-    const bool near_done = rmax_prev * rate <= 4.0 * tol;
-    const bool early_skip = (tuning("eig_skip_it1", 0) && it == 1) || it < skip_rr_n;
-    const bool do_rr = !early_skip && !(rr_every > 1 && it >= 3 && rmax_prev < 1e-6 * tuning("eig_rr_skip_below_e6", 1000) && since_rr + 1 < rr_every && !near_done);
-    // Late Rayleigh-Ritz steps only refine a nearly diagonal T: the filter does not wait for them.  It is
-    // linear, p(G) (Q W) = (p(G) Q) W, so it runs on the block as it is, with the bounds of the previous
-    // step (once the residuals are below 1e-3 they move in the third digit: measured, earlier steps lose
-    // more to the stale interval than they gain), while the refinement runs on the second stream; the
-    // rotation W is applied to the filtered block afterwards.  Not on the step that is expected to
-    // converge: there the filter's products would be thrown away.
-    const bool overlap = can_overlap && do_rr && it >= tuning("eig_overlap_from_it", 3) && !near_done &&
-                         rmax_prev <= 1e-6 * (double)tuning("eig_overlap_below_e6", 10000);
-    double rmax = rmax_prev * rate, top = std::max(theta[0], 1e-300);
-    if (do_rr && overlap) {
-      since_rr = 0;
-      FLGP_TRY(gram_small(Q, Z, w.T));
-      FLGP_HIP(hipEventRecord(side.ev, st));
-      // the other stream first (round 4: it used to be enqueued BEHIND the filter's launches, and the host needs ~0.4 ms to
-      // enqueue a filter of degree 24 -- the refinement, which is the longer of the two, started that much late): T = W Th W^T
-      FLGP_HIP(hipStreamWaitEvent(side.st, side.ev, 0));
-      {
-        int nsw = std::max(1, (rmax_prev > 1e-4 * tuning("eig_refine3_above_e4", 2000) ? 3 : (rmax_prev > 1e-8 * tuning("eig_refine2_above_e8", 100) ? 2 : 1)) - tuning("eig_refine_minus", 0));
-        if (last_m >= tuning("eig_sweeps2_from_m", 11)) nsw = std::max(nsw, 2);   // a strong filter leaves T further from diagonal than the residual says (measured: one sweep after degree 24 un-converged the cluster pairs)
-        FLGP_TRY(jacobi_refine(side.st, w.T, b, K, w, lam, &sweeps, nsw, false));
-        sweeps = nsw;
-      }
-      FLGP_TRY(sorted_basis_dev(side.st, b, w, wt));   // order and W on the device: the host is not asked
-      FLGP_HIP(hipEventRecord(side.ev, side.st));
-      FLGP_HIP(hipMemcpyAsync(w.Qold, Q, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
-      if (soft_on && tuning("eig_soft_estimate", 1)) FLGP_TRY(residual_estimate(Q, Z, w.T));
-      const FilterPlan fp = plan_filter(top, it);
-      FLGP_TRY(apply_filter(fp, Q, Z, F[1], F[2], &cur, &spare));
-      FLGP_HIP(hipStreamWaitEvent(st, side.ev, 0));
-      // the two buffers of {Q, F1, F2} that do not hold the filtered block take A and B
-      double *trio[3] = {Q, F[1], F[2]};
-      double *x[2]; int nx = 0;
-      for (int q = 0; q < 3; ++q) if (trio[q] != cur) x[nx++] = trio[q];
-      A = x[0]; B = x[1];
-      FLGP_TRY(rotate2(w.Qold, Z, w.W, A, B));   // A = Ritz vectors, B = G * Ritz vectors
-      FLGP_TRY(residuals(A, B, &rmax));
-      top = std::max(theta[0], 1e-300);
-      if (after_rr(rmax, top, true)) { converged = true; result = A; break; }
-      contract_pred(fp);                  // (the residuals just measured are those of the block BEFORE this iteration's filter)
-      FLGP_TRY(rotate(cur, w.W, Z));      // the filtered block in the new Ritz order (Z is free by now)
-      FLGP_HIP(hipMemcpyAsync(w.Qold, A, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
-      free1 = cur; free2 = Z;
-      spare = cur;
-      cur = Z;
-    } else {
-      if (do_rr) {
-        since_rr = 0;
-        A = F[1]; B = F[2]; free1 = Q; free2 = Z;
-        // ---- Rayleigh-Ritz on span(Q): Z = G Q, T = Q^T Z, T = W Th W^T
-        FLGP_TRY(gram_small(Q, Z, w.T));
-        // T is far from diagonal only while the block is far from invariant: full Jacobi for the first
-        // iterations, afterwards a single sweep refines the (already nearly diagonal) Ritz basis
-        // (a fixed small number of global sweeps alone is NOT enough, even late: the guard columns
-        //  never converge, so their diagonal block of T stays dense -- measured: 2 sweeps put rmax
-        //  back to 4e-2.  jacobi_refine diagonalises that block first.)
-        if (it < 2) {       // bounds and a rough Ritz basis are all that is needed yet: loose threshold, capped sweeps
-          sweeps = tuning(it == 0 ? "eig_sweeps_it0" : "eig_sweeps_it1", 2);
-          FLGP_TRY(jacobi_eig(st, w.T, b, b, w, lam, nullptr, sweeps, 1e10, false, false));
-        } else if (rmax_prev > 5e-2) {
-          sweeps = tuning("eig_sweeps_it2", 2);
-          FLGP_TRY(jacobi_eig(st, w.T, b, b, w, lam, nullptr, sweeps, 1e6, false, false));
-        } else {
-          sweeps = std::max(1, (rmax_prev > 1e-4 * tuning("eig_refine3_above_e4", 2000) ? 3 : (rmax_prev > 1e-8 * tuning("eig_refine2_above_e8", 100) ? 2 : 1)) - tuning("eig_refine_minus", 0));
-          if (last_m >= tuning("eig_sweeps2_from_m", 11)) sweeps = std::max(sweeps, 2);
-          FLGP_TRY(jacobi_refine(st, w.T, b, K, w, lam, nullptr, sweeps, false));
-        }
-        FLGP_TRY(sorted_basis_dev(st, b, w, wt));
-        FLGP_TRY(rotate2(Q, Z, w.W, A, B));   // A = Ritz vectors, B = G * Ritz vectors
-        FLGP_TRY(residuals(A, B, &rmax));
-        top = std::max(theta[0], 1e-300);
-        if (after_rr(rmax, top, false)) { converged = true; result = A; break; }
-      } else {
-        ++since_rr;
-        A = Q; B = Z; free1 = F[1]; free2 = F[2];
-        if (it >= skip_rr_n) rmax_prev *= rate;
-      }
-      FilterPlan fp;
-      if (it < skip_rr_n) {   // (the start orthonormalisation has synchronised the stream: h_apriori is valid)
-        double n1 = 0.0, tr = 0.0;
-        if (bs.built) { n1 = bs.h_bounds[0]; tr = bs.h_bounds[1]; }   // gathered by the block-sparse set-up's pass over G
-        else for (int q = 0; q < APRIORI_BLOCKS; ++q) { n1 = std::max(n1, h_apriori[q]); tr += h_apriori[APRIORI_BLOCKS + q]; }
-        double cut0 = tr / (double)s;
-        if (!(n1 > 0.0) || !std::isfinite(n1)) { set_error("eigensolver: the matrix is zero or not finite"); return FLGP_ERR_INVALID; }
-        if (!(cut0 > 1e-3 * n1)) cut0 = 1e-3 * n1;
-        if (cut0 > 0.5 * n1) cut0 = 0.5 * n1;
-        fp.c = fp.e = 0.5 * cut0;
-        fp.sigma1 = fp.e / (n1 - fp.c);
-        fp.m = std::max(2, it == 0 ? tuning("eig_m0", 8) : tuning("eig_m1", 6));
-        top = n1;
-      } else {
-        fp = plan_filter(top, it);
-      }
-      // the Ritz vectors are needed again after the filter (see below): keep a copy
-      FLGP_HIP(hipMemcpyAsync(w.Qold, A, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
-      FLGP_TRY(apply_filter(fp, A, B, free1, free2, &cur, &spare));
-      if (it >= skip_rr_n) contract_pred(fp);
-    }
-    // ---- de-contaminate: a filtered column y_j = p(G) q_j carries its error components along the
-    //      higher Ritz directions amplified by p(th_i)/p(th_j) (up to `amp`).  One Gram-Schmidt pass
-    //      against the OLD Ritz vectors in sorted order removes exactly those:
-    //          y_j <- y_j - sum_{i<j} q_i (q_i . y_j)
-    //      (two GEMMs).  What is left is nearly orthogonal, so the symmetric orthonormalisation below
-    //      no longer mixes eigen-directions and the next T stays diagonal up to the guard block.
-    //      (Not after the a-priori filter of iteration 0: the start block is no Ritz basis, and projecting along its
-    //      columns would take the block out of span p(G) Q.)
-    if (!(it < skip_rr_n)) {
-      if (use_rot) {
-        // T^T = cur^T Qold, strictly lower: the same sums (products commute), laid out k-major as rot.hip reads W
-        GemmFusedReduce fr{8, nullptr, nullptr, w.red, w.redcnt, false};
-        FLGP_TRY(gram_small(cur, w.Qold, w.T, fuse_reduce ? &fr : nullptr));
-        if (!fr.done) {
-          hipLaunchKernelGGL(mask_strict_upper_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b, 1);
-          FLGP_TRY(check_launch("mask_strict_upper_kernel"));
-        }
-        FLGP_TRY(rot_launch(st, s, b, -1.0, w.Qold, nullptr, w.T, 1.0, cur, nullptr, cur, nullptr));
-      } else {
-      GemmFusedReduce fr{2, nullptr, nullptr, w.red, w.redcnt, false};   // the strict upper triangle, by the reduction kernel
-      FLGP_TRY(gram_small(w.Qold, cur, w.T, fuse_reduce ? &fr : nullptr));
-      if (!fr.done) {
-        hipLaunchKernelGGL(mask_strict_upper_kernel, dim3(ceil_div((long)b * b, 256)), dim3(256), 0, st, w.T, b);
-        FLGP_TRY(check_launch("mask_strict_upper_kernel"));
-      }
-      FLGP_TRY(gemm_launch(st, s, b, b, -1.0, w.Qold, 1, s, w.T, 1, b, 1.0, cur, 1, s, cur, 1, s, w.gemm_ws, w.gemm_ws_elems,
-                           0.0, nullptr, w.tickets));
-      }
-    }
-    // ---- orthonormalise the filtered block (B is free by now; twice if ill-conditioned)
-    FLGP_TRY(orth(cur, B, &cond));
-    double *R = B;
-    if (cond > 1e8) {
-      FLGP_TRY(orth(B, spare, &cond));
-      R = spare;
-    }
-    // new roles: Q = R, the other three buffers are free
-    double *pool[4] = {A, B, free1, free2};
-    int nf = 0;
-    for (int q = 0; q < 4; ++q)
-      if (pool[q] != R) F[nf++] = pool[q];
-    Q = R;
+  for (S.it = 0; S.it < max_it; ++S.it) {
+    FLGP_TRY(S.iteration(&converged));
+    if (converged) break;
   }
-  if (info) { info[0] = it; info[1] = gprods; info[2] = 0; info[3] = ns_orths * 1000 + jac_orths; }
-  if (!converged) {
-    // A spectrum the filter cannot split -- e.g. r = 1, where G is the identity up to the 1e-9 guards and the wanted
-    // and unwanted eigenvalues coincide -- never meets the residual test.  While the full decomposition is affordable
-    // (s <= 4096) it is taken instead, with its own workspace: any orthonormal basis of a degenerate eigenspace is a
-    // valid answer, and the Jacobi route always delivers one.
-    if (s <= 8192 && tuning("eig_dense_fallback", 1)) {
-      DevBuf fw, fvals, fV;
-      const size_t fb = eig_workspace_bytes(s, s);
-      FLGP_TRY(fw.alloc(fb));
-      FLGP_TRY(fvals.alloc(sizeof(double) * (size_t)s));
-      FLGP_TRY(fV.alloc(sizeof(double) * (size_t)s * s));
-      if (tuning("eig_verbose", 0)) fprintf(stderr, "[flgp eig] no convergence after %d outer iterations: full decomposition instead\n", max_it);
-      FLGP_TRY(flgp_dev_eig_topk(stream, dG, ldg, s, s, tol, fvals.as<double>(), fV.as<double>(), s, fw.p, fb, nullptr));
-      FLGP_HIP(hipMemcpyAsync(d_values, fvals.p, sizeof(double) * K, hipMemcpyDeviceToDevice, st));
-      FLGP_HIP(hipMemcpy2DAsync(dV, sizeof(double) * (size_t)ldv, fV.p, sizeof(double) * (size_t)s, sizeof(double) * (size_t)s, K,
-                                hipMemcpyDeviceToDevice, st));
-      FLGP_HIP(stream_wait(st));
-      if (info) info[2] = 1;
-      return FLGP_OK;
-    }
-    set_error("eigensolver: %d of the residuals still above %.1e after %d outer iterations", K, tol, max_it);
-    return FLGP_ERR_NOCONV;
-  }
-  if (rt_h) {       // (through the pinned slot: an upload from pageable memory is staged by the runtime first)
-    memcpy(rt_h, theta.data(), sizeof(double) * K);
-    FLGP_HIP(hipMemcpyAsync(d_values, rt_h, sizeof(double) * K, hipMemcpyHostToDevice, st));
-  } else {
-    FLGP_HIP(hipMemcpyAsync(d_values, theta.data(), sizeof(double) * K, hipMemcpyHostToDevice, st));
-  }
-  if (bs.on) {   // the solver worked on P G P^T: rows back to the caller's anchor order
-    hipLaunchKernelGGL(bs_unpermute_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, result, s, K, bs.perm, dV, ldv);
-    FLGP_TRY(check_launch("bs_unpermute_kernel"));
-  } else {
-    FLGP_HIP(hipMemcpy2DAsync(dV, sizeof(double) * ldv, result, sizeof(double) * s, sizeof(double) * s, K,
-                              hipMemcpyDeviceToDevice, st));
-  }
-  FLGP_HIP(stream_wait(st));
-  return FLGP_OK;
+  return S.finish(converged, stream, d_values, dV, ldv, info);
 }
 
 extern "C" void flgp_dev_jac_set_trace(void *d_trace) { flgp::g_jac_trace = (long long *)d_trace; }

@@ -621,6 +621,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_sym_kernel(GemmArgs g, int 
   if (tid == 0) *counter = 0;
 }
 
+// split-K planes of a product with `ntiles` output tiles and depth Kd, before the workspace limit: fill the chip (tile64: the
+// 64-wide tiles' budget of blocks), but keep at least gemm_min_stages (default 5) stages of depth gk per block -- with fewer,
+// the partial planes (and the reduction that reads them back) cost more than the extra blocks gain: the 256 x 256 x 5000
+// Gram products of the eigensolver spent 33 us in the reduction of 128 planes next to 26 us in the GEMM
+int gemm_split_limit(int Kd, int ntiles, int gk, bool tile64) {
+  const int nsplit = (tile64 ? tuning("gemm_tile64_blocks", 256) : 512) / ntiles;
+  const int maxk = Kd / (tuning("gemm_min_stages", 5) * gk);
+  return nsplit < maxk ? nsplit : maxk;
+}
+
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
@@ -659,12 +669,7 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
   const size_t per = g.tickets ? (size_t)ntiles * PLANE : (size_t)g.M * g.N;
   int nsplit = 1;
   if (work && !pair && ntiles < 256 && Kd >= 8 * GK) {
-    nsplit = (gbt == 64 ? tuning("gemm_tile64_blocks", 256) : 512) / ntiles;
-    // at least gemm_min_stages (default 5) stages per block: with fewer, the partial planes (and the reduction that
-    // reads them back) cost more than the extra blocks gain -- the 256 x 256 x 5000 Gram products of the
-    // eigensolver spent 33 us in the reduction of 128 planes next to 26 us in the GEMM
-    const int maxk = Kd / (tuning("gemm_min_stages", 5) * GK);
-    if (nsplit > maxk) nsplit = maxk;
+    nsplit = gemm_split_limit(Kd, ntiles, GK, gbt == 64);
     if ((size_t)nsplit * per > work_elems) nsplit = (int)(work_elems / per);
     if (nsplit < 1) nsplit = 1;
   }

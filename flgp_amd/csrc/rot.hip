@@ -13,6 +13,7 @@
 //     contiguous bytes of a column of out.
 // Tile 64 x 64, four waves of 32 x 32; gridDim.y = 2 runs a second rotation by the same W (the Rayleigh-Ritz pair).
 #include "common.h"
+#include <mutex>
 #include <type_traits>
 
 namespace flgp {
@@ -153,8 +154,19 @@ __global__ __launch_bounds__(256, 2) void rot_kernel(RotArgs g) {   // (GKR: k d
 // whether rot_launch takes the shape (else the caller multiplies with gemm_launch on the same operands)
 bool rot_applicable(int s, int b, const double *X, const double *X2, const double *WT, const double *out, const double *out2) {
   auto al = [](const void *p) { return (((size_t)p) & 15) == 0; };
-  return tuning("eig_rot_kernel", 1) && b >= 64 && b <= 256 && b % 64 == 0 && s >= 64 && s % 2 == 0 && al(X) && al(WT) && al(out) &&
+  return b >= 64 && b <= 256 && b % 64 == 0 && s >= 64 && s % 2 == 0 && al(X) && al(WT) && al(out) &&
          (!X2 || (al(X2) && al(out2)));
+}
+
+// multiprocessors of device `dev` (< 64), asked once per device; 0 if the query failed
+static int device_cus(int dev) {
+  static std::once_flag once[64];
+  static int cus[64];
+  std::call_once(once[dev], [dev] {
+    hipDeviceProp_t pr;
+    cus[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 0;
+  });
+  return cus[dev];
 }
 
 // out = alpha X W + beta E   (and out2 = alpha X2 W + beta E2 when X2 is given)
@@ -164,29 +176,18 @@ int rot_launch(hipStream_t st, int s, int b, double alpha, const double *X, cons
   g.X = X; g.X2 = X2; g.WT = WT; g.E = (beta == 0.0) ? nullptr : E; g.E2 = (beta == 0.0) ? nullptr : E2;
   g.out = out; g.out2 = out2; g.s = s; g.b = b; g.alpha = alpha; g.beta = beta;
   // 32-row tiles while 64-row tiles would leave the chip unevenly loaded (fewer than four tiles per CU)
-  int n_cu = 256;
-  {
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-      if (!cached[dev]) { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess) cached[dev] = pr.multiProcessorCount; }
-      if (cached[dev] > 0) n_cu = cached[dev];
-    }
-  }
+  int n_cu = 256, dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && device_cus(dev) > 0) n_cu = device_cus(dev);
   const int np = X2 ? 2 : 1;
-  const int tm_knob = tuning("eig_rot_tile", 0);
-  const bool tm32 = tm_knob ? tm_knob == 32 : ((long)(b / 64) * ceil_div(s, 64) * np < 4L * n_cu);
+  const bool tm32 = (long)(b / 64) * ceil_div(s, 64) * np < 4L * n_cu;
   const int nt = (b / 64) * ceil_div(s, tm32 ? 32 : 64);
   const dim3 grid(nt, np);
   const double fl = 2.0 * (double)s * b * b * np;
   ProfScope ps("gemm_f64_kernel", st, fl);
   ProfScope ps2("gemm_medium", st, fl);
-  if (tm32 && tuning("eig_rot_gk16", 1)) {
+  if (tm32) {   // (16-deep stages: the 32-row tiles' X loads are half as wide)
     if (g.E) hipLaunchKernelGGL((rot_kernel<32, 16, true>), grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL((rot_kernel<32, 16, false>), grid, dim3(256), 0, st, g);
-  } else if (tm32) {
-    if (g.E) hipLaunchKernelGGL((rot_kernel<32, 32, true>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((rot_kernel<32, 32, false>), grid, dim3(256), 0, st, g);
   } else {
     if (g.E) hipLaunchKernelGGL((rot_kernel<64, 32, true>), grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL((rot_kernel<64, 32, false>), grid, dim3(256), 0, st, g);
@@ -295,9 +296,7 @@ __global__ __launch_bounds__(256, 2) void gramk_kernel(const double *__restrict_
 
 static int gramk_split(int s, int b, int *klen_out) {
   const int ntiles = (b / 64) * (b / 64);
-  int nsplit = tuning("gemm_tile64_blocks", 256) / ntiles;          // as gemm_launch splits the same product
-  const int maxk = s / (tuning("gemm_min_stages", 5) * 16);
-  if (nsplit > maxk) nsplit = maxk;
+  int nsplit = gemm_split_limit(s, ntiles, 16, true);               // as gemm_launch splits the same product
   if (nsplit < 1) nsplit = 1;
   int klen = ceil_div(s, nsplit);
   klen = (klen + ROT_GK - 1) / ROT_GK * ROT_GK;
@@ -307,7 +306,7 @@ static int gramk_split(int s, int b, int *klen_out) {
 
 bool gramk_applicable(int s, int b, const double *Xa, const double *Xb, size_t work_elems) {
   auto al = [](const void *p) { return (((size_t)p) & 15) == 0; };
-  if (!(tuning("eig_gram_kernel", 1) && b >= 64 && b <= 256 && b % 64 == 0 && s >= 256 && s % 2 == 0 && al(Xa) && al(Xb))) return false;
+  if (!(b >= 64 && b <= 256 && b % 64 == 0 && s >= 256 && s % 2 == 0 && al(Xa) && al(Xb))) return false;
   int klen;
   const int nsplit = gramk_split(s, b, &klen);
   return nsplit >= 2 && (size_t)nsplit * b * b <= work_elems;
