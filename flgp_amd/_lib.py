@@ -55,6 +55,10 @@ _SIGNATURES = {
     "flgp_eigenpair_predict_regression": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_double, c_double, c_double, P]),
     "flgp_eigenpair_predict_regression_different": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_double, P, c_double, P]),
     "flgp_eigenpair_posterior_variance": (c_int, [P, c_int, P, c_int, P, c_int, c_double, c_double, c_double, P]),
+    "flgp_logit_la_marginal_likelihood": (c_int, [P, c_int, P, P, c_double, c_int, P, P]),
+    "flgp_eigenpair_logit_marginal_likelihood": (c_int, [P, c_int, c_double, c_double, P, c_int, P, P, c_double, c_int, P, P]),
+    "flgp_eigenpair_posterior_classification": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_double,
+                                                        c_int, P, P]),
     "flgp_eigenpair_free": (None, [P]),
     "flgp_kmeans_minibatch": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, ctypes.c_ulonglong, P, P, P]),
     "flgp_kmeans_lloyd": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
@@ -101,6 +105,8 @@ _SIGNATURES = {
     "flgp_dev_u_recover": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, c_int, P, c_int, P, P]),
     "flgp_dev_hk": (c_int, [P, P, c_int, c_double, P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int,
                             P, c_int, P]),
+    "flgp_dev_cholesky": (c_int, [P, P, c_int, c_int, P]),
+    "flgp_dev_chol_solve": (c_int, [P, P, c_int, P, c_int, c_int, P]),
     "flgp_dev_gemm": (c_int, [P, c_int, c_int, c_int, c_double, P, c_long, c_long, P, c_long, c_long,
                               c_double, P, c_long, c_long, P, c_long, c_long, P, c_size_t]),
     "flgp_dev_rotate": (c_int, [P, c_int, c_int, c_double, P, P, P, c_double, P, P, P]),

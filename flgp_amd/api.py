@@ -175,6 +175,31 @@ def HK_from_spectrum_cpp(eigenpair, K, t, idx0, idx1):
     return H
 
 
+def marginal_log_likelihood_logit_la_cpp(C, Y, N, tol=1e-5, max_iter=100, return_iters=False):
+    """marginal_log_likelihood_logit_la_cpp (src/train.cpp:716-760; defaults src/train.h:35-36): the Laplace-approximate
+    log marginal likelihood of the binomial logit GP with covariance C (m x m), Y successes of N trials per row.  Newton's
+    loop and its Cholesky factorisations run on the device.  ``return_iters``: also return the Newton iterations run."""
+    C = _f64(C, "C")
+    m = C.shape[0]
+    if C.shape != (m, m):
+        raise ValueError("C must be square")
+    Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+    N = np.ascontiguousarray(np.broadcast_to(np.asarray(N, dtype=np.float64), (m,)))
+    if Y.size != m:
+        raise ValueError("Y must have one entry per row of C")
+    amll = ctypes.c_double(); it = ctypes.c_int()
+    check(_lib.lib().flgp_logit_la_marginal_likelihood(_ptr(C), m, _ptr(Y), _ptr(N), float(tol), int(max_iter),
+                                                       ctypes.byref(amll), ctypes.byref(it)))
+    return (amll.value, it.value) if return_iters else amll.value
+
+
+def multi_train_split(Y):
+    """multi_train_split (src/MultiClassification.cpp:14-26): one 0/1 column per class 0 .. max(Y)."""
+    Y = np.asarray(Y).reshape(-1)
+    J = int(Y.max()) + 1
+    return (Y[:, None] == np.arange(J)[None, :]).astype(np.float64)
+
+
 class ResidentEigenPair:
     """An ``EigenPair`` that stays in HBM (include/flgp_hip.h, "device-resident EigenPair"): what the training
     loop needs, since it calls ``HK_from_spectrum_cpp`` with the same pair and a new ``t`` on every objective
@@ -251,6 +276,53 @@ class ResidentEigenPair:
         check(_lib.lib().flgp_eigenpair_posterior_variance(self._h, int(K), _ptr(idx0), idx0.size, _ptr(idx1), idx1.size,
                                                            float(pars[0]), float(pars[1]), float(sigma), _ptr(out)))
         return out
+
+    def marginal_log_likelihood_logit_la(self, K, t, idx, Y, N=None, sigma=1e-3, tol=1e-5, max_iter=100, return_iters=False):
+        """The objective of the logit drivers' hyper-parameter search (negative_marginal_likelihood_logit_cpp,
+        src/train.cpp:28-34, negated back): ``marginal_log_likelihood_logit_la_cpp(HK(idx, idx) + sigma I, Y, N)`` with C
+        built on the device from the resident V; only the scalar comes back.  N defaults to one trial per row (what the
+        drivers pass, src/Fit.cpp:553 and src/MultiClassification.cpp:36); sigma's default is the R wrappers' (R/Fit.R)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        m = idx.size
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        N = np.ones(m) if N is None else np.ascontiguousarray(np.broadcast_to(np.asarray(N, dtype=np.float64), (m,)))
+        if Y.size != m:
+            raise ValueError("Y must have one entry per row of idx")
+        amll = ctypes.c_double(); it = ctypes.c_int()
+        check(_lib.lib().flgp_eigenpair_logit_marginal_likelihood(self._h, int(K), float(t), float(sigma), _ptr(idx), m, _ptr(Y),
+                                                                  _ptr(N), float(tol), int(max_iter), ctypes.byref(amll),
+                                                                  ctypes.byref(it)))
+        return (amll.value, it.value) if return_iters else amll.value
+
+    def posterior_distribution_classification(self, idx0, idx1, K, t, Y, sigma11, sigma22, tol=1e-5, max_iter=100):
+        """posterior_distribution_classification (src/Utils.cpp:252-299; defaults src/Utils.h:80) with
+        C11 = HK(idx0, idx0) + sigma11 I, C21 = HK(idx1, idx0), C22 = diag HK(idx1, idx1) + sigma22: the binary drivers
+        pass sigma11 = sigma22 = sigma (src/Fit.cpp:571-583), the one-vs-rest route sigma11 = 0 (src/Utils.cpp:357-360).
+        Returns {"mean", "cov"} for the rows idx1; C21 is never formed (include/flgp_hip.h)."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        if Y.size != idx0.size:
+            raise ValueError("Y must have one entry per row of idx0")
+        mean = np.zeros(idx1.size); cov = np.zeros(idx1.size)
+        check(_lib.lib().flgp_eigenpair_posterior_classification(self._h, int(K), float(t), float(sigma11), float(sigma22),
+                                                                 _ptr(idx0), idx0.size, _ptr(Y), _ptr(idx1), idx1.size, float(tol),
+                                                                 int(max_iter), _ptr(mean), _ptr(cov)))
+        return {"mean": mean, "cov": cov}
+
+    def posterior_distribution_multiclassification(self, idx0, idx1, K, ts, Y, sigma, tol=1e-5, max_iter=100):
+        """posterior_distribution_multiclassification (src/Utils.cpp:336-369): one-vs-rest over the J = max(Y) + 1 classes
+        of ``multi_train_split(Y)``, class j at its own ``ts[j]``, sigma on C22 only.  Returns {"mean", "cov"}, m_new x J."""
+        aug_y = multi_train_split(Y)
+        J = aug_y.shape[1]
+        ts = np.asarray(ts, dtype=np.float64).reshape(-1)
+        if ts.size != J:
+            raise ValueError(f"need one t per class: {J} classes, {ts.size} values of t")
+        idx1 = np.asarray(idx1)
+        mean = np.zeros((idx1.size, J), order="F"); cov = np.zeros((idx1.size, J), order="F")
+        for j in range(J):
+            post = self.posterior_distribution_classification(idx0, idx1, K, ts[j], aug_y[:, j], 0.0, sigma, tol, max_iter)
+            mean[:, j] = post["mean"]; cov[:, j] = post["cov"]
+        return {"mean": mean, "cov": cov}
 
     def to_host(self):
         values = np.zeros(self.K); vectors = np.zeros((self.n, self.K), order="F")

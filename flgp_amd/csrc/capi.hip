@@ -1187,6 +1187,129 @@ extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K
   return G.verdict(st.s, "posterior_variance");
 }
 
+// ---- classification consumers: the Laplace approximation of the logit GP on the device (gpc.hip) ---------
+namespace {
+int check_labels(const double *Y, const double *N, int m, const char *who) {
+  for (int a = 0; a < m; ++a) {
+    const double n = N ? N[a] : 1.0;
+    FLGP_REQUIRE(n > 0.0 && n < HUGE_VAL, "%s: N[%d]=%g must be positive", who, a, n);
+    FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] <= n, "%s: Y[%d]=%g is outside [0, N[%d]=%g]", who, a, Y[a], a, n);
+  }
+  return FLGP_OK;
+}
+// Newton loop + final sums on the device-resident C (m x m); only the scalar comes down
+int logit_la_on_device(hipStream_t st, const double *dC, int m, const double *Y, const double *N, double tol, int max_iter,
+                       double *amll, int *iters, const char *who) {
+  DevBuf dY, dN;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(dN.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st));
+  FLGP_TRY(h2d(dN.p, N, sizeof(double) * (size_t)m, st));
+  GpcNewton S;
+  FLGP_TRY(S.alloc(m));
+  int it = 0;
+  FLGP_TRY(S.run(st, dC, dY.as<double>(), dN.as<double>(), tol, max_iter, who, &it));
+  if (iters) *iters = it;
+  return S.amll(st, dY.as<double>(), dN.as<double>(), amll);
+}
+}  // namespace
+
+extern "C" int flgp_logit_la_marginal_likelihood(const double *C, int m, const double *Y, const double *N, double tol,
+                                                 int max_iter, double *amll, int *iters) {
+  FLGP_REQUIRE(C && Y && N && amll, "logit_la_marginal_likelihood: null pointer");
+  FLGP_REQUIRE(m >= 1 && max_iter >= 1, "logit_la_marginal_likelihood: bad shape (m=%d max_iter=%d)", m, max_iter);
+  FLGP_TRY(check_labels(Y, N, m, "logit_la_marginal_likelihood"));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dC;
+  FLGP_TRY(dC.alloc(sizeof(double) * (size_t)m * m));
+  FLGP_TRY(h2d(dC.p, C, sizeof(double) * (size_t)m * m, st.s));
+  return logit_la_on_device(st.s, dC.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_la_marginal_likelihood");
+}
+
+extern "C" int flgp_eigenpair_logit_marginal_likelihood(const flgp_eigenpair *ep, int K, double t, double sigma, const int *idx,
+                                                        int m, const double *Y, const double *N, double tol, int max_iter,
+                                                        double *amll, int *iters) {
+  FLGP_REQUIRE(ep && idx && Y && N && amll, "logit_marginal_likelihood: null pointer");
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1, "logit_marginal_likelihood: bad shape (K=%d of %d, m=%d, max_iter=%d)",
+               K, ep->K, m, max_iter);
+  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx[a] >= 0 && idx[a] < ep->n, "logit_marginal_likelihood: idx[%d]=%d out of range", a, idx[a]);
+  FLGP_TRY(check_labels(Y, N, m, "logit_marginal_likelihood"));
+  Stream st;
+  FLGP_TRY(st.create());
+  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
+  // C = HK(idx, idx) + sigma I       (src/train.cpp:30-31)
+  DevBuf i0, C, work;
+  const int *d0; int r0;
+  FLGP_TRY(upload_idx(st.s, idx, m, i0, &d0, &r0));
+  FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
+  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
+  FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
+  FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, sigma));
+  return logit_la_on_device(st.s, C.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_marginal_likelihood");
+}
+
+// posterior_distribution_classification (src/Utils.cpp:252-299) with C11 = HK(idx0, idx0) + sigma11 I,
+// C21 = HK(idx1, idx0) = V2 L V1^T, C22 = rowsum(V2 L .* V2) + sigma22.  mean = V2 L V1^T (Y - pi);
+// var_i = C22_i - v2_i^T M v2_i with M = X^T X, X = L_B^-1 sqrt(W) V1 L: O(m_new K^2), C21 is never formed.
+extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
+                                                       const int *idx0, int m, const double *Y, const int *idx1, int mnew,
+                                                       double tol, int max_iter, double *mean, double *cov) {
+  const char *who = "posterior_classification";
+  FLGP_REQUIRE(ep && idx0 && idx1 && Y && mean && cov, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && max_iter >= 1,
+               "%s: bad shape (K=%d of %d, m=%d, m_new=%d, max_iter=%d)", who, K, ep->K, m, mnew, max_iter);
+  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < ep->n, "%s: idx0[%d]=%d out of range", who, a, idx0[a]);
+  for (int a = 0; a < mnew; ++a) FLGP_REQUIRE(idx1[a] >= 0 && idx1[a] < ep->n, "%s: idx1[%d]=%d out of range", who, a, idx1[a]);
+  FLGP_TRY(check_labels(Y, nullptr, m, who));
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));                    // G.l = exp(-t (1 - values))
+  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
+  DevBuf i0, C, work, dY;
+  const int *d0; int r0;
+  FLGP_TRY(upload_idx(st.s, idx0, m, i0, &d0, &r0));
+  FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
+  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
+  FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
+  if (sigma11 != 0.0) FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, sigma11));
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
+  // the mode (N = 1), then B factored again at the final f          (src/Utils.cpp:268-293)
+  GpcNewton S;
+  FLGP_TRY(S.alloc(m));
+  int it = 0;
+  FLGP_TRY(S.run(st.s, C.as<double>(), dY.as<double>(), nullptr, tol, max_iter, who, &it));
+  FLGP_TRY(S.weights(st.s, C.as<double>(), dY.as<double>(), nullptr));
+  GatheredV g0, g1;
+  FLGP_TRY(gather_v(st.s, ep, K, idx0, m, g0));
+  FLGP_TRY(gather_v(st.s, ep, K, idx1, mnew, g1));
+  DevBuf X, Mp, u, Wp, out, gw;
+  const size_t we = (size_t)128 * K * K + 1024;
+  FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
+  FLGP_TRY(Mp.alloc(sizeof(double) * (size_t)K * (K + 1)));
+  FLGP_TRY(u.alloc(sizeof(double) * (size_t)K));
+  FLGP_TRY(Wp.alloc(sizeof(double) * (size_t)mnew * (K + 1)));
+  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_TRY(gw.alloc(sizeof(double) * we));
+  FLGP_TRY(gpc_scale2(st.s, g0.V, g0.ld, S.sW.as<double>(), G.l.as<double>(), m, K, X.as<double>()));     // sqrt(W) V1 L
+  FLGP_TRY(chol_trsv(st.s, S.B.as<double>(), m, m, X.as<double>(), m, K, 1, S.flag.as<int>()));         // L_B^-1 (.)
+  FLGP_TRY(gemm_launch(st.s, K, K, m, 1.0, X.as<double>(), m, 1, X.as<double>(), 1, m, 0.0, nullptr, 0, 0, Mp.as<double>(), 1, K,
+                       gw.as<double>(), we, 0.0, nullptr));                                                  // M = X^T X
+  FLGP_TRY(gemm_launch(st.s, K, 1, m, 1.0, g0.V, g0.ld, 1, S.resid.as<double>(), 1, m, 0.0, nullptr, 0, 0, u.as<double>(), 1, K,
+                       gw.as<double>(), we, 0.0, nullptr));                                                  // V1^T (Y - pi)
+  FLGP_TRY(gpr_scale(st.s, u.as<double>(), G.l.as<double>(), nullptr, K, 1, Mp.as<double>() + (size_t)K * K));  // column K: L (.)
+  FLGP_TRY(gemm_launch(st.s, mnew, K + 1, K, 1.0, g1.V, 1, g1.ld, Mp.as<double>(), 1, K, 0.0, nullptr, 0, 0, Wp.as<double>(), 1,
+                       mnew, nullptr, 0, 0.0, nullptr));                                                     // V2 [M | u]
+  FLGP_TRY(gpr_rowquad(st.s, g1.V, g1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, out.as<double>()));
+  FLGP_TRY(d2h(mean, Wp.as<double>() + (size_t)K * mnew, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
+  int bad = 0;
+  FLGP_HIP(hipMemcpyAsync(&bad, S.flag.p, sizeof(int), hipMemcpyDeviceToHost, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return GpcNewton::pivot_error(bad, who, 0);      // the loop checked its own factorisations: this is the one at the mode
+}
+
 extern "C" void flgp_eigenpair_free(flgp_eigenpair *ep) { delete ep; }
 
 extern "C" int flgp_heat_kernel_spectrum(const double *X_all, int n, int d, const double *U, int s, int ucols,

@@ -175,6 +175,25 @@ int gpr_rowquad(hipStream_t st, const double *dV2, long ld2, const double *dW, i
 int gpr_rowdot(hipStream_t st, const double *dC21, const double *dAl, int mnew, int m, const double *dV2, long ld2, int K,
                const double *d_l, double c, double *d_cov);
 
+// Laplace approximation of the logit GP on the device (gpc.hip)
+int chol_blocked(hipStream_t st, double *dA, long lda, int m, int *d_flag);       // flag: first bad pivot + 1
+// mode bit 0: L y = b, bit 1: L^T x = y; one workgroup per right-hand side
+int chol_trsv(hipStream_t st, const double *dL, long lda, int m, double *dB, long ldb, int nrhs, int mode, const int *d_flag);
+int chol_logdet(hipStream_t st, const double *dL, long lda, int m, double *d_out);
+int gpc_scale2(hipStream_t st, const double *dM, long ldm, const double *d_a, const double *d_b, int rows, int cols, double *d_out);
+// The state of one Newton loop (GPML Alg. 3.1) on an m x m covariance C.  dN = nullptr: the posterior's N = 1 form.
+struct GpcNewton {
+  DevBuf B, f, fnew, sW, b, a, r, resid, scal, flag;
+  int m = 0;
+  int alloc(int m_);
+  // pi, sqrt(W), b (and resid = Y - pi) from f; B = sW C sW + I factored in place
+  int weights(hipStream_t st, const double *dC, const double *dY, const double *dN);
+  int run(hipStream_t st, const double *dC, const double *dY, const double *dN, double tol, int max_iter, const char *who,
+          int *iters);
+  int amll(hipStream_t st, const double *dY, const double *dN, double *out);   // synchronises
+  static int pivot_error(int bad, const char *who, int iter);   // iter 0: the factorisation at the final f
+};
+
 // host wait for a stream that polls an event instead of sleeping in hipStreamSynchronize (eig.hip)
 hipError_t stream_wait(hipStream_t st);
 

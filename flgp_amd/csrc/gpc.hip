@@ -1,0 +1,405 @@
+// The classification consumers of an EigenPair, on the device: the Laplace approximation of the logit GP.
+//   marginal_log_likelihood_logit_la_cpp (reference src/train.cpp:716-760): Newton's method for the posterior mode
+//     (GPML Alg. 3.1) with one m x m Cholesky factorisation per iteration, then the approximate marginal likelihood;
+//   posterior_distribution_classification (src/Utils.cpp:252-299): the same loop with N = 1, then the predictive mean and
+//     variance (Alg. 3.2) in the low-rank form C21 = V2 L V1^T, never forming the m_new x m matrix C21.
+// The Newton loop factors an m x m matrix (m = 1000 at BASELINE configs[2]) every iteration, so the factorisation here is
+// blocked and right-looking: a 64-column diagonal panel factored in the registers of one wave, the panel column solved
+// by a grid of waves, the trailing update through the MFMA GEMM.  gpr.hip's one-workgroup chol_solve stays as it is for
+// the regression entries (their bits do not change).  Everything is fixed-order: two calls give the same bits.
+#include "common.h"
+
+namespace flgp {
+
+constexpr int CNB = 64;   // panel width = one wave
+
+__device__ __forceinline__ double readlane_d(double x, int l) {
+  const long long v = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_readlane((int)v, l);
+  const int hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+
+// Lower Cholesky factor of the diagonal block A(k0:k0+nb, k0:k0+nb) in place, one wave: lane i holds row i of the block
+// in registers (rows past nb are padded with the identity), column j's pivot and multipliers are read across lanes with
+// readlane.  flag[0] = (global index + 1) of the first pivot that is not positive; a set flag turns later steps off.
+__global__ __launch_bounds__(64) void chol_panel_kernel(double *__restrict__ A, long lda, int m, int k0, int *__restrict__ flag) {
+  if (flag[0]) return;
+  const int lane = threadIdx.x;
+  const int nb = min(CNB, m - k0);
+  double r[CNB];
+#pragma unroll
+  for (int k = 0; k < CNB; ++k) {
+    double v = (lane >= nb && k == lane) ? 1.0 : 0.0;
+    if (lane < nb && k <= lane) v = A[(size_t)(k0 + k) * lda + k0 + lane];
+    r[k] = v;
+  }
+  int bad = 0;
+#pragma unroll
+  for (int j = 0; j < CNB; ++j) {
+    double d = readlane_d(r[j], j);
+    if (!(d > 0.0)) {
+      if (!bad) bad = k0 + j + 1;
+      d = 1.0;
+    }
+    const double ljj = __builtin_sqrt(d);
+    const double lij = lane > j ? r[j] / ljj : (lane == j ? ljj : r[j]);
+    r[j] = lij;
+#pragma unroll
+    for (int k = j + 1; k < CNB; ++k) {
+      const double lkj = readlane_d(lij, k);
+      if (lane >= k) r[k] -= lij * lkj;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < CNB; ++k)
+    if (lane < nb && k <= lane) A[(size_t)(k0 + k) * lda + k0 + lane] = r[k];
+  if (bad && lane == 0) flag[0] = bad;
+}
+
+// Panel column: L21 = A21 L11^-T for the rows below the diagonal block, a thread per row (x L11^T = a by forward
+// substitution), L11 in LDS (identity-padded past nb; every lane reads the same element: a broadcast), the row's
+// unknowns in LDS as well (a register array of 64 unrolled twice over spills).
+__global__ __launch_bounds__(64) void chol_trsm_kernel(double *__restrict__ A, long lda, int m, int k0, const int *__restrict__ flag) {
+  if (flag[0]) return;
+  __shared__ double Ls[CNB][CNB];   // Ls[k][j] = L11(j, k)
+  __shared__ double xs[CNB][64];    // xs[j][lane] = x_j of this lane's row
+  const int tid = threadIdx.x;
+  const int nb = min(CNB, m - k0);
+  for (int e = tid; e < CNB * CNB; e += 64) {
+    const int j = e % CNB, k = e / CNB;
+    double v = (j == k) ? 1.0 : 0.0;
+    if (j < nb && k <= j) v = A[(size_t)(k0 + k) * lda + k0 + j];
+    Ls[k][j] = v;
+  }
+  __syncthreads();
+  const int i = k0 + nb + blockIdx.x * 64 + tid;
+  if (i >= m) return;
+  for (int j = 0; j < nb; ++j) {
+    double acc = A[(size_t)(k0 + j) * lda + i];
+    for (int k = 0; k < j; ++k) acc -= xs[k][tid] * Ls[k][j];
+    acc = acc / Ls[j][j];
+    xs[j][tid] = acc;
+    A[(size_t)(k0 + j) * lda + i] = acc;
+  }
+}
+
+// In-place lower Cholesky factor of the SPD m x m matrix A (column-major, leading dimension lda).  Only the lower triangle
+// is read and only the lower triangle of the result is the factor (the trailing GEMM also rewrites the upper one).
+int chol_blocked(hipStream_t st, double *dA, long lda, int m, int *d_flag) {
+  ProfScope ps("chol_blocked", st, (double)m * m * m / 3.0);
+  for (int k0 = 0; k0 < m; k0 += CNB) {
+    const int nb = std::min(CNB, m - k0), rem = m - k0 - nb;
+    hipLaunchKernelGGL(chol_panel_kernel, dim3(1), dim3(64), 0, st, dA, lda, m, k0, d_flag);
+    FLGP_TRY(check_launch("chol_panel_kernel"));
+    if (rem <= 0) break;
+    hipLaunchKernelGGL(chol_trsm_kernel, dim3(ceil_div(rem, 64)), dim3(64), 0, st, dA, lda, m, k0, d_flag);
+    FLGP_TRY(check_launch("chol_trsm_kernel"));
+    // A22 <- A22 - L21 L21^T
+    const double *L21 = dA + (size_t)k0 * lda + k0 + nb;
+    double *A22 = dA + (size_t)(k0 + nb) * lda + k0 + nb;
+    FLGP_TRY(gemm_launch(st, rem, rem, nb, -1.0, L21, 1, lda, L21, lda, 1, 1.0, A22, 1, lda, A22, 1, lda, nullptr, 0, 0.0,
+                         nullptr));
+  }
+  return FLGP_OK;
+}
+
+// Triangular solves with the factor chol_blocked left in L, one workgroup per right-hand side (column c of B, leading
+// dimension ldb), in place: mode bit 0 solves L y = b, bit 1 then L^T x = y.  Blocks of 64 unknowns: the triangle of a
+// block is solved by one wave in registers, the rest of the rows by the whole workgroup (forward: an axpy per row,
+// backward: a dot product along a column of L per row, reduced in a fixed order).
+__global__ __launch_bounds__(256) void chol_trsv_kernel(const double *__restrict__ L, long lda, int m, double *__restrict__ B,
+                                                        long ldb, int mode, const int *__restrict__ flag) {
+  if (flag[0]) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double *b = B + (size_t)blockIdx.x * ldb;
+  __shared__ double ys[CNB];
+  if (mode & 1) {
+    for (int b0 = 0; b0 < m; b0 += CNB) {
+      const int nb = min(CNB, m - b0);
+      if (wave == 0) {
+        double yi = lane < nb ? b[b0 + lane] : 0.0;
+#pragma unroll
+        for (int j = 0; j < CNB; ++j) {
+          if (j < nb) {
+            const double yj = readlane_d(yi, j) / L[(size_t)(b0 + j) * lda + b0 + j];
+            if (lane == j) yi = yj;
+            if (lane > j && lane < nb) yi -= L[(size_t)(b0 + j) * lda + b0 + lane] * yj;
+          }
+        }
+        if (lane < nb) b[b0 + lane] = yi;
+        ys[lane] = yi;
+      }
+      __syncthreads();
+      for (int i = b0 + nb + tid; i < m; i += 256) {
+        double acc = b[i];
+        for (int j = 0; j < nb; ++j) acc -= L[(size_t)(b0 + j) * lda + i] * ys[j];
+        b[i] = acc;
+      }
+      __syncthreads();
+    }
+  }
+  if (mode & 2) {
+    for (int b0 = ((m - 1) / CNB) * CNB; b0 >= 0; b0 -= CNB) {
+      const int nb = min(CNB, m - b0), e = b0 + nb;
+      for (int rr = wave; rr < nb; rr += 4) {
+        const double *li = L + (size_t)(b0 + rr) * lda;   // column b0+rr of L = row b0+rr of L^T
+        double acc = 0.0;
+        for (int k = e + lane; k < m; k += 64) acc += li[k] * b[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (lane == 0) ys[rr] = acc;
+      }
+      __syncthreads();
+      if (wave == 0) {
+        double xi = lane < nb ? b[b0 + lane] - ys[lane] : 0.0;
+#pragma unroll
+        for (int j = CNB - 1; j >= 0; --j) {
+          if (j < nb) {
+            const double xj = readlane_d(xi, j) / L[(size_t)(b0 + j) * lda + b0 + j];
+            if (lane == j) xi = xj;
+            if (lane < j) xi -= L[(size_t)(b0 + lane) * lda + b0 + j] * xj;
+          }
+        }
+        if (lane < nb) b[b0 + lane] = xi;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+int chol_trsv(hipStream_t st, const double *dL, long lda, int m, double *dB, long ldb, int nrhs, int mode, const int *d_flag) {
+  if (nrhs <= 0) return FLGP_OK;
+  hipLaunchKernelGGL(chol_trsv_kernel, dim3(nrhs), dim3(256), 0, st, dL, lda, m, dB, ldb, mode, d_flag);
+  return check_launch("chol_trsv_kernel");
+}
+
+// sum(log(L_ii + 1e-9)) in a fixed order (one workgroup)
+__device__ __forceinline__ double block_sum_1024(double v, double *red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int off = 512; off > 0; off >>= 1) {
+    if (tid < off) red[tid] += red[tid + off];
+    __syncthreads();
+  }
+  const double s = red[0];
+  __syncthreads();
+  return s;
+}
+
+__global__ __launch_bounds__(1024) void chol_logdet_kernel(const double *__restrict__ L, long lda, int m, double *__restrict__ out) {
+  __shared__ double red[1024];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < m; i += 1024) s += log(L[(size_t)i * lda + i] + 1e-9);
+  s = block_sum_1024(s, red);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+int chol_logdet(hipStream_t st, const double *dL, long lda, int m, double *d_out) {
+  hipLaunchKernelGGL(chol_logdet_kernel, dim3(1), dim3(1024), 0, st, dL, lda, m, d_out);
+  return check_launch("chol_logdet_kernel");
+}
+
+// ---- Newton's method for the posterior mode (GPML Alg. 3.1) ----------------------------------------------------------
+
+// pi = 1 / (1 + exp(-f)); with N (marginal likelihood, src/train.cpp:737-743): W = N pi (1 - pi),
+// b = W f + Y (1 - pi) + (N - Y)(-pi); without (posterior, src/Utils.cpp:269-276): W = pi (1 - pi), b = W f + (Y - pi).
+// sW = sqrt(W); resid (optional) = Y - pi.
+__global__ void gpc_w_kernel(const double *__restrict__ f, const double *__restrict__ Y, const double *__restrict__ N, int m,
+                             double *__restrict__ sW, double *__restrict__ b, double *__restrict__ resid) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const double fi = f[i], yi = Y[i];
+  const double pi = 1.0 / (1.0 + exp(-fi));
+  double W, bi;
+  if (N) {
+    const double ni = N[i];
+    W = ni * pi * (1.0 - pi);
+    bi = W * fi + yi * (1.0 - pi) + (ni - yi) * (-pi);
+  } else {
+    W = pi * (1.0 - pi);
+    bi = W * fi + (yi - pi);
+  }
+  sW[i] = __builtin_sqrt(W);
+  if (b) b[i] = bi;
+  if (resid) resid[i] = yi - pi;
+}
+
+// B = sW C sW + I   (column-major m x m)
+__global__ void gpc_b_kernel(const double *__restrict__ C, const double *__restrict__ sW, int m, double *__restrict__ B) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)m * m) return;
+  const int i = (int)(e % m), j = (int)(e / m);
+  B[e] = sW[i] * C[e] * sW[j] + (i == j ? 1.0 : 0.0);
+}
+
+// y = s .* (C x) (s optional), C m x m column-major: 64 rows per workgroup, the columns split over 16 waves, the 16
+// partial sums added in a fixed order
+__global__ __launch_bounds__(1024) void gpc_gemv_kernel(const double *__restrict__ C, int m, const double *__restrict__ x,
+                                                        const double *__restrict__ s, double *__restrict__ y) {
+  __shared__ double part[16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + lane;
+  const int chunk = (m + 15) / 16, k0 = wave * chunk, k1 = min(m, k0 + chunk);
+  double acc = 0.0;
+  if (i < m)
+    for (int k = k0; k < k1; ++k) acc += C[(size_t)k * m + i] * x[k];
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && i < m) {
+    double t = 0.0;
+    for (int w = 0; w < 16; ++w) t += part[w][lane];
+    y[i] = s ? s[i] * t : t;
+  }
+}
+
+// a = b - sW .* r
+__global__ void gpc_a_kernel(const double *__restrict__ b, const double *__restrict__ sW, const double *__restrict__ r, int m,
+                             double *__restrict__ a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) a[i] = b[i] - sW[i] * r[i];
+}
+
+// diff = |f - f_new|_1 (fixed order), then f <- f_new
+__global__ __launch_bounds__(1024) void gpc_step_kernel(double *__restrict__ f, const double *__restrict__ fnew, int m,
+                                                        double *__restrict__ diff) {
+  __shared__ double red[1024];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < m; i += 1024) {
+    const double fn = fnew[i];
+    s += __builtin_fabs(f[i] - fn);
+    f[i] = fn;
+  }
+  s = block_sum_1024(s, red);
+  if (threadIdx.x == 0) diff[0] = s;
+}
+
+// amll = -0.5 sum(a f) + (sum(Y log pi) + sum((N - Y) log(1 - pi))) - sum(log(L_ii + 1e-9))   (src/train.cpp:753-757)
+__global__ __launch_bounds__(1024) void gpc_amll_kernel(const double *__restrict__ f, const double *__restrict__ a,
+                                                        const double *__restrict__ Y, const double *__restrict__ N,
+                                                        const double *__restrict__ L, long lda, int m, double *__restrict__ out) {
+  __shared__ double red[1024];
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+  for (int i = threadIdx.x; i < m; i += 1024) {
+    const double pi = 1.0 / (1.0 + exp(-f[i]));
+    s1 += a[i] * f[i];
+    s2 += Y[i] * log(pi);
+    s3 += (N[i] - Y[i]) * log(1.0 - pi);
+    s4 += log(L[(size_t)i * lda + i] + 1e-9);
+  }
+  s1 = block_sum_1024(s1, red);
+  s2 = block_sum_1024(s2, red);
+  s3 = block_sum_1024(s3, red);
+  s4 = block_sum_1024(s4, red);
+  if (threadIdx.x == 0) {
+    double amll = -0.5 * s1;
+    amll += s2 + s3;
+    amll -= s4;
+    out[0] = amll;
+  }
+}
+
+// out(i, j) = a(i) * M(i, j) * b(j): M rows x cols with leading dimension ldm, out contiguous
+__global__ void gpc_scale2_kernel(const double *__restrict__ M, long ldm, const double *__restrict__ a, const double *__restrict__ b,
+                                  int rows, int cols, double *__restrict__ out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)rows * cols) return;
+  const int i = (int)(e % rows), j = (int)(e / rows);
+  out[e] = a[i] * M[(size_t)j * ldm + i] * b[j];
+}
+
+int gpc_scale2(hipStream_t st, const double *dM, long ldm, const double *d_a, const double *d_b, int rows, int cols, double *d_out) {
+  hipLaunchKernelGGL(gpc_scale2_kernel, dim3(ceil_div((long)rows * cols, 256)), dim3(256), 0, st, dM, ldm, d_a, d_b, rows, cols, d_out);
+  return check_launch("gpc_scale2_kernel");
+}
+
+int GpcNewton::alloc(int m_) {
+  m = m_;
+  const size_t v = sizeof(double) * (size_t)m;
+  FLGP_TRY(B.alloc(v * m));
+  FLGP_TRY(f.alloc(v)); FLGP_TRY(fnew.alloc(v)); FLGP_TRY(sW.alloc(v)); FLGP_TRY(b.alloc(v));
+  FLGP_TRY(a.alloc(v)); FLGP_TRY(r.alloc(v)); FLGP_TRY(resid.alloc(v));
+  FLGP_TRY(scal.alloc(sizeof(double) * 4)); FLGP_TRY(flag.alloc(sizeof(int)));
+  return FLGP_OK;
+}
+
+int GpcNewton::weights(hipStream_t st, const double *dC, const double *dY, const double *dN) {
+  hipLaunchKernelGGL(gpc_w_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, f.as<double>(), dY, dN, m, sW.as<double>(),
+                     b.as<double>(), resid.as<double>());
+  FLGP_TRY(check_launch("gpc_w_kernel"));
+  hipLaunchKernelGGL(gpc_b_kernel, dim3(ceil_div((long)m * m, 256)), dim3(256), 0, st, dC, sW.as<double>(), m, B.as<double>());
+  FLGP_TRY(check_launch("gpc_b_kernel"));
+  return chol_blocked(st, B.as<double>(), m, m, flag.as<int>());
+}
+
+// Alg. 3.1 from f = 0.  The host reads |f - f_new|_1 and the pivot flag back after every iteration (8 + 4 bytes) and
+// decides; the loop's state never leaves the device.  Afterwards B holds the factor and a the vector of the LAST
+// iteration, f the final mode -- what the reference's final sums use (src/train.cpp:753-757).
+int GpcNewton::run(hipStream_t st, const double *dC, const double *dY, const double *dN, double tol, int max_iter,
+                   const char *who, int *iters) {
+  FLGP_HIP(hipMemsetAsync(f.p, 0, sizeof(double) * (size_t)m, st));
+  FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+  *iters = 0;
+  for (int it = 0; it < max_iter; ++it) {
+    {
+      ProfScope ps("logit_la_newton_iter", st, 0.0);      // the device time of one iteration, without the host's read-back
+      FLGP_TRY(weights(st, dC, dY, dN));
+      hipLaunchKernelGGL(gpc_gemv_kernel, dim3(ceil_div(m, 64)), dim3(1024), 0, st, dC, m, b.as<double>(), sW.as<double>(), r.as<double>());
+      FLGP_TRY(check_launch("gpc_gemv_kernel"));                                                  // sW (C b)
+      FLGP_TRY(chol_trsv(st, B.as<double>(), m, m, r.as<double>(), m, 1, 3, flag.as<int>()));      // B^-1 (.)
+      hipLaunchKernelGGL(gpc_a_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, b.as<double>(), sW.as<double>(), r.as<double>(), m,
+                         a.as<double>());
+      FLGP_TRY(check_launch("gpc_a_kernel"));
+      hipLaunchKernelGGL(gpc_gemv_kernel, dim3(ceil_div(m, 64)), dim3(1024), 0, st, dC, m, a.as<double>(), (const double *)nullptr,
+                         fnew.as<double>());
+      FLGP_TRY(check_launch("gpc_gemv_kernel"));                                                  // f_new = C a
+      hipLaunchKernelGGL(gpc_step_kernel, dim3(1), dim3(1024), 0, st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
+      FLGP_TRY(check_launch("gpc_step_kernel"));
+    }
+    double diff = 0.0;
+    int bad = 0;
+    FLGP_HIP(hipMemcpyAsync(&diff, scal.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    FLGP_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    FLGP_HIP(hipStreamSynchronize(st));
+    *iters = it + 1;
+    FLGP_TRY(pivot_error(bad, who, it + 1));
+    if (diff < tol) break;
+  }
+  return FLGP_OK;
+}
+
+int GpcNewton::pivot_error(int bad, const char *who, int iter) {
+  if (!bad) return FLGP_OK;
+  if (iter > 0)
+    set_error("%s: B = sqrt(W) C sqrt(W) + I is not positive definite (Cholesky pivot %d <= 0 in Newton iteration %d)", who,
+              bad - 1, iter);
+  else
+    set_error("%s: B = sqrt(W) C sqrt(W) + I is not positive definite at the mode (Cholesky pivot %d <= 0)", who, bad - 1);
+  return FLGP_ERR_NOCONV;
+}
+
+int GpcNewton::amll(hipStream_t st, const double *dY, const double *dN, double *out) {
+  hipLaunchKernelGGL(gpc_amll_kernel, dim3(1), dim3(1024), 0, st, f.as<double>(), a.as<double>(), dY, dN, B.as<double>(), (long)m,
+                     m, scal.as<double>() + 1);
+  FLGP_TRY(check_launch("gpc_amll_kernel"));
+  FLGP_HIP(hipMemcpyAsync(out, scal.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, st));
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
+}
+
+}  // namespace flgp
+
+using namespace flgp;
+
+extern "C" int flgp_dev_cholesky(void *stream, double *d_A, int m, int single_workgroup, int *d_flag) {
+  FLGP_REQUIRE(d_A && d_flag && m >= 1, "cholesky: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (single_workgroup) return chol_solve(st, d_A, m, nullptr, 0, d_flag);
+  return chol_blocked(st, d_A, m, m, d_flag);
+}
+
+extern "C" int flgp_dev_chol_solve(void *stream, const double *d_L, int m, double *d_B, int nrhs, int mode, const int *d_flag) {
+  FLGP_REQUIRE(d_L && d_B && d_flag && m >= 1 && nrhs >= 0 && mode >= 1 && mode <= 3, "chol_solve: bad arguments");
+  return chol_trsv((hipStream_t)stream, d_L, m, m, d_B, m, nrhs, mode, d_flag);
+}
