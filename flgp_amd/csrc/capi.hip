@@ -58,12 +58,6 @@ extern "C" int flgp_dev_spectrum_usable(void *stream, const double *d_eig, int K
 
 namespace {
 
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() { if (s) (void)hipStreamDestroy(s); }
-  int create() { FLGP_HIP(hipStreamCreate(&s)); return FLGP_OK; }
-};
-
 int check_distance(const char *distance) {
   if (distance && !strcmp(distance, "Euclidean")) return FLGP_OK;
   // reference: Rcpp::stop("The distance method of KNN is not supported!\n"), src/Utils.cpp:123
@@ -108,22 +102,12 @@ struct InputCheck {
   // synchronises; FLGP_ERR_INVALID with the reason
   int verdict(hipStream_t st, const char *who) {
     int h = 0;
-    FLGP_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    FLGP_HIP(hipStreamSynchronize(st));
+    FLGP_TRY(read_flag(st, flag.p, &h));
     if (h & 1) { set_error("%s: the input holds NA / NaN / Inf values (the reference returns garbage here; this library refuses)", who); return FLGP_ERR_INVALID; }
     if (h & 2) { set_error("%s: a column index of the sparse matrix is outside [0, s)", who); return FLGP_ERR_INVALID; }
     return FLGP_OK;
   }
 };
-
-int h2d(void *dst, const void *src, size_t bytes, hipStream_t st) {
-  if (bytes) FLGP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
-  return FLGP_OK;
-}
-int d2h(void *dst, const void *src, size_t bytes, hipStream_t st) {
-  if (bytes) FLGP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-  return FLGP_OK;
-}
 
 // device-side state of one similarity matrix: anchors, k-NN, ELL (+ CSC view)
 struct Sim {
@@ -324,12 +308,6 @@ int parse_kernel(const char *kernel, int *se) {
   // the reference only prints and carries on with an empty Z (src/Spectrum.cpp:65-67); here it is an error
   set_error("The kernel type is not supported!");
   return FLGP_ERR_UNSUPPORTED;
-}
-
-bool is_range(const int *idx, int cnt) {
-  for (int i = 1; i < cnt; ++i)
-    if (idx[i] != idx[0] + i) return false;
-  return true;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -669,47 +647,11 @@ extern "C" int flgp_spectrum_from_Z(const int *csr_j, const double *csr_x, int n
   return FLGP_OK;
 }
 
-extern "C" int flgp_hk_from_spectrum(const double *values, const double *vectors, int n, int K, double t,
-                                     const int *idx0, int n0, const int *idx1, int n1, double *H) {
-  FLGP_REQUIRE(values && vectors && idx0 && idx1 && H, "HK_from_spectrum: null pointer");
-  FLGP_REQUIRE(n >= 1 && K >= 1 && n0 >= 0 && n1 >= 0, "HK_from_spectrum: bad shape");
-  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
-  if (n0 == 0 || n1 == 0) return FLGP_OK;
-  Stream st;
-  FLGP_TRY(st.create());
-  DevBuf dval, dvec, di0, di1, dH, work;
-  const bool r0 = is_range(idx0, n0), r1 = is_range(idx1, n1);
-  FLGP_TRY(dval.alloc(sizeof(double) * K));
-  FLGP_TRY(dvec.alloc(sizeof(double) * (size_t)n * K));
-  FLGP_TRY(dH.alloc(sizeof(double) * (size_t)n0 * n1));
-  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n0, n1, K, !r0)));
-  FLGP_TRY(h2d(dval.p, values, sizeof(double) * K, st.s));
-  FLGP_TRY(h2d(dvec.p, vectors, sizeof(double) * (size_t)n * K, st.s));
-  if (!r0) { FLGP_TRY(di0.alloc(sizeof(int) * n0)); FLGP_TRY(h2d(di0.p, idx0, sizeof(int) * n0, st.s)); }
-  if (!r1) { FLGP_TRY(di1.alloc(sizeof(int) * n1)); FLGP_TRY(h2d(di1.p, idx1, sizeof(int) * n1, st.s)); }
-  FLGP_TRY(flgp_dev_hk(st.s, dval.as<double>(), K, t, dvec.as<double>(), n, r0 ? nullptr : di0.as<int>(), r0 ? idx0[0] : 0,
-                       n0, dvec.as<double>(), n, r1 ? nullptr : di1.as<int>(), r1 ? idx1[0] : 0, n1, dH.as<double>(), n0,
-                       work.as<double>()));
-  FLGP_TRY(d2h(H, dH.p, sizeof(double) * (size_t)n0 * n1, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  return FLGP_OK;
-}
-
-// ---- device-resident EigenPair
-struct flgp_eigenpair {
-  DevBuf values, vectors;   // K, n x K column-major
-  int n = 0, K = 0, device = 0;
-};
-
-static int hk_on_device(hipStream_t st, const double *d_values, const double *d_vectors, int n, int K, double t,
-                        const int *idx0, int n0, const int *idx1, int n1, double *H) {
-  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
+// H (n0 x n1, host) = HK(idx0, idx1) of a pair on the device in one contraction and one copy; a row range is read in place
+static int hk_gathered_to_host(hipStream_t st, const double *d_values, const double *d_vectors, int n, int K, double t,
+                               const int *idx0, int n0, const int *idx1, int n1, double *H) {
   DevBuf di0, di1, dH, work;
   const bool r0 = is_range(idx0, n0), r1 = is_range(idx1, n1);
-  if (r0 && r1 && n0 > 0 && n1 > 0)     // the callers' usual case (LinSpaced ranges, src/Spectrum.cpp:38-39): pipelined
-    return hk_ranges_to_host(st, d_values, K, t, d_vectors, n, idx0[0], n0, idx1[0], n1, H);
   FLGP_TRY(dH.alloc(sizeof(double) * (size_t)n0 * n1));
   FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n0, n1, K, !r0)));
   if (!r0) { FLGP_TRY(di0.alloc(sizeof(int) * n0)); FLGP_TRY(h2d(di0.p, idx0, sizeof(int) * n0, st)); }
@@ -719,6 +661,32 @@ static int hk_on_device(hipStream_t st, const double *d_values, const double *d_
   FLGP_TRY(d2h(H, dH.p, sizeof(double) * (size_t)n0 * n1, st));
   FLGP_HIP(hipStreamSynchronize(st));
   return FLGP_OK;
+}
+
+extern "C" int flgp_hk_from_spectrum(const double *values, const double *vectors, int n, int K, double t,
+                                     const int *idx0, int n0, const int *idx1, int n1, double *H) {
+  FLGP_REQUIRE(values && vectors && idx0 && idx1 && H, "HK_from_spectrum: null pointer");
+  FLGP_REQUIRE(n >= 1 && K >= 1 && n0 >= 0 && n1 >= 0, "HK_from_spectrum: bad shape");
+  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
+  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
+  if (n0 == 0 || n1 == 0) return FLGP_OK;
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dval, dvec;
+  FLGP_TRY(dval.alloc(sizeof(double) * K));
+  FLGP_TRY(dvec.alloc(sizeof(double) * (size_t)n * K));
+  FLGP_TRY(h2d(dval.p, values, sizeof(double) * K, st.s));
+  FLGP_TRY(h2d(dvec.p, vectors, sizeof(double) * (size_t)n * K, st.s));
+  return hk_gathered_to_host(st.s, dval.as<double>(), dvec.as<double>(), n, K, t, idx0, n0, idx1, n1, H);
+}
+
+static int hk_on_device(hipStream_t st, const double *d_values, const double *d_vectors, int n, int K, double t,
+                        const int *idx0, int n0, const int *idx1, int n1, double *H) {
+  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
+  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
+  if (is_range(idx0, n0) && is_range(idx1, n1) && n0 > 0 && n1 > 0)   // the callers' usual case (LinSpaced ranges, src/Spectrum.cpp:38-39): pipelined
+    return hk_ranges_to_host(st, d_values, K, t, d_vectors, n, idx0[0], n0, idx1[0], n1, H);
+  return hk_gathered_to_host(st, d_values, d_vectors, n, K, t, idx0, n0, idx1, n1, H);
 }
 
 extern "C" int flgp_eigenpair_from_host(const double *values, const double *vectors, int n, int K, flgp_eigenpair **out) {
@@ -881,433 +849,6 @@ extern "C" int flgp_hk_from_eigenpair(const flgp_eigenpair *ep, int K, double t,
   Stream st;
   FLGP_TRY(st.create());
   return hk_on_device(st.s, (const double *)ep->values.p, (const double *)ep->vectors.p, ep->n, K, t, idx0, n0, idx1, n1, H);
-}
-
-// V = vectors[idx, 0:K] gathered into a dense m x K block on the device (a row range is used in place)
-struct GatheredV {
-  DevBuf buf, didx;
-  const double *V = nullptr;
-  long ld = 0;
-};
-static int gather_v(hipStream_t st, const flgp_eigenpair *ep, int K, const int *idx, int m, GatheredV &g) {
-  FLGP_REQUIRE(ep && idx, "eigenpair: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1, "eigenpair: need 1 <= K <= %d and m >= 1", ep->K);
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx[a] >= 0 && idx[a] < ep->n, "eigenpair: idx[%d]=%d out of range", a, idx[a]);
-  if (is_range(idx, m)) {
-    g.V = (const double *)ep->vectors.p + idx[0];
-    g.ld = ep->n;
-    return FLGP_OK;
-  }
-  FLGP_TRY(g.buf.alloc(sizeof(double) * (size_t)m * K));
-  FLGP_TRY(g.didx.alloc(sizeof(int) * (size_t)m));
-  FLGP_TRY(h2d(g.didx.p, idx, sizeof(int) * (size_t)m, st));
-  FLGP_TRY(flgp_dev_gather_rows(st, (const double *)ep->vectors.p, ep->n, g.didx.as<int>(), m, K, g.buf.as<double>()));
-  g.V = g.buf.as<double>();
-  g.ld = m;
-  return FLGP_OK;
-}
-
-extern "C" int flgp_eigenpair_vtv(const flgp_eigenpair *ep, int K, const int *idx, int m, double *VtV) {
-  FLGP_REQUIRE(VtV, "eigenpair_vtv: null pointer");
-  Stream st;
-  FLGP_TRY(st.create());
-  GatheredV g;
-  FLGP_TRY(gather_v(st.s, ep, K, idx, m, g));
-  DevBuf out, work;
-  const size_t we = (size_t)128 * K * K;
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)K * K));
-  FLGP_TRY(work.alloc(sizeof(double) * we));
-  // (K x m)(m x K): A(i,k) = V(k,i), B(k,j) = V(k,j)
-  FLGP_TRY(gemm_launch(st.s, K, K, m, 1.0, g.V, g.ld, 1, g.V, 1, g.ld, 0.0, nullptr, 0, 0, out.as<double>(), 1, K,
-                       work.as<double>(), we, 0.0, nullptr));
-  FLGP_TRY(d2h(VtV, out.p, sizeof(double) * (size_t)K * K, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  return FLGP_OK;
-}
-
-extern "C" int flgp_eigenpair_vty(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y, int q,
-                                  double *VtY) {
-  FLGP_REQUIRE(Y && VtY && q >= 1, "eigenpair_vty: bad arguments");
-  Stream st;
-  FLGP_TRY(st.create());
-  GatheredV g;
-  FLGP_TRY(gather_v(st.s, ep, K, idx, m, g));
-  DevBuf dY, out, work;
-  const size_t we = (size_t)64 * K * q + 1024;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q));
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)K * q));
-  FLGP_TRY(work.alloc(sizeof(double) * we));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
-  FLGP_TRY(gemm_launch(st.s, K, q, m, 1.0, g.V, g.ld, 1, dY.as<double>(), 1, m, 0.0, nullptr, 0, 0, out.as<double>(), 1, K,
-                       work.as<double>(), we, 0.0, nullptr));
-  FLGP_TRY(d2h(VtY, out.p, sizeof(double) * (size_t)K * q, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  return FLGP_OK;
-}
-
-extern "C" int flgp_eigenpair_vc(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *C, int q,
-                                 double *VC) {
-  FLGP_REQUIRE(C && VC && q >= 1, "eigenpair_vc: bad arguments");
-  Stream st;
-  FLGP_TRY(st.create());
-  GatheredV g;
-  FLGP_TRY(gather_v(st.s, ep, K, idx, m, g));
-  DevBuf dC, out;
-  FLGP_TRY(dC.alloc(sizeof(double) * (size_t)K * q));
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)m * q));
-  FLGP_TRY(h2d(dC.p, C, sizeof(double) * (size_t)K * q, st.s));
-  FLGP_TRY(gemm_launch(st.s, m, q, K, 1.0, g.V, 1, g.ld, dC.as<double>(), 1, K, 0.0, nullptr, 0, 0, out.as<double>(), 1, m,
-                       nullptr, 0, 0.0, nullptr));
-  FLGP_TRY(d2h(VC, out.p, sizeof(double) * (size_t)m * q, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  return FLGP_OK;
-}
-
-// ---- regression consumers of the resident pair: the Woodbury algebra stays on the device --------------
-namespace {
-struct GprCtx {
-  DevBuf ls, l, flag;
-  int prepare(hipStream_t st, const flgp_eigenpair *ep, int K, double t) {
-    FLGP_TRY(ls.alloc(sizeof(double) * (size_t)K)); FLGP_TRY(l.alloc(sizeof(double) * (size_t)K));
-    FLGP_TRY(flag.alloc(sizeof(int)));
-    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    return gpr_weights(st, (const double *)ep->values.p, K, t, ls.as<double>(), l.as<double>());
-  }
-  int verdict(hipStream_t st, const char *who) {   // synchronises
-    int h = 0;
-    FLGP_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    FLGP_HIP(hipStreamSynchronize(st));
-    if (h) { set_error("%s: the system matrix is not positive definite (Cholesky pivot <= 0)", who); return FLGP_ERR_NOCONV; }
-    return FLGP_OK;
-  }
-};
-// device index array of a gather (nullptr for a contiguous range)
-int upload_idx(hipStream_t st, const int *idx, int cnt, DevBuf &buf, const int **d_out, int *row0) {
-  *d_out = nullptr; *row0 = 0;
-  if (is_range(idx, cnt)) { *row0 = cnt ? idx[0] : 0; return FLGP_OK; }
-  FLGP_TRY(buf.alloc(sizeof(int) * (size_t)cnt));
-  FLGP_TRY(h2d(buf.p, idx, sizeof(int) * (size_t)cnt, st));
-  *d_out = buf.as<int>();
-  return FLGP_OK;
-}
-}  // namespace
-
-extern "C" int flgp_eigenpair_predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
-                                                 int mnew, const double *Y, int q, double t, double noise, double sigma,
-                                                 double *Y_pred) {
-  FLGP_REQUIRE(ep && idx0 && idx1 && Y && Y_pred, "predict_regression: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && q >= 1, "predict_regression: bad shape (K=%d m=%d m_new=%d q=%d)", K, m, mnew, q);
-  const double c = noise + sigma;
-  FLGP_REQUIRE(c > 0.0, "predict_regression: noise + sigma must be positive");
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < ep->n, "predict_regression: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int a = 0; a < mnew; ++a) FLGP_REQUIRE(idx1[a] >= 0 && idx1[a] < ep->n, "predict_regression: idx1[%d]=%d out of range", a, idx1[a]);
-  Stream st;
-  FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));
-  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
-  DevBuf dY, out;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q));
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew * q));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
-  if (m <= K) {
-    // Cvv + (sigma + noise) I, Cholesky, alpha = C^-1 Y, Y_pred = Cnv alpha        (src/Predict.cpp:48-58)
-    DevBuf i0, i1, C, Cnv, work;
-    const int *d0, *d1; int r0, r1;
-    FLGP_TRY(upload_idx(st.s, idx0, m, i0, &d0, &r0));
-    FLGP_TRY(upload_idx(st.s, idx1, mnew, i1, &d1, &r1));
-    FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
-    FLGP_TRY(Cnv.alloc(sizeof(double) * (size_t)mnew * m));
-    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(std::max(m, mnew), m, K, 1)));
-    FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
-    FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, sigma));
-    FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, noise));
-    FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d1, r1, mnew, dvec, ep->n, d0, r0, m, Cnv.as<double>(), mnew, work.as<double>()));
-    FLGP_TRY(chol_solve(st.s, C.as<double>(), m, dY.as<double>(), q, G.flag.as<int>()));
-    FLGP_TRY(gemm_launch(st.s, mnew, q, m, 1.0, Cnv.as<double>(), 1, mnew, dY.as<double>(), 1, m, 0.0, nullptr, 0, 0,
-                         out.as<double>(), 1, mnew, nullptr, 0, 0.0, nullptr));
-  } else {
-    // Woodbury: Q = Ls V^T V Ls + (noise + sigma) I  (K x K)                       (src/Predict.cpp:59-74)
-    GatheredV g0, g1;
-    FLGP_TRY(gather_v(st.s, ep, K, idx0, m, g0));
-    FLGP_TRY(gather_v(st.s, ep, K, idx1, mnew, g1));
-    DevBuf VtV, VtY, Q, R, T1, work;
-    const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
-    FLGP_TRY(VtV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(VtY.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
-    FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
-    FLGP_TRY(gemm_launch(st.s, K, K, m, 1.0, g0.V, g0.ld, 1, g0.V, 1, g0.ld, 0.0, nullptr, 0, 0, VtV.as<double>(), 1, K,
-                         work.as<double>(), we, 0.0, nullptr));
-    FLGP_TRY(gemm_launch(st.s, K, q, m, 1.0, g0.V, g0.ld, 1, dY.as<double>(), 1, m, 0.0, nullptr, 0, 0, VtY.as<double>(), 1, K,
-                         work.as<double>(), we, 0.0, nullptr));
-    FLGP_TRY(gpr_q(st.s, VtV.as<double>(), G.ls.as<double>(), K, c, Q.as<double>()));
-    FLGP_TRY(gpr_scale(st.s, VtY.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));          // Ls V^T Y
-    FLGP_TRY(chol_solve(st.s, Q.as<double>(), K, R.as<double>(), q, G.flag.as<int>()));                       // Q^-1 (.)
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));            // Ls (.)
-    // V^T alpha = (V^T Y - V^T V Ls Q^-1 Ls V^T Y) / (noise + sigma)
-    FLGP_TRY(gemm_launch(st.s, K, q, K, 1.0, VtV.as<double>(), 1, K, R.as<double>(), 1, K, 0.0, nullptr, 0, 0, T1.as<double>(), 1, K,
-                         nullptr, 0, 0.0, nullptr));
-    FLGP_TRY(gpr_diff(st.s, VtY.as<double>(), T1.as<double>(), 1.0 / c, (long)K * q, T1.as<double>()));
-    FLGP_TRY(gpr_scale(st.s, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));           // exp(-t lam) (.)
-    FLGP_TRY(gemm_launch(st.s, mnew, q, K, 1.0, g1.V, 1, g1.ld, T1.as<double>(), 1, K, 0.0, nullptr, 0, 0, out.as<double>(), 1,
-                         mnew, nullptr, 0, 0.0, nullptr));
-  }
-  FLGP_TRY(d2h(Y_pred, out.p, sizeof(double) * (size_t)mnew * q, st.s));
-  return G.verdict(st.s, "predict_regression");
-}
-
-// predict_regression_cpp with noisepar = "different" (reference src/Predict.cpp:76-110): one noise variance per training
-// row, pars = (t, noise_1 .. noise_m).  m <= K: the m x m kernel matrix with sigma + noise_i on its diagonal.  m > K: with
-// Z^-1 = diag(1 / (noise_i + sigma)),  Q = Ls V^T Z^-1 V Ls + I,  alpha = Z^-1 Y - Z^-1 V Ls Q^-1 Ls V^T Z^-1 Y; only
-// V^T alpha = V^T Z^-1 Y - (V^T Z^-1 V) Ls Q^-1 Ls V^T Z^-1 Y is formed (K x q), never the m x q alpha.
-extern "C" int flgp_eigenpair_predict_regression_different(const flgp_eigenpair *ep, int K, const int *idx0, int m,
-                                                           const int *idx1, int mnew, const double *Y, int q, double t,
-                                                           const double *noise, double sigma, double *Y_pred) {
-  FLGP_REQUIRE(ep && idx0 && idx1 && Y && Y_pred && noise, "predict_regression: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && q >= 1, "predict_regression: bad shape (K=%d m=%d m_new=%d q=%d)", K, m, mnew, q);
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(noise[a] + sigma > 0.0, "predict_regression: noise[%d] + sigma must be positive", a);
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < ep->n, "predict_regression: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int a = 0; a < mnew; ++a) FLGP_REQUIRE(idx1[a] >= 0 && idx1[a] < ep->n, "predict_regression: idx1[%d]=%d out of range", a, idx1[a]);
-  Stream st;
-  FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));
-  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
-  DevBuf dY, out, dnoise;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q));
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew * q));
-  FLGP_TRY(dnoise.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
-  FLGP_TRY(h2d(dnoise.p, noise, sizeof(double) * (size_t)m, st.s));
-  if (m <= K) {
-    // Cvv + sigma I + diag(noise), Cholesky, alpha = C^-1 Y, Y_pred = Cnv alpha       (src/Predict.cpp:78-91)
-    DevBuf i0, i1, C, Cnv, work;
-    const int *d0, *d1; int r0, r1;
-    FLGP_TRY(upload_idx(st.s, idx0, m, i0, &d0, &r0));
-    FLGP_TRY(upload_idx(st.s, idx1, mnew, i1, &d1, &r1));
-    FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
-    FLGP_TRY(Cnv.alloc(sizeof(double) * (size_t)mnew * m));
-    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(std::max(m, mnew), m, K, 1)));
-    FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
-    FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, sigma));
-    FLGP_TRY(gpr_add_diag_vec(st.s, C.as<double>(), m, dnoise.as<double>()));
-    FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d1, r1, mnew, dvec, ep->n, d0, r0, m, Cnv.as<double>(), mnew, work.as<double>()));
-    FLGP_TRY(chol_solve(st.s, C.as<double>(), m, dY.as<double>(), q, G.flag.as<int>()));
-    FLGP_TRY(gemm_launch(st.s, mnew, q, m, 1.0, Cnv.as<double>(), 1, mnew, dY.as<double>(), 1, m, 0.0, nullptr, 0, 0,
-                         out.as<double>(), 1, mnew, nullptr, 0, 0.0, nullptr));
-  } else {
-    GatheredV g0, g1;
-    FLGP_TRY(gather_v(st.s, ep, K, idx0, m, g0));
-    FLGP_TRY(gather_v(st.s, ep, K, idx1, mnew, g1));
-    DevBuf zinv, ZV, ZY, VtZV, VtZY, Q, R, T1, work;
-    const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
-    FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
-    FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
-    FLGP_TRY(VtZV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(VtZY.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
-    FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
-    FLGP_TRY(gpr_zinv(st.s, dnoise.as<double>(), sigma, m, zinv.as<double>()));                                  // :98-101
-    FLGP_TRY(gpr_rowscale_ld(st.s, g0.V, g0.ld, zinv.as<double>(), m, K, ZV.as<double>()));                     // Z^-1 V
-    FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, zinv.as<double>(), m, q, ZY.as<double>()));              // Z^-1 Y
-    FLGP_TRY(gemm_launch(st.s, K, K, m, 1.0, g0.V, g0.ld, 1, ZV.as<double>(), 1, m, 0.0, nullptr, 0, 0, VtZV.as<double>(), 1, K,
-                         work.as<double>(), we, 0.0, nullptr));                                                 // V^T Z^-1 V   :102
-    FLGP_TRY(gemm_launch(st.s, K, q, m, 1.0, g0.V, g0.ld, 1, ZY.as<double>(), 1, m, 0.0, nullptr, 0, 0, VtZY.as<double>(), 1, K,
-                         work.as<double>(), we, 0.0, nullptr));                                                 // V^T Z^-1 Y
-    FLGP_TRY(gpr_q(st.s, VtZV.as<double>(), G.ls.as<double>(), K, 1.0, Q.as<double>()));                        // :103-104
-    FLGP_TRY(gpr_scale(st.s, VtZY.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));
-    FLGP_TRY(chol_solve(st.s, Q.as<double>(), K, R.as<double>(), q, G.flag.as<int>()));                         // :105-106
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));
-    FLGP_TRY(gemm_launch(st.s, K, q, K, 1.0, VtZV.as<double>(), 1, K, R.as<double>(), 1, K, 0.0, nullptr, 0, 0, T1.as<double>(), 1, K,
-                         nullptr, 0, 0.0, nullptr));
-    FLGP_TRY(gpr_diff(st.s, VtZY.as<double>(), T1.as<double>(), 1.0, (long)K * q, T1.as<double>()));            // V^T alpha
-    FLGP_TRY(gpr_scale(st.s, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));               // exp(-t lam) (.)
-    FLGP_TRY(gemm_launch(st.s, mnew, q, K, 1.0, g1.V, 1, g1.ld, T1.as<double>(), 1, K, 0.0, nullptr, 0, 0, out.as<double>(), 1,
-                         mnew, nullptr, 0, 0.0, nullptr));                                                      // :108-109
-  }
-  FLGP_TRY(d2h(Y_pred, out.p, sizeof(double) * (size_t)mnew * q, st.s));
-  return G.verdict(st.s, "predict_regression");
-}
-
-extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
-                                                 int mnew, double t, double var, double sigma, double *cov) {
-  FLGP_REQUIRE(ep && idx0 && idx1 && cov, "posterior_variance: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1, "posterior_variance: bad shape (K=%d m=%d m_new=%d)", K, m, mnew);
-  const double c = var + sigma;
-  FLGP_REQUIRE(c > 0.0, "posterior_variance: var + sigma must be positive");
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < ep->n, "posterior_variance: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int a = 0; a < mnew; ++a) FLGP_REQUIRE(idx1[a] >= 0 && idx1[a] < ep->n, "posterior_variance: idx1[%d]=%d out of range", a, idx1[a]);
-  Stream st;
-  FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));
-  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
-  GatheredV g1;
-  FLGP_TRY(gather_v(st.s, ep, K, idx1, mnew, g1));
-  DevBuf out;
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew));
-  if (m <= K) {
-    // K11 = C11 + (var + sigma) I; alpha = C21 K11^-1; beta = rowsum(C21 .* alpha)          (src/Utils.cpp:227-237)
-    DevBuf i0, i1, C, C12, X, work;
-    const int *d0, *d1; int r0, r1;
-    FLGP_TRY(upload_idx(st.s, idx0, m, i0, &d0, &r0));
-    FLGP_TRY(upload_idx(st.s, idx1, mnew, i1, &d1, &r1));
-    FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
-    FLGP_TRY(C12.alloc(sizeof(double) * (size_t)m * mnew)); FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * mnew));
-    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, std::max(m, mnew), K, 1)));
-    FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
-    FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, c));
-    FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d1, r1, mnew, C12.as<double>(), m, work.as<double>()));
-    FLGP_HIP(hipMemcpyAsync(X.p, C12.p, sizeof(double) * (size_t)m * mnew, hipMemcpyDeviceToDevice, st.s));
-    FLGP_TRY(chol_solve(st.s, C.as<double>(), m, X.as<double>(), mnew, G.flag.as<int>()));
-    FLGP_TRY(gpr_rowdot(st.s, C12.as<double>(), X.as<double>(), mnew, m, g1.V, g1.ld, K, G.l.as<double>(), c, out.as<double>()));
-  } else {
-    // alpha = 1/(var+sigma) L V1^T (V1 - V1 Ls Q^-1 Ls V1^T V1) L; beta_i = V2(i,:) alpha V2(i,:)^T  (src/Utils.cpp:238-246)
-    GatheredV g0;
-    FLGP_TRY(gather_v(st.s, ep, K, idx0, m, g0));
-    DevBuf VtV, Q, R, T1, W, work;
-    const size_t we = (size_t)128 * K * K + 1024;
-    FLGP_TRY(VtV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(W.alloc(sizeof(double) * (size_t)mnew * K)); FLGP_TRY(work.alloc(sizeof(double) * we));
-    FLGP_TRY(gemm_launch(st.s, K, K, m, 1.0, g0.V, g0.ld, 1, g0.V, 1, g0.ld, 0.0, nullptr, 0, 0, VtV.as<double>(), 1, K,
-                         work.as<double>(), we, 0.0, nullptr));
-    FLGP_TRY(gpr_q(st.s, VtV.as<double>(), G.ls.as<double>(), K, c, Q.as<double>()));
-    FLGP_TRY(gpr_scale(st.s, VtV.as<double>(), G.ls.as<double>(), nullptr, K, K, R.as<double>()));          // Ls V1^T V1
-    FLGP_TRY(chol_solve(st.s, Q.as<double>(), K, R.as<double>(), K, G.flag.as<int>()));
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, K, R.as<double>()));            // Ls Q^-1 Ls VtV
-    FLGP_TRY(gemm_launch(st.s, K, K, K, 1.0, VtV.as<double>(), 1, K, R.as<double>(), 1, K, 0.0, nullptr, 0, 0, T1.as<double>(), 1, K,
-                         nullptr, 0, 0.0, nullptr));
-    FLGP_TRY(gpr_diff(st.s, VtV.as<double>(), T1.as<double>(), 1.0 / c, (long)K * K, T1.as<double>()));     // (VtV - ...)/(var+sigma)
-    FLGP_TRY(gpr_scale(st.s, T1.as<double>(), G.l.as<double>(), G.l.as<double>(), K, K, T1.as<double>()));   // L (.) L
-    FLGP_TRY(gemm_launch(st.s, mnew, K, K, 1.0, g1.V, 1, g1.ld, T1.as<double>(), 1, K, 0.0, nullptr, 0, 0, W.as<double>(), 1,
-                         mnew, nullptr, 0, 0.0, nullptr));                                                  // V2 alpha
-    FLGP_TRY(gpr_rowquad(st.s, g1.V, g1.ld, W.as<double>(), mnew, K, G.l.as<double>(), c, out.as<double>()));
-  }
-  FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
-  return G.verdict(st.s, "posterior_variance");
-}
-
-// ---- classification consumers: the Laplace approximation of the logit GP on the device (gpc.hip) ---------
-namespace {
-int check_labels(const double *Y, const double *N, int m, const char *who) {
-  for (int a = 0; a < m; ++a) {
-    const double n = N ? N[a] : 1.0;
-    FLGP_REQUIRE(n > 0.0 && n < HUGE_VAL, "%s: N[%d]=%g must be positive", who, a, n);
-    FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] <= n, "%s: Y[%d]=%g is outside [0, N[%d]=%g]", who, a, Y[a], a, n);
-  }
-  return FLGP_OK;
-}
-// Newton loop + final sums on the device-resident C (m x m); only the scalar comes down
-int logit_la_on_device(hipStream_t st, const double *dC, int m, const double *Y, const double *N, double tol, int max_iter,
-                       double *amll, int *iters, const char *who) {
-  DevBuf dY, dN;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(dN.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st));
-  FLGP_TRY(h2d(dN.p, N, sizeof(double) * (size_t)m, st));
-  GpcNewton S;
-  FLGP_TRY(S.alloc(m));
-  int it = 0;
-  FLGP_TRY(S.run(st, dC, dY.as<double>(), dN.as<double>(), tol, max_iter, who, &it));
-  if (iters) *iters = it;
-  return S.amll(st, dY.as<double>(), dN.as<double>(), amll);
-}
-}  // namespace
-
-extern "C" int flgp_logit_la_marginal_likelihood(const double *C, int m, const double *Y, const double *N, double tol,
-                                                 int max_iter, double *amll, int *iters) {
-  FLGP_REQUIRE(C && Y && N && amll, "logit_la_marginal_likelihood: null pointer");
-  FLGP_REQUIRE(m >= 1 && max_iter >= 1, "logit_la_marginal_likelihood: bad shape (m=%d max_iter=%d)", m, max_iter);
-  FLGP_TRY(check_labels(Y, N, m, "logit_la_marginal_likelihood"));
-  Stream st;
-  FLGP_TRY(st.create());
-  DevBuf dC;
-  FLGP_TRY(dC.alloc(sizeof(double) * (size_t)m * m));
-  FLGP_TRY(h2d(dC.p, C, sizeof(double) * (size_t)m * m, st.s));
-  return logit_la_on_device(st.s, dC.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_la_marginal_likelihood");
-}
-
-extern "C" int flgp_eigenpair_logit_marginal_likelihood(const flgp_eigenpair *ep, int K, double t, double sigma, const int *idx,
-                                                        int m, const double *Y, const double *N, double tol, int max_iter,
-                                                        double *amll, int *iters) {
-  FLGP_REQUIRE(ep && idx && Y && N && amll, "logit_marginal_likelihood: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1, "logit_marginal_likelihood: bad shape (K=%d of %d, m=%d, max_iter=%d)",
-               K, ep->K, m, max_iter);
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx[a] >= 0 && idx[a] < ep->n, "logit_marginal_likelihood: idx[%d]=%d out of range", a, idx[a]);
-  FLGP_TRY(check_labels(Y, N, m, "logit_marginal_likelihood"));
-  Stream st;
-  FLGP_TRY(st.create());
-  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
-  // C = HK(idx, idx) + sigma I       (src/train.cpp:30-31)
-  DevBuf i0, C, work;
-  const int *d0; int r0;
-  FLGP_TRY(upload_idx(st.s, idx, m, i0, &d0, &r0));
-  FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
-  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
-  FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
-  FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, sigma));
-  return logit_la_on_device(st.s, C.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_marginal_likelihood");
-}
-
-// posterior_distribution_classification (src/Utils.cpp:252-299) with C11 = HK(idx0, idx0) + sigma11 I,
-// C21 = HK(idx1, idx0) = V2 L V1^T, C22 = rowsum(V2 L .* V2) + sigma22.  mean = V2 L V1^T (Y - pi);
-// var_i = C22_i - v2_i^T M v2_i with M = X^T X, X = L_B^-1 sqrt(W) V1 L: O(m_new K^2), C21 is never formed.
-extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
-                                                       const int *idx0, int m, const double *Y, const int *idx1, int mnew,
-                                                       double tol, int max_iter, double *mean, double *cov) {
-  const char *who = "posterior_classification";
-  FLGP_REQUIRE(ep && idx0 && idx1 && Y && mean && cov, "%s: null pointer", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && max_iter >= 1,
-               "%s: bad shape (K=%d of %d, m=%d, m_new=%d, max_iter=%d)", who, K, ep->K, m, mnew, max_iter);
-  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < ep->n, "%s: idx0[%d]=%d out of range", who, a, idx0[a]);
-  for (int a = 0; a < mnew; ++a) FLGP_REQUIRE(idx1[a] >= 0 && idx1[a] < ep->n, "%s: idx1[%d]=%d out of range", who, a, idx1[a]);
-  FLGP_TRY(check_labels(Y, nullptr, m, who));
-  Stream st;
-  FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));                    // G.l = exp(-t (1 - values))
-  const double *dval = (const double *)ep->values.p, *dvec = (const double *)ep->vectors.p;
-  DevBuf i0, C, work, dY;
-  const int *d0; int r0;
-  FLGP_TRY(upload_idx(st.s, idx0, m, i0, &d0, &r0));
-  FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
-  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
-  FLGP_TRY(flgp_dev_hk(st.s, dval, K, t, dvec, ep->n, d0, r0, m, dvec, ep->n, d0, r0, m, C.as<double>(), m, work.as<double>()));
-  if (sigma11 != 0.0) FLGP_TRY(gpr_add_diag(st.s, C.as<double>(), m, sigma11));
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
-  // the mode (N = 1), then B factored again at the final f          (src/Utils.cpp:268-293)
-  GpcNewton S;
-  FLGP_TRY(S.alloc(m));
-  int it = 0;
-  FLGP_TRY(S.run(st.s, C.as<double>(), dY.as<double>(), nullptr, tol, max_iter, who, &it));
-  FLGP_TRY(S.weights(st.s, C.as<double>(), dY.as<double>(), nullptr));
-  GatheredV g0, g1;
-  FLGP_TRY(gather_v(st.s, ep, K, idx0, m, g0));
-  FLGP_TRY(gather_v(st.s, ep, K, idx1, mnew, g1));
-  DevBuf X, Mp, u, Wp, out, gw;
-  const size_t we = (size_t)128 * K * K + 1024;
-  FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
-  FLGP_TRY(Mp.alloc(sizeof(double) * (size_t)K * (K + 1)));
-  FLGP_TRY(u.alloc(sizeof(double) * (size_t)K));
-  FLGP_TRY(Wp.alloc(sizeof(double) * (size_t)mnew * (K + 1)));
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew));
-  FLGP_TRY(gw.alloc(sizeof(double) * we));
-  FLGP_TRY(gpc_scale2(st.s, g0.V, g0.ld, S.sW.as<double>(), G.l.as<double>(), m, K, X.as<double>()));     // sqrt(W) V1 L
-  FLGP_TRY(chol_trsv(st.s, S.B.as<double>(), m, m, X.as<double>(), m, K, 1, S.flag.as<int>()));         // L_B^-1 (.)
-  FLGP_TRY(gemm_launch(st.s, K, K, m, 1.0, X.as<double>(), m, 1, X.as<double>(), 1, m, 0.0, nullptr, 0, 0, Mp.as<double>(), 1, K,
-                       gw.as<double>(), we, 0.0, nullptr));                                                  // M = X^T X
-  FLGP_TRY(gemm_launch(st.s, K, 1, m, 1.0, g0.V, g0.ld, 1, S.resid.as<double>(), 1, m, 0.0, nullptr, 0, 0, u.as<double>(), 1, K,
-                       gw.as<double>(), we, 0.0, nullptr));                                                  // V1^T (Y - pi)
-  FLGP_TRY(gpr_scale(st.s, u.as<double>(), G.l.as<double>(), nullptr, K, 1, Mp.as<double>() + (size_t)K * K));  // column K: L (.)
-  FLGP_TRY(gemm_launch(st.s, mnew, K + 1, K, 1.0, g1.V, 1, g1.ld, Mp.as<double>(), 1, K, 0.0, nullptr, 0, 0, Wp.as<double>(), 1,
-                       mnew, nullptr, 0, 0.0, nullptr));                                                     // V2 [M | u]
-  FLGP_TRY(gpr_rowquad(st.s, g1.V, g1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, out.as<double>()));
-  FLGP_TRY(d2h(mean, Wp.as<double>() + (size_t)K * mnew, sizeof(double) * (size_t)mnew, st.s));
-  FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
-  int bad = 0;
-  FLGP_HIP(hipMemcpyAsync(&bad, S.flag.p, sizeof(int), hipMemcpyDeviceToHost, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  return GpcNewton::pivot_error(bad, who, 0);      // the loop checked its own factorisations: this is the one at the mode
 }
 
 extern "C" void flgp_eigenpair_free(flgp_eigenpair *ep) { delete ep; }

@@ -109,6 +109,34 @@ inline int check_launch(const char *what) {
   return FLGP_OK;
 }
 
+// the host entry points' own stream, destroyed on every way out
+struct Stream {
+  hipStream_t s = nullptr;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  int create() { FLGP_HIP(hipStreamCreate(&s)); return FLGP_OK; }
+};
+
+inline int h2d(void *dst, const void *src, size_t bytes, hipStream_t st) {
+  if (bytes) FLGP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+  return FLGP_OK;
+}
+inline int d2h(void *dst, const void *src, size_t bytes, hipStream_t st) {
+  if (bytes) FLGP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+  return FLGP_OK;
+}
+// *h = the device int at d_flag once everything queued on `st` has run (synchronises the stream)
+inline int read_flag(hipStream_t st, const void *d_flag, int *h) {
+  FLGP_HIP(hipMemcpyAsync(h, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
+}
+
+inline bool is_range(const int *idx, int cnt) {
+  for (int i = 1; i < cnt; ++i)
+    if (idx[i] != idx[0] + i) return false;
+  return true;
+}
+
 // C(i,j) = alpha * sum_k A(i,k) B(k,j) + beta * E(i,j) + gamma * E2(i,j)   (gemm.hip)
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
@@ -204,3 +232,9 @@ int launch_lae_reg(hipStream_t st, const double *dX, int n, int ldx, int d, cons
                    const int *d_knn, int ldk, int *d_ei, double *d_ev);
 
 }  // namespace flgp
+
+// device-resident EigenPair (include/flgp_hip.h): made in capi.hip, consumed there (H) and in eigenpair.hip
+struct flgp_eigenpair {
+  flgp::DevBuf values, vectors;   // K, n x K column-major
+  int n = 0, K = 0, device = 0;
+};

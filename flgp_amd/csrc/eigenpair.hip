@@ -1,0 +1,399 @@
+// Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products,
+// regression prediction and posterior variance (dense algebra in gpr.hip) and the Laplace approximation of
+// the logit GP (gpc.hip).  Each entry checks its arguments on the host, then runs on one stream of its own.
+#include "common.h"
+#include <algorithm>
+#include <cmath>
+
+using namespace flgp;
+
+namespace {
+
+// One index array into the pair's rows.  check() refuses a row outside [0, n) before any device work, as
+// "<who>: <name>[<a>]=<v> out of range".  At first use a contiguous range is taken in place (row0) and any other set is
+// uploaded once (d): the scan runs beside the device work queued by then.  gather() makes V = vectors[rows, 0:K] (m x K at
+// ld; a range is read in place).
+struct Rows {
+  const int *idx = nullptr;
+  int m = 0, row0 = 0;
+  bool resolved = false;
+  const int *d = nullptr;        // flgp_dev_hk's index argument: nullptr for a range
+  const double *V = nullptr;
+  long ld = 0;
+  DevBuf didx, vbuf;
+  int check(const flgp_eigenpair *ep, const int *idx_, int m_, const char *who, const char *name) {
+    for (int a = 0; a < m_; ++a) FLGP_REQUIRE(idx_[a] >= 0 && idx_[a] < ep->n, "%s: %s[%d]=%d out of range", who, name, a, idx_[a]);
+    idx = idx_; m = m_;
+    return FLGP_OK;
+  }
+  int upload(hipStream_t st) {
+    if (resolved) return FLGP_OK;
+    resolved = true;
+    if (is_range(idx, m)) { row0 = idx[0]; return FLGP_OK; }
+    FLGP_TRY(didx.alloc(sizeof(int) * (size_t)m));
+    FLGP_TRY(h2d(didx.p, idx, sizeof(int) * (size_t)m, st));
+    d = didx.as<int>();
+    return FLGP_OK;
+  }
+  int gather(hipStream_t st, const flgp_eigenpair *ep, int K) {
+    FLGP_TRY(upload(st));
+    if (!d) { V = (const double *)ep->vectors.p + row0; ld = ep->n; return FLGP_OK; }
+    FLGP_TRY(vbuf.alloc(sizeof(double) * (size_t)m * K));
+    FLGP_TRY(flgp_dev_gather_rows(st, (const double *)ep->vectors.p, ep->n, d, m, K, vbuf.as<double>()));
+    V = vbuf.as<double>(); ld = m;
+    return FLGP_OK;
+  }
+};
+
+// H = HK(a, b) from the first K pairs (a.m x b.m, ld a.m); both row sets uploaded, `work` sized by the caller
+int hk(hipStream_t st, const flgp_eigenpair *ep, int K, double t, const Rows &a, const Rows &b, double *H, double *work) {
+  const double *dvec = (const double *)ep->vectors.p;
+  return flgp_dev_hk(st, (const double *)ep->values.p, K, t, dvec, ep->n, a.d, a.row0, a.m, dvec, ep->n, b.d, b.row0, b.m, H,
+                     a.m, work);
+}
+// C = C11 = HK(r, r) + sigma I (r.m x r.m), with `work` of work_bytes for it and the caller's later contractions.  A zero
+// sigma launches nothing: the diagonal of HK(r, r) is a sum of squares, never -0.
+int hk_c11(hipStream_t st, const flgp_eigenpair *ep, int K, double t, Rows &r, double sigma, DevBuf &C, DevBuf &work,
+           size_t work_bytes) {
+  FLGP_TRY(r.upload(st));
+  FLGP_TRY(C.alloc(sizeof(double) * (size_t)r.m * r.m));
+  FLGP_TRY(work.alloc(work_bytes));
+  FLGP_TRY(hk(st, ep, K, t, r, r, C.as<double>(), work.as<double>()));
+  return sigma != 0.0 ? gpr_add_diag(st, C.as<double>(), r.m, sigma) : FLGP_OK;
+}
+
+// Column-major products, C (M x N, ld M) = A^T B with A k x M, or = A B with A M x k; B k x N.  `work` / `we` go to
+// gemm_launch unchanged: they bound its k-split, so they decide the bits.
+int gemm_tn(hipStream_t st, int M, int N, int k, const double *A, long lda, const double *B, long ldb, double *C, double *work,
+            size_t we) {
+  return gemm_launch(st, M, N, k, 1.0, A, lda, 1, B, 1, ldb, 0.0, nullptr, 0, 0, C, 1, M, work, we, 0.0, nullptr);
+}
+int gemm_nn(hipStream_t st, int M, int N, int k, const double *A, long lda, const double *B, long ldb, double *C, double *work,
+            size_t we) {
+  return gemm_launch(st, M, N, k, 1.0, A, 1, lda, B, 1, ldb, 0.0, nullptr, 0, 0, C, 1, M, work, we, 0.0, nullptr);
+}
+
+// The V products: out (host) = V^T B (tn, K x q) or V B (m x q) with V = vectors[idx, 0:K] and B the caller's (m or K rows,
+// q columns; nullptr: V itself).  `we` is the workspace of the V^T B product.
+int v_product(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *B, int q, bool tn, size_t we, double *out_h) {
+  FLGP_REQUIRE(ep && idx, "eigenpair: null pointer");
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1, "eigenpair: need 1 <= K <= %d and m >= 1", ep->K);
+  Rows R;
+  FLGP_TRY(R.check(ep, idx, m, "eigenpair", "idx"));
+  Stream st;
+  FLGP_TRY(st.create());
+  FLGP_TRY(R.gather(st.s, ep, K));
+  const int brows = tn ? m : K, orows = tn ? K : m;
+  DevBuf dB, out, work;
+  if (B) FLGP_TRY(dB.alloc(sizeof(double) * (size_t)brows * q));
+  FLGP_TRY(out.alloc(sizeof(double) * (size_t)orows * q));
+  if (tn) FLGP_TRY(work.alloc(sizeof(double) * we));
+  if (B) FLGP_TRY(h2d(dB.p, B, sizeof(double) * (size_t)brows * q, st.s));
+  const double *b = B ? dB.as<double>() : R.V;
+  const long ldb = B ? brows : R.ld;
+  FLGP_TRY(tn ? gemm_tn(st.s, K, q, m, R.V, R.ld, b, ldb, out.as<double>(), work.as<double>(), we)
+              : gemm_nn(st.s, m, q, K, R.V, R.ld, b, ldb, out.as<double>(), nullptr, 0));
+  FLGP_TRY(d2h(out_h, out.p, sizeof(double) * (size_t)orows * q, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+}  // namespace
+
+extern "C" int flgp_eigenpair_vtv(const flgp_eigenpair *ep, int K, const int *idx, int m, double *VtV) {
+  FLGP_REQUIRE(VtV, "eigenpair_vtv: null pointer");
+  return v_product(ep, K, idx, m, nullptr, K, true, (size_t)128 * K * K, VtV);
+}
+
+extern "C" int flgp_eigenpair_vty(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y, int q,
+                                  double *VtY) {
+  FLGP_REQUIRE(Y && VtY && q >= 1, "eigenpair_vty: bad arguments");
+  return v_product(ep, K, idx, m, Y, q, true, (size_t)64 * K * q + 1024, VtY);
+}
+
+extern "C" int flgp_eigenpair_vc(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *C, int q,
+                                 double *VC) {
+  FLGP_REQUIRE(C && VC && q >= 1, "eigenpair_vc: bad arguments");
+  return v_product(ep, K, idx, m, C, q, false, 0, VC);
+}
+
+// ---- regression consumers of the resident pair: the Woodbury algebra stays on the device --------------
+namespace {
+struct GprCtx {
+  DevBuf ls, l, flag;
+  int prepare(hipStream_t st, const flgp_eigenpair *ep, int K, double t) {
+    FLGP_TRY(ls.alloc(sizeof(double) * (size_t)K)); FLGP_TRY(l.alloc(sizeof(double) * (size_t)K));
+    FLGP_TRY(flag.alloc(sizeof(int)));
+    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    return gpr_weights(st, (const double *)ep->values.p, K, t, ls.as<double>(), l.as<double>());
+  }
+  int verdict(hipStream_t st, const char *who) {   // synchronises
+    int h = 0;
+    FLGP_TRY(read_flag(st, flag.p, &h));
+    if (h) { set_error("%s: the system matrix is not positive definite (Cholesky pivot <= 0)", who); return FLGP_ERR_NOCONV; }
+    return FLGP_OK;
+  }
+};
+
+// Woodbury, noisepar = "same": Q = Ls V^T V Ls + c I (K x K), c = noise + sigma             (src/Predict.cpp:59-74)
+int woodbury_same(hipStream_t st, GprCtx &G, int K, int q, const Rows &r0, const Rows &r1, const double *dY, double c,
+                  double *out) {
+  const int m = r0.m;
+  DevBuf VtV, VtY, Q, R, T1, work;
+  const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
+  FLGP_TRY(VtV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+  FLGP_TRY(VtY.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
+  FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
+  FLGP_TRY(gemm_tn(st, K, K, m, r0.V, r0.ld, r0.V, r0.ld, VtV.as<double>(), work.as<double>(), we));
+  FLGP_TRY(gemm_tn(st, K, q, m, r0.V, r0.ld, dY, m, VtY.as<double>(), work.as<double>(), we));
+  FLGP_TRY(gpr_q(st, VtV.as<double>(), G.ls.as<double>(), K, c, Q.as<double>()));
+  FLGP_TRY(gpr_scale(st, VtY.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));          // Ls V^T Y
+  FLGP_TRY(chol_solve(st, Q.as<double>(), K, R.as<double>(), q, G.flag.as<int>()));                       // Q^-1 (.)
+  FLGP_TRY(gpr_scale(st, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));            // Ls (.)
+  // V^T alpha = (V^T Y - V^T V Ls Q^-1 Ls V^T Y) / (noise + sigma)
+  FLGP_TRY(gemm_nn(st, K, q, K, VtV.as<double>(), K, R.as<double>(), K, T1.as<double>(), nullptr, 0));
+  FLGP_TRY(gpr_diff(st, VtY.as<double>(), T1.as<double>(), 1.0 / c, (long)K * q, T1.as<double>()));
+  FLGP_TRY(gpr_scale(st, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));           // exp(-t lam) (.)
+  return gemm_nn(st, r1.m, q, K, r1.V, r1.ld, T1.as<double>(), K, out, nullptr, 0);
+}
+
+// Woodbury, noisepar = "different" (src/Predict.cpp:92-110): with Z^-1 = diag(1 / (noise_i + sigma)),
+// Q = Ls V^T Z^-1 V Ls + I,  alpha = Z^-1 Y - Z^-1 V Ls Q^-1 Ls V^T Z^-1 Y; only
+// V^T alpha = V^T Z^-1 Y - (V^T Z^-1 V) Ls Q^-1 Ls V^T Z^-1 Y is formed (K x q), never the m x q alpha.
+int woodbury_different(hipStream_t st, GprCtx &G, int K, int q, const Rows &r0, const Rows &r1, const double *dY,
+                       const double *dnoise, double sigma, double *out) {
+  const int m = r0.m;
+  DevBuf zinv, ZV, ZY, VtZV, VtZY, Q, R, T1, work;
+  const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
+  FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
+  FLGP_TRY(VtZV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+  FLGP_TRY(VtZY.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
+  FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
+  FLGP_TRY(gpr_zinv(st, dnoise, sigma, m, zinv.as<double>()));                                  // :98-101
+  FLGP_TRY(gpr_rowscale_ld(st, r0.V, r0.ld, zinv.as<double>(), m, K, ZV.as<double>()));        // Z^-1 V
+  FLGP_TRY(gpr_rowscale_ld(st, dY, m, zinv.as<double>(), m, q, ZY.as<double>()));               // Z^-1 Y
+  FLGP_TRY(gemm_tn(st, K, K, m, r0.V, r0.ld, ZV.as<double>(), m, VtZV.as<double>(), work.as<double>(), we));   // V^T Z^-1 V   :102
+  FLGP_TRY(gemm_tn(st, K, q, m, r0.V, r0.ld, ZY.as<double>(), m, VtZY.as<double>(), work.as<double>(), we));   // V^T Z^-1 Y
+  FLGP_TRY(gpr_q(st, VtZV.as<double>(), G.ls.as<double>(), K, 1.0, Q.as<double>()));                        // :103-104
+  FLGP_TRY(gpr_scale(st, VtZY.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));
+  FLGP_TRY(chol_solve(st, Q.as<double>(), K, R.as<double>(), q, G.flag.as<int>()));                         // :105-106
+  FLGP_TRY(gpr_scale(st, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));
+  FLGP_TRY(gemm_nn(st, K, q, K, VtZV.as<double>(), K, R.as<double>(), K, T1.as<double>(), nullptr, 0));
+  FLGP_TRY(gpr_diff(st, VtZY.as<double>(), T1.as<double>(), 1.0, (long)K * q, T1.as<double>()));            // V^T alpha
+  FLGP_TRY(gpr_scale(st, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));               // exp(-t lam) (.)
+  return gemm_nn(st, r1.m, q, K, r1.V, r1.ld, T1.as<double>(), K, out, nullptr, 0);                         // :108-109
+}
+
+// predict_regression_cpp (reference src/Predict.cpp:40-110): noise_vec == nullptr is noisepar = "same" (one variance
+// `noise` for every training row), otherwise "different" (noise_vec[a] for row a, the reference's pars[1..m]).
+int predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1, int mnew, const double *Y,
+                       int q, double t, double noise, const double *noise_vec, double sigma, double *Y_pred) {
+  FLGP_REQUIRE(ep && idx0 && idx1 && Y && Y_pred, "predict_regression: null pointer");
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && q >= 1, "predict_regression: bad shape (K=%d m=%d m_new=%d q=%d)", K, m, mnew, q);
+  if (noise_vec)
+    for (int a = 0; a < m; ++a) FLGP_REQUIRE(noise_vec[a] + sigma > 0.0, "predict_regression: noise[%d] + sigma must be positive", a);
+  else
+    FLGP_REQUIRE(noise + sigma > 0.0, "predict_regression: noise + sigma must be positive");
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, "predict_regression", "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, "predict_regression", "idx1"));
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));
+  DevBuf dY, out, dnoise;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q));
+  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew * q));
+  if (noise_vec) FLGP_TRY(dnoise.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
+  if (noise_vec) FLGP_TRY(h2d(dnoise.p, noise_vec, sizeof(double) * (size_t)m, st.s));
+  if (m <= K) {
+    // Cvv + sigma I + (noise I or diag(noise)), Cholesky, alpha = C^-1 Y, Y_pred = Cnv alpha   (src/Predict.cpp:48-58, 78-91)
+    DevBuf C, Cnv, work;
+    FLGP_TRY(r1.upload(st.s));
+    FLGP_TRY(Cnv.alloc(sizeof(double) * (size_t)mnew * m));
+    FLGP_TRY(hk_c11(st.s, ep, K, t, r0, sigma, C, work, flgp_dev_hk_workspace(std::max(m, mnew), m, K, 1)));
+    FLGP_TRY(noise_vec ? gpr_add_diag_vec(st.s, C.as<double>(), m, dnoise.as<double>()) : gpr_add_diag(st.s, C.as<double>(), m, noise));
+    FLGP_TRY(hk(st.s, ep, K, t, r1, r0, Cnv.as<double>(), work.as<double>()));
+    FLGP_TRY(chol_solve(st.s, C.as<double>(), m, dY.as<double>(), q, G.flag.as<int>()));
+    FLGP_TRY(gemm_nn(st.s, mnew, q, m, Cnv.as<double>(), mnew, dY.as<double>(), m, out.as<double>(), nullptr, 0));
+  } else {
+    FLGP_TRY(r0.gather(st.s, ep, K));
+    FLGP_TRY(r1.gather(st.s, ep, K));
+    FLGP_TRY(noise_vec ? woodbury_different(st.s, G, K, q, r0, r1, dY.as<double>(), dnoise.as<double>(), sigma, out.as<double>())
+                       : woodbury_same(st.s, G, K, q, r0, r1, dY.as<double>(), noise + sigma, out.as<double>()));
+  }
+  FLGP_TRY(d2h(Y_pred, out.p, sizeof(double) * (size_t)mnew * q, st.s));
+  return G.verdict(st.s, "predict_regression");
+}
+}  // namespace
+
+extern "C" int flgp_eigenpair_predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
+                                                 int mnew, const double *Y, int q, double t, double noise, double sigma,
+                                                 double *Y_pred) {
+  return predict_regression(ep, K, idx0, m, idx1, mnew, Y, q, t, noise, nullptr, sigma, Y_pred);
+}
+
+extern "C" int flgp_eigenpair_predict_regression_different(const flgp_eigenpair *ep, int K, const int *idx0, int m,
+                                                           const int *idx1, int mnew, const double *Y, int q, double t,
+                                                           const double *noise, double sigma, double *Y_pred) {
+  FLGP_REQUIRE(noise, "predict_regression: null pointer");
+  return predict_regression(ep, K, idx0, m, idx1, mnew, Y, q, t, 0.0, noise, sigma, Y_pred);
+}
+
+extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
+                                                 int mnew, double t, double var, double sigma, double *cov) {
+  FLGP_REQUIRE(ep && idx0 && idx1 && cov, "posterior_variance: null pointer");
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1, "posterior_variance: bad shape (K=%d m=%d m_new=%d)", K, m, mnew);
+  const double c = var + sigma;
+  FLGP_REQUIRE(c > 0.0, "posterior_variance: var + sigma must be positive");
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, "posterior_variance", "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, "posterior_variance", "idx1"));
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  DevBuf out;
+  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew));
+  if (m <= K) {
+    // K11 = C11 + (var + sigma) I; alpha = C21 K11^-1; beta = rowsum(C21 .* alpha)          (src/Utils.cpp:227-237)
+    DevBuf C, C12, X, work;
+    FLGP_TRY(C12.alloc(sizeof(double) * (size_t)m * mnew)); FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * mnew));
+    FLGP_TRY(hk_c11(st.s, ep, K, t, r0, c, C, work, flgp_dev_hk_workspace(m, std::max(m, mnew), K, 1)));
+    FLGP_TRY(hk(st.s, ep, K, t, r0, r1, C12.as<double>(), work.as<double>()));
+    FLGP_HIP(hipMemcpyAsync(X.p, C12.p, sizeof(double) * (size_t)m * mnew, hipMemcpyDeviceToDevice, st.s));
+    FLGP_TRY(chol_solve(st.s, C.as<double>(), m, X.as<double>(), mnew, G.flag.as<int>()));
+    FLGP_TRY(gpr_rowdot(st.s, C12.as<double>(), X.as<double>(), mnew, m, r1.V, r1.ld, K, G.l.as<double>(), c, out.as<double>()));
+  } else {
+    // alpha = 1/(var+sigma) L V1^T (V1 - V1 Ls Q^-1 Ls V1^T V1) L; beta_i = V2(i,:) alpha V2(i,:)^T  (src/Utils.cpp:238-246)
+    FLGP_TRY(r0.gather(st.s, ep, K));
+    DevBuf VtV, Q, R, T1, W, work;
+    const size_t we = (size_t)128 * K * K + 1024;
+    FLGP_TRY(VtV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(W.alloc(sizeof(double) * (size_t)mnew * K)); FLGP_TRY(work.alloc(sizeof(double) * we));
+    FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, r0.V, r0.ld, VtV.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_q(st.s, VtV.as<double>(), G.ls.as<double>(), K, c, Q.as<double>()));
+    FLGP_TRY(gpr_scale(st.s, VtV.as<double>(), G.ls.as<double>(), nullptr, K, K, R.as<double>()));          // Ls V1^T V1
+    FLGP_TRY(chol_solve(st.s, Q.as<double>(), K, R.as<double>(), K, G.flag.as<int>()));
+    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, K, R.as<double>()));            // Ls Q^-1 Ls VtV
+    FLGP_TRY(gemm_nn(st.s, K, K, K, VtV.as<double>(), K, R.as<double>(), K, T1.as<double>(), nullptr, 0));
+    FLGP_TRY(gpr_diff(st.s, VtV.as<double>(), T1.as<double>(), 1.0 / c, (long)K * K, T1.as<double>()));     // (VtV - ...)/(var+sigma)
+    FLGP_TRY(gpr_scale(st.s, T1.as<double>(), G.l.as<double>(), G.l.as<double>(), K, K, T1.as<double>()));   // L (.) L
+    FLGP_TRY(gemm_nn(st.s, mnew, K, K, r1.V, r1.ld, T1.as<double>(), K, W.as<double>(), nullptr, 0));      // V2 alpha
+    FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, W.as<double>(), mnew, K, G.l.as<double>(), c, out.as<double>()));
+  }
+  FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
+  return G.verdict(st.s, "posterior_variance");
+}
+
+// ---- classification consumers: the Laplace approximation of the logit GP on the device (gpc.hip) ---------
+namespace {
+int check_labels(const double *Y, const double *N, int m, const char *who) {
+  for (int a = 0; a < m; ++a) {
+    const double n = N ? N[a] : 1.0;
+    FLGP_REQUIRE(n > 0.0 && n < HUGE_VAL, "%s: N[%d]=%g must be positive", who, a, n);
+    FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] <= n, "%s: Y[%d]=%g is outside [0, N[%d]=%g]", who, a, Y[a], a, n);
+  }
+  return FLGP_OK;
+}
+// Newton loop + final sums on the device-resident C (m x m); only the scalar comes down
+int logit_la_on_device(hipStream_t st, const double *dC, int m, const double *Y, const double *N, double tol, int max_iter,
+                       double *amll, int *iters, const char *who) {
+  DevBuf dY, dN;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(dN.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st));
+  FLGP_TRY(h2d(dN.p, N, sizeof(double) * (size_t)m, st));
+  GpcNewton S;
+  FLGP_TRY(S.alloc(m));
+  int it = 0;
+  FLGP_TRY(S.run(st, dC, dY.as<double>(), dN.as<double>(), tol, max_iter, who, &it));
+  if (iters) *iters = it;
+  return S.amll(st, dY.as<double>(), dN.as<double>(), amll);
+}
+}  // namespace
+
+extern "C" int flgp_logit_la_marginal_likelihood(const double *C, int m, const double *Y, const double *N, double tol,
+                                                 int max_iter, double *amll, int *iters) {
+  FLGP_REQUIRE(C && Y && N && amll, "logit_la_marginal_likelihood: null pointer");
+  FLGP_REQUIRE(m >= 1 && max_iter >= 1, "logit_la_marginal_likelihood: bad shape (m=%d max_iter=%d)", m, max_iter);
+  FLGP_TRY(check_labels(Y, N, m, "logit_la_marginal_likelihood"));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dC;
+  FLGP_TRY(dC.alloc(sizeof(double) * (size_t)m * m));
+  FLGP_TRY(h2d(dC.p, C, sizeof(double) * (size_t)m * m, st.s));
+  return logit_la_on_device(st.s, dC.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_la_marginal_likelihood");
+}
+
+extern "C" int flgp_eigenpair_logit_marginal_likelihood(const flgp_eigenpair *ep, int K, double t, double sigma, const int *idx,
+                                                        int m, const double *Y, const double *N, double tol, int max_iter,
+                                                        double *amll, int *iters) {
+  FLGP_REQUIRE(ep && idx && Y && N && amll, "logit_marginal_likelihood: null pointer");
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1, "logit_marginal_likelihood: bad shape (K=%d of %d, m=%d, max_iter=%d)",
+               K, ep->K, m, max_iter);
+  Rows r0;
+  FLGP_TRY(r0.check(ep, idx, m, "logit_marginal_likelihood", "idx"));
+  FLGP_TRY(check_labels(Y, N, m, "logit_marginal_likelihood"));
+  Stream st;
+  FLGP_TRY(st.create());
+  // C = HK(idx, idx) + sigma I       (src/train.cpp:30-31)
+  DevBuf C, work;
+  FLGP_TRY(hk_c11(st.s, ep, K, t, r0, sigma, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
+  return logit_la_on_device(st.s, C.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_marginal_likelihood");
+}
+
+// posterior_distribution_classification (src/Utils.cpp:252-299) with C11 = HK(idx0, idx0) + sigma11 I,
+// C21 = HK(idx1, idx0) = V2 L V1^T, C22 = rowsum(V2 L .* V2) + sigma22.  mean = V2 L V1^T (Y - pi);
+// var_i = C22_i - v2_i^T M v2_i with M = X^T X, X = L_B^-1 sqrt(W) V1 L: O(m_new K^2), C21 is never formed.
+extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
+                                                       const int *idx0, int m, const double *Y, const int *idx1, int mnew,
+                                                       double tol, int max_iter, double *mean, double *cov) {
+  const char *who = "posterior_classification";
+  FLGP_REQUIRE(ep && idx0 && idx1 && Y && mean && cov, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && max_iter >= 1,
+               "%s: bad shape (K=%d of %d, m=%d, m_new=%d, max_iter=%d)", who, K, ep->K, m, mnew, max_iter);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  FLGP_TRY(check_labels(Y, nullptr, m, who));
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));                    // G.l = exp(-t (1 - values))
+  DevBuf C, work, dY;
+  FLGP_TRY(hk_c11(st.s, ep, K, t, r0, sigma11, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
+  // the mode (N = 1), then B factored again at the final f          (src/Utils.cpp:268-293)
+  GpcNewton S;
+  FLGP_TRY(S.alloc(m));
+  int it = 0;
+  FLGP_TRY(S.run(st.s, C.as<double>(), dY.as<double>(), nullptr, tol, max_iter, who, &it));
+  FLGP_TRY(S.weights(st.s, C.as<double>(), dY.as<double>(), nullptr));
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  DevBuf X, Mp, u, Wp, out, gw;
+  const size_t we = (size_t)128 * K * K + 1024;
+  FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
+  FLGP_TRY(Mp.alloc(sizeof(double) * (size_t)K * (K + 1)));
+  FLGP_TRY(u.alloc(sizeof(double) * (size_t)K));
+  FLGP_TRY(Wp.alloc(sizeof(double) * (size_t)mnew * (K + 1)));
+  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_TRY(gw.alloc(sizeof(double) * we));
+  FLGP_TRY(gpc_scale2(st.s, r0.V, r0.ld, S.sW.as<double>(), G.l.as<double>(), m, K, X.as<double>()));     // sqrt(W) V1 L
+  FLGP_TRY(chol_trsv(st.s, S.B.as<double>(), m, m, X.as<double>(), m, K, 1, S.flag.as<int>()));         // L_B^-1 (.)
+  FLGP_TRY(gemm_tn(st.s, K, K, m, X.as<double>(), m, X.as<double>(), m, Mp.as<double>(), gw.as<double>(), we));        // M = X^T X
+  FLGP_TRY(gemm_tn(st.s, K, 1, m, r0.V, r0.ld, S.resid.as<double>(), m, u.as<double>(), gw.as<double>(), we));         // V1^T (Y - pi)
+  FLGP_TRY(gpr_scale(st.s, u.as<double>(), G.l.as<double>(), nullptr, K, 1, Mp.as<double>() + (size_t)K * K));  // column K: L (.)
+  FLGP_TRY(gemm_nn(st.s, mnew, K + 1, K, r1.V, r1.ld, Mp.as<double>(), K, Wp.as<double>(), nullptr, 0));          // V2 [M | u]
+  FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, out.as<double>()));
+  FLGP_TRY(d2h(mean, Wp.as<double>() + (size_t)K * mnew, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
+  int bad = 0;
+  FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
+  return GpcNewton::pivot_error(bad, who, 0);      // the loop checked its own factorisations: this is the one at the mode
+}
