@@ -11,6 +11,11 @@ namespace flgp {
 void set_error(const char *fmt, ...);
 int tuning(const char *key, int dflt);
 
+// the current device's multiprocessor count and maximum LDS per block (bytes), asked once per device (core.hip); a figure
+// whose query failed is 0
+struct DeviceFigures { int cus, lds_per_block; };
+DeviceFigures device_figures();
+
 // optional per-launch HIP-event timing (core.hip); work = algorithmic flops or bytes of the launch
 int prof_begin(const char *name, hipStream_t st, double work);
 void prof_end(int idx, hipStream_t st);
@@ -141,7 +146,7 @@ inline bool is_range(const int *idx, int cnt) {
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
-                const double *E2, int *tickets = nullptr, struct GemmFusedReduce *fused = nullptr,
+                const double *E2, struct GemmFusedReduce *fused = nullptr,
                 const struct GemmPair *pair = nullptr);
 // `pair`: a second product C2 = alpha A2 B2 of the same shape and strides in the same launch (no E / E2, never split):
 // two of the solver's s x b rotations fill the chip where one leaves its fixed costs exposed.
@@ -171,11 +176,6 @@ struct GemmFusedReduce {
   int *counter;
   bool done;
 };
-// `tickets`: GEMM_MAX_TICKETS zero-initialised ints owned by the caller (one stream at a time, like `work`); with them
-// a split-K product finishes inside the GEMM kernel (the last piece of a tile to arrive adds the partial planes in a
-// fixed order) instead of in a second launch.  The kernel leaves them zero.
-constexpr int GEMM_MAX_TICKETS = 1024;
-
 
 // heat-kernel contraction on LDS-resident panels of V (hk.hip); d_vw holds hk_panel_vw_elems(n1, K) doubles
 bool hk_panel_applicable(int n0, int n1, int K, long ldh);

@@ -27,6 +27,20 @@ int tuning(const char *key, int dflt) {
   return it == g_tune.end() ? dflt : it->second;
 }
 
+DeviceFigures device_figures() {
+  static std::once_flag once[64];
+  static DeviceFigures fig[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return DeviceFigures{0, 0};
+  std::call_once(once[dev], [dev] {
+    int v = 0;
+    fig[dev].cus = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 0;
+    v = 0;
+    fig[dev].lds_per_block = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0 ? v : 0;
+  });
+  return fig[dev];
+}
+
 // ---- per-kernel HIP-event timing (off by default; bench.py switches it on) ----
 struct ProfRec { int name_id; hipEvent_t e0, e1; double work; };
 static std::mutex g_prof_mu;

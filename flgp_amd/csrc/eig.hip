@@ -1172,7 +1172,6 @@ struct EigWork {
   double *T, *JB, *JV, *W, *X2, *Id;
   double *lam, *scale, *res, *theta, *dinv, *gemm_ws, *apriori;   // res (b) and theta (b) are adjacent: one copy to the host
   int *perm, *flags;
-  int *tickets;         // GEMM_MAX_TICKETS zeroed counters of the in-kernel split-K reduction (main stream only)
   double *red;          // one double per 16 x 16 tile of a b x b matrix + an int counter (zero between launches): GemmFusedReduce
   int *redcnt;
   size_t gemm_ws_elems;
@@ -1234,7 +1233,7 @@ static size_t eig_workspace_bytes(int s, int K, const EigParams &P) {
   if (!dense) tot += 5 * align_up(sizeof(double) * (size_t)s * b);
   tot += 6 * align_up(sizeof(double) * (size_t)b * b);
   tot += 5 * align_up(sizeof(double) * (size_t)b) + align_up(sizeof(double) * 2 * APRIORI_BLOCKS);
-  tot += align_up(sizeof(int) * (size_t)b) + align_up(sizeof(int) * 16) + align_up(sizeof(int) * GEMM_MAX_TICKETS);
+  tot += align_up(sizeof(int) * (size_t)b) + align_up(sizeof(int) * 16);
   if (!dense) tot += align_up(sizeof(double) * eig_gemm_ws_elems(s, b));
   if (!dense) tot += align_up(sizeof(double) * ((size_t)ceil_div(b, 16) * ceil_div(b, 16) + 2));
   if (!dense && s >= 1024) tot += bsg_workspace_bytes(s, b);   // (used from s = 1536 on by default; tunable)
@@ -1446,7 +1445,7 @@ struct EigSolver {
   int gemmG(const double *Xin, double alpha, double beta, const double *E, double gamma, const double *E2,
                        double *out) {  // out = alpha G Xin + beta E + gamma E2   (s x b)
     return gemm_launch(st, s, b, s, alpha, dG, 1, ldg, Xin, 1, s, beta, E, 1, s, out, 1, s, w.gemm_ws,
-                       w.gemm_ws_elems, gamma, E2, w.tickets);
+                       w.gemm_ws_elems, gamma, E2);
   }
   // ---- block-sparse products (bs.on): blocks live transposed (b x s, the b values of one row contiguous) while
   //      the filter runs, so that both the tiled GEMM (over the listed k stages of P G P^T) and the CSR remainder
@@ -1475,19 +1474,19 @@ struct EigSolver {
   int gram_small(const double *Xa, const double *Xb, double *out, GemmFusedReduce *fr = nullptr) {  // out = Xa^T Xb   (b x b)
     if (gramk_applicable(s, b, Xa, Xb, w.gemm_ws_elems)) return gramk_launch(st, s, b, Xa, Xb, out, w.gemm_ws, w.gemm_ws_elems, fr);
     return gemm_launch(st, b, b, s, 1.0, Xa, s, 1, Xb, 1, s, 0.0, nullptr, 0, 0, out, 1, b, w.gemm_ws,
-                       w.gemm_ws_elems, 0.0, nullptr, w.tickets, fr);
+                       w.gemm_ws_elems, 0.0, nullptr, fr);
   }
   int rotate(const double *Xin, const double *Wm, double *out) {  // out = Xin Wm   (s x b)(b x b)
     if (use_rot) return rot_launch(st, s, b, 1.0, Xin, nullptr, Wm, 0.0, nullptr, nullptr, out, nullptr);
     return gemm_launch(st, s, b, b, 1.0, Xin, 1, s, Wm, 1, b, 0.0, nullptr, 0, 0, out, 1, s, w.gemm_ws,
-                       w.gemm_ws_elems, 0.0, nullptr, w.tickets);
+                       w.gemm_ws_elems, 0.0, nullptr);
   }
   // two rotations by the same W in one launch (the Ritz vectors and G times them)
   int rotate2(const double *X1, const double *X2, const double *Wm, double *out1, double *out2) {
     if (use_rot) return rot_launch(st, s, b, 1.0, X1, X2, Wm, 0.0, nullptr, nullptr, out1, out2);
     const GemmPair pr{X2, Wm, out2};
     return gemm_launch(st, s, b, b, 1.0, X1, 1, s, Wm, 1, b, 0.0, nullptr, 0, 0, out1, 1, s, w.gemm_ws, w.gemm_ws_elems, 0.0,
-                       nullptr, nullptr, nullptr, &pr);
+                       nullptr, nullptr, &pr);
   }
   int small_gemm(const double *Am, const double *Bm, double alpha, double beta, const double *E,
                             double *out) {  // out = alpha Am Bm + beta E   (b x b, column-major)
@@ -1945,7 +1944,7 @@ struct EigSolver {
       FLGP_TRY(check_launch("mask_strict_upper_kernel"));
     }
     return gemm_launch(st, s, b, b, -1.0, w.Qold, 1, s, w.T, 1, b, 1.0, cur, 1, s, cur, 1, s, w.gemm_ws, w.gemm_ws_elems,
-                       0.0, nullptr, w.tickets);
+                       0.0, nullptr);
   }
 
   // ---- Rayleigh-Ritz and convergence -------------------------------------------------------------
@@ -2213,8 +2212,6 @@ static int eig_topk_impl(void *stream, const double *dG, int ldg, int s, int K, 
   w.res = (double *)take(sizeof(double) * 2 * b); w.theta = w.res + b; w.dinv = (double *)take(sizeof(double) * b);
   w.apriori = (double *)take(sizeof(double) * 2 * APRIORI_BLOCKS);
   w.perm = (int *)take(sizeof(int) * b); w.flags = (int *)take(sizeof(int) * 16);
-  w.tickets = (int *)take(sizeof(int) * GEMM_MAX_TICKETS);
-  FLGP_HIP(hipMemsetAsync(w.tickets, 0, sizeof(int) * GEMM_MAX_TICKETS, st));
   w.gemm_ws_elems = dense ? 0 : eig_gemm_ws_elems(s, b);
   w.gemm_ws = dense ? nullptr : (double *)take(sizeof(double) * w.gemm_ws_elems);
   w.red = nullptr; w.redcnt = nullptr;

@@ -44,22 +44,10 @@ struct GemmArgs {
   int shift_edges;                    // edge tiles slide back inside the matrix (they recompute a few columns / rows)
   int ksplit_len;                     // k range per blockIdx.z (multiple of GK); partials when gridDim.z > 1
   double *part;                       // [z][M][N] row-major partials
-  // in-kernel split-K reduction (optional): one counter per output tile, all zero between launches.  The pieces of a
-  // tile store their accumulators as planes of PLANE doubles in the thread order they are held in, take a ticket, and
-  // the piece that arrives last adds the planes in ascending z (a fixed order: deterministic) and runs the epilogue.
-  int *tickets;
   // a second product of the same shape in the same launch (gridDim.y = 2): its own operands and result, everything else shared
   const double *A2, *B2;
   double *C2;
 };
-
-constexpr int PLANE = GB * GB;    // doubles per partial plane of one 128 x 128 tile
-
-// 16-byte store that is written through to the memory side (sc1), so that a workgroup on another XCD can read it
-// after the ticket hand-off without a release fence over this XCD's whole L2 (MI355X guide: "publish-large")
-__device__ __forceinline__ void store_wt_d2(double *p, d2 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-}
 
 // ---- operand staging: a 128(rows) x 16(k) tile goes global -> 8 registers per thread -> LDS [k][row].
 // Three thread mappings, chosen per operand and per stage (uniform over the workgroup):
@@ -427,67 +415,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
   if (!done) pipeline(no_t{}, rc_t{}, rc_t{});
 
   // epilogue: D(row = (lane>>4) + 4*reg, col = lane&15) of each 16x16 tile
-  const bool partial = gridDim.z > 1;
-  if constexpr (GBT == 128) if (partial && g.tickets) {
-    // ---- split-K finished inside the kernel
-    __shared__ int last_piece;
-    const int tile_id = tm * ntn + tn;
-    const int npieces = (int)gridDim.z;
-    if (npieces > 1) {
-      double *plane = g.part + ((size_t)zidx * nt + tile_id) * PLANE;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            store_wt_d2(plane + ((size_t)((mi * 4 + ni) * 2 + h) * 256 + tid) * 2, d2{acc[mi][ni][2 * h], acc[mi][ni][2 * h + 1]});
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(&g.tickets[tile_id], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_piece = (old == npieces - 1);
-        if (old == npieces - 1) {
-          __hip_atomic_store(&g.tickets[tile_id], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-      }
-      __syncthreads();
-      if (!last_piece) return;
-      const double *p0 = g.part + (size_t)tile_id * PLANE + (size_t)tid * 2;
-      const size_t zstride = (size_t)nt * PLANE;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        d2 sum[4][2];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) sum[ni][h] = d2{0.0, 0.0};
-        for (int z = 0; z < npieces; ++z) {   // ascending z: the order does not depend on which piece came last
-          d2 v[4][2];
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-              v[ni][h] = __builtin_nontemporal_load((const d2 *)(p0 + z * zstride + (size_t)((mi * 4 + ni) * 2 + h) * 512));
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) sum[ni][h] += v[ni][h];
-        }
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          acc[mi][ni][0] = sum[ni][0][0]; acc[mi][ni][1] = sum[ni][0][1];
-          acc[mi][ni][2] = sum[ni][1][0]; acc[mi][ni][3] = sum[ni][1][1];
-        }
-      }
-    }
-  }
   // The 16 MI^2 results of a thread go out through one base pointer and compile-time multiples of the two strides; which
   // terms the epilogue has (planes / E / E2) and whether the tile needs bounds checks is decided once, not per element
   // (per element it was a chain of scalar branches and three 64-bit multiply-adds: ~20 instructions each, 3 us per tile).
-  const bool to_planes = partial && !g.tickets;
+  const bool to_planes = gridDim.z > 1;
   const int ti0 = row0 + wr + fk, tj0 = col0 + wc + fr;
   auto emit = [&](auto pl_c, auto he_c, auto he2_c, auto in_c) {
     constexpr bool PL = decltype(pl_c)::value, HE = decltype(he_c)::value, HE2 = decltype(he2_c)::value, IN = decltype(in_c)::value;
@@ -634,7 +565,7 @@ int gemm_split_limit(int Kd, int ntiles, int gk, bool tile64) {
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
-                const double *E2, int *tickets, GemmFusedReduce *fused, const GemmPair *pair) {
+                const double *E2, GemmFusedReduce *fused, const GemmPair *pair) {
   if (fused) fused->done = false;
   if (pair && (E || E2 || fused)) { set_error("gemm: a paired product takes no E / E2 / fused reduction"); return FLGP_ERR_INVALID; }
   if (M <= 0 || N <= 0) return FLGP_OK;
@@ -656,17 +587,14 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
     if (pair) { g.A2 = pair->A2; g.B2 = pair->B2; }
   }
   if (!pair) { g.A2 = g.B2 = nullptr; g.C2 = nullptr; } else g.C2 = pair->C2;
-  g.tickets = (work && !fused && !pair && tuning("gemm_fused_reduce", 0)) ? tickets : nullptr;
   g.alpha = alpha; g.beta = beta; g.gamma = gamma;
   g.E2 = (gamma == 0.0) ? nullptr : E2;
   if (beta == 0.0) g.E = nullptr;
   // tile size: 64 where tiles of 128 would leave most of the 256 CUs without one (the solver's s x b and b x b products)
   int gbt = GB;
-  if (ceil_div(g.M, GB) * ceil_div(g.N, GB) < tuning("gemm_tile64_below", 200) && !g.tickets) gbt = 64;
+  if (ceil_div(g.M, GB) * ceil_div(g.N, GB) < tuning("gemm_tile64_below", 200)) gbt = 64;
   const int ntiles = ceil_div(g.M, gbt) * ceil_div(g.N, gbt);
-  if (ntiles > GEMM_MAX_TICKETS) g.tickets = nullptr;
-  // one partial plane: M x N doubles for the reduction kernel, whole 128 x 128 tiles for the in-kernel reduction
-  const size_t per = g.tickets ? (size_t)ntiles * PLANE : (size_t)g.M * g.N;
+  const size_t per = (size_t)g.M * g.N;   // one partial plane
   int nsplit = 1;
   if (work && !pair && ntiles < 256 && Kd >= 8 * GK) {
     nsplit = gemm_split_limit(Kd, ntiles, GK, gbt == 64);
@@ -681,24 +609,18 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
   // overlapping tiles write some elements twice: harmless unless the epilogue reads what it overwrites
   // (with the reduction kernel every element is written exactly once, by that kernel, whatever the tiles overlap)
   const bool aliased = (const double *)g.C == g.E || (const double *)g.C == g.E2;
-  g.shift_edges = ((nsplit > 1 && !g.tickets) || !aliased) ? 1 : 0;
+  g.shift_edges = (nsplit > 1 || !aliased) ? 1 : 0;
   {
     const double fl = 2.0 * (double)M * (double)N * (double)Kd;
     ProfScope ps("gemm_f64_kernel", st, fl);
     // second record per shape class (large / medium / small) for the bench breakdown
     ProfScope ps2(fl > 5e9 ? "gemm_large" : (fl > 2e8 ? "gemm_medium" : "gemm_small"), st, fl);
     const int ny = pair ? 2 : 1;
-    // unused dynamic LDS caps the workgroups the dispatcher may stack on one CU (experiment knob, KB)
-    const int pad_kb = (gbt == 64) ? tuning("gemm_lds_pad_kb", 0) : 0;
-    if (pad_kb > 0) {
-      static int attr_set = 0;
-      if (!attr_set) { FLGP_HIP(hipFuncSetAttribute((const void *)gemm_f64_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024)); attr_set = 1; }
-    }
-    if (gbt == 64) hipLaunchKernelGGL(gemm_f64_kernel<64>, dim3(ntiles, ny, nsplit), dim3(256), (size_t)pad_kb * 1024, st, g);
+    if (gbt == 64) hipLaunchKernelGGL(gemm_f64_kernel<64>, dim3(ntiles, ny, nsplit), dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_f64_kernel<128>, dim3(ntiles, ny, nsplit), dim3(256), 0, st, g);
   }
   FLGP_TRY(check_launch("gemm_f64_kernel"));
-  if (!g.tickets && nsplit > 1) {
+  if (nsplit > 1) {
     if (fused && g.M == g.N && alpha == 1.0 && !g.E && !g.E2 && (g.c_is == 1 || g.c_js == 1)) {
       const int nt1 = ceil_div(g.M, 16);
       hipLaunchKernelGGL(splitk_reduce_sym_kernel, dim3(nt1 * nt1), dim3(256), 0, st, g, nsplit, fused->mode, fused->dinv,
@@ -755,7 +677,7 @@ int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, do
   g.alpha = 1.0; g.beta = 0.0; g.gamma = 0.0;
   g.E = g.E2 = nullptr; g.e_is = g.e_js = 0;
   g.C = C; g.c_is = b; g.c_js = 1;            // kernel (i, j) = caller (column, row), as gemm_launch orients a column-major result
-  g.shift_edges = 0; g.ksplit_len = 0; g.part = const_cast<double *>(part); g.tickets = nullptr;
+  g.shift_edges = 0; g.ksplit_len = 0; g.part = const_cast<double *>(part);
   g.A2 = g.B2 = nullptr; g.C2 = nullptr;
   if (fused) {
     const int nt1 = ceil_div(b, 16);
@@ -775,7 +697,7 @@ extern "C" int flgp_dev_gemm_pair(void *stream, int M, int N, int Kd, double alp
   FLGP_REQUIRE(M >= 0 && N >= 0 && Kd >= 0 && A && B && C && A2 && B2 && C2, "gemm_pair: bad arguments");
   const GemmPair pr{A2, B2, C2};
   return gemm_launch((hipStream_t)stream, M, N, Kd, alpha, A, a_is, a_ks, B, b_ks, b_js, 0.0, nullptr, 0, 0, C, c_is, c_js,
-                     nullptr, 0, 0.0, nullptr, nullptr, nullptr, &pr);
+                     nullptr, 0, 0.0, nullptr, nullptr, &pr);
 }
 
 extern "C" int flgp_dev_gather_rows(void *stream, const double *dV, int ld, const int *d_idx, int n0, int K,

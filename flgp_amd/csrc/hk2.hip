@@ -35,6 +35,9 @@ constexpr unsigned BUF_WORD3 = 0x00020000u;      // raw buffer, 32-bit data form
 
 constexpr int HP2 = 64;             // rows of V0 per panel
 constexpr int HK2_WAVES = 8;
+// H is written once and not read again on the device: non-temporal stores (aux bit 1) keep it from pushing the L2-resident
+// small operand and the next panels out of the caches
+constexpr int H_STORE_AUX = 2;
 
 struct Hk2Args {
   const double *V0; long ld0; int n0;     // V0(a, k) = V0[a + k ld0], a < n0
@@ -45,9 +48,9 @@ struct Hk2Args {
   int nblocks;                            // panels: ceil(n0 / HP2)
 };
 
-// Round 4.  (1) The stage count follows K exactly: NKS k steps (K = 200: 50, not 52 -- 4 % of the MFMAs were multiplications
-// by the zero padding); a ring stage is two k steps, so NKP = NKS / 2 may be odd (25) and the two-slot ring then changes
-// parity from one tile to the next: the tile body takes the parity as a template parameter.  (2) The next panel no longer
+// Round 4.  (1) The stage count is a template parameter: NKS k steps (hk2_nks).  A ring stage is two k steps, so NKP =
+// NKS / 2 may be odd (13) and the two-slot ring then changes parity from one tile to the next: the tile body takes the
+// parity as a template parameter.  (2) The next panel no longer
 // waits in 56 VGPRs through the whole last tile (484 bytes of scratch per lane, re-written every panel: 1.9 GB of HBM
 // writes per launch that were not H): LDS holds TWO copies of the panel's first NA k steps (A0 / A1, used alternately) and
 // one of the remaining NB = NKS - NA (B) -- (2 NA + NB) x 2 KB <= 156 KB.  During a panel's last tile the next panel's A part
@@ -55,7 +58,7 @@ struct Hk2Args {
 // doubles per lane) is kept in registers until the barrier that frees B.  The fetch is unconditional (the last panel fetches
 // itself again) so that every path into a tile has the same queue of outstanding loads and the compiler's vmcnt counts
 // stay exact.
-template <int NKS, int NA, int STORE_AUX>
+template <int NKS, int NA>
 __global__ __launch_bounds__(512, 1) void hk_panel2_kernel(Hk2Args g) {
   static_assert(NKS % 2 == 0 && NA <= NKS && NA >= 8, "k steps come in ring stages of two");
   constexpr int NKP = NKS / 2;            // ring stages per tile
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(512, 1) void hk_panel2_kernel(Hk2Args g) {
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
               const double v = acc[m][ni][reg];      // (a copy: __builtin_bit_cast of the vector element itself took element 0)
-              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ku2, v), h_rsrc, h_lane + (unsigned)(ni * 128), row_off[m][reg], STORE_AUX);
+              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ku2, v), h_rsrc, h_lane + (unsigned)(ni * 128), row_off[m][reg], H_STORE_AUX);
             }
           }
       } else {
@@ -232,7 +235,7 @@ __global__ __launch_bounds__(512, 1) void hk_panel2_kernel(Hk2Args g) {
             for (int ni = 0; ni < 4; ++ni)
               if (a0 + ni * 16 < (long)g.n0 && b < g.n1) {
                 const double v = acc[m][ni][reg];
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ku2, v), h_rsrc, h_lane + (unsigned)(ni * 128), row_off[m][reg], STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ku2, v), h_rsrc, h_lane + (unsigned)(ni * 128), row_off[m][reg], H_STORE_AUX);
               }
           }
       }
@@ -292,24 +295,14 @@ __global__ void hk2_scale_kernel(const double *__restrict__ values, int K, int n
 static int hk2_nks(int K) {
   const int ks = (K + 3) / 4;
   if (ks > 52 || ks < 23) return 0;
-  // 47..50 steps run in the 52-step instance by default: it needs no scratch (the 50-step one keeps 68 B per lane, 1 GB of
-  // HBM traffic per launch at configs[2]) and takes the same time -- at the power-limited clock the MFMAs on the zero padding
-  // cost nothing (7.18 / 7.19 ms in the path either way).  hk2_pad52 = 0: the exact-K instance.
-  if (ks > 50 || (ks >= 47 && tuning("hk2_pad52", 1))) return 52;
-  if (ks > 28) return ks >= 47 ? 50 : 0;
+  // 47..52 steps run in the 52-step instance: it needs no scratch (an exact 50-step one kept 68 B per lane, 1 GB of HBM
+  // traffic per launch at configs[2]) and takes the same time -- at the power-limited clock the MFMAs on the zero padding
+  // cost nothing (7.18 / 7.19 ms in the path either way).
+  if (ks >= 47) return 52;
+  if (ks > 28) return 0;
   return ks > 26 ? 28 : 26;
 }
-static int hk2_na(int nks) { return nks == 50 ? 28 : 26 + (nks == 28 ? 2 : 0); }   // 50 -> 28, 52 -> 26, 28 -> 28, 26 -> 26: (2 NA + NB) <= 78 k steps of 2 KB
-
-static int hk2_lds_limit() {         // per device: the kernels want up to 156 KB of dynamic LDS
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  static int cache[64];
-  if (cache[dev]) return cache[dev];
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) v = 0;
-  cache[dev] = v;
-  return v;
-}
+static int hk2_na(int nks) { return nks == 28 ? 28 : 26; }   // 52 -> 26, 28 -> 28, 26 -> 26: (2 NA + NB) <= 78 k steps of 2 KB
 
 bool hk_panel2_applicable(int n0, int n1, int K, long ldh) {
   const int nks = hk2_nks(K);
@@ -317,7 +310,7 @@ bool hk_panel2_applicable(int n0, int n1, int K, long ldh) {
   const int slots = 2 * hk2_na(nks) + (nks - hk2_na(nks));
   return tuning("hk_panel", 1) && tuning("hk_panel2", 1) && n1 >= tuning("hk_panel2_min_n1", 480) &&    // (fewer than 15 tile pairs leave waves without work)
          n0 >= tuning("hk_panel_min_n0", 2048) && ldh <= 7000000L && n1 <= 100000 &&   // (store offsets of a tile pair, (35 ldh + 63) * 8, and the operand's size stay below 2^31)
-         hk2_lds_limit() >= slots * 2048;       // (a device with less LDS takes the tiled GEMM that is still in the dispatcher)
+         device_figures().lds_per_block >= slots * 2048;   // (up to 156 KB of dynamic LDS: a device with less takes the tiled GEMM that is still in the dispatcher)
 }
 
 int hk_panel2_launch(hipStream_t st, const double *d_values, int K, double t, const double *V0, long ld0, int n0,
@@ -334,17 +327,8 @@ int hk_panel2_launch(hipStream_t st, const double *d_values, int K, double t, co
   g.K = K;
   g.H = dH; g.ldh = ldh;
   g.nblocks = ceil_div(n0, HP2);
-  int dev = 0, n_cu = 0;
-  (void)hipGetDevice(&dev);
-  {
-    static int cu_cache[64];      // keyed by device (the first caller's count was used for every device)
-    if (dev >= 0 && dev < 64 && cu_cache[dev]) n_cu = cu_cache[dev];
-    else {
-      if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-      if (dev >= 0 && dev < 64) cu_cache[dev] = n_cu;
-    }
-  }
-  int grid = n_cu;
+  const int cus = device_figures().cus;
+  int grid = cus > 0 ? cus : 256;
   if (grid > g.nblocks) grid = g.nblocks;
   const size_t lds = sizeof(double) * (size_t)(2 * na + (nks - na)) * HP2 * 4;
   const double fl = 2.0 * (double)n0 * (double)n1 * (double)K;
@@ -354,14 +338,10 @@ int hk_panel2_launch(hipStream_t st, const double *d_values, int K, double t, co
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, g);
     return FLGP_OK;
   };
-  // H is written once and not read again on the device: non-temporal stores (aux bit 1) keep it from pushing the
-  // L2-resident small operand and the next panels out of the caches (knob hk_store_nt, default on: see DESIGN.md)
-  const bool nt = tuning("hk_store_nt", 1) != 0;
   switch (nks) {
-    case 50: if (nt) FLGP_TRY(go(hk_panel2_kernel<50, 28, 2>)); else FLGP_TRY(go(hk_panel2_kernel<50, 28, 0>)); break;
-    case 52: if (nt) FLGP_TRY(go(hk_panel2_kernel<52, 26, 2>)); else FLGP_TRY(go(hk_panel2_kernel<52, 26, 0>)); break;
-    case 28: if (nt) FLGP_TRY(go(hk_panel2_kernel<28, 28, 2>)); else FLGP_TRY(go(hk_panel2_kernel<28, 28, 0>)); break;
-    default: if (nt) FLGP_TRY(go(hk_panel2_kernel<26, 26, 2>)); else FLGP_TRY(go(hk_panel2_kernel<26, 26, 0>)); break;
+    case 52: FLGP_TRY(go(hk_panel2_kernel<52, 26>)); break;
+    case 28: FLGP_TRY(go(hk_panel2_kernel<28, 28>)); break;
+    default: FLGP_TRY(go(hk_panel2_kernel<26, 26>)); break;
   }
   return check_launch("hk_panel2_kernel");
 }

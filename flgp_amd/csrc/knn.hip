@@ -379,9 +379,7 @@ template <int DP, int RCAP>
 __global__ __launch_bounds__(256, 2) void knn_screen_kernel(const double *__restrict__ X, int n, int ldx, int d,
                                                             const double *__restrict__ Ut, const double *__restrict__ uu,
                                                             int s, int r, int *__restrict__ idx_out,
-                                                            double *__restrict__ dist_out, int ldo, int stop_after) {
-  // stop_after (tuning knob knn_screen_stop, 0 in production): 1 / 2 = return after pass 1 / pass 2 without results, so
-  // that scripts/knn_time.py can time the phases of this one kernel
+                                                            double *__restrict__ dist_out, int ldo) {
   constexpr int NT = 256, PB = 256, CH = 256, QC = KNN_SCREEN_QC;
   static_assert(DP == 4 || DP == 8 || DP == 16, "the screen panel is written for dpad 4, 8 and 16");
   static_assert(CH == 256, "one 1 KB LDS-DMA moves a chunk's start values");
@@ -459,9 +457,7 @@ __global__ __launch_bounds__(256, 2) void knn_screen_kernel(const double *__rest
     tau[t] = off[t] ? __builtin_inff() : m - KNN_SCREEN_MU * xxf[t];
     __syncthreads();
   }
-  if (stop_after == 1) { if (tau[0] + tau[1] == 12345.0f) idx_out[0] = 0; return; }
   screen_sweep<1, CH, QC, PB>(panel, ctab + s_pad, nch, abuf, cbuf, q, bhi, blo, g, tau, cnt, tid);
-  if (stop_after == 2) { if (cnt[0] + cnt[1] == 123456) idx_out[0] = 0; return; }
 #pragma unroll
   for (int t = 0; t < 2; ++t) qcnt[kh * PB + w * 64 + t * 32 + col] = off[t] ? QC + 1 : cnt[t] / (4 * PB);
   __syncthreads();
@@ -857,7 +853,7 @@ static int launch_knn_screen(hipStream_t st, const double *dX, int n, int ldx, i
                              const double *duu, int s, int r, int *d_idx, double *d_dist, int ldo) {
   ProfScope ps("knn_kernel", st, 2.0 * (double)n * (double)s * (double)d);
   hipLaunchKernelGGL((knn_screen_kernel<DP, RCAP>), dim3(ceil_div(n, 256)), dim3(256), 0, st, dX, n, ldx, d, dUt, duu, s,
-                     r, d_idx, d_dist, ldo, tuning("knn_screen_stop", 0));
+                     r, d_idx, d_dist, ldo);
   return check_launch("knn_screen_kernel");
 }
 
@@ -918,10 +914,8 @@ extern "C" int flgp_dev_knn(void *stream, const double *dX, int n, int ldx, int 
   if (n == 0) return FLGP_OK;
   if (dpad > 64) return knn_wide(st, dX, n, ldx, d, dUt, dpad, duu, s, r, d_idx, d_dist, ldo);
   const int rcap = r <= 4 ? 4 : (r <= 8 ? 8 : (r <= 16 ? 16 : 32));
-  const int variant = tuning("knn_variant", 0);
-  if (r == 1 && tuning("knn_nn1", 1)) {   // the 1-NN of Lloyd's assignment step and of the cluster counts
-    const int v1 = tuning("knn_nn1_variant", 0);
-    if (v1 == 0 || v1 == 5) {
+  if (r == 1) {   // the 1-NN of Lloyd's assignment step and of the cluster counts (knn_nn1_variant != 0: the VALU kernels)
+    if (tuning("knn_nn1_variant", 0) == 0) {
       if (dpad == 4) return launch_knn1_mfma<4>(st, dX, n, ldx, d, dUt, duu, s, d_idx, d_dist);
       if (dpad == 8) return launch_knn1_mfma<8>(st, dX, n, ldx, d, dUt, duu, s, d_idx, d_dist);
       if (dpad == 16) return launch_knn1_mfma<16>(st, dX, n, ldx, d, dUt, duu, s, d_idx, d_dist);
@@ -930,13 +924,7 @@ extern "C" int flgp_dev_knn(void *stream, const double *dX, int n, int ldx, int 
     }
     if (dpad == 4) return launch_knn<4, 1, 2, 4, 2, 12>(KNN_ARGS);
     if (dpad == 8) return launch_knn<8, 1, 2, 4, 4, 12>(KNN_ARGS);
-    if (dpad == 16) {
-      if (v1 == 1) return launch_knn<16, 1, 1, 2, 8, 8>(KNN_ARGS);
-      if (v1 == 2) return launch_knn<16, 1, 1, 4, 8, 8>(KNN_ARGS);
-      if (v1 == 3) return launch_knn<16, 1, 2, 4, 8, 8>(KNN_ARGS);
-      if (v1 == 4) return launch_knn<16, 1, 4, 2, 8, 8>(KNN_ARGS);
-      return launch_knn<16, 1, 4, 2, 8, 8>(KNN_ARGS);
-    }
+    if (dpad == 16) return launch_knn<16, 1, 4, 2, 8, 8>(KNN_ARGS);
     if (dpad == 32) return launch_knn<32, 1, 1, 2, 16, 8>(KNN_ARGS);
     if (dpad == 64) return launch_knn<64, 1, 1, 2, 16, 8>(KNN_ARGS);
   }
@@ -946,7 +934,7 @@ extern "C" int flgp_dev_knn(void *stream, const double *dX, int n, int ldx, int 
   // per 1e6 points).  knn_mfma = 1 / 0 forces one or the other.
   // d <= 16, r <= 16, enough anchors for 32 groups of them: the matrix-core screen (knn_screen = 0 switches it off)
   if (dpad <= 16 && r >= 2 && r <= 16 && s >= 512 && s <= 32768 && tuning("knn_screen", 1) &&
-      tuning("knn_mfma", -1) < 0 && variant == 0) {
+      tuning("knn_mfma", -1) < 0) {
 #define KNN_SCREEN_CASE(DPv, RCv) if (dpad == DPv && rcap == RCv) return launch_knn_screen<DPv, RCv>(KNN_ARGS);
     KNN_SCREEN_CASE(4, 4) KNN_SCREEN_CASE(4, 8) KNN_SCREEN_CASE(4, 16)
     KNN_SCREEN_CASE(8, 4) KNN_SCREEN_CASE(8, 8) KNN_SCREEN_CASE(8, 16)
@@ -961,18 +949,6 @@ extern "C" int flgp_dev_knn(void *stream, const double *dX, int n, int ldx, int 
     KNN_MFMA_CASE(16, 4) KNN_MFMA_CASE(16, 8) KNN_MFMA_CASE(16, 16) KNN_MFMA_CASE(16, 32)
     KNN_MFMA_CASE(32, 4) KNN_MFMA_CASE(32, 8) KNN_MFMA_CASE(32, 16) KNN_MFMA_CASE(32, 32)
     KNN_MFMA_CASE(64, 4) KNN_MFMA_CASE(64, 8) KNN_MFMA_CASE(64, 16) KNN_MFMA_CASE(64, 32)
-  }
-  // experimental shapes, d <= 16 and r <= 16 only (selected through flgp_set_tuning)
-  if (dpad == 16 && rcap == 16) {
-    if (variant == 1) return launch_knn<16, 16, 2, 4, 8, 12>(KNN_ARGS);
-    if (variant == 2) return launch_knn<16, 16, 2, 2, 16, 8>(KNN_ARGS);
-    if (variant == 4) return launch_knn<16, 16, 1, 4, 0, 12>(KNN_ARGS);
-    if (variant == 5) return launch_knn<16, 16, 1, 2, 16, 8>(KNN_ARGS);
-    if (variant == 6) return launch_knn<16, 16, 1, 2, 8, 8>(KNN_ARGS);
-    if (variant == 7) return launch_knn<16, 16, 1, 2, 4, 8>(KNN_ARGS);
-    if (variant == 8) return launch_knn<16, 16, 1, 2, 12, 8>(KNN_ARGS);
-    if (variant == 9) return launch_knn<16, 16, 1, 1, 8, 8>(KNN_ARGS);
-    if (variant == 10) return launch_knn<16, 16, 1, 2, 0, 8>(KNN_ARGS);
   }
   KNN_CASE(4, 4) KNN_CASE(4, 8) KNN_CASE(4, 16) KNN_CASE(4, 32)
   KNN_CASE(8, 4) KNN_CASE(8, 8) KNN_CASE(8, 16) KNN_CASE(8, 32)

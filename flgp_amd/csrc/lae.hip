@@ -260,11 +260,9 @@ extern "C" int flgp_dev_lae(void *stream, const double *dX, int n, int ldx, int 
   if (n == 0) return FLGP_OK;
   int *it = nullptr;
 #define LAE_ARGS st, dX, n, ldx, d, dUt, dpad, r, d_knn_idx, ldk, d_ell_idx, d_ell_val, it
-  if (tuning("lae_variant", 1) == 1) {
-    // register-resident kernels (lae_reg.h) where r x d/lanes fits the VGPR file; LDS kernels otherwise
-    const int rc = launch_lae_reg(st, dX, n, ldx, d, dUt, dpad, r, d_knn_idx, ldk, d_ell_idx, d_ell_val);
-    if (rc != FLGP_LAE_REG_NONE) return rc;
-  }
+  // register-resident kernels (lae_reg.h) where r x d/lanes fits the VGPR file; LDS kernels otherwise
+  const int rc = launch_lae_reg(st, dX, n, ldx, d, dUt, dpad, r, d_knn_idx, ldk, d_ell_idx, d_ell_val);
+  if (rc != FLGP_LAE_REG_NONE) return rc;
   switch (r) {
     case 1: return launch_lae<1, true>(LAE_ARGS);
     case 2: return launch_lae<2, true>(LAE_ARGS);

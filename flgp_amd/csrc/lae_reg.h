@@ -303,21 +303,20 @@ int launch_lae_reg_t(FLGP_LAE_REG_ARGS) {
 // Kernels built for a compile-time r.  One lane per point on the narrowest slice that holds d; once
 // R x 16 doubles no longer fit the 256 architectural VGPRs (R >= 9: the rest would sit in AGPRs behind
 // two v_accvgpr_read per operand) two lanes share a point.  Measured on 1e6 points, r = 10, d = 16:
-// 16x1 3.0 ms, 8x2 2.6 ms, 4x4 4.0 ms; LDS-resident kernel 8.5 ms (scripts/exp_lae.py).
+// 16x1 3.0 ms, 8x2 2.6 ms, 4x4 4.0 ms; LDS-resident kernel 8.5 ms (NOTEBOOK.md, LAE).
 template <int R>
-int launch_lae_reg_r(FLGP_LAE_REG_ARGS, int force_dpl, int force_lp) {
-  if (force_dpl == 4 && force_lp == 4 && d <= 16) return launch_lae_reg_t<R, 4, 4>(FLGP_LAE_REG_PASS);
-  if (force_dpl == 8 && force_lp == 4 && d <= 32) return launch_lae_reg_t<R, 8, 4>(FLGP_LAE_REG_PASS);
-  if (force_dpl == 8 && force_lp == 2 && d <= 16) return launch_lae_reg_t<R, 8, 2>(FLGP_LAE_REG_PASS);
+int launch_lae_reg_r(FLGP_LAE_REG_ARGS) {
   if (d <= 4) return launch_lae_reg_t<R, 4, 1>(FLGP_LAE_REG_PASS);
   if (d <= 8) return launch_lae_reg_t<R, 8, 1>(FLGP_LAE_REG_PASS);
-  if constexpr (R <= 10) {
-    if (d <= 16 && (R <= 8 || force_dpl == 16)) return launch_lae_reg_t<R, 16, 1>(FLGP_LAE_REG_PASS);
+  if constexpr (R <= 8) {
+    if (d <= 16) return launch_lae_reg_t<R, 16, 1>(FLGP_LAE_REG_PASS);
+  } else {
     if (d <= 16) return launch_lae_reg_t<R, 8, 2>(FLGP_LAE_REG_PASS);
+  }
+  if constexpr (R <= 10) {
     if (d <= 32) return launch_lae_reg_t<R, 16, 2>(FLGP_LAE_REG_PASS);
     if (d <= 64) return launch_lae_reg_t<R, 16, 4>(FLGP_LAE_REG_PASS);
   } else {
-    if (d <= 16) return launch_lae_reg_t<R, 8, 2>(FLGP_LAE_REG_PASS);
     if (d <= 32) return launch_lae_reg_t<R, 8, 4>(FLGP_LAE_REG_PASS);
   }
   return FLGP_LAE_REG_NONE;

@@ -13,7 +13,6 @@
 //     contiguous bytes of a column of out.
 // Tile 64 x 64, four waves of 32 x 32; gridDim.y = 2 runs a second rotation by the same W (the Rayleigh-Ritz pair).
 #include "common.h"
-#include <mutex>
 #include <type_traits>
 
 namespace flgp {
@@ -158,17 +157,6 @@ bool rot_applicable(int s, int b, const double *X, const double *X2, const doubl
          (!X2 || (al(X2) && al(out2)));
 }
 
-// multiprocessors of device `dev` (< 64), asked once per device; 0 if the query failed
-static int device_cus(int dev) {
-  static std::once_flag once[64];
-  static int cus[64];
-  std::call_once(once[dev], [dev] {
-    hipDeviceProp_t pr;
-    cus[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 0;
-  });
-  return cus[dev];
-}
-
 // out = alpha X W + beta E   (and out2 = alpha X2 W + beta E2 when X2 is given)
 int rot_launch(hipStream_t st, int s, int b, double alpha, const double *X, const double *X2, const double *WT, double beta,
                const double *E, const double *E2, double *out, double *out2) {
@@ -176,8 +164,7 @@ int rot_launch(hipStream_t st, int s, int b, double alpha, const double *X, cons
   g.X = X; g.X2 = X2; g.WT = WT; g.E = (beta == 0.0) ? nullptr : E; g.E2 = (beta == 0.0) ? nullptr : E2;
   g.out = out; g.out2 = out2; g.s = s; g.b = b; g.alpha = alpha; g.beta = beta;
   // 32-row tiles while 64-row tiles would leave the chip unevenly loaded (fewer than four tiles per CU)
-  int n_cu = 256, dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && device_cus(dev) > 0) n_cu = device_cus(dev);
+  const int cus = device_figures().cus, n_cu = cus > 0 ? cus : 256;
   const int np = X2 ? 2 : 1;
   const bool tm32 = (long)(b / 64) * ceil_div(s, 64) * np < 4L * n_cu;
   const int nt = (b / 64) * ceil_div(s, tm32 ? 32 : 64);

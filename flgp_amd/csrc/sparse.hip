@@ -730,11 +730,10 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
     if (d_work) {
       hipLaunchKernelGGL(transpose_v_kernel, dim3(ceil_div(s, 32), ceil_div(K, 32)), dim3(256), 0, st, dV, ldv, s, K,
                          d_work);
-      const int wide = tuning("u_recover_wide", 4);
-      if (wide >= 4 && K % 4 == 0) {
+      if (K % 4 == 0) {
         hipLaunchKernelGGL((u_recover_wide_kernel<4, 32>), dim3(ceil_div(n, 32), ceil_div(K, 256)), dim3(256), 0, st, d_ell_idx,
                            d_ell_val, n, r, d_work, d_eig, K, scale, d_vectors, ldo);
-      } else if (wide >= 2 && K % 2 == 0) {
+      } else if (K % 2 == 0) {
         hipLaunchKernelGGL((u_recover_wide_kernel<2, 64>), dim3(ceil_div(n, 64), ceil_div(K, 128)), dim3(256), 0, st, d_ell_idx,
                            d_ell_val, n, r, d_work, d_eig, K, scale, d_vectors, ldo);
       } else {
