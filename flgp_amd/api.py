@@ -324,6 +324,29 @@ class ResidentEigenPair:
             mean[:, j] = post["mean"]; cov[:, j] = post["cov"]
         return {"mean": mean, "cov": cov}
 
+    def regression_objective(self, x, K, idx, Y, sigma=1e-5, noise="same", approach="posterior", prior=None, grad=True):
+        """The objective train_regression_gp_cpp minimises (src/train.cpp:333-555) and its gradient, on the resident pair:
+        ``x = (t, noise)`` for noise = "same", ``(t, noise_1, ..., noise_m)`` for "different"; approach "marginal" (the
+        negative marginal log likelihood) or "posterior" (plus the prior, ``prior = (p, q, tau, alpha, beta)``, None for
+        PostOFDataReg's defaults).  sigma's default is the R wrappers' (R/Fit.R:56).  Returns ``(value, grad)``, or the
+        value alone when ``grad=False``; the gradient is clipped as the reference clips it."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        m = idx.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+        pr = None if prior is None else np.ascontiguousarray(np.asarray(prior, dtype=np.float64).reshape(-1))
+        if pr is not None and pr.size != 5:
+            raise ValueError("prior must hold (p, q, tau, alpha, beta)")
+        value = ctypes.c_double()
+        g = np.zeros(x.size) if grad else None
+        check(_lib.lib().flgp_eigenpair_regression_objective(self._h, int(K), _ptr(idx), m, _ptr(Y), Y.shape[1], float(sigma),
+                                                             _b(noise), _b(approach), _ptr(pr), _ptr(x), x.size,
+                                                             ctypes.byref(value), _ptr(g)))
+        return (value.value, g) if grad else value.value
+
     def to_host(self):
         values = np.zeros(self.K); vectors = np.zeros((self.n, self.K), order="F")
         check(_lib.lib().flgp_eigenpair_to_host(self._h, _ptr(values), _ptr(vectors)))

@@ -222,6 +222,28 @@ struct GpcNewton {
   static int pivot_error(int bad, const char *who, int iter);   // iter 0: the factorisation at the final f
 };
 
+// The regression training objectives on the device (gpr_grad.hip).  tri_inverse: X = L^-1 (m x m, upper triangle zeroed)
+// for a lower factor of chol_blocked; dT holds 64 x m doubles, `work` (we doubles) bounds the GEMM's k-split.
+int tri_inverse(hipStream_t st, const double *dL, long lda, int m, double *dX, long ldx, double *dT, double *work, size_t we,
+                const int *d_flag);
+int rg_colsumsq(hipStream_t st, const double *dX, long ldx, int rows, int cols, double *d_out);   // out[j] = |X(:, j)|^2
+int rg_rowsumsq(hipStream_t st, const double *dX, long ldx, int rows, int cols, double *d_out);   // out[i] = |X(i, :)|^2
+// The pieces of one evaluation (device pointers) and where its value and gradient go: out = [value, grad_0 .. grad_{nx-1}].
+// direct (m <= K): d = diag C^-1 (m), s = |columns of L^-1 V|^2 (K).  Woodbury: M = V^T V ("same") or V^T Z^-1 V, Qinv = Q^-1,
+// M1 = Q^-1 Ls M (K x K), ls = exp(-t lambda / 2); "different": d = |rows of V Ls L_Q^-T|^2 (m).  Vta = V^T alpha (K x q).
+struct RgTerms {
+  int m, q, K, direct, different, posterior, grad;
+  double sigma, c;            // c = x1 + sigma ("same")
+  double prior[5];            // p, q, tau, alpha, beta
+  const double *x;            // nx
+  const double *Y, *alpha;    // m x q
+  const double *logdet;       // sum log(L_ii + 1e-9) of the factor
+  const double *values, *ls;
+  const double *Vta, *d, *s, *M, *Qinv, *M1;
+  double *out;
+};
+int rg_assemble(hipStream_t st, const RgTerms &T);
+
 // host wait for a stream that polls an event instead of sleeping in hipStreamSynchronize (eig.hip)
 hipError_t stream_wait(hipStream_t st);
 

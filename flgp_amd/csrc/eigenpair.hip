@@ -4,6 +4,7 @@
 #include "common.h"
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 using namespace flgp;
 
@@ -396,4 +397,147 @@ extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep,
   int bad = 0;
   FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
   return GpcNewton::pivot_error(bad, who, 0);      // the loop checked its own factorisations: this is the one at the mode
+}
+
+// ---- regression training objectives: train_regression_gp_cpp's four objectives on the resident pair ------
+namespace {
+bool all_finite(const double *v, int cnt) {
+  for (int a = 0; a < cnt; ++a)
+    if (!std::isfinite(v[a])) return false;
+  return true;
+}
+}  // namespace
+
+// negative_marginal_likelihood{,_diff_noise}_regression_cpp (src/train.cpp:351-436, 459-555) and their posterior forms
+// (:333-348, 438-457).  Only x goes up and [value, grad] comes down.  The m x m matrices of the direct branch (C^-1, U, G)
+// are replaced by L^-1 (gpr_grad.hip); the Woodbury branch forms alpha (m x q) as the reference does.
+extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y, int q,
+                                                   double sigma, const char *noise, const char *approach, const double *prior,
+                                                   const double *x, int nx, double *value, double *grad) {
+  const char *who = "regression_objective";
+  FLGP_REQUIRE(noise && approach, "%s: null pointer", who);
+  const bool different = std::strcmp(noise, "different") == 0;
+  if (!different && std::strcmp(noise, "same") != 0) { set_error("The noise setting is illegal!"); return FLGP_ERR_UNSUPPORTED; }
+  const bool posterior = std::strcmp(approach, "posterior") == 0;
+  if (!posterior && std::strcmp(approach, "marginal") != 0) {
+    set_error("This model selection approach is not supported!");
+    return FLGP_ERR_UNSUPPORTED;
+  }
+  FLGP_REQUIRE(ep && idx && Y && x && value, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && q >= 1, "%s: bad shape (K=%d of %d, m=%d, q=%d)", who, K, ep->K, m, q);
+  FLGP_REQUIRE(nx == (different ? m + 1 : 2), "%s: noise \"%s\" takes %d parameters, not %d", who, noise, different ? m + 1 : 2, nx);
+  FLGP_REQUIRE(all_finite(x, nx), "%s: x must be finite", who);
+  for (int a = 1; a < nx; ++a) FLGP_REQUIRE(x[a] + sigma > 0.0, "%s: x[%d] + sigma must be positive", who, a);
+  FLGP_REQUIRE(!posterior || x[0] > 0.0, "%s: t = x[0] must be positive under \"posterior\"", who);
+  Rows r;
+  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
+  const bool direct = m <= K, want_grad = grad != nullptr;
+  const double t = x[0];
+  RgTerms T{};
+  T.m = m; T.q = q; T.K = K; T.direct = direct; T.different = different; T.posterior = posterior; T.grad = want_grad;
+  T.sigma = sigma; T.c = different ? 1.0 : x[1] + sigma;
+  const double dflt[5] = {1.0, 10.0, 2.0, 0.1, 1e-3};         // PostOFDataReg (src/train.h:153-155)
+  for (int a = 0; a < 5; ++a) T.prior[a] = prior ? prior[a] : dflt[a];
+
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = exp(-t lambda / 2) + 0.0
+  DevBuf dY, dx, alpha, out, ld, Vta, d, s, work;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q)); FLGP_TRY(alpha.alloc(sizeof(double) * (size_t)m * q));
+  FLGP_TRY(dx.alloc(sizeof(double) * (size_t)nx)); FLGP_TRY(out.alloc(sizeof(double) * (size_t)(1 + nx)));
+  FLGP_TRY(ld.alloc(sizeof(double)));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
+  FLGP_TRY(h2d(dx.p, x, sizeof(double) * (size_t)nx, st.s));
+  const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
+  if (want_grad) FLGP_TRY(Vta.alloc(sizeof(double) * (size_t)K * q));
+  if (want_grad || (different && !direct)) FLGP_TRY(d.alloc(sizeof(double) * (size_t)m));
+  DevBuf C, hw, Li, Tb, W, M, Q, R, Tq, ZV, Qinv, LsM, M1, P;
+  if (direct) {
+    // C = HK(idx, idx) + sigma I + (x1 I or diag(x[1..m])), factored; alpha = C^-1 Y        (:362-369, :469-477)
+    FLGP_TRY(hk_c11(st.s, ep, K, t, r, sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
+    FLGP_TRY(different ? gpr_add_diag_vec(st.s, C.as<double>(), m, dx.as<double>() + 1) : gpr_add_diag(st.s, C.as<double>(), m, x[1]));
+    FLGP_TRY(chol_blocked(st.s, C.as<double>(), m, m, G.flag.as<int>()));
+    FLGP_HIP(hipMemcpyAsync(alpha.p, dY.p, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToDevice, st.s));
+    FLGP_TRY(chol_trsv(st.s, C.as<double>(), m, m, alpha.as<double>(), m, q, 3, G.flag.as<int>()));
+    FLGP_TRY(chol_logdet(st.s, C.as<double>(), m, m, ld.as<double>()));
+    if (want_grad) {
+      // d_i = (C^-1)_ii, s_k = |(L^-1 V)_{:,k}|^2, V^T alpha
+      const size_t wi = (size_t)32 * 64 * m;
+      FLGP_TRY(Li.alloc(sizeof(double) * (size_t)m * m)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * m));
+      FLGP_TRY(W.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(s.alloc(sizeof(double) * (size_t)K));
+      FLGP_TRY(work.alloc(sizeof(double) * std::max(wi, we)));
+      FLGP_TRY(tri_inverse(st.s, C.as<double>(), m, m, Li.as<double>(), m, Tb.as<double>(), work.as<double>(), wi, G.flag.as<int>()));
+      FLGP_TRY(rg_colsumsq(st.s, Li.as<double>(), m, m, m, d.as<double>()));
+      FLGP_TRY(r.gather(st.s, ep, K));
+      FLGP_TRY(gemm_nn(st.s, m, K, m, Li.as<double>(), m, r.V, r.ld, W.as<double>(), nullptr, 0));
+      FLGP_TRY(rg_colsumsq(st.s, W.as<double>(), m, m, K, s.as<double>()));
+      FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we));
+    }
+  } else {
+    // Woodbury (:395-405, :492-502): M = V^T V or V^T Z^-1 V, Q = Ls M Ls + (c or 1) I, alpha = Z^-1 (Y - V Ls Q^-1 Ls V^T Z^-1 Y)
+    FLGP_TRY(r.gather(st.s, ep, K));
+    FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(Tq.alloc(sizeof(double) * (size_t)m * q));
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    const double *B = r.V;      // Z^-1 V for "different"
+    long ldb = r.ld;
+    if (different) {
+      FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K));
+      FLGP_TRY(gpr_zinv(st.s, dx.as<double>() + 1, sigma, m, d.as<double>()));                          // d = z^-1 for now
+      FLGP_TRY(gpr_rowscale_ld(st.s, r.V, r.ld, d.as<double>(), m, K, ZV.as<double>()));
+      FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));     // Z^-1 Y
+      B = ZV.as<double>(); ldb = m;
+    }
+    FLGP_TRY(gemm_tn(st.s, K, K, m, r.V, r.ld, B, ldb, M.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, different ? alpha.as<double>() : dY.as<double>(), m, R.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_q(st.s, M.as<double>(), G.ls.as<double>(), K, T.c, Q.as<double>()));
+    FLGP_TRY(chol_blocked(st.s, Q.as<double>(), K, K, G.flag.as<int>()));
+    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls V^T Z^-1 Y
+    FLGP_TRY(chol_trsv(st.s, Q.as<double>(), K, K, R.as<double>(), K, q, 3, G.flag.as<int>()));             // Q^-1 (.)
+    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls (.)
+    FLGP_TRY(gemm_nn(st.s, m, q, K, r.V, r.ld, R.as<double>(), K, Tq.as<double>(), nullptr, 0));             // V (.)
+    FLGP_TRY(gpr_diff(st.s, dY.as<double>(), Tq.as<double>(), different ? 1.0 : 1.0 / T.c, (long)m * q, alpha.as<double>()));
+    if (different) FLGP_TRY(gpr_rowscale_ld(st.s, alpha.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));
+    FLGP_TRY(chol_logdet(st.s, Q.as<double>(), K, K, ld.as<double>()));
+    if (want_grad) {
+      // Q^-1 = L_Q^-T L_Q^-1, M1 = Q^-1 Ls M, V^T alpha; "different": d_i = |row i of V Ls L_Q^-T|^2
+      const size_t wi = (size_t)32 * 64 * K;
+      FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+      FLGP_TRY(Qinv.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(LsM.alloc(sizeof(double) * (size_t)K * K));
+      FLGP_TRY(M1.alloc(sizeof(double) * (size_t)K * K));
+      DevBuf wt;
+      FLGP_TRY(wt.alloc(sizeof(double) * wi));
+      FLGP_TRY(tri_inverse(st.s, Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, G.flag.as<int>()));
+      FLGP_TRY(gemm_tn(st.s, K, K, K, Li.as<double>(), K, Li.as<double>(), K, Qinv.as<double>(), work.as<double>(), we));
+      FLGP_TRY(gpr_scale(st.s, M.as<double>(), G.ls.as<double>(), nullptr, K, K, LsM.as<double>()));
+      FLGP_TRY(gemm_nn(st.s, K, K, K, Qinv.as<double>(), K, LsM.as<double>(), K, M1.as<double>(), nullptr, 0));
+      FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we));
+      if (different) {
+        // P = V (L_Q^-1 Ls)^T (m x K): B(k, j) = Li(j, k) ls_k
+        FLGP_TRY(P.alloc(sizeof(double) * (size_t)m * K));
+        FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, G.ls.as<double>(), K, K, LsM.as<double>()));     // reuse: Li Ls
+        FLGP_TRY(gemm_launch(st.s, m, K, K, 1.0, r.V, 1, r.ld, LsM.as<double>(), K, 1, 0.0, nullptr, 0, 0, P.as<double>(), 1, m,
+                             nullptr, 0, 0.0, nullptr));
+        FLGP_TRY(rg_rowsumsq(st.s, P.as<double>(), m, m, K, d.as<double>()));
+      }
+    }
+  }
+  T.x = dx.as<double>(); T.Y = dY.as<double>(); T.alpha = alpha.as<double>(); T.logdet = ld.as<double>();
+  T.values = (const double *)ep->values.p; T.ls = G.ls.as<double>();
+  T.Vta = Vta.as<double>(); T.d = d.as<double>(); T.s = s.as<double>();
+  T.M = M.as<double>(); T.Qinv = Qinv.as<double>(); T.M1 = M1.as<double>();
+  T.out = out.as<double>();
+  FLGP_TRY(rg_assemble(st.s, T));
+  std::vector<double> h((size_t)nx + 1);
+  FLGP_TRY(d2h(h.data(), out.p, sizeof(double) * h.size(), st.s));
+  FLGP_TRY(G.verdict(st.s, who));
+  const int cnt = want_grad ? nx + 1 : 1;
+  if (!all_finite(h.data(), cnt)) {
+    set_error("%s: the objective is not finite (the system matrix is numerically singular)", who);
+    return FLGP_ERR_NOCONV;
+  }
+  *value = h[0];
+  if (want_grad) std::memcpy(grad, h.data() + 1, sizeof(double) * (size_t)nx);
+  return FLGP_OK;
 }
