@@ -109,6 +109,8 @@ _SIGNATURES = {
                             P, c_int, P]),
     "flgp_dev_cholesky": (c_int, [P, P, c_int, c_int, P]),
     "flgp_dev_chol_solve": (c_int, [P, P, c_int, P, c_int, c_int, P]),
+    "flgp_dev_tri_inverse_workspace": (c_size_t, [c_int]),
+    "flgp_dev_tri_inverse": (c_int, [P, P, c_int, P, P, c_size_t, P]),
     "flgp_dev_gemm": (c_int, [P, c_int, c_int, c_int, c_double, P, c_long, c_long, P, c_long, c_long,
                               c_double, P, c_long, c_long, P, c_long, c_long, P, c_size_t]),
     "flgp_dev_rotate": (c_int, [P, c_int, c_int, c_double, P, P, P, c_double, P, P, P]),

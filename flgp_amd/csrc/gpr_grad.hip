@@ -243,3 +243,19 @@ int rg_assemble(hipStream_t st, const RgTerms &T) {
 }
 
 }  // namespace flgp
+
+using namespace flgp;
+
+// T (64 x m) and the k-split planes, sized as the direct branch of the regression objective sizes them (eigenpair.hip)
+extern "C" size_t flgp_dev_tri_inverse_workspace(int m) {
+  return m < 1 ? 0 : sizeof(double) * ((size_t)TNB * m + (size_t)32 * TNB * m);
+}
+
+extern "C" int flgp_dev_tri_inverse(void *stream, const double *d_L, int m, double *d_X, void *d_work, size_t work_bytes,
+                                    const int *d_flag) {
+  FLGP_REQUIRE(d_L && d_X && d_work && d_flag && m >= 1, "tri_inverse: bad arguments");
+  FLGP_REQUIRE(work_bytes >= flgp_dev_tri_inverse_workspace(m), "tri_inverse: workspace of %zu bytes, %zu needed", work_bytes,
+               flgp_dev_tri_inverse_workspace(m));
+  double *T = (double *)d_work;
+  return tri_inverse((hipStream_t)stream, d_L, m, m, d_X, m, T, T + (size_t)TNB * m, (size_t)32 * TNB * m, d_flag);
+}

@@ -119,3 +119,22 @@ def test_header_states_the_eig_info_contract():
     assert "FOUR ints" in doc and "[3]" in doc
     src = open(os.path.join(ROOT, "flgp_amd", "csrc", "eig.hip")).read()
     assert "info[4]" not in src and "info[3]" in src
+
+
+def test_tri_inverse_entry_workspace_and_refusals():
+    """flgp_dev_tri_inverse (include/flgp_hip.h): the workspace query is the 64 x m block-row product plus 32 k-split
+    planes of 64 x m, and the entry refuses a short workspace or a null pointer before any device work."""
+    L = _lib.lib()
+    for m in (1, 64, 65, 1025):
+        assert L.flgp_dev_tri_inverse_workspace(m) == 8 * (64 + 32 * 64) * m
+    assert L.flgp_dev_tri_inverse_workspace(0) == 0
+    ws = L.flgp_dev_tri_inverse_workspace(100)
+    with pytest.raises(api.FlgpError) as e:          # the pointers are never dereferenced: the size check comes first
+        _lib.check(L.flgp_dev_tri_inverse(None, 8, 100, 8, 8, ws - 1, 8))
+    assert e.value.code == -1 and "workspace" in e.value.message
+    with pytest.raises(api.FlgpError) as e:
+        _lib.check(L.flgp_dev_tri_inverse(None, None, 100, 8, 8, ws, 8))
+    assert e.value.code == -1
+    with pytest.raises(api.FlgpError) as e:
+        _lib.check(L.flgp_dev_tri_inverse(None, 8, 0, 8, 8, ws, 8))
+    assert e.value.code == -1

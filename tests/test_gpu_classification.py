@@ -217,6 +217,42 @@ def test_posterior_multiclassification_against_numpy_loop():
     rp.free()
 
 
+# ---- block edges of the resident entries -----------------------------------------------------------------------------
+# m = 1 and 65 (one and two panels of chol_blocked / chol_trsv), m_new = 1, and K = 64, 65, 129 right-hand sides of
+# chol_trsv mode 1 in the posterior (L_B^-1 sqrt(W) V1 L: one workgroup per column of V1)
+@pytest.mark.parametrize("m,K,mnew", [(1, 50, 1), (1, 65, 300), (65, 50, 1), (65, 64, 300), (200, 65, 129), (300, 129, 1)])
+def test_resident_block_edges(m, K, mnew):
+    n = 3000
+    ep, rp = synthetic_pair(n, 130, seed=m + K)
+    rng = np.random.default_rng(m * K + mnew)
+    idx0 = rng.permutation(n)[:m]; idx1 = rng.permutation(n)[:mnew]
+    Y = (rng.uniform(size=m) < 0.4).astype(np.float64)
+    t, sigma = 2.0, 1e-3
+    got, it = rp.marginal_log_likelihood_logit_la(K, t, idx0, Y, sigma=sigma, return_iters=True)
+    ref, it_ref = np_amll(hk(ep.values, ep.vectors, K, t, idx0, idx0) + sigma * np.eye(m), Y, np.ones(m))
+    assert it == it_ref and abs(got - ref) <= 1e-10 * abs(ref), (got, ref)
+    post = rp.posterior_distribution_classification(idx0, idx1, K, t, Y, sigma, sigma)
+    assert post["mean"].shape == (mnew,) and post["cov"].shape == (mnew,)
+    check_posterior(post, ep, K, t, idx0, idx1, Y, sigma, sigma)
+    rp.free()
+
+
+def test_posterior_multiclassification_k65():
+    n, K, m = 3000, 65, 150
+    ep, rp = synthetic_pair(n, K, seed=23)
+    rng = np.random.default_rng(24)
+    idx0 = rng.permutation(n)[:m]; idx1 = np.arange(n - 129, n)
+    Y = rng.integers(0, 3, m).astype(np.float64)
+    ts = [1.0, 2.5, 4.0]
+    sigma = 1e-3
+    post = rp.posterior_distribution_multiclassification(idx0, idx1, K, ts, Y, sigma)
+    assert post["mean"].shape == (idx1.size, 3)
+    aug = api.multi_train_split(Y)
+    for j in range(3):
+        check_posterior({"mean": post["mean"][:, j], "cov": post["cov"][:, j]}, ep, K, ts[j], idx0, idx1, aug[:, j], 0.0, sigma)
+    rp.free()
+
+
 # ---- errors, determinism ----------------------------------------------------------------------------------------------
 def test_errors():
     n = 2000

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import np_regression_objective as npr
 from conftest import make_case
 from flgp_amd import _lib, api, synth
 from flgp_amd.pipeline import HeatKernelPath, HipStages, PathConfig
@@ -1004,6 +1005,46 @@ def test_posterior_variance_many_new_rows(oracle):
     np.testing.assert_allclose(gotv, refv, rtol=0, atol=1e-9 * np.abs(refv).max() + 2e-15 * prior * m / (noise + sigma))
     assert dt < 5.0, dt
     rp.free()
+
+
+@pytest.fixture(scope="module")
+def wide_pair():
+    """A synthetic resident pair (orthonormal V times sqrt(n), values in (0, 1]) with K = 1100 > 1024."""
+    assert torch.cuda.is_available(), "the -m gpu tests need an MI355X"
+    torch.cuda.init()
+    values, V = npr.synthetic_pair(3000, 1100, np.random.default_rng(1100))
+    rp = api.ResidentEigenPair.from_host(api.EigenPair(values, V))
+    yield values, V, rp
+    rp.free()
+
+
+# m <= K: the one-workgroup Cholesky (chol_solve_kernel, 1024 threads) below one wave, across the 64 boundary and past
+# the 1024 stride (m = 1100 wraps the column scaling and the trailing update); m_new = 1 and 129 put chol_apply_kernel's
+# 128-wide grid on one partial and two blocks.  m > K: Woodbury at K across one block.
+@pytest.mark.parametrize("m,K,mnew", [(1, 1100, 129), (64, 1100, 1), (65, 1100, 129), (1025, 1100, 129), (1100, 1100, 1),
+                                      (1100, 1100, 129), (40, 1, 129), (300, 64, 1), (300, 65, 129), (700, 129, 129)])
+def test_resident_regression_block_and_stride_edges(oracle, wide_pair, m, K, mnew):
+    values, V, rp = wide_pair
+    n = V.shape[0]
+    rng = np.random.default_rng(m * 7 + K + mnew)
+    idx0 = rng.permutation(n)[:m]; idx1 = rng.permutation(n)[:mnew]
+    Y = rng.normal(size=(m, 2))
+    sigma = 1e-3
+    for t, noise in [(2.0, 0.1), (6.0, 1e-2)]:
+        ref = oracle.np_predict_regression(values, V, Y, idx0, idx1, K, (t, noise), sigma)
+        got = rp.predict_regression_cpp(Y, idx0, idx1, K, (t, noise), sigma)
+        assert got.shape == (mnew, 2)
+        np.testing.assert_allclose(got, ref, rtol=0, atol=1e-9 * np.abs(ref).max())
+        refv = oracle.np_posterior_covariance_regression(values, V, idx0, idx1, K, (t, noise), sigma)
+        gotv = rp.posterior_covariance_regression(idx0, idx1, K, (t, noise), sigma)
+        # the bound of test_resident_regression_prediction_and_posterior_variance
+        prior = ((V[idx1, :K] ** 2) * np.exp(-t * (1.0 - values[:K]))).sum(1).max()
+        np.testing.assert_allclose(gotv, refv, rtol=0, atol=1e-9 * np.abs(refv).max() + 2e-15 * prior * m / (noise + sigma))
+        assert (gotv > 0).all()
+    pars = np.concatenate([[2.0], rng.uniform(0.05, 0.5, m)])
+    ref = oracle.np_predict_regression_different(values, V, Y, idx0, idx1, K, pars, sigma)
+    got = rp.predict_regression_cpp(Y, idx0, idx1, K, pars, sigma, noisepar="different")
+    np.testing.assert_allclose(got, ref, rtol=0, atol=1e-9 * np.abs(ref).max())
 
 
 @pytest.mark.parametrize("n,d,s,a2,K,seed", [(3000, 3, 300, 1.0, 30, 0), (5000, 7, 500, 0.5, 60, 1),

@@ -15,6 +15,7 @@ import np_regression_objective as R  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 N, KP = 3000, 48          # pair size; every case uses K = KP, so m <= 48 is the direct branch
+KW = 1200                 # the wide pair of the block- and stride-edge cases
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -29,6 +30,17 @@ def torch_first():
 def pair():
     rng = np.random.default_rng(5)
     values, V = R.synthetic_pair(N, KP, rng)
+    rp = api.ResidentEigenPair.from_host(api.EigenPair(values, V))
+    yield values, V, rp
+    rp.free()
+
+
+@pytest.fixture(scope="module")
+def wide_pair():
+    """K up to 1200 > 1024: the direct branch reaches m > 1024 (multi-block tri_inverse, chol_logdet and rg_assemble
+    loops past their 1024-thread stride) and K > 1024 in rg_assemble's k-loops; Woodbury runs at small K and m = 2500."""
+    rng = np.random.default_rng(1200)
+    values, V = R.synthetic_pair(N, KW, rng)
     rp = api.ResidentEigenPair.from_host(api.EigenPair(values, V))
     yield values, V, rp
     rp.free()
@@ -61,6 +73,39 @@ def test_against_restatement(pair, noise, approach, m, q, kind):
     x = xs(noise, m, rng)
     dev = rp.regression_objective(x, KP, idx, Y, sigma=1e-5, noise=noise, approach=approach)
     close(dev, R.objective(values, V, KP, idx, Y, x, 1e-5, noise, approach))
+
+
+# Each edge of the dense layer once under "same" and once under "different", the approaches and q in {1, 5, 70} spread
+# over them: direct (K = 1200 >= m) at m across the 64-wide blocks and the 1024 stride; Woodbury at K across one block
+# with m = K + 1 and m = 2500 (rg_assemble's per-row loop of "different" wraps twice).
+EDGE_CASES = [
+    # noise, approach, m, K, q
+    ("same", "marginal", 1, KW, 1), ("different", "posterior", 1, KW, 5),
+    ("same", "posterior", 63, KW, 70), ("different", "marginal", 63, KW, 1),
+    ("same", "marginal", 64, KW, 5), ("different", "posterior", 64, KW, 70),
+    ("same", "posterior", 65, KW, 1), ("different", "marginal", 65, KW, 5),
+    ("same", "marginal", 129, KW, 70), ("different", "posterior", 129, KW, 1),
+    ("same", "posterior", 1025, KW, 5), ("different", "marginal", 1025, KW, 70),
+    ("same", "marginal", 1100, KW, 1), ("different", "posterior", 1100, KW, 5),
+    ("same", "marginal", 2, 1, 1), ("different", "posterior", 2500, 1, 5),
+    ("same", "posterior", 2500, 63, 70), ("different", "marginal", 64, 63, 1),
+    ("same", "marginal", 65, 64, 5), ("different", "posterior", 2500, 64, 70),
+    ("same", "posterior", 2500, 65, 1), ("different", "marginal", 66, 65, 5),
+    ("same", "marginal", 130, 129, 70), ("different", "posterior", 2500, 129, 1),
+]
+
+
+@pytest.mark.parametrize("noise,approach,m,K,q", EDGE_CASES,
+                         ids=[f"{n}-{a}-m{m}-K{k}-q{q}" for n, a, m, k, q in EDGE_CASES])
+def test_block_and_stride_edges(wide_pair, noise, approach, m, K, q):
+    values, V, rp = wide_pair
+    rng = np.random.default_rng(m * 131 + K * 7 + q)
+    idx = rows("scattered", m, rng)
+    Y = rng.standard_normal((m, q))
+    x = xs(noise, m, rng)
+    dev = rp.regression_objective(x, K, idx, Y, sigma=1e-5, noise=noise, approach=approach)
+    assert dev[1].shape == ((m + 1) if noise == "different" else 2,)
+    close(dev, R.objective(values, V, K, idx, Y, x, 1e-5, noise, approach))
 
 
 @pytest.mark.parametrize("m,scale", [(30, 10.0), (150, 1.0)], ids=["direct", "woodbury"])
