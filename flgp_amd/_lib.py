@@ -61,6 +61,12 @@ _SIGNATURES = {
                                                         c_int, P, P]),
     "flgp_eigenpair_regression_objective": (c_int, [P, c_int, P, c_int, P, c_int, c_double, c_char_p, c_char_p, P, P, c_int,
                                                     P, P]),
+    "flgp_pg_draw": (c_int, [P, P, c_int, ctypes.c_ulonglong, P]),
+    "flgp_pg_logit_predict": (c_int, [P, c_int, P, P, c_int, c_int, ctypes.c_ulonglong, P, P, P, P]),
+    "flgp_eigenpair_pg_predict": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_int,
+                                          ctypes.c_ulonglong, P, P, P, P]),
+    "flgp_eigenpair_pg_predict_multiclass": (c_int, [P, c_int, P, c_int, c_double, P, c_int, P, P, c_int, c_int,
+                                                     ctypes.c_ulonglong, P, P]),
     "flgp_eigenpair_free": (None, [P]),
     "flgp_kmeans_minibatch": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, ctypes.c_ulonglong, P, P, P]),
     "flgp_kmeans_lloyd": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),

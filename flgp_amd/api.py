@@ -200,6 +200,56 @@ def multi_train_split(Y):
     return (Y[:, None] == np.arange(J)[None, :]).astype(np.float64)
 
 
+def _seed(seed):
+    """A chain's seed: the caller's, or one drawn from numpy's default generator.  R passes one drawn from its own RNG, so
+    that ``set.seed`` still reproduces a fit ("Polya-Gamma prediction")."""
+    if seed is None:
+        return int(np.random.default_rng().integers(0, 2**63))
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def pgdraw(b, c, seed=None):
+    """pgdraw(b, c) (BayesLogit / pgdraw's contract): omega_i ~ PG(b_i, c_i), drawn on the device.  ``b`` is a positive
+    integer or one per entry (None: all ones); the draws are reproducible from ``seed`` (pg.hip documents the layout)."""
+    c = np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1))
+    bb = None if b is None else np.ascontiguousarray(np.broadcast_to(np.asarray(b, dtype=np.float64), c.shape))
+    out = np.zeros(c.size)
+    check(_lib.lib().flgp_pg_draw(_ptr(bb), _ptr(c), c.size, _seed(seed), _ptr(out)))
+    return out
+
+
+def test_pgbinary_cpp(C, Y, Cnv, N_sample=100, output_pi=False, seed=None):
+    """test_pgbinary_cpp (src/Predict.cpp:11-26; defaults src/Predict.h:33-37): N_sample Gibbs sweeps of the Polya-Gamma
+    logit model with covariance C (m x m), then the collapsed prediction of the rows of Cnv (m_new x m).  Returns the R
+    list's keys: {"Y_pred"} and, with ``output_pi``, "pi_pred"."""
+    C = _f64(C, "C")
+    m = C.shape[0]
+    if C.shape != (m, m):
+        raise ValueError("C must be square")
+    Cnv = _f64(Cnv, "Cnv")
+    if Cnv.shape[1] != m:
+        raise ValueError("Cnv must have one column per row of C")
+    Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+    if Y.size != m:
+        raise ValueError("Y must have one entry per row of C")
+    mnew = Cnv.shape[0]
+    pi = np.zeros(mnew); y = np.zeros(mnew)
+    check(_lib.lib().flgp_pg_logit_predict(_ptr(C), m, _ptr(Y), _ptr(Cnv), mnew, int(N_sample), _seed(seed), _ptr(pi), _ptr(y),
+                                           None, None))
+    return {"Y_pred": y, "pi_pred": pi} if output_pi else {"Y_pred": y}
+
+
+def _pg_logit_predict_state(C, Y, Cnv, N_sample, seed):
+    """test_pgbinary_cpp with the chain's final omega and f as well: (pi_pred, Y_pred, omega, f)."""
+    C = _f64(C, "C"); Cnv = _f64(Cnv, "Cnv")
+    m = C.shape[0]
+    Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+    pi = np.zeros(Cnv.shape[0]); y = np.zeros(Cnv.shape[0]); om = np.zeros(m); f = np.zeros(m)
+    check(_lib.lib().flgp_pg_logit_predict(_ptr(C), m, _ptr(Y), _ptr(Cnv), Cnv.shape[0], int(N_sample), _seed(seed), _ptr(pi),
+                                           _ptr(y), _ptr(om), _ptr(f)))
+    return pi, y, om, f
+
+
 class ResidentEigenPair:
     """An ``EigenPair`` that stays in HBM (include/flgp_hip.h, "device-resident EigenPair"): what the training
     loop needs, since it calls ``HK_from_spectrum_cpp`` with the same pair and a new ``t`` on every objective
@@ -346,6 +396,46 @@ class ResidentEigenPair:
                                                              _b(noise), _b(approach), _ptr(pr), _ptr(x), x.size,
                                                              ctypes.byref(value), _ptr(g)))
         return (value.value, g) if grad else value.value
+
+    def test_pgbinary(self, idx0, idx1, K, t, Y, sigma, sigma_nv, N_sample=100, output_pi=False, seed=None,
+                      return_state=False):
+        """test_pgbinary_cpp (src/Predict.cpp:11-26) on the resident pair with C = HK(idx0, idx0) + sigma I: the Gibbs
+        sweeps and the collapsed prediction of the rows idx1 run on the device.  ``sigma_nv`` is what the new rows'
+        covariance adds where a row of idx1 is one of idx0: sigma for the binary drivers (C = [Cvv; Cnv],
+        src/Fit.cpp:574-576), 0 for the one-vs-rest route.  Returns {"Y_pred"} (+ "pi_pred" with ``output_pi``, + the
+        chain's final "omega" and "f" with ``return_state``)."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        if Y.size != idx0.size:
+            raise ValueError("Y must have one entry per row of idx0")
+        pi = np.zeros(idx1.size); y = np.zeros(idx1.size)
+        om = np.zeros(idx0.size) if return_state else None
+        f = np.zeros(idx0.size) if return_state else None
+        check(_lib.lib().flgp_eigenpair_pg_predict(self._h, int(K), float(t), float(sigma), float(sigma_nv), _ptr(idx0), idx0.size,
+                                                   _ptr(Y), _ptr(idx1), idx1.size, int(N_sample), _seed(seed), _ptr(pi), _ptr(y),
+                                                   _ptr(om), _ptr(f)))
+        out = {"Y_pred": y}
+        if output_pi:
+            out["pi_pred"] = pi
+        if return_state:
+            out["omega"] = om; out["f"] = f
+        return out
+
+    def predict_logit_mult_gp_cpp(self, idx0, idx1, K, ts, Y, sigma, N_sample=100, seed=None, output_probs=False):
+        """predict_logit_mult_gp_cpp (src/MultiClassification.cpp:57-88) on the resident pair: one Polya-Gamma chain per
+        class of ``multi_train_split(Y)``, class j at ``ts[j]`` with seed + j and sigma on Cvv only, then the first arg-max
+        of the class probabilities.  Returns y_pred (m_new), or (y_pred, probs m_new x J) with ``output_probs``."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        if Y.size != idx0.size:
+            raise ValueError("Y must have one entry per row of idx0")
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        J = ts.size
+        probs = np.zeros((idx1.size, J), order="F"); labels = np.zeros(idx1.size)
+        check(_lib.lib().flgp_eigenpair_pg_predict_multiclass(self._h, int(K), _ptr(ts), J, float(sigma), _ptr(idx0), idx0.size,
+                                                              _ptr(Y), _ptr(idx1), idx1.size, int(N_sample), _seed(seed),
+                                                              _ptr(probs), _ptr(labels)))
+        return (labels, probs) if output_probs else labels
 
     def to_host(self):
         values = np.zeros(self.K); vectors = np.zeros((self.n, self.K), order="F")

@@ -209,6 +209,8 @@ int chol_blocked(hipStream_t st, double *dA, long lda, int m, int *d_flag);     
 int chol_trsv(hipStream_t st, const double *dL, long lda, int m, double *dB, long ldb, int nrhs, int mode, const int *d_flag);
 int chol_logdet(hipStream_t st, const double *dL, long lda, int m, double *d_out);
 int gpc_scale2(hipStream_t st, const double *dM, long ldm, const double *d_a, const double *d_b, int rows, int cols, double *d_out);
+int gpc_bmat(hipStream_t st, const double *dC, const double *d_sW, int m, double *dB);      // B = sW C sW + I (m x m)
+int gpc_gemv(hipStream_t st, const double *dC, int m, const double *d_x, const double *d_s, double *d_y);   // y = s .* (C x)
 // The state of one Newton loop (GPML Alg. 3.1) on an m x m covariance C.  dN = nullptr: the posterior's N = 1 form.
 struct GpcNewton {
   DevBuf B, f, fnew, sW, b, a, r, resid, scal, flag;
@@ -243,6 +245,23 @@ struct RgTerms {
   double *out;
 };
 int rg_assemble(hipStream_t st, const RgTerms &T);
+
+// The Polya-Gamma Gibbs sampler (pg.hip; its random-number layout is documented there).  pg_stream_base: the base of
+// stream `stream` under `seed`, as flgp_amd/synth.py's _stream_base.
+unsigned long long pg_stream_base(unsigned long long seed, unsigned long long stream);
+int pg_draw_launch(hipStream_t st, const double *d_b, const double *d_c, long n, unsigned long long base, double *d_out);
+int pg_normals(hipStream_t st, unsigned long long seed, int sweep, int K, int m, double *d_out);   // K + 2m normals
+int pg_f0r(hipStream_t st, int m, const double *Vz, const double *z2, double ss, const double *z3, const double *kappa,
+           const double *omega, double *f0, double *r, double *sw);
+int pg_dvec(hipStream_t st, int m, const double *omega, double sigma, double *sw, double *dh, double *a);
+int pg_mul(hipStream_t st, int m, const double *a, const double *x, const double *b, double *out);
+int pg_wb_out(hipStream_t st, int m, const double *sw, const double *dh, const double *g, const double *Xv, double *out);
+int pg_axpy3(hipStream_t st, int m, const double *x, const double *y, double c, const double *z, double *out);
+int pg_trmv(hipStream_t st, const double *dL, long lda, int m, const double *z, double *y, const int *d_flag);
+int pg_pi(hipStream_t st, long n, const double *mean, double sigma_nv, const long *ptr, const int *list, const double *w,
+          double *pi, long ld, double *y);
+int pg_argmax(hipStream_t st, long n, int J, const double *probs, double *labels);
+int pg_init(hipStream_t st, int m, const double *Y, double *kappa, double *omega, double *f);
 
 // host wait for a stream that polls an event instead of sleeping in hipStreamSynchronize (eig.hip)
 hipError_t stream_wait(hipStream_t st);

@@ -541,3 +541,315 @@ extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int
   if (want_grad) std::memcpy(grad, h.data() + 1, sizeof(double) * (size_t)nx);
   return FLGP_OK;
 }
+
+// ---- Polya-Gamma Gibbs prediction: test_pgbinary_cpp and predict_logit_mult_gp_cpp (pg.hip) ---------------
+namespace {
+// One chain of PGLogitModel (src/PGLogitModel.cpp) with C = V1 L V1^T + sigma I (eigen routes) or a dense C.  Each sweep
+// resamples f in Matheron's form, with the law of _resample_f (:25-39) and one solve against B = sW C sW + I:
+//   f0 = V1 L^1/2 z1 + sqrt(sigma) z2 (dense: L_C z2), r = kappa / sW - sW f0 - z3, f = f0 + C (sW B^-1 r),
+// then omega ~ PG(1, f).  B^-1: route DENSE / DIRECT factor the m x m B; WOODBURY (m > K) writes B = D + U L U^T with
+// D = 1 + sigma omega, U = sW V1 and factors the K x K Q = I + X^T X, X = D^-1/2 U L^1/2:
+//   sW B^-1 r = sW D^-1/2 (g - X Q^-1 X^T g),  g = D^-1/2 r.
+// C x = V1 (L (V1^T x)) + sigma x in both eigen routes; C is formed only to build B in DIRECT.
+enum PgRoute { PG_DENSE, PG_DIRECT, PG_WOODBURY };
+struct PgChain {
+  PgRoute route = PG_DENSE;
+  int m = 0, K = 0;
+  double sigma = 0.0;
+  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;   // eigen routes: V1 (m x K at ld1), L, L^1/2
+  long ld1 = 0;
+  const double *C = nullptr, *LC = nullptr;                  // DENSE / DIRECT: C (m x m); DENSE: its factor
+  int *flag = nullptr;
+  DevBuf kappa, omega, f, f0, r, sw, z, x, t1, t2, B, X, dh, a, u, work;
+  size_t we = 0;
+
+  int alloc(int m_, int K_) {
+    m = m_; K = K_;
+    const size_t v = sizeof(double) * (size_t)m;
+    FLGP_TRY(kappa.alloc(v)); FLGP_TRY(omega.alloc(v)); FLGP_TRY(f.alloc(v)); FLGP_TRY(f0.alloc(v)); FLGP_TRY(r.alloc(v));
+    FLGP_TRY(sw.alloc(v)); FLGP_TRY(x.alloc(v)); FLGP_TRY(t1.alloc(v)); FLGP_TRY(t2.alloc(v));
+    FLGP_TRY(z.alloc(sizeof(double) * ((size_t)2 * m + K)));
+    FLGP_TRY(u.alloc(sizeof(double) * (size_t)std::max(K, 1)));
+    we = (size_t)128 * K * K + (size_t)64 * K + 1024;
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    if (route == PG_WOODBURY) {
+      FLGP_TRY(B.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
+      FLGP_TRY(dh.alloc(v)); FLGP_TRY(a.alloc(v));
+    } else {
+      FLGP_TRY(B.alloc(sizeof(double) * (size_t)m * m));
+    }
+    return FLGP_OK;
+  }
+  // sW (and the Woodbury pieces) from omega, B or Q factored in place
+  int factor(hipStream_t st) {
+    if (route != PG_WOODBURY) {
+      FLGP_TRY(pg_dvec(st, m, omega.as<double>(), 0.0, sw.as<double>(), t1.as<double>(), t2.as<double>()));
+      FLGP_TRY(gpc_bmat(st, C, sw.as<double>(), m, B.as<double>()));
+      return chol_blocked(st, B.as<double>(), m, m, flag);
+    }
+    FLGP_TRY(pg_dvec(st, m, omega.as<double>(), sigma, sw.as<double>(), dh.as<double>(), a.as<double>()));
+    FLGP_TRY(gpc_scale2(st, V1, ld1, a.as<double>(), ls, m, K, X.as<double>()));
+    FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, B.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_add_diag(st, B.as<double>(), K, 1.0));
+    return chol_blocked(st, B.as<double>(), K, K, flag);
+  }
+  // out = sW .* B^-1 rin with the factor of the last factor()
+  int solve(hipStream_t st, const double *rin, double *out) {
+    if (route != PG_WOODBURY) {
+      FLGP_HIP(hipMemcpyAsync(t1.p, rin, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+      FLGP_TRY(chol_trsv(st, B.as<double>(), m, m, t1.as<double>(), m, 1, 3, flag));
+      return pg_mul(st, m, sw.as<double>(), t1.as<double>(), nullptr, out);
+    }
+    FLGP_TRY(pg_mul(st, m, dh.as<double>(), rin, nullptr, t1.as<double>()));                                       // g
+    FLGP_TRY(gemm_tn(st, K, 1, m, X.as<double>(), m, t1.as<double>(), m, u.as<double>(), work.as<double>(), we));   // X^T g
+    FLGP_TRY(chol_trsv(st, B.as<double>(), K, K, u.as<double>(), K, 1, 3, flag));                                  // Q^-1 (.)
+    FLGP_TRY(gemm_nn(st, m, 1, K, X.as<double>(), m, u.as<double>(), K, t2.as<double>(), nullptr, 0));             // X (.)
+    return pg_wb_out(st, m, sw.as<double>(), dh.as<double>(), t1.as<double>(), t2.as<double>(), out);
+  }
+  // out = add + C xin (add may be nullptr)
+  int cmul(hipStream_t st, const double *xin, const double *add, double *out) {
+    if (route == PG_DENSE) {
+      FLGP_TRY(gpc_gemv(st, C, m, xin, nullptr, t2.as<double>()));
+      return pg_axpy3(st, m, add, t2.as<double>(), 0.0, nullptr, out);
+    }
+    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, xin, m, u.as<double>(), work.as<double>(), we));
+    FLGP_TRY(pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>()));
+    FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, t2.as<double>(), nullptr, 0));
+    return pg_axpy3(st, m, add, t2.as<double>(), sigma, xin, out);
+  }
+  int run(hipStream_t st, const double *dY, int n_sample, unsigned long long seed) {
+    FLGP_TRY(pg_init(st, m, dY, kappa.as<double>(), omega.as<double>(), f.as<double>()));
+    const int kz = route == PG_DENSE ? 0 : K;
+    double *z1 = z.as<double>(), *z2 = z1 + kz, *z3 = z2 + m;
+    for (int s = 0; s < n_sample; ++s) {
+      ProfScope ps("pg_sweep", st, 0.0);
+      FLGP_TRY(pg_normals(st, seed, s, kz, m, z1));
+      if (route == PG_DENSE) {
+        FLGP_TRY(pg_trmv(st, LC, m, m, z2, t2.as<double>(), flag));                                         // L_C z2
+      } else {
+        FLGP_TRY(pg_mul(st, K, ls, z1, nullptr, u.as<double>()));
+        FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, t2.as<double>(), nullptr, 0));            // V1 L^1/2 z1
+      }
+      FLGP_TRY(pg_f0r(st, m, t2.as<double>(), z2, route == PG_DENSE ? 0.0 : std::sqrt(sigma), z3, kappa.as<double>(),
+                      omega.as<double>(), f0.as<double>(), r.as<double>(), sw.as<double>()));
+      FLGP_TRY(factor(st));
+      FLGP_TRY(solve(st, r.as<double>(), x.as<double>()));
+      FLGP_TRY(cmul(st, x.as<double>(), f0.as<double>(), f.as<double>()));
+      FLGP_TRY(pg_draw_launch(st, nullptr, f.as<double>(), m, pg_stream_base(seed, 4ull * (unsigned long long)s + 3),
+                              omega.as<double>()));
+    }
+    return FLGP_OK;
+  }
+  // _collapsed_predict (src/PGLogitModel.cpp:61-73) at the final omega, first half: w = kappa - sW B^-1 (sW C kappa) in x
+  int collapsed_w(hipStream_t st) {
+    FLGP_TRY(factor(st));
+    FLGP_TRY(cmul(st, kappa.as<double>(), nullptr, r.as<double>()));                       // C kappa
+    FLGP_TRY(pg_mul(st, m, sw.as<double>(), r.as<double>(), nullptr, r.as<double>()));
+    FLGP_TRY(solve(st, r.as<double>(), f0.as<double>()));
+    return pg_axpy3(st, m, kappa.as<double>(), nullptr, -1.0, f0.as<double>(), x.as<double>());
+  }
+};
+
+// For every new row i the training positions j with idx0_j = idx1_i, as CSR (ptr: m_new + 1, list): where the binary
+// drivers' C = [Cvv; Cnv] carries sigma on the diagonal of its top block (src/Fit.cpp:574-576).
+struct PgMatch {
+  DevBuf ptr, list;
+  int build(hipStream_t st, const int *idx0, int m, const int *idx1, int mnew) {
+    std::vector<std::pair<int, int>> pos((size_t)m);
+    for (int j = 0; j < m; ++j) pos[(size_t)j] = {idx0[j], j};
+    std::sort(pos.begin(), pos.end());
+    std::vector<long> hp((size_t)mnew + 1, 0);
+    std::vector<int> hl;
+    for (int i = 0; i < mnew; ++i) {
+      auto lo = std::lower_bound(pos.begin(), pos.end(), std::make_pair(idx1[i], -1));
+      for (; lo != pos.end() && lo->first == idx1[i]; ++lo) hl.push_back(lo->second);
+      hp[(size_t)i + 1] = (long)hl.size();
+    }
+    FLGP_TRY(ptr.alloc(sizeof(long) * hp.size()));
+    FLGP_TRY(list.alloc(sizeof(int) * std::max<size_t>(hl.size(), 1)));
+    FLGP_TRY(h2d(ptr.p, hp.data(), sizeof(long) * hp.size(), st));
+    FLGP_TRY(h2d(list.p, hl.data(), sizeof(int) * hl.size(), st));
+    FLGP_HIP(hipStreamSynchronize(st));      // the host vectors go out of scope
+    return FLGP_OK;
+  }
+};
+
+int pg_verdict(hipStream_t st, const void *d_flag, const char *who) {   // synchronises
+  int bad = 0;
+  FLGP_TRY(read_flag(st, d_flag, &bad));
+  if (bad) {
+    set_error("%s: a Cholesky factorisation met a pivot <= 0 (pivot %d): the covariance is not positive definite or the "
+              "chain diverged", who, bad - 1);
+    return FLGP_ERR_NOCONV;
+  }
+  return FLGP_OK;
+}
+
+int check_pg_common(const double *Y, int m, int mnew, int n_sample, const char *who) {
+  FLGP_REQUIRE(m >= 1 && mnew >= 1, "%s: bad shape (m=%d, m_new=%d)", who, m, mnew);
+  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
+  for (int a = 0; a < m; ++a) FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] <= 1.0, "%s: Y[%d]=%g is outside [0, 1]", who, a, Y[a]);
+  return FLGP_OK;
+}
+
+// One binary chain on the resident pair (V1, V2 gathered by the caller) and its collapsed prediction of the new rows:
+// pi into d_pi[i * ld_pi] and labels into d_y (either may be nullptr); final omega and f stay in P.
+int pg_eigen_binary(hipStream_t st, const flgp_eigenpair *ep, int K, double t, double sigma, double sigma_nv, Rows &r0,
+                    const Rows &r1, const double *dY, int n_sample, unsigned long long seed, PgMatch *match,
+                    PgChain &P, DevBuf &flag, double *d_pi, long ld_pi, double *d_y) {
+  const int m = r0.m, mnew = r1.m;
+  GprCtx G;
+  FLGP_TRY(G.prepare(st, ep, K, t));          // ls = exp(-t (1 - values) / 2), l = exp(-t (1 - values))
+  DevBuf C, hw;
+  P.route = m <= K ? PG_DIRECT : PG_WOODBURY;
+  if (P.route == PG_DIRECT) {
+    FLGP_TRY(hk_c11(st, ep, K, t, r0, sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
+    P.C = C.as<double>();
+  }
+  P.sigma = sigma; P.V1 = r0.V; P.ld1 = r0.ld; P.l = G.l.as<double>(); P.ls = G.ls.as<double>(); P.flag = flag.as<int>();
+  FLGP_TRY(P.alloc(m, K));
+  FLGP_TRY(P.run(st, dY, n_sample, seed));
+  FLGP_TRY(P.collapsed_w(st));
+  // mean = V2 L V1^T w, then pi = logistic(mean + sigma_nv sum_{idx0_j = idx1_i} w_j)
+  DevBuf mean;
+  FLGP_TRY(mean.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_TRY(gemm_tn(st, K, 1, m, r0.V, r0.ld, P.x.as<double>(), m, P.u.as<double>(), P.work.as<double>(), P.we));
+  FLGP_TRY(pg_mul(st, K, P.l, P.u.as<double>(), nullptr, P.u.as<double>()));
+  FLGP_TRY(gemm_nn(st, mnew, 1, K, r1.V, r1.ld, P.u.as<double>(), K, mean.as<double>(), nullptr, 0));
+  FLGP_TRY(pg_pi(st, mnew, mean.as<double>(), sigma_nv, match ? match->ptr.as<long>() : nullptr,
+                 match ? match->list.as<int>() : nullptr, P.x.as<double>(), d_pi, ld_pi, d_y));
+  FLGP_HIP(hipStreamSynchronize(st));         // the chain's buffers are given back to the cache on the way out
+  return FLGP_OK;
+}
+}  // namespace
+
+extern "C" int flgp_pg_draw(const double *b, const double *c, int n, unsigned long long seed, double *omega) {
+  const char *who = "pg_draw";
+  FLGP_REQUIRE(c && omega, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: bad shape (n=%d)", who, n);
+  for (int i = 0; i < n; ++i) {
+    FLGP_REQUIRE(std::isfinite(c[i]), "%s: c[%d]=%g must be finite", who, i, c[i]);
+    if (b) FLGP_REQUIRE(b[i] >= 1.0 && b[i] <= 1e6 && b[i] == std::floor(b[i]), "%s: b[%d]=%g must be an integer >= 1", who, i, b[i]);
+  }
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf db, dc, out;
+  if (b) FLGP_TRY(db.alloc(sizeof(double) * (size_t)n));
+  FLGP_TRY(dc.alloc(sizeof(double) * (size_t)n)); FLGP_TRY(out.alloc(sizeof(double) * (size_t)n));
+  if (b) FLGP_TRY(h2d(db.p, b, sizeof(double) * (size_t)n, st.s));
+  FLGP_TRY(h2d(dc.p, c, sizeof(double) * (size_t)n, st.s));
+  FLGP_TRY(pg_draw_launch(st.s, b ? db.as<double>() : nullptr, dc.as<double>(), n, pg_stream_base(seed, 3), out.as<double>()));
+  FLGP_TRY(d2h(omega, out.p, sizeof(double) * (size_t)n, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+extern "C" int flgp_pg_logit_predict(const double *C, int m, const double *Y, const double *Cnv, int mnew, int n_sample,
+                                     unsigned long long seed, double *pi_pred, double *y_pred, double *omega_out, double *f_out) {
+  const char *who = "pg_logit_predict";
+  FLGP_REQUIRE(C && Y && Cnv && pi_pred && y_pred, "%s: null pointer", who);
+  FLGP_TRY(check_pg_common(Y, m, mnew, n_sample, who));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dC, dLC, dY, dCnv, flag, mean, dpi, dy;
+  const size_t mm = sizeof(double) * (size_t)m * m;
+  FLGP_TRY(dC.alloc(mm)); FLGP_TRY(dLC.alloc(mm)); FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
+  FLGP_TRY(dCnv.alloc(sizeof(double) * (size_t)mnew * m)); FLGP_TRY(flag.alloc(sizeof(int)));
+  FLGP_TRY(mean.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dpi.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_TRY(dy.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st.s));
+  FLGP_TRY(h2d(dC.p, C, mm, st.s));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(h2d(dCnv.p, Cnv, sizeof(double) * (size_t)mnew * m, st.s));
+  FLGP_HIP(hipMemcpyAsync(dLC.p, dC.p, mm, hipMemcpyDeviceToDevice, st.s));
+  FLGP_TRY(chol_blocked(st.s, dLC.as<double>(), m, m, flag.as<int>()));          // C = L_C L_C^T, once per call
+  PgChain P;
+  P.route = PG_DENSE; P.C = dC.as<double>(); P.LC = dLC.as<double>(); P.flag = flag.as<int>();
+  FLGP_TRY(P.alloc(m, 0));
+  FLGP_TRY(P.run(st.s, dY.as<double>(), n_sample, seed));
+  FLGP_TRY(P.collapsed_w(st.s));
+  FLGP_TRY(gemm_nn(st.s, mnew, 1, m, dCnv.as<double>(), mnew, P.x.as<double>(), m, mean.as<double>(), nullptr, 0));   // Cnv w
+  FLGP_TRY(pg_pi(st.s, mnew, mean.as<double>(), 0.0, nullptr, nullptr, nullptr, dpi.as<double>(), 1, dy.as<double>()));
+  FLGP_TRY(d2h(pi_pred, dpi.p, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_TRY(d2h(y_pred, dy.p, sizeof(double) * (size_t)mnew, st.s));
+  if (omega_out) FLGP_TRY(d2h(omega_out, P.omega.p, sizeof(double) * (size_t)m, st.s));
+  if (f_out) FLGP_TRY(d2h(f_out, P.f.p, sizeof(double) * (size_t)m, st.s));
+  return pg_verdict(st.s, flag.p, who);
+}
+
+extern "C" int flgp_eigenpair_pg_predict(const flgp_eigenpair *ep, int K, double t, double sigma, double sigma_nv,
+                                         const int *idx0, int m, const double *Y, const int *idx1, int mnew, int n_sample,
+                                         unsigned long long seed, double *pi_pred, double *y_pred, double *omega_out,
+                                         double *f_out) {
+  const char *who = "eigenpair_pg_predict";
+  FLGP_REQUIRE(idx0 && Y && idx1 && pi_pred && y_pred, "%s: null pointer", who);
+  FLGP_REQUIRE(std::isfinite(t), "%s: t must be finite", who);
+  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(sigma_nv), "%s: sigma must be finite and >= 0", who);
+  FLGP_TRY(check_pg_common(Y, m, mnew, n_sample, who));
+  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dY, flag, dpi, dy;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(flag.alloc(sizeof(int)));
+  FLGP_TRY(dpi.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dy.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st.s));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  PgMatch match;
+  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, idx0, m, idx1, mnew));
+  PgChain P;
+  FLGP_TRY(pg_eigen_binary(st.s, ep, K, t, sigma, sigma_nv, r0, r1, dY.as<double>(), n_sample, seed,
+                           sigma_nv != 0.0 ? &match : nullptr, P, flag, dpi.as<double>(), 1, dy.as<double>()));
+  FLGP_TRY(d2h(pi_pred, dpi.p, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_TRY(d2h(y_pred, dy.p, sizeof(double) * (size_t)mnew, st.s));
+  if (omega_out) FLGP_TRY(d2h(omega_out, P.omega.p, sizeof(double) * (size_t)m, st.s));
+  if (f_out) FLGP_TRY(d2h(f_out, P.f.p, sizeof(double) * (size_t)m, st.s));
+  return pg_verdict(st.s, flag.p, who);
+}
+
+// predict_logit_mult_gp_cpp (src/MultiClassification.cpp:57-88): one-vs-rest over the J classes of multi_train_split(Y),
+// class j exactly flgp_eigenpair_pg_predict with t = ts[j], sigma_nv = 0 and seed + j; the chains run one after another
+// on one stream.  labels: the first arg-max of each row of probs (m_new x J).
+extern "C" int flgp_eigenpair_pg_predict_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma,
+                                                    const int *idx0, int m, const double *Y, const int *idx1, int mnew,
+                                                    int n_sample, unsigned long long seed, double *probs, double *labels) {
+  const char *who = "eigenpair_pg_predict_multiclass";
+  FLGP_REQUIRE(ts && idx0 && Y && idx1 && probs && labels, "%s: null pointer", who);
+  FLGP_REQUIRE(J >= 1 && m >= 1 && mnew >= 1, "%s: bad shape (J=%d, m=%d, m_new=%d)", who, J, m, mnew);
+  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
+  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0, "%s: sigma must be finite and >= 0", who);
+  for (int j = 0; j < J; ++j) FLGP_REQUIRE(std::isfinite(ts[j]), "%s: ts[%d] must be finite", who, j);
+  for (int a = 0; a < m; ++a)
+    FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] < J && Y[a] == std::floor(Y[a]), "%s: Y[%d]=%g is not a class label in 0 .. %d", who, a,
+                 Y[a], J - 1);
+  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dY, flag, dprobs, dlab;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * J)); FLGP_TRY(flag.alloc(sizeof(int)));
+  FLGP_TRY(dprobs.alloc(sizeof(double) * (size_t)mnew * J)); FLGP_TRY(dlab.alloc(sizeof(double) * (size_t)mnew));
+  std::vector<double> aug((size_t)m * J, 0.0);          // multi_train_split (src/MultiClassification.cpp:14-26)
+  for (int a = 0; a < m; ++a) aug[(size_t)Y[a] * m + a] = 1.0;
+  FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st.s));
+  FLGP_TRY(h2d(dY.p, aug.data(), sizeof(double) * aug.size(), st.s));
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  for (int j = 0; j < J; ++j) {
+    PgChain P;
+    FLGP_TRY(pg_eigen_binary(st.s, ep, K, ts[j], sigma, 0.0, r0, r1, dY.as<double>() + (size_t)j * m, n_sample,
+                             seed + (unsigned long long)j, nullptr, P, flag, dprobs.as<double>() + (size_t)j * mnew, 1, nullptr));
+  }
+  FLGP_TRY(pg_argmax(st.s, mnew, J, dprobs.as<double>(), dlab.as<double>()));
+  FLGP_TRY(d2h(probs, dprobs.p, sizeof(double) * (size_t)mnew * J, st.s));
+  FLGP_TRY(d2h(labels, dlab.p, sizeof(double) * (size_t)mnew, st.s));
+  return pg_verdict(st.s, flag.p, who);
+}

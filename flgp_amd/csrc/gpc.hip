@@ -314,6 +314,16 @@ int gpc_scale2(hipStream_t st, const double *dM, long ldm, const double *d_a, co
   return check_launch("gpc_scale2_kernel");
 }
 
+int gpc_bmat(hipStream_t st, const double *dC, const double *d_sW, int m, double *dB) {
+  hipLaunchKernelGGL(gpc_b_kernel, dim3(ceil_div((long)m * m, 256)), dim3(256), 0, st, dC, d_sW, m, dB);
+  return check_launch("gpc_b_kernel");
+}
+
+int gpc_gemv(hipStream_t st, const double *dC, int m, const double *d_x, const double *d_s, double *d_y) {
+  hipLaunchKernelGGL(gpc_gemv_kernel, dim3(ceil_div(m, 64)), dim3(1024), 0, st, dC, m, d_x, d_s, d_y);
+  return check_launch("gpc_gemv_kernel");
+}
+
 int GpcNewton::alloc(int m_) {
   m = m_;
   const size_t v = sizeof(double) * (size_t)m;
