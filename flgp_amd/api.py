@@ -374,6 +374,28 @@ class ResidentEigenPair:
             mean[:, j] = post["mean"]; cov[:, j] = post["cov"]
         return {"mean": mean, "cov": cov}
 
+    def logit_objective(self, t, K, idx, Y, N=None, sigma=1e-3, approach="posterior", prior=None, tol=1e-5, max_iter=100,
+                        return_iters=False):
+        """The value train_lae_logit_gp_cpp's COBYLA minimises at t (src/train.cpp:14-34), on the resident pair with
+        C = HK(idx, idx) + sigma I: approach "marginal" (-amll) or "posterior" (plus the prior, ``prior = (p, q, tau)``,
+        None for PostOFData's defaults).  N None: one trial per row.  m <= K runs the dense loop of
+        ``marginal_log_likelihood_logit_la``, m > K a K x K low-rank loop (include/flgp_hip.h).  sigma's default is the R
+        logit wrappers'.  Returns the value, or ``(value, iters)`` with ``return_iters``."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        m = idx.size
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        if Y.size != m:
+            raise ValueError("Y must have one entry per row of idx")
+        N = None if N is None else np.ascontiguousarray(np.broadcast_to(np.asarray(N, dtype=np.float64), (m,)))
+        pr = None if prior is None else np.ascontiguousarray(np.asarray(prior, dtype=np.float64).reshape(-1))
+        if pr is not None and pr.size != 3:
+            raise ValueError("prior must hold (p, q, tau)")
+        value = ctypes.c_double(); it = ctypes.c_int()
+        check(_lib.lib().flgp_eigenpair_logit_objective(self._h, int(K), _ptr(idx), m, _ptr(Y), _ptr(N), float(sigma),
+                                                        _b(approach), _ptr(pr), float(t), float(tol), int(max_iter),
+                                                        ctypes.byref(value), ctypes.byref(it)))
+        return (value.value, it.value) if return_iters else value.value
+
     def regression_objective(self, x, K, idx, Y, sigma=1e-5, noise="same", approach="posterior", prior=None, grad=True):
         """The objective train_regression_gp_cpp minimises (src/train.cpp:333-555) and its gradient, on the resident pair:
         ``x = (t, noise)`` for noise = "same", ``(t, noise_1, ..., noise_m)`` for "different"; approach "marginal" (the

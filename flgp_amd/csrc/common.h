@@ -223,6 +223,17 @@ struct GpcNewton {
   int amll(hipStream_t st, const double *dY, const double *dN, double *out);   // synchronises
   static int pivot_error(int bad, const char *who, int iter);   // iter 0: the factorisation at the final f
 };
+// The elementwise steps and final sums of the low-rank Newton loop (m > K, C = V1 L V1^T + sigma I; eigenpair.hip).
+// gpc_weights: sW and b from f (gpc_w_kernel); gpc_step: diff = |f - f_new|_1 in a fixed order, f <- f_new;
+// gpc_lr_dvec: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh; gpc_lr_a: a = b - sW .* (dh .* (g - Xv));
+// gpc_lr_amll: -0.5 a^T f + sum Y log pi + sum (N - Y) log(1 - pi) - 0.5 sum log D - sum log (L_Q)_kk (K x K factor).
+int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b);
+int gpc_step(hipStream_t st, double *d_f, const double *d_fnew, int m, double *d_diff);
+int gpc_lr_dvec(hipStream_t st, const double *d_sW, double sigma, int m, double *d_D, double *d_dh, double *d_xs);
+int gpc_lr_a(hipStream_t st, const double *d_b, const double *d_sW, const double *d_dh, const double *d_g, const double *d_Xv,
+             int m, double *d_a);
+int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const double *d_Y, const double *d_N, const double *d_D,
+                const double *d_LQ, int K, int m, double *d_out);
 
 // The regression training objectives on the device (gpr_grad.hip).  tri_inverse: X = L^-1 (m x m, upper triangle zeroed)
 // for a lower factor of chol_blocked; dT holds 64 x m doubles, `work` (we doubles) bounds the GEMM's k-split.

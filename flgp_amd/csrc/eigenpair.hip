@@ -1,6 +1,6 @@
 // Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products,
 // regression prediction and posterior variance (dense algebra in gpr.hip) and the Laplace approximation of
-// the logit GP (gpc.hip).  Each entry checks its arguments on the host, then runs on one stream of its own.
+// the logit GP (gpc.hip) with its training objective (a K x K low-rank Newton loop for m > K).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -539,6 +539,142 @@ extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int
   }
   *value = h[0];
   if (want_grad) std::memcpy(grad, h.data() + 1, sizeof(double) * (size_t)nx);
+  return FLGP_OK;
+}
+
+// ---- logit training objective: what train_lae_logit_gp_cpp's COBYLA minimises, on the resident pair ------
+namespace {
+// Alg. 3.1 for m > K on C = V1 L V1^T + sigma I (L = exp(-t (1 - values))), O(m K^2) per iteration, never an m x m matrix.
+// With D = 1 + sigma W, B = sW C sW + I = D + U L U^T (U = sW V1), so with X = D^-1/2 U L^1/2 (m x K) and Q = I + X^T X:
+//   B^-1 y = D^-1 y - D^-1/2 X Q^-1 X^T D^-1/2 y,   det B = det D det Q.
+// Per iteration: sW, b from f; D, X, Q factored (K x K); c = C b; r = B^-1 (sW c); a = b - sW r; f_new = C a.  As in
+// GpcNewton, a, D and L_Q stay those of the LAST iteration and f is the final mode; everything is fixed-order.
+struct GpcLowRank {
+  int m = 0, K = 0;
+  double sigma = 0.0;
+  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;    // V1 (m x K at ld1), L, L^1/2
+  long ld1 = 0;
+  DevBuf f, fnew, sW, b, a, D, dh, xs, c, g, Xv, X, Q, u, scal, flag, work;
+  size_t we = 0;
+
+  int alloc(int m_, int K_) {
+    m = m_; K = K_;
+    const size_t v = sizeof(double) * (size_t)m;
+    FLGP_TRY(f.alloc(v)); FLGP_TRY(fnew.alloc(v)); FLGP_TRY(sW.alloc(v)); FLGP_TRY(b.alloc(v)); FLGP_TRY(a.alloc(v));
+    FLGP_TRY(D.alloc(v)); FLGP_TRY(dh.alloc(v)); FLGP_TRY(xs.alloc(v)); FLGP_TRY(c.alloc(v)); FLGP_TRY(g.alloc(v));
+    FLGP_TRY(Xv.alloc(v));
+    FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(u.alloc(sizeof(double) * (size_t)K));
+    we = (size_t)128 * K * K + (size_t)64 * K + 1024;
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    FLGP_TRY(scal.alloc(sizeof(double) * 2)); FLGP_TRY(flag.alloc(sizeof(int)));
+    return FLGP_OK;
+  }
+  // out = V1 (L (V1^T x)) + sigma x   (Xv is the scratch)
+  int cmul(hipStream_t st, const double *x, double *out) {
+    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, x, m, u.as<double>(), work.as<double>(), we));
+    FLGP_TRY(pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>()));
+    FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, Xv.as<double>(), nullptr, 0));
+    return pg_axpy3(st, m, Xv.as<double>(), nullptr, sigma, x, out);
+  }
+  int iteration(hipStream_t st, const double *dY, const double *dN) {
+    ProfScope ps("logit_lr_newton_iter", st, 0.0);
+    FLGP_TRY(gpc_weights(st, f.as<double>(), dY, dN, m, sW.as<double>(), b.as<double>()));
+    FLGP_TRY(gpc_lr_dvec(st, sW.as<double>(), sigma, m, D.as<double>(), dh.as<double>(), xs.as<double>()));
+    FLGP_TRY(gpc_scale2(st, V1, ld1, xs.as<double>(), ls, m, K, X.as<double>()));                                // X
+    FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, Q.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_add_diag(st, Q.as<double>(), K, 1.0));
+    FLGP_TRY(chol_blocked(st, Q.as<double>(), K, K, flag.as<int>()));                                             // Q = L_Q L_Q^T
+    FLGP_TRY(cmul(st, b.as<double>(), c.as<double>()));                                                           // c = C b
+    FLGP_TRY(pg_mul(st, m, xs.as<double>(), c.as<double>(), nullptr, g.as<double>()));                           // g = D^-1/2 sW c
+    FLGP_TRY(gemm_tn(st, K, 1, m, X.as<double>(), m, g.as<double>(), m, u.as<double>(), work.as<double>(), we));  // X^T g
+    FLGP_TRY(chol_trsv(st, Q.as<double>(), K, K, u.as<double>(), K, 1, 3, flag.as<int>()));                        // Q^-1 (.)
+    FLGP_TRY(gemm_nn(st, m, 1, K, X.as<double>(), m, u.as<double>(), K, Xv.as<double>(), nullptr, 0));           // X (.)
+    FLGP_TRY(gpc_lr_a(st, b.as<double>(), sW.as<double>(), dh.as<double>(), g.as<double>(), Xv.as<double>(), m, a.as<double>()));
+    FLGP_TRY(cmul(st, a.as<double>(), fnew.as<double>()));                                                        // f_new = C a
+    return gpc_step(st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
+  }
+  // the loop from f = 0 with GpcNewton::run's host protocol (12 bytes read back per iteration), then the final sums
+  int run(hipStream_t st, const double *dY, const double *dN, double tol, int max_iter, const char *who, int *iters, double *amll) {
+    FLGP_HIP(hipMemsetAsync(f.p, 0, sizeof(double) * (size_t)m, st));
+    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    *iters = 0;
+    for (int it = 0; it < max_iter; ++it) {
+      FLGP_TRY(iteration(st, dY, dN));
+      double diff = 0.0;
+      int bad = 0;
+      FLGP_HIP(hipMemcpyAsync(&diff, scal.p, sizeof(double), hipMemcpyDeviceToHost, st));
+      FLGP_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+      FLGP_HIP(hipStreamSynchronize(st));
+      *iters = it + 1;
+      FLGP_TRY(GpcNewton::pivot_error(bad, who, it + 1));
+      if (diff < tol) break;
+    }
+    FLGP_TRY(gpc_lr_amll(st, f.as<double>(), a.as<double>(), dY, dN, D.as<double>(), Q.as<double>(), K, m, scal.as<double>() + 1));
+    FLGP_HIP(hipMemcpyAsync(amll, scal.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, st));
+    FLGP_HIP(hipStreamSynchronize(st));
+    return FLGP_OK;
+  }
+};
+}  // namespace
+
+// negative_marginal_likelihood_logit_cpp / negative_log_posterior_logit_cpp (src/train.cpp:14-34): m <= K runs
+// flgp_eigenpair_logit_marginal_likelihood's dense loop unchanged, m > K the low-rank loop above.
+extern "C" int flgp_eigenpair_logit_objective(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y,
+                                              const double *N, double sigma, const char *approach, const double *prior,
+                                              double t, double tol, int max_iter, double *value, int *iters) {
+  const char *who = "logit_objective";
+  FLGP_REQUIRE(approach, "%s: null pointer", who);
+  const bool posterior = std::strcmp(approach, "posterior") == 0;
+  if (!posterior && std::strcmp(approach, "marginal") != 0) {
+    set_error("This model selection approach is not supported!");
+    return FLGP_ERR_UNSUPPORTED;
+  }
+  FLGP_REQUIRE(ep && idx && Y && value, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1, "%s: bad shape (K=%d of %d, m=%d, max_iter=%d)", who, K, ep->K,
+               m, max_iter);
+  Rows r;
+  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
+  FLGP_TRY(check_labels(Y, N, m, who));
+  FLGP_REQUIRE(std::isfinite(t), "%s: t=%g must be finite", who, t);
+  FLGP_REQUIRE(!posterior || t > 0.0, "%s: t=%g must be positive under \"posterior\"", who, t);
+  FLGP_REQUIRE(sigma >= 0.0 && std::isfinite(sigma), "%s: sigma=%g must be finite and >= 0", who, sigma);
+  const double dflt[3] = {1e-2, 10.0, 2.0};                     // PostOFData (src/train.h:138-140)
+  double pr[3];
+  for (int k = 0; k < 3; ++k) pr[k] = prior ? prior[k] : dflt[k];
+  FLGP_REQUIRE(all_finite(pr, 3), "%s: prior (p, q, tau) must be finite", who);
+  std::vector<double> ones;
+  if (!N) { ones.assign((size_t)m, 1.0); N = ones.data(); }    // the one-vs-rest route (src/MultiClassification.cpp:36)
+
+  Stream st;
+  FLGP_TRY(st.create());
+  double amll = 0.0;
+  int it = 0;
+  if (m <= K) {
+    // C = HK(idx, idx) + sigma I       (src/train.cpp:30-31)
+    DevBuf C, work;
+    FLGP_TRY(hk_c11(st.s, ep, K, t, r, sigma, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
+    FLGP_TRY(logit_la_on_device(st.s, C.as<double>(), m, Y, N, tol, max_iter, &amll, &it, who));
+  } else {
+    GprCtx G;
+    FLGP_TRY(G.prepare(st.s, ep, K, t));                        // ls = L^1/2, l = L
+    FLGP_TRY(r.gather(st.s, ep, K));
+    DevBuf dY, dN;
+    FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(dN.alloc(sizeof(double) * (size_t)m));
+    FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
+    FLGP_TRY(h2d(dN.p, N, sizeof(double) * (size_t)m, st.s));
+    GpcLowRank S;
+    S.sigma = sigma; S.V1 = r.V; S.ld1 = r.ld; S.l = G.l.as<double>(); S.ls = G.ls.as<double>();
+    FLGP_TRY(S.alloc(m, K));
+    FLGP_TRY(S.run(st.s, dY.as<double>(), dN.as<double>(), tol, max_iter, who, &it, &amll));
+  }
+  if (iters) *iters = it;
+  if (posterior) {
+    const double p = pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]);   // src/train.cpp:17-24
+    *value = -amll + p;
+  } else {
+    *value = -amll;
+  }
   return FLGP_OK;
 }
 

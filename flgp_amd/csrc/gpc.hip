@@ -398,6 +398,81 @@ int GpcNewton::amll(hipStream_t st, const double *dY, const double *dN, double *
   return FLGP_OK;
 }
 
+// ---- the low-rank Newton loop (m > K, C = V1 L V1^T + sigma I; the loop itself is in eigenpair.hip) -------------------
+
+// W = sW^2: D = 1 + sigma W, dh = D^-1/2, xs = sW dh (the row scaling of X = diag(xs) V1 L^1/2)
+__global__ void gpc_lr_d_kernel(const double *__restrict__ sW, double sigma, int m, double *__restrict__ D,
+                                double *__restrict__ dh, double *__restrict__ xs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const double s = sW[i], d = 1.0 + sigma * (s * s), h = 1.0 / __builtin_sqrt(d);
+  D[i] = d; dh[i] = h; xs[i] = s * h;
+}
+
+// a = b - sW .* r with r = B^-1 (sW .* c) = dh .* (g - Xv), g = dh .* sW .* c, Xv = X Q^-1 X^T g
+__global__ void gpc_lr_a_kernel(const double *__restrict__ b, const double *__restrict__ sW, const double *__restrict__ dh,
+                                const double *__restrict__ g, const double *__restrict__ Xv, int m, double *__restrict__ a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) a[i] = b[i] - sW[i] * (dh[i] * (g[i] - Xv[i]));
+}
+
+// amll = -0.5 sum(a f) + (sum(Y log pi) + sum((N - Y) log(1 - pi))) - 0.5 sum(log D_i) - sum(log (L_Q)_kk): log det B =
+// log det D + log det Q exactly (no 1e-9 on the pivots: the one departure from gpc_amll_kernel, include/flgp_hip.h)
+__global__ __launch_bounds__(1024) void gpc_lr_amll_kernel(const double *__restrict__ f, const double *__restrict__ a,
+                                                           const double *__restrict__ Y, const double *__restrict__ N,
+                                                           const double *__restrict__ D, const double *__restrict__ LQ, int K,
+                                                           int m, double *__restrict__ out) {
+  __shared__ double red[1024];
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
+  for (int i = threadIdx.x; i < m; i += 1024) {
+    const double pi = 1.0 / (1.0 + exp(-f[i]));
+    s1 += a[i] * f[i];
+    s2 += Y[i] * log(pi);
+    s3 += (N[i] - Y[i]) * log(1.0 - pi);
+    s4 += log(D[i]);
+  }
+  for (int k = threadIdx.x; k < K; k += 1024) s5 += log(LQ[(size_t)k * K + k]);
+  s1 = block_sum_1024(s1, red);
+  s2 = block_sum_1024(s2, red);
+  s3 = block_sum_1024(s3, red);
+  s4 = block_sum_1024(s4, red);
+  s5 = block_sum_1024(s5, red);
+  if (threadIdx.x == 0) {
+    double amll = -0.5 * s1;
+    amll += s2 + s3;
+    amll -= 0.5 * s4;
+    amll -= s5;
+    out[0] = amll;
+  }
+}
+
+int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b) {
+  hipLaunchKernelGGL(gpc_w_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_f, d_Y, d_N, m, d_sW, d_b, (double *)nullptr);
+  return check_launch("gpc_w_kernel");
+}
+
+int gpc_step(hipStream_t st, double *d_f, const double *d_fnew, int m, double *d_diff) {
+  hipLaunchKernelGGL(gpc_step_kernel, dim3(1), dim3(1024), 0, st, d_f, d_fnew, m, d_diff);
+  return check_launch("gpc_step_kernel");
+}
+
+int gpc_lr_dvec(hipStream_t st, const double *d_sW, double sigma, int m, double *d_D, double *d_dh, double *d_xs) {
+  hipLaunchKernelGGL(gpc_lr_d_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_sW, sigma, m, d_D, d_dh, d_xs);
+  return check_launch("gpc_lr_d_kernel");
+}
+
+int gpc_lr_a(hipStream_t st, const double *d_b, const double *d_sW, const double *d_dh, const double *d_g, const double *d_Xv,
+             int m, double *d_a) {
+  hipLaunchKernelGGL(gpc_lr_a_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_sW, d_dh, d_g, d_Xv, m, d_a);
+  return check_launch("gpc_lr_a_kernel");
+}
+
+int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const double *d_Y, const double *d_N, const double *d_D,
+                const double *d_LQ, int K, int m, double *d_out) {
+  hipLaunchKernelGGL(gpc_lr_amll_kernel, dim3(1), dim3(1024), 0, st, d_f, d_a, d_Y, d_N, d_D, d_LQ, K, m, d_out);
+  return check_launch("gpc_lr_amll_kernel");
+}
+
 }  // namespace flgp
 
 using namespace flgp;
