@@ -1,6 +1,9 @@
-// Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products,
-// regression prediction and posterior variance (dense algebra in gpr.hip) and the Laplace approximation of
-// the logit GP (gpc.hip) with its training objective (a K x K low-rank Newton loop for m > K).  Each entry checks its arguments on the host, then runs on one stream of its own.
+// Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products;
+// regression prediction, posterior variance and the training objectives with their gradients (kernels in
+// gpr.hip and gpr_grad.hip); the Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
+// 8f-5, gpc.hip); Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
+// woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
+// the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -10,10 +13,16 @@ using namespace flgp;
 
 namespace {
 
+// X = the host's `bytes` at `host`, allocated and copied on `st`
+int upload(DevBuf &X, const void *host, size_t bytes, hipStream_t st) {
+  FLGP_TRY(X.alloc(bytes));
+  return h2d(X.p, host, bytes, st);
+}
+
 // One index array into the pair's rows.  check() refuses a row outside [0, n) before any device work, as
-// "<who>: <name>[<a>]=<v> out of range".  At first use a contiguous range is taken in place (row0) and any other set is
-// uploaded once (d): the scan runs beside the device work queued by then.  gather() makes V = vectors[rows, 0:K] (m x K at
-// ld; a range is read in place).
+// "<who>: <name>[<a>]=<v> out of range".  At first use (resolve) a contiguous range is taken in place (row0) and any other
+// set is uploaded once (d): the scan runs beside the device work queued by then.  gather() makes V = vectors[rows, 0:K]
+// (m x K at ld; a range is read in place).
 struct Rows {
   const int *idx = nullptr;
   int m = 0, row0 = 0;
@@ -27,17 +36,16 @@ struct Rows {
     idx = idx_; m = m_;
     return FLGP_OK;
   }
-  int upload(hipStream_t st) {
+  int resolve(hipStream_t st) {
     if (resolved) return FLGP_OK;
     resolved = true;
     if (is_range(idx, m)) { row0 = idx[0]; return FLGP_OK; }
-    FLGP_TRY(didx.alloc(sizeof(int) * (size_t)m));
-    FLGP_TRY(h2d(didx.p, idx, sizeof(int) * (size_t)m, st));
+    FLGP_TRY(upload(didx, idx, sizeof(int) * (size_t)m, st));
     d = didx.as<int>();
     return FLGP_OK;
   }
   int gather(hipStream_t st, const flgp_eigenpair *ep, int K) {
-    FLGP_TRY(upload(st));
+    FLGP_TRY(resolve(st));
     if (!d) { V = (const double *)ep->vectors.p + row0; ld = ep->n; return FLGP_OK; }
     FLGP_TRY(vbuf.alloc(sizeof(double) * (size_t)m * K));
     FLGP_TRY(flgp_dev_gather_rows(st, (const double *)ep->vectors.p, ep->n, d, m, K, vbuf.as<double>()));
@@ -56,7 +64,7 @@ int hk(hipStream_t st, const flgp_eigenpair *ep, int K, double t, const Rows &a,
 // sigma launches nothing: the diagonal of HK(r, r) is a sum of squares, never -0.
 int hk_c11(hipStream_t st, const flgp_eigenpair *ep, int K, double t, Rows &r, double sigma, DevBuf &C, DevBuf &work,
            size_t work_bytes) {
-  FLGP_TRY(r.upload(st));
+  FLGP_TRY(r.resolve(st));
   FLGP_TRY(C.alloc(sizeof(double) * (size_t)r.m * r.m));
   FLGP_TRY(work.alloc(work_bytes));
   FLGP_TRY(hk(st, ep, K, t, r, r, C.as<double>(), work.as<double>()));
@@ -64,7 +72,9 @@ int hk_c11(hipStream_t st, const flgp_eigenpair *ep, int K, double t, Rows &r, d
 }
 
 // Column-major products, C (M x N, ld M) = A^T B with A k x M, or = A B with A M x k; B k x N.  `work` / `we` go to
-// gemm_launch unchanged: they bound its k-split, so they decide the bits.
+// gemm_launch unchanged: they bound its k-split, so they decide the bits.  vt_work_elems: the `we` of the consumers that
+// form a K x K and a K x q product V^T (.) from one workspace.
+size_t vt_work_elems(int K, int q) { return (size_t)128 * K * K + (size_t)64 * K * q + 1024; }
 int gemm_tn(hipStream_t st, int M, int N, int k, const double *A, long lda, const double *B, long ldb, double *C, double *work,
             size_t we) {
   return gemm_launch(st, M, N, k, 1.0, A, lda, 1, B, 1, ldb, 0.0, nullptr, 0, 0, C, 1, M, work, we, 0.0, nullptr);
@@ -86,10 +96,9 @@ int v_product(const flgp_eigenpair *ep, int K, const int *idx, int m, const doub
   FLGP_TRY(R.gather(st.s, ep, K));
   const int brows = tn ? m : K, orows = tn ? K : m;
   DevBuf dB, out, work;
-  if (B) FLGP_TRY(dB.alloc(sizeof(double) * (size_t)brows * q));
   FLGP_TRY(out.alloc(sizeof(double) * (size_t)orows * q));
   if (tn) FLGP_TRY(work.alloc(sizeof(double) * we));
-  if (B) FLGP_TRY(h2d(dB.p, B, sizeof(double) * (size_t)brows * q, st.s));
+  if (B) FLGP_TRY(upload(dB, B, sizeof(double) * (size_t)brows * q, st.s));
   const double *b = B ? dB.as<double>() : R.V;
   const long ldb = B ? brows : R.ld;
   FLGP_TRY(tn ? gemm_tn(st.s, K, q, m, R.V, R.ld, b, ldb, out.as<double>(), work.as<double>(), we)
@@ -136,54 +145,20 @@ struct GprCtx {
   }
 };
 
-// Woodbury, noisepar = "same": Q = Ls V^T V Ls + c I (K x K), c = noise + sigma             (src/Predict.cpp:59-74)
-int woodbury_same(hipStream_t st, GprCtx &G, int K, int q, const Rows &r0, const Rows &r1, const double *dY, double c,
-                  double *out) {
-  const int m = r0.m;
-  DevBuf VtV, VtY, Q, R, T1, work;
-  const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
-  FLGP_TRY(VtV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-  FLGP_TRY(VtY.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
-  FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
-  FLGP_TRY(gemm_tn(st, K, K, m, r0.V, r0.ld, r0.V, r0.ld, VtV.as<double>(), work.as<double>(), we));
-  FLGP_TRY(gemm_tn(st, K, q, m, r0.V, r0.ld, dY, m, VtY.as<double>(), work.as<double>(), we));
-  FLGP_TRY(gpr_q(st, VtV.as<double>(), G.ls.as<double>(), K, c, Q.as<double>()));
-  FLGP_TRY(gpr_scale(st, VtY.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));          // Ls V^T Y
-  FLGP_TRY(chol_solve(st, Q.as<double>(), K, R.as<double>(), q, G.flag.as<int>()));                       // Q^-1 (.)
-  FLGP_TRY(gpr_scale(st, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));            // Ls (.)
-  // V^T alpha = (V^T Y - V^T V Ls Q^-1 Ls V^T Y) / (noise + sigma)
-  FLGP_TRY(gemm_nn(st, K, q, K, VtV.as<double>(), K, R.as<double>(), K, T1.as<double>(), nullptr, 0));
-  FLGP_TRY(gpr_diff(st, VtY.as<double>(), T1.as<double>(), 1.0 / c, (long)K * q, T1.as<double>()));
-  FLGP_TRY(gpr_scale(st, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));           // exp(-t lam) (.)
-  return gemm_nn(st, r1.m, q, K, r1.V, r1.ld, T1.as<double>(), K, out, nullptr, 0);
-}
-
-// Woodbury, noisepar = "different" (src/Predict.cpp:92-110): with Z^-1 = diag(1 / (noise_i + sigma)),
-// Q = Ls V^T Z^-1 V Ls + I,  alpha = Z^-1 Y - Z^-1 V Ls Q^-1 Ls V^T Z^-1 Y; only
-// V^T alpha = V^T Z^-1 Y - (V^T Z^-1 V) Ls Q^-1 Ls V^T Z^-1 Y is formed (K x q), never the m x q alpha.
-int woodbury_different(hipStream_t st, GprCtx &G, int K, int q, const Rows &r0, const Rows &r1, const double *dY,
-                       const double *dnoise, double sigma, double *out) {
-  const int m = r0.m;
-  DevBuf zinv, ZV, ZY, VtZV, VtZY, Q, R, T1, work;
-  const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
-  FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
-  FLGP_TRY(VtZV.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-  FLGP_TRY(VtZY.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
-  FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
-  FLGP_TRY(gpr_zinv(st, dnoise, sigma, m, zinv.as<double>()));                                  // :98-101
-  FLGP_TRY(gpr_rowscale_ld(st, r0.V, r0.ld, zinv.as<double>(), m, K, ZV.as<double>()));        // Z^-1 V
-  FLGP_TRY(gpr_rowscale_ld(st, dY, m, zinv.as<double>(), m, q, ZY.as<double>()));               // Z^-1 Y
-  FLGP_TRY(gemm_tn(st, K, K, m, r0.V, r0.ld, ZV.as<double>(), m, VtZV.as<double>(), work.as<double>(), we));   // V^T Z^-1 V   :102
-  FLGP_TRY(gemm_tn(st, K, q, m, r0.V, r0.ld, ZY.as<double>(), m, VtZY.as<double>(), work.as<double>(), we));   // V^T Z^-1 Y
-  FLGP_TRY(gpr_q(st, VtZV.as<double>(), G.ls.as<double>(), K, 1.0, Q.as<double>()));                        // :103-104
-  FLGP_TRY(gpr_scale(st, VtZY.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));
-  FLGP_TRY(chol_solve(st, Q.as<double>(), K, R.as<double>(), q, G.flag.as<int>()));                         // :105-106
-  FLGP_TRY(gpr_scale(st, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));
-  FLGP_TRY(gemm_nn(st, K, q, K, VtZV.as<double>(), K, R.as<double>(), K, T1.as<double>(), nullptr, 0));
-  FLGP_TRY(gpr_diff(st, VtZY.as<double>(), T1.as<double>(), 1.0, (long)K * q, T1.as<double>()));            // V^T alpha
-  FLGP_TRY(gpr_scale(st, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));               // exp(-t lam) (.)
-  return gemm_nn(st, r1.m, q, K, r1.V, r1.ld, T1.as<double>(), K, out, nullptr, 0);                         // :108-109
+// The regression Woodbury step (m > K) on M = V^T Z^-1 V (K x K) and the right-hand side S = V^T Z^-1 Y (K x q), both the
+// caller's:  Q = Ls M Ls + c I,  T1 = (S - M Ls Q^-1 Ls S) * scale.  noisepar "same" (src/Predict.cpp:59-74) has Z = I,
+// c = noise + sigma and scale = 1 / c; "different" (:92-110) has Z = diag(noise_i + sigma) and c = scale = 1.  T1 is then
+// V^T alpha: the m x q alpha is never formed.  The posterior variance (src/Utils.cpp:238-246) passes M as its own S.
+// Q (K x K) and R (K x q) are scratch.  No GEMM here splits its k, so the step takes no workspace: the V^T products that
+// do, and their `we`, stay with the callers.
+int woodbury_step(hipStream_t st, GprCtx &G, int K, int q, const double *M, const double *S, double c, double scale, double *Q,
+                  double *R, double *T1) {
+  FLGP_TRY(gpr_q(st, M, G.ls.as<double>(), K, c, Q));
+  FLGP_TRY(gpr_scale(st, S, G.ls.as<double>(), nullptr, K, q, R));          // Ls S
+  FLGP_TRY(chol_solve(st, Q, K, R, q, G.flag.as<int>()));                    // Q^-1 (.)
+  FLGP_TRY(gpr_scale(st, R, G.ls.as<double>(), nullptr, K, q, R));          // Ls (.)
+  FLGP_TRY(gemm_nn(st, K, q, K, M, K, R, K, T1, nullptr, 0));
+  return gpr_diff(st, S, T1, scale, (long)K * q, T1);
 }
 
 // predict_regression_cpp (reference src/Predict.cpp:40-110): noise_vec == nullptr is noisepar = "same" (one variance
@@ -204,15 +179,13 @@ int predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, 
   GprCtx G;
   FLGP_TRY(G.prepare(st.s, ep, K, t));
   DevBuf dY, out, dnoise;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q));
   FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew * q));
-  if (noise_vec) FLGP_TRY(dnoise.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
-  if (noise_vec) FLGP_TRY(h2d(dnoise.p, noise_vec, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * q, st.s));
+  if (noise_vec) FLGP_TRY(upload(dnoise, noise_vec, sizeof(double) * (size_t)m, st.s));
   if (m <= K) {
     // Cvv + sigma I + (noise I or diag(noise)), Cholesky, alpha = C^-1 Y, Y_pred = Cnv alpha   (src/Predict.cpp:48-58, 78-91)
     DevBuf C, Cnv, work;
-    FLGP_TRY(r1.upload(st.s));
+    FLGP_TRY(r1.resolve(st.s));
     FLGP_TRY(Cnv.alloc(sizeof(double) * (size_t)mnew * m));
     FLGP_TRY(hk_c11(st.s, ep, K, t, r0, sigma, C, work, flgp_dev_hk_workspace(std::max(m, mnew), m, K, 1)));
     FLGP_TRY(noise_vec ? gpr_add_diag_vec(st.s, C.as<double>(), m, dnoise.as<double>()) : gpr_add_diag(st.s, C.as<double>(), m, noise));
@@ -220,10 +193,30 @@ int predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, 
     FLGP_TRY(chol_solve(st.s, C.as<double>(), m, dY.as<double>(), q, G.flag.as<int>()));
     FLGP_TRY(gemm_nn(st.s, mnew, q, m, Cnv.as<double>(), mnew, dY.as<double>(), m, out.as<double>(), nullptr, 0));
   } else {
+    // V^T alpha by the Woodbury step, then Y_pred = V2 exp(-t lam) V^T alpha                   (src/Predict.cpp:59-75, 92-110)
     FLGP_TRY(r0.gather(st.s, ep, K));
     FLGP_TRY(r1.gather(st.s, ep, K));
-    FLGP_TRY(noise_vec ? woodbury_different(st.s, G, K, q, r0, r1, dY.as<double>(), dnoise.as<double>(), sigma, out.as<double>())
-                       : woodbury_same(st.s, G, K, q, r0, r1, dY.as<double>(), noise + sigma, out.as<double>()));
+    DevBuf zinv, ZV, ZY, M, S, Q, R, T1, work;
+    const size_t we = vt_work_elems(K, q);
+    FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(S.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
+    FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(work.alloc(sizeof(double) * we));
+    const double *Vz = r0.V, *Yz = dY.as<double>();                                               // Z^-1 V, Z^-1 Y: "same" has Z = I
+    long ldz = r0.ld;
+    double c = noise + sigma, scale = 1.0 / c;
+    if (noise_vec) {
+      FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
+      FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
+      FLGP_TRY(gpr_zinv(st.s, dnoise.as<double>(), sigma, m, zinv.as<double>()));                // :98-101
+      FLGP_TRY(gpr_rowscale_ld(st.s, r0.V, r0.ld, zinv.as<double>(), m, K, ZV.as<double>()));
+      FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, zinv.as<double>(), m, q, ZY.as<double>()));
+      Vz = ZV.as<double>(); ldz = m; Yz = ZY.as<double>(); c = scale = 1.0;
+    }
+    FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, Vz, ldz, M.as<double>(), work.as<double>(), we));    // V^T Z^-1 V   :102
+    FLGP_TRY(gemm_tn(st.s, K, q, m, r0.V, r0.ld, Yz, m, S.as<double>(), work.as<double>(), we));      // V^T Z^-1 Y
+    FLGP_TRY(woodbury_step(st.s, G, K, q, M.as<double>(), S.as<double>(), c, scale, Q.as<double>(), R.as<double>(), T1.as<double>()));
+    FLGP_TRY(gpr_scale(st.s, T1.as<double>(), G.l.as<double>(), nullptr, K, q, T1.as<double>()));          // exp(-t lam) (.)
+    FLGP_TRY(gemm_nn(st.s, mnew, q, K, r1.V, r1.ld, T1.as<double>(), K, out.as<double>(), nullptr, 0));    // :108-109
   }
   FLGP_TRY(d2h(Y_pred, out.p, sizeof(double) * (size_t)mnew * q, st.s));
   return G.verdict(st.s, "predict_regression");
@@ -277,12 +270,8 @@ extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K
     FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(T1.alloc(sizeof(double) * (size_t)K * K));
     FLGP_TRY(W.alloc(sizeof(double) * (size_t)mnew * K)); FLGP_TRY(work.alloc(sizeof(double) * we));
     FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, r0.V, r0.ld, VtV.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_q(st.s, VtV.as<double>(), G.ls.as<double>(), K, c, Q.as<double>()));
-    FLGP_TRY(gpr_scale(st.s, VtV.as<double>(), G.ls.as<double>(), nullptr, K, K, R.as<double>()));          // Ls V1^T V1
-    FLGP_TRY(chol_solve(st.s, Q.as<double>(), K, R.as<double>(), K, G.flag.as<int>()));
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, K, R.as<double>()));            // Ls Q^-1 Ls VtV
-    FLGP_TRY(gemm_nn(st.s, K, K, K, VtV.as<double>(), K, R.as<double>(), K, T1.as<double>(), nullptr, 0));
-    FLGP_TRY(gpr_diff(st.s, VtV.as<double>(), T1.as<double>(), 1.0 / c, (long)K * K, T1.as<double>()));     // (VtV - ...)/(var+sigma)
+    FLGP_TRY(woodbury_step(st.s, G, K, K, VtV.as<double>(), VtV.as<double>(), c, 1.0 / c, Q.as<double>(), R.as<double>(),
+                           T1.as<double>()));                                                              // (VtV - ...)/(var+sigma)
     FLGP_TRY(gpr_scale(st.s, T1.as<double>(), G.l.as<double>(), G.l.as<double>(), K, K, T1.as<double>()));   // L (.) L
     FLGP_TRY(gemm_nn(st.s, mnew, K, K, r1.V, r1.ld, T1.as<double>(), K, W.as<double>(), nullptr, 0));      // V2 alpha
     FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, W.as<double>(), mnew, K, G.l.as<double>(), c, out.as<double>()));
@@ -305,9 +294,8 @@ int check_labels(const double *Y, const double *N, int m, const char *who) {
 int logit_la_on_device(hipStream_t st, const double *dC, int m, const double *Y, const double *N, double tol, int max_iter,
                        double *amll, int *iters, const char *who) {
   DevBuf dY, dN;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(dN.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st));
-  FLGP_TRY(h2d(dN.p, N, sizeof(double) * (size_t)m, st));
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st));
+  FLGP_TRY(upload(dN, N, sizeof(double) * (size_t)m, st));
   GpcNewton S;
   FLGP_TRY(S.alloc(m));
   int it = 0;
@@ -325,8 +313,7 @@ extern "C" int flgp_logit_la_marginal_likelihood(const double *C, int m, const d
   Stream st;
   FLGP_TRY(st.create());
   DevBuf dC;
-  FLGP_TRY(dC.alloc(sizeof(double) * (size_t)m * m));
-  FLGP_TRY(h2d(dC.p, C, sizeof(double) * (size_t)m * m, st.s));
+  FLGP_TRY(upload(dC, C, sizeof(double) * (size_t)m * m, st.s));
   return logit_la_on_device(st.s, dC.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_la_marginal_likelihood");
 }
 
@@ -367,8 +354,7 @@ extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep,
   FLGP_TRY(G.prepare(st.s, ep, K, t));                    // G.l = exp(-t (1 - values))
   DevBuf C, work, dY;
   FLGP_TRY(hk_c11(st.s, ep, K, t, r0, sigma11, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
   // the mode (N = 1), then B factored again at the final f          (src/Utils.cpp:268-293)
   GpcNewton S;
   FLGP_TRY(S.alloc(m));
@@ -406,6 +392,124 @@ bool all_finite(const double *v, int cnt) {
     if (!std::isfinite(v[a])) return false;
   return true;
 }
+// One evaluation of the objective.  It owns every device buffer that RgTerms points into, and the steps' scratch, until the
+// result has come down: a step leaves pointers behind, so none of them is a step's local.
+struct RgEval {
+  Stream st;
+  const flgp_eigenpair *ep = nullptr;
+  Rows r;
+  GprCtx G;                                                     // ls = exp(-t lambda / 2) + 0.0
+  RgTerms T{};
+  const double *x = nullptr;                                    // the host's: t = x[0]; "same": noise = x[1]
+  size_t we = 0;                                                // of `work` under every V^T product
+  DevBuf dY, dx, alpha, out, ld, Vta, d, s, work;
+  DevBuf C, hw, Li, Tb, W;
+  DevBuf M, Q, R, Tq, ZV, Qinv, LsM, M1, P;
+
+  // the stream, the spectral weights, Y and x up, and what every branch fills
+  int begin(const double *Y, int nx) {
+    FLGP_TRY(st.create());
+    FLGP_TRY(G.prepare(st.s, ep, T.K, x[0]));
+    FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)T.m * T.q, st.s));
+    FLGP_TRY(upload(dx, x, sizeof(double) * (size_t)nx, st.s));
+    FLGP_TRY(alpha.alloc(sizeof(double) * (size_t)T.m * T.q)); FLGP_TRY(out.alloc(sizeof(double) * (size_t)(1 + nx)));
+    FLGP_TRY(ld.alloc(sizeof(double)));
+    if (T.grad) FLGP_TRY(Vta.alloc(sizeof(double) * (size_t)T.K * T.q));
+    if (T.grad || (T.different && !T.direct)) FLGP_TRY(d.alloc(sizeof(double) * (size_t)T.m));
+    return FLGP_OK;
+  }
+  // C = HK(idx, idx) + sigma I + (x1 I or diag(x[1..m])), factored; alpha = C^-1 Y        (:362-369, :469-477)
+  int direct_terms() {
+    const int m = T.m, q = T.q, K = T.K;
+    FLGP_TRY(hk_c11(st.s, ep, K, x[0], r, T.sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
+    FLGP_TRY(T.different ? gpr_add_diag_vec(st.s, C.as<double>(), m, dx.as<double>() + 1) : gpr_add_diag(st.s, C.as<double>(), m, x[1]));
+    FLGP_TRY(chol_blocked(st.s, C.as<double>(), m, m, G.flag.as<int>()));
+    FLGP_HIP(hipMemcpyAsync(alpha.p, dY.p, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToDevice, st.s));
+    FLGP_TRY(chol_trsv(st.s, C.as<double>(), m, m, alpha.as<double>(), m, q, 3, G.flag.as<int>()));
+    FLGP_TRY(chol_logdet(st.s, C.as<double>(), m, m, ld.as<double>()));
+    if (!T.grad) return FLGP_OK;
+    // d_i = (C^-1)_ii, s_k = |(L^-1 V)_{:,k}|^2, V^T alpha
+    const size_t wi = (size_t)32 * 64 * m;
+    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)m * m)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * m));
+    FLGP_TRY(W.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(s.alloc(sizeof(double) * (size_t)K));
+    FLGP_TRY(work.alloc(sizeof(double) * std::max(wi, we)));
+    FLGP_TRY(tri_inverse(st.s, C.as<double>(), m, m, Li.as<double>(), m, Tb.as<double>(), work.as<double>(), wi, G.flag.as<int>()));
+    FLGP_TRY(rg_colsumsq(st.s, Li.as<double>(), m, m, m, d.as<double>()));
+    FLGP_TRY(r.gather(st.s, ep, K));
+    FLGP_TRY(gemm_nn(st.s, m, K, m, Li.as<double>(), m, r.V, r.ld, W.as<double>(), nullptr, 0));
+    FLGP_TRY(rg_colsumsq(st.s, W.as<double>(), m, m, K, s.as<double>()));
+    return gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we);
+  }
+  // Woodbury (:395-405, :492-502): M = V^T V or V^T Z^-1 V, Q = Ls M Ls + (c or 1) I, alpha = Z^-1 (Y - V Ls Q^-1 Ls V^T Z^-1 Y).
+  // The factor of Q stays for the log-determinant and the gradient, so this is chol_blocked, not woodbury_step's chol_solve.
+  int woodbury_terms() {
+    const int m = T.m, q = T.q, K = T.K;
+    FLGP_TRY(r.gather(st.s, ep, K));
+    FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(Tq.alloc(sizeof(double) * (size_t)m * q));
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    const double *B = r.V;      // Z^-1 V for "different"
+    long ldb = r.ld;
+    if (T.different) {
+      FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K));
+      FLGP_TRY(gpr_zinv(st.s, dx.as<double>() + 1, T.sigma, m, d.as<double>()));                          // d = z^-1 for now
+      FLGP_TRY(gpr_rowscale_ld(st.s, r.V, r.ld, d.as<double>(), m, K, ZV.as<double>()));
+      FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));     // Z^-1 Y
+      B = ZV.as<double>(); ldb = m;
+    }
+    FLGP_TRY(gemm_tn(st.s, K, K, m, r.V, r.ld, B, ldb, M.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, T.different ? alpha.as<double>() : dY.as<double>(), m, R.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_q(st.s, M.as<double>(), G.ls.as<double>(), K, T.c, Q.as<double>()));
+    FLGP_TRY(chol_blocked(st.s, Q.as<double>(), K, K, G.flag.as<int>()));
+    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls V^T Z^-1 Y
+    FLGP_TRY(chol_trsv(st.s, Q.as<double>(), K, K, R.as<double>(), K, q, 3, G.flag.as<int>()));             // Q^-1 (.)
+    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls (.)
+    FLGP_TRY(gemm_nn(st.s, m, q, K, r.V, r.ld, R.as<double>(), K, Tq.as<double>(), nullptr, 0));             // V (.)
+    FLGP_TRY(gpr_diff(st.s, dY.as<double>(), Tq.as<double>(), T.different ? 1.0 : 1.0 / T.c, (long)m * q, alpha.as<double>()));
+    if (T.different) FLGP_TRY(gpr_rowscale_ld(st.s, alpha.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));
+    FLGP_TRY(chol_logdet(st.s, Q.as<double>(), K, K, ld.as<double>()));
+    if (!T.grad) return FLGP_OK;
+    // Q^-1 = L_Q^-T L_Q^-1, M1 = Q^-1 Ls M, V^T alpha; "different": d_i = |row i of V Ls L_Q^-T|^2
+    const size_t wi = (size_t)32 * 64 * K;
+    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+    FLGP_TRY(Qinv.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(LsM.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(M1.alloc(sizeof(double) * (size_t)K * K));
+    DevBuf wt;                 // tri_inverse's own planes: nothing points into them after this step
+    FLGP_TRY(wt.alloc(sizeof(double) * wi));
+    FLGP_TRY(tri_inverse(st.s, Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, G.flag.as<int>()));
+    FLGP_TRY(gemm_tn(st.s, K, K, K, Li.as<double>(), K, Li.as<double>(), K, Qinv.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_scale(st.s, M.as<double>(), G.ls.as<double>(), nullptr, K, K, LsM.as<double>()));
+    FLGP_TRY(gemm_nn(st.s, K, K, K, Qinv.as<double>(), K, LsM.as<double>(), K, M1.as<double>(), nullptr, 0));
+    FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we));
+    if (!T.different) return FLGP_OK;
+    // P = V (L_Q^-1 Ls)^T (m x K): B(k, j) = Li(j, k) ls_k
+    FLGP_TRY(P.alloc(sizeof(double) * (size_t)m * K));
+    FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, G.ls.as<double>(), K, K, LsM.as<double>()));     // reuse: Li Ls
+    FLGP_TRY(gemm_launch(st.s, m, K, K, 1.0, r.V, 1, r.ld, LsM.as<double>(), K, 1, 0.0, nullptr, 0, 0, P.as<double>(), 1, m,
+                         nullptr, 0, 0.0, nullptr));
+    return rg_rowsumsq(st.s, P.as<double>(), m, m, K, d.as<double>());
+  }
+  // rg_assemble on what the steps left, then [value, grad] down
+  int finish(const char *who, int nx, double *value, double *grad) {
+    T.x = dx.as<double>(); T.Y = dY.as<double>(); T.alpha = alpha.as<double>(); T.logdet = ld.as<double>();
+    T.values = (const double *)ep->values.p; T.ls = G.ls.as<double>();
+    T.Vta = Vta.as<double>(); T.d = d.as<double>(); T.s = s.as<double>();
+    T.M = M.as<double>(); T.Qinv = Qinv.as<double>(); T.M1 = M1.as<double>();
+    T.out = out.as<double>();
+    FLGP_TRY(rg_assemble(st.s, T));
+    std::vector<double> h((size_t)nx + 1);
+    FLGP_TRY(d2h(h.data(), out.p, sizeof(double) * h.size(), st.s));
+    FLGP_TRY(G.verdict(st.s, who));
+    const int cnt = T.grad ? nx + 1 : 1;
+    if (!all_finite(h.data(), cnt)) {
+      set_error("%s: the objective is not finite (the system matrix is numerically singular)", who);
+      return FLGP_ERR_NOCONV;
+    }
+    *value = h[0];
+    if (T.grad) std::memcpy(grad, h.data() + 1, sizeof(double) * (size_t)nx);
+    return FLGP_OK;
+  }
+};
 }  // namespace
 
 // negative_marginal_likelihood{,_diff_noise}_regression_cpp (src/train.cpp:351-436, 459-555) and their posterior forms
@@ -429,167 +533,95 @@ extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int
   FLGP_REQUIRE(all_finite(x, nx), "%s: x must be finite", who);
   for (int a = 1; a < nx; ++a) FLGP_REQUIRE(x[a] + sigma > 0.0, "%s: x[%d] + sigma must be positive", who, a);
   FLGP_REQUIRE(!posterior || x[0] > 0.0, "%s: t = x[0] must be positive under \"posterior\"", who);
-  Rows r;
-  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
-  const bool direct = m <= K, want_grad = grad != nullptr;
-  const double t = x[0];
-  RgTerms T{};
-  T.m = m; T.q = q; T.K = K; T.direct = direct; T.different = different; T.posterior = posterior; T.grad = want_grad;
+  RgEval E;
+  FLGP_TRY(E.r.check(ep, idx, m, who, "idx"));
+  E.ep = ep; E.x = x; E.we = vt_work_elems(K, q);
+  RgTerms &T = E.T;
+  T.m = m; T.q = q; T.K = K; T.direct = m <= K; T.different = different; T.posterior = posterior; T.grad = grad != nullptr;
   T.sigma = sigma; T.c = different ? 1.0 : x[1] + sigma;
   const double dflt[5] = {1.0, 10.0, 2.0, 0.1, 1e-3};         // PostOFDataReg (src/train.h:153-155)
   for (int a = 0; a < 5; ++a) T.prior[a] = prior ? prior[a] : dflt[a];
 
-  Stream st;
-  FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = exp(-t lambda / 2) + 0.0
-  DevBuf dY, dx, alpha, out, ld, Vta, d, s, work;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * q)); FLGP_TRY(alpha.alloc(sizeof(double) * (size_t)m * q));
-  FLGP_TRY(dx.alloc(sizeof(double) * (size_t)nx)); FLGP_TRY(out.alloc(sizeof(double) * (size_t)(1 + nx)));
-  FLGP_TRY(ld.alloc(sizeof(double)));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m * q, st.s));
-  FLGP_TRY(h2d(dx.p, x, sizeof(double) * (size_t)nx, st.s));
-  const size_t we = (size_t)128 * K * K + (size_t)64 * K * q + 1024;
-  if (want_grad) FLGP_TRY(Vta.alloc(sizeof(double) * (size_t)K * q));
-  if (want_grad || (different && !direct)) FLGP_TRY(d.alloc(sizeof(double) * (size_t)m));
-  DevBuf C, hw, Li, Tb, W, M, Q, R, Tq, ZV, Qinv, LsM, M1, P;
-  if (direct) {
-    // C = HK(idx, idx) + sigma I + (x1 I or diag(x[1..m])), factored; alpha = C^-1 Y        (:362-369, :469-477)
-    FLGP_TRY(hk_c11(st.s, ep, K, t, r, sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
-    FLGP_TRY(different ? gpr_add_diag_vec(st.s, C.as<double>(), m, dx.as<double>() + 1) : gpr_add_diag(st.s, C.as<double>(), m, x[1]));
-    FLGP_TRY(chol_blocked(st.s, C.as<double>(), m, m, G.flag.as<int>()));
-    FLGP_HIP(hipMemcpyAsync(alpha.p, dY.p, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToDevice, st.s));
-    FLGP_TRY(chol_trsv(st.s, C.as<double>(), m, m, alpha.as<double>(), m, q, 3, G.flag.as<int>()));
-    FLGP_TRY(chol_logdet(st.s, C.as<double>(), m, m, ld.as<double>()));
-    if (want_grad) {
-      // d_i = (C^-1)_ii, s_k = |(L^-1 V)_{:,k}|^2, V^T alpha
-      const size_t wi = (size_t)32 * 64 * m;
-      FLGP_TRY(Li.alloc(sizeof(double) * (size_t)m * m)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * m));
-      FLGP_TRY(W.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(s.alloc(sizeof(double) * (size_t)K));
-      FLGP_TRY(work.alloc(sizeof(double) * std::max(wi, we)));
-      FLGP_TRY(tri_inverse(st.s, C.as<double>(), m, m, Li.as<double>(), m, Tb.as<double>(), work.as<double>(), wi, G.flag.as<int>()));
-      FLGP_TRY(rg_colsumsq(st.s, Li.as<double>(), m, m, m, d.as<double>()));
-      FLGP_TRY(r.gather(st.s, ep, K));
-      FLGP_TRY(gemm_nn(st.s, m, K, m, Li.as<double>(), m, r.V, r.ld, W.as<double>(), nullptr, 0));
-      FLGP_TRY(rg_colsumsq(st.s, W.as<double>(), m, m, K, s.as<double>()));
-      FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we));
-    }
-  } else {
-    // Woodbury (:395-405, :492-502): M = V^T V or V^T Z^-1 V, Q = Ls M Ls + (c or 1) I, alpha = Z^-1 (Y - V Ls Q^-1 Ls V^T Z^-1 Y)
-    FLGP_TRY(r.gather(st.s, ep, K));
-    FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(Tq.alloc(sizeof(double) * (size_t)m * q));
-    FLGP_TRY(work.alloc(sizeof(double) * we));
-    const double *B = r.V;      // Z^-1 V for "different"
-    long ldb = r.ld;
-    if (different) {
-      FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K));
-      FLGP_TRY(gpr_zinv(st.s, dx.as<double>() + 1, sigma, m, d.as<double>()));                          // d = z^-1 for now
-      FLGP_TRY(gpr_rowscale_ld(st.s, r.V, r.ld, d.as<double>(), m, K, ZV.as<double>()));
-      FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));     // Z^-1 Y
-      B = ZV.as<double>(); ldb = m;
-    }
-    FLGP_TRY(gemm_tn(st.s, K, K, m, r.V, r.ld, B, ldb, M.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, different ? alpha.as<double>() : dY.as<double>(), m, R.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_q(st.s, M.as<double>(), G.ls.as<double>(), K, T.c, Q.as<double>()));
-    FLGP_TRY(chol_blocked(st.s, Q.as<double>(), K, K, G.flag.as<int>()));
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls V^T Z^-1 Y
-    FLGP_TRY(chol_trsv(st.s, Q.as<double>(), K, K, R.as<double>(), K, q, 3, G.flag.as<int>()));             // Q^-1 (.)
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls (.)
-    FLGP_TRY(gemm_nn(st.s, m, q, K, r.V, r.ld, R.as<double>(), K, Tq.as<double>(), nullptr, 0));             // V (.)
-    FLGP_TRY(gpr_diff(st.s, dY.as<double>(), Tq.as<double>(), different ? 1.0 : 1.0 / T.c, (long)m * q, alpha.as<double>()));
-    if (different) FLGP_TRY(gpr_rowscale_ld(st.s, alpha.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));
-    FLGP_TRY(chol_logdet(st.s, Q.as<double>(), K, K, ld.as<double>()));
-    if (want_grad) {
-      // Q^-1 = L_Q^-T L_Q^-1, M1 = Q^-1 Ls M, V^T alpha; "different": d_i = |row i of V Ls L_Q^-T|^2
-      const size_t wi = (size_t)32 * 64 * K;
-      FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
-      FLGP_TRY(Qinv.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(LsM.alloc(sizeof(double) * (size_t)K * K));
-      FLGP_TRY(M1.alloc(sizeof(double) * (size_t)K * K));
-      DevBuf wt;
-      FLGP_TRY(wt.alloc(sizeof(double) * wi));
-      FLGP_TRY(tri_inverse(st.s, Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, G.flag.as<int>()));
-      FLGP_TRY(gemm_tn(st.s, K, K, K, Li.as<double>(), K, Li.as<double>(), K, Qinv.as<double>(), work.as<double>(), we));
-      FLGP_TRY(gpr_scale(st.s, M.as<double>(), G.ls.as<double>(), nullptr, K, K, LsM.as<double>()));
-      FLGP_TRY(gemm_nn(st.s, K, K, K, Qinv.as<double>(), K, LsM.as<double>(), K, M1.as<double>(), nullptr, 0));
-      FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we));
-      if (different) {
-        // P = V (L_Q^-1 Ls)^T (m x K): B(k, j) = Li(j, k) ls_k
-        FLGP_TRY(P.alloc(sizeof(double) * (size_t)m * K));
-        FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, G.ls.as<double>(), K, K, LsM.as<double>()));     // reuse: Li Ls
-        FLGP_TRY(gemm_launch(st.s, m, K, K, 1.0, r.V, 1, r.ld, LsM.as<double>(), K, 1, 0.0, nullptr, 0, 0, P.as<double>(), 1, m,
-                             nullptr, 0, 0.0, nullptr));
-        FLGP_TRY(rg_rowsumsq(st.s, P.as<double>(), m, m, K, d.as<double>()));
-      }
-    }
-  }
-  T.x = dx.as<double>(); T.Y = dY.as<double>(); T.alpha = alpha.as<double>(); T.logdet = ld.as<double>();
-  T.values = (const double *)ep->values.p; T.ls = G.ls.as<double>();
-  T.Vta = Vta.as<double>(); T.d = d.as<double>(); T.s = s.as<double>();
-  T.M = M.as<double>(); T.Qinv = Qinv.as<double>(); T.M1 = M1.as<double>();
-  T.out = out.as<double>();
-  FLGP_TRY(rg_assemble(st.s, T));
-  std::vector<double> h((size_t)nx + 1);
-  FLGP_TRY(d2h(h.data(), out.p, sizeof(double) * h.size(), st.s));
-  FLGP_TRY(G.verdict(st.s, who));
-  const int cnt = want_grad ? nx + 1 : 1;
-  if (!all_finite(h.data(), cnt)) {
-    set_error("%s: the objective is not finite (the system matrix is numerically singular)", who);
-    return FLGP_ERR_NOCONV;
-  }
-  *value = h[0];
-  if (want_grad) std::memcpy(grad, h.data() + 1, sizeof(double) * (size_t)nx);
-  return FLGP_OK;
+  FLGP_TRY(E.begin(Y, nx));
+  FLGP_TRY(T.direct ? E.direct_terms() : E.woodbury_terms());
+  return E.finish(who, nx, value, grad);
 }
 
 // ---- logit training objective: what train_lae_logit_gp_cpp's COBYLA minimises, on the resident pair ------
 namespace {
-// Alg. 3.1 for m > K on C = V1 L V1^T + sigma I (L = exp(-t (1 - values))), O(m K^2) per iteration, never an m x m matrix.
-// With D = 1 + sigma W, B = sW C sW + I = D + U L U^T (U = sW V1), so with X = D^-1/2 U L^1/2 (m x K) and Q = I + X^T X:
+// The low-rank pieces of C = V1 L V1^T + sigma I (V1 m x K at ld1, L = exp(-t (1 - values)), ls = L^1/2) that the logit
+// loop below and the Polya-Gamma sweep share.  With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with
+// X = diag(xs) V1 L^1/2 (xs = D^-1/2 sW) and Q = I + X^T X (K x K):
 //   B^-1 y = D^-1 y - D^-1/2 X Q^-1 X^T D^-1/2 y,   det B = det D det Q.
-// Per iteration: sW, b from f; D, X, Q factored (K x K); c = C b; r = B^-1 (sW c); a = b - sW r; f_new = C a.  As in
-// GpcNewton, a, D and L_Q stay those of the LAST iteration and f is the final mode; everything is fixed-order.
-struct GpcLowRank {
+// The callers' elementwise kernels make xs and use the result; the sigma x term of C x is theirs too.
+struct LowRankB {
   int m = 0, K = 0;
-  double sigma = 0.0;
-  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;    // V1 (m x K at ld1), L, L^1/2
+  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;
   long ld1 = 0;
-  DevBuf f, fnew, sW, b, a, D, dh, xs, c, g, Xv, X, Q, u, scal, flag, work;
+  double sigma = 0.0;          // C's: the callers' kernels use it, nothing below does
+  int *flag = nullptr;
+  DevBuf X, Q, u, work;        // Q holds its factor L_Q after factor(); u (K) and work (we) are scratch
   size_t we = 0;
 
-  int alloc(int m_, int K_) {
-    m = m_; K = K_;
+  int alloc(int m_, int K_, bool factored, int *flag_) {     // !factored: cmul only (no X, no Q)
+    m = m_; K = K_; flag = flag_;
+    we = vt_work_elems(K, 1);
+    FLGP_TRY(u.alloc(sizeof(double) * (size_t)std::max(K, 1))); FLGP_TRY(work.alloc(sizeof(double) * we));
+    if (!factored) return FLGP_OK;
+    FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
+    return Q.alloc(sizeof(double) * (size_t)K * K);
+  }
+  // X = diag(xs) V1 L^1/2, Q = I + X^T X = L_Q L_Q^T
+  int factor(hipStream_t st, const double *xs) {
+    FLGP_TRY(gpc_scale2(st, V1, ld1, xs, ls, m, K, X.as<double>()));
+    FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, Q.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_add_diag(st, Q.as<double>(), K, 1.0));
+    return chol_blocked(st, Q.as<double>(), K, K, flag);
+  }
+  // Xv = X Q^-1 X^T g with the factor of the last factor()
+  int apply(hipStream_t st, const double *g, double *Xv) {
+    FLGP_TRY(gemm_tn(st, K, 1, m, X.as<double>(), m, g, m, u.as<double>(), work.as<double>(), we));
+    FLGP_TRY(chol_trsv(st, Q.as<double>(), K, K, u.as<double>(), K, 1, 3, flag));
+    return gemm_nn(st, m, 1, K, X.as<double>(), m, u.as<double>(), K, Xv, nullptr, 0);
+  }
+  // out = Vl L V1^T x for any Vl (rows x K at ldl): V1 itself in C x, the new rows' V2 in a predicted mean
+  int cmul(hipStream_t st, const double *Vl, long ldl, int rows, const double *x, double *out) {
+    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, x, m, u.as<double>(), work.as<double>(), we));
+    FLGP_TRY(pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>()));
+    return gemm_nn(st, rows, 1, K, Vl, ldl, u.as<double>(), K, out, nullptr, 0);
+  }
+};
+
+// Alg. 3.1 for m > K on LowRankB's C, O(m K^2) per iteration, never an m x m matrix.  Per iteration: sW, b from f; D, X, Q
+// factored (K x K); c = C b; r = B^-1 (sW c); a = b - sW r; f_new = C a.  As in GpcNewton, a, D and L_Q stay those of the
+// LAST iteration and f is the final mode; everything is fixed-order.
+struct GpcLowRank {
+  int m = 0;
+  LowRankB L;                  // the caller sets V1, ld1, l, ls, sigma
+  DevBuf f, fnew, sW, b, a, D, dh, xs, c, g, Xv, scal, flag;
+
+  int alloc(int m_, int K) {
+    m = m_;
     const size_t v = sizeof(double) * (size_t)m;
     FLGP_TRY(f.alloc(v)); FLGP_TRY(fnew.alloc(v)); FLGP_TRY(sW.alloc(v)); FLGP_TRY(b.alloc(v)); FLGP_TRY(a.alloc(v));
     FLGP_TRY(D.alloc(v)); FLGP_TRY(dh.alloc(v)); FLGP_TRY(xs.alloc(v)); FLGP_TRY(c.alloc(v)); FLGP_TRY(g.alloc(v));
     FLGP_TRY(Xv.alloc(v));
-    FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(u.alloc(sizeof(double) * (size_t)K));
-    we = (size_t)128 * K * K + (size_t)64 * K + 1024;
-    FLGP_TRY(work.alloc(sizeof(double) * we));
     FLGP_TRY(scal.alloc(sizeof(double) * 2)); FLGP_TRY(flag.alloc(sizeof(int)));
-    return FLGP_OK;
+    return L.alloc(m, K, true, flag.as<int>());
   }
-  // out = V1 (L (V1^T x)) + sigma x   (Xv is the scratch)
+  // out = C x   (Xv is the scratch)
   int cmul(hipStream_t st, const double *x, double *out) {
-    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, x, m, u.as<double>(), work.as<double>(), we));
-    FLGP_TRY(pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>()));
-    FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, Xv.as<double>(), nullptr, 0));
-    return pg_axpy3(st, m, Xv.as<double>(), nullptr, sigma, x, out);
+    FLGP_TRY(L.cmul(st, L.V1, L.ld1, m, x, Xv.as<double>()));
+    return pg_axpy3(st, m, Xv.as<double>(), nullptr, L.sigma, x, out);
   }
   int iteration(hipStream_t st, const double *dY, const double *dN) {
     ProfScope ps("logit_lr_newton_iter", st, 0.0);
     FLGP_TRY(gpc_weights(st, f.as<double>(), dY, dN, m, sW.as<double>(), b.as<double>()));
-    FLGP_TRY(gpc_lr_dvec(st, sW.as<double>(), sigma, m, D.as<double>(), dh.as<double>(), xs.as<double>()));
-    FLGP_TRY(gpc_scale2(st, V1, ld1, xs.as<double>(), ls, m, K, X.as<double>()));                                // X
-    FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, Q.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_add_diag(st, Q.as<double>(), K, 1.0));
-    FLGP_TRY(chol_blocked(st, Q.as<double>(), K, K, flag.as<int>()));                                             // Q = L_Q L_Q^T
+    FLGP_TRY(gpc_lr_dvec(st, sW.as<double>(), L.sigma, m, D.as<double>(), dh.as<double>(), xs.as<double>()));
+    FLGP_TRY(L.factor(st, xs.as<double>()));
     FLGP_TRY(cmul(st, b.as<double>(), c.as<double>()));                                                           // c = C b
     FLGP_TRY(pg_mul(st, m, xs.as<double>(), c.as<double>(), nullptr, g.as<double>()));                           // g = D^-1/2 sW c
-    FLGP_TRY(gemm_tn(st, K, 1, m, X.as<double>(), m, g.as<double>(), m, u.as<double>(), work.as<double>(), we));  // X^T g
-    FLGP_TRY(chol_trsv(st, Q.as<double>(), K, K, u.as<double>(), K, 1, 3, flag.as<int>()));                        // Q^-1 (.)
-    FLGP_TRY(gemm_nn(st, m, 1, K, X.as<double>(), m, u.as<double>(), K, Xv.as<double>(), nullptr, 0));           // X (.)
+    FLGP_TRY(L.apply(st, g.as<double>(), Xv.as<double>()));
     FLGP_TRY(gpc_lr_a(st, b.as<double>(), sW.as<double>(), dh.as<double>(), g.as<double>(), Xv.as<double>(), m, a.as<double>()));
     FLGP_TRY(cmul(st, a.as<double>(), fnew.as<double>()));                                                        // f_new = C a
     return gpc_step(st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
@@ -610,7 +642,7 @@ struct GpcLowRank {
       FLGP_TRY(GpcNewton::pivot_error(bad, who, it + 1));
       if (diff < tol) break;
     }
-    FLGP_TRY(gpc_lr_amll(st, f.as<double>(), a.as<double>(), dY, dN, D.as<double>(), Q.as<double>(), K, m, scal.as<double>() + 1));
+    FLGP_TRY(gpc_lr_amll(st, f.as<double>(), a.as<double>(), dY, dN, D.as<double>(), L.Q.as<double>(), L.K, m, scal.as<double>() + 1));
     FLGP_HIP(hipMemcpyAsync(amll, scal.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, st));
     FLGP_HIP(hipStreamSynchronize(st));
     return FLGP_OK;
@@ -660,11 +692,10 @@ extern "C" int flgp_eigenpair_logit_objective(const flgp_eigenpair *ep, int K, c
     FLGP_TRY(G.prepare(st.s, ep, K, t));                        // ls = L^1/2, l = L
     FLGP_TRY(r.gather(st.s, ep, K));
     DevBuf dY, dN;
-    FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(dN.alloc(sizeof(double) * (size_t)m));
-    FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
-    FLGP_TRY(h2d(dN.p, N, sizeof(double) * (size_t)m, st.s));
+    FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
+    FLGP_TRY(upload(dN, N, sizeof(double) * (size_t)m, st.s));
     GpcLowRank S;
-    S.sigma = sigma; S.V1 = r.V; S.ld1 = r.ld; S.l = G.l.as<double>(); S.ls = G.ls.as<double>();
+    S.L.sigma = sigma; S.L.V1 = r.V; S.L.ld1 = r.ld; S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
     FLGP_TRY(S.alloc(m, K));
     FLGP_TRY(S.run(st.s, dY.as<double>(), dN.as<double>(), tol, max_iter, who, &it, &amll));
   }
@@ -684,32 +715,27 @@ namespace {
 // resamples f in Matheron's form, with the law of _resample_f (:25-39) and one solve against B = sW C sW + I:
 //   f0 = V1 L^1/2 z1 + sqrt(sigma) z2 (dense: L_C z2), r = kappa / sW - sW f0 - z3, f = f0 + C (sW B^-1 r),
 // then omega ~ PG(1, f).  B^-1: route DENSE / DIRECT factor the m x m B; WOODBURY (m > K) writes B = D + U L U^T with
-// D = 1 + sigma omega, U = sW V1 and factors the K x K Q = I + X^T X, X = D^-1/2 U L^1/2:
+// D = 1 + sigma omega, U = sW V1 and factors the K x K Q = I + X^T X, X = D^-1/2 U L^1/2 (LowRankB):
 //   sW B^-1 r = sW D^-1/2 (g - X Q^-1 X^T g),  g = D^-1/2 r.
-// C x = V1 (L (V1^T x)) + sigma x in both eigen routes; C is formed only to build B in DIRECT.
+// C x = V1 (L (V1^T x)) + sigma x in both eigen routes; C is formed only to build B in DIRECT.  The routes split along two
+// lines, the solve (m x m in DENSE and DIRECT) and C x (dense only in DENSE), so they stay branches, not two solver objects.
 enum PgRoute { PG_DENSE, PG_DIRECT, PG_WOODBURY };
 struct PgChain {
   PgRoute route = PG_DENSE;
-  int m = 0, K = 0;
-  double sigma = 0.0;
-  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;   // eigen routes: V1 (m x K at ld1), L, L^1/2
-  long ld1 = 0;
+  int m = 0;
+  LowRankB L;                                                // eigen routes: the caller sets V1, ld1, l, ls, sigma
   const double *C = nullptr, *LC = nullptr;                  // DENSE / DIRECT: C (m x m); DENSE: its factor
   int *flag = nullptr;
-  DevBuf kappa, omega, f, f0, r, sw, z, x, t1, t2, B, X, dh, a, u, work;
-  size_t we = 0;
+  DevBuf kappa, omega, f, f0, r, sw, z, x, t1, t2, B, dh, a;
 
-  int alloc(int m_, int K_) {
-    m = m_; K = K_;
+  int alloc(int m_, int K) {
+    m = m_;
     const size_t v = sizeof(double) * (size_t)m;
     FLGP_TRY(kappa.alloc(v)); FLGP_TRY(omega.alloc(v)); FLGP_TRY(f.alloc(v)); FLGP_TRY(f0.alloc(v)); FLGP_TRY(r.alloc(v));
     FLGP_TRY(sw.alloc(v)); FLGP_TRY(x.alloc(v)); FLGP_TRY(t1.alloc(v)); FLGP_TRY(t2.alloc(v));
     FLGP_TRY(z.alloc(sizeof(double) * ((size_t)2 * m + K)));
-    FLGP_TRY(u.alloc(sizeof(double) * (size_t)std::max(K, 1)));
-    we = (size_t)128 * K * K + (size_t)64 * K + 1024;
-    FLGP_TRY(work.alloc(sizeof(double) * we));
+    FLGP_TRY(L.alloc(m, K, route == PG_WOODBURY, flag));
     if (route == PG_WOODBURY) {
-      FLGP_TRY(B.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
       FLGP_TRY(dh.alloc(v)); FLGP_TRY(a.alloc(v));
     } else {
       FLGP_TRY(B.alloc(sizeof(double) * (size_t)m * m));
@@ -723,11 +749,8 @@ struct PgChain {
       FLGP_TRY(gpc_bmat(st, C, sw.as<double>(), m, B.as<double>()));
       return chol_blocked(st, B.as<double>(), m, m, flag);
     }
-    FLGP_TRY(pg_dvec(st, m, omega.as<double>(), sigma, sw.as<double>(), dh.as<double>(), a.as<double>()));
-    FLGP_TRY(gpc_scale2(st, V1, ld1, a.as<double>(), ls, m, K, X.as<double>()));
-    FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, B.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_add_diag(st, B.as<double>(), K, 1.0));
-    return chol_blocked(st, B.as<double>(), K, K, flag);
+    FLGP_TRY(pg_dvec(st, m, omega.as<double>(), L.sigma, sw.as<double>(), dh.as<double>(), a.as<double>()));
+    return L.factor(st, a.as<double>());
   }
   // out = sW .* B^-1 rin with the factor of the last factor()
   int solve(hipStream_t st, const double *rin, double *out) {
@@ -737,9 +760,7 @@ struct PgChain {
       return pg_mul(st, m, sw.as<double>(), t1.as<double>(), nullptr, out);
     }
     FLGP_TRY(pg_mul(st, m, dh.as<double>(), rin, nullptr, t1.as<double>()));                                       // g
-    FLGP_TRY(gemm_tn(st, K, 1, m, X.as<double>(), m, t1.as<double>(), m, u.as<double>(), work.as<double>(), we));   // X^T g
-    FLGP_TRY(chol_trsv(st, B.as<double>(), K, K, u.as<double>(), K, 1, 3, flag));                                  // Q^-1 (.)
-    FLGP_TRY(gemm_nn(st, m, 1, K, X.as<double>(), m, u.as<double>(), K, t2.as<double>(), nullptr, 0));             // X (.)
+    FLGP_TRY(L.apply(st, t1.as<double>(), t2.as<double>()));
     return pg_wb_out(st, m, sw.as<double>(), dh.as<double>(), t1.as<double>(), t2.as<double>(), out);
   }
   // out = add + C xin (add may be nullptr)
@@ -748,14 +769,12 @@ struct PgChain {
       FLGP_TRY(gpc_gemv(st, C, m, xin, nullptr, t2.as<double>()));
       return pg_axpy3(st, m, add, t2.as<double>(), 0.0, nullptr, out);
     }
-    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, xin, m, u.as<double>(), work.as<double>(), we));
-    FLGP_TRY(pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>()));
-    FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, t2.as<double>(), nullptr, 0));
-    return pg_axpy3(st, m, add, t2.as<double>(), sigma, xin, out);
+    FLGP_TRY(L.cmul(st, L.V1, L.ld1, m, xin, t2.as<double>()));
+    return pg_axpy3(st, m, add, t2.as<double>(), L.sigma, xin, out);
   }
   int run(hipStream_t st, const double *dY, int n_sample, unsigned long long seed) {
     FLGP_TRY(pg_init(st, m, dY, kappa.as<double>(), omega.as<double>(), f.as<double>()));
-    const int kz = route == PG_DENSE ? 0 : K;
+    const int kz = route == PG_DENSE ? 0 : L.K;
     double *z1 = z.as<double>(), *z2 = z1 + kz, *z3 = z2 + m;
     for (int s = 0; s < n_sample; ++s) {
       ProfScope ps("pg_sweep", st, 0.0);
@@ -763,10 +782,10 @@ struct PgChain {
       if (route == PG_DENSE) {
         FLGP_TRY(pg_trmv(st, LC, m, m, z2, t2.as<double>(), flag));                                         // L_C z2
       } else {
-        FLGP_TRY(pg_mul(st, K, ls, z1, nullptr, u.as<double>()));
-        FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, t2.as<double>(), nullptr, 0));            // V1 L^1/2 z1
+        FLGP_TRY(pg_mul(st, L.K, L.ls, z1, nullptr, L.u.as<double>()));
+        FLGP_TRY(gemm_nn(st, m, 1, L.K, L.V1, L.ld1, L.u.as<double>(), L.K, t2.as<double>(), nullptr, 0));  // V1 L^1/2 z1
       }
-      FLGP_TRY(pg_f0r(st, m, t2.as<double>(), z2, route == PG_DENSE ? 0.0 : std::sqrt(sigma), z3, kappa.as<double>(),
+      FLGP_TRY(pg_f0r(st, m, t2.as<double>(), z2, route == PG_DENSE ? 0.0 : std::sqrt(L.sigma), z3, kappa.as<double>(),
                       omega.as<double>(), f0.as<double>(), r.as<double>(), sw.as<double>()));
       FLGP_TRY(factor(st));
       FLGP_TRY(solve(st, r.as<double>(), x.as<double>()));
@@ -801,10 +820,8 @@ struct PgMatch {
       for (; lo != pos.end() && lo->first == idx1[i]; ++lo) hl.push_back(lo->second);
       hp[(size_t)i + 1] = (long)hl.size();
     }
-    FLGP_TRY(ptr.alloc(sizeof(long) * hp.size()));
-    FLGP_TRY(list.alloc(sizeof(int) * std::max<size_t>(hl.size(), 1)));
-    FLGP_TRY(h2d(ptr.p, hp.data(), sizeof(long) * hp.size(), st));
-    FLGP_TRY(h2d(list.p, hl.data(), sizeof(int) * hl.size(), st));
+    FLGP_TRY(upload(ptr, hp.data(), sizeof(long) * hp.size(), st));
+    FLGP_TRY(upload(list, hl.data(), sizeof(int) * hl.size(), st));          // an empty list still gets a buffer
     FLGP_HIP(hipStreamSynchronize(st));      // the host vectors go out of scope
     return FLGP_OK;
   }
@@ -842,16 +859,14 @@ int pg_eigen_binary(hipStream_t st, const flgp_eigenpair *ep, int K, double t, d
     FLGP_TRY(hk_c11(st, ep, K, t, r0, sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
     P.C = C.as<double>();
   }
-  P.sigma = sigma; P.V1 = r0.V; P.ld1 = r0.ld; P.l = G.l.as<double>(); P.ls = G.ls.as<double>(); P.flag = flag.as<int>();
+  P.L.sigma = sigma; P.L.V1 = r0.V; P.L.ld1 = r0.ld; P.L.l = G.l.as<double>(); P.L.ls = G.ls.as<double>(); P.flag = flag.as<int>();
   FLGP_TRY(P.alloc(m, K));
   FLGP_TRY(P.run(st, dY, n_sample, seed));
   FLGP_TRY(P.collapsed_w(st));
   // mean = V2 L V1^T w, then pi = logistic(mean + sigma_nv sum_{idx0_j = idx1_i} w_j)
   DevBuf mean;
   FLGP_TRY(mean.alloc(sizeof(double) * (size_t)mnew));
-  FLGP_TRY(gemm_tn(st, K, 1, m, r0.V, r0.ld, P.x.as<double>(), m, P.u.as<double>(), P.work.as<double>(), P.we));
-  FLGP_TRY(pg_mul(st, K, P.l, P.u.as<double>(), nullptr, P.u.as<double>()));
-  FLGP_TRY(gemm_nn(st, mnew, 1, K, r1.V, r1.ld, P.u.as<double>(), K, mean.as<double>(), nullptr, 0));
+  FLGP_TRY(P.L.cmul(st, r1.V, r1.ld, mnew, P.x.as<double>(), mean.as<double>()));
   FLGP_TRY(pg_pi(st, mnew, mean.as<double>(), sigma_nv, match ? match->ptr.as<long>() : nullptr,
                  match ? match->list.as<int>() : nullptr, P.x.as<double>(), d_pi, ld_pi, d_y));
   FLGP_HIP(hipStreamSynchronize(st));         // the chain's buffers are given back to the cache on the way out
@@ -870,10 +885,9 @@ extern "C" int flgp_pg_draw(const double *b, const double *c, int n, unsigned lo
   Stream st;
   FLGP_TRY(st.create());
   DevBuf db, dc, out;
-  if (b) FLGP_TRY(db.alloc(sizeof(double) * (size_t)n));
-  FLGP_TRY(dc.alloc(sizeof(double) * (size_t)n)); FLGP_TRY(out.alloc(sizeof(double) * (size_t)n));
-  if (b) FLGP_TRY(h2d(db.p, b, sizeof(double) * (size_t)n, st.s));
-  FLGP_TRY(h2d(dc.p, c, sizeof(double) * (size_t)n, st.s));
+  FLGP_TRY(out.alloc(sizeof(double) * (size_t)n));
+  if (b) FLGP_TRY(upload(db, b, sizeof(double) * (size_t)n, st.s));
+  FLGP_TRY(upload(dc, c, sizeof(double) * (size_t)n, st.s));
   FLGP_TRY(pg_draw_launch(st.s, b ? db.as<double>() : nullptr, dc.as<double>(), n, pg_stream_base(seed, 3), out.as<double>()));
   FLGP_TRY(d2h(omega, out.p, sizeof(double) * (size_t)n, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));
