@@ -69,6 +69,7 @@ _SIGNATURES = {
                                           ctypes.c_ulonglong, P, P, P, P]),
     "flgp_eigenpair_pg_predict_multiclass": (c_int, [P, c_int, P, c_int, c_double, P, c_int, P, P, c_int, c_int,
                                                      ctypes.c_ulonglong, P, P]),
+    "flgp_negative_log_likelihood": (c_int, [P, P, P, c_long, c_int, c_char_p, c_int, ctypes.c_ulonglong, P, P]),
     "flgp_eigenpair_free": (None, [P]),
     "flgp_kmeans_minibatch": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, ctypes.c_ulonglong, P, P, P]),
     "flgp_kmeans_lloyd": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
@@ -92,6 +93,10 @@ _SIGNATURES = {
     "flgp_dev_v_to_z": (c_int, [P, P, c_int, P]),
     "flgp_dev_se_weights_den": (c_int, [P, P, P, c_int, c_int, c_int, c_double, P, P]),
     "flgp_dev_mean": (c_int, [P, P, c_long, P, P]),
+    "flgp_dev_nll_workspace": (c_size_t, [c_long, c_int]),
+    "flgp_dev_nll_classification": (c_int, [P, P, P, P, c_long, c_int, c_int, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong,
+                                            P, P, P]),
+    "flgp_dev_nll_regression": (c_int, [P, P, P, P, c_long, P, P, P]),
     "flgp_dev_se_weights": (c_int, [P, P, P, c_int, c_int, c_int, c_double, P, P]),
     "flgp_dev_csc_workspace": (c_size_t, [c_int, c_int, c_int]),
     "flgp_dev_csc_build": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_size_t]),

@@ -250,6 +250,37 @@ def _pg_logit_predict_state(C, Y, Cnv, N_sample, seed):
     return pi, y, om, f
 
 
+def negative_log_likelihood(mean, cov, target, type, n_samples=100, seed=None, return_like=False):
+    """negative_log_likelihood (src/Utils.cpp:302-318), on the device: the score of a ``posterior`` list.  ``type`` is
+    "regression", "binary" (``nll_classification``) or "multinomial" (``target`` holds class labels 0 .. J-1, ``mean`` and
+    ``cov`` are n x J).  The classification types average the logistic likelihood over ``n_samples`` normals per row (the
+    reference fixes 100), reproducible from ``seed`` (nll.hip documents the layout).  ``return_like``: also the per-row
+    likelihoods (n, or n x J), for "regression" the per-row terms."""
+    target = np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1))
+    n = target.size
+    mean = np.asarray(mean, dtype=np.float64); cov = np.asarray(cov, dtype=np.float64)
+    if type == "multinomial":
+        if mean.ndim != 2 or mean.shape[0] != n or cov.shape != mean.shape:
+            raise ValueError("mean and cov must be n x J matrices with one row per entry of target")
+        mean = np.asfortranarray(mean); cov = np.asfortranarray(cov)
+        J = mean.shape[1]
+    else:
+        if mean.size != n or cov.size != n:
+            raise ValueError("mean and cov must be vectors with one entry per entry of target")
+        mean = np.ascontiguousarray(mean.reshape(-1)); cov = np.ascontiguousarray(cov.reshape(-1))
+        J = 1
+    nll = ctypes.c_double()
+    like = np.zeros(mean.shape, order="F") if return_like else None
+    check(_lib.lib().flgp_negative_log_likelihood(_ptr(mean), _ptr(cov), _ptr(target), n, J, _b(type), int(n_samples), _seed(seed),
+                                                  ctypes.byref(nll), _ptr(like)))
+    return (nll.value, like) if return_like else nll.value
+
+
+def nll_classification(mean, cov, target, n_samples=100, seed=None, return_like=False):
+    """nll_classification (src/Utils.cpp:321-336; default src/Utils.h): the "binary" route of negative_log_likelihood."""
+    return negative_log_likelihood(mean, cov, target, "binary", n_samples, seed, return_like)
+
+
 class ResidentEigenPair:
     """An ``EigenPair`` that stays in HBM (include/flgp_hip.h, "device-resident EigenPair"): what the training
     loop needs, since it calls ``HK_from_spectrum_cpp`` with the same pair and a new ``t`` on every objective

@@ -5,10 +5,11 @@
 // per entry.  X ~ J*(1, z) with z = |c| / 2 and truncation point t = 0.64, returned as X / 4; PG(b, c) for an integer b is
 // the sum of b such draws, in order.
 //
-// Random numbers.  The construction of flgp_amd/synth.py, unchanged, so that numpy can regenerate every number the device
-// consumes: stream st under seed has the base splitmix64(seed * 0x100000001B3 + st); its counter q gives the uniform
-// ((splitmix64(base + q) >> 11) + 0.5) 2^-53; normal i of a stream is Box-Muller on the uniforms 2i, 2i + 1,
-// sqrt(-2 log u_2i) cos(2 pi u_2i+1); an exponential is -log u.  Nothing depends on the launch geometry.
+// Random numbers.  The construction of flgp_amd/synth.py, unchanged (rng.h, shared with nll.hip), so that numpy can
+// regenerate every number the device consumes: stream st under seed has the base splitmix64(seed * 0x100000001B3 + st);
+// its counter q gives the uniform ((splitmix64(base + q) >> 11) + 0.5) 2^-53; normal i of a stream is Box-Muller on the
+// uniforms 2i, 2i + 1, sqrt(-2 log u_2i) cos(2 pi u_2i+1); an exponential is -log u.  Nothing depends on the launch
+// geometry.
 //
 // Layout of one chain (flgp_eigenpair_pg_predict, flgp_pg_logit_predict), sweep s = 0 .. n_sample - 1:
 //   stream 4s     normal k (k < K): z1 of f0 = V1 L^1/2 z1 + sqrt(sigma) z2 (unused by the dense entry);
@@ -31,23 +32,11 @@
 // non-finite argument) returns NaN, so a diverging chain cannot hang the device; the pivot flag of the next
 // factorisation reports it.
 #include "common.h"
+#include "rng.h"
 
 namespace flgp {
 
 namespace {
-__host__ __device__ inline unsigned long long pg_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ double pg_unif(unsigned long long base, unsigned long long q) {
-  return ((double)(pg_mix(base + q) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-}
-__device__ __forceinline__ double pg_box_muller(double u1, double u2) {
-  return sqrt(-2.0 * log(u1)) * cos(2.0 * M_PI * u2);
-}
-
 constexpr double PG_T = 0.64;
 
 // log Phi(x), without the underflow of Phi for x << 0
@@ -64,7 +53,7 @@ __device__ __forceinline__ double pg_a(int n, double x) {
 
 struct PgCtr {
   unsigned long long base, q;
-  __device__ double next() { return pg_unif(base, q++); }
+  __device__ double next() { return rng_unif(base, q++); }
 };
 
 // X ~ J*(1, z), z >= 0
@@ -97,7 +86,7 @@ __device__ double jstar_draw(double z, PgCtr &r) {
     } else {
       do {
         const double u1 = r.next(), u2 = r.next();
-        const double nr = pg_box_muller(u1, u2);
+        const double nr = rng_box_muller(u1, u2);
         const double a = mu * (nr * nr);
         X = mu / (1.0 + 0.5 * a + 0.5 * sqrt(a * a + 4.0 * a));
         if (r.next() > mu / (mu + X)) X = mu * mu / X;
@@ -122,7 +111,7 @@ __device__ double jstar_draw(double z, PgCtr &r) {
 }  // namespace
 
 unsigned long long pg_stream_base(unsigned long long seed, unsigned long long stream) {
-  return pg_mix(seed * 0x100000001B3ull + stream);
+  return rng_stream_base(seed, stream);
 }
 
 // out[i] = PG(b_i, c_i) (b == nullptr: b_i = 1) on the stream with base `base`, entry i at counter i 2^32
@@ -155,7 +144,7 @@ __global__ void pg_normals_kernel(unsigned long long b0, unsigned long long b1, 
   else if (e < K + m) { base = b1; i = e - K; }
   else { base = b2; i = e - K - m; }
   const unsigned long long q = 2ull * (unsigned long long)i;
-  out[e] = pg_box_muller(pg_unif(base, q), pg_unif(base, q + 1));
+  out[e] = rng_box_muller(rng_unif(base, q), rng_unif(base, q + 1));
 }
 
 int pg_normals(hipStream_t st, unsigned long long seed, int sweep, int K, int m, double *d_out) {
