@@ -4,8 +4,6 @@
 #include "common.h"
 #include <chrono>
 #include <memory>
-#include <condition_variable>
-#include <mutex>
 #include <cstring>
 #include <cmath>
 #include <string>
@@ -13,16 +11,6 @@
 #include <vector>
 
 using namespace flgp;
-
-extern "C" int flgp_dev_anchor_rows(int s);
-extern "C" int flgp_dev_v_to_z(void *stream, const double *d_v, int r, double *d_z);
-extern "C" size_t flgp_dev_hk_workspace(int n0, int n1, int K, int gather0);
-extern "C" int flgp_dev_mean(void *stream, const double *d_x, long count, double *d_out, double *d_work);
-extern "C" int flgp_dev_col_scale_row_normalize(void *stream, const int *d_ell_idx, double *d_ell_val, int n, int r,
-                                                const double *d_colsum, const double *d_num_class);
-extern "C" int flgp_dev_se_weights_den(void *stream, const int *d_knn_idx, const double *d_knn_dist, int n, int ldk,
-                                       int r, double den, int *d_ell_idx, double *d_ell_val);
-
 
 // u = A v / sigma (flgp_dev_u_recover) needs sigma > 0 for every wanted pair.  K == s on a rank-deficient A, an anchor no
 // point chose, an SE bandwidth that underflows a column: the Gram route cannot deliver those left vectors (the
@@ -128,21 +116,31 @@ struct Sim {
   ~Sim() { if (csc_ev) { (void)hipEventSynchronize(csc_ev); (void)hipEventDestroy(csc_ev); } }
 };
 
-int upload_points(Sim &S, hipStream_t st, const double *X, int n, int d, const double *U, int s, int ucols,
-                  bool need_sizes) {
-  FLGP_REQUIRE(X && U, "null pointer");
-  FLGP_REQUIRE(n >= 1 && d >= 1 && s >= 1, "bad shape n=%d d=%d s=%d", n, d, s);
+// the anchors' columns at the host boundary: the coordinates, and the cluster sizes behind them where the Laplacian reads them
+int check_anchor_columns(int d, int ucols, int glc) {
   FLGP_REQUIRE(ucols == d || ucols == d + 1, "U must have d or d+1 columns (d=%d, got %d)", d, ucols);
-  FLGP_REQUIRE(!need_sizes || ucols == d + 1,
+  FLGP_REQUIRE(glc != FLGP_GL_CLUSTER_NORMALIZED || ucols == d + 1,
                "gl=\"cluster-normalized\" needs the cluster sizes in column d+1 of U (the reference reads out of bounds here)");
+  return FLGP_OK;
+}
+
+// the k-NN kernels' panel of the device anchors dU (s x d, ld ldu): Ut and uu, allocated here (knn.hip)
+int anchor_panel(hipStream_t st, const double *dU, int s, int ldu, int d, DevBuf &Ut, DevBuf &uu) {
   const int dpad = flgp_dev_anchor_dpad(d);
   FLGP_REQUIRE(dpad > 0, "kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
-  S.n = n; S.d = d; S.s = s;
   const int rows = flgp_dev_anchor_rows(s);
+  FLGP_TRY(Ut.alloc(sizeof(double) * (size_t)rows * dpad));
+  FLGP_TRY(uu.alloc(sizeof(double) * (size_t)rows));
+  return flgp_dev_anchor_prep(st, dU, s, ldu, d, Ut.as<double>(), uu.as<double>());
+}
+
+int upload_points(Sim &S, hipStream_t st, const double *X, int n, int d, const double *U, int s, int ucols, int glc) {
+  FLGP_REQUIRE(X && U, "null pointer");
+  FLGP_REQUIRE(n >= 1 && d >= 1 && s >= 1, "bad shape n=%d d=%d s=%d", n, d, s);
+  FLGP_TRY(check_anchor_columns(d, ucols, glc));
+  S.n = n; S.d = d; S.s = s;
   FLGP_TRY(S.X.alloc(sizeof(double) * (size_t)n * d));
   FLGP_TRY(S.U.alloc(sizeof(double) * (size_t)s * ucols));
-  FLGP_TRY(S.Ut.alloc(sizeof(double) * (size_t)rows * dpad));
-  FLGP_TRY(S.uu.alloc(sizeof(double) * (size_t)rows));
   FLGP_TRY(h2d(S.X.p, X, sizeof(double) * (size_t)n * d, st));
   FLGP_TRY(h2d(S.U.p, U, sizeof(double) * (size_t)s * ucols, st));
   {   // a NaN row would leave the k-NN lists empty (knn.hip); refuse before anything is computed from it
@@ -152,7 +150,7 @@ int upload_points(Sim &S, hipStream_t st, const double *X, int n, int d, const d
     FLGP_TRY(ck.finite(st, S.U.as<double>(), (long)s * ucols));
     FLGP_TRY(ck.verdict(st, "points / anchors"));
   }
-  return flgp_dev_anchor_prep(st, S.U.as<double>(), s, s, d, S.Ut.as<double>(), S.uu.as<double>());
+  return anchor_panel(st, S.U.as<double>(), s, s, d, S.Ut, S.uu);
 }
 
 int run_knn(Sim &S, hipStream_t st, int r, bool want_dist) {
@@ -254,7 +252,7 @@ int csr_out(Sim &S, hipStream_t st, int *csr_p, int *csr_j, double *csr_x) {
 // spectrum_from_Z_cpp on the device ELL (reference src/Spectrum.cpp:146-161): leaves values (K)
 // and vectors (n x K) on the device
 struct Spectrum {
-  DevBuf G, eig, V, values, vectors, work, uwork;
+  DevBuf G, eig, V, values, vectors, work, uwork;     // values / vectors: the caller's where it has set (borrowed) them
   int K = 0;
 };
 
@@ -294,8 +292,8 @@ int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info) {
   if (info) for (int q = 0; q < 4; ++q) info[q] = solve_info[q];
   FLGP_TRY(flgp_dev_spectrum_usable_route(st, P.eig.as<double>(), K, solve_info[2]));
   // u = A v / sigma, vectors = u sqrt(n), values = sigma^2 (or sigma if root)  (:153-158)
-  FLGP_TRY(P.values.alloc(sizeof(double) * (size_t)K));
-  FLGP_TRY(P.vectors.alloc(sizeof(double) * (size_t)S.n * K));
+  if (!P.values.p) FLGP_TRY(P.values.alloc(sizeof(double) * (size_t)K));
+  if (!P.vectors.p) FLGP_TRY(P.vectors.alloc(sizeof(double) * (size_t)S.n * K));
   FLGP_TRY(P.uwork.alloc(flgp_dev_u_recover_workspace(S.s, K)));
   return flgp_dev_u_recover(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.r, P.V.as<double>(), S.s, S.s,
                             P.eig.as<double>(), K, std::sqrt((double)(S.n_global ? S.n_global : (long)S.n)), root,
@@ -310,199 +308,64 @@ int parse_kernel(const char *kernel, int *se) {
   return FLGP_ERR_UNSUPPORTED;
 }
 
-// ------------------------------------------------------------------------------------------
-// H to the caller's (pageable) buffer without serialising GEMM, PCIe and the host copy.
-// H is n0 x n1 column-major and the contraction is independent per column, so H goes over in blocks of columns:
-// block c is contracted into one of two device buffers while block c-1 crosses PCIe into one of two pinned buffers and
-// block c-2 is copied from there into the caller's memory by a few host threads.  (hipMemcpyAsync straight into
-// pageable memory stages through the runtime's own bounce buffer on ONE thread and never overlaps the GEMM: 0.44-0.74 s
-// for the 8 GB of BASELINE configs[2] in round 1, against 0.16 s of PCIe.)  The pinned buffers are kept for the
-// lifetime of the process (pinning 1 GB costs more than the whole call).
-// ------------------------------------------------------------------------------------------
-struct PinnedRing {
-  void *buf[2] = {nullptr, nullptr};
-  size_t bytes = 0;
-  bool busy = false;
-  void drop() {
-    for (int q = 0; q < 2; ++q) { if (buf[q]) (void)hipHostFree(buf[q]); buf[q] = nullptr; }
-    bytes = 0;
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// heat_kernel_spectrum_cpp from host points and anchors up to the pair on the device (reference src/Spectrum.cpp:28-37):
+// the strings, the entry's own argument check (args_ok, else args_msg), then on a stream of its own upload -> cross
+// similarity -> spectrum, not synchronised.  t_begin / t_uploaded: the clock before and after the upload.
+struct HostSpectrum {
+  Stream st;
+  Sim S;
+  Spectrum P;
+  double t_begin = 0.0, t_uploaded = 0.0;
+  int run(bool args_ok, const char *args_msg, const double *X_all, int n, int d, const double *U, int s, int ucols, int r, int K,
+          const char *kernel, const char *gl, int root, double epsilon) {
+    int se = 0;
+    FLGP_TRY(parse_kernel(kernel, &se));
+    const int glc = flgp_parse_gl(gl);
+    if (glc < 0) return glc;
+    FLGP_REQUIRE(args_ok, "%s", args_msg);
+    FLGP_TRY(st.create());
+    t_begin = now_s();
+    FLGP_TRY(upload_points(S, st.s, X_all, n, d, U, s, ucols, glc));
+    t_uploaded = now_s();
+    S.want_csc = true;
+    FLGP_TRY(cross_similarity(S, st.s, r, se, glc, epsilon, ucols));
+    return spectrum(S, st.s, K, root, P, nullptr);
   }
-  int ensure(size_t need) {
-    if (need <= bytes) return FLGP_OK;
-    drop();
-    for (int q = 0; q < 2; ++q)
-      if (hipHostMalloc(&buf[q], need, hipHostMallocDefault) != hipSuccess) {
-        set_error("hipHostMalloc of %zu bytes failed", need);
-        drop();
-        return FLGP_ERR_NOMEM;
-      }
-    bytes = need;
-    return FLGP_OK;
-  }
-};
-// The rings are handed out one per call in flight (the lock covers the hand-out only, not the multi-GB transfer): a
-// second caller gets a ring of its own, up to `hk_rings_max` (2); beyond that callers queue.  flgp_release_pinned()
-// gives the idle ones back to the system.
-static std::mutex g_ring_mu;
-static std::condition_variable g_ring_cv;
-static std::vector<PinnedRing *> g_rings;
-struct RingLease {
-  PinnedRing *r = nullptr;
-  explicit RingLease(int at_least = 0) {     // at_least: the ranks of one multi-GPU call each need a ring at the same time
-    std::unique_lock<std::mutex> lk(g_ring_mu);
-    const size_t cap = (size_t)std::max(std::max(1, tuning("hk_rings_max", 2)), at_least);
-    for (;;) {
-      for (PinnedRing *c : g_rings) if (!c->busy) { r = c; break; }
-      if (!r && g_rings.size() < cap) { r = new PinnedRing(); g_rings.push_back(r); }
-      if (r) break;
-      g_ring_cv.wait(lk);
-    }
-    r->busy = true;
-  }
-  ~RingLease() {
-    { std::lock_guard<std::mutex> lk(g_ring_mu); r->busy = false; }
-    g_ring_cv.notify_one();
-  }
-};
-// events of one call, destroyed on every way out
-struct EventSet {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  int create() {
-    for (int q = 0; q < 4; ++q)
-      if (hipEventCreateWithFlags(&e[q], hipEventDisableTiming) != hipSuccess) { e[q] = nullptr; set_error("hipEventCreate failed"); return FLGP_ERR_HIP; }
-    return FLGP_OK;
-  }
-  ~EventSet() { for (int q = 0; q < 4; ++q) if (e[q]) (void)hipEventDestroy(e[q]); }
 };
 
-static void parallel_copy(char *dst, const char *src, size_t bytes, int nthreads, std::vector<std::thread> &pool) {
-  const size_t per = (bytes / nthreads + 4095) / 4096 * 4096;
-  for (int q = 0; q < nthreads; ++q) {
-    const size_t a = (size_t)q * per;
-    if (a >= bytes) break;
-    const size_t len = std::min(per, bytes - a);
-    pool.emplace_back([=] { memcpy(dst + a, src + a, len); });
-  }
+// a caller's ELL (n x r column indices and values) on the device; refused where an index is no column (they become
+// addresses in the CSC / Gram kernels) or, with check_values, a value is not finite
+int upload_ell(Sim &S, hipStream_t st, const int *csr_j, const double *csr_x, int n, int s, int r, bool check_values,
+               const char *who) {
+  S.n = n; S.s = s; S.r = r;
+  FLGP_TRY(alloc_ell(S));
+  FLGP_TRY(h2d(S.ell_idx.p, csr_j, sizeof(int) * (size_t)n * r, st));
+  FLGP_TRY(h2d(S.ell_val.p, csr_x, sizeof(double) * (size_t)n * r, st));
+  InputCheck ck;
+  FLGP_TRY(ck.begin(st));
+  FLGP_TRY(ck.indices(st, S.ell_idx.as<int>(), (long)n * r, s));
+  if (check_values) FLGP_TRY(ck.finite(st, S.ell_val.as<double>(), (long)n * r));
+  return ck.verdict(st, who);
 }
 
-// H(:, b) for b in [0, n1): rows [row0_0, row0_0 + n0) of V against rows [row0_1, row0_1 + n1); H host, ld n0
-static int hk_ranges_to_host(hipStream_t st, const double *d_values, int K, double t, const double *d_vectors, int ldv,
-                             int row0_0, int n0, int row0_1, int n1, double *H) {
-  if (n0 == 0 || n1 == 0) return FLGP_OK;
-  const size_t colbytes = sizeof(double) * (size_t)n0;
-  // block width: ~512 MB per block, a multiple of 64 columns where that is possible (half a GEMM tile)
-  int nc = (int)std::max<size_t>(1, ((size_t)std::max(1, tuning("hk_block_mb", 512)) << 20) / colbytes);
-  if (nc >= 64) nc = nc / 64 * 64;
-  if (nc > n1) nc = n1;
-  const int nblk = ceil_div(n1, nc);
-  if (nblk <= 1 || tuning("hk_pipelined_d2h", 1) == 0) {   // small: one contraction, one copy
-    DevBuf dH, work;
-    FLGP_TRY(dH.alloc(colbytes * n1));
-    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n0, n1, K, 0)));
-    FLGP_TRY(flgp_dev_hk(st, d_values, K, t, d_vectors, ldv, nullptr, row0_0, n0, d_vectors, ldv, nullptr, row0_1, n1,
-                         dH.as<double>(), n0, work.as<double>()));
-    FLGP_TRY(d2h(H, dH.p, colbytes * n1, st));
-    FLGP_HIP(hipStreamSynchronize(st));
-    return FLGP_OK;
-  }
-  RingLease lease;
-  PinnedRing &ring = *lease.r;
-  const size_t blkbytes = colbytes * nc;
-  FLGP_TRY(ring.ensure(blkbytes));
-  DevBuf dH[2], work;
-  FLGP_TRY(dH[0].alloc(blkbytes)); FLGP_TRY(dH[1].alloc(blkbytes));
-  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n0, nc, K, 0)));
-  Stream cp;
-  FLGP_TRY(cp.create());
-  EventSet evs;
-  FLGP_TRY(evs.create());
-  hipEvent_t *gemm_done = evs.e, *dma_done = evs.e + 2;
-  const int nthreads = std::max(1, std::min(tuning("hk_copy_threads", 8), (int)std::thread::hardware_concurrency()));
-  std::vector<std::thread> copiers[2];
-  auto join = [&](int q) { for (auto &th : copiers[q]) th.join(); copiers[q].clear(); };
-  int rc = FLGP_OK;
-  for (int c = 0; c <= nblk + 1 && rc == FLGP_OK; ++c) {
-    const int q = c & 1;
-    if (c < nblk) {
-      const int b0 = c * nc, w = std::min(nc, n1 - b0);
-      // device buffer q was last read by the DMA of block c-2, pinned buffer q by the host copy of block c-2
-      if (c >= 2) { if (hipStreamWaitEvent(st, dma_done[q], 0) != hipSuccess) rc = FLGP_ERR_HIP; }
-      if (rc == FLGP_OK)
-        rc = flgp_dev_hk(st, d_values, K, t, d_vectors, ldv, nullptr, row0_0, n0, d_vectors, ldv, nullptr, row0_1 + b0, w,
-                         dH[q].as<double>(), n0, work.as<double>());
-      if (rc == FLGP_OK && hipEventRecord(gemm_done[q], st) != hipSuccess) rc = FLGP_ERR_HIP;
-      join(q);                                   // host copy of block c-2 out of pinned buffer q
-      if (rc == FLGP_OK && (hipStreamWaitEvent(cp.s, gemm_done[q], 0) != hipSuccess ||
-                            hipMemcpyAsync(ring.buf[q], dH[q].p, colbytes * w, hipMemcpyDeviceToHost, cp.s) != hipSuccess ||
-                            hipEventRecord(dma_done[q], cp.s) != hipSuccess)) rc = FLGP_ERR_HIP;
-    }
-    if (c >= 1 && c - 1 < nblk && rc == FLGP_OK) {   // block c-1 has been enqueued: when it has landed, copy it out
-      const int p = (c - 1) & 1, b0 = (c - 1) * nc, w = std::min(nc, n1 - b0);
-      if (hipEventSynchronize(dma_done[p]) != hipSuccess) rc = FLGP_ERR_HIP;
-      else parallel_copy((char *)H + colbytes * b0, (const char *)ring.buf[p], colbytes * w, nthreads, copiers[p]);
-    }
-  }
-  join(0); join(1);
-  (void)hipStreamSynchronize(cp.s);
-  (void)hipStreamSynchronize(st);
-  if (rc == FLGP_ERR_HIP) set_error("HIP error in the pipelined copy of H");
-  return rc;
+// the rows of an EigenPair that a heat-kernel block asks for lie in [0, n)
+int check_rows(const int *idx0, int n0, const int *idx1, int n1, int n) {
+  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
+  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
+  return FLGP_OK;
 }
 
-// A device matrix (rows x cols, column-major, ld = rows) to the caller's pageable memory with column c at H + c * ldh
-// (ldh >= rows: a rank's row block of the whole H), through the pinned ring: the DMA of block c runs while a few host
-// threads copy block c-1 out of its pinned buffer.  What the multi-GPU host entry uses per rank (round 4; a single
-// hipMemcpy2DAsync into pageable memory staged through the runtime's bounce buffer on one thread before).
-static int d2h_cols_pipelined(hipStream_t st, const double *dM, long rows, int cols, double *H, long ldh, int rings_at_least) {
-  if (rows <= 0 || cols <= 0) return FLGP_OK;
-  const size_t colbytes = sizeof(double) * (size_t)rows;
-  int nc = (int)std::max<size_t>(1, ((size_t)std::max(1, tuning("hk_block_mb", 512)) << 19) / colbytes);   // half of the GEMM path's block: nothing to overlap with but the copies themselves
-  if (nc > cols) nc = cols;
-  const int nblk = ceil_div(cols, nc);
-  RingLease lease(rings_at_least);
-  PinnedRing &ring = *lease.r;
-  FLGP_TRY(ring.ensure(colbytes * nc));
-  EventSet evs;
-  FLGP_TRY(evs.create());
-  hipEvent_t *dma_done = evs.e;
-  const int nthreads = std::max(1, std::min(tuning("hk_copy_threads", 8), (int)std::thread::hardware_concurrency()));
-  std::vector<std::thread> copiers[2];
-  auto join = [&](int q) { for (auto &th : copiers[q]) th.join(); copiers[q].clear(); };
-  int rc = FLGP_OK;
-  for (int c = 0; c <= nblk && rc == FLGP_OK; ++c) {
-    const int q = c & 1;
-    if (c < nblk) {
-      const int b0 = c * nc, w = std::min(nc, cols - b0);
-      join(q);                                   // the host copy of block c-2 has left pinned buffer q
-      if (hipMemcpyAsync(ring.buf[q], dM + (size_t)b0 * rows, colbytes * w, hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipEventRecord(dma_done[q], st) != hipSuccess) rc = FLGP_ERR_HIP;
-    }
-    if (c >= 1 && rc == FLGP_OK) {
-      const int p = (c - 1) & 1, b0 = (c - 1) * nc, w = std::min(nc, cols - b0);
-      if (hipEventSynchronize(dma_done[p]) != hipSuccess) { rc = FLGP_ERR_HIP; break; }
-      const char *src = (const char *)ring.buf[p];
-      const int per = (w + nthreads - 1) / nthreads;
-      for (int tq = 0; tq < nthreads; ++tq) {
-        const int c0 = tq * per, c1 = std::min(w, c0 + per);
-        if (c0 >= c1) break;
-        copiers[p].emplace_back([=] {
-          for (int cc = c0; cc < c1; ++cc) memcpy(H + (size_t)(b0 + cc) * (size_t)ldh, src + colbytes * (size_t)cc, colbytes);
-        });
-      }
-    }
-  }
-  join(0); join(1);
-  (void)hipStreamSynchronize(st);
-  if (rc == FLGP_ERR_HIP) set_error("HIP error in the pipelined copy of a rank's rows of H");
-  return rc;
+// a new EigenPair of the current device, its buffers still empty
+int new_eigenpair(int n, int K, std::unique_ptr<flgp_eigenpair> &ep) {
+  ep.reset(new flgp_eigenpair());
+  ep->n = n; ep->K = K;
+  FLGP_HIP(hipGetDevice(&ep->device));
+  return FLGP_OK;
 }
 
 }  // namespace
-
-extern "C" void flgp_release_pinned(void) {
-  std::lock_guard<std::mutex> lk(g_ring_mu);
-  for (PinnedRing *c : g_rings) if (!c->busy) c->drop();
-}
 
 extern "C" int flgp_knn(const double *X, int n, int d, const double *U, int s, int r, const char *distance,
                         int *ind_knn, double *dist) {
@@ -512,7 +375,7 @@ extern "C" int flgp_knn(const double *X, int n, int d, const double *U, int s, i
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, d, false));
+  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, d, FLGP_GL_RW));
   FLGP_TRY(run_knn(S, st.s, r, dist != nullptr));
   FLGP_TRY(d2h(ind_knn, S.knn_idx.p, sizeof(int) * (size_t)n * r, st.s));
   if (dist) FLGP_TRY(d2h(dist, S.knn_dist.p, sizeof(double) * (size_t)n * r, st.s));
@@ -542,7 +405,7 @@ extern "C" int flgp_local_anchor_embedding(const double *x, int d, const double 
   FLGP_TRY(st.create());
   Sim S;
   // one point, its r anchors in the given order: "k-NN" indices are 0..r-1
-  FLGP_TRY(upload_points(S, st.s, x, 1, d, U, r, d, false));
+  FLGP_TRY(upload_points(S, st.s, x, 1, d, U, r, d, FLGP_GL_RW));
   S.r = r;
   std::vector<int> ids(r);
   for (int a = 0; a < r; ++a) ids[a] = a;
@@ -562,7 +425,7 @@ extern "C" int flgp_lae(const double *X, int n, int d, const double *U, int s, i
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, d, false));
+  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, d, FLGP_GL_RW));
   FLGP_TRY(cross_similarity(S, st.s, r, 0, -1 /* no Laplacian */, 0.0, d));
   return csr_out(S, st.s, csr_p, csr_j, csr_x);
 }
@@ -575,7 +438,7 @@ extern "C" int flgp_cross_similarity_lae(const double *X, int n, int d, const do
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, ucols, glc == FLGP_GL_CLUSTER_NORMALIZED));
+  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, ucols, glc));
   FLGP_TRY(cross_similarity(S, st.s, r, 0, glc, 0.0, ucols));
   return csr_out(S, st.s, csr_p, csr_j, csr_x);
 }
@@ -588,7 +451,7 @@ extern "C" int flgp_cross_similarity_se(const double *X, int n, int d, const dou
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, ucols, glc == FLGP_GL_CLUSTER_NORMALIZED));
+  FLGP_TRY(upload_points(S, st.s, X, n, d, U, s, ucols, glc));
   FLGP_TRY(cross_similarity(S, st.s, r, 1, glc, epsilon, ucols));
   return csr_out(S, st.s, csr_p, csr_j, csr_x);
 }
@@ -602,16 +465,7 @@ extern "C" int flgp_graph_laplacian(const int *csr_j, double *csr_x, int n, int 
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  S.n = n; S.s = s; S.r = r;
-  FLGP_TRY(alloc_ell(S));
-  FLGP_TRY(h2d(S.ell_idx.p, csr_j, sizeof(int) * (size_t)n * r, st.s));
-  FLGP_TRY(h2d(S.ell_val.p, csr_x, sizeof(double) * (size_t)n * r, st.s));
-  {   // the column indices become addresses in the CSC / Gram kernels
-    InputCheck ck;
-    FLGP_TRY(ck.begin(st.s));
-    FLGP_TRY(ck.indices(st.s, S.ell_idx.as<int>(), (long)n * r, s));
-    FLGP_TRY(ck.verdict(st.s, "graph_laplacian"));
-  }
+  FLGP_TRY(upload_ell(S, st.s, csr_j, csr_x, n, s, r, false, "graph_laplacian"));
   if (num_class) {
     FLGP_TRY(S.num_class.alloc(sizeof(double) * (size_t)s));
     FLGP_TRY(h2d(S.num_class.p, num_class, sizeof(double) * (size_t)s, st.s));
@@ -628,17 +482,7 @@ extern "C" int flgp_spectrum_from_Z(const int *csr_j, const double *csr_x, int n
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  S.n = n; S.s = s; S.r = r;
-  FLGP_TRY(alloc_ell(S));
-  FLGP_TRY(h2d(S.ell_idx.p, csr_j, sizeof(int) * (size_t)n * r, st.s));
-  FLGP_TRY(h2d(S.ell_val.p, csr_x, sizeof(double) * (size_t)n * r, st.s));
-  {
-    InputCheck ck;
-    FLGP_TRY(ck.begin(st.s));
-    FLGP_TRY(ck.indices(st.s, S.ell_idx.as<int>(), (long)n * r, s));
-    FLGP_TRY(ck.finite(st.s, S.ell_val.as<double>(), (long)n * r));
-    FLGP_TRY(ck.verdict(st.s, "spectrum_from_Z"));
-  }
+  FLGP_TRY(upload_ell(S, st.s, csr_j, csr_x, n, s, r, true, "spectrum_from_Z"));
   Spectrum P;
   FLGP_TRY(spectrum(S, st.s, K, root, P, nullptr));
   FLGP_TRY(d2h(values, P.values.p, sizeof(double) * (size_t)P.K, st.s));
@@ -667,8 +511,7 @@ extern "C" int flgp_hk_from_spectrum(const double *values, const double *vectors
                                      const int *idx0, int n0, const int *idx1, int n1, double *H) {
   FLGP_REQUIRE(values && vectors && idx0 && idx1 && H, "HK_from_spectrum: null pointer");
   FLGP_REQUIRE(n >= 1 && K >= 1 && n0 >= 0 && n1 >= 0, "HK_from_spectrum: bad shape");
-  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
+  FLGP_TRY(check_rows(idx0, n0, idx1, n1, n));
   if (n0 == 0 || n1 == 0) return FLGP_OK;
   Stream st;
   FLGP_TRY(st.create());
@@ -682,8 +525,7 @@ extern "C" int flgp_hk_from_spectrum(const double *values, const double *vectors
 
 static int hk_on_device(hipStream_t st, const double *d_values, const double *d_vectors, int n, int K, double t,
                         const int *idx0, int n0, const int *idx1, int n1, double *H) {
-  for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
-  for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
+  FLGP_TRY(check_rows(idx0, n0, idx1, n1, n));
   if (is_range(idx0, n0) && is_range(idx1, n1) && n0 > 0 && n1 > 0)   // the callers' usual case (LinSpaced ranges, src/Spectrum.cpp:38-39): pipelined
     return hk_ranges_to_host(st, d_values, K, t, d_vectors, n, idx0[0], n0, idx1[0], n1, H);
   return hk_gathered_to_host(st, d_values, d_vectors, n, K, t, idx0, n0, idx1, n1, H);
@@ -695,9 +537,8 @@ extern "C" int flgp_eigenpair_from_host(const double *values, const double *vect
   *out = nullptr;
   Stream st;
   FLGP_TRY(st.create());
-  std::unique_ptr<flgp_eigenpair> ep(new flgp_eigenpair());
-  ep->n = n; ep->K = K;
-  FLGP_HIP(hipGetDevice(&ep->device));
+  std::unique_ptr<flgp_eigenpair> ep;
+  FLGP_TRY(new_eigenpair(n, K, ep));
   FLGP_TRY(ep->values.alloc(sizeof(double) * (size_t)K));
   FLGP_TRY(ep->vectors.alloc(sizeof(double) * (size_t)n * K));
   FLGP_TRY(h2d(ep->values.p, values, sizeof(double) * (size_t)K, st.s));
@@ -710,36 +551,19 @@ extern "C" int flgp_eigenpair_from_host(const double *values, const double *vect
 extern "C" int flgp_heat_kernel_spectrum_resident(const double *X_all, int n, int d, const double *U, int s, int ucols,
                                                   int r, int K, const char *kernel, const char *gl, int root,
                                                   double epsilon, flgp_eigenpair **out) {
-  int se = 0;
-  FLGP_TRY(parse_kernel(kernel, &se));
-  const int glc = flgp_parse_gl(gl);
-  if (glc < 0) return glc;
-  FLGP_REQUIRE(out, "heat_kernel_spectrum_resident: null pointer");
-  *out = nullptr;
-  Stream st;
-  FLGP_TRY(st.create());
-  Sim S;
-  FLGP_TRY(upload_points(S, st.s, X_all, n, d, U, s, ucols, glc == FLGP_GL_CLUSTER_NORMALIZED));
-  S.want_csc = true;
-  FLGP_TRY(cross_similarity(S, st.s, r, se, glc, epsilon, ucols));
-  Spectrum P;
-  FLGP_TRY(spectrum(S, st.s, K, root, P, nullptr));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  std::unique_ptr<flgp_eigenpair> ep(new flgp_eigenpair());
-  ep->n = n; ep->K = P.K;
-  FLGP_HIP(hipGetDevice(&ep->device));
-  std::swap(ep->values.p, P.values.p);     // the buffers change owner: no copy
-  std::swap(ep->vectors.p, P.vectors.p);
+  if (out) *out = nullptr;
+  HostSpectrum h;
+  FLGP_TRY(h.run(out != nullptr, "heat_kernel_spectrum_resident: null pointer", X_all, n, d, U, s, ucols, r, K, kernel, gl, root, epsilon));
+  FLGP_HIP(hipStreamSynchronize(h.st.s));
+  std::unique_ptr<flgp_eigenpair> ep;
+  FLGP_TRY(new_eigenpair(n, h.P.K, ep));
+  std::swap(ep->values.p, h.P.values.p);     // the buffers change owner: no copy
+  std::swap(ep->vectors.p, h.P.vectors.p);
   *out = ep.release();
   return FLGP_OK;
 }
 
 // ---- anchors by Lloyd k-means on the device (kmeans.hip)
-extern "C" int flgp_dev_kmeans_lloyd(void *stream, const double *dX, int n, int ldx, int d, int s, double *dC, int ldc,
-                                     double *d_size, int iter_max, int *iters_out, double *withinss_out);
-extern "C" int flgp_dev_kmeans_init(void *stream, const double *dX, int n, int ldx, int d, const int *d_rows, int s,
-                                    double *dC, int ldc);
-
 extern "C" int flgp_kmeans_lloyd(const double *X, int n, int d, int s, const int *init_rows, int nstart, int iter_max,
                                  double *U_out, int *iters_out, double *withinss_out) {
   FLGP_REQUIRE(X && init_rows && U_out, "kmeans_lloyd: null pointer");
@@ -778,9 +602,6 @@ extern "C" int flgp_kmeans_lloyd(const double *X, int n, int d, int s, const int
 }
 
 // ---- Nystrom-extension spectrum (reference src/Fit.cpp:244-289)
-extern "C" int flgp_dev_nystrom_eigenpair(void *stream, const double *dX, int n, int ldx, int d, const double *dU, int s,
-                                          int ldu, double a2, int K, double *d_values, double *d_vectors, int ldv);
-
 static int nystrom_on_device(hipStream_t st, const double *X, int n, int d, const double *U, int s, double a2, int K,
                              DevBuf &dval, DevBuf &dvec) {
   FLGP_REQUIRE(X && U, "nystrom_eigenpair: null pointer");
@@ -815,11 +636,10 @@ extern "C" int flgp_nystrom_eigenpair_resident(const double *X, int n, int d, co
   *out = nullptr;
   Stream st;
   FLGP_TRY(st.create());
-  std::unique_ptr<flgp_eigenpair> ep(new flgp_eigenpair());
+  std::unique_ptr<flgp_eigenpair> ep;
+  FLGP_TRY(new_eigenpair(n, K, ep));
   FLGP_TRY(nystrom_on_device(st.s, X, n, d, U, s, a2, K, ep->values, ep->vectors));
   FLGP_HIP(hipStreamSynchronize(st.s));
-  ep->n = n; ep->K = K;
-  FLGP_HIP(hipGetDevice(&ep->device));
   *out = ep.release();
   return FLGP_OK;
 }
@@ -856,52 +676,28 @@ extern "C" void flgp_eigenpair_free(flgp_eigenpair *ep) { delete ep; }
 extern "C" int flgp_heat_kernel_spectrum(const double *X_all, int n, int d, const double *U, int s, int ucols,
                                          int r, int K, const char *kernel, const char *gl, int root,
                                          double epsilon, double *values, double *vectors) {
-  int se = 0;
-  FLGP_TRY(parse_kernel(kernel, &se));
-  const int glc = flgp_parse_gl(gl);
-  if (glc < 0) return glc;
-  FLGP_REQUIRE(values && vectors, "heat_kernel_spectrum: null pointer");
-  Stream st;
-  FLGP_TRY(st.create());
-  Sim S;
-  FLGP_TRY(upload_points(S, st.s, X_all, n, d, U, s, ucols, glc == FLGP_GL_CLUSTER_NORMALIZED));
-  S.want_csc = true;
-  FLGP_TRY(cross_similarity(S, st.s, r, se, glc, epsilon, ucols));
-  Spectrum P;
-  FLGP_TRY(spectrum(S, st.s, K, root, P, nullptr));
-  FLGP_TRY(d2h(values, P.values.p, sizeof(double) * (size_t)P.K, st.s));
-  FLGP_TRY(d2h(vectors, P.vectors.p, sizeof(double) * (size_t)n * P.K, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
+  HostSpectrum h;
+  FLGP_TRY(h.run(values && vectors, "heat_kernel_spectrum: null pointer", X_all, n, d, U, s, ucols, r, K, kernel, gl, root, epsilon));
+  FLGP_TRY(d2h(values, h.P.values.p, sizeof(double) * (size_t)h.P.K, h.st.s));
+  FLGP_TRY(d2h(vectors, h.P.vectors.p, sizeof(double) * (size_t)n * h.P.K, h.st.s));
+  FLGP_HIP(hipStreamSynchronize(h.st.s));
   return FLGP_OK;
 }
 
 extern "C" int flgp_heat_kernel_covariance(const double *X_all, int n, int m, int d, const double *U, int s,
                                            int ucols, int r, double t, int K, const char *kernel, const char *gl,
                                            int root, double epsilon, double *H) {
-  int se = 0;
-  FLGP_TRY(parse_kernel(kernel, &se));
-  const int glc = flgp_parse_gl(gl);
-  if (glc < 0) return glc;
-  FLGP_REQUIRE(H && m >= 1 && m <= n, "heat_kernel_covariance: need 1 <= m <= n and H");
-  Stream st;
-  FLGP_TRY(st.create());
-  Sim S;
+  HostSpectrum h;
   const bool verbose = tuning("e2e_verbose", 0) != 0;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  FLGP_TRY(upload_points(S, st.s, X_all, n, d, U, s, ucols, glc == FLGP_GL_CLUSTER_NORMALIZED));
-  const double t1 = now();
-  S.want_csc = true;
-  FLGP_TRY(cross_similarity(S, st.s, r, se, glc, epsilon, ucols));
-  Spectrum P;
-  FLGP_TRY(spectrum(S, st.s, K, root, P, nullptr));
-  if (verbose) (void)hipStreamSynchronize(st.s);
-  const double t2 = now();
+  FLGP_TRY(h.run(H && m >= 1 && m <= n, "heat_kernel_covariance: need 1 <= m <= n and H", X_all, n, d, U, s, ucols, r, K, kernel, gl, root,
+                 epsilon));
+  if (verbose) (void)hipStreamSynchronize(h.st.s);
+  const double t2 = now_s();
   // H = V[0:n] diag(exp(-t(1-values))) V[0:m]^T  (idx0 = 0..n-1, idx1 = 0..m-1, src/Spectrum.cpp:38-40)
-  FLGP_TRY(hk_ranges_to_host(st.s, P.values.as<double>(), P.K, t, P.vectors.as<double>(), n, 0, n, 0, m, H));
+  FLGP_TRY(hk_ranges_to_host(h.st.s, h.P.values.as<double>(), h.P.K, t, h.P.vectors.as<double>(), n, 0, n, 0, m, H));
   if (verbose)
-    fprintf(stderr, "[flgp e2e] upload %.1f ms, similarity + spectrum %.1f ms, H to host %.1f ms\n", (t1 - t0) * 1e3, (t2 - t1) * 1e3,
-            (now() - t2) * 1e3);
+    fprintf(stderr, "[flgp e2e] upload %.1f ms, similarity + spectrum %.1f ms, H to host %.1f ms\n", (h.t_uploaded - h.t_begin) * 1e3,
+            (t2 - h.t_uploaded) * 1e3, (now_s() - t2) * 1e3);
   return FLGP_OK;
 }
 
@@ -971,15 +767,10 @@ extern "C" int flgp_dev_cluster_sizes(void *stream, const flgp_comm *comm, const
                                       const double *dU, int ldu, int s, double *d_sizes_out) {
   hipStream_t st = (hipStream_t)stream;
   FLGP_REQUIRE(dX_loc && dU && d_sizes_out && n_loc >= 1 && s >= 1 && ldx >= n_loc && ldu >= s, "cluster_sizes: bad arguments");
-  const int dpad = flgp_dev_anchor_dpad(d);
-  FLGP_REQUIRE(dpad > 0, "kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
-  const int rows = flgp_dev_anchor_rows(s);
   DevBuf Ut, uu, idx, cnt;
-  FLGP_TRY(Ut.alloc(sizeof(double) * (size_t)rows * dpad));
-  FLGP_TRY(uu.alloc(sizeof(double) * (size_t)rows));
+  FLGP_TRY(anchor_panel(st, dU, s, ldu, d, Ut, uu));
   FLGP_TRY(idx.alloc(sizeof(int) * (size_t)n_loc));
   FLGP_TRY(cnt.alloc(sizeof(int) * (size_t)s));
-  FLGP_TRY(flgp_dev_anchor_prep(st, dU, s, ldu, d, Ut.as<double>(), uu.as<double>()));
   FLGP_TRY(flgp_dev_knn(st, dX_loc, n_loc, ldx, d, Ut.as<double>(), uu.as<double>(), s, 1, idx.as<int>(), nullptr, n_loc));
   FLGP_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * (size_t)s, st));
   hipLaunchKernelGGL(count_labels_kernel, dim3((unsigned)std::min<long>(2048, ((long)n_loc + 255) / 256)), dim3(256), 0, st, idx.as<int>(),
@@ -1009,16 +800,11 @@ extern "C" int flgp_dev_heat_kernel_covariance_sharded(void *stream, const flgp_
   FLGP_REQUIRE(m >= 1 && (long)m <= n_global && ldh >= n_loc, "sharded covariance: need 1 <= m <= n and ldh >= n_loc");
   FLGP_REQUIRE(glc != FLGP_GL_CLUSTER_NORMALIZED || d_sizes, "gl=\"cluster-normalized\" needs the cluster sizes");
   FLGP_REQUIRE(!d_vectors_out || ldv >= n_loc, "sharded covariance: ldv < n_loc");
-  const int dpad = flgp_dev_anchor_dpad(d);
-  FLGP_REQUIRE(dpad > 0, "kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
   if (K < 0) K = s;
   Sim S;
   S.n = n_loc; S.d = d; S.s = s; S.ldx = ldx; S.comm = comm; S.n_global = n_global; S.sizes = d_sizes;
   S.X.borrow(dX_loc);
-  const int rows = flgp_dev_anchor_rows(s);
-  FLGP_TRY(S.Ut.alloc(sizeof(double) * (size_t)rows * dpad));
-  FLGP_TRY(S.uu.alloc(sizeof(double) * (size_t)rows));
-  FLGP_TRY(flgp_dev_anchor_prep(st, dU, s, ldu, d, S.Ut.as<double>(), S.uu.as<double>()));
+  FLGP_TRY(anchor_panel(st, dU, s, ldu, d, S.Ut, S.uu));
   S.want_csc = true;
   FLGP_TRY(cross_similarity(S, st, r, se, glc, epsilon, d));
   Spectrum P;
@@ -1067,9 +853,7 @@ extern "C" int flgp_heat_kernel_covariance_rank(const flgp_comm *comm, const dou
     FLGP_REQUIRE(n_loc >= 1 && ldx_host >= n_loc && ldh_host >= n_loc && d >= 1 && s >= 1, "heat_kernel_covariance_rank: bad shape");
     FLGP_REQUIRE(n_global >= n_loc && row_lo >= 0 && row_lo + n_loc <= n_global && m >= 1 && (long)m <= n_global,
                  "heat_kernel_covariance_rank: rows [%ld, %ld) / m = %d do not fit n = %ld", row_lo, row_lo + n_loc, m, n_global);
-    FLGP_REQUIRE(ucols == d || ucols == d + 1, "U must have d or d+1 columns (d=%d, got %d)", d, ucols);
-    FLGP_REQUIRE(glc != FLGP_GL_CLUSTER_NORMALIZED || ucols == d + 1,
-                 "gl=\"cluster-normalized\" needs the cluster sizes in column d+1 of U (the reference reads out of bounds here)");
+    FLGP_TRY(check_anchor_columns(d, ucols, glc));
     FLGP_TRY(st.create());
     FLGP_TRY(dX.alloc(sizeof(double) * (size_t)n_loc * d));
     FLGP_TRY(dUall.alloc(sizeof(double) * (size_t)s * ucols));
@@ -1110,9 +894,7 @@ extern "C" int flgp_heat_kernel_covariance_multi(const double *X_all, int n, int
   FLGP_REQUIRE(X_all && U && H && devices, "heat_kernel_covariance_multi: null pointer");
   FLGP_REQUIRE(ndev >= 1 && ndev <= 16 && n >= ndev, "heat_kernel_covariance_multi: need 1 <= ndev <= 16 ranks and n >= ndev");
   FLGP_REQUIRE(m >= 1 && m <= n && d >= 1 && s >= 1, "heat_kernel_covariance_multi: bad shape");
-  FLGP_REQUIRE(ucols == d || ucols == d + 1, "U must have d or d+1 columns (d=%d, got %d)", d, ucols);
-  FLGP_REQUIRE(glc != FLGP_GL_CLUSTER_NORMALIZED || ucols == d + 1,
-               "gl=\"cluster-normalized\" needs the cluster sizes in column d+1 of U (the reference reads out of bounds here)");
+  FLGP_TRY(check_anchor_columns(d, ucols, glc));
   int ndev_sys = 0;
   FLGP_HIP(hipGetDeviceCount(&ndev_sys));
   for (int a = 0; a < ndev; ++a)
@@ -1213,7 +995,7 @@ extern "C" int flgp_lae_eigenmap(const double *X, int n, int d, const double *U,
 static int se_grid_core(Sim &S, hipStream_t st0, int r, int K, const double *a2s, int l, int glc, int root, const double *sizes,
                         double *values, double *vectors, double *d_values, double *d_vectors, double *distances_mean_out,
                         int max_parallel, int *iters_out) {
-  const int n = S.n, d = S.d, s = S.s;
+  const int n = S.n, s = S.s;
   FLGP_TRY(run_knn(S, st0, r, true));
   FLGP_TRY(alloc_ell(S));
   // pattern (sorted by column) and the mean distance; the weights of this first call are discarded
@@ -1230,7 +1012,6 @@ static int se_grid_core(Sim &S, hipStream_t st0, int r, int K, const double *a2s
   if (distances_mean_out) *distances_mean_out = mean;
   int dev = 0;
   FLGP_HIP(hipGetDevice(&dev));
-  (void)d;
 
   std::vector<int> rcs(l, FLGP_OK);
   std::vector<std::string> msgs(l);
@@ -1238,41 +1019,24 @@ static int se_grid_core(Sim &S, hipStream_t st0, int r, int K, const double *a2s
     FLGP_HIP(hipSetDevice(dev));
     Stream ws;
     FLGP_TRY(ws.create());
-    Sim W;   // shares pattern / CSC with S, owns its values
+    Sim W;   // borrows the pattern and its CSC view from S, owns its values and column sums
     W.n = n; W.d = S.d; W.s = s; W.r = r;
+    W.ell_idx.borrow(S.ell_idx.p); W.colptr.borrow(S.colptr.p); W.pos.borrow(S.pos.p);
+    W.have_csc = true;
     FLGP_TRY(W.ell_val.alloc(sizeof(double) * (size_t)n * r));
     DevBuf scratch_idx;
     FLGP_TRY(scratch_idx.alloc(sizeof(int) * (size_t)n * r));
     FLGP_TRY(flgp_dev_se_weights_den(ws.s, S.knn_idx.as<int>(), S.knn_dist.as<double>(), n, n, r, a2s[i] * mean,
                                      scratch_idx.as<int>(), W.ell_val.as<double>()));
-    const int *eidx = S.ell_idx.as<int>();
-    const int *colptr = S.colptr.as<int>(), *pos = S.pos.as<int>();
-    if (glc != FLGP_GL_RW) {
-      FLGP_TRY(colsum_of(W, ws.s, eidx, W.ell_val.as<double>()));
-      FLGP_TRY(flgp_dev_col_scale_row_normalize(ws.s, eidx, W.ell_val.as<double>(), n, r, W.colsum.as<double>(),
-                                                glc == FLGP_GL_CLUSTER_NORMALIZED ? sizes : nullptr));
-    } else {
-      FLGP_TRY(flgp_dev_row_normalize(ws.s, W.ell_val.as<double>(), n, r));
-    }
-    FLGP_TRY(colsum_of(W, ws.s, eidx, W.ell_val.as<double>()));
-    FLGP_TRY(flgp_dev_col_scale(ws.s, eidx, W.ell_val.as<double>(), n, r, W.colsum.as<double>(), nullptr, 1));
-    DevBuf G, eig, V, vals, vecs, ework, uwork;
-    FLGP_TRY(G.alloc(sizeof(double) * (size_t)s * s));
-    FLGP_TRY(flgp_dev_gram(ws.s, eidx, W.ell_val.as<double>(), n, s, r, colptr, pos, G.as<double>(), s));
-    const size_t wb = flgp_dev_eig_workspace(s, K);
-    FLGP_TRY(ework.alloc(wb));
-    FLGP_TRY(eig.alloc(sizeof(double) * (size_t)K));
-    FLGP_TRY(V.alloc(sizeof(double) * (size_t)s * K));
-    int solve_info[4] = {0, 0, 0, 0};
-    FLGP_TRY(flgp_dev_eig_topk(ws.s, G.as<double>(), s, s, K, 0.0, eig.as<double>(), V.as<double>(), s, ework.p, wb, solve_info));
-    if (iters_out) iters_out[i] = solve_info[0];
-    FLGP_TRY(flgp_dev_spectrum_usable_route(ws.s, eig.as<double>(), K, solve_info[2]));   // (a bandwidth that underflows a column of Z ends here, with the message)
-    double *vals_p = d_values ? d_values + (size_t)i * K : nullptr, *vecs_p = d_vectors ? d_vectors + (size_t)i * n * K : nullptr;
-    if (!vals_p) { FLGP_TRY(vals.alloc(sizeof(double) * (size_t)K)); vals_p = vals.as<double>(); }
-    if (!vecs_p) { FLGP_TRY(vecs.alloc(sizeof(double) * (size_t)n * K)); vecs_p = vecs.as<double>(); }
-    FLGP_TRY(uwork.alloc(flgp_dev_u_recover_workspace(s, K)));
-    FLGP_TRY(flgp_dev_u_recover(ws.s, eidx, W.ell_val.as<double>(), n, r, V.as<double>(), s, s, eig.as<double>(), K,
-                                std::sqrt((double)n), root, vecs_p, n, vals_p, uwork.as<double>()));
+    FLGP_TRY(laplacian(W, ws.s, glc, sizes));
+    Spectrum P;     // straight into the caller's device blocks where it has them
+    if (d_values) P.values.borrow(d_values + (size_t)i * K);
+    if (d_vectors) P.vectors.borrow(d_vectors + (size_t)i * n * K);
+    int info[4] = {0, 0, 0, 0};
+    const int rc = spectrum(W, ws.s, K, root, P, info);   // (a bandwidth that underflows a column of Z ends here, with the message)
+    if (iters_out) iters_out[i] = info[0];
+    FLGP_TRY(rc);
+    const double *vals_p = P.values.as<double>(), *vecs_p = P.vectors.as<double>();
     if (values) FLGP_TRY(d2h(values + (size_t)i * K, vals_p, sizeof(double) * (size_t)K, ws.s));
     if (vectors) FLGP_TRY(d2h(vectors + (size_t)i * n * K, vecs_p, sizeof(double) * (size_t)n * K, ws.s));
     FLGP_HIP(hipStreamSynchronize(ws.s));
@@ -1301,7 +1065,7 @@ extern "C" int flgp_se_spectrum_grid(const double *X_all, int n, int d, const do
   Stream st;
   FLGP_TRY(st.create());
   Sim S;
-  FLGP_TRY(upload_points(S, st.s, X_all, n, d, U, s, ucols, glc == FLGP_GL_CLUSTER_NORMALIZED));
+  FLGP_TRY(upload_points(S, st.s, X_all, n, d, U, s, ucols, glc));
   const double *sizes = (ucols == d + 1) ? S.U.as<double>() + (size_t)d * s : nullptr;
   return se_grid_core(S, st.s, r, K, a2s, l, glc, root, sizes, values, vectors, nullptr, nullptr, distances_mean_out, max_parallel, nullptr);
 }
@@ -1321,15 +1085,10 @@ extern "C" int flgp_dev_se_spectrum_grid(void *stream, const double *dX, int n, 
   FLGP_REQUIRE(glc != FLGP_GL_CLUSTER_NORMALIZED || d_sizes, "gl=\"cluster-normalized\" needs the cluster sizes");
   if (K < 0) K = s;
   FLGP_REQUIRE(K >= 1 && K <= s, "need 1 <= K <= s (K=%d, s=%d)", K, s);
-  const int dpad = flgp_dev_anchor_dpad(d);
-  FLGP_REQUIRE(dpad > 0, "kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
   Sim S;
   S.n = n; S.d = d; S.s = s; S.ldx = ldx;
   S.X.borrow(dX);
-  const int rows = flgp_dev_anchor_rows(s);
-  FLGP_TRY(S.Ut.alloc(sizeof(double) * (size_t)rows * dpad));
-  FLGP_TRY(S.uu.alloc(sizeof(double) * (size_t)rows));
-  FLGP_TRY(flgp_dev_anchor_prep(st, dU, s, ldu, d, S.Ut.as<double>(), S.uu.as<double>()));
+  FLGP_TRY(anchor_panel(st, dU, s, ldu, d, S.Ut, S.uu));
   return se_grid_core(S, st, r, K, a2s, l, glc, root, d_sizes, nullptr, nullptr, d_values, d_vectors, distances_mean_out, max_parallel,
                       iters_out);
 }

@@ -188,6 +188,14 @@ int hk_panel_launch(hipStream_t st, const double *d_values, int K, double t, con
                     const double *dV1, int ld1, const int *d_idx1, int row0_1, int n1, double *dH, long ldh,
                     double *d_vw);
 
+// Pipelined copies to the caller's pageable memory through the pinned rings (hostcopy.hip); both synchronise `st`.
+// hk_ranges_to_host: H (host, ld n0) = HK of rows [row0_0, row0_0 + n0) of V against rows [row0_1, row0_1 + n1).
+// d2h_cols_pipelined: a device matrix (rows x cols, column-major, ld = rows) with column c to H + c * ldh (ldh >= rows: a
+// rank's row block of the whole H).
+int hk_ranges_to_host(hipStream_t st, const double *d_values, int K, double t, const double *d_vectors, int ldv,
+                      int row0_0, int n0, int row0_1, int n1, double *H);
+int d2h_cols_pipelined(hipStream_t st, const double *dM, long rows, int cols, double *H, long ldh, int rings_at_least);
+
 // dense algebra of the regression consumers of an EigenPair (gpr.hip)
 int chol_solve(hipStream_t st, double *dA, int N, double *dB, int nrhs, int *d_flag);
 int gpr_weights(hipStream_t st, const double *d_values, int K, double t, double *d_ls, double *d_l);
@@ -285,7 +293,7 @@ int launch_lae_reg(hipStream_t st, const double *dX, int n, int ldx, int d, cons
 
 }  // namespace flgp
 
-// device-resident EigenPair (include/flgp_hip.h): made in capi.hip, consumed there (H) and in eigenpair.hip
+// device-resident EigenPair (include/flgp_hip.h): made in capi.hip, consumed there (H, copied out by hostcopy.hip) and in eigenpair.hip
 struct flgp_eigenpair {
   flgp::DevBuf values, vectors;   // K, n x K column-major
   int n = 0, K = 0, device = 0;

@@ -1215,6 +1215,62 @@ def test_se_bandwidth_grid(oracle):
     print(f"SE grid: 10 spectra concurrent {t_par*1e3:.1f} ms, sequential {t_seq*1e3:.1f} ms")
 
 
+@pytest.mark.parametrize("root", [False, True])
+@pytest.mark.parametrize("gl", ["rw", "normalized", "cluster-normalized"])
+def test_se_grid_across_its_modes(oracle, gl, root):
+    """The bandwidth grid runs each bandwidth through the Laplacian and spectrum steps of the single-spectrum entries, on
+    a pattern shared by all of them: every gl mode and both root settings against the oracle, the same bits whatever the
+    concurrency, and the same bits from the device entry (called as bench.py calls it), with and without the vectors.
+    (Oracle, on the CPU: sigma_K^2 / sigma_1^2 >= 0.67 for all 18 spectra -- the usable-spectrum floor is far away.)"""
+    n, d, s, r, K, m = 600, 3, 40, 3, 8, 50
+    X, U0, U = make_case(n, d, s, r, seed=808)
+    a2s = np.array([0.1, 1.0, 10.0])
+    models = dict(gl=gl, root=root)
+    pairs, mean = api.se_spectrum_grid(X[:m], X[m:], s, r, K=K, a2s=a2s, models=models, U=U, max_parallel=3)
+    ref, omean = oracle.se_spectrum_grid(X, U, r, K, a2s, gl=gl, root=root)
+    assert abs(mean - omean) <= 1e-13 * omean
+    idx0 = np.arange(n, dtype=np.int32); idx1 = np.arange(m, dtype=np.int32)
+    for ep, (ov, ovec) in zip(pairs, ref):
+        np.testing.assert_allclose(ep.values, ov, rtol=EIG_RTOL, atol=1e-12)
+        H = oracle.hk_from_spectrum(ep.values, ep.vectors, K, 4.0, idx0, idx1)
+        Ho = oracle.hk_from_spectrum(ov, ovec, K, 4.0, idx0, idx1)
+        assert np.abs(H - Ho).max() <= H_RTOL * np.abs(Ho).max()
+    seq, _ = api.se_spectrum_grid(X[:m], X[m:], s, r, K=K, a2s=a2s, models=models, U=U, max_parallel=1)
+    for a, b in zip(pairs, seq):
+        np.testing.assert_array_equal(a.values, b.values)
+        np.testing.assert_array_equal(a.vectors, b.vectors)
+    # the device entry on device copies of the same X / U / sizes
+    L = _lib.lib()
+    dX, dU, dsz = cm(X), cm(U0), torch.from_numpy(U[:, d].copy()).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+
+    def dev_grid(with_vectors):
+        vals = torch.zeros((3, K), dtype=torch.float64, device="cuda:0")
+        vecs = torch.zeros((3, K, n), dtype=torch.float64, device="cuda:0") if with_vectors else None    # block i: n x K column-major
+        iters = (ctypes.c_int * 3)(); dmean = ctypes.c_double(0.0)
+        _lib.check(L.flgp_dev_se_spectrum_grid(st, dX.data_ptr(), n, n, d, dU.data_ptr(), s, s, dsz.data_ptr(), r, K, a2s.ctypes.data, 3,
+                                               gl.encode(), int(root), vals.data_ptr(), vecs.data_ptr() if with_vectors else None,
+                                               ctypes.addressof(dmean), 3, ctypes.addressof(iters)))
+        assert dmean.value == mean and all(it >= 1 for it in iters), list(iters)
+        return vals.cpu().numpy(), vecs.cpu().numpy() if with_vectors else None
+    vals, vecs = dev_grid(True)
+    for i, ep in enumerate(pairs):
+        np.testing.assert_array_equal(vals[i], ep.values)
+        np.testing.assert_array_equal(vecs[i].T, ep.vectors)
+    np.testing.assert_array_equal(dev_grid(False)[0], vals)
+
+
+def test_se_grid_names_the_bandwidth_it_refuses():
+    """The far-anchor case of test_unusable_spectrum_is_refused_on_every_path through the grid: the message is the spectrum
+    step's own, behind the bandwidth it belongs to."""
+    n, d, s, r, m = 600, 3, 40, 3, 50
+    X, U0, U = make_case(n, d, s, r, seed=31)
+    U = U.copy(); U[7, :d] = 1e6
+    with pytest.raises(api.FlgpError) as e:
+        api.se_spectrum_grid(X[:m], X[m:], s, r, K=s, a2s=np.array([1.0]), models=dict(gl="rw"), U=U, max_parallel=1)
+    assert "bandwidth 0" in e.value.message and "null space" in e.value.message, e.value.message
+
+
 def test_unusable_spectrum_is_refused_on_every_path(stages):
     """sigma_K = 0 (K reaches into the null space: here K == s with an anchor that no point chose, and an SE bandwidth
     far below the neighbour distances) has no left vectors on the Gram route.  Every path that goes from the
@@ -1259,7 +1315,7 @@ def test_pipeline_matches_host_entry_points(oracle, stages):
 
 
 def test_pipelined_copy_of_H_is_the_same_matrix(oracle):
-    """The host boundary sends H in column blocks (GEMM, PCIe and the host copy overlapped: csrc/capi.hip,
+    """The host boundary sends H in column blocks (GEMM, PCIe and the host copy overlapped: csrc/hostcopy.hip,
     hk_ranges_to_host).  Forced down to many small blocks -- with a ragged last one -- it must deliver, bit for bit, the
     matrix of the single-copy path, through both entry points that use it."""
     L = _lib.lib()
@@ -1590,6 +1646,26 @@ def test_sharded_covariance_behind_the_c_abi(oracle, devices):
     assert np.abs(Hm - H1).max() <= H_RTOL * np.abs(H1).max()
     with pytest.raises(api.FlgpError):                                  # an error on the ranks comes back, nobody hangs
         api.heat_kernel_covariance_cpp(X[:m], X[m:], s, s + 1, t, K, models, 1, 0.7, U=U, devices=devices)
+
+
+def test_strided_pipelined_copy_in_many_blocks():
+    """A rank's rows of H leave through the pinned ring in column blocks, each column to its own place in the caller's H
+    (csrc/hostcopy.hip, d2h_cols_pipelined).  Two ranks on the one card (the in-process communicator sums in rank order:
+    deterministic); at hk_block_mb = 1 the 3501 / 3500 rows go in 19 blocks of 18 columns, the last one 9 wide, and must
+    land as the same matrix as in one block."""
+    L = _lib.lib()
+    n, d, s, r, K, m, t = 7001, 6, 300, 6, 40, 333, 4.0
+    X, U0, U = make_case(n, d, s, r, seed=77)
+    models = dict(kernel="lae", gl="cluster-normalized", root=True)
+    try:
+        L.flgp_set_tuning(b"hk_block_mb", 512)
+        H0 = api.heat_kernel_covariance_cpp(X[:m], X[m:], s, r, t, K, models, 1, 0.1, U=U, devices=[0, 0])
+        L.flgp_set_tuning(b"hk_block_mb", 1)
+        H1 = api.heat_kernel_covariance_cpp(X[:m], X[m:], s, r, t, K, models, 1, 0.1, U=U, devices=[0, 0])
+    finally:
+        L.flgp_set_tuning(b"hk_block_mb", 512)
+    assert np.abs(H0).max() > 0
+    np.testing.assert_array_equal(H1, H0)
 
 
 def test_one_bad_shard_fails_every_rank_together(oracle):
