@@ -115,6 +115,7 @@ _SIGNATURES = {
     "flgp_dev_jac_set_trace": (None, [P]),
     "flgp_dev_bsg_apply": (c_int, [P, P, c_int, c_int, P, c_int, c_double, c_double, P, P, P, c_size_t, P]),
     "flgp_dev_u_recover_workspace": (c_size_t, [c_int, c_int]),
+    "flgp_dev_u_recover_route": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "flgp_dev_spectrum_usable": (c_int, [P, P, c_int]),
     "flgp_dev_spectrum_usable_route": (c_int, [P, P, c_int, c_int]),
     "flgp_dev_u_recover": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, c_int, P, c_int, P, P]),

@@ -515,6 +515,166 @@ __global__ __launch_bounds__(256) void u_recover_wide_kernel(const int *__restri
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// U-recovery from an LDS-resident column slice.  The kernels above gather the r rows of Vt a point needs from L2 (and, Vt being
+// s K 8 bytes against 4 MB of L2 per XCD, from the Infinity Cache): n r K 8 bytes of 32-byte pieces.  Rows share no anchors
+// with their neighbours, so they cannot be staged by rows -- but W eigen-columns of ALL s anchors are s W 8 bytes, and W = 4
+// fits the 163840 bytes of LDS a workgroup may declare up to s = 5120.  A workgroup keeps one such slice, walks a range of
+// rows with lane = row, gathers from LDS and writes its W output columns in 512-byte pieces; idx / val are streamed once
+// per slice instead (K / W times 12 n r bytes, from L2 where the workgroups of an XCD walk the same rows).
+// Arithmetic as u_recover_kernel: acc = 0; acc += A(i,a) V(idx,k) (a ascending, mul then add); (acc / sigma_k) * scale.
+// ----------------------------------------------------------------------------------------
+#ifndef U_RECOVER_LDS_THREADS
+#define U_RECOVER_LDS_THREADS 1024
+#endif
+#ifndef U_RECOVER_LDS_MIN_N           // rows from which the LDS kernel is the faster one (DESIGN.md section 4 has the measurements)
+#define U_RECOVER_LDS_MIN_N 10000
+#endif
+constexpr int U_LDS_BYTES = 163840;
+
+// eigen-columns per slice: min(4, floor(163840 / (8 s))); 0 = not even one column fits
+static int u_lds_width(int s) {
+  const long w = s >= 1 ? (long)U_LDS_BYTES / (8L * s) : 0;
+  return w > 4 ? 4 : (int)w;
+}
+
+// Vts[slice][j][c] = V(j, slice W + c), columns past K zero: the image a workgroup of u_recover_lds_kernel copies into LDS
+template <int W>
+__global__ __launch_bounds__(256) void transpose_v_slices_kernel(const double *__restrict__ V, int ldv, int s, int K,
+                                                                 double *__restrict__ Vts) {
+  const int j = blockIdx.x * 256 + threadIdx.x, sl = blockIdx.y;
+  if (j >= s) return;
+  double *o = Vts + ((size_t)sl * s + j) * W;
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    const int k = sl * W + c;
+    o[c] = k < K ? V[(size_t)k * ldv + j] : 0.0;
+  }
+}
+
+// where double q of a slice sits in LDS.  W = 4: an anchor is two 16-byte halves and a ds_read_b128 of "the first half" of 16
+// random anchors would use the even ones of the 16 slots of a bank row only; bit 3 of the anchor swaps its halves.
+template <int W> __device__ __forceinline__ int u_lds_slot(int q) { return W == 4 ? q ^ (((q >> 5) & 1) << 1) : q; }
+
+template <int W>
+__global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(const int *__restrict__ ell_idx,
+                                                                              const double *__restrict__ val, int n, int r, int s,
+                                                                              const double *__restrict__ Vts,
+                                                                              const double *__restrict__ eig, int K, double scale,
+                                                                              double *__restrict__ out, int ldo, int rows_per_range) {
+  typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));   // a row starts on 8 bytes (values) / 4 (indices)
+  typedef int i2u __attribute__((ext_vector_type(2), aligned(4)));
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  extern __shared__ __attribute__((aligned(16))) double u_slice[];
+  const int tid = threadIdx.x, T = blockDim.x, sl = blockIdx.y;
+  const double *src = Vts + (size_t)sl * s * W;
+  for (int q = tid; q < s * W; q += T) u_slice[u_lds_slot<W>(q)] = src[q];
+  double sg[W];
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    const int k = sl * W + c;
+    const double e = k < K ? eig[k] : 0.0;
+    sg[c] = __builtin_sqrt(e > 0.0 ? e : 0.0);
+  }
+  __syncthreads();
+  const long i_lo = (long)blockIdx.x * rows_per_range;
+  const long i_hi = (i_lo + rows_per_range < n) ? i_lo + rows_per_range : n;
+  const long last_pair = (long)n * r - 2;       // (n r >= 2: the route rule)
+  // Eight entries of a row as four pairs: a 16-byte load of values and an 8-byte load of indices per lane, the pair starting
+  // at the even slot a of row i.  The pair of an odd r's last slot reaches into the next row, and in the last row of all it
+  // is moved back by one (`up` below).  Loads are unconditional, so that the number in flight is the same on every path and
+  // the wait counts stay tight; what a lane has no use for (past its row, past its range) is read from ONE address, the
+  // range's first entry, which costs the cache a single line look-up.
+  struct Chunk { double z0[4], z1[4]; int j0[4], j1[4]; };
+  auto fetch = [&](long i, int ch) {
+    Chunk c;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int a = 8 * ch + 2 * u;
+      long b = (i < i_hi && a < r) ? i * r + a : i_lo * r;
+      b = b < last_pair ? b : last_pair;
+      const d2u z = *(const d2u *)(val + b);
+      const i2u j = *(const i2u *)(ell_idx + b);
+      c.z0[u] = z[0]; c.z1[u] = z[1];
+      c.j0[u] = j[0]; c.j1[u] = j[1];
+    }
+    return c;
+  };
+  // one entry of a chunk, slot a = 8 ch + 2 u + h of row i: its value and the W doubles of its anchor
+  auto gather = [&](const Chunk &cur, int u, int h, bool moved, double &z, double (&v)[W]) {
+    const bool up = h || moved;
+    const int id = up ? cur.j1[u] : cur.j0[u];
+    z = up ? cur.z1[u] : cur.z0[u];
+    if constexpr (W == 4) {
+      const int x = ((id >> 3) & 1) << 1;
+      const d2 lo = *(const d2 *)&u_slice[id * 4 + x], hi = *(const d2 *)&u_slice[id * 4 + (x ^ 2)];
+      v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
+    } else if constexpr (W == 2) {
+      const d2 lo = *(const d2 *)&u_slice[id * 2];
+      v[0] = lo[0]; v[1] = lo[1];
+    } else {
+#pragma unroll
+      for (int c = 0; c < W; ++c) v[c] = u_slice[id * W + c];
+    }
+  };
+  double acc[W];
+#pragma unroll
+  for (int c = 0; c < W; ++c) acc[c] = 0.0;
+  const int nch = (r + 7) >> 3;
+  // chunk ch of row i: its entries in ascending order; behind the row's last chunk the W results are stored
+  auto apply = [&](const Chunk &cur, long i, int ch) {
+    const int left = r - ch * 8;
+    if (left >= 8) {                                                   // (uniform) a whole chunk: its eight gathers, then the sums
+      double z[8], v[8][W];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gather(cur, e >> 1, e & 1, false, z[e], v[e]);   // (an entry follows every pair: none moved)
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int c = 0; c < W; ++c) acc[c] += z[e] * v[e][c];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool moved = i * r + ch * 8 + 2 * u > last_pair;         // only the last slot of the last row, r odd
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          if (2 * u + h < left) {
+            double z, v[W];
+            gather(cur, u, h, moved, z, v);
+#pragma unroll
+            for (int c = 0; c < W; ++c) acc[c] += z * v[c];
+          }
+      }
+    }
+    if (ch == nch - 1) {
+      if (i < i_hi) {
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+          const int k = sl * W + c;
+          if (k < K) out[(size_t)k * ldo + i] = sg[c] > 0.0 ? (acc[c] / sg[c]) * scale : 0.0;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < W; ++c) acc[c] = 0.0;
+    }
+  };
+  // The (row, chunk) steps of a lane in order, two buffers: the loads of step t + 1 fly while step t is applied.  (One buffer
+  // handed on at the end of the step would wait for them at the hand-over.)
+  const long nit = i_hi > i_lo ? (i_hi - i_lo + T - 1) / T : 0;
+  const long steps = nit * nch;
+  long ia = i_lo + tid; int cha = 0;                                   // step t
+  auto next = [&](long &i, int &ch) { if (++ch == nch) { ch = 0; i += T; } };
+  Chunk A = fetch(ia, cha), B;
+  for (long t = 0; t < steps; t += 2) {
+    long ib = ia; int chb = cha; next(ib, chb);                        // step t + 1 (past the last step: masked loads)
+    B = fetch(ib, chb);
+    apply(A, ia, cha);
+    ia = ib; cha = chb; next(ia, cha);
+    A = fetch(ia, cha);
+    if (t + 1 < steps) apply(B, ib, chb);
+  }
+}
+
 __global__ void values_out_kernel(const double *__restrict__ eig, int K, int root, double *__restrict__ values) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
@@ -718,7 +878,52 @@ extern "C" int flgp_dev_sym_unpack(void *stream, const double *d_packed, int s, 
   return check_launch("sym_unpack_kernel");
 }
 
-extern "C" size_t flgp_dev_u_recover_workspace(int s, int K) { return sizeof(double) * (size_t)s * K + 256; }
+// the transposed V of the gather kernels (s K doubles), or the slices of the LDS kernel with the last one filled up
+extern "C" size_t flgp_dev_u_recover_workspace(int s, int K) {
+  const int w = u_lds_width(s);
+  const size_t cols = w >= 1 && K >= 1 ? (size_t)ceil_div(K, w) * w : (size_t)(K > 0 ? K : 0);
+  return sizeof(double) * (size_t)(s > 0 ? s : 0) * cols + 256;
+}
+
+// Which kernel flgp_dev_u_recover runs: 0 u_recover_kernel (no workspace), 1 tiled, 2 wide<2,64>, 3 wide<4,32>, 4 LDS slices.
+// The LDS kernel needs the workspace, a slice that fits (s <= 20480) and n >= U_RECOVER_LDS_MIN_N, the smallest n at which
+// it was measured against the gather kernels (and was faster, as at every larger one).
+extern "C" int flgp_dev_u_recover_route(int n, int r, int s, int K, int has_work) {
+  if (!has_work) return 0;
+  if (u_lds_width(s) >= 1 && n >= U_RECOVER_LDS_MIN_N && (long)n * r >= 2) return 4;      // (two entries: the kernel loads pairs)
+  return K % 4 == 0 ? 3 : K % 2 == 0 ? 2 : 1;
+}
+
+static int num_cus() {
+  static int cus[16] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
+  if (!cus[dev]) {
+    int c = 0;
+    cus[dev] = (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && c > 0) ? c : 256;
+  }
+  return cus[dev];
+}
+
+template <int W>
+static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
+                                int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
+                                double *d_work) {
+  const int slices = ceil_div(K, W);
+  hipLaunchKernelGGL((transpose_v_slices_kernel<W>), dim3(ceil_div(s, 256), slices), dim3(256), 0, st, dV, ldv, s, K, d_work);
+  FLGP_TRY(check_launch("transpose_v_slices_kernel"));
+  // about one workgroup per CU, one round; a range is whole waves of rows
+  int ranges = num_cus() / slices;
+  if (ranges < 1) ranges = 1;
+  int rows = ceil_div(ceil_div(n, ranges), 64) * 64;
+  ranges = ceil_div(n, rows);
+  const size_t lds = sizeof(double) * (size_t)s * W;
+  if (lds > 48 * 1024)
+    FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((u_recover_lds_kernel<W>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st, d_ell_idx, d_ell_val,
+                     n, r, s, d_work, d_eig, K, scale, d_vectors, ldo, rows);
+  return FLGP_OK;
+}
 
 extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r,
                                   const double *dV, int ldv, int s, const double *d_eig, int K, double scale,
@@ -727,7 +932,16 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
   FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && K >= 1 && ldo >= n, "u_recover: bad shape");
   if (n > 0) {
     ProfScope ps("u_recover_kernel", st, 12.0 * (double)n * r + 8.0 * (double)s * K + 8.0 * (double)n * K);
-    if (d_work) {
+    const int route = flgp_dev_u_recover_route(n, r, s, K, d_work != nullptr);
+    if (route == 4) {
+      switch (u_lds_width(s)) {
+#define U_LDS_CASE(Wv)                                                                                                         \
+  case Wv: FLGP_TRY(u_recover_lds_launch<Wv>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)); break
+        U_LDS_CASE(1); U_LDS_CASE(2); U_LDS_CASE(3);
+        default: U_LDS_CASE(4);
+#undef U_LDS_CASE
+      }
+    } else if (d_work) {
       hipLaunchKernelGGL(transpose_v_kernel, dim3(ceil_div(s, 32), ceil_div(K, 32)), dim3(256), 0, st, dV, ldv, s, K,
                          d_work);
       if (K % 4 == 0) {
