@@ -77,6 +77,14 @@ _SIGNATURES = {
     "flgp_nystrom_eigenpair_resident": (c_int, [P, c_int, c_int, P, c_int, c_double, c_int, P]),
     "flgp_heat_kernel_covariance": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_double, c_int,
                                             c_char_p, c_char_p, c_int, c_double, P]),
+    "flgp_nystrom_grid_create": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, P]),
+    "flgp_nystrom_grid_dims": (c_int, [P, P, P, P, P, P]),
+    "flgp_nystrom_grid_values": (c_int, [P, P, P]),
+    "flgp_nystrom_grid_free": (None, [P]),
+    "flgp_nystrom_grid_extend": (c_int, [P, c_int, P, c_int, P, P]),
+    "flgp_nystrom_grid_extend_resident": (c_int, [P, c_int, P, c_int, P]),
+    "flgp_nystrom_grid_extend_all": (c_int, [P, P, c_int, P]),
+    "flgp_nystrom_grid_extend_all_resident": (c_int, [P, P, c_int, P]),
     "flgp_se_spectrum_grid": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P, c_int]),
     "flgp_lae_eigenmap": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, P, P]),
     "flgp_dev_se_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P,
@@ -85,6 +93,9 @@ _SIGNATURES = {
     "flgp_dev_anchor_dpad": (c_int, [c_int]),
     "flgp_dev_anchor_rows": (c_int, [c_int]),
     "flgp_dev_anchor_prep": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "flgp_dev_nystrom_grid_create": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P]),
+    "flgp_dev_nystrom_grid_extend": (c_int, [P, P, c_int, P, c_int, c_int, P, P, c_int]),
+    "flgp_dev_nystrom_grid_extend_all": (c_int, [P, P, P, c_int, c_int, P, P, c_int]),
     "flgp_dev_nystrom_eigenpair": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, c_double, c_int, P, P, c_int]),
     "flgp_dev_kmeans_lloyd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P]),
     "flgp_dev_kmeans_init": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, c_int]),

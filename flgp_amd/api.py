@@ -538,6 +538,114 @@ def nystrom_eigenpair_cpp(X, U, a2, K, resident=False):
     return EigenPair(values, vectors)
 
 
+_DEFAULT_A2S = np.exp(np.linspace(np.log(0.1), np.log(10.0), 10))      # R/Fit.R:187-189
+
+
+class NystromGrid:
+    """The anchor side of the ``fit_nystrom_*`` bandwidth loop (reference src/Fit.cpp:244-333) on the device, for l
+    bandwidths: D_UU and its mean once, per bandwidth the top-K eigenpairs of W_UU.  ``extend`` / ``extend_all`` are the
+    Nystrom extension of a row set -- no eigensolve; their results are bit for bit those of
+    :func:`nystrom_eigenpair_cpp` at the same bandwidth.  Made by :func:`nystrom_spectrum_grid`."""
+
+    def __init__(self, handle, a2s, s, d, K, workers=1):
+        self._h = handle
+        self.a2s = np.array(a2s, dtype=np.float64).reshape(-1)
+        self.s, self.d, self.l, self.K, self.workers = int(s), int(d), self.a2s.size, int(K), int(workers)
+        self._values = None
+        self._mean = None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the Nystrom grid has been freed")
+        return self._h
+
+    def _fetch(self):
+        if self._values is None:
+            values = np.zeros((self.l, self.K)); mean = ctypes.c_double()
+            check(_lib.lib().flgp_nystrom_grid_values(self._handle(), _ptr(values), ctypes.byref(mean)))
+            self._values, self._mean = values, mean.value
+
+    @property
+    def values(self):
+        """l x K: row i holds the K eigenvalues of bandwidth i, descending."""
+        self._handle(); self._fetch()
+        return self._values
+
+    @property
+    def distances_mean(self):
+        """The mean squared distance between anchors (``distances_UU.mean()``, src/Fit.cpp:248)."""
+        self._handle(); self._fetch()
+        return self._mean
+
+    def _rows(self, X):
+        h = self._handle()
+        X = _f64(X, "X")
+        if X.shape[1] != self.d:
+            raise ValueError(f"X has {X.shape[1]} columns but the grid's anchors have {self.d}")
+        if X.shape[0] < 1:
+            raise ValueError("X must have at least one row")
+        return h, X
+
+    def extend(self, i, X, resident=False):
+        """EigenPair of bandwidth ``i`` on the rows of ``X`` (a :class:`ResidentEigenPair` with ``resident``)."""
+        h, X = self._rows(X)
+        i = int(i)
+        if not 0 <= i < self.l:
+            raise IndexError(f"bandwidth index {i} outside 0..{self.l - 1}")
+        n = X.shape[0]
+        if resident:
+            out = ctypes.c_void_p()
+            check(_lib.lib().flgp_nystrom_grid_extend_resident(h, i, _ptr(X), n, ctypes.byref(out)))
+            return ResidentEigenPair(out)
+        values = np.zeros(self.K); vectors = np.zeros((n, self.K), order="F")
+        check(_lib.lib().flgp_nystrom_grid_extend(h, i, _ptr(X), n, _ptr(values), _ptr(vectors)))
+        return EigenPair(values, vectors)
+
+    def extend_all(self, X, resident=False):
+        """The l EigenPairs on the rows of ``X`` (the training rows inside the grid): one distance pass for all
+        bandwidths.  Returns a list, bandwidth i at position i."""
+        h, X = self._rows(X)
+        n = X.shape[0]
+        if resident:
+            out = (ctypes.c_void_p * self.l)()
+            check(_lib.lib().flgp_nystrom_grid_extend_all_resident(h, _ptr(X), n, ctypes.addressof(out)))
+            return [ResidentEigenPair(ctypes.c_void_p(out[i])) for i in range(self.l)]
+        vectors = np.zeros((self.l, self.K, n))      # block i: n x K column-major
+        check(_lib.lib().flgp_nystrom_grid_extend_all(h, _ptr(X), n, _ptr(vectors)))
+        vals = self.values
+        return [EigenPair(vals[i].copy(), np.asfortranarray(vectors[i].T)) for i in range(self.l)]
+
+    def free(self):
+        if self._h is not None:
+            _lib.lib().flgp_nystrom_grid_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def nystrom_spectrum_grid(U, a2s=None, K=None, max_parallel=10):
+    """The anchor side of the ``fit_nystrom_*`` drivers for the bandwidths ``a2s`` (default: the ten of R/Fit.R:187-189).
+    ``U`` is s x d (cluster-size column already dropped).  Returns a :class:`NystromGrid`; see include/flgp_hip.h for
+    how ``max_parallel`` is clipped; the default is the measured choice (ten concurrent dense solves: 1.6x at s = 5000,
+    1.3x at s = 1e4 over one worker) and changes no bit of the result."""
+    U = _f64(U, "U")
+    a2s = np.ascontiguousarray(_DEFAULT_A2S if a2s is None else a2s, dtype=np.float64).reshape(-1)
+    if a2s.size < 1:
+        raise ValueError("a2s must hold at least one bandwidth")
+    s, d = U.shape
+    if K is None or not 1 <= int(K) <= s:
+        raise ValueError(f"need 1 <= K <= s (K={K}, s={s})")
+    h = ctypes.c_void_p()
+    check(_lib.lib().flgp_nystrom_grid_create(_ptr(U), s, d, _ptr(a2s), a2s.size, int(K), int(max_parallel), ctypes.byref(h)))
+    workers = ctypes.c_int()
+    check(_lib.lib().flgp_nystrom_grid_dims(h, None, None, None, None, ctypes.byref(workers)))
+    return NystromGrid(h, a2s, s, d, K, workers.value)
+
+
 def kmeans_lloyd(X, s, init_rows, iter_max=100):
     """Lloyd k-means on the device (include/flgp_hip.h ``flgp_kmeans_lloyd``).  ``init_rows``: (nstart, s) or (s,) row
     indices of the starting centres.  Returns (U (s x (d+1), sizes last), rounds, tot_withinss)."""

@@ -644,6 +644,136 @@ extern "C" int flgp_nystrom_eigenpair_resident(const double *X, int n, int d, co
   return FLGP_OK;
 }
 
+// ---- the bandwidth grid of the fit_nystrom_* drivers (src/Fit.cpp:244-333): anchor side once, extension per row set
+extern "C" int flgp_nystrom_grid_create(const double *U, int s, int d, const double *a2s, int l, int K, int max_parallel,
+                                        flgp_nystrom_grid **out) {
+  FLGP_REQUIRE(out, "nystrom_grid_create: null pointer");
+  *out = nullptr;
+  FLGP_REQUIRE(U && a2s, "nystrom_grid_create: null pointer");
+  FLGP_REQUIRE(l >= 1, "nystrom_grid_create: need at least one bandwidth (l=%d)", l);
+  FLGP_REQUIRE(d >= 1 && s >= 2 && K >= 1 && K <= s, "nystrom_grid_create: bad shape (d=%d s=%d K=%d)", d, s, K);
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dU;
+  FLGP_TRY(dU.alloc(sizeof(double) * (size_t)s * d));
+  FLGP_TRY(h2d(dU.p, U, sizeof(double) * (size_t)s * d, st.s));
+  return flgp_dev_nystrom_grid_create(st.s, dU.as<double>(), s, s, d, a2s, l, K, max_parallel, out);
+}
+
+extern "C" int flgp_nystrom_grid_dims(const flgp_nystrom_grid *grid, int *s, int *d, int *l, int *K, int *workers) {
+  FLGP_REQUIRE(grid, "nystrom_grid_dims: null handle");
+  if (s) *s = grid->s;
+  if (d) *d = grid->d;
+  if (l) *l = grid->l;
+  if (K) *K = grid->K;
+  if (workers) *workers = grid->workers;
+  return FLGP_OK;
+}
+
+extern "C" int flgp_nystrom_grid_values(const flgp_nystrom_grid *grid, double *values, double *distances_mean_out) {
+  FLGP_REQUIRE(grid, "nystrom_grid_values: null handle");
+  if (distances_mean_out) *distances_mean_out = grid->mean;
+  if (!values) return FLGP_OK;
+  Stream st;
+  FLGP_TRY(st.create());
+  FLGP_HIP(hipMemcpy2DAsync(values, sizeof(double) * (size_t)grid->K, grid->values.p, sizeof(double) * grid->vs,
+                            sizeof(double) * (size_t)grid->K, grid->l, hipMemcpyDeviceToHost, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+extern "C" void flgp_nystrom_grid_free(flgp_nystrom_grid *grid) { delete grid; }
+
+namespace {
+// the rows of X on the device and the vectors of `count` bandwidths (i0 < 0: all of them) in `dvec[.]`
+int nystrom_grid_extend_host(hipStream_t st, const flgp_nystrom_grid *grid, int i0, const double *X, int n, DevBuf *dvec) {
+  FLGP_REQUIRE(grid, "nystrom_grid_extend: null handle");
+  FLGP_REQUIRE(X, "nystrom_grid_extend: null pointer");
+  FLGP_REQUIRE(n >= 1, "nystrom_grid_extend: need n >= 1 (n=%d)", n);
+  FLGP_REQUIRE(i0 < grid->l, "nystrom_grid_extend: bandwidth %d outside 0..%d", i0, grid->l - 1);
+  const int d = grid->d, K = grid->K, cnt = i0 < 0 ? grid->l : 1;
+  DevBuf dX;
+  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)n * d));
+  FLGP_TRY(h2d(dX.p, X, sizeof(double) * (size_t)n * d, st));
+  std::vector<double *> blocks(cnt);
+  for (int i = 0; i < cnt; ++i) {
+    FLGP_TRY(dvec[i].alloc(sizeof(double) * (size_t)n * K));
+    blocks[i] = dvec[i].as<double>();
+  }
+  if (i0 >= 0) return flgp_dev_nystrom_grid_extend(st, grid, i0, dX.as<double>(), n, n, nullptr, blocks[0], n);
+  int dev = -1;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == grid->device, "nystrom_grid_extend_all: the grid lives on device %d, the current device is %d", grid->device, dev);
+  return nystrom_grid_extend_all(st, grid, dX.as<double>(), n, n, blocks.data(), n);
+}
+}  // namespace
+
+extern "C" int flgp_nystrom_grid_extend(const flgp_nystrom_grid *grid, int i, const double *X, int n, double *values,
+                                        double *vectors) {
+  FLGP_REQUIRE(grid && vectors, "nystrom_grid_extend: null pointer");
+  FLGP_REQUIRE(i >= 0 && i < grid->l, "nystrom_grid_extend: bandwidth %d outside 0..%d", i, grid->l - 1);
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dvec;
+  FLGP_TRY(nystrom_grid_extend_host(st.s, grid, i, X, n, &dvec));
+  if (values) FLGP_TRY(d2h(values, grid->values_of(i), sizeof(double) * (size_t)grid->K, st.s));
+  FLGP_TRY(d2h(vectors, dvec.p, sizeof(double) * (size_t)n * grid->K, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+extern "C" int flgp_nystrom_grid_extend_resident(const flgp_nystrom_grid *grid, int i, const double *X, int n,
+                                                 flgp_eigenpair **out) {
+  FLGP_REQUIRE(out, "nystrom_grid_extend_resident: null pointer");
+  *out = nullptr;
+  FLGP_REQUIRE(grid, "nystrom_grid_extend_resident: null handle");
+  FLGP_REQUIRE(i >= 0 && i < grid->l, "nystrom_grid_extend: bandwidth %d outside 0..%d", i, grid->l - 1);
+  Stream st;
+  FLGP_TRY(st.create());
+  std::unique_ptr<flgp_eigenpair> ep;
+  FLGP_TRY(new_eigenpair(n, grid->K, ep));
+  FLGP_TRY(ep->values.alloc(sizeof(double) * (size_t)grid->K));
+  FLGP_TRY(nystrom_grid_extend_host(st.s, grid, i, X, n, &ep->vectors));
+  FLGP_HIP(hipMemcpyAsync(ep->values.p, grid->values_of(i), sizeof(double) * (size_t)grid->K, hipMemcpyDeviceToDevice, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  *out = ep.release();
+  return FLGP_OK;
+}
+
+extern "C" int flgp_nystrom_grid_extend_all(const flgp_nystrom_grid *grid, const double *X, int n, double *vectors) {
+  FLGP_REQUIRE(grid && vectors, "nystrom_grid_extend_all: null pointer");
+  Stream st;
+  FLGP_TRY(st.create());
+  std::vector<DevBuf> dvec(grid->l);
+  FLGP_TRY(nystrom_grid_extend_host(st.s, grid, -1, X, n, dvec.data()));
+  const size_t blk = (size_t)n * grid->K;
+  for (int i = 0; i < grid->l; ++i) FLGP_TRY(d2h(vectors + (size_t)i * blk, dvec[i].p, sizeof(double) * blk, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+extern "C" int flgp_nystrom_grid_extend_all_resident(const flgp_nystrom_grid *grid, const double *X, int n,
+                                                     flgp_eigenpair **out) {
+  FLGP_REQUIRE(grid && out, "nystrom_grid_extend_all_resident: null pointer");
+  const int l = grid->l, K = grid->K;
+  for (int i = 0; i < l; ++i) out[i] = nullptr;
+  Stream st;
+  FLGP_TRY(st.create());
+  std::vector<std::unique_ptr<flgp_eigenpair>> eps(l);
+  std::vector<DevBuf> dvec(l);
+  FLGP_TRY(nystrom_grid_extend_host(st.s, grid, -1, X, n, dvec.data()));
+  for (int i = 0; i < l; ++i) {
+    FLGP_TRY(new_eigenpair(n, K, eps[i]));
+    FLGP_TRY(eps[i]->values.alloc(sizeof(double) * (size_t)K));
+    FLGP_HIP(hipMemcpyAsync(eps[i]->values.p, grid->values_of(i), sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, st.s));
+    DevBuf &a = eps[i]->vectors, &b = dvec[i];      // the buffer changes owner: no copy
+    std::swap(a.p, b.p); std::swap(a.owned, b.owned); std::swap(a.cap, b.cap); std::swap(a.dev, b.dev);
+  }
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  for (int i = 0; i < l; ++i) out[i] = eps[i].release();
+  return FLGP_OK;
+}
+
 extern "C" int flgp_eigenpair_dims(const flgp_eigenpair *ep, int *n, int *K) {
   FLGP_REQUIRE(ep, "eigenpair_dims: null handle");
   if (n) *n = ep->n;

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 #include "../../include/flgp_hip.h"
 
 namespace flgp {
@@ -147,7 +148,11 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
                 const double *E2, struct GemmFusedReduce *fused = nullptr,
-                const struct GemmPair *pair = nullptr);
+                const struct GemmPair *pair = nullptr, int force_split = 0);
+// The number of split-K planes gemm_launch chooses for this shape and workspace.  `force_split` > 0 makes a launch take
+// that number instead (the workspace must hold it): a row block of a product then adds every element's terms in the
+// order the whole product does, whatever the block's own tile count would have chosen.
+int gemm_plan_split(int M, int N, int Kd, size_t work_elems);
 // `pair`: a second product C2 = alpha A2 B2 of the same shape and strides in the same launch (no E / E2, never split):
 // two of the solver's s x b rotations fill the chip where one leaves its fixed costs exposed.
 struct GemmPair { const double *A2, *B2; double *C2; };
@@ -297,4 +302,29 @@ int launch_lae_reg(hipStream_t st, const double *dX, int n, int ldx, int d, cons
 struct flgp_eigenpair {
   flgp::DevBuf values, vectors;   // K, n x K column-major
   int n = 0, K = 0, device = 0;
+};
+
+struct flgp_nystrom_grid;
+namespace flgp {
+// Nystrom extension from a grid's anchor side (nystrom.hip); both synchronise `st`.  d_vectors[i] (extend_all): the n x K
+// block of bandwidth i (ldv).
+int nystrom_grid_extend(hipStream_t st, const flgp_nystrom_grid *G, int i, const double *dX, int n, int ldx, double *d_vectors,
+                        int ldv);
+int nystrom_grid_extend_all(hipStream_t st, const flgp_nystrom_grid *G, const double *dX, int n, int ldx,
+                            double *const *d_vectors, int ldv);
+}  // namespace flgp
+
+// anchor side of the Nystrom bandwidth grid (include/flgp_hip.h): made and consumed in nystrom.hip
+struct flgp_nystrom_grid {
+  flgp::DevBuf U, Ut, uu;         // the anchors (s x d column-major, ld s) and their padded panel
+  flgp::DevBuf values, rsu, eigv; // per bandwidth: K values, s factors 1 / (rs_U + 1e-9), s x K pre-scaled eigenvectors
+  std::vector<double> a2s, inv_c; // l bandwidths and 1 / (a2 mean)
+  double mean = 0.0;
+  int s = 0, d = 0, dpad = 0, l = 0, K = 0, device = 0, workers = 0;
+  // bandwidth i's block starts at i * vs / i * rs / i * es doubles: strides rounded up to 256 bytes, so that every
+  // block is aligned like an allocation of its own (what the single-bandwidth entry handed to the eigensolver)
+  size_t vs = 0, rs = 0, es = 0;
+  const double *values_of(int i) const { return (const double *)values.p + (size_t)i * vs; }
+  const double *rsu_of(int i) const { return (const double *)rsu.p + (size_t)i * rs; }
+  const double *eigv_of(int i) const { return (const double *)eigv.p + (size_t)i * es; }
 };

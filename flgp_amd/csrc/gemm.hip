@@ -562,10 +562,29 @@ int gemm_split_limit(int Kd, int ntiles, int gk, bool tile64) {
   return nsplit < maxk ? nsplit : maxk;
 }
 
+// the split-K planes gemm_launch takes for an M x N x Kd product with a workspace of work_elems doubles (the final k
+// ranges: two products with the same Kd and the same answer here add every element's terms in the same order)
+int gemm_plan_split(int M, int N, int Kd, size_t work_elems) {
+  if (M <= 0 || N <= 0) return 1;
+  int gbt = GB;
+  if (ceil_div(M, GB) * ceil_div(N, GB) < tuning("gemm_tile64_below", 200)) gbt = 64;
+  const int ntiles = ceil_div(M, gbt) * ceil_div(N, gbt);
+  const size_t per = (size_t)M * N;
+  int nsplit = 1;
+  if (ntiles < 256 && Kd >= 8 * GK) {
+    nsplit = gemm_split_limit(Kd, ntiles, GK, gbt == 64);
+    if ((size_t)nsplit * per > work_elems) nsplit = (int)(work_elems / per);
+    if (nsplit < 1) nsplit = 1;
+  }
+  int klen = ceil_div(Kd > 0 ? Kd : 1, nsplit);
+  klen = (klen + GK - 1) / GK * GK;
+  return ceil_div(Kd > 0 ? Kd : 1, klen);
+}
+
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
-                const double *E2, GemmFusedReduce *fused, const GemmPair *pair) {
+                const double *E2, GemmFusedReduce *fused, const GemmPair *pair, int force_split) {
   if (fused) fused->done = false;
   if (pair && (E || E2 || fused)) { set_error("gemm: a paired product takes no E / E2 / fused reduction"); return FLGP_ERR_INVALID; }
   if (M <= 0 || N <= 0) return FLGP_OK;
@@ -595,11 +614,13 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
   if (ceil_div(g.M, GB) * ceil_div(g.N, GB) < tuning("gemm_tile64_below", 200)) gbt = 64;
   const int ntiles = ceil_div(g.M, gbt) * ceil_div(g.N, gbt);
   const size_t per = (size_t)g.M * g.N;   // one partial plane
-  int nsplit = 1;
-  if (work && !pair && ntiles < 256 && Kd >= 8 * GK) {
-    nsplit = gemm_split_limit(Kd, ntiles, GK, gbt == 64);
-    if ((size_t)nsplit * per > work_elems) nsplit = (int)(work_elems / per);
-    if (nsplit < 1) nsplit = 1;
+  int nsplit = (work && !pair) ? gemm_plan_split(M, N, Kd, work_elems) : 1;
+  if (force_split > 0) {     // the caller's plan (of a larger product that this one is a row block of): the same chains per element
+    if (pair || (force_split > 1 && (!work || (size_t)force_split * per > work_elems))) {
+      set_error("gemm: a forced split of %d planes needs a workspace of %zu doubles", force_split, (size_t)force_split * per);
+      return FLGP_ERR_INVALID;
+    }
+    nsplit = force_split;
   }
   int klen = ceil_div(Kd > 0 ? Kd : 1, nsplit);
   klen = (klen + GK - 1) / GK * GK;

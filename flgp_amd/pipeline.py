@@ -188,6 +188,60 @@ class HipStages:
                                                          values.data_ptr(), vectors.data_ptr(), n))
         return values, vectors
 
+    # The Nystrom bandwidth grid (include/flgp_hip.h, flgp_dev_nystrom_grid_*).  The stage set holds one handle per
+    # `owner` (the path object that asked for it): making a new grid for an owner gives its previous one back.
+    def nystrom_grid(self, U, a2s, K, max_parallel=10, owner=None):  # U: (d, s); returns values (l, K) and the mean of D_UU
+        import ctypes
+        import numpy as np
+        self.nystrom_grid_free(owner)
+        d, s = U.shape
+        a2 = np.ascontiguousarray(a2s, dtype=np.float64).reshape(-1)
+        h = ctypes.c_void_p(); mean = ctypes.c_double()
+        _lib.check(self.L.flgp_dev_nystrom_grid_create(self._st(), U.data_ptr(), s, s, d, a2.ctypes.data, a2.size, int(K),
+                                                       int(max_parallel), ctypes.byref(h)))
+        self.__dict__.setdefault("_nys_grids", {})[id(owner)] = (h, d, a2.size, int(K))
+        values = np.zeros((a2.size, int(K)))
+        _lib.check(self.L.flgp_nystrom_grid_values(h, values.ctypes.data, ctypes.byref(mean)))
+        return torch.from_numpy(values).to(self.device), mean.value
+
+    def _nystrom_grid_of(self, owner, X):
+        g = getattr(self, "_nys_grids", {}).get(id(owner))
+        if g is None:
+            raise ValueError("no Nystrom grid: call nystrom_grid first")
+        if X.shape[0] != g[1]:
+            raise ValueError(f"X has {X.shape[0]} columns but the grid's anchors have {g[1]}")
+        return g
+
+    def nystrom_grid_extend(self, i, X, owner=None):  # X: (d, n_loc) -> vectors (K, n_loc) of bandwidth i
+        h, _, l, K = self._nystrom_grid_of(owner, X)
+        if not 0 <= int(i) < l:
+            raise IndexError(f"bandwidth index {i} outside 0..{l - 1}")
+        n = X.shape[1]
+        vectors = self.empty((K, max(n, 1)))
+        if n:
+            _lib.check(self.L.flgp_dev_nystrom_grid_extend(self._st(), h, int(i), X.data_ptr(), n, n, None, vectors.data_ptr(), n))
+        return vectors
+
+    def nystrom_grid_extend_all(self, X, owner=None):  # X: (d, n_loc) -> vectors (l, K, n_loc)
+        h, _, l, K = self._nystrom_grid_of(owner, X)
+        n = X.shape[1]
+        vectors = self.empty((l, K, max(n, 1)))
+        if n:
+            _lib.check(self.L.flgp_dev_nystrom_grid_extend_all(self._st(), h, X.data_ptr(), n, n, None, vectors.data_ptr(), n))
+        return vectors
+
+    def nystrom_grid_free(self, owner=None):
+        g = getattr(self, "_nys_grids", {}).pop(id(owner), None)
+        if g is not None:
+            self.L.flgp_nystrom_grid_free(g[0])
+
+    def __del__(self):
+        try:
+            for g in getattr(self, "_nys_grids", {}).values():
+                self.L.flgp_nystrom_grid_free(g[0])
+        except Exception:
+            pass
+
     # -- plumbing used by the driver (no arithmetic of the path)
     def bincount(self, idx_row, s):
         return torch.bincount(idx_row.to(torch.int64), minlength=s).to(torch.float64)
@@ -401,3 +455,25 @@ class NystromPath(HeatKernelPath):
         """X_loc: (d, n_loc) local rows; U: (d, s) anchors as returned by :meth:`gather_anchors`.
         Returns (values (K,), vectors (K, n_loc))."""
         return self.stages.nystrom(X_loc, U, a2, K)
+
+    def run_nystrom_grid(self, X_train_loc, U, a2s, K: int, max_parallel: int = 10):
+        """The bandwidth loop of the fit_nystrom_* drivers (src/Fit.cpp:244-333): the anchor side for all of ``a2s``
+        (replicated per rank, like :meth:`run_nystrom`'s) and the extension of the local training rows for every
+        bandwidth.  Returns (values (l, K), vectors (l, K, n_loc), mean of D_UU).  The stage set keeps this path's
+        grid until the next call or :meth:`free_grid`; :meth:`extend_chosen` extends the winner to any local rows
+        without another eigensolve."""
+        values, mean = self.stages.nystrom_grid(U, a2s, K, max_parallel, owner=self)
+        return values, self.stages.nystrom_grid_extend_all(X_train_loc, owner=self), mean
+
+    def extend_chosen(self, i: int, X_loc):
+        """vectors (K, n_loc) of bandwidth ``i`` of this path's grid (the after-loop step, src/Fit.cpp:321-325)."""
+        return self.stages.nystrom_grid_extend(i, X_loc, owner=self)
+
+    def free_grid(self):
+        self.stages.nystrom_grid_free(owner=self)
+
+    def __del__(self):
+        try:
+            self.free_grid()
+        except Exception:
+            pass
