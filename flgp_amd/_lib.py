@@ -85,6 +85,13 @@ _SIGNATURES = {
     "flgp_nystrom_grid_extend_resident": (c_int, [P, c_int, P, c_int, P]),
     "flgp_nystrom_grid_extend_all": (c_int, [P, P, c_int, P]),
     "flgp_nystrom_grid_extend_all_resident": (c_int, [P, P, c_int, P]),
+    "flgp_heat_kernel_spectrum_model": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, c_char_p,
+                                                c_int, c_double, P, P]),
+    "flgp_spectrum_model_dims": (c_int, [P, P, P, P, P, P, P, P, P]),
+    "flgp_spectrum_model_to_host": (c_int, [P, P, P, P, P, P, P]),
+    "flgp_spectrum_model_extend": (c_int, [P, P, c_int, P]),
+    "flgp_spectrum_model_extend_resident": (c_int, [P, P, c_int, P, P, c_int, P]),
+    "flgp_spectrum_model_free": (None, [P]),
     "flgp_se_spectrum_grid": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P, c_int]),
     "flgp_lae_eigenmap": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, P, P]),
     "flgp_dev_se_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P,
@@ -116,6 +123,8 @@ _SIGNATURES = {
     "flgp_dev_col_scale": (c_int, [P, P, P, c_int, c_int, P, P, c_int]),
     "flgp_dev_row_normalize": (c_int, [P, P, c_int, c_int]),
     "flgp_dev_col_scale_row_normalize": (c_int, [P, P, P, c_int, c_int, P, P]),
+    "flgp_dev_extend_scale": (c_int, [P, P, P, c_int, c_int, P, P, P]),
+    "flgp_dev_spectrum_model_extend": (c_int, [P, P, P, c_int, c_int, P, c_int]),
     "flgp_dev_gram": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_int]),
     "flgp_dev_sym_pack": (c_int, [P, P, c_int, c_int, P]),
     "flgp_dev_sym_unpack": (c_int, [P, P, c_int, P, c_int]),

@@ -521,6 +521,109 @@ def heat_kernel_spectrum_resident(X, X_new, s, r, K=-1, models=None, nstart=1, e
     return ResidentEigenPair(h)
 
 
+class SpectrumModel:
+    """A fitted graph-Laplacian spectrum (include/flgp_hip.h, "fitted spectrum model"): the anchors, the fit's two
+    column-sum vectors, the cluster sizes, the anchor-side eigenpairs and sqrt(n_fit), kept on the device.  ``extend``
+    runs the fit's row chain under them for rows that were not in the fit -- no eigensolve; for a row that was in the fit
+    it returns that row of the fit's vectors bit for bit.  It is not a refit: refit when the new rows are a sizeable
+    share of ``n_fit``.  Made by :func:`heat_kernel_spectrum_model`."""
+
+    _GL = ("rw", "normalized", "cluster-normalized")
+
+    def __init__(self, handle, dims=None):
+        self._h = handle
+        if dims is None:
+            v = [ctypes.c_int() for _ in range(8)]
+            check(_lib.lib().flgp_spectrum_model_dims(self._h, *[ctypes.byref(x) for x in v]))
+            dims = [x.value for x in v]
+        self.n_fit, self.d, self.s, self.r, self.K, kernel_se, gl, root = (int(x) for x in dims)
+        self.kernel = "se" if kernel_se else "lae"
+        self.gl = self._GL[gl]
+        self.root = bool(root)
+
+    @property
+    def dims(self):
+        return {"n_fit": self.n_fit, "d": self.d, "s": self.s, "r": self.r, "K": self.K, "kernel": self.kernel,
+                "gl": self.gl, "root": self.root}
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the spectrum model has been freed")
+        return self._h
+
+    def to_host(self):
+        """The frozen state as a dict: ``values`` (K, as the pair's), ``eig`` (K, the solver's), ``V`` (s x K),
+        ``colsum_gl`` (s; zeros for "rw"), ``colsum_spectrum`` (s), ``sizes`` (s; zeros unless cluster-normalized)."""
+        h = self._handle()
+        out = {"values": np.zeros(self.K), "eig": np.zeros(self.K), "V": np.zeros((self.s, self.K), order="F"),
+               "colsum_gl": np.zeros(self.s), "colsum_spectrum": np.zeros(self.s), "sizes": np.zeros(self.s)}
+        check(_lib.lib().flgp_spectrum_model_to_host(h, _ptr(out["values"]), _ptr(out["eig"]), _ptr(out["V"]),
+                                                     _ptr(out["colsum_gl"]), _ptr(out["colsum_spectrum"]), _ptr(out["sizes"])))
+        return out
+
+    def extend(self, X, resident=False, head=None, head_rows=None):
+        """The eigenvector rows of the points ``X`` (n_new x d): an :class:`EigenPair` with the fit's values, or with
+        ``resident`` a :class:`ResidentEigenPair` whose first rows are the rows ``head_rows`` of the resident pair
+        ``head`` (default: all of them) and whose last n_new rows are the extension -- one pair for the consumers, idx0
+        the training rows and idx1 the new ones."""
+        h = self._handle()
+        X = _f64(X, "X")
+        if X.shape[1] != self.d:
+            raise ValueError(f"X has {X.shape[1]} columns but the model was fitted on {self.d}")
+        n = X.shape[0]
+        if n < 1:
+            raise ValueError("X must have at least one row")
+        if not resident:
+            if head is not None or head_rows is not None:
+                raise ValueError("head / head_rows need resident=True")
+            values = np.zeros(self.K); vectors = np.zeros((n, self.K), order="F")
+            check(_lib.lib().flgp_spectrum_model_extend(h, _ptr(X), n, _ptr(vectors)))
+            check(_lib.lib().flgp_spectrum_model_to_host(h, _ptr(values), None, None, None, None, None))
+            return EigenPair(values, vectors)
+        hh, rows, n_head = None, None, 0
+        if head is not None:
+            if head._h is None:
+                raise ValueError("the head pair has been freed")
+            if head.K != self.K:
+                raise ValueError(f"the head pair has K = {head.K}, the model K = {self.K}")
+            rows = np.ascontiguousarray(np.arange(head.n) if head_rows is None else head_rows, dtype=np.int32).reshape(-1)
+            if rows.size and (rows.min() < 0 or rows.max() >= head.n):
+                raise IndexError(f"head_rows outside 0..{head.n - 1}")
+            hh, n_head = head._h, rows.size
+        elif head_rows is not None:
+            raise ValueError("head_rows without head")
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_spectrum_model_extend_resident(h, _ptr(X), n, hh, _ptr(rows) if n_head else None, n_head,
+                                                             ctypes.byref(out)))
+        return ResidentEigenPair(out)
+
+    def free(self):
+        if self._h is not None:
+            _lib.lib().flgp_spectrum_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def heat_kernel_spectrum_model(X, X_new, s, r, K=-1, models=None, nstart=1, epsilon=0.1, U=None):
+    """:func:`heat_kernel_spectrum_resident` that also keeps what an extension to unseen rows needs: returns
+    ``(SpectrumModel, ResidentEigenPair)``, the pair bit for bit the resident entry's."""
+    models = dict(_DEFAULT_MODELS_CPP, **(models or {}))
+    X = _f64(X, "X"); X_new = _f64(X_new, "X_new")
+    X_all = np.asfortranarray(np.vstack([X, X_new]))
+    n, d = X_all.shape
+    U = _anchors(X_all, s, models, U, nstart)
+    hm = ctypes.c_void_p(); hp = ctypes.c_void_p()
+    check(_lib.lib().flgp_heat_kernel_spectrum_model(_ptr(X_all), n, d, _ptr(U), s, U.shape[1], int(r), int(K),
+                                                     _b(models["kernel"]), _b(models["gl"]), int(bool(models["root"])),
+                                                     float(epsilon), ctypes.byref(hm), ctypes.byref(hp)))
+    return SpectrumModel(hm), ResidentEigenPair(hp)
+
+
 def nystrom_eigenpair_cpp(X, U, a2, K, resident=False):
     """The per-bandwidth block of the ``fit_nystrom_*`` drivers (reference src/Fit.cpp:244-289): Gaussian similarity
     of the anchors with the double normalisation, ``eigs_sym(W_UU, K)``, and the Nystrom extension to the rows of

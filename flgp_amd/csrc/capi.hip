@@ -97,6 +97,17 @@ struct InputCheck {
   }
 };
 
+}  // namespace
+namespace flgp {
+int check_finite_on_device(hipStream_t st, const double *d_x, long count, const char *who) {
+  InputCheck ck;
+  FLGP_TRY(ck.begin(st));
+  FLGP_TRY(ck.finite(st, d_x, count));
+  return ck.verdict(st, who);
+}
+}  // namespace flgp
+namespace {
+
 // device-side state of one similarity matrix: anchors, k-NN, ELL (+ CSC view)
 struct Sim {
   DevBuf X, U, Ut, uu, knn_idx, knn_dist, ell_idx, ell_val, colptr, pos, colsum, cswork, work, num_class;
@@ -113,6 +124,9 @@ struct Sim {
   // stream beside them (round 4) and joined before the Gram kernel, its first reader
   hipEvent_t csc_ev = nullptr;
   bool csc_pending = false, want_csc = false;
+  // the fitted spectrum model's captures (null for every other caller): where the Laplacian's column sums and the
+  // spectrum's are copied before `colsum` is written again
+  DevBuf *keep_colsum_gl = nullptr, *keep_colsum_spectrum = nullptr;
   ~Sim() { if (csc_ev) { (void)hipEventSynchronize(csc_ev); (void)hipEventDestroy(csc_ev); } }
 };
 
@@ -175,6 +189,14 @@ int colsum_of(Sim &S, hipStream_t st, const int *d_idx, const double *d_val) {
   return flgp_dev_colsum(st, d_idx, d_val, S.n, S.r, S.s, S.colsum.as<double>(), S.cswork.p, wb);
 }
 
+// S.colsum (s doubles) into a capture of the fitted spectrum model, where the caller has set one
+int keep_colsum(Sim &S, hipStream_t st, DevBuf *keep) {
+  if (!keep) return FLGP_OK;
+  FLGP_TRY(keep->alloc(sizeof(double) * (size_t)S.s));
+  FLGP_HIP(hipMemcpyAsync(keep->p, S.colsum.p, sizeof(double) * (size_t)S.s, hipMemcpyDeviceToDevice, st));
+  return FLGP_OK;
+}
+
 int build_csc(Sim &S, hipStream_t st) {
   if (S.have_csc) return FLGP_OK;
   const size_t wb = flgp_dev_csc_workspace(S.n, S.s, S.r);
@@ -218,6 +240,7 @@ int laplacian(Sim &S, hipStream_t st, int gl, const double *d_num_class) {
   if (gl != FLGP_GL_RW) {
     FLGP_TRY(colsum_of(S, st, S.ell_idx.as<int>(), S.ell_val.as<double>()));
     FLGP_TRY(flgp_comm_all_reduce_sum(S.comm, S.colsum.as<double>(), (size_t)S.s, st));            // exchange 2a
+    FLGP_TRY(keep_colsum(S, st, S.keep_colsum_gl));
     return flgp_dev_col_scale_row_normalize(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.r, S.colsum.as<double>(),
                                             gl == FLGP_GL_CLUSTER_NORMALIZED ? d_num_class : nullptr);     // one pass over the values
   }
@@ -264,6 +287,7 @@ int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info) {
   // A = Z diag(1/sqrt(|colsum|+1e-9))  (:149-150)
   FLGP_TRY(colsum_of(S, st, S.ell_idx.as<int>(), S.ell_val.as<double>()));
   FLGP_TRY(flgp_comm_all_reduce_sum(S.comm, S.colsum.as<double>(), (size_t)S.s, st));              // exchange 2b
+  FLGP_TRY(keep_colsum(S, st, S.keep_colsum_spectrum));
   FLGP_TRY(flgp_dev_col_scale(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.r, S.colsum.as<double>(), nullptr, 1));
   // Gram + top-K eigenpairs (replaces RSpectra::svds / BDCSVD, src/TruncatedSVD.cpp:17-30)
   FLGP_TRY(P.G.alloc(sizeof(double) * (size_t)S.s * S.s));
@@ -355,6 +379,12 @@ int check_rows(const int *idx0, int n0, const int *idx1, int n1, int n) {
   for (int a = 0; a < n0; ++a) FLGP_REQUIRE(idx0[a] >= 0 && idx0[a] < n, "HK_from_spectrum: idx0[%d]=%d out of range", a, idx0[a]);
   for (int b = 0; b < n1; ++b) FLGP_REQUIRE(idx1[b] >= 0 && idx1[b] < n, "HK_from_spectrum: idx1[%d]=%d out of range", b, idx1[b]);
   return FLGP_OK;
+}
+
+// `from`'s memory changes owner: no copy
+void move_buf(DevBuf &to, DevBuf &from) {
+  to.release();
+  std::swap(to.p, from.p); std::swap(to.owned, from.owned); std::swap(to.cap, from.cap); std::swap(to.dev, from.dev);
 }
 
 // a new EigenPair of the current device, its buffers still empty
@@ -560,6 +590,46 @@ extern "C" int flgp_heat_kernel_spectrum_resident(const double *X_all, int n, in
   std::swap(ep->values.p, h.P.values.p);     // the buffers change owner: no copy
   std::swap(ep->vectors.p, h.P.vectors.p);
   *out = ep.release();
+  return FLGP_OK;
+}
+
+// ---- the fit of a spectrum model (the extension is model.hip): the resident entry's launches on the same
+// data, with the two column-sum vectors copied out on the way and the anchor side kept instead of dropped
+extern "C" int flgp_heat_kernel_spectrum_model(const double *X_all, int n, int d, const double *U, int s, int ucols, int r,
+                                               int K, const char *kernel, const char *gl, int root, double epsilon,
+                                               flgp_spectrum_model **model, flgp_eigenpair **pair) {
+  if (model) *model = nullptr;
+  if (pair) *pair = nullptr;
+  std::unique_ptr<flgp_spectrum_model> mo(new flgp_spectrum_model());
+  HostSpectrum h;
+  h.S.keep_colsum_gl = &mo->colsum_gl;
+  h.S.keep_colsum_spectrum = &mo->colsum_spectrum;
+  FLGP_TRY(h.run(model != nullptr, "heat_kernel_spectrum_model: null pointer", X_all, n, d, U, s, ucols, r, K, kernel, gl, root, epsilon));
+  hipStream_t st = h.st.s;
+  K = h.P.K;
+  mo->n_fit = n; mo->d = d; mo->s = s; mo->r = r; mo->K = K; mo->root = root ? 1 : 0; mo->epsilon = epsilon;
+  FLGP_TRY(parse_kernel(kernel, &mo->kernel_se));
+  mo->gl = flgp_parse_gl(gl);
+  FLGP_HIP(hipGetDevice(&mo->device));
+  FLGP_TRY(mo->values.alloc(sizeof(double) * (size_t)K));
+  FLGP_HIP(hipMemcpyAsync(mo->values.p, h.P.values.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, st));
+  if (mo->gl == FLGP_GL_CLUSTER_NORMALIZED) {      // U.col(d), what cross_similarity() handed the Laplacian
+    FLGP_TRY(mo->sizes.alloc(sizeof(double) * (size_t)s));
+    FLGP_HIP(hipMemcpyAsync(mo->sizes.p, h.S.U.as<double>() + (size_t)d * s, sizeof(double) * (size_t)s, hipMemcpyDeviceToDevice, st));
+  }
+  FLGP_HIP(hipStreamSynchronize(st));
+  move_buf(mo->Ut, h.S.Ut);
+  move_buf(mo->uu, h.S.uu);
+  move_buf(mo->V, h.P.V);
+  move_buf(mo->eig, h.P.eig);
+  if (pair) {
+    std::unique_ptr<flgp_eigenpair> ep;
+    FLGP_TRY(new_eigenpair(n, K, ep));
+    std::swap(ep->values.p, h.P.values.p);     // as the resident entry
+    std::swap(ep->vectors.p, h.P.vectors.p);
+    *pair = ep.release();
+  }
+  *model = mo.release();
   return FLGP_OK;
 }
 

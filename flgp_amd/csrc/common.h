@@ -304,6 +304,21 @@ struct flgp_eigenpair {
   int n = 0, K = 0, device = 0;
 };
 
+// fitted spectrum model (include/flgp_hip.h): made in capi.hip (the fit), consumed in model.hip (the extension)
+struct flgp_spectrum_model {
+  flgp::DevBuf Ut, uu;                              // the k-NN / LAE panel of the anchors
+  flgp::DevBuf V, eig, values;                      // s x K (ld s), K (the solver's), K (as the pair's)
+  flgp::DevBuf colsum_gl, colsum_spectrum, sizes;   // s each; colsum_gl unset for "rw", sizes unless cluster-normalized
+  int n_fit = 0, d = 0, s = 0, r = 0, K = 0, kernel_se = 0, gl = 0, root = 0, device = 0;
+  double epsilon = 0.0;
+};
+namespace flgp {
+// FLGP_ERR_INVALID with the host entries' message where d_x holds a non-finite value (capi.hip; synchronises `st`)
+int check_finite_on_device(hipStream_t st, const double *d_x, long count, const char *who);
+// out(a, k) = V(idx[a], k) into a matrix of leading dimension ldo (gemm.hip)
+int gather_rows_ld(hipStream_t st, const double *dV, int ld, const int *d_idx, int n0, int K, double *d_out, int ldo);
+}  // namespace flgp
+
 struct flgp_nystrom_grid;
 namespace flgp {
 // Nystrom extension from a grid's anchor side (nystrom.hip); both synchronise `st`.  d_vectors[i] (extend_all): the n x K

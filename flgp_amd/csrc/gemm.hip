@@ -667,12 +667,13 @@ __global__ void hk_scale_kernel(const double *__restrict__ values, int K, double
   Vw[e] = V1[(size_t)k * ld1 + row] * w;
 }
 
+// out: n0 x K column-major with leading dimension ldo (>= n0: the top rows of a taller matrix)
 __global__ void gather_rows_kernel(const double *__restrict__ V, int ld, const int *__restrict__ idx, int n0, int K,
-                                   double *__restrict__ out) {
+                                   double *__restrict__ out, int ldo) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (long)n0 * K) return;
   const int a = (int)(e % n0), k = (int)(e / n0);
-  out[e] = V[(size_t)k * ld + idx[a]];
+  out[(size_t)k * ldo + a] = V[(size_t)k * ld + idx[a]];
 }
 
 }  // namespace flgp
@@ -726,9 +727,18 @@ extern "C" int flgp_dev_gather_rows(void *stream, const double *dV, int ld, cons
   FLGP_REQUIRE(dV && d_idx && d_out && n0 >= 0 && K >= 1, "gather_rows: bad arguments");
   if (n0 == 0) return FLGP_OK;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div((long)n0 * K, 256)), dim3(256), 0, (hipStream_t)stream, dV, ld, d_idx,
-                     n0, K, d_out);
+                     n0, K, d_out, n0);
   return check_launch("gather_rows_kernel");
 }
+
+namespace flgp {
+int gather_rows_ld(hipStream_t st, const double *dV, int ld, const int *d_idx, int n0, int K, double *d_out, int ldo) {
+  FLGP_REQUIRE(dV && d_idx && d_out && n0 >= 0 && K >= 1 && ldo >= n0, "gather_rows: bad arguments");
+  if (n0 == 0) return FLGP_OK;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div((long)n0 * K, 256)), dim3(256), 0, st, dV, ld, d_idx, n0, K, d_out, ldo);
+  return check_launch("gather_rows_kernel");
+}
+}  // namespace flgp
 
 extern "C" size_t flgp_dev_hk_workspace(int n0, int n1, int K, int gather0) {
   // (the padded operand of the panel kernel, hk.hip, is the larger of the two layouts of Vw)
@@ -747,7 +757,7 @@ extern "C" int flgp_dev_hk(void *stream, const double *d_values, int K, double t
   if (d_idx0) {  // general row gather (mat_indexing, src/Utils.h:130-137); callers normally pass ranges
     double *G0 = d_work + hk_panel_vw_elems(n1, K);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div((long)n0 * K, 256)), dim3(256), 0, st, dV0, ld0, d_idx0,
-                       n0, K, G0);
+                       n0, K, G0, n0);
     FLGP_TRY(check_launch("gather_rows_kernel"));
     V0 = G0;
     v0_ld = n0;

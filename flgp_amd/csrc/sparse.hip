@@ -274,6 +274,43 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(double *__restrict__
   for (int e = threadIdx.x; e < cnt; e += 256) g[e] = rn_rows[e];
 }
 
+// A row's values under GIVEN column sums (the fitted spectrum model's extension, model.hip): col_scale_kernel's mode 0,
+// the row normalisation above and col_scale_kernel's mode 1 in one pass over the values, in row_normalize_kernel's shape
+// (256 rows per workgroup through LDS, coalesced in and out).  Every entry sees the same rounded operations in the same
+// order as in the three kernels, so the bits are theirs; c1 == nullptr ("rw"): no scaling on the way in.  The column
+// indices are read again on the way out (coalesced, and in cache from the way in) rather than kept in LDS.
+__global__ __launch_bounds__(256) void extend_scale_kernel(const int *__restrict__ idx, double *__restrict__ val, int n, int r,
+                                                           const double *__restrict__ c1, const double *__restrict__ num_class,
+                                                           const double *__restrict__ c2) {
+  extern __shared__ double es_rows[];
+  const long i0 = (long)blockIdx.x * 256;
+  const int rows = (n - i0 < 256) ? (int)(n - i0) : 256;
+  double *g = val + (size_t)i0 * r;
+  const int *gi = idx + (size_t)i0 * r;
+  const int cnt = rows * r;
+  if (c1) {
+    for (int e = threadIdx.x; e < cnt; e += 256) {
+      const int j = gi[e];
+      double v = g[e];
+      v = v * (1.0 / (c1[j] + 1e-9));                  // src/Utils.cpp:201,204
+      if (num_class) v = v * num_class[j];             // src/Utils.cpp:205
+      es_rows[e] = v;
+    }
+  } else
+  for (int e = threadIdx.x; e < cnt; e += 256) es_rows[e] = g[e];
+  __syncthreads();
+  if ((int)threadIdx.x < rows) {
+    double *row = es_rows + (size_t)threadIdx.x * r;
+    double rs = 0.0;
+    for (int a = 0; a < r; ++a) rs += row[a];        // ascending column order (src/Utils.cpp:210)
+    const double inv = 1.0 / (rs + 1e-9);
+    for (int a = 0; a < r; ++a) row[a] = inv * row[a];  // src/Utils.cpp:211
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < cnt; e += 256)
+    g[e] = es_rows[e] * (1.0 / __builtin_sqrt(__builtin_fabs(c2[gi[e]]) + 1e-9));  // src/Spectrum.cpp:150
+}
+
 // ----------------------------------------------------------------------------------------
 // Gram: one wave per column j1.  The wave owns row j1 of G in LDS (s doubles) and walks the column's entries in
 // ascending row order: every G(j1, j2) is summed in ascending row order -- deterministic, and identical to the oracle.
@@ -810,6 +847,20 @@ extern "C" int flgp_dev_col_scale_row_normalize(void *stream, const int *d_ell_i
   hipLaunchKernelGGL(row_normalize_kernel, dim3(ceil_div(n, 256)), dim3(256), lds, (hipStream_t)stream, d_ell_val, n, r, d_ell_idx,
                      d_colsum, d_num_class);
   return check_launch("row_normalize_kernel");
+}
+
+// the extension's three scalings in one pass (extend_scale_kernel): the bits of flgp_dev_col_scale(mode 0) ->
+// flgp_dev_row_normalize -> flgp_dev_col_scale(mode 1) under the given column sums
+extern "C" int flgp_dev_extend_scale(void *stream, const int *d_ell_idx, double *d_ell_val, int n, int r,
+                                     const double *d_colsum_gl, const double *d_num_class, const double *d_colsum_spectrum) {
+  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && n >= 0 && d_ell_idx && d_ell_val && d_colsum_spectrum, "extend_scale: bad arguments");
+  if (n == 0) return FLGP_OK;
+  const size_t lds = sizeof(double) * 256 * (size_t)r;
+  if (lds > 48 * 1024)
+    FLGP_HIP(hipFuncSetAttribute((const void *)extend_scale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(extend_scale_kernel, dim3(ceil_div(n, 256)), dim3(256), lds, (hipStream_t)stream, d_ell_idx, d_ell_val, n, r,
+                     d_colsum_gl, d_num_class, d_colsum_spectrum);
+  return check_launch("extend_scale_kernel");
 }
 
 extern "C" int flgp_dev_gram(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int s, int r,
