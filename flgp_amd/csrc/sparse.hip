@@ -315,52 +315,56 @@ __global__ __launch_bounds__(256) void extend_scale_kernel(const int *__restrict
 // Gram: one wave per column j1.  The wave owns row j1 of G in LDS (s doubles) and walks the column's entries in
 // ascending row order: every G(j1, j2) is summed in ascending row order -- deterministic, and identical to the oracle.
 // A row's r products go to r distinct bins; consecutive rows of a column share anchors (they all have j1, and usually
-// more).  One ds_add_f64 serves a group of 64 / LPR rows: lanes that hit the same bin are applied in ascending lane order
+// more).  One ds_add_f64 serves a group of rows: lanes that hit the same bin are applied in ascending lane order
 // (= ascending row), and the LDS unit executes a wave's instructions in order, so the sums stay sequential without a
 // round trip through registers (see the note at `apply` below).
 //
-// Where the time goes (round 2, scripts/ubench_ldsatomic.hip): a ds_add_f64 costs ~60 cycles per instruction per
-// wave whatever the number of active lanes, and four waves per CU get four times that throughput -- 2000 rows per
-// column, 5000 columns, 1024 resident waves: 0.25 ms.  The round-1 kernel took 2.4 ms because each step of six rows
-// first chased pos -> entry -> row (an integer division and two dependent gathers) with a single step of look-ahead.
-// Here LPR lanes serve a row (64 / LPR rows per group), the loads of GRAM_PF groups are in flight while the previous
-// GRAM_PF groups are applied, the next 64 positions are fetched a block ahead, and entry / r is a multiplication.
+// Where the time goes: a ds_add_f64 costs ~60 cycles per instruction per wave whatever the number of active lanes
+// (scripts/ubench_ldsatomic.hip), and four waves per CU get four times that throughput: 0.25 ms at the flagship shape.
+// The row of G caps a CU at one wave per SIMD, so nothing else hides a wave's memory latency: what counts is how many
+// rows a wave has in flight.  Hence
+//   * a group is as many rows as 64 lanes hold: LPR lanes per row, 64 / LPR rows per ds_add_f64.  LPR = r where that
+//     gains a row over the power-of-two packing (six rows at r = 10 instead of four), else 16 or 32;
+//   * the column is walked in steps of GF groups, and the wave keeps GF groups of loads in flight at all times: as soon
+//     as a group is applied, the group GF places on (the same place of the next step) is fetched into its registers;
+//   * the positions of a step are fetched two steps ahead, so that they are there when its first group is fetched;
+//   * every load is issued unconditionally at a valid address (an idle slot reads entry p0 / row 0), so that the number
+//     in flight does not depend on the data and the compiler's vmcnt waits are counted, not vmcnt(0);
+//   * entry / r is a multiplication.
 // ----------------------------------------------------------------------------------------
-constexpr int GRAM_PF = 4;      // groups of rows whose loads are in flight together
-
-// WIN: the wave owns the columns [w0, w0 + wn) of row j1 only (window blockIdx.y); products for other windows are skipped
+// WIN: the wave owns the columns [w0, w0 + wn) of row j1 only (window blockIdx.y); products for other windows are skipped.
+// LPR: lanes per row, 0 for r itself.
 template <int LPR, bool WIN>
 __global__ __launch_bounds__(64) void gram_kernel(const int *__restrict__ ell_idx, const double *__restrict__ val,
                                                   int s, int r, double inv_r, const int *__restrict__ colptr,
                                                   const int *__restrict__ pos, double *__restrict__ G, int ldg, int wmax) {
   extern __shared__ double acc[];
-  constexpr int RPG = 64 / LPR;     // rows per group
-  constexpr int NG = 64 / RPG;      // groups per block of 64 positions
+  // groups in flight: 3 loads each + 2 of positions stay below the 63 vector loads a wave can have outstanding.  Eleven
+  // groups of six rows are the 64 positions of a step at r = 10 (groups beyond a step's positions load for nothing).
+  constexpr int GF = LPR ? 16 : 11;
   const int lane = threadIdx.x;
   const int j1 = blockIdx.x;
   const int w0 = WIN ? (int)blockIdx.y * wmax : 0;
   const int wn = WIN ? ((s - w0 < wmax) ? s - w0 : wmax) : s;
   for (int j = lane; j < wn; j += 64) acc[j] = 0.0;
   __syncthreads();
-  const int sub = lane / LPR;       // which row of a group this lane serves
-  const int a = lane % LPR;         // slot inside the row
-  const bool slot_ok = a < r;
-  const int ac = slot_ok ? a : 0;
+  const int lpr = LPR ? LPR : r;
+  const int rpg = 64 / lpr;         // rows per group
+  const int sub = lane / lpr;       // which row of a group this lane serves: lane order is row order
+  const int a = lane - sub * lpr;   // slot inside the row
+  const bool slot_ok = a < r && sub < rpg;
+  const int ac = a < r ? a : 0;
   const int p0 = colptr[j1], p1 = colptr[j1 + 1];
-  int epos = (p0 + lane < p1) ? pos[p0 + lane] : 0;
-  for (int pc = p0; pc < p1; pc += 64) {
-    const int pn = pc + 64 + lane;
-    const int epos_next = (pn < p1) ? pos[pn] : 0;                 // a block ahead
-    const int cnt = (p1 - pc < 64) ? p1 - pc : 64;
+  if (p0 < p1) {
+    const int ng = (63 + rpg) / rpg;                        // groups that 64 positions make (the last one may be partial)
+    const int step = (ng <= GF) ? 64 : GF * rpg;            // positions per step: a step is at most GF groups
+    auto positions = [&](int pb) { const int p = pb + lane; return pos[p < p1 ? p : p0]; };
     struct Grp { int j2; double v, vj; bool act; };
-    // loads are unconditional (inactive slots read entry 0 of row 0: a valid address), so that the number in flight
-    // does not depend on the path and the compiler's wait counts stay tight
-    auto fetch = [&](int g) {
+    // the group whose lanes were handed the entries `en` (0 where idle)
+    auto fetch = [&](int en, bool act) {
       Grp o;
-      const int slot = g * RPG + sub;
-      o.act = slot_ok && slot < cnt;
-      const int e = __shfl(epos, slot & 63, 64);
-      const int ee = o.act ? e : 0;
+      o.act = act;
+      const int ee = act ? en : 0;
       const int row = (int)(((double)ee + 0.5) * inv_r);            // == ee / r exactly for ee < 2^31, r <= 32
       const size_t rowbase = (size_t)row * r;
       o.j2 = ell_idx[rowbase + ac];
@@ -368,30 +372,38 @@ __global__ __launch_bounds__(64) void gram_kernel(const int *__restrict__ ell_id
       o.vj = val[ee];
       return o;
     };
-    // ONE ds_add_f64 per group of RPG rows: lanes of different rows that hit the same bin (bin j1 always, usually more)
-    // are applied by the LDS unit in ascending lane order = ascending row, which is the oracle's order.  (Until round 4
-    // the source spelled this as RPG instructions, one row each; per thread that is the same program, the compiler had
-    // merged them all along, and with a window test in the condition it split them in another order -- 1 ulp off in 0.5 %
-    // of the entries.  The lane-order rule is what the bit-exact tests on all 1e6 rows of configs[2] have been checking.)
+    // ONE ds_add_f64 per group: lanes of different rows that hit the same bin (bin j1 always, usually more) are applied
+    // by the LDS unit in ascending lane order = ascending row, which is the oracle's order, and the LDS unit executes a
+    // wave's instructions in program order = group order.  (Spelled as one instruction per row, the compiler merges them --
+    // and with a window test in the condition it once split them in another order: 1 ulp off in 0.5 % of the entries.)
     auto apply = [&](const Grp &o) {
       const double prod = o.vj * o.v;
       const bool on = o.act && (!WIN || (unsigned)(o.j2 - w0) < (unsigned)wn);
       const int bin = on ? o.j2 - w0 : 0;
       if (on) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double *)&acc[bin], prod);
     };
-    Grp cur[GRAM_PF], nxt[GRAM_PF];
+    // The loop starts a step early, with nothing to apply: the first groups are then fetched by the loop's own code, in
+    // the loop's own order, and the wait counts at its head are those of the steady state.
+    Grp q[GF];
 #pragma unroll
-    for (int u = 0; u < GRAM_PF; ++u) cur[u] = fetch(u);
-    for (int g0 = 0; g0 < NG; g0 += GRAM_PF) {
-      if (g0 * RPG >= cnt) break;                                   // uniform: the rest of the block is empty
+    for (int u = 0; u < GF; ++u) q[u] = Grp{0, 0.0, 0.0, false};
+    int e1 = positions(p0);
+    asm volatile("" : "+v"(e1));    // waited for here: a load pending on entry would make the loop's first wait vmcnt(0) for good
+    for (int pc = p0 - step; pc < p1; pc += step) {
+      const int e2 = positions(pc + 2 * step);
+      const int left = p1 - pc - step;                              // entries from the next step on
+      const int cnt = left < step ? left : step;                    // (<= 0 after the last step: its fetches are all idle)
+      // every group's entries in one go: the shuffles pass through the LDS unit behind the adds of the step before
+      int en[GF];
 #pragma unroll
-      for (int u = 0; u < GRAM_PF; ++u) nxt[u] = fetch(g0 + GRAM_PF + u);   // (past the block: slot >= cnt, inactive)
+      for (int u = 0; u < GF; ++u) en[u] = __shfl(e1, (u * rpg + sub) & 63, 64);
 #pragma unroll
-      for (int u = 0; u < GRAM_PF; ++u) apply(cur[u]);
-#pragma unroll
-      for (int u = 0; u < GRAM_PF; ++u) cur[u] = nxt[u];
+      for (int u = 0; u < GF; ++u) {
+        apply(q[u]);
+        q[u] = fetch(en[u], slot_ok && u * rpg + sub < cnt);
+      }
+      e1 = e2;
     }
-    epos = epos_next;
   }
   __syncthreads();
   double *out = G + (size_t)j1 * ldg + w0;
@@ -871,15 +883,19 @@ extern "C" int flgp_dev_gram(void *stream, const int *d_ell_idx, const double *d
   const int wmax = lds_window(s);
   const size_t lds = sizeof(double) * (size_t)wmax;
   const bool win = wmax < s;
-  const void *fn = r <= 16 ? (win ? (const void *)gram_kernel<16, true> : (const void *)gram_kernel<16, false>)
-                           : (win ? (const void *)gram_kernel<32, true> : (const void *)gram_kernel<32, false>);
+  // lanes per row: r itself where that puts more rows into a group than the power-of-two packing does (r <= 12, 17..21)
+  const int lpr = (64 / r > (r <= 16 ? 4 : 2)) ? 0 : (r <= 16 ? 16 : 32);
+  const void *fn = lpr == 0 ? (win ? (const void *)gram_kernel<0, true> : (const void *)gram_kernel<0, false>)
+                 : lpr == 16 ? (win ? (const void *)gram_kernel<16, true> : (const void *)gram_kernel<16, false>)
+                             : (win ? (const void *)gram_kernel<32, true> : (const void *)gram_kernel<32, false>);
   if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope ps("gram_kernel", (hipStream_t)stream, 12.0 * (double)n * r + 8.0 * (double)s * s);
   const dim3 grid(s, win ? ceil_div(s, wmax) : 1);
 #define GRAM_LAUNCH(LPRv, WINv)                                                                                                \
   hipLaunchKernelGGL((gram_kernel<LPRv, WINv>), grid, dim3(64), lds, (hipStream_t)stream, d_ell_idx, d_ell_val, s, r,         \
                      1.0 / (double)r, d_colptr, d_pos, dG, ldg, wmax)
-  if (r <= 16) { if (win) GRAM_LAUNCH(16, true); else GRAM_LAUNCH(16, false); }
+  if (lpr == 0) { if (win) GRAM_LAUNCH(0, true); else GRAM_LAUNCH(0, false); }
+  else if (lpr == 16) { if (win) GRAM_LAUNCH(16, true); else GRAM_LAUNCH(16, false); }
   else { if (win) GRAM_LAUNCH(32, true); else GRAM_LAUNCH(32, false); }
 #undef GRAM_LAUNCH
   return check_launch("gram_kernel");
