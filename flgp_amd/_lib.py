@@ -59,6 +59,8 @@ _SIGNATURES = {
     "flgp_eigenpair_logit_marginal_likelihood": (c_int, [P, c_int, c_double, c_double, P, c_int, P, P, c_double, c_int, P, P]),
     "flgp_eigenpair_posterior_classification": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_double,
                                                         c_int, P, P]),
+    "flgp_eigenpair_logit_posterior": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_double, c_int,
+                                               P, P, P]),
     "flgp_eigenpair_logit_objective": (c_int, [P, c_int, P, c_int, P, P, c_double, c_char_p, P, c_double, c_double, c_int, P,
                                                P]),
     "flgp_eigenpair_regression_objective": (c_int, [P, c_int, P, c_int, P, c_int, c_double, c_char_p, c_char_p, P, P, c_int,

@@ -390,6 +390,24 @@ class ResidentEigenPair:
                                                                  int(max_iter), _ptr(mean), _ptr(cov)))
         return {"mean": mean, "cov": cov}
 
+    def logit_posterior(self, idx0, idx1, K, t, Y, sigma11, sigma22, tol=1e-5, max_iter=100, return_iters=False):
+        """The Laplace posterior of ``posterior_distribution_classification`` with a route of its own for more labelled
+        rows than eigenpairs: m <= K gives that method's bits, m > K finds the mode in weight space (a K x K system per
+        Newton iteration, no m x m matrix) and reads the rows idx1 from the pair in place, in one fused kernel
+        (include/flgp_hip.h); there var >= sigma22 exactly.  sigma11, sigma22 >= 0.  Returns {"mean", "cov"} for the rows
+        idx1, or ``({"mean", "cov"}, iters)`` with ``return_iters``."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        if Y.size != idx0.size:
+            raise ValueError("Y must have one entry per row of idx0")
+        mean = np.zeros(idx1.size); cov = np.zeros(idx1.size)
+        it = ctypes.c_int()
+        check(_lib.lib().flgp_eigenpair_logit_posterior(self._h, int(K), float(t), float(sigma11), float(sigma22), _ptr(idx0),
+                                                        idx0.size, _ptr(Y), _ptr(idx1), idx1.size, float(tol), int(max_iter),
+                                                        _ptr(mean), _ptr(cov), ctypes.byref(it)))
+        post = {"mean": mean, "cov": cov}
+        return (post, it.value) if return_iters else post
+
     def posterior_distribution_multiclassification(self, idx0, idx1, K, ts, Y, sigma, tol=1e-5, max_iter=100):
         """posterior_distribution_multiclassification (src/Utils.cpp:336-369): one-vs-rest over the J = max(Y) + 1 classes
         of ``multi_train_split(Y)``, class j at its own ``ts[j]``, sigma on C22 only.  Returns {"mean", "cov"}, m_new x J."""

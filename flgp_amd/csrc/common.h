@@ -247,6 +247,21 @@ int gpc_lr_a(hipStream_t st, const double *d_b, const double *d_sW, const double
              int m, double *d_a);
 int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const double *d_Y, const double *d_N, const double *d_D,
                 const double *d_LQ, int K, int m, double *d_out);
+// The weight-space Newton loop's elementwise steps and the predictive rows of the logit posterior for m > K (gpc.hip; the
+// loop is in eigenpair.hip).  gpc_ws_bd: out = b / D; gpc_ws_fnew: f_new = p + sigma (b - sW^2 p) / D.
+// gpc_predict_rows: mean_i = u^T v_i and cov_i = c + |G v_i|^2 for the mnew rows v_i = V(rows_i, 0:K) of the pair, read in
+// place (d_idx, or row0 + i when it is nullptr), G (K x K at ld K, lower triangular) and u (K) the caller's; d_Gf holds
+// gpc_predict_operand_elems(K) doubles.  One fused MFMA kernel, for K <= GPC_PREDICT_KMAX on a device whose LDS holds 16
+// rows (gpc_predict_rows_applicable); wider K takes gemm + gpc_rowsumsq_add (out[i] = c + |Z(i, :)|^2) in the caller.
+constexpr int GPC_PREDICT_KMAX = 1024;
+int gpc_ws_bd(hipStream_t st, const double *d_b, const double *d_D, int m, double *d_out);
+int gpc_ws_fnew(hipStream_t st, const double *d_b, const double *d_sW, const double *d_D, const double *d_p, double sigma, int m,
+                double *d_fnew);
+size_t gpc_predict_operand_elems(int K);
+bool gpc_predict_rows_applicable(int K);
+int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, const double *dG,
+                     const double *d_u, double c, double *d_Gf, double *d_mean, double *d_cov);
+int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out);
 
 // The regression training objectives on the device (gpr_grad.hip).  tri_inverse: X = L^-1 (m x m, upper triangle zeroed)
 // for a lower factor of chol_blocked; dT holds 64 x m doubles, `work` (we doubles) bounds the GEMM's k-split.

@@ -1,7 +1,7 @@
 // Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products;
 // regression prediction, posterior variance and the training objectives with their gradients (kernels in
 // gpr.hip and gpr_grad.hip); the Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
-// 8f-5, gpc.hip); Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
+// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11); Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
 // the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
@@ -334,20 +334,24 @@ extern "C" int flgp_eigenpair_logit_marginal_likelihood(const flgp_eigenpair *ep
   return logit_la_on_device(st.s, C.as<double>(), m, Y, N, tol, max_iter, amll, iters, "logit_marginal_likelihood");
 }
 
-// posterior_distribution_classification (src/Utils.cpp:252-299) with C11 = HK(idx0, idx0) + sigma11 I,
-// C21 = HK(idx1, idx0) = V2 L V1^T, C22 = rowsum(V2 L .* V2) + sigma22.  mean = V2 L V1^T (Y - pi);
-// var_i = C22_i - v2_i^T M v2_i with M = X^T X, X = L_B^-1 sqrt(W) V1 L: O(m_new K^2), C21 is never formed.
-extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
-                                                       const int *idx0, int m, const double *Y, const int *idx1, int mnew,
-                                                       double tol, int max_iter, double *mean, double *cov) {
-  const char *who = "posterior_classification";
+namespace {
+// The argument checks the two posterior entries share, under the caller's name; r0 / r1 take the row sets.
+int posterior_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, const int *idx1,
+                    int mnew, int max_iter, const double *mean, const double *cov, Rows &r0, Rows &r1) {
   FLGP_REQUIRE(ep && idx0 && idx1 && Y && mean && cov, "%s: null pointer", who);
   FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && max_iter >= 1,
                "%s: bad shape (K=%d of %d, m=%d, m_new=%d, max_iter=%d)", who, K, ep->K, m, mnew, max_iter);
-  Rows r0, r1;
   FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
   FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
-  FLGP_TRY(check_labels(Y, nullptr, m, who));
+  return check_labels(Y, nullptr, m, who);
+}
+
+// posterior_distribution_classification (src/Utils.cpp:252-299) with C11 = HK(idx0, idx0) + sigma11 I,
+// C21 = HK(idx1, idx0) = V2 L V1^T, C22 = rowsum(V2 L .* V2) + sigma22.  mean = V2 L V1^T (Y - pi);
+// var_i = C22_i - v2_i^T M v2_i with M = X^T X, X = L_B^-1 sqrt(W) V1 L: O(m_new K^2), C21 is never formed.
+// The dense route of both posterior entries: the m x m C11 and B, whatever m is.
+int posterior_dense(const char *who, const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22, Rows &r0, int m,
+                    const double *Y, Rows &r1, int mnew, double tol, int max_iter, double *mean, double *cov, int *iters) {
   Stream st;
   FLGP_TRY(st.create());
   GprCtx G;
@@ -360,6 +364,7 @@ extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep,
   FLGP_TRY(S.alloc(m));
   int it = 0;
   FLGP_TRY(S.run(st.s, C.as<double>(), dY.as<double>(), nullptr, tol, max_iter, who, &it));
+  if (iters) *iters = it;
   FLGP_TRY(S.weights(st.s, C.as<double>(), dY.as<double>(), nullptr));
   FLGP_TRY(r0.gather(st.s, ep, K));
   FLGP_TRY(r1.gather(st.s, ep, K));
@@ -376,13 +381,26 @@ extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep,
   FLGP_TRY(gemm_tn(st.s, K, K, m, X.as<double>(), m, X.as<double>(), m, Mp.as<double>(), gw.as<double>(), we));        // M = X^T X
   FLGP_TRY(gemm_tn(st.s, K, 1, m, r0.V, r0.ld, S.resid.as<double>(), m, u.as<double>(), gw.as<double>(), we));         // V1^T (Y - pi)
   FLGP_TRY(gpr_scale(st.s, u.as<double>(), G.l.as<double>(), nullptr, K, 1, Mp.as<double>() + (size_t)K * K));  // column K: L (.)
-  FLGP_TRY(gemm_nn(st.s, mnew, K + 1, K, r1.V, r1.ld, Mp.as<double>(), K, Wp.as<double>(), nullptr, 0));          // V2 [M | u]
-  FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, out.as<double>()));
+  {
+    ProfScope ps("posterior_dense_predict", st.s, 2.0 * mnew * K * (K + 1));
+    FLGP_TRY(gemm_nn(st.s, mnew, K + 1, K, r1.V, r1.ld, Mp.as<double>(), K, Wp.as<double>(), nullptr, 0));        // V2 [M | u]
+    FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, out.as<double>()));
+  }
   FLGP_TRY(d2h(mean, Wp.as<double>() + (size_t)K * mnew, sizeof(double) * (size_t)mnew, st.s));
   FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
   int bad = 0;
   FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
   return GpcNewton::pivot_error(bad, who, 0);      // the loop checked its own factorisations: this is the one at the mode
+}
+}  // namespace
+
+extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
+                                                       const int *idx0, int m, const double *Y, const int *idx1, int mnew,
+                                                       double tol, int max_iter, double *mean, double *cov) {
+  const char *who = "posterior_classification";
+  Rows r0, r1;
+  FLGP_TRY(posterior_check(who, ep, K, idx0, m, Y, idx1, mnew, max_iter, mean, cov, r0, r1));
+  return posterior_dense(who, ep, K, t, sigma11, sigma22, r0, m, Y, r1, mnew, tol, max_iter, mean, cov, nullptr);
 }
 
 // ---- regression training objectives: train_regression_gp_cpp's four objectives on the resident pair ------
@@ -707,6 +725,145 @@ extern "C" int flgp_eigenpair_logit_objective(const flgp_eigenpair *ep, int K, c
     *value = -amll;
   }
   return FLGP_OK;
+}
+
+// ---- logit posterior for m > K: the mode in weight space, the predictive rows in one pass ----------------
+namespace {
+// Alg. 3.1's step written as a = (I + W C)^-1 b on LowRankB's C, which gives Phi^T a = Q^-1 Phi^T D^-1 b exactly
+// (Phi = V1 L^1/2, D = 1 + sigma W, X = diag(sqrt(W / D)) Phi, Q = I + X^T X).  Per iteration from f = 0, N = 1:
+//   W, b from f; D, xs; Q factored;  beta = Q^-1 L^1/2 V1^T (b / D);  p = V1 L^1/2 beta;  f_new = p + sigma (b - W p) / D.
+// Unlike GpcLowRank's a = b - sW dh (g - X Q^-1 X^T g), whose difference of two nearly equal vectors costs the mean
+// m lambda / 4 in relative accuracy (harmless for amll, which is stationary at the mode), the one subtraction here is
+// multiplied by sigma.  solve() is also the final step at the mode: beta there gives mean_i = v2_i^T L^1/2 beta.
+struct GpcWeightSpace {
+  int m = 0;
+  LowRankB L;                  // the caller sets V1, ld1, l, ls, sigma
+  DevBuf f, fnew, sW, b, D, dh, xs, bd, p, beta, scal, flag;
+
+  int alloc(int m_, int K) {
+    m = m_;
+    const size_t v = sizeof(double) * (size_t)m;
+    FLGP_TRY(f.alloc(v)); FLGP_TRY(fnew.alloc(v)); FLGP_TRY(sW.alloc(v)); FLGP_TRY(b.alloc(v)); FLGP_TRY(D.alloc(v));
+    FLGP_TRY(dh.alloc(v)); FLGP_TRY(xs.alloc(v)); FLGP_TRY(bd.alloc(v)); FLGP_TRY(p.alloc(v));
+    FLGP_TRY(beta.alloc(sizeof(double) * (size_t)K));
+    FLGP_TRY(scal.alloc(sizeof(double) * 2)); FLGP_TRY(flag.alloc(sizeof(int)));
+    return L.alloc(m, K, true, flag.as<int>());
+  }
+  // W, b, D, X and L_Q at the current f, then beta = Q^-1 L^1/2 V1^T (b / D)
+  int solve(hipStream_t st, const double *dY) {
+    const int K = L.K;
+    FLGP_TRY(gpc_weights(st, f.as<double>(), dY, nullptr, m, sW.as<double>(), b.as<double>()));
+    FLGP_TRY(gpc_lr_dvec(st, sW.as<double>(), L.sigma, m, D.as<double>(), dh.as<double>(), xs.as<double>()));
+    FLGP_TRY(L.factor(st, xs.as<double>()));
+    FLGP_TRY(gpc_ws_bd(st, b.as<double>(), D.as<double>(), m, bd.as<double>()));
+    FLGP_TRY(gemm_tn(st, K, 1, m, L.V1, L.ld1, bd.as<double>(), m, beta.as<double>(), L.work.as<double>(), L.we));
+    FLGP_TRY(pg_mul(st, K, L.ls, beta.as<double>(), nullptr, beta.as<double>()));                             // r
+    return chol_trsv(st, L.Q.as<double>(), K, K, beta.as<double>(), K, 1, 3, flag.as<int>());
+  }
+  // L.u = L^1/2 beta
+  int scaled_beta(hipStream_t st) { return pg_mul(st, L.K, L.ls, beta.as<double>(), nullptr, L.u.as<double>()); }
+  int iteration(hipStream_t st, const double *dY) {
+    ProfScope ps("logit_ws_newton_iter", st, 0.0);
+    FLGP_TRY(solve(st, dY));
+    FLGP_TRY(scaled_beta(st));
+    FLGP_TRY(gemm_nn(st, m, 1, L.K, L.V1, L.ld1, L.u.as<double>(), L.K, p.as<double>(), nullptr, 0));
+    FLGP_TRY(gpc_ws_fnew(st, b.as<double>(), sW.as<double>(), D.as<double>(), p.as<double>(), L.sigma, m, fnew.as<double>()));
+    return gpc_step(st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
+  }
+  // the loop from f = 0 with GpcLowRank::run's host protocol (12 bytes read back per iteration)
+  int run(hipStream_t st, const double *dY, double tol, int max_iter, const char *who, int *iters) {
+    FLGP_HIP(hipMemsetAsync(f.p, 0, sizeof(double) * (size_t)m, st));
+    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    *iters = 0;
+    for (int it = 0; it < max_iter; ++it) {
+      FLGP_TRY(iteration(st, dY));
+      double diff = 0.0;
+      int bad = 0;
+      FLGP_HIP(hipMemcpyAsync(&diff, scal.p, sizeof(double), hipMemcpyDeviceToHost, st));
+      FLGP_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+      FLGP_HIP(hipStreamSynchronize(st));
+      *iters = it + 1;
+      FLGP_TRY(GpcNewton::pivot_error(bad, who, it + 1));
+      if (diff < tol) break;
+    }
+    return FLGP_OK;
+  }
+};
+
+// mean_i = u^T v2_i, cov_i = sigma22 + |G v2_i|^2 for the rows r1 of the pair (G K x K lower triangular, u K; device
+// pointers, as dmean / dcov).  K <= GPC_PREDICT_KMAX: gpc_predict_rows, the rows read in place.  Wider K: Z = V2 G^T by the
+// MFMA GEMM and its row sums of squares, in row blocks that keep Z (and the gathered rows of an index set) at 256 MB each.
+int predict_rows(hipStream_t st, const flgp_eigenpair *ep, int K, Rows &r1, const double *G, const double *u, double sigma22,
+                 double *dmean, double *dcov) {
+  FLGP_TRY(r1.resolve(st));
+  const double *dvec = (const double *)ep->vectors.p;
+  if (gpc_predict_rows_applicable(K)) {
+    DevBuf Gf;
+    FLGP_TRY(Gf.alloc(sizeof(double) * gpc_predict_operand_elems(K)));
+    return gpc_predict_rows(st, dvec, ep->n, r1.d, r1.row0, r1.m, K, G, u, sigma22, Gf.as<double>(), dmean, dcov);
+  }
+  ProfScope ps("gpc_predict_rows_wide", st, 2.0 * r1.m * K * (K + 1));
+  const int rb = (int)std::min<size_t>((size_t)r1.m, std::max<size_t>(64, (((size_t)256 << 20) / (sizeof(double) * K)) / 64 * 64));
+  DevBuf Z, Vb;
+  FLGP_TRY(Z.alloc(sizeof(double) * (size_t)rb * K));
+  if (r1.d) FLGP_TRY(Vb.alloc(sizeof(double) * (size_t)rb * K));
+  for (int o = 0; o < r1.m; o += rb) {
+    const int rows = std::min(rb, r1.m - o);
+    const double *V = dvec + r1.row0 + o;
+    long ld = ep->n;
+    if (r1.d) {
+      FLGP_TRY(flgp_dev_gather_rows(st, dvec, ep->n, r1.d + o, rows, K, Vb.as<double>()));
+      V = Vb.as<double>(); ld = rows;
+    }
+    FLGP_TRY(gemm_launch(st, rows, K, K, 1.0, V, 1, ld, G, K, 1, 0.0, nullptr, 0, 0, Z.as<double>(), 1, rows, nullptr, 0, 0.0,
+                         nullptr));                                                                   // Z = V2 G^T
+    FLGP_TRY(gpc_rowsumsq_add(st, Z.as<double>(), rows, rows, K, sigma22, dcov + o));
+    FLGP_TRY(gemm_nn(st, rows, 1, K, V, ld, u, K, dmean + o, nullptr, 0));
+  }
+  return FLGP_OK;
+}
+}  // namespace
+
+extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
+                                              const int *idx0, int m, const double *Y, const int *idx1, int mnew, double tol,
+                                              int max_iter, double *mean, double *cov, int *iters) {
+  const char *who = "logit_posterior";
+  Rows r0, r1;
+  FLGP_TRY(posterior_check(who, ep, K, idx0, m, Y, idx1, mnew, max_iter, mean, cov, r0, r1));
+  FLGP_REQUIRE(std::isfinite(t), "%s: t=%g must be finite", who, t);
+  FLGP_REQUIRE(sigma11 >= 0.0 && std::isfinite(sigma11), "%s: sigma11=%g must be finite and >= 0", who, sigma11);
+  FLGP_REQUIRE(sigma22 >= 0.0 && std::isfinite(sigma22), "%s: sigma22=%g must be finite and >= 0", who, sigma22);
+  if (m <= K) return posterior_dense(who, ep, K, t, sigma11, sigma22, r0, m, Y, r1, mnew, tol, max_iter, mean, cov, iters);
+
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = L^1/2, l = L
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  DevBuf dY;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
+  GpcWeightSpace S;
+  S.L.sigma = sigma11; S.L.V1 = r0.V; S.L.ld1 = r0.ld; S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
+  FLGP_TRY(S.alloc(m, K));
+  int it = 0;
+  FLGP_TRY(S.run(st.s, dY.as<double>(), tol, max_iter, who, &it));
+  if (iters) *iters = it;
+  // the weights once more at the final f (as GpcNewton::weights in the dense route), then Gp = [L_Q^-1 L^1/2 ; (L^1/2 beta)^T]
+  FLGP_TRY(S.solve(st.s, dY.as<double>()));
+  FLGP_TRY(S.scaled_beta(st.s));
+  DevBuf Li, Tb, wt, dmean, dcov;
+  const size_t wi = (size_t)32 * 64 * K;
+  FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+  FLGP_TRY(wt.alloc(sizeof(double) * wi));
+  FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dcov.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_TRY(tri_inverse(st.s, S.L.Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, S.flag.as<int>()));
+  FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, G.ls.as<double>(), K, K, Li.as<double>()));            // L_Q^-1 L^1/2
+  FLGP_TRY(predict_rows(st.s, ep, K, r1, Li.as<double>(), S.L.u.as<double>(), sigma22, dmean.as<double>(), dcov.as<double>()));
+  FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_TRY(d2h(cov, dcov.p, sizeof(double) * (size_t)mnew, st.s));
+  int bad = 0;
+  FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
+  return GpcNewton::pivot_error(bad, who, 0);
 }
 
 // ---- Polya-Gamma Gibbs prediction: test_pgbinary_cpp and predict_logit_mult_gp_cpp (pg.hip) ---------------

@@ -473,6 +473,216 @@ int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const doub
   return check_launch("gpc_lr_amll_kernel");
 }
 
+// ---- the weight-space Newton loop and the fused predictive rows (m > K; the loop is in eigenpair.hip) ------
+
+// out = b / D
+__global__ void gpc_ws_bd_kernel(const double *__restrict__ b, const double *__restrict__ D, int m, double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) out[i] = b[i] / D[i];
+}
+
+// f_new = p + sigma (b - W p) / D with W = sW^2: the one subtraction of the step, and it is multiplied by sigma
+__global__ void gpc_ws_fnew_kernel(const double *__restrict__ b, const double *__restrict__ sW, const double *__restrict__ D,
+                                   const double *__restrict__ p, double sigma, int m, double *__restrict__ fnew) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const double s = sW[i], pi = p[i];
+  fnew[i] = pi + sigma * ((b[i] - (s * s) * pi) / D[i]);
+}
+
+int gpc_ws_bd(hipStream_t st, const double *d_b, const double *d_D, int m, double *d_out) {
+  hipLaunchKernelGGL(gpc_ws_bd_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_D, m, d_out);
+  return check_launch("gpc_ws_bd_kernel");
+}
+
+int gpc_ws_fnew(hipStream_t st, const double *d_b, const double *d_sW, const double *d_D, const double *d_p, double sigma, int m,
+                double *d_fnew) {
+  hipLaunchKernelGGL(gpc_ws_fnew_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_sW, d_D, d_p, sigma, m, d_fnew);
+  return check_launch("gpc_ws_fnew_kernel");
+}
+
+// The predictive operand Gp = [G ; u^T] ((K + 1) x K: G = L_Q^-1 L^1/2 lower triangular at ld K, u = L^1/2 beta) in the
+// order gpc_predict_rows_kernel loads it: Gf[(jt * nks + ks) * 64 + lane] = Gp(16 jt + (lane & 15), 4 ks + (lane >> 4)),
+// the A fragment of one v_mfma_f64_16x16x4_f64, zero past row K and past column K - 1.  A wave's fragment is 512
+// contiguous bytes and the k steps of a j-tile follow each other.
+__global__ void gpc_predict_prep_kernel(const double *__restrict__ G, const double *__restrict__ u, int K, int nks, long total,
+                                        double *__restrict__ Gf) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int lane = (int)(e & 63);
+  const long f = e >> 6;
+  const int ks = (int)(f % nks), jt = (int)(f / nks);
+  const int j = 16 * jt + (lane & 15), k = 4 * ks + (lane >> 4);
+  double v = 0.0;
+  if (k < K) {
+    if (j < K) v = k <= j ? G[(size_t)k * K + j] : 0.0;
+    else if (j == K) v = u[k];
+  }
+  Gf[e] = v;
+}
+
+typedef double gd4 __attribute__((ext_vector_type(4)));
+
+constexpr int PR_WAVES = 8;                  // waves per workgroup of gpc_predict_rows_kernel
+constexpr int PR_THREADS = 64 * PR_WAVES;
+// LDS row stride (doubles) of a block of R rows: 16 (mod 32), so that the two k of a 32-lane group of ds_read_b64 fall
+// into different halves of the 64 banks
+__host__ __device__ constexpr int pr_stride(int R) { return R == 16 ? 16 : R + 16; }
+
+// mean_i = z_K, cov_i = c + sum_{j < K} z_j^2 with z = Gp v_i, for the rows v_i = V(rows_i, 0:K) of the pair read in place
+// (rows_i = idx[i], or row0 + i when idx is nullptr; V column-major at ld).  A workgroup stages R = 16 RT rows in LDS
+// (vs[k][r], zero past K and past mnew), then its waves split the j-tiles of 16 outputs: D(16 j x 16 rows) +=
+// A(16 j x 4 k) B(4 k x 16 rows), A streamed from Gf (L2), B from LDS.  Tile jt runs the k steps below 4 (jt + 1) only
+// (Gp's first K rows are lower triangular); the last tile, which holds u, runs all nks.  The tiles go to the waves in
+// descending cost, back and forth over the waves.  C/D: lane l holds rows j = (l >> 4) + 4 reg of new row l & 15, so a
+// lane squares and adds its four results (reg ascending), the four lane groups meet through two xor exchanges
+// ((g0 + g1) + (g2 + g3) on every lane) and the tiles of a row are added in ascending jt by one thread: the bits of a
+// row depend on that row and Gp alone -- not on mnew, the grid, the row's position or its neighbours.
+template <int RT>
+__global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_kernel(const double *__restrict__ V, long ld,
+                                                                      const int *__restrict__ idx, int row0, int mnew, int K,
+                                                                      int nks, int njt, const double *__restrict__ Gf, double c,
+                                                                      double *__restrict__ mean, double *__restrict__ cov) {
+  constexpr int R = 16 * RT, RS = pr_stride(R), KSTEP = PR_THREADS / R;
+  extern __shared__ double pr_lds[];
+  double *vs = pr_lds;                         // [4 nks][RS]
+  double *ts = pr_lds + (size_t)4 * nks * RS;  // [njt][R]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long base = (long)blockIdx.x * R;
+  {
+    // every load is unconditional (row and k clamped into the block's live part) so that four are in flight per thread;
+    // the zero padding is applied on the way into LDS
+    const int r = tid % R;
+    const long i = base + r;
+    const bool live = i < mnew;
+    const long ic = live ? i : (long)mnew - 1;
+    const double *src = V + (idx ? (long)idx[ic] : (long)row0 + ic);
+    for (int k0 = tid / R; k0 < 4 * nks; k0 += 4 * KSTEP) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = src[(size_t)min(k0 + u * KSTEP, K - 1) * ld];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + u * KSTEP;
+        if (k < 4 * nks) vs[(size_t)k * RS + r] = (live && k < K) ? v[u] : 0.0;
+      }
+    }
+  }
+  __syncthreads();
+  const int g = lane >> 4, col = lane & 15;
+  const int jlast = njt - 1, qK = (K & 15) >> 2, gK = K & 3;      // z_K: tile jlast, lane group gK, register qK
+  for (int round = 0; round * PR_WAVES < njt; ++round) {
+    const int d = round * PR_WAVES + ((round & 1) ? PR_WAVES - 1 - wave : wave);
+    if (d >= njt) continue;
+    const int jt = jlast - d;
+    const int steps = jt == jlast ? nks : min(4 * (jt + 1), nks);
+    const double *A = Gf + (size_t)jt * nks * 64 + lane;
+    const double *B = vs + (size_t)g * RS + col;
+    gd4 acc[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[rt] = gd4{0.0, 0.0, 0.0, 0.0};
+    // four A fragments ahead of the four being multiplied (the loads clamped into the tile, the steps guarded)
+    double a[4], an[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = A[(size_t)min(u, steps - 1) * 64];
+    for (int ks = 0; ks < steps; ks += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) an[u] = A[(size_t)min(ks + 4 + u, steps - 1) * 64];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ks + u < steps) {
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt)
+            acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], B[(size_t)(ks + u) * 4 * RS + rt * 16], acc[rt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = an[u];
+    }
+    const int j0 = 16 * jt + g;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const gd4 z = acc[rt];
+      double s = j0 < K ? z.x * z.x : 0.0;
+      s += j0 + 4 < K ? z.y * z.y : 0.0;
+      s += j0 + 8 < K ? z.z * z.z : 0.0;
+      s += j0 + 12 < K ? z.w * z.w : 0.0;
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (g == 0) ts[(size_t)jt * R + rt * 16 + col] = s;
+      if (jt == jlast && g == gK) {
+        const long i = base + rt * 16 + col;
+        const double zK = qK == 0 ? z.x : (qK == 1 ? z.y : (qK == 2 ? z.z : z.w));
+        if (i < mnew) mean[i] = zK;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < R && base + tid < mnew) {
+    double s = 0.0;
+    for (int jt = 0; jt < njt; ++jt) s += ts[(size_t)jt * R + tid];
+    cov[base + tid] = c + s;
+  }
+}
+
+// dynamic LDS of a block of R rows
+static size_t pr_lds_bytes(int R, int nks, int njt) { return sizeof(double) * ((size_t)4 * nks * pr_stride(R) + (size_t)njt * R); }
+
+size_t gpc_predict_operand_elems(int K) { return (size_t)ceil_div(K + 1, 16) * ceil_div(K, 4) * 64; }
+
+// Block of rows: the largest of 64, 32, 16 that leaves room for two workgroups per CU (one stages while the other
+// multiplies), otherwise the largest that fits at all.  K <= GPC_PREDICT_KMAX always fits 16 rows in 160 KB.
+static int pr_rows(int nks, int njt, int lds_max) {
+  for (int R = 64; R >= 16; R >>= 1)
+    if (2 * pr_lds_bytes(R, nks, njt) <= (size_t)lds_max) return R;
+  for (int R = 64; R >= 16; R >>= 1)
+    if (pr_lds_bytes(R, nks, njt) <= (size_t)lds_max) return R;
+  return 0;
+}
+
+bool gpc_predict_rows_applicable(int K) {
+  if (K > GPC_PREDICT_KMAX) return false;
+  const int lds = device_figures().lds_per_block;
+  return pr_rows(ceil_div(K, 4), ceil_div(K + 1, 16), lds > 0 ? lds : 65536) != 0;
+}
+
+int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, const double *dG,
+                     const double *d_u, double c, double *d_Gf, double *d_mean, double *d_cov) {
+  const int nks = ceil_div(K, 4), njt = ceil_div(K + 1, 16);
+  const int lds_dev = device_figures().lds_per_block;
+  const int R = pr_rows(nks, njt, lds_dev > 0 ? lds_dev : 65536);
+  if (!R) { set_error("gpc_predict_rows: K=%d does not fit the device's LDS", K); return FLGP_ERR_UNSUPPORTED; }
+  ProfScope ps("gpc_predict_rows", st, (double)mnew * K * (K + 1));
+  const long total = (long)gpc_predict_operand_elems(K);
+  hipLaunchKernelGGL(gpc_predict_prep_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, dG, d_u, K, nks, total, d_Gf);
+  FLGP_TRY(check_launch("gpc_predict_prep_kernel"));
+  const size_t lds = pr_lds_bytes(R, nks, njt);
+  const dim3 grid(ceil_div(mnew, R)), block(PR_THREADS);
+  auto launch = [&](auto kfn) -> int {
+    if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kfn, grid, block, lds, st, dV, ld, d_idx, row0, mnew, K, nks, njt, (const double *)d_Gf, c, d_mean, d_cov);
+    return check_launch("gpc_predict_rows_kernel");
+  };
+  if (R == 64) return launch(gpc_predict_rows_kernel<4>);
+  if (R == 32) return launch(gpc_predict_rows_kernel<2>);
+  return launch(gpc_predict_rows_kernel<1>);
+}
+
+// out[i] = c + sum_k Z(i, k)^2, k ascending, a thread per row (the K > GPC_PREDICT_KMAX route of the predictive rows)
+__global__ void gpc_rowsumsq_add_kernel(const double *__restrict__ Z, long ldz, int rows, int cols, double c,
+                                        double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  double s = 0.0;
+  for (int k = 0; k < cols; ++k) { const double v = Z[(size_t)k * ldz + i]; s += v * v; }
+  out[i] = c + s;
+}
+
+int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out) {
+  hipLaunchKernelGGL(gpc_rowsumsq_add_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, st, dZ, ldz, rows, cols, c, d_out);
+  return check_launch("gpc_rowsumsq_add_kernel");
+}
+
 }  // namespace flgp
 
 using namespace flgp;
