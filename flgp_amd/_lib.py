@@ -61,6 +61,11 @@ _SIGNATURES = {
                                                         c_int, P, P]),
     "flgp_eigenpair_logit_posterior": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_double, c_int,
                                                P, P, P]),
+    "flgp_eigenpair_logit_posterior_multiclass": (c_int, [P, c_int, P, c_int, c_double, c_double, P, c_int, P, P, c_int,
+                                                          c_double, c_int, c_int, P, P, P]),
+    "flgp_eigenpair_logit_posterior_multiclass_nll": (c_int, [P, c_int, P, c_int, c_double, c_double, P, c_int, P, P, c_int,
+                                                              c_double, c_int, c_int, P, P, P, P, c_int, ctypes.c_ulonglong,
+                                                              P]),
     "flgp_eigenpair_logit_objective": (c_int, [P, c_int, P, c_int, P, P, c_double, c_char_p, P, c_double, c_double, c_int, P,
                                                P]),
     "flgp_eigenpair_regression_objective": (c_int, [P, c_int, P, c_int, P, c_int, c_double, c_char_p, c_char_p, P, P, c_int,

@@ -423,6 +423,50 @@ class ResidentEigenPair:
             mean[:, j] = post["mean"]; cov[:, j] = post["cov"]
         return {"mean": mean, "cov": cov}
 
+    def logit_posterior_multiclass(self, idx0, idx1, K, ts, Y, sigma, sigma11=0.0, tol=1e-5, max_iter=100, max_parallel=4,
+                                   return_iters=False, target=None, n_samples=100, seed=None, return_posterior=True):
+        """The one-vs-rest posterior of ``posterior_distribution_multiclassification`` in one call
+        (flgp_eigenpair_logit_posterior_multiclass, include/flgp_hip.h): ``Y`` holds class labels 0 .. J-1 with
+        J = ``len(ts)``, class j is ``logit_posterior`` on ``Y == j`` at ``ts[j]`` with ``sigma22 = sigma`` (``sigma11``
+        defaults to the reference's 0), bit for bit.  The rows, the labels and V1 go up once and, for m > K, one fused
+        kernel reads the rows idx1 once for all classes.  ``max_parallel``: host threads (a stream each) the J Newton
+        loops are dealt to for m > K; the default 4 is the number of hardware queues a process opens by default, so more
+        workers share queues.  A class without a member is allowed.  Returns {"mean", "cov"}, m_new x J Fortran-ordered.
+        With ``target`` (m_new class labels naming all J classes) the result is scored on the device as
+        ``negative_log_likelihood(mean, cov, target, "multinomial", n_samples, seed)`` and "nll" is added;
+        ``return_posterior=False`` then brings down that one number only.  ``return_iters``: also the J iteration counts."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        J = ts.size
+        if Y.size != idx0.size:
+            raise ValueError("Y must have one entry per row of idx0")
+        if target is None and not return_posterior:
+            raise ValueError("return_posterior=False needs a target to score")
+        if target is not None:
+            target = np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1))
+            if target.size != idx1.size:
+                raise ValueError("target must have one entry per row of idx1")
+            if target.size and np.isfinite(target).all() and int(target.max()) + 1 != J:
+                raise ValueError(f"need one t per class: target names {int(target.max()) + 1} classes, {J} values of t")
+        mean = cov = None
+        if return_posterior:
+            mean = np.zeros((idx1.size, J), order="F"); cov = np.zeros((idx1.size, J), order="F")
+        its = np.zeros(max(J, 1), dtype=np.int32)
+        head = (self._h, int(K), _ptr(ts), J, float(sigma11), float(sigma), _ptr(idx0), idx0.size, _ptr(Y), _ptr(idx1), idx1.size,
+                float(tol), int(max_iter), int(max_parallel), _ptr(mean), _ptr(cov), _ptr(its))
+        out = {}
+        if target is None:
+            check(_lib.lib().flgp_eigenpair_logit_posterior_multiclass(*head))
+        else:
+            nll = ctypes.c_double()
+            check(_lib.lib().flgp_eigenpair_logit_posterior_multiclass_nll(*head, _ptr(target), int(n_samples), _seed(seed),
+                                                                           ctypes.byref(nll)))
+            out["nll"] = nll.value
+        if return_posterior:
+            out["mean"] = mean; out["cov"] = cov
+        return (out, its[:J].copy()) if return_iters else out
+
     def logit_objective(self, t, K, idx, Y, N=None, sigma=1e-3, approach="posterior", prior=None, tol=1e-5, max_iter=100,
                         return_iters=False):
         """The value train_lae_logit_gp_cpp's COBYLA minimises at t (src/train.cpp:14-34), on the resident pair with

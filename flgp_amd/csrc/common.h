@@ -253,6 +253,9 @@ int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const doub
 // place (d_idx, or row0 + i when it is nullptr), G (K x K at ld K, lower triangular) and u (K) the caller's; d_Gf holds
 // gpc_predict_operand_elems(K) doubles.  One fused MFMA kernel, for K <= GPC_PREDICT_KMAX on a device whose LDS holds 16
 // rows (gpc_predict_rows_applicable); wider K takes gemm + gpc_rowsumsq_add (out[i] = c + |Z(i, :)|^2) in the caller.
+// The one-vs-rest posterior: gpc_class_indicator: out = (labels == j); gpc_predict_prep writes one operand
+// [G ; u^T] into d_Gf, gpc_predict_rows_multi multiplies J of them, stored back to back, against the rows staged once and
+// writes column j of d_mean / d_cov (ldo): the bits of gpc_predict_rows on operand j.
 constexpr int GPC_PREDICT_KMAX = 1024;
 int gpc_ws_bd(hipStream_t st, const double *d_b, const double *d_D, int m, double *d_out);
 int gpc_ws_fnew(hipStream_t st, const double *d_b, const double *d_sW, const double *d_D, const double *d_p, double sigma, int m,
@@ -261,6 +264,10 @@ size_t gpc_predict_operand_elems(int K);
 bool gpc_predict_rows_applicable(int K);
 int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, const double *dG,
                      const double *d_u, double c, double *d_Gf, double *d_mean, double *d_cov);
+int gpc_class_indicator(hipStream_t st, const double *d_labels, int m, int j, double *d_out);
+int gpc_predict_prep(hipStream_t st, int K, const double *dG, const double *d_u, double *d_Gf);
+int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int J,
+                           const double *d_Gf, double c, double *d_mean, double *d_cov, long ldo);
 int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out);
 
 // The regression training objectives on the device (gpr_grad.hip).  tri_inverse: X = L^-1 (m x m, upper triangle zeroed)
@@ -301,6 +308,10 @@ int pg_pi(hipStream_t st, long n, const double *mean, double sigma_nv, const lon
           double *pi, long ld, double *y);
 int pg_argmax(hipStream_t st, long n, int J, const double *probs, double *labels);
 int pg_init(hipStream_t st, int m, const double *Y, double *kappa, double *omega, double *f);
+
+// The multinomial label check of the host entries (nll.hip): v[i] an integer in [0, J), as "<who>: <name>[i]=.. is not a
+// class label in 0 .. J-1"; with all_named also max(v) + 1 == J, under negative_log_likelihood's message.
+int check_class_labels(const char *who, const char *name, const double *v, long n, int J, bool all_named);
 
 // host wait for a stream that polls an event instead of sleeping in hipStreamSynchronize (eig.hip)
 hipError_t stream_wait(hipStream_t st);

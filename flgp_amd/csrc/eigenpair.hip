@@ -1,12 +1,15 @@
 // Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products;
 // regression prediction, posterior variance and the training objectives with their gradients (kernels in
 // gpr.hip and gpr_grad.hip); the Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
-// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11); Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
+// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12);
+// Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
 // the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
+#include <string>
+#include <thread>
 #include <vector>
 
 using namespace flgp;
@@ -30,6 +33,7 @@ struct Rows {
   const int *d = nullptr;        // flgp_dev_hk's index argument: nullptr for a range
   const double *V = nullptr;
   long ld = 0;
+  int gathered_K = 0;            // the K of the last gather(): asking again for it does nothing
   DevBuf didx, vbuf;
   int check(const flgp_eigenpair *ep, const int *idx_, int m_, const char *who, const char *name) {
     for (int a = 0; a < m_; ++a) FLGP_REQUIRE(idx_[a] >= 0 && idx_[a] < ep->n, "%s: %s[%d]=%d out of range", who, name, a, idx_[a]);
@@ -46,10 +50,11 @@ struct Rows {
   }
   int gather(hipStream_t st, const flgp_eigenpair *ep, int K) {
     FLGP_TRY(resolve(st));
-    if (!d) { V = (const double *)ep->vectors.p + row0; ld = ep->n; return FLGP_OK; }
+    if (gathered_K == K) return FLGP_OK;
+    if (!d) { V = (const double *)ep->vectors.p + row0; ld = ep->n; gathered_K = K; return FLGP_OK; }
     FLGP_TRY(vbuf.alloc(sizeof(double) * (size_t)m * K));
     FLGP_TRY(flgp_dev_gather_rows(st, (const double *)ep->vectors.p, ep->n, d, m, K, vbuf.as<double>()));
-    V = vbuf.as<double>(); ld = m;
+    V = vbuf.as<double>(); ld = m; gathered_K = K;
     return FLGP_OK;
   }
 };
@@ -335,62 +340,85 @@ extern "C" int flgp_eigenpair_logit_marginal_likelihood(const flgp_eigenpair *ep
 }
 
 namespace {
-// The argument checks the two posterior entries share, under the caller's name; r0 / r1 take the row sets.
-int posterior_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, const int *idx1,
-                    int mnew, int max_iter, const double *mean, const double *cov, Rows &r0, Rows &r1) {
-  FLGP_REQUIRE(ep && idx0 && idx1 && Y && mean && cov, "%s: null pointer", who);
+// The argument checks the posterior entries share, under the caller's name; r0 / r1 take the row sets.  `others`: the
+// entry's remaining pointers are there.
+int posterior_check_rows(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1, int mnew,
+                         int max_iter, bool others, Rows &r0, Rows &r1) {
+  FLGP_REQUIRE(ep && idx0 && idx1 && others, "%s: null pointer", who);
   FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && max_iter >= 1,
                "%s: bad shape (K=%d of %d, m=%d, m_new=%d, max_iter=%d)", who, K, ep->K, m, mnew, max_iter);
   FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
-  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  return r1.check(ep, idx1, mnew, who, "idx1");
+}
+int posterior_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, const int *idx1,
+                    int mnew, int max_iter, const double *mean, const double *cov, Rows &r0, Rows &r1) {
+  FLGP_TRY(posterior_check_rows(who, ep, K, idx0, m, idx1, mnew, max_iter, Y && mean && cov, r0, r1));
   return check_labels(Y, nullptr, m, who);
+}
+int posterior_check_sigmas(const char *who, double sigma11, double sigma22) {
+  FLGP_REQUIRE(sigma11 >= 0.0 && std::isfinite(sigma11), "%s: sigma11=%g must be finite and >= 0", who, sigma11);
+  FLGP_REQUIRE(sigma22 >= 0.0 && std::isfinite(sigma22), "%s: sigma22=%g must be finite and >= 0", who, sigma22);
+  return FLGP_OK;
 }
 
 // posterior_distribution_classification (src/Utils.cpp:252-299) with C11 = HK(idx0, idx0) + sigma11 I,
 // C21 = HK(idx1, idx0) = V2 L V1^T, C22 = rowsum(V2 L .* V2) + sigma22.  mean = V2 L V1^T (Y - pi);
 // var_i = C22_i - v2_i^T M v2_i with M = X^T X, X = L_B^-1 sqrt(W) V1 L: O(m_new K^2), C21 is never formed.
-// The dense route of both posterior entries: the m x m C11 and B, whatever m is.
-int posterior_dense(const char *who, const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22, Rows &r0, int m,
-                    const double *Y, Rows &r1, int mnew, double tol, int max_iter, double *mean, double *cov, int *iters) {
-  Stream st;
-  FLGP_TRY(st.create());
+// The dense route of the posterior entries: the m x m C11 and B, whatever m is.  On the caller's stream, Y and the two
+// results (m_new each) on the device; synchronises.
+int posterior_dense_on(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
+                       Rows &r0, int m, const double *dY, Rows &r1, int mnew, double tol, int max_iter, double *dmean,
+                       double *dcov, int *iters) {
   GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));                    // G.l = exp(-t (1 - values))
-  DevBuf C, work, dY;
-  FLGP_TRY(hk_c11(st.s, ep, K, t, r0, sigma11, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
-  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(G.prepare(st, ep, K, t));                    // G.l = exp(-t (1 - values))
+  DevBuf C, work;
+  FLGP_TRY(hk_c11(st, ep, K, t, r0, sigma11, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
   // the mode (N = 1), then B factored again at the final f          (src/Utils.cpp:268-293)
   GpcNewton S;
   FLGP_TRY(S.alloc(m));
   int it = 0;
-  FLGP_TRY(S.run(st.s, C.as<double>(), dY.as<double>(), nullptr, tol, max_iter, who, &it));
+  FLGP_TRY(S.run(st, C.as<double>(), dY, nullptr, tol, max_iter, who, &it));
   if (iters) *iters = it;
-  FLGP_TRY(S.weights(st.s, C.as<double>(), dY.as<double>(), nullptr));
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  FLGP_TRY(r1.gather(st.s, ep, K));
-  DevBuf X, Mp, u, Wp, out, gw;
+  FLGP_TRY(S.weights(st, C.as<double>(), dY, nullptr));
+  FLGP_TRY(r0.gather(st, ep, K));
+  FLGP_TRY(r1.gather(st, ep, K));
+  DevBuf X, Mp, u, Wp, gw;
   const size_t we = (size_t)128 * K * K + 1024;
   FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
   FLGP_TRY(Mp.alloc(sizeof(double) * (size_t)K * (K + 1)));
   FLGP_TRY(u.alloc(sizeof(double) * (size_t)K));
   FLGP_TRY(Wp.alloc(sizeof(double) * (size_t)mnew * (K + 1)));
-  FLGP_TRY(out.alloc(sizeof(double) * (size_t)mnew));
   FLGP_TRY(gw.alloc(sizeof(double) * we));
-  FLGP_TRY(gpc_scale2(st.s, r0.V, r0.ld, S.sW.as<double>(), G.l.as<double>(), m, K, X.as<double>()));     // sqrt(W) V1 L
-  FLGP_TRY(chol_trsv(st.s, S.B.as<double>(), m, m, X.as<double>(), m, K, 1, S.flag.as<int>()));         // L_B^-1 (.)
-  FLGP_TRY(gemm_tn(st.s, K, K, m, X.as<double>(), m, X.as<double>(), m, Mp.as<double>(), gw.as<double>(), we));        // M = X^T X
-  FLGP_TRY(gemm_tn(st.s, K, 1, m, r0.V, r0.ld, S.resid.as<double>(), m, u.as<double>(), gw.as<double>(), we));         // V1^T (Y - pi)
-  FLGP_TRY(gpr_scale(st.s, u.as<double>(), G.l.as<double>(), nullptr, K, 1, Mp.as<double>() + (size_t)K * K));  // column K: L (.)
+  FLGP_TRY(gpc_scale2(st, r0.V, r0.ld, S.sW.as<double>(), G.l.as<double>(), m, K, X.as<double>()));     // sqrt(W) V1 L
+  FLGP_TRY(chol_trsv(st, S.B.as<double>(), m, m, X.as<double>(), m, K, 1, S.flag.as<int>()));         // L_B^-1 (.)
+  FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, Mp.as<double>(), gw.as<double>(), we));        // M = X^T X
+  FLGP_TRY(gemm_tn(st, K, 1, m, r0.V, r0.ld, S.resid.as<double>(), m, u.as<double>(), gw.as<double>(), we));         // V1^T (Y - pi)
+  FLGP_TRY(gpr_scale(st, u.as<double>(), G.l.as<double>(), nullptr, K, 1, Mp.as<double>() + (size_t)K * K));  // column K: L (.)
   {
-    ProfScope ps("posterior_dense_predict", st.s, 2.0 * mnew * K * (K + 1));
-    FLGP_TRY(gemm_nn(st.s, mnew, K + 1, K, r1.V, r1.ld, Mp.as<double>(), K, Wp.as<double>(), nullptr, 0));        // V2 [M | u]
-    FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, out.as<double>()));
+    ProfScope ps("posterior_dense_predict", st, 2.0 * mnew * K * (K + 1));
+    FLGP_TRY(gemm_nn(st, mnew, K + 1, K, r1.V, r1.ld, Mp.as<double>(), K, Wp.as<double>(), nullptr, 0));        // V2 [M | u]
+    FLGP_TRY(gpr_rowquad(st, r1.V, r1.ld, Wp.as<double>(), mnew, K, G.l.as<double>(), sigma22, dcov));
   }
-  FLGP_TRY(d2h(mean, Wp.as<double>() + (size_t)K * mnew, sizeof(double) * (size_t)mnew, st.s));
-  FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_HIP(hipMemcpyAsync(dmean, Wp.as<double>() + (size_t)K * mnew, sizeof(double) * (size_t)mnew, hipMemcpyDeviceToDevice, st));
   int bad = 0;
-  FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
+  FLGP_TRY(read_flag(st, S.flag.p, &bad));
   return GpcNewton::pivot_error(bad, who, 0);      // the loop checked its own factorisations: this is the one at the mode
+}
+
+// the binary entries' call of it: a stream of its own, Y up, mean and cov down
+int posterior_dense(const char *who, const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22, Rows &r0, int m,
+                    const double *Y, Rows &r1, int mnew, double tol, int max_iter, double *mean, double *cov, int *iters) {
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dY, dmean, dcov;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dcov.alloc(sizeof(double) * (size_t)mnew));
+  FLGP_TRY(posterior_dense_on(st.s, who, ep, K, t, sigma11, sigma22, r0, m, dY.as<double>(), r1, mnew, tol, max_iter,
+                              dmean.as<double>(), dcov.as<double>(), iters));
+  FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_TRY(d2h(cov, dcov.p, sizeof(double) * (size_t)mnew, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
 }
 }  // namespace
 
@@ -831,8 +859,7 @@ extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, d
   Rows r0, r1;
   FLGP_TRY(posterior_check(who, ep, K, idx0, m, Y, idx1, mnew, max_iter, mean, cov, r0, r1));
   FLGP_REQUIRE(std::isfinite(t), "%s: t=%g must be finite", who, t);
-  FLGP_REQUIRE(sigma11 >= 0.0 && std::isfinite(sigma11), "%s: sigma11=%g must be finite and >= 0", who, sigma11);
-  FLGP_REQUIRE(sigma22 >= 0.0 && std::isfinite(sigma22), "%s: sigma22=%g must be finite and >= 0", who, sigma22);
+  FLGP_TRY(posterior_check_sigmas(who, sigma11, sigma22));
   if (m <= K) return posterior_dense(who, ep, K, t, sigma11, sigma22, r0, m, Y, r1, mnew, tol, max_iter, mean, cov, iters);
 
   Stream st;
@@ -864,6 +891,186 @@ extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, d
   int bad = 0;
   FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
   return GpcNewton::pivot_error(bad, who, 0);
+}
+
+// ---- one-vs-rest logit posterior: J classes over one pass of the pair ------------------------------------
+namespace {
+// What one worker of the m > K route reuses across its classes: the weight-space loop's state, the label column and the
+// scratch of the operand.  Everything in it is overwritten before it is read, so a class's bits do not depend on which
+// worker ran it or on what the worker ran before.
+struct McWorker {
+  GpcWeightSpace S;
+  DevBuf dY, Li, Tb, wt;
+  size_t wi = 0;
+  int alloc(int m, int K) {
+    wi = (size_t)32 * 64 * K;
+    FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
+    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+    FLGP_TRY(wt.alloc(sizeof(double) * wi));
+    return S.alloc(m, K);
+  }
+  // device bytes of one worker: X, Q, the GEMM workspaces and the operand's scratch; `wide`: predict_rows' two row blocks
+  static double bytes(int m, int K, bool wide) {
+    const double k = K;
+    return 8.0 * ((double)m * k + 2.0 * k * k + (double)vt_work_elems(K, 1) + 10.0 * m + (64.0 + 32.0 * 64.0) * k + 2.0 * k) +
+           (wide ? 2.0 * 256.0 * (1 << 20) : 0.0);
+  }
+};
+
+// The shared body of the two entries.  nll == nullptr: flgp_eigenpair_logit_posterior_multiclass (mean and cov wanted).
+int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma11, double sigma22, const int *idx0,
+                         int m, const double *Y, const int *idx1, int mnew, double tol, int max_iter, int max_parallel,
+                         double *mean, double *cov, int *iters, const double *target, int n_samples, unsigned long long seed,
+                         double *nll) {
+  const char *who = "logit_posterior_multiclass";
+  FLGP_REQUIRE(J >= 1, "%s: J=%d must be at least 1", who, J);
+  Rows r0, r1;
+  const bool outputs = nll ? (target && !mean == !cov) : (mean && cov);
+  FLGP_TRY(posterior_check_rows(who, ep, K, idx0, m, idx1, mnew, max_iter, ts && Y && outputs, r0, r1));
+  for (int j = 0; j < J; ++j) FLGP_REQUIRE(std::isfinite(ts[j]), "%s: ts[%d]=%g must be finite", who, j, ts[j]);
+  FLGP_TRY(posterior_check_sigmas(who, sigma11, sigma22));
+  FLGP_TRY(check_class_labels(who, "Y", Y, m, J, false));
+  if (nll) {
+    FLGP_REQUIRE(n_samples >= 1, "%s: n_samples=%d must be at least 1", who, n_samples);
+    FLGP_REQUIRE((long)mnew <= (long)0x7FFFFFFF * 256 / J, "%s: bad shape (m_new=%d, J=%d)", who, mnew, J);
+    FLGP_TRY(check_class_labels(who, "target", target, mnew, J, true));
+  }
+  std::vector<int> its((size_t)J, 0);
+  char who_j[64];
+  auto name_class = [&](int j, char *buf) { std::snprintf(buf, sizeof(who_j), "%s: class %d", who, j); };
+
+  Stream st;
+  FLGP_TRY(st.create());
+  FLGP_TRY(r1.resolve(st.s));
+  const size_t col = (size_t)mnew, nj = sizeof(double) * col * J;
+  DevBuf dlab, dmean, dcov;
+  FLGP_TRY(upload(dlab, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(dmean.alloc(nj)); FLGP_TRY(dcov.alloc(nj));
+  if (m <= K) {
+    // the dense body per class, one after another; column j = (Y == j) is formed on the device
+    DevBuf dYj;
+    FLGP_TRY(dYj.alloc(sizeof(double) * (size_t)m));
+    for (int j = 0; j < J; ++j) {
+      name_class(j, who_j);
+      FLGP_TRY(gpc_class_indicator(st.s, dlab.as<double>(), m, j, dYj.as<double>()));
+      FLGP_TRY(posterior_dense_on(st.s, who_j, ep, K, ts[j], sigma11, sigma22, r0, m, dYj.as<double>(), r1, mnew, tol, max_iter,
+                                  dmean.as<double>() + j * col, dcov.as<double>() + j * col, &its[j]));
+    }
+  } else {
+    // shared and read-only from here: the row sets, the labels, V1.  Class j owns its spectrum weights and its operand
+    // (or, on the wide route, its columns of the result); a worker owns the loop's state and runs its classes in turn.
+    FLGP_TRY(r0.gather(st.s, ep, K));
+    FLGP_HIP(hipStreamSynchronize(st.s));
+    const bool fused = gpc_predict_rows_applicable(K);
+    const size_t ge = gpc_predict_operand_elems(K);
+    DevBuf Gf;
+    if (fused) FLGP_TRY(Gf.alloc(sizeof(double) * ge * J));
+    std::vector<GprCtx> ctx((size_t)J);
+    int workers = std::min(max_parallel < 1 ? 1 : max_parallel, J);
+    if (workers > 1) {       // no more than fit into 90 % of the free memory
+      size_t free_b = 0, total_b = 0;
+      FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+      const double fit = 0.9 * (double)free_b / McWorker::bytes(m, K, !fused);
+      if (fit < workers) workers = fit < 1.0 ? 1 : (int)fit;
+    }
+    std::vector<int> rcs((size_t)J, FLGP_OK);
+    std::vector<std::string> msgs((size_t)J);
+    // one class on a worker's stream: the binary entry's launches in the binary entry's order
+    auto one_class = [&](hipStream_t ws, McWorker &W, int j) -> int {
+      char name[64];
+      name_class(j, name);
+      GprCtx &G = ctx[(size_t)j];
+      FLGP_TRY(G.prepare(ws, ep, K, ts[j]));                      // ls = L^1/2, l = L
+      FLGP_TRY(gpc_class_indicator(ws, dlab.as<double>(), m, j, W.dY.as<double>()));
+      GpcWeightSpace &S = W.S;
+      S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
+      FLGP_TRY(S.run(ws, W.dY.as<double>(), tol, max_iter, name, &its[(size_t)j]));
+      FLGP_TRY(S.solve(ws, W.dY.as<double>()));
+      FLGP_TRY(S.scaled_beta(ws));
+      FLGP_TRY(tri_inverse(ws, S.L.Q.as<double>(), K, K, W.Li.as<double>(), K, W.Tb.as<double>(), W.wt.as<double>(), W.wi,
+                           S.flag.as<int>()));
+      FLGP_TRY(gpr_scale(ws, W.Li.as<double>(), nullptr, G.ls.as<double>(), K, K, W.Li.as<double>()));            // L_Q^-1 L^1/2
+      if (fused)
+        FLGP_TRY(gpc_predict_prep(ws, K, W.Li.as<double>(), S.L.u.as<double>(), Gf.as<double>() + ge * j));
+      else
+        FLGP_TRY(predict_rows(ws, ep, K, r1, W.Li.as<double>(), S.L.u.as<double>(), sigma22, dmean.as<double>() + j * col,
+                              dcov.as<double>() + j * col));
+      int bad = 0;
+      FLGP_TRY(read_flag(ws, S.flag.p, &bad));
+      return GpcNewton::pivot_error(bad, name, 0);
+    };
+    // worker w takes classes w, w + workers, ... and stops at its first failure: the lowest failing class is always run
+    auto run_worker = [&](hipStream_t ws, int w) -> int {
+      McWorker W;
+      W.S.L.sigma = sigma11; W.S.L.V1 = r0.V; W.S.L.ld1 = r0.ld;
+      FLGP_TRY(W.alloc(m, K));
+      for (int j = w; j < J; j += workers) {
+        rcs[(size_t)j] = one_class(ws, W, j);
+        if (rcs[(size_t)j] != FLGP_OK) { msgs[(size_t)j] = flgp_last_error(); break; }
+      }
+      return FLGP_OK;
+    };
+    if (workers == 1) {      // in line, on the entry's stream
+      FLGP_TRY(run_worker(st.s, 0));
+    } else {                 // one host thread and one stream per worker
+      int dev = 0;
+      FLGP_HIP(hipGetDevice(&dev));
+      auto run = [&, dev](int w) {
+        auto body = [&]() -> int {
+          FLGP_HIP(hipSetDevice(dev));
+          Stream ws;
+          FLGP_TRY(ws.create());
+          return run_worker(ws.s, w);
+        };
+        const int rc = body();
+        if (rc != FLGP_OK && rcs[(size_t)w] == FLGP_OK) { rcs[(size_t)w] = rc; msgs[(size_t)w] = flgp_last_error(); }
+      };
+      std::vector<std::thread> th;
+      for (int w = 0; w < workers; ++w) th.emplace_back(run, w);
+      for (auto &t : th) t.join();
+    }
+    for (int j = 0; j < J; ++j)
+      if (rcs[(size_t)j] != FLGP_OK) { set_error("%s", msgs[(size_t)j].c_str()); return rcs[(size_t)j]; }
+    // every worker's stream has been waited for: the J operands are in place
+    if (fused)
+      FLGP_TRY(gpc_predict_rows_multi(st.s, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, J, Gf.as<double>(),
+                                      sigma22, dmean.as<double>(), dcov.as<double>(), (long)mnew));
+  }
+  if (iters) std::copy(its.begin(), its.end(), iters);
+  DevBuf dtarget, dnll, work;
+  if (nll) {
+    FLGP_TRY(upload(dtarget, target, sizeof(double) * col, st.s));
+    FLGP_TRY(dnll.alloc(sizeof(double))); FLGP_TRY(work.alloc(flgp_dev_nll_workspace(mnew, J)));
+    FLGP_TRY(flgp_dev_nll_classification(st.s, dmean.as<double>(), dcov.as<double>(), dtarget.as<double>(), mnew, J, 1, n_samples,
+                                         seed, 0, nullptr, dnll.as<double>(), work.as<double>()));
+    FLGP_TRY(d2h(nll, dnll.p, sizeof(double), st.s));
+  }
+  if (mean) {
+    FLGP_TRY(d2h(mean, dmean.p, nj, st.s));
+    FLGP_TRY(d2h(cov, dcov.p, nj, st.s));
+  }
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+}  // namespace
+
+extern "C" int flgp_eigenpair_logit_posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma11,
+                                                         double sigma22, const int *idx0, int m, const double *Y, const int *idx1,
+                                                         int mnew, double tol, int max_iter, int max_parallel, double *mean,
+                                                         double *cov, int *iters) {
+  return posterior_multiclass(ep, K, ts, J, sigma11, sigma22, idx0, m, Y, idx1, mnew, tol, max_iter, max_parallel, mean, cov,
+                              iters, nullptr, 0, 0, nullptr);
+}
+
+extern "C" int flgp_eigenpair_logit_posterior_multiclass_nll(const flgp_eigenpair *ep, int K, const double *ts, int J,
+                                                             double sigma11, double sigma22, const int *idx0, int m,
+                                                             const double *Y, const int *idx1, int mnew, double tol, int max_iter,
+                                                             int max_parallel, double *mean, double *cov, int *iters,
+                                                             const double *target, int n_samples, unsigned long long seed,
+                                                             double *nll) {
+  FLGP_REQUIRE(nll, "logit_posterior_multiclass: null pointer");
+  return posterior_multiclass(ep, K, ts, J, sigma11, sigma22, idx0, m, Y, idx1, mnew, tol, max_iter, max_parallel, mean, cov,
+                              iters, target, n_samples, seed, nll);
 }
 
 // ---- Polya-Gamma Gibbs prediction: test_pgbinary_cpp and predict_logit_mult_gp_cpp (pg.hip) ---------------

@@ -490,6 +490,17 @@ __global__ void gpc_ws_fnew_kernel(const double *__restrict__ b, const double *_
   fnew[i] = pi + sigma * ((b[i] - (s * s) * pi) / D[i]);
 }
 
+// out = (labels == j): column j of the one-vs-rest indicator matrix, never stored as a matrix
+__global__ void gpc_class_indicator_kernel(const double *__restrict__ labels, int m, double j, double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) out[i] = labels[i] == j ? 1.0 : 0.0;
+}
+
+int gpc_class_indicator(hipStream_t st, const double *d_labels, int m, int j, double *d_out) {
+  hipLaunchKernelGGL(gpc_class_indicator_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_labels, m, (double)j, d_out);
+  return check_launch("gpc_class_indicator_kernel");
+}
+
 int gpc_ws_bd(hipStream_t st, const double *d_b, const double *d_D, int m, double *d_out) {
   hipLaunchKernelGGL(gpc_ws_bd_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_D, m, d_out);
   return check_launch("gpc_ws_bd_kernel");
@@ -538,37 +549,39 @@ __host__ __device__ constexpr int pr_stride(int R) { return R == 16 ? 16 : R + 1
 // lane squares and adds its four results (reg ascending), the four lane groups meet through two xor exchanges
 // ((g0 + g1) + (g2 + g3) on every lane) and the tiles of a row are added in ascending jt by one thread: the bits of a
 // row depend on that row and Gp alone -- not on mnew, the grid, the row's position or its neighbours.
+// The three steps are written once, for the single-operand kernel and the J-operand kernel below.
+
+// vs[k][r] = V(rows_{base + r}, k) for the block's R rows, zero past K and past mnew
 template <int RT>
-__global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_kernel(const double *__restrict__ V, long ld,
-                                                                      const int *__restrict__ idx, int row0, int mnew, int K,
-                                                                      int nks, int njt, const double *__restrict__ Gf, double c,
-                                                                      double *__restrict__ mean, double *__restrict__ cov) {
+__device__ __forceinline__ void pr_stage(const double *__restrict__ V, long ld, const int *__restrict__ idx, int row0, int mnew,
+                                         int K, int nks, long base, double *__restrict__ vs) {
   constexpr int R = 16 * RT, RS = pr_stride(R), KSTEP = PR_THREADS / R;
-  extern __shared__ double pr_lds[];
-  double *vs = pr_lds;                         // [4 nks][RS]
-  double *ts = pr_lds + (size_t)4 * nks * RS;  // [njt][R]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long base = (long)blockIdx.x * R;
-  {
-    // every load is unconditional (row and k clamped into the block's live part) so that four are in flight per thread;
-    // the zero padding is applied on the way into LDS
-    const int r = tid % R;
-    const long i = base + r;
-    const bool live = i < mnew;
-    const long ic = live ? i : (long)mnew - 1;
-    const double *src = V + (idx ? (long)idx[ic] : (long)row0 + ic);
-    for (int k0 = tid / R; k0 < 4 * nks; k0 += 4 * KSTEP) {
-      double v[4];
+  const int tid = threadIdx.x;
+  // every load is unconditional (row and k clamped into the block's live part) so that four are in flight per thread;
+  // the zero padding is applied on the way into LDS
+  const int r = tid % R;
+  const long i = base + r;
+  const bool live = i < mnew;
+  const long ic = live ? i : (long)mnew - 1;
+  const double *src = V + (idx ? (long)idx[ic] : (long)row0 + ic);
+  for (int k0 = tid / R; k0 < 4 * nks; k0 += 4 * KSTEP) {
+    double v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = src[(size_t)min(k0 + u * KSTEP, K - 1) * ld];
+    for (int u = 0; u < 4; ++u) v[u] = src[(size_t)min(k0 + u * KSTEP, K - 1) * ld];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int k = k0 + u * KSTEP;
-        if (k < 4 * nks) vs[(size_t)k * RS + r] = (live && k < K) ? v[u] : 0.0;
-      }
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + u * KSTEP;
+      if (k < 4 * nks) vs[(size_t)k * RS + r] = (live && k < K) ? v[u] : 0.0;
     }
   }
-  __syncthreads();
+}
+
+// the j-tiles of one operand Gf against the staged rows: ts[jt][r] = the tile's sum of squares, mean[base + r] = z_K
+template <int RT>
+__device__ __forceinline__ void pr_tiles(const double *__restrict__ Gf, const double *__restrict__ vs, double *__restrict__ ts,
+                                         int K, int nks, int njt, long base, int mnew, double *__restrict__ mean) {
+  constexpr int R = 16 * RT, RS = pr_stride(R);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, col = lane & 15;
   const int jlast = njt - 1, qK = (K & 15) >> 2, gK = K & 3;      // z_K: tile jlast, lane group gK, register qK
   for (int round = 0; round * PR_WAVES < njt; ++round) {
@@ -617,11 +630,62 @@ __global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_kernel(const doub
       }
     }
   }
-  __syncthreads();
+}
+
+// cov[base + r] = c + the row's tiles in ascending jt, one thread per row
+template <int RT>
+__device__ __forceinline__ void pr_rowsum(const double *__restrict__ ts, int njt, long base, int mnew, double c,
+                                          double *__restrict__ cov) {
+  constexpr int R = 16 * RT;
+  const int tid = threadIdx.x;
   if (tid < R && base + tid < mnew) {
     double s = 0.0;
     for (int jt = 0; jt < njt; ++jt) s += ts[(size_t)jt * R + tid];
     cov[base + tid] = c + s;
+  }
+}
+
+template <int RT>
+__global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_kernel(const double *__restrict__ V, long ld,
+                                                                      const int *__restrict__ idx, int row0, int mnew, int K,
+                                                                      int nks, int njt, const double *__restrict__ Gf, double c,
+                                                                      double *__restrict__ mean, double *__restrict__ cov) {
+  constexpr int R = 16 * RT, RS = pr_stride(R);
+  extern __shared__ double pr_lds[];
+  double *vs = pr_lds;                         // [4 nks][RS]
+  double *ts = pr_lds + (size_t)4 * nks * RS;  // [njt][R]
+  const long base = (long)blockIdx.x * R;
+  pr_stage<RT>(V, ld, idx, row0, mnew, K, nks, base, vs);
+  __syncthreads();
+  pr_tiles<RT>(Gf, vs, ts, K, nks, njt, base, mnew, mean);
+  __syncthreads();
+  pr_rowsum<RT>(ts, njt, base, mnew, c, cov);
+}
+
+// The same for J operands stored back to back (operand j at Gf + j * gf_elems, each written by gpc_predict_prep) into
+// column j of mean / cov (column-major at ldo): the block's rows are staged once and every operand is multiplied against
+// them, so the pair is read once instead of J times.  Per (row, operand) the steps are those of the kernel above, which
+// makes column j the bits of that kernel on operand j.  The workgroups walk the operands in the same order, so the one
+// in use stays in L2.  One ts scratch: a barrier after an operand's tiles and one after its row sums.
+template <int RT>
+__global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_multi_kernel(const double *__restrict__ V, long ld,
+                                                                            const int *__restrict__ idx, int row0, int mnew,
+                                                                            int K, int nks, int njt, int J,
+                                                                            const double *__restrict__ Gf, long gf_elems,
+                                                                            double c, double *__restrict__ mean,
+                                                                            double *__restrict__ cov, long ldo) {
+  constexpr int R = 16 * RT, RS = pr_stride(R);
+  extern __shared__ double pr_lds[];
+  double *vs = pr_lds;                         // [4 nks][RS]
+  double *ts = pr_lds + (size_t)4 * nks * RS;  // [njt][R]
+  const long base = (long)blockIdx.x * R;
+  pr_stage<RT>(V, ld, idx, row0, mnew, K, nks, base, vs);
+  __syncthreads();
+  for (int j = 0; j < J; ++j) {
+    pr_tiles<RT>(Gf + (size_t)j * gf_elems, vs, ts, K, nks, njt, base, mnew, mean + (size_t)j * ldo);
+    __syncthreads();
+    pr_rowsum<RT>(ts, njt, base, mnew, c, cov + (size_t)j * ldo);
+    if (j + 1 < J) __syncthreads();
   }
 }
 
@@ -646,17 +710,30 @@ bool gpc_predict_rows_applicable(int K) {
   return pr_rows(ceil_div(K, 4), ceil_div(K + 1, 16), lds > 0 ? lds : 65536) != 0;
 }
 
+int gpc_predict_prep(hipStream_t st, int K, const double *dG, const double *d_u, double *d_Gf) {
+  const long total = (long)gpc_predict_operand_elems(K);
+  hipLaunchKernelGGL(gpc_predict_prep_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, dG, d_u, K, ceil_div(K, 4), total, d_Gf);
+  return check_launch("gpc_predict_prep_kernel");
+}
+
+// the block of rows and the dynamic LDS of both kernels at this K; 0 rows: K does not fit the device's LDS
+static int pr_shape(const char *who, int K, int *nks, int *njt, size_t *lds) {
+  *nks = ceil_div(K, 4); *njt = ceil_div(K + 1, 16);
+  const int lds_dev = device_figures().lds_per_block;
+  const int R = pr_rows(*nks, *njt, lds_dev > 0 ? lds_dev : 65536);
+  if (!R) { set_error("%s: K=%d does not fit the device's LDS", who, K); return 0; }
+  *lds = pr_lds_bytes(R, *nks, *njt);
+  return R;
+}
+
 int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, const double *dG,
                      const double *d_u, double c, double *d_Gf, double *d_mean, double *d_cov) {
-  const int nks = ceil_div(K, 4), njt = ceil_div(K + 1, 16);
-  const int lds_dev = device_figures().lds_per_block;
-  const int R = pr_rows(nks, njt, lds_dev > 0 ? lds_dev : 65536);
-  if (!R) { set_error("gpc_predict_rows: K=%d does not fit the device's LDS", K); return FLGP_ERR_UNSUPPORTED; }
+  int nks, njt;
+  size_t lds;
+  const int R = pr_shape("gpc_predict_rows", K, &nks, &njt, &lds);
+  if (!R) return FLGP_ERR_UNSUPPORTED;
   ProfScope ps("gpc_predict_rows", st, (double)mnew * K * (K + 1));
-  const long total = (long)gpc_predict_operand_elems(K);
-  hipLaunchKernelGGL(gpc_predict_prep_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, dG, d_u, K, nks, total, d_Gf);
-  FLGP_TRY(check_launch("gpc_predict_prep_kernel"));
-  const size_t lds = pr_lds_bytes(R, nks, njt);
+  FLGP_TRY(gpc_predict_prep(st, K, dG, d_u, d_Gf));
   const dim3 grid(ceil_div(mnew, R)), block(PR_THREADS);
   auto launch = [&](auto kfn) -> int {
     if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -666,6 +743,25 @@ int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx
   if (R == 64) return launch(gpc_predict_rows_kernel<4>);
   if (R == 32) return launch(gpc_predict_rows_kernel<2>);
   return launch(gpc_predict_rows_kernel<1>);
+}
+
+int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int J,
+                           const double *d_Gf, double c, double *d_mean, double *d_cov, long ldo) {
+  int nks, njt;
+  size_t lds;
+  const int R = pr_shape("gpc_predict_rows_multi", K, &nks, &njt, &lds);
+  if (!R) return FLGP_ERR_UNSUPPORTED;
+  ProfScope ps("gpc_predict_rows_multi", st, (double)J * mnew * K * (K + 1));
+  const long gf_elems = (long)gpc_predict_operand_elems(K);
+  const dim3 grid(ceil_div(mnew, R)), block(PR_THREADS);
+  auto launch = [&](auto kfn) -> int {
+    if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kfn, grid, block, lds, st, dV, ld, d_idx, row0, mnew, K, nks, njt, J, d_Gf, gf_elems, c, d_mean, d_cov, ldo);
+    return check_launch("gpc_predict_rows_multi_kernel");
+  };
+  if (R == 64) return launch(gpc_predict_rows_multi_kernel<4>);
+  if (R == 32) return launch(gpc_predict_rows_multi_kernel<2>);
+  return launch(gpc_predict_rows_multi_kernel<1>);
 }
 
 // out[i] = c + sum_k Z(i, k)^2, k ascending, a thread per row (the K > GPC_PREDICT_KMAX route of the predictive rows)

@@ -90,6 +90,19 @@ int nll_reduce(hipStream_t st, long n, int J, int regression, double *d_work, do
 
 }  // namespace
 
+int flgp::check_class_labels(const char *who, const char *name, const double *v, long n, int J, bool all_named) {
+  double top = -1.0;
+  for (long i = 0; i < n; ++i) {
+    FLGP_REQUIRE(v[i] >= 0.0 && v[i] < J && v[i] == std::floor(v[i]), "%s: %s[%ld]=%g is not a class label in 0 .. %d", who, name, i,
+                 v[i], J - 1);
+    if (v[i] > top) top = v[i];
+  }
+  // the reference takes J from the labels: a posterior with another column count would be read out of bounds there
+  if (all_named)
+    FLGP_REQUIRE((int)top + 1 == J, "%s: the labels name %d classes, mean and cov have J=%d columns", who, (int)top + 1, J);
+  return FLGP_OK;
+}
+
 extern "C" size_t flgp_dev_nll_workspace(long n, int J) {
   if (n < 1 || J < 1) return 0;
   return sizeof(double) * (size_t)J * ((size_t)n + (size_t)nll_parts(n) + 1);
@@ -139,16 +152,7 @@ extern "C" int flgp_negative_log_likelihood(const double *mean, const double *co
   FLGP_REQUIRE(n >= 1 && J >= 1 && n <= (long)0x7FFFFFFF * 256 / J, "%s: bad shape (n=%ld, J=%d)", who, n, J);
   FLGP_REQUIRE(mul || J == 1, "%s: type \"%s\" takes one column (J=%d)", who, type, J);
   if (!reg) FLGP_REQUIRE(n_samples >= 1, "%s: n_samples=%d must be at least 1", who, n_samples);
-  if (mul) {
-    double top = -1.0;
-    for (long i = 0; i < n; ++i) {
-      FLGP_REQUIRE(target[i] >= 0.0 && target[i] < J && target[i] == std::floor(target[i]),
-                   "%s: target[%ld]=%g is not a class label in 0 .. %d", who, i, target[i], J - 1);
-      if (target[i] > top) top = target[i];
-    }
-    // the reference takes J from the labels: a posterior with another column count would be read out of bounds there
-    FLGP_REQUIRE((int)top + 1 == J, "%s: the labels name %d classes, mean and cov have J=%d columns", who, (int)top + 1, J);
-  }
+  if (mul) FLGP_TRY(check_class_labels(who, "target", target, n, J, true));
   Stream st;
   FLGP_TRY(st.create());
   const size_t nj = sizeof(double) * (size_t)n * J;
