@@ -55,6 +55,8 @@ _SIGNATURES = {
     "flgp_eigenpair_predict_regression": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_double, c_double, c_double, P]),
     "flgp_eigenpair_predict_regression_different": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_double, P, c_double, P]),
     "flgp_eigenpair_posterior_variance": (c_int, [P, c_int, P, c_int, P, c_int, c_double, c_double, c_double, P]),
+    "flgp_eigenpair_regression_posterior": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_double, P, c_int, c_double, P, P,
+                                                    P, P, P]),
     "flgp_logit_la_marginal_likelihood": (c_int, [P, c_int, P, P, c_double, c_int, P, P]),
     "flgp_eigenpair_logit_marginal_likelihood": (c_int, [P, c_int, c_double, c_double, P, c_int, P, P, c_double, c_int, P, P]),
     "flgp_eigenpair_posterior_classification": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_double,

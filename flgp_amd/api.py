@@ -358,6 +358,55 @@ class ResidentEigenPair:
                                                            float(pars[0]), float(pars[1]), float(sigma), _ptr(out)))
         return out
 
+    def regression_posterior(self, Y, idx0, idx1, K, pars, sigma, noisepar="same", target=None, train=True,
+                             return_posterior=True):
+        """The testing step of the four ``fit_*_regression_gp_cpp`` drivers (src/Fit.cpp:70-79) in one call
+        (flgp_eigenpair_regression_posterior, include/flgp_hip.h): ``predict_regression_cpp`` on the training rows and
+        on the new rows and ``posterior_covariance_regression`` at ``(pars[0], pars[1])``.  ``pars`` as
+        ``predict_regression_cpp``.  m <= K gives the three existing methods' bits; m > K solves in weight space (K x K
+        systems, idx0 / idx1 / Y uploaded and V1 gathered once) and reads the rows from the pair in place, in one fused
+        kernel per row set; there cov >= pars[1] + sigma exactly.  Returns the drivers' list shape
+        ``{"Y_pred": {"train", "test"}, "posterior": {"mean", "cov"}}`` (m x q, m_new x q Fortran-ordered; "mean" is
+        "test").  ``train=False`` skips the training rows ("train" is None).  With ``target`` (m_new values, q = 1) the
+        result is scored on the device as ``negative_log_likelihood(mean, cov, target, "regression")`` and "nll" is
+        added; ``return_posterior=False`` then brings down that one number only."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        m, mnew = idx0.size, idx1.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx0")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        q = Y.shape[1]
+        if noisepar not in ("same", "different"):
+            raise FlgpError(-3, 'regression_posterior: noisepar must be "same" or "different"')
+        nz = np.ascontiguousarray(np.asarray(pars[1:], dtype=np.float64).reshape(-1))
+        if noisepar == "different" and nz.size != m:
+            raise ValueError('noisepar="different" needs one noise variance per training row: pars = (t, noise_1 .. noise_m)')
+        if noisepar == "same":
+            nz = nz[:1].copy()
+        if target is None and not return_posterior:
+            raise ValueError("return_posterior=False needs a target to score")
+        nll = None
+        if target is not None:
+            target = np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1))
+            if target.size != mnew:
+                raise ValueError("target must have one entry per row of idx1")
+            nll = ctypes.c_double()
+        tr = te = cov = None
+        if return_posterior:
+            tr = np.zeros((m, q), order="F") if train else None
+            te = np.zeros((mnew, q), order="F"); cov = np.zeros(mnew)
+        check(_lib.lib().flgp_eigenpair_regression_posterior(self._h, int(K), _ptr(idx0), m, _ptr(idx1), mnew, _ptr(Y), q,
+                                                             float(pars[0]), _ptr(nz), nz.size, float(sigma), _ptr(tr), _ptr(te),
+                                                             _ptr(cov), _ptr(target), ctypes.addressof(nll) if nll is not None else None))
+        out = {}
+        if return_posterior:
+            out["Y_pred"] = {"train": tr, "test": te}
+            out["posterior"] = {"mean": te, "cov": cov}
+        if nll is not None:
+            out["nll"] = nll.value
+        return out
+
     def marginal_log_likelihood_logit_la(self, K, t, idx, Y, N=None, sigma=1e-3, tol=1e-5, max_iter=100, return_iters=False):
         """The objective of the logit drivers' hyper-parameter search (negative_marginal_likelihood_logit_cpp,
         src/train.cpp:28-34, negated back): ``marginal_log_likelihood_logit_la_cpp(HK(idx, idx) + sigma I, Y, N)`` with C

@@ -211,6 +211,7 @@ int gpr_add_diag(hipStream_t st, double *dA, int N, double c);
 int gpr_add_diag_vec(hipStream_t st, double *dA, int N, const double *d_v);
 int gpr_rowscale_ld(hipStream_t st, const double *dM, long ldm, const double *d_a, int rows, int cols, double *d_out);
 int gpr_zinv(hipStream_t st, const double *d_noise, double sigma, int m, double *d_zinv);
+int gpr_scalar_mul(hipStream_t st, const double *d_x, double s, int n, double *d_out);   // out = s x
 int gpr_rowquad(hipStream_t st, const double *dV2, long ld2, const double *dW, int mnew, int K, const double *d_l, double c,
                 double *d_cov);
 int gpr_rowdot(hipStream_t st, const double *dC21, const double *dAl, int mnew, int m, const double *dV2, long ld2, int K,
@@ -269,6 +270,18 @@ int gpc_predict_prep(hipStream_t st, int K, const double *dG, const double *d_u,
 int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int J,
                            const double *d_Gf, double c, double *d_mean, double *d_cov, long ldo);
 int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out);
+// The rows of the regression posterior for m > K (gpc.hip, beside the kernels above whose staging and row
+// sums they share): mean(i, 0:q) = U^T v_i (d_mean column-major at ldo) and cov_i = c + |G v_i|^2, the operand
+// Gp = [G ; U^T] ((K + q) x K; U K x q at ld K) written once by gpr_predict_prep into gpr_predict_operand_elems(K, q)
+// doubles.  dG == nullptr writes zeros for G; d_cov == nullptr skips the triangle's tiles: the mean rows only.  A mean's
+// bits do not depend on either.  For K <= GPC_PREDICT_KMAX and q <= GPR_PREDICT_QMAX on a device whose LDS holds 16 rows
+// (gpr_predict_rows_applicable); beyond, the caller takes the GEMM route.
+constexpr int GPR_PREDICT_QMAX = 64;
+size_t gpr_predict_operand_elems(int K, int q);
+bool gpr_predict_rows_applicable(int K, int q);
+int gpr_predict_prep(hipStream_t st, int K, int q, const double *dG, const double *dU, double *d_Gf);
+int gpr_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int q,
+                     const double *d_Gf, double c, double *d_mean, long ldo, double *d_cov);
 
 // The regression training objectives on the device (gpr_grad.hip).  tri_inverse: X = L^-1 (m x m, upper triangle zeroed)
 // for a lower factor of chol_blocked; dT holds 64 x m doubles, `work` (we doubles) bounds the GEMM's k-split.

@@ -1,6 +1,7 @@
 // Consumers of the device-resident EigenPair (include/flgp_hip.h; the pair itself is made in capi.hip): the V products;
 // regression prediction, posterior variance and the training objectives with their gradients (kernels in
-// gpr.hip and gpr_grad.hip); the Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
+// gpr.hip and gpr_grad.hip; the drivers' whole testing step in one call, in weight space for m > K: DESIGN 8 f-13); the
+// Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
 // 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12);
 // Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
@@ -168,17 +169,18 @@ int woodbury_step(hipStream_t st, GprCtx &G, int K, int q, const double *M, cons
 
 // predict_regression_cpp (reference src/Predict.cpp:40-110): noise_vec == nullptr is noisepar = "same" (one variance
 // `noise` for every training row), otherwise "different" (noise_vec[a] for row a, the reference's pars[1..m]).
-int predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1, int mnew, const double *Y,
-                       int q, double t, double noise, const double *noise_vec, double sigma, double *Y_pred) {
-  FLGP_REQUIRE(ep && idx0 && idx1 && Y && Y_pred, "predict_regression: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && q >= 1, "predict_regression: bad shape (K=%d m=%d m_new=%d q=%d)", K, m, mnew, q);
+// `who` names the entry in every message (the regression posterior runs this body for m <= K).
+int predict_regression(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1, int mnew,
+                       const double *Y, int q, double t, double noise, const double *noise_vec, double sigma, double *Y_pred) {
+  FLGP_REQUIRE(ep && idx0 && idx1 && Y && Y_pred, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1 && q >= 1, "%s: bad shape (K=%d m=%d m_new=%d q=%d)", who, K, m, mnew, q);
   if (noise_vec)
-    for (int a = 0; a < m; ++a) FLGP_REQUIRE(noise_vec[a] + sigma > 0.0, "predict_regression: noise[%d] + sigma must be positive", a);
+    for (int a = 0; a < m; ++a) FLGP_REQUIRE(noise_vec[a] + sigma > 0.0, "%s: noise[%d] + sigma must be positive", who, a);
   else
-    FLGP_REQUIRE(noise + sigma > 0.0, "predict_regression: noise + sigma must be positive");
+    FLGP_REQUIRE(noise + sigma > 0.0, "%s: noise + sigma must be positive", who);
   Rows r0, r1;
-  FLGP_TRY(r0.check(ep, idx0, m, "predict_regression", "idx0"));
-  FLGP_TRY(r1.check(ep, idx1, mnew, "predict_regression", "idx1"));
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
   Stream st;
   FLGP_TRY(st.create());
   GprCtx G;
@@ -224,32 +226,34 @@ int predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, 
     FLGP_TRY(gemm_nn(st.s, mnew, q, K, r1.V, r1.ld, T1.as<double>(), K, out.as<double>(), nullptr, 0));    // :108-109
   }
   FLGP_TRY(d2h(Y_pred, out.p, sizeof(double) * (size_t)mnew * q, st.s));
-  return G.verdict(st.s, "predict_regression");
+  return G.verdict(st.s, who);
 }
 }  // namespace
 
 extern "C" int flgp_eigenpair_predict_regression(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
                                                  int mnew, const double *Y, int q, double t, double noise, double sigma,
                                                  double *Y_pred) {
-  return predict_regression(ep, K, idx0, m, idx1, mnew, Y, q, t, noise, nullptr, sigma, Y_pred);
+  return predict_regression("predict_regression", ep, K, idx0, m, idx1, mnew, Y, q, t, noise, nullptr, sigma, Y_pred);
 }
 
 extern "C" int flgp_eigenpair_predict_regression_different(const flgp_eigenpair *ep, int K, const int *idx0, int m,
                                                            const int *idx1, int mnew, const double *Y, int q, double t,
                                                            const double *noise, double sigma, double *Y_pred) {
   FLGP_REQUIRE(noise, "predict_regression: null pointer");
-  return predict_regression(ep, K, idx0, m, idx1, mnew, Y, q, t, 0.0, noise, sigma, Y_pred);
+  return predict_regression("predict_regression", ep, K, idx0, m, idx1, mnew, Y, q, t, 0.0, noise, sigma, Y_pred);
 }
 
-extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
-                                                 int mnew, double t, double var, double sigma, double *cov) {
-  FLGP_REQUIRE(ep && idx0 && idx1 && cov, "posterior_variance: null pointer");
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1, "posterior_variance: bad shape (K=%d m=%d m_new=%d)", K, m, mnew);
+namespace {
+// posterior_covariance_regression (reference src/Utils.cpp:214-250), under the caller's name as predict_regression
+int posterior_variance(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1, int mnew,
+                       double t, double var, double sigma, double *cov) {
+  FLGP_REQUIRE(ep && idx0 && idx1 && cov, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && mnew >= 1, "%s: bad shape (K=%d m=%d m_new=%d)", who, K, m, mnew);
   const double c = var + sigma;
-  FLGP_REQUIRE(c > 0.0, "posterior_variance: var + sigma must be positive");
+  FLGP_REQUIRE(c > 0.0, "%s: var + sigma must be positive", who);
   Rows r0, r1;
-  FLGP_TRY(r0.check(ep, idx0, m, "posterior_variance", "idx0"));
-  FLGP_TRY(r1.check(ep, idx1, mnew, "posterior_variance", "idx1"));
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
   Stream st;
   FLGP_TRY(st.create());
   GprCtx G;
@@ -282,7 +286,13 @@ extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K
     FLGP_TRY(gpr_rowquad(st.s, r1.V, r1.ld, W.as<double>(), mnew, K, G.l.as<double>(), c, out.as<double>()));
   }
   FLGP_TRY(d2h(cov, out.p, sizeof(double) * (size_t)mnew, st.s));
-  return G.verdict(st.s, "posterior_variance");
+  return G.verdict(st.s, who);
+}
+}  // namespace
+
+extern "C" int flgp_eigenpair_posterior_variance(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
+                                                 int mnew, double t, double var, double sigma, double *cov) {
+  return posterior_variance("posterior_variance", ep, K, idx0, m, idx1, mnew, t, var, sigma, cov);
 }
 
 // ---- classification consumers: the Laplace approximation of the logit GP on the device (gpc.hip) ---------
@@ -1071,6 +1081,167 @@ extern "C" int flgp_eigenpair_logit_posterior_multiclass_nll(const flgp_eigenpai
   FLGP_REQUIRE(nll, "logit_posterior_multiclass: null pointer");
   return posterior_multiclass(ep, K, ts, J, sigma11, sigma22, idx0, m, Y, idx1, mnew, tol, max_iter, max_parallel, mean, cov,
                               iters, target, n_samples, seed, nll);
+}
+
+// ---- regression posterior: the drivers' testing step (src/Fit.cpp:70-79) in one call --------------------
+namespace {
+// mean(i, 0:q) = U^T v_i (dmean at ld r.m) and, with dcov, cov_i = c + |G v_i|^2 for the rows r of the pair.  Gf: the fused
+// kernel's operand (gpr_predict_prep on G and U), the rows read in place.  Gf == nullptr: the GEMM route of predict_rows,
+// Z = V G^T and its row sums of squares and a K-wide product for the mean, in row blocks of at most 256 MB.
+int regression_rows(hipStream_t st, const flgp_eigenpair *ep, int K, int q, Rows &r, const double *G, const double *U,
+                    const double *Gf, double c, double *dmean, double *dcov) {
+  FLGP_TRY(r.resolve(st));
+  const double *dvec = (const double *)ep->vectors.p;
+  if (Gf) return gpr_predict_rows(st, dvec, ep->n, r.d, r.row0, r.m, K, q, Gf, c, dmean, (long)r.m, dcov);
+  ProfScope ps("gpr_predict_rows_wide", st, 2.0 * r.m * K * (dcov ? K + q : q));
+  const int rb = (int)std::min<size_t>((size_t)r.m, std::max<size_t>(64, (((size_t)256 << 20) / (sizeof(double) * K)) / 64 * 64));
+  DevBuf Z, Vb;
+  if (dcov) FLGP_TRY(Z.alloc(sizeof(double) * (size_t)rb * K));
+  if (r.d) FLGP_TRY(Vb.alloc(sizeof(double) * (size_t)rb * K));
+  for (int o = 0; o < r.m; o += rb) {
+    const int rows = std::min(rb, r.m - o);
+    const double *V = dvec + r.row0 + o;
+    long ld = ep->n;
+    if (r.d) {
+      FLGP_TRY(flgp_dev_gather_rows(st, dvec, ep->n, r.d + o, rows, K, Vb.as<double>()));
+      V = Vb.as<double>(); ld = rows;
+    }
+    if (dcov) {
+      FLGP_TRY(gemm_launch(st, rows, K, K, 1.0, V, 1, ld, G, K, 1, 0.0, nullptr, 0, 0, Z.as<double>(), 1, rows, nullptr, 0, 0.0,
+                           nullptr));                                                                 // Z = V2 G^T
+      FLGP_TRY(gpc_rowsumsq_add(st, Z.as<double>(), rows, rows, K, c, dcov + o));
+    }
+    FLGP_TRY(gemm_launch(st, rows, q, K, 1.0, V, 1, ld, U, 1, K, 0.0, nullptr, 0, 0, dmean + o, 1, (long)r.m, nullptr, 0, 0.0,
+                         nullptr));                                                                   // V2 U into rows o ..
+  }
+  return FLGP_OK;
+}
+
+// m <= K: the three existing bodies, unchanged, under this entry's name; the score is the host entry on their results
+int regression_posterior_dense(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
+                               int mnew, const double *Y, int q, double t, const double *noise, bool different, double sigma,
+                               double *train_pred, double *test_pred, double *cov, const double *target, double *nll) {
+  const double *nv = different ? noise : nullptr;
+  std::vector<double> tp, cv;
+  if (nll && !test_pred) { tp.resize((size_t)mnew * q); test_pred = tp.data(); }
+  if (nll && !cov) { cv.resize((size_t)mnew); cov = cv.data(); }
+  if (train_pred) FLGP_TRY(predict_regression(who, ep, K, idx0, m, idx0, m, Y, q, t, noise[0], nv, sigma, train_pred));
+  if (test_pred) FLGP_TRY(predict_regression(who, ep, K, idx0, m, idx1, mnew, Y, q, t, noise[0], nv, sigma, test_pred));
+  if (cov) FLGP_TRY(posterior_variance(who, ep, K, idx0, m, idx1, mnew, t, noise[0], sigma, cov));
+  if (nll) FLGP_TRY(flgp_negative_log_likelihood(test_pred, cov, target, mnew, 1, "regression", 1, 0, nll, nullptr));
+  return FLGP_OK;
+}
+}  // namespace
+
+// m > K in weight space.  With Phi = V1 L^1/2 and c = noise[0] + sigma:
+//   "same":       Q = Phi^T Phi + c I,                   beta = Q^-1 L^1/2 V1^T Y        (push-through of Phi^T (Phi Phi^T + c I)^-1)
+//   "different":  Q_d = I + L^1/2 V1^T Z^-1 V1 L^1/2,    beta = Q_d^-1 L^1/2 V1^T Z^-1 Y,  Z = diag(noise_a + sigma)
+//   mean = V2 L^1/2 beta,   var_i = c + |sqrt(c) L_Q^-1 L^1/2 v2_i|^2   with Q = Phi^T Phi + c I = L_Q L_Q^T in both models
+// (C22_i - beta_i of src/Utils.cpp:238-246 is c + c u^T Q^-1 u with u = L^1/2 v2_i: no subtraction is left, var_i >= c).
+extern "C" int flgp_eigenpair_regression_posterior(const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
+                                                   int mnew, const double *Y, int q, double t, const double *noise,
+                                                   int n_noise, double sigma, double *train_pred, double *test_pred,
+                                                   double *cov, const double *target, double *nll) {
+  const char *who = "regression_posterior";
+  // what needs neither the pair nor the arrays comes first
+  FLGP_REQUIRE(K >= 1 && m >= 1 && mnew >= 1 && q >= 1, "%s: bad shape (K=%d, m=%d, m_new=%d, q=%d)", who, K, m, mnew, q);
+  FLGP_REQUIRE(n_noise == 1 || n_noise == m, "%s: n_noise=%d must be 1 (\"same\") or m=%d (\"different\")", who, n_noise, m);
+  FLGP_REQUIRE(!target == !nll, "%s: target and nll must be given together", who);
+  FLGP_REQUIRE(!target || q == 1, "%s: the score takes one column (q=%d)", who, q);
+  FLGP_REQUIRE(std::isfinite(t) && std::isfinite(sigma), "%s: t=%g and sigma=%g must be finite", who, t, sigma);
+  FLGP_REQUIRE(ep && idx0 && idx1 && Y && noise, "%s: null pointer", who);
+  FLGP_REQUIRE(train_pred || test_pred || cov || nll, "%s: null pointer (no output is wanted)", who);
+  FLGP_REQUIRE(K <= ep->K, "%s: bad shape (K=%d of %d)", who, K, ep->K);
+  for (int a = 0; a < n_noise; ++a)
+    FLGP_REQUIRE(noise[a] + sigma > 0.0, "%s: noise[%d] + sigma must be positive", who, a);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  const bool different = n_noise != 1;
+  if (m <= K)
+    return regression_posterior_dense(who, ep, K, idx0, m, idx1, mnew, Y, q, t, noise, different, sigma, train_pred, test_pred,
+                                      cov, target, nll);
+
+  const bool want_cov = cov || nll, want_test = test_pred || want_cov;
+  const double c = noise[0] + sigma;
+  Stream st;
+  FLGP_TRY(st.create());
+  GprCtx G;
+  FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = L^1/2
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  DevBuf dY, dnoise, zinv, ZV, ZY, M, S, Qd, Qs, U, work;
+  const size_t we = vt_work_elems(K, q);
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * q, st.s));
+  FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Qd.alloc(sizeof(double) * (size_t)K * K));
+  FLGP_TRY(S.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(U.alloc(sizeof(double) * (size_t)K * q));
+  FLGP_TRY(work.alloc(sizeof(double) * we));
+  const double *ls = G.ls.as<double>();
+  int *flag = G.flag.as<int>();
+  // the mean's system: M = V1^T Z^-1 V1, S = V1^T Z^-1 Y ("same": Z = I and c on Q's diagonal)
+  const double *Vz = r0.V, *Yz = dY.as<double>();
+  long ldz = r0.ld;
+  if (different) {
+    FLGP_TRY(upload(dnoise, noise, sizeof(double) * (size_t)m, st.s));
+    FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
+    FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
+    FLGP_TRY(gpr_zinv(st.s, dnoise.as<double>(), sigma, m, zinv.as<double>()));
+    FLGP_TRY(gpr_rowscale_ld(st.s, r0.V, r0.ld, zinv.as<double>(), m, K, ZV.as<double>()));
+    FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, zinv.as<double>(), m, q, ZY.as<double>()));
+    Vz = ZV.as<double>(); ldz = m; Yz = ZY.as<double>();
+  }
+  FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, Vz, ldz, M.as<double>(), work.as<double>(), we));
+  FLGP_TRY(gemm_tn(st.s, K, q, m, r0.V, r0.ld, Yz, m, S.as<double>(), work.as<double>(), we));
+  FLGP_TRY(gpr_q(st.s, M.as<double>(), ls, K, different ? 1.0 : c, Qd.as<double>()));
+  FLGP_TRY(chol_blocked(st.s, Qd.as<double>(), K, K, flag));
+  FLGP_TRY(gpr_scale(st.s, S.as<double>(), ls, nullptr, K, q, U.as<double>()));                          // L^1/2 S
+  FLGP_TRY(chol_trsv(st.s, Qd.as<double>(), K, K, U.as<double>(), K, q, 3, flag));                        // beta
+  FLGP_TRY(gpr_scale(st.s, U.as<double>(), ls, nullptr, K, q, U.as<double>()));                          // U = L^1/2 beta
+  // the variance's operand: sqrt(c) L_Q^-1 L^1/2; "different" factors Q_s = L^1/2 V1^T V1 L^1/2 + c I beside Q_d
+  DevBuf Li, Tb, wt, lsc;
+  if (want_cov) {
+    const double *LQ = Qd.as<double>();
+    if (different) {
+      FLGP_TRY(Qs.alloc(sizeof(double) * (size_t)K * K));
+      FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, r0.V, r0.ld, M.as<double>(), work.as<double>(), we));
+      FLGP_TRY(gpr_q(st.s, M.as<double>(), ls, K, c, Qs.as<double>()));
+      FLGP_TRY(chol_blocked(st.s, Qs.as<double>(), K, K, flag));
+      LQ = Qs.as<double>();
+    }
+    const size_t wi = (size_t)32 * 64 * K;
+    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+    FLGP_TRY(wt.alloc(sizeof(double) * wi)); FLGP_TRY(lsc.alloc(sizeof(double) * (size_t)K));
+    FLGP_TRY(tri_inverse(st.s, LQ, K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, flag));
+    FLGP_TRY(gpr_scalar_mul(st.s, ls, std::sqrt(c), K, lsc.as<double>()));
+    FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, lsc.as<double>(), K, K, Li.as<double>()));
+  }
+  const double *Gm = want_cov ? Li.as<double>() : nullptr;
+  DevBuf Gf;
+  if (gpr_predict_rows_applicable(K, q)) {
+    FLGP_TRY(Gf.alloc(sizeof(double) * gpr_predict_operand_elems(K, q)));
+    FLGP_TRY(gpr_predict_prep(st.s, K, q, Gm, U.as<double>(), Gf.as<double>()));
+  }
+  const double *gf = Gf.p ? Gf.as<double>() : nullptr;
+  DevBuf dtrain, dmean, dcov, dtarget, dnll, nwork;
+  if (train_pred) {           // the training rows through the same kernel: the mean rows only
+    FLGP_TRY(dtrain.alloc(sizeof(double) * (size_t)m * q));
+    FLGP_TRY(regression_rows(st.s, ep, K, q, r0, Gm, U.as<double>(), gf, c, dtrain.as<double>(), nullptr));
+    FLGP_TRY(d2h(train_pred, dtrain.p, sizeof(double) * (size_t)m * q, st.s));
+  }
+  if (want_test) {
+    FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)mnew * q));
+    if (want_cov) FLGP_TRY(dcov.alloc(sizeof(double) * (size_t)mnew));
+    FLGP_TRY(regression_rows(st.s, ep, K, q, r1, Gm, U.as<double>(), gf, c, dmean.as<double>(), want_cov ? dcov.as<double>() : nullptr));
+  }
+  if (nll) {                  // scored where it lies, before anything is copied
+    FLGP_TRY(upload(dtarget, target, sizeof(double) * (size_t)mnew, st.s));
+    FLGP_TRY(dnll.alloc(sizeof(double))); FLGP_TRY(nwork.alloc(flgp_dev_nll_workspace(mnew, 1)));
+    FLGP_TRY(flgp_dev_nll_regression(st.s, dmean.as<double>(), dcov.as<double>(), dtarget.as<double>(), mnew, nullptr,
+                                     dnll.as<double>(), nwork.as<double>()));
+    FLGP_TRY(d2h(nll, dnll.p, sizeof(double), st.s));
+  }
+  if (test_pred) FLGP_TRY(d2h(test_pred, dmean.p, sizeof(double) * (size_t)mnew * q, st.s));
+  if (cov) FLGP_TRY(d2h(cov, dcov.p, sizeof(double) * (size_t)mnew, st.s));
+  return G.verdict(st.s, who);
 }
 
 // ---- Polya-Gamma Gibbs prediction: test_pgbinary_cpp and predict_logit_mult_gp_cpp (pg.hip) ---------------

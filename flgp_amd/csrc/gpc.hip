@@ -7,6 +7,8 @@
 // blocked and right-looking: a 64-column diagonal panel factored in the registers of one wave, the panel column solved
 // by a grid of waves, the trailing update through the MFMA GEMM.  gpr.hip's one-workgroup chol_solve stays as it is for
 // the regression entries (their bits do not change).  Everything is fixed-order: two calls give the same bits.
+// The fused predictive rows of the logit posterior are here too, and beside them the rows of the
+// regression posterior (f-13), which share their staging and row sums.
 #include "common.h"
 
 namespace flgp {
@@ -762,6 +764,144 @@ int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int 
   if (R == 64) return launch(gpc_predict_rows_multi_kernel<4>);
   if (R == 32) return launch(gpc_predict_rows_multi_kernel<2>);
   return launch(gpc_predict_rows_multi_kernel<1>);
+}
+
+// ---- the regression posterior's rows: q mean rows under the triangle ------------------------------------
+// The operand Gp = [G ; U^T] ((K + q) x K: G lower triangular at ld K, or nullptr for zeros when no variance is wanted;
+// U K x q at ld K) in the fragment order of gpc_predict_prep_kernel, njt = ceil((K + q) / 16) j-tiles.
+__global__ void gpr_predict_prep_kernel(const double *__restrict__ G, const double *__restrict__ U, int K, int q, int nks,
+                                        long total, double *__restrict__ Gf) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int lane = (int)(e & 63);
+  const long f = e >> 6;
+  const int ks = (int)(f % nks), jt = (int)(f / nks);
+  const int j = 16 * jt + (lane & 15), k = 4 * ks + (lane >> 4);
+  double v = 0.0;
+  if (k < K) {
+    if (j < K) v = (G && k <= j) ? G[(size_t)k * K + j] : 0.0;
+    else if (j < K + q) v = U[(size_t)(j - K) * K + k];
+  }
+  Gf[e] = v;
+}
+
+// pr_tiles for that operand, the tiles jt0 .. njt - 1: a tile wholly inside the triangle (16 (jt + 1) <= K) runs the k steps
+// below 4 (jt + 1), every tile that holds a mean row runs all nks.  Rows j < K are squared into ts as in pr_tiles (skipped
+// when ts is nullptr: no variance is wanted and jt0 = K / 16, the first tile with a mean row); mean row K + col comes from
+// tile (K + col) / 16, lane group (K + col) & 3, register ((K + col) & 15) >> 2 and goes to mean[col * ldo + i].  For q = 1
+// the steps, the sums and the stored mean are pr_tiles' own.
+template <int RT>
+__device__ __forceinline__ void pr_tiles_q(const double *__restrict__ Gf, const double *__restrict__ vs, double *__restrict__ ts,
+                                           int K, int q, int nks, int njt, int jt0, long base, int mnew,
+                                           double *__restrict__ mean, long ldo) {
+  constexpr int R = 16 * RT, RS = pr_stride(R);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, col = lane & 15;
+  const int jlast = njt - 1, ntiles = njt - jt0;
+  for (int round = 0; round * PR_WAVES < ntiles; ++round) {
+    const int d = round * PR_WAVES + ((round & 1) ? PR_WAVES - 1 - wave : wave);
+    if (d >= ntiles) continue;
+    const int jt = jlast - d;
+    const int steps = 16 * (jt + 1) <= K ? min(4 * (jt + 1), nks) : nks;
+    const double *A = Gf + (size_t)jt * nks * 64 + lane;
+    const double *B = vs + (size_t)g * RS + col;
+    gd4 acc[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[rt] = gd4{0.0, 0.0, 0.0, 0.0};
+    double a[4], an[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = A[(size_t)min(u, steps - 1) * 64];
+    for (int ks = 0; ks < steps; ks += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) an[u] = A[(size_t)min(ks + 4 + u, steps - 1) * 64];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ks + u < steps) {
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt)
+            acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], B[(size_t)(ks + u) * 4 * RS + rt * 16], acc[rt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = an[u];
+    }
+    const int j0 = 16 * jt + g;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const gd4 z = acc[rt];
+      if (ts) {
+        double s = j0 < K ? z.x * z.x : 0.0;
+        s += j0 + 4 < K ? z.y * z.y : 0.0;
+        s += j0 + 8 < K ? z.z * z.z : 0.0;
+        s += j0 + 12 < K ? z.w * z.w : 0.0;
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        if (g == 0) ts[(size_t)jt * R + rt * 16 + col] = s;
+      }
+      const long i = base + rt * 16 + col;
+      if (j0 + 12 >= K && i < mnew) {
+        const int c0 = j0 - K;                              // the mean column of register 0; registers are 4 rows apart
+        if (c0 >= 0 && c0 < q) mean[(size_t)c0 * ldo + i] = z.x;
+        if (c0 + 4 >= 0 && c0 + 4 < q) mean[(size_t)(c0 + 4) * ldo + i] = z.y;
+        if (c0 + 8 >= 0 && c0 + 8 < q) mean[(size_t)(c0 + 8) * ldo + i] = z.z;
+        if (c0 + 12 >= 0 && c0 + 12 < q) mean[(size_t)(c0 + 12) * ldo + i] = z.w;
+      }
+    }
+  }
+}
+
+// mean(i, 0:q) = U^T v_i and, with cov, cov_i = c + |G v_i|^2 for the rows v_i of the pair read in place: the staging and the
+// row sums of gpc_predict_rows_kernel, pr_tiles_q between them.  cov == nullptr: the mean rows only (the training rows).
+template <int RT>
+__global__ __launch_bounds__(PR_THREADS) void gpr_predict_rows_kernel(const double *__restrict__ V, long ld,
+                                                                      const int *__restrict__ idx, int row0, int mnew, int K,
+                                                                      int q, int nks, int njt, const double *__restrict__ Gf,
+                                                                      double c, double *__restrict__ mean, long ldo,
+                                                                      double *__restrict__ cov) {
+  constexpr int R = 16 * RT, RS = pr_stride(R);
+  extern __shared__ double pr_lds[];
+  double *vs = pr_lds;                         // [4 nks][RS]
+  double *ts = pr_lds + (size_t)4 * nks * RS;  // [njt][R]
+  const long base = (long)blockIdx.x * R;
+  pr_stage<RT>(V, ld, idx, row0, mnew, K, nks, base, vs);
+  __syncthreads();
+  pr_tiles_q<RT>(Gf, vs, cov ? ts : nullptr, K, q, nks, njt, cov ? 0 : K / 16, base, mnew, mean, ldo);
+  if (!cov) return;
+  __syncthreads();
+  pr_rowsum<RT>(ts, njt, base, mnew, c, cov);
+}
+
+size_t gpr_predict_operand_elems(int K, int q) { return (size_t)ceil_div(K + q, 16) * ceil_div(K, 4) * 64; }
+
+bool gpr_predict_rows_applicable(int K, int q) {
+  if (K > GPC_PREDICT_KMAX || q > GPR_PREDICT_QMAX) return false;
+  const int lds = device_figures().lds_per_block;
+  return pr_rows(ceil_div(K, 4), ceil_div(K + q, 16), lds > 0 ? lds : 65536) != 0;
+}
+
+int gpr_predict_prep(hipStream_t st, int K, int q, const double *dG, const double *dU, double *d_Gf) {
+  const long total = (long)gpr_predict_operand_elems(K, q);
+  hipLaunchKernelGGL(gpr_predict_prep_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, dG, dU, K, q, ceil_div(K, 4), total, d_Gf);
+  return check_launch("gpr_predict_prep_kernel");
+}
+
+int gpr_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int q,
+                     const double *d_Gf, double c, double *d_mean, long ldo, double *d_cov) {
+  const int nks = ceil_div(K, 4), njt = ceil_div(K + q, 16);
+  const int lds_dev = device_figures().lds_per_block;
+  const int R = pr_rows(nks, njt, lds_dev > 0 ? lds_dev : 65536);
+  if (!R) { set_error("gpr_predict_rows: K=%d, q=%d do not fit the device's LDS", K, q); return FLGP_ERR_UNSUPPORTED; }
+  const size_t lds = pr_lds_bytes(R, nks, njt);
+  ProfScope ps("gpr_predict_rows", st, (double)mnew * K * (d_cov ? K + 2 * q : 2 * q));
+  const dim3 grid(ceil_div(mnew, R)), block(PR_THREADS);
+  auto launch = [&](auto kfn) -> int {
+    if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kfn, grid, block, lds, st, dV, ld, d_idx, row0, mnew, K, q, nks, njt, d_Gf, c, d_mean, ldo, d_cov);
+    return check_launch("gpr_predict_rows_kernel");
+  };
+  if (R == 64) return launch(gpr_predict_rows_kernel<4>);
+  if (R == 32) return launch(gpr_predict_rows_kernel<2>);
+  return launch(gpr_predict_rows_kernel<1>);
 }
 
 // out[i] = c + sum_k Z(i, k)^2, k ascending, a thread per row (the K > GPC_PREDICT_KMAX route of the predictive rows)

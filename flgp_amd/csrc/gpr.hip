@@ -130,7 +130,13 @@ __global__ void gpr_zinv_kernel(const double *__restrict__ noise, double sigma, 
   if (i < m) zinv[i] = 1.0 / (noise[i] + sigma);
 }
 
-// cov_i = sum_k V2(i,k)^2 l_k + c - sum_k V2(i,k) W(i,k)            (src/Utils.cpp:249: rowwise sums, k ascending)
+// out[i] = s * x[i]
+__global__ void gpr_scalar_mul_kernel(const double *__restrict__ x, double s, int n, double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = s * x[i];
+}
+
+// cov_i = sum_k V2(i,k)^2 l_k + c - sum_k V2(i,k) W(i,k)           (src/Utils.cpp:249: rowwise sums, k ascending)
 __global__ void gpr_rowquad_kernel(const double *__restrict__ V2, long ld2, const double *__restrict__ W, int mnew, int K,
                                    const double *__restrict__ l, double c, double *__restrict__ cov) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -188,6 +194,10 @@ int gpr_rowscale_ld(hipStream_t st, const double *dM, long ldm, const double *d_
 int gpr_zinv(hipStream_t st, const double *d_noise, double sigma, int m, double *d_zinv) {
   hipLaunchKernelGGL(gpr_zinv_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_noise, sigma, m, d_zinv);
   return check_launch("gpr_zinv_kernel");
+}
+int gpr_scalar_mul(hipStream_t st, const double *d_x, double s, int n, double *d_out) {
+  hipLaunchKernelGGL(gpr_scalar_mul_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_x, s, n, d_out);
+  return check_launch("gpr_scalar_mul_kernel");
 }
 int gpr_rowquad(hipStream_t st, const double *dV2, long ld2, const double *dW, int mnew, int K, const double *d_l, double c,
                 double *d_cov) {
