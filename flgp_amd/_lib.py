@@ -159,6 +159,10 @@ _SIGNATURES = {
     "flgp_dev_rotate": (c_int, [P, c_int, c_int, c_double, P, P, P, c_double, P, P, P]),
     "flgp_dev_gram_small": (c_int, [P, c_int, c_int, P, P, P, P, c_size_t]),
     "flgp_dev_gemm_pair": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_long, c_long, P, P, c_long, c_long, P, P, c_long, c_long]),
+    "flgp_dev_gemm_ex": (c_int, [P, c_int, c_int, c_int, c_double, P, c_long, c_long, P, c_long, c_long,
+                                 c_double, P, c_long, c_long, P, c_long, c_long, P, c_size_t, c_double,
+                                 P, c_int, c_int, P, P, P, P, P, P, P, ctypes.POINTER(c_int)]),
+    "flgp_dev_gram_small_fused": (c_int, [P, c_int, c_int, P, P, P, P, c_size_t, c_int, P, P, P, P]),
     "flgp_dev_gather_rows": (c_int, [P, P, c_int, P, c_int, c_int, P]),
     # row-sharded path behind the C ABI: communicators + sharded entry points
     "flgp_comm_inproc_create": (c_int, [c_int, P]),

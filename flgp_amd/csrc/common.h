@@ -148,10 +148,11 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
                 const double *E2, struct GemmFusedReduce *fused = nullptr,
-                const struct GemmPair *pair = nullptr, int force_split = 0);
+                const struct GemmPair *pair = nullptr, int force_split = 0, int *planes_out = nullptr);
 // The number of split-K planes gemm_launch chooses for this shape and workspace.  `force_split` > 0 makes a launch take
 // that number instead (the workspace must hold it): a row block of a product then adds every element's terms in the
-// order the whole product does, whatever the block's own tile count would have chosen.
+// order the whole product does, whatever the block's own tile count would have chosen.  `planes_out` (optional) receives the
+// number of planes a launch took.
 int gemm_plan_split(int M, int N, int Kd, size_t work_elems);
 // `pair`: a second product C2 = alpha A2 B2 of the same shape and strides in the same launch (no E / E2, never split):
 // two of the solver's s x b rotations fill the chip where one leaves its fixed costs exposed.
@@ -171,6 +172,7 @@ int rot_launch(hipStream_t st, int s, int b, double alpha, const double *X, cons
 // eigensolver's small matrices need no kernels of their own behind the product:
 //   mode bit 0: S <- D S D with D = diag(1 / sqrt(S_jj)) (0 where S_jj <= 0), D stored in dinv;
 //        bit 1: only the strictly upper triangle (row < column) of S is kept, the rest zero (bit 3: the strictly lower one);
+//               rows and columns are the caller's own, for a column-major and a row-major C alike;
 //        bit 2: |S - I|_F^2 (after bits 0 / 1) as GEMM_DIST_PARTS partial sums in a fixed order into dist[] (may be host memory).
 // `scratch` holds one double per 16 x 16 tile of S, `counter` one int that is zero between launches.  `done` tells the caller
 // whether the reduction kernel ran (the product was split) -- if not, S is the plain product and the caller runs its own kernels.

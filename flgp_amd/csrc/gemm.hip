@@ -478,7 +478,7 @@ __global__ void splitk_reduce_kernel(GemmArgs g, int nsplit) {
 // q mod 32, in ascending q -- so the result does not depend on the order the tiles ran in.
 __global__ __launch_bounds__(256) void splitk_reduce_sym_kernel(GemmArgs g, int nsplit, int mode, double *__restrict__ dinv,
                                                                 double *__restrict__ dist, double *__restrict__ scratch,
-                                                                int *__restrict__ counter) {
+                                                                int *__restrict__ counter, int j_is_row) {
   __shared__ double dg[32];
   __shared__ double red[256];
   __shared__ int last;
@@ -513,8 +513,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_sym_kernel(GemmArgs g, int 
   __syncthreads();
   double d2 = 0.0;
   if (live) {
-    // (row, column) of the caller's matrix: whichever of (i, j) has the unit stride is the row of a column-major result
-    const bool j_is_row = g.c_js == 1;
+    // (row, column) of the caller's matrix: gemm_launch turns a column-major result round (kernel (i, j) = caller (column,
+    // row)) and leaves a row-major one as it is -- g.c_js is 1 either way, so the launch says which it did
     const int row = j_is_row ? j : i, col = j_is_row ? i : j;
     if (mode & 1) {
       const double drow = j_is_row ? dg[16 + (tid & 15)] : dg[tid >> 4], dcol = j_is_row ? dg[tid >> 4] : dg[16 + (tid & 15)];
@@ -584,13 +584,14 @@ int gemm_plan_split(int M, int N, int Kd, size_t work_elems) {
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
-                const double *E2, GemmFusedReduce *fused, const GemmPair *pair, int force_split) {
+                const double *E2, GemmFusedReduce *fused, const GemmPair *pair, int force_split, int *planes_out) {
   if (fused) fused->done = false;
   if (pair && (E || E2 || fused)) { set_error("gemm: a paired product takes no E / E2 / fused reduction"); return FLGP_ERR_INVALID; }
   if (M <= 0 || N <= 0) return FLGP_OK;
   GemmArgs g;
   // orient so that the contiguous output dimension is the kernel's column dimension
-  if (c_is == 1 && c_js != 1) {
+  const bool swapped = c_is == 1 && c_js != 1;
+  if (swapped) {
     g.M = N; g.N = M; g.Kd = Kd;
     g.A = B; g.a_is = b_js; g.a_ks = b_ks;
     g.B = A; g.b_ks = a_ks; g.b_js = a_is;
@@ -625,6 +626,7 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
   int klen = ceil_div(Kd > 0 ? Kd : 1, nsplit);
   klen = (klen + GK - 1) / GK * GK;
   nsplit = ceil_div(Kd > 0 ? Kd : 1, klen);
+  if (planes_out) *planes_out = nsplit;
   g.ksplit_len = klen;
   g.part = work;
   // overlapping tiles write some elements twice: harmless unless the epilogue reads what it overwrites
@@ -645,7 +647,7 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
     if (fused && g.M == g.N && alpha == 1.0 && !g.E && !g.E2 && (g.c_is == 1 || g.c_js == 1)) {
       const int nt1 = ceil_div(g.M, 16);
       hipLaunchKernelGGL(splitk_reduce_sym_kernel, dim3(nt1 * nt1), dim3(256), 0, st, g, nsplit, fused->mode, fused->dinv,
-                         fused->dist, fused->scratch, fused->counter);
+                         fused->dist, fused->scratch, fused->counter, swapped ? 1 : 0);
       FLGP_TRY(check_launch("splitk_reduce_sym_kernel"));
       fused->done = true;
       return FLGP_OK;
@@ -689,6 +691,27 @@ extern "C" int flgp_dev_gemm(void *stream, int M, int N, int Kd, double alpha, c
                      c_is, c_js, d_work, work_elems, 0.0, nullptr);
 }
 
+// test / benchmark entry: flgp_dev_gemm with every argument of gemm_launch (gamma E2, a forced split, the fused reduction when
+// fused_mode >= 0, a second product when A2 is given); info[0] = the planes the launch took, info[1] = GemmFusedReduce::done
+extern "C" int flgp_dev_gemm_ex(void *stream, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
+                                const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
+                                double *C, long c_is, long c_js, double *d_work, size_t work_elems, double gamma,
+                                const double *E2, int force_split, int fused_mode, double *d_dinv, double *d_dist,
+                                double *d_scratch, int *d_counter, const double *A2, const double *B2, double *C2, int *info) {
+  FLGP_REQUIRE(M >= 0 && N >= 0 && Kd >= 0 && A && B && C && info, "gemm_ex: bad arguments");
+  FLGP_REQUIRE(!(A2 || B2 || C2) || (A2 && B2 && C2), "gemm_ex: a second product needs A2, B2 and C2");
+  FLGP_REQUIRE(fused_mode < 0 || (d_scratch && d_counter && (!(fused_mode & 1) || d_dinv) && (!(fused_mode & 4) || d_dist)),
+               "gemm_ex: the fused reduction needs its buffers");
+  info[0] = info[1] = 0;
+  GemmFusedReduce fr{fused_mode, d_dinv, d_dist, d_scratch, d_counter, false};
+  const GemmPair pr{A2, B2, C2};
+  const int rc = gemm_launch((hipStream_t)stream, M, N, Kd, alpha, A, a_is, a_ks, B, b_ks, b_js, beta, E, e_is, e_js, C, c_is,
+                             c_js, d_work, work_elems, gamma, E2, fused_mode >= 0 ? &fr : nullptr, A2 ? &pr : nullptr, force_split,
+                             &info[0]);
+  info[1] = fr.done ? 1 : 0;
+  return rc;
+}
+
 // The reduction half of a split product on its own (rot.hip's Gram kernel writes the planes): C(ic, jc) = sum over planes of
 // part[z][jc][ic] for a column-major b x b result with leading dimension b, with the fused extras of GemmFusedReduce.
 namespace flgp {
@@ -704,7 +727,7 @@ int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, do
   if (fused) {
     const int nt1 = ceil_div(b, 16);
     hipLaunchKernelGGL(splitk_reduce_sym_kernel, dim3(nt1 * nt1), dim3(256), 0, st, g, nsplit, fused->mode, fused->dinv, fused->dist,
-                       fused->scratch, fused->counter);
+                       fused->scratch, fused->counter, 1);
     fused->done = true;
     return check_launch("splitk_reduce_sym_kernel");
   }

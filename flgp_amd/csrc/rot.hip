@@ -327,6 +327,19 @@ extern "C" int flgp_dev_gram_small(void *stream, int s, int b, const double *Xa,
   return gramk_launch((hipStream_t)stream, s, b, Xa, Xb, out, d_work, work_elems, nullptr);
 }
 
+// test / benchmark entry: flgp_dev_gram_small with the fused reduction (GemmFusedReduce, common.h) the eigensolver asks for
+extern "C" int flgp_dev_gram_small_fused(void *stream, int s, int b, const double *Xa, const double *Xb, double *out, double *d_work,
+                                         size_t work_elems, int fused_mode, double *d_dinv, double *d_dist, double *d_scratch,
+                                         int *d_counter) {
+  FLGP_REQUIRE(Xa && Xb && out && d_work, "gram_small_fused: bad arguments");
+  FLGP_REQUIRE(fused_mode < 0 || (d_scratch && d_counter && (!(fused_mode & 1) || d_dinv) && (!(fused_mode & 4) || d_dist)),
+               "gram_small_fused: the fused reduction needs its buffers");
+  FLGP_REQUIRE(gramk_applicable(s, b, Xa, Xb, work_elems), "gram_small_fused: the kernel is built for 64 <= b <= 256 (multiples of 64), even "
+                                                            "s >= 256, 16-byte aligned operands and a workspace for its planes");
+  GemmFusedReduce fr{fused_mode, d_dinv, d_dist, d_scratch, d_counter, false};
+  return gramk_launch((hipStream_t)stream, s, b, Xa, Xb, out, d_work, work_elems, fused_mode >= 0 ? &fr : nullptr);
+}
+
 // test / benchmark entry: out = alpha X W + beta E with W given k-major (WT[k * b + j] = W(k, j)); X2 / out2 optional
 extern "C" int flgp_dev_rotate(void *stream, int s, int b, double alpha, const double *X, const double *X2, const double *WT,
                                double beta, const double *E, double *out, double *out2) {
