@@ -950,9 +950,11 @@ int bsg_setup(hipStream_t st, const double *dG, int ldg, int s, BsG &g, hipStrea
   const double *C = xfer.data();
   memcpy(g.h_meta, xfer.data() + (size_t)p * p, sizeof(int) * BSG_META);
   const int *lab = (const int *)(xfer.data() + (size_t)p * p) + BSG_META;
+  // denser than the CSR allows: the caller stays with the dense products.  (Before C is looked at: every kernel of the ordering
+  // has returned at once, so C is whatever the workspace held -- a NaN there used to refuse a finite matrix.)
+  if (g.h_meta[BSG_M_OFF]) return FLGP_OK;
   for (int q = 0; q < p * p; ++q)
     if (!std::isfinite(C[q])) { set_error("block-sparse ordering: the matrix is not finite"); return FLGP_ERR_INVALID; }
-  if (g.h_meta[BSG_M_OFF]) return FLGP_OK;     // denser than the CSR allows: the caller stays with the dense products
   // chain the clusters: start at the heaviest, always continue with the unused cluster most strongly tied to the last
   std::vector<int> order, rank(p + 1, p);
   std::vector<char> used(p, 0);

@@ -1193,6 +1193,11 @@ static bool eig_use_dense(int s, int K, const EigParams &P) {
   return K >= s || s <= 256 || 2 * b >= s;
 }
 
+// does a truncated solve try the block-sparse set-up?  (65536: bsg_lists_kernel keeps one int per 64-anchor tile in LDS)
+static bool eig_try_blocksparse(int s, const EigParams &P) {
+  return s >= std::max(1024, P.bs_min_s) && s <= 65536 && P.blocksparse;
+}
+
 static size_t eig_gemm_ws_elems(int s, int b) {
   // split-K partials (whole 128 x 128 tiles): the s x b products use up to 16 planes, the b x b ones up to 128
   const size_t sp = (size_t)(s + 127) / 128 * 128, bp = (size_t)(b + 127) / 128 * 128;
@@ -1327,14 +1332,24 @@ static int jacobi_eig(hipStream_t st, const double *T, int ldt, int b, EigWork &
 //   1. the g x g block is diagonalised completely by one workgroup inside LDS (one launch),
 //   2. with V0 = blockdiag(I, Vg), B0 = T V0, `sweeps` global sweeps finish the job
 //      (quadratic convergence: couplings eps -> eps^2 per sweep).
+// How jacobi_refine treats the trailing g x g block, g = b - K: 0 = not at all (no guard block to speak of, or the pair
+// (Vg, Bg) of the sub-Jacobi would not fit X2: a full jacobi_eig instead), 1 = one workgroup inside LDS
+// (small_sym_eig_kernel<64>), 2 = the block Jacobi on the g x g matrix itself.
+static int refine_route(int b, int K) {
+  const int g = b - K;
+  if (g < 2 || 2 * (size_t)g * g > (size_t)b * b) return 0;
+  return g <= 64 ? 1 : 2;
+}
+
 static int jacobi_refine(hipStream_t st, const double *T, int b, int K, EigWork &w, const EigParams &P,
                          std::vector<double> &h_lam, int *sweeps_out, int sweeps, bool to_host = true) {
   const int g = b - K;
-  if (g < 2 || 2 * (size_t)g * g > (size_t)b * b)
+  const int route = refine_route(b, K);
+  if (route == 0)
     return jacobi_eig(st, T, b, b, w, P, h_lam, sweeps_out, -1, 1.0);
   ProfScope ps("jacobi_refine", st, 8.0 * (double)b * b);
   double *Vg = w.X2;
-  if (g <= 64) {
+  if (route == 1) {
     const size_t lds_small = sizeof(double) * (4 * 64 * 64 + 2 * 64) + sizeof(int) * 64;
     FLGP_HIP(hipFuncSetAttribute((const void *)small_sym_eig_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds_small));
@@ -1758,7 +1773,7 @@ struct EigSolver {
   // ---- set-up and start block ------------------------------------------------------------------
   // p: the workspace behind EigWork (the block-sparse products carve theirs from it)
   int setup(char *p) {
-    if (s >= std::max(1024, P.bs_min_s) && s <= 65536 && P.blocksparse) {   // (65536: bsg_lists_kernel keeps one int per 64-anchor tile in LDS)
+    if (eig_try_blocksparse(s, P)) {
       bsg_carve(bs, p, s, b);
       if (g_ctx && g_ctx->pinned) bsg_host_slots(bs, g_ctx->pinned, (char *)g_ctx->pinned + HOST_SMALL_BYTES, HOST_BIG_BYTES);
       FLGP_TRY(bsg_setup(st, dG, ldg, s, bs, g_ctx ? g_ctx->side : nullptr, g_ctx ? g_ctx->side_ev : nullptr));
@@ -2163,6 +2178,28 @@ using namespace flgp;
 extern "C" size_t flgp_dev_eig_workspace(int s, int K) {
   if (K < 0 || K > s) K = s;
   return eig_workspace_bytes(s, K, eig_params());
+}
+
+// What flgp_dev_eig_topk(s, K) would choose with the tuning as it stands, from the functions the solve itself calls.
+// Launches nothing.
+extern "C" int flgp_dev_eig_plan(int s, int K, int *plan) {
+  FLGP_REQUIRE(s >= 1 && plan, "eig_plan: bad arguments");
+  if (K < 0) K = s;
+  FLGP_REQUIRE(K >= 1 && K <= s, "eig_plan: need 1 <= K <= s (K=%d, s=%d)", K, s);
+  const EigParams P = eig_params();
+  const bool dense = eig_use_dense(s, K, P);
+  const int b = dense ? s : eig_block_size(s, K, P);
+  const JacobiPlan jp = jacobi_plan(b);
+  const int route = dense ? 0 : refine_route(b, K);
+  plan[0] = dense ? 1 : 0;
+  plan[1] = b;
+  plan[2] = jp.nloc;
+  plan[3] = jp.nbc;
+  plan[4] = route;
+  plan[5] = route == 2 ? jacobi_plan(b - K).nloc : 0;
+  plan[6] = b - K;
+  plan[7] = (!dense && eig_try_blocksparse(s, P)) ? 1 : 0;
+  return FLGP_OK;
 }
 
 static int eig_topk_impl(void *stream, const double *dG, int ldg, int s, int K, double tol, double *d_values, double *dV,
