@@ -135,6 +135,11 @@ _SIGNATURES = {
     "flgp_dev_extend_scale": (c_int, [P, P, P, c_int, c_int, P, P, P]),
     "flgp_dev_spectrum_model_extend": (c_int, [P, P, P, c_int, c_int, P, c_int]),
     "flgp_dev_gram": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_int]),
+    "flgp_dev_gram_order": (c_int, [P, P, c_int, P]),
+    "flgp_dev_gram_ordered": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P, c_int]),
+    "flgp_dev_gram_uses_records": (c_int, [c_int, c_int]),
+    "flgp_dev_gram_record_bytes": (c_size_t, [c_int, c_int]),
+    "flgp_dev_gram_pack": (c_int, [P, P, P, c_int, c_int, P]),
     "flgp_dev_sym_pack": (c_int, [P, P, c_int, c_int, P]),
     "flgp_dev_sym_unpack": (c_int, [P, P, c_int, P, c_int]),
     "flgp_dev_eig_workspace": (c_size_t, [c_int, c_int]),

@@ -110,7 +110,7 @@ namespace {
 
 // device-side state of one similarity matrix: anchors, k-NN, ELL (+ CSC view)
 struct Sim {
-  DevBuf X, U, Ut, uu, knn_idx, knn_dist, ell_idx, ell_val, colptr, pos, colsum, cswork, work, num_class;
+  DevBuf X, U, Ut, uu, knn_idx, knn_dist, ell_idx, ell_val, colptr, pos, order, colsum, cswork, work, num_class;
   int n = 0, d = 0, s = 0, r = 0;
   bool have_csc = false;
   // row-sharded runs (flgp_dev_heat_kernel_covariance_sharded): n is the LOCAL row count, ldx the leading dimension of
@@ -204,6 +204,8 @@ int build_csc(Sim &S, hipStream_t st) {
   FLGP_TRY(S.colptr.alloc(sizeof(int) * (size_t)(S.s + 1)));
   FLGP_TRY(S.pos.alloc(sizeof(int) * (size_t)S.n * S.r));
   FLGP_TRY(flgp_dev_csc_build(st, S.ell_idx.as<int>(), S.n, S.s, S.r, S.colptr.as<int>(), S.pos.as<int>(), S.work.p, wb));
+  FLGP_TRY(S.order.alloc(sizeof(int) * (size_t)S.s));
+  FLGP_TRY(flgp_dev_gram_order(st, S.colptr.as<int>(), S.s, S.order.as<int>()));     // Gram's columns, longest first
   S.have_csc = true;
   return FLGP_OK;
 }
@@ -275,7 +277,7 @@ int csr_out(Sim &S, hipStream_t st, int *csr_p, int *csr_j, double *csr_x) {
 // spectrum_from_Z_cpp on the device ELL (reference src/Spectrum.cpp:146-161): leaves values (K)
 // and vectors (n x K) on the device
 struct Spectrum {
-  DevBuf G, eig, V, values, vectors, work, uwork;     // values / vectors: the caller's where it has set (borrowed) them
+  DevBuf G, rec, eig, V, values, vectors, work, uwork;     // values / vectors: the caller's where it has set (borrowed) them
   int K = 0;
 };
 
@@ -292,8 +294,12 @@ int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info) {
   // Gram + top-K eigenpairs (replaces RSpectra::svds / BDCSVD, src/TruncatedSVD.cpp:17-30)
   FLGP_TRY(P.G.alloc(sizeof(double) * (size_t)S.s * S.s));
   FLGP_TRY(join_csc(S, st));
-  FLGP_TRY(flgp_dev_gram(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.s, S.r, S.colptr.as<int>(),
-                         S.pos.as<int>(), P.G.as<double>(), S.s));
+  if (flgp_dev_gram_uses_records(S.s, S.r)) {     // the scaled rows as 128-byte records: one cache line per visit
+    FLGP_TRY(P.rec.alloc(flgp_dev_gram_record_bytes(S.n, S.r)));
+    FLGP_TRY(flgp_dev_gram_pack(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.r, P.rec.as<double>()));
+  }
+  FLGP_TRY(flgp_dev_gram_ordered(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.s, S.r, S.colptr.as<int>(),
+                                 S.pos.as<int>(), S.order.as<int>(), P.rec.as<double>(), P.G.as<double>(), S.s));
   if (flgp_comm_world(S.comm) > 1) {
     // exchange 3: the Gram partials of the row blocks.  Only the upper triangle travels (s(s+1)/2 doubles); unpacking
     // mirrors it, which also leaves G symmetric bit for bit whatever order the transport added the ranks in.  The
@@ -1221,7 +1227,7 @@ static int se_grid_core(Sim &S, hipStream_t st0, int r, int K, const double *a2s
     FLGP_TRY(ws.create());
     Sim W;   // borrows the pattern and its CSC view from S, owns its values and column sums
     W.n = n; W.d = S.d; W.s = s; W.r = r;
-    W.ell_idx.borrow(S.ell_idx.p); W.colptr.borrow(S.colptr.p); W.pos.borrow(S.pos.p);
+    W.ell_idx.borrow(S.ell_idx.p); W.colptr.borrow(S.colptr.p); W.pos.borrow(S.pos.p); W.order.borrow(S.order.p);
     W.have_csc = true;
     FLGP_TRY(W.ell_val.alloc(sizeof(double) * (size_t)n * r));
     DevBuf scratch_idx;

@@ -330,20 +330,71 @@ __global__ __launch_bounds__(256) void extend_scale_kernel(const int *__restrict
 //   * the positions of a step are fetched two steps ahead, so that they are there when its first group is fetched;
 //   * every load is issued unconditionally at a valid address (an idle slot reads entry p0 / row 0), so that the number
 //     in flight does not depend on the data and the compiler's vmcnt waits are counted, not vmcnt(0);
-//   * entry / r is a multiplication.
+//   * entry / r is a multiplication;
+//   * the waves are dealt their columns longest first (`order`, gram_order_kernel below): a column is one wave's work
+//     from end to end, and the longest one at the flagship shape is 278 steps where a fair share is 153 -- started
+//     last it runs on alone.  Which wave takes which column changes no sum.
 // ----------------------------------------------------------------------------------------
+// order[0..s): the columns by descending entry count, ties by ascending column: an exact rank sort.  Thread j counts
+// the keys (count, s - 1 - j) above its own -- they are all distinct, so the ranks are a permutation.  A workgroup
+// serves 64 columns (lane = column) with sixteen waves that take a sixteenth of the keys each: the key a wave compares
+// against is the same in all its lanes, so it comes through the scalar cache and costs the vector unit a compare and
+// an add.  (Tiles of keys in LDS, 256 columns per workgroup and one wave per SIMD: 0.10 ms at s = 5000, every read
+// waited for.)  Nothing to tune or to fall back from up to FLGP_SMAX.
+constexpr int ORDER_WAVES = 16;
+__device__ __forceinline__ unsigned long long gram_order_key(const int *__restrict__ colptr, int s, int j) {
+  return ((unsigned long long)(unsigned)(colptr[j + 1] - colptr[j]) << 32) | (unsigned)(s - 1 - j);
+}
+__global__ __launch_bounds__(64 * ORDER_WAVES) void gram_order_kernel(const int *__restrict__ colptr, int s,
+                                                                       int *__restrict__ order) {
+  __shared__ int part[ORDER_WAVES][64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int j = blockIdx.x * 64 + lane;
+  const unsigned long long mine = gram_order_key(colptr, s, j < s ? j : s - 1);
+  const int per = (s + ORDER_WAVES - 1) / ORDER_WAVES;
+  const int q0 = w * per, q1 = q0 + per < s ? q0 + per : s;
+  int rank = 0;
+#pragma unroll 8
+  for (int q = q0; q < q1; ++q) rank += gram_order_key(colptr, s, q) > mine ? 1 : 0;
+  part[w][lane] = rank;
+  __syncthreads();
+  if (w == 0 && j < s) {
+    int total = 0;
+#pragma unroll
+    for (int k = 0; k < ORDER_WAVES; ++k) total += part[k][lane];
+    order[total] = j;
+  }
+}
+
+// A row's record: its r values, then its r indices, in 128 bytes (r <= 10), 256 (r <= 21) or 384: one cache line per
+// visit of gram_kernel at r <= 10 where the two ELL rows (80 bytes at 80 i, 40 at 40 i) straddle 2.93 on average.
+static int gram_record_doubles(int r) { return ceil_div(12 * r, 128) * 16; }
+__global__ __launch_bounds__(256) void gram_pack_kernel(const int *__restrict__ ell_idx, const double *__restrict__ val, long nnz,
+                                                        int r, double inv_r, int recd, double *__restrict__ rec) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nnz) return;
+  const long row = (long)(((double)e + 0.5) * inv_r);
+  const int a = (int)(e - row * r);
+  double *rp = rec + (size_t)row * recd;
+  rp[a] = val[e];
+  ((int *)(rp + r))[a] = ell_idx[e];
+}
+
 // WIN: the wave owns the columns [w0, w0 + wn) of row j1 only (window blockIdx.y); products for other windows are skipped.
-// LPR: lanes per row, 0 for r itself.
-template <int LPR, bool WIN>
+// LPR: lanes per row, 0 for r itself.  order: the column of workgroup blockIdx.x, or nullptr for blockIdx.x itself.
+// REC: a visit reads the row's 128-byte-aligned record (gram_pack_kernel) instead of the ELL arrays.
+template <int LPR, bool WIN, bool REC>
 __global__ __launch_bounds__(64) void gram_kernel(const int *__restrict__ ell_idx, const double *__restrict__ val,
                                                   int s, int r, double inv_r, const int *__restrict__ colptr,
-                                                  const int *__restrict__ pos, double *__restrict__ G, int ldg, int wmax) {
+                                                  const int *__restrict__ pos, double *__restrict__ G, int ldg, int wmax,
+                                                  const int *__restrict__ order, const double *__restrict__ rec, int recd) {
   extern __shared__ double acc[];
   // groups in flight: 3 loads each + 2 of positions stay below the 63 vector loads a wave can have outstanding.  Eleven
   // groups of six rows are the 64 positions of a step at r = 10 (groups beyond a step's positions load for nothing).
   constexpr int GF = LPR ? 16 : 11;
   const int lane = threadIdx.x;
-  const int j1 = blockIdx.x;
+  const int j1 = order ? order[blockIdx.x] : (int)blockIdx.x;
   const int w0 = WIN ? (int)blockIdx.y * wmax : 0;
   const int wn = WIN ? ((s - w0 < wmax) ? s - w0 : wmax) : s;
   for (int j = lane; j < wn; j += 64) acc[j] = 0.0;
@@ -366,10 +417,17 @@ __global__ __launch_bounds__(64) void gram_kernel(const int *__restrict__ ell_id
       o.act = act;
       const int ee = act ? en : 0;
       const int row = (int)(((double)ee + 0.5) * inv_r);            // == ee / r exactly for ee < 2^31, r <= 32
-      const size_t rowbase = (size_t)row * r;
-      o.j2 = ell_idx[rowbase + ac];
-      o.v = val[rowbase + ac];
-      o.vj = val[ee];
+      if constexpr (REC) {
+        const double *rp = rec + (size_t)row * recd;
+        o.j2 = ((const int *)(rp + r))[ac];
+        o.v = rp[ac];
+        o.vj = rp[ee - row * r];
+      } else {
+        const size_t rowbase = (size_t)row * r;
+        o.j2 = ell_idx[rowbase + ac];
+        o.v = val[rowbase + ac];
+        o.vj = val[ee];
+      }
       return o;
     };
     // ONE ds_add_f64 per group: lanes of different rows that hit the same bin (bin j1 always, usually more) are applied
@@ -605,7 +663,8 @@ __global__ __launch_bounds__(256) void transpose_v_slices_kernel(const double *_
 // random anchors would use the even ones of the 16 slots of a bank row only; bit 3 of the anchor swaps its halves.
 template <int W> __device__ __forceinline__ int u_lds_slot(int q) { return W == 4 ? q ^ (((q >> 5) & 1) << 1) : q; }
 
-template <int W>
+// NP: pairs of entries per step (u_lds_pairs below: the fewest equal steps of at most six pairs that cover a row).
+template <int W, int NP>
 __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(const int *__restrict__ ell_idx,
                                                                               const double *__restrict__ val, int n, int r, int s,
                                                                               const double *__restrict__ Vts,
@@ -629,17 +688,22 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
   const long i_lo = (long)blockIdx.x * rows_per_range;
   const long i_hi = (i_lo + rows_per_range < n) ? i_lo + rows_per_range : n;
   const long last_pair = (long)n * r - 2;       // (n r >= 2: the route rule)
-  // Eight entries of a row as four pairs: a 16-byte load of values and an 8-byte load of indices per lane, the pair starting
-  // at the even slot a of row i.  The pair of an odd r's last slot reaches into the next row, and in the last row of all it
-  // is moved back by one (`up` below).  Loads are unconditional, so that the number in flight is the same on every path and
+  // A step is CE = 2 NP entries of a row as NP pairs: a 16-byte load of values and an 8-byte load of indices per lane, the
+  // pair starting at the even slot a of row i.  NP is cut to the row (five pairs, one step at r = 10): with steps of eight
+  // entries whatever r, the second step of a row of ten issued three of its four pairs for nothing and took the ragged path.
+  // The pair of an odd r's last slot reaches into the next row, and in the last row of all it is moved back by one (`up` below).  Loads are unconditional, so that the number in flight is the same on every path and
   // the wait counts stay tight; what a lane has no use for (past its row, past its range) is read from ONE address, the
   // range's first entry, which costs the cache a single line look-up.
-  struct Chunk { double z0[4], z1[4]; int j0[4], j1[4]; };
+  constexpr int CE = 2 * NP;
+  // gathers issued ahead of their sums: the whole step up to four pairs, half of it beyond (a third at W = 4, NP = 6) --
+  // the most for which two buffers and the gathered anchors stay inside the 128 VGPRs of a 1024-thread workgroup
+  constexpr int GB = NP <= 4 ? CE : (W == 4 && NP == 6) ? 4 : NP;
+  struct Chunk { double z0[NP], z1[NP]; int j0[NP], j1[NP]; };
   auto fetch = [&](long i, int ch) {
     Chunk c;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int a = 8 * ch + 2 * u;
+    for (int u = 0; u < NP; ++u) {
+      const int a = CE * ch + 2 * u;
       long b = (i < i_hi && a < r) ? i * r + a : i_lo * r;
       b = b < last_pair ? b : last_pair;
       const d2u z = *(const d2u *)(val + b);
@@ -649,7 +713,7 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
     }
     return c;
   };
-  // one entry of a chunk, slot a = 8 ch + 2 u + h of row i: its value and the W doubles of its anchor
+  // one entry of a chunk, slot a = CE ch + 2 u + h of row i: its value and the W doubles of its anchor
   auto gather = [&](const Chunk &cur, int u, int h, bool moved, double &z, double (&v)[W]) {
     const bool up = h || moved;
     const int id = up ? cur.j1[u] : cur.j0[u];
@@ -669,22 +733,26 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
   double acc[W];
 #pragma unroll
   for (int c = 0; c < W; ++c) acc[c] = 0.0;
-  const int nch = (r + 7) >> 3;
+  const int nch = (r + CE - 1) / CE;
   // chunk ch of row i: its entries in ascending order; behind the row's last chunk the W results are stored
   auto apply = [&](const Chunk &cur, long i, int ch) {
-    const int left = r - ch * 8;
-    if (left >= 8) {                                                   // (uniform) a whole chunk: its eight gathers, then the sums
-      double z[8], v[8][W];
+    const int left = r - ch * CE;
+    if (left >= CE) {                                                  // (uniform) a whole chunk: GB gathers, then their sums
 #pragma unroll
-      for (int e = 0; e < 8; ++e) gather(cur, e >> 1, e & 1, false, z[e], v[e]);   // (an entry follows every pair: none moved)
+      for (int e0 = 0; e0 < CE; e0 += GB) {
+        double z[GB], v[GB][W];
 #pragma unroll
-      for (int e = 0; e < 8; ++e)
+        for (int e = e0; e < e0 + GB && e < CE; ++e)                     // (an entry follows every pair: none moved)
+          gather(cur, e >> 1, e & 1, false, z[e - e0], v[e - e0]);
 #pragma unroll
-        for (int c = 0; c < W; ++c) acc[c] += z[e] * v[e][c];
+        for (int e = e0; e < e0 + GB && e < CE; ++e)
+#pragma unroll
+          for (int c = 0; c < W; ++c) acc[c] += z[e - e0] * v[e - e0][c];
+      }
     } else {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool moved = i * r + ch * 8 + 2 * u > last_pair;         // only the last slot of the last row, r odd
+      for (int u = 0; u < NP; ++u) {
+        const bool moved = i * r + ch * CE + 2 * u > last_pair;         // only the last slot of the last row, r odd
 #pragma unroll
         for (int h = 0; h < 2; ++h)
           if (2 * u + h < left) {
@@ -875,8 +943,38 @@ extern "C" int flgp_dev_extend_scale(void *stream, const int *d_ell_idx, double 
   return check_launch("extend_scale_kernel");
 }
 
-extern "C" int flgp_dev_gram(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int s, int r,
-                             const int *d_colptr, const int *d_pos, double *dG, int ldg) {
+extern "C" int flgp_dev_gram_order(void *stream, const int *d_colptr, int s, int *d_order) {
+  FLGP_REQUIRE(s >= 1 && s <= FLGP_SMAX && d_colptr && d_order, "Gram order: need 1 <= s <= %d (got %d) and both arrays", FLGP_SMAX, s);
+  hipLaunchKernelGGL(gram_order_kernel, dim3(ceil_div(s, 64)), dim3(64 * ORDER_WAVES), 0, (hipStream_t)stream, d_colptr, s, d_order);
+  return check_launch("gram_order_kernel");
+}
+
+extern "C" size_t flgp_dev_gram_record_bytes(int n, int r) {
+  return sizeof(double) * (size_t)(n > 0 ? n : 0) * (size_t)gram_record_doubles(r > 0 ? r : 1) + 256;
+}
+
+// Do the records pay?  Where one workgroup holds the whole row of G (no windows): 0.505 -> 0.288 ms for a pack of 0.041 ms
+// at the flagship shape; with two windows of s = 20 500 every row is visited twice as often and the kernel is bound
+// elsewhere (3.40 -> 3.44 ms).
+extern "C" int flgp_dev_gram_uses_records(int s, int r) {
+  return s >= 1 && s <= FLGP_SMAX && r >= 1 && r <= FLGP_RMAX && lds_window(s) >= s;
+}
+
+extern "C" int flgp_dev_gram_pack(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, double *d_rec) {
+  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && n >= 0 && d_rec, "Gram records: bad arguments");
+  FLGP_REQUIRE(((size_t)d_rec & 127) == 0, "Gram records: the buffer must be 128-byte aligned");
+  const long nnz = (long)n * r;
+  if (nnz == 0) return FLGP_OK;
+  hipLaunchKernelGGL(gram_pack_kernel, dim3(ceil_div(nnz, 256)), dim3(256), 0, (hipStream_t)stream, d_ell_idx, d_ell_val, nnz, r,
+                     1.0 / (double)r, gram_record_doubles(r), d_rec);
+  return check_launch("gram_pack_kernel");
+}
+
+// d_order: flgp_dev_gram_order's list (any permutation of the columns gives the same G), or NULL.  d_rec: the records of
+// flgp_dev_gram_pack for these ELL arrays, or NULL to read the arrays themselves.
+extern "C" int flgp_dev_gram_ordered(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int s, int r,
+                                     const int *d_colptr, const int *d_pos, const int *d_order, const double *d_rec,
+                                     double *dG, int ldg) {
   (void)n;
   FLGP_REQUIRE(s >= 1 && s <= FLGP_SMAX, "Gram: need 1 <= s <= %d (got %d)", FLGP_SMAX, s);
   FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && ldg >= s, "Gram: bad r / ldg");
@@ -885,20 +983,30 @@ extern "C" int flgp_dev_gram(void *stream, const int *d_ell_idx, const double *d
   const bool win = wmax < s;
   // lanes per row: r itself where that puts more rows into a group than the power-of-two packing does (r <= 12, 17..21)
   const int lpr = (64 / r > (r <= 16 ? 4 : 2)) ? 0 : (r <= 16 ? 16 : 32);
-  const void *fn = lpr == 0 ? (win ? (const void *)gram_kernel<0, true> : (const void *)gram_kernel<0, false>)
-                 : lpr == 16 ? (win ? (const void *)gram_kernel<16, true> : (const void *)gram_kernel<16, false>)
-                             : (win ? (const void *)gram_kernel<32, true> : (const void *)gram_kernel<32, false>);
-  if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const bool recs = d_rec != nullptr;
+  const int recd = gram_record_doubles(r);
   ProfScope ps("gram_kernel", (hipStream_t)stream, 12.0 * (double)n * r + 8.0 * (double)s * s);
   const dim3 grid(s, win ? ceil_div(s, wmax) : 1);
-#define GRAM_LAUNCH(LPRv, WINv)                                                                                                \
-  hipLaunchKernelGGL((gram_kernel<LPRv, WINv>), grid, dim3(64), lds, (hipStream_t)stream, d_ell_idx, d_ell_val, s, r,         \
-                     1.0 / (double)r, d_colptr, d_pos, dG, ldg, wmax)
+#define GRAM_LAUNCH3(LPRv, WINv, RECv)                                                                                         \
+  do {                                                                                                                         \
+    if (lds > 48 * 1024)                                                                                                       \
+      FLGP_HIP(hipFuncSetAttribute((const void *)gram_kernel<LPRv, WINv, RECv>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                   (int)lds));                                                                                 \
+    hipLaunchKernelGGL((gram_kernel<LPRv, WINv, RECv>), grid, dim3(64), lds, (hipStream_t)stream, d_ell_idx, d_ell_val, s, r,  \
+                       1.0 / (double)r, d_colptr, d_pos, dG, ldg, wmax, d_order, d_rec, recd);                                 \
+  } while (0)
+#define GRAM_LAUNCH(LPRv, WINv) do { if (recs) GRAM_LAUNCH3(LPRv, WINv, true); else GRAM_LAUNCH3(LPRv, WINv, false); } while (0)
   if (lpr == 0) { if (win) GRAM_LAUNCH(0, true); else GRAM_LAUNCH(0, false); }
   else if (lpr == 16) { if (win) GRAM_LAUNCH(16, true); else GRAM_LAUNCH(16, false); }
   else { if (win) GRAM_LAUNCH(32, true); else GRAM_LAUNCH(32, false); }
 #undef GRAM_LAUNCH
+#undef GRAM_LAUNCH3
   return check_launch("gram_kernel");
+}
+
+extern "C" int flgp_dev_gram(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int s, int r,
+                             const int *d_colptr, const int *d_pos, double *dG, int ldg) {
+  return flgp_dev_gram_ordered(stream, d_ell_idx, d_ell_val, n, s, r, d_colptr, d_pos, nullptr, nullptr, dG, ldg);
 }
 
 // ---- upper triangle of a symmetric matrix as one contiguous run (exchange 3 of the row-sharded path sends s(s+1)/2
@@ -972,7 +1080,16 @@ static int num_cus() {
   return cus[dev];
 }
 
-template <int W>
+// pairs per step of u_recover_lds_kernel: a row is ceil(r / 2) pairs, walked in the fewest steps of at most U_LDS_MAX_PAIRS,
+// all of one size: one step up to r = 12, two steps of 4..6 pairs up to r = 24, three of 5 or 6 up to r = 32.  At most two
+// pairs, in the row's last step, are loaded for nothing.  (Seven and eight pairs in two buffers spill at four eigen-columns.)
+constexpr int U_LDS_MAX_PAIRS = 6;
+static int u_lds_pairs(int r) {
+  const int pairs = (r + 1) / 2, steps = ceil_div(pairs, U_LDS_MAX_PAIRS);
+  return ceil_div(pairs, steps);
+}
+
+template <int W, int NP>
 static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
                                 int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
                                 double *d_work) {
@@ -986,10 +1103,23 @@ static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const doub
   ranges = ceil_div(n, rows);
   const size_t lds = sizeof(double) * (size_t)s * W;
   if (lds > 48 * 1024)
-    FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((u_recover_lds_kernel<W>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st, d_ell_idx, d_ell_val,
+    FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((u_recover_lds_kernel<W, NP>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st, d_ell_idx, d_ell_val,
                      n, r, s, d_work, d_eig, K, scale, d_vectors, ldo, rows);
   return FLGP_OK;
+}
+
+template <int W>
+static int u_recover_lds_pairs(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
+                               int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
+                               double *d_work) {
+  switch (u_lds_pairs(r)) {
+#define U_LDS_PAIRS(NPv)                                                                                                       \
+  case NPv: return u_recover_lds_launch<W, NPv>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)
+    U_LDS_PAIRS(1); U_LDS_PAIRS(2); U_LDS_PAIRS(3); U_LDS_PAIRS(4); U_LDS_PAIRS(5);
+    default: U_LDS_PAIRS(6);
+#undef U_LDS_PAIRS
+  }
 }
 
 extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r,
@@ -1003,7 +1133,7 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
     if (route == 4) {
       switch (u_lds_width(s)) {
 #define U_LDS_CASE(Wv)                                                                                                         \
-  case Wv: FLGP_TRY(u_recover_lds_launch<Wv>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)); break
+  case Wv: FLGP_TRY(u_recover_lds_pairs<Wv>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)); break
         U_LDS_CASE(1); U_LDS_CASE(2); U_LDS_CASE(3);
         default: U_LDS_CASE(4);
 #undef U_LDS_CASE

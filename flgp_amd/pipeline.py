@@ -98,7 +98,9 @@ class HipStages:
         colptr = self.empty((s + 1,), torch.int32); pos = self.empty((max(n * r, 1),), torch.int32)
         _lib.check(self.L.flgp_dev_csc_build(self._st(), ell_idx.data_ptr(), n, s, r, colptr.data_ptr(), pos.data_ptr(),
                                              work.data_ptr(), wb))
-        return dict(colptr=colptr, pos=pos, s=s)
+        order = self.empty((s,), torch.int32)       # Gram's columns, longest first: made here, beside the scalings
+        _lib.check(self.L.flgp_dev_gram_order(self._st(), colptr.data_ptr(), s, order.data_ptr()))
+        return dict(colptr=colptr, pos=pos, s=s, order=order)
 
     def colsum(self, ell_idx, ell_val, s):
         n, r = ell_idx.shape
@@ -128,8 +130,14 @@ class HipStages:
         n, r = ell_idx.shape
         s = csc["s"]
         G = self.empty((s, s))
-        _lib.check(self.L.flgp_dev_gram(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, s, r, csc["colptr"].data_ptr(),
-                                        csc["pos"].data_ptr(), G.data_ptr(), s))
+        order = csc.get("order")
+        rec = None
+        if n and self.L.flgp_dev_gram_uses_records(s, r):     # the rows as 128-byte records: one cache line per visit
+            rec = self.empty((self.L.flgp_dev_gram_record_bytes(n, r) // 8,))
+            _lib.check(self.L.flgp_dev_gram_pack(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, r, rec.data_ptr()))
+        _lib.check(self.L.flgp_dev_gram_ordered(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, s, r, csc["colptr"].data_ptr(),
+                                                csc["pos"].data_ptr(), order.data_ptr() if order is not None else None,
+                                                rec.data_ptr() if rec is not None else None, G.data_ptr(), s))
         return G
 
     def sym_pack(self, G):
@@ -416,8 +424,9 @@ class HeatKernelPath:
         tm.mark("laplacian")
         if side is not None:
             main.wait_stream(side)
-            for tns in (csc["colptr"], csc["pos"]):
-                tns.record_stream(main)
+            for tns in csc.values():
+                if torch.is_tensor(tns):
+                    tns.record_stream(main)
         tm.mark("csc")                                                        # (what of the CSC build the scalings did not cover)
         # k6: Gram, replicated top-K eigensolve
         G = S.gram(ell_idx, ell_val, csc)

@@ -1,4 +1,5 @@
-"""GPU box: flgp_dev_gram of this tree against the same entry of another build of the library (the parent commit's), on
+"""GPU box: Gram of this tree (flgp_dev_gram_ordered on the list of flgp_dev_gram_order, as the path runs it; the list's own
+kernel is timed beside it) against flgp_dev_gram of another build of the library (the parent commit's), on
 the flagship inputs: BASELINE configs[2], all 1e6 rows, through k-NN -> LAE -> Laplacian scalings as pipeline.py runs them.
 G must be the same bits (torch.equal); both calls are timed back to back (HIP events, mean of --reps).
 usage: python scripts/gram_compare.py --other path/to/libflgp_hip.so [--s 5000 20500] [--n 1000000] [--r 10] [--out file.json]"""
@@ -43,10 +44,7 @@ for s in args.s:
     S.col_scale(ei, ev, S.colsum(ei, ev, s), None, 1)
     counts = torch.diff(csc["colptr"]).cpu().numpy()
 
-    def run(L):
-        G = torch.full((s, s), float("nan"), dtype=torch.float64, device="cuda:0")
-        call = lambda: L.flgp_dev_gram(S._st(), ei.data_ptr(), ev.data_ptr(), n, s, r, csc["colptr"].data_ptr(),
-                                       csc["pos"].data_ptr(), G.data_ptr(), s)
+    def timed(call):
         for _ in range(3):
             assert call() == 0
         torch.cuda.synchronize()
@@ -56,19 +54,42 @@ for s in args.s:
             call()
         e1.record(torch.cuda.current_stream())
         torch.cuda.synchronize()
-        return G, e0.elapsed_time(e1) / args.reps
+        return e0.elapsed_time(e1) / args.reps
 
+    def run(L, rec_ptr=None):
+        G = torch.full((s, s), float("nan"), dtype=torch.float64, device="cuda:0")
+        if L is other:
+            call = lambda: L.flgp_dev_gram(S._st(), ei.data_ptr(), ev.data_ptr(), n, s, r, csc["colptr"].data_ptr(),
+                                           csc["pos"].data_ptr(), G.data_ptr(), s)
+        else:
+            call = lambda: L.flgp_dev_gram_ordered(S._st(), ei.data_ptr(), ev.data_ptr(), n, s, r, csc["colptr"].data_ptr(),
+                                                   csc["pos"].data_ptr(), csc["order"].data_ptr(), rec_ptr, G.data_ptr(), s)
+        return G, timed(call)
+
+    order2 = torch.empty_like(csc["order"])
+    order_call = lambda: S.L.flgp_dev_gram_order(S._st(), csc["colptr"].data_ptr(), s, order2.data_ptr())
+    ms_order = timed(order_call)
+    rec = torch.empty((S.L.flgp_dev_gram_record_bytes(n, r) // 8,), dtype=torch.float64, device="cuda:0")
+    pack_call = lambda: S.L.flgp_dev_gram_pack(S._st(), ei.data_ptr(), ev.data_ptr(), n, r, rec.data_ptr())
+    ms_pack = timed(pack_call)
     G_new, ms_new = run(S.L)
+    G_rec, ms_rec = run(S.L, rec.data_ptr())
     G_old, ms_old = run(other)
     G_new2, ms_new2 = run(S.L)
     G_old2, ms_old2 = run(other)
+    G_rec2, ms_rec2 = run(S.L, rec.data_ptr())
+    ms_pack2 = timed(pack_call)
+    ms_order2 = timed(order_call)
+    assert torch.equal(order2, csc["order"])
     res = {"n": n, "s": s, "r": r, "equal": bool(torch.equal(G_new, G_old)), "symmetric": bool(torch.equal(G_new, G_new.t())),
            "finite": bool(torch.isfinite(G_new).all()), "ms_this_tree": [ms_new, ms_new2], "ms_other": [ms_old, ms_old2],
+           "ms_order_kernel": [ms_order, ms_order2], "ms_from_records": [ms_rec, ms_rec2], "ms_pack_kernel": [ms_pack, ms_pack2],
+           "records_equal": bool(torch.equal(G_rec, G_old) and torch.equal(G_rec2, G_old)),
            "column_counts": {"min": int(counts.min()), "median": float(np.median(counts)), "mean": float(counts.mean()),
                              "p99": float(np.percentile(counts, 99)), "max": int(counts.max())}}
     print(json.dumps(res), flush=True)
     results.append(res)
-    del G_new, G_old, G_new2, G_old2, ei, ev, csc, knn_idx
+    del G_new, G_old, G_new2, G_old2, G_rec, G_rec2, rec, ei, ev, csc, knn_idx
     torch.cuda.empty_cache()
 if args.out:
     json.dump(results, open(args.out, "w"), indent=1)
