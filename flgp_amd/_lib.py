@@ -94,6 +94,13 @@ _SIGNATURES = {
     "flgp_nystrom_grid_extend_resident": (c_int, [P, c_int, P, c_int, P]),
     "flgp_nystrom_grid_extend_all": (c_int, [P, P, c_int, P]),
     "flgp_nystrom_grid_extend_all_resident": (c_int, [P, P, c_int, P]),
+    "flgp_glgp_neighbours": (c_int, [c_double, c_int]),
+    "flgp_glgp_spectrum_grid": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_double, c_int, P, P, P, P, P]),
+    "flgp_dev_glgp_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_double, c_int, P, P, P, P]),
+    "flgp_dev_glgp_select": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "flgp_dev_glgp_distances": (c_int, [P, P, c_int, c_int, c_int, P, c_int]),
+    "flgp_glgp_last_iterations": (c_int, [P, c_int]),
+    "flgp_dev_glgp_similarity": (c_int, [P, P, c_int, c_int, P, P, c_double, P, c_int, P]),
     "flgp_heat_kernel_spectrum_model": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, c_char_p,
                                                 c_int, c_double, P, P]),
     "flgp_spectrum_model_dims": (c_int, [P, P, P, P, P, P, P, P, P]),

@@ -1008,6 +1008,49 @@ def se_spectrum_grid(X, X_new, s, r, K=-1, a2s=None, models=None, nstart=1, U=No
     return [EigenPair(values[i].copy(), np.asfortranarray(vectors[i].T)) for i in range(a2s.size)], float(mean[0])
 
 
+def glgp_neighbours(threshold, n):
+    """r of the sparse GLGP route: ``max(round(threshold * n), 3)`` (src/Fit.cpp:388)."""
+    return int(_lib.lib().flgp_glgp_neighbours(float(threshold), int(n)))
+
+
+def glgp_spectrum_grid(X, X_new, K, a2s=None, threshold=0.01, sparse=True, resident=False, max_parallel=4):
+    """The spectrum step of fit_gl_{regression,logit,logit_mult}_gp_cpp (src/Fit.cpp:383-449) on the rows ``[X; X_new]``
+    for the bandwidths ``a2s`` (default: the ten of R/Fit.R:227-240): the dense n x n Gaussian similarity, or with
+    ``sparse`` (the R default) the one of every point's r = max(round(threshold n), 3) nearest rows, symmetrised; the two
+    normalisations; the top-K eigenpairs.  n <= 32768.  Returns (list of EigenPair -- ResidentEigenPair with ``resident``
+    --, distances_mean, r); see include/flgp_hip.h for the one departure from ``eigs_sym`` (largest algebraic values)."""
+    a2s = np.ascontiguousarray(_DEFAULT_A2S if a2s is None else a2s, dtype=np.float64).reshape(-1)
+    if a2s.size < 1:
+        raise ValueError("a2s must hold at least one bandwidth")
+    X = _f64(X, "X"); X_new = _f64(X_new, "X_new")
+    if X.shape[1] != X_new.shape[1]:
+        raise ValueError("X and X_new must have the same number of columns")
+    X_all = np.asfortranarray(np.vstack([X, X_new]))
+    n, d = X_all.shape
+    if n < 3:
+        raise ValueError(f"need at least 3 rows (n={n})")
+    if K is None or not 1 <= int(K) <= n:
+        raise ValueError(f"need 1 <= K <= n (K={K}, n={n})")
+    K = int(K); l = a2s.size
+    if sparse and not (np.isfinite(threshold) and threshold > 0):
+        raise ValueError(f"threshold must be positive and finite (got {threshold})")
+    if sparse and np.floor(float(threshold) * n + 0.5) > n:
+        raise ValueError(f"threshold {threshold} asks for more than n = {n} neighbours")
+    mean = ctypes.c_double(); r = ctypes.c_int()
+    L = _lib.lib()
+    if resident:
+        out = (ctypes.c_void_p * l)()
+        check(L.flgp_glgp_spectrum_grid(_ptr(X_all), n, d, K, _ptr(a2s), l, int(bool(sparse)), float(threshold), int(max_parallel),
+                                        None, None, ctypes.addressof(out), ctypes.byref(mean), ctypes.byref(r)))
+        pairs = [ResidentEigenPair(ctypes.c_void_p(out[i])) for i in range(l)]
+    else:
+        values = np.zeros((l, K)); vectors = np.zeros((l, K, n))      # block i: n x K column-major
+        check(L.flgp_glgp_spectrum_grid(_ptr(X_all), n, d, K, _ptr(a2s), l, int(bool(sparse)), float(threshold), int(max_parallel),
+                                        _ptr(values), _ptr(vectors), None, ctypes.byref(mean), ctypes.byref(r)))
+        pairs = [EigenPair(values[i].copy(), np.asfortranarray(vectors[i].T)) for i in range(l)]
+    return pairs, mean.value, r.value
+
+
 def lae_eigenmap(X, s, r=3, ndim=2, subsample="kmeans", norm="cluster-normalized", nstart=1, U=None):
     """lae_eigenmap (src/Spectrum.cpp:17-25, defaults src/Spectrum.h:43-44)."""
     X = _f64(X, "X")

@@ -368,6 +368,15 @@ int nystrom_grid_extend(hipStream_t st, const flgp_nystrom_grid *G, int i, const
                         int ldv);
 int nystrom_grid_extend_all(hipStream_t st, const flgp_nystrom_grid *G, const double *dX, int n, int ldx,
                             double *const *d_vectors, int ldv);
+// The steps of the anchor side that the GLGP grid (glgp.hip) shares: see nystrom.hip.  The void ones only launch.
+int nys_self_distances(hipStream_t st, const double *dU, int s, int ldu, int d, int dpad, const double *Ut, const double *uu,
+                       double *D, double *p1, double *xx, double *rsx);
+void nys_exp_from(hipStream_t st, const double *D, double *W, long count, double inv_c);
+void nys_colsum(hipStream_t st, const double *M, int s, long ld, double *colsum);
+void nys_symscale(hipStream_t st, double *W, int s, const double *a);
+void nys_first_scaling(hipStream_t st, double *W, int s, double *rs, bool have_sums = false);
+void nys_second_factor(hipStream_t st, const double *W, int s, double *sd);
+void nys_vector_norms(hipStream_t st, double *V, int s, int K, const double *sd, double *nrm);
 }  // namespace flgp
 
 // anchor side of the Nystrom bandwidth grid (include/flgp_hip.h): made and consumed in nystrom.hip

@@ -119,12 +119,12 @@ __global__ void nys_exp_kernel(double *__restrict__ M, long count, double inv_c)
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < count) M[e] = exp(-M[e] * inv_c);
 }
-// colsum[j] = sum_i M(i, j) (rows ascending, one workgroup per column, fixed tree)
-__global__ __launch_bounds__(256) void nys_colsum_kernel(const double *__restrict__ M, int s, double *__restrict__ colsum) {
+// colsum[j] = sum_i M(i, j) (rows ascending, one workgroup per column, fixed tree); M column-major at ld
+__global__ __launch_bounds__(256) void nys_colsum_kernel(const double *__restrict__ M, int s, long ld, double *__restrict__ colsum) {
   __shared__ double red[256];
   const int j = blockIdx.x;
   double a = 0.0;
-  for (int i = threadIdx.x; i < s; i += 256) a += M[(size_t)j * s + i];
+  for (int i = threadIdx.x; i < s; i += 256) a += M[(size_t)j * ld + i];
   red[threadIdx.x] = a;
   __syncthreads();
   for (int off = 128; off > 0; off >>= 1) {
@@ -300,6 +300,50 @@ static int launch_sim_grid(hipStream_t st, int dpad, const double *X, int nb, in
   return check_launch("nys_sim_grid_kernel");
 }
 
+// ---- the steps of the anchor side that the GLGP grid (glgp.hip) takes as well: the same kernels in the same order
+// D(x, j) = fma(-2, dot, |u_x|^2) + |u_j|^2 of the points with themselves (s x s, ld s) and its row sums in rsx; p1 holds
+// ceil(s / 64) x s doubles, xx s (read for dpad > 64 only)
+int nys_self_distances(hipStream_t st, const double *dU, int s, int ldu, int d, int dpad, const double *Ut, const double *uu,
+                       double *D, double *p1, double *xx, double *rsx) {
+  const int nchunk = ceil_div(s, 64);
+  if (dpad > 64) {   // no register kernel beyond d = 64: dot products by the GEMM (one chain per element, the same bits)
+    hipLaunchKernelGGL(nys_sqnorm_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, dU, s, ldu, d, xx);
+    FLGP_TRY(check_launch("nys_sqnorm_kernel"));
+    FLGP_TRY(gemm_launch(st, s, s, d, 1.0, dU, 1, ldu, dU, ldu, 1, 0.0, nullptr, 0, 0, D, 1, s, nullptr, 0, 0.0, nullptr));
+    hipLaunchKernelGGL(nys_dist_rows_kernel, dim3(ceil_div(s, 256), nchunk), dim3(256), 0, st, D, s, s, xx, uu, p1);
+    FLGP_TRY(check_launch("nys_dist_rows_kernel"));
+  } else {
+    FLGP_TRY((launch_sim<0>(st, dpad, dU, s, ldu, d, Ut, uu, s, 0.0, nullptr, D, s, p1, nullptr)));
+  }
+  hipLaunchKernelGGL(nys_reduce_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, p1, nullptr, nchunk, s, 0.0, rsx, nullptr);
+  return check_launch("nys_reduce_kernel");
+}
+void nys_exp_from(hipStream_t st, const double *D, double *W, long count, double inv_c) {
+  hipLaunchKernelGGL(nys_exp_from_kernel, dim3(ceil_div(count, 256)), dim3(256), 0, st, D, W, count, inv_c);
+}
+void nys_colsum(hipStream_t st, const double *M, int s, long ld, double *colsum) {
+  hipLaunchKernelGGL(nys_colsum_kernel, dim3(s), dim3(256), 0, st, M, s, ld, colsum);
+}
+void nys_symscale(hipStream_t st, double *W, int s, const double *a) {
+  hipLaunchKernelGGL(nys_symscale_kernel, dim3(ceil_div((long)s * s, 256)), dim3(256), 0, st, W, s, a);
+}
+// rs = 1 / (rowsum(W) + 1e-9), or from the sums already in rs (have_sums);  W <- diag(rs) W diag(rs)
+void nys_first_scaling(hipStream_t st, double *W, int s, double *rs, bool have_sums) {
+  if (!have_sums) nys_colsum(st, W, s, s, rs);
+  hipLaunchKernelGGL(nys_vec_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, rs, s, 0);      // 1/(rs + 1e-9)
+  nys_symscale(st, W, s, rs);
+}
+// sd = 1 / sqrt(rowsum(W) + 1e-9); the caller scales with it
+void nys_second_factor(hipStream_t st, const double *W, int s, double *sd) {
+  nys_colsum(st, W, s, s, sd);
+  hipLaunchKernelGGL(nys_vec_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, sd, s, 1);       // 1/sqrt(. + 1e-9)
+}
+// V(j, k) <- sd[j] V(j, k) (s x K, ld s) and the column norms
+void nys_vector_norms(hipStream_t st, double *V, int s, int K, const double *sd, double *nrm) {
+  hipLaunchKernelGGL(nys_rowscale_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, V, s, K, s, sd);
+  hipLaunchKernelGGL(nys_colnorm_kernel, dim3(K), dim3(256), 0, st, V, s, nrm);
+}
+
 // Rows of X per block of the extension with `nz` blocks of Z_XU (rows x s each) resident: whole rounds of the GEMM grid
 // (128 x 128 tiles, two co-resident workgroups per CU, 256 CUs) while the nz blocks together stay under 2 GB; below one
 // round a multiple of 256, and never fewer than 256.  (include/flgp_hip.h states this rule for the callers.)
@@ -467,17 +511,13 @@ int anchor_side(hipStream_t st, flgp_nystrom_grid *G, int i, const double *D, An
   double *W = A.W.as<double>(), *sd = A.sd.as<double>(), *nrm = A.nrm.as<double>();
   double *rsu = (double *)G->rsu_of(i), *values = (double *)G->values_of(i), *eigv = (double *)G->eigv_of(i);
   // W is symmetric, so column sums are row sums
-  hipLaunchKernelGGL(nys_exp_from_kernel, dim3(ceil_div(ss, 256)), dim3(256), 0, st, D, W, ss, G->inv_c[i]);
-  hipLaunchKernelGGL(nys_colsum_kernel, dim3(s), dim3(256), 0, st, W, s, rsu);
-  hipLaunchKernelGGL(nys_vec_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, rsu, s, 0);      // 1/(rs_U + 1e-9)
-  hipLaunchKernelGGL(nys_symscale_kernel, dim3(ceil_div(ss, 256)), dim3(256), 0, st, W, s, rsu);
-  hipLaunchKernelGGL(nys_colsum_kernel, dim3(s), dim3(256), 0, st, W, s, sd);
-  hipLaunchKernelGGL(nys_vec_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, sd, s, 1);       // 1/sqrt(. + 1e-9)
-  hipLaunchKernelGGL(nys_symscale_kernel, dim3(ceil_div(ss, 256)), dim3(256), 0, st, W, s, sd);
+  nys_exp_from(st, D, W, ss, G->inv_c[i]);
+  nys_first_scaling(st, W, s, rsu);
+  nys_second_factor(st, W, s, sd);
+  nys_symscale(st, W, s, sd);
   FLGP_TRY(check_launch("nystrom W_UU"));
   FLGP_TRY(flgp_dev_eig_topk(st, W, s, s, K, 0.0, values, eigv, s, A.work.p, A.wb, nullptr));
-  hipLaunchKernelGGL(nys_rowscale_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, eigv, s, K, s, sd);
-  hipLaunchKernelGGL(nys_colnorm_kernel, dim3(K), dim3(256), 0, st, eigv, s, nrm);
+  nys_vector_norms(st, eigv, s, K, sd, nrm);
   hipLaunchKernelGGL(nys_vfinal_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, eigv, s, K, nrm, rsu, values,
                      std::sqrt((double)s));
   FLGP_TRY(check_launch("nystrom V_UU"));
@@ -526,21 +566,8 @@ extern "C" int flgp_dev_nystrom_grid_create(void *stream, const double *dU, int 
                             hipMemcpyDeviceToDevice, st));
   FLGP_TRY(flgp_dev_anchor_prep(st, dU, s, ldu, d, G->Ut.as<double>(), G->uu.as<double>()));
   // ---- D_UU and its mean (src/Fit.cpp:244,248), once for the grid
-  if (dpad > 64) {   // no register kernel beyond d = 64: dot products by the GEMM (one chain per element, the same bits)
-    hipLaunchKernelGGL(nys_sqnorm_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, dU, s, ldu, d, xx.as<double>());
-    FLGP_TRY(check_launch("nys_sqnorm_kernel"));
-    FLGP_TRY(gemm_launch(st, s, s, d, 1.0, dU, 1, ldu, dU, ldu, 1, 0.0, nullptr, 0, 0, D.as<double>(), 1, s, nullptr, 0, 0.0,
-                         nullptr));
-    hipLaunchKernelGGL(nys_dist_rows_kernel, dim3(ceil_div(s, 256), nchunk), dim3(256), 0, st, D.as<double>(), s, s,
-                       xx.as<double>(), G->uu.as<double>(), p1.as<double>());
-    FLGP_TRY(check_launch("nys_dist_rows_kernel"));
-  } else {
-    FLGP_TRY((launch_sim<0>(st, dpad, dU, s, ldu, d, G->Ut.as<double>(), G->uu.as<double>(), s, 0.0, nullptr, D.as<double>(), s,
-                            p1.as<double>(), nullptr)));
-  }
-  hipLaunchKernelGGL(nys_reduce_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, p1.as<double>(), nullptr, nchunk, s, 0.0,
-                     rsx.as<double>(), nullptr);
-  FLGP_TRY(check_launch("nys_reduce_kernel"));
+  FLGP_TRY(nys_self_distances(st, dU, s, ldu, d, dpad, G->Ut.as<double>(), G->uu.as<double>(), D.as<double>(), p1.as<double>(),
+                              xx.as<double>(), rsx.as<double>()));
   std::vector<double> hrow(s);
   FLGP_HIP(hipMemcpyAsync(hrow.data(), rsx.p, sizeof(double) * s, hipMemcpyDeviceToHost, st));
   FLGP_HIP(hipStreamSynchronize(st));
