@@ -1216,48 +1216,38 @@ static int se_grid_core(Sim &S, hipStream_t st0, int r, int K, const double *a2s
   FLGP_TRY(d2h(&mean, dmean.p, sizeof(double), st0));
   FLGP_HIP(hipStreamSynchronize(st0));
   if (distances_mean_out) *distances_mean_out = mean;
-  int dev = 0;
-  FLGP_HIP(hipGetDevice(&dev));
 
-  std::vector<int> rcs(l, FLGP_OK);
-  std::vector<std::string> msgs(l);
-  auto work = [&](int i) -> int {
-    FLGP_HIP(hipSetDevice(dev));
-    Stream ws;
-    FLGP_TRY(ws.create());
-    Sim W;   // borrows the pattern and its CSC view from S, owns its values and column sums
+  // what a worker keeps across its bandwidths: the weights and the pattern copy that the weights kernel writes beside them
+  struct SeWorker { DevBuf ell_val, scratch_idx; };
+  auto setup = [&](SeWorker &A) -> int {
+    FLGP_TRY(A.ell_val.alloc(sizeof(double) * (size_t)n * r));
+    return A.scratch_idx.alloc(sizeof(int) * (size_t)n * r);
+  };
+  auto work = [&](hipStream_t ws, SeWorker &A, int i) -> int {
+    Sim W;   // borrows the pattern and its CSC view from S and the values from its worker, owns its column sums
     W.n = n; W.d = S.d; W.s = s; W.r = r;
     W.ell_idx.borrow(S.ell_idx.p); W.colptr.borrow(S.colptr.p); W.pos.borrow(S.pos.p); W.order.borrow(S.order.p);
     W.have_csc = true;
-    FLGP_TRY(W.ell_val.alloc(sizeof(double) * (size_t)n * r));
-    DevBuf scratch_idx;
-    FLGP_TRY(scratch_idx.alloc(sizeof(int) * (size_t)n * r));
-    FLGP_TRY(flgp_dev_se_weights_den(ws.s, S.knn_idx.as<int>(), S.knn_dist.as<double>(), n, n, r, a2s[i] * mean,
-                                     scratch_idx.as<int>(), W.ell_val.as<double>()));
-    FLGP_TRY(laplacian(W, ws.s, glc, sizes));
+    W.ell_val.borrow(A.ell_val.p);
+    FLGP_TRY(flgp_dev_se_weights_den(ws, S.knn_idx.as<int>(), S.knn_dist.as<double>(), n, n, r, a2s[i] * mean,
+                                     A.scratch_idx.as<int>(), W.ell_val.as<double>()));
+    FLGP_TRY(laplacian(W, ws, glc, sizes));
     Spectrum P;     // straight into the caller's device blocks where it has them
     if (d_values) P.values.borrow(d_values + (size_t)i * K);
     if (d_vectors) P.vectors.borrow(d_vectors + (size_t)i * n * K);
     int info[4] = {0, 0, 0, 0};
-    const int rc = spectrum(W, ws.s, K, root, P, info);   // (a bandwidth that underflows a column of Z ends here, with the message)
+    const int rc = spectrum(W, ws, K, root, P, info);   // (a bandwidth that underflows a column of Z ends here, with the message)
     if (iters_out) iters_out[i] = info[0];
     FLGP_TRY(rc);
     const double *vals_p = P.values.as<double>(), *vecs_p = P.vectors.as<double>();
-    if (values) FLGP_TRY(d2h(values + (size_t)i * K, vals_p, sizeof(double) * (size_t)K, ws.s));
-    if (vectors) FLGP_TRY(d2h(vectors + (size_t)i * n * K, vecs_p, sizeof(double) * (size_t)n * K, ws.s));
-    FLGP_HIP(hipStreamSynchronize(ws.s));
+    if (values) FLGP_TRY(d2h(values + (size_t)i * K, vals_p, sizeof(double) * (size_t)K, ws));
+    if (vectors) FLGP_TRY(d2h(vectors + (size_t)i * n * K, vecs_p, sizeof(double) * (size_t)n * K, ws));
+    FLGP_HIP(hipStreamSynchronize(ws));
     return FLGP_OK;
   };
-  if (max_parallel < 1) max_parallel = 1;
-  for (int i0 = 0; i0 < l; i0 += max_parallel) {
-    std::vector<std::thread> th;
-    for (int i = i0; i < l && i < i0 + max_parallel; ++i)
-      th.emplace_back([&, i]() { rcs[i] = work(i); if (rcs[i] != FLGP_OK) msgs[i] = flgp_last_error(); });
-    for (auto &t : th) t.join();
-  }
-  for (int i = 0; i < l; ++i)
-    if (rcs[i] != FLGP_OK) { set_error("bandwidth %d (a2=%g): %s", i, a2s[i], msgs[i].c_str()); return rcs[i]; }
-  return FLGP_OK;
+  DevicePool pool;     // no memory cap: a spectrum's buffers are not known here
+  FLGP_TRY(pool.plan(max_parallel, l, 0.0));
+  return bandwidth_failure(pool.run<SeWorker>(st0, l, setup, work), a2s);
 }
 
 extern "C" int flgp_se_spectrum_grid(const double *X_all, int n, int d, const double *U, int s, int ucols, int r,

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/flgp_hip.h"
+#include "worker_pool.h"
 
 namespace flgp {
 
@@ -121,6 +122,42 @@ struct Stream {
   ~Stream() { if (s) (void)hipStreamDestroy(s); }
   int create() { FLGP_HIP(hipStreamCreate(&s)); return FLGP_OK; }
 };
+
+// The worker pool (worker_pool.h) on the current device.  plan(): the worker count, capped by the free memory where
+// bytes_per_worker > 0.  run<Own>(): setup(Own &) makes what a worker owns, item(stream, Own &, i) runs item i on
+// it.  A single worker runs on the calling thread and on `st`; several have a host thread and a stream each.
+struct DevicePool {
+  int dev = 0, workers = 1;
+  int plan(int max_parallel, int items, double bytes_per_worker) {
+    FLGP_HIP(hipGetDevice(&dev));
+    size_t free_b = 0, total_b = 0;
+    if (bytes_per_worker > 0.0 && plan_workers(max_parallel, items, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+    workers = plan_workers(max_parallel, items, (double)free_b, bytes_per_worker);
+    return FLGP_OK;
+  }
+  template <class Own, class Setup, class Item>
+  PoolFailure run(hipStream_t st, int items, Setup setup, Item item) const {
+    struct State { Stream own; hipStream_t st = nullptr; Own a; };     // `a` goes before its stream does
+    return run_strided<State>(
+        items, workers,
+        [&](int, State &S) -> int {
+          if (workers == 1) {
+            S.st = st;
+          } else {
+            FLGP_HIP(hipSetDevice(dev));
+            FLGP_TRY(S.own.create());
+            S.st = S.own.s;
+          }
+          return setup(S.a);
+        },
+        [&](State &S, int i) -> int { return item(S.st, S.a, i); }, [] { return std::string(flgp_last_error()); });
+  }
+};
+// how the bandwidth grids report what their pool found
+inline int bandwidth_failure(const PoolFailure &f, const double *a2s) {
+  if (f.item >= 0) set_error("bandwidth %d (a2=%g): %s", f.item, a2s[f.item], f.message.c_str());
+  return f.status;
+}
 
 inline int h2d(void *dst, const void *src, size_t bytes, hipStream_t st) {
   if (bytes) FLGP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
@@ -368,12 +405,28 @@ int nystrom_grid_extend(hipStream_t st, const flgp_nystrom_grid *G, int i, const
                         int ldv);
 int nystrom_grid_extend_all(hipStream_t st, const flgp_nystrom_grid *G, const double *dX, int n, int ldx,
                             double *const *d_vectors, int ldv);
+// "bandwidth %d (a2=%g): <who>: a2 must be positive and finite" for the first of the l bandwidths that is not
+int check_bandwidths(const char *who, const double *a2s, int l);
 // The steps of the anchor side that the GLGP grid (glgp.hip) shares: see nystrom.hip.  The void ones only launch.
+// What nys_self_distances needs beside its result: the partial and whole row sums (rsx is part of the result), the squared
+// norms and, for a caller that does not keep one (with_panel), the padded panel of the s points (flgp_dev_anchor_prep)
+struct NysScratch {
+  DevBuf p1, xx, rsx, Ut, uu;
+  int alloc(int s, int dpad, bool with_panel) {
+    FLGP_TRY(p1.alloc(sizeof(double) * (size_t)ceil_div(s, 64) * s));
+    FLGP_TRY(xx.alloc(sizeof(double) * (size_t)s));
+    FLGP_TRY(rsx.alloc(sizeof(double) * (size_t)s));
+    if (!with_panel) return FLGP_OK;
+    const size_t rows = (size_t)flgp_dev_anchor_rows(s);
+    FLGP_TRY(Ut.alloc(sizeof(double) * rows * dpad));
+    return uu.alloc(sizeof(double) * rows);
+  }
+};
 int nys_self_distances(hipStream_t st, const double *dU, int s, int ldu, int d, int dpad, const double *Ut, const double *uu,
-                       double *D, double *p1, double *xx, double *rsx);
-void nys_exp_from(hipStream_t st, const double *D, double *W, long count, double inv_c);
+                       double *D, NysScratch &T);
+// W = exp(-D inv_c) (s x s), its first scaling (rs) and second factor (sd), W <- diag(sd) W diag(sd)
+void nys_normalised_w(hipStream_t st, const double *D, double *W, int s, double inv_c, double *rs, double *sd);
 void nys_colsum(hipStream_t st, const double *M, int s, long ld, double *colsum);
-void nys_symscale(hipStream_t st, double *W, int s, const double *a);
 void nys_first_scaling(hipStream_t st, double *W, int s, double *rs, bool have_sums = false);
 void nys_second_factor(hipStream_t st, const double *W, int s, double *sd);
 void nys_vector_norms(hipStream_t st, double *V, int s, int K, const double *sd, double *nrm);

@@ -9,8 +9,6 @@
 #include "common.h"
 #include <algorithm>
 #include <cmath>
-#include <string>
-#include <thread>
 #include <vector>
 
 using namespace flgp;
@@ -976,15 +974,6 @@ int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int 
     DevBuf Gf;
     if (fused) FLGP_TRY(Gf.alloc(sizeof(double) * ge * J));
     std::vector<GprCtx> ctx((size_t)J);
-    int workers = std::min(max_parallel < 1 ? 1 : max_parallel, J);
-    if (workers > 1) {       // no more than fit into 90 % of the free memory
-      size_t free_b = 0, total_b = 0;
-      FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-      const double fit = 0.9 * (double)free_b / McWorker::bytes(m, K, !fused);
-      if (fit < workers) workers = fit < 1.0 ? 1 : (int)fit;
-    }
-    std::vector<int> rcs((size_t)J, FLGP_OK);
-    std::vector<std::string> msgs((size_t)J);
     // one class on a worker's stream: the binary entry's launches in the binary entry's order
     auto one_class = [&](hipStream_t ws, McWorker &W, int j) -> int {
       char name[64];
@@ -1009,38 +998,17 @@ int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int 
       FLGP_TRY(read_flag(ws, S.flag.p, &bad));
       return GpcNewton::pivot_error(bad, name, 0);
     };
-    // worker w takes classes w, w + workers, ... and stops at its first failure: the lowest failing class is always run
-    auto run_worker = [&](hipStream_t ws, int w) -> int {
-      McWorker W;
-      W.S.L.sigma = sigma11; W.S.L.V1 = r0.V; W.S.L.ld1 = r0.ld;
-      FLGP_TRY(W.alloc(m, K));
-      for (int j = w; j < J; j += workers) {
-        rcs[(size_t)j] = one_class(ws, W, j);
-        if (rcs[(size_t)j] != FLGP_OK) { msgs[(size_t)j] = flgp_last_error(); break; }
-      }
-      return FLGP_OK;
-    };
-    if (workers == 1) {      // in line, on the entry's stream
-      FLGP_TRY(run_worker(st.s, 0));
-    } else {                 // one host thread and one stream per worker
-      int dev = 0;
-      FLGP_HIP(hipGetDevice(&dev));
-      auto run = [&, dev](int w) {
-        auto body = [&]() -> int {
-          FLGP_HIP(hipSetDevice(dev));
-          Stream ws;
-          FLGP_TRY(ws.create());
-          return run_worker(ws.s, w);
-        };
-        const int rc = body();
-        if (rc != FLGP_OK && rcs[(size_t)w] == FLGP_OK) { rcs[(size_t)w] = rc; msgs[(size_t)w] = flgp_last_error(); }
-      };
-      std::vector<std::thread> th;
-      for (int w = 0; w < workers; ++w) th.emplace_back(run, w);
-      for (auto &t : th) t.join();
-    }
-    for (int j = 0; j < J; ++j)
-      if (rcs[(size_t)j] != FLGP_OK) { set_error("%s", msgs[(size_t)j].c_str()); return rcs[(size_t)j]; }
+    // the classes are dealt to the pool's workers (worker_pool.h), one worker on the entry's stream
+    DevicePool pool;
+    FLGP_TRY(pool.plan(max_parallel, J, McWorker::bytes(m, K, !fused)));
+    const PoolFailure bad = pool.run<McWorker>(
+        st.s, J,
+        [&](McWorker &W) {
+          W.S.L.sigma = sigma11; W.S.L.V1 = r0.V; W.S.L.ld1 = r0.ld;
+          return W.alloc(m, K);
+        },
+        one_class);
+    if (bad.item >= 0) { set_error("%s", bad.message.c_str()); return bad.status; }
     // every worker's stream has been waited for: the J operands are in place
     if (fused)
       FLGP_TRY(gpc_predict_rows_multi(st.s, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, J, Gf.as<double>(),

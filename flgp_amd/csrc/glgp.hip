@@ -5,8 +5,8 @@
 //            Z = (Z_kept + Z_kept^T) / 2
 //   rs = rowsum(Z) + 1e-9;  A = Z / (rs rs^T);  sd = 1/sqrt(rowsum(A) + 1e-9);  W = sd A sd
 //   (values, V) = top-K eigenpairs of W;  V <- sd V, columns rescaled to norm sqrt(n) (+1e-9 guard)
-// The dense route IS the anchor side of the Nystrom grid with U = X_all (nystrom.hip), launch for launch, up to the last
-// kernel.  The sparsified W is indefinite (eigenvalues down to about -0.33) and the eigensolver damps [0, cut], so the sparse
+// The dense route IS the anchor side of the Nystrom grid with U = X_all, up to the last kernel: both go through
+// nys_self_distances and nys_normalised_w (nystrom.hip).  The sparsified W is indefinite (eigenvalues down to about -0.33) and the eigensolver damps [0, cut], so the sparse
 // route hands it W' = (W + I) / 2, whose spectrum lies in (0, 1), and returns 2 lambda' - 1.
 // The kept set of point i is never stored as an index list: it is {j : D < tau_i or (D == tau_i and j <= jcut_i)} with
 // tau_i the r-th smallest of the list and jcut_i the column of the last kept one among those equal to it (ties go to the
@@ -16,8 +16,6 @@
 #include <cmath>
 #include <memory>
 #include <mutex>
-#include <string>
-#include <thread>
 
 namespace flgp {
 
@@ -207,13 +205,6 @@ __global__ void glgp_vfinal_kernel(double *__restrict__ V, int n, int K, const d
 
 using namespace flgp;
 
-extern "C" int flgp_dev_anchor_dpad(int d);
-extern "C" int flgp_dev_anchor_rows(int s);
-extern "C" int flgp_dev_anchor_prep(void *stream, const double *dU, int s, int ldu, int d, double *dUt, double *duu);
-extern "C" size_t flgp_dev_eig_workspace(int s, int K);
-extern "C" int flgp_dev_eig_topk(void *stream, const double *dG, int ldg, int s, int K, double tol, double *d_values,
-                                 double *dV, int ldv, void *d_work, size_t work_bytes, int *info);
-
 extern "C" int flgp_glgp_neighbours(double threshold, int n) {
   const double x = std::floor(threshold * (double)n + 0.5);
   if (!(x >= 3.0)) return 3;
@@ -252,11 +243,7 @@ int glgp_check(const void *X, int n, int d, int K, const double *a2s, int l, int
   FLGP_REQUIRE(d >= 1 && flgp_dev_anchor_dpad(d) > 0, "glgp: kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
   FLGP_REQUIRE(K >= 1 && K <= n, "glgp: need 1 <= K <= n (K=%d, n=%d)", K, n);
   FLGP_REQUIRE(l >= 1, "glgp: need at least one bandwidth (l=%d)", l);
-  for (int i = 0; i < l; ++i)
-    if (!(a2s[i] > 0.0) || !std::isfinite(a2s[i])) {
-      set_error("bandwidth %d (a2=%g): glgp: a2 must be positive and finite", i, a2s[i]);
-      return FLGP_ERR_INVALID;
-    }
+  FLGP_TRY(check_bandwidths("glgp", a2s, l));
   if (sparse) {
     FLGP_REQUIRE(std::isfinite(threshold) && threshold > 0.0, "glgp: threshold must be positive and finite (got %g)", threshold);
     FLGP_REQUIRE(threshold * (double)n + 0.5 < (double)n + 1.0, "glgp: threshold %g asks for more than n = %d neighbours", threshold, n);
@@ -304,11 +291,8 @@ int glgp_bandwidth(hipStream_t st, const GlgpGrid &G, int i, GlgpWorker &A, doub
       nys_first_scaling(st, W, n, rs, true);
       nys_second_factor(st, W, n, sd);
       hipLaunchKernelGGL(glgp_symscale_shift_kernel, dim3(ceil_div((long)n * n, 256)), dim3(256), 0, st, W, n, sd);
-    } else {             // the Nystrom grid's anchor side, launch for launch
-      nys_exp_from(st, G.D, W, (long)n * n, G.inv_c[i]);
-      nys_first_scaling(st, W, n, rs);
-      nys_second_factor(st, W, n, sd);
-      nys_symscale(st, W, n, sd);
+    } else {             // the Nystrom grid's anchor side
+      nys_normalised_w(st, G.D, W, n, G.inv_c[i], rs, sd);
     }
     FLGP_TRY(check_launch("glgp W"));
   }
@@ -336,9 +320,8 @@ int glgp_bandwidth(hipStream_t st, const GlgpGrid &G, int i, GlgpWorker &A, doub
 
 // Dt (ldd): column i = point i's list, D = fma(-2, dot_ij, |x_i|^2) + |x_j|^2 at row j -- the transpose of what the Nystrom
 // distance step leaves in D0 (n x n)
-int glgp_lists(hipStream_t st, const double *dX, int n, int ldx, int d, int dpad, const double *Ut, const double *uu, double *D0,
-               double *p1, double *xx, double *rsx, double *Dt, long ldd) {
-  FLGP_TRY(nys_self_distances(st, dX, n, ldx, d, dpad, Ut, uu, D0, p1, xx, rsx));
+int glgp_lists(hipStream_t st, const double *dX, int n, int ldx, int d, int dpad, NysScratch &S, double *D0, double *Dt, long ldd) {
+  FLGP_TRY(nys_self_distances(st, dX, n, ldx, d, dpad, S.Ut.as<double>(), S.uu.as<double>(), D0, S));
   const int T = ceil_div(n, GLGP_T);
   hipLaunchKernelGGL(glgp_transpose_kernel, dim3(T, T), dim3(256), 0, st, D0, n, Dt, ldd);
   return check_launch("glgp_transpose_kernel");
@@ -347,7 +330,7 @@ int glgp_lists(hipStream_t st, const double *dX, int n, int ldx, int d, int dpad
 // the grid on device points; out_val[i] / out_vec[i]: where bandwidth i goes (either array may be NULL)
 int glgp_grid(hipStream_t st, const double *dX, int n, int ldx, int d, int K, const double *a2s, int l, int sparse,
               double threshold, int max_parallel, double *const *out_val, double *const *out_vec, double *mean_out, int *r_out) {
-  const int dpad = flgp_dev_anchor_dpad(d), rows = flgp_dev_anchor_rows(n), nchunk = ceil_div(n, 64);
+  const int dpad = flgp_dev_anchor_dpad(d);
   const int r = sparse ? flgp_glgp_neighbours(threshold, n) : n;
   FLGP_REQUIRE(r <= n, "glgp: threshold %g asks for %d of n = %d neighbours", threshold, r, n);
   if (ldx == n) FLGP_TRY(check_finite_on_device(st, dX, (long)n * d, "glgp"));
@@ -357,32 +340,27 @@ int glgp_grid(hipStream_t st, const double *dX, int n, int ldx, int d, int K, co
   DevBuf D, tau, jcut;
   double total = 0.0;
   {
-    DevBuf Ut, uu, p1, xx, rsx, D0;
-    FLGP_TRY(Ut.alloc(sizeof(double) * (size_t)rows * dpad));
-    FLGP_TRY(uu.alloc(sizeof(double) * (size_t)rows));
-    FLGP_TRY(p1.alloc(sizeof(double) * (size_t)nchunk * n));
-    FLGP_TRY(xx.alloc(sizeof(double) * (size_t)n));
-    FLGP_TRY(rsx.alloc(sizeof(double) * (size_t)n));
+    NysScratch T;
+    DevBuf D0;
+    FLGP_TRY(T.alloc(n, dpad, true));
     FLGP_TRY(D.alloc(sizeof(double) * (size_t)n * n));
-    FLGP_TRY(flgp_dev_anchor_prep(st, dX, n, ldx, d, Ut.as<double>(), uu.as<double>()));
+    FLGP_TRY(flgp_dev_anchor_prep(st, dX, n, ldx, d, T.Ut.as<double>(), T.uu.as<double>()));
     std::vector<double> hrow(n);
     if (!sparse) {      // D and mean(D) as the Nystrom grid takes them (src/Fit.cpp:383,394)
       ProfScope prof("glgp_distances", st, 8.0 * n * (double)n);
-      FLGP_TRY(nys_self_distances(st, dX, n, ldx, d, dpad, Ut.as<double>(), uu.as<double>(), D.as<double>(), p1.as<double>(),
-                                  xx.as<double>(), rsx.as<double>()));
-      FLGP_TRY(d2h(hrow.data(), rsx.p, sizeof(double) * n, st));
+      FLGP_TRY(nys_self_distances(st, dX, n, ldx, d, dpad, T.Ut.as<double>(), T.uu.as<double>(), D.as<double>(), T));
+      FLGP_TRY(d2h(hrow.data(), T.rsx.p, sizeof(double) * n, st));
     } else {            // the lists, their r-th smallest and the kept sums (:396-428)
       FLGP_TRY(D0.alloc(sizeof(double) * (size_t)n * n));
       FLGP_TRY(tau.alloc(sizeof(double) * (size_t)n));
       FLGP_TRY(jcut.alloc(sizeof(int) * (size_t)n));
       {
         ProfScope prof("glgp_distances", st, 24.0 * n * (double)n);
-        FLGP_TRY(glgp_lists(st, dX, n, ldx, d, dpad, Ut.as<double>(), uu.as<double>(), D0.as<double>(), p1.as<double>(),
-                            xx.as<double>(), rsx.as<double>(), D.as<double>(), n));
+        FLGP_TRY(glgp_lists(st, dX, n, ldx, d, dpad, T, D0.as<double>(), D.as<double>(), n));
       }
       ProfScope prof("glgp_select", st, 8.0 * n * (double)n);
-      FLGP_TRY(flgp_dev_glgp_select(st, D.as<double>(), n, n, r, tau.as<double>(), jcut.as<int>(), rsx.as<double>()));
-      FLGP_TRY(d2h(hrow.data(), rsx.p, sizeof(double) * n, st));
+      FLGP_TRY(flgp_dev_glgp_select(st, D.as<double>(), n, n, r, tau.as<double>(), jcut.as<int>(), T.rsx.as<double>()));
+      FLGP_TRY(d2h(hrow.data(), T.rsx.p, sizeof(double) * n, st));
       G.tau = tau.as<double>(); G.jcut = jcut.as<int>();
     }
     FLGP_HIP(hipStreamSynchronize(st));
@@ -399,53 +377,16 @@ int glgp_grid(hipStream_t st, const double *dX, int n, int ldx, int d, int K, co
     std::lock_guard<std::mutex> lk(g_iters_mu);
     g_iters.assign(l, -1);
   }
-  // ---- workers, as the Nystrom grid: at most max_parallel, at most l, and no more than fit into 90 % of the free memory
-  int workers = max_parallel < 1 ? 1 : max_parallel;
-  if (workers > l) workers = l;
-  if (workers > 1) {
-    size_t free_b = 0, total_b = 0;
-    FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-    const double per = 8.0 * n * (double)n + (double)flgp_dev_eig_workspace(n, K) + 8.0 * (2.0 * n + 2.0 * K + (double)n * K);
-    const double fit = 0.9 * (double)free_b / per;
-    if (fit < workers) workers = fit < 1.0 ? 1 : (int)fit;
-  }
-  std::vector<int> rcs(l, FLGP_OK);
-  std::vector<std::string> msgs(l);
-  auto val_of = [&](int i) { return out_val ? out_val[i] : nullptr; };
-  auto vec_of = [&](int i) { return out_vec ? out_vec[i] : nullptr; };
-  if (workers == 1) {      // in line, on the caller's stream
-    GlgpWorker A;
-    FLGP_TRY(A.alloc(n, K));
-    for (int i = 0; i < l; ++i) {
-      rcs[i] = glgp_bandwidth(st, G, i, A, val_of(i), vec_of(i));
-      if (rcs[i] != FLGP_OK) { msgs[i] = flgp_last_error(); break; }
-    }
-  } else {                 // one host thread and one stream per worker; worker w takes bandwidths w, w + workers, ...
-    int dev = 0;
-    FLGP_HIP(hipGetDevice(&dev));
-    auto run = [&](int w) {
-      auto body = [&]() -> int {
-        FLGP_HIP(hipSetDevice(dev));
-        Stream ws;
-        FLGP_TRY(ws.create());
-        GlgpWorker A;
-        FLGP_TRY(A.alloc(n, K));
-        for (int i = w; i < l; i += workers) {
-          rcs[i] = glgp_bandwidth(ws.s, G, i, A, val_of(i), vec_of(i));
-          if (rcs[i] != FLGP_OK) { msgs[i] = flgp_last_error(); return FLGP_OK; }
-        }
-        return FLGP_OK;
-      };
-      const int rc = body();
-      if (rc != FLGP_OK && rcs[w] == FLGP_OK) { rcs[w] = rc; msgs[w] = flgp_last_error(); }
-    };
-    std::vector<std::thread> th;
-    for (int w = 0; w < workers; ++w) th.emplace_back(run, w);
-    for (auto &t : th) t.join();
-  }
-  for (int i = 0; i < l; ++i)
-    if (rcs[i] != FLGP_OK) { set_error("bandwidth %d (a2=%g): %s", i, a2s[i], msgs[i].c_str()); return rcs[i]; }
-  return FLGP_OK;
+  // ---- workers as the Nystrom grid's (worker_pool.h); one owns W, the eigensolver's workspace and an n x K block
+  DevicePool pool;
+  FLGP_TRY(pool.plan(max_parallel, l,
+                     8.0 * n * (double)n + (double)flgp_dev_eig_workspace(n, K) + 8.0 * (2.0 * n + 2.0 * K + (double)n * K)));
+  return bandwidth_failure(pool.run<GlgpWorker>(
+                               st, l, [&](GlgpWorker &A) { return A.alloc(n, K); },
+                               [&](hipStream_t ws, GlgpWorker &A, int i) {
+                                 return glgp_bandwidth(ws, G, i, A, out_val ? out_val[i] : nullptr, out_vec ? out_vec[i] : nullptr);
+                               }),
+                           a2s);
 }
 
 }  // namespace
@@ -465,17 +406,12 @@ extern "C" int flgp_dev_glgp_distances(void *stream, const double *dX, int n, in
                FLGP_SMAX, n);
   const int dpad = flgp_dev_anchor_dpad(d);
   FLGP_REQUIRE(d >= 1 && dpad > 0, "glgp_distances: kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
-  const int rows = flgp_dev_anchor_rows(n), nchunk = ceil_div(n, 64);
-  DevBuf Ut, uu, p1, xx, rsx, D0;
-  FLGP_TRY(Ut.alloc(sizeof(double) * (size_t)rows * dpad));
-  FLGP_TRY(uu.alloc(sizeof(double) * (size_t)rows));
-  FLGP_TRY(p1.alloc(sizeof(double) * (size_t)nchunk * n));
-  FLGP_TRY(xx.alloc(sizeof(double) * (size_t)n));
-  FLGP_TRY(rsx.alloc(sizeof(double) * (size_t)n));
+  NysScratch T;
+  DevBuf D0;
+  FLGP_TRY(T.alloc(n, dpad, true));
   FLGP_TRY(D0.alloc(sizeof(double) * (size_t)n * n));
-  FLGP_TRY(flgp_dev_anchor_prep(st, dX, n, ldx, d, Ut.as<double>(), uu.as<double>()));
-  FLGP_TRY(glgp_lists(st, dX, n, ldx, d, dpad, Ut.as<double>(), uu.as<double>(), D0.as<double>(), p1.as<double>(),
-                      xx.as<double>(), rsx.as<double>(), dDt, ldd));
+  FLGP_TRY(flgp_dev_anchor_prep(st, dX, n, ldx, d, T.Ut.as<double>(), T.uu.as<double>()));
+  FLGP_TRY(glgp_lists(st, dX, n, ldx, d, dpad, T, D0.as<double>(), dDt, ldd));
   FLGP_HIP(hipStreamSynchronize(st));
   return FLGP_OK;
 }

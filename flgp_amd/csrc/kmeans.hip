@@ -52,9 +52,6 @@ __global__ void km_gather_rows_kernel(const double *__restrict__ X, int ldx, int
 
 using namespace flgp;
 
-extern "C" int flgp_dev_anchor_dpad(int d);
-extern "C" int flgp_dev_anchor_rows(int s);
-extern "C" int flgp_dev_anchor_prep(void *stream, const double *dU, int s, int ldu, int d, double *dUt, double *duu);
 extern "C" int flgp_dev_knn(void *stream, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu,
                             int s, int r, int *d_idx, double *d_dist, int ldo);
 extern "C" size_t flgp_dev_csc_workspace(int n, int s, int r);

@@ -177,9 +177,6 @@ static inline double mb_uniform(unsigned long long seed, unsigned long long st, 
 
 using namespace flgp;
 
-extern "C" int flgp_dev_anchor_dpad(int d);
-extern "C" int flgp_dev_anchor_rows(int s);
-extern "C" int flgp_dev_anchor_prep(void *stream, const double *dU, int s, int ldu, int d, double *dUt, double *duu);
 extern "C" int flgp_dev_knn(void *stream, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu,
                             int s, int r, int *d_idx, double *d_dist, int ldo);
 extern "C" int flgp_dev_mean(void *stream, const double *d_x, long count, double *d_out, double *d_work);

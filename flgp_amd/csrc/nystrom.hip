@@ -13,8 +13,6 @@
 #include "common.h"
 #include <cmath>
 #include <memory>
-#include <string>
-#include <thread>
 
 namespace flgp {
 
@@ -304,8 +302,9 @@ static int launch_sim_grid(hipStream_t st, int dpad, const double *X, int nb, in
 // D(x, j) = fma(-2, dot, |u_x|^2) + |u_j|^2 of the points with themselves (s x s, ld s) and its row sums in rsx; p1 holds
 // ceil(s / 64) x s doubles, xx s (read for dpad > 64 only)
 int nys_self_distances(hipStream_t st, const double *dU, int s, int ldu, int d, int dpad, const double *Ut, const double *uu,
-                       double *D, double *p1, double *xx, double *rsx) {
+                       double *D, NysScratch &T) {
   const int nchunk = ceil_div(s, 64);
+  double *p1 = T.p1.as<double>(), *xx = T.xx.as<double>(), *rsx = T.rsx.as<double>();
   if (dpad > 64) {   // no register kernel beyond d = 64: dot products by the GEMM (one chain per element, the same bits)
     hipLaunchKernelGGL(nys_sqnorm_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, dU, s, ldu, d, xx);
     FLGP_TRY(check_launch("nys_sqnorm_kernel"));
@@ -337,6 +336,13 @@ void nys_first_scaling(hipStream_t st, double *W, int s, double *rs, bool have_s
 void nys_second_factor(hipStream_t st, const double *W, int s, double *sd) {
   nys_colsum(st, W, s, s, sd);
   hipLaunchKernelGGL(nys_vec_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, sd, s, 1);       // 1/sqrt(. + 1e-9)
+}
+// W is symmetric, so column sums are row sums
+void nys_normalised_w(hipStream_t st, const double *D, double *W, int s, double inv_c, double *rs, double *sd) {
+  nys_exp_from(st, D, W, (long)s * s, inv_c);
+  nys_first_scaling(st, W, s, rs);
+  nys_second_factor(st, W, s, sd);
+  nys_symscale(st, W, s, sd);
 }
 // V(j, k) <- sd[j] V(j, k) (s x K, ld s) and the column norms
 void nys_vector_norms(hipStream_t st, double *V, int s, int K, const double *sd, double *nrm) {
@@ -477,16 +483,18 @@ int nystrom_grid_extend_all(hipStream_t st, const flgp_nystrom_grid *G, const do
   return FLGP_OK;
 }
 
+int check_bandwidths(const char *who, const double *a2s, int l) {
+  for (int i = 0; i < l; ++i)
+    if (!(a2s[i] > 0.0) || !std::isfinite(a2s[i])) {
+      set_error("bandwidth %d (a2=%g): %s: a2 must be positive and finite", i, a2s[i], who);
+      return FLGP_ERR_INVALID;
+    }
+  return FLGP_OK;
+}
+
 }  // namespace flgp
 
 using namespace flgp;
-
-extern "C" int flgp_dev_anchor_dpad(int d);
-extern "C" int flgp_dev_anchor_rows(int s);
-extern "C" int flgp_dev_anchor_prep(void *stream, const double *dU, int s, int ldu, int d, double *dUt, double *duu);
-extern "C" size_t flgp_dev_eig_workspace(int s, int K);
-extern "C" int flgp_dev_eig_topk(void *stream, const double *dG, int ldg, int s, int K, double tol, double *d_values,
-                                 double *dV, int ldv, void *d_work, size_t work_bytes, int *info);
 
 namespace {
 
@@ -507,14 +515,9 @@ struct AnchorWorker {
 // norm sqrt(s) (:278-280) and the two diagonal factors of the extension folded in
 int anchor_side(hipStream_t st, flgp_nystrom_grid *G, int i, const double *D, AnchorWorker &A) {
   const int s = G->s, K = G->K;
-  const long ss = (long)s * s;
   double *W = A.W.as<double>(), *sd = A.sd.as<double>(), *nrm = A.nrm.as<double>();
   double *rsu = (double *)G->rsu_of(i), *values = (double *)G->values_of(i), *eigv = (double *)G->eigv_of(i);
-  // W is symmetric, so column sums are row sums
-  nys_exp_from(st, D, W, ss, G->inv_c[i]);
-  nys_first_scaling(st, W, s, rsu);
-  nys_second_factor(st, W, s, sd);
-  nys_symscale(st, W, s, sd);
+  nys_normalised_w(st, D, W, s, G->inv_c[i], rsu, sd);
   FLGP_TRY(check_launch("nystrom W_UU"));
   FLGP_TRY(flgp_dev_eig_topk(st, W, s, s, K, 0.0, values, eigv, s, A.work.p, A.wb, nullptr));
   nys_vector_norms(st, eigv, s, K, sd, nrm);
@@ -539,18 +542,14 @@ extern "C" int flgp_dev_nystrom_grid_create(void *stream, const double *dU, int 
   FLGP_REQUIRE(dpad > 0 && d >= 1, "nystrom: kernels are built for 1 <= d <= %d (got %d)", FLGP_DMAX, d);
   FLGP_REQUIRE(s >= 2 && K >= 1 && K <= s, "nystrom: need 1 <= K <= s, s >= 2 (K=%d, s=%d)", K, s);
   FLGP_REQUIRE(ldu >= s, "nystrom: leading dimensions too small");
-  for (int i = 0; i < l; ++i)
-    if (!(a2s[i] > 0.0) || !std::isfinite(a2s[i])) {
-      set_error("bandwidth %d (a2=%g): nystrom: a2 must be positive and finite", i, a2s[i]);
-      return FLGP_ERR_INVALID;
-    }
+  FLGP_TRY(check_bandwidths("nystrom", a2s, l));
   std::unique_ptr<flgp_nystrom_grid> G(new flgp_nystrom_grid());
   G->s = s; G->d = d; G->dpad = dpad; G->l = l; G->K = K;
   G->a2s.assign(a2s, a2s + l);
   FLGP_HIP(hipGetDevice(&G->device));
   const int rows = flgp_dev_anchor_rows(s);
-  const int nchunk = ceil_div(s, 64);
-  DevBuf D, p1, rsx, xx;
+  DevBuf D;
+  NysScratch T;
   FLGP_TRY(G->U.alloc(sizeof(double) * (size_t)s * d));
   FLGP_TRY(G->Ut.alloc(sizeof(double) * (size_t)rows * dpad));
   FLGP_TRY(G->uu.alloc(sizeof(double) * (size_t)rows));
@@ -559,17 +558,14 @@ extern "C" int flgp_dev_nystrom_grid_create(void *stream, const double *dU, int 
   FLGP_TRY(G->rsu.alloc(sizeof(double) * l * G->rs));
   FLGP_TRY(G->eigv.alloc(sizeof(double) * l * G->es));
   FLGP_TRY(D.alloc(sizeof(double) * (size_t)s * s));
-  FLGP_TRY(p1.alloc(sizeof(double) * (size_t)nchunk * s));
-  FLGP_TRY(rsx.alloc(sizeof(double) * (size_t)s));
-  FLGP_TRY(xx.alloc(sizeof(double) * (size_t)s));
+  FLGP_TRY(T.alloc(s, dpad, false));
   FLGP_HIP(hipMemcpy2DAsync(G->U.p, sizeof(double) * (size_t)s, dU, sizeof(double) * (size_t)ldu, sizeof(double) * (size_t)s, d,
                             hipMemcpyDeviceToDevice, st));
   FLGP_TRY(flgp_dev_anchor_prep(st, dU, s, ldu, d, G->Ut.as<double>(), G->uu.as<double>()));
   // ---- D_UU and its mean (src/Fit.cpp:244,248), once for the grid
-  FLGP_TRY(nys_self_distances(st, dU, s, ldu, d, dpad, G->Ut.as<double>(), G->uu.as<double>(), D.as<double>(), p1.as<double>(),
-                              xx.as<double>(), rsx.as<double>()));
+  FLGP_TRY(nys_self_distances(st, dU, s, ldu, d, dpad, G->Ut.as<double>(), G->uu.as<double>(), D.as<double>(), T));
   std::vector<double> hrow(s);
-  FLGP_HIP(hipMemcpyAsync(hrow.data(), rsx.p, sizeof(double) * s, hipMemcpyDeviceToHost, st));
+  FLGP_HIP(hipMemcpyAsync(hrow.data(), T.rsx.p,sizeof(double) * s, hipMemcpyDeviceToHost, st));
   FLGP_HIP(hipStreamSynchronize(st));
   double total = 0.0;
   for (int i = 0; i < s; ++i) total += hrow[i];
@@ -578,52 +574,16 @@ extern "C" int flgp_dev_nystrom_grid_create(void *stream, const double *dU, int 
   G->mean = mean;
   G->inv_c.resize(l);
   for (int i = 0; i < l; ++i) G->inv_c[i] = 1.0 / (a2s[i] * mean);
-  // ---- workers: at most max_parallel, at most l, and no more than fit into 90 % of the free memory
-  int workers = max_parallel < 1 ? 1 : max_parallel;
-  if (workers > l) workers = l;
-  if (workers > 1) {
-    size_t free_b = 0, total_b = 0;
-    FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-    const double per = 8.0 * s * (double)s + (double)flgp_dev_eig_workspace(s, K) + 8.0 * (s + K);
-    const double fit = 0.9 * (double)free_b / per;
-    if (fit < workers) workers = fit < 1.0 ? 1 : (int)fit;
-  }
-  G->workers = workers;
-  std::vector<int> rcs(l, FLGP_OK);
-  std::vector<std::string> msgs(l);
-  if (workers == 1) {      // in line, on the caller's stream
-    AnchorWorker A;
-    FLGP_TRY(A.alloc(s, K));
-    for (int i = 0; i < l; ++i) {
-      rcs[i] = anchor_side(st, G.get(), i, D.as<double>(), A);
-      if (rcs[i] != FLGP_OK) { msgs[i] = flgp_last_error(); break; }
-    }
-  } else {                 // one host thread and one stream per worker; worker w takes bandwidths w, w + workers, ...
-    const int dev = G->device;
-    flgp_nystrom_grid *Gp = G.get();
-    const double *Dp = D.as<double>();
-    auto run = [&, Gp, Dp, dev](int w) {
-      auto body = [&]() -> int {
-        FLGP_HIP(hipSetDevice(dev));
-        Stream ws;
-        FLGP_TRY(ws.create());
-        AnchorWorker A;
-        FLGP_TRY(A.alloc(s, K));
-        for (int i = w; i < l; i += workers) {
-          rcs[i] = anchor_side(ws.s, Gp, i, Dp, A);
-          if (rcs[i] != FLGP_OK) { msgs[i] = flgp_last_error(); return FLGP_OK; }
-        }
-        return FLGP_OK;
-      };
-      const int rc = body();
-      if (rc != FLGP_OK && rcs[w] == FLGP_OK) { rcs[w] = rc; msgs[w] = flgp_last_error(); }
-    };
-    std::vector<std::thread> th;
-    for (int w = 0; w < workers; ++w) th.emplace_back(run, w);
-    for (auto &t : th) t.join();
-  }
-  for (int i = 0; i < l; ++i)
-    if (rcs[i] != FLGP_OK) { set_error("bandwidth %d (a2=%g): %s", i, a2s[i], msgs[i].c_str()); return rcs[i]; }
+  // ---- workers: at most max_parallel, at most l, and no more than fit into 90 % of the free memory (worker_pool.h)
+  DevicePool pool;
+  FLGP_TRY(pool.plan(max_parallel, l, 8.0 * s * (double)s + (double)flgp_dev_eig_workspace(s, K) + 8.0 * (s + K)));
+  G->workers = pool.workers;
+  flgp_nystrom_grid *Gp = G.get();
+  const double *Dp = D.as<double>();
+  FLGP_TRY(bandwidth_failure(pool.run<AnchorWorker>(
+                                 st, l, [&](AnchorWorker &A) { return A.alloc(s, K); },
+                                 [&](hipStream_t ws, AnchorWorker &A, int i) { return anchor_side(ws, Gp, i, Dp, A); }),
+                             a2s));
   *out = G.release();
   return FLGP_OK;
 }

@@ -1271,6 +1271,47 @@ def test_se_grid_names_the_bandwidth_it_refuses():
     assert "bandwidth 0" in e.value.message and "null space" in e.value.message, e.value.message
 
 
+def test_se_grid_names_the_lowest_refused_bandwidth_whatever_the_workers():
+    """The same far anchor under three bandwidths, each of which the spectrum step refuses: with one worker (in line), two
+    and three the call raises the same message, that of bandwidth 0 -- a worker stops at its first refusal, and the lowest
+    refused bandwidth is always among those that ran."""
+    n, d, s, r, m = 600, 3, 40, 3, 50
+    X, U0, U = make_case(n, d, s, r, seed=31)
+    U = U.copy(); U[7, :d] = 1e6
+    messages = []
+    for max_parallel in (1, 2, 3):
+        with pytest.raises(api.FlgpError) as e:
+            api.se_spectrum_grid(X[:m], X[m:], s, r, K=s, a2s=np.array([0.5, 1.0, 2.0]), models=dict(gl="rw"), U=U,
+                                 max_parallel=max_parallel)
+        assert "bandwidth 0" in e.value.message and "null space" in e.value.message, (max_parallel, e.value.message)
+        messages.append(e.value.message)
+    assert messages[0] == messages[1] == messages[2], messages
+
+
+def test_se_grid_refuses_one_bandwidth_among_four(oracle):
+    """Only some bandwidths refused: anchor 7 sits outside the cloud where one point alone lists it, as its third
+    neighbour at 3.75 mean distances.  At a2 = 0.01 that weight is exp(-375) of its row and the anchor's column of Z is
+    numerically empty; at a2 = 0.5, 1, 2 it is not.  The oracle says so first (sigma_40^2 / sigma_1^2 is 1.4e-38 against
+    0.031 .. 0.040; the floor of the full decomposition is 1e-13), then the grid must name bandwidth 1 -- run by worker 0
+    in line, by worker 1 of two and of four -- with one message."""
+    n, d, s, r, m = 600, 3, 40, 3, 50
+    X, U0, U = make_case(n, d, s, r, seed=31)
+    U = U.copy(); U[7, :d] = (-5.08, 0.82, 11.86)
+    a2s = np.array([1.0, 0.01, 0.5, 2.0])
+    ref, _ = oracle.se_spectrum_grid(X, U, r, s, a2s, gl="rw", root=False)
+    ratios = [float(v[-1] / v[0]) for v, _ in ref]
+    assert ratios[1] < 1e-19 and min(ratios[0], ratios[2], ratios[3]) > 1e-3, ratios
+    grid = dict(models=dict(gl="rw"), U=U)
+    assert len(api.se_spectrum_grid(X[:m], X[m:], s, r, K=s, a2s=a2s[[0, 2, 3]], max_parallel=3, **grid)[0]) == 3    # the others pass
+    messages = []
+    for max_parallel in (1, 2, 4):
+        with pytest.raises(api.FlgpError) as e:
+            api.se_spectrum_grid(X[:m], X[m:], s, r, K=s, a2s=a2s, max_parallel=max_parallel, **grid)
+        assert "bandwidth 1 " in e.value.message and "null space" in e.value.message, (max_parallel, e.value.message)
+        messages.append(e.value.message)
+    assert messages[0] == messages[1] == messages[2], messages
+
+
 def test_unusable_spectrum_is_refused_on_every_path(stages):
     """sigma_K = 0 (K reaches into the null space: here K == s with an anchor that no point chose, and an SE bandwidth
     far below the neighbour distances) has no left vectors on the Gram route.  Every path that goes from the

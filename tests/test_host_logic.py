@@ -77,3 +77,16 @@ def test_bounded_host_wait(tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", src, "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "host_wait ok" in out.stdout, out.stdout
+
+
+def test_worker_pool(tmp_path):
+    """The bandwidth grids and the one-vs-rest classes deal their items to workers through csrc/worker_pool.h: the
+    worker-count rule, item i on worker i mod workers, a worker stopping at its first failure, the lowest failing item
+    reported with the text of the thread that failed, a single worker on the calling thread.  Generic over the device
+    operations and exercised here with plain callables."""
+    import subprocess
+    src = os.path.join(os.path.dirname(__file__), "c", "worker_pool_check.cc")
+    exe = str(tmp_path / "worker_pool_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", src, "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "worker_pool ok" in out.stdout, out.stdout
