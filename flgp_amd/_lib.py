@@ -70,6 +70,8 @@ _SIGNATURES = {
                                                               P]),
     "flgp_eigenpair_logit_objective": (c_int, [P, c_int, P, c_int, P, P, c_double, c_char_p, P, c_double, c_double, c_int, P,
                                                P]),
+    "flgp_eigenpair_logit_objective_batch": (c_int, [P, c_int, P, c_int, P, c_int, P, P, P, c_int, c_double, c_char_p, P,
+                                                     c_double, c_int, c_int, P, P]),
     "flgp_eigenpair_regression_objective": (c_int, [P, c_int, P, c_int, P, c_int, c_double, c_char_p, c_char_p, P, P, c_int,
                                                     P, P]),
     "flgp_pg_draw": (c_int, [P, P, c_int, ctypes.c_ulonglong, P]),

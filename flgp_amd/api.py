@@ -538,6 +538,74 @@ class ResidentEigenPair:
                                                         ctypes.byref(value), ctypes.byref(it)))
         return (value.value, it.value) if return_iters else value.value
 
+    def logit_objective_batch(self, ts, K, idx, Y, col=None, N=None, sigma=1e-3, approach="posterior", prior=None, tol=1e-5,
+                              max_iter=100, max_parallel=0, return_iters=False):
+        """``logit_objective`` for B problems in one call (flgp_eigenpair_logit_objective_batch, include/flgp_hip.h):
+        problem b is column ``col[b]`` of ``Y`` (m, or m x ncol; ``col`` None needs ncol == B and means 0 .. B-1) at
+        ``ts[b]``; everything else is shared.  Each value (and iteration count) is, bit for bit, ``logit_objective`` on
+        that column at that t, whatever else shares the call.  For m > K the B low-rank Newton loops advance in the same
+        launches, ``max_parallel`` problems per chunk (0: as many as fit the device memory); for m <= K it is the number
+        of host workers the dense loops are dealt to.  A bad ``col[b]`` or ``ts[b]`` is refused here, before the
+        library is called, with the library's own text.  Returns the B values, or ``(values, iters)``."""
+        who = "logit_objective_batch"
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        m = idx.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        ncol = Y.shape[1]
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        B = ts.size
+        if col is None and ncol != B:
+            raise FlgpError(-1, f"{who}: col may be NULL only if ncol == B (ncol={ncol}, B={B})")
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per value of t")
+        for b in range(B):
+            c = b if cols is None else int(cols[b])
+            head = "problem %d (t=%g): %s: " % (b, ts[b], who)
+            if not 0 <= c < ncol:
+                raise FlgpError(-1, head + "col=%d is outside [0, ncol=%d)" % (c, ncol))
+            if not np.isfinite(ts[b]):
+                raise FlgpError(-1, head + "t must be finite")
+            if approach == "posterior" and not ts[b] > 0.0:
+                raise FlgpError(-1, head + 't must be positive under "posterior"')
+        N = None if N is None else np.ascontiguousarray(np.broadcast_to(np.asarray(N, dtype=np.float64), (m,)))
+        pr = None if prior is None else np.ascontiguousarray(np.asarray(prior, dtype=np.float64).reshape(-1))
+        if pr is not None and pr.size != 3:
+            raise ValueError("prior must hold (p, q, tau)")
+        values = np.zeros(max(B, 1)); its = np.zeros(max(B, 1), dtype=np.int32)
+        check(_lib.lib().flgp_eigenpair_logit_objective_batch(self._h, int(K), _ptr(idx), m, _ptr(Y), ncol, _ptr(N), _ptr(cols),
+                                                              _ptr(ts), B, float(sigma), _b(approach), _ptr(pr), float(tol),
+                                                              int(max_iter), int(max_parallel), _ptr(values), _ptr(its)))
+        values = values[:B].copy(); its = its[:B].copy()
+        return (values, its) if return_iters else values
+
+    def logit_objective_multiclass(self, ts, K, idx, labels, sigma=1e-3, approach="posterior", prior=None, tol=1e-5,
+                                   max_iter=100, max_parallel=0, return_iters=False):
+        """One step of train_logit_mult_gp_cpp's J one-vs-rest searches (src/MultiClassification.cpp:29-53) in one call:
+        ``labels`` holds integers 0 .. J-1 (max + 1 == J, as the multiclass posterior asks), class j's response is the
+        indicator column ``labels == j`` of ``multi_train_split`` with one trial per row.  ``ts``: J values (class j at
+        ``ts[j]``) or a J x T array (a T-point profile per class, B = J T problems).  Returns an array of ``ts``'s shape
+        whose entries are ``logit_objective`` on the class's column, bit for bit; with ``return_iters`` also the
+        iteration counts in that shape."""
+        lab = np.asarray(labels, dtype=np.float64).reshape(-1)
+        if lab.size == 0 or not np.isfinite(lab).all() or (lab != np.floor(lab)).any() or (lab < 0).any():
+            raise ValueError("labels must be class labels 0 .. J-1")
+        aug_y = multi_train_split(lab)
+        J = aug_y.shape[1]
+        ts = np.asarray(ts, dtype=np.float64)
+        if ts.ndim not in (1, 2) or ts.shape[0] != J:
+            raise ValueError(f"need one t (or one row of t) per class: {J} classes, ts of shape {ts.shape}")
+        T = 1 if ts.ndim == 1 else ts.shape[1]
+        col = np.repeat(np.arange(J, dtype=np.int32), T)             # problem j T + k: class j at ts[j, k]
+        values, its = self.logit_objective_batch(ts.reshape(-1), K, idx, aug_y, col=col, sigma=sigma, approach=approach,
+                                                 prior=prior, tol=tol, max_iter=max_iter, max_parallel=max_parallel,
+                                                 return_iters=True)
+        values = values.reshape(ts.shape); its = its.reshape(ts.shape)
+        return (values, its) if return_iters else values
+
     def regression_objective(self, x, K, idx, Y, sigma=1e-5, noise="same", approach="posterior", prior=None, grad=True):
         """The objective train_regression_gp_cpp minimises (src/train.cpp:333-555) and its gradient, on the resident pair:
         ``x = (t, noise)`` for noise = "same", ``(t, noise_1, ..., noise_m)`` for "different"; approach "marginal" (the

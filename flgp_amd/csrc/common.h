@@ -185,7 +185,8 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
                 const double *E2, struct GemmFusedReduce *fused = nullptr,
-                const struct GemmPair *pair = nullptr, int force_split = 0, int *planes_out = nullptr);
+                const struct GemmPair *pair = nullptr, int force_split = 0, int *planes_out = nullptr,
+                const struct GemmBatch *batch = nullptr);
 // The number of split-K planes gemm_launch chooses for this shape and workspace.  `force_split` > 0 makes a launch take
 // that number instead (the workspace must hold it): a row block of a product then adds every element's terms in the
 // order the whole product does, whatever the block's own tile count would have chosen.  `planes_out` (optional) receives the
@@ -194,6 +195,13 @@ int gemm_plan_split(int M, int N, int Kd, size_t work_elems);
 // `pair`: a second product C2 = alpha A2 B2 of the same shape and strides in the same launch (no E / E2, never split):
 // two of the solver's s x b rotations fill the chip where one leaves its fixed costs exposed.
 struct GemmPair { const double *A2, *B2; double *C2; };
+// `batch`: `count` products of this shape and these element strides in one launch (and one reduction launch when split).
+// Problem q reads the device int slots[q] and takes A + slot a_bs, B + slot b_bs, C + slot c_bs, E + slot e_bs and its
+// split-K planes at work + slot part_bs (work_elems: the planes of ONE problem); a stride of 0 shares the operand.  No pair,
+// E2 or fused reduction.  The tiles, the k ranges and the reduction order of a problem are those of a launch of that
+// problem alone with the same split, so with force_split = that launch's gemm_plan_split every problem keeps its bits.
+constexpr int GEMM_BATCH_MAX = 32768;     // (the reduction kernel carries the problem in gridDim.y)
+struct GemmBatch { int count; const int *slots; long a_bs, b_bs, c_bs, e_bs, part_bs; };
 int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, double *C, GemmFusedReduce *fused);
 // The eigensolver's b x b Gram product out = Xa^T Xb (Xa, Xb: s x b column-major) on its own kernel (rot.hip): split over the
 // rows, planes reduced by gemm.hip's reduction kernels (with the fused extras).  false: not this shape, nothing was launched.
@@ -287,6 +295,40 @@ int gpc_lr_a(hipStream_t st, const double *d_b, const double *d_sW, const double
              int m, double *d_a);
 int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const double *d_Y, const double *d_N, const double *d_D,
                 const double *d_LQ, int K, int m, double *d_out);
+// The low-rank loop for a chunk of independent problems in the same launches (gpc.hip, the loop itself in
+// eigenpair.hip).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
+// of A slot numbers (the problems still iterating) and carry its index in the grid, so a step is one launch whatever A is
+// and a slot that left the list is not written again.  The strides are doubles between two slots; Y, N, V1 are shared.
+struct LrChunk {
+  int m, K, slots;
+  long sv, sk, sx, sq;                                          // of the m-vectors, the K-vectors, X (m x K) and Q (K x K)
+  double *f, *fnew, *sW, *b, *a, *D, *dh, *xs, *c, *g, *Xv;    // m each
+  double *u, *l, *ls;                                           // K each; l and ls are the slot's spectrum weights
+  double *X, *Q;                                                // Q holds the factor L_Q after lrb_chol
+  const double *Y; long ldy; const int *ycol;                   // slot s's responses: Y + ycol[s] ldy (ycol on the device)
+  const double *N, *V1; long ld1;
+  double sigma;
+  int *flag;                                                    // one pivot flag per slot (chol_blocked's)
+  double *amll;                                                 // one result per slot
+};
+// lrb_weights: gpr_weights for slot s at d_ts[s], s < slots.  lrb_w .. lrb_a: gpc_weights, gpc_lr_dvec, gpc_scale2 (X),
+// gpr_add_diag (Q, 1), pg_mul (two factors), pg_axpy3 (x + c z) and gpc_lr_a on the listed slots (lrb_mul / lrb_axpy: n
+// elements, a stride per operand, 0 = shared).  lrb_step: gpc_step per listed problem, d_stat[q] = the norm of act[q] and
+// ((int *)(d_stat + A))[q] = its pivot flag: 12 A bytes for the host.  lrb_chol: chol_blocked of every listed Q; lrb_trsv:
+// u <- Q^-1 u per listed slot; lrb_amll: gpc_lr_amll of every slot of the chunk into amll[slot].
+int lrb_weights(hipStream_t st, const double *d_values, int K, const double *d_ts, int slots, long sk, double *d_ls, double *d_l);
+int lrb_w(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_d(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_scale2(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_add_diag(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_mul(hipStream_t st, int n, const double *a, long sa, const double *x, long sx, double *out, long so, const int *act, int A);
+int lrb_axpy(hipStream_t st, int n, const double *x, long sx, double c, const double *z, long sz, double *out, long so,
+             const int *act, int A);
+int lrb_a(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_step(hipStream_t st, const LrChunk &c, const int *act, int A, double *d_stat);
+int lrb_chol(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_trsv(hipStream_t st, const LrChunk &c, const int *act, int A);
+int lrb_amll(hipStream_t st, const LrChunk &c);
 // The weight-space Newton loop's elementwise steps and the predictive rows of the logit posterior for m > K (gpc.hip; the
 // loop is in eigenpair.hip).  gpc_ws_bd: out = b / D; gpc_ws_fnew: f_new = p + sigma (b - sW^2 p) / D.
 // gpc_predict_rows: mean_i = u^T v_i and cov_i = c + |G v_i|^2 for the mnew rows v_i = V(rows_i, 0:K) of the pair, read in

@@ -2,7 +2,8 @@
 // regression prediction, posterior variance and the training objectives with their gradients (kernels in
 // gpr.hip and gpr_grad.hip; the drivers' whole testing step in one call, in weight space for m > K: DESIGN 8 f-13); the
 // Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
-// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12);
+// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12; the
+// training objective for B problems in one call: f-15);
 // Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
 // the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
@@ -759,6 +760,249 @@ extern "C" int flgp_eigenpair_logit_objective(const flgp_eigenpair *ep, int K, c
     *value = -amll + p;
   } else {
     *value = -amll;
+  }
+  return FLGP_OK;
+}
+
+// ---- the logit training objective for B problems in one call ---------------------------------------------
+namespace {
+inline long pad32(long n) { return (n + 31) / 32 * 32; }     // a slot starts 256-byte aligned, like an allocation of its own
+
+// GpcLowRank for a chunk of problems (m > K): slot s of every buffer belongs to problem p0 + s for the whole chunk, the
+// device list `act` names the slots still iterating and every step of an iteration is one launch over that list
+// (gpc.hip, LrChunk).  The split products take, per problem, the plan the single call takes (planQ for Q = X^T X, planU
+// for the two K x 1 products) on planes of the slot's own.
+struct LrBatch {
+  LrChunk C;
+  DevBuf vec, kv, X, Q, part, stat, flag, amll, act;
+  int planQ = 1, planU = 1;
+  size_t pe = 0;                 // doubles of one slot's planes
+  long sp = 0;
+
+  static void plans(int m, int K, int *planQ, int *planU, size_t *pe) {
+    const size_t we = vt_work_elems(K, 1);
+    *planQ = gemm_plan_split(K, K, m, we);
+    *planU = gemm_plan_split(K, 1, m, we);
+    *pe = std::max((size_t)*planQ * K * K, (size_t)*planU * K);
+  }
+  // device bytes of one problem: X, Q, eleven m-vectors, u, l, ls, its planes and its scalars
+  static double bytes(int m, int K) {
+    int a, b;
+    size_t pe;
+    plans(m, K, &a, &b, &pe);
+    return 8.0 * ((double)pad32((long)m * K) + pad32((long)K * K) + 11.0 * pad32(m) + 3.0 * pad32(K) + pad32((long)pe)) + 32.0;
+  }
+  int alloc(int m, int K, int slots) {
+    C.m = m; C.K = K; C.slots = slots;
+    C.sv = pad32(m); C.sk = pad32(K); C.sx = pad32((long)m * K); C.sq = pad32((long)K * K);
+    plans(m, K, &planQ, &planU, &pe);
+    sp = pad32((long)pe);
+    const size_t S = (size_t)slots;
+    FLGP_TRY(vec.alloc(sizeof(double) * 11 * S * C.sv)); FLGP_TRY(kv.alloc(sizeof(double) * 3 * S * C.sk));
+    FLGP_TRY(X.alloc(sizeof(double) * S * C.sx)); FLGP_TRY(Q.alloc(sizeof(double) * S * C.sq));
+    FLGP_TRY(part.alloc(sizeof(double) * S * sp)); FLGP_TRY(stat.alloc(12 * S));
+    FLGP_TRY(flag.alloc(sizeof(int) * S)); FLGP_TRY(amll.alloc(sizeof(double) * S)); FLGP_TRY(act.alloc(sizeof(int) * S));
+    double *v = vec.as<double>(), *k = kv.as<double>();
+    const size_t vs = S * C.sv, ks = S * C.sk;
+    C.f = v; C.fnew = v + vs; C.sW = v + 2 * vs; C.b = v + 3 * vs; C.a = v + 4 * vs; C.D = v + 5 * vs; C.dh = v + 6 * vs;
+    C.xs = v + 7 * vs; C.c = v + 8 * vs; C.g = v + 9 * vs; C.Xv = v + 10 * vs;
+    C.u = k; C.l = k + ks; C.ls = k + 2 * ks;
+    C.X = X.as<double>(); C.Q = Q.as<double>(); C.flag = flag.as<int>(); C.amll = amll.as<double>();
+    return FLGP_OK;
+  }
+  // C (M x 1) = A^T B or A B per listed slot, as gemm_tn / gemm_nn on the slot's operands (a stride of 0: the shared V1)
+  int tn(hipStream_t st, int A, const double *Am, long lda, long a_bs, const double *x, double *out) {
+    const GemmBatch gb{A, act.as<int>(), a_bs, C.sv, C.sk, 0, sp};
+    return gemm_launch(st, C.K, 1, C.m, 1.0, Am, lda, 1, x, 1, C.m, 0.0, nullptr, 0, 0, out, 1, C.K, part.as<double>(), pe, 0.0,
+                       nullptr, nullptr, nullptr, planU, nullptr, &gb);
+  }
+  int nn(hipStream_t st, int A, const double *Am, long lda, long a_bs, const double *u, double *out) {
+    const GemmBatch gb{A, act.as<int>(), a_bs, C.sk, C.sv, 0, 0};
+    return gemm_launch(st, C.m, 1, C.K, 1.0, Am, 1, lda, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, C.m, nullptr, 0, 0.0, nullptr,
+                       nullptr, nullptr, 0, nullptr, &gb);
+  }
+  // out = C x   (GpcLowRank::cmul; Xv is the scratch)
+  int cmul(hipStream_t st, int A, const double *x, double *out) {
+    const int *a = act.as<int>();
+    FLGP_TRY(tn(st, A, C.V1, C.ld1, 0, x, C.u));
+    FLGP_TRY(lrb_mul(st, C.K, C.l, C.sk, C.u, C.sk, C.u, C.sk, a, A));
+    FLGP_TRY(nn(st, A, C.V1, C.ld1, 0, C.u, C.Xv));
+    return lrb_axpy(st, C.m, C.Xv, C.sv, C.sigma, x, C.sv, out, C.sv, a, A);
+  }
+  // GpcLowRank::iteration for the A listed slots: its launches in its order, each once
+  int iteration(hipStream_t st, int A) {
+    ProfScope ps("logit_lr_batch_iter", st, 0.0);
+    const int *a = act.as<int>();
+    FLGP_TRY(lrb_w(st, C, a, A));
+    FLGP_TRY(lrb_d(st, C, a, A));
+    FLGP_TRY(lrb_scale2(st, C, a, A));                                                        // LowRankB::factor
+    {
+      const GemmBatch gb{A, a, C.sx, C.sx, C.sq, 0, sp};
+      FLGP_TRY(gemm_launch(st, C.K, C.K, C.m, 1.0, C.X, C.m, 1, C.X, 1, C.m, 0.0, nullptr, 0, 0, C.Q, 1, C.K, part.as<double>(), pe,
+                           0.0, nullptr, nullptr, nullptr, planQ, nullptr, &gb));
+    }
+    FLGP_TRY(lrb_add_diag(st, C, a, A));
+    FLGP_TRY(lrb_chol(st, C, a, A));
+    FLGP_TRY(cmul(st, A, C.b, C.c));                                                          // c = C b
+    FLGP_TRY(lrb_mul(st, C.m, C.xs, C.sv, C.c, C.sv, C.g, C.sv, a, A));                       // g = D^-1/2 sW c
+    FLGP_TRY(tn(st, A, C.X, C.m, C.sx, C.g, C.u));                                            // LowRankB::apply
+    FLGP_TRY(lrb_trsv(st, C, a, A));
+    FLGP_TRY(nn(st, A, C.X, C.m, C.sx, C.u, C.Xv));
+    FLGP_TRY(lrb_a(st, C, a, A));
+    FLGP_TRY(cmul(st, A, C.a, C.fnew));                                                       // f_new = C a
+    return lrb_step(st, C, a, A, stat.as<double>());
+  }
+};
+
+struct BatchFailure { int problem = -1, bad = 0, iter = 0; };
+
+// The chunk [p0, p0 + S) from f = 0: after every iteration the host reads the A norms and the A flags (12 A bytes), notes
+// the iteration count of every listed problem and takes the converged ones (and the failed ones) off the list, which is
+// where GpcLowRank::run stops for them.  amll_h / its: the S results.
+int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+                   int p0, double *amll_h, int *its, BatchFailure &fail) {
+  LrChunk &C = L.C;
+  C.slots = S;
+  FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
+  FLGP_HIP(hipMemsetAsync(C.f, 0, sizeof(double) * (size_t)S * C.sv, st));
+  FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
+  std::vector<int> act((size_t)S), next;
+  for (int s = 0; s < S; ++s) act[(size_t)s] = s;
+  std::vector<double> stat((size_t)S * 2);       // 12 A bytes are read into it: A doubles, then A ints
+  bool changed = true;
+  for (int it = 0; it < max_iter && !act.empty(); ++it) {
+    const int A = (int)act.size();
+    if (changed) FLGP_TRY(h2d(L.act.p, act.data(), sizeof(int) * (size_t)A, st));
+    FLGP_TRY(L.iteration(st, A));
+    FLGP_TRY(d2h(stat.data(), L.stat.p, (size_t)12 * A, st));
+    FLGP_HIP(hipStreamSynchronize(st));
+    const int *bad = (const int *)(stat.data() + A);
+    next.clear();
+    for (int q = 0; q < A; ++q) {
+      const int s = act[(size_t)q];
+      its[s] = it + 1;
+      if (bad[q]) {
+        if (fail.problem < 0 || p0 + s < fail.problem) { fail.problem = p0 + s; fail.bad = bad[q]; fail.iter = it + 1; }
+      } else if (!(stat[(size_t)q] < tol)) {
+        next.push_back(s);
+      }
+    }
+    changed = next.size() != act.size();
+    act.swap(next);
+  }
+  FLGP_TRY(lrb_amll(st, C));
+  FLGP_TRY(d2h(amll_h, C.amll, sizeof(double) * (size_t)S, st));
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
+}
+
+// what a worker of the dense route (m <= K) owns: its C, the contraction's workspace and the loop's state
+struct DenseObjWorker {
+  DevBuf C, work;
+  GpcNewton S;
+  int alloc(int m, int K) {
+    FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
+    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
+    return S.alloc(m);
+  }
+  static double bytes(int m, int K) { return 8.0 * (2.0 * m * m + 8.0 * m) + (double)flgp_dev_hk_workspace(m, m, K, 1); }
+};
+}  // namespace
+
+extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y,
+                                                    int ncol, const double *N, const int *col, const double *ts, int B,
+                                                    double sigma, const char *approach, const double *prior, double tol,
+                                                    int max_iter, int max_parallel, double *values, int *iters) {
+  const char *who = "logit_objective_batch";
+  FLGP_REQUIRE(approach, "%s: null pointer", who);
+  const bool posterior = std::strcmp(approach, "posterior") == 0;
+  if (!posterior && std::strcmp(approach, "marginal") != 0) {
+    set_error("This model selection approach is not supported!");
+    return FLGP_ERR_UNSUPPORTED;
+  }
+  FLGP_REQUIRE(ep && idx && Y && ts && values, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1 && B >= 1 && ncol >= 1,
+               "%s: bad shape (K=%d of %d, m=%d, max_iter=%d, B=%d, ncol=%d)", who, K, ep->K, m, max_iter, B, ncol);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  for (int b = 0; b < B; ++b) {
+    const int c = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "problem %d (t=%g): %s: col=%d is outside [0, ncol=%d)", b, ts[b], who, c, ncol);
+    FLGP_REQUIRE(std::isfinite(ts[b]), "problem %d (t=%g): %s: t must be finite", b, ts[b], who);
+    FLGP_REQUIRE(!posterior || ts[b] > 0.0, "problem %d (t=%g): %s: t must be positive under \"posterior\"", b, ts[b], who);
+  }
+  FLGP_REQUIRE(sigma >= 0.0 && std::isfinite(sigma), "%s: sigma=%g must be finite and >= 0", who, sigma);
+  const double dflt[3] = {1e-2, 10.0, 2.0};                     // PostOFData (src/train.h:138-140)
+  double pr[3];
+  for (int k = 0; k < 3; ++k) pr[k] = prior ? prior[k] : dflt[k];
+  FLGP_REQUIRE(all_finite(pr, 3), "%s: prior (p, q, tau) must be finite", who);
+  Rows r;
+  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
+  for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, N, m, who));
+  std::vector<double> ones;
+  if (!N) { ones.assign((size_t)m, 1.0); N = ones.data(); }
+  std::vector<int> cols((size_t)B);
+  for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
+  auto name_failure = [&](int b, const std::string &msg) { set_error("problem %d (t=%g): %s", b, ts[b], msg.c_str()); };
+
+  Stream st;
+  FLGP_TRY(st.create());
+  // up once: the rows, Y, N and, for the batched loop, the problems' columns and values of t
+  DevBuf dY, dN;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * ncol, st.s));
+  FLGP_TRY(upload(dN, N, sizeof(double) * (size_t)m, st.s));
+  std::vector<double> amll((size_t)B, 0.0);
+  std::vector<int> its((size_t)B, 0);
+  if (m <= K) {
+    // the single entry's dense loop per problem, the problems dealt to the pool's workers (worker_pool.h)
+    FLGP_TRY(r.resolve(st.s));
+    FLGP_HIP(hipStreamSynchronize(st.s));
+    DevicePool pool;
+    FLGP_TRY(pool.plan(max_parallel, B, DenseObjWorker::bytes(m, K)));
+    const PoolFailure bad = pool.run<DenseObjWorker>(
+        st.s, B, [&](DenseObjWorker &W) { return W.alloc(m, K); },
+        [&](hipStream_t ws, DenseObjWorker &W, int b) -> int {
+          const double *y = dY.as<double>() + (size_t)cols[(size_t)b] * m;
+          FLGP_TRY(hk(ws, ep, K, ts[b], r, r, W.C.as<double>(), W.work.as<double>()));      // C = HK(idx, idx) + sigma I
+          if (sigma != 0.0) FLGP_TRY(gpr_add_diag(ws, W.C.as<double>(), m, sigma));
+          FLGP_TRY(W.S.run(ws, W.C.as<double>(), y, dN.as<double>(), tol, max_iter, who, &its[(size_t)b]));
+          return W.S.amll(ws, y, dN.as<double>(), &amll[(size_t)b]);
+        });
+    if (bad.item >= 0) { name_failure(bad.item, bad.message); return bad.status; }
+  } else {
+    FLGP_TRY(r.gather(st.s, ep, K));
+    DevBuf dcol, dts;
+    FLGP_TRY(upload(dcol, cols.data(), sizeof(int) * (size_t)B, st.s));
+    FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st.s));
+    // the chunk: max_parallel problems, or (<= 0) all of them; either way no more than fit into 90 % of the free memory
+    size_t free_b = 0, total_b = 0;
+    FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+    int chunk = plan_workers(max_parallel > 0 ? max_parallel : B, B, (double)free_b, LrBatch::bytes(m, K));
+    chunk = std::min(chunk, GEMM_BATCH_MAX);
+    LrBatch L;
+    FLGP_TRY(L.alloc(m, K, chunk));
+    L.C.Y = dY.as<double>(); L.C.ldy = m; L.C.N = dN.as<double>();
+    L.C.V1 = r.V; L.C.ld1 = r.ld; L.C.sigma = sigma;
+    for (int p0 = 0; p0 < B; p0 += chunk) {
+      const int S = std::min(chunk, B - p0);
+      L.C.ycol = dcol.as<int>() + p0;
+      BatchFailure fail;
+      FLGP_TRY(lr_batch_chunk(st.s, L, ep, dts.as<double>() + p0, S, tol, max_iter, p0, amll.data() + p0, its.data() + p0, fail));
+      if (fail.problem >= 0) {
+        const int rc = GpcNewton::pivot_error(fail.bad, who, fail.iter);
+        name_failure(fail.problem, std::string(flgp_last_error()));
+        return rc;
+      }
+    }
+  }
+  for (int b = 0; b < B; ++b) {
+    const double t = ts[b];
+    if (posterior) {
+      const double p = pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]);   // src/train.cpp:17-24
+      values[b] = -amll[(size_t)b] + p;
+    } else {
+      values[b] = -amll[(size_t)b];
+    }
+    if (iters) iters[b] = its[(size_t)b];
   }
   return FLGP_OK;
 }

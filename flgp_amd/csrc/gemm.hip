@@ -47,6 +47,10 @@ struct GemmArgs {
   // a second product of the same shape in the same launch (gridDim.y = 2): its own operands and result, everything else shared
   const double *A2, *B2;
   double *C2;
+  // a batch of products of the same shape and strides in the same launch (gemm_f64_kernel<., true>): problem q of nbatch takes
+  // the tiles [q ntiles, (q + 1) ntiles) of gridDim.x and the operands at slot bslots[q] times the strides below
+  const int *bslots;
+  long a_bs, b_bs, c_bs, e_bs, part_bs;
 };
 
 // ---- operand staging: a 128(rows) x 16(k) tile goes global -> 8 registers per thread -> LDS [k][row].
@@ -259,7 +263,7 @@ __device__ __forceinline__ void fast_store(const double (&reg)[GBT / 16], double
 // GBT = 128: the tile of the large shapes.  GBT = 64 (each wave a 32 x 32 sub-tile, 2 x 2 MFMA tiles): the solver's
 // s x b and b x b products, which have 80 and 4 tiles of 128 -- a quarter of the chip, or split-K planes and a reduction
 // launch to make up for it -- and 316 / 16 tiles of 64.
-template <int GBT>
+template <int GBT, bool BATCH>
 __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
   constexpr int GB = GBT, GLD = gld_of(GBT), MI = GBT / 32, NR = GBT / 16;
   // two LDS stages: the tile of stage s+1 is written while stage s is being multiplied, one barrier per stage
@@ -273,8 +277,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
   const int ntm = (g.M + GB - 1) / GB, ntn = (g.N + GB - 1) / GB;
   const int nt = ntm * ntn;
   int bid = blockIdx.x;
-  const double *gA = g.A, *gB = g.B;
-  double *gC = g.C;
+  const double *gA = g.A, *gB = g.B, *gE = g.E;
+  double *gC = g.C, *gP = g.part;
+  if constexpr (BATCH) {   // the problem's own operands; its tiles in the order a launch of this problem alone walks them
+    const int q = bid / nt;
+    bid -= q * nt;
+    const long slot = g.bslots[q];
+    gA += slot * g.a_bs; gB += slot * g.b_bs; gC += slot * g.c_bs; gP += slot * g.part_bs;
+    if (gE) gE += slot * g.e_bs;
+  }
   if (gridDim.y > 1) {   // two products: the bands run over both tile sets (workgroups go to the XCDs by their linear id)
     const int lin = blockIdx.y * gridDim.x + blockIdx.x, nt2 = 2 * nt;
     const int q = nt2 / 8, rem = nt2 % 8, xcd = lin % 8;
@@ -423,8 +434,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
   auto emit = [&](auto pl_c, auto he_c, auto he2_c, auto in_c) {
     constexpr bool PL = decltype(pl_c)::value, HE = decltype(he_c)::value, HE2 = decltype(he2_c)::value, IN = decltype(in_c)::value;
     const long cis = PL ? (long)g.N : g.c_is, cjs = PL ? 1L : g.c_js;
-    double *cb = (PL ? g.part + (size_t)zidx * g.M * g.N : gC) + (size_t)ti0 * cis + (size_t)tj0 * cjs;
-    const double *eb = HE ? g.E + (size_t)ti0 * g.e_is + (size_t)tj0 * g.e_js : nullptr;
+    double *cb = (PL ? gP + (size_t)zidx * g.M * g.N : gC) + (size_t)ti0 * cis + (size_t)tj0 * cjs;
+    const double *eb = HE ? gE + (size_t)ti0 * g.e_is + (size_t)tj0 * g.e_js : nullptr;
     const double *e2b = HE2 ? g.E2 + (size_t)ti0 * g.e_is + (size_t)tj0 * g.e_js : nullptr;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
@@ -453,8 +464,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
     const bool inside = row0 + GB <= g.M && col0 + GB <= g.N;
     auto pick_in = [&](auto pl_c, auto he_c, auto he2_c) { if (inside) emit(pl_c, he_c, he2_c, T_{}); else emit(pl_c, he_c, he2_c, F_{}); };
     if (to_planes) pick_in(T_{}, F_{}, F_{});
-    else if (g.E && g.E2) pick_in(F_{}, T_{}, T_{});
-    else if (g.E) pick_in(F_{}, T_{}, F_{});
+    else if (gE && g.E2) pick_in(F_{}, T_{}, T_{});
+    else if (gE) pick_in(F_{}, T_{}, F_{});
     else if (g.E2) pick_in(F_{}, F_{}, T_{});
     else pick_in(F_{}, F_{}, F_{});
   }
@@ -470,6 +481,21 @@ __global__ void splitk_reduce_kernel(GemmArgs g, int nsplit) {
   if (g.E) o += g.beta * g.E[(size_t)i * g.e_is + (size_t)j * g.e_js];
   if (g.E2) o += g.gamma * g.E2[(size_t)i * g.e_is + (size_t)j * g.e_js];
   g.C[(size_t)i * g.c_is + (size_t)j * g.c_js] = o;
+}
+
+// splitk_reduce_kernel for the problems of a batch (blockIdx.y): each problem's planes in the same fixed order
+__global__ void splitk_reduce_batch_kernel(GemmArgs g, int nsplit) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)g.M * g.N) return;
+  const long slot = g.bslots[blockIdx.y];
+  const double *part = g.part + slot * g.part_bs;
+  const double *E = g.E ? g.E + slot * g.e_bs : nullptr;
+  const int i = (int)(idx / g.N), j = (int)(idx % g.N);
+  double v = 0.0;
+  for (int z = 0; z < nsplit; ++z) v += part[((size_t)z * g.M + i) * g.N + j];  // fixed order
+  double o = g.alpha * v;
+  if (E) o += g.beta * E[(size_t)i * g.e_is + (size_t)j * g.e_js];
+  (g.C + slot * g.c_bs)[(size_t)i * g.c_is + (size_t)j * g.c_js] = o;
 }
 
 // The reduction of a split SQUARE product with the small-matrix work of the eigensolver folded in (GemmFusedReduce,
@@ -584,10 +610,15 @@ int gemm_plan_split(int M, int N, int Kd, size_t work_elems) {
 int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double *A, long a_is, long a_ks,
                 const double *B, long b_ks, long b_js, double beta, const double *E, long e_is, long e_js,
                 double *C, long c_is, long c_js, double *work, size_t work_elems, double gamma,
-                const double *E2, GemmFusedReduce *fused, const GemmPair *pair, int force_split, int *planes_out) {
+                const double *E2, GemmFusedReduce *fused, const GemmPair *pair, int force_split, int *planes_out,
+                const GemmBatch *batch) {
   if (fused) fused->done = false;
   if (pair && (E || E2 || fused)) { set_error("gemm: a paired product takes no E / E2 / fused reduction"); return FLGP_ERR_INVALID; }
-  if (M <= 0 || N <= 0) return FLGP_OK;
+  if (batch && (pair || fused || (E2 && gamma != 0.0) || batch->count > GEMM_BATCH_MAX)) {
+    set_error("gemm: a batch takes no second product, E2 or fused reduction, and at most %d problems", GEMM_BATCH_MAX);
+    return FLGP_ERR_INVALID;
+  }
+  if (M <= 0 || N <= 0 || (batch && batch->count <= 0)) return FLGP_OK;
   GemmArgs g;
   // orient so that the contiguous output dimension is the kernel's column dimension
   const bool swapped = c_is == 1 && c_js != 1;
@@ -607,6 +638,12 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
     if (pair) { g.A2 = pair->A2; g.B2 = pair->B2; }
   }
   if (!pair) { g.A2 = g.B2 = nullptr; g.C2 = nullptr; } else g.C2 = pair->C2;
+  g.bslots = nullptr; g.a_bs = g.b_bs = g.c_bs = g.e_bs = g.part_bs = 0;
+  if (batch) {
+    g.bslots = batch->slots;
+    g.a_bs = swapped ? batch->b_bs : batch->a_bs; g.b_bs = swapped ? batch->a_bs : batch->b_bs;
+    g.c_bs = batch->c_bs; g.e_bs = batch->e_bs; g.part_bs = batch->part_bs;
+  }
   g.alpha = alpha; g.beta = beta; g.gamma = gamma;
   g.E2 = (gamma == 0.0) ? nullptr : E2;
   if (beta == 0.0) g.E = nullptr;
@@ -639,10 +676,19 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
     // second record per shape class (large / medium / small) for the bench breakdown
     ProfScope ps2(fl > 5e9 ? "gemm_large" : (fl > 2e8 ? "gemm_medium" : "gemm_small"), st, fl);
     const int ny = pair ? 2 : 1;
-    if (gbt == 64) hipLaunchKernelGGL(gemm_f64_kernel<64>, dim3(ntiles, ny, nsplit), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(gemm_f64_kernel<128>, dim3(ntiles, ny, nsplit), dim3(256), 0, st, g);
+    if (batch) {
+      if ((long)ntiles * batch->count > 0x7FFFFFFFL) { set_error("gemm: %d tiles x %d problems exceed a grid", ntiles, batch->count); return FLGP_ERR_INVALID; }
+      const dim3 grid(ntiles * batch->count, 1, nsplit);
+      if (gbt == 64) hipLaunchKernelGGL((gemm_f64_kernel<64, true>), grid, dim3(256), 0, st, g);
+      else hipLaunchKernelGGL((gemm_f64_kernel<128, true>), grid, dim3(256), 0, st, g);
+    } else if (gbt == 64) hipLaunchKernelGGL((gemm_f64_kernel<64, false>), dim3(ntiles, ny, nsplit), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((gemm_f64_kernel<128, false>), dim3(ntiles, ny, nsplit), dim3(256), 0, st, g);
   }
   FLGP_TRY(check_launch("gemm_f64_kernel"));
+  if (nsplit > 1 && batch) {
+    hipLaunchKernelGGL(splitk_reduce_batch_kernel, dim3(ceil_div((long)g.M * g.N, 256), batch->count), dim3(256), 0, st, g, nsplit);
+    return check_launch("splitk_reduce_batch_kernel");
+  }
   if (nsplit > 1) {
     if (fused && g.M == g.N && alpha == 1.0 && !g.E && !g.E2 && (g.c_is == 1 || g.c_js == 1)) {
       const int nt1 = ceil_div(g.M, 16);
@@ -724,6 +770,7 @@ int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, do
   g.C = C; g.c_is = b; g.c_js = 1;            // kernel (i, j) = caller (column, row), as gemm_launch orients a column-major result
   g.shift_edges = 0; g.ksplit_len = 0; g.part = const_cast<double *>(part);
   g.A2 = g.B2 = nullptr; g.C2 = nullptr;
+  g.bslots = nullptr; g.a_bs = g.b_bs = g.c_bs = g.e_bs = g.part_bs = 0;
   if (fused) {
     const int nt1 = ceil_div(b, 16);
     hipLaunchKernelGGL(splitk_reduce_sym_kernel, dim3(nt1 * nt1), dim3(256), 0, st, g, nsplit, fused->mode, fused->dinv, fused->dist,

@@ -25,7 +25,8 @@ __device__ __forceinline__ double readlane_d(double x, int l) {
 // Lower Cholesky factor of the diagonal block A(k0:k0+nb, k0:k0+nb) in place, one wave: lane i holds row i of the block
 // in registers (rows past nb are padded with the identity), column j's pivot and multipliers are read across lanes with
 // readlane.  flag[0] = (global index + 1) of the first pivot that is not positive; a set flag turns later steps off.
-__global__ __launch_bounds__(64) void chol_panel_kernel(double *__restrict__ A, long lda, int m, int k0, int *__restrict__ flag) {
+// (the steps are written once, for this kernel and the one-wave-per-problem kernel of the batched loop below)
+__device__ __forceinline__ void chol_panel_body(double *__restrict__ A, long lda, int m, int k0, int *__restrict__ flag) {
   if (flag[0]) return;
   const int lane = threadIdx.x;
   const int nb = min(CNB, m - k0);
@@ -58,11 +59,15 @@ __global__ __launch_bounds__(64) void chol_panel_kernel(double *__restrict__ A, 
     if (lane < nb && k <= lane) A[(size_t)(k0 + k) * lda + k0 + lane] = r[k];
   if (bad && lane == 0) flag[0] = bad;
 }
+__global__ __launch_bounds__(64) void chol_panel_kernel(double *__restrict__ A, long lda, int m, int k0, int *__restrict__ flag) {
+  chol_panel_body(A, lda, m, k0, flag);
+}
 
 // Panel column: L21 = A21 L11^-T for the rows below the diagonal block, a thread per row (x L11^T = a by forward
 // substitution), L11 in LDS (identity-padded past nb; every lane reads the same element: a broadcast), the row's
 // unknowns in LDS as well (a register array of 64 unrolled twice over spills).
-__global__ __launch_bounds__(64) void chol_trsm_kernel(double *__restrict__ A, long lda, int m, int k0, const int *__restrict__ flag) {
+__device__ __forceinline__ void chol_trsm_body(double *__restrict__ A, long lda, int m, int k0, const int *__restrict__ flag,
+                                               int rowblock) {
   if (flag[0]) return;
   __shared__ double Ls[CNB][CNB];   // Ls[k][j] = L11(j, k)
   __shared__ double xs[CNB][64];    // xs[j][lane] = x_j of this lane's row
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(64) void chol_trsm_kernel(double *__restrict__ A, l
     Ls[k][j] = v;
   }
   __syncthreads();
-  const int i = k0 + nb + blockIdx.x * 64 + tid;
+  const int i = k0 + nb + rowblock * 64 + tid;
   if (i >= m) return;
   for (int j = 0; j < nb; ++j) {
     double acc = A[(size_t)(k0 + j) * lda + i];
@@ -84,6 +89,9 @@ __global__ __launch_bounds__(64) void chol_trsm_kernel(double *__restrict__ A, l
     xs[j][tid] = acc;
     A[(size_t)(k0 + j) * lda + i] = acc;
   }
+}
+__global__ __launch_bounds__(64) void chol_trsm_kernel(double *__restrict__ A, long lda, int m, int k0, const int *__restrict__ flag) {
+  chol_trsm_body(A, lda, m, k0, flag, blockIdx.x);
 }
 
 // In-place lower Cholesky factor of the SPD m x m matrix A (column-major, leading dimension lda).  Only the lower triangle
@@ -110,11 +118,11 @@ int chol_blocked(hipStream_t st, double *dA, long lda, int m, int *d_flag) {
 // dimension ldb), in place: mode bit 0 solves L y = b, bit 1 then L^T x = y.  Blocks of 64 unknowns: the triangle of a
 // block is solved by one wave in registers, the rest of the rows by the whole workgroup (forward: an axpy per row,
 // backward: a dot product along a column of L per row, reduced in a fixed order).
-__global__ __launch_bounds__(256) void chol_trsv_kernel(const double *__restrict__ L, long lda, int m, double *__restrict__ B,
-                                                        long ldb, int mode, const int *__restrict__ flag) {
+// (b: the workgroup's right-hand side)
+__device__ __forceinline__ void chol_trsv_body(const double *__restrict__ L, long lda, int m, double *__restrict__ b, int mode,
+                                               const int *__restrict__ flag) {
   if (flag[0]) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double *b = B + (size_t)blockIdx.x * ldb;
   __shared__ double ys[CNB];
   if (mode & 1) {
     for (int b0 = 0; b0 < m; b0 += CNB) {
@@ -168,6 +176,10 @@ __global__ __launch_bounds__(256) void chol_trsv_kernel(const double *__restrict
       __syncthreads();
     }
   }
+}
+__global__ __launch_bounds__(256) void chol_trsv_kernel(const double *__restrict__ L, long lda, int m, double *__restrict__ B,
+                                                        long ldb, int mode, const int *__restrict__ flag) {
+  chol_trsv_body(L, lda, m, B + (size_t)blockIdx.x * ldb, mode, flag);
 }
 
 int chol_trsv(hipStream_t st, const double *dL, long lda, int m, double *dB, long ldb, int nrhs, int mode, const int *d_flag) {
@@ -420,10 +432,10 @@ __global__ void gpc_lr_a_kernel(const double *__restrict__ b, const double *__re
 
 // amll = -0.5 sum(a f) + (sum(Y log pi) + sum((N - Y) log(1 - pi))) - 0.5 sum(log D_i) - sum(log (L_Q)_kk): log det B =
 // log det D + log det Q exactly (no 1e-9 on the pivots: the one departure from gpc_amll_kernel, include/flgp_hip.h)
-__global__ __launch_bounds__(1024) void gpc_lr_amll_kernel(const double *__restrict__ f, const double *__restrict__ a,
-                                                           const double *__restrict__ Y, const double *__restrict__ N,
-                                                           const double *__restrict__ D, const double *__restrict__ LQ, int K,
-                                                           int m, double *__restrict__ out) {
+__device__ __forceinline__ void gpc_lr_amll_body(const double *__restrict__ f, const double *__restrict__ a,
+                                                 const double *__restrict__ Y, const double *__restrict__ N,
+                                                 const double *__restrict__ D, const double *__restrict__ LQ, int K, int m,
+                                                 double *__restrict__ out) {
   __shared__ double red[1024];
   double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
   for (int i = threadIdx.x; i < m; i += 1024) {
@@ -446,6 +458,12 @@ __global__ __launch_bounds__(1024) void gpc_lr_amll_kernel(const double *__restr
     amll -= s5;
     out[0] = amll;
   }
+}
+__global__ __launch_bounds__(1024) void gpc_lr_amll_kernel(const double *__restrict__ f, const double *__restrict__ a,
+                                                           const double *__restrict__ Y, const double *__restrict__ N,
+                                                           const double *__restrict__ D, const double *__restrict__ LQ, int K,
+                                                           int m, double *__restrict__ out) {
+  gpc_lr_amll_body(f, a, Y, N, D, LQ, K, m, out);
 }
 
 int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b) {
@@ -473,6 +491,191 @@ int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const doub
                 const double *d_LQ, int K, int m, double *d_out) {
   hipLaunchKernelGGL(gpc_lr_amll_kernel, dim3(1), dim3(1024), 0, st, d_f, d_a, d_Y, d_N, d_D, d_LQ, K, m, d_out);
   return check_launch("gpc_lr_amll_kernel");
+}
+
+// ---- the low-rank Newton loop for a chunk of independent problems (the loop is in eigenpair.hip) --------
+// Every kernel above that the single loop launches, with the problem in blockIdx.y: entry q of the device list `act` names
+// the slot whose buffers the workgroups of row q use (LrChunk, common.h).  The expressions are the single kernels' own,
+// operation for operation, so a slot holds the bits the single loop would hold for its problem.
+
+__global__ void lrb_weights_kernel(const double *__restrict__ values, int K, const double *__restrict__ ts, long sk,
+                                   double *__restrict__ ls, double *__restrict__ l) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const long s = blockIdx.y;
+  const double t = ts[s];
+  const double lam = 1.0 - values[k];            // gpr_weights_kernel
+  ls[s * sk + k] = exp(-0.5 * t * lam) + 0.0;
+  l[s * sk + k] = exp(-t * lam);
+}
+
+__global__ void lrb_w_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long s = act[blockIdx.y], o = s * c.sv + i;
+  const double fi = c.f[o], yi = c.Y[(size_t)c.ycol[s] * c.ldy + i];
+  const double pi = 1.0 / (1.0 + exp(-fi));      // gpc_w_kernel with N
+  const double ni = c.N[i];
+  const double W = ni * pi * (1.0 - pi);
+  const double bi = W * fi + yi * (1.0 - pi) + (ni - yi) * (-pi);
+  c.sW[o] = __builtin_sqrt(W);
+  c.b[o] = bi;
+}
+
+__global__ void lrb_d_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long o = (long)act[blockIdx.y] * c.sv + i;
+  const double s = c.sW[o], d = 1.0 + c.sigma * (s * s), h = 1.0 / __builtin_sqrt(d);   // gpc_lr_d_kernel
+  c.D[o] = d; c.dh[o] = h; c.xs[o] = s * h;
+}
+
+// X = diag(xs) V1 diag(ls)   (gpc_scale2_kernel)
+__global__ void lrb_scale2_kernel(LrChunk c, const int *__restrict__ act) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)c.m * c.K) return;
+  const long s = act[blockIdx.y];
+  const int i = (int)(e % c.m), j = (int)(e / c.m);
+  c.X[s * c.sx + e] = c.xs[s * c.sv + i] * c.V1[(size_t)j * c.ld1 + i] * c.ls[s * c.sk + j];
+}
+
+// Q(i, i) += 1   (gpr_add_diag_kernel)
+__global__ void lrb_add_diag_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < c.K) c.Q[(long)act[blockIdx.y] * c.sq + (size_t)i * c.K + i] += 1.0;
+}
+
+// out = a .* x   (pg_mul_kernel without its third factor); a stride of 0 shares the vector
+__global__ void lrb_mul_kernel(int n, const double *__restrict__ a, long sa, const double *__restrict__ x, long sx,
+                               double *__restrict__ out, long so, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long s = act[blockIdx.y];
+  out[s * so + i] = a[s * sa + i] * x[s * sx + i];
+}
+
+// out = x + c z   (pg_axpy3_kernel with x and z)
+__global__ void lrb_axpy_kernel(int n, const double *__restrict__ x, long sx, double c, const double *__restrict__ z, long sz,
+                                double *__restrict__ out, long so, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long s = act[blockIdx.y];
+  double v = x[s * sx + i];
+  v = v + c * z[s * sz + i];
+  out[s * so + i] = v;
+}
+
+__global__ void lrb_a_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long o = (long)act[blockIdx.y] * c.sv + i;
+  c.a[o] = c.b[o] - c.sW[o] * (c.dh[o] * (c.g[o] - c.Xv[o]));      // gpc_lr_a_kernel
+}
+
+// gpc_step_kernel, one workgroup per problem: diff[q] = |f - f_new|_1, f <- f_new, and behind the A norms the A pivot
+// flags of the same problems, so that the host reads both in one copy
+__global__ __launch_bounds__(1024) void lrb_step_kernel(LrChunk c, const int *__restrict__ act, int A, double *__restrict__ stat) {
+  __shared__ double red[1024];
+  const long s = act[blockIdx.x];
+  double *f = c.f + s * c.sv;
+  const double *fnew = c.fnew + s * c.sv;
+  double sum = 0.0;
+  for (int i = threadIdx.x; i < c.m; i += 1024) {
+    const double fn = fnew[i];
+    sum += __builtin_fabs(f[i] - fn);
+    f[i] = fn;
+  }
+  sum = block_sum_1024(sum, red);
+  if (threadIdx.x == 0) {
+    stat[blockIdx.x] = sum;
+    ((int *)(stat + A))[blockIdx.x] = c.flag[s];
+  }
+}
+
+__global__ __launch_bounds__(64) void lrb_chol_panel_kernel(LrChunk c, const int *__restrict__ act, int k0) {
+  const long s = act[blockIdx.x];
+  chol_panel_body(c.Q + s * c.sq, c.K, c.K, k0, c.flag + s);
+}
+__global__ __launch_bounds__(64) void lrb_chol_trsm_kernel(LrChunk c, const int *__restrict__ act, int k0) {
+  const long s = act[blockIdx.y];
+  chol_trsm_body(c.Q + s * c.sq, c.K, c.K, k0, c.flag + s, blockIdx.x);
+}
+// u <- Q^-1 u with the slot's factor, one workgroup per problem
+__global__ __launch_bounds__(256) void lrb_trsv_kernel(LrChunk c, const int *__restrict__ act) {
+  const long s = act[blockIdx.x];
+  chol_trsv_body(c.Q + s * c.sq, c.K, c.K, c.u + s * c.sk, 3, c.flag + s);
+}
+// the final sums of every slot of the chunk (no list: a problem that left the loop kept its f, a, D and L_Q)
+__global__ __launch_bounds__(1024) void lrb_amll_kernel(LrChunk c) {
+  const long s = blockIdx.x;
+  gpc_lr_amll_body(c.f + s * c.sv, c.a + s * c.sv, c.Y + (size_t)c.ycol[s] * c.ldy, c.N, c.D + s * c.sv, c.Q + s * c.sq, c.K,
+                   c.m, c.amll + s);
+}
+
+int lrb_weights(hipStream_t st, const double *d_values, int K, const double *d_ts, int slots, long sk, double *d_ls, double *d_l) {
+  hipLaunchKernelGGL(lrb_weights_kernel, dim3(ceil_div(K, 256), slots), dim3(256), 0, st, d_values, K, d_ts, sk, d_ls, d_l);
+  return check_launch("lrb_weights_kernel");
+}
+int lrb_w(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_w_kernel, dim3(ceil_div(c.m, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("lrb_w_kernel");
+}
+int lrb_d(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_d_kernel, dim3(ceil_div(c.m, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("lrb_d_kernel");
+}
+int lrb_scale2(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_scale2_kernel, dim3(ceil_div((long)c.m * c.K, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("lrb_scale2_kernel");
+}
+int lrb_add_diag(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_add_diag_kernel, dim3(ceil_div(c.K, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("lrb_add_diag_kernel");
+}
+int lrb_mul(hipStream_t st, int n, const double *a, long sa, const double *x, long sx, double *out, long so, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_mul_kernel, dim3(ceil_div(n, 256), A), dim3(256), 0, st, n, a, sa, x, sx, out, so, act);
+  return check_launch("lrb_mul_kernel");
+}
+int lrb_axpy(hipStream_t st, int n, const double *x, long sx, double c, const double *z, long sz, double *out, long so,
+             const int *act, int A) {
+  hipLaunchKernelGGL(lrb_axpy_kernel, dim3(ceil_div(n, 256), A), dim3(256), 0, st, n, x, sx, c, z, sz, out, so, act);
+  return check_launch("lrb_axpy_kernel");
+}
+int lrb_a(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_a_kernel, dim3(ceil_div(c.m, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("lrb_a_kernel");
+}
+int lrb_step(hipStream_t st, const LrChunk &c, const int *act, int A, double *d_stat) {
+  hipLaunchKernelGGL(lrb_step_kernel, dim3(A), dim3(1024), 0, st, c, act, A, d_stat);
+  return check_launch("lrb_step_kernel");
+}
+// chol_blocked on the Q of every listed slot: its panels in its order, one launch per step whatever A is
+int lrb_chol(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  ProfScope ps("chol_blocked_batch", st, (double)A * c.K * c.K * c.K / 3.0);
+  const int m = c.K;
+  const long lda = c.K;
+  for (int k0 = 0; k0 < m; k0 += CNB) {
+    const int nb = std::min(CNB, m - k0), rem = m - k0 - nb;
+    hipLaunchKernelGGL(lrb_chol_panel_kernel, dim3(A), dim3(64), 0, st, c, act, k0);
+    FLGP_TRY(check_launch("lrb_chol_panel_kernel"));
+    if (rem <= 0) break;
+    hipLaunchKernelGGL(lrb_chol_trsm_kernel, dim3(ceil_div(rem, 64), A), dim3(64), 0, st, c, act, k0);
+    FLGP_TRY(check_launch("lrb_chol_trsm_kernel"));
+    const double *L21 = c.Q + (size_t)k0 * lda + k0 + nb;
+    double *A22 = c.Q + (size_t)(k0 + nb) * lda + k0 + nb;
+    const GemmBatch gb{A, act, c.sq, c.sq, c.sq, c.sq, 0};
+    FLGP_TRY(gemm_launch(st, rem, rem, nb, -1.0, L21, 1, lda, L21, lda, 1, 1.0, A22, 1, lda, A22, 1, lda, nullptr, 0, 0.0,
+                         nullptr, nullptr, nullptr, 0, nullptr, &gb));
+  }
+  return FLGP_OK;
+}
+int lrb_trsv(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(lrb_trsv_kernel, dim3(A), dim3(256), 0, st, c, act);
+  return check_launch("lrb_trsv_kernel");
+}
+int lrb_amll(hipStream_t st, const LrChunk &c) {
+  hipLaunchKernelGGL(lrb_amll_kernel, dim3(c.slots), dim3(1024), 0, st, c);
+  return check_launch("lrb_amll_kernel");
 }
 
 // ---- the weight-space Newton loop and the fused predictive rows (m > K; the loop is in eigenpair.hip) ------
