@@ -284,19 +284,14 @@ struct GpcNewton {
   int amll(hipStream_t st, const double *dY, const double *dN, double *out);   // synchronises
   static int pivot_error(int bad, const char *who, int iter);   // iter 0: the factorisation at the final f
 };
-// The elementwise steps and final sums of the low-rank Newton loop (m > K, C = V1 L V1^T + sigma I; eigenpair.hip).
+// The elementwise steps of the weight-space Newton loop (m > K, C = V1 L V1^T + sigma I; GpcWeightSpace, eigenpair.hip).
 // gpc_weights: sW and b from f (gpc_w_kernel); gpc_step: diff = |f - f_new|_1 in a fixed order, f <- f_new;
-// gpc_lr_dvec: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh; gpc_lr_a: a = b - sW .* (dh .* (g - Xv));
-// gpc_lr_amll: -0.5 a^T f + sum Y log pi + sum (N - Y) log(1 - pi) - 0.5 sum log D - sum log (L_Q)_kk (K x K factor).
+// gpc_lr_dvec: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh.
 int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b);
 int gpc_step(hipStream_t st, double *d_f, const double *d_fnew, int m, double *d_diff);
 int gpc_lr_dvec(hipStream_t st, const double *d_sW, double sigma, int m, double *d_D, double *d_dh, double *d_xs);
-int gpc_lr_a(hipStream_t st, const double *d_b, const double *d_sW, const double *d_dh, const double *d_g, const double *d_Xv,
-             int m, double *d_a);
-int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const double *d_Y, const double *d_N, const double *d_D,
-                const double *d_LQ, int K, int m, double *d_out);
-// The low-rank loop for a chunk of independent problems in the same launches (gpc.hip, the loop itself in
-// eigenpair.hip).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
+// The low-rank Newton loop of the logit training objective (m > K) for a chunk of independent problems in the same
+// launches (gpc.hip, the loop itself in eigenpair.hip: LrBatch).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
 // of A slot numbers (the problems still iterating) and carry its index in the grid, so a step is one launch whatever A is
 // and a slot that left the list is not written again.  The strides are doubles between two slots; Y, N, V1 are shared.
 struct LrChunk {
@@ -311,11 +306,13 @@ struct LrChunk {
   int *flag;                                                    // one pivot flag per slot (chol_blocked's)
   double *amll;                                                 // one result per slot
 };
-// lrb_weights: gpr_weights for slot s at d_ts[s], s < slots.  lrb_w .. lrb_a: gpc_weights, gpc_lr_dvec, gpc_scale2 (X),
-// gpr_add_diag (Q, 1), pg_mul (two factors), pg_axpy3 (x + c z) and gpc_lr_a on the listed slots (lrb_mul / lrb_axpy: n
-// elements, a stride per operand, 0 = shared).  lrb_step: gpc_step per listed problem, d_stat[q] = the norm of act[q] and
-// ((int *)(d_stat + A))[q] = its pivot flag: 12 A bytes for the host.  lrb_chol: chol_blocked of every listed Q; lrb_trsv:
-// u <- Q^-1 u per listed slot; lrb_amll: gpc_lr_amll of every slot of the chunk into amll[slot].
+// lrb_weights: l = exp(-t (1 - values)) and ls = l^1/2 for slot s at t = d_ts[s], s < slots.  On the listed slots: lrb_w:
+// sW and b from f, Y, N; lrb_d: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh; lrb_scale2: X = diag(xs) V1 diag(ls);
+// lrb_add_diag: Q += I; lrb_mul: out = a .* x, lrb_axpy: out = x + c z (n elements, a stride per operand, 0 = shared);
+// lrb_a: a = b - sW .* (dh .* (g - Xv)).  lrb_step: |f - f_new|_1 in a fixed order and f <- f_new per listed problem,
+// d_stat[q] = the norm of act[q] and ((int *)(d_stat + A))[q] = its pivot flag: 12 A bytes for the host.  lrb_chol:
+// chol_blocked of every listed Q; lrb_trsv: u <- Q^-1 u per listed slot; lrb_amll, for every slot of the chunk: amll[slot] =
+// -0.5 a^T f + sum Y log pi + sum (N - Y) log(1 - pi) - 0.5 sum log D - sum log (L_Q)_kk (the K x K factor).
 int lrb_weights(hipStream_t st, const double *d_values, int K, const double *d_ts, int slots, long sk, double *d_ls, double *d_l);
 int lrb_w(hipStream_t st, const LrChunk &c, const int *act, int A);
 int lrb_d(hipStream_t st, const LrChunk &c, const int *act, int A);

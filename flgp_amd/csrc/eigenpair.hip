@@ -602,10 +602,11 @@ extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int
   return E.finish(who, nx, value, grad);
 }
 
-// ---- logit training objective: what train_lae_logit_gp_cpp's COBYLA minimises, on the resident pair ------
+// ---- logit training objective: what train_lae_logit_gp_cpp's COBYLA minimises, on the
+// resident pair, for B problems (labels, t) in one call; the single entry is the batch of one ------------------------------
 namespace {
-// The low-rank pieces of C = V1 L V1^T + sigma I (V1 m x K at ld1, L = exp(-t (1 - values)), ls = L^1/2) that the logit
-// loop below and the Polya-Gamma sweep share.  With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with
+// The low-rank pieces of C = V1 L V1^T + sigma I (V1 m x K at ld1, L = exp(-t (1 - values)), ls = L^1/2) that the
+// weight-space logit loop (GpcWeightSpace) and the Polya-Gamma sweep share.  With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with
 // X = diag(xs) V1 L^1/2 (xs = D^-1/2 sW) and Q = I + X^T X (K x K):
 //   B^-1 y = D^-1 y - D^-1/2 X Q^-1 X^T D^-1/2 y,   det B = det D det Q.
 // The callers' elementwise kernels make xs and use the result; the sigma x term of C x is theirs too.
@@ -647,131 +648,17 @@ struct LowRankB {
   }
 };
 
-// Alg. 3.1 for m > K on LowRankB's C, O(m K^2) per iteration, never an m x m matrix.  Per iteration: sW, b from f; D, X, Q
-// factored (K x K); c = C b; r = B^-1 (sW c); a = b - sW r; f_new = C a.  As in GpcNewton, a, D and L_Q stay those of the
-// LAST iteration and f is the final mode; everything is fixed-order.
-struct GpcLowRank {
-  int m = 0;
-  LowRankB L;                  // the caller sets V1, ld1, l, ls, sigma
-  DevBuf f, fnew, sW, b, a, D, dh, xs, c, g, Xv, scal, flag;
-
-  int alloc(int m_, int K) {
-    m = m_;
-    const size_t v = sizeof(double) * (size_t)m;
-    FLGP_TRY(f.alloc(v)); FLGP_TRY(fnew.alloc(v)); FLGP_TRY(sW.alloc(v)); FLGP_TRY(b.alloc(v)); FLGP_TRY(a.alloc(v));
-    FLGP_TRY(D.alloc(v)); FLGP_TRY(dh.alloc(v)); FLGP_TRY(xs.alloc(v)); FLGP_TRY(c.alloc(v)); FLGP_TRY(g.alloc(v));
-    FLGP_TRY(Xv.alloc(v));
-    FLGP_TRY(scal.alloc(sizeof(double) * 2)); FLGP_TRY(flag.alloc(sizeof(int)));
-    return L.alloc(m, K, true, flag.as<int>());
-  }
-  // out = C x   (Xv is the scratch)
-  int cmul(hipStream_t st, const double *x, double *out) {
-    FLGP_TRY(L.cmul(st, L.V1, L.ld1, m, x, Xv.as<double>()));
-    return pg_axpy3(st, m, Xv.as<double>(), nullptr, L.sigma, x, out);
-  }
-  int iteration(hipStream_t st, const double *dY, const double *dN) {
-    ProfScope ps("logit_lr_newton_iter", st, 0.0);
-    FLGP_TRY(gpc_weights(st, f.as<double>(), dY, dN, m, sW.as<double>(), b.as<double>()));
-    FLGP_TRY(gpc_lr_dvec(st, sW.as<double>(), L.sigma, m, D.as<double>(), dh.as<double>(), xs.as<double>()));
-    FLGP_TRY(L.factor(st, xs.as<double>()));
-    FLGP_TRY(cmul(st, b.as<double>(), c.as<double>()));                                                           // c = C b
-    FLGP_TRY(pg_mul(st, m, xs.as<double>(), c.as<double>(), nullptr, g.as<double>()));                           // g = D^-1/2 sW c
-    FLGP_TRY(L.apply(st, g.as<double>(), Xv.as<double>()));
-    FLGP_TRY(gpc_lr_a(st, b.as<double>(), sW.as<double>(), dh.as<double>(), g.as<double>(), Xv.as<double>(), m, a.as<double>()));
-    FLGP_TRY(cmul(st, a.as<double>(), fnew.as<double>()));                                                        // f_new = C a
-    return gpc_step(st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
-  }
-  // the loop from f = 0 with GpcNewton::run's host protocol (12 bytes read back per iteration), then the final sums
-  int run(hipStream_t st, const double *dY, const double *dN, double tol, int max_iter, const char *who, int *iters, double *amll) {
-    FLGP_HIP(hipMemsetAsync(f.p, 0, sizeof(double) * (size_t)m, st));
-    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    *iters = 0;
-    for (int it = 0; it < max_iter; ++it) {
-      FLGP_TRY(iteration(st, dY, dN));
-      double diff = 0.0;
-      int bad = 0;
-      FLGP_HIP(hipMemcpyAsync(&diff, scal.p, sizeof(double), hipMemcpyDeviceToHost, st));
-      FLGP_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-      FLGP_HIP(hipStreamSynchronize(st));
-      *iters = it + 1;
-      FLGP_TRY(GpcNewton::pivot_error(bad, who, it + 1));
-      if (diff < tol) break;
-    }
-    FLGP_TRY(gpc_lr_amll(st, f.as<double>(), a.as<double>(), dY, dN, D.as<double>(), L.Q.as<double>(), L.K, m, scal.as<double>() + 1));
-    FLGP_HIP(hipMemcpyAsync(amll, scal.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, st));
-    FLGP_HIP(hipStreamSynchronize(st));
-    return FLGP_OK;
-  }
-};
-}  // namespace
-
-// negative_marginal_likelihood_logit_cpp / negative_log_posterior_logit_cpp (src/train.cpp:14-34): m <= K runs
-// flgp_eigenpair_logit_marginal_likelihood's dense loop unchanged, m > K the low-rank loop above.
-extern "C" int flgp_eigenpair_logit_objective(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y,
-                                              const double *N, double sigma, const char *approach, const double *prior,
-                                              double t, double tol, int max_iter, double *value, int *iters) {
-  const char *who = "logit_objective";
-  FLGP_REQUIRE(approach, "%s: null pointer", who);
-  const bool posterior = std::strcmp(approach, "posterior") == 0;
-  if (!posterior && std::strcmp(approach, "marginal") != 0) {
-    set_error("This model selection approach is not supported!");
-    return FLGP_ERR_UNSUPPORTED;
-  }
-  FLGP_REQUIRE(ep && idx && Y && value, "%s: null pointer", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1, "%s: bad shape (K=%d of %d, m=%d, max_iter=%d)", who, K, ep->K,
-               m, max_iter);
-  Rows r;
-  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
-  FLGP_TRY(check_labels(Y, N, m, who));
-  FLGP_REQUIRE(std::isfinite(t), "%s: t=%g must be finite", who, t);
-  FLGP_REQUIRE(!posterior || t > 0.0, "%s: t=%g must be positive under \"posterior\"", who, t);
-  FLGP_REQUIRE(sigma >= 0.0 && std::isfinite(sigma), "%s: sigma=%g must be finite and >= 0", who, sigma);
-  const double dflt[3] = {1e-2, 10.0, 2.0};                     // PostOFData (src/train.h:138-140)
-  double pr[3];
-  for (int k = 0; k < 3; ++k) pr[k] = prior ? prior[k] : dflt[k];
-  FLGP_REQUIRE(all_finite(pr, 3), "%s: prior (p, q, tau) must be finite", who);
-  std::vector<double> ones;
-  if (!N) { ones.assign((size_t)m, 1.0); N = ones.data(); }    // the one-vs-rest route (src/MultiClassification.cpp:36)
-
-  Stream st;
-  FLGP_TRY(st.create());
-  double amll = 0.0;
-  int it = 0;
-  if (m <= K) {
-    // C = HK(idx, idx) + sigma I       (src/train.cpp:30-31)
-    DevBuf C, work;
-    FLGP_TRY(hk_c11(st.s, ep, K, t, r, sigma, C, work, flgp_dev_hk_workspace(m, m, K, 1)));
-    FLGP_TRY(logit_la_on_device(st.s, C.as<double>(), m, Y, N, tol, max_iter, &amll, &it, who));
-  } else {
-    GprCtx G;
-    FLGP_TRY(G.prepare(st.s, ep, K, t));                        // ls = L^1/2, l = L
-    FLGP_TRY(r.gather(st.s, ep, K));
-    DevBuf dY, dN;
-    FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
-    FLGP_TRY(upload(dN, N, sizeof(double) * (size_t)m, st.s));
-    GpcLowRank S;
-    S.L.sigma = sigma; S.L.V1 = r.V; S.L.ld1 = r.ld; S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
-    FLGP_TRY(S.alloc(m, K));
-    FLGP_TRY(S.run(st.s, dY.as<double>(), dN.as<double>(), tol, max_iter, who, &it, &amll));
-  }
-  if (iters) *iters = it;
-  if (posterior) {
-    const double p = pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]);   // src/train.cpp:17-24
-    *value = -amll + p;
-  } else {
-    *value = -amll;
-  }
-  return FLGP_OK;
-}
-
-// ---- the logit training objective for B problems in one call ---------------------------------------------
-namespace {
 inline long pad32(long n) { return (n + 31) / 32 * 32; }     // a slot starts 256-byte aligned, like an allocation of its own
 
-// GpcLowRank for a chunk of problems (m > K): slot s of every buffer belongs to problem p0 + s for the whole chunk, the
-// device list `act` names the slots still iterating and every step of an iteration is one launch over that list
-// (gpc.hip, LrChunk).  The split products take, per problem, the plan the single call takes (planQ for Q = X^T X, planU
-// for the two K x 1 products) on planes of the slot's own.
+// Alg. 3.1 for m > K on C = V1 L V1^T + sigma I, O(m K^2) per iteration, never an m x m matrix, for a chunk of problems.
+// With D = 1 + sigma W, xs = D^-1/2 sW, X = diag(xs) V1 L^1/2 and Q = I + X^T X (LowRankB's identities), per iteration:
+// sW, b from f; D, X, Q factored (K x K); c = C b; g = xs c; r = B^-1 (sW c) = D^-1/2 (g - X Q^-1 X^T g); a = b - sW r;
+// f_new = C a.  As in GpcNewton, a, D and L_Q stay those of the LAST iteration and f is the final mode; everything is
+// fixed-order.  Slot s of every buffer belongs to problem p0 + s for the whole chunk, the device list `act` names the slots
+// still iterating and every step of an iteration is one launch over that list (gpc.hip, LrChunk), so a problem's bits
+// depend on nothing that shares its chunk.  The split products take, per problem, the plan of an unbatched product with a
+// workspace of vt_work_elems(K, 1) doubles (planQ for Q = X^T X, planU for the two K x 1 products) on planes of the
+// slot's own.
 struct LrBatch {
   LrChunk C;
   DevBuf vec, kv, X, Q, part, stat, flag, amll, act;
@@ -821,7 +708,7 @@ struct LrBatch {
     return gemm_launch(st, C.m, 1, C.K, 1.0, Am, 1, lda, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, C.m, nullptr, 0, 0.0, nullptr,
                        nullptr, nullptr, 0, nullptr, &gb);
   }
-  // out = C x   (GpcLowRank::cmul; Xv is the scratch)
+  // out = C x = V1 (L (V1^T x)) + sigma x   (Xv is the scratch)
   int cmul(hipStream_t st, int A, const double *x, double *out) {
     const int *a = act.as<int>();
     FLGP_TRY(tn(st, A, C.V1, C.ld1, 0, x, C.u));
@@ -829,13 +716,13 @@ struct LrBatch {
     FLGP_TRY(nn(st, A, C.V1, C.ld1, 0, C.u, C.Xv));
     return lrb_axpy(st, C.m, C.Xv, C.sv, C.sigma, x, C.sv, out, C.sv, a, A);
   }
-  // GpcLowRank::iteration for the A listed slots: its launches in its order, each once
+  // one Newton iteration of the A listed slots: every launch once, whatever A is
   int iteration(hipStream_t st, int A) {
     ProfScope ps("logit_lr_batch_iter", st, 0.0);
     const int *a = act.as<int>();
-    FLGP_TRY(lrb_w(st, C, a, A));
-    FLGP_TRY(lrb_d(st, C, a, A));
-    FLGP_TRY(lrb_scale2(st, C, a, A));                                                        // LowRankB::factor
+    FLGP_TRY(lrb_w(st, C, a, A));                                                             // sW, b
+    FLGP_TRY(lrb_d(st, C, a, A));                                                             // D, dh, xs
+    FLGP_TRY(lrb_scale2(st, C, a, A));                                                        // X, then Q = I + X^T X = L_Q L_Q^T
     {
       const GemmBatch gb{A, a, C.sx, C.sx, C.sq, 0, sp};
       FLGP_TRY(gemm_launch(st, C.K, C.K, C.m, 1.0, C.X, C.m, 1, C.X, 1, C.m, 0.0, nullptr, 0, 0, C.Q, 1, C.K, part.as<double>(), pe,
@@ -845,10 +732,10 @@ struct LrBatch {
     FLGP_TRY(lrb_chol(st, C, a, A));
     FLGP_TRY(cmul(st, A, C.b, C.c));                                                          // c = C b
     FLGP_TRY(lrb_mul(st, C.m, C.xs, C.sv, C.c, C.sv, C.g, C.sv, a, A));                       // g = D^-1/2 sW c
-    FLGP_TRY(tn(st, A, C.X, C.m, C.sx, C.g, C.u));                                            // LowRankB::apply
+    FLGP_TRY(tn(st, A, C.X, C.m, C.sx, C.g, C.u));                                            // Xv = X Q^-1 X^T g
     FLGP_TRY(lrb_trsv(st, C, a, A));
     FLGP_TRY(nn(st, A, C.X, C.m, C.sx, C.u, C.Xv));
-    FLGP_TRY(lrb_a(st, C, a, A));
+    FLGP_TRY(lrb_a(st, C, a, A));                                                             // a = b - sW dh (g - Xv)
     FLGP_TRY(cmul(st, A, C.a, C.fnew));                                                       // f_new = C a
     return lrb_step(st, C, a, A, stat.as<double>());
   }
@@ -857,8 +744,9 @@ struct LrBatch {
 struct BatchFailure { int problem = -1, bad = 0, iter = 0; };
 
 // The chunk [p0, p0 + S) from f = 0: after every iteration the host reads the A norms and the A flags (12 A bytes), notes
-// the iteration count of every listed problem and takes the converged ones (and the failed ones) off the list, which is
-// where GpcLowRank::run stops for them.  amll_h / its: the S results.
+// the iteration count of every listed problem and takes the converged ones (norm < tol) and the failed ones (a pivot
+// flag) off the list: GpcNewton::run's protocol per problem.  The final sums follow for every slot.  amll_h / its: the S
+// results.
 int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
                    int p0, double *amll_h, int *its, BatchFailure &fail) {
   LrChunk &C = L.C;
@@ -906,43 +794,52 @@ struct DenseObjWorker {
     return S.alloc(m);
   }
   static double bytes(int m, int K) { return 8.0 * (2.0 * m * m + 8.0 * m) + (double)flgp_dev_hk_workspace(m, m, K, 1); }
+  // one problem: C = HK(r, r) + sigma I at t (src/train.cpp:30-31; a zero sigma launches nothing: the diagonal of HK(r, r)
+  // is a sum of squares, never -0), GpcNewton's loop on it and the final sums
+  int objective(hipStream_t st, const flgp_eigenpair *ep, int K, double t, const Rows &r, double sigma, const double *dY,
+                const double *dN, double tol, int max_iter, const char *who, int *iters, double *amll) {
+    FLGP_TRY(hk(st, ep, K, t, r, r, C.as<double>(), work.as<double>()));
+    if (sigma != 0.0) FLGP_TRY(gpr_add_diag(st, C.as<double>(), r.m, sigma));
+    FLGP_TRY(S.run(st, C.as<double>(), dY, dN, tol, max_iter, who, iters));
+    return S.amll(st, dY, dN, amll);
+  }
 };
-}  // namespace
 
-extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y,
-                                                    int ncol, const double *N, const int *col, const double *ts, int B,
-                                                    double sigma, const char *approach, const double *prior, double tol,
-                                                    int max_iter, int max_parallel, double *values, int *iters) {
-  const char *who = "logit_objective_batch";
+// The checks the two entries word alike, under the caller's name; each entry calls them at its own place among its others.
+int objective_approach(const char *who, const char *approach, bool *posterior) {
   FLGP_REQUIRE(approach, "%s: null pointer", who);
-  const bool posterior = std::strcmp(approach, "posterior") == 0;
-  if (!posterior && std::strcmp(approach, "marginal") != 0) {
+  *posterior = std::strcmp(approach, "posterior") == 0;
+  if (!*posterior && std::strcmp(approach, "marginal") != 0) {
     set_error("This model selection approach is not supported!");
     return FLGP_ERR_UNSUPPORTED;
   }
-  FLGP_REQUIRE(ep && idx && Y && ts && values, "%s: null pointer", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1 && B >= 1 && ncol >= 1,
-               "%s: bad shape (K=%d of %d, m=%d, max_iter=%d, B=%d, ncol=%d)", who, K, ep->K, m, max_iter, B, ncol);
-  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
-  for (int b = 0; b < B; ++b) {
-    const int c = col ? col[b] : b;
-    FLGP_REQUIRE(c >= 0 && c < ncol, "problem %d (t=%g): %s: col=%d is outside [0, ncol=%d)", b, ts[b], who, c, ncol);
-    FLGP_REQUIRE(std::isfinite(ts[b]), "problem %d (t=%g): %s: t must be finite", b, ts[b], who);
-    FLGP_REQUIRE(!posterior || ts[b] > 0.0, "problem %d (t=%g): %s: t must be positive under \"posterior\"", b, ts[b], who);
-  }
+  return FLGP_OK;
+}
+// sigma, then pr = the caller's prior (p, q, tau) or PostOFData's defaults (src/train.h:138-140)
+int objective_sigma_prior(const char *who, double sigma, const double *prior, double *pr) {
   FLGP_REQUIRE(sigma >= 0.0 && std::isfinite(sigma), "%s: sigma=%g must be finite and >= 0", who, sigma);
-  const double dflt[3] = {1e-2, 10.0, 2.0};                     // PostOFData (src/train.h:138-140)
-  double pr[3];
+  const double dflt[3] = {1e-2, 10.0, 2.0};
   for (int k = 0; k < 3; ++k) pr[k] = prior ? prior[k] : dflt[k];
   FLGP_REQUIRE(all_finite(pr, 3), "%s: prior (p, q, tau) must be finite", who);
-  Rows r;
-  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
-  for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, N, m, who));
+  return FLGP_OK;
+}
+
+// The B checked problems on the checked rows r: problem b is column col[b] of Y (r.m x ncol; col NULL: column b) at ts[b],
+// N NULL is one trial per row (the one-vs-rest route, src/MultiClassification.cpp:36).  A problem that fails is reported
+// as "problem b (t=..): <text>" (by_problem, the batch entry's form) or with the text alone.  values and iters (may be
+// NULL) are written on success only.
+int logit_objectives(const char *who, bool by_problem, const flgp_eigenpair *ep, int K, Rows &r, const double *Y, int ncol,
+                     const double *N, const int *col, const double *ts, int B, double sigma, bool posterior, const double *pr,
+                     double tol, int max_iter, int max_parallel, double *values, int *iters) {
+  const int m = r.m;
   std::vector<double> ones;
   if (!N) { ones.assign((size_t)m, 1.0); N = ones.data(); }
   std::vector<int> cols((size_t)B);
   for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
-  auto name_failure = [&](int b, const std::string &msg) { set_error("problem %d (t=%g): %s", b, ts[b], msg.c_str()); };
+  auto name_failure = [&](int b, const std::string &msg) {
+    if (by_problem) set_error("problem %d (t=%g): %s", b, ts[b], msg.c_str());
+    else set_error("%s", msg.c_str());
+  };
 
   Stream st;
   FLGP_TRY(st.create());
@@ -953,7 +850,7 @@ extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, in
   std::vector<double> amll((size_t)B, 0.0);
   std::vector<int> its((size_t)B, 0);
   if (m <= K) {
-    // the single entry's dense loop per problem, the problems dealt to the pool's workers (worker_pool.h)
+    // the dense loop per problem, the problems dealt to the pool's workers (worker_pool.h); one worker runs on st
     FLGP_TRY(r.resolve(st.s));
     FLGP_HIP(hipStreamSynchronize(st.s));
     DevicePool pool;
@@ -961,11 +858,8 @@ extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, in
     const PoolFailure bad = pool.run<DenseObjWorker>(
         st.s, B, [&](DenseObjWorker &W) { return W.alloc(m, K); },
         [&](hipStream_t ws, DenseObjWorker &W, int b) -> int {
-          const double *y = dY.as<double>() + (size_t)cols[(size_t)b] * m;
-          FLGP_TRY(hk(ws, ep, K, ts[b], r, r, W.C.as<double>(), W.work.as<double>()));      // C = HK(idx, idx) + sigma I
-          if (sigma != 0.0) FLGP_TRY(gpr_add_diag(ws, W.C.as<double>(), m, sigma));
-          FLGP_TRY(W.S.run(ws, W.C.as<double>(), y, dN.as<double>(), tol, max_iter, who, &its[(size_t)b]));
-          return W.S.amll(ws, y, dN.as<double>(), &amll[(size_t)b]);
+          return W.objective(ws, ep, K, ts[b], r, sigma, dY.as<double>() + (size_t)cols[(size_t)b] * m, dN.as<double>(), tol,
+                             max_iter, who, &its[(size_t)b], &amll[(size_t)b]);
         });
     if (bad.item >= 0) { name_failure(bad.item, bad.message); return bad.status; }
   } else {
@@ -973,11 +867,12 @@ extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, in
     DevBuf dcol, dts;
     FLGP_TRY(upload(dcol, cols.data(), sizeof(int) * (size_t)B, st.s));
     FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st.s));
-    // the chunk: max_parallel problems, or (<= 0) all of them; either way no more than fit into 90 % of the free memory
+    // the chunk: max_parallel problems, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of
+    // the free memory
+    const int want = max_parallel > 0 ? max_parallel : B;
     size_t free_b = 0, total_b = 0;
-    FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-    int chunk = plan_workers(max_parallel > 0 ? max_parallel : B, B, (double)free_b, LrBatch::bytes(m, K));
-    chunk = std::min(chunk, GEMM_BATCH_MAX);
+    if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+    const int chunk = std::min(plan_workers(want, B, (double)free_b, LrBatch::bytes(m, K)), GEMM_BATCH_MAX);
     LrBatch L;
     FLGP_TRY(L.alloc(m, K, chunk));
     L.C.Y = dY.as<double>(); L.C.ldy = m; L.C.N = dN.as<double>();
@@ -996,23 +891,68 @@ extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, in
   }
   for (int b = 0; b < B; ++b) {
     const double t = ts[b];
-    if (posterior) {
-      const double p = pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]);   // src/train.cpp:17-24
-      values[b] = -amll[(size_t)b] + p;
-    } else {
-      values[b] = -amll[(size_t)b];
-    }
+    // negative_marginal_likelihood_logit_cpp / negative_log_posterior_logit_cpp (src/train.cpp:14-34)
+    const double p = posterior ? pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]) : 0.0;
+    values[b] = posterior ? -amll[(size_t)b] + p : -amll[(size_t)b];
     if (iters) iters[b] = its[(size_t)b];
   }
   return FLGP_OK;
 }
+}  // namespace
+
+// The single entry is the batch of one: one problem, one chunk of one slot (m > K) or one worker on the entry's stream.
+extern "C" int flgp_eigenpair_logit_objective(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y,
+                                              const double *N, double sigma, const char *approach, const double *prior,
+                                              double t, double tol, int max_iter, double *value, int *iters) {
+  const char *who = "logit_objective";
+  bool posterior = false;
+  double pr[3];
+  FLGP_TRY(objective_approach(who, approach, &posterior));
+  FLGP_REQUIRE(ep && idx && Y && value, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1, "%s: bad shape (K=%d of %d, m=%d, max_iter=%d)", who, K, ep->K,
+               m, max_iter);
+  Rows r;
+  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
+  FLGP_TRY(check_labels(Y, N, m, who));
+  FLGP_REQUIRE(std::isfinite(t), "%s: t=%g must be finite", who, t);
+  FLGP_REQUIRE(!posterior || t > 0.0, "%s: t=%g must be positive under \"posterior\"", who, t);
+  FLGP_TRY(objective_sigma_prior(who, sigma, prior, pr));
+  return logit_objectives(who, false, ep, K, r, Y, 1, N, nullptr, &t, 1, sigma, posterior, pr, tol, max_iter, 1, value, iters);
+}
+
+extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y,
+                                                    int ncol, const double *N, const int *col, const double *ts, int B,
+                                                    double sigma, const char *approach, const double *prior, double tol,
+                                                    int max_iter, int max_parallel, double *values, int *iters) {
+  const char *who = "logit_objective_batch";
+  bool posterior = false;
+  double pr[3];
+  FLGP_TRY(objective_approach(who, approach, &posterior));
+  FLGP_REQUIRE(ep && idx && Y && ts && values, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && max_iter >= 1 && B >= 1 && ncol >= 1,
+               "%s: bad shape (K=%d of %d, m=%d, max_iter=%d, B=%d, ncol=%d)", who, K, ep->K, m, max_iter, B, ncol);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  for (int b = 0; b < B; ++b) {
+    const int c = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "problem %d (t=%g): %s: col=%d is outside [0, ncol=%d)", b, ts[b], who, c, ncol);
+    FLGP_REQUIRE(std::isfinite(ts[b]), "problem %d (t=%g): %s: t must be finite", b, ts[b], who);
+    FLGP_REQUIRE(!posterior || ts[b] > 0.0, "problem %d (t=%g): %s: t must be positive under \"posterior\"", b, ts[b], who);
+  }
+  FLGP_TRY(objective_sigma_prior(who, sigma, prior, pr));
+  Rows r;
+  FLGP_TRY(r.check(ep, idx, m, who, "idx"));
+  for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, N, m, who));
+  return logit_objectives(who, true, ep, K, r, Y, ncol, N, col, ts, B, sigma, posterior, pr, tol, max_iter, max_parallel, values,
+                          iters);
+}
+
 
 // ---- logit posterior for m > K: the mode in weight space, the predictive rows in one pass ----------------
 namespace {
 // Alg. 3.1's step written as a = (I + W C)^-1 b on LowRankB's C, which gives Phi^T a = Q^-1 Phi^T D^-1 b exactly
 // (Phi = V1 L^1/2, D = 1 + sigma W, X = diag(sqrt(W / D)) Phi, Q = I + X^T X).  Per iteration from f = 0, N = 1:
 //   W, b from f; D, xs; Q factored;  beta = Q^-1 L^1/2 V1^T (b / D);  p = V1 L^1/2 beta;  f_new = p + sigma (b - W p) / D.
-// Unlike GpcLowRank's a = b - sW dh (g - X Q^-1 X^T g), whose difference of two nearly equal vectors costs the mean
+// Unlike LrBatch's a = b - sW dh (g - X Q^-1 X^T g), whose difference of two nearly equal vectors costs the mean
 // m lambda / 4 in relative accuracy (harmless for amll, which is stationary at the mode), the one subtraction here is
 // multiplied by sigma.  solve() is also the final step at the mode: beta there gives mean_i = v2_i^T L^1/2 beta.
 struct GpcWeightSpace {
@@ -1050,7 +990,7 @@ struct GpcWeightSpace {
     FLGP_TRY(gpc_ws_fnew(st, b.as<double>(), sW.as<double>(), D.as<double>(), p.as<double>(), L.sigma, m, fnew.as<double>()));
     return gpc_step(st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
   }
-  // the loop from f = 0 with GpcLowRank::run's host protocol (12 bytes read back per iteration)
+  // the loop from f = 0 with GpcNewton::run's host protocol (12 bytes read back per iteration)
   int run(hipStream_t st, const double *dY, double tol, int max_iter, const char *who, int *iters) {
     FLGP_HIP(hipMemsetAsync(f.p, 0, sizeof(double) * (size_t)m, st));
     FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
@@ -1102,6 +1042,38 @@ int predict_rows(hipStream_t st, const flgp_eigenpair *ep, int K, Rows &r1, cons
   }
   return FLGP_OK;
 }
+
+// What the binary entry owns, and what one worker of the one-vs-rest route (m > K) reuses across its classes: the
+// weight-space loop's state, the label column and the scratch of the operand.  Everything in it is overwritten before it
+// is read, so a class's bits do not depend on which worker ran it or on what the worker ran before.
+struct McWorker {
+  GpcWeightSpace S;            // the caller sets L.V1, L.ld1, L.sigma and, per problem, L.l and L.ls
+  DevBuf dY, Li, Tb, wt;
+  size_t wi = 0;
+  int alloc(int m, int K) {
+    wi = (size_t)32 * 64 * K;
+    FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
+    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+    FLGP_TRY(wt.alloc(sizeof(double) * wi));
+    return S.alloc(m, K);
+  }
+  // device bytes of one worker: X, Q, the GEMM workspaces and the operand's scratch; `wide`: predict_rows' two row blocks
+  static double bytes(int m, int K, bool wide) {
+    const double k = K;
+    return 8.0 * ((double)m * k + 2.0 * k * k + (double)vt_work_elems(K, 1) + 10.0 * m + (64.0 + 32.0 * 64.0) * k + 2.0 * k) +
+           (wide ? 2.0 * 256.0 * (1 << 20) : 0.0);
+  }
+  // The mode of the labels in dY, then the weights once more at the final f (as GpcNewton::weights in the dense route) and
+  // the operand Gp = [L_Q^-1 L^1/2 ; (L^1/2 beta)^T]: Li and S.L.u.  The caller reads S.flag when its stream has run.
+  int mode_and_operand(hipStream_t st, double tol, int max_iter, const char *who, int *iters) {
+    const int K = S.L.K;
+    FLGP_TRY(S.run(st, dY.as<double>(), tol, max_iter, who, iters));
+    FLGP_TRY(S.solve(st, dY.as<double>()));
+    FLGP_TRY(S.scaled_beta(st));
+    FLGP_TRY(tri_inverse(st, S.L.Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, S.flag.as<int>()));
+    return gpr_scale(st, Li.as<double>(), nullptr, S.L.ls, K, K, Li.as<double>());                            // L_Q^-1 L^1/2
+  }
+};
 }  // namespace
 
 extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
@@ -1119,25 +1091,17 @@ extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, d
   GprCtx G;
   FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = L^1/2, l = L
   FLGP_TRY(r0.gather(st.s, ep, K));
-  DevBuf dY;
-  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
-  GpcWeightSpace S;
+  McWorker W;
+  GpcWeightSpace &S = W.S;
   S.L.sigma = sigma11; S.L.V1 = r0.V; S.L.ld1 = r0.ld; S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
-  FLGP_TRY(S.alloc(m, K));
+  FLGP_TRY(W.alloc(m, K));
+  FLGP_TRY(h2d(W.dY.p, Y, sizeof(double) * (size_t)m, st.s));
   int it = 0;
-  FLGP_TRY(S.run(st.s, dY.as<double>(), tol, max_iter, who, &it));
+  FLGP_TRY(W.mode_and_operand(st.s, tol, max_iter, who, &it));
   if (iters) *iters = it;
-  // the weights once more at the final f (as GpcNewton::weights in the dense route), then Gp = [L_Q^-1 L^1/2 ; (L^1/2 beta)^T]
-  FLGP_TRY(S.solve(st.s, dY.as<double>()));
-  FLGP_TRY(S.scaled_beta(st.s));
-  DevBuf Li, Tb, wt, dmean, dcov;
-  const size_t wi = (size_t)32 * 64 * K;
-  FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
-  FLGP_TRY(wt.alloc(sizeof(double) * wi));
+  DevBuf dmean, dcov;
   FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dcov.alloc(sizeof(double) * (size_t)mnew));
-  FLGP_TRY(tri_inverse(st.s, S.L.Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, S.flag.as<int>()));
-  FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, G.ls.as<double>(), K, K, Li.as<double>()));            // L_Q^-1 L^1/2
-  FLGP_TRY(predict_rows(st.s, ep, K, r1, Li.as<double>(), S.L.u.as<double>(), sigma22, dmean.as<double>(), dcov.as<double>()));
+  FLGP_TRY(predict_rows(st.s, ep, K, r1, W.Li.as<double>(), S.L.u.as<double>(), sigma22, dmean.as<double>(), dcov.as<double>()));
   FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)mnew, st.s));
   FLGP_TRY(d2h(cov, dcov.p, sizeof(double) * (size_t)mnew, st.s));
   int bad = 0;
@@ -1147,28 +1111,6 @@ extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, d
 
 // ---- one-vs-rest logit posterior: J classes over one pass of the pair ------------------------------------
 namespace {
-// What one worker of the m > K route reuses across its classes: the weight-space loop's state, the label column and the
-// scratch of the operand.  Everything in it is overwritten before it is read, so a class's bits do not depend on which
-// worker ran it or on what the worker ran before.
-struct McWorker {
-  GpcWeightSpace S;
-  DevBuf dY, Li, Tb, wt;
-  size_t wi = 0;
-  int alloc(int m, int K) {
-    wi = (size_t)32 * 64 * K;
-    FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
-    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
-    FLGP_TRY(wt.alloc(sizeof(double) * wi));
-    return S.alloc(m, K);
-  }
-  // device bytes of one worker: X, Q, the GEMM workspaces and the operand's scratch; `wide`: predict_rows' two row blocks
-  static double bytes(int m, int K, bool wide) {
-    const double k = K;
-    return 8.0 * ((double)m * k + 2.0 * k * k + (double)vt_work_elems(K, 1) + 10.0 * m + (64.0 + 32.0 * 64.0) * k + 2.0 * k) +
-           (wide ? 2.0 * 256.0 * (1 << 20) : 0.0);
-  }
-};
-
 // The shared body of the two entries.  nll == nullptr: flgp_eigenpair_logit_posterior_multiclass (mean and cov wanted).
 int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma11, double sigma22, const int *idx0,
                          int m, const double *Y, const int *idx1, int mnew, double tol, int max_iter, int max_parallel,
@@ -1227,12 +1169,7 @@ int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int 
       FLGP_TRY(gpc_class_indicator(ws, dlab.as<double>(), m, j, W.dY.as<double>()));
       GpcWeightSpace &S = W.S;
       S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
-      FLGP_TRY(S.run(ws, W.dY.as<double>(), tol, max_iter, name, &its[(size_t)j]));
-      FLGP_TRY(S.solve(ws, W.dY.as<double>()));
-      FLGP_TRY(S.scaled_beta(ws));
-      FLGP_TRY(tri_inverse(ws, S.L.Q.as<double>(), K, K, W.Li.as<double>(), K, W.Tb.as<double>(), W.wt.as<double>(), W.wi,
-                           S.flag.as<int>()));
-      FLGP_TRY(gpr_scale(ws, W.Li.as<double>(), nullptr, G.ls.as<double>(), K, K, W.Li.as<double>()));            // L_Q^-1 L^1/2
+      FLGP_TRY(W.mode_and_operand(ws, tol, max_iter, name, &its[(size_t)j]));
       if (fused)
         FLGP_TRY(gpc_predict_prep(ws, K, W.Li.as<double>(), S.L.u.as<double>(), Gf.as<double>() + ge * j));
       else

@@ -412,7 +412,7 @@ int GpcNewton::amll(hipStream_t st, const double *dY, const double *dN, double *
   return FLGP_OK;
 }
 
-// ---- the low-rank Newton loop (m > K, C = V1 L V1^T + sigma I; the loop itself is in eigenpair.hip) -------------------
+// ---- the elementwise steps of the weight-space Newton loop (m > K, C = V1 L V1^T + sigma I; GpcWeightSpace, eigenpair.hip)
 
 // W = sW^2: D = 1 + sigma W, dh = D^-1/2, xs = sW dh (the row scaling of X = diag(xs) V1 L^1/2)
 __global__ void gpc_lr_d_kernel(const double *__restrict__ sW, double sigma, int m, double *__restrict__ D,
@@ -421,49 +421,6 @@ __global__ void gpc_lr_d_kernel(const double *__restrict__ sW, double sigma, int
   if (i >= m) return;
   const double s = sW[i], d = 1.0 + sigma * (s * s), h = 1.0 / __builtin_sqrt(d);
   D[i] = d; dh[i] = h; xs[i] = s * h;
-}
-
-// a = b - sW .* r with r = B^-1 (sW .* c) = dh .* (g - Xv), g = dh .* sW .* c, Xv = X Q^-1 X^T g
-__global__ void gpc_lr_a_kernel(const double *__restrict__ b, const double *__restrict__ sW, const double *__restrict__ dh,
-                                const double *__restrict__ g, const double *__restrict__ Xv, int m, double *__restrict__ a) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) a[i] = b[i] - sW[i] * (dh[i] * (g[i] - Xv[i]));
-}
-
-// amll = -0.5 sum(a f) + (sum(Y log pi) + sum((N - Y) log(1 - pi))) - 0.5 sum(log D_i) - sum(log (L_Q)_kk): log det B =
-// log det D + log det Q exactly (no 1e-9 on the pivots: the one departure from gpc_amll_kernel, include/flgp_hip.h)
-__device__ __forceinline__ void gpc_lr_amll_body(const double *__restrict__ f, const double *__restrict__ a,
-                                                 const double *__restrict__ Y, const double *__restrict__ N,
-                                                 const double *__restrict__ D, const double *__restrict__ LQ, int K, int m,
-                                                 double *__restrict__ out) {
-  __shared__ double red[1024];
-  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
-  for (int i = threadIdx.x; i < m; i += 1024) {
-    const double pi = 1.0 / (1.0 + exp(-f[i]));
-    s1 += a[i] * f[i];
-    s2 += Y[i] * log(pi);
-    s3 += (N[i] - Y[i]) * log(1.0 - pi);
-    s4 += log(D[i]);
-  }
-  for (int k = threadIdx.x; k < K; k += 1024) s5 += log(LQ[(size_t)k * K + k]);
-  s1 = block_sum_1024(s1, red);
-  s2 = block_sum_1024(s2, red);
-  s3 = block_sum_1024(s3, red);
-  s4 = block_sum_1024(s4, red);
-  s5 = block_sum_1024(s5, red);
-  if (threadIdx.x == 0) {
-    double amll = -0.5 * s1;
-    amll += s2 + s3;
-    amll -= 0.5 * s4;
-    amll -= s5;
-    out[0] = amll;
-  }
-}
-__global__ __launch_bounds__(1024) void gpc_lr_amll_kernel(const double *__restrict__ f, const double *__restrict__ a,
-                                                           const double *__restrict__ Y, const double *__restrict__ N,
-                                                           const double *__restrict__ D, const double *__restrict__ LQ, int K,
-                                                           int m, double *__restrict__ out) {
-  gpc_lr_amll_body(f, a, Y, N, D, LQ, K, m, out);
 }
 
 int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b) {
@@ -481,22 +438,13 @@ int gpc_lr_dvec(hipStream_t st, const double *d_sW, double sigma, int m, double 
   return check_launch("gpc_lr_d_kernel");
 }
 
-int gpc_lr_a(hipStream_t st, const double *d_b, const double *d_sW, const double *d_dh, const double *d_g, const double *d_Xv,
-             int m, double *d_a) {
-  hipLaunchKernelGGL(gpc_lr_a_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_sW, d_dh, d_g, d_Xv, m, d_a);
-  return check_launch("gpc_lr_a_kernel");
-}
-
-int gpc_lr_amll(hipStream_t st, const double *d_f, const double *d_a, const double *d_Y, const double *d_N, const double *d_D,
-                const double *d_LQ, int K, int m, double *d_out) {
-  hipLaunchKernelGGL(gpc_lr_amll_kernel, dim3(1), dim3(1024), 0, st, d_f, d_a, d_Y, d_N, d_D, d_LQ, K, m, d_out);
-  return check_launch("gpc_lr_amll_kernel");
-}
-
 // ---- the low-rank Newton loop for a chunk of independent problems (the loop is in eigenpair.hip) --------
-// Every kernel above that the single loop launches, with the problem in blockIdx.y: entry q of the device list `act` names
-// the slot whose buffers the workgroups of row q use (LrChunk, common.h).  The expressions are the single kernels' own,
-// operation for operation, so a slot holds the bits the single loop would hold for its problem.
+// The elementwise steps, the K x K factorisation and the final sums of Alg. 3.1 on C = V1 L V1^T + sigma I (LrBatch,
+// eigenpair.hip), with the problem in the grid (blockIdx.y, or blockIdx.x where a workgroup takes a whole problem): entry q
+// of the device list `act` names the slot whose buffers the workgroups of row q use (LrChunk, common.h).  A workgroup reads
+// and writes its own slot only and every sum is in a fixed order, so a slot's bits do not depend on the list.
+
+// the slot's spectrum weights at its t: l = exp(-t (1 - values)), ls = l^1/2
 
 __global__ void lrb_weights_kernel(const double *__restrict__ values, int K, const double *__restrict__ ts, long sk,
                                    double *__restrict__ ls, double *__restrict__ l) {
@@ -504,17 +452,18 @@ __global__ void lrb_weights_kernel(const double *__restrict__ values, int K, con
   if (k >= K) return;
   const long s = blockIdx.y;
   const double t = ts[s];
-  const double lam = 1.0 - values[k];            // gpr_weights_kernel
+  const double lam = 1.0 - values[k];
   ls[s * sk + k] = exp(-0.5 * t * lam) + 0.0;
   l[s * sk + k] = exp(-t * lam);
 }
 
+// pi = logistic(f), W = N pi (1 - pi): sW = W^1/2, b = W f + (Y - N pi), the latter as Y (1 - pi) - (N - Y) pi
 __global__ void lrb_w_kernel(LrChunk c, const int *__restrict__ act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= c.m) return;
   const long s = act[blockIdx.y], o = s * c.sv + i;
   const double fi = c.f[o], yi = c.Y[(size_t)c.ycol[s] * c.ldy + i];
-  const double pi = 1.0 / (1.0 + exp(-fi));      // gpc_w_kernel with N
+  const double pi = 1.0 / (1.0 + exp(-fi));
   const double ni = c.N[i];
   const double W = ni * pi * (1.0 - pi);
   const double bi = W * fi + yi * (1.0 - pi) + (ni - yi) * (-pi);
@@ -522,15 +471,16 @@ __global__ void lrb_w_kernel(LrChunk c, const int *__restrict__ act) {
   c.b[o] = bi;
 }
 
+// W = sW^2: D = 1 + sigma W, dh = D^-1/2, xs = sW dh (the row scaling of X)
 __global__ void lrb_d_kernel(LrChunk c, const int *__restrict__ act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= c.m) return;
   const long o = (long)act[blockIdx.y] * c.sv + i;
-  const double s = c.sW[o], d = 1.0 + c.sigma * (s * s), h = 1.0 / __builtin_sqrt(d);   // gpc_lr_d_kernel
+  const double s = c.sW[o], d = 1.0 + c.sigma * (s * s), h = 1.0 / __builtin_sqrt(d);
   c.D[o] = d; c.dh[o] = h; c.xs[o] = s * h;
 }
 
-// X = diag(xs) V1 diag(ls)   (gpc_scale2_kernel)
+// X = diag(xs) V1 diag(ls)
 __global__ void lrb_scale2_kernel(LrChunk c, const int *__restrict__ act) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (long)c.m * c.K) return;
@@ -539,13 +489,13 @@ __global__ void lrb_scale2_kernel(LrChunk c, const int *__restrict__ act) {
   c.X[s * c.sx + e] = c.xs[s * c.sv + i] * c.V1[(size_t)j * c.ld1 + i] * c.ls[s * c.sk + j];
 }
 
-// Q(i, i) += 1   (gpr_add_diag_kernel)
+// Q(i, i) += 1
 __global__ void lrb_add_diag_kernel(LrChunk c, const int *__restrict__ act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < c.K) c.Q[(long)act[blockIdx.y] * c.sq + (size_t)i * c.K + i] += 1.0;
 }
 
-// out = a .* x   (pg_mul_kernel without its third factor); a stride of 0 shares the vector
+// out = a .* x; a stride of 0 shares the vector
 __global__ void lrb_mul_kernel(int n, const double *__restrict__ a, long sa, const double *__restrict__ x, long sx,
                                double *__restrict__ out, long so, const int *__restrict__ act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -554,7 +504,7 @@ __global__ void lrb_mul_kernel(int n, const double *__restrict__ a, long sa, con
   out[s * so + i] = a[s * sa + i] * x[s * sx + i];
 }
 
-// out = x + c z   (pg_axpy3_kernel with x and z)
+// out = x + c z
 __global__ void lrb_axpy_kernel(int n, const double *__restrict__ x, long sx, double c, const double *__restrict__ z, long sz,
                                 double *__restrict__ out, long so, const int *__restrict__ act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -565,14 +515,15 @@ __global__ void lrb_axpy_kernel(int n, const double *__restrict__ x, long sx, do
   out[s * so + i] = v;
 }
 
+// a = b - sW .* r with r = B^-1 (sW .* c) = dh .* (g - Xv), g = dh .* sW .* c, Xv = X Q^-1 X^T g
 __global__ void lrb_a_kernel(LrChunk c, const int *__restrict__ act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= c.m) return;
   const long o = (long)act[blockIdx.y] * c.sv + i;
-  c.a[o] = c.b[o] - c.sW[o] * (c.dh[o] * (c.g[o] - c.Xv[o]));      // gpc_lr_a_kernel
+  c.a[o] = c.b[o] - c.sW[o] * (c.dh[o] * (c.g[o] - c.Xv[o]));
 }
 
-// gpc_step_kernel, one workgroup per problem: diff[q] = |f - f_new|_1, f <- f_new, and behind the A norms the A pivot
+// One workgroup per problem: stat[q] = |f - f_new|_1 in a fixed order, f <- f_new, and behind the A norms the A pivot
 // flags of the same problems, so that the host reads both in one copy
 __global__ __launch_bounds__(1024) void lrb_step_kernel(LrChunk c, const int *__restrict__ act, int A, double *__restrict__ stat) {
   __shared__ double red[1024];
@@ -592,6 +543,7 @@ __global__ __launch_bounds__(1024) void lrb_step_kernel(LrChunk c, const int *__
   }
 }
 
+// the panel and the row-block steps of chol_blocked on the slot's Q
 __global__ __launch_bounds__(64) void lrb_chol_panel_kernel(LrChunk c, const int *__restrict__ act, int k0) {
   const long s = act[blockIdx.x];
   chol_panel_body(c.Q + s * c.sq, c.K, c.K, k0, c.flag + s);
@@ -605,11 +557,37 @@ __global__ __launch_bounds__(256) void lrb_trsv_kernel(LrChunk c, const int *__r
   const long s = act[blockIdx.x];
   chol_trsv_body(c.Q + s * c.sq, c.K, c.K, c.u + s * c.sk, 3, c.flag + s);
 }
-// the final sums of every slot of the chunk (no list: a problem that left the loop kept its f, a, D and L_Q)
+// The final sums of every slot of the chunk (no list: a problem that left the loop kept its f, a, D and L_Q), one workgroup
+// per slot: amll = -0.5 sum(a f) + (sum(Y log pi) + sum((N - Y) log(1 - pi))) - 0.5 sum(log D_i) - sum(log (L_Q)_kk).
+// log det B = log det D + log det Q exactly (no 1e-9 on the pivots: the one departure from gpc_amll_kernel,
+// include/flgp_hip.h).
 __global__ __launch_bounds__(1024) void lrb_amll_kernel(LrChunk c) {
+  __shared__ double red[1024];
   const long s = blockIdx.x;
-  gpc_lr_amll_body(c.f + s * c.sv, c.a + s * c.sv, c.Y + (size_t)c.ycol[s] * c.ldy, c.N, c.D + s * c.sv, c.Q + s * c.sq, c.K,
-                   c.m, c.amll + s);
+  const double *__restrict__ f = c.f + s * c.sv, *__restrict__ a = c.a + s * c.sv, *__restrict__ D = c.D + s * c.sv;
+  const double *__restrict__ Y = c.Y + (size_t)c.ycol[s] * c.ldy, *__restrict__ N = c.N, *__restrict__ LQ = c.Q + s * c.sq;
+  const int K = c.K;
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
+  for (int i = threadIdx.x; i < c.m; i += 1024) {
+    const double pi = 1.0 / (1.0 + exp(-f[i]));
+    s1 += a[i] * f[i];
+    s2 += Y[i] * log(pi);
+    s3 += (N[i] - Y[i]) * log(1.0 - pi);
+    s4 += log(D[i]);
+  }
+  for (int k = threadIdx.x; k < K; k += 1024) s5 += log(LQ[(size_t)k * K + k]);
+  s1 = block_sum_1024(s1, red);
+  s2 = block_sum_1024(s2, red);
+  s3 = block_sum_1024(s3, red);
+  s4 = block_sum_1024(s4, red);
+  s5 = block_sum_1024(s5, red);
+  if (threadIdx.x == 0) {
+    double amll = -0.5 * s1;
+    amll += s2 + s3;
+    amll -= 0.5 * s4;
+    amll -= s5;
+    c.amll[s] = amll;
+  }
 }
 
 int lrb_weights(hipStream_t st, const double *d_values, int K, const double *d_ts, int slots, long sk, double *d_ls, double *d_l) {
@@ -649,7 +627,7 @@ int lrb_step(hipStream_t st, const LrChunk &c, const int *act, int A, double *d_
   hipLaunchKernelGGL(lrb_step_kernel, dim3(A), dim3(1024), 0, st, c, act, A, d_stat);
   return check_launch("lrb_step_kernel");
 }
-// chol_blocked on the Q of every listed slot: its panels in its order, one launch per step whatever A is
+// Q = L_Q L_Q^T in place for every listed slot: chol_blocked's panels in its order, one launch per step whatever A is
 int lrb_chol(hipStream_t st, const LrChunk &c, const int *act, int A) {
   ProfScope ps("chol_blocked_batch", st, (double)A * c.K * c.K * c.K / 3.0);
   const int m = c.K;

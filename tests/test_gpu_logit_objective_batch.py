@@ -1,21 +1,24 @@
 """GPU: the logit training objective for B problems in one call (flgp_eigenpair_logit_objective_batch).
 The single entry flgp_eigenpair_logit_objective is the reference and the contract is equality of bits: every value and
 every iteration count of a batch is what the single entry returns for that column at that t -- for any B, any order, any
-chunk size and whichever other problems share the call.  No tolerance appears anywhere in this file."""
+chunk size and whichever other problems share the call.  The single entry is now the batch of one, so that reference
+shares the batch's code: what it shows here is that a problem's bits do not depend on its company.  The independent
+reference is the pinned bits of the loop the single entry ran before (tests/golden/logit_objective_bits.npz), which
+test_gpu_logit_objective_bits.py holds both entries to on the shapes and configurations of this file.  No tolerance
+appears anywhere in this file."""
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 
-from flgp_amd import _lib, api
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from flgp_amd import _lib  # noqa: E402
+from logit_objective_cases import (LOWRANK_SHAPES, N_COLS, N_ROWS, PRIOR, TS, responses, rows,  # noqa: E402
+                                   synthetic_pair)
 
 pytestmark = pytest.mark.gpu
-
-N_ROWS, N_COLS = 3000, 240
-TS = (0.3, 1.0, 4.0, 20.0)
-PRIOR = (0.5, 3.0, 1.5)
-LOWRANK_SHAPES = [(64, 65), (65, 300), (200, 201), (200, 1000)]     # (K, m): one row above K, K off the 64-column panel,
-#                                                                     one and four Cholesky panels
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -27,13 +30,6 @@ def torch_first():
     torch.cuda.init()
 
 
-def synthetic_pair(n, K, seed):
-    rng = np.random.default_rng(seed)
-    values = np.sort(rng.uniform(0.4, 1.0, K))[::-1].copy()
-    V = np.asfortranarray(rng.standard_normal((n, K)))
-    return api.EigenPair(values, V), api.ResidentEigenPair.from_host(api.EigenPair(values, V))
-
-
 @pytest.fixture(scope="module")
 def pair(torch_first):
     _, rp = synthetic_pair(N_ROWS, N_COLS, seed=21)
@@ -41,31 +37,8 @@ def pair(torch_first):
     rp.free()
 
 
-def rows(n, m, kind, seed):
-    rng = np.random.default_rng(seed)
-    if kind == "perm":
-        return rng.permutation(n)[:m]
-    idx = rng.integers(0, n, m)                                  # repeated rows
-    idx[m // 2:] = idx[: m - m // 2]
-    return idx
-
-
-def responses(m, seed, singleton=True):
-    """Y (m x 6): the one-vs-rest indicators of five classes (class 4 with a single member when the rows allow it), then a
-    binomial column for N in 1..5 -- under that N the indicator columns are valid responses too."""
-    rng = np.random.default_rng(seed)
-    labels = rng.integers(0, 4 if singleton and m >= 5 else 5, m)
-    if singleton and m >= 5:
-        labels[rng.integers(0, m)] = 4
-    N = rng.integers(1, 6, m).astype(np.float64)
-    Y = np.zeros((m, 6), order="F")
-    Y[:, :5] = labels[:, None] == np.arange(5)[None, :]
-    Y[:, 5] = rng.binomial(N.astype(int), 0.35)
-    return labels, Y, N
-
-
 class Single:
-    """The reference: single calls of the existing entry, each (column, t) of a configuration made once."""
+    """The reference: single calls (batches of one), each (column, t) of a configuration made once."""
 
     def __init__(self, rp, K, idx, Y, N, sigma, approach, prior, max_iter=100):
         self.rp, self.K, self.idx, self.Y, self.N = rp, K, idx, Y, N
