@@ -163,6 +163,10 @@ _SIGNATURES = {
     "flgp_dev_spectrum_usable": (c_int, [P, P, c_int]),
     "flgp_dev_spectrum_usable_route": (c_int, [P, P, c_int, c_int]),
     "flgp_dev_u_recover": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, c_int, P, c_int, P, P]),
+    "flgp_dev_hk_rows_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "flgp_dev_hk_rows_route": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "flgp_dev_hk_rows": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, P, c_double, P, c_int, c_int,
+                                 P, c_int, P]),
     "flgp_dev_hk": (c_int, [P, P, c_int, c_double, P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int,
                             P, c_int, P]),
     "flgp_dev_cholesky": (c_int, [P, P, c_int, c_int, P]),

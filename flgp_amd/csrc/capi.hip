@@ -279,9 +279,12 @@ int csr_out(Sim &S, hipStream_t st, int *csr_p, int *csr_j, double *csr_x) {
 struct Spectrum {
   DevBuf G, rec, eig, V, values, vectors, work, uwork;     // values / vectors: the caller's where it has set (borrowed) them
   int K = 0;
+  int vec_rows = 0;     // rows of `vectors` (its leading dimension): S.n, or the caller's row limit
 };
 
-int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info) {
+// row_limit >= 0: only the first row_limit local rows of the vectors are recovered (a caller that takes H from the sparse
+// rows needs the training rows it owns and nothing else: no n x K store)
+int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info, int row_limit = -1) {
   if (K < 0) K = S.s;   // reference: K < 0 -> s (src/Spectrum.cpp:31-33,69-71; src/TruncatedSVD.cpp:11-13)
   FLGP_REQUIRE(K >= 1 && K <= S.s, "need 1 <= K <= s (K=%d, s=%d)", K, S.s);
   P.K = K;
@@ -323,11 +326,12 @@ int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info) {
   FLGP_TRY(flgp_dev_spectrum_usable_route(st, P.eig.as<double>(), K, solve_info[2]));
   // u = A v / sigma, vectors = u sqrt(n), values = sigma^2 (or sigma if root)  (:153-158)
   if (!P.values.p) FLGP_TRY(P.values.alloc(sizeof(double) * (size_t)K));
-  if (!P.vectors.p) FLGP_TRY(P.vectors.alloc(sizeof(double) * (size_t)S.n * K));
+  P.vec_rows = row_limit >= 0 && row_limit < S.n ? row_limit : S.n;
+  if (!P.vectors.p) FLGP_TRY(P.vectors.alloc(sizeof(double) * (size_t)std::max(P.vec_rows, 1) * K));
   FLGP_TRY(P.uwork.alloc(flgp_dev_u_recover_workspace(S.s, K)));
-  return flgp_dev_u_recover(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.r, P.V.as<double>(), S.s, S.s,
+  return flgp_dev_u_recover(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), P.vec_rows, S.r, P.V.as<double>(), S.s, S.s,
                             P.eig.as<double>(), K, std::sqrt((double)(S.n_global ? S.n_global : (long)S.n)), root,
-                            P.vectors.as<double>(), S.n, P.values.as<double>(), P.uwork.as<double>());
+                            P.vectors.as<double>(), std::max(P.vec_rows, 1), P.values.as<double>(), P.uwork.as<double>());
 }
 
 int parse_kernel(const char *kernel, int *se) {
@@ -1013,21 +1017,35 @@ extern "C" int flgp_dev_heat_kernel_covariance_sharded(void *stream, const flgp_
   FLGP_TRY(anchor_panel(st, dU, s, ldu, d, S.Ut, S.uu));
   S.want_csc = true;
   FLGP_TRY(cross_similarity(S, st, r, se, glc, epsilon, d));
+  // H from the sparse rows (flgp_dev_hk_rows) where its route rule says so.  It needs no row of V beyond the training block,
+  // so a caller that does not ask for the vectors has only the training rows this rank owns recovered (the same bits as in the
+  // whole recovery: every U-recovery kernel delivers the same).
+  const int hk_rows = flgp_dev_hk_rows_route(n_loc, r, s, K, m);
+  const long own = row_lo < m ? std::min<long>(row_lo + n_loc, (long)m) - row_lo : 0;     // training rows of this rank
   Spectrum P;
-  FLGP_TRY(spectrum(S, st, K, root, P, info));
+  FLGP_TRY(spectrum(S, st, K, root, P, info, hk_rows && !d_vectors_out ? (int)own : -1));
   // exchange 4: the training block V[0:m] (m x K), zero where this rank owns no row of it, summed over the ranks
   DevBuf V1, work;
   FLGP_TRY(V1.alloc(sizeof(double) * (size_t)m * K));
   FLGP_HIP(hipMemsetAsync(V1.p, 0, sizeof(double) * (size_t)m * K, st));
-  if (row_lo < m) {
-    const long cnt = std::min<long>(row_lo + n_loc, (long)m) - row_lo;
-    FLGP_HIP(hipMemcpy2DAsync(V1.as<double>() + row_lo, sizeof(double) * (size_t)m, P.vectors.p, sizeof(double) * (size_t)n_loc,
-                              sizeof(double) * (size_t)cnt, K, hipMemcpyDeviceToDevice, st));
-  }
+  if (own > 0)
+    FLGP_HIP(hipMemcpy2DAsync(V1.as<double>() + row_lo, sizeof(double) * (size_t)m, P.vectors.p, sizeof(double) * (size_t)P.vec_rows,
+                              sizeof(double) * (size_t)own, K, hipMemcpyDeviceToDevice, st));
   FLGP_TRY(flgp_comm_all_reduce_sum(comm, V1.as<double>(), (size_t)m * K, st));
-  FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n_loc, m, K, 0)));
-  FLGP_TRY(flgp_dev_hk(st, P.values.as<double>(), K, t, P.vectors.as<double>(), n_loc, nullptr, 0, n_loc, V1.as<double>(), m, nullptr, 0,
-                       m, dH_loc, ldh, work.as<double>()));
+  if (hk_rows) {
+    // V1 is all-reduced and the anchor-side pair (P.V, P.eig, P.values) is replicated, so Wm = Vs diag(scale / sigma) Vw^T has the
+    // same bits on every rank, and a row of H depends on its own row of A and on Wm alone: H of N ranks is bit for bit H of one
+    // (as long as every rank takes this route: a rank with fewer than 10000 rows keeps the contraction, and its rows of H
+    // then differ from the one-rank H in their last bits).
+    FLGP_TRY(work.alloc(flgp_dev_hk_rows_workspace(s, m, K)));
+    FLGP_TRY(flgp_dev_hk_rows(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), n_loc, S.r, P.V.as<double>(), s, s, P.eig.as<double>(), K,
+                              std::sqrt((double)n_global), P.values.as<double>(), t, V1.as<double>(), m, m, dH_loc, ldh,
+                              work.as<double>()));
+  } else {
+    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n_loc, m, K, 0)));
+    FLGP_TRY(flgp_dev_hk(st, P.values.as<double>(), K, t, P.vectors.as<double>(), n_loc, nullptr, 0, n_loc, V1.as<double>(), m, nullptr,
+                         0, m, dH_loc, ldh, work.as<double>()));
+  }
   if (d_values_out) FLGP_HIP(hipMemcpyAsync(d_values_out, P.values.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, st));
   if (d_vectors_out)
     FLGP_HIP(hipMemcpy2DAsync(d_vectors_out, sizeof(double) * (size_t)ldv, P.vectors.p, sizeof(double) * (size_t)n_loc,

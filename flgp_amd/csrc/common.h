@@ -233,6 +233,9 @@ struct GemmFusedReduce {
 bool hk_panel_applicable(int n0, int n1, int K, long ldh);
 bool hk_panel2_applicable(int n0, int n1, int K, long ldh);    // hk2.hip: the same with the k loop unrolled (K in 97..112, 193..208)
 size_t hk_panel_vw_elems(int n1, int K);
+// Vw(b, k) = exp(-t (1 - values_k)) V1(row(b), k), b-contiguous: d_vw[b + k n1] (gemm.hip; row(b) = d_idx1[b] or row0_1 + b)
+int hk_scale_launch(hipStream_t st, const double *d_values, int K, double t, const double *dV1, int ld1, const int *d_idx1,
+                    int row0_1, int n1, double *d_vw);
 int hk_panel2_launch(hipStream_t st, const double *d_values, int K, double t, const double *V0, long ld0, int n0,
                      const double *dV1, int ld1, const int *d_idx1, int row0_1, int n1, double *dH, long ldh,
                      double *d_vw);

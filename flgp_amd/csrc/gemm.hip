@@ -715,6 +715,13 @@ __global__ void hk_scale_kernel(const double *__restrict__ values, int K, double
   Vw[e] = V1[(size_t)k * ld1 + row] * w;
 }
 
+int hk_scale_launch(hipStream_t st, const double *d_values, int K, double t, const double *dV1, int ld1, const int *d_idx1,
+                    int row0_1, int n1, double *d_vw) {
+  hipLaunchKernelGGL(hk_scale_kernel, dim3(ceil_div((long)n1 * K, 256)), dim3(256), 0, st, d_values, K, t, dV1, ld1,
+                     d_idx1, row0_1, n1, d_vw);
+  return check_launch("hk_scale_kernel");
+}
+
 // out: n0 x K column-major with leading dimension ldo (>= n0: the top rows of a taller matrix)
 __global__ void gather_rows_kernel(const double *__restrict__ V, int ld, const int *__restrict__ idx, int n0, int K,
                                    double *__restrict__ out, int ldo) {
@@ -837,9 +844,7 @@ extern "C" int flgp_dev_hk(void *stream, const double *d_values, int K, double t
     return hk_panel2_launch(st, d_values, K, t, V0, v0_ld, n0, dV1, ld1, d_idx1, row0_1, n1, dH, ldh, Vw);
   if (hk_panel_applicable(n0, n1, K, ldh))
     return hk_panel_launch(st, d_values, K, t, V0, v0_ld, n0, dV1, ld1, d_idx1, row0_1, n1, dH, ldh, Vw);
-  hipLaunchKernelGGL(hk_scale_kernel, dim3(ceil_div((long)n1 * K, 256)), dim3(256), 0, st, d_values, K, t, dV1, ld1,
-                     d_idx1, row0_1, n1, Vw);
-  FLGP_TRY(check_launch("hk_scale_kernel"));
+  FLGP_TRY(hk_scale_launch(st, d_values, K, t, dV1, ld1, d_idx1, row0_1, n1, Vw));
   // H(a,b) = sum_k V0(a,k) Vw(b,k)
   return gemm_launch(st, n0, n1, K, 1.0, V0, 1, v0_ld, Vw, n1, 1, 0.0, nullptr, 0, 0, dH, 1, ldh, nullptr, 0, 0.0,
                      nullptr);

@@ -638,6 +638,9 @@ __global__ __launch_bounds__(256) void u_recover_wide_kernel(const int *__restri
 #define U_RECOVER_LDS_MIN_N 10000
 #endif
 constexpr int U_LDS_BYTES = 163840;
+// flgp_dev_hk_rows_route: the K W / r from which the heat-kernel rows take over from the MFMA contraction -- against
+// hk_panel2_kernel (m >= 480) and against hk_panel_kernel (100 <= m < 480; no smaller m was measured)
+constexpr int HK_ROWS_MIN_KW_PER_R = 60, HK_ROWS_MIN_KW_PER_R_SMALL_M = 40, HK_ROWS_PANEL2_M = 480, HK_ROWS_MIN_M = 100;
 
 // eigen-columns per slice: min(4, floor(163840 / (8 s))); 0 = not even one column fits
 static int u_lds_width(int s) {
@@ -664,7 +667,9 @@ __global__ __launch_bounds__(256) void transpose_v_slices_kernel(const double *_
 template <int W> __device__ __forceinline__ int u_lds_slot(int q) { return W == 4 ? q ^ (((q >> 5) & 1) << 1) : q; }
 
 // NP: pairs of entries per step (u_lds_pairs below: the fewest equal steps of at most six pairs that cover a row).
-template <int W, int NP>
+// RAW: the sums are stored as they are, out(i, k) = sum_a val(i, a) M(idx(i, a), k), and eig / scale are not read (the heat-kernel
+// rows of flgp_dev_hk_rows, where M is the s x m matrix Wm and the scaling is already inside it).
+template <int W, int NP, bool RAW>
 __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(const int *__restrict__ ell_idx,
                                                                               const double *__restrict__ val, int n, int r, int s,
                                                                               const double *__restrict__ Vts,
@@ -681,7 +686,7 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
 #pragma unroll
   for (int c = 0; c < W; ++c) {
     const int k = sl * W + c;
-    const double e = k < K ? eig[k] : 0.0;
+    const double e = (!RAW && k < K) ? eig[k] : 0.0;
     sg[c] = __builtin_sqrt(e > 0.0 ? e : 0.0);
   }
   __syncthreads();
@@ -768,7 +773,7 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
 #pragma unroll
         for (int c = 0; c < W; ++c) {
           const int k = sl * W + c;
-          if (k < K) out[(size_t)k * ldo + i] = sg[c] > 0.0 ? (acc[c] / sg[c]) * scale : 0.0;
+          if (k < K) out[(size_t)k * ldo + i] = RAW ? acc[c] : sg[c] > 0.0 ? (acc[c] / sg[c]) * scale : 0.0;
         }
       }
 #pragma unroll
@@ -797,6 +802,19 @@ __global__ void values_out_kernel(const double *__restrict__ eig, int K, int roo
   if (k >= K) return;
   const double ev = eig[k] > 0.0 ? eig[k] : 0.0;
   values[k] = root ? __builtin_sqrt(ev) : ev;   // values = d^2 (src/TruncatedSVD.cpp:29), sqrt if root (src/Spectrum.cpp:153-155)
+}
+
+// B(j, k) = Vs(j, k) q_k with q_k = scale / sigma_k, sigma_k = sqrt(max(eig_k, 0)), and q_k = 0 where sigma_k = 0 (the zero
+// column of U-recovery); B is s x K column-major with leading dimension s
+__global__ void hk_rows_b_kernel(const double *__restrict__ Vs, int ldv, int s, const double *__restrict__ eig, int K,
+                                 double scale, double *__restrict__ B) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)s * K) return;
+  const int j = (int)(e % s), k = (int)(e / s);
+  const double ev = eig[k];
+  const double sigma = __builtin_sqrt(ev > 0.0 ? ev : 0.0);
+  const double q = sigma > 0.0 ? scale / sigma : 0.0;
+  B[e] = Vs[(size_t)k * ldv + j] * q;
 }
 
 struct CscPlan {
@@ -1089,7 +1107,7 @@ static int u_lds_pairs(int r) {
   return ceil_div(pairs, steps);
 }
 
-template <int W, int NP>
+template <int W, int NP, bool RAW>
 static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
                                 int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
                                 double *d_work) {
@@ -1103,22 +1121,36 @@ static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const doub
   ranges = ceil_div(n, rows);
   const size_t lds = sizeof(double) * (size_t)s * W;
   if (lds > 48 * 1024)
-    FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((u_recover_lds_kernel<W, NP>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st, d_ell_idx, d_ell_val,
+    FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W, NP, RAW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((u_recover_lds_kernel<W, NP, RAW>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st, d_ell_idx, d_ell_val,
                      n, r, s, d_work, d_eig, K, scale, d_vectors, ldo, rows);
   return FLGP_OK;
 }
 
-template <int W>
+template <int W, bool RAW>
 static int u_recover_lds_pairs(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
                                int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
                                double *d_work) {
   switch (u_lds_pairs(r)) {
 #define U_LDS_PAIRS(NPv)                                                                                                       \
-  case NPv: return u_recover_lds_launch<W, NPv>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)
+  case NPv: return u_recover_lds_launch<W, NPv, RAW>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)
     U_LDS_PAIRS(1); U_LDS_PAIRS(2); U_LDS_PAIRS(3); U_LDS_PAIRS(4); U_LDS_PAIRS(5);
     default: U_LDS_PAIRS(6);
 #undef U_LDS_PAIRS
+  }
+}
+
+// the slice image of dV (s x K, ld = ldv) into d_work, then the LDS row kernel at the slice width of s
+template <bool RAW>
+static int u_recover_lds_width(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
+                               int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
+                               double *d_work) {
+  switch (u_lds_width(s)) {
+#define U_LDS_CASE(Wv)                                                                                                         \
+  case Wv: return u_recover_lds_pairs<Wv, RAW>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)
+    U_LDS_CASE(1); U_LDS_CASE(2); U_LDS_CASE(3);
+    default: U_LDS_CASE(4);
+#undef U_LDS_CASE
   }
 }
 
@@ -1131,13 +1163,7 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
     ProfScope ps("u_recover_kernel", st, 12.0 * (double)n * r + 8.0 * (double)s * K + 8.0 * (double)n * K);
     const int route = flgp_dev_u_recover_route(n, r, s, K, d_work != nullptr);
     if (route == 4) {
-      switch (u_lds_width(s)) {
-#define U_LDS_CASE(Wv)                                                                                                         \
-  case Wv: FLGP_TRY(u_recover_lds_pairs<Wv>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)); break
-        U_LDS_CASE(1); U_LDS_CASE(2); U_LDS_CASE(3);
-        default: U_LDS_CASE(4);
-#undef U_LDS_CASE
-      }
+      FLGP_TRY(u_recover_lds_width<false>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work));
     } else if (d_work) {
       hipLaunchKernelGGL(transpose_v_kernel, dim3(ceil_div(s, 32), ceil_div(K, 32)), dim3(256), 0, st, dV, ldv, s, K,
                          d_work);
@@ -1162,4 +1188,64 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
     FLGP_TRY(check_launch("values_out_kernel"));
   }
   return FLGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------
+// Heat-kernel covariance from the sparse rows.  On the covariance path every row of V is a combination of r anchor rows,
+//   V(i, k) = ((sum_a A(i, a) Vs(idx(i, a), k)) / sigma_k) scale,
+// so H(i, b) = sum_k V(i, k) e^{-t (1 - lambda_k)} V1(b, k) = sum_a A(i, a) Wm(idx(i, a), b) with the s x m matrix
+//   Wm = B Vw^T,  B = Vs diag(scale / sigma_k),  Vw(b, k) = e^{-t (1 - lambda_k)} V1(b, k):
+// 2 n r m + 2 s m K flop instead of 2 n m K, and H is the LDS row kernel of U-recovery applied to Wm with K := m (its output
+// layout is H's).  Workspace, in doubles: B (s K) | Vw (m K) | Wm (s m) | the slice image of Wm, each part on a 256-byte edge.
+// ----------------------------------------------------------------------------------------
+namespace {
+struct HkRowsLayout { size_t b, vw, wm, image, total; };
+HkRowsLayout hk_rows_layout(int s, int m, int K) {
+  auto up = [](size_t e) { return (e + 31) / 32 * 32; };
+  const int w = u_lds_width(s);
+  const size_t S = s > 0 ? s : 0, M = m > 0 ? m : 0, Kk = K > 0 ? K : 0;
+  HkRowsLayout L;
+  L.b = 0;
+  L.vw = L.b + up(S * Kk);
+  L.wm = L.vw + up(M * Kk);
+  L.image = L.wm + up(S * M);
+  L.total = L.image + up(S * (w >= 1 ? (size_t)ceil_div(M, w) * w : M));
+  return L;
+}
+}  // namespace
+
+extern "C" size_t flgp_dev_hk_rows_workspace(int s, int m, int K) { return sizeof(double) * hk_rows_layout(s, m, K).total + 256; }
+
+// 1: flgp_dev_hk_rows computes H; 0: the caller keeps flgp_dev_u_recover + flgp_dev_hk.  The row kernel needs what the LDS
+// kernel of U-recovery needs; beyond that the MFMA contraction costs ~ n m K and the rows ~ n r ceil(m / W) (W columns per
+// slice), so the rows win from some K W / r on.  Measured at r = 10, n = 1e5 and 1e6 (profiles/r08_hk_rows_crossover.json,
+// rows / MFMA at the call alone): m = 1000: 0.71-0.79 at K W / r = 80, 1.26-1.36 at 40, 1.6-3.0 below; m = 100 (the
+// contraction is hk_panel_kernel there): 0.45-0.56 at 80, 0.69-0.86 at 40, 0.86-1.26 at 20.
+// Tuning knob hk_rows: 0 never, 1 (default) by this rule, 2 wherever the row kernel applies.
+extern "C" int flgp_dev_hk_rows_route(int n, int r, int s, int K, int m) {
+  const int knob = tuning("hk_rows", 1);
+  const int w = u_lds_width(s);
+  if (!knob || w < 1 || n < U_RECOVER_LDS_MIN_N || (long)n * r < 2 || r < 1 || r > FLGP_RMAX || K < 1 || m < 1) return 0;
+  if (knob == 2) return 1;
+  if (m < HK_ROWS_MIN_M) return 0;
+  return (long)K * w >= (m >= HK_ROWS_PANEL2_M ? HK_ROWS_MIN_KW_PER_R : HK_ROWS_MIN_KW_PER_R_SMALL_M) * (long)r;
+}
+
+extern "C" int flgp_dev_hk_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dVs,
+                                int ldv, int s, const double *d_eig, int K, double scale, const double *d_values, double t,
+                                const double *dV1, int ld1, int m, double *dH, int ldh, double *d_work) {
+  hipStream_t st = (hipStream_t)stream;
+  FLGP_REQUIRE(d_ell_idx && d_ell_val && dVs && d_eig && d_values && dV1 && dH && d_work, "hk_rows: null pointer");
+  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && K >= 1 && m >= 1 && s >= 1 && ldv >= s && ld1 >= m && ldh >= n, "hk_rows: bad shape");
+  FLGP_REQUIRE(u_lds_width(s) >= 1 && n >= U_RECOVER_LDS_MIN_N && (long)n * r >= 2,
+               "hk_rows: no LDS slice for n=%d r=%d s=%d (ask flgp_dev_hk_rows_route)", n, r, s);
+  const HkRowsLayout L = hk_rows_layout(s, m, K);
+  double *B = d_work + L.b, *Vw = d_work + L.vw, *Wm = d_work + L.wm, *image = d_work + L.image;
+  hipLaunchKernelGGL(hk_rows_b_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, dVs, ldv, s, d_eig, K, scale, B);
+  FLGP_TRY(check_launch("hk_rows_b_kernel"));
+  FLGP_TRY(hk_scale_launch(st, d_values, K, t, dV1, ld1, nullptr, 0, m, Vw));
+  // Wm(j, b) = sum_k B(j, k) Vw(b, k): no workspace, so one k-ascending MFMA chain per element (never split)
+  FLGP_TRY(gemm_launch(st, s, m, K, 1.0, B, 1, s, Vw, m, 1, 0.0, nullptr, 0, 0, Wm, 1, s, nullptr, 0, 0.0, nullptr));
+  ProfScope ps("hk_rows_kernel", st, 2.0 * (double)n * r * m);     // (with the slice image of Wm: 16 s m bytes)
+  return u_recover_lds_width<true>(st, d_ell_idx, d_ell_val, n, r, Wm, s, s, nullptr, m, 1.0, dH, ldh, image);
 }

@@ -187,6 +187,22 @@ class HipStages:
                                       V1.data_ptr(), n1, None, 0, n1, H.data_ptr(), n0, work.data_ptr()))
         return H
 
+    def hk_rows_route(self, n, r, s, K, m):
+        """Does hk_rows compute H for this shape (flgp_dev_hk_rows_route)?  Otherwise the caller keeps u_recover + hk."""
+        return bool(self.L.flgp_dev_hk_rows_route(n, r, s, K, m))
+
+    def hk_rows(self, ell_idx, ell_val, V, eig, scale, values, t, V1):
+        """H (m, n) from the sparse rows: H = A (Vs diag(scale / sigma) Vw^T), without the n x K vectors."""
+        n, r = ell_idx.shape
+        K, s = V.shape
+        m = V1.shape[1]
+        H = self.empty((m, n))
+        work = self.empty((self.L.flgp_dev_hk_rows_workspace(s, m, K) // 8 + 1,))
+        _lib.check(self.L.flgp_dev_hk_rows(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, r, V.data_ptr(), s, s, eig.data_ptr(),
+                                           K, float(scale), values.data_ptr(), float(t), V1.data_ptr(), m, m, H.data_ptr(), n,
+                                           work.data_ptr()))
+        return H
+
     def nystrom(self, X, U, a2, K):  # X: (d, n_loc), U: (d, s) -> values (K,), vectors (K, n_loc)
         d, n = X.shape
         s = U.shape[1]
@@ -446,7 +462,10 @@ class HeatKernelPath:
             cnt = min(hi, m) - lo
             V1[:, lo:lo + cnt] = vectors[:, :cnt]
         self._all_reduce(V1)                                                  # exchange 4
-        H = S.hk(values, cfg.t, vectors[:, :n_loc].contiguous() if vectors.shape[1] != n_loc else vectors, V1)
+        if hasattr(S, "hk_rows") and n_loc and S.hk_rows_route(n_loc, cfg.r, s, K, m):   # H from the sparse rows and the s x m matrix Wm
+            H = S.hk_rows(ell_idx, ell_val, V, eig, math.sqrt(float(n_global)), values, cfg.t, V1)
+        else:
+            H = S.hk(values, cfg.t, vectors[:, :n_loc].contiguous() if vectors.shape[1] != n_loc else vectors, V1)
         tm.mark("heat_kernel")
         res = PathResult(values=values, vectors=vectors, H=H, stage_ms=tm.result(), eig_info=info)
         if keep:
