@@ -80,6 +80,8 @@ _SIGNATURES = {
                                           ctypes.c_ulonglong, P, P, P, P]),
     "flgp_eigenpair_pg_predict_multiclass": (c_int, [P, c_int, P, c_int, c_double, P, c_int, P, P, c_int, c_int,
                                                      ctypes.c_ulonglong, P, P]),
+    "flgp_eigenpair_pg_predict_batch": (c_int, [P, c_int, P, c_int, P, c_int, P, P, P, c_int, c_double, c_double, P, c_int,
+                                                c_int, c_int, P, P, P, P, P]),
     "flgp_negative_log_likelihood": (c_int, [P, P, P, c_long, c_int, c_char_p, c_int, ctypes.c_ulonglong, P, P]),
     "flgp_eigenpair_free": (None, [P]),
     "flgp_kmeans_minibatch": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, ctypes.c_ulonglong, P, P, P]),

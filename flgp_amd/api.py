@@ -669,6 +669,80 @@ class ResidentEigenPair:
                                                               _ptr(probs), _ptr(labels)))
         return (labels, probs) if output_probs else labels
 
+    def test_pgbinary_batch(self, idx0, idx1, K, ts, Y, sigma, sigma_nv, col=None, seeds=None, seed=None, N_sample=100,
+                            max_parallel=0, output_pi=False, return_state=False, return_argmax=False):
+        """``test_pgbinary`` for B chains in one call (DESIGN 8 f-16): chain b is column ``col[b]`` of ``Y`` (m x ncol;
+        ``col=None`` needs one column per chain) at ``ts[b]`` with ``seeds[b]`` (default ``seed + b``).  For m > K the
+        chains of a chunk of ``max_parallel`` (<= 0: all) share every launch of the sweep; for m <= K they are dealt to
+        ``max_parallel`` workers (<= 0: min(B, 4)).  Returns the keys of ``test_pgbinary`` with a trailing chain axis
+        ("Y_pred", "pi_pred": m_new x B; "omega", "f": m x B), each column ``test_pgbinary``'s bit for bit, plus "argmax"
+        (m_new: the first chain with the largest pi) with ``return_argmax``."""
+        who = "eigenpair_pg_predict_batch"
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        m, mnew = idx0.size, idx1.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx0")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        ncol = Y.shape[1]
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        B = ts.size
+        if col is None and ncol != B:
+            raise FlgpError(-1, f"{who}: col may be NULL only if ncol == B (ncol={ncol}, B={B})")
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per value of t")
+        if seeds is None:
+            s0 = _seed(seed)
+            seeds = [(s0 + b) & 0xFFFFFFFFFFFFFFFF for b in range(B)]
+        seeds = np.ascontiguousarray(np.asarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in np.asarray(seeds, dtype=object).reshape(-1)],
+                                                dtype=np.uint64))
+        if seeds.size != B:
+            raise ValueError("seeds must have one entry per value of t")
+        for b in range(B):
+            c = b if cols is None else int(cols[b])
+            head = "chain %d (t=%g, seed=%d): %s: " % (b, ts[b], int(seeds[b]), who)
+            if not 0 <= c < ncol:
+                raise FlgpError(-1, head + "col=%d is outside [0, ncol=%d)" % (c, ncol))
+            if not np.isfinite(ts[b]):
+                raise FlgpError(-1, head + "t must be finite")
+        nB = max(B, 1)
+        pi = np.zeros((mnew, nB), order="F"); y = np.zeros((mnew, nB), order="F")
+        om = np.zeros((m, nB), order="F") if return_state else None
+        f = np.zeros((m, nB), order="F") if return_state else None
+        am = np.zeros(mnew) if return_argmax else None
+        check(_lib.lib().flgp_eigenpair_pg_predict_batch(self._h, int(K), _ptr(idx0), m, _ptr(Y), ncol, _ptr(cols), _ptr(ts),
+                                                         _ptr(seeds), B, float(sigma), float(sigma_nv), _ptr(idx1), mnew,
+                                                         int(N_sample), int(max_parallel), _ptr(pi), _ptr(y), _ptr(am), _ptr(om),
+                                                         _ptr(f)))
+        out = {"Y_pred": y}
+        if output_pi:
+            out["pi_pred"] = pi
+        if return_state:
+            out["omega"] = om; out["f"] = f
+        if return_argmax:
+            out["argmax"] = am
+        return out
+
+    def predict_logit_mult_gp_batch(self, idx0, idx1, K, ts, Y, sigma, N_sample=100, seed=None, output_probs=False,
+                                    max_parallel=0):
+        """``predict_logit_mult_gp_cpp`` with the J = ``len(ts)`` one-vs-rest chains in one batched call: ``Y`` holds class
+        labels 0 .. J-1 (a class without a member is allowed), chain j is the indicator column ``Y == j`` at ``ts[j]`` with
+        seed + j and sigma on Cvv only.  Labels and probs equal ``predict_logit_mult_gp_cpp``'s bit for bit."""
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32)
+        lab = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(-1))
+        if lab.size != idx0.size:
+            raise ValueError("Y must have one entry per row of idx0")
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        J = ts.size
+        for a in range(lab.size):
+            if not (0.0 <= lab[a] < J and lab[a] == np.floor(lab[a])):
+                raise FlgpError(-1, "eigenpair_pg_predict_batch: Y[%d]=%g is not a class label in 0 .. %d" % (a, lab[a], J - 1))
+        aug = (lab[:, None] == np.arange(J)[None, :]).astype(np.float64)
+        out = self.test_pgbinary_batch(idx0, idx1, K, ts, aug, sigma, 0.0, seed=_seed(seed), N_sample=N_sample,
+                                       max_parallel=max_parallel, output_pi=True, return_argmax=True)
+        return (out["argmax"], out["pi_pred"]) if output_probs else out["argmax"]
+
     def to_host(self):
         values = np.zeros(self.K); vectors = np.zeros((self.n, self.K), order="F")
         check(_lib.lib().flgp_eigenpair_to_host(self._h, _ptr(values), _ptr(vectors)))

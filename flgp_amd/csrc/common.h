@@ -402,6 +402,34 @@ int pg_pi(hipStream_t st, long n, const double *mean, double sigma_nv, const lon
           double *pi, long ld, double *y);
 int pg_argmax(hipStream_t st, long n, int J, const double *probs, double *labels);
 int pg_init(hipStream_t st, int m, const double *Y, double *kappa, double *omega, double *f);
+// The Woodbury sweep (m > K) for a chunk of chains in the same launches (pg.hip, the sweep itself in
+// eigenpair.hip: PgBatch).  A chain owns slot s of every buffer below for the whole chunk and the kernels carry the slot in
+// gridDim.y, so a step is one launch whatever the chunk holds.  sv and sz are the doubles between two slots of an
+// m-vector and of z; Y is shared, chain s reading column ycol[s] and drawing from seed[s] (both on the device).  The K x K
+// pieces (X, Q, u, l, ls, the pivot flags) are LrChunk's, on the lrb_* kernels.
+struct PgChunk {
+  int m, K, slots;
+  long sv, sz;
+  double *kappa, *omega, *f, *f0, *r, *sw, *x, *t1, *t2, *dh, *a;   // m each
+  double *z;                                                         // z1 (K), z2 (m), z3 (m) of the sweep
+  const double *Y; long ldy; const int *ycol;
+  const unsigned long long *seed;
+  double sigma;
+};
+// Each is its pg_* namesake on every slot, expression for expression: pgb_init (column ycol[s] of Y), pgb_normals (the three
+// stream bases of (seed[s], sweep) made on the device), pgb_f0r (Vz = t2), pgb_dvec, pgb_draw (omega ~ PG(1, f) on stream
+// 4 sweep + 3 of seed[s]); pgb_wb_out: out = sw .* dh .* (t1 - t2); pgb_axpy3: out = x + y + c z, a missing term left out
+// (the operands at stride sv); pgb_pi: column s of pi and y (n x slots at ldo) from the slot's mean (stride smean) and
+// its w = x (stride sv) over the shared match list.
+int pgb_init(hipStream_t st, const PgChunk &c);
+int pgb_normals(hipStream_t st, const PgChunk &c, int sweep);
+int pgb_f0r(hipStream_t st, const PgChunk &c, double ss);
+int pgb_dvec(hipStream_t st, const PgChunk &c);
+int pgb_wb_out(hipStream_t st, const PgChunk &c, double *out);
+int pgb_axpy3(hipStream_t st, const PgChunk &c, const double *x, const double *y, double cz, const double *z, double *out);
+int pgb_draw(hipStream_t st, const PgChunk &c, int sweep);
+int pgb_pi(hipStream_t st, long n, int slots, const double *mean, long smean, double sigma_nv, const long *ptr, const int *list,
+           const double *w, long sw, double *pi, double *y, long ldo);
 
 // The multinomial label check of the host entries (nll.hip): v[i] an integer in [0, J), as "<who>: <name>[i]=.. is not a
 // class label in 0 .. J-1"; with all_named also max(v) + 1 == J, under negative_log_likelihood's message.

@@ -4,7 +4,7 @@
 // Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
 // 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12; the
 // training objective for B problems in one call: f-15);
-// Polya-Gamma Gibbs prediction (pg.hip).  The algebra they share is written once:
+// Polya-Gamma Gibbs prediction (pg.hip; B chains in one call: DESIGN 8 f-16).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
 // the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
@@ -1511,15 +1511,15 @@ struct PgMatch {
   }
 };
 
+int pg_pivot_error(int bad, const char *who) {
+  set_error("%s: a Cholesky factorisation met a pivot <= 0 (pivot %d): the covariance is not positive definite or the "
+            "chain diverged", who, bad - 1);
+  return FLGP_ERR_NOCONV;
+}
 int pg_verdict(hipStream_t st, const void *d_flag, const char *who) {   // synchronises
   int bad = 0;
   FLGP_TRY(read_flag(st, d_flag, &bad));
-  if (bad) {
-    set_error("%s: a Cholesky factorisation met a pivot <= 0 (pivot %d): the covariance is not positive definite or the "
-              "chain diverged", who, bad - 1);
-    return FLGP_ERR_NOCONV;
-  }
-  return FLGP_OK;
+  return bad ? pg_pivot_error(bad, who) : FLGP_OK;
 }
 
 int check_pg_common(const double *Y, int m, int mnew, int n_sample, const char *who) {
@@ -1556,6 +1556,149 @@ int pg_eigen_binary(hipStream_t st, const flgp_eigenpair *ep, int K, double t, d
   FLGP_HIP(hipStreamSynchronize(st));         // the chain's buffers are given back to the cache on the way out
   return FLGP_OK;
 }
+
+// PgChain's Woodbury route (m > K) for a chunk of chains in the same launches.  Slot s of every buffer
+// belongs to chain p0 + s for the whole chunk; each step of run / factor / solve / cmul / collapsed_w is one launch over
+// the slots: the pgb_* kernels (pg.hip) for the chain's own elementwise steps, LrBatch's kernels (lrb_*, on the LrChunk
+// view C whose xs is the chain's a) for X, Q and its factor, and the batched GEMM with V1 / V2 at stride 0.  Every chain
+// runs all n_sample sweeps, so the slot list is the identity.  The split products take, per chain, LowRankB's plan (a
+// workspace of vt_work_elems(K, 1) doubles) on planes of the slot's own: LrBatch::plans.
+struct PgBatch {
+  PgChunk P;
+  LrChunk C;
+  DevBuf vec, zb, kv, X, Q, part, flag, act, mean;
+  int planQ = 1, planU = 1, mnew = 0;
+  size_t pe = 0;
+  long sp = 0, sm = 0;           // doubles between two slots' planes and predicted means
+
+  // device bytes of one chain: X, Q, eleven m-vectors, z, u, l, ls, its planes, its mean over the new rows, flag and list entry
+  static double bytes(int m, int K, int mnew) {
+    int a, b;
+    size_t pe;
+    LrBatch::plans(m, K, &a, &b, &pe);
+    return 8.0 * ((double)pad32((long)m * K) + pad32((long)K * K) + 11.0 * pad32(m) + pad32(2L * m + K) + 3.0 * pad32(K) +
+                  pad32((long)pe) + pad32(mnew)) + 8.0;
+  }
+  int alloc(hipStream_t st, int m, int K, int mnew_, int slots) {
+    mnew = mnew_;
+    C = LrChunk{};
+    C.m = m; C.K = K; C.slots = slots;
+    C.sv = pad32(m); C.sk = pad32(K); C.sx = pad32((long)m * K); C.sq = pad32((long)K * K);
+    P = PgChunk{};
+    P.m = m; P.K = K; P.slots = slots; P.sv = C.sv; P.sz = pad32(2L * m + K); P.ldy = m;
+    LrBatch::plans(m, K, &planQ, &planU, &pe);
+    sp = pad32((long)pe); sm = pad32(mnew);
+    const size_t S = (size_t)slots;
+    FLGP_TRY(vec.alloc(sizeof(double) * 11 * S * P.sv)); FLGP_TRY(zb.alloc(sizeof(double) * S * P.sz));
+    FLGP_TRY(kv.alloc(sizeof(double) * 3 * S * C.sk));
+    FLGP_TRY(X.alloc(sizeof(double) * S * C.sx)); FLGP_TRY(Q.alloc(sizeof(double) * S * C.sq));
+    FLGP_TRY(part.alloc(sizeof(double) * S * sp)); FLGP_TRY(mean.alloc(sizeof(double) * S * sm));
+    FLGP_TRY(flag.alloc(sizeof(int) * S)); FLGP_TRY(act.alloc(sizeof(int) * S));
+    double *v = vec.as<double>(), *k = kv.as<double>();
+    const size_t vs = S * P.sv, ks = S * C.sk;
+    P.kappa = v; P.omega = v + vs; P.f = v + 2 * vs; P.f0 = v + 3 * vs; P.r = v + 4 * vs; P.sw = v + 5 * vs; P.x = v + 6 * vs;
+    P.t1 = v + 7 * vs; P.t2 = v + 8 * vs; P.dh = v + 9 * vs; P.a = v + 10 * vs;
+    P.z = zb.as<double>();
+    C.xs = P.a;
+    C.u = k; C.l = k + ks; C.ls = k + 2 * ks;
+    C.X = X.as<double>(); C.Q = Q.as<double>(); C.flag = flag.as<int>();
+    std::vector<int> ident(S);
+    for (int s = 0; s < slots; ++s) ident[(size_t)s] = s;
+    FLGP_TRY(h2d(act.p, ident.data(), sizeof(int) * S, st));
+    FLGP_HIP(hipStreamSynchronize(st));      // ident goes out of scope
+    return FLGP_OK;
+  }
+  // LrBatch's two K x 1 / m x 1 products per slot, on this chunk's strides
+  int tn(hipStream_t st, const double *Am, long lda, long a_bs, const double *x, double *out) {
+    const GemmBatch gb{P.slots, act.as<int>(), a_bs, P.sv, C.sk, 0, sp};
+    return gemm_launch(st, C.K, 1, C.m, 1.0, Am, lda, 1, x, 1, C.m, 0.0, nullptr, 0, 0, out, 1, C.K, part.as<double>(), pe, 0.0,
+                       nullptr, nullptr, nullptr, planU, nullptr, &gb);
+  }
+  int nn(hipStream_t st, int rows, const double *Am, long lda, long a_bs, const double *u, double *out, long o_bs) {
+    const GemmBatch gb{P.slots, act.as<int>(), a_bs, C.sk, o_bs, 0, 0};
+    return gemm_launch(st, rows, 1, C.K, 1.0, Am, 1, lda, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, rows, nullptr, 0, 0.0, nullptr,
+                       nullptr, nullptr, 0, nullptr, &gb);
+  }
+  // u = L (V1^T x) per slot: the first two steps of LowRankB::cmul
+  int lvt(hipStream_t st, const double *x) {
+    FLGP_TRY(tn(st, C.V1, C.ld1, 0, x, C.u));
+    return lrb_mul(st, C.K, C.l, C.sk, C.u, C.sk, C.u, C.sk, act.as<int>(), P.slots);
+  }
+  int factor(hipStream_t st) {
+    const int *a = act.as<int>();
+    const int S = P.slots;
+    FLGP_TRY(pgb_dvec(st, P));
+    FLGP_TRY(lrb_scale2(st, C, a, S));
+    const GemmBatch gb{S, a, C.sx, C.sx, C.sq, 0, sp};
+    FLGP_TRY(gemm_launch(st, C.K, C.K, C.m, 1.0, C.X, C.m, 1, C.X, 1, C.m, 0.0, nullptr, 0, 0, C.Q, 1, C.K, part.as<double>(), pe,
+                         0.0, nullptr, nullptr, nullptr, planQ, nullptr, &gb));
+    FLGP_TRY(lrb_add_diag(st, C, a, S));
+    return lrb_chol(st, C, a, S);
+  }
+  int solve(hipStream_t st, const double *rin, double *out) {
+    const int *a = act.as<int>();
+    FLGP_TRY(lrb_mul(st, C.m, P.dh, P.sv, rin, P.sv, P.t1, P.sv, a, P.slots));                  // g
+    FLGP_TRY(tn(st, C.X, C.m, C.sx, P.t1, C.u));
+    FLGP_TRY(lrb_trsv(st, C, a, P.slots));
+    FLGP_TRY(nn(st, C.m, C.X, C.m, C.sx, C.u, P.t2, P.sv));
+    return pgb_wb_out(st, P, out);
+  }
+  int cmul(hipStream_t st, const double *xin, const double *add, double *out) {
+    FLGP_TRY(lvt(st, xin));
+    FLGP_TRY(nn(st, C.m, C.V1, C.ld1, 0, C.u, P.t2, P.sv));
+    return pgb_axpy3(st, P, add, P.t2, P.sigma, xin, out);
+  }
+  // the chains of the chunk [p0, p0 + S): weights, the n_sample sweeps, the collapsed w (in x) and pi / y of the new rows
+  // into columns p0 .. of d_pi / d_y (d_y may be nullptr)
+  int run(hipStream_t st, const flgp_eigenpair *ep, const double *d_ts, int S, int n_sample, const Rows &r1, double sigma_nv,
+          PgMatch *match, double *d_pi, double *d_y) {
+    P.slots = C.slots = S;
+    const int *a = act.as<int>();
+    FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
+    FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
+    FLGP_TRY(pgb_init(st, P));
+    const double ss = std::sqrt(P.sigma);
+    for (int s = 0; s < n_sample; ++s) {
+      ProfScope ps("pg_batch_sweep", st, 0.0);
+      FLGP_TRY(pgb_normals(st, P, s));
+      FLGP_TRY(lrb_mul(st, C.K, C.ls, C.sk, P.z, P.sz, C.u, C.sk, a, S));
+      FLGP_TRY(nn(st, C.m, C.V1, C.ld1, 0, C.u, P.t2, P.sv));                                  // V1 L^1/2 z1
+      FLGP_TRY(pgb_f0r(st, P, ss));
+      FLGP_TRY(factor(st));
+      FLGP_TRY(solve(st, P.r, P.x));
+      FLGP_TRY(cmul(st, P.x, P.f0, P.f));
+      FLGP_TRY(pgb_draw(st, P, s));
+    }
+    FLGP_TRY(factor(st));                                                                      // PgChain::collapsed_w
+    FLGP_TRY(cmul(st, P.kappa, nullptr, P.r));
+    FLGP_TRY(lrb_mul(st, C.m, P.sw, P.sv, P.r, P.sv, P.r, P.sv, a, S));
+    FLGP_TRY(solve(st, P.r, P.f0));
+    FLGP_TRY(pgb_axpy3(st, P, P.kappa, nullptr, -1.0, P.f0, P.x));
+    FLGP_TRY(lvt(st, P.x));                                                                    // mean = V2 L V1^T w
+    FLGP_TRY(nn(st, mnew, r1.V, r1.ld, 0, C.u, mean.as<double>(), sm));
+    return pgb_pi(st, mnew, S, mean.as<double>(), sm, sigma_nv, match ? match->ptr.as<long>() : nullptr,
+                  match ? match->list.as<int>() : nullptr, P.x, P.sv, d_pi, d_y, mnew);
+  }
+};
+
+// what a worker of the m x m route (m <= K) owns and reuses across its chains: C, the contraction's workspace, the
+// spectrum weights, the chain's state and the mean over the new rows
+struct PgDirectWorker {
+  DevBuf C, work, ls, l, mean;
+  PgChain P;
+  int alloc(int m, int K, int mnew, const Rows &r0, double sigma) {
+    FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
+    FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
+    FLGP_TRY(ls.alloc(sizeof(double) * (size_t)K)); FLGP_TRY(l.alloc(sizeof(double) * (size_t)K));
+    FLGP_TRY(mean.alloc(sizeof(double) * (size_t)mnew));
+    P.route = PG_DIRECT; P.C = C.as<double>();
+    P.L.sigma = sigma; P.L.V1 = r0.V; P.L.ld1 = r0.ld; P.L.l = l.as<double>(); P.L.ls = ls.as<double>();
+    return P.alloc(m, K);
+  }
+  static double bytes(int m, int K, int mnew) {
+    return 8.0 * (2.0 * m * m + 11.0 * m + 3.0 * K + mnew + (double)vt_work_elems(K, 1)) + (double)flgp_dev_hk_workspace(m, m, K, 1);
+  }
+};
 }  // namespace
 
 extern "C" int flgp_pg_draw(const double *b, const double *c, int n, unsigned long long seed, double *omega) {
@@ -1686,4 +1829,126 @@ extern "C" int flgp_eigenpair_pg_predict_multiclass(const flgp_eigenpair *ep, in
   FLGP_TRY(d2h(probs, dprobs.p, sizeof(double) * (size_t)mnew * J, st.s));
   FLGP_TRY(d2h(labels, dlab.p, sizeof(double) * (size_t)mnew, st.s));
   return pg_verdict(st.s, flag.p, who);
+}
+
+// B chains in one call: chain b is column col[b] of Y at ts[b] with seeds[b], and its columns of the
+// outputs are flgp_eigenpair_pg_predict's, bit for bit, whatever shares the call.  m > K: chunks of chains in the same
+// launches (PgBatch); m <= K: the chains dealt to pool workers, each with a PgChain of its own on the m x m route.
+extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                                               const int *col, const double *ts, const unsigned long long *seeds, int B,
+                                               double sigma, double sigma_nv, const int *idx1, int mnew, int n_sample,
+                                               int max_parallel, double *pi_pred, double *y_pred, double *argmax_out,
+                                               double *omega_out, double *f_out) {
+  const char *who = "eigenpair_pg_predict_batch";
+  FLGP_REQUIRE(idx0 && Y && ts && seeds && idx1 && pi_pred, "%s: null pointer", who);
+  FLGP_REQUIRE(B >= 1 && m >= 1 && mnew >= 1 && ncol >= 1, "%s: bad shape (B=%d, m=%d, m_new=%d, ncol=%d)", who, B, m, mnew, ncol);
+  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  std::vector<int> cols((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int c = cols[(size_t)b] = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "chain %d (t=%g, seed=%llu): %s: col=%d is outside [0, ncol=%d)", b, ts[b], seeds[b], who, c, ncol);
+    FLGP_REQUIRE(std::isfinite(ts[b]), "chain %d (t=%g, seed=%llu): %s: t must be finite", b, ts[b], seeds[b], who);
+  }
+  for (int c = 0; c < ncol; ++c)
+    for (int a = 0; a < m; ++a) {
+      const double y = Y[(size_t)c * m + a];
+      FLGP_REQUIRE(y >= 0.0 && y <= 1.0, "%s: Y[%d, %d]=%g is outside [0, 1]", who, a, c, y);
+    }
+  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(sigma_nv), "%s: sigma must be finite and >= 0", who);
+  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+
+  Stream st;
+  FLGP_TRY(st.create());
+  const size_t vb = sizeof(double) * (size_t)m, nb = sizeof(double) * (size_t)mnew;
+  DevBuf dY, dpi, dy, dlab, dflag;
+  FLGP_TRY(upload(dY, Y, vb * ncol, st.s));
+  FLGP_TRY(dpi.alloc(nb * B));
+  if (y_pred) FLGP_TRY(dy.alloc(nb * B));
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  PgMatch match;
+  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, idx0, m, idx1, mnew));
+  PgMatch *mt = sigma_nv != 0.0 ? &match : nullptr;
+  std::vector<int> flags((size_t)B, 0);       // one pivot flag per chain, read after the chain's sweeps
+  if (m <= K) {
+    FLGP_TRY(dflag.alloc(sizeof(int) * (size_t)B));
+    FLGP_HIP(hipMemsetAsync(dflag.p, 0, sizeof(int) * (size_t)B, st.s));
+    FLGP_HIP(hipStreamSynchronize(st.s));      // the workers' streams start from the gathered rows and the cleared flags
+    DevicePool pool;
+    FLGP_TRY(pool.plan(max_parallel > 0 ? max_parallel : std::min(B, 4), B, PgDirectWorker::bytes(m, K, mnew)));
+    const PoolFailure bad = pool.run<PgDirectWorker>(
+        st.s, B, [&](PgDirectWorker &W) { return W.alloc(m, K, mnew, r0, sigma); },
+        [&](hipStream_t ws, PgDirectWorker &W, int b) -> int {
+          PgChain &P = W.P;
+          P.flag = P.L.flag = dflag.as<int>() + b;
+          FLGP_TRY(gpr_weights(ws, (const double *)ep->values.p, K, ts[b], W.ls.as<double>(), W.l.as<double>()));
+          FLGP_TRY(hk(ws, ep, K, ts[b], r0, r0, W.C.as<double>(), W.work.as<double>()));
+          if (sigma != 0.0) FLGP_TRY(gpr_add_diag(ws, W.C.as<double>(), m, sigma));
+          FLGP_TRY(P.run(ws, dY.as<double>() + (size_t)cols[(size_t)b] * m, n_sample, seeds[b]));
+          FLGP_TRY(P.collapsed_w(ws));
+          FLGP_TRY(P.L.cmul(ws, r1.V, r1.ld, mnew, P.x.as<double>(), W.mean.as<double>()));
+          FLGP_TRY(pg_pi(ws, mnew, W.mean.as<double>(), sigma_nv, mt ? mt->ptr.as<long>() : nullptr,
+                         mt ? mt->list.as<int>() : nullptr, P.x.as<double>(), dpi.as<double>() + (size_t)b * mnew, 1,
+                         y_pred ? dy.as<double>() + (size_t)b * mnew : nullptr));
+          if (omega_out) FLGP_TRY(d2h(omega_out + (size_t)b * m, P.omega.p, vb, ws));
+          if (f_out) FLGP_TRY(d2h(f_out + (size_t)b * m, P.f.p, vb, ws));
+          FLGP_HIP(hipStreamSynchronize(ws));    // the worker's buffers take the next chain
+          return FLGP_OK;
+        });
+    if (bad.item >= 0) {
+      set_error("chain %d (t=%g, seed=%llu): %s", bad.item, ts[bad.item], seeds[bad.item], bad.message.c_str());
+      return bad.status;
+    }
+    FLGP_TRY(d2h(flags.data(), dflag.p, sizeof(int) * (size_t)B, st.s));
+  } else {
+    DevBuf dcol, dts, dseed;
+    FLGP_TRY(upload(dcol, cols.data(), sizeof(int) * (size_t)B, st.s));
+    FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st.s));
+    FLGP_TRY(upload(dseed, seeds, sizeof(unsigned long long) * (size_t)B, st.s));
+    // the chunk: max_parallel chains, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of the
+    // free memory
+    const int want = max_parallel > 0 ? max_parallel : B;
+    size_t free_b = 0, total_b = 0;
+    if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+    const int chunk = std::min(plan_workers(want, B, (double)free_b, PgBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
+    PgBatch L;
+    FLGP_TRY(L.alloc(st.s, m, K, mnew, chunk));
+    L.P.Y = dY.as<double>(); L.P.sigma = sigma;
+    L.C.V1 = r0.V; L.C.ld1 = r0.ld; L.C.sigma = sigma;
+    for (int p0 = 0; p0 < B; p0 += chunk) {
+      const int S = std::min(chunk, B - p0);
+      L.P.ycol = dcol.as<int>() + p0; L.P.seed = dseed.as<unsigned long long>() + p0;
+      FLGP_TRY(L.run(st.s, ep, dts.as<double>() + p0, S, n_sample, r1, sigma_nv, mt, dpi.as<double>() + (size_t)p0 * mnew,
+                     y_pred ? dy.as<double>() + (size_t)p0 * mnew : nullptr));
+      // the slots' omega and f, packed: m x S from rows sv apart
+      if (omega_out)
+        FLGP_HIP(hipMemcpy2DAsync(omega_out + (size_t)p0 * m, vb, L.P.omega, sizeof(double) * (size_t)L.P.sv, vb, (size_t)S,
+                                  hipMemcpyDeviceToHost, st.s));
+      if (f_out)
+        FLGP_HIP(hipMemcpy2DAsync(f_out + (size_t)p0 * m, vb, L.P.f, sizeof(double) * (size_t)L.P.sv, vb, (size_t)S,
+                                  hipMemcpyDeviceToHost, st.s));
+      FLGP_TRY(d2h(flags.data() + p0, L.C.flag, sizeof(int) * (size_t)S, st.s));
+    }
+  }
+  if (argmax_out) {
+    FLGP_TRY(dlab.alloc(nb));
+    FLGP_TRY(pg_argmax(st.s, mnew, B, dpi.as<double>(), dlab.as<double>()));
+    FLGP_TRY(d2h(argmax_out, dlab.p, nb, st.s));
+  }
+  FLGP_TRY(d2h(pi_pred, dpi.p, nb * B, st.s));
+  if (y_pred) FLGP_TRY(d2h(y_pred, dy.p, nb * B, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  for (int b = 0; b < B; ++b)
+    if (flags[(size_t)b]) {
+      const int rc = pg_pivot_error(flags[(size_t)b], who);
+      const std::string msg(flgp_last_error());
+      set_error("chain %d (t=%g, seed=%llu): %s", b, ts[b], seeds[b], msg.c_str());
+      return rc;
+    }
+  return FLGP_OK;
 }

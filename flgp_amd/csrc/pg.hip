@@ -11,7 +11,8 @@
 // uniforms 2i, 2i + 1, sqrt(-2 log u_2i) cos(2 pi u_2i+1); an exponential is -log u.  Nothing depends on the launch
 // geometry.
 //
-// Layout of one chain (flgp_eigenpair_pg_predict, flgp_pg_logit_predict), sweep s = 0 .. n_sample - 1:
+// Layout of one chain (flgp_eigenpair_pg_predict, flgp_pg_logit_predict, and every chain of
+// flgp_eigenpair_pg_predict_batch under its own seed), sweep s = 0 .. n_sample - 1:
 //   stream 4s     normal k (k < K): z1 of f0 = V1 L^1/2 z1 + sqrt(sigma) z2 (unused by the dense entry);
 //   stream 4s + 1 normal a (a < m): z2 (the dense entry: f0 = L_C z2);
 //   stream 4s + 2 normal a: z3 of r = kappa / sqrt(omega) - sqrt(omega) f0 - z3;
@@ -304,6 +305,141 @@ __global__ void pg_init_kernel(int m, const double *__restrict__ Y, double *__re
 int pg_init(hipStream_t st, int m, const double *Y, double *kappa, double *omega, double *f) {
   hipLaunchKernelGGL(pg_init_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, m, Y, kappa, omega, f);
   return check_launch("pg_init_kernel");
+}
+
+// ---- the Woodbury sweep for a chunk of chains (PgChunk, common.h; the sweep is in eigenpair.hip) ----------
+// The kernels above with the chain's slot in blockIdx.y.  A thread reads and writes its own slot only, every expression is
+// its namesake's and every random number is a function of (seed[slot], sweep, stream, entry, draw), so a chain's bits are
+// those of the single entry whatever shares its chunk.
+
+__global__ void pgb_init_kernel(PgChunk c) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long s = blockIdx.y, o = s * c.sv + i;
+  c.kappa[o] = c.Y[(size_t)c.ycol[s] * c.ldy + i] - 0.5;
+  c.omega[o] = 1.0;
+  c.f[o] = 0.0;
+}
+
+__global__ void pgb_normals_kernel(PgChunk c, unsigned long long s4) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = c.K, m = c.m;
+  if (e >= K + 2 * m) return;
+  const long s = blockIdx.y;
+  const unsigned long long seed = c.seed[s];
+  unsigned long long base;
+  int i;
+  if (e < K) { base = rng_stream_base(seed, s4); i = e; }
+  else if (e < K + m) { base = rng_stream_base(seed, s4 + 1); i = e - K; }
+  else { base = rng_stream_base(seed, s4 + 2); i = e - K - m; }
+  const unsigned long long q = 2ull * (unsigned long long)i;
+  c.z[s * c.sz + e] = rng_box_muller(rng_unif(base, q), rng_unif(base, q + 1));
+}
+
+__global__ void pgb_f0r_kernel(PgChunk c, double ss) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long sl = blockIdx.y, o = sl * c.sv + i;
+  const double *z2 = c.z + sl * c.sz + c.K, *z3 = z2 + c.m;
+  const double f = c.t2[o] + ss * z2[i];
+  const double s = sqrt(c.omega[o]);
+  c.f0[o] = f;
+  c.r[o] = c.kappa[o] / s - s * f - z3[i];
+  c.sw[o] = s;
+}
+
+__global__ void pgb_dvec_kernel(PgChunk c) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long o = (long)blockIdx.y * c.sv + i;
+  const double w = c.omega[o];
+  const double s = sqrt(w), d = 1.0 / sqrt(1.0 + c.sigma * w);
+  c.sw[o] = s; c.dh[o] = d; c.a[o] = s * d;
+}
+
+__global__ void pgb_wb_out_kernel(PgChunk c, double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long o = (long)blockIdx.y * c.sv + i;
+  out[o] = c.sw[o] * (c.dh[o] * (c.t1[o] - c.t2[o]));
+}
+
+// (out may be x: an element is read before it is written, by its own thread)
+__global__ void pgb_axpy3_kernel(int m, long sv, const double *x, const double *y, double c, const double *z, double *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const long o = (long)blockIdx.y * sv + i;
+  double v = x ? x[o] : 0.0;
+  if (y) v = x ? v + y[o] : y[o];
+  if (z) v = (x || y) ? v + c * z[o] : c * z[o];
+  out[o] = v;
+}
+
+__global__ void pgb_draw_kernel(PgChunk c, unsigned long long stream) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long sl = blockIdx.y, o = sl * c.sv + i;
+  PgCtr r{rng_stream_base(c.seed[sl], stream), (unsigned long long)i << 32};
+  const double z = 0.5 * fabs(c.f[o]);
+  double s = 0.0;
+  s += 0.25 * jstar_draw(z, r);
+  c.omega[o] = s;
+}
+
+__global__ void pgb_pi_kernel(long n, const double *__restrict__ mean, long smean, double sigma_nv, const long *__restrict__ ptr,
+                              const int *__restrict__ list, const double *__restrict__ w, long sw, double *__restrict__ pi,
+                              double *__restrict__ y, long ldo) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long s = blockIdx.y;
+  double f = mean[s * smean + i];
+  if (ptr) {
+    const double *ws = w + s * sw;
+    double acc = 0.0;
+    for (long p = ptr[i]; p < ptr[i + 1]; ++p) acc += ws[list[p]];
+    f = f + sigma_nv * acc;
+  }
+  const double v = 1.0 / (1.0 + exp(-f));
+  pi[s * ldo + i] = v;
+  if (y) y[s * ldo + i] = v > 0.5 ? 1.0 : 0.0;
+}
+
+int pgb_init(hipStream_t st, const PgChunk &c) {
+  hipLaunchKernelGGL(pgb_init_kernel, dim3(ceil_div(c.m, 256), c.slots), dim3(256), 0, st, c);
+  return check_launch("pgb_init_kernel");
+}
+int pgb_normals(hipStream_t st, const PgChunk &c, int sweep) {
+  hipLaunchKernelGGL(pgb_normals_kernel, dim3(ceil_div(c.K + 2 * c.m, 256), c.slots), dim3(256), 0, st, c,
+                     4ull * (unsigned long long)sweep);
+  return check_launch("pgb_normals_kernel");
+}
+int pgb_f0r(hipStream_t st, const PgChunk &c, double ss) {
+  hipLaunchKernelGGL(pgb_f0r_kernel, dim3(ceil_div(c.m, 256), c.slots), dim3(256), 0, st, c, ss);
+  return check_launch("pgb_f0r_kernel");
+}
+int pgb_dvec(hipStream_t st, const PgChunk &c) {
+  hipLaunchKernelGGL(pgb_dvec_kernel, dim3(ceil_div(c.m, 256), c.slots), dim3(256), 0, st, c);
+  return check_launch("pgb_dvec_kernel");
+}
+int pgb_wb_out(hipStream_t st, const PgChunk &c, double *out) {
+  hipLaunchKernelGGL(pgb_wb_out_kernel, dim3(ceil_div(c.m, 256), c.slots), dim3(256), 0, st, c, out);
+  return check_launch("pgb_wb_out_kernel");
+}
+int pgb_axpy3(hipStream_t st, const PgChunk &c, const double *x, const double *y, double cz, const double *z, double *out) {
+  hipLaunchKernelGGL(pgb_axpy3_kernel, dim3(ceil_div(c.m, 256), c.slots), dim3(256), 0, st, c.m, c.sv, x, y, cz, z, out);
+  return check_launch("pgb_axpy3_kernel");
+}
+int pgb_draw(hipStream_t st, const PgChunk &c, int sweep) {
+  hipLaunchKernelGGL(pgb_draw_kernel, dim3(ceil_div(c.m, 256), c.slots), dim3(256), 0, st, c,
+                     4ull * (unsigned long long)sweep + 3);
+  return check_launch("pgb_draw_kernel");
+}
+int pgb_pi(hipStream_t st, long n, int slots, const double *mean, long smean, double sigma_nv, const long *ptr, const int *list,
+           const double *w, long sw, double *pi, double *y, long ldo) {
+  if (n <= 0 || slots <= 0) return FLGP_OK;
+  hipLaunchKernelGGL(pgb_pi_kernel, dim3(ceil_div(n, 256), slots), dim3(256), 0, st, n, mean, smean, sigma_nv, ptr, list, w, sw,
+                     pi, y, ldo);
+  return check_launch("pgb_pi_kernel");
 }
 
 }  // namespace flgp
