@@ -68,6 +68,8 @@ _SIGNATURES = {
     "flgp_eigenpair_logit_posterior_multiclass_nll": (c_int, [P, c_int, P, c_int, c_double, c_double, P, c_int, P, P, c_int,
                                                               c_double, c_int, c_int, P, P, P, P, c_int, ctypes.c_ulonglong,
                                                               P]),
+    "flgp_eigenpair_logit_posterior_batch": (c_int, [P, c_int, P, c_int, P, c_int, P, P, c_int, c_double, c_double, P, c_int,
+                                                     c_double, c_int, c_int, P, P, P]),
     "flgp_eigenpair_logit_objective": (c_int, [P, c_int, P, c_int, P, P, c_double, c_char_p, P, c_double, c_double, c_int, P,
                                                P]),
     "flgp_eigenpair_logit_objective_batch": (c_int, [P, c_int, P, c_int, P, c_int, P, P, P, c_int, c_double, c_char_p, P,

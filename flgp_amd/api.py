@@ -516,6 +516,47 @@ class ResidentEigenPair:
             out["mean"] = mean; out["cov"] = cov
         return (out, its[:J].copy()) if return_iters else out
 
+    def logit_posterior_batch(self, idx0, idx1, K, ts, Y, col=None, sigma11=0.0, sigma22=1e-3, tol=1e-5, max_iter=100,
+                              max_parallel=0, return_iters=False):
+        """``logit_posterior`` for B problems in one call (flgp_eigenpair_logit_posterior_batch, include/flgp_hip.h):
+        problem b is column ``col[b]`` of ``Y`` (m, or m x ncol, entries in [0, 1]; ``col`` None needs ncol == B and means
+        0 .. B-1) at ``ts[b]``; the rows, K, the sigmas, tol and max_iter are shared.  Column b of the result (and its
+        iteration count) is, bit for bit, ``logit_posterior`` on that column at that t, whatever else shares the call.  For
+        m > K the B weight-space Newton loops advance in the same launches, ``max_parallel`` problems per chunk (0: as many
+        as fit the device memory), and one fused kernel per chunk reads the rows idx1 once for all its problems; m <= K runs
+        the dense route per problem.  The one-vs-rest posterior is this call on the m x J indicator matrix with
+        ``sigma11 = 0``.  A bad ``col[b]`` or ``ts[b]`` is refused here, before the library is called, with the library's
+        own text.  Returns {"mean", "cov"}, m_new x B Fortran-ordered, or ``({"mean", "cov"}, iters)``."""
+        who = "logit_posterior_batch"
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
+        m = idx0.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx0")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        ncol = Y.shape[1]
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        B = ts.size
+        if col is None and ncol != B:
+            raise FlgpError(-1, f"{who}: col may be NULL only if ncol == B (ncol={ncol}, B={B})")
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per value of t")
+        for b in range(B):
+            c = b if cols is None else int(cols[b])
+            head = "problem %d (t=%g): %s: " % (b, ts[b], who)
+            if not 0 <= c < ncol:
+                raise FlgpError(-1, head + "col=%d is outside [0, ncol=%d)" % (c, ncol))
+            if not np.isfinite(ts[b]):
+                raise FlgpError(-1, head + "t must be finite")
+        mean = np.zeros((idx1.size, max(B, 1)), order="F"); cov = np.zeros((idx1.size, max(B, 1)), order="F")
+        its = np.zeros(max(B, 1), dtype=np.int32)
+        check(_lib.lib().flgp_eigenpair_logit_posterior_batch(self._h, int(K), _ptr(idx0), m, _ptr(Y), ncol, _ptr(cols), _ptr(ts), B,
+                                                              float(sigma11), float(sigma22), _ptr(idx1), idx1.size, float(tol),
+                                                              int(max_iter), int(max_parallel), _ptr(mean), _ptr(cov), _ptr(its)))
+        post = {"mean": mean[:, :B], "cov": cov[:, :B]}
+        return (post, its[:B].copy()) if return_iters else post
+
     def logit_objective(self, t, K, idx, Y, N=None, sigma=1e-3, approach="posterior", prior=None, tol=1e-5, max_iter=100,
                         return_iters=False):
         """The value train_lae_logit_gp_cpp's COBYLA minimises at t (src/train.cpp:14-34), on the resident pair with

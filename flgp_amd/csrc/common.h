@@ -351,6 +351,22 @@ int gpc_predict_prep(hipStream_t st, int K, const double *dG, const double *d_u,
 int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int J,
                            const double *d_Gf, double c, double *d_mean, double *d_cov, long ldo);
 int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out);
+// The weight-space loop and the predictive operands for a chunk of problems in the same launches (gpc.hip,
+// the loop in eigenpair.hip: WsBatch), on LrChunk's slots and lists, beside the lrb_* steps it shares.  On the listed
+// slots: wsb_w: sW and b from f and Y with N = 1 (gpc_w_kernel's form without N); wsb_bd: c = b / D; wsb_fnew:
+// f_new = g + sigma (b - sW^2 g) / D; wsb_scale_cols: M(i, j) *= ls(j) on the K x K matrix at Q's stride;
+// wsb_predict_prep: gpc_predict_prep on (dG at Q's stride, u) into operand s of d_Gf.  wsb_tri_inverse: tri_inverse of the
+// factor in Q for every slot 0 .. A-1 (`all` lists them), dX at Q's stride, dT 64 x K per slot at stride st_, the split
+// planes of a slot at part + slot sp (pe doubles each, at least wsb_tri_inverse_planes(K, we)); `we` is the workspace whose
+// plan an unbatched tri_inverse would take.
+int wsb_w(hipStream_t st, const LrChunk &c, const int *act, int A);
+int wsb_bd(hipStream_t st, const LrChunk &c, const int *act, int A);
+int wsb_fnew(hipStream_t st, const LrChunk &c, const int *act, int A);
+int wsb_scale_cols(hipStream_t st, const LrChunk &c, const int *act, int A, double *dM);
+int wsb_predict_prep(hipStream_t st, const LrChunk &c, const int *act, int A, const double *dG, double *d_Gf);
+size_t wsb_tri_inverse_planes(int K, size_t we);
+int wsb_tri_inverse(hipStream_t st, const LrChunk &c, const int *all, int A, double *dX, double *dT, long st_, double *part,
+                    size_t pe, long sp, size_t we);
 // The rows of the regression posterior for m > K (gpc.hip, beside the kernels above whose staging and row
 // sums they share): mean(i, 0:q) = U^T v_i (d_mean column-major at ldo) and cov_i = c + |G v_i|^2, the operand
 // Gp = [G ; U^T] ((K + q) x K; U K x q at ld K) written once by gpr_predict_prep into gpr_predict_operand_elems(K, q)

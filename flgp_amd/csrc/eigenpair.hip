@@ -2,7 +2,8 @@
 // regression prediction, posterior variance and the training objectives with their gradients (kernels in
 // gpr.hip and gpr_grad.hip; the drivers' whole testing step in one call, in weight space for m > K: DESIGN 8 f-13); the
 // Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
-// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12; the
+// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12; B
+// posteriors on any response matrix in one call, their weight-space loops in shared launches: f-17; the
 // training objective for B problems in one call: f-15);
 // Polya-Gamma Gibbs prediction (pg.hip; B chains in one call: DESIGN 8 f-16).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
@@ -1230,6 +1231,231 @@ extern "C" int flgp_eigenpair_logit_posterior_multiclass_nll(const flgp_eigenpai
   FLGP_REQUIRE(nll, "logit_posterior_multiclass: null pointer");
   return posterior_multiclass(ep, K, ts, J, sigma11, sigma22, idx0, m, Y, idx1, mnew, tol, max_iter, max_parallel, mean, cov,
                               iters, target, n_samples, seed, nll);
+}
+
+// ---- logit posterior for a batch of (labels, t) problems: the weight-space loops in shared launches ------
+namespace {
+// GpcWeightSpace for a chunk of problems on LrBatch's slots, lists and planes: slot s of every buffer belongs to problem
+// p0 + s for the whole chunk and every step of an iteration is one launch over the device list of the slots still
+// iterating, so a problem's bits depend on nothing that shares its chunk.  Of the chunk's m-vectors c holds b / D and g
+// holds p; u holds beta and then L^1/2 beta (a and Xv are not used).  The products take LrBatch's plans, which are those
+// of LowRankB's workspace, the single entry's.  Beside the loop's state a slot owns what McWorker owns: L_Q^-1 (Li), the
+// 64 x K block and the planes of the triangular inverse, and its predictive operand.
+struct WsBatch {
+  LrBatch L;
+  DevBuf Li, Tb, tpart, Gf, all;
+  size_t wi = 0, tpe = 0, ge = 0;
+  long stb = 0, stp = 0;
+
+  // device bytes of one problem: LrBatch's (X, Q, the m-vectors, u, l, ls, the loop's planes), L_Q^-1, the 64 x K block,
+  // the inverse's planes, the operand and two output columns
+  static double bytes(int m, int K, int mnew) {
+    const size_t wi = (size_t)32 * 64 * K;
+    return LrBatch::bytes(m, K) + 8.0 * ((double)pad32((long)K * K) + pad32((long)64 * K) +
+                                         pad32((long)wsb_tri_inverse_planes(K, wi)) + (double)gpc_predict_operand_elems(K) +
+                                         2.0 * mnew) + 4.0;
+  }
+  int alloc(int m, int K, int slots, bool fused) {
+    FLGP_TRY(L.alloc(m, K, slots));
+    wi = (size_t)32 * 64 * K;                                  // McWorker's workspace: it bounds the inverse's splits
+    tpe = wsb_tri_inverse_planes(K, wi);
+    stb = pad32((long)64 * K); stp = pad32((long)tpe);
+    ge = gpc_predict_operand_elems(K);
+    const size_t S = (size_t)slots;
+    FLGP_TRY(Li.alloc(sizeof(double) * S * L.C.sq)); FLGP_TRY(Tb.alloc(sizeof(double) * S * stb));
+    FLGP_TRY(tpart.alloc(sizeof(double) * std::max<size_t>(S * stp, 1)));
+    if (fused) FLGP_TRY(Gf.alloc(sizeof(double) * S * ge));
+    return all.alloc(sizeof(int) * S);
+  }
+  // GpcWeightSpace::solve on the A listed slots: W, b, D, X and L_Q at the current f, then u = Q^-1 L^1/2 V1^T (b / D)
+  int solve(hipStream_t st, const int *a, int A) {
+    LrChunk &C = L.C;
+    FLGP_TRY(wsb_w(st, C, a, A));                                                             // sW, b
+    FLGP_TRY(lrb_d(st, C, a, A));                                                             // D, dh, xs
+    FLGP_TRY(lrb_scale2(st, C, a, A));                                                        // X, then Q = I + X^T X = L_Q L_Q^T
+    {
+      const GemmBatch gb{A, a, C.sx, C.sx, C.sq, 0, L.sp};
+      FLGP_TRY(gemm_launch(st, C.K, C.K, C.m, 1.0, C.X, C.m, 1, C.X, 1, C.m, 0.0, nullptr, 0, 0, C.Q, 1, C.K, L.part.as<double>(),
+                           L.pe, 0.0, nullptr, nullptr, nullptr, L.planQ, nullptr, &gb));
+    }
+    FLGP_TRY(lrb_add_diag(st, C, a, A));
+    FLGP_TRY(lrb_chol(st, C, a, A));
+    FLGP_TRY(wsb_bd(st, C, a, A));                                                            // c = b / D
+    FLGP_TRY(tn(st, a, A, C.c, C.u));                                                         // V1^T (.)
+    FLGP_TRY(lrb_mul(st, C.K, C.ls, C.sk, C.u, C.sk, C.u, C.sk, a, A));                       // L^1/2 (.)
+    return lrb_trsv(st, C, a, A);                                                             // beta
+  }
+  // LrBatch::tn / nn against the shared V1 with the list given (the final step runs on every slot, not on the loop's list)
+  int tn(hipStream_t st, const int *a, int A, const double *x, double *out) {
+    LrChunk &C = L.C;
+    const GemmBatch gb{A, a, 0, C.sv, C.sk, 0, L.sp};
+    return gemm_launch(st, C.K, 1, C.m, 1.0, C.V1, C.ld1, 1, x, 1, C.m, 0.0, nullptr, 0, 0, out, 1, C.K, L.part.as<double>(), L.pe,
+                       0.0, nullptr, nullptr, nullptr, L.planU, nullptr, &gb);
+  }
+  int nn(hipStream_t st, const int *a, int A, const double *u, double *out) {
+    LrChunk &C = L.C;
+    const GemmBatch gb{A, a, 0, C.sk, C.sv, 0, 0};
+    return gemm_launch(st, C.m, 1, C.K, 1.0, C.V1, 1, C.ld1, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, C.m, nullptr, 0, 0.0, nullptr,
+                       nullptr, nullptr, 0, nullptr, &gb);
+  }
+  // u <- L^1/2 beta
+  int scaled_beta(hipStream_t st, const int *a, int A) {
+    LrChunk &C = L.C;
+    return lrb_mul(st, C.K, C.ls, C.sk, C.u, C.sk, C.u, C.sk, a, A);
+  }
+  // GpcWeightSpace::iteration of the A listed slots: every launch once, whatever A is
+  int iteration(hipStream_t st, int A) {
+    ProfScope ps("logit_ws_batch_iter", st, 0.0);
+    LrChunk &C = L.C;
+    const int *a = L.act.as<int>();
+    FLGP_TRY(solve(st, a, A));
+    FLGP_TRY(scaled_beta(st, a, A));
+    FLGP_TRY(nn(st, a, A, C.u, C.g));                                                         // p = V1 L^1/2 beta
+    FLGP_TRY(wsb_fnew(st, C, a, A));                                                          // f_new = p + sigma (b - W p) / D
+    return lrb_step(st, C, a, A, L.stat.as<double>());
+  }
+  // The final step of McWorker::mode_and_operand for every slot 0 .. S-1: the weights once more at the final f, L_Q, beta,
+  // u = L^1/2 beta, Li = L_Q^-1 L^1/2, and (fused) the slot's operand [Li ; u^T]
+  int operands(hipStream_t st, int S) {
+    LrChunk &C = L.C;
+    const int *a = all.as<int>();
+    FLGP_TRY(solve(st, a, S));
+    FLGP_TRY(scaled_beta(st, a, S));
+    FLGP_TRY(wsb_tri_inverse(st, C, a, S, Li.as<double>(), Tb.as<double>(), stb, tpart.as<double>(), tpe, stp, wi));
+    FLGP_TRY(wsb_scale_cols(st, C, a, S, Li.as<double>()));
+    return Gf.p ? wsb_predict_prep(st, C, a, S, Li.as<double>(), Gf.as<double>()) : FLGP_OK;
+  }
+};
+
+// The chunk [p0, p0 + S) from f = 0 with lr_batch_chunk's protocol: after every iteration the host reads the A norms and
+// the A flags (12 A bytes), notes the iteration count of every listed problem and takes the converged and the failed ones
+// off the list; nothing writes a slot that left.  Then the final step for every slot, and its pivot flags (iter 0: the
+// factorisation at the mode).  fail: the lowest failing problem of the chunk; its: the S counts.
+int ws_batch_chunk(hipStream_t st, WsBatch &W, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+                   int p0, int *its, BatchFailure &fail) {
+  LrBatch &L = W.L;
+  LrChunk &C = L.C;
+  C.slots = S;
+  FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
+  FLGP_HIP(hipMemsetAsync(C.f, 0, sizeof(double) * (size_t)S * C.sv, st));
+  FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
+  std::vector<int> act((size_t)S), next;
+  for (int s = 0; s < S; ++s) act[(size_t)s] = s;
+  FLGP_TRY(h2d(W.all.p, act.data(), sizeof(int) * (size_t)S, st));
+  FLGP_HIP(hipStreamSynchronize(st));            // `act` changes below: the copy has read it
+  std::vector<double> stat((size_t)S * 2);       // 12 A bytes are read into it: A doubles, then A ints
+  bool changed = true;
+  for (int it = 0; it < max_iter && !act.empty(); ++it) {
+    const int A = (int)act.size();
+    if (changed) FLGP_TRY(h2d(L.act.p, act.data(), sizeof(int) * (size_t)A, st));
+    FLGP_TRY(W.iteration(st, A));
+    FLGP_TRY(d2h(stat.data(), L.stat.p, (size_t)12 * A, st));
+    FLGP_HIP(hipStreamSynchronize(st));
+    const int *bad = (const int *)(stat.data() + A);
+    next.clear();
+    for (int q = 0; q < A; ++q) {
+      const int s = act[(size_t)q];
+      its[s] = it + 1;
+      if (bad[q]) {
+        if (fail.problem < 0 || p0 + s < fail.problem) { fail.problem = p0 + s; fail.bad = bad[q]; fail.iter = it + 1; }
+      } else if (!(stat[(size_t)q] < tol)) {
+        next.push_back(s);
+      }
+    }
+    changed = next.size() != act.size();
+    act.swap(next);
+  }
+  if (fail.problem >= 0) return FLGP_OK;
+  FLGP_TRY(W.operands(st, S));
+  std::vector<int> flags((size_t)S, 0);
+  FLGP_TRY(d2h(flags.data(), C.flag, sizeof(int) * (size_t)S, st));
+  FLGP_HIP(hipStreamSynchronize(st));
+  for (int s = 0; s < S; ++s)
+    if (flags[(size_t)s]) { fail.problem = p0 + s; fail.bad = flags[(size_t)s]; fail.iter = 0; break; }
+  return FLGP_OK;
+}
+}  // namespace
+
+extern "C" int flgp_eigenpair_logit_posterior_batch(const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
+                                                    int ncol, const int *col, const double *ts, int B, double sigma11,
+                                                    double sigma22, const int *idx1, int mnew, double tol, int max_iter,
+                                                    int max_parallel, double *mean, double *cov, int *iters) {
+  const char *who = "logit_posterior_batch";
+  FLGP_REQUIRE(idx0 && Y && ts && idx1 && mean && cov, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && m >= 1 && mnew >= 1 && max_iter >= 1 && B >= 1 && ncol >= 1,
+               "%s: bad shape (K=%d, m=%d, m_new=%d, max_iter=%d, B=%d, ncol=%d)", who, K, m, mnew, max_iter, B, ncol);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  std::vector<int> cols((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int c = cols[(size_t)b] = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "problem %d (t=%g): %s: col=%d is outside [0, ncol=%d)", b, ts[b], who, c, ncol);
+    FLGP_REQUIRE(std::isfinite(ts[b]), "problem %d (t=%g): %s: t must be finite", b, ts[b], who);
+  }
+  FLGP_TRY(posterior_check_sigmas(who, sigma11, sigma22));
+  for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, nullptr, m, who));
+  Rows r0, r1;
+  FLGP_TRY(posterior_check_rows(who, ep, K, idx0, m, idx1, mnew, max_iter, true, r0, r1));    // the pair is looked at last
+  auto name_failure = [&](int b, const std::string &msg) { set_error("problem %d (t=%g): %s", b, ts[b], msg.c_str()); };
+
+  Stream st;
+  FLGP_TRY(st.create());
+  FLGP_TRY(r1.resolve(st.s));
+  const size_t colb = (size_t)mnew, nb = sizeof(double) * colb * B;
+  DevBuf dY, dmean, dcov;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * ncol, st.s));
+  FLGP_TRY(dmean.alloc(nb)); FLGP_TRY(dcov.alloc(nb));
+  std::vector<int> its((size_t)B, 0);
+  if (m <= K) {
+    // the dense body per problem, one after another
+    for (int b = 0; b < B; ++b) {
+      const int rc = posterior_dense_on(st.s, who, ep, K, ts[b], sigma11, sigma22, r0, m, dY.as<double>() + (size_t)cols[(size_t)b] * m,
+                                        r1, mnew, tol, max_iter, dmean.as<double>() + b * colb, dcov.as<double>() + b * colb,
+                                        &its[(size_t)b]);
+      if (rc != FLGP_OK) { name_failure(b, std::string(flgp_last_error())); return rc; }
+    }
+  } else {
+    FLGP_TRY(r0.gather(st.s, ep, K));
+    DevBuf dcol, dts;
+    FLGP_TRY(upload(dcol, cols.data(), sizeof(int) * (size_t)B, st.s));
+    FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st.s));
+    const bool fused = gpc_predict_rows_applicable(K);
+    // the chunk: max_parallel problems, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of
+    // the free memory
+    const int want = max_parallel > 0 ? max_parallel : B;
+    size_t free_b = 0, total_b = 0;
+    if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+    const int chunk = std::min(plan_workers(want, B, (double)free_b, WsBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
+    WsBatch W;
+    FLGP_TRY(W.alloc(m, K, chunk, fused));
+    LrChunk &C = W.L.C;
+    C.Y = dY.as<double>(); C.ldy = m; C.N = nullptr;
+    C.V1 = r0.V; C.ld1 = r0.ld; C.sigma = sigma11;
+    for (int p0 = 0; p0 < B; p0 += chunk) {
+      const int S = std::min(chunk, B - p0);
+      C.ycol = dcol.as<int>() + p0;
+      BatchFailure fail;
+      FLGP_TRY(ws_batch_chunk(st.s, W, ep, dts.as<double>() + p0, S, tol, max_iter, p0, its.data() + p0, fail));
+      if (fail.problem >= 0) {
+        const int rc = GpcNewton::pivot_error(fail.bad, who, fail.iter);
+        name_failure(fail.problem, std::string(flgp_last_error()));
+        return rc;
+      }
+      double *cm = dmean.as<double>() + p0 * colb, *cc = dcov.as<double>() + p0 * colb;
+      if (fused) {
+        // one pass over the rows idx1 of the pair for the chunk's S operands
+        FLGP_TRY(gpc_predict_rows_multi(st.s, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, S, W.Gf.as<double>(),
+                                        sigma22, cm, cc, (long)mnew));
+      } else {
+        for (int s = 0; s < S; ++s)
+          FLGP_TRY(predict_rows(st.s, ep, K, r1, W.Li.as<double>() + s * C.sq, C.u + s * C.sk, sigma22, cm + s * colb, cc + s * colb));
+      }
+    }
+  }
+  FLGP_TRY(d2h(mean, dmean.p, nb, st.s));
+  FLGP_TRY(d2h(cov, dcov.p, nb, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  if (iters) std::copy(its.begin(), its.end(), iters);
+  return FLGP_OK;
 }
 
 // ---- regression posterior: the drivers' testing step (src/Fit.cpp:70-79) in one call --------------------

@@ -947,6 +947,160 @@ int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int 
   return launch(gpc_predict_rows_multi_kernel<1>);
 }
 
+// ---- the weight-space Newton loop and the predictive operands for a chunk of problems (WsBatch, eigenpair.hip)
+// The steps of GpcWeightSpace that the lrb_* kernels above do not already have, in their form: the slot in blockIdx.y
+// through the device list, a workgroup on its own slot only.  Each keeps the expression tree of the kernel it stands
+// beside (gpc_w_kernel without N, gpc_ws_bd_kernel, gpc_ws_fnew_kernel, tri_inv_diag_kernel, gpr_scale_kernel's column
+// scaling, gpc_predict_prep_kernel), so a slot's bits are the binary entry's.  bd = b / D sits in the chunk's c, p in its g.
+
+// pi = logistic(f), W = pi (1 - pi): sW = W^1/2, b = W f + (Y - pi)   (N = 1, src/Utils.cpp:269-276)
+__global__ void wsb_w_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long s = act[blockIdx.y], o = s * c.sv + i;
+  const double fi = c.f[o], yi = c.Y[(size_t)c.ycol[s] * c.ldy + i];
+  const double pi = 1.0 / (1.0 + exp(-fi));
+  const double W = pi * (1.0 - pi);
+  const double bi = W * fi + (yi - pi);
+  c.sW[o] = __builtin_sqrt(W);
+  c.b[o] = bi;
+}
+
+// c = b / D
+__global__ void wsb_bd_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long o = (long)act[blockIdx.y] * c.sv + i;
+  c.c[o] = c.b[o] / c.D[o];
+}
+
+// f_new = p + sigma (b - W p) / D with W = sW^2 and p = g
+__global__ void wsb_fnew_kernel(LrChunk c, const int *__restrict__ act) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long o = (long)act[blockIdx.y] * c.sv + i;
+  const double s = c.sW[o], pi = c.g[o];
+  c.fnew[o] = pi + c.sigma * ((c.b[o] - (s * s) * pi) / c.D[o]);
+}
+
+// tri_inv_diag_kernel on the slot's factor: X(b0:b0+nb, b0:b0+nb) = L_Q(b0:b0+nb, b0:b0+nb)^-1 for block b0 = 64 blockIdx.x,
+// lane c one column by forward substitution (the block width is tri_inverse's, which is the factorisation's panel width)
+__global__ __launch_bounds__(64) void wsb_tri_inv_diag_kernel(LrChunk ch, const int *__restrict__ act, double *__restrict__ Xall) {
+  const long s = act[blockIdx.y];
+  if (ch.flag[s]) return;
+  const double *__restrict__ L = ch.Q + s * ch.sq;
+  double *__restrict__ X = Xall + s * ch.sq;
+  const int m = ch.K;
+  const long lda = ch.K, ldx = ch.K;
+  __shared__ double Lt[CNB][CNB];       // Lt[k][i] = L(b0 + i, b0 + k)
+  __shared__ double xs[CNB][CNB + 1];   // xs[i][c] = X(b0 + i, b0 + c)
+  const int c = threadIdx.x, b0 = blockIdx.x * CNB, nb = min(CNB, m - b0);
+  for (int e = c; e < CNB * CNB; e += CNB) {
+    const int i = e % CNB, k = e / CNB;
+    Lt[k][i] = (i < nb && k <= i) ? L[(size_t)(b0 + k) * lda + b0 + i] : (i == k ? 1.0 : 0.0);
+  }
+  __syncthreads();
+  for (int i = 0; i < nb; ++i) {
+    double acc = (i == c) ? 1.0 : 0.0;
+    for (int k = 0; k < i; ++k) acc -= Lt[k][i] * xs[k][c];
+    xs[i][c] = acc / Lt[i][i];
+  }
+  __syncthreads();
+  for (int e = c; e < nb * nb; e += CNB) {
+    const int i = e % nb, k = e / nb;
+    X[(size_t)(b0 + k) * ldx + b0 + i] = xs[i][k];
+  }
+}
+
+// M(i, j) *= ls(j) on the slot's K x K matrix
+__global__ void wsb_scale_cols_kernel(LrChunk c, const int *__restrict__ act, double *__restrict__ M) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)c.K * c.K) return;
+  const long s = act[blockIdx.y];
+  const int j = (int)(e / c.K);
+  double v = M[s * c.sq + e];
+  v *= c.ls[s * c.sk + j];
+  M[s * c.sq + e] = v;
+}
+
+// gpc_predict_prep_kernel on the slot's G and u: operand s at Gf + s total
+__global__ void wsb_predict_prep_kernel(LrChunk c, const int *__restrict__ act, const double *__restrict__ Gall, int nks, long total,
+                                        double *__restrict__ Gf) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const long s = act[blockIdx.y];
+  const double *__restrict__ G = Gall + s * c.sq, *__restrict__ u = c.u + s * c.sk;
+  const int K = c.K;
+  const int lane = (int)(e & 63);
+  const long f = e >> 6;
+  const int ks = (int)(f % nks), jt = (int)(f / nks);
+  const int j = 16 * jt + (lane & 15), k = 4 * ks + (lane >> 4);
+  double v = 0.0;
+  if (k < K) {
+    if (j < K) v = k <= j ? G[(size_t)k * K + j] : 0.0;
+    else if (j == K) v = u[k];
+  }
+  Gf[s * total + e] = v;
+}
+
+int wsb_w(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(wsb_w_kernel, dim3(ceil_div(c.m, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("wsb_w_kernel");
+}
+int wsb_bd(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(wsb_bd_kernel, dim3(ceil_div(c.m, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("wsb_bd_kernel");
+}
+int wsb_fnew(hipStream_t st, const LrChunk &c, const int *act, int A) {
+  hipLaunchKernelGGL(wsb_fnew_kernel, dim3(ceil_div(c.m, 256), A), dim3(256), 0, st, c, act);
+  return check_launch("wsb_fnew_kernel");
+}
+int wsb_scale_cols(hipStream_t st, const LrChunk &c, const int *act, int A, double *dM) {
+  hipLaunchKernelGGL(wsb_scale_cols_kernel, dim3(ceil_div((long)c.K * c.K, 256), A), dim3(256), 0, st, c, act, dM);
+  return check_launch("wsb_scale_cols_kernel");
+}
+int wsb_predict_prep(hipStream_t st, const LrChunk &c, const int *act, int A, const double *dG, double *d_Gf) {
+  const long total = (long)gpc_predict_operand_elems(c.K);
+  hipLaunchKernelGGL(wsb_predict_prep_kernel, dim3(ceil_div(total, 256), A), dim3(256), 0, st, c, act, dG, ceil_div(c.K, 4), total,
+                     d_Gf);
+  return check_launch("wsb_predict_prep_kernel");
+}
+
+// the planes one slot needs for the split products of wsb_tri_inverse: the largest over its block rows
+size_t wsb_tri_inverse_planes(int K, size_t we) {
+  size_t pe = 0;
+  for (int r0 = CNB; r0 < K; r0 += CNB) {
+    const int nb = std::min(CNB, K - r0);
+    pe = std::max(pe, (size_t)gemm_plan_split(nb, r0, r0, we) * nb * r0);
+  }
+  return pe;
+}
+
+// tri_inverse (gpr_grad.hip) on the factor in Q of every slot 0 .. A-1 (`all`: the device list 0, 1, ..), X = L_Q^-1 at Q's
+// stride: one memset, the diagonal blocks of every slot in one launch, then per block row its two products for all slots
+// in one launch each.  The first takes the split an unbatched tri_inverse with a workspace of `we` doubles chooses, on the
+// slot's own planes (part at stride sp, pe >= wsb_tri_inverse_planes(K, we) doubles each); T holds 64 x K per slot at stride st_.
+int wsb_tri_inverse(hipStream_t st, const LrChunk &c, const int *all, int A, double *dX, double *dT, long st_, double *part,
+                    size_t pe, long sp, size_t we) {
+  const int m = c.K;
+  const long lda = c.K, ldx = c.K;
+  ProfScope ps("tri_inverse_batch", st, (double)A * m * m * m / 3.0);
+  FLGP_HIP(hipMemsetAsync(dX, 0, sizeof(double) * (size_t)A * c.sq, st));
+  const int nblk = ceil_div(m, CNB);
+  hipLaunchKernelGGL(wsb_tri_inv_diag_kernel, dim3(nblk, A), dim3(CNB), 0, st, c, all, dX);
+  FLGP_TRY(check_launch("wsb_tri_inv_diag_kernel"));
+  for (int r = 1; r < nblk; ++r) {
+    const int r0 = r * CNB, nb = std::min(CNB, m - r0);
+    const GemmBatch g1{A, all, c.sq, c.sq, st_, 0, sp};
+    FLGP_TRY(gemm_launch(st, nb, r0, r0, 1.0, c.Q + r0, 1, lda, dX, 1, ldx, 0.0, nullptr, 0, 0, dT, 1, CNB, part, pe, 0.0, nullptr,
+                         nullptr, nullptr, gemm_plan_split(nb, r0, r0, we), nullptr, &g1));
+    const GemmBatch g2{A, all, c.sq, st_, c.sq, 0, 0};
+    FLGP_TRY(gemm_launch(st, nb, r0, nb, -1.0, dX + (size_t)r0 * ldx + r0, 1, ldx, dT, 1, CNB, 0.0, nullptr, 0, 0, dX + r0, 1, ldx,
+                         nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0, nullptr, &g2));
+  }
+  return FLGP_OK;
+}
+
 // ---- the regression posterior's rows: q mean rows under the triangle ------------------------------------
 // The operand Gp = [G ; U^T] ((K + q) x K: G lower triangular at ld K, or nullptr for zeros when no variance is wanted;
 // U K x q at ld K) in the fragment order of gpc_predict_prep_kernel, njt = ceil((K + q) / 16) j-tiles.
