@@ -171,7 +171,13 @@ _SIGNATURES = {
     "flgp_dev_hk_rows_route": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "flgp_dev_hk_rows": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, P, c_double, P, c_int, c_int,
                                  P, c_int, P]),
-    "flgp_dev_hk": (c_int, [P, P, c_int, c_double, P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int,
+    "flgp_dev_row_tiles_route": (c_int, [c_int, c_int, c_int]),
+    "flgp_dev_row_tiles_bytes": (c_size_t, [c_int, c_int]),
+    "flgp_dev_row_tiles_pack": (c_int, [P, P, P, c_int, c_int, P]),
+    "flgp_dev_u_recover_tiles": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, c_int, P, c_int, P, P]),
+    "flgp_dev_hk_rows_tiles": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_double, P, c_double, P, c_int, c_int,
+                                       P, c_int, P]),
+    "flgp_dev_hk":(c_int, [P, P, c_int, c_double, P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int,
                             P, c_int, P]),
     "flgp_dev_cholesky": (c_int, [P, P, c_int, c_int, P]),
     "flgp_dev_chol_solve": (c_int, [P, P, c_int, P, c_int, c_int, P]),

@@ -277,14 +277,16 @@ int csr_out(Sim &S, hipStream_t st, int *csr_p, int *csr_j, double *csr_x) {
 // spectrum_from_Z_cpp on the device ELL (reference src/Spectrum.cpp:146-161): leaves values (K)
 // and vectors (n x K) on the device
 struct Spectrum {
-  DevBuf G, rec, eig, V, values, vectors, work, uwork;     // values / vectors: the caller's where it has set (borrowed) them
+  DevBuf G, rec, tiles, eig, V, values, vectors, work, uwork;     // values / vectors: the caller's where it has set (borrowed) them
+                                                                  // tiles: the wave tiles of the scaled rows, where they were packed
   int K = 0;
   int vec_rows = 0;     // rows of `vectors` (its leading dimension): S.n, or the caller's row limit
 };
 
 // row_limit >= 0: only the first row_limit local rows of the vectors are recovered (a caller that takes H from the sparse
-// rows needs the training rows it owns and nothing else: no n x K store)
-int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info, int row_limit = -1) {
+// rows needs the training rows it owns and nothing else: no n x K store).  rows_follow: the caller goes on to
+// flgp_dev_hk_rows_tiles, so the tiles are packed even where the recovery itself has too few rows to read them.
+int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info, int row_limit = -1, bool rows_follow = false) {
   if (K < 0) K = S.s;   // reference: K < 0 -> s (src/Spectrum.cpp:31-33,69-71; src/TruncatedSVD.cpp:11-13)
   FLGP_REQUIRE(K >= 1 && K <= S.s, "need 1 <= K <= s (K=%d, s=%d)", K, S.s);
   P.K = K;
@@ -326,9 +328,21 @@ int spectrum(Sim &S, hipStream_t st, int K, int root, Spectrum &P, int *info, in
   FLGP_TRY(flgp_dev_spectrum_usable_route(st, P.eig.as<double>(), K, solve_info[2]));
   // u = A v / sigma, vectors = u sqrt(n), values = sigma^2 (or sigma if root)  (:153-158)
   if (!P.values.p) FLGP_TRY(P.values.alloc(sizeof(double) * (size_t)K));
+  // the scaled rows as wave tiles for the LDS row kernel (flgp_dev_row_tiles_route: knob row_tiles): one coalesced request per
+  // wave and pair.  Packed here, behind the eigensolver, so that the row kernels find them in the cache; the tiles of the
+  // first vec_rows rows are a prefix of them.
   P.vec_rows = row_limit >= 0 && row_limit < S.n ? row_limit : S.n;
+  const bool tiles_recover = flgp_dev_row_tiles_route(P.vec_rows, S.r, S.s) != 0;
+  if (tiles_recover || (rows_follow && flgp_dev_row_tiles_route(S.n, S.r, S.s))) {
+    FLGP_TRY(P.tiles.alloc(flgp_dev_row_tiles_bytes(S.n, S.r)));
+    FLGP_TRY(flgp_dev_row_tiles_pack(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), S.n, S.r, P.tiles.p));
+  }
   if (!P.vectors.p) FLGP_TRY(P.vectors.alloc(sizeof(double) * (size_t)std::max(P.vec_rows, 1) * K));
   FLGP_TRY(P.uwork.alloc(flgp_dev_u_recover_workspace(S.s, K)));
+  if (P.tiles.p && tiles_recover)
+    return flgp_dev_u_recover_tiles(st, P.tiles.p, P.vec_rows, S.r, P.V.as<double>(), S.s, S.s, P.eig.as<double>(), K,
+                                    std::sqrt((double)(S.n_global ? S.n_global : (long)S.n)), root, P.vectors.as<double>(),
+                                    std::max(P.vec_rows, 1), P.values.as<double>(), P.uwork.as<double>());
   return flgp_dev_u_recover(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), P.vec_rows, S.r, P.V.as<double>(), S.s, S.s,
                             P.eig.as<double>(), K, std::sqrt((double)(S.n_global ? S.n_global : (long)S.n)), root,
                             P.vectors.as<double>(), std::max(P.vec_rows, 1), P.values.as<double>(), P.uwork.as<double>());
@@ -1023,7 +1037,7 @@ extern "C" int flgp_dev_heat_kernel_covariance_sharded(void *stream, const flgp_
   const int hk_rows = flgp_dev_hk_rows_route(n_loc, r, s, K, m);
   const long own = row_lo < m ? std::min<long>(row_lo + n_loc, (long)m) - row_lo : 0;     // training rows of this rank
   Spectrum P;
-  FLGP_TRY(spectrum(S, st, K, root, P, info, hk_rows && !d_vectors_out ? (int)own : -1));
+  FLGP_TRY(spectrum(S, st, K, root, P, info, hk_rows && !d_vectors_out ? (int)own : -1, hk_rows != 0));
   // exchange 4: the training block V[0:m] (m x K), zero where this rank owns no row of it, summed over the ranks
   DevBuf V1, work;
   FLGP_TRY(V1.alloc(sizeof(double) * (size_t)m * K));
@@ -1038,9 +1052,14 @@ extern "C" int flgp_dev_heat_kernel_covariance_sharded(void *stream, const flgp_
     // (as long as every rank takes this route: a rank with fewer than 10000 rows keeps the contraction, and its rows of H
     // then differ from the one-rank H in their last bits).
     FLGP_TRY(work.alloc(flgp_dev_hk_rows_workspace(s, m, K)));
-    FLGP_TRY(flgp_dev_hk_rows(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), n_loc, S.r, P.V.as<double>(), s, s, P.eig.as<double>(), K,
-                              std::sqrt((double)n_global), P.values.as<double>(), t, V1.as<double>(), m, m, dH_loc, ldh,
-                              work.as<double>()));
+    if (P.tiles.p)
+      FLGP_TRY(flgp_dev_hk_rows_tiles(st, P.tiles.p, n_loc, S.r, P.V.as<double>(), s, s, P.eig.as<double>(), K,
+                                      std::sqrt((double)n_global), P.values.as<double>(), t, V1.as<double>(), m, m, dH_loc, ldh,
+                                      work.as<double>()));
+    else
+      FLGP_TRY(flgp_dev_hk_rows(st, S.ell_idx.as<int>(), S.ell_val.as<double>(), n_loc, S.r, P.V.as<double>(), s, s,
+                                P.eig.as<double>(), K, std::sqrt((double)n_global), P.values.as<double>(), t, V1.as<double>(), m, m,
+                                dH_loc, ldh, work.as<double>()));
   } else {
     FLGP_TRY(work.alloc(flgp_dev_hk_workspace(n_loc, m, K, 0)));
     FLGP_TRY(flgp_dev_hk(st, P.values.as<double>(), K, t, P.vectors.as<double>(), n_loc, nullptr, 0, n_loc, V1.as<double>(), m, nullptr,

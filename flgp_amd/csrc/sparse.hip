@@ -648,6 +648,49 @@ static int u_lds_width(int s) {
   return w > 4 ? 4 : (int)w;
 }
 
+// pairs per step of u_recover_lds_kernel: a row is ceil(r / 2) pairs, walked in the fewest steps of at most U_LDS_MAX_PAIRS,
+// all of one size: one step up to r = 12, two steps of 4..6 pairs up to r = 24, three of 5 or 6 up to r = 32.  At most two
+// pairs, in the row's last step, are loaded for nothing.  (Seven and eight pairs in two buffers spill at four eigen-columns.)
+constexpr int U_LDS_MAX_PAIRS = 6;
+static int u_lds_pairs(int r) {
+  const int pairs = (r + 1) / 2, steps = ceil_div(pairs, U_LDS_MAX_PAIRS);
+  return ceil_div(pairs, steps);
+}
+
+// ----------------------------------------------------------------------------------------
+// Wave tiles of the ELL rows: what a wave of u_recover_lds_kernel (lane = row) loads in one instruction, stored contiguously.
+// Tile T holds rows 64 T .. 64 T + 63: PT x 64 value pairs of 16 bytes, pair p of lane l at (p 64 + l) 16, then PT x 64 index
+// pairs of 8 bytes in the same order; pair p of a row is its entries 2 p and 2 p + 1, and PT = steps x u_lds_pairs(r) is the
+// number of pair slots the row kernel loads per row (5 at r = 10, 8 at r = 13, 15 at r = 25).  A tile is PT 1536 bytes, so every
+// tile starts on a 128-byte edge.  Slots past r and rows past n hold value 0.0 and index 0: they are loaded (every load is
+// unconditional and in bounds) and never summed.  A wave's load is then one coalesced 1 KB (values) or 512 B (indices) request:
+// 8 + 4 cache lines where the row-major arrays (80-byte and 40-byte stride at r = 10) give 40 + 20.
+// ----------------------------------------------------------------------------------------
+static int row_tile_pairs(int r) { return ceil_div((r + 1) / 2, U_LDS_MAX_PAIRS) * u_lds_pairs(r); }
+constexpr int ROW_TILE_PAIR_BYTES = 64 * (16 + 8);
+// one thread per (tile, pair slot, lane): strided reads (it runs once per step), 1 KB / 512 B coalesced writes per wave
+__global__ __launch_bounds__(256) void row_tiles_pack_kernel(const int *__restrict__ ell_idx, const double *__restrict__ val, int n,
+                                                             int r, int pt, long slots, char *__restrict__ tiles) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  typedef int i2 __attribute__((ext_vector_type(2)));
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;       // (tile pt + p) 64 + lane
+  if (g >= slots) return;
+  const int lane = (int)(g & 63);
+  const long tp = g >> 6, tile = tp / pt;
+  const int p = (int)(tp - tile * pt);
+  const long row = tile * 64 + lane;
+  d2 z = {0.0, 0.0};
+  i2 j = {0, 0};
+  if (row < n) {
+    const long b = row * r + 2 * p;
+    if (2 * p < r) { z[0] = val[b]; j[0] = ell_idx[b]; }
+    if (2 * p + 1 < r) { z[1] = val[b + 1]; j[1] = ell_idx[b + 1]; }
+  }
+  char *tb = tiles + (size_t)tile * pt * ROW_TILE_PAIR_BYTES;
+  ((d2 *)tb)[p * 64 + lane] = z;
+  ((i2 *)(tb + (size_t)pt * 1024))[p * 64 + lane] = j;
+}
+
 // Vts[slice][j][c] = V(j, slice W + c), columns past K zero: the image a workgroup of u_recover_lds_kernel copies into LDS
 template <int W>
 __global__ __launch_bounds__(256) void transpose_v_slices_kernel(const double *__restrict__ V, int ldv, int s, int K,
@@ -666,10 +709,12 @@ __global__ __launch_bounds__(256) void transpose_v_slices_kernel(const double *_
 // random anchors would use the even ones of the 16 slots of a bank row only; bit 3 of the anchor swaps its halves.
 template <int W> __device__ __forceinline__ int u_lds_slot(int q) { return W == 4 ? q ^ (((q >> 5) & 1) << 1) : q; }
 
-// NP: pairs of entries per step (u_lds_pairs below: the fewest equal steps of at most six pairs that cover a row).
+// NP: pairs of entries per step (u_lds_pairs above: the fewest equal steps of at most six pairs that cover a row).
 // RAW: the sums are stored as they are, out(i, k) = sum_a val(i, a) M(idx(i, a), k), and eig / scale are not read (the heat-kernel
 // rows of flgp_dev_hk_rows, where M is the s x m matrix Wm and the scaling is already inside it).
-template <int W, int NP, bool RAW>
+// TIL: the rows come from their wave tiles (row_tiles_pack_kernel), passed as `val`; ell_idx is not read.  Only the loads
+// differ: the same values and indices reach the same sums in the same order.
+template <int W, int NP, bool RAW, bool TIL>
 __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(const int *__restrict__ ell_idx,
                                                                               const double *__restrict__ val, int n, int r, int s,
                                                                               const double *__restrict__ Vts,
@@ -688,6 +733,10 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
     const int k = sl * W + c;
     const double e = (!RAW && k < K) ? eig[k] : 0.0;
     sg[c] = __builtin_sqrt(e > 0.0 ? e : 0.0);
+    if constexpr (TIL && !RAW) {          // the same in every lane: kept in scalar registers, it leaves the loop its 128 VGPRs
+      sg[c] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(sg[c])),
+                               __builtin_amdgcn_readfirstlane(__double2loint(sg[c])));
+    }
   }
   __syncthreads();
   const long i_lo = (long)blockIdx.x * rows_per_range;
@@ -704,17 +753,44 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
   // the most for which two buffers and the gathered anchors stay inside the 128 VGPRs of a 1024-thread workgroup
   constexpr int GB = NP <= 4 ? CE : (W == 4 && NP == 6) ? 4 : NP;
   struct Chunk { double z0[NP], z1[NP]; int j0[NP], j1[NP]; };
-  auto fetch = [&](long i, int ch) {
+  // TIL: a wave's 64 rows are one tile (ranges are whole waves of rows), so the base is uniform and a pair is one 16-byte and
+  // one 8-byte load at base + lane x size + a constant; a wave whose rows all lie past the range re-reads the range's first
+  // tile.  No pair reaches into the next row, so nothing is ever `moved`.
+  typedef int i2 __attribute__((ext_vector_type(2)));
+  const int pt = (((r + 1) / 2 + U_LDS_MAX_PAIRS - 1) / U_LDS_MAX_PAIRS) * NP;       // row_tile_pairs(r)
+  const int lane = tid & 63, wave0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+  // row i = i_lo + tid + rd T of chunk ch (rd, the round, only so that the tile's address is built from uniform values alone)
+  auto fetch = [&](long i, int ch, int rd) {
     Chunk c;
+    if constexpr (TIL) {
+      const int w0 = (int)i_lo + wave0 + rd * T;                       // the wave's first row
+      const int tile = (w0 < (int)i_hi ? w0 : (int)i_lo) >> 6;
+      // scalar bases, set 2 KB into the step's values so that every pair's constant fits the load's signed 13-bit offset
+      typedef const __attribute__((address_space(1))) char *gbytes;
+      typedef const __attribute__((address_space(1))) d2 *gd2;
+      typedef const __attribute__((address_space(1))) i2 *gi2;
+      const size_t tb = (size_t)val + (size_t)tile * (size_t)(pt * ROW_TILE_PAIR_BYTES);
+      size_t zb = tb + (ch * (NP * 1024) + 2048);
+      size_t jb = tb + (pt * 1024 + ch * (NP * 512));
+      asm("" : "+s"(zb), "+s"(jb));       // the bases stay scalar: left to itself, the loop carries per-lane 64-bit addresses
 #pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      const int a = CE * ch + 2 * u;
-      long b = (i < i_hi && a < r) ? i * r + a : i_lo * r;
-      b = b < last_pair ? b : last_pair;
-      const d2u z = *(const d2u *)(val + b);
-      const i2u j = *(const i2u *)(ell_idx + b);
-      c.z0[u] = z[0]; c.z1[u] = z[1];
-      c.j0[u] = j[0]; c.j1[u] = j[1];
+      for (int u = 0; u < NP; ++u) {
+        const d2 z = *(gd2)((gbytes)zb + (size_t)(unsigned)(lane * 16) + (u * 1024 - 2048));
+        const i2 j = *(gi2)((gbytes)jb + (size_t)(unsigned)(lane * 8) + u * 512);
+        c.z0[u] = z[0]; c.z1[u] = z[1];
+        c.j0[u] = j[0]; c.j1[u] = j[1];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < NP; ++u) {
+        const int a = CE * ch + 2 * u;
+        long b = (i < i_hi && a < r) ? i * r + a : i_lo * r;
+        b = b < last_pair ? b : last_pair;
+        const d2u z = *(const d2u *)(val + b);
+        const i2u j = *(const i2u *)(ell_idx + b);
+        c.z0[u] = z[0]; c.z1[u] = z[1];
+        c.j0[u] = j[0]; c.j1[u] = j[1];
+      }
     }
     return c;
   };
@@ -757,7 +833,7 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
     } else {
 #pragma unroll
       for (int u = 0; u < NP; ++u) {
-        const bool moved = i * r + ch * CE + 2 * u > last_pair;         // only the last slot of the last row, r odd
+        const bool moved = !TIL && i * r + ch * CE + 2 * u > last_pair; // only the last slot of the last row, r odd
 #pragma unroll
         for (int h = 0; h < 2; ++h)
           if (2 * u + h < left) {
@@ -784,15 +860,15 @@ __global__ __launch_bounds__(U_RECOVER_LDS_THREADS) void u_recover_lds_kernel(co
   // handed on at the end of the step would wait for them at the hand-over.)
   const long nit = i_hi > i_lo ? (i_hi - i_lo + T - 1) / T : 0;
   const long steps = nit * nch;
-  long ia = i_lo + tid; int cha = 0;                                   // step t
-  auto next = [&](long &i, int &ch) { if (++ch == nch) { ch = 0; i += T; } };
-  Chunk A = fetch(ia, cha), B;
+  long ia = i_lo + tid; int cha = 0, rda = 0;                          // step t
+  auto next = [&](long &i, int &ch, int &rd) { if (++ch == nch) { ch = 0; i += T; ++rd; } };
+  Chunk A = fetch(ia, cha, rda), B;
   for (long t = 0; t < steps; t += 2) {
-    long ib = ia; int chb = cha; next(ib, chb);                        // step t + 1 (past the last step: masked loads)
-    B = fetch(ib, chb);
+    long ib = ia; int chb = cha, rdb = rda; next(ib, chb, rdb);        // step t + 1 (past the last step: masked loads)
+    B = fetch(ib, chb, rdb);
     apply(A, ia, cha);
-    ia = ib; cha = chb; next(ia, cha);
-    A = fetch(ia, cha);
+    ia = ib; cha = chb; rda = rdb; next(ia, cha, rda);
+    A = fetch(ia, cha, rda);
     if (t + 1 < steps) apply(B, ib, chb);
   }
 }
@@ -1098,19 +1174,11 @@ static int num_cus() {
   return cus[dev];
 }
 
-// pairs per step of u_recover_lds_kernel: a row is ceil(r / 2) pairs, walked in the fewest steps of at most U_LDS_MAX_PAIRS,
-// all of one size: one step up to r = 12, two steps of 4..6 pairs up to r = 24, three of 5 or 6 up to r = 32.  At most two
-// pairs, in the row's last step, are loaded for nothing.  (Seven and eight pairs in two buffers spill at four eigen-columns.)
-constexpr int U_LDS_MAX_PAIRS = 6;
-static int u_lds_pairs(int r) {
-  const int pairs = (r + 1) / 2, steps = ceil_div(pairs, U_LDS_MAX_PAIRS);
-  return ceil_div(pairs, steps);
-}
-
+// d_tiles: the wave tiles of the rows (flgp_dev_row_tiles_pack), or NULL to read the ELL arrays themselves
 template <int W, int NP, bool RAW>
-static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
-                                int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
-                                double *d_work) {
+static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, const void *d_tiles, int n, int r,
+                                const double *dV, int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors,
+                                int ldo, double *d_work) {
   const int slices = ceil_div(K, W);
   hipLaunchKernelGGL((transpose_v_slices_kernel<W>), dim3(ceil_div(s, 256), slices), dim3(256), 0, st, dV, ldv, s, K, d_work);
   FLGP_TRY(check_launch("transpose_v_slices_kernel"));
@@ -1120,20 +1188,29 @@ static int u_recover_lds_launch(hipStream_t st, const int *d_ell_idx, const doub
   int rows = ceil_div(ceil_div(n, ranges), 64) * 64;
   ranges = ceil_div(n, rows);
   const size_t lds = sizeof(double) * (size_t)s * W;
-  if (lds > 48 * 1024)
-    FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W, NP, RAW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((u_recover_lds_kernel<W, NP, RAW>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st, d_ell_idx, d_ell_val,
-                     n, r, s, d_work, d_eig, K, scale, d_vectors, ldo, rows);
+#define U_LDS_LAUNCH(TILv, idxv, valv)                                                                                         \
+  do {                                                                                                                         \
+    if (lds > 48 * 1024)                                                                                                       \
+      FLGP_HIP(hipFuncSetAttribute((const void *)u_recover_lds_kernel<W, NP, RAW, TILv>,                                       \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                     \
+    hipLaunchKernelGGL((u_recover_lds_kernel<W, NP, RAW, TILv>), dim3(ranges, slices), dim3(U_RECOVER_LDS_THREADS), lds, st,   \
+                       idxv, valv, n, r, s, d_work, d_eig, K, scale, d_vectors, ldo, rows);                                    \
+  } while (0)
+  if (d_tiles) U_LDS_LAUNCH(true, (const int *)nullptr, (const double *)d_tiles);
+  else U_LDS_LAUNCH(false, d_ell_idx, d_ell_val);
+#undef U_LDS_LAUNCH
   return FLGP_OK;
 }
 
 template <int W, bool RAW>
-static int u_recover_lds_pairs(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
-                               int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
-                               double *d_work) {
+static int u_recover_lds_pairs(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, const void *d_tiles, int n, int r,
+                               const double *dV, int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors,
+                               int ldo, double *d_work) {
   switch (u_lds_pairs(r)) {
 #define U_LDS_PAIRS(NPv)                                                                                                       \
-  case NPv: return u_recover_lds_launch<W, NPv, RAW>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)
+  case NPv:                                                                                                                    \
+    return u_recover_lds_launch<W, NPv, RAW>(st, d_ell_idx, d_ell_val, d_tiles, n, r, dV, ldv, s, d_eig, K, scale, d_vectors,  \
+                                             ldo, d_work)
     U_LDS_PAIRS(1); U_LDS_PAIRS(2); U_LDS_PAIRS(3); U_LDS_PAIRS(4); U_LDS_PAIRS(5);
     default: U_LDS_PAIRS(6);
 #undef U_LDS_PAIRS
@@ -1142,16 +1219,40 @@ static int u_recover_lds_pairs(hipStream_t st, const int *d_ell_idx, const doubl
 
 // the slice image of dV (s x K, ld = ldv) into d_work, then the LDS row kernel at the slice width of s
 template <bool RAW>
-static int u_recover_lds_width(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dV,
-                               int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors, int ldo,
-                               double *d_work) {
+static int u_recover_lds_width(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, const void *d_tiles, int n, int r,
+                               const double *dV, int ldv, int s, const double *d_eig, int K, double scale, double *d_vectors,
+                               int ldo, double *d_work) {
   switch (u_lds_width(s)) {
 #define U_LDS_CASE(Wv)                                                                                                         \
-  case Wv: return u_recover_lds_pairs<Wv, RAW>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work)
+  case Wv:                                                                                                                     \
+    return u_recover_lds_pairs<Wv, RAW>(st, d_ell_idx, d_ell_val, d_tiles, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo,  \
+                                        d_work)
     U_LDS_CASE(1); U_LDS_CASE(2); U_LDS_CASE(3);
     default: U_LDS_CASE(4);
 #undef U_LDS_CASE
   }
+}
+
+extern "C" size_t flgp_dev_row_tiles_bytes(int n, int r) {
+  if (n <= 0 || r < 1 || r > FLGP_RMAX) return 0;
+  return (size_t)ceil_div(n, 64) * (size_t)row_tile_pairs(r) * ROW_TILE_PAIR_BYTES;
+}
+
+// 1: the drivers pack the tiles and call the tiles entries (the LDS row kernel's conditions and the knob row_tiles, default 1)
+extern "C" int flgp_dev_row_tiles_route(int n, int r, int s) {
+  return tuning("row_tiles", 1) != 0 && r >= 1 && r <= FLGP_RMAX && flgp_dev_u_recover_route(n, r, s, 1, 1) == 4;
+}
+
+extern "C" int flgp_dev_row_tiles_pack(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, void *d_tiles) {
+  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && n >= 0, "row tiles: bad arguments");
+  if (n == 0) return FLGP_OK;
+  FLGP_REQUIRE(d_ell_idx && d_ell_val && d_tiles, "row tiles: null pointer");
+  FLGP_REQUIRE(((size_t)d_tiles & 127) == 0, "row tiles: the buffer must be 128-byte aligned");
+  const int pt = row_tile_pairs(r);
+  const long slots = (long)ceil_div(n, 64) * pt * 64;
+  hipLaunchKernelGGL(row_tiles_pack_kernel, dim3(ceil_div(slots, 256)), dim3(256), 0, (hipStream_t)stream, d_ell_idx, d_ell_val, n,
+                     r, pt, slots, (char *)d_tiles);
+  return check_launch("row_tiles_pack_kernel");
 }
 
 extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r,
@@ -1163,7 +1264,8 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
     ProfScope ps("u_recover_kernel", st, 12.0 * (double)n * r + 8.0 * (double)s * K + 8.0 * (double)n * K);
     const int route = flgp_dev_u_recover_route(n, r, s, K, d_work != nullptr);
     if (route == 4) {
-      FLGP_TRY(u_recover_lds_width<false>(st, d_ell_idx, d_ell_val, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work));
+      FLGP_TRY(u_recover_lds_width<false>(st, d_ell_idx, d_ell_val, nullptr, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo,
+                                          d_work));
     } else if (d_work) {
       hipLaunchKernelGGL(transpose_v_kernel, dim3(ceil_div(s, 32), ceil_div(K, 32)), dim3(256), 0, st, dV, ldv, s, K,
                          d_work);
@@ -1181,6 +1283,27 @@ extern "C" int flgp_dev_u_recover(void *stream, const int *d_ell_idx, const doub
       hipLaunchKernelGGL(u_recover_kernel, dim3(ceil_div(n, 256), ceil_div(K, 8)), dim3(256), 0, st, d_ell_idx,
                          d_ell_val, n, r, dV, ldv, d_eig, K, scale, d_vectors, ldo);
     }
+    FLGP_TRY(check_launch("u_recover_kernel"));
+  }
+  if (d_values_out) {
+    hipLaunchKernelGGL(values_out_kernel, dim3(ceil_div(K, 256)), dim3(256), 0, st, d_eig, K, root, d_values_out);
+    FLGP_TRY(check_launch("values_out_kernel"));
+  }
+  return FLGP_OK;
+}
+
+// flgp_dev_u_recover on the wave tiles of the rows: the LDS slice kernel (route 4) and nothing else
+extern "C" int flgp_dev_u_recover_tiles(void *stream, const void *d_tiles, int n, int r, const double *dV, int ldv, int s,
+                                        const double *d_eig, int K, double scale, int root, double *d_vectors, int ldo,
+                                        double *d_values_out, double *d_work) {
+  hipStream_t st = (hipStream_t)stream;
+  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && K >= 1 && ldo >= n, "u_recover_tiles: bad shape");
+  FLGP_REQUIRE(d_tiles && ((size_t)d_tiles & 127) == 0, "u_recover_tiles: the tiles must be there and 128-byte aligned");
+  FLGP_REQUIRE(flgp_dev_u_recover_route(n, r, s, K, d_work != nullptr) == 4,
+               "u_recover_tiles: no LDS slice route for n=%d r=%d s=%d (ask flgp_dev_u_recover_route)", n, r, s);
+  {
+    ProfScope ps("u_recover_kernel", st, 12.0 * (double)n * r + 8.0 * (double)s * K + 8.0 * (double)n * K);
+    FLGP_TRY(u_recover_lds_width<false>(st, nullptr, nullptr, d_tiles, n, r, dV, ldv, s, d_eig, K, scale, d_vectors, ldo, d_work));
     FLGP_TRY(check_launch("u_recover_kernel"));
   }
   if (d_values_out) {
@@ -1231,14 +1354,16 @@ extern "C" int flgp_dev_hk_rows_route(int n, int r, int s, int K, int m) {
   return (long)K * w >= (m >= HK_ROWS_PANEL2_M ? HK_ROWS_MIN_KW_PER_R : HK_ROWS_MIN_KW_PER_R_SMALL_M) * (long)r;
 }
 
-extern "C" int flgp_dev_hk_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dVs,
-                                int ldv, int s, const double *d_eig, int K, double scale, const double *d_values, double t,
-                                const double *dV1, int ld1, int m, double *dH, int ldh, double *d_work) {
+// the rows from the ELL arrays, or from their wave tiles where d_tiles is there; `who` names the entry in the messages
+static int hk_rows_run(const char *who, void *stream, const int *d_ell_idx, const double *d_ell_val, const void *d_tiles, int n, int r,
+                       const double *dVs, int ldv, int s, const double *d_eig, int K, double scale, const double *d_values, double t,
+                       const double *dV1, int ld1, int m, double *dH, int ldh, double *d_work) {
   hipStream_t st = (hipStream_t)stream;
-  FLGP_REQUIRE(d_ell_idx && d_ell_val && dVs && d_eig && d_values && dV1 && dH && d_work, "hk_rows: null pointer");
-  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && K >= 1 && m >= 1 && s >= 1 && ldv >= s && ld1 >= m && ldh >= n, "hk_rows: bad shape");
+  FLGP_REQUIRE((d_tiles || (d_ell_idx && d_ell_val)) && dVs && d_eig && d_values && dV1 && dH && d_work, "%s: null pointer", who);
+  FLGP_REQUIRE(((size_t)d_tiles & 127) == 0, "%s: the tiles must be 128-byte aligned", who);
+  FLGP_REQUIRE(r >= 1 && r <= FLGP_RMAX && K >= 1 && m >= 1 && s >= 1 && ldv >= s && ld1 >= m && ldh >= n, "%s: bad shape", who);
   FLGP_REQUIRE(u_lds_width(s) >= 1 && n >= U_RECOVER_LDS_MIN_N && (long)n * r >= 2,
-               "hk_rows: no LDS slice for n=%d r=%d s=%d (ask flgp_dev_hk_rows_route)", n, r, s);
+               "%s: no LDS slice for n=%d r=%d s=%d (ask flgp_dev_hk_rows_route)", who, n, r, s);
   const HkRowsLayout L = hk_rows_layout(s, m, K);
   double *B = d_work + L.b, *Vw = d_work + L.vw, *Wm = d_work + L.wm, *image = d_work + L.image;
   hipLaunchKernelGGL(hk_rows_b_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, dVs, ldv, s, d_eig, K, scale, B);
@@ -1247,5 +1372,22 @@ extern "C" int flgp_dev_hk_rows(void *stream, const int *d_ell_idx, const double
   // Wm(j, b) = sum_k B(j, k) Vw(b, k): no workspace, so one k-ascending MFMA chain per element (never split)
   FLGP_TRY(gemm_launch(st, s, m, K, 1.0, B, 1, s, Vw, m, 1, 0.0, nullptr, 0, 0, Wm, 1, s, nullptr, 0, 0.0, nullptr));
   ProfScope ps("hk_rows_kernel", st, 2.0 * (double)n * r * m);     // (with the slice image of Wm: 16 s m bytes)
-  return u_recover_lds_width<true>(st, d_ell_idx, d_ell_val, n, r, Wm, s, s, nullptr, m, 1.0, dH, ldh, image);
+  return u_recover_lds_width<true>(st, d_ell_idx, d_ell_val, d_tiles, n, r, Wm, s, s, nullptr, m, 1.0, dH, ldh, image);
+}
+
+extern "C" int flgp_dev_hk_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *dVs,
+                                int ldv, int s, const double *d_eig, int K, double scale, const double *d_values, double t,
+                                const double *dV1, int ld1, int m, double *dH, int ldh, double *d_work) {
+  FLGP_REQUIRE(d_ell_idx && d_ell_val, "hk_rows: null pointer");
+  return hk_rows_run("hk_rows", stream, d_ell_idx, d_ell_val, nullptr, n, r, dVs, ldv, s, d_eig, K, scale, d_values, t, dV1, ld1, m,
+                     dH, ldh, d_work);
+}
+
+// flgp_dev_hk_rows on the wave tiles of the rows (flgp_dev_row_tiles_pack)
+extern "C" int flgp_dev_hk_rows_tiles(void *stream, const void *d_tiles, int n, int r, const double *dVs, int ldv, int s,
+                                      const double *d_eig, int K, double scale, const double *d_values, double t,
+                                      const double *dV1, int ld1, int m, double *dH, int ldh, double *d_work) {
+  FLGP_REQUIRE(d_tiles, "hk_rows_tiles: null pointer");
+  return hk_rows_run("hk_rows_tiles", stream, nullptr, nullptr, d_tiles, n, r, dVs, ldv, s, d_eig, K, scale, d_values, t, dV1, ld1,
+                     m, dH, ldh, d_work);
 }

@@ -163,8 +163,19 @@ class HipStages:
         return eig, V, dict(outer_iterations=info[0], g_products=info[1], dense=bool(info[2]),
                             newton_schulz_orths=info[3] // 1000, jacobi_orths=info[3] % 1000)
 
-    def u_recover(self, ell_idx, ell_val, V, eig, scale, root, dense=None):
-        """dense: did the full decomposition deliver `eig` (eig_topk's info["dense"])?  Default: K == s."""
+    def row_tiles(self, ell_idx, ell_val, s):
+        """The rows as wave tiles for the LDS row kernel of u_recover / hk_rows (flgp_dev_row_tiles_pack), or None where
+        flgp_dev_row_tiles_route says that the row-major arrays are read (shape, knob row_tiles)."""
+        n, r = ell_idx.shape
+        if not self.L.flgp_dev_row_tiles_route(n, r, s):
+            return None
+        tiles = self.empty((self.L.flgp_dev_row_tiles_bytes(n, r) // 8,))
+        _lib.check(self.L.flgp_dev_row_tiles_pack(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, r, tiles.data_ptr()))
+        return tiles
+
+    def u_recover(self, ell_idx, ell_val, V, eig, scale, root, dense=None, tiles=None):
+        """dense: did the full decomposition deliver `eig` (eig_topk's info["dense"])?  Default: K == s.
+        tiles: row_tiles() of these arrays, or None."""
         n, r = ell_idx.shape
         K, s = V.shape
         if dense is None:
@@ -172,6 +183,11 @@ class HipStages:
         values = self.empty((K,)); vectors = self.empty((K, max(n, 1)))
         work = self.empty((self.L.flgp_dev_u_recover_workspace(s, K) // 8 + 1,))
         _lib.check(self.L.flgp_dev_spectrum_usable_route(self._st(), eig.data_ptr(), K, int(bool(dense))))   # sigma_K resolved, or the reason why not
+        if tiles is not None:
+            _lib.check(self.L.flgp_dev_u_recover_tiles(self._st(), tiles.data_ptr(), n, r, V.data_ptr(), s, s, eig.data_ptr(), K,
+                                                       float(scale), int(bool(root)), vectors.data_ptr(), max(n, 1),
+                                                       values.data_ptr(), work.data_ptr()))
+            return values, vectors
         _lib.check(self.L.flgp_dev_u_recover(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, r, V.data_ptr(), s, s,
                                              eig.data_ptr(), K, float(scale), int(bool(root)), vectors.data_ptr(), max(n, 1),
                                              values.data_ptr(), work.data_ptr()))
@@ -191,13 +207,19 @@ class HipStages:
         """Does hk_rows compute H for this shape (flgp_dev_hk_rows_route)?  Otherwise the caller keeps u_recover + hk."""
         return bool(self.L.flgp_dev_hk_rows_route(n, r, s, K, m))
 
-    def hk_rows(self, ell_idx, ell_val, V, eig, scale, values, t, V1):
-        """H (m, n) from the sparse rows: H = A (Vs diag(scale / sigma) Vw^T), without the n x K vectors."""
+    def hk_rows(self, ell_idx, ell_val, V, eig, scale, values, t, V1, tiles=None):
+        """H (m, n) from the sparse rows: H = A (Vs diag(scale / sigma) Vw^T), without the n x K vectors.
+        tiles: row_tiles() of these arrays, or None."""
         n, r = ell_idx.shape
         K, s = V.shape
         m = V1.shape[1]
         H = self.empty((m, n))
         work = self.empty((self.L.flgp_dev_hk_rows_workspace(s, m, K) // 8 + 1,))
+        if tiles is not None:
+            _lib.check(self.L.flgp_dev_hk_rows_tiles(self._st(), tiles.data_ptr(), n, r, V.data_ptr(), s, s, eig.data_ptr(), K,
+                                                     float(scale), values.data_ptr(), float(t), V1.data_ptr(), m, m, H.data_ptr(), n,
+                                                     work.data_ptr()))
+            return H
         _lib.check(self.L.flgp_dev_hk_rows(self._st(), ell_idx.data_ptr(), ell_val.data_ptr(), n, r, V.data_ptr(), s, s, eig.data_ptr(),
                                            K, float(scale), values.data_ptr(), float(t), V1.data_ptr(), m, m, H.data_ptr(), n,
                                            work.data_ptr()))
@@ -452,7 +474,10 @@ class HeatKernelPath:
         K = s if cfg.K < 0 else cfg.K
         eig, V, info = S.eig_topk(G, K)
         tm.mark("eig")
-        values, vectors = S.u_recover(ell_idx, ell_val, V, eig, math.sqrt(float(n_global)), cfg.root, dense=info.get("dense"))
+        # the scaled rows as wave tiles for the two row kernels below: packed behind the eigensolver, so that they find them in the cache
+        tiles = S.row_tiles(ell_idx, ell_val, s) if hasattr(S, "row_tiles") else None
+        tkw = {} if tiles is None else {"tiles": tiles}
+        values, vectors = S.u_recover(ell_idx, ell_val, V, eig, math.sqrt(float(n_global)), cfg.root, dense=info.get("dense"), **tkw)
         tm.mark("u_recover")
         # k7: heat kernel against the training block V[0:m]
         m = cfg.m
@@ -463,7 +488,7 @@ class HeatKernelPath:
             V1[:, lo:lo + cnt] = vectors[:, :cnt]
         self._all_reduce(V1)                                                  # exchange 4
         if hasattr(S, "hk_rows") and n_loc and S.hk_rows_route(n_loc, cfg.r, s, K, m):   # H from the sparse rows and the s x m matrix Wm
-            H = S.hk_rows(ell_idx, ell_val, V, eig, math.sqrt(float(n_global)), values, cfg.t, V1)
+            H = S.hk_rows(ell_idx, ell_val, V, eig, math.sqrt(float(n_global)), values, cfg.t, V1, **tkw)
         else:
             H = S.hk(values, cfg.t, vectors[:, :n_loc].contiguous() if vectors.shape[1] != n_loc else vectors, V1)
         tm.mark("heat_kernel")
