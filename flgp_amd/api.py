@@ -670,6 +670,20 @@ class ResidentEigenPair:
                                                              ctypes.byref(value), _ptr(g)))
         return (value.value, g) if grad else value.value
 
+    def regression_objective_batch(self, xs, K, idx, Y, sigma=1e-5, noise="same", approach="posterior", prior=None,
+                                   grad=True, max_parallel=0, return_status=False):
+        """``regression_objective`` on this pair at the rows ``xs`` (A x nx) in one call: a multi-start or a line search.
+        A :class:`RegressionObjectiveBatch` that lists this pair once per row, evaluated once and freed.  Returns what its
+        call returns: ``(values, grads)``, each bit for bit the single call's."""
+        xs = np.asarray(xs, dtype=np.float64)
+        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+        ctx = RegressionObjectiveBatch([self] * xs.shape[0], K, idx, Y, sigma=sigma, noise=noise, approach=approach,
+                                       prior=prior, max_parallel=max_parallel)
+        try:
+            return ctx(xs, grad=grad, return_status=return_status)
+        finally:
+            ctx.free()
+
     def test_pgbinary(self, idx0, idx1, K, t, Y, sigma, sigma_nv, N_sample=100, output_pi=False, seed=None,
                       return_state=False):
         """test_pgbinary_cpp (src/Predict.cpp:11-26) on the resident pair with C = HK(idx0, idx0) + sigma I: the Gibbs
@@ -813,6 +827,112 @@ def heat_kernel_spectrum_resident(X, X_new, s, r, K=-1, models=None, nstart=1, e
                                                         _b(models["kernel"]), _b(models["gl"]), int(bool(models["root"])),
                                                         float(epsilon), ctypes.byref(h)))
     return ResidentEigenPair(h)
+
+
+class RegressionObjectiveBatch:
+    """The regression training objective for B (pair, x) problems in one call (flgp_regression_batch_*, include/flgp_hip.h;
+    DESIGN 8 f-18): a context made once per bandwidth grid and called once per optimiser step.  Problem b is
+    ``pairs[b]`` (a :class:`ResidentEigenPair`; a pair may be listed several times) on the shared rows ``idx``, responses
+    ``Y``, ``sigma``, ``noise``, ``approach`` and ``prior``.  The pairs must outlive the context (it keeps them alive).
+
+    ``ctx(X, prob=None, grad=True, return_status=False)``: row a of ``X`` (A x nx) is the x of problem ``prob[a]``
+    (``prob`` None: problems 0 .. B-1, A == B; any order and repeats otherwise).  Returns ``(values, grads)`` of shapes
+    (A,) and (A, nx), or the values alone with ``grad=False``; each entry is ``regression_objective`` on that pair at that
+    x, bit for bit, whatever shares the call.  With ``return_status`` a third array holds 0 or -5 per position, a failed
+    position's numbers are NaN and nothing is raised; without it the lowest failing position raises.  What the library
+    would refuse about ``X`` and ``prob`` is refused here, before it is called, with its texts."""
+
+    _WHO = "regression_objective_batch"
+
+    def __init__(self, pairs, K, idx, Y, sigma=1e-5, noise="same", approach="posterior", prior=None, max_parallel=0):
+        self._h = None
+        self._pairs = list(pairs)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        m = idx.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        pr = None if prior is None else np.ascontiguousarray(np.asarray(prior, dtype=np.float64).reshape(-1))
+        if pr is not None and pr.size != 5:
+            raise ValueError("prior must hold (p, q, tau, alpha, beta)")
+        B = len(self._pairs)
+        eps = (ctypes.c_void_p * max(B, 1))(*[p._h for p in self._pairs])
+        h = ctypes.c_void_p()
+        check(_lib.lib().flgp_regression_batch_create(eps, B, int(K), _ptr(idx), m, _ptr(Y), Y.shape[1], float(sigma),
+                                                      _b(noise), _b(approach), _ptr(pr), int(max_parallel), ctypes.byref(h)))
+        self._h = h
+        self._set(B, int(K), m, Y.shape[1], float(sigma), str(noise), str(approach))
+        c = ctypes.c_int()
+        check(_lib.lib().flgp_regression_batch_dims(self._h, None, None, None, None, None, ctypes.byref(c)))
+        self.chunk = c.value
+
+    def _set(self, B, K, m, q, sigma, noise, approach):
+        self.B, self.K, self.m, self.q, self.sigma, self.noise, self.approach = B, K, m, q, sigma, noise, approach
+        self.nx = m + 1 if noise == "different" else 2
+
+    def _checked(self, X, prob):
+        """X as (A, nx) C-contiguous and prob as int32 (or None), refused as the library refuses them"""
+        who = self._WHO
+        X = np.asarray(X, dtype=np.float64)
+        X = X.reshape(1, -1) if X.ndim == 1 else X
+        if X.ndim != 2 or X.shape[1] != self.nx:
+            raise FlgpError(-1, '%s: noise "%s" takes %d parameters, not %d' % (who, self.noise, self.nx,
+                                                                                   X.shape[-1] if X.ndim else 0))
+        X = np.ascontiguousarray(X)
+        A = X.shape[0]
+        if A < 1:
+            raise FlgpError(-1, "%s: A=%d problems" % (who, A))
+        if prob is None:
+            if A != self.B:
+                raise FlgpError(-1, "%s: prob may be NULL only if A == B (A=%d, B=%d)" % (who, A, self.B))
+        else:
+            prob = np.ascontiguousarray(np.asarray(prob, dtype=np.int32).reshape(-1))
+            if prob.size != A:
+                raise ValueError("prob must have one entry per row of X")
+        # one vectorised pass; only a call that will be refused walks the positions for the first offender, in the library's order
+        ok = np.isfinite(X).all() and (X[:, 1:] + self.sigma > 0.0).all()
+        ok = ok and (self.approach != "posterior" or (X[:, 0] > 0.0).all())
+        ok = ok and (prob is None or ((prob >= 0) & (prob < self.B)).all())
+        if ok:
+            return X, prob
+        for a in range(A):
+            head = "position %d: %s: " % (a, who)
+            if prob is not None and not 0 <= int(prob[a]) < self.B:
+                raise FlgpError(-1, head + "prob=%d is outside [0, B=%d)" % (int(prob[a]), self.B))
+            if not np.isfinite(X[a]).all():
+                raise FlgpError(-1, head + "x must be finite")
+            low = np.flatnonzero(~(X[a, 1:] + self.sigma > 0.0))
+            if low.size:
+                raise FlgpError(-1, head + "x[%d] + sigma must be positive" % (1 + int(low[0])))
+            if self.approach == "posterior" and not X[a, 0] > 0.0:
+                raise FlgpError(-1, head + 't = x[0] must be positive under "posterior"')
+        return X, prob
+
+    def __call__(self, X, prob=None, grad=True, return_status=False):
+        X, prob = self._checked(X, prob)
+        A = X.shape[0]
+        values = np.zeros(A)
+        grads = np.zeros((A, self.nx)) if grad else None
+        status = np.zeros(A, dtype=np.int32) if return_status else None
+        check(_lib.lib().flgp_regression_batch_eval(self._h, _ptr(prob), A, _ptr(X), self.nx, _ptr(values), _ptr(grads), self.nx,
+                                                    _ptr(status)))
+        out = (values, grads) if grad else (values,)
+        if return_status:
+            out = out + (status,)
+        return out if len(out) > 1 else out[0]
+
+    def free(self):
+        if self._h is not None:
+            _lib.lib().flgp_regression_batch_free(self._h)
+            self._h = None
+        self._pairs = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class SpectrumModel:

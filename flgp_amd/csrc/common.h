@@ -201,7 +201,9 @@ struct GemmPair { const double *A2, *B2; double *C2; };
 // E2 or fused reduction.  The tiles, the k ranges and the reduction order of a problem are those of a launch of that
 // problem alone with the same split, so with force_split = that launch's gemm_plan_split every problem keeps its bits.
 constexpr int GEMM_BATCH_MAX = 32768;     // (the reduction kernel carries the problem in gridDim.y)
-struct GemmBatch { int count; const int *slots; long a_bs, b_bs, c_bs, e_bs, part_bs; };
+// a_slots (optional device list of `count` ints): A of problem q at a_slots[q] a_bs instead, for an operand that belongs to
+// something several problems share without sharing the rest (the rows of a pair under many x).
+struct GemmBatch { int count; const int *slots; long a_bs, b_bs, c_bs, e_bs, part_bs; const int *a_slots = nullptr; };
 int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, double *C, GemmFusedReduce *fused);
 // The eigensolver's b x b Gram product out = Xa^T Xb (Xa, Xb: s x b column-major) on its own kernel (rot.hip): split over the
 // rows, planes reduced by gemm.hip's reduction kernels (with the fused extras).  false: not this shape, nothing was launched.
@@ -328,6 +330,8 @@ int lrb_a(hipStream_t st, const LrChunk &c, const int *act, int A);
 int lrb_step(hipStream_t st, const LrChunk &c, const int *act, int A, double *d_stat);
 int lrb_chol(hipStream_t st, const LrChunk &c, const int *act, int A);
 int lrb_trsv(hipStream_t st, const LrChunk &c, const int *act, int A);
+// lrb_trsv's q-column form: the q columns of R (K x q per slot at stride sr) <- Q^-1 (.), a workgroup per column
+int lrb_trsv_cols(hipStream_t st, const LrChunk &c, const int *act, int A, double *R, long sr, int q);
 int lrb_amll(hipStream_t st, const LrChunk &c);
 // The weight-space Newton loop's elementwise steps and the predictive rows of the logit posterior for m > K (gpc.hip; the
 // loop is in eigenpair.hip).  gpc_ws_bd: out = b / D; gpc_ws_fnew: f_new = p + sigma (b - sW^2 p) / D.
@@ -401,6 +405,45 @@ struct RgTerms {
   double *out;
 };
 int rg_assemble(hipStream_t st, const RgTerms &T);
+// The Woodbury route (m > K) of the same objective for a chunk of problems in the same launches (the steps in
+// eigenpair.hip: RgBatch).  Problem s of the chunk owns slot s of every buffer below and the kernels carry the slot in
+// gridDim.y (rgb_assemble: one workgroup per slot), so a step is one launch whatever the chunk holds.  The strides are
+// doubles between two slots.  What belongs to a pair and not to a problem (its eigenvalues, its gathered rows V and, for
+// "same", M0 = V^T V) is stored once per distinct pair and found through pair[s] (on the device).  Y is shared.
+struct RgbChunk {
+  int m, q, K, nx, different, posterior, grad;
+  double sigma, prior[5];
+  long sv, sk, skq, smq, sq, sx, sxn;      // of an m-vector, a K-vector, K x q, m x q, K x K, m x K and x (nx)
+  const int *pair;
+  const double *values, *V, *M0;          // per pair at sk, sx (ld m) and sq
+  const double *Y;
+  double *x, *c, *ci;                      // x per slot; c[s] = x1 + sigma or 1, ci[s] = gpr_diff's factor (1 / c or 1)
+  double *ls;                              // K: exp(-t lambda / 2) + 0.0 at t = x[0]
+  double *alpha, *Tq;                      // m x q
+  double *R, *Vta;                         // K x q
+  double *M, *Q, *Li, *Qinv, *LsM, *M1;    // K x K; M is written for "different" only ("same" reads M0)
+  double *d;                               // m
+  double *ZV, *P;                          // m x K, "different" only
+  double *logdet;                          // one per slot
+  int *flag;                               // one pivot flag per slot (chol_blocked's)
+  double *out;                             // slots x (1 + nx) doubles [value, grad], then one int per slot: its flag
+};
+// Each is its gpr_* / rg_* namesake on every slot, expression for expression.  rgb_weights: ls from values[pair[s]] at
+// x[s][0]; rgb_q: Q from M (or M0[pair[s]]), ls and c[s]; rgb_scale: out = diag(a) M diag(b) (a, b optional; `list`
+// optional: M of slot s at list[s] sm); rgb_diff: out = f[s] (X - Z); rgb_zinv: d = 1 / (x[1..m] + sigma);
+// rgb_rowscale: out(i, j) = a(i) M(i, j), M at ldm; rgb_rowsumsq: out[i] = |X(i, :)|^2, k ascending.  rgb_assemble: the
+// log-determinant of the factor in Q (chol_logdet's sum), then rg_assemble's value and gradient of the slot into out.
+int rgb_weights(hipStream_t st, const RgbChunk &c, int slots);
+int rgb_q(hipStream_t st, const RgbChunk &c, int slots);
+int rgb_scale(hipStream_t st, int slots, int rows, int cols, const double *M, long sm, const int *list, const double *a, long sa,
+              const double *b, long sb, double *out, long so);
+int rgb_diff(hipStream_t st, int slots, long count, const double *X, long sx, const double *Z, long sz, const double *f,
+             double *out, long so);
+int rgb_zinv(hipStream_t st, const RgbChunk &c, int slots);
+int rgb_rowscale(hipStream_t st, int slots, int rows, int cols, const double *M, long ldm, long sm, const int *list,
+                 const double *a, long sa, double *out, long so);
+int rgb_rowsumsq(hipStream_t st, int slots, const double *X, long sx, long ldx, int rows, int cols, double *out, long so);
+int rgb_assemble(hipStream_t st, const RgbChunk &c, int slots);
 
 // The Polya-Gamma Gibbs sampler (pg.hip; its random-number layout is documented there).  pg_stream_base: the base of
 // stream `stream` under `seed`, as flgp_amd/synth.py's _stream_base.

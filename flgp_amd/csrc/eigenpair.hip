@@ -4,13 +4,16 @@
 // Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
 // 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12; B
 // posteriors on any response matrix in one call, their weight-space loops in shared launches: f-17; the
-// training objective for B problems in one call: f-15);
+// training objective for B problems in one call: f-15; the regression objective for B (pair, x) problems through a training
+// context: f-18);
 // Polya-Gamma Gibbs prediction (pg.hip; B chains in one call: DESIGN 8 f-16).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
 // the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
+#include <memory>
+#include <string>
 #include <vector>
 
 using namespace flgp;
@@ -2176,5 +2179,376 @@ extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, 
       set_error("chain %d (t=%g, seed=%llu): %s", b, ts[b], seeds[b], msg.c_str());
       return rc;
     }
+  return FLGP_OK;
+}
+
+// ---- regression training objective for B (pair, x) problems in one call -------------------------------
+// A training context: made once per grid of pairs, evaluated once per optimiser step.  What depends on (pair, rows, Y) only
+// is built at create; an evaluation uploads the x of its problems and brings their values and gradients down.
+namespace {
+struct NoState {};
+}  // namespace
+
+struct flgp_regression_batch {
+  int B = 0, K = 0, m = 0, q = 0, nx = 0, chunk = 1, P = 0, max_parallel = 0, device = 0;
+  bool different = false, posterior = false, direct = false, range = false;
+  double sigma = 0.0, prior[5] = {0, 0, 0, 0, 0};
+  std::vector<const flgp_eigenpair *> pairs;      // the P distinct ones, in order of first appearance
+  std::vector<int> pair_of, idx;                  // problem -> pair; the rows (the host's copy)
+  Stream st;
+  DevBuf didx, dY, vals, V, M0, R0;               // per pair: K eigenvalues, the gathered rows, "same": V^T V and V^T Y
+  // the Woodbury route's chunk
+  RgbChunk C{};
+  LrChunk L{};                                    // its K x K factor under the lrb_* / wsb_* steps: K, Q, sq, flag
+  DevBuf in, ls, alpha, Tq, R, Vta, M, Q, Li, Tb, Qinv, LsM, M1, d, ZV, Pm, logdet, flag, out, part, all;
+  int planM = 1, planR = 1, planQi = 1;           // the splits of the single entry's products on its workspace
+  size_t pe = 0, wi = 0;
+  long sp = 0, stb = 0, in_elems = 0, off_c = 0, off_ci = 0, off_pair = 0;
+  double *h_in = nullptr, *h_out = nullptr;       // pinned mirrors of `in` and `out`
+  ~flgp_regression_batch() {
+    if (h_in) (void)hipHostFree(h_in);
+    if (h_out) (void)hipHostFree(h_out);
+  }
+
+  static void plans(int m, int K, int q, int *pM, int *pR, int *pQi, size_t *pe, size_t *wi) {
+    const size_t we = vt_work_elems(K, q);
+    *pM = gemm_plan_split(K, K, m, we);
+    *pR = gemm_plan_split(K, q, m, we);
+    *pQi = gemm_plan_split(K, K, K, we);
+    *wi = (size_t)32 * 64 * K;
+    *pe = std::max(std::max((size_t)*pM * K * K, (size_t)*pR * K * q),
+                   std::max((size_t)*pQi * K * K, wsb_tri_inverse_planes(K, *wi)));
+  }
+  // device bytes of one slot of the Woodbury chunk: x, c, 1 / c and the pair's number; ls; alpha, Tq; R, Vta; Q, Li, Qinv,
+  // LsM, M1 and T (64 x K); its planes; logdet, the results and two flags; "different": M, d, ZV and P as well
+  static double slot_bytes(int m, int K, int q, int nx, bool different) {
+    int a, b, c;
+    size_t pe, wi;
+    plans(m, K, q, &a, &b, &c, &pe, &wi);
+    double e = (double)pad32(nx) + 3.0 + pad32(K) + 2.0 * pad32((long)m * q) + 2.0 * pad32((long)K * q) +
+               5.0 * pad32((long)K * K) + pad32((long)64 * K) + pad32((long)pe) + 1.0 + (1.0 + nx);
+    if (different) e += (double)pad32((long)K * K) + pad32(m) + 2.0 * pad32((long)m * K);
+    return 8.0 * e + 8.0;
+  }
+  int alloc_chunk() {
+    RgbChunk &c = C;
+    const size_t S = (size_t)chunk;
+    plans(m, K, q, &planM, &planR, &planQi, &pe, &wi);
+    sp = pad32((long)pe); stb = pad32((long)64 * K);
+    c.sv = pad32(m); c.sk = pad32(K); c.skq = pad32((long)K * q); c.smq = pad32((long)m * q); c.sq = pad32((long)K * K);
+    c.sx = pad32((long)m * K); c.sxn = pad32(nx);
+    // one upload per chunk: [x of every slot | c | 1 / c | the pairs' numbers (ints)]
+    off_c = (long)S * c.sxn; off_ci = off_c + pad32(chunk); off_pair = off_ci + pad32(chunk); in_elems = off_pair + pad32(chunk);
+    FLGP_TRY(in.alloc(sizeof(double) * (size_t)in_elems));
+    FLGP_TRY(ls.alloc(sizeof(double) * S * c.sk));
+    FLGP_TRY(alpha.alloc(sizeof(double) * S * c.smq)); FLGP_TRY(Tq.alloc(sizeof(double) * S * c.smq));
+    FLGP_TRY(R.alloc(sizeof(double) * S * c.skq)); FLGP_TRY(Vta.alloc(sizeof(double) * S * c.skq));
+    FLGP_TRY(Q.alloc(sizeof(double) * S * c.sq)); FLGP_TRY(Li.alloc(sizeof(double) * S * c.sq));
+    FLGP_TRY(Qinv.alloc(sizeof(double) * S * c.sq)); FLGP_TRY(LsM.alloc(sizeof(double) * S * c.sq));
+    FLGP_TRY(M1.alloc(sizeof(double) * S * c.sq)); FLGP_TRY(Tb.alloc(sizeof(double) * S * stb));
+    FLGP_TRY(part.alloc(sizeof(double) * S * std::max(sp, 32L)));
+    FLGP_TRY(logdet.alloc(sizeof(double) * S)); FLGP_TRY(flag.alloc(sizeof(int) * S));
+    FLGP_TRY(out.alloc(sizeof(double) * S * (size_t)(1 + nx) + sizeof(int) * S));
+    FLGP_TRY(all.alloc(sizeof(int) * S));
+    if (different) {
+      FLGP_TRY(M.alloc(sizeof(double) * S * c.sq)); FLGP_TRY(d.alloc(sizeof(double) * S * c.sv));
+      FLGP_TRY(ZV.alloc(sizeof(double) * S * c.sx)); FLGP_TRY(Pm.alloc(sizeof(double) * S * c.sx));
+    }
+    FLGP_HIP(hipHostMalloc((void **)&h_in, sizeof(double) * (size_t)in_elems, hipHostMallocDefault));
+    FLGP_HIP(hipHostMalloc((void **)&h_out, sizeof(double) * S * (size_t)(1 + nx) + sizeof(int) * S, hipHostMallocDefault));
+    std::memset(h_in, 0, sizeof(double) * (size_t)in_elems);
+    std::vector<int> ids(S);
+    for (size_t s = 0; s < S; ++s) ids[s] = (int)s;
+    FLGP_TRY(h2d(all.p, ids.data(), sizeof(int) * S, st.s));
+    FLGP_HIP(hipStreamSynchronize(st.s));
+    c.m = m; c.q = q; c.K = K; c.nx = nx; c.different = different; c.posterior = posterior; c.grad = 1;
+    c.sigma = sigma;
+    for (int a = 0; a < 5; ++a) c.prior[a] = prior[a];
+    c.x = in.as<double>(); c.c = c.x + off_c; c.ci = c.x + off_ci; c.pair = (const int *)(c.x + off_pair);
+    c.values = vals.as<double>(); c.V = V.as<double>(); c.M0 = M0.as<double>(); c.Y = dY.as<double>();
+    c.ls = ls.as<double>(); c.alpha = alpha.as<double>(); c.Tq = Tq.as<double>(); c.R = R.as<double>(); c.Vta = Vta.as<double>();
+    c.M = M.as<double>(); c.Q = Q.as<double>(); c.Li = Li.as<double>(); c.Qinv = Qinv.as<double>(); c.LsM = LsM.as<double>();
+    c.M1 = M1.as<double>(); c.d = d.as<double>(); c.ZV = ZV.as<double>(); c.P = Pm.as<double>();
+    c.logdet = logdet.as<double>(); c.flag = flag.as<int>(); c.out = out.as<double>();
+    L = LrChunk{};
+    L.m = m; L.K = K; L.slots = chunk; L.sv = c.sv; L.sk = c.sk; L.sx = c.sx; L.sq = c.sq;
+    L.Q = c.Q; L.flag = c.flag;
+    return FLGP_OK;
+  }
+  // one batched product on the chunk's planes; la / lb: the list of the A / B operand where it is not the slots' own
+  int gemm(int S, int Mr, int Nc, int Kd, const double *A, long a_is, long a_ks, long a_bs, const int *la, const double *Bm,
+           long b_ks, long b_js, long b_bs, double *Cm, long c_js, long c_bs, int split) {
+    GemmBatch gb{S, all.as<int>(), a_bs, b_bs, c_bs, 0, split ? sp : 0};
+    gb.a_slots = la;
+    return gemm_launch(st.s, Mr, Nc, Kd, 1.0, A, a_is, a_ks, Bm, b_ks, b_js, 0.0, nullptr, 0, 0, Cm, 1, c_js,
+                       split ? part.as<double>() : nullptr, split ? pe : 0, 0.0, nullptr, nullptr, nullptr, split, nullptr, &gb);
+  }
+  // RgEval::woodbury_terms and rg_assemble for the S slots whose x, c and pairs are in h_in: every step one launch
+  int woodbury_chunk(int S, bool grad) {
+    RgbChunk &c = C;
+    hipStream_t s = st.s;
+    c.grad = grad ? 1 : 0;
+    const int *pl = c.pair, *a = all.as<int>();
+    FLGP_TRY(h2d(in.p, h_in, sizeof(double) * (size_t)in_elems, s));
+    FLGP_HIP(hipMemsetAsync(c.flag, 0, sizeof(int) * (size_t)S, s));
+    FLGP_TRY(rgb_weights(s, c, S));
+    if (different) {
+      FLGP_TRY(rgb_zinv(s, c, S));                                                                        // d = z^-1 for now
+      FLGP_TRY(rgb_rowscale(s, S, m, K, c.V, m, c.sx, pl, c.d, c.sv, c.ZV, c.sx));                      // Z^-1 V
+      FLGP_TRY(rgb_rowscale(s, S, m, q, c.Y, m, 0, nullptr, c.d, c.sv, c.alpha, c.smq));                // Z^-1 Y
+      FLGP_TRY(gemm(S, K, K, m, c.V, m, 1, c.sx, pl, c.ZV, 1, m, c.sx, c.M, K, c.sq, planM));           // M = V^T Z^-1 V
+      FLGP_TRY(gemm(S, K, q, m, c.V, m, 1, c.sx, pl, c.alpha, 1, m, c.smq, c.R, K, c.skq, planR));      // V^T Z^-1 Y
+    }
+    FLGP_TRY(rgb_q(s, c, S));
+    FLGP_TRY(lrb_chol(s, L, a, S));
+    // Ls V^T Z^-1 Y ("same": from the pair's R0), Q^-1 (.), Ls (.)
+    if (different) FLGP_TRY(rgb_scale(s, S, K, q, c.R, c.skq, nullptr, c.ls, c.sk, nullptr, 0, c.R, c.skq));
+    else FLGP_TRY(rgb_scale(s, S, K, q, R0.as<double>(), c.skq, pl, c.ls, c.sk, nullptr, 0, c.R, c.skq));
+    FLGP_TRY(lrb_trsv_cols(s, L, a, S, c.R, c.skq, q));
+    FLGP_TRY(rgb_scale(s, S, K, q, c.R, c.skq, nullptr, c.ls, c.sk, nullptr, 0, c.R, c.skq));
+    FLGP_TRY(gemm(S, m, q, K, c.V, 1, m, c.sx, pl, c.R, 1, K, c.skq, c.Tq, m, c.smq, 0));               // V (.)
+    FLGP_TRY(rgb_diff(s, S, (long)m * q, c.Y, 0, c.Tq, c.smq, c.ci, c.alpha, c.smq));
+    if (different) FLGP_TRY(rgb_rowscale(s, S, m, q, c.alpha, m, c.smq, nullptr, c.d, c.sv, c.alpha, c.smq));
+    if (grad) {
+      // Q^-1 = L_Q^-T L_Q^-1, M1 = Q^-1 Ls M, V^T alpha; "different": d_i = |row i of V Ls L_Q^-T|^2
+      const double *Mm = different ? c.M : c.M0;
+      const int *ml = different ? nullptr : pl;
+      FLGP_TRY(wsb_tri_inverse(s, L, a, S, c.Li, Tb.as<double>(), stb, part.as<double>(), pe, sp, wi));
+      FLGP_TRY(gemm(S, K, K, K, c.Li, K, 1, c.sq, nullptr, c.Li, 1, K, c.sq, c.Qinv, K, c.sq, planQi));
+      FLGP_TRY(rgb_scale(s, S, K, K, Mm, c.sq, ml, c.ls, c.sk, nullptr, 0, c.LsM, c.sq));
+      FLGP_TRY(gemm(S, K, K, K, c.Qinv, 1, K, c.sq, nullptr, c.LsM, 1, K, c.sq, c.M1, K, c.sq, 0));
+      FLGP_TRY(gemm(S, K, q, m, c.V, m, 1, c.sx, pl, c.alpha, 1, m, c.smq, c.Vta, K, c.skq, planR));
+      if (different) {
+        FLGP_TRY(rgb_scale(s, S, K, K, c.Li, c.sq, nullptr, nullptr, 0, c.ls, c.sk, c.LsM, c.sq));     // reuse: Li Ls
+        FLGP_TRY(gemm(S, m, K, K, c.V, 1, m, c.sx, pl, c.LsM, K, 1, c.sq, c.P, m, c.sx, 0));            // P = V (Li Ls)^T
+        FLGP_TRY(rgb_rowsumsq(s, S, c.P, c.sx, m, m, K, c.d, c.sv));
+      }
+    }
+    FLGP_TRY(rgb_assemble(s, c, S));
+    FLGP_TRY(d2h(h_out, out.p, sizeof(double) * (size_t)S * (1 + nx) + sizeof(int) * (size_t)S, s));
+    FLGP_HIP(hipStreamSynchronize(s));
+    return FLGP_OK;
+  }
+  // one problem of the direct route (m <= K) on the worker's stream: RgEval's begin without its stream and its upload of
+  // Y, then its direct_terms and finish
+  int direct_one(hipStream_t ws, const char *who, int b, const double *x, double *value, double *grad) {
+    const flgp_eigenpair *ep = pairs[(size_t)pair_of[(size_t)b]];
+    RgEval E;
+    struct Lend { Stream &s; ~Lend() { s.s = nullptr; } } lend{E.st};     // the pool's stream goes back before E does
+    E.st.s = ws;
+    E.ep = ep; E.x = x; E.we = vt_work_elems(K, q);
+    Rows &r = E.r;
+    r.idx = idx.data(); r.m = m; r.resolved = true; r.gathered_K = K;
+    if (range) { r.row0 = idx[0]; r.V = (const double *)ep->vectors.p + r.row0; r.ld = ep->n; }
+    else { r.d = didx.as<int>(); r.V = V.as<double>() + (size_t)pair_of[(size_t)b] * C.sx; r.ld = m; }
+    RgTerms &T = E.T;
+    T.m = m; T.q = q; T.K = K; T.direct = 1; T.different = different; T.posterior = posterior; T.grad = grad != nullptr;
+    T.sigma = sigma; T.c = different ? 1.0 : x[1] + sigma;
+    for (int a = 0; a < 5; ++a) T.prior[a] = prior[a];
+    FLGP_TRY(E.G.prepare(ws, ep, K, x[0]));
+    E.dY.borrow(dY.p);
+    FLGP_TRY(upload(E.dx, x, sizeof(double) * (size_t)nx, ws));
+    FLGP_TRY(E.alpha.alloc(sizeof(double) * (size_t)m * q)); FLGP_TRY(E.out.alloc(sizeof(double) * (size_t)(1 + nx)));
+    FLGP_TRY(E.ld.alloc(sizeof(double)));
+    if (T.grad) { FLGP_TRY(E.Vta.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(E.d.alloc(sizeof(double) * (size_t)m)); }
+    FLGP_TRY(E.direct_terms());
+    return E.finish(who, nx, value, grad);
+  }
+};
+
+namespace {
+// the two strings, refused as the single entry refuses them
+int rgb_strings(const char *who, const char *noise, const char *approach, bool *different, bool *posterior) {
+  FLGP_REQUIRE(noise && approach, "%s: null pointer", who);
+  *different = std::strcmp(noise, "different") == 0;
+  if (!*different && std::strcmp(noise, "same") != 0) { set_error("The noise setting is illegal!"); return FLGP_ERR_UNSUPPORTED; }
+  *posterior = std::strcmp(approach, "posterior") == 0;
+  if (!*posterior && std::strcmp(approach, "marginal") != 0) {
+    set_error("This model selection approach is not supported!");
+    return FLGP_ERR_UNSUPPORTED;
+  }
+  return FLGP_OK;
+}
+}  // namespace
+
+extern "C" int flgp_regression_batch_create(const flgp_eigenpair *const *eps, int B, int K, const int *idx, int m,
+                                            const double *Y, int q, double sigma, const char *noise, const char *approach,
+                                            const double *prior, int max_parallel, flgp_regression_batch **out) {
+  const char *who = "regression_objective_batch";
+  bool different = false, posterior = false;
+  FLGP_TRY(rgb_strings(who, noise, approach, &different, &posterior));
+  FLGP_REQUIRE(eps && idx && Y && out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(B >= 1, "%s: B=%d problems", who, B);
+  for (int b = 0; b < B; ++b) {
+    FLGP_REQUIRE(eps[b], "problem %d: %s: null pointer", b, who);
+    FLGP_REQUIRE(K >= 1 && K <= eps[b]->K && m >= 1 && q >= 1, "problem %d: %s: bad shape (K=%d of %d, m=%d, q=%d)", b, who, K,
+                 eps[b]->K, m, q);
+    FLGP_REQUIRE(eps[b]->device == eps[0]->device, "problem %d: %s: the pair lives on device %d, problem 0's on device %d", b,
+                 who, eps[b]->device, eps[0]->device);
+  }
+  for (int b = 0; b < B; ++b)
+    for (int a = 0; a < m; ++a)
+      FLGP_REQUIRE(idx[a] >= 0 && idx[a] < eps[b]->n, "problem %d: %s: idx[%d]=%d out of range", b, who, a, idx[a]);
+  int dev = 0;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == eps[0]->device, "%s: the pairs live on device %d, the current device is %d", who, eps[0]->device, dev);
+  std::unique_ptr<flgp_regression_batch> H(new flgp_regression_batch);
+  flgp_regression_batch &h = *H;
+  h.B = B; h.K = K; h.m = m; h.q = q; h.nx = different ? m + 1 : 2; h.max_parallel = max_parallel;
+  h.different = different; h.posterior = posterior; h.direct = m <= K; h.sigma = sigma;
+  h.device = eps[0]->device;
+  const double dflt[5] = {1.0, 10.0, 2.0, 0.1, 1e-3};         // PostOFDataReg (src/train.h:153-155)
+  for (int a = 0; a < 5; ++a) h.prior[a] = prior ? prior[a] : dflt[a];
+  h.pair_of.resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    size_t p = 0;
+    while (p < h.pairs.size() && h.pairs[p] != eps[b]) ++p;
+    if (p == h.pairs.size()) h.pairs.push_back(eps[b]);
+    h.pair_of[(size_t)b] = (int)p;
+  }
+  h.P = (int)h.pairs.size();
+  h.idx.assign(idx, idx + m);
+  h.range = is_range(idx, m);
+  FLGP_TRY(h.st.create());
+  hipStream_t st = h.st.s;
+  FLGP_TRY(upload(h.dY, Y, sizeof(double) * (size_t)m * q, st));
+  FLGP_TRY(upload(h.didx, idx, sizeof(int) * (size_t)m, st));
+  const long sx = pad32((long)m * K), sk = pad32(K), sq = pad32((long)K * K), skq = pad32((long)K * q);
+  h.C.sx = sx;
+  // the pairs' rows: every pair's for the Woodbury route (one buffer under the slots' strides), for the direct route only
+  // where the rows are no range (a range is read in place, as Rows::gather reads it)
+  if (!h.direct || !h.range) {
+    FLGP_TRY(h.V.alloc(sizeof(double) * (size_t)h.P * sx));
+    for (int p = 0; p < h.P; ++p)
+      FLGP_TRY(flgp_dev_gather_rows(st, (const double *)h.pairs[(size_t)p]->vectors.p, h.pairs[(size_t)p]->n, h.didx.as<int>(), m,
+                                    K, h.V.as<double>() + (size_t)p * sx));
+  }
+  if (h.direct) {
+    h.chunk = plan_workers(max_parallel, B, 0.0, 0.0);
+    FLGP_HIP(hipStreamSynchronize(st));
+    *out = H.release();
+    return FLGP_OK;
+  }
+  FLGP_TRY(h.vals.alloc(sizeof(double) * (size_t)h.P * sk));
+  for (int p = 0; p < h.P; ++p)
+    FLGP_HIP(hipMemcpyAsync(h.vals.as<double>() + (size_t)p * sk, h.pairs[(size_t)p]->values.p, sizeof(double) * (size_t)K,
+                            hipMemcpyDeviceToDevice, st));
+  if (!different) {
+    // M0 = V^T V and R0 = V^T Y per pair: the single entry's two products, on its workspace
+    const size_t we = vt_work_elems(K, q);
+    DevBuf work;
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    FLGP_TRY(h.M0.alloc(sizeof(double) * (size_t)h.P * sq)); FLGP_TRY(h.R0.alloc(sizeof(double) * (size_t)h.P * skq));
+    for (int p = 0; p < h.P; ++p) {
+      const double *Vp = h.V.as<double>() + (size_t)p * sx;
+      FLGP_TRY(gemm_tn(st, K, K, m, Vp, m, Vp, m, h.M0.as<double>() + (size_t)p * sq, work.as<double>(), we));
+      FLGP_TRY(gemm_tn(st, K, q, m, Vp, m, h.dY.as<double>(), m, h.R0.as<double>() + (size_t)p * skq, work.as<double>(), we));
+    }
+    FLGP_HIP(hipStreamSynchronize(st));
+  }
+  // the chunk: max_parallel problems, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of the
+  // free memory
+  const int want = max_parallel > 0 ? max_parallel : B;
+  size_t free_b = 0, total_b = 0;
+  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  h.chunk = std::min(plan_workers(want, B, (double)free_b, flgp_regression_batch::slot_bytes(m, K, q, h.nx, different)),
+                     GEMM_BATCH_MAX);
+  FLGP_TRY(h.alloc_chunk());
+  FLGP_HIP(hipStreamSynchronize(st));
+  *out = H.release();
+  return FLGP_OK;
+}
+
+extern "C" int flgp_regression_batch_dims(const flgp_regression_batch *h, int *B, int *K, int *m, int *q, int *nx, int *chunk) {
+  FLGP_REQUIRE(h, "regression_objective_batch: null pointer");
+  if (B) *B = h->B;
+  if (K) *K = h->K;
+  if (m) *m = h->m;
+  if (q) *q = h->q;
+  if (nx) *nx = h->nx;
+  if (chunk) *chunk = h->chunk;
+  return FLGP_OK;
+}
+
+extern "C" void flgp_regression_batch_free(flgp_regression_batch *h) { delete h; }
+
+extern "C" int flgp_regression_batch_eval(flgp_regression_batch *hp, const int *prob, int A, const double *X, int ldx,
+                                          double *values, double *grads, int ldg, int *status) {
+  const char *who = "regression_objective_batch";
+  FLGP_REQUIRE(hp && X && values, "%s: null pointer", who);
+  flgp_regression_batch &h = *hp;
+  const int nx = h.nx, m = h.m;
+  FLGP_REQUIRE(A >= 1, "%s: A=%d problems", who, A);
+  FLGP_REQUIRE(prob || A == h.B, "%s: prob may be NULL only if A == B (A=%d, B=%d)", who, A, h.B);
+  FLGP_REQUIRE(ldx >= nx, "%s: noise \"%s\" takes %d parameters, not %d", who, h.different ? "different" : "same", nx, ldx);
+  FLGP_REQUIRE(!grads || ldg >= nx, "%s: noise \"%s\" takes %d parameters, not %d", who, h.different ? "different" : "same", nx,
+               ldg);
+  for (int a = 0; a < A; ++a) {
+    const int b = prob ? prob[a] : a;
+    FLGP_REQUIRE(b >= 0 && b < h.B, "position %d: %s: prob=%d is outside [0, B=%d)", a, who, b, h.B);
+    const double *x = X + (size_t)a * ldx;
+    FLGP_REQUIRE(all_finite(x, nx), "position %d: %s: x must be finite", a, who);
+    for (int i = 1; i < nx; ++i) FLGP_REQUIRE(x[i] + h.sigma > 0.0, "position %d: %s: x[%d] + sigma must be positive", a, who, i);
+    FLGP_REQUIRE(!h.posterior || x[0] > 0.0, "position %d: %s: t = x[0] must be positive under \"posterior\"", a, who);
+  }
+  int dev = 0;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == h.device, "%s: the pairs live on device %d, the current device is %d", who, h.device, dev);
+  std::vector<int> stat((size_t)A, FLGP_OK);
+  std::vector<std::string> why((size_t)A);
+  const int cnt = grads ? nx + 1 : 1;
+  auto fail = [&](int a, const char *text) {
+    stat[(size_t)a] = FLGP_ERR_NOCONV;
+    why[(size_t)a] = text;
+    values[a] = std::nan("");
+    if (grads) std::fill(grads + (size_t)a * ldg, grads + (size_t)a * ldg + nx, std::nan(""));
+  };
+  if (h.direct) {
+    // the problems dealt to the pool's workers (worker_pool.h), each on the single entry's own steps; one worker runs on
+    // the context's stream
+    DevicePool pool;
+    FLGP_TRY(pool.plan(h.max_parallel, A, 8.0 * (4.0 * m * m + 96.0 * m + (double)m * h.K + 2.0 * m * h.q) +
+                                              (double)flgp_dev_hk_workspace(m, m, h.K, 1)));
+    const PoolFailure bad = pool.run<NoState>(
+        h.st.s, A, [](NoState &) { return FLGP_OK; },
+        [&](hipStream_t ws, NoState &, int a) -> int {
+          const int b = prob ? prob[a] : a;
+          const int rc = h.direct_one(ws, who, b, X + (size_t)a * ldx, &values[a], grads ? grads + (size_t)a * ldg : nullptr);
+          if (rc == FLGP_ERR_NOCONV) { fail(a, flgp_last_error()); return FLGP_OK; }
+          return rc;
+        });
+    if (bad.item >= 0) { set_error("position %d: %s", bad.item, bad.message.c_str()); return bad.status; }
+  } else {
+    // RgEval::finish's two verdicts, under this entry's name
+    const std::string not_pd = std::string(who) + ": the system matrix is not positive definite (Cholesky pivot <= 0)";
+    const std::string not_finite = std::string(who) + ": the objective is not finite (the system matrix is numerically singular)";
+    for (int p0 = 0; p0 < A; p0 += h.chunk) {
+      const int S = std::min(h.chunk, A - p0);
+      int *hpair = (int *)(h.h_in + h.off_pair);
+      for (int s = 0; s < S; ++s) {
+        const int a = p0 + s, b = prob ? prob[a] : a;
+        const double *x = X + (size_t)a * ldx;
+        std::memcpy(h.h_in + (size_t)s * h.C.sxn, x, sizeof(double) * (size_t)nx);
+        const double c = h.different ? 1.0 : x[1] + h.sigma;
+        h.h_in[h.off_c + s] = c;
+        h.h_in[h.off_ci + s] = h.different ? 1.0 : 1.0 / c;
+        hpair[s] = h.pair_of[(size_t)b];
+      }
+      FLGP_TRY(h.woodbury_chunk(S, grads != nullptr));
+      const int *flags = (const int *)(h.h_out + (size_t)S * (1 + nx));
+      for (int s = 0; s < S; ++s) {
+        const int a = p0 + s;
+        const double *o = h.h_out + (size_t)s * (1 + nx);
+        if (flags[s]) { fail(a, not_pd.c_str()); continue; }
+        if (!all_finite(o, cnt)) { fail(a, not_finite.c_str()); continue; }
+        values[a] = o[0];
+        if (grads) std::memcpy(grads + (size_t)a * ldg, o + 1, sizeof(double) * (size_t)nx);
+      }
+    }
+  }
+  if (status) { std::memcpy(status, stat.data(), sizeof(int) * (size_t)A); return FLGP_OK; }
+  for (int a = 0; a < A; ++a)
+    if (stat[(size_t)a] != FLGP_OK) { set_error("position %d: %s", a, why[(size_t)a].c_str()); return stat[(size_t)a]; }
   return FLGP_OK;
 }

@@ -51,6 +51,8 @@ struct GemmArgs {
   // the tiles [q ntiles, (q + 1) ntiles) of gridDim.x and the operands at slot bslots[q] times the strides below
   const int *bslots;
   long a_bs, b_bs, c_bs, e_bs, part_bs;
+  // a list of its own for the kernel's A or B (nullptr: bslots; GemmBatch::a_slots after gemm_launch's orientation)
+  const int *a_slots, *b_slots;
 };
 
 // ---- operand staging: a 128(rows) x 16(k) tile goes global -> 8 registers per thread -> LDS [k][row].
@@ -283,7 +285,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
     const int q = bid / nt;
     bid -= q * nt;
     const long slot = g.bslots[q];
-    gA += slot * g.a_bs; gB += slot * g.b_bs; gC += slot * g.c_bs; gP += slot * g.part_bs;
+    gA += (g.a_slots ? (long)g.a_slots[q] : slot) * g.a_bs; gB += (g.b_slots ? (long)g.b_slots[q] : slot) * g.b_bs;
+    gC += slot * g.c_bs; gP += slot * g.part_bs;
     if (gE) gE += slot * g.e_bs;
   }
   if (gridDim.y > 1) {   // two products: the bands run over both tile sets (workgroups go to the XCDs by their linear id)
@@ -639,8 +642,10 @@ int gemm_launch(hipStream_t st, int M, int N, int Kd, double alpha, const double
   }
   if (!pair) { g.A2 = g.B2 = nullptr; g.C2 = nullptr; } else g.C2 = pair->C2;
   g.bslots = nullptr; g.a_bs = g.b_bs = g.c_bs = g.e_bs = g.part_bs = 0;
+  g.a_slots = g.b_slots = nullptr;
   if (batch) {
     g.bslots = batch->slots;
+    g.a_slots = swapped ? nullptr : batch->a_slots; g.b_slots = swapped ? batch->a_slots : nullptr;
     g.a_bs = swapped ? batch->b_bs : batch->a_bs; g.b_bs = swapped ? batch->a_bs : batch->b_bs;
     g.c_bs = batch->c_bs; g.e_bs = batch->e_bs; g.part_bs = batch->part_bs;
   }
@@ -778,6 +783,7 @@ int gemm_reduce_square(hipStream_t st, int b, const double *part, int nsplit, do
   g.shift_edges = 0; g.ksplit_len = 0; g.part = const_cast<double *>(part);
   g.A2 = g.B2 = nullptr; g.C2 = nullptr;
   g.bslots = nullptr; g.a_bs = g.b_bs = g.c_bs = g.e_bs = g.part_bs = 0;
+  g.a_slots = g.b_slots = nullptr;
   if (fused) {
     const int nt1 = ceil_div(b, 16);
     hipLaunchKernelGGL(splitk_reduce_sym_kernel, dim3(nt1 * nt1), dim3(256), 0, st, g, nsplit, fused->mode, fused->dinv, fused->dist,

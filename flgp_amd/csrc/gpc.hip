@@ -651,6 +651,15 @@ int lrb_trsv(hipStream_t st, const LrChunk &c, const int *act, int A) {
   hipLaunchKernelGGL(lrb_trsv_kernel, dim3(A), dim3(256), 0, st, c, act);
   return check_launch("lrb_trsv_kernel");
 }
+// column blockIdx.x of the slot's K x q right-hand sides: chol_trsv's workgroup per column on the slot's factor
+__global__ __launch_bounds__(256) void lrb_trsv_cols_kernel(LrChunk c, const int *__restrict__ act, double *__restrict__ R, long sr) {
+  const long s = act[blockIdx.y];
+  chol_trsv_body(c.Q + s * c.sq, c.K, c.K, R + s * sr + (size_t)blockIdx.x * c.K, 3, c.flag + s);
+}
+int lrb_trsv_cols(hipStream_t st, const LrChunk &c, const int *act, int A, double *R, long sr, int q) {
+  hipLaunchKernelGGL(lrb_trsv_cols_kernel, dim3(q, A), dim3(256), 0, st, c, act, R, sr);
+  return check_launch("lrb_trsv_cols_kernel");
+}
 int lrb_amll(hipStream_t st, const LrChunk &c) {
   hipLaunchKernelGGL(lrb_amll_kernel, dim3(c.slots), dim3(1024), 0, st, c);
   return check_launch("lrb_amll_kernel");

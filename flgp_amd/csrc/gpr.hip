@@ -204,6 +204,99 @@ int gpr_rowquad(hipStream_t st, const double *dV2, long ld2, const double *dW, i
   hipLaunchKernelGGL(gpr_rowquad_kernel, dim3(ceil_div(mnew, 256)), dim3(256), 0, st, dV2, ld2, dW, mnew, K, d_l, c, d_cov);
   return check_launch("gpr_rowquad_kernel");
 }
+// ---- the elementwise steps of the regression objective for a chunk of problems (RgbChunk, common.h) -------
+// Each is the kernel of the same name above with the slot in blockIdx.y and the operands at the slot's stride: the
+// expressions are those kernels', term for term, so a slot's bits are the single evaluation's.
+
+// gpr_weights_kernel's ls at the slot's t = x[0], on the eigenvalues of the slot's pair
+__global__ void rgb_weights_kernel(RgbChunk c) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= c.K) return;
+  const long s = blockIdx.y;
+  const double t = c.x[s * c.sxn];
+  const double lam = 1.0 - c.values[c.pair[s] * c.sk + k];
+  c.ls[s * c.sk + k] = exp(-0.5 * t * lam) + 0.0;
+}
+// gpr_q_kernel
+__global__ void rgb_q_kernel(RgbChunk c) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = c.K;
+  if (e >= (long)K * K) return;
+  const long s = blockIdx.y;
+  const double *__restrict__ VtV = c.different ? c.M + s * c.sq : c.M0 + c.pair[s] * c.sq;
+  const double *__restrict__ ls = c.ls + s * c.sk;
+  const double cc = c.c[s];
+  const int i = (int)(e % K), j = (int)(e / K);
+  c.Q[s * c.sq + e] = ls[i] * VtV[e] * ls[j] + (i == j ? cc : 0.0);
+}
+// gpr_scale_kernel
+__global__ void rgb_scale_kernel(int rows, int cols, const double *M, long sm, const int *__restrict__ list,
+                                 const double *a, long sa, const double *b, long sb, double *out, long so) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)rows * cols) return;
+  const long s = blockIdx.y;
+  const int i = (int)(e % rows), j = (int)(e / rows);
+  double v = M[(list ? (long)list[s] : s) * sm + e];
+  if (a) v *= a[s * sa + i];
+  if (b) v *= b[s * sb + j];
+  out[s * so + e] = v;
+}
+// gpr_diff_kernel with the slot's factor
+__global__ void rgb_diff_kernel(long count, const double *__restrict__ X, long sx, const double *Z, long sz,
+                                const double *__restrict__ f, double *out, long so) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  const long s = blockIdx.y;
+  const double alpha = f[s];
+  out[s * so + e] = alpha * (X[s * sx + e] - Z[s * sz + e]);
+}
+// gpr_zinv_kernel on x[1 .. m]
+__global__ void rgb_zinv_kernel(RgbChunk c) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.m) return;
+  const long s = blockIdx.y;
+  const double *noise = c.x + s * c.sxn + 1;
+  c.d[s * c.sv + i] = 1.0 / (noise[i] + c.sigma);
+}
+// gpr_rowscale_ld_kernel
+__global__ void rgb_rowscale_kernel(int rows, int cols, const double *M, long ldm, long sm, const int *__restrict__ list,
+                                    const double *__restrict__ a, long sa, double *out, long so) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)rows * cols) return;
+  const long s = blockIdx.y;
+  const int i = (int)(e % rows), j = (int)(e / rows);
+  out[s * so + e] = a[s * sa + i] * M[(list ? (long)list[s] : s) * sm + (size_t)j * ldm + i];
+}
+
+int rgb_weights(hipStream_t st, const RgbChunk &c, int slots) {
+  hipLaunchKernelGGL(rgb_weights_kernel, dim3(ceil_div(c.K, 256), slots), dim3(256), 0, st, c);
+  return check_launch("rgb_weights_kernel");
+}
+int rgb_q(hipStream_t st, const RgbChunk &c, int slots) {
+  hipLaunchKernelGGL(rgb_q_kernel, dim3(ceil_div((long)c.K * c.K, 256), slots), dim3(256), 0, st, c);
+  return check_launch("rgb_q_kernel");
+}
+int rgb_scale(hipStream_t st, int slots, int rows, int cols, const double *M, long sm, const int *list, const double *a, long sa,
+              const double *b, long sb, double *out, long so) {
+  hipLaunchKernelGGL(rgb_scale_kernel, dim3(ceil_div((long)rows * cols, 256), slots), dim3(256), 0, st, rows, cols, M, sm, list, a,
+                     sa, b, sb, out, so);
+  return check_launch("rgb_scale_kernel");
+}
+int rgb_diff(hipStream_t st, int slots, long count, const double *X, long sx, const double *Z, long sz, const double *f,
+             double *out, long so) {
+  hipLaunchKernelGGL(rgb_diff_kernel, dim3(ceil_div(count, 256), slots), dim3(256), 0, st, count, X, sx, Z, sz, f, out, so);
+  return check_launch("rgb_diff_kernel");
+}
+int rgb_zinv(hipStream_t st, const RgbChunk &c, int slots) {
+  hipLaunchKernelGGL(rgb_zinv_kernel, dim3(ceil_div(c.m, 256), slots), dim3(256), 0, st, c);
+  return check_launch("rgb_zinv_kernel");
+}
+int rgb_rowscale(hipStream_t st, int slots, int rows, int cols, const double *M, long ldm, long sm, const int *list,
+                 const double *a, long sa, double *out, long so) {
+  hipLaunchKernelGGL(rgb_rowscale_kernel, dim3(ceil_div((long)rows * cols, 256), slots), dim3(256), 0, st, rows, cols, M, ldm, sm,
+                     list, a, sa, out, so);
+  return check_launch("rgb_rowscale_kernel");
+}
 int gpr_rowdot(hipStream_t st, const double *dC21, const double *dAl, int mnew, int m, const double *dV2, long ld2, int K,
                const double *d_l, double c, double *d_cov) {
   hipLaunchKernelGGL(gpr_rowdot_kernel, dim3(ceil_div(mnew, 256)), dim3(256), 0, st, dC21, dAl, mnew, m, dV2, ld2, K, d_l, c, d_cov);

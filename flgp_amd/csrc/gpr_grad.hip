@@ -116,8 +116,8 @@ __device__ __forceinline__ double rg_a(const double *values, int k, double t) {
 }
 
 // value and gradient from the pieces RgTerms names (one workgroup); out = [value, grad_0 .. grad_{nx-1}]
-__global__ __launch_bounds__(1024) void rg_assemble_kernel(RgTerms T) {
-  __shared__ double red[1024];
+// (written once, for the kernel of one evaluation and the one-workgroup-per-slot kernel of the batch below)
+__device__ __forceinline__ void rg_assemble_body(const RgTerms &T, double *red) {
   const int tid = threadIdx.x, m = T.m, q = T.q, K = T.K;
   const double *x = T.x, sigma = T.sigma;
   const long mq = (long)m * q;
@@ -236,10 +236,64 @@ __global__ __launch_bounds__(1024) void rg_assemble_kernel(RgTerms T) {
     }
   }
 }
+__global__ __launch_bounds__(1024) void rg_assemble_kernel(RgTerms T) {
+  __shared__ double red[1024];
+  rg_assemble_body(T, red);
+}
 
 int rg_assemble(hipStream_t st, const RgTerms &T) {
   hipLaunchKernelGGL(rg_assemble_kernel, dim3(1), dim3(1024), 0, st, T);
   return check_launch("rg_assemble_kernel");
+}
+
+// ---- the same for a chunk of problems (RgbChunk, common.h) ---------------------------------------------
+// rg_rowsumsq_kernel on the slot's X
+__global__ void rgb_rowsumsq_kernel(const double *__restrict__ X, long sx, long ldx, int rows, int cols, double *__restrict__ out,
+                                    long so) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  const long sl = blockIdx.y;
+  const double *x = X + sl * sx;
+  double s = 0.0;
+  for (int k = 0; k < cols; ++k) { const double v = x[(size_t)k * ldx + i]; s += v * v; }
+  out[sl * so + i] = s;
+}
+int rgb_rowsumsq(hipStream_t st, int slots, const double *X, long sx, long ldx, int rows, int cols, double *out, long so) {
+  hipLaunchKernelGGL(rgb_rowsumsq_kernel, dim3(ceil_div(rows, 256), slots), dim3(256), 0, st, X, sx, ldx, rows, cols, out, so);
+  return check_launch("rgb_rowsumsq_kernel");
+}
+
+// One workgroup per slot: chol_logdet_kernel's sum over the factor in Q (gpc.hip: a stride of 1024, the same tree), then
+// rg_assemble_body on the slot's pieces, and the slot's pivot flag behind the chunk's results for the host's one copy.
+__global__ __launch_bounds__(1024) void rgb_assemble_kernel(RgbChunk c) {
+  __shared__ double red[1024];
+  const long s = blockIdx.x;
+  const int K = c.K;
+  const double *LQ = c.Q + s * c.sq;
+  double ld = 0.0;
+  for (int i = threadIdx.x; i < K; i += 1024) ld += log(LQ[(size_t)i * K + i] + 1e-9);
+  ld = rg_block_sum(ld, red);
+  if (threadIdx.x == 0) {
+    c.logdet[s] = ld;
+    ((int *)(c.out + (size_t)gridDim.x * (1 + c.nx)))[s] = c.flag[s];
+  }
+  RgTerms T;
+  T.m = c.m; T.q = c.q; T.K = K; T.direct = 0; T.different = c.different; T.posterior = c.posterior; T.grad = c.grad;
+  T.sigma = c.sigma; T.c = c.c[s];
+  for (int a = 0; a < 5; ++a) T.prior[a] = c.prior[a];
+  T.x = c.x + s * c.sxn;
+  T.Y = c.Y; T.alpha = c.alpha + s * c.smq;
+  T.logdet = c.logdet + s;
+  T.values = c.values + c.pair[s] * c.sk; T.ls = c.ls + s * c.sk;
+  T.Vta = c.Vta + s * c.skq; T.d = c.d + s * c.sv; T.s = nullptr;
+  T.M = c.different ? c.M + s * c.sq : c.M0 + c.pair[s] * c.sq;
+  T.Qinv = c.Qinv + s * c.sq; T.M1 = c.M1 + s * c.sq;
+  T.out = c.out + s * (1 + c.nx);
+  rg_assemble_body(T, red);
+}
+int rgb_assemble(hipStream_t st, const RgbChunk &c, int slots) {
+  hipLaunchKernelGGL(rgb_assemble_kernel, dim3(slots), dim3(1024), 0, st, c);
+  return check_launch("rgb_assemble_kernel");
 }
 
 }  // namespace flgp
