@@ -389,7 +389,6 @@ int gpr_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx
 int tri_inverse(hipStream_t st, const double *dL, long lda, int m, double *dX, long ldx, double *dT, double *work, size_t we,
                 const int *d_flag);
 int rg_colsumsq(hipStream_t st, const double *dX, long ldx, int rows, int cols, double *d_out);   // out[j] = |X(:, j)|^2
-int rg_rowsumsq(hipStream_t st, const double *dX, long ldx, int rows, int cols, double *d_out);   // out[i] = |X(i, :)|^2
 // The pieces of one evaluation (device pointers) and where its value and gradient go: out = [value, grad_0 .. grad_{nx-1}].
 // direct (m <= K): d = diag C^-1 (m), s = |columns of L^-1 V|^2 (K).  Woodbury: M = V^T V ("same") or V^T Z^-1 V, Qinv = Q^-1,
 // M1 = Q^-1 Ls M (K x K), ls = exp(-t lambda / 2); "different": d = |rows of V Ls L_Q^-T|^2 (m).  Vta = V^T alpha (K x q).

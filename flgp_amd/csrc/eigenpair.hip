@@ -12,6 +12,8 @@
 #include "common.h"
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <memory>
 #include <string>
 #include <vector>
@@ -138,6 +140,14 @@ extern "C" int flgp_eigenpair_vc(const flgp_eigenpair *ep, int K, const int *idx
 
 // ---- regression consumers of the resident pair: the Woodbury algebra stays on the device --------------
 namespace {
+// the two verdicts on a system matrix that did not factor, under the entry's name, and how one is returned
+std::string not_positive_definite(const char *who) {
+  return std::string(who) + ": the system matrix is not positive definite (Cholesky pivot <= 0)";
+}
+std::string not_finite(const char *who) {
+  return std::string(who) + ": the objective is not finite (the system matrix is numerically singular)";
+}
+int noconv(const std::string &verdict) { set_error("%s", verdict.c_str()); return FLGP_ERR_NOCONV; }
 struct GprCtx {
   DevBuf ls, l, flag;
   int prepare(hipStream_t st, const flgp_eigenpair *ep, int K, double t) {
@@ -149,8 +159,7 @@ struct GprCtx {
   int verdict(hipStream_t st, const char *who) {   // synchronises
     int h = 0;
     FLGP_TRY(read_flag(st, flag.p, &h));
-    if (h) { set_error("%s: the system matrix is not positive definite (Cholesky pivot <= 0)", who); return FLGP_ERR_NOCONV; }
-    return FLGP_OK;
+    return h ? noconv(not_positive_definite(who)) : FLGP_OK;
   }
 };
 
@@ -444,167 +453,66 @@ extern "C" int flgp_eigenpair_posterior_classification(const flgp_eigenpair *ep,
   return posterior_dense(who, ep, K, t, sigma11, sigma22, r0, m, Y, r1, mnew, tol, max_iter, mean, cov, nullptr);
 }
 
-// ---- regression training objectives: train_regression_gp_cpp's four objectives on the resident pair ------
+// ---- regression training objectives: train_regression_gp_cpp's four objectives on the resident pair.  The
+// entries and the Woodbury route (m > K) are with the training context at the end of this file -------------
 namespace {
 bool all_finite(const double *v, int cnt) {
   for (int a = 0; a < cnt; ++a)
     if (!std::isfinite(v[a])) return false;
   return true;
 }
-// One evaluation of the objective.  It owns every device buffer that RgTerms points into, and the steps' scratch, until the
-// result has come down: a step leaves pointers behind, so none of them is a step's local.
-struct RgEval {
-  Stream st;
+// One evaluation on the direct route (m <= K), on the caller's stream.  It owns every device buffer that RgTerms points
+// into, and the steps' scratch, until the result has come down: a step leaves pointers behind, so none of them is a step's
+// local.  The caller (flgp_regression_batch::direct_one) fills it.
+struct RgDirect {
+  hipStream_t st = nullptr;
   const flgp_eigenpair *ep = nullptr;
   Rows r;
   GprCtx G;                                                     // ls = exp(-t lambda / 2) + 0.0
   RgTerms T{};
   const double *x = nullptr;                                    // the host's: t = x[0]; "same": noise = x[1]
-  size_t we = 0;                                                // of `work` under every V^T product
   DevBuf dY, dx, alpha, out, ld, Vta, d, s, work;
   DevBuf C, hw, Li, Tb, W;
-  DevBuf M, Q, R, Tq, ZV, Qinv, LsM, M1, P;
 
-  // the stream, the spectral weights, Y and x up, and what every branch fills
-  int begin(const double *Y, int nx) {
-    FLGP_TRY(st.create());
-    FLGP_TRY(G.prepare(st.s, ep, T.K, x[0]));
-    FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)T.m * T.q, st.s));
-    FLGP_TRY(upload(dx, x, sizeof(double) * (size_t)nx, st.s));
-    FLGP_TRY(alpha.alloc(sizeof(double) * (size_t)T.m * T.q)); FLGP_TRY(out.alloc(sizeof(double) * (size_t)(1 + nx)));
-    FLGP_TRY(ld.alloc(sizeof(double)));
-    if (T.grad) FLGP_TRY(Vta.alloc(sizeof(double) * (size_t)T.K * T.q));
-    if (T.grad || (T.different && !T.direct)) FLGP_TRY(d.alloc(sizeof(double) * (size_t)T.m));
-    return FLGP_OK;
-  }
   // C = HK(idx, idx) + sigma I + (x1 I or diag(x[1..m])), factored; alpha = C^-1 Y        (:362-369, :469-477)
-  int direct_terms() {
+  int terms() {
     const int m = T.m, q = T.q, K = T.K;
-    FLGP_TRY(hk_c11(st.s, ep, K, x[0], r, T.sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
-    FLGP_TRY(T.different ? gpr_add_diag_vec(st.s, C.as<double>(), m, dx.as<double>() + 1) : gpr_add_diag(st.s, C.as<double>(), m, x[1]));
-    FLGP_TRY(chol_blocked(st.s, C.as<double>(), m, m, G.flag.as<int>()));
-    FLGP_HIP(hipMemcpyAsync(alpha.p, dY.p, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToDevice, st.s));
-    FLGP_TRY(chol_trsv(st.s, C.as<double>(), m, m, alpha.as<double>(), m, q, 3, G.flag.as<int>()));
-    FLGP_TRY(chol_logdet(st.s, C.as<double>(), m, m, ld.as<double>()));
+    FLGP_TRY(hk_c11(st, ep, K, x[0], r, T.sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
+    FLGP_TRY(T.different ? gpr_add_diag_vec(st, C.as<double>(), m, dx.as<double>() + 1) : gpr_add_diag(st, C.as<double>(), m, x[1]));
+    FLGP_TRY(chol_blocked(st, C.as<double>(), m, m, G.flag.as<int>()));
+    FLGP_HIP(hipMemcpyAsync(alpha.p, dY.p, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToDevice, st));
+    FLGP_TRY(chol_trsv(st, C.as<double>(), m, m, alpha.as<double>(), m, q, 3, G.flag.as<int>()));
+    FLGP_TRY(chol_logdet(st, C.as<double>(), m, m, ld.as<double>()));
     if (!T.grad) return FLGP_OK;
     // d_i = (C^-1)_ii, s_k = |(L^-1 V)_{:,k}|^2, V^T alpha
-    const size_t wi = (size_t)32 * 64 * m;
+    const size_t wi = (size_t)32 * 64 * m, we = vt_work_elems(K, q);
     FLGP_TRY(Li.alloc(sizeof(double) * (size_t)m * m)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * m));
     FLGP_TRY(W.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(s.alloc(sizeof(double) * (size_t)K));
     FLGP_TRY(work.alloc(sizeof(double) * std::max(wi, we)));
-    FLGP_TRY(tri_inverse(st.s, C.as<double>(), m, m, Li.as<double>(), m, Tb.as<double>(), work.as<double>(), wi, G.flag.as<int>()));
-    FLGP_TRY(rg_colsumsq(st.s, Li.as<double>(), m, m, m, d.as<double>()));
-    FLGP_TRY(r.gather(st.s, ep, K));
-    FLGP_TRY(gemm_nn(st.s, m, K, m, Li.as<double>(), m, r.V, r.ld, W.as<double>(), nullptr, 0));
-    FLGP_TRY(rg_colsumsq(st.s, W.as<double>(), m, m, K, s.as<double>()));
-    return gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we);
-  }
-  // Woodbury (:395-405, :492-502): M = V^T V or V^T Z^-1 V, Q = Ls M Ls + (c or 1) I, alpha = Z^-1 (Y - V Ls Q^-1 Ls V^T Z^-1 Y).
-  // The factor of Q stays for the log-determinant and the gradient, so this is chol_blocked, not woodbury_step's chol_solve.
-  int woodbury_terms() {
-    const int m = T.m, q = T.q, K = T.K;
-    FLGP_TRY(r.gather(st.s, ep, K));
-    FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Q.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(Tq.alloc(sizeof(double) * (size_t)m * q));
-    FLGP_TRY(work.alloc(sizeof(double) * we));
-    const double *B = r.V;      // Z^-1 V for "different"
-    long ldb = r.ld;
-    if (T.different) {
-      FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K));
-      FLGP_TRY(gpr_zinv(st.s, dx.as<double>() + 1, T.sigma, m, d.as<double>()));                          // d = z^-1 for now
-      FLGP_TRY(gpr_rowscale_ld(st.s, r.V, r.ld, d.as<double>(), m, K, ZV.as<double>()));
-      FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));     // Z^-1 Y
-      B = ZV.as<double>(); ldb = m;
-    }
-    FLGP_TRY(gemm_tn(st.s, K, K, m, r.V, r.ld, B, ldb, M.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, T.different ? alpha.as<double>() : dY.as<double>(), m, R.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_q(st.s, M.as<double>(), G.ls.as<double>(), K, T.c, Q.as<double>()));
-    FLGP_TRY(chol_blocked(st.s, Q.as<double>(), K, K, G.flag.as<int>()));
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls V^T Z^-1 Y
-    FLGP_TRY(chol_trsv(st.s, Q.as<double>(), K, K, R.as<double>(), K, q, 3, G.flag.as<int>()));             // Q^-1 (.)
-    FLGP_TRY(gpr_scale(st.s, R.as<double>(), G.ls.as<double>(), nullptr, K, q, R.as<double>()));             // Ls (.)
-    FLGP_TRY(gemm_nn(st.s, m, q, K, r.V, r.ld, R.as<double>(), K, Tq.as<double>(), nullptr, 0));             // V (.)
-    FLGP_TRY(gpr_diff(st.s, dY.as<double>(), Tq.as<double>(), T.different ? 1.0 : 1.0 / T.c, (long)m * q, alpha.as<double>()));
-    if (T.different) FLGP_TRY(gpr_rowscale_ld(st.s, alpha.as<double>(), m, d.as<double>(), m, q, alpha.as<double>()));
-    FLGP_TRY(chol_logdet(st.s, Q.as<double>(), K, K, ld.as<double>()));
-    if (!T.grad) return FLGP_OK;
-    // Q^-1 = L_Q^-T L_Q^-1, M1 = Q^-1 Ls M, V^T alpha; "different": d_i = |row i of V Ls L_Q^-T|^2
-    const size_t wi = (size_t)32 * 64 * K;
-    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
-    FLGP_TRY(Qinv.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(LsM.alloc(sizeof(double) * (size_t)K * K));
-    FLGP_TRY(M1.alloc(sizeof(double) * (size_t)K * K));
-    DevBuf wt;                 // tri_inverse's own planes: nothing points into them after this step
-    FLGP_TRY(wt.alloc(sizeof(double) * wi));
-    FLGP_TRY(tri_inverse(st.s, Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, G.flag.as<int>()));
-    FLGP_TRY(gemm_tn(st.s, K, K, K, Li.as<double>(), K, Li.as<double>(), K, Qinv.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_scale(st.s, M.as<double>(), G.ls.as<double>(), nullptr, K, K, LsM.as<double>()));
-    FLGP_TRY(gemm_nn(st.s, K, K, K, Qinv.as<double>(), K, LsM.as<double>(), K, M1.as<double>(), nullptr, 0));
-    FLGP_TRY(gemm_tn(st.s, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we));
-    if (!T.different) return FLGP_OK;
-    // P = V (L_Q^-1 Ls)^T (m x K): B(k, j) = Li(j, k) ls_k
-    FLGP_TRY(P.alloc(sizeof(double) * (size_t)m * K));
-    FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, G.ls.as<double>(), K, K, LsM.as<double>()));     // reuse: Li Ls
-    FLGP_TRY(gemm_launch(st.s, m, K, K, 1.0, r.V, 1, r.ld, LsM.as<double>(), K, 1, 0.0, nullptr, 0, 0, P.as<double>(), 1, m,
-                         nullptr, 0, 0.0, nullptr));
-    return rg_rowsumsq(st.s, P.as<double>(), m, m, K, d.as<double>());
+    FLGP_TRY(tri_inverse(st, C.as<double>(), m, m, Li.as<double>(), m, Tb.as<double>(), work.as<double>(), wi, G.flag.as<int>()));
+    FLGP_TRY(rg_colsumsq(st, Li.as<double>(), m, m, m, d.as<double>()));
+    FLGP_TRY(r.gather(st, ep, K));
+    FLGP_TRY(gemm_nn(st, m, K, m, Li.as<double>(), m, r.V, r.ld, W.as<double>(), nullptr, 0));
+    FLGP_TRY(rg_colsumsq(st, W.as<double>(), m, m, K, s.as<double>()));
+    return gemm_tn(st, K, q, m, r.V, r.ld, alpha.as<double>(), m, Vta.as<double>(), work.as<double>(), we);
   }
   // rg_assemble on what the steps left, then [value, grad] down
   int finish(const char *who, int nx, double *value, double *grad) {
     T.x = dx.as<double>(); T.Y = dY.as<double>(); T.alpha = alpha.as<double>(); T.logdet = ld.as<double>();
     T.values = (const double *)ep->values.p; T.ls = G.ls.as<double>();
     T.Vta = Vta.as<double>(); T.d = d.as<double>(); T.s = s.as<double>();
-    T.M = M.as<double>(); T.Qinv = Qinv.as<double>(); T.M1 = M1.as<double>();
     T.out = out.as<double>();
-    FLGP_TRY(rg_assemble(st.s, T));
+    FLGP_TRY(rg_assemble(st, T));
     std::vector<double> h((size_t)nx + 1);
-    FLGP_TRY(d2h(h.data(), out.p, sizeof(double) * h.size(), st.s));
-    FLGP_TRY(G.verdict(st.s, who));
-    const int cnt = T.grad ? nx + 1 : 1;
-    if (!all_finite(h.data(), cnt)) {
-      set_error("%s: the objective is not finite (the system matrix is numerically singular)", who);
-      return FLGP_ERR_NOCONV;
-    }
+    FLGP_TRY(d2h(h.data(), out.p, sizeof(double) * h.size(), st));
+    FLGP_TRY(G.verdict(st, who));
+    if (!all_finite(h.data(), T.grad ? nx + 1 : 1)) return noconv(not_finite(who));
     *value = h[0];
     if (T.grad) std::memcpy(grad, h.data() + 1, sizeof(double) * (size_t)nx);
     return FLGP_OK;
   }
 };
 }  // namespace
-
-// negative_marginal_likelihood{,_diff_noise}_regression_cpp (src/train.cpp:351-436, 459-555) and their posterior forms
-// (:333-348, 438-457).  Only x goes up and [value, grad] comes down.  The m x m matrices of the direct branch (C^-1, U, G)
-// are replaced by L^-1 (gpr_grad.hip); the Woodbury branch forms alpha (m x q) as the reference does.
-extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y, int q,
-                                                   double sigma, const char *noise, const char *approach, const double *prior,
-                                                   const double *x, int nx, double *value, double *grad) {
-  const char *who = "regression_objective";
-  FLGP_REQUIRE(noise && approach, "%s: null pointer", who);
-  const bool different = std::strcmp(noise, "different") == 0;
-  if (!different && std::strcmp(noise, "same") != 0) { set_error("The noise setting is illegal!"); return FLGP_ERR_UNSUPPORTED; }
-  const bool posterior = std::strcmp(approach, "posterior") == 0;
-  if (!posterior && std::strcmp(approach, "marginal") != 0) {
-    set_error("This model selection approach is not supported!");
-    return FLGP_ERR_UNSUPPORTED;
-  }
-  FLGP_REQUIRE(ep && idx && Y && x && value, "%s: null pointer", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && q >= 1, "%s: bad shape (K=%d of %d, m=%d, q=%d)", who, K, ep->K, m, q);
-  FLGP_REQUIRE(nx == (different ? m + 1 : 2), "%s: noise \"%s\" takes %d parameters, not %d", who, noise, different ? m + 1 : 2, nx);
-  FLGP_REQUIRE(all_finite(x, nx), "%s: x must be finite", who);
-  for (int a = 1; a < nx; ++a) FLGP_REQUIRE(x[a] + sigma > 0.0, "%s: x[%d] + sigma must be positive", who, a);
-  FLGP_REQUIRE(!posterior || x[0] > 0.0, "%s: t = x[0] must be positive under \"posterior\"", who);
-  RgEval E;
-  FLGP_TRY(E.r.check(ep, idx, m, who, "idx"));
-  E.ep = ep; E.x = x; E.we = vt_work_elems(K, q);
-  RgTerms &T = E.T;
-  T.m = m; T.q = q; T.K = K; T.direct = m <= K; T.different = different; T.posterior = posterior; T.grad = grad != nullptr;
-  T.sigma = sigma; T.c = different ? 1.0 : x[1] + sigma;
-  const double dflt[5] = {1.0, 10.0, 2.0, 0.1, 1e-3};         // PostOFDataReg (src/train.h:153-155)
-  for (int a = 0; a < 5; ++a) T.prior[a] = prior ? prior[a] : dflt[a];
-
-  FLGP_TRY(E.begin(Y, nx));
-  FLGP_TRY(T.direct ? E.direct_terms() : E.woodbury_terms());
-  return E.finish(who, nx, value, grad);
-}
 
 // ---- logit training objective: what train_lae_logit_gp_cpp's COBYLA minimises, on the
 // resident pair, for B problems (labels, t) in one call; the single entry is the batch of one ------------------------------
@@ -2185,30 +2093,51 @@ extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, 
 // ---- regression training objective for B (pair, x) problems in one call -------------------------------
 // A training context: made once per grid of pairs, evaluated once per optimiser step.  What depends on (pair, rows, Y) only
 // is built at create; an evaluation uploads the x of its problems and brings their values and gradients down.
+// flgp_eigenpair_regression_objective is the context of one problem, made on the stack, evaluated once and gone: the library
+// holds the Woodbury steps once.
 namespace {
 struct NoState {};
+// The host's side of a buffer that is copied every evaluation: pinned for a context, which lives through many; plain memory
+// for the single entry's, which is used once (a pageable copy, as its upload and d2h always were).
+struct HostMirror {
+  double *p = nullptr;
+  bool pinned = false;
+  ~HostMirror() { if (pinned) (void)hipHostFree(p); else std::free(p); }
+  int alloc(size_t bytes, bool pin) {
+    pinned = pin;
+    if (pin) FLGP_HIP(hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
+    else p = (double *)std::malloc(bytes);
+    if (!p) { set_error("malloc of %zu bytes failed", bytes); return FLGP_ERR_NOMEM; }
+    return FLGP_OK;
+  }
+};
 }  // namespace
 
 struct flgp_regression_batch {
   int B = 0, K = 0, m = 0, q = 0, nx = 0, chunk = 1, P = 0, max_parallel = 0, device = 0;
-  bool different = false, posterior = false, direct = false, range = false;
+  bool different = false, posterior = false, direct = false;
+  bool in_place = false;                          // the rows are a range and are read where the pair keeps them
   double sigma = 0.0, prior[5] = {0, 0, 0, 0, 0};
   std::vector<const flgp_eigenpair *> pairs;      // the P distinct ones, in order of first appearance
   std::vector<int> pair_of, idx;                  // problem -> pair; the rows (the host's copy)
   Stream st;
   DevBuf didx, dY, vals, V, M0, R0;               // per pair: K eigenvalues, the gathered rows, "same": V^T V and V^T Y
+  DevBuf work0;                                   // the workspace of M0 and R0: giving it back waits for the device, so the
+                                                  // one-shot context keeps it to its end and create returns it after its wait
+  // pair p's rows (m x K) and their leading dimension: where the pair keeps them, or the gathered copy
+  const double *rows_of(int p) const {
+    return in_place ? (const double *)pairs[(size_t)p]->vectors.p + idx[0] : (const double *)V.p + (size_t)p * C.sx;
+  }
+  long ld_of(int p) const { return in_place ? pairs[(size_t)p]->n : m; }
   // the Woodbury route's chunk
   RgbChunk C{};
   LrChunk L{};                                    // its K x K factor under the lrb_* / wsb_* steps: K, Q, sq, flag
-  DevBuf in, ls, alpha, Tq, R, Vta, M, Q, Li, Tb, Qinv, LsM, M1, d, ZV, Pm, logdet, flag, out, part, all;
+  DevBuf in, ls, alpha, Tq, R, Vta, M, Q, Li, Tb, Qinv, LsM, M1, d, ZV, Pm, logdet, flag, out, part;
   int planM = 1, planR = 1, planQi = 1;           // the splits of the single entry's products on its workspace
   size_t pe = 0, wi = 0;
-  long sp = 0, stb = 0, in_elems = 0, off_c = 0, off_ci = 0, off_pair = 0;
-  double *h_in = nullptr, *h_out = nullptr;       // pinned mirrors of `in` and `out`
-  ~flgp_regression_batch() {
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-  }
+  long sp = 0, stb = 0, in_elems = 0, off_c = 0, off_ci = 0, off_pair = 0, off_all = 0;
+  HostMirror h_in, h_out;                         // of `in` and `out`
+  const int *all = nullptr;                       // 0 .. chunk-1, in `in`
 
   static void plans(int m, int K, int q, int *pM, int *pR, int *pQi, size_t *pe, size_t *wi) {
     const size_t we = vt_work_elems(K, q);
@@ -2230,15 +2159,16 @@ struct flgp_regression_batch {
     if (different) e += (double)pad32((long)K * K) + pad32(m) + 2.0 * pad32((long)m * K);
     return 8.0 * e + 8.0;
   }
-  int alloc_chunk() {
+  int alloc_chunk(bool pinned) {
     RgbChunk &c = C;
     const size_t S = (size_t)chunk;
     plans(m, K, q, &planM, &planR, &planQi, &pe, &wi);
     sp = pad32((long)pe); stb = pad32((long)64 * K);
     c.sv = pad32(m); c.sk = pad32(K); c.skq = pad32((long)K * q); c.smq = pad32((long)m * q); c.sq = pad32((long)K * K);
     c.sx = pad32((long)m * K); c.sxn = pad32(nx);
-    // one upload per chunk: [x of every slot | c | 1 / c | the pairs' numbers (ints)]
-    off_c = (long)S * c.sxn; off_ci = off_c + pad32(chunk); off_pair = off_ci + pad32(chunk); in_elems = off_pair + pad32(chunk);
+    // one upload per chunk: [x of every slot | c | 1 / c | the pairs' numbers (ints) | 0 .. chunk-1 (ints), written once]
+    off_c = (long)S * c.sxn; off_ci = off_c + pad32(chunk); off_pair = off_ci + pad32(chunk); off_all = off_pair + pad32(chunk);
+    in_elems = off_all + pad32(chunk);
     FLGP_TRY(in.alloc(sizeof(double) * (size_t)in_elems));
     FLGP_TRY(ls.alloc(sizeof(double) * S * c.sk));
     FLGP_TRY(alpha.alloc(sizeof(double) * S * c.smq)); FLGP_TRY(Tq.alloc(sizeof(double) * S * c.smq));
@@ -2249,23 +2179,20 @@ struct flgp_regression_batch {
     FLGP_TRY(part.alloc(sizeof(double) * S * std::max(sp, 32L)));
     FLGP_TRY(logdet.alloc(sizeof(double) * S)); FLGP_TRY(flag.alloc(sizeof(int) * S));
     FLGP_TRY(out.alloc(sizeof(double) * S * (size_t)(1 + nx) + sizeof(int) * S));
-    FLGP_TRY(all.alloc(sizeof(int) * S));
     if (different) {
       FLGP_TRY(M.alloc(sizeof(double) * S * c.sq)); FLGP_TRY(d.alloc(sizeof(double) * S * c.sv));
       FLGP_TRY(ZV.alloc(sizeof(double) * S * c.sx)); FLGP_TRY(Pm.alloc(sizeof(double) * S * c.sx));
     }
-    FLGP_HIP(hipHostMalloc((void **)&h_in, sizeof(double) * (size_t)in_elems, hipHostMallocDefault));
-    FLGP_HIP(hipHostMalloc((void **)&h_out, sizeof(double) * S * (size_t)(1 + nx) + sizeof(int) * S, hipHostMallocDefault));
-    std::memset(h_in, 0, sizeof(double) * (size_t)in_elems);
-    std::vector<int> ids(S);
-    for (size_t s = 0; s < S; ++s) ids[s] = (int)s;
-    FLGP_TRY(h2d(all.p, ids.data(), sizeof(int) * S, st.s));
-    FLGP_HIP(hipStreamSynchronize(st.s));
+    FLGP_TRY(h_in.alloc(sizeof(double) * (size_t)in_elems, pinned));
+    FLGP_TRY(h_out.alloc(sizeof(double) * S * (size_t)(1 + nx) + sizeof(int) * S, pinned));
+    std::memset(h_in.p, 0, sizeof(double) * (size_t)in_elems);
+    for (size_t s = 0; s < S; ++s) ((int *)(h_in.p + off_all))[s] = (int)s;
     c.m = m; c.q = q; c.K = K; c.nx = nx; c.different = different; c.posterior = posterior; c.grad = 1;
     c.sigma = sigma;
     for (int a = 0; a < 5; ++a) c.prior[a] = prior[a];
     c.x = in.as<double>(); c.c = c.x + off_c; c.ci = c.x + off_ci; c.pair = (const int *)(c.x + off_pair);
-    c.values = vals.as<double>(); c.V = V.as<double>(); c.M0 = M0.as<double>(); c.Y = dY.as<double>();
+    all = (const int *)(c.x + off_all);
+    c.values = vals.as<double>(); c.V = rows_of(0); c.M0 = M0.as<double>(); c.Y = dY.as<double>();
     c.ls = ls.as<double>(); c.alpha = alpha.as<double>(); c.Tq = Tq.as<double>(); c.R = R.as<double>(); c.Vta = Vta.as<double>();
     c.M = M.as<double>(); c.Q = Q.as<double>(); c.Li = Li.as<double>(); c.Qinv = Qinv.as<double>(); c.LsM = LsM.as<double>();
     c.M1 = M1.as<double>(); c.d = d.as<double>(); c.ZV = ZV.as<double>(); c.P = Pm.as<double>();
@@ -2278,26 +2205,29 @@ struct flgp_regression_batch {
   // one batched product on the chunk's planes; la / lb: the list of the A / B operand where it is not the slots' own
   int gemm(int S, int Mr, int Nc, int Kd, const double *A, long a_is, long a_ks, long a_bs, const int *la, const double *Bm,
            long b_ks, long b_js, long b_bs, double *Cm, long c_js, long c_bs, int split) {
-    GemmBatch gb{S, all.as<int>(), a_bs, b_bs, c_bs, 0, split ? sp : 0};
+    GemmBatch gb{S, all, a_bs, b_bs, c_bs, 0, split ? sp : 0};
     gb.a_slots = la;
     return gemm_launch(st.s, Mr, Nc, Kd, 1.0, A, a_is, a_ks, Bm, b_ks, b_js, 0.0, nullptr, 0, 0, Cm, 1, c_js,
                        split ? part.as<double>() : nullptr, split ? pe : 0, 0.0, nullptr, nullptr, nullptr, split, nullptr, &gb);
   }
-  // RgEval::woodbury_terms and rg_assemble for the S slots whose x, c and pairs are in h_in: every step one launch
+  // Woodbury (:395-405, :492-502) for the S slots whose x, c and pairs are in h_in, every step one launch: M = V^T V or
+  // V^T Z^-1 V, Q = Ls M Ls + (c or 1) I, alpha = Z^-1 (Y - V Ls Q^-1 Ls V^T Z^-1 Y), then value and gradient.  The factor
+  // of Q stays for the log-determinant and the gradient, so this is a blocked Cholesky, not woodbury_step's chol_solve.
   int woodbury_chunk(int S, bool grad) {
     RgbChunk &c = C;
     hipStream_t s = st.s;
     c.grad = grad ? 1 : 0;
-    const int *pl = c.pair, *a = all.as<int>();
-    FLGP_TRY(h2d(in.p, h_in, sizeof(double) * (size_t)in_elems, s));
+    const int *pl = c.pair, *a = all;
+    const long ldv = ld_of(0);
+    FLGP_TRY(h2d(in.p, h_in.p, sizeof(double) * (size_t)in_elems, s));
     FLGP_HIP(hipMemsetAsync(c.flag, 0, sizeof(int) * (size_t)S, s));
     FLGP_TRY(rgb_weights(s, c, S));
     if (different) {
       FLGP_TRY(rgb_zinv(s, c, S));                                                                        // d = z^-1 for now
-      FLGP_TRY(rgb_rowscale(s, S, m, K, c.V, m, c.sx, pl, c.d, c.sv, c.ZV, c.sx));                      // Z^-1 V
+      FLGP_TRY(rgb_rowscale(s, S, m, K, c.V, ldv, c.sx, pl, c.d, c.sv, c.ZV, c.sx));                      // Z^-1 V
       FLGP_TRY(rgb_rowscale(s, S, m, q, c.Y, m, 0, nullptr, c.d, c.sv, c.alpha, c.smq));                // Z^-1 Y
-      FLGP_TRY(gemm(S, K, K, m, c.V, m, 1, c.sx, pl, c.ZV, 1, m, c.sx, c.M, K, c.sq, planM));           // M = V^T Z^-1 V
-      FLGP_TRY(gemm(S, K, q, m, c.V, m, 1, c.sx, pl, c.alpha, 1, m, c.smq, c.R, K, c.skq, planR));      // V^T Z^-1 Y
+      FLGP_TRY(gemm(S, K, K, m, c.V, ldv, 1, c.sx, pl, c.ZV, 1, m, c.sx, c.M, K, c.sq, planM));           // M = V^T Z^-1 V
+      FLGP_TRY(gemm(S, K, q, m, c.V, ldv, 1, c.sx, pl, c.alpha, 1, m, c.smq, c.R, K, c.skq, planR));      // V^T Z^-1 Y
     }
     FLGP_TRY(rgb_q(s, c, S));
     FLGP_TRY(lrb_chol(s, L, a, S));
@@ -2306,7 +2236,7 @@ struct flgp_regression_batch {
     else FLGP_TRY(rgb_scale(s, S, K, q, R0.as<double>(), c.skq, pl, c.ls, c.sk, nullptr, 0, c.R, c.skq));
     FLGP_TRY(lrb_trsv_cols(s, L, a, S, c.R, c.skq, q));
     FLGP_TRY(rgb_scale(s, S, K, q, c.R, c.skq, nullptr, c.ls, c.sk, nullptr, 0, c.R, c.skq));
-    FLGP_TRY(gemm(S, m, q, K, c.V, 1, m, c.sx, pl, c.R, 1, K, c.skq, c.Tq, m, c.smq, 0));               // V (.)
+    FLGP_TRY(gemm(S, m, q, K, c.V, 1, ldv, c.sx, pl, c.R, 1, K, c.skq, c.Tq, m, c.smq, 0));               // V (.)
     FLGP_TRY(rgb_diff(s, S, (long)m * q, c.Y, 0, c.Tq, c.smq, c.ci, c.alpha, c.smq));
     if (different) FLGP_TRY(rgb_rowscale(s, S, m, q, c.alpha, m, c.smq, nullptr, c.d, c.sv, c.alpha, c.smq));
     if (grad) {
@@ -2317,30 +2247,30 @@ struct flgp_regression_batch {
       FLGP_TRY(gemm(S, K, K, K, c.Li, K, 1, c.sq, nullptr, c.Li, 1, K, c.sq, c.Qinv, K, c.sq, planQi));
       FLGP_TRY(rgb_scale(s, S, K, K, Mm, c.sq, ml, c.ls, c.sk, nullptr, 0, c.LsM, c.sq));
       FLGP_TRY(gemm(S, K, K, K, c.Qinv, 1, K, c.sq, nullptr, c.LsM, 1, K, c.sq, c.M1, K, c.sq, 0));
-      FLGP_TRY(gemm(S, K, q, m, c.V, m, 1, c.sx, pl, c.alpha, 1, m, c.smq, c.Vta, K, c.skq, planR));
+      FLGP_TRY(gemm(S, K, q, m, c.V, ldv, 1, c.sx, pl, c.alpha, 1, m, c.smq, c.Vta, K, c.skq, planR));
       if (different) {
         FLGP_TRY(rgb_scale(s, S, K, K, c.Li, c.sq, nullptr, nullptr, 0, c.ls, c.sk, c.LsM, c.sq));     // reuse: Li Ls
-        FLGP_TRY(gemm(S, m, K, K, c.V, 1, m, c.sx, pl, c.LsM, K, 1, c.sq, c.P, m, c.sx, 0));            // P = V (Li Ls)^T
+        FLGP_TRY(gemm(S, m, K, K, c.V, 1, ldv, c.sx, pl, c.LsM, K, 1, c.sq, c.P, m, c.sx, 0));            // P = V (Li Ls)^T
         FLGP_TRY(rgb_rowsumsq(s, S, c.P, c.sx, m, m, K, c.d, c.sv));
       }
     }
     FLGP_TRY(rgb_assemble(s, c, S));
-    FLGP_TRY(d2h(h_out, out.p, sizeof(double) * (size_t)S * (1 + nx) + sizeof(int) * (size_t)S, s));
+    FLGP_TRY(d2h(h_out.p, out.p, sizeof(double) * (size_t)S * (1 + nx) + sizeof(int) * (size_t)S, s));
     FLGP_HIP(hipStreamSynchronize(s));
     return FLGP_OK;
   }
-  // one problem of the direct route (m <= K) on the worker's stream: RgEval's begin without its stream and its upload of
-  // Y, then its direct_terms and finish
+  // one problem of the direct route (m <= K) on the worker's stream: the spectral weights, x up and what the steps fill; Y
+  // and the rows are the context's
   int direct_one(hipStream_t ws, const char *who, int b, const double *x, double *value, double *grad) {
-    const flgp_eigenpair *ep = pairs[(size_t)pair_of[(size_t)b]];
-    RgEval E;
-    struct Lend { Stream &s; ~Lend() { s.s = nullptr; } } lend{E.st};     // the pool's stream goes back before E does
-    E.st.s = ws;
-    E.ep = ep; E.x = x; E.we = vt_work_elems(K, q);
+    const int p = pair_of[(size_t)b];
+    const flgp_eigenpair *ep = pairs[(size_t)p];
+    RgDirect E;
+    E.st = ws; E.ep = ep; E.x = x;
     Rows &r = E.r;
     r.idx = idx.data(); r.m = m; r.resolved = true; r.gathered_K = K;
-    if (range) { r.row0 = idx[0]; r.V = (const double *)ep->vectors.p + r.row0; r.ld = ep->n; }
-    else { r.d = didx.as<int>(); r.V = V.as<double>() + (size_t)pair_of[(size_t)b] * C.sx; r.ld = m; }
+    r.V = rows_of(p); r.ld = ld_of(p);
+    if (in_place) r.row0 = idx[0];
+    else r.d = didx.as<int>();
     RgTerms &T = E.T;
     T.m = m; T.q = q; T.K = K; T.direct = 1; T.different = different; T.posterior = posterior; T.grad = grad != nullptr;
     T.sigma = sigma; T.c = different ? 1.0 : x[1] + sigma;
@@ -2351,14 +2281,16 @@ struct flgp_regression_batch {
     FLGP_TRY(E.alpha.alloc(sizeof(double) * (size_t)m * q)); FLGP_TRY(E.out.alloc(sizeof(double) * (size_t)(1 + nx)));
     FLGP_TRY(E.ld.alloc(sizeof(double)));
     if (T.grad) { FLGP_TRY(E.Vta.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(E.d.alloc(sizeof(double) * (size_t)m)); }
-    FLGP_TRY(E.direct_terms());
+    FLGP_TRY(E.terms());
     return E.finish(who, nx, value, grad);
   }
 };
 
 namespace {
-// the two strings, refused as the single entry refuses them
-int rgb_strings(const char *who, const char *noise, const char *approach, bool *different, bool *posterior) {
+constexpr double RG_DEFAULT_PRIOR[5] = {1.0, 10.0, 2.0, 0.1, 1e-3};         // PostOFDataReg (src/train.h:153-155)
+
+// the two strings of every entry, refused with the reference's texts
+int rg_strings(const char *who, const char *noise, const char *approach, bool *different, bool *posterior) {
   FLGP_REQUIRE(noise && approach, "%s: null pointer", who);
   *different = std::strcmp(noise, "different") == 0;
   if (!*different && std::strcmp(noise, "same") != 0) { set_error("The noise setting is illegal!"); return FLGP_ERR_UNSUPPORTED; }
@@ -2369,14 +2301,171 @@ int rgb_strings(const char *who, const char *noise, const char *approach, bool *
   }
   return FLGP_OK;
 }
+
+// what every entry refuses about one x; `at`: "" or "position <a>: "
+int rg_check_x(const char *at, const char *who, const double *x, int nx, double sigma, bool posterior) {
+  FLGP_REQUIRE(all_finite(x, nx), "%s%s: x must be finite", at, who);
+  for (int i = 1; i < nx; ++i) FLGP_REQUIRE(x[i] + sigma > 0.0, "%s%s: x[%d] + sigma must be positive", at, who, i);
+  FLGP_REQUIRE(!posterior || x[0] > 0.0, "%s%s: t = x[0] must be positive under \"posterior\"", at, who);
+  return FLGP_OK;
+}
+
+// The context of the problems eps[0 .. B-1], whose arguments the entry has checked: what depends on (pair, rows, Y) only.
+// Nothing here waits for the device, so the one-shot call queues its evaluation behind this.  `pinned`: see HostMirror.
+int rg_build(flgp_regression_batch &h, const flgp_eigenpair *const *eps, int B, int K, const int *idx, int m, const double *Y,
+             int q, double sigma, bool different, bool posterior, const double *prior, int max_parallel, bool pinned) {
+  h.B = B; h.K = K; h.m = m; h.q = q; h.nx = different ? m + 1 : 2; h.max_parallel = max_parallel;
+  h.different = different; h.posterior = posterior; h.direct = m <= K; h.sigma = sigma;
+  h.device = eps[0]->device;
+  for (int a = 0; a < 5; ++a) h.prior[a] = prior ? prior[a] : RG_DEFAULT_PRIOR[a];
+  h.pair_of.resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    size_t p = 0;
+    while (p < h.pairs.size() && h.pairs[p] != eps[b]) ++p;
+    if (p == h.pairs.size()) h.pairs.push_back(eps[b]);
+    h.pair_of[(size_t)b] = (int)p;
+  }
+  h.P = (int)h.pairs.size();
+  h.idx.assign(idx, idx + m);
+  // A range of rows is read in place, as Rows::gather reads it: by the direct route always, by the Woodbury route -- whose
+  // launches take one base and one leading dimension for every pair -- where there is one pair.  Any other rows are
+  // gathered, every distinct pair's into one buffer under the slots' strides.
+  h.in_place = is_range(idx, m) && (h.direct || h.P == 1);
+  FLGP_TRY(h.st.create());
+  hipStream_t st = h.st.s;
+  FLGP_TRY(upload(h.dY, Y, sizeof(double) * (size_t)m * q, st));
+  const long sx = pad32((long)m * K), sk = pad32(K), sq = pad32((long)K * K), skq = pad32((long)K * q);
+  h.C.sx = sx;
+  if (!h.in_place) {
+    FLGP_TRY(upload(h.didx, idx, sizeof(int) * (size_t)m, st));
+    FLGP_TRY(h.V.alloc(sizeof(double) * (size_t)h.P * sx));
+    for (int p = 0; p < h.P; ++p)
+      FLGP_TRY(flgp_dev_gather_rows(st, (const double *)h.pairs[(size_t)p]->vectors.p, h.pairs[(size_t)p]->n, h.didx.as<int>(), m,
+                                    K, h.V.as<double>() + (size_t)p * sx));
+  }
+  if (h.direct) {
+    h.chunk = plan_workers(max_parallel, B, 0.0, 0.0);
+    return FLGP_OK;
+  }
+  if (h.P == 1) h.vals.borrow(h.pairs[0]->values.p);      // a lone pair's eigenvalues are read where they are
+  else FLGP_TRY(h.vals.alloc(sizeof(double) * (size_t)h.P * sk));
+  for (int p = 0; h.P > 1 && p < h.P; ++p)
+    FLGP_HIP(hipMemcpyAsync(h.vals.as<double>() + (size_t)p * sk, h.pairs[(size_t)p]->values.p, sizeof(double) * (size_t)K,
+                            hipMemcpyDeviceToDevice, st));
+  if (!different) {
+    // M0 = V^T V and R0 = V^T Y per pair, on the workspace that decides their split
+    const size_t we = vt_work_elems(K, q);
+    DevBuf &work = h.work0;
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    FLGP_TRY(h.M0.alloc(sizeof(double) * (size_t)h.P * sq)); FLGP_TRY(h.R0.alloc(sizeof(double) * (size_t)h.P * skq));
+    for (int p = 0; p < h.P; ++p) {
+      const double *Vp = h.rows_of(p);
+      const long ld = h.ld_of(p);
+      FLGP_TRY(gemm_tn(st, K, K, m, Vp, ld, Vp, ld, h.M0.as<double>() + (size_t)p * sq, work.as<double>(), we));
+      FLGP_TRY(gemm_tn(st, K, q, m, Vp, ld, h.dY.as<double>(), m, h.R0.as<double>() + (size_t)p * skq, work.as<double>(), we));
+    }
+  }
+  // the chunk: max_parallel problems, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of the
+  // free memory
+  const int want = max_parallel > 0 ? max_parallel : B;
+  size_t free_b = 0, total_b = 0;
+  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  h.chunk = std::min(plan_workers(want, B, (double)free_b, flgp_regression_batch::slot_bytes(m, K, q, h.nx, different)),
+                     GEMM_BATCH_MAX);
+  return h.alloc_chunk(pinned);
+}
+
+// A evaluations on a context, whose arguments the entry has checked.  A failed position is reported under `who`, as
+// "position <a>: ..." where by_position.
+int rg_eval(flgp_regression_batch &h, const char *who, bool by_position, const int *prob, int A, const double *X, int ldx,
+            double *values, double *grads, int ldg, int *status) {
+  const int nx = h.nx, m = h.m;
+  std::vector<int> stat((size_t)A, FLGP_OK);
+  std::vector<std::string> why((size_t)A);
+  const int cnt = grads ? nx + 1 : 1;
+  auto fail = [&](int a, const std::string &verdict) {
+    stat[(size_t)a] = FLGP_ERR_NOCONV;
+    why[(size_t)a] = verdict;
+    if (!by_position) return;                           // the single entry leaves its outputs as they were, as it always did
+    values[a] = std::nan("");
+    if (grads) std::fill(grads + (size_t)a * ldg, grads + (size_t)a * ldg + nx, std::nan(""));
+  };
+  auto report = [&](int a, const std::string &text, int rc) {
+    if (by_position) set_error("position %d: %s", a, text.c_str());
+    else set_error("%s", text.c_str());
+    return rc;
+  };
+  if (h.direct) {
+    // the problems dealt to the pool's workers (worker_pool.h); one worker runs on the calling thread and the context's stream
+    DevicePool pool;
+    FLGP_TRY(pool.plan(h.max_parallel, A, 8.0 * (4.0 * m * m + 96.0 * m + (double)m * h.K + 2.0 * m * h.q) +
+                                              (double)flgp_dev_hk_workspace(m, m, h.K, 1)));
+    const PoolFailure bad = pool.run<NoState>(
+        h.st.s, A, [](NoState &) { return FLGP_OK; },
+        [&](hipStream_t ws, NoState &, int a) -> int {
+          const int b = prob ? prob[a] : a;
+          const int rc = h.direct_one(ws, who, b, X + (size_t)a * ldx, &values[a], grads ? grads + (size_t)a * ldg : nullptr);
+          if (rc == FLGP_ERR_NOCONV) { fail(a, flgp_last_error()); return FLGP_OK; }
+          return rc;
+        });
+    if (bad.item >= 0) return report(bad.item, bad.message, bad.status);
+  } else {
+    for (int p0 = 0; p0 < A; p0 += h.chunk) {
+      const int S = std::min(h.chunk, A - p0);
+      int *hpair = (int *)(h.h_in.p + h.off_pair);
+      for (int s = 0; s < S; ++s) {
+        const int a = p0 + s, b = prob ? prob[a] : a;
+        const double *x = X + (size_t)a * ldx;
+        std::memcpy(h.h_in.p + (size_t)s * h.C.sxn, x, sizeof(double) * (size_t)nx);
+        const double c = h.different ? 1.0 : x[1] + h.sigma;
+        h.h_in.p[h.off_c + s] = c;
+        h.h_in.p[h.off_ci + s] = h.different ? 1.0 : 1.0 / c;
+        hpair[s] = h.pair_of[(size_t)b];
+      }
+      FLGP_TRY(h.woodbury_chunk(S, grads != nullptr));
+      const int *flags = (const int *)(h.h_out.p + (size_t)S * (1 + nx));
+      for (int s = 0; s < S; ++s) {                     // the flag is judged before the numbers
+        const int a = p0 + s;
+        const double *o = h.h_out.p + (size_t)s * (1 + nx);
+        if (flags[s]) { fail(a, not_positive_definite(who)); continue; }
+        if (!all_finite(o, cnt)) { fail(a, not_finite(who)); continue; }
+        values[a] = o[0];
+        if (grads) std::memcpy(grads + (size_t)a * ldg, o + 1, sizeof(double) * (size_t)nx);
+      }
+    }
+  }
+  if (status) { std::memcpy(status, stat.data(), sizeof(int) * (size_t)A); return FLGP_OK; }
+  for (int a = 0; a < A; ++a)
+    if (stat[(size_t)a] != FLGP_OK) return report(a, why[(size_t)a], stat[(size_t)a]);
+  return FLGP_OK;
+}
 }  // namespace
+
+// negative_marginal_likelihood{,_diff_noise}_regression_cpp (src/train.cpp:351-436, 459-555) and their posterior forms
+// (:333-348, 438-457): the context of one problem.  The m x m matrices of the direct branch (C^-1, U, G) are replaced by L^-1
+// (gpr_grad.hip); the Woodbury branch forms alpha (m x q) as the reference does.
+extern "C" int flgp_eigenpair_regression_objective(const flgp_eigenpair *ep, int K, const int *idx, int m, const double *Y, int q,
+                                                   double sigma, const char *noise, const char *approach, const double *prior,
+                                                   const double *x, int nx, double *value, double *grad) {
+  const char *who = "regression_objective";
+  bool different = false, posterior = false;
+  FLGP_TRY(rg_strings(who, noise, approach, &different, &posterior));
+  FLGP_REQUIRE(ep && idx && Y && x && value, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K && m >= 1 && q >= 1, "%s: bad shape (K=%d of %d, m=%d, q=%d)", who, K, ep->K, m, q);
+  FLGP_REQUIRE(nx == (different ? m + 1 : 2), "%s: noise \"%s\" takes %d parameters, not %d", who, noise, different ? m + 1 : 2, nx);
+  FLGP_TRY(rg_check_x("", who, x, nx, sigma, posterior));
+  for (int a = 0; a < m; ++a) FLGP_REQUIRE(idx[a] >= 0 && idx[a] < ep->n, "%s: idx[%d]=%d out of range", who, a, idx[a]);
+  flgp_regression_batch h;
+  FLGP_TRY(rg_build(h, &ep, 1, K, idx, m, Y, q, sigma, different, posterior, prior, 1, false));
+  return rg_eval(h, who, false, nullptr, 1, x, nx, value, grad, nx, nullptr);
+}
 
 extern "C" int flgp_regression_batch_create(const flgp_eigenpair *const *eps, int B, int K, const int *idx, int m,
                                             const double *Y, int q, double sigma, const char *noise, const char *approach,
                                             const double *prior, int max_parallel, flgp_regression_batch **out) {
   const char *who = "regression_objective_batch";
   bool different = false, posterior = false;
-  FLGP_TRY(rgb_strings(who, noise, approach, &different, &posterior));
+  FLGP_TRY(rg_strings(who, noise, approach, &different, &posterior));
   FLGP_REQUIRE(eps && idx && Y && out, "%s: null pointer", who);
   *out = nullptr;
   FLGP_REQUIRE(B >= 1, "%s: B=%d problems", who, B);
@@ -2394,68 +2483,9 @@ extern "C" int flgp_regression_batch_create(const flgp_eigenpair *const *eps, in
   FLGP_HIP(hipGetDevice(&dev));
   FLGP_REQUIRE(dev == eps[0]->device, "%s: the pairs live on device %d, the current device is %d", who, eps[0]->device, dev);
   std::unique_ptr<flgp_regression_batch> H(new flgp_regression_batch);
-  flgp_regression_batch &h = *H;
-  h.B = B; h.K = K; h.m = m; h.q = q; h.nx = different ? m + 1 : 2; h.max_parallel = max_parallel;
-  h.different = different; h.posterior = posterior; h.direct = m <= K; h.sigma = sigma;
-  h.device = eps[0]->device;
-  const double dflt[5] = {1.0, 10.0, 2.0, 0.1, 1e-3};         // PostOFDataReg (src/train.h:153-155)
-  for (int a = 0; a < 5; ++a) h.prior[a] = prior ? prior[a] : dflt[a];
-  h.pair_of.resize((size_t)B);
-  for (int b = 0; b < B; ++b) {
-    size_t p = 0;
-    while (p < h.pairs.size() && h.pairs[p] != eps[b]) ++p;
-    if (p == h.pairs.size()) h.pairs.push_back(eps[b]);
-    h.pair_of[(size_t)b] = (int)p;
-  }
-  h.P = (int)h.pairs.size();
-  h.idx.assign(idx, idx + m);
-  h.range = is_range(idx, m);
-  FLGP_TRY(h.st.create());
-  hipStream_t st = h.st.s;
-  FLGP_TRY(upload(h.dY, Y, sizeof(double) * (size_t)m * q, st));
-  FLGP_TRY(upload(h.didx, idx, sizeof(int) * (size_t)m, st));
-  const long sx = pad32((long)m * K), sk = pad32(K), sq = pad32((long)K * K), skq = pad32((long)K * q);
-  h.C.sx = sx;
-  // the pairs' rows: every pair's for the Woodbury route (one buffer under the slots' strides), for the direct route only
-  // where the rows are no range (a range is read in place, as Rows::gather reads it)
-  if (!h.direct || !h.range) {
-    FLGP_TRY(h.V.alloc(sizeof(double) * (size_t)h.P * sx));
-    for (int p = 0; p < h.P; ++p)
-      FLGP_TRY(flgp_dev_gather_rows(st, (const double *)h.pairs[(size_t)p]->vectors.p, h.pairs[(size_t)p]->n, h.didx.as<int>(), m,
-                                    K, h.V.as<double>() + (size_t)p * sx));
-  }
-  if (h.direct) {
-    h.chunk = plan_workers(max_parallel, B, 0.0, 0.0);
-    FLGP_HIP(hipStreamSynchronize(st));
-    *out = H.release();
-    return FLGP_OK;
-  }
-  FLGP_TRY(h.vals.alloc(sizeof(double) * (size_t)h.P * sk));
-  for (int p = 0; p < h.P; ++p)
-    FLGP_HIP(hipMemcpyAsync(h.vals.as<double>() + (size_t)p * sk, h.pairs[(size_t)p]->values.p, sizeof(double) * (size_t)K,
-                            hipMemcpyDeviceToDevice, st));
-  if (!different) {
-    // M0 = V^T V and R0 = V^T Y per pair: the single entry's two products, on its workspace
-    const size_t we = vt_work_elems(K, q);
-    DevBuf work;
-    FLGP_TRY(work.alloc(sizeof(double) * we));
-    FLGP_TRY(h.M0.alloc(sizeof(double) * (size_t)h.P * sq)); FLGP_TRY(h.R0.alloc(sizeof(double) * (size_t)h.P * skq));
-    for (int p = 0; p < h.P; ++p) {
-      const double *Vp = h.V.as<double>() + (size_t)p * sx;
-      FLGP_TRY(gemm_tn(st, K, K, m, Vp, m, Vp, m, h.M0.as<double>() + (size_t)p * sq, work.as<double>(), we));
-      FLGP_TRY(gemm_tn(st, K, q, m, Vp, m, h.dY.as<double>(), m, h.R0.as<double>() + (size_t)p * skq, work.as<double>(), we));
-    }
-    FLGP_HIP(hipStreamSynchronize(st));
-  }
-  // the chunk: max_parallel problems, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of the
-  // free memory
-  const int want = max_parallel > 0 ? max_parallel : B;
-  size_t free_b = 0, total_b = 0;
-  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-  h.chunk = std::min(plan_workers(want, B, (double)free_b, flgp_regression_batch::slot_bytes(m, K, q, h.nx, different)),
-                     GEMM_BATCH_MAX);
-  FLGP_TRY(h.alloc_chunk());
-  FLGP_HIP(hipStreamSynchronize(st));
+  FLGP_TRY(rg_build(*H, eps, B, K, idx, m, Y, q, sigma, different, posterior, prior, max_parallel, true));
+  FLGP_HIP(hipStreamSynchronize(H->st.s));                // the caller's idx and Y have gone up
+  H->work0.release();
   *out = H.release();
   return FLGP_OK;
 }
@@ -2478,7 +2508,7 @@ extern "C" int flgp_regression_batch_eval(flgp_regression_batch *hp, const int *
   const char *who = "regression_objective_batch";
   FLGP_REQUIRE(hp && X && values, "%s: null pointer", who);
   flgp_regression_batch &h = *hp;
-  const int nx = h.nx, m = h.m;
+  const int nx = h.nx;
   FLGP_REQUIRE(A >= 1, "%s: A=%d problems", who, A);
   FLGP_REQUIRE(prob || A == h.B, "%s: prob may be NULL only if A == B (A=%d, B=%d)", who, A, h.B);
   FLGP_REQUIRE(ldx >= nx, "%s: noise \"%s\" takes %d parameters, not %d", who, h.different ? "different" : "same", nx, ldx);
@@ -2486,69 +2516,14 @@ extern "C" int flgp_regression_batch_eval(flgp_regression_batch *hp, const int *
                ldg);
   for (int a = 0; a < A; ++a) {
     const int b = prob ? prob[a] : a;
-    FLGP_REQUIRE(b >= 0 && b < h.B, "position %d: %s: prob=%d is outside [0, B=%d)", a, who, b, h.B);
-    const double *x = X + (size_t)a * ldx;
-    FLGP_REQUIRE(all_finite(x, nx), "position %d: %s: x must be finite", a, who);
-    for (int i = 1; i < nx; ++i) FLGP_REQUIRE(x[i] + h.sigma > 0.0, "position %d: %s: x[%d] + sigma must be positive", a, who, i);
-    FLGP_REQUIRE(!h.posterior || x[0] > 0.0, "position %d: %s: t = x[0] must be positive under \"posterior\"", a, who);
+    char at[32];
+    std::snprintf(at, sizeof at, "position %d: ", a);
+    FLGP_REQUIRE(b >= 0 && b < h.B, "%s%s: prob=%d is outside [0, B=%d)", at, who, b, h.B);
+    FLGP_TRY(rg_check_x(at, who, X + (size_t)a * ldx, nx, h.sigma, h.posterior));
   }
   int dev = 0;
   FLGP_HIP(hipGetDevice(&dev));
   FLGP_REQUIRE(dev == h.device, "%s: the pairs live on device %d, the current device is %d", who, h.device, dev);
-  std::vector<int> stat((size_t)A, FLGP_OK);
-  std::vector<std::string> why((size_t)A);
-  const int cnt = grads ? nx + 1 : 1;
-  auto fail = [&](int a, const char *text) {
-    stat[(size_t)a] = FLGP_ERR_NOCONV;
-    why[(size_t)a] = text;
-    values[a] = std::nan("");
-    if (grads) std::fill(grads + (size_t)a * ldg, grads + (size_t)a * ldg + nx, std::nan(""));
-  };
-  if (h.direct) {
-    // the problems dealt to the pool's workers (worker_pool.h), each on the single entry's own steps; one worker runs on
-    // the context's stream
-    DevicePool pool;
-    FLGP_TRY(pool.plan(h.max_parallel, A, 8.0 * (4.0 * m * m + 96.0 * m + (double)m * h.K + 2.0 * m * h.q) +
-                                              (double)flgp_dev_hk_workspace(m, m, h.K, 1)));
-    const PoolFailure bad = pool.run<NoState>(
-        h.st.s, A, [](NoState &) { return FLGP_OK; },
-        [&](hipStream_t ws, NoState &, int a) -> int {
-          const int b = prob ? prob[a] : a;
-          const int rc = h.direct_one(ws, who, b, X + (size_t)a * ldx, &values[a], grads ? grads + (size_t)a * ldg : nullptr);
-          if (rc == FLGP_ERR_NOCONV) { fail(a, flgp_last_error()); return FLGP_OK; }
-          return rc;
-        });
-    if (bad.item >= 0) { set_error("position %d: %s", bad.item, bad.message.c_str()); return bad.status; }
-  } else {
-    // RgEval::finish's two verdicts, under this entry's name
-    const std::string not_pd = std::string(who) + ": the system matrix is not positive definite (Cholesky pivot <= 0)";
-    const std::string not_finite = std::string(who) + ": the objective is not finite (the system matrix is numerically singular)";
-    for (int p0 = 0; p0 < A; p0 += h.chunk) {
-      const int S = std::min(h.chunk, A - p0);
-      int *hpair = (int *)(h.h_in + h.off_pair);
-      for (int s = 0; s < S; ++s) {
-        const int a = p0 + s, b = prob ? prob[a] : a;
-        const double *x = X + (size_t)a * ldx;
-        std::memcpy(h.h_in + (size_t)s * h.C.sxn, x, sizeof(double) * (size_t)nx);
-        const double c = h.different ? 1.0 : x[1] + h.sigma;
-        h.h_in[h.off_c + s] = c;
-        h.h_in[h.off_ci + s] = h.different ? 1.0 : 1.0 / c;
-        hpair[s] = h.pair_of[(size_t)b];
-      }
-      FLGP_TRY(h.woodbury_chunk(S, grads != nullptr));
-      const int *flags = (const int *)(h.h_out + (size_t)S * (1 + nx));
-      for (int s = 0; s < S; ++s) {
-        const int a = p0 + s;
-        const double *o = h.h_out + (size_t)s * (1 + nx);
-        if (flags[s]) { fail(a, not_pd.c_str()); continue; }
-        if (!all_finite(o, cnt)) { fail(a, not_finite.c_str()); continue; }
-        values[a] = o[0];
-        if (grads) std::memcpy(grads + (size_t)a * ldg, o + 1, sizeof(double) * (size_t)nx);
-      }
-    }
-  }
-  if (status) { std::memcpy(status, stat.data(), sizeof(int) * (size_t)A); return FLGP_OK; }
-  for (int a = 0; a < A; ++a)
-    if (stat[(size_t)a] != FLGP_OK) { set_error("position %d: %s", a, why[(size_t)a].c_str()); return stat[(size_t)a]; }
-  return FLGP_OK;
+  return rg_eval(h, who, true, prob, A, X, ldx, values, grads, ldg, status);
 }
+

@@ -80,20 +80,6 @@ int rg_colsumsq(hipStream_t st, const double *dX, long ldx, int rows, int cols, 
   return check_launch("rg_colsumsq_kernel");
 }
 
-// out[i] = sum_k X(i, k)^2, k ascending, a thread per row (X rows x cols, leading dimension ldx)
-__global__ void rg_rowsumsq_kernel(const double *__restrict__ X, long ldx, int rows, int cols, double *__restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows) return;
-  double s = 0.0;
-  for (int k = 0; k < cols; ++k) { const double v = X[(size_t)k * ldx + i]; s += v * v; }
-  out[i] = s;
-}
-
-int rg_rowsumsq(hipStream_t st, const double *dX, long ldx, int rows, int cols, double *d_out) {
-  hipLaunchKernelGGL(rg_rowsumsq_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, st, dX, ldx, rows, cols, d_out);
-  return check_launch("rg_rowsumsq_kernel");
-}
-
 __device__ __forceinline__ double rg_block_sum(double v, double *red) {
   const int tid = threadIdx.x;
   red[tid] = v;
@@ -247,7 +233,7 @@ int rg_assemble(hipStream_t st, const RgTerms &T) {
 }
 
 // ---- the same for a chunk of problems (RgbChunk, common.h) ---------------------------------------------
-// rg_rowsumsq_kernel on the slot's X
+// out[i] = sum_k X(i, k)^2 on the slot's X (rows x cols, leading dimension ldx), k ascending, a thread per row
 __global__ void rgb_rowsumsq_kernel(const double *__restrict__ X, long sx, long ldx, int rows, int cols, double *__restrict__ out,
                                     long so) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -10,7 +10,12 @@ with, per shape and noise model:
 and, at m = 1000, the triangular inverse alone (its flgp_prof time inside the direct evaluation) against chol_trsv with m
 right-hand sides on the identity (flgp_dev_chol_solve, mode 1), the route the inverse replaces.
 
+--single: the single entry alone, wall clock, at the rows of single_rows(); --compare PARENT_LIB: that under the parent
+commit's library and this tree's in alternating fresh processes, with the gate of compare()
+(profiles/regression_objective_single_timing.json).
+
 Usage: python scripts/time_regression_objective.py [--reps 5]
+       python scripts/time_regression_objective.py --compare /path/to/parent/libflgp_hip.so --out profiles/regression_objective_single_timing.json
 """
 import argparse
 import ctypes
@@ -141,11 +146,88 @@ def inverse_vs_trsv(m, reps, tri_ms):
     return dict(m=m, tri_inverse_ms=tri_ms, trsv_m_rhs_ms=min(times), trsv_m_rhs_median_ms=float(np.median(times)))
 
 
+def single_rows(reps):
+    """--single: the single entry alone at n = 1e6, K = 200, q = 1 (wall clock around the Python call, best of `reps` after a
+    warm-up), and one eval of a B = 10 context at m = 1000 "same".  {row: ms}"""
+    n, K, sigma = 1_000_000, 200, 1e-5
+    rng = np.random.default_rng(0)
+    V = np.asfortranarray(rng.standard_normal((n, K)))
+    pairs = []
+    for _ in range(10):     # ten pairs on the same vectors, values of their own
+        pairs.append(api.ResidentEigenPair.from_host(api.EigenPair(np.sort(rng.uniform(0.4, 1.0, K))[::-1].copy(), V)))
+    del V
+    rp = pairs[0]
+    out = {}
+
+    def row(name, m, noise, grad, kind="scattered"):
+        idx = np.arange(5000, 5000 + m) if kind == "range" else rng.choice(n, m, replace=False)
+        Y = rng.standard_normal((m, 1))
+        x = np.r_[3.0, 0.2] if noise == "same" else np.r_[3.0, rng.uniform(0.05, 0.4, m)]
+        f = lambda: rp.regression_objective(x, K, idx, Y, sigma=sigma, noise=noise, grad=grad)  # noqa: E731
+        f()
+        out[name] = best(f, reps)[0] * 1e3
+
+    for m in (1000, 10_000):
+        for noise in ("same", "different"):
+            row(f"woodbury m={m} {noise} grad", m, noise, True)
+    row("woodbury m=1000 same value", 1000, "same", False)
+    row("woodbury m=100000 same grad range", 100_000, "same", True, kind="range")
+    for noise in ("same", "different"):
+        row(f"direct m=200 {noise} grad", 200, noise, True)
+    row("direct m=200 same value", 200, "same", False)
+    idx = rng.choice(n, 1000, replace=False)
+    Y = rng.standard_normal((1000, 1))
+    X = np.array([np.r_[rng.uniform(1.0, 6.0), rng.uniform(0.05, 0.4)] for _ in range(10)])
+    ctx = api.RegressionObjectiveBatch(pairs, K, idx, Y, sigma=sigma, noise="same")
+    ctx(X)
+    out["batch B=10 m=1000 same grad"] = best(lambda: ctx(X), reps)[0] * 1e3
+    ctx.free()
+    for p in pairs:
+        p.free()
+    return out
+
+
+def compare(parent_lib, rounds, reps, out_path):
+    """--compare: --single under the library of the parent commit and under this tree's, alternating, each round a fresh
+    process with its own time limit.  Gate per row: head's best <= parent's best + parent's spread (max - min of its rounds)."""
+    import subprocess
+    runs = {"parent": [], "head": []}
+    for _ in range(rounds):
+        for who, lib in (("parent", parent_lib), ("head", None)):
+            cmd = [sys.executable, os.path.abspath(__file__), "--single", "--reps", str(reps)] + (["--lib", lib] if lib else [])
+            res = subprocess.run(cmd, capture_output=True, text=True, timeout=400, check=True)
+            runs[who].append(json.loads(res.stdout.strip().splitlines()[-1]))
+            print(who, runs[who][-1], file=sys.stderr, flush=True)
+    rows = []
+    for name in runs["parent"][0]:
+        p = [r[name] for r in runs["parent"]]; h = [r[name] for r in runs["head"]]
+        rows.append(dict(row=name, parent_rounds_ms=p, head_rounds_ms=h, parent_best_ms=min(p), parent_spread_ms=max(p) - min(p),
+                         head_best_ms=min(h), within_gate=bool(min(h) <= min(p) + (max(p) - min(p)))))
+    res = {"shape": dict(n=1_000_000, K=200, q=1), "rounds": rounds, "reps": reps, "rows": rows}
+    if out_path:
+        with open(out_path, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--single", action="store_true", help="time the single entry alone (see single_rows)")
+    ap.add_argument("--lib", default=None, help="with --single: another build of libflgp_hip.so")
+    ap.add_argument("--compare", default=None, metavar="PARENT_LIB", help="--single under PARENT_LIB and this tree's library")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.compare:
+        return compare(args.compare, args.rounds, args.reps, args.out)
+    if args.lib:
+        _lib.LIB_PATH = os.path.abspath(args.lib)
     torch.cuda.init()       # torch's HIP runtime opens the device before libflgp_hip.so does
+    if args.single:
+        print(json.dumps(single_rows(args.reps)))
+        return
     res = {"reps": args.reps}
     res["woodbury"] = shape_case(1_000_000, 200, 1000, args.reps, 0)
     res["direct"] = shape_case(100_000, 2000, 1000, args.reps, 1)

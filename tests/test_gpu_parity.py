@@ -860,7 +860,7 @@ def test_hk_panel_kernel_bit_identical_to_gemm(oracle, n0, n1, K, gather):
     assert np.abs(Hp - Ho).max() <= H_RTOL * np.abs(Ho).max()
 
 
-@pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if "known" not in p and "logit_objective" not in p))
+@pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if "known" not in p and not p.endswith("_bits.npz")))
 def test_golden_fixtures_through_the_abi(path):
     g = np.load(path)
     X, U = g["X"], g["U"]

@@ -1,7 +1,10 @@
 """GPU: the regression training objective for B (pair, x) problems in one call (flgp_regression_batch_*).
 The contract is bit for bit: every value and gradient of a batch is what the single entry
-(flgp_eigenpair_regression_objective, untouched and therefore the independent reference) returns for that pair at that x,
-whatever shares the call.  No tolerance appears in the bit tests; one test ties the batch to the numpy restatement."""
+(flgp_eigenpair_regression_objective) returns for that pair at that x, whatever shares the call.  The single entry is now
+the batch of one, so these tests compare a problem in company with the same problem alone; the independent reference is
+the pinned fixture tests/golden/regression_objective_bits.npz, which test_gpu_regression_objective_bits.py holds both
+entries to on this file's shapes.  No tolerance appears in the bit tests; one test ties the batch to the numpy
+restatement."""
 import os
 import sys
 
@@ -179,7 +182,7 @@ def test_company_and_order_do_not_change_the_bits(pairs, noise):
 @pytest.mark.parametrize("noise", ["same", "different"])
 @pytest.mark.parametrize("K,m", [(50, 40), (200, 200), (65, 1)], ids=["K50-m40", "K200-m200", "K65-m1"])
 def test_direct_route(pairs, K, m, noise, max_parallel):
-    """m <= K: the problems are dealt to the pool's workers, each on the single entry's own steps"""
+    """m <= K: the problems are dealt to the pool's workers; the single entry is one such item on one worker"""
     for kind, approach, grad in (("scattered", "posterior", True), ("range", "marginal", True), ("scattered", "marginal", False)):
         P = Problems(pairs, 7, K, m, 3, noise, approach, grad, seed=K + m, kind=kind, max_parallel=max_parallel)
         try:

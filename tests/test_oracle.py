@@ -181,7 +181,7 @@ def test_hk_c_vs_numpy(oracle):
     np.testing.assert_allclose(H, oracle.np_hk(vals, vec, K, 1.7, idx0, idx1), rtol=1e-13, atol=1e-14)
 
 
-@pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if "logit_objective" not in p))
+@pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if not p.endswith("_bits.npz")))
 def test_golden_fixtures(oracle, path):
     if os.path.basename(path) == "known_answers.npz":
         pytest.skip("covered by test_v_to_z_known_answers")

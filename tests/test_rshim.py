@@ -156,7 +156,7 @@ def _kmeans_callback(rmock, U, d):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if "known" not in p and "logit_objective" not in p))
+@pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if "known" not in p and not p.endswith("_bits.npz")))
 def test_golden_fixtures_through_the_call_shim(rmock, path):
     """.Call("_FLGP_KNN_cpp", ..., output = TRUE), _FLGP_LAE_cpp, _FLGP_cross_similarity_lae_cpp and
     _FLGP_heat_kernel_covariance_cpp on the golden fixtures: indices and dgRMatrix slots exact, H within 1e-8, the PROTECT
