@@ -478,10 +478,10 @@ class ResidentEigenPair:
         (flgp_eigenpair_logit_posterior_multiclass, include/flgp_hip.h): ``Y`` holds class labels 0 .. J-1 with
         J = ``len(ts)``, class j is ``logit_posterior`` on ``Y == j`` at ``ts[j]`` with ``sigma22 = sigma`` (``sigma11``
         defaults to the reference's 0), bit for bit.  The rows, the labels and V1 go up once and, for m > K, one fused
-        kernel reads the rows idx1 once for all classes.  ``max_parallel``: host threads (a stream each) the J Newton
-        loops are dealt to for m > K; the default 4 is the number of hardware queues a process opens by default, so more
-        workers share queues.  A class without a member is allowed.  Returns {"mean", "cov"}, m_new x J Fortran-ordered.
-        With ``target`` (m_new class labels naming all J classes) the result is scored on the device as
+        kernel per chunk reads the rows idx1 once for all its classes.  ``max_parallel``: for m > K the number of classes
+        per chunk, whose Newton loops advance in the same launches on one stream (below 1: one class per chunk; never
+        more than J or than fit the device memory); results do not depend on it.  A class without a member is allowed.
+        Returns {"mean", "cov"}, m_new x J Fortran-ordered.  With ``target`` (m_new class labels naming all J classes) the result is scored on the device as
         ``negative_log_likelihood(mean, cov, target, "multinomial", n_samples, seed)`` and "nll" is added;
         ``return_posterior=False`` then brings down that one number only.  ``return_iters``: also the J iteration counts."""
         idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
@@ -524,9 +524,9 @@ class ResidentEigenPair:
         iteration count) is, bit for bit, ``logit_posterior`` on that column at that t, whatever else shares the call.  For
         m > K the B weight-space Newton loops advance in the same launches, ``max_parallel`` problems per chunk (0: as many
         as fit the device memory), and one fused kernel per chunk reads the rows idx1 once for all its problems; m <= K runs
-        the dense route per problem.  The one-vs-rest posterior is this call on the m x J indicator matrix with
-        ``sigma11 = 0``.  A bad ``col[b]`` or ``ts[b]`` is refused here, before the library is called, with the library's
-        own text.  Returns {"mean", "cov"}, m_new x B Fortran-ordered, or ``({"mean", "cov"}, iters)``."""
+        the dense route per problem.  ``logit_posterior`` is this call with B = 1 and the one-vs-rest posterior is this
+        call on the m x J indicator matrix: one body in the library.  A bad ``col[b]`` or ``ts[b]`` is refused here, before
+        the library is called, with the library's own text.  Returns {"mean", "cov"}, m_new x B Fortran-ordered, or ``({"mean", "cov"}, iters)``."""
         who = "logit_posterior_batch"
         idx0 = np.ascontiguousarray(idx0, dtype=np.int32); idx1 = np.ascontiguousarray(idx1, dtype=np.int32)
         m = idx0.size

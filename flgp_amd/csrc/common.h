@@ -289,12 +289,6 @@ struct GpcNewton {
   int amll(hipStream_t st, const double *dY, const double *dN, double *out);   // synchronises
   static int pivot_error(int bad, const char *who, int iter);   // iter 0: the factorisation at the final f
 };
-// The elementwise steps of the weight-space Newton loop (m > K, C = V1 L V1^T + sigma I; GpcWeightSpace, eigenpair.hip).
-// gpc_weights: sW and b from f (gpc_w_kernel); gpc_step: diff = |f - f_new|_1 in a fixed order, f <- f_new;
-// gpc_lr_dvec: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh.
-int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b);
-int gpc_step(hipStream_t st, double *d_f, const double *d_fnew, int m, double *d_diff);
-int gpc_lr_dvec(hipStream_t st, const double *d_sW, double sigma, int m, double *d_D, double *d_dh, double *d_xs);
 // The low-rank Newton loop of the logit training objective (m > K) for a chunk of independent problems in the same
 // launches (gpc.hip, the loop itself in eigenpair.hip: LrBatch).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
 // of A slot numbers (the problems still iterating) and carry its index in the grid, so a step is one launch whatever A is
@@ -333,25 +327,17 @@ int lrb_trsv(hipStream_t st, const LrChunk &c, const int *act, int A);
 // lrb_trsv's q-column form: the q columns of R (K x q per slot at stride sr) <- Q^-1 (.), a workgroup per column
 int lrb_trsv_cols(hipStream_t st, const LrChunk &c, const int *act, int A, double *R, long sr, int q);
 int lrb_amll(hipStream_t st, const LrChunk &c);
-// The weight-space Newton loop's elementwise steps and the predictive rows of the logit posterior for m > K (gpc.hip; the
-// loop is in eigenpair.hip).  gpc_ws_bd: out = b / D; gpc_ws_fnew: f_new = p + sigma (b - sW^2 p) / D.
-// gpc_predict_rows: mean_i = u^T v_i and cov_i = c + |G v_i|^2 for the mnew rows v_i = V(rows_i, 0:K) of the pair, read in
-// place (d_idx, or row0 + i when it is nullptr), G (K x K at ld K, lower triangular) and u (K) the caller's; d_Gf holds
-// gpc_predict_operand_elems(K) doubles.  One fused MFMA kernel, for K <= GPC_PREDICT_KMAX on a device whose LDS holds 16
-// rows (gpc_predict_rows_applicable); wider K takes gemm + gpc_rowsumsq_add (out[i] = c + |Z(i, :)|^2) in the caller.
-// The one-vs-rest posterior: gpc_class_indicator: out = (labels == j); gpc_predict_prep writes one operand
-// [G ; u^T] into d_Gf, gpc_predict_rows_multi multiplies J of them, stored back to back, against the rows staged once and
-// writes column j of d_mean / d_cov (ldo): the bits of gpc_predict_rows on operand j.
+// The predictive rows of the logit posterior for m > K (gpc.hip; the loop is in eigenpair.hip: WsBatch).
+// gpc_predict_rows_multi: mean_i = u^T v_i and cov_i = c + |G v_i|^2 for the mnew rows v_i = V(rows_i, 0:K) of the pair, read
+// in place (d_idx, or row0 + i when it is nullptr), against J operands [G ; u^T] (G K x K lower triangular, u K) stored
+// back to back in d_Gf, gpc_predict_operand_elems(K) doubles each as wsb_predict_prep writes them: the rows are staged once
+// and column j of d_mean / d_cov (ldo) depends on operand j alone.  One fused MFMA kernel, for K <= GPC_PREDICT_KMAX on a
+// device whose LDS holds 16 rows (gpc_predict_rows_applicable); wider K takes gemm + gpc_rowsumsq_add
+// (out[i] = c + |Z(i, :)|^2) in the caller.  gpc_class_indicator: out = (labels == j), a column of the one-vs-rest matrix.
 constexpr int GPC_PREDICT_KMAX = 1024;
-int gpc_ws_bd(hipStream_t st, const double *d_b, const double *d_D, int m, double *d_out);
-int gpc_ws_fnew(hipStream_t st, const double *d_b, const double *d_sW, const double *d_D, const double *d_p, double sigma, int m,
-                double *d_fnew);
 size_t gpc_predict_operand_elems(int K);
 bool gpc_predict_rows_applicable(int K);
-int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, const double *dG,
-                     const double *d_u, double c, double *d_Gf, double *d_mean, double *d_cov);
 int gpc_class_indicator(hipStream_t st, const double *d_labels, int m, int j, double *d_out);
-int gpc_predict_prep(hipStream_t st, int K, const double *dG, const double *d_u, double *d_Gf);
 int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int J,
                            const double *d_Gf, double c, double *d_mean, double *d_cov, long ldo);
 int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out);
@@ -359,7 +345,7 @@ int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int c
 // the loop in eigenpair.hip: WsBatch), on LrChunk's slots and lists, beside the lrb_* steps it shares.  On the listed
 // slots: wsb_w: sW and b from f and Y with N = 1 (gpc_w_kernel's form without N); wsb_bd: c = b / D; wsb_fnew:
 // f_new = g + sigma (b - sW^2 g) / D; wsb_scale_cols: M(i, j) *= ls(j) on the K x K matrix at Q's stride;
-// wsb_predict_prep: gpc_predict_prep on (dG at Q's stride, u) into operand s of d_Gf.  wsb_tri_inverse: tri_inverse of the
+// wsb_predict_prep: the operand [G ; u^T] of (dG at Q's stride, u) into operand s of d_Gf.  wsb_tri_inverse: tri_inverse of the
 // factor in Q for every slot 0 .. A-1 (`all` lists them), dX at Q's stride, dT 64 x K per slot at stride st_, the split
 // planes of a slot at part + slot sp (pe doubles each, at least wsb_tri_inverse_planes(K, we)); `we` is the workspace whose
 // plan an unbatched tri_inverse would take.

@@ -2,13 +2,13 @@
 // regression prediction, posterior variance and the training objectives with their gradients (kernels in
 // gpr.hip and gpr_grad.hip; the drivers' whole testing step in one call, in weight space for m > K: DESIGN 8 f-13); the
 // Laplace approximation of the logit GP, its posterior and its training objective (SURVEY
-// 8f-5, gpc.hip; the posterior's route for m > K: DESIGN 8 f-11; the J one-vs-rest posteriors in one call: f-12; B
-// posteriors on any response matrix in one call, their weight-space loops in shared launches: f-17; the
+// 8f-5, gpc.hip; the posterior's route for m > K, B problems in shared launches: DESIGN 8 f-11; the binary entry is its
+// batch of one, the J one-vs-rest posteriors its batch of J: f-12; any response matrix in one call: f-17; the
 // training objective for B problems in one call: f-15; the regression objective for B (pair, x) problems through a training
 // context: f-18);
 // Polya-Gamma Gibbs prediction (pg.hip; B chains in one call: DESIGN 8 f-16).  The algebra they share is written once:
-// woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the logit loop and
-// the Gibbs sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
+// woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the Gibbs
+// sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -518,7 +518,7 @@ struct RgDirect {
 // resident pair, for B problems (labels, t) in one call; the single entry is the batch of one ------------------------------
 namespace {
 // The low-rank pieces of C = V1 L V1^T + sigma I (V1 m x K at ld1, L = exp(-t (1 - values)), ls = L^1/2) that the
-// weight-space logit loop (GpcWeightSpace) and the Polya-Gamma sweep share.  With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with
+// Polya-Gamma sweep (PgChain) works on.  With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with
 // X = diag(xs) V1 L^1/2 (xs = D^-1/2 sW) and Q = I + X^T X (K x K):
 //   B^-1 y = D^-1 y - D^-1/2 X Q^-1 X^T D^-1/2 y,   det B = det D det Q.
 // The callers' elementwise kernels make xs and use the result; the sigma x term of C x is theirs too.
@@ -655,12 +655,15 @@ struct LrBatch {
 
 struct BatchFailure { int problem = -1, bad = 0, iter = 0; };
 
-// The chunk [p0, p0 + S) from f = 0: after every iteration the host reads the A norms and the A flags (12 A bytes), notes
-// the iteration count of every listed problem and takes the converged ones (norm < tol) and the failed ones (a pivot
-// flag) off the list: GpcNewton::run's protocol per problem.  The final sums follow for every slot.  amll_h / its: the S
-// results.
-int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
-                   int p0, double *amll_h, int *its, BatchFailure &fail) {
+// The host side of a chunk's Newton loops, the objective's (lr_batch_chunk) and the posterior's (ws_batch_chunk): the chunk
+// [p0, p0 + S) from f = 0, `iteration(A)` one Newton iteration of the A listed slots.  After every iteration the host reads
+// the A norms and the A flags (12 A bytes), notes the iteration count of every listed problem and takes the converged ones
+// (norm < tol) and the failed ones (a pivot flag) off the list: GpcNewton::run's protocol per problem; nothing writes a
+// slot that left.  fail: the lowest failing problem; its: the S counts.  d_all (or nullptr): a device list that gets
+// 0 .. S-1, for the steps that follow the loop on every slot.
+template <class Iteration>
+int batch_newton_loop(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+                      int p0, int *its, BatchFailure &fail, int *d_all, Iteration iteration) {
   LrChunk &C = L.C;
   C.slots = S;
   FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
@@ -668,12 +671,16 @@ int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const d
   FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
   std::vector<int> act((size_t)S), next;
   for (int s = 0; s < S; ++s) act[(size_t)s] = s;
+  if (d_all) {
+    FLGP_TRY(h2d(d_all, act.data(), sizeof(int) * (size_t)S, st));
+    FLGP_HIP(hipStreamSynchronize(st));          // `act` changes below: the copy has read it
+  }
   std::vector<double> stat((size_t)S * 2);       // 12 A bytes are read into it: A doubles, then A ints
   bool changed = true;
   for (int it = 0; it < max_iter && !act.empty(); ++it) {
     const int A = (int)act.size();
     if (changed) FLGP_TRY(h2d(L.act.p, act.data(), sizeof(int) * (size_t)A, st));
-    FLGP_TRY(L.iteration(st, A));
+    FLGP_TRY(iteration(A));
     FLGP_TRY(d2h(stat.data(), L.stat.p, (size_t)12 * A, st));
     FLGP_HIP(hipStreamSynchronize(st));
     const int *bad = (const int *)(stat.data() + A);
@@ -690,8 +697,15 @@ int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const d
     changed = next.size() != act.size();
     act.swap(next);
   }
-  FLGP_TRY(lrb_amll(st, C));
-  FLGP_TRY(d2h(amll_h, C.amll, sizeof(double) * (size_t)S, st));
+  return FLGP_OK;
+}
+
+// The objective's chunk: the loops, then the final sums for every slot.  amll_h / its: the S results.
+int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+                   int p0, double *amll_h, int *its, BatchFailure &fail) {
+  FLGP_TRY(batch_newton_loop(st, L, ep, d_ts, S, tol, max_iter, p0, its, fail, nullptr, [&](int A) { return L.iteration(st, A); }));
+  FLGP_TRY(lrb_amll(st, L.C));
+  FLGP_TRY(d2h(amll_h, L.C.amll, sizeof(double) * (size_t)S, st));
   FLGP_HIP(hipStreamSynchronize(st));
   return FLGP_OK;
 }
@@ -859,81 +873,16 @@ extern "C" int flgp_eigenpair_logit_objective_batch(const flgp_eigenpair *ep, in
 }
 
 
-// ---- logit posterior for m > K: the mode in weight space, the predictive rows in one pass ----------------
+// ---- logit posterior: the binary entry, the one-vs-rest entries and the batch entry on one body; for
+// m > K the mode in weight space for a chunk of problems in shared launches, the predictive rows in one pass ---------------
 namespace {
-// Alg. 3.1's step written as a = (I + W C)^-1 b on LowRankB's C, which gives Phi^T a = Q^-1 Phi^T D^-1 b exactly
-// (Phi = V1 L^1/2, D = 1 + sigma W, X = diag(sqrt(W / D)) Phi, Q = I + X^T X).  Per iteration from f = 0, N = 1:
-//   W, b from f; D, xs; Q factored;  beta = Q^-1 L^1/2 V1^T (b / D);  p = V1 L^1/2 beta;  f_new = p + sigma (b - W p) / D.
-// Unlike LrBatch's a = b - sW dh (g - X Q^-1 X^T g), whose difference of two nearly equal vectors costs the mean
-// m lambda / 4 in relative accuracy (harmless for amll, which is stationary at the mode), the one subtraction here is
-// multiplied by sigma.  solve() is also the final step at the mode: beta there gives mean_i = v2_i^T L^1/2 beta.
-struct GpcWeightSpace {
-  int m = 0;
-  LowRankB L;                  // the caller sets V1, ld1, l, ls, sigma
-  DevBuf f, fnew, sW, b, D, dh, xs, bd, p, beta, scal, flag;
-
-  int alloc(int m_, int K) {
-    m = m_;
-    const size_t v = sizeof(double) * (size_t)m;
-    FLGP_TRY(f.alloc(v)); FLGP_TRY(fnew.alloc(v)); FLGP_TRY(sW.alloc(v)); FLGP_TRY(b.alloc(v)); FLGP_TRY(D.alloc(v));
-    FLGP_TRY(dh.alloc(v)); FLGP_TRY(xs.alloc(v)); FLGP_TRY(bd.alloc(v)); FLGP_TRY(p.alloc(v));
-    FLGP_TRY(beta.alloc(sizeof(double) * (size_t)K));
-    FLGP_TRY(scal.alloc(sizeof(double) * 2)); FLGP_TRY(flag.alloc(sizeof(int)));
-    return L.alloc(m, K, true, flag.as<int>());
-  }
-  // W, b, D, X and L_Q at the current f, then beta = Q^-1 L^1/2 V1^T (b / D)
-  int solve(hipStream_t st, const double *dY) {
-    const int K = L.K;
-    FLGP_TRY(gpc_weights(st, f.as<double>(), dY, nullptr, m, sW.as<double>(), b.as<double>()));
-    FLGP_TRY(gpc_lr_dvec(st, sW.as<double>(), L.sigma, m, D.as<double>(), dh.as<double>(), xs.as<double>()));
-    FLGP_TRY(L.factor(st, xs.as<double>()));
-    FLGP_TRY(gpc_ws_bd(st, b.as<double>(), D.as<double>(), m, bd.as<double>()));
-    FLGP_TRY(gemm_tn(st, K, 1, m, L.V1, L.ld1, bd.as<double>(), m, beta.as<double>(), L.work.as<double>(), L.we));
-    FLGP_TRY(pg_mul(st, K, L.ls, beta.as<double>(), nullptr, beta.as<double>()));                             // r
-    return chol_trsv(st, L.Q.as<double>(), K, K, beta.as<double>(), K, 1, 3, flag.as<int>());
-  }
-  // L.u = L^1/2 beta
-  int scaled_beta(hipStream_t st) { return pg_mul(st, L.K, L.ls, beta.as<double>(), nullptr, L.u.as<double>()); }
-  int iteration(hipStream_t st, const double *dY) {
-    ProfScope ps("logit_ws_newton_iter", st, 0.0);
-    FLGP_TRY(solve(st, dY));
-    FLGP_TRY(scaled_beta(st));
-    FLGP_TRY(gemm_nn(st, m, 1, L.K, L.V1, L.ld1, L.u.as<double>(), L.K, p.as<double>(), nullptr, 0));
-    FLGP_TRY(gpc_ws_fnew(st, b.as<double>(), sW.as<double>(), D.as<double>(), p.as<double>(), L.sigma, m, fnew.as<double>()));
-    return gpc_step(st, f.as<double>(), fnew.as<double>(), m, scal.as<double>());
-  }
-  // the loop from f = 0 with GpcNewton::run's host protocol (12 bytes read back per iteration)
-  int run(hipStream_t st, const double *dY, double tol, int max_iter, const char *who, int *iters) {
-    FLGP_HIP(hipMemsetAsync(f.p, 0, sizeof(double) * (size_t)m, st));
-    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    *iters = 0;
-    for (int it = 0; it < max_iter; ++it) {
-      FLGP_TRY(iteration(st, dY));
-      double diff = 0.0;
-      int bad = 0;
-      FLGP_HIP(hipMemcpyAsync(&diff, scal.p, sizeof(double), hipMemcpyDeviceToHost, st));
-      FLGP_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-      FLGP_HIP(hipStreamSynchronize(st));
-      *iters = it + 1;
-      FLGP_TRY(GpcNewton::pivot_error(bad, who, it + 1));
-      if (diff < tol) break;
-    }
-    return FLGP_OK;
-  }
-};
-
 // mean_i = u^T v2_i, cov_i = sigma22 + |G v2_i|^2 for the rows r1 of the pair (G K x K lower triangular, u K; device
-// pointers, as dmean / dcov).  K <= GPC_PREDICT_KMAX: gpc_predict_rows, the rows read in place.  Wider K: Z = V2 G^T by the
+// pointers, as dmean / dcov) where K is too wide for the fused kernel (gpc_predict_rows_applicable): Z = V2 G^T by the
 // MFMA GEMM and its row sums of squares, in row blocks that keep Z (and the gathered rows of an index set) at 256 MB each.
-int predict_rows(hipStream_t st, const flgp_eigenpair *ep, int K, Rows &r1, const double *G, const double *u, double sigma22,
-                 double *dmean, double *dcov) {
+int predict_rows_wide(hipStream_t st, const flgp_eigenpair *ep, int K, Rows &r1, const double *G, const double *u, double sigma22,
+                      double *dmean, double *dcov) {
   FLGP_TRY(r1.resolve(st));
   const double *dvec = (const double *)ep->vectors.p;
-  if (gpc_predict_rows_applicable(K)) {
-    DevBuf Gf;
-    FLGP_TRY(Gf.alloc(sizeof(double) * gpc_predict_operand_elems(K)));
-    return gpc_predict_rows(st, dvec, ep->n, r1.d, r1.row0, r1.m, K, G, u, sigma22, Gf.as<double>(), dmean, dcov);
-  }
   ProfScope ps("gpc_predict_rows_wide", st, 2.0 * r1.m * K * (K + 1));
   const int rb = (int)std::min<size_t>((size_t)r1.m, std::max<size_t>(64, (((size_t)256 << 20) / (sizeof(double) * K)) / 64 * 64));
   DevBuf Z, Vb;
@@ -955,39 +904,188 @@ int predict_rows(hipStream_t st, const flgp_eigenpair *ep, int K, Rows &r1, cons
   return FLGP_OK;
 }
 
-// What the binary entry owns, and what one worker of the one-vs-rest route (m > K) reuses across its classes: the
-// weight-space loop's state, the label column and the scratch of the operand.  Everything in it is overwritten before it
-// is read, so a class's bits do not depend on which worker ran it or on what the worker ran before.
-struct McWorker {
-  GpcWeightSpace S;            // the caller sets L.V1, L.ld1, L.sigma and, per problem, L.l and L.ls
-  DevBuf dY, Li, Tb, wt;
-  size_t wi = 0;
-  int alloc(int m, int K) {
-    wi = (size_t)32 * 64 * K;
-    FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m));
-    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
-    FLGP_TRY(wt.alloc(sizeof(double) * wi));
-    return S.alloc(m, K);
+// The weight-space Newton loop of the posterior for a chunk of problems.  Alg. 3.1's step written as a = (I + W C)^-1 b on
+// C = V1 L V1^T + sigma I, which gives Phi^T a = Q^-1 Phi^T D^-1 b exactly (Phi = V1 L^1/2, D = 1 + sigma W,
+// X = diag(sqrt(W / D)) Phi, Q = I + X^T X).  Per iteration from f = 0, N = 1:
+//   W, b from f; D, xs; Q factored;  beta = Q^-1 L^1/2 V1^T (b / D);  p = V1 L^1/2 beta;  f_new = p + sigma (b - W p) / D.
+// Unlike LrBatch's a = b - sW dh (g - X Q^-1 X^T g), whose difference of two nearly equal vectors costs the mean
+// m lambda / 4 in relative accuracy (harmless for amll, which is stationary at the mode), the one subtraction here is
+// multiplied by sigma.  solve() is also the final step at the mode: beta there gives mean_i = v2_i^T L^1/2 beta.
+// It runs on LrBatch's slots, lists and planes: slot s of every buffer belongs to problem p0 + s for the whole chunk and
+// every step of an iteration is one launch over the device list of the slots still iterating, so a problem's bits depend
+// on nothing that shares its chunk.  Of the chunk's m-vectors c holds b / D and g holds p; u holds beta and then
+// L^1/2 beta (a and Xv are not used).  The products take LrBatch's plans.  Beside the loop's state a slot owns L_Q^-1 (Li),
+// the 64 x K block and the planes of the triangular inverse, and its predictive operand.
+struct WsBatch {
+  LrBatch L;
+  DevBuf Li, Tb, tpart, Gf, all;
+  size_t wi = 0, tpe = 0, ge = 0;
+  long stb = 0, stp = 0;
+
+  // device bytes of one problem: LrBatch's (X, Q, the m-vectors, u, l, ls, the loop's planes), L_Q^-1, the 64 x K block,
+  // the inverse's planes, the operand and two output columns
+  static double bytes(int m, int K, int mnew) {
+    const size_t wi = (size_t)32 * 64 * K;
+    return LrBatch::bytes(m, K) + 8.0 * ((double)pad32((long)K * K) + pad32((long)64 * K) +
+                                         pad32((long)wsb_tri_inverse_planes(K, wi)) + (double)gpc_predict_operand_elems(K) +
+                                         2.0 * mnew) + 4.0;
   }
-  // device bytes of one worker: X, Q, the GEMM workspaces and the operand's scratch; `wide`: predict_rows' two row blocks
-  static double bytes(int m, int K, bool wide) {
-    const double k = K;
-    return 8.0 * ((double)m * k + 2.0 * k * k + (double)vt_work_elems(K, 1) + 10.0 * m + (64.0 + 32.0 * 64.0) * k + 2.0 * k) +
-           (wide ? 2.0 * 256.0 * (1 << 20) : 0.0);
+  int alloc(int m, int K, int slots, bool fused) {
+    FLGP_TRY(L.alloc(m, K, slots));
+    wi = (size_t)32 * 64 * K;                                  // bounds the inverse's splits: its value fixes the bits
+    tpe = wsb_tri_inverse_planes(K, wi);
+    stb = pad32((long)64 * K); stp = pad32((long)tpe);
+    ge = gpc_predict_operand_elems(K);
+    const size_t S = (size_t)slots;
+    FLGP_TRY(Li.alloc(sizeof(double) * S * L.C.sq)); FLGP_TRY(Tb.alloc(sizeof(double) * S * stb));
+    FLGP_TRY(tpart.alloc(sizeof(double) * std::max<size_t>(S * stp, 1)));
+    if (fused) FLGP_TRY(Gf.alloc(sizeof(double) * S * ge));
+    return all.alloc(sizeof(int) * S);
   }
-  // The mode of the labels in dY, then the weights once more at the final f (as GpcNewton::weights in the dense route) and
-  // the operand Gp = [L_Q^-1 L^1/2 ; (L^1/2 beta)^T]: Li and S.L.u.  The caller reads S.flag when its stream has run.
-  int mode_and_operand(hipStream_t st, double tol, int max_iter, const char *who, int *iters) {
-    const int K = S.L.K;
-    FLGP_TRY(S.run(st, dY.as<double>(), tol, max_iter, who, iters));
-    FLGP_TRY(S.solve(st, dY.as<double>()));
-    FLGP_TRY(S.scaled_beta(st));
-    FLGP_TRY(tri_inverse(st, S.L.Q.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, S.flag.as<int>()));
-    return gpr_scale(st, Li.as<double>(), nullptr, S.L.ls, K, K, Li.as<double>());                            // L_Q^-1 L^1/2
+  // on the A listed slots: W, b, D, X and L_Q at the current f, then u = beta = Q^-1 L^1/2 V1^T (b / D)
+  int solve(hipStream_t st, const int *a, int A) {
+    LrChunk &C = L.C;
+    FLGP_TRY(wsb_w(st, C, a, A));                                                             // sW, b
+    FLGP_TRY(lrb_d(st, C, a, A));                                                             // D, dh, xs
+    FLGP_TRY(lrb_scale2(st, C, a, A));                                                        // X, then Q = I + X^T X = L_Q L_Q^T
+    {
+      const GemmBatch gb{A, a, C.sx, C.sx, C.sq, 0, L.sp};
+      FLGP_TRY(gemm_launch(st, C.K, C.K, C.m, 1.0, C.X, C.m, 1, C.X, 1, C.m, 0.0, nullptr, 0, 0, C.Q, 1, C.K, L.part.as<double>(),
+                           L.pe, 0.0, nullptr, nullptr, nullptr, L.planQ, nullptr, &gb));
+    }
+    FLGP_TRY(lrb_add_diag(st, C, a, A));
+    FLGP_TRY(lrb_chol(st, C, a, A));
+    FLGP_TRY(wsb_bd(st, C, a, A));                                                            // c = b / D
+    FLGP_TRY(tn(st, a, A, C.c, C.u));                                                         // V1^T (.)
+    FLGP_TRY(lrb_mul(st, C.K, C.ls, C.sk, C.u, C.sk, C.u, C.sk, a, A));                       // L^1/2 (.)
+    return lrb_trsv(st, C, a, A);                                                             // beta
+  }
+  // LrBatch::tn / nn against the shared V1 with the list given (the final step runs on every slot, not on the loop's list)
+  int tn(hipStream_t st, const int *a, int A, const double *x, double *out) {
+    LrChunk &C = L.C;
+    const GemmBatch gb{A, a, 0, C.sv, C.sk, 0, L.sp};
+    return gemm_launch(st, C.K, 1, C.m, 1.0, C.V1, C.ld1, 1, x, 1, C.m, 0.0, nullptr, 0, 0, out, 1, C.K, L.part.as<double>(), L.pe,
+                       0.0, nullptr, nullptr, nullptr, L.planU, nullptr, &gb);
+  }
+  int nn(hipStream_t st, const int *a, int A, const double *u, double *out) {
+    LrChunk &C = L.C;
+    const GemmBatch gb{A, a, 0, C.sk, C.sv, 0, 0};
+    return gemm_launch(st, C.m, 1, C.K, 1.0, C.V1, 1, C.ld1, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, C.m, nullptr, 0, 0.0, nullptr,
+                       nullptr, nullptr, 0, nullptr, &gb);
+  }
+  // u <- L^1/2 beta
+  int scaled_beta(hipStream_t st, const int *a, int A) {
+    LrChunk &C = L.C;
+    return lrb_mul(st, C.K, C.ls, C.sk, C.u, C.sk, C.u, C.sk, a, A);
+  }
+  // one Newton iteration of the A listed slots: every launch once, whatever A is
+  int iteration(hipStream_t st, int A) {
+    ProfScope ps("logit_ws_batch_iter", st, 0.0);
+    LrChunk &C = L.C;
+    const int *a = L.act.as<int>();
+    FLGP_TRY(solve(st, a, A));
+    FLGP_TRY(scaled_beta(st, a, A));
+    FLGP_TRY(nn(st, a, A, C.u, C.g));                                                         // p = V1 L^1/2 beta
+    FLGP_TRY(wsb_fnew(st, C, a, A));                                                          // f_new = p + sigma (b - W p) / D
+    return lrb_step(st, C, a, A, L.stat.as<double>());
+  }
+  // The final step for every slot 0 .. S-1: the weights once more at the final f (as GpcNewton::weights in the dense
+  // route), L_Q, beta,
+  // u = L^1/2 beta, Li = L_Q^-1 L^1/2, and (fused) the slot's operand [Li ; u^T]
+  int operands(hipStream_t st, int S) {
+    LrChunk &C = L.C;
+    const int *a = all.as<int>();
+    FLGP_TRY(solve(st, a, S));
+    FLGP_TRY(scaled_beta(st, a, S));
+    FLGP_TRY(wsb_tri_inverse(st, C, a, S, Li.as<double>(), Tb.as<double>(), stb, tpart.as<double>(), tpe, stp, wi));
+    FLGP_TRY(wsb_scale_cols(st, C, a, S, Li.as<double>()));
+    return Gf.p ? wsb_predict_prep(st, C, a, S, Li.as<double>(), Gf.as<double>()) : FLGP_OK;
   }
 };
+
+// The posterior's chunk [p0, p0 + S): the loops, then the final step for every slot and its pivot flags (iter 0: the
+// factorisation at the mode).  A chunk with a failure in the loop skips the final step, so fail is the lowest problem that
+// failed in the loop or, if none did, the lowest that failed at the mode.  its: the S counts.  r1, the rows the caller
+// predicts for next, are resolved while the device runs the final step: the scan of a long idx1 costs the host alone.
+int ws_batch_chunk(hipStream_t st, WsBatch &W, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+                   int p0, int *its, BatchFailure &fail, Rows &r1) {
+  FLGP_TRY(batch_newton_loop(st, W.L, ep, d_ts, S, tol, max_iter, p0, its, fail, W.all.as<int>(),
+                             [&](int A) { return W.iteration(st, A); }));
+  if (fail.problem >= 0) return FLGP_OK;
+  FLGP_TRY(W.operands(st, S));
+  FLGP_TRY(r1.resolve(st));
+  std::vector<int> flags((size_t)S, 0);
+  FLGP_TRY(d2h(flags.data(), W.L.C.flag, sizeof(int) * (size_t)S, st));
+  FLGP_HIP(hipStreamSynchronize(st));
+  for (int s = 0; s < S; ++s)
+    if (flags[(size_t)s]) { fail.problem = p0 + s; fail.bad = flags[(size_t)s]; fail.iter = 0; break; }
+  return FLGP_OK;
+}
+
+// The B checked problems on the checked rows r0 / r1, on the entry's stream: problem b is column cols[b] of dY (r0.m x ncol
+// on the device) at ts[b]; column b of dmean / dcov (r1.m x B on the device) and its[b] (host) are its results.
+// m <= K: the dense body per problem, one after another.  m > K: V1 gathered once, then chunks of max_parallel problems
+// (<= 0: all B; where that is more than one, no more than fit into 90 % of the free memory), each with one fused pass over
+// the rows r1 for all its operands (the wide route: per slot).
+// A problem that fails ends the call: fail.problem names it -- the first on the dense route, the lowest of the first
+// failing chunk otherwise (ws_batch_chunk) -- and fail.iter is 0 for the factorisation at the mode, which follows a loop
+// whose count is in its[], and otherwise the loop's iteration (-1 on the dense route: in its loop).  The status is returned
+// and the text is the failure's under the problem's name: `who`, or "<who>: class <b>" (by_class).
+int logit_posteriors(hipStream_t st, const char *who, bool by_class, const flgp_eigenpair *ep, int K, Rows &r0, Rows &r1,
+                     const double *dY, const int *cols, const double *ts, int B, double sigma11, double sigma22, double tol,
+                     int max_iter, int max_parallel, double *dmean, double *dcov, int *its, BatchFailure &fail) {
+  const int m = r0.m, mnew = r1.m;
+  const size_t colb = (size_t)mnew;
+  char name[64];
+  auto name_of = [&](int b) -> const char * {
+    if (!by_class) return who;
+    std::snprintf(name, sizeof(name), "%s: class %d", who, b);
+    return name;
+  };
+  if (m <= K) {
+    for (int b = 0; b < B; ++b) {
+      its[b] = 0;
+      const int rc = posterior_dense_on(st, name_of(b), ep, K, ts[b], sigma11, sigma22, r0, m, dY + (size_t)cols[b] * m, r1, mnew,
+                                        tol, max_iter, dmean + b * colb, dcov + b * colb, &its[b]);
+      if (rc != FLGP_OK) { fail.problem = b; fail.iter = its[b] > 0 ? 0 : -1; return rc; }
+    }
+    return FLGP_OK;
+  }
+  FLGP_TRY(r0.gather(st, ep, K));
+  DevBuf dcol, dts;
+  FLGP_TRY(upload(dcol, cols, sizeof(int) * (size_t)B, st));
+  FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st));
+  const bool fused = gpc_predict_rows_applicable(K);
+  const int want = max_parallel > 0 ? max_parallel : B;
+  size_t free_b = 0, total_b = 0;
+  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  const int chunk = std::min(plan_workers(want, B, (double)free_b, WsBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
+  WsBatch W;
+  FLGP_TRY(W.alloc(m, K, chunk, fused));
+  LrChunk &C = W.L.C;
+  C.Y = dY; C.ldy = m; C.N = nullptr;
+  C.V1 = r0.V; C.ld1 = r0.ld; C.sigma = sigma11;
+  for (int p0 = 0; p0 < B; p0 += chunk) {
+    const int S = std::min(chunk, B - p0);
+    C.ycol = dcol.as<int>() + p0;
+    FLGP_TRY(ws_batch_chunk(st, W, ep, dts.as<double>() + p0, S, tol, max_iter, p0, its + p0, fail, r1));
+    if (fail.problem >= 0) return GpcNewton::pivot_error(fail.bad, name_of(fail.problem), fail.iter);
+    double *cm = dmean + p0 * colb, *cc = dcov + p0 * colb;
+    if (fused) {
+      // one pass over the rows idx1 of the pair for the chunk's S operands
+      FLGP_TRY(gpc_predict_rows_multi(st, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, S, W.Gf.as<double>(),
+                                      sigma22, cm, cc, (long)mnew));
+    } else {
+      for (int s = 0; s < S; ++s)
+        FLGP_TRY(predict_rows_wide(st, ep, K, r1, W.Li.as<double>() + s * C.sq, C.u + s * C.sk, sigma22, cm + s * colb,
+                                   cc + s * colb));
+    }
+  }
+  return FLGP_OK;
+}
 }  // namespace
 
+// The binary entry is the batch of one: one problem, one chunk of one slot (m > K) or one run of the dense body.
 extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, double t, double sigma11, double sigma22,
                                               const int *idx0, int m, const double *Y, const int *idx1, int mnew, double tol,
                                               int max_iter, double *mean, double *cov, int *iters) {
@@ -996,32 +1094,28 @@ extern "C" int flgp_eigenpair_logit_posterior(const flgp_eigenpair *ep, int K, d
   FLGP_TRY(posterior_check(who, ep, K, idx0, m, Y, idx1, mnew, max_iter, mean, cov, r0, r1));
   FLGP_REQUIRE(std::isfinite(t), "%s: t=%g must be finite", who, t);
   FLGP_TRY(posterior_check_sigmas(who, sigma11, sigma22));
-  if (m <= K) return posterior_dense(who, ep, K, t, sigma11, sigma22, r0, m, Y, r1, mnew, tol, max_iter, mean, cov, iters);
 
   Stream st;
   FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = L^1/2, l = L
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  McWorker W;
-  GpcWeightSpace &S = W.S;
-  S.L.sigma = sigma11; S.L.V1 = r0.V; S.L.ld1 = r0.ld; S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
-  FLGP_TRY(W.alloc(m, K));
-  FLGP_TRY(h2d(W.dY.p, Y, sizeof(double) * (size_t)m, st.s));
+  const size_t nb = sizeof(double) * (size_t)mnew;
+  DevBuf dY, dmean, dcov;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(dmean.alloc(nb)); FLGP_TRY(dcov.alloc(nb));
+  const int col = 0;
   int it = 0;
-  FLGP_TRY(W.mode_and_operand(st.s, tol, max_iter, who, &it));
-  if (iters) *iters = it;
-  DevBuf dmean, dcov;
-  FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dcov.alloc(sizeof(double) * (size_t)mnew));
-  FLGP_TRY(predict_rows(st.s, ep, K, r1, W.Li.as<double>(), S.L.u.as<double>(), sigma22, dmean.as<double>(), dcov.as<double>()));
-  FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)mnew, st.s));
-  FLGP_TRY(d2h(cov, dcov.p, sizeof(double) * (size_t)mnew, st.s));
-  int bad = 0;
-  FLGP_TRY(read_flag(st.s, S.flag.p, &bad));
-  return GpcNewton::pivot_error(bad, who, 0);
+  BatchFailure fail;
+  const int rc = logit_posteriors(st.s, who, false, ep, K, r0, r1, dY.as<double>(), &col, &t, 1, sigma11, sigma22, tol, max_iter,
+                                  1, dmean.as<double>(), dcov.as<double>(), &it, fail);
+  // the count is the loop's: it is there before the factorisation at the mode is looked at
+  if (iters && (rc == FLGP_OK || (fail.problem == 0 && fail.iter == 0))) *iters = it;
+  if (rc != FLGP_OK) return rc;
+  FLGP_TRY(d2h(mean, dmean.p, nb, st.s));
+  FLGP_TRY(d2h(cov, dcov.p, nb, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
 }
 
-// ---- one-vs-rest logit posterior: J classes over one pass of the pair ------------------------------------
+// ---- one-vs-rest logit posterior: the batch of J on the indicator matrix ---------------------------------
 namespace {
 // The shared body of the two entries.  nll == nullptr: flgp_eigenpair_logit_posterior_multiclass (mean and cov wanted).
 int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma11, double sigma22, const int *idx0,
@@ -1041,72 +1135,23 @@ int posterior_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int 
     FLGP_REQUIRE((long)mnew <= (long)0x7FFFFFFF * 256 / J, "%s: bad shape (m_new=%d, J=%d)", who, mnew, J);
     FLGP_TRY(check_class_labels(who, "target", target, mnew, J, true));
   }
-  std::vector<int> its((size_t)J, 0);
-  char who_j[64];
-  auto name_class = [&](int j, char *buf) { std::snprintf(buf, sizeof(who_j), "%s: class %d", who, j); };
 
   Stream st;
   FLGP_TRY(st.create());
-  FLGP_TRY(r1.resolve(st.s));
   const size_t col = (size_t)mnew, nj = sizeof(double) * col * J;
-  DevBuf dlab, dmean, dcov;
+  DevBuf dlab, dY, dmean, dcov;
   FLGP_TRY(upload(dlab, Y, sizeof(double) * (size_t)m, st.s));
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * J));
   FLGP_TRY(dmean.alloc(nj)); FLGP_TRY(dcov.alloc(nj));
-  if (m <= K) {
-    // the dense body per class, one after another; column j = (Y == j) is formed on the device
-    DevBuf dYj;
-    FLGP_TRY(dYj.alloc(sizeof(double) * (size_t)m));
-    for (int j = 0; j < J; ++j) {
-      name_class(j, who_j);
-      FLGP_TRY(gpc_class_indicator(st.s, dlab.as<double>(), m, j, dYj.as<double>()));
-      FLGP_TRY(posterior_dense_on(st.s, who_j, ep, K, ts[j], sigma11, sigma22, r0, m, dYj.as<double>(), r1, mnew, tol, max_iter,
-                                  dmean.as<double>() + j * col, dcov.as<double>() + j * col, &its[j]));
-    }
-  } else {
-    // shared and read-only from here: the row sets, the labels, V1.  Class j owns its spectrum weights and its operand
-    // (or, on the wide route, its columns of the result); a worker owns the loop's state and runs its classes in turn.
-    FLGP_TRY(r0.gather(st.s, ep, K));
-    FLGP_HIP(hipStreamSynchronize(st.s));
-    const bool fused = gpc_predict_rows_applicable(K);
-    const size_t ge = gpc_predict_operand_elems(K);
-    DevBuf Gf;
-    if (fused) FLGP_TRY(Gf.alloc(sizeof(double) * ge * J));
-    std::vector<GprCtx> ctx((size_t)J);
-    // one class on a worker's stream: the binary entry's launches in the binary entry's order
-    auto one_class = [&](hipStream_t ws, McWorker &W, int j) -> int {
-      char name[64];
-      name_class(j, name);
-      GprCtx &G = ctx[(size_t)j];
-      FLGP_TRY(G.prepare(ws, ep, K, ts[j]));                      // ls = L^1/2, l = L
-      FLGP_TRY(gpc_class_indicator(ws, dlab.as<double>(), m, j, W.dY.as<double>()));
-      GpcWeightSpace &S = W.S;
-      S.L.l = G.l.as<double>(); S.L.ls = G.ls.as<double>();
-      FLGP_TRY(W.mode_and_operand(ws, tol, max_iter, name, &its[(size_t)j]));
-      if (fused)
-        FLGP_TRY(gpc_predict_prep(ws, K, W.Li.as<double>(), S.L.u.as<double>(), Gf.as<double>() + ge * j));
-      else
-        FLGP_TRY(predict_rows(ws, ep, K, r1, W.Li.as<double>(), S.L.u.as<double>(), sigma22, dmean.as<double>() + j * col,
-                              dcov.as<double>() + j * col));
-      int bad = 0;
-      FLGP_TRY(read_flag(ws, S.flag.p, &bad));
-      return GpcNewton::pivot_error(bad, name, 0);
-    };
-    // the classes are dealt to the pool's workers (worker_pool.h), one worker on the entry's stream
-    DevicePool pool;
-    FLGP_TRY(pool.plan(max_parallel, J, McWorker::bytes(m, K, !fused)));
-    const PoolFailure bad = pool.run<McWorker>(
-        st.s, J,
-        [&](McWorker &W) {
-          W.S.L.sigma = sigma11; W.S.L.V1 = r0.V; W.S.L.ld1 = r0.ld;
-          return W.alloc(m, K);
-        },
-        one_class);
-    if (bad.item >= 0) { set_error("%s", bad.message.c_str()); return bad.status; }
-    // every worker's stream has been waited for: the J operands are in place
-    if (fused)
-      FLGP_TRY(gpc_predict_rows_multi(st.s, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, J, Gf.as<double>(),
-                                      sigma22, dmean.as<double>(), dcov.as<double>(), (long)mnew));
+  // column j = (Y == j): the indicator matrix of multi_train_split, formed on the device
+  std::vector<int> cols((size_t)J), its((size_t)J, 0);
+  for (int j = 0; j < J; ++j) {
+    cols[(size_t)j] = j;
+    FLGP_TRY(gpc_class_indicator(st.s, dlab.as<double>(), m, j, dY.as<double>() + (size_t)j * m));
   }
+  BatchFailure fail;      // the body has worded it: "<who>: class <j>: .."
+  FLGP_TRY(logit_posteriors(st.s, who, true, ep, K, r0, r1, dY.as<double>(), cols.data(), ts, J, sigma11, sigma22, tol, max_iter,
+                            std::max(max_parallel, 1), dmean.as<double>(), dcov.as<double>(), its.data(), fail));
   if (iters) std::copy(its.begin(), its.end(), iters);
   DevBuf dtarget, dnll, work;
   if (nll) {
@@ -1144,149 +1189,7 @@ extern "C" int flgp_eigenpair_logit_posterior_multiclass_nll(const flgp_eigenpai
                               iters, target, n_samples, seed, nll);
 }
 
-// ---- logit posterior for a batch of (labels, t) problems: the weight-space loops in shared launches ------
-namespace {
-// GpcWeightSpace for a chunk of problems on LrBatch's slots, lists and planes: slot s of every buffer belongs to problem
-// p0 + s for the whole chunk and every step of an iteration is one launch over the device list of the slots still
-// iterating, so a problem's bits depend on nothing that shares its chunk.  Of the chunk's m-vectors c holds b / D and g
-// holds p; u holds beta and then L^1/2 beta (a and Xv are not used).  The products take LrBatch's plans, which are those
-// of LowRankB's workspace, the single entry's.  Beside the loop's state a slot owns what McWorker owns: L_Q^-1 (Li), the
-// 64 x K block and the planes of the triangular inverse, and its predictive operand.
-struct WsBatch {
-  LrBatch L;
-  DevBuf Li, Tb, tpart, Gf, all;
-  size_t wi = 0, tpe = 0, ge = 0;
-  long stb = 0, stp = 0;
-
-  // device bytes of one problem: LrBatch's (X, Q, the m-vectors, u, l, ls, the loop's planes), L_Q^-1, the 64 x K block,
-  // the inverse's planes, the operand and two output columns
-  static double bytes(int m, int K, int mnew) {
-    const size_t wi = (size_t)32 * 64 * K;
-    return LrBatch::bytes(m, K) + 8.0 * ((double)pad32((long)K * K) + pad32((long)64 * K) +
-                                         pad32((long)wsb_tri_inverse_planes(K, wi)) + (double)gpc_predict_operand_elems(K) +
-                                         2.0 * mnew) + 4.0;
-  }
-  int alloc(int m, int K, int slots, bool fused) {
-    FLGP_TRY(L.alloc(m, K, slots));
-    wi = (size_t)32 * 64 * K;                                  // McWorker's workspace: it bounds the inverse's splits
-    tpe = wsb_tri_inverse_planes(K, wi);
-    stb = pad32((long)64 * K); stp = pad32((long)tpe);
-    ge = gpc_predict_operand_elems(K);
-    const size_t S = (size_t)slots;
-    FLGP_TRY(Li.alloc(sizeof(double) * S * L.C.sq)); FLGP_TRY(Tb.alloc(sizeof(double) * S * stb));
-    FLGP_TRY(tpart.alloc(sizeof(double) * std::max<size_t>(S * stp, 1)));
-    if (fused) FLGP_TRY(Gf.alloc(sizeof(double) * S * ge));
-    return all.alloc(sizeof(int) * S);
-  }
-  // GpcWeightSpace::solve on the A listed slots: W, b, D, X and L_Q at the current f, then u = Q^-1 L^1/2 V1^T (b / D)
-  int solve(hipStream_t st, const int *a, int A) {
-    LrChunk &C = L.C;
-    FLGP_TRY(wsb_w(st, C, a, A));                                                             // sW, b
-    FLGP_TRY(lrb_d(st, C, a, A));                                                             // D, dh, xs
-    FLGP_TRY(lrb_scale2(st, C, a, A));                                                        // X, then Q = I + X^T X = L_Q L_Q^T
-    {
-      const GemmBatch gb{A, a, C.sx, C.sx, C.sq, 0, L.sp};
-      FLGP_TRY(gemm_launch(st, C.K, C.K, C.m, 1.0, C.X, C.m, 1, C.X, 1, C.m, 0.0, nullptr, 0, 0, C.Q, 1, C.K, L.part.as<double>(),
-                           L.pe, 0.0, nullptr, nullptr, nullptr, L.planQ, nullptr, &gb));
-    }
-    FLGP_TRY(lrb_add_diag(st, C, a, A));
-    FLGP_TRY(lrb_chol(st, C, a, A));
-    FLGP_TRY(wsb_bd(st, C, a, A));                                                            // c = b / D
-    FLGP_TRY(tn(st, a, A, C.c, C.u));                                                         // V1^T (.)
-    FLGP_TRY(lrb_mul(st, C.K, C.ls, C.sk, C.u, C.sk, C.u, C.sk, a, A));                       // L^1/2 (.)
-    return lrb_trsv(st, C, a, A);                                                             // beta
-  }
-  // LrBatch::tn / nn against the shared V1 with the list given (the final step runs on every slot, not on the loop's list)
-  int tn(hipStream_t st, const int *a, int A, const double *x, double *out) {
-    LrChunk &C = L.C;
-    const GemmBatch gb{A, a, 0, C.sv, C.sk, 0, L.sp};
-    return gemm_launch(st, C.K, 1, C.m, 1.0, C.V1, C.ld1, 1, x, 1, C.m, 0.0, nullptr, 0, 0, out, 1, C.K, L.part.as<double>(), L.pe,
-                       0.0, nullptr, nullptr, nullptr, L.planU, nullptr, &gb);
-  }
-  int nn(hipStream_t st, const int *a, int A, const double *u, double *out) {
-    LrChunk &C = L.C;
-    const GemmBatch gb{A, a, 0, C.sk, C.sv, 0, 0};
-    return gemm_launch(st, C.m, 1, C.K, 1.0, C.V1, 1, C.ld1, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, C.m, nullptr, 0, 0.0, nullptr,
-                       nullptr, nullptr, 0, nullptr, &gb);
-  }
-  // u <- L^1/2 beta
-  int scaled_beta(hipStream_t st, const int *a, int A) {
-    LrChunk &C = L.C;
-    return lrb_mul(st, C.K, C.ls, C.sk, C.u, C.sk, C.u, C.sk, a, A);
-  }
-  // GpcWeightSpace::iteration of the A listed slots: every launch once, whatever A is
-  int iteration(hipStream_t st, int A) {
-    ProfScope ps("logit_ws_batch_iter", st, 0.0);
-    LrChunk &C = L.C;
-    const int *a = L.act.as<int>();
-    FLGP_TRY(solve(st, a, A));
-    FLGP_TRY(scaled_beta(st, a, A));
-    FLGP_TRY(nn(st, a, A, C.u, C.g));                                                         // p = V1 L^1/2 beta
-    FLGP_TRY(wsb_fnew(st, C, a, A));                                                          // f_new = p + sigma (b - W p) / D
-    return lrb_step(st, C, a, A, L.stat.as<double>());
-  }
-  // The final step of McWorker::mode_and_operand for every slot 0 .. S-1: the weights once more at the final f, L_Q, beta,
-  // u = L^1/2 beta, Li = L_Q^-1 L^1/2, and (fused) the slot's operand [Li ; u^T]
-  int operands(hipStream_t st, int S) {
-    LrChunk &C = L.C;
-    const int *a = all.as<int>();
-    FLGP_TRY(solve(st, a, S));
-    FLGP_TRY(scaled_beta(st, a, S));
-    FLGP_TRY(wsb_tri_inverse(st, C, a, S, Li.as<double>(), Tb.as<double>(), stb, tpart.as<double>(), tpe, stp, wi));
-    FLGP_TRY(wsb_scale_cols(st, C, a, S, Li.as<double>()));
-    return Gf.p ? wsb_predict_prep(st, C, a, S, Li.as<double>(), Gf.as<double>()) : FLGP_OK;
-  }
-};
-
-// The chunk [p0, p0 + S) from f = 0 with lr_batch_chunk's protocol: after every iteration the host reads the A norms and
-// the A flags (12 A bytes), notes the iteration count of every listed problem and takes the converged and the failed ones
-// off the list; nothing writes a slot that left.  Then the final step for every slot, and its pivot flags (iter 0: the
-// factorisation at the mode).  fail: the lowest failing problem of the chunk; its: the S counts.
-int ws_batch_chunk(hipStream_t st, WsBatch &W, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
-                   int p0, int *its, BatchFailure &fail) {
-  LrBatch &L = W.L;
-  LrChunk &C = L.C;
-  C.slots = S;
-  FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
-  FLGP_HIP(hipMemsetAsync(C.f, 0, sizeof(double) * (size_t)S * C.sv, st));
-  FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
-  std::vector<int> act((size_t)S), next;
-  for (int s = 0; s < S; ++s) act[(size_t)s] = s;
-  FLGP_TRY(h2d(W.all.p, act.data(), sizeof(int) * (size_t)S, st));
-  FLGP_HIP(hipStreamSynchronize(st));            // `act` changes below: the copy has read it
-  std::vector<double> stat((size_t)S * 2);       // 12 A bytes are read into it: A doubles, then A ints
-  bool changed = true;
-  for (int it = 0; it < max_iter && !act.empty(); ++it) {
-    const int A = (int)act.size();
-    if (changed) FLGP_TRY(h2d(L.act.p, act.data(), sizeof(int) * (size_t)A, st));
-    FLGP_TRY(W.iteration(st, A));
-    FLGP_TRY(d2h(stat.data(), L.stat.p, (size_t)12 * A, st));
-    FLGP_HIP(hipStreamSynchronize(st));
-    const int *bad = (const int *)(stat.data() + A);
-    next.clear();
-    for (int q = 0; q < A; ++q) {
-      const int s = act[(size_t)q];
-      its[s] = it + 1;
-      if (bad[q]) {
-        if (fail.problem < 0 || p0 + s < fail.problem) { fail.problem = p0 + s; fail.bad = bad[q]; fail.iter = it + 1; }
-      } else if (!(stat[(size_t)q] < tol)) {
-        next.push_back(s);
-      }
-    }
-    changed = next.size() != act.size();
-    act.swap(next);
-  }
-  if (fail.problem >= 0) return FLGP_OK;
-  FLGP_TRY(W.operands(st, S));
-  std::vector<int> flags((size_t)S, 0);
-  FLGP_TRY(d2h(flags.data(), C.flag, sizeof(int) * (size_t)S, st));
-  FLGP_HIP(hipStreamSynchronize(st));
-  for (int s = 0; s < S; ++s)
-    if (flags[(size_t)s]) { fail.problem = p0 + s; fail.bad = flags[(size_t)s]; fail.iter = 0; break; }
-  return FLGP_OK;
-}
-}  // namespace
-
+// ---- logit posterior for a batch of (labels, t) problems -------------------------------------------------
 extern "C" int flgp_eigenpair_logit_posterior_batch(const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
                                                     int ncol, const int *col, const double *ts, int B, double sigma11,
                                                     double sigma22, const int *idx1, int mnew, double tol, int max_iter,
@@ -1306,61 +1209,20 @@ extern "C" int flgp_eigenpair_logit_posterior_batch(const flgp_eigenpair *ep, in
   for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, nullptr, m, who));
   Rows r0, r1;
   FLGP_TRY(posterior_check_rows(who, ep, K, idx0, m, idx1, mnew, max_iter, true, r0, r1));    // the pair is looked at last
-  auto name_failure = [&](int b, const std::string &msg) { set_error("problem %d (t=%g): %s", b, ts[b], msg.c_str()); };
 
   Stream st;
   FLGP_TRY(st.create());
-  FLGP_TRY(r1.resolve(st.s));
-  const size_t colb = (size_t)mnew, nb = sizeof(double) * colb * B;
+  const size_t nb = sizeof(double) * (size_t)mnew * B;
   DevBuf dY, dmean, dcov;
   FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * ncol, st.s));
   FLGP_TRY(dmean.alloc(nb)); FLGP_TRY(dcov.alloc(nb));
   std::vector<int> its((size_t)B, 0);
-  if (m <= K) {
-    // the dense body per problem, one after another
-    for (int b = 0; b < B; ++b) {
-      const int rc = posterior_dense_on(st.s, who, ep, K, ts[b], sigma11, sigma22, r0, m, dY.as<double>() + (size_t)cols[(size_t)b] * m,
-                                        r1, mnew, tol, max_iter, dmean.as<double>() + b * colb, dcov.as<double>() + b * colb,
-                                        &its[(size_t)b]);
-      if (rc != FLGP_OK) { name_failure(b, std::string(flgp_last_error())); return rc; }
-    }
-  } else {
-    FLGP_TRY(r0.gather(st.s, ep, K));
-    DevBuf dcol, dts;
-    FLGP_TRY(upload(dcol, cols.data(), sizeof(int) * (size_t)B, st.s));
-    FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st.s));
-    const bool fused = gpc_predict_rows_applicable(K);
-    // the chunk: max_parallel problems, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of
-    // the free memory
-    const int want = max_parallel > 0 ? max_parallel : B;
-    size_t free_b = 0, total_b = 0;
-    if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-    const int chunk = std::min(plan_workers(want, B, (double)free_b, WsBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
-    WsBatch W;
-    FLGP_TRY(W.alloc(m, K, chunk, fused));
-    LrChunk &C = W.L.C;
-    C.Y = dY.as<double>(); C.ldy = m; C.N = nullptr;
-    C.V1 = r0.V; C.ld1 = r0.ld; C.sigma = sigma11;
-    for (int p0 = 0; p0 < B; p0 += chunk) {
-      const int S = std::min(chunk, B - p0);
-      C.ycol = dcol.as<int>() + p0;
-      BatchFailure fail;
-      FLGP_TRY(ws_batch_chunk(st.s, W, ep, dts.as<double>() + p0, S, tol, max_iter, p0, its.data() + p0, fail));
-      if (fail.problem >= 0) {
-        const int rc = GpcNewton::pivot_error(fail.bad, who, fail.iter);
-        name_failure(fail.problem, std::string(flgp_last_error()));
-        return rc;
-      }
-      double *cm = dmean.as<double>() + p0 * colb, *cc = dcov.as<double>() + p0 * colb;
-      if (fused) {
-        // one pass over the rows idx1 of the pair for the chunk's S operands
-        FLGP_TRY(gpc_predict_rows_multi(st.s, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, S, W.Gf.as<double>(),
-                                        sigma22, cm, cc, (long)mnew));
-      } else {
-        for (int s = 0; s < S; ++s)
-          FLGP_TRY(predict_rows(st.s, ep, K, r1, W.Li.as<double>() + s * C.sq, C.u + s * C.sk, sigma22, cm + s * colb, cc + s * colb));
-      }
-    }
+  BatchFailure fail;
+  const int rc = logit_posteriors(st.s, who, false, ep, K, r0, r1, dY.as<double>(), cols.data(), ts, B, sigma11, sigma22, tol,
+                                  max_iter, max_parallel, dmean.as<double>(), dcov.as<double>(), its.data(), fail);
+  if (rc != FLGP_OK) {
+    if (fail.problem >= 0) set_error("problem %d (t=%g): %s", fail.problem, ts[fail.problem], std::string(flgp_last_error()).c_str());
+    return rc;
   }
   FLGP_TRY(d2h(mean, dmean.p, nb, st.s));
   FLGP_TRY(d2h(cov, dcov.p, nb, st.s));
@@ -1372,7 +1234,7 @@ extern "C" int flgp_eigenpair_logit_posterior_batch(const flgp_eigenpair *ep, in
 // ---- regression posterior: the drivers' testing step (src/Fit.cpp:70-79) in one call --------------------
 namespace {
 // mean(i, 0:q) = U^T v_i (dmean at ld r.m) and, with dcov, cov_i = c + |G v_i|^2 for the rows r of the pair.  Gf: the fused
-// kernel's operand (gpr_predict_prep on G and U), the rows read in place.  Gf == nullptr: the GEMM route of predict_rows,
+// kernel's operand (gpr_predict_prep on G and U), the rows read in place.  Gf == nullptr: the GEMM route of predict_rows_wide,
 // Z = V G^T and its row sums of squares and a K-wide product for the mean, in row blocks of at most 256 MB.
 int regression_rows(hipStream_t st, const flgp_eigenpair *ep, int K, int q, Rows &r, const double *G, const double *U,
                     const double *Gf, double c, double *dmean, double *dcov) {

@@ -412,32 +412,6 @@ int GpcNewton::amll(hipStream_t st, const double *dY, const double *dN, double *
   return FLGP_OK;
 }
 
-// ---- the elementwise steps of the weight-space Newton loop (m > K, C = V1 L V1^T + sigma I; GpcWeightSpace, eigenpair.hip)
-
-// W = sW^2: D = 1 + sigma W, dh = D^-1/2, xs = sW dh (the row scaling of X = diag(xs) V1 L^1/2)
-__global__ void gpc_lr_d_kernel(const double *__restrict__ sW, double sigma, int m, double *__restrict__ D,
-                                double *__restrict__ dh, double *__restrict__ xs) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const double s = sW[i], d = 1.0 + sigma * (s * s), h = 1.0 / __builtin_sqrt(d);
-  D[i] = d; dh[i] = h; xs[i] = s * h;
-}
-
-int gpc_weights(hipStream_t st, const double *d_f, const double *d_Y, const double *d_N, int m, double *d_sW, double *d_b) {
-  hipLaunchKernelGGL(gpc_w_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_f, d_Y, d_N, m, d_sW, d_b, (double *)nullptr);
-  return check_launch("gpc_w_kernel");
-}
-
-int gpc_step(hipStream_t st, double *d_f, const double *d_fnew, int m, double *d_diff) {
-  hipLaunchKernelGGL(gpc_step_kernel, dim3(1), dim3(1024), 0, st, d_f, d_fnew, m, d_diff);
-  return check_launch("gpc_step_kernel");
-}
-
-int gpc_lr_dvec(hipStream_t st, const double *d_sW, double sigma, int m, double *d_D, double *d_dh, double *d_xs) {
-  hipLaunchKernelGGL(gpc_lr_d_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_sW, sigma, m, d_D, d_dh, d_xs);
-  return check_launch("gpc_lr_d_kernel");
-}
-
 // ---- the low-rank Newton loop for a chunk of independent problems (the loop is in eigenpair.hip) --------
 // The elementwise steps, the K x K factorisation and the final sums of Alg. 3.1 on C = V1 L V1^T + sigma I (LrBatch,
 // eigenpair.hip), with the problem in the grid (blockIdx.y, or blockIdx.x where a workgroup takes a whole problem): entry q
@@ -665,22 +639,7 @@ int lrb_amll(hipStream_t st, const LrChunk &c) {
   return check_launch("lrb_amll_kernel");
 }
 
-// ---- the weight-space Newton loop and the fused predictive rows (m > K; the loop is in eigenpair.hip) ------
-
-// out = b / D
-__global__ void gpc_ws_bd_kernel(const double *__restrict__ b, const double *__restrict__ D, int m, double *__restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) out[i] = b[i] / D[i];
-}
-
-// f_new = p + sigma (b - W p) / D with W = sW^2: the one subtraction of the step, and it is multiplied by sigma
-__global__ void gpc_ws_fnew_kernel(const double *__restrict__ b, const double *__restrict__ sW, const double *__restrict__ D,
-                                   const double *__restrict__ p, double sigma, int m, double *__restrict__ fnew) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const double s = sW[i], pi = p[i];
-  fnew[i] = pi + sigma * ((b[i] - (s * s) * pi) / D[i]);
-}
+// ---- the one-vs-rest indicator and the fused predictive rows of the logit posterior (m > K) ------------------
 
 // out = (labels == j): column j of the one-vs-rest indicator matrix, never stored as a matrix
 __global__ void gpc_class_indicator_kernel(const double *__restrict__ labels, int m, double j, double *__restrict__ out) {
@@ -693,40 +652,14 @@ int gpc_class_indicator(hipStream_t st, const double *d_labels, int m, int j, do
   return check_launch("gpc_class_indicator_kernel");
 }
 
-int gpc_ws_bd(hipStream_t st, const double *d_b, const double *d_D, int m, double *d_out) {
-  hipLaunchKernelGGL(gpc_ws_bd_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_D, m, d_out);
-  return check_launch("gpc_ws_bd_kernel");
-}
-
-int gpc_ws_fnew(hipStream_t st, const double *d_b, const double *d_sW, const double *d_D, const double *d_p, double sigma, int m,
-                double *d_fnew) {
-  hipLaunchKernelGGL(gpc_ws_fnew_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, d_b, d_sW, d_D, d_p, sigma, m, d_fnew);
-  return check_launch("gpc_ws_fnew_kernel");
-}
-
 // The predictive operand Gp = [G ; u^T] ((K + 1) x K: G = L_Q^-1 L^1/2 lower triangular at ld K, u = L^1/2 beta) in the
-// order gpc_predict_rows_kernel loads it: Gf[(jt * nks + ks) * 64 + lane] = Gp(16 jt + (lane & 15), 4 ks + (lane >> 4)),
-// the A fragment of one v_mfma_f64_16x16x4_f64, zero past row K and past column K - 1.  A wave's fragment is 512
-// contiguous bytes and the k steps of a j-tile follow each other.
-__global__ void gpc_predict_prep_kernel(const double *__restrict__ G, const double *__restrict__ u, int K, int nks, long total,
-                                        double *__restrict__ Gf) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int lane = (int)(e & 63);
-  const long f = e >> 6;
-  const int ks = (int)(f % nks), jt = (int)(f / nks);
-  const int j = 16 * jt + (lane & 15), k = 4 * ks + (lane >> 4);
-  double v = 0.0;
-  if (k < K) {
-    if (j < K) v = k <= j ? G[(size_t)k * K + j] : 0.0;
-    else if (j == K) v = u[k];
-  }
-  Gf[e] = v;
-}
+// order the kernel below loads it (wsb_predict_prep_kernel writes it): Gf[(jt * nks + ks) * 64 + lane] =
+// Gp(16 jt + (lane & 15), 4 ks + (lane >> 4)), the A fragment of one v_mfma_f64_16x16x4_f64, zero past row K and past
+// column K - 1.  A wave's fragment is 512 contiguous bytes and the k steps of a j-tile follow each other.
 
 typedef double gd4 __attribute__((ext_vector_type(4)));
 
-constexpr int PR_WAVES = 8;                  // waves per workgroup of gpc_predict_rows_kernel
+constexpr int PR_WAVES = 8;                  // waves per workgroup of gpc_predict_rows_multi_kernel
 constexpr int PR_THREADS = 64 * PR_WAVES;
 // LDS row stride (doubles) of a block of R rows: 16 (mod 32), so that the two k of a 32-lane group of ds_read_b64 fall
 // into different halves of the 64 banks
@@ -741,7 +674,7 @@ __host__ __device__ constexpr int pr_stride(int R) { return R == 16 ? 16 : R + 1
 // lane squares and adds its four results (reg ascending), the four lane groups meet through two xor exchanges
 // ((g0 + g1) + (g2 + g3) on every lane) and the tiles of a row are added in ascending jt by one thread: the bits of a
 // row depend on that row and Gp alone -- not on mnew, the grid, the row's position or its neighbours.
-// The three steps are written once, for the single-operand kernel and the J-operand kernel below.
+// The three steps are written once, for the kernel below and the regression posterior's (gpr_predict_rows_kernel).
 
 // vs[k][r] = V(rows_{base + r}, k) for the block's R rows, zero past K and past mnew
 template <int RT>
@@ -837,28 +770,11 @@ __device__ __forceinline__ void pr_rowsum(const double *__restrict__ ts, int njt
   }
 }
 
-template <int RT>
-__global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_kernel(const double *__restrict__ V, long ld,
-                                                                      const int *__restrict__ idx, int row0, int mnew, int K,
-                                                                      int nks, int njt, const double *__restrict__ Gf, double c,
-                                                                      double *__restrict__ mean, double *__restrict__ cov) {
-  constexpr int R = 16 * RT, RS = pr_stride(R);
-  extern __shared__ double pr_lds[];
-  double *vs = pr_lds;                         // [4 nks][RS]
-  double *ts = pr_lds + (size_t)4 * nks * RS;  // [njt][R]
-  const long base = (long)blockIdx.x * R;
-  pr_stage<RT>(V, ld, idx, row0, mnew, K, nks, base, vs);
-  __syncthreads();
-  pr_tiles<RT>(Gf, vs, ts, K, nks, njt, base, mnew, mean);
-  __syncthreads();
-  pr_rowsum<RT>(ts, njt, base, mnew, c, cov);
-}
-
-// The same for J operands stored back to back (operand j at Gf + j * gf_elems, each written by gpc_predict_prep) into
-// column j of mean / cov (column-major at ldo): the block's rows are staged once and every operand is multiplied against
-// them, so the pair is read once instead of J times.  Per (row, operand) the steps are those of the kernel above, which
-// makes column j the bits of that kernel on operand j.  The workgroups walk the operands in the same order, so the one
-// in use stays in L2.  One ts scratch: a barrier after an operand's tiles and one after its row sums.
+// J operands stored back to back (operand j at Gf + j * gf_elems, each written by wsb_predict_prep) into column j of
+// mean / cov (column-major at ldo): the block's rows are staged once and every operand is multiplied against them, so the
+// pair is read once, not J times.  Per (row, operand) the steps are the three above, so column j depends on operand j
+// alone.  The workgroups walk the operands in the same order, so the one in use stays in L2.  One ts scratch: a barrier
+// after an operand's tiles and one after its row sums.
 template <int RT>
 __global__ __launch_bounds__(PR_THREADS) void gpc_predict_rows_multi_kernel(const double *__restrict__ V, long ld,
                                                                             const int *__restrict__ idx, int row0, int mnew,
@@ -902,13 +818,7 @@ bool gpc_predict_rows_applicable(int K) {
   return pr_rows(ceil_div(K, 4), ceil_div(K + 1, 16), lds > 0 ? lds : 65536) != 0;
 }
 
-int gpc_predict_prep(hipStream_t st, int K, const double *dG, const double *d_u, double *d_Gf) {
-  const long total = (long)gpc_predict_operand_elems(K);
-  hipLaunchKernelGGL(gpc_predict_prep_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, dG, d_u, K, ceil_div(K, 4), total, d_Gf);
-  return check_launch("gpc_predict_prep_kernel");
-}
-
-// the block of rows and the dynamic LDS of both kernels at this K; 0 rows: K does not fit the device's LDS
+// the block of rows and the dynamic LDS of the kernel at this K; 0 rows: K does not fit the device's LDS
 static int pr_shape(const char *who, int K, int *nks, int *njt, size_t *lds) {
   *nks = ceil_div(K, 4); *njt = ceil_div(K + 1, 16);
   const int lds_dev = device_figures().lds_per_block;
@@ -916,25 +826,6 @@ static int pr_shape(const char *who, int K, int *nks, int *njt, size_t *lds) {
   if (!R) { set_error("%s: K=%d does not fit the device's LDS", who, K); return 0; }
   *lds = pr_lds_bytes(R, *nks, *njt);
   return R;
-}
-
-int gpc_predict_rows(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, const double *dG,
-                     const double *d_u, double c, double *d_Gf, double *d_mean, double *d_cov) {
-  int nks, njt;
-  size_t lds;
-  const int R = pr_shape("gpc_predict_rows", K, &nks, &njt, &lds);
-  if (!R) return FLGP_ERR_UNSUPPORTED;
-  ProfScope ps("gpc_predict_rows", st, (double)mnew * K * (K + 1));
-  FLGP_TRY(gpc_predict_prep(st, K, dG, d_u, d_Gf));
-  const dim3 grid(ceil_div(mnew, R)), block(PR_THREADS);
-  auto launch = [&](auto kfn) -> int {
-    if (lds > 48 * 1024) FLGP_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kfn, grid, block, lds, st, dV, ld, d_idx, row0, mnew, K, nks, njt, (const double *)d_Gf, c, d_mean, d_cov);
-    return check_launch("gpc_predict_rows_kernel");
-  };
-  if (R == 64) return launch(gpc_predict_rows_kernel<4>);
-  if (R == 32) return launch(gpc_predict_rows_kernel<2>);
-  return launch(gpc_predict_rows_kernel<1>);
 }
 
 int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int *d_idx, int row0, int mnew, int K, int J,
@@ -957,10 +848,10 @@ int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int 
 }
 
 // ---- the weight-space Newton loop and the predictive operands for a chunk of problems (WsBatch, eigenpair.hip)
-// The steps of GpcWeightSpace that the lrb_* kernels above do not already have, in their form: the slot in blockIdx.y
-// through the device list, a workgroup on its own slot only.  Each keeps the expression tree of the kernel it stands
-// beside (gpc_w_kernel without N, gpc_ws_bd_kernel, gpc_ws_fnew_kernel, tri_inv_diag_kernel, gpr_scale_kernel's column
-// scaling, gpc_predict_prep_kernel), so a slot's bits are the binary entry's.  bd = b / D sits in the chunk's c, p in its g.
+// The steps of the weight-space loop that the lrb_* kernels above do not already have, in their form: the slot in
+// blockIdx.y through the device list, a workgroup on its own slot only.  Each keeps the expression tree of the unbatched
+// kernel it stands beside where there is one (gpc_w_kernel without N, tri_inv_diag_kernel, gpr_scale_kernel's column
+// scaling), so a slot's bits do not depend on its chunk.  bd = b / D sits in the chunk's c, p in its g.
 
 // pi = logistic(f), W = pi (1 - pi): sW = W^1/2, b = W f + (Y - pi)   (N = 1, src/Utils.cpp:269-276)
 __global__ void wsb_w_kernel(LrChunk c, const int *__restrict__ act) {
@@ -1032,7 +923,7 @@ __global__ void wsb_scale_cols_kernel(LrChunk c, const int *__restrict__ act, do
   M[s * c.sq + e] = v;
 }
 
-// gpc_predict_prep_kernel on the slot's G and u: operand s at Gf + s total
+// the predictive operand [G ; u^T] of the slot's G and u in the fused kernel's fragment order: operand s at Gf + s total
 __global__ void wsb_predict_prep_kernel(LrChunk c, const int *__restrict__ act, const double *__restrict__ Gall, int nks, long total,
                                         double *__restrict__ Gf) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1112,7 +1003,7 @@ int wsb_tri_inverse(hipStream_t st, const LrChunk &c, const int *all, int A, dou
 
 // ---- the regression posterior's rows: q mean rows under the triangle ------------------------------------
 // The operand Gp = [G ; U^T] ((K + q) x K: G lower triangular at ld K, or nullptr for zeros when no variance is wanted;
-// U K x q at ld K) in the fragment order of gpc_predict_prep_kernel, njt = ceil((K + q) / 16) j-tiles.
+// U K x q at ld K) in the fragment order of wsb_predict_prep_kernel, njt = ceil((K + q) / 16) j-tiles.
 __global__ void gpr_predict_prep_kernel(const double *__restrict__ G, const double *__restrict__ U, int K, int q, int nks,
                                         long total, double *__restrict__ Gf) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1195,7 +1086,7 @@ __device__ __forceinline__ void pr_tiles_q(const double *__restrict__ Gf, const 
 }
 
 // mean(i, 0:q) = U^T v_i and, with cov, cov_i = c + |G v_i|^2 for the rows v_i of the pair read in place: the staging and the
-// row sums of gpc_predict_rows_kernel, pr_tiles_q between them.  cov == nullptr: the mean rows only (the training rows).
+// row sums of gpc_predict_rows_multi_kernel, pr_tiles_q between them.  cov == nullptr: the mean rows only (the training rows).
 template <int RT>
 __global__ __launch_bounds__(PR_THREADS) void gpr_predict_rows_kernel(const double *__restrict__ V, long ld,
                                                                       const int *__restrict__ idx, int row0, int mnew, int K,

@@ -1,5 +1,5 @@
-// Independent work items on one device, `workers` at a time: the bandwidths of the Nystrom, GLGP and SE grids and the
-// classes of the one-vs-rest posterior.  Worker w owns one State (on the device: a stream and its buffers, see DevicePool
+// Independent work items on one device, `workers` at a time: the bandwidths of the Nystrom, GLGP and SE grids, the dense
+// logit objectives and the Polya-Gamma chains for m <= K.  Worker w owns one State (on the device: a stream and its buffers, see DevicePool
 // in common.h) and takes items w, w + workers, ...; the call reports the lowest failing item.  Generic over the
 // operations and free of HIP so that the scheduling is tested on the CPU (tests/c/worker_pool_check.cc).
 #pragma once

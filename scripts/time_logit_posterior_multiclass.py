@@ -6,11 +6,11 @@ profiles/logit_posterior_multiclass_timing.json.  Per m:
 
   * A: the J binary calls with their columns stacked into two m_new x J arrays (wall clock).  Timed twice, as the first and
     the last block, so that A's own run-to-run spread is on record;
-  * B: the new entry at max_parallel 1, 2, 4 and 8 (wall clock: the uploads and the two m_new x J arrays coming down are in it);
+  * B: the new entry at max_parallel (classes per chunk) 1, 2, 4 and 8 (wall clock: the uploads and the two m_new x J arrays coming down are in it);
   * C: the _nll entry, score only (one double comes down);
-  * the device time of the fused predictive pass (gpc_predict_rows_multi) against the sum of the J single-class passes of
-    A (gpc_predict_rows), both by HIP events on the entries' streams (flgp_prof);
-  * the wall time of the J modes alone at each worker count: the new entry on one new row, where the pass is a single
+  * the device time of the fused predictive pass of B at J classes per chunk against the sum of the J one-operand passes of
+    A (both gpc_predict_rows_multi), by HIP events on the entries' streams (flgp_prof);
+  * the wall time of the J modes alone at each chunk size: the new entry on one new row, where the pass is a single
     workgroup.
 
 Best of --reps after a warm-up, the blocks alternating in one process in the order A, B1, B2, B4, B8, C, A.
@@ -111,8 +111,8 @@ def main():
         row["A_last"], _ = wall(A, args.reps)
         row["A_spread_ms"] = abs(row["A_first"]["ms"] - row["A_last"]["ms"])
         row["A_ms"] = min(row["A_first"]["ms"], row["A_last"]["ms"])
-        single, count = device_ms(A, args.reps, "gpc_predict_rows")
-        fused, _ = device_ms(lambda: B(4), args.reps, "gpc_predict_rows_multi")
+        single, count = device_ms(A, args.reps, "gpc_predict_rows_multi")
+        fused, _ = device_ms(lambda: B(J), args.reps, "gpc_predict_rows_multi")
         row["predict_device_ms"] = dict(J_single_passes=single, single_passes=count, fused_pass=fused)
         row["modes_wall_ms"] = {str(w): wall(lambda: B(w, idx1[:1]), args.reps)[0]["ms"] for w in WORKERS}
         res["rows"].append(row)

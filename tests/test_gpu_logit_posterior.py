@@ -220,7 +220,7 @@ def test_wide_k(wide_pair, K, fused, perm):
     L.flgp_prof_reset(); L.flgp_prof_enable(2)
     try:
         post, it = rp.logit_posterior(idx0, idx1, K, t, Y, s11, s22, return_iters=True)
-        routes = prof_count("gpc_predict_rows"), prof_count("gpc_predict_rows_wide")
+        routes = prof_count("gpc_predict_rows_multi"), prof_count("gpc_predict_rows_wide")
     finally:
         L.flgp_prof_enable(0); L.flgp_prof_reset()
     assert routes == ((1, 0) if fused else (0, 1))

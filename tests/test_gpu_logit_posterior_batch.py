@@ -4,6 +4,11 @@ binary entry flgp_eigenpair_logit_posterior on column col[b] of Y at ts[b] -- on
 sets, for any B, order, mix, duplicates and chunk size.  Every comparison with the single entry is np.array_equal; one
 independent anchor against the dense numpy restatement (tests/np_logit_posterior.py) under its existing tolerances.
 
+The binary entry is the batch of one and the one-vs-rest entry the batch of J (one body in the library), so the
+comparisons with them here are consistency checks: company, order, chunking and B do not show.  The independent
+reference is the pinned bits of the loops those entries ran before (tests/golden/logit_posterior_bits.npz), which
+test_gpu_logit_posterior_bits.py holds every entry to.
+
 One resident synthetic pair of 500 rows per width; idx1 is every third row (167 rows: a partial last row block of the fused
 kernel, and rows shared with idx0)."""
 import ctypes

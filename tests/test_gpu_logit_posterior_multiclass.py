@@ -1,8 +1,12 @@
 """GPU: the one-vs-rest logit posterior in one call (flgp_eigenpair_logit_posterior_multiclass and its _nll
 variant).  The contract is bit for bit: column j of mean / cov and iters[j] are the bytes of the binary entry
 flgp_eigenpair_logit_posterior on Y == j at ts[j], on both sides of m = K, for ranges and index sets, every J and every
-worker count; nll is the bytes of negative_log_likelihood on the returned arrays.  One independent anchor against the dense
-numpy restatement (tests/np_logit_posterior.py) under its existing tolerances, and the refusals.
+chunk size (max_parallel); nll is the bytes of negative_log_likelihood on the returned arrays.  One independent anchor against
+the dense numpy restatement (tests/np_logit_posterior.py) under its existing tolerances, and the refusals.
+
+Both entries run one body in the library (the binary entry is its batch of one), so the comparisons with the binary entry
+here are consistency checks; the independent reference is the pinned bits of the loops the entries ran before
+(tests/golden/logit_posterior_bits.npz, test_gpu_logit_posterior_bits.py).
 
 The pair is tests/test_gpu_logit_posterior.py's (3000 rows, 200 columns, seed 101); ts[j] = 0.5 + 0.7 j."""
 import ctypes
