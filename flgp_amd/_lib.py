@@ -80,6 +80,11 @@ _SIGNATURES = {
     "flgp_regression_batch_dims": (c_int, [P, P, P, P, P, P, P]),
     "flgp_regression_batch_eval": (c_int, [P, P, c_int, P, c_int, P, P, c_int, P]),
     "flgp_regression_batch_free": (None, [P]),
+    "flgp_logit_batch_create": (c_int, [P, P, c_int, c_int, P, c_int, P, c_int, P, c_double, c_char_p, P, c_double, c_int,
+                                        c_int, P]),
+    "flgp_logit_batch_dims": (c_int, [P, P, P, P, P, P, P]),
+    "flgp_logit_batch_eval": (c_int, [P, P, c_int, P, P, P, P]),
+    "flgp_logit_batch_free": (None, [P]),
     "flgp_pg_draw": (c_int, [P, P, c_int, ctypes.c_ulonglong, P]),
     "flgp_pg_logit_predict": (c_int, [P, c_int, P, P, c_int, c_int, ctypes.c_ulonglong, P, P, P, P]),
     "flgp_eigenpair_pg_predict": (c_int, [P, c_int, c_double, c_double, c_double, P, c_int, P, P, c_int, c_int,

@@ -935,6 +935,121 @@ class RegressionObjectiveBatch:
             pass
 
 
+class LogitObjectiveBatch:
+    """The logit training objective for B (pair, labels, t) problems per evaluation (flgp_logit_batch_*,
+    include/flgp_hip.h): a context made once per bandwidth grid and called once per step of the t-searches.
+    Problem b is ``pairs[b]`` (a :class:`ResidentEigenPair`; a pair may be listed several times) with column ``col[b]`` of
+    ``Y`` (m, or m x ncol; ``col`` None needs ncol == B and means 0 .. B-1); the rows ``idx``, ``N``, ``sigma``,
+    ``approach``, ``prior``, ``tol`` and ``max_iter`` are shared.  The pairs must outlive the context (it keeps them alive).
+
+    ``ctx(ts, prob=None, return_iters=False, return_status=False)``: ``ts[a]`` is the t of problem ``prob[a]`` (``prob``
+    None: problems 0 .. B-1, A == B; any order and repeats otherwise).  Returns the A values, each ``logit_objective`` on
+    that pair and column at that t, bit for bit, whatever shares the call and whatever was evaluated before; with
+    ``return_iters`` also the iteration counts.  With ``return_status`` a last array holds 0 or -5 per position, a failed
+    position's value is NaN and nothing is raised; without it the lowest failing position raises.  What the library would
+    refuse about ``ts`` and ``prob`` is refused here, before it is called, with its texts."""
+
+    _WHO = "logit_objective_context"
+
+    def __init__(self, pairs, K, idx, Y, col=None, N=None, sigma=1e-3, approach="posterior", prior=None, tol=1e-5,
+                 max_iter=100, max_parallel=0):
+        self._h = None
+        self._pairs = list(pairs)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        m = idx.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx")
+        Y = np.asfortranarray(Y.reshape(m, -1))
+        B = len(self._pairs)
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per pair")
+        N = None if N is None else np.ascontiguousarray(np.broadcast_to(np.asarray(N, dtype=np.float64), (m,)))
+        pr = None if prior is None else np.ascontiguousarray(np.asarray(prior, dtype=np.float64).reshape(-1))
+        if pr is not None and pr.size != 3:
+            raise ValueError("prior must hold (p, q, tau)")
+        eps = (ctypes.c_void_p * max(B, 1))(*[p._h for p in self._pairs])
+        h = ctypes.c_void_p()
+        check(_lib.lib().flgp_logit_batch_create(eps, _ptr(cols), B, int(K), _ptr(idx), m, _ptr(Y), Y.shape[1], _ptr(N),
+                                                 float(sigma), _b(approach), _ptr(pr), float(tol), int(max_iter),
+                                                 int(max_parallel), ctypes.byref(h)))
+        self._h = h
+        self._set(B, int(K), m, Y.shape[1], str(approach))
+        P, c = ctypes.c_int(), ctypes.c_int()
+        check(_lib.lib().flgp_logit_batch_dims(self._h, None, ctypes.byref(P), None, None, None, ctypes.byref(c)))
+        self.P, self.chunk = P.value, c.value
+
+    @classmethod
+    def for_classes(cls, pairs, K, idx, labels, **kw):
+        """The one-vs-rest grid: ``labels`` holds integers 0 .. J-1 (max + 1 == J), the columns are
+        ``multi_train_split(labels)`` with one trial per row, B = P J and problem p J + j is class j on ``pairs[p]``.
+        ``kw``: sigma, approach, prior, tol, max_iter, max_parallel."""
+        lab = np.asarray(labels, dtype=np.float64).reshape(-1)
+        if lab.size == 0 or not np.isfinite(lab).all() or (lab != np.floor(lab)).any() or (lab < 0).any():
+            raise ValueError("labels must be class labels 0 .. J-1")
+        aug_y = multi_train_split(lab)
+        J = aug_y.shape[1]
+        pairs = list(pairs)
+        ctx = cls([p for p in pairs for _ in range(J)], K, idx, aug_y, col=np.tile(np.arange(J, dtype=np.int32), len(pairs)),
+                  **kw)
+        ctx.J = J
+        return ctx
+
+    def _set(self, B, K, m, ncol, approach):
+        self.B, self.K, self.m, self.ncol, self.approach = B, K, m, ncol, approach
+
+    def _checked(self, ts, prob):
+        """ts as float64 (A,) and prob as int32 (or None), refused as the library refuses them"""
+        who = self._WHO
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        A = ts.size
+        if A < 1:
+            raise FlgpError(-1, "%s: A=%d problems" % (who, A))
+        if prob is None:
+            if A != self.B:
+                raise FlgpError(-1, "%s: prob may be NULL only if A == B (A=%d, B=%d)" % (who, A, self.B))
+        else:
+            prob = np.ascontiguousarray(np.asarray(prob, dtype=np.int32).reshape(-1))
+            if prob.size != A:
+                raise ValueError("prob must have one entry per value of t")
+        # one vectorised pass; only a call that will be refused walks the positions for the first offender, in the library's order
+        ok = np.isfinite(ts).all() and (self.approach != "posterior" or (ts > 0.0).all())
+        ok = ok and (prob is None or ((prob >= 0) & (prob < self.B)).all())
+        if ok:
+            return ts, prob
+        for a in range(A):
+            head = "position %d (t=%g): %s: " % (a, ts[a], who)
+            if prob is not None and not 0 <= int(prob[a]) < self.B:
+                raise FlgpError(-1, head + "prob=%d is outside [0, B=%d)" % (int(prob[a]), self.B))
+            if not np.isfinite(ts[a]):
+                raise FlgpError(-1, head + "t must be finite")
+            if self.approach == "posterior" and not ts[a] > 0.0:
+                raise FlgpError(-1, head + 't must be positive under "posterior"')
+        return ts, prob
+
+    def __call__(self, ts, prob=None, return_iters=False, return_status=False):
+        ts, prob = self._checked(ts, prob)
+        A = ts.size
+        values = np.zeros(A); its = np.zeros(A, dtype=np.int32)
+        status = np.zeros(A, dtype=np.int32) if return_status else None
+        check(_lib.lib().flgp_logit_batch_eval(self._h, _ptr(prob), A, _ptr(ts), _ptr(values), _ptr(its), _ptr(status)))
+        out = (values,) + ((its,) if return_iters else ()) + ((status,) if return_status else ())
+        return out if len(out) > 1 else out[0]
+
+    def free(self):
+        if self._h is not None:
+            _lib.lib().flgp_logit_batch_free(self._h)
+            self._h = None
+        self._pairs = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class SpectrumModel:
     """A fitted graph-Laplacian spectrum (include/flgp_hip.h, "fitted spectrum model"): the anchors, the fit's two
     column-sum vectors, the cluster sizes, the anchor-side eigenpairs and sqrt(n_fit), kept on the device.  ``extend``

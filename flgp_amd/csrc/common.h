@@ -293,6 +293,8 @@ struct GpcNewton {
 // launches (gpc.hip, the loop itself in eigenpair.hip: LrBatch).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
 // of A slot numbers (the problems still iterating) and carry its index in the grid, so a step is one launch whatever A is
 // and a slot that left the list is not written again.  The strides are doubles between two slots; Y, N, V1 are shared.
+// `pair` (nullptr: one pair, V1 shared): a device list with the pair of every SLOT, for a chunk whose problems
+// sit on several pairs; slot s then reads its rows at V1 + pair[s] s1 and its eigenvalues at values + pair[s] sk.
 struct LrChunk {
   int m, K, slots;
   long sv, sk, sx, sq;                                          // of the m-vectors, the K-vectors, X (m x K) and Q (K x K)
@@ -304,15 +306,18 @@ struct LrChunk {
   double sigma;
   int *flag;                                                    // one pivot flag per slot (chol_blocked's)
   double *amll;                                                 // one result per slot
+  const int *pair = nullptr; long s1 = 0;                       // the slot's pair and the doubles between two pairs' rows
 };
-// lrb_weights: l = exp(-t (1 - values)) and ls = l^1/2 for slot s at t = d_ts[s], s < slots.  On the listed slots: lrb_w:
-// sW and b from f, Y, N; lrb_d: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh; lrb_scale2: X = diag(xs) V1 diag(ls);
+// lrb_weights: l = exp(-t (1 - values)) and ls = l^1/2 for slot s at t = d_ts[s], s < slots (d_pair, or nullptr: LrChunk's
+// `pair`, the values of pair p at d_values + p sk).  On the listed slots: lrb_w:
+// sW and b from f, Y, N; lrb_d: D = 1 + sigma sW^2, dh = D^-1/2, xs = sW dh; lrb_scale2: X = diag(xs) V1 diag(ls) (V1 of the slot's pair);
 // lrb_add_diag: Q += I; lrb_mul: out = a .* x, lrb_axpy: out = x + c z (n elements, a stride per operand, 0 = shared);
 // lrb_a: a = b - sW .* (dh .* (g - Xv)).  lrb_step: |f - f_new|_1 in a fixed order and f <- f_new per listed problem,
 // d_stat[q] = the norm of act[q] and ((int *)(d_stat + A))[q] = its pivot flag: 12 A bytes for the host.  lrb_chol:
 // chol_blocked of every listed Q; lrb_trsv: u <- Q^-1 u per listed slot; lrb_amll, for every slot of the chunk: amll[slot] =
 // -0.5 a^T f + sum Y log pi + sum (N - Y) log(1 - pi) - 0.5 sum log D - sum log (L_Q)_kk (the K x K factor).
-int lrb_weights(hipStream_t st, const double *d_values, int K, const double *d_ts, int slots, long sk, double *d_ls, double *d_l);
+int lrb_weights(hipStream_t st, const double *d_values, const int *d_pair, int K, const double *d_ts, int slots, long sk,
+                double *d_ls, double *d_l);
 int lrb_w(hipStream_t st, const LrChunk &c, const int *act, int A);
 int lrb_d(hipStream_t st, const LrChunk &c, const int *act, int A);
 int lrb_scale2(hipStream_t st, const LrChunk &c, const int *act, int A);

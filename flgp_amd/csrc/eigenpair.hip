@@ -570,10 +570,13 @@ inline long pad32(long n) { return (n + 31) / 32 * 32; }     // a slot starts 25
 // still iterating and every step of an iteration is one launch over that list (gpc.hip, LrChunk), so a problem's bits
 // depend on nothing that shares its chunk.  The split products take, per problem, the plan of an unbatched product with a
 // workspace of vt_work_elems(K, 1) doubles (planQ for Q = X^T X, planU for the two K x 1 products) on planes of the
-// slot's own.
+// slot's own.  A chunk on several pairs (C.pair, pair_h its host copy) keeps, behind `act`, the pair of every
+// listed POSITION for the four products against V1: the batched GEMM finds an operand of a list of its own by position.
 struct LrBatch {
   LrChunk C;
   DevBuf vec, kv, X, Q, part, stat, flag, amll, act;
+  const int *pair_h = nullptr;   // slot -> pair, where C.pair is set
+  std::vector<int> apair;        // the host's side of act_pair()
   int planQ = 1, planU = 1;
   size_t pe = 0;                 // doubles of one slot's planes
   long sp = 0;
@@ -600,7 +603,8 @@ struct LrBatch {
     FLGP_TRY(vec.alloc(sizeof(double) * 11 * S * C.sv)); FLGP_TRY(kv.alloc(sizeof(double) * 3 * S * C.sk));
     FLGP_TRY(X.alloc(sizeof(double) * S * C.sx)); FLGP_TRY(Q.alloc(sizeof(double) * S * C.sq));
     FLGP_TRY(part.alloc(sizeof(double) * S * sp)); FLGP_TRY(stat.alloc(12 * S));
-    FLGP_TRY(flag.alloc(sizeof(int) * S)); FLGP_TRY(amll.alloc(sizeof(double) * S)); FLGP_TRY(act.alloc(sizeof(int) * S));
+    FLGP_TRY(flag.alloc(sizeof(int) * S)); FLGP_TRY(amll.alloc(sizeof(double) * S)); FLGP_TRY(act.alloc(sizeof(int) * 2 * S));
+    apair.assign(S, 0);
     double *v = vec.as<double>(), *k = kv.as<double>();
     const size_t vs = S * C.sv, ks = S * C.sk;
     C.f = v; C.fnew = v + vs; C.sW = v + 2 * vs; C.b = v + 3 * vs; C.a = v + 4 * vs; C.D = v + 5 * vs; C.dh = v + 6 * vs;
@@ -609,23 +613,28 @@ struct LrBatch {
     C.X = X.as<double>(); C.Q = Q.as<double>(); C.flag = flag.as<int>(); C.amll = amll.as<double>();
     return FLGP_OK;
   }
-  // C (M x 1) = A^T B or A B per listed slot, as gemm_tn / gemm_nn on the slot's operands (a stride of 0: the shared V1)
-  int tn(hipStream_t st, int A, const double *Am, long lda, long a_bs, const double *x, double *out) {
-    const GemmBatch gb{A, act.as<int>(), a_bs, C.sv, C.sk, 0, sp};
+  // the pair of act[q] at position q, or nullptr for a chunk on one pair; batch_newton_loop keeps it beside `act`
+  const int *act_pair() const { return C.pair ? (const int *)act.p + apair.size() : nullptr; }
+  // C (M x 1) = A^T B or A B per listed slot, as gemm_tn / gemm_nn on the slot's operands (a stride of 0: the shared V1;
+  // la: the operand's own list, for V1 of the position's pair)
+  int tn(hipStream_t st, int A, const double *Am, long lda, long a_bs, const double *x, double *out, const int *la = nullptr) {
+    GemmBatch gb{A, act.as<int>(), a_bs, C.sv, C.sk, 0, sp};
+    gb.a_slots = la;
     return gemm_launch(st, C.K, 1, C.m, 1.0, Am, lda, 1, x, 1, C.m, 0.0, nullptr, 0, 0, out, 1, C.K, part.as<double>(), pe, 0.0,
                        nullptr, nullptr, nullptr, planU, nullptr, &gb);
   }
-  int nn(hipStream_t st, int A, const double *Am, long lda, long a_bs, const double *u, double *out) {
-    const GemmBatch gb{A, act.as<int>(), a_bs, C.sk, C.sv, 0, 0};
+  int nn(hipStream_t st, int A, const double *Am, long lda, long a_bs, const double *u, double *out, const int *la = nullptr) {
+    GemmBatch gb{A, act.as<int>(), a_bs, C.sk, C.sv, 0, 0};
+    gb.a_slots = la;
     return gemm_launch(st, C.m, 1, C.K, 1.0, Am, 1, lda, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, C.m, nullptr, 0, 0.0, nullptr,
                        nullptr, nullptr, 0, nullptr, &gb);
   }
   // out = C x = V1 (L (V1^T x)) + sigma x   (Xv is the scratch)
   int cmul(hipStream_t st, int A, const double *x, double *out) {
-    const int *a = act.as<int>();
-    FLGP_TRY(tn(st, A, C.V1, C.ld1, 0, x, C.u));
+    const int *a = act.as<int>(), *la = act_pair();
+    FLGP_TRY(tn(st, A, C.V1, C.ld1, C.s1, x, C.u, la));
     FLGP_TRY(lrb_mul(st, C.K, C.l, C.sk, C.u, C.sk, C.u, C.sk, a, A));
-    FLGP_TRY(nn(st, A, C.V1, C.ld1, 0, C.u, C.Xv));
+    FLGP_TRY(nn(st, A, C.V1, C.ld1, C.s1, C.u, C.Xv, la));
     return lrb_axpy(st, C.m, C.Xv, C.sv, C.sigma, x, C.sv, out, C.sv, a, A);
   }
   // one Newton iteration of the A listed slots: every launch once, whatever A is
@@ -653,20 +662,23 @@ struct LrBatch {
   }
 };
 
-struct BatchFailure { int problem = -1, bad = 0, iter = 0; };
+// bad_of / iter_of (optional, one entry per slot of the chunk): every failing slot's flag and iteration, for a caller that
+// reports per problem
+struct BatchFailure { int problem = -1, bad = 0, iter = 0; int *bad_of = nullptr, *iter_of = nullptr; };
 
 // The host side of a chunk's Newton loops, the objective's (lr_batch_chunk) and the posterior's (ws_batch_chunk): the chunk
 // [p0, p0 + S) from f = 0, `iteration(A)` one Newton iteration of the A listed slots.  After every iteration the host reads
 // the A norms and the A flags (12 A bytes), notes the iteration count of every listed problem and takes the converged ones
 // (norm < tol) and the failed ones (a pivot flag) off the list: GpcNewton::run's protocol per problem; nothing writes a
 // slot that left.  fail: the lowest failing problem; its: the S counts.  d_all (or nullptr): a device list that gets
-// 0 .. S-1, for the steps that follow the loop on every slot.
+// 0 .. S-1, for the steps that follow the loop on every slot.  d_values: the pair's eigenvalues, or, for a chunk on several
+// pairs (C.pair), every pair's at stride C.sk; such a chunk's list goes up with the pair of every position behind it.
 template <class Iteration>
-int batch_newton_loop(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+int batch_newton_loop(hipStream_t st, LrBatch &L, const double *d_values, const double *d_ts, int S, double tol, int max_iter,
                       int p0, int *its, BatchFailure &fail, int *d_all, Iteration iteration) {
   LrChunk &C = L.C;
   C.slots = S;
-  FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
+  FLGP_TRY(lrb_weights(st, d_values, C.pair, C.K, d_ts, S, C.sk, C.ls, C.l));
   FLGP_HIP(hipMemsetAsync(C.f, 0, sizeof(double) * (size_t)S * C.sv, st));
   FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
   std::vector<int> act((size_t)S), next;
@@ -680,6 +692,10 @@ int batch_newton_loop(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, cons
   for (int it = 0; it < max_iter && !act.empty(); ++it) {
     const int A = (int)act.size();
     if (changed) FLGP_TRY(h2d(L.act.p, act.data(), sizeof(int) * (size_t)A, st));
+    if (changed && C.pair) {                     // read, like `act`, before the wait below, and not written until after it
+      for (int q = 0; q < A; ++q) L.apair[(size_t)q] = L.pair_h[act[(size_t)q]];
+      FLGP_TRY(h2d((void *)L.act_pair(), L.apair.data(), sizeof(int) * (size_t)A, st));
+    }
     FLGP_TRY(iteration(A));
     FLGP_TRY(d2h(stat.data(), L.stat.p, (size_t)12 * A, st));
     FLGP_HIP(hipStreamSynchronize(st));
@@ -689,6 +705,7 @@ int batch_newton_loop(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, cons
       const int s = act[(size_t)q];
       its[s] = it + 1;
       if (bad[q]) {
+        if (fail.bad_of) { fail.bad_of[s] = bad[q]; fail.iter_of[s] = it + 1; }
         if (fail.problem < 0 || p0 + s < fail.problem) { fail.problem = p0 + s; fail.bad = bad[q]; fail.iter = it + 1; }
       } else if (!(stat[(size_t)q] < tol)) {
         next.push_back(s);
@@ -701,9 +718,9 @@ int batch_newton_loop(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, cons
 }
 
 // The objective's chunk: the loops, then the final sums for every slot.  amll_h / its: the S results.
-int lr_batch_chunk(hipStream_t st, LrBatch &L, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
+int lr_batch_chunk(hipStream_t st, LrBatch &L, const double *d_values, const double *d_ts, int S, double tol, int max_iter,
                    int p0, double *amll_h, int *its, BatchFailure &fail) {
-  FLGP_TRY(batch_newton_loop(st, L, ep, d_ts, S, tol, max_iter, p0, its, fail, nullptr, [&](int A) { return L.iteration(st, A); }));
+  FLGP_TRY(batch_newton_loop(st, L, d_values, d_ts, S, tol, max_iter, p0, its, fail, nullptr, [&](int A) { return L.iteration(st, A); }));
   FLGP_TRY(lrb_amll(st, L.C));
   FLGP_TRY(d2h(amll_h, L.C.amll, sizeof(double) * (size_t)S, st));
   FLGP_HIP(hipStreamSynchronize(st));
@@ -748,6 +765,12 @@ int objective_sigma_prior(const char *who, double sigma, const double *prior, do
   for (int k = 0; k < 3; ++k) pr[k] = prior ? prior[k] : dflt[k];
   FLGP_REQUIRE(all_finite(pr, 3), "%s: prior (p, q, tau) must be finite", who);
   return FLGP_OK;
+}
+
+// negative_marginal_likelihood_logit_cpp / negative_log_posterior_logit_cpp (src/train.cpp:14-34) from the loop's amll
+double logit_objective_value(bool posterior, const double *pr, double t, double amll) {
+  const double p = posterior ? pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]) : 0.0;
+  return posterior ? -amll + p : -amll;
 }
 
 // The B checked problems on the checked rows r: problem b is column col[b] of Y (r.m x ncol; col NULL: column b) at ts[b],
@@ -807,7 +830,8 @@ int logit_objectives(const char *who, bool by_problem, const flgp_eigenpair *ep,
       const int S = std::min(chunk, B - p0);
       L.C.ycol = dcol.as<int>() + p0;
       BatchFailure fail;
-      FLGP_TRY(lr_batch_chunk(st.s, L, ep, dts.as<double>() + p0, S, tol, max_iter, p0, amll.data() + p0, its.data() + p0, fail));
+      FLGP_TRY(lr_batch_chunk(st.s, L, (const double *)ep->values.p, dts.as<double>() + p0, S, tol, max_iter, p0, amll.data() + p0,
+                              its.data() + p0, fail));
       if (fail.problem >= 0) {
         const int rc = GpcNewton::pivot_error(fail.bad, who, fail.iter);
         name_failure(fail.problem, std::string(flgp_last_error()));
@@ -816,10 +840,7 @@ int logit_objectives(const char *who, bool by_problem, const flgp_eigenpair *ep,
     }
   }
   for (int b = 0; b < B; ++b) {
-    const double t = ts[b];
-    // negative_marginal_likelihood_logit_cpp / negative_log_posterior_logit_cpp (src/train.cpp:14-34)
-    const double p = posterior ? pr[0] * std::log(t + 1e-9) + std::pow(t / pr[2], -pr[1]) : 0.0;
-    values[b] = posterior ? -amll[(size_t)b] + p : -amll[(size_t)b];
+    values[b] = logit_objective_value(posterior, pr, ts[b], amll[(size_t)b]);
     if (iters) iters[b] = its[(size_t)b];
   }
   return FLGP_OK;
@@ -1009,7 +1030,7 @@ struct WsBatch {
 // predicts for next, are resolved while the device runs the final step: the scan of a long idx1 costs the host alone.
 int ws_batch_chunk(hipStream_t st, WsBatch &W, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
                    int p0, int *its, BatchFailure &fail, Rows &r1) {
-  FLGP_TRY(batch_newton_loop(st, W.L, ep, d_ts, S, tol, max_iter, p0, its, fail, W.all.as<int>(),
+  FLGP_TRY(batch_newton_loop(st, W.L, (const double *)ep->values.p, d_ts, S, tol, max_iter, p0, its, fail, W.all.as<int>(),
                              [&](int A) { return W.iteration(st, A); }));
   if (fail.problem >= 0) return FLGP_OK;
   FLGP_TRY(W.operands(st, S));
@@ -1653,7 +1674,7 @@ struct PgBatch {
           PgMatch *match, double *d_pi, double *d_y) {
     P.slots = C.slots = S;
     const int *a = act.as<int>();
-    FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, C.K, d_ts, S, C.sk, C.ls, C.l));
+    FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, nullptr, C.K, d_ts, S, C.sk, C.ls, C.l));
     FLGP_HIP(hipMemsetAsync(C.flag, 0, sizeof(int) * (size_t)S, st));
     FLGP_TRY(pgb_init(st, P));
     const double ss = std::sqrt(P.sigma);
@@ -2389,3 +2410,231 @@ extern "C" int flgp_regression_batch_eval(flgp_regression_batch *hp, const int *
   return rg_eval(h, who, true, prob, A, X, ldx, values, grads, ldg, status);
 }
 
+
+// ---- logit training context: B (pair, labels, t) problems per evaluation on state made once ------------
+// What create keeps: one stream; idx, Y, N and the problems' columns on the device; for m > K every distinct pair's rows
+// (m x K) in one buffer under the slots' stride and the pairs' eigenvalues at stride sk (a lone pair's are read where they
+// are, and a range of its rows in place), the chunk's LrBatch and one pinned upload buffer; for m <= K the resolved rows.
+struct flgp_logit_batch {
+  int B = 0, P = 0, K = 0, m = 0, ncol = 0, chunk = 1, max_parallel = 0, max_iter = 0, device = 0;
+  bool posterior = false, dense = false, in_place = false;
+  double sigma = 0.0, tol = 0.0, pr[3] = {0, 0, 0};
+  std::vector<const flgp_eigenpair *> pairs;      // the P distinct ones, in order of first appearance
+  std::vector<int> pair_of, col, idx;             // problem -> pair, problem -> column of Y; the rows (the host's copy)
+  Stream st;
+  DevBuf didx, dY, dN, V, vals, in;
+  LrBatch L;                                      // the low-rank route's chunk
+  HostMirror h_in;                                // one upload per chunk: [t of every slot | its column (ints) | its pair (ints)]
+  long off_col = 0, off_pair = 0, in_elems = 0;
+
+  // the rows as the dense route's contraction takes them: resolved at create, nothing owned
+  void rows(Rows &r) const {
+    r.idx = idx.data(); r.m = m; r.resolved = true;
+    if (in_place) r.row0 = idx[0];
+    else r.d = (const int *)didx.p;
+  }
+};
+
+namespace {
+const char *const LB_WHO = "logit_objective_context";
+
+// The context of the checked problems: what depends on (pairs, rows, Y, N) only.
+int lb_build(flgp_logit_batch &h, const flgp_eigenpair *const *eps, const int *col, int B, int K, const int *idx, int m,
+             const double *Y, int ncol, const double *N, double sigma, bool posterior, const double *pr, double tol, int max_iter,
+             int max_parallel) {
+  h.B = B; h.K = K; h.m = m; h.ncol = ncol; h.max_parallel = max_parallel; h.max_iter = max_iter;
+  h.posterior = posterior; h.dense = m <= K; h.sigma = sigma; h.tol = tol;
+  h.device = eps[0]->device;
+  for (int a = 0; a < 3; ++a) h.pr[a] = pr[a];
+  h.pair_of.resize((size_t)B); h.col.resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    size_t p = 0;
+    while (p < h.pairs.size() && h.pairs[p] != eps[b]) ++p;
+    if (p == h.pairs.size()) h.pairs.push_back(eps[b]);
+    h.pair_of[(size_t)b] = (int)p;
+    h.col[(size_t)b] = col ? col[b] : b;
+  }
+  h.P = (int)h.pairs.size();
+  h.idx.assign(idx, idx + m);
+  // A range of rows is read in place, as Rows::gather reads it: by the dense route always (its contraction reads the
+  // pair's own rows), by the low-rank route -- whose launches take one base and one leading dimension -- for a lone pair.
+  h.in_place = is_range(idx, m) && (h.dense || h.P == 1);
+  FLGP_TRY(h.st.create());
+  hipStream_t st = h.st.s;
+  std::vector<double> ones;
+  if (!N) { ones.assign((size_t)m, 1.0); N = ones.data(); }
+  FLGP_TRY(upload(h.dY, Y, sizeof(double) * (size_t)m * ncol, st));
+  FLGP_TRY(upload(h.dN, N, sizeof(double) * (size_t)m, st));
+  if (!h.in_place) FLGP_TRY(upload(h.didx, idx, sizeof(int) * (size_t)m, st));
+  if (h.dense) {
+    h.chunk = plan_workers(max_parallel, B, 0.0, 0.0);
+    FLGP_HIP(hipStreamSynchronize(st));          // `ones` goes with this frame
+    return FLGP_OK;
+  }
+  const long sx = pad32((long)m * K), sk = pad32(K);
+  if (!h.in_place) {
+    FLGP_TRY(h.V.alloc(sizeof(double) * (size_t)h.P * sx));
+    for (int p = 0; p < h.P; ++p)
+      FLGP_TRY(flgp_dev_gather_rows(st, (const double *)h.pairs[(size_t)p]->vectors.p, h.pairs[(size_t)p]->n, h.didx.as<int>(), m,
+                                    K, h.V.as<double>() + (size_t)p * sx));
+  }
+  if (h.P == 1) h.vals.borrow(h.pairs[0]->values.p);      // a lone pair's eigenvalues are read where they are
+  else FLGP_TRY(h.vals.alloc(sizeof(double) * (size_t)h.P * sk));
+  for (int p = 0; h.P > 1 && p < h.P; ++p)
+    FLGP_HIP(hipMemcpyAsync(h.vals.as<double>() + (size_t)p * sk, h.pairs[(size_t)p]->values.p, sizeof(double) * (size_t)K,
+                            hipMemcpyDeviceToDevice, st));
+  // the chunk, as the batch entry plans it: max_parallel problems, or (<= 0) all of them; where that is more than one, no
+  // more than fit into 90 % of the free memory
+  const int want = max_parallel > 0 ? max_parallel : B;
+  size_t free_b = 0, total_b = 0;
+  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  h.chunk = std::min(plan_workers(want, B, (double)free_b, LrBatch::bytes(m, K)), GEMM_BATCH_MAX);
+  FLGP_TRY(h.L.alloc(m, K, h.chunk));
+  h.off_col = pad32(h.chunk); h.off_pair = 2 * h.off_col; h.in_elems = 3 * h.off_col;
+  FLGP_TRY(h.in.alloc(sizeof(double) * (size_t)h.in_elems));
+  FLGP_TRY(h.h_in.alloc(sizeof(double) * (size_t)h.in_elems, true));
+  std::memset(h.h_in.p, 0, sizeof(double) * (size_t)h.in_elems);
+  LrChunk &C = h.L.C;
+  C.Y = h.dY.as<double>(); C.ldy = m; C.N = h.dN.as<double>(); C.sigma = sigma;
+  C.ycol = (const int *)(h.in.as<double>() + h.off_col);
+  C.V1 = h.in_place ? (const double *)h.pairs[0]->vectors.p + idx[0] : h.V.as<double>();
+  C.ld1 = h.in_place ? h.pairs[0]->n : m;
+  if (h.P > 1) {                                  // a slot finds its pair through the list; one pair is the shared V1
+    C.pair = (const int *)(h.in.as<double>() + h.off_pair); C.s1 = sx;
+    h.L.pair_h = (const int *)(h.h_in.p + h.off_pair);
+  }
+  FLGP_HIP(hipStreamSynchronize(st));            // the caller's idx, Y and N have gone up
+  return FLGP_OK;
+}
+
+// A checked evaluations.  A position whose factorisation meets a pivot <= 0 fails alone (status, NaN).
+int lb_eval(flgp_logit_batch &h, const int *prob, int A, const double *ts, double *values, int *iters, int *status) {
+  const char *who = LB_WHO;
+  const int m = h.m, K = h.K;
+  std::vector<int> stat((size_t)A, FLGP_OK), its((size_t)A, 0);
+  std::vector<double> amll((size_t)A, 0.0);
+  std::vector<std::string> why((size_t)A);
+  auto report = [&](int a, const std::string &text, int rc) {
+    set_error("position %d (t=%g): %s", a, ts[a], text.c_str());
+    return rc;
+  };
+  if (h.dense) {
+    // the dense loop per position, the positions dealt to the pool's workers; one worker runs on the context's stream
+    DevicePool pool;
+    FLGP_TRY(pool.plan(h.max_parallel, A, DenseObjWorker::bytes(m, K)));
+    const PoolFailure bad = pool.run<DenseObjWorker>(
+        h.st.s, A, [&](DenseObjWorker &W) { return W.alloc(m, K); },
+        [&](hipStream_t ws, DenseObjWorker &W, int a) -> int {
+          const int b = prob ? prob[a] : a;
+          Rows r;
+          h.rows(r);
+          const int rc = W.objective(ws, h.pairs[(size_t)h.pair_of[(size_t)b]], K, ts[a], r, h.sigma,
+                                     h.dY.as<double>() + (size_t)h.col[(size_t)b] * m, h.dN.as<double>(), h.tol, h.max_iter, who,
+                                     &its[(size_t)a], &amll[(size_t)a]);
+          if (rc == FLGP_ERR_NOCONV) { stat[(size_t)a] = rc; why[(size_t)a] = flgp_last_error(); return FLGP_OK; }
+          return rc;
+        });
+    if (bad.item >= 0) return report(bad.item, bad.message, bad.status);
+  } else {
+    std::vector<int> bad_of((size_t)h.chunk), iter_of((size_t)h.chunk);
+    int *hcol = (int *)(h.h_in.p + h.off_col), *hpair = (int *)(h.h_in.p + h.off_pair);
+    for (int p0 = 0; p0 < A; p0 += h.chunk) {
+      const int S = std::min(h.chunk, A - p0);
+      for (int s = 0; s < S; ++s) {
+        const int a = p0 + s, b = prob ? prob[a] : a;
+        h.h_in.p[s] = ts[a];
+        hcol[s] = h.col[(size_t)b];
+        hpair[s] = h.pair_of[(size_t)b];
+      }
+      FLGP_TRY(h2d(h.in.p, h.h_in.p, sizeof(double) * (size_t)h.in_elems, h.st.s));
+      std::fill(bad_of.begin(), bad_of.end(), 0);
+      BatchFailure fail;
+      fail.bad_of = bad_of.data(); fail.iter_of = iter_of.data();
+      // (the chunk's last wait is behind everything that read h_in: the next chunk may fill it)
+      FLGP_TRY(lr_batch_chunk(h.st.s, h.L, h.vals.as<double>(), h.in.as<double>(), S, h.tol, h.max_iter, p0, amll.data() + p0,
+                              its.data() + p0, fail));
+      for (int s = 0; s < S; ++s)
+        if (bad_of[(size_t)s]) {
+          stat[(size_t)(p0 + s)] = GpcNewton::pivot_error(bad_of[(size_t)s], who, iter_of[(size_t)s]);
+          why[(size_t)(p0 + s)] = flgp_last_error();
+        }
+    }
+  }
+  for (int a = 0; a < A; ++a) {
+    const bool ok = stat[(size_t)a] == FLGP_OK;
+    values[a] = ok ? logit_objective_value(h.posterior, h.pr, ts[a], amll[(size_t)a]) : std::nan("");
+    if (iters) iters[a] = its[(size_t)a];
+  }
+  if (status) { std::memcpy(status, stat.data(), sizeof(int) * (size_t)A); return FLGP_OK; }
+  for (int a = 0; a < A; ++a)
+    if (stat[(size_t)a] != FLGP_OK) return report(a, why[(size_t)a], stat[(size_t)a]);
+  return FLGP_OK;
+}
+}  // namespace
+
+extern "C" int flgp_logit_batch_create(const flgp_eigenpair *const *eps, const int *col, int B, int K, const int *idx, int m,
+                                       const double *Y, int ncol, const double *N, double sigma, const char *approach,
+                                       const double *prior, double tol, int max_iter, int max_parallel,
+                                       flgp_logit_batch **out) {
+  const char *who = LB_WHO;
+  bool posterior = false;
+  double pr[3];
+  FLGP_TRY(objective_approach(who, approach, &posterior));
+  FLGP_REQUIRE(eps && idx && Y && out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(B >= 1 && K >= 1 && m >= 1 && ncol >= 1 && max_iter >= 1, "%s: bad shape (B=%d, K=%d, m=%d, ncol=%d, max_iter=%d)",
+               who, B, K, m, ncol, max_iter);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  for (int b = 0; b < B; ++b) {
+    FLGP_REQUIRE(eps[b], "problem %d: %s: null pointer", b, who);
+    FLGP_REQUIRE(K <= eps[b]->K, "problem %d: %s: bad shape (K=%d of %d)", b, who, K, eps[b]->K);
+    FLGP_REQUIRE(eps[b]->device == eps[0]->device, "problem %d: %s: the pair lives on device %d, problem 0's on device %d", b,
+                 who, eps[b]->device, eps[0]->device);
+    const int c = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "problem %d: %s: col=%d is outside [0, ncol=%d)", b, who, c, ncol);
+  }
+  for (int b = 0; b < B; ++b)
+    for (int a = 0; a < m; ++a)
+      FLGP_REQUIRE(idx[a] >= 0 && idx[a] < eps[b]->n, "problem %d: %s: idx[%d]=%d out of range", b, who, a, idx[a]);
+  FLGP_TRY(objective_sigma_prior(who, sigma, prior, pr));
+  for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, N, m, who));
+  int dev = 0;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == eps[0]->device, "%s: the pairs live on device %d, the current device is %d", who, eps[0]->device, dev);
+  std::unique_ptr<flgp_logit_batch> H(new flgp_logit_batch);
+  FLGP_TRY(lb_build(*H, eps, col, B, K, idx, m, Y, ncol, N, sigma, posterior, pr, tol, max_iter, max_parallel));
+  *out = H.release();
+  return FLGP_OK;
+}
+
+extern "C" int flgp_logit_batch_dims(const flgp_logit_batch *h, int *B, int *P, int *K, int *m, int *ncol, int *chunk) {
+  FLGP_REQUIRE(h, "%s: null pointer", LB_WHO);
+  if (B) *B = h->B;
+  if (P) *P = h->P;
+  if (K) *K = h->K;
+  if (m) *m = h->m;
+  if (ncol) *ncol = h->ncol;
+  if (chunk) *chunk = h->chunk;
+  return FLGP_OK;
+}
+
+extern "C" void flgp_logit_batch_free(flgp_logit_batch *h) { delete h; }
+
+extern "C" int flgp_logit_batch_eval(flgp_logit_batch *hp, const int *prob, int A, const double *ts, double *values, int *iters,
+                                     int *status) {
+  const char *who = LB_WHO;
+  FLGP_REQUIRE(hp && ts && values, "%s: null pointer", who);
+  flgp_logit_batch &h = *hp;
+  FLGP_REQUIRE(A >= 1, "%s: A=%d problems", who, A);
+  FLGP_REQUIRE(prob || A == h.B, "%s: prob may be NULL only if A == B (A=%d, B=%d)", who, A, h.B);
+  for (int a = 0; a < A; ++a) {
+    const int b = prob ? prob[a] : a;
+    FLGP_REQUIRE(b >= 0 && b < h.B, "position %d (t=%g): %s: prob=%d is outside [0, B=%d)", a, ts[a], who, b, h.B);
+    FLGP_REQUIRE(std::isfinite(ts[a]), "position %d (t=%g): %s: t must be finite", a, ts[a], who);
+    FLGP_REQUIRE(!h.posterior || ts[a] > 0.0, "position %d (t=%g): %s: t must be positive under \"posterior\"", a, ts[a], who);
+  }
+  int dev = 0;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == h.device, "%s: the pairs live on device %d, the current device is %d", who, h.device, dev);
+  return lb_eval(h, prob, A, ts, values, iters, status);
+}

@@ -420,12 +420,13 @@ int GpcNewton::amll(hipStream_t st, const double *dY, const double *dN, double *
 
 // the slot's spectrum weights at its t: l = exp(-t (1 - values)), ls = l^1/2
 
-__global__ void lrb_weights_kernel(const double *__restrict__ values, int K, const double *__restrict__ ts, long sk,
-                                   double *__restrict__ ls, double *__restrict__ l) {
+__global__ void lrb_weights_kernel(const double *__restrict__ values, const int *__restrict__ pair, int K,
+                                   const double *__restrict__ ts, long sk, double *__restrict__ ls, double *__restrict__ l) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
   const long s = blockIdx.y;
   const double t = ts[s];
+  if (pair) values += (long)pair[s] * sk;                 // the slot's pair (every slot is listed here: s is the slot)
   const double lam = 1.0 - values[k];
   ls[s * sk + k] = exp(-0.5 * t * lam) + 0.0;
   l[s * sk + k] = exp(-t * lam);
@@ -454,13 +455,15 @@ __global__ void lrb_d_kernel(LrChunk c, const int *__restrict__ act) {
   c.D[o] = d; c.dh[o] = h; c.xs[o] = s * h;
 }
 
-// X = diag(xs) V1 diag(ls)
+// X = diag(xs) V1 diag(ls), V1 the shared one or that of the SLOT's pair (c.pair is indexed by the slot, not by the
+// position in `act`: the two part as soon as a slot has left the list)
 __global__ void lrb_scale2_kernel(LrChunk c, const int *__restrict__ act) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (long)c.m * c.K) return;
   const long s = act[blockIdx.y];
   const int i = (int)(e % c.m), j = (int)(e / c.m);
-  c.X[s * c.sx + e] = c.xs[s * c.sv + i] * c.V1[(size_t)j * c.ld1 + i] * c.ls[s * c.sk + j];
+  const double *V1 = c.pair ? c.V1 + (long)c.pair[s] * c.s1 : c.V1;
+  c.X[s * c.sx + e] = c.xs[s * c.sv + i] * V1[(size_t)j * c.ld1 + i] * c.ls[s * c.sk + j];
 }
 
 // Q(i, i) += 1
@@ -564,8 +567,10 @@ __global__ __launch_bounds__(1024) void lrb_amll_kernel(LrChunk c) {
   }
 }
 
-int lrb_weights(hipStream_t st, const double *d_values, int K, const double *d_ts, int slots, long sk, double *d_ls, double *d_l) {
-  hipLaunchKernelGGL(lrb_weights_kernel, dim3(ceil_div(K, 256), slots), dim3(256), 0, st, d_values, K, d_ts, sk, d_ls, d_l);
+int lrb_weights(hipStream_t st, const double *d_values, const int *d_pair, int K, const double *d_ts, int slots, long sk,
+                double *d_ls, double *d_l) {
+  hipLaunchKernelGGL(lrb_weights_kernel, dim3(ceil_div(K, 256), slots), dim3(256), 0, st, d_values, d_pair, K, d_ts, sk, d_ls,
+                     d_l);
   return check_launch("lrb_weights_kernel");
 }
 int lrb_w(hipStream_t st, const LrChunk &c, const int *act, int A) {
