@@ -123,6 +123,13 @@ _SIGNATURES = {
     "flgp_spectrum_model_extend": (c_int, [P, P, c_int, P]),
     "flgp_spectrum_model_extend_resident": (c_int, [P, P, c_int, P, P, c_int, P]),
     "flgp_spectrum_model_free": (None, [P]),
+    "flgp_predictor_regression_create": (c_int, [P, P, c_int, P, c_int, P, c_int, c_double, P, c_int, c_double, P]),
+    "flgp_predictor_logit_create": (c_int, [P, P, c_int, P, c_int, P, c_int, P, P, c_int, c_double, c_double, c_double, c_int,
+                                            c_int, P, P]),
+    "flgp_predictor_dims": (c_int, [P, P, P, P, P, P, P, P, P]),
+    "flgp_predictor_to_host": (c_int, [P, P, P]),
+    "flgp_predictor_apply": (c_int, [P, P, c_int, P, P]),
+    "flgp_predictor_free": (None, [P]),
     "flgp_se_spectrum_grid": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P, c_int]),
     "flgp_lae_eigenmap": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, P, P]),
     "flgp_dev_se_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P,
@@ -156,6 +163,8 @@ _SIGNATURES = {
     "flgp_dev_col_scale_row_normalize": (c_int, [P, P, P, c_int, c_int, P, P]),
     "flgp_dev_extend_scale": (c_int, [P, P, P, c_int, c_int, P, P, P]),
     "flgp_dev_spectrum_model_extend": (c_int, [P, P, P, c_int, c_int, P, c_int]),
+    "flgp_dev_predictor_rows": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, c_int, c_int, P, P, c_long, P, c_long]),
+    "flgp_dev_predictor_apply": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_long]),
     "flgp_dev_gram": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_int]),
     "flgp_dev_gram_order": (c_int, [P, P, c_int, P]),
     "flgp_dev_gram_ordered": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P, c_int]),

@@ -1153,6 +1153,118 @@ def heat_kernel_spectrum_model(X, X_new, s, r, K=-1, models=None, nstart=1, epsi
     return SpectrumModel(hm), ResidentEigenPair(hp)
 
 
+class Predictor:
+    """A trained posterior folded into a fitted :class:`SpectrumModel` (include/flgp_hip.h, "fitted predictor"): fit
+    once, then ``apply`` gives the posterior mean and variance of rows that arrive later from their r anchor weights and
+    the s x (K + q) operand ``P`` -- no eigenvector rows are stored and nothing of the training is redone.  Made by
+    :meth:`regression` or :meth:`logit` with the arguments of ``ResidentEigenPair.regression_posterior`` /
+    ``logit_posterior_batch`` that define the trained state.  The model is borrowed and must outlive the predictor."""
+
+    _KIND = ("regression", "logit")
+
+    def __init__(self, handle, model, iters=None):
+        self._h = handle
+        self._model = model          # keeps the borrowed model alive
+        self.iters = iters
+        v = [ctypes.c_int() for _ in range(7)]
+        ldp = ctypes.c_long()
+        check(_lib.lib().flgp_predictor_dims(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(ldp)))
+        self.d, self.s, self.r, self.K, self.groups, self.q, kind = (int(x.value) for x in v)
+        self.kind = self._KIND[kind]
+        self.ldp = int(ldp.value)
+
+    @staticmethod
+    def _trained(model, pair, idx0, Y):
+        if not isinstance(model, SpectrumModel):
+            raise TypeError("model must be a SpectrumModel")
+        if pair._h is None:
+            raise ValueError("the pair has been freed")
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32).reshape(-1)
+        m = idx0.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx0")
+        return model._handle(), idx0, m, np.asfortranarray(Y.reshape(m, -1))
+
+    @classmethod
+    def regression(cls, model, pair, Y, idx0, K, pars, sigma, noisepar="same"):
+        """The regression posterior at ``pars = (t, noise ..)`` on the training rows ``idx0`` of ``pair`` (the fit's
+        pair), as ``regression_posterior``; in weight space whatever m is."""
+        hm, idx0, m, Y = cls._trained(model, pair, idx0, Y)
+        if noisepar not in ("same", "different"):
+            raise FlgpError(-3, 'predictor_regression: noisepar must be "same" or "different"')
+        nz = np.ascontiguousarray(np.asarray(pars[1:], dtype=np.float64).reshape(-1))
+        if noisepar == "different" and nz.size != m:
+            raise ValueError('noisepar="different" needs one noise variance per training row: pars = (t, noise_1 .. noise_m)')
+        if noisepar == "same":
+            nz = nz[:1].copy()
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_predictor_regression_create(hm, pair._h, int(K), _ptr(idx0), m, _ptr(Y), Y.shape[1], float(pars[0]),
+                                                          _ptr(nz), nz.size, float(sigma), ctypes.byref(out)))
+        return cls(out, model)
+
+    @classmethod
+    def logit(cls, model, pair, idx0, K, ts, Y, col=None, sigma11=0.0, sigma22=1e-3, tol=1e-5, max_iter=100, max_parallel=0):
+        """The Laplace logit posteriors of B problems, as ``logit_posterior_batch``: group b of the predictor is column
+        ``col[b]`` of ``Y`` at ``ts[b]``.  ``iters`` holds the Newton counts."""
+        hm, idx0, m, Y = cls._trained(model, pair, idx0, Y)
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        B = ts.size
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per value of t")
+        its = np.zeros(max(B, 1), dtype=np.int32)
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_predictor_logit_create(hm, pair._h, int(K), _ptr(idx0), m, _ptr(Y), Y.shape[1], _ptr(cols), _ptr(ts), B,
+                                                     float(sigma11), float(sigma22), float(tol), int(max_iter), int(max_parallel),
+                                                     _ptr(its), ctypes.byref(out)))
+        return cls(out, model, its[:B].copy())
+
+    @property
+    def dims(self):
+        return {"d": self.d, "s": self.s, "r": self.r, "K": self.K, "groups": self.groups, "q": self.q, "kind": self.kind,
+                "ldp": self.ldp}
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the predictor has been freed")
+        self._model._handle()
+        return self._h
+
+    def to_host(self):
+        """``{"P": s x ldp (row-major; group g in columns g (K + q) .., its last q the mean's), "cg": groups}``."""
+        h = self._handle()
+        out = {"P": np.zeros((self.s, self.ldp)), "cg": np.zeros(self.groups)}
+        check(_lib.lib().flgp_predictor_to_host(h, _ptr(out["P"]), _ptr(out["cg"])))
+        return out
+
+    def apply(self, X, var=True):
+        """The posterior of the rows ``X`` (n_new x d): ``{"mean": n_new x (groups q), "var": n_new x groups}``
+        Fortran-ordered; ``var=False`` skips the variance ("var" is None) and leaves the mean's bits unchanged."""
+        h = self._handle()
+        X = _f64(X, "X")
+        if X.shape[1] != self.d:
+            raise ValueError(f"X has {X.shape[1]} columns but the model was fitted on {self.d}")
+        n = X.shape[0]
+        if n < 1:
+            raise ValueError("X must have at least one row")
+        mean = np.zeros((n, self.groups * self.q), order="F")
+        v = np.zeros((n, self.groups), order="F") if var else None
+        check(_lib.lib().flgp_predictor_apply(h, _ptr(X), n, _ptr(mean), _ptr(v)))
+        return {"mean": mean, "var": v}
+
+    def free(self):
+        if self._h is not None:
+            _lib.lib().flgp_predictor_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def nystrom_eigenpair_cpp(X, U, a2, K, resident=False):
     """The per-bandwidth block of the ``fit_nystrom_*`` drivers (reference src/Fit.cpp:244-289): Gaussian similarity
     of the anchors with the double normalisation, ``eigs_sym(W_UU, K)``, and the Nystrom extension to the rows of

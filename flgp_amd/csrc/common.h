@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <vector>
 #include "../../include/flgp_hip.h"
 #include "worker_pool.h"
@@ -514,6 +515,32 @@ namespace flgp {
 int check_finite_on_device(hipStream_t st, const double *d_x, long count, const char *who);
 // out(a, k) = V(idx[a], k) into a matrix of leading dimension ldo (gemm.hip)
 int gather_rows_ld(hipStream_t st, const double *dV, int ld, const int *d_idx, int n0, int K, double *d_out, int ldo);
+// The model's row chain up to the weights (model.hip): k-NN -> LAE / SE weights -> flgp_dev_extend_scale for rows [0, nb) of
+// dX (ldx) into W.ell_idx / W.ell_val (nb x r); asynchronous on `st`.  ModelRowWork: its workspaces for a block of at most
+// `rows` rows.  model_block_rows: the block of the knob model_extend_block.
+struct ModelRowWork {
+  DevBuf knn_idx, knn_dist, ell_idx, ell_val;
+  int alloc(const flgp_spectrum_model *m, int rows);
+};
+int model_block_rows();
+int model_rows(hipStream_t st, const flgp_spectrum_model *m, ModelRowWork &W, const double *dX, int nb, int ldx);
+// B(j, k) = Vs(j, k) q_k, q_k = scale / sigma_k (0 where sigma_k = 0): the anchor side of flgp_dev_hk_rows (sparse.hip)
+int hk_rows_b(hipStream_t st, const double *dVs, int ldv, int s, const double *d_eig, int K, double scale, double *dB);
+// The trained operands of the posteriors for the predictor (predictor.hip), by the weight-space route whatever m is, on
+// the launches of the m > K bodies of the entries they mirror (eigenpair.hip).  *_check: that entry's refusals under `who`,
+// before any device work.  The sink receives the operands of problems [p0, p0 + S) while they are valid: G (K x K, ld K)
+// of problem p0 + a at G + a sg and U (K x q, ld K) at U + a su, with var_i = c + |G u_i|^2 and mean_i = U^T u_i; it queues
+// its work on `st`.  Both synchronise `st` and return the mirrored entry's verdict.
+using OperandSink = std::function<int(int p0, int S, const double *G, long sg, const double *U, long su)>;
+int regression_operands_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int q,
+                              double t, const double *noise, int n_noise, double sigma);
+int regression_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
+                        int q, double t, const double *noise, int n_noise, double sigma, const OperandSink &sink);
+int logit_operands_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                         const int *col, const double *ts, int B, double sigma11, double sigma22, int max_iter);
+int logit_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
+                   int ncol, const int *col, const double *ts, int B, double sigma11, double tol, int max_iter, int max_parallel,
+                   int *its, const OperandSink &sink);
 }  // namespace flgp
 
 struct flgp_nystrom_grid;

@@ -5,7 +5,7 @@
 // 8f-5, gpc.hip; the posterior's route for m > K, B problems in shared launches: DESIGN 8 f-11; the binary entry is its
 // batch of one, the J one-vs-rest posteriors its batch of J: f-12; any response matrix in one call: f-17; the
 // training objective for B problems in one call: f-15; the regression objective for B (pair, x) problems through a training
-// context: f-18);
+// context: f-18; the trained operands of both posteriors for the fitted predictor of predictor.hip: f-20);
 // Polya-Gamma Gibbs prediction (pg.hip; B chains in one call: DESIGN 8 f-16).  The algebra they share is written once:
 // woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the Gibbs
 // sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
@@ -1026,20 +1026,57 @@ struct WsBatch {
 
 // The posterior's chunk [p0, p0 + S): the loops, then the final step for every slot and its pivot flags (iter 0: the
 // factorisation at the mode).  A chunk with a failure in the loop skips the final step, so fail is the lowest problem that
-// failed in the loop or, if none did, the lowest that failed at the mode.  its: the S counts.  r1, the rows the caller
+// failed in the loop or, if none did, the lowest that failed at the mode.  its: the S counts.  r1 (optional), the rows the caller
 // predicts for next, are resolved while the device runs the final step: the scan of a long idx1 costs the host alone.
 int ws_batch_chunk(hipStream_t st, WsBatch &W, const flgp_eigenpair *ep, const double *d_ts, int S, double tol, int max_iter,
-                   int p0, int *its, BatchFailure &fail, Rows &r1) {
+                   int p0, int *its, BatchFailure &fail, Rows *r1) {
   FLGP_TRY(batch_newton_loop(st, W.L, (const double *)ep->values.p, d_ts, S, tol, max_iter, p0, its, fail, W.all.as<int>(),
                              [&](int A) { return W.iteration(st, A); }));
   if (fail.problem >= 0) return FLGP_OK;
   FLGP_TRY(W.operands(st, S));
-  FLGP_TRY(r1.resolve(st));
+  if (r1) FLGP_TRY(r1->resolve(st));
   std::vector<int> flags((size_t)S, 0);
   FLGP_TRY(d2h(flags.data(), W.L.C.flag, sizeof(int) * (size_t)S, st));
   FLGP_HIP(hipStreamSynchronize(st));
   for (int s = 0; s < S; ++s)
     if (flags[(size_t)s]) { fail.problem = p0 + s; fail.bad = flags[(size_t)s]; fail.iter = 0; break; }
+  return FLGP_OK;
+}
+
+// The weight-space route of B problems on the checked rows r0: V1 gathered once, then chunks of max_parallel problems (<= 0:
+// all B; where that is more than one, no more than fit into 90 % of the free memory, a problem counted with the rows r1 it
+// predicts for), each run to its operands (ws_batch_chunk; `fused`: with the fused kernel's form of them) and handed to
+// `each` (p0, S, W) while they are valid.  The posterior entries predict the rows r1 there, the predictor folds the
+// operands into its anchor side (r1 == nullptr): one loop, the same launches.  A failing chunk ends the call as logit_posteriors says.
+template <class Each>
+int ws_chunks(hipStream_t st, const char *who, bool by_class, const flgp_eigenpair *ep, int K, Rows &r0, Rows *r1, const double *dY,
+              const int *cols, const double *ts, int B, double sigma11, double tol, int max_iter, int max_parallel, bool fused,
+              int *its, BatchFailure &fail, Each each) {
+  const int m = r0.m, mnew = r1 ? r1->m : 0;
+  FLGP_TRY(r0.gather(st, ep, K));
+  DevBuf dcol, dts;
+  FLGP_TRY(upload(dcol, cols, sizeof(int) * (size_t)B, st));
+  FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st));
+  const int want = max_parallel > 0 ? max_parallel : B;
+  size_t free_b = 0, total_b = 0;
+  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  const int chunk = std::min(plan_workers(want, B, (double)free_b, WsBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
+  WsBatch W;
+  FLGP_TRY(W.alloc(m, K, chunk, fused));
+  LrChunk &C = W.L.C;
+  C.Y = dY; C.ldy = m; C.N = nullptr;
+  C.V1 = r0.V; C.ld1 = r0.ld; C.sigma = sigma11;
+  for (int p0 = 0; p0 < B; p0 += chunk) {
+    const int S = std::min(chunk, B - p0);
+    C.ycol = dcol.as<int>() + p0;
+    FLGP_TRY(ws_batch_chunk(st, W, ep, dts.as<double>() + p0, S, tol, max_iter, p0, its + p0, fail, r1));
+    if (fail.problem >= 0) {
+      char name[64];
+      std::snprintf(name, sizeof(name), "%s: class %d", who, fail.problem);
+      return GpcNewton::pivot_error(fail.bad, by_class ? name : who, fail.iter);
+    }
+    FLGP_TRY(each(p0, S, W));
+  }
   return FLGP_OK;
 }
 
@@ -1072,37 +1109,19 @@ int logit_posteriors(hipStream_t st, const char *who, bool by_class, const flgp_
     }
     return FLGP_OK;
   }
-  FLGP_TRY(r0.gather(st, ep, K));
-  DevBuf dcol, dts;
-  FLGP_TRY(upload(dcol, cols, sizeof(int) * (size_t)B, st));
-  FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st));
   const bool fused = gpc_predict_rows_applicable(K);
-  const int want = max_parallel > 0 ? max_parallel : B;
-  size_t free_b = 0, total_b = 0;
-  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-  const int chunk = std::min(plan_workers(want, B, (double)free_b, WsBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
-  WsBatch W;
-  FLGP_TRY(W.alloc(m, K, chunk, fused));
-  LrChunk &C = W.L.C;
-  C.Y = dY; C.ldy = m; C.N = nullptr;
-  C.V1 = r0.V; C.ld1 = r0.ld; C.sigma = sigma11;
-  for (int p0 = 0; p0 < B; p0 += chunk) {
-    const int S = std::min(chunk, B - p0);
-    C.ycol = dcol.as<int>() + p0;
-    FLGP_TRY(ws_batch_chunk(st, W, ep, dts.as<double>() + p0, S, tol, max_iter, p0, its + p0, fail, r1));
-    if (fail.problem >= 0) return GpcNewton::pivot_error(fail.bad, name_of(fail.problem), fail.iter);
-    double *cm = dmean + p0 * colb, *cc = dcov + p0 * colb;
-    if (fused) {
-      // one pass over the rows idx1 of the pair for the chunk's S operands
-      FLGP_TRY(gpc_predict_rows_multi(st, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, S, W.Gf.as<double>(),
-                                      sigma22, cm, cc, (long)mnew));
-    } else {
-      for (int s = 0; s < S; ++s)
-        FLGP_TRY(predict_rows_wide(st, ep, K, r1, W.Li.as<double>() + s * C.sq, C.u + s * C.sk, sigma22, cm + s * colb,
-                                   cc + s * colb));
-    }
-  }
-  return FLGP_OK;
+  return ws_chunks(st, who, by_class, ep, K, r0, &r1, dY, cols, ts, B, sigma11, tol, max_iter, max_parallel, fused, its, fail,
+                   [&](int p0, int S, WsBatch &W) -> int {
+                     const LrChunk &C = W.L.C;
+                     double *cm = dmean + p0 * colb, *cc = dcov + p0 * colb;
+                     if (fused)      // one pass over the rows idx1 of the pair for the chunk's S operands
+                       return gpc_predict_rows_multi(st, (const double *)ep->vectors.p, ep->n, r1.d, r1.row0, mnew, K, S,
+                                                     W.Gf.as<double>(), sigma22, cm, cc, (long)mnew);
+                     for (int s = 0; s < S; ++s)
+                       FLGP_TRY(predict_rows_wide(st, ep, K, r1, W.Li.as<double>() + s * C.sq, C.u + s * C.sk, sigma22, cm + s * colb,
+                                                  cc + s * colb));
+                     return FLGP_OK;
+                   });
 }
 }  // namespace
 
@@ -1286,6 +1305,66 @@ int regression_rows(hipStream_t st, const flgp_eigenpair *ep, int K, int q, Rows
   return FLGP_OK;
 }
 
+// The trained state of the regression posterior in weight space (the formulas are above the entry below): U = L^1/2 beta
+// (K x q) and, with want_cov, Li = sqrt(c) L_Q^-1 L^1/2 (K x K), from the checked training rows r0.  The entry below and the
+// predictor's operands (regression_operands) run it: one body, the same launches.  G.flag holds the pivot verdict.
+struct GprOperand {
+  GprCtx G;
+  DevBuf dY, dnoise, zinv, ZV, ZY, M, S, Qd, Qs, U, work;
+  DevBuf Li, Tb, wt, lsc;
+  int build(hipStream_t st, const flgp_eigenpair *ep, int K, Rows &r0, const double *Y, int q, double t, const double *noise,
+            bool different, double sigma, bool want_cov) {
+    const int m = r0.m;
+    const double c = noise[0] + sigma;
+    FLGP_TRY(G.prepare(st, ep, K, t));                          // ls = L^1/2
+    FLGP_TRY(r0.gather(st, ep, K));
+    const size_t we = vt_work_elems(K, q);
+    FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * q, st));
+    FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Qd.alloc(sizeof(double) * (size_t)K * K));
+    FLGP_TRY(S.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(U.alloc(sizeof(double) * (size_t)K * q));
+    FLGP_TRY(work.alloc(sizeof(double) * we));
+    const double *ls = G.ls.as<double>();
+    int *flag = G.flag.as<int>();
+    // the mean's system: M = V1^T Z^-1 V1, S = V1^T Z^-1 Y ("same": Z = I and c on Q's diagonal)
+    const double *Vz = r0.V, *Yz = dY.as<double>();
+    long ldz = r0.ld;
+    if (different) {
+      FLGP_TRY(upload(dnoise, noise, sizeof(double) * (size_t)m, st));
+      FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
+      FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
+      FLGP_TRY(gpr_zinv(st, dnoise.as<double>(), sigma, m, zinv.as<double>()));
+      FLGP_TRY(gpr_rowscale_ld(st, r0.V, r0.ld, zinv.as<double>(), m, K, ZV.as<double>()));
+      FLGP_TRY(gpr_rowscale_ld(st, dY.as<double>(), m, zinv.as<double>(), m, q, ZY.as<double>()));
+      Vz = ZV.as<double>(); ldz = m; Yz = ZY.as<double>();
+    }
+    FLGP_TRY(gemm_tn(st, K, K, m, r0.V, r0.ld, Vz, ldz, M.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gemm_tn(st, K, q, m, r0.V, r0.ld, Yz, m, S.as<double>(), work.as<double>(), we));
+    FLGP_TRY(gpr_q(st, M.as<double>(), ls, K, different ? 1.0 : c, Qd.as<double>()));
+    FLGP_TRY(chol_blocked(st, Qd.as<double>(), K, K, flag));
+    FLGP_TRY(gpr_scale(st, S.as<double>(), ls, nullptr, K, q, U.as<double>()));                          // L^1/2 S
+    FLGP_TRY(chol_trsv(st, Qd.as<double>(), K, K, U.as<double>(), K, q, 3, flag));                        // beta
+    FLGP_TRY(gpr_scale(st, U.as<double>(), ls, nullptr, K, q, U.as<double>()));                          // U = L^1/2 beta
+    // the variance's operand: sqrt(c) L_Q^-1 L^1/2; "different" factors Q_s = L^1/2 V1^T V1 L^1/2 + c I beside Q_d
+    if (want_cov) {
+      const double *LQ = Qd.as<double>();
+      if (different) {
+        FLGP_TRY(Qs.alloc(sizeof(double) * (size_t)K * K));
+        FLGP_TRY(gemm_tn(st, K, K, m, r0.V, r0.ld, r0.V, r0.ld, M.as<double>(), work.as<double>(), we));
+        FLGP_TRY(gpr_q(st, M.as<double>(), ls, K, c, Qs.as<double>()));
+        FLGP_TRY(chol_blocked(st, Qs.as<double>(), K, K, flag));
+        LQ = Qs.as<double>();
+      }
+      const size_t wi = (size_t)32 * 64 * K;
+      FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+      FLGP_TRY(wt.alloc(sizeof(double) * wi)); FLGP_TRY(lsc.alloc(sizeof(double) * (size_t)K));
+      FLGP_TRY(tri_inverse(st, LQ, K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, flag));
+      FLGP_TRY(gpr_scalar_mul(st, ls, std::sqrt(c), K, lsc.as<double>()));
+      FLGP_TRY(gpr_scale(st, Li.as<double>(), nullptr, lsc.as<double>(), K, K, Li.as<double>()));
+    }
+    return FLGP_OK;
+  }
+};
+
 // m <= K: the three existing bodies, unchanged, under this entry's name; the score is the host entry on their results
 int regression_posterior_dense(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const int *idx1,
                                int mnew, const double *Y, int q, double t, const double *noise, bool different, double sigma,
@@ -1335,71 +1414,25 @@ extern "C" int flgp_eigenpair_regression_posterior(const flgp_eigenpair *ep, int
   const double c = noise[0] + sigma;
   Stream st;
   FLGP_TRY(st.create());
-  GprCtx G;
-  FLGP_TRY(G.prepare(st.s, ep, K, t));                          // ls = L^1/2
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  DevBuf dY, dnoise, zinv, ZV, ZY, M, S, Qd, Qs, U, work;
-  const size_t we = vt_work_elems(K, q);
-  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * q, st.s));
-  FLGP_TRY(M.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Qd.alloc(sizeof(double) * (size_t)K * K));
-  FLGP_TRY(S.alloc(sizeof(double) * (size_t)K * q)); FLGP_TRY(U.alloc(sizeof(double) * (size_t)K * q));
-  FLGP_TRY(work.alloc(sizeof(double) * we));
-  const double *ls = G.ls.as<double>();
-  int *flag = G.flag.as<int>();
-  // the mean's system: M = V1^T Z^-1 V1, S = V1^T Z^-1 Y ("same": Z = I and c on Q's diagonal)
-  const double *Vz = r0.V, *Yz = dY.as<double>();
-  long ldz = r0.ld;
-  if (different) {
-    FLGP_TRY(upload(dnoise, noise, sizeof(double) * (size_t)m, st.s));
-    FLGP_TRY(zinv.alloc(sizeof(double) * (size_t)m));
-    FLGP_TRY(ZV.alloc(sizeof(double) * (size_t)m * K)); FLGP_TRY(ZY.alloc(sizeof(double) * (size_t)m * q));
-    FLGP_TRY(gpr_zinv(st.s, dnoise.as<double>(), sigma, m, zinv.as<double>()));
-    FLGP_TRY(gpr_rowscale_ld(st.s, r0.V, r0.ld, zinv.as<double>(), m, K, ZV.as<double>()));
-    FLGP_TRY(gpr_rowscale_ld(st.s, dY.as<double>(), m, zinv.as<double>(), m, q, ZY.as<double>()));
-    Vz = ZV.as<double>(); ldz = m; Yz = ZY.as<double>();
-  }
-  FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, Vz, ldz, M.as<double>(), work.as<double>(), we));
-  FLGP_TRY(gemm_tn(st.s, K, q, m, r0.V, r0.ld, Yz, m, S.as<double>(), work.as<double>(), we));
-  FLGP_TRY(gpr_q(st.s, M.as<double>(), ls, K, different ? 1.0 : c, Qd.as<double>()));
-  FLGP_TRY(chol_blocked(st.s, Qd.as<double>(), K, K, flag));
-  FLGP_TRY(gpr_scale(st.s, S.as<double>(), ls, nullptr, K, q, U.as<double>()));                          // L^1/2 S
-  FLGP_TRY(chol_trsv(st.s, Qd.as<double>(), K, K, U.as<double>(), K, q, 3, flag));                        // beta
-  FLGP_TRY(gpr_scale(st.s, U.as<double>(), ls, nullptr, K, q, U.as<double>()));                          // U = L^1/2 beta
-  // the variance's operand: sqrt(c) L_Q^-1 L^1/2; "different" factors Q_s = L^1/2 V1^T V1 L^1/2 + c I beside Q_d
-  DevBuf Li, Tb, wt, lsc;
-  if (want_cov) {
-    const double *LQ = Qd.as<double>();
-    if (different) {
-      FLGP_TRY(Qs.alloc(sizeof(double) * (size_t)K * K));
-      FLGP_TRY(gemm_tn(st.s, K, K, m, r0.V, r0.ld, r0.V, r0.ld, M.as<double>(), work.as<double>(), we));
-      FLGP_TRY(gpr_q(st.s, M.as<double>(), ls, K, c, Qs.as<double>()));
-      FLGP_TRY(chol_blocked(st.s, Qs.as<double>(), K, K, flag));
-      LQ = Qs.as<double>();
-    }
-    const size_t wi = (size_t)32 * 64 * K;
-    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
-    FLGP_TRY(wt.alloc(sizeof(double) * wi)); FLGP_TRY(lsc.alloc(sizeof(double) * (size_t)K));
-    FLGP_TRY(tri_inverse(st.s, LQ, K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, flag));
-    FLGP_TRY(gpr_scalar_mul(st.s, ls, std::sqrt(c), K, lsc.as<double>()));
-    FLGP_TRY(gpr_scale(st.s, Li.as<double>(), nullptr, lsc.as<double>(), K, K, Li.as<double>()));
-  }
-  const double *Gm = want_cov ? Li.as<double>() : nullptr;
+  GprOperand O;
+  FLGP_TRY(O.build(st.s, ep, K, r0, Y, q, t, noise, different, sigma, want_cov));
+  const double *Gm = want_cov ? O.Li.as<double>() : nullptr;
   DevBuf Gf;
   if (gpr_predict_rows_applicable(K, q)) {
     FLGP_TRY(Gf.alloc(sizeof(double) * gpr_predict_operand_elems(K, q)));
-    FLGP_TRY(gpr_predict_prep(st.s, K, q, Gm, U.as<double>(), Gf.as<double>()));
+    FLGP_TRY(gpr_predict_prep(st.s, K, q, Gm, O.U.as<double>(), Gf.as<double>()));
   }
   const double *gf = Gf.p ? Gf.as<double>() : nullptr;
   DevBuf dtrain, dmean, dcov, dtarget, dnll, nwork;
   if (train_pred) {           // the training rows through the same kernel: the mean rows only
     FLGP_TRY(dtrain.alloc(sizeof(double) * (size_t)m * q));
-    FLGP_TRY(regression_rows(st.s, ep, K, q, r0, Gm, U.as<double>(), gf, c, dtrain.as<double>(), nullptr));
+    FLGP_TRY(regression_rows(st.s, ep, K, q, r0, Gm, O.U.as<double>(), gf, c, dtrain.as<double>(), nullptr));
     FLGP_TRY(d2h(train_pred, dtrain.p, sizeof(double) * (size_t)m * q, st.s));
   }
   if (want_test) {
     FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)mnew * q));
     if (want_cov) FLGP_TRY(dcov.alloc(sizeof(double) * (size_t)mnew));
-    FLGP_TRY(regression_rows(st.s, ep, K, q, r1, Gm, U.as<double>(), gf, c, dmean.as<double>(), want_cov ? dcov.as<double>() : nullptr));
+    FLGP_TRY(regression_rows(st.s, ep, K, q, r1, Gm, O.U.as<double>(), gf, c, dmean.as<double>(), want_cov ? dcov.as<double>() : nullptr));
   }
   if (nll) {                  // scored where it lies, before anything is copied
     FLGP_TRY(upload(dtarget, target, sizeof(double) * (size_t)mnew, st.s));
@@ -1410,7 +1443,77 @@ extern "C" int flgp_eigenpair_regression_posterior(const flgp_eigenpair *ep, int
   }
   if (test_pred) FLGP_TRY(d2h(test_pred, dmean.p, sizeof(double) * (size_t)mnew * q, st.s));
   if (cov) FLGP_TRY(d2h(cov, dcov.p, sizeof(double) * (size_t)mnew, st.s));
-  return G.verdict(st.s, who);
+  return O.G.verdict(st.s, who);
+}
+
+// ---- the trained operands for the predictor (common.h, predictor.hip) -----------------------------------
+// The checks of flgp_eigenpair_regression_posterior that concern the trained state, in its order
+int flgp::regression_operands_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int q,
+                                    double t, const double *noise, int n_noise, double sigma) {
+  FLGP_REQUIRE(K >= 1 && m >= 1 && q >= 1, "%s: bad shape (K=%d, m=%d, q=%d)", who, K, m, q);
+  FLGP_REQUIRE(n_noise == 1 || n_noise == m, "%s: n_noise=%d must be 1 (\"same\") or m=%d (\"different\")", who, n_noise, m);
+  FLGP_REQUIRE(std::isfinite(t) && std::isfinite(sigma), "%s: t=%g and sigma=%g must be finite", who, t, sigma);
+  FLGP_REQUIRE(ep && idx0 && Y && noise, "%s: null pointer", who);
+  FLGP_REQUIRE(K <= ep->K, "%s: bad shape (K=%d of %d)", who, K, ep->K);
+  for (int a = 0; a < n_noise; ++a)
+    FLGP_REQUIRE(noise[a] + sigma > 0.0, "%s: noise[%d] + sigma must be positive", who, a);
+  Rows r0;
+  return r0.check(ep, idx0, m, who, "idx0");
+}
+
+// GprOperand whatever m is: the K x K system exists on both sides of m = K
+int flgp::regression_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m,
+                              const double *Y, int q, double t, const double *noise, int n_noise, double sigma,
+                              const OperandSink &sink) {
+  Rows r0;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  GprOperand O;
+  FLGP_TRY(O.build(st, ep, K, r0, Y, q, t, noise, n_noise != 1, sigma, true));
+  FLGP_TRY(sink(0, 1, O.Li.as<double>(), 0, O.U.as<double>(), 0));
+  return O.G.verdict(st, who);
+}
+
+int flgp::logit_operands_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                               const int *col, const double *ts, int B, double sigma11, double sigma22, int max_iter) {
+  FLGP_REQUIRE(idx0 && Y && ts, "%s: null pointer", who);
+  FLGP_REQUIRE(K >= 1 && m >= 1 && max_iter >= 1 && B >= 1 && ncol >= 1, "%s: bad shape (K=%d, m=%d, max_iter=%d, B=%d, ncol=%d)", who,
+               K, m, max_iter, B, ncol);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  for (int b = 0; b < B; ++b) {
+    const int c = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "problem %d (t=%g): %s: col=%d is outside [0, ncol=%d)", b, ts[b], who, c, ncol);
+    FLGP_REQUIRE(std::isfinite(ts[b]), "problem %d (t=%g): %s: t must be finite", b, ts[b], who);
+  }
+  FLGP_TRY(posterior_check_sigmas(who, sigma11, sigma22));
+  for (int c = 0; c < ncol; ++c) FLGP_TRY(check_labels(Y + (size_t)c * m, nullptr, m, who));
+  FLGP_REQUIRE(ep, "%s: null pointer", who);                                                 // the pair is looked at last
+  FLGP_REQUIRE(K <= ep->K, "%s: bad shape (K=%d of %d)", who, K, ep->K);
+  Rows r0;
+  return r0.check(ep, idx0, m, who, "idx0");
+}
+
+// ws_chunks whatever m is, the sink in the place of the predictive rows; a failure is worded as the batch entry's
+int flgp::logit_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
+                         int ncol, const int *col, const double *ts, int B, double sigma11, double tol, int max_iter,
+                         int max_parallel, int *its, const OperandSink &sink) {
+  Rows r0;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  std::vector<int> cols((size_t)B);
+  for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
+  DevBuf dY;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * ncol, st));
+  BatchFailure fail;
+  const int rc = ws_chunks(st, who, false, ep, K, r0, nullptr, dY.as<double>(), cols.data(), ts, B, sigma11, tol, max_iter,
+                           max_parallel, false, its, fail, [&](int p0, int S, WsBatch &W) {
+                             const LrChunk &C = W.L.C;
+                             return sink(p0, S, W.Li.as<double>(), C.sq, C.u, C.sk);
+                           });
+  if (rc != FLGP_OK) {
+    if (fail.problem >= 0) set_error("problem %d (t=%g): %s", fail.problem, ts[fail.problem], std::string(flgp_last_error()).c_str());
+    return rc;
+  }
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
 }
 
 // ---- Polya-Gamma Gibbs prediction: test_pgbinary_cpp and predict_logit_mult_gp_cpp (pg.hip) ---------------

@@ -1,7 +1,8 @@
 // The fitted spectrum model's extension (include/flgp_hip.h): the fit's row chain
 //   k-NN -> LAE / SE weights -> the three scalings under the fit's column sums -> u = a V / sigma * sqrt(n_fit)
 // for rows that were not in the fit, on the stage entries the fit itself runs (knn.hip, lae.hip, sparse.hip).  The fit
-// that makes the handle is capi.hip's flgp_heat_kernel_spectrum_model.
+// that makes the handle is capi.hip's flgp_heat_kernel_spectrum_model.  The chain up to the weights (model_rows) is shared
+// with the fitted predictor (predictor.hip, f-20), which puts its row kernel in the place of U-recovery.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -9,32 +10,19 @@
 
 using namespace flgp;
 
-namespace {
+namespace flgp {
 
-int block_rows() { return std::max(256, tuning("model_extend_block", 1 << 20)); }
+int model_block_rows() { return std::max(256, tuning("model_extend_block", 1 << 20)); }
 
-int on_model_device(const flgp_spectrum_model *m, const char *who) {
-  int dev = -1;
-  FLGP_HIP(hipGetDevice(&dev));
-  FLGP_REQUIRE(dev == m->device, "%s: the model lives on device %d, the current device is %d", who, m->device, dev);
-  return FLGP_OK;
+int ModelRowWork::alloc(const flgp_spectrum_model *m, int rows) {
+  FLGP_TRY(knn_idx.alloc(sizeof(int) * (size_t)rows * m->r));
+  if (m->kernel_se) FLGP_TRY(knn_dist.alloc(sizeof(double) * (size_t)rows * m->r));
+  FLGP_TRY(ell_idx.alloc(sizeof(int) * (size_t)rows * m->r));
+  return ell_val.alloc(sizeof(double) * (size_t)rows * m->r);
 }
 
-// the workspaces of one block of at most `rows` rows
-struct ExtendWork {
-  DevBuf knn_idx, knn_dist, ell_idx, ell_val, uwork;
-  int alloc(const flgp_spectrum_model *m, int rows) {
-    FLGP_TRY(knn_idx.alloc(sizeof(int) * (size_t)rows * m->r));
-    if (m->kernel_se) FLGP_TRY(knn_dist.alloc(sizeof(double) * (size_t)rows * m->r));
-    FLGP_TRY(ell_idx.alloc(sizeof(int) * (size_t)rows * m->r));
-    FLGP_TRY(ell_val.alloc(sizeof(double) * (size_t)rows * m->r));
-    return uwork.alloc(flgp_dev_u_recover_workspace(m->s, m->K));
-  }
-};
-
-// rows [0, nb) of dX (ldx) into rows [0, nb) of d_out (ldo): asynchronous on `st`
-int extend_block(hipStream_t st, const flgp_spectrum_model *m, ExtendWork &W, const double *dX, int nb, int ldx, double *d_out,
-                 int ldo) {
+// The row chain up to the scaled anchor weights, for the extension below and the predictor (predictor.hip)
+int model_rows(hipStream_t st, const flgp_spectrum_model *m, ModelRowWork &W, const double *dX, int nb, int ldx) {
   const int r = m->r, s = m->s;
   const double *Ut = (const double *)m->Ut.p;
   FLGP_TRY(flgp_dev_knn(st, dX, nb, ldx, m->d, Ut, (const double *)m->uu.p, s, r, W.knn_idx.as<int>(),
@@ -44,19 +32,45 @@ int extend_block(hipStream_t st, const flgp_spectrum_model *m, ExtendWork &W, co
                                  W.ell_val.as<double>()));
   else
     FLGP_TRY(flgp_dev_lae(st, dX, nb, ldx, m->d, Ut, s, r, W.knn_idx.as<int>(), nb, W.ell_idx.as<int>(), W.ell_val.as<double>()));
-  FLGP_TRY(flgp_dev_extend_scale(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, r,
-                                 m->gl == FLGP_GL_RW ? nullptr : (const double *)m->colsum_gl.p,
-                                 m->gl == FLGP_GL_CLUSTER_NORMALIZED ? (const double *)m->sizes.p : nullptr,
-                                 (const double *)m->colsum_spectrum.p));
+  return flgp_dev_extend_scale(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, r,
+                               m->gl == FLGP_GL_RW ? nullptr : (const double *)m->colsum_gl.p,
+                               m->gl == FLGP_GL_CLUSTER_NORMALIZED ? (const double *)m->sizes.p : nullptr,
+                               (const double *)m->colsum_spectrum.p);
+}
+
+}  // namespace flgp
+
+namespace {
+
+int on_model_device(const flgp_spectrum_model *m, const char *who) {
+  int dev = -1;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == m->device, "%s: the model lives on device %d, the current device is %d", who, m->device, dev);
+  return FLGP_OK;
+}
+
+// the workspaces of one block of at most `rows` rows
+struct ExtendWork : ModelRowWork {
+  DevBuf uwork;
+  int alloc(const flgp_spectrum_model *m, int rows) {
+    FLGP_TRY(ModelRowWork::alloc(m, rows));
+    return uwork.alloc(flgp_dev_u_recover_workspace(m->s, m->K));
+  }
+};
+
+// rows [0, nb) of dX (ldx) into rows [0, nb) of d_out (ldo): asynchronous on `st`
+int extend_block(hipStream_t st, const flgp_spectrum_model *m, ExtendWork &W, const double *dX, int nb, int ldx, double *d_out,
+                 int ldo) {
+  FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
   // sqrt(n_fit): the scale of the fit's rows, whatever the number of new ones
-  return flgp_dev_u_recover(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, r, (const double *)m->V.p, s, s,
+  return flgp_dev_u_recover(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)m->V.p, m->s, m->s,
                             (const double *)m->eig.p, m->K, std::sqrt((double)m->n_fit), m->root, d_out, ldo, nullptr,
                             W.uwork.as<double>());
 }
 
 // host rows X (n_new x d, ld n_new) block by block into d_out (+ row offset already applied, ldo): synchronises `st`
 int extend_from_host(hipStream_t st, const flgp_spectrum_model *m, const double *X, int n_new, double *d_out, int ldo) {
-  const int B = std::min(block_rows(), n_new), d = m->d;
+  const int B = std::min(model_block_rows(), n_new), d = m->d;
   ExtendWork W;
   DevBuf dX;
   FLGP_TRY(W.alloc(m, B));
@@ -82,7 +96,7 @@ extern "C" int flgp_dev_spectrum_model_extend(void *stream, const flgp_spectrum_
   FLGP_REQUIRE(ldx >= n_new && ldv >= n_new, "spectrum_model_extend: a leading dimension is below n_new = %d", n_new);
   FLGP_REQUIRE(m, "spectrum_model_extend: null handle");
   FLGP_TRY(on_model_device(m, "spectrum_model_extend"));
-  const int B = std::min(block_rows(), n_new);
+  const int B = std::min(model_block_rows(), n_new);
   ExtendWork W;
   FLGP_TRY(W.alloc(m, B));
   for (long i0 = 0; i0 < n_new; i0 += B)

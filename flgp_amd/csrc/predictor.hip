@@ -1,0 +1,289 @@
+// The fitted predictor (include/flgp_hip.h): a trained posterior folded into the anchor side of a fitted
+// spectrum model once,
+//   P = Bq Gp^T   (s x (K + q) per group),   Bq(j, k) = Vs(j, k) sqrt(n_fit) / sigma_k,   Gp = [G ; U^T],
+// so that the posterior of a row that arrives later is z_i = a_i P on the row's r scaled anchor weights: its last q entries
+// the mean, c plus the squares of its first K entries the variance.  No n_new x K array exists.  The trained operands come
+// from the bodies of the entries the handle mirrors (eigenpair.hip: regression_operands, logit_operands); the row chain up
+// to the weights is the model's (model.hip: model_rows).
+#include "common.h"
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+using namespace flgp;
+
+struct flgp_predictor {
+  const flgp_spectrum_model *model = nullptr;   // borrowed
+  DevBuf P, cg;                                 // s x ldp row-major, groups
+  std::vector<int> iters;                       // logit: one count per group
+  int K = 0, groups = 0, q = 0, kind = 0, device = 0;
+  long ldp = 0;
+};
+
+namespace flgp {
+
+// One wave per (row, group).  Lane l of column chunk c holds column j = 64 c + l of the group's K + q: z is the chain over
+// a ascending, multiply then add, from 0.0.  A column j >= K is the mean's entry j - K.  For j < K the lane adds z^2 to its
+// own sum, so lane l holds S_l = the squares of k = l, l + 64, l + 128, .. added in that order from 0.0 (0.0 where K <= l);
+// then six butterfly steps S_l <- S_l + S_(l xor o), o = 32, 16, 8, 4, 2, 1, leave the same total in every lane and
+// var = cg + S_0.  The order is a function of (K, k) alone, every term is a square, and nothing depends on the grid.
+// The row's r (index, value) pairs sit in lanes 0 .. r-1 and are broadcast from there: they are wave-uniform, so a row of P
+// is one coalesced load per chunk.
+constexpr int PRED_WAVES = 4;
+__global__ __launch_bounds__(PRED_WAVES * 64) void predictor_rows_kernel(const int *__restrict__ ell_idx,
+                                                                          const double *__restrict__ ell_val, int n, int r,
+                                                                          const double *__restrict__ P, long ldp, int groups,
+                                                                          int K, int q, const double *__restrict__ cg,
+                                                                          double *__restrict__ mean, long ldm,
+                                                                          double *__restrict__ var, long ldv) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int w = K + q;
+  // the columns a call needs: the mean's alone where var is skipped, the squares' alone where the mean is
+  const int j_lo = var ? 0 : K, j_hi = mean ? w : K;
+  const int c_lo = j_lo / 64, c_hi = (j_hi + 63) / 64;
+  for (long i = (long)blockIdx.x * PRED_WAVES + wave; i < n; i += (long)gridDim.x * PRED_WAVES) {
+    int my_idx = 0;
+    double my_val = 0.0;
+    if (lane < r) { my_idx = ell_idx[i * r + lane]; my_val = ell_val[i * r + lane]; }
+    for (int g = blockIdx.y; g < groups; g += gridDim.y) {
+      const double *__restrict__ Pg = P + (long)g * w;
+      double sq = 0.0;
+      for (int c = c_lo; c < c_hi; ++c) {
+        const int j = c * 64 + lane;
+        const bool on = j >= j_lo && j < j_hi;
+        double z = 0.0;
+        for (int a = 0; a < r; ++a) {           // every lane takes the broadcast; a lane past the columns loads nothing
+          const long ja = __builtin_amdgcn_readlane(my_idx, a);
+          const double va = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_val), a),
+                                             __builtin_amdgcn_readlane(__double2loint(my_val), a));
+          if (on) z = z + va * Pg[ja * ldp + j];
+        }
+        if (on) {
+          if (j < K) sq = sq + z * z;
+          else mean[((long)g * q + (j - K)) * ldm + i] = z;
+        }
+      }
+      if (var) {
+        for (int o = 32; o >= 1; o >>= 1) sq = sq + __shfl_xor(sq, o);
+        if (lane == 0) var[(long)g * ldv + i] = cg[g] + sq;
+      }
+    }
+  }
+}
+
+}  // namespace flgp
+
+extern "C" int flgp_dev_predictor_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r,
+                                       const double *d_P, long ldp, int s, int groups, int K, int q, const double *d_cg,
+                                       double *d_mean, long ldm, double *d_var, long ldv) {
+  const char *who = "predictor_rows";
+  FLGP_REQUIRE(d_ell_idx && d_ell_val && d_P, "%s: null pointer", who);
+  FLGP_REQUIRE(d_mean || d_var, "%s: null pointer (no output is wanted)", who);
+  FLGP_REQUIRE(!d_var || d_cg, "%s: null pointer (the variance needs cg)", who);
+  FLGP_REQUIRE(n >= 1 && r >= 1 && r <= FLGP_RMAX && s >= 1 && groups >= 1 && K >= 1 && q >= 0,
+               "%s: bad shape (n=%d, r=%d, s=%d, groups=%d, K=%d, q=%d)", who, n, r, s, groups, K, q);
+  FLGP_REQUIRE(!d_mean || q >= 1, "%s: a mean needs q >= 1 (q=%d)", who, q);
+  FLGP_REQUIRE(ldp >= (long)groups * ((long)K + q), "%s: ldp=%ld is below groups (K + q) = %ld", who, ldp,
+               (long)groups * ((long)K + q));
+  FLGP_REQUIRE((!d_mean || ldm >= n) && (!d_var || ldv >= n), "%s: a leading dimension is below n = %d", who, n);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("predictor_rows", st, 2.0 * (double)n * r * groups * ((double)K + q));
+  const dim3 grid(std::min(ceil_div(n, PRED_WAVES), 1 << 20), std::min(groups, 65535));
+  hipLaunchKernelGGL(predictor_rows_kernel, grid, dim3(PRED_WAVES * 64), 0, st, d_ell_idx, d_ell_val, n, r, d_P, ldp, groups, K, q,
+                     d_cg, d_mean, ldm, d_var, ldv);
+  return check_launch("predictor_rows_kernel");
+}
+
+namespace {
+
+// what a create entry checks about the model (not null: looked at first) and the pair after its mirrored entry's checks; the
+// comparison of the values is the first device work
+int check_model(const char *who, const flgp_spectrum_model *model, const flgp_eigenpair *ep) {
+  FLGP_REQUIRE(ep->K == model->K, "%s: the pair has K = %d, the model K = %d", who, ep->K, model->K);
+  int dev = -1;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == model->device && dev == ep->device, "%s: the model lives on device %d, the pair on device %d, the current device is %d",
+               who, model->device, ep->device, dev);
+  std::vector<double> a((size_t)ep->K), b((size_t)ep->K);
+  FLGP_HIP(hipMemcpy(a.data(), ep->values.p, sizeof(double) * a.size(), hipMemcpyDeviceToHost));
+  FLGP_HIP(hipMemcpy(b.data(), model->values.p, sizeof(double) * b.size(), hipMemcpyDeviceToHost));
+  FLGP_REQUIRE(std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0,
+               "%s: the pair's values are not the model's (a pair from another fit)", who);
+  return FLGP_OK;
+}
+
+// The handle's P zeroed and the anchor side Bq (s x K, ld s) written; then fold() per chunk of operands
+struct Folder {
+  flgp_predictor *h;
+  DevBuf Bq;
+  int begin(hipStream_t st, const flgp_spectrum_model *model, int K, int groups, int q, int kind) {
+    h->model = model; h->K = K; h->groups = groups; h->q = q; h->kind = kind; h->device = model->device;
+    h->ldp = ((long)groups * (K + q) + 15) / 16 * 16;
+    FLGP_TRY(h->P.alloc(sizeof(double) * (size_t)model->s * h->ldp));
+    FLGP_TRY(h->cg.alloc(sizeof(double) * (size_t)groups));
+    FLGP_TRY(Bq.alloc(sizeof(double) * (size_t)model->s * K));
+    FLGP_HIP(hipMemsetAsync(h->P.p, 0, sizeof(double) * (size_t)model->s * h->ldp, st));
+    return hk_rows_b(st, (const double *)model->V.p, model->s, model->s, (const double *)model->eig.p, K,
+                     std::sqrt((double)model->n_fit), Bq.as<double>());
+  }
+  // groups [p0, p0 + S): P(:, g (K + q) + k') = sum_k Bq(:, k) G_g(k', k), P(:, g (K + q) + K + c) = sum_k Bq(:, k) U_g(k, c); no
+  // workspace, so each element is one k-ascending chain
+  int fold(hipStream_t st, int p0, int S, const double *G, long sg, const double *U, long su) {
+    const int s = h->model->s, K = h->K, q = h->q;
+    for (int a = 0; a < S; ++a) {
+      double *Pg = h->P.as<double>() + (long)(p0 + a) * (K + q);
+      FLGP_TRY(flgp_dev_gemm(st, s, K, K, 1.0, Bq.as<double>(), 1, s, G + a * sg, K, 1, 0.0, nullptr, 0, 0, Pg, h->ldp, 1, nullptr, 0));
+      FLGP_TRY(flgp_dev_gemm(st, s, q, K, 1.0, Bq.as<double>(), 1, s, U + a * su, 1, K, 0.0, nullptr, 0, 0, Pg + K, h->ldp, 1, nullptr,
+                             0));
+    }
+    return FLGP_OK;
+  }
+};
+
+int on_handle_device(const flgp_predictor *h, const char *who) {
+  int dev = -1;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == h->device, "%s: the predictor lives on device %d, the current device is %d", who, h->device, dev);
+  return FLGP_OK;
+}
+
+// rows [0, nb) of dX (ldx): the model's row chain up to the weights, then the row kernel; asynchronous on `st`
+int apply_block(hipStream_t st, const flgp_predictor *h, ModelRowWork &W, const double *dX, int nb, int ldx, double *d_mean, long ldm,
+                double *d_var, long ldv) {
+  const flgp_spectrum_model *m = h->model;
+  FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
+  return flgp_dev_predictor_rows(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, m->s, h->groups,
+                                 h->K, h->q, (const double *)h->cg.p, d_mean, ldm, d_var, ldv);
+}
+
+}  // namespace
+
+extern "C" int flgp_predictor_regression_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0,
+                                                int m, const double *Y, int q, double t, const double *noise, int n_noise,
+                                                double sigma, flgp_predictor **out) {
+  const char *who = "predictor_regression";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(model, "%s: null model", who);
+  FLGP_TRY(regression_operands_check(who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma));
+  FLGP_TRY(check_model(who, model, ep));
+  Stream st;
+  FLGP_TRY(st.create());
+  std::unique_ptr<flgp_predictor> h(new flgp_predictor());
+  Folder F{h.get()};
+  FLGP_TRY(F.begin(st.s, model, K, 1, q, FLGP_PREDICTOR_REGRESSION));
+  const double c = noise[0] + sigma;
+  FLGP_TRY(h2d(h->cg.p, &c, sizeof(double), st.s));
+  FLGP_TRY(regression_operands(st.s, who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma,
+                               [&](int p0, int S, const double *G, long sg, const double *U, long su) {
+                                 return F.fold(st.s, p0, S, G, sg, U, su);
+                               }));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  *out = h.release();
+  return FLGP_OK;
+}
+
+extern "C" int flgp_predictor_logit_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0, int m,
+                                           const double *Y, int ncol, const int *col, const double *ts, int B, double sigma11,
+                                           double sigma22, double tol, int max_iter, int max_parallel, int *iters,
+                                           flgp_predictor **out) {
+  const char *who = "predictor_logit";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(model, "%s: null model", who);
+  FLGP_TRY(logit_operands_check(who, ep, K, idx0, m, Y, ncol, col, ts, B, sigma11, sigma22, max_iter));
+  FLGP_TRY(check_model(who, model, ep));
+  Stream st;
+  FLGP_TRY(st.create());
+  std::unique_ptr<flgp_predictor> h(new flgp_predictor());
+  Folder F{h.get()};
+  FLGP_TRY(F.begin(st.s, model, K, B, 1, FLGP_PREDICTOR_LOGIT));
+  const std::vector<double> cg((size_t)B, sigma22);
+  FLGP_TRY(h2d(h->cg.p, cg.data(), sizeof(double) * (size_t)B, st.s));
+  h->iters.assign((size_t)B, 0);
+  const int rc = logit_operands(st.s, who, ep, K, idx0, m, Y, ncol, col, ts, B, sigma11, tol, max_iter, max_parallel, h->iters.data(),
+                                [&](int p0, int S, const double *G, long sg, const double *U, long su) {
+                                  return F.fold(st.s, p0, S, G, sg, U, su);
+                                });
+  if (rc != FLGP_OK) { (void)hipStreamSynchronize(st.s); return rc; }
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  if (iters) std::copy(h->iters.begin(), h->iters.end(), iters);
+  *out = h.release();
+  return FLGP_OK;
+}
+
+extern "C" int flgp_predictor_dims(const flgp_predictor *h, int *d, int *s, int *r, int *K, int *groups, int *q, int *kind, long *ldp) {
+  FLGP_REQUIRE(h, "predictor_dims: null handle");
+  if (d) *d = h->model->d;
+  if (s) *s = h->model->s;
+  if (r) *r = h->model->r;
+  if (K) *K = h->K;
+  if (groups) *groups = h->groups;
+  if (q) *q = h->q;
+  if (kind) *kind = h->kind;
+  if (ldp) *ldp = h->ldp;
+  return FLGP_OK;
+}
+
+extern "C" int flgp_predictor_to_host(const flgp_predictor *h, double *P, double *cg) {
+  FLGP_REQUIRE(h, "predictor_to_host: null handle");
+  FLGP_TRY(on_handle_device(h, "predictor_to_host"));
+  Stream st;
+  FLGP_TRY(st.create());
+  if (P) FLGP_TRY(d2h(P, h->P.p, sizeof(double) * (size_t)h->model->s * h->ldp, st.s));
+  if (cg) FLGP_TRY(d2h(cg, h->cg.p, sizeof(double) * (size_t)h->groups, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+extern "C" int flgp_dev_predictor_apply(void *stream, const flgp_predictor *h, const double *dX, int n_new, int ldx, double *d_mean,
+                                        long ldm, double *d_var, long ldv) {
+  const char *who = "predictor_apply";
+  hipStream_t st = (hipStream_t)stream;
+  FLGP_REQUIRE(dX && (d_mean || d_var), "%s: null pointer", who);
+  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
+  FLGP_REQUIRE(ldx >= n_new && (!d_mean || ldm >= n_new) && (!d_var || ldv >= n_new), "%s: a leading dimension is below n_new = %d", who,
+               n_new);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_TRY(on_handle_device(h, who));
+  const int B = std::min(model_block_rows(), n_new);
+  ModelRowWork W;
+  FLGP_TRY(W.alloc(h->model, B));
+  for (long i0 = 0; i0 < n_new; i0 += B)
+    FLGP_TRY(apply_block(st, h, W, dX + i0, (int)std::min<long>(B, n_new - i0), ldx, d_mean ? d_mean + i0 : nullptr, ldm,
+                         d_var ? d_var + i0 : nullptr, ldv));
+  FLGP_HIP(hipStreamSynchronize(st));     // (the workspaces die here)
+  return FLGP_OK;
+}
+
+extern "C" int flgp_predictor_apply(const flgp_predictor *h, const double *X, int n_new, double *mean, double *var) {
+  const char *who = "predictor_apply";
+  FLGP_REQUIRE(X && (mean || var), "%s: null pointer", who);
+  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_TRY(on_handle_device(h, who));
+  const flgp_spectrum_model *m = h->model;
+  const int B = std::min(model_block_rows(), n_new), d = m->d, gq = h->groups * h->q;
+  Stream st;
+  FLGP_TRY(st.create());
+  ModelRowWork W;
+  DevBuf dX, dmean, dvar;
+  FLGP_TRY(W.alloc(m, B));
+  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
+  if (mean) FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)n_new * gq));
+  if (var) FLGP_TRY(dvar.alloc(sizeof(double) * (size_t)n_new * h->groups));
+  for (long i0 = 0; i0 < n_new; i0 += B) {
+    const int nb = (int)std::min<long>(B, n_new - i0);
+    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_new, sizeof(double) * (size_t)nb, d,
+                              hipMemcpyHostToDevice, st.s));
+    FLGP_TRY(check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points"));
+    FLGP_TRY(apply_block(st.s, h, W, dX.as<double>(), nb, nb, mean ? dmean.as<double>() + i0 : nullptr, n_new,
+                         var ? dvar.as<double>() + i0 : nullptr, n_new));
+  }
+  if (mean) FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)n_new * gq, st.s));
+  if (var) FLGP_TRY(d2h(var, dvar.p, sizeof(double) * (size_t)n_new * h->groups, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+extern "C" void flgp_predictor_free(flgp_predictor *h) { delete h; }

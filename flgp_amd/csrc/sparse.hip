@@ -893,6 +893,11 @@ __global__ void hk_rows_b_kernel(const double *__restrict__ Vs, int ldv, int s, 
   B[e] = Vs[(size_t)k * ldv + j] * q;
 }
 
+int hk_rows_b(hipStream_t st, const double *dVs, int ldv, int s, const double *d_eig, int K, double scale, double *dB) {
+  hipLaunchKernelGGL(hk_rows_b_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, dVs, ldv, s, d_eig, K, scale, dB);
+  return check_launch("hk_rows_b_kernel");
+}
+
 struct CscPlan {
   int nchunks, chunk, nbits;
   size_t hist_bytes, tot_bytes;
@@ -1366,8 +1371,7 @@ static int hk_rows_run(const char *who, void *stream, const int *d_ell_idx, cons
                "%s: no LDS slice for n=%d r=%d s=%d (ask flgp_dev_hk_rows_route)", who, n, r, s);
   const HkRowsLayout L = hk_rows_layout(s, m, K);
   double *B = d_work + L.b, *Vw = d_work + L.vw, *Wm = d_work + L.wm, *image = d_work + L.image;
-  hipLaunchKernelGGL(hk_rows_b_kernel, dim3(ceil_div((long)s * K, 256)), dim3(256), 0, st, dVs, ldv, s, d_eig, K, scale, B);
-  FLGP_TRY(check_launch("hk_rows_b_kernel"));
+  FLGP_TRY(hk_rows_b(st, dVs, ldv, s, d_eig, K, scale, B));
   FLGP_TRY(hk_scale_launch(st, d_values, K, t, dV1, ld1, nullptr, 0, m, Vw));
   // Wm(j, b) = sum_k B(j, k) Vw(b, k): no workspace, so one k-ascending MFMA chain per element (never split)
   FLGP_TRY(gemm_launch(st, s, m, K, 1.0, B, 1, s, Vw, m, 1, 0.0, nullptr, 0, 0, Wm, 1, s, nullptr, 0, 0.0, nullptr));
