@@ -1158,13 +1158,15 @@ class Predictor:
     once, then ``apply`` gives the posterior mean and variance of rows that arrive later from their r anchor weights and
     the s x (K + q) operand ``P`` -- no eigenvector rows are stored and nothing of the training is redone.  Made by
     :meth:`regression` or :meth:`logit` with the arguments of ``ResidentEigenPair.regression_posterior`` /
-    ``logit_posterior_batch`` that define the trained state.  The model is borrowed and must outlive the predictor."""
+    ``logit_posterior_batch`` that define the trained state.  The model is borrowed and must outlive the predictor.
+    :meth:`nystrom_regression` and :meth:`nystrom_logit` make the same handle over one bandwidth of a
+    :class:`NystromGrid`: dense weights, the mean alone without the similarity ever going to memory."""
 
     _KIND = ("regression", "logit")
 
     def __init__(self, handle, model, iters=None):
         self._h = handle
-        self._model = model          # keeps the borrowed model alive
+        self._model = model          # keeps the borrowed model (or Nystrom grid) alive
         self.iters = iters
         v = [ctypes.c_int() for _ in range(7)]
         ldp = ctypes.c_long()
@@ -1219,6 +1221,59 @@ class Predictor:
                                                      float(sigma11), float(sigma22), float(tol), int(max_iter), int(max_parallel),
                                                      _ptr(its), ctypes.byref(out)))
         return cls(out, model, its[:B].copy())
+
+    @staticmethod
+    def _trained_nystrom(grid, i, pair, idx0, Y):
+        if not isinstance(grid, NystromGrid):
+            raise TypeError("grid must be a NystromGrid")
+        hg = grid._handle()
+        i = int(i)
+        if not 0 <= i < grid.l:
+            raise IndexError(f"bandwidth index {i} outside 0..{grid.l - 1}")
+        if pair._h is None:
+            raise ValueError("the pair has been freed")
+        idx0 = np.ascontiguousarray(idx0, dtype=np.int32).reshape(-1)
+        m = idx0.size
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape[0] != m) or (Y.ndim < 2 and Y.size != m):
+            raise ValueError("Y must have one row per entry of idx0")
+        return hg, i, idx0, m, np.asfortranarray(Y.reshape(m, -1))
+
+    @classmethod
+    def nystrom_regression(cls, grid, i, pair, Y, idx0, K, pars, sigma, noisepar="same"):
+        """:meth:`regression` over bandwidth ``i`` of a :class:`NystromGrid` (include/flgp_hip.h, "Nystrom predictor"):
+        ``pair`` is the resident pair of the training rows, ``grid.extend(i, X_train, resident=True)``, and ``idx0`` its
+        rows.  The grid is borrowed (the predictor keeps it alive); ``dims["r"]`` is 0: the weights are dense."""
+        hg, i, idx0, m, Y = cls._trained_nystrom(grid, i, pair, idx0, Y)
+        if noisepar not in ("same", "different"):
+            raise FlgpError(-3, 'predictor_nystrom_regression: noisepar must be "same" or "different"')
+        nz = np.ascontiguousarray(np.asarray(pars[1:], dtype=np.float64).reshape(-1))
+        if noisepar == "different" and nz.size != m:
+            raise ValueError('noisepar="different" needs one noise variance per training row: pars = (t, noise_1 .. noise_m)')
+        if noisepar == "same":
+            nz = nz[:1].copy()
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_predictor_nystrom_regression_create(hg, i, pair._h, int(K), _ptr(idx0), m, _ptr(Y), Y.shape[1],
+                                                                  float(pars[0]), _ptr(nz), nz.size, float(sigma), ctypes.byref(out)))
+        return cls(out, grid)
+
+    @classmethod
+    def nystrom_logit(cls, grid, i, pair, idx0, K, ts, Y, col=None, sigma11=0.0, sigma22=1e-3, tol=1e-5, max_iter=100,
+                      max_parallel=0):
+        """:meth:`logit` over bandwidth ``i`` of a :class:`NystromGrid`; ``pair`` and ``idx0`` as in
+        :meth:`nystrom_regression`."""
+        hg, i, idx0, m, Y = cls._trained_nystrom(grid, i, pair, idx0, Y)
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        B = ts.size
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per value of t")
+        its = np.zeros(max(B, 1), dtype=np.int32)
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_predictor_nystrom_logit_create(hg, i, pair._h, int(K), _ptr(idx0), m, _ptr(Y), Y.shape[1], _ptr(cols),
+                                                             _ptr(ts), B, float(sigma11), float(sigma22), float(tol), int(max_iter),
+                                                             int(max_parallel), _ptr(its), ctypes.byref(out)))
+        return cls(out, grid, its[:B].copy())
 
     @property
     def dims(self):

@@ -576,6 +576,10 @@ void nys_colsum(hipStream_t st, const double *M, int s, long ld, double *colsum)
 void nys_first_scaling(hipStream_t st, double *W, int s, double *rs, bool have_sums = false);
 void nys_second_factor(hipStream_t st, const double *W, int s, double *sd);
 void nys_vector_norms(hipStream_t st, double *V, int s, int K, const double *sd, double *nrm);
+// For the Nystrom predictor: R(1), the rows per block of the single-bandwidth extension (at most n), and whether the dot
+// products of a row block come from the GEMM (the knob nystrom_dot_gemm; always for dpad > 64, which has no register kernel)
+int nys_row_block(int s, int K, int n);
+bool nys_dots_via_gemm(int dpad);
 }  // namespace flgp
 
 // anchor side of the Nystrom bandwidth grid (include/flgp_hip.h): made and consumed in nystrom.hip

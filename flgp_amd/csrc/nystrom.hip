@@ -492,6 +492,11 @@ int check_bandwidths(const char *who, const double *a2s, int l) {
   return FLGP_OK;
 }
 
+// what the Nystrom predictor (nystrom_predictor.hip, predictor.hip) shares with the extension: its single-bandwidth row
+// block R(1) and its choice of the dot-product route
+int nys_row_block(int s, int K, int n) { return row_block(s, K, n, 1); }
+bool nys_dots_via_gemm(int dpad) { return dpad > 64 || dots_via_gemm(dpad); }
+
 }  // namespace flgp
 
 using namespace flgp;

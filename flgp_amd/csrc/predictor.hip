@@ -5,6 +5,8 @@
 // the mean, c plus the squares of its first K entries the variance.  No n_new x K array exists.  The trained operands come
 // from the bodies of the entries the handle mirrors (eigenpair.hip: regression_operands, logit_operands); the row chain up
 // to the weights is the model's (model.hip: model_rows).
+// The same handle over one bandwidth of a Nystrom grid (f-21): the anchor side is the grid's pre-scaled eigenvectors V', the
+// weights are dense and the row path is nystrom_predictor.hip's.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -13,7 +15,9 @@
 using namespace flgp;
 
 struct flgp_predictor {
-  const flgp_spectrum_model *model = nullptr;   // borrowed
+  const flgp_spectrum_model *model = nullptr;   // borrowed: a spectrum model, or
+  const flgp_nystrom_grid *grid = nullptr;      // bandwidth gi of a Nystrom grid (f-21: dense weights, nystrom_predictor.hip)
+  int gi = 0, s = 0, d = 0;
   DevBuf P, cg;                                 // s x ldp row-major, groups
   std::vector<int> iters;                       // logit: one count per group
   int K = 0, groups = 0, q = 0, kind = 0, device = 0;
@@ -112,29 +116,41 @@ int check_model(const char *who, const flgp_spectrum_model *model, const flgp_ei
   return FLGP_OK;
 }
 
-// The handle's P zeroed and the anchor side Bq (s x K, ld s) written; then fold() per chunk of operands
+// The handle's P zeroed and the anchor side B (s x K, ld s) chosen: for a model Bq, written here; for a Nystrom grid the
+// bandwidth's pre-scaled eigenvectors V', which carry every scaling already.  Then fold() per chunk of operands
 struct Folder {
   flgp_predictor *h;
   DevBuf Bq;
-  int begin(hipStream_t st, const flgp_spectrum_model *model, int K, int groups, int q, int kind) {
-    h->model = model; h->K = K; h->groups = groups; h->q = q; h->kind = kind; h->device = model->device;
+  const double *B = nullptr;
+  int shape(hipStream_t st, int s, int d, int device, int K, int groups, int q, int kind) {
+    h->s = s; h->d = d; h->K = K; h->groups = groups; h->q = q; h->kind = kind; h->device = device;
     h->ldp = ((long)groups * (K + q) + 15) / 16 * 16;
-    FLGP_TRY(h->P.alloc(sizeof(double) * (size_t)model->s * h->ldp));
+    FLGP_TRY(h->P.alloc(sizeof(double) * (size_t)s * h->ldp));
     FLGP_TRY(h->cg.alloc(sizeof(double) * (size_t)groups));
+    FLGP_HIP(hipMemsetAsync(h->P.p, 0, sizeof(double) * (size_t)s * h->ldp, st));
+    return FLGP_OK;
+  }
+  int begin(hipStream_t st, const flgp_spectrum_model *model, int K, int groups, int q, int kind) {
+    h->model = model;
+    FLGP_TRY(shape(st, model->s, model->d, model->device, K, groups, q, kind));
     FLGP_TRY(Bq.alloc(sizeof(double) * (size_t)model->s * K));
-    FLGP_HIP(hipMemsetAsync(h->P.p, 0, sizeof(double) * (size_t)model->s * h->ldp, st));
+    B = Bq.as<double>();
     return hk_rows_b(st, (const double *)model->V.p, model->s, model->s, (const double *)model->eig.p, K,
                      std::sqrt((double)model->n_fit), Bq.as<double>());
+  }
+  int begin(hipStream_t st, const flgp_nystrom_grid *grid, int i, int K, int groups, int q, int kind) {
+    h->grid = grid; h->gi = i;
+    B = grid->eigv_of(i);
+    return shape(st, grid->s, grid->d, grid->device, K, groups, q, kind);
   }
   // groups [p0, p0 + S): P(:, g (K + q) + k') = sum_k Bq(:, k) G_g(k', k), P(:, g (K + q) + K + c) = sum_k Bq(:, k) U_g(k, c); no
   // workspace, so each element is one k-ascending chain
   int fold(hipStream_t st, int p0, int S, const double *G, long sg, const double *U, long su) {
-    const int s = h->model->s, K = h->K, q = h->q;
+    const int s = h->s, K = h->K, q = h->q;
     for (int a = 0; a < S; ++a) {
       double *Pg = h->P.as<double>() + (long)(p0 + a) * (K + q);
-      FLGP_TRY(flgp_dev_gemm(st, s, K, K, 1.0, Bq.as<double>(), 1, s, G + a * sg, K, 1, 0.0, nullptr, 0, 0, Pg, h->ldp, 1, nullptr, 0));
-      FLGP_TRY(flgp_dev_gemm(st, s, q, K, 1.0, Bq.as<double>(), 1, s, U + a * su, 1, K, 0.0, nullptr, 0, 0, Pg + K, h->ldp, 1, nullptr,
-                             0));
+      FLGP_TRY(flgp_dev_gemm(st, s, K, K, 1.0, B, 1, s, G + a * sg, K, 1, 0.0, nullptr, 0, 0, Pg, h->ldp, 1, nullptr, 0));
+      FLGP_TRY(flgp_dev_gemm(st, s, q, K, 1.0, B, 1, s, U + a * su, 1, K, 0.0, nullptr, 0, 0, Pg + K, h->ldp, 1, nullptr, 0));
     }
     return FLGP_OK;
   }
@@ -156,22 +172,52 @@ int apply_block(hipStream_t st, const flgp_predictor *h, ModelRowWork &W, const 
                                  h->K, h->q, (const double *)h->cg.p, d_mean, ldm, d_var, ldv);
 }
 
-}  // namespace
+// ---- a Nystrom handle (f-21): what create checks after the mirrored entry's checks, and the row blocks of apply
+int check_grid(const char *who, const flgp_nystrom_grid *grid, int i, const flgp_eigenpair *ep) {
+  FLGP_REQUIRE(ep->K == grid->K, "%s: the pair has K = %d, the grid K = %d", who, ep->K, grid->K);
+  int dev = -1;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == grid->device && dev == ep->device, "%s: the grid lives on device %d, the pair on device %d, the current device is %d",
+               who, grid->device, ep->device, dev);
+  std::vector<double> a((size_t)ep->K), b((size_t)ep->K);
+  FLGP_HIP(hipMemcpy(a.data(), ep->values.p, sizeof(double) * a.size(), hipMemcpyDeviceToHost));
+  FLGP_HIP(hipMemcpy(b.data(), grid->values_of(i), sizeof(double) * b.size(), hipMemcpyDeviceToHost));
+  FLGP_REQUIRE(std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0,
+               "%s: the pair's values are not those of bandwidth %d (a pair from another bandwidth or grid)", who, i);
+  return FLGP_OK;
+}
 
-extern "C" int flgp_predictor_regression_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0,
-                                                int m, const double *Y, int q, double t, const double *noise, int n_noise,
-                                                double sigma, flgp_predictor **out) {
-  const char *who = "predictor_regression";
-  FLGP_REQUIRE(out, "%s: null pointer", who);
-  *out = nullptr;
-  FLGP_REQUIRE(model, "%s: null model", who);
+// rows per block: min(R(1) of the extension, model_extend_block), and the workspace of one block
+struct NystromRowWork {
+  DevBuf work;
+  size_t bytes = 0;
+  int B = 0;
+  int alloc(const flgp_predictor *h, int n_new, bool want_var) {
+    B = std::min(nys_row_block(h->s, h->K, n_new), std::min(model_block_rows(), n_new));
+    bytes = flgp_dev_nystrom_predictor_workspace(B, h->s, h->groups, h->K, h->q, want_var ? 1 : 0);
+    return work.alloc(bytes);
+  }
+};
+int nystrom_apply_block(hipStream_t st, const flgp_predictor *h, NystromRowWork &W, const double *dX, int nb, int ldx, double *d_mean,
+                        long ldm, double *d_var, long ldv) {
+  const flgp_nystrom_grid *G = h->grid;
+  return flgp_dev_nystrom_predictor_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p,
+                                         G->s, G->s, G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, h->groups, h->K,
+                                         h->q, (const double *)h->cg.p, d_mean, ldm, d_var, ldv, W.work.p, W.bytes);
+}
+
+// The create entries: one body per kind of posterior, shared by the two kinds of handle.  `check` is what the handle refuses
+// after the mirrored entry's checks (its last part the first device work), `begin` its Folder::begin.
+template <class Check, class Begin>
+int create_regression(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int q, double t,
+                      const double *noise, int n_noise, double sigma, flgp_predictor **out, Check check, Begin begin) {
   FLGP_TRY(regression_operands_check(who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma));
-  FLGP_TRY(check_model(who, model, ep));
+  FLGP_TRY(check());
   Stream st;
   FLGP_TRY(st.create());
   std::unique_ptr<flgp_predictor> h(new flgp_predictor());
   Folder F{h.get()};
-  FLGP_TRY(F.begin(st.s, model, K, 1, q, FLGP_PREDICTOR_REGRESSION));
+  FLGP_TRY(begin(F, st.s));
   const double c = noise[0] + sigma;
   FLGP_TRY(h2d(h->cg.p, &c, sizeof(double), st.s));
   FLGP_TRY(regression_operands(st.s, who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma,
@@ -183,21 +229,17 @@ extern "C" int flgp_predictor_regression_create(const flgp_spectrum_model *model
   return FLGP_OK;
 }
 
-extern "C" int flgp_predictor_logit_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0, int m,
-                                           const double *Y, int ncol, const int *col, const double *ts, int B, double sigma11,
-                                           double sigma22, double tol, int max_iter, int max_parallel, int *iters,
-                                           flgp_predictor **out) {
-  const char *who = "predictor_logit";
-  FLGP_REQUIRE(out, "%s: null pointer", who);
-  *out = nullptr;
-  FLGP_REQUIRE(model, "%s: null model", who);
+template <class Check, class Begin>
+int create_logit(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol, const int *col,
+                 const double *ts, int B, double sigma11, double sigma22, double tol, int max_iter, int max_parallel, int *iters,
+                 flgp_predictor **out, Check check, Begin begin) {
   FLGP_TRY(logit_operands_check(who, ep, K, idx0, m, Y, ncol, col, ts, B, sigma11, sigma22, max_iter));
-  FLGP_TRY(check_model(who, model, ep));
+  FLGP_TRY(check());
   Stream st;
   FLGP_TRY(st.create());
   std::unique_ptr<flgp_predictor> h(new flgp_predictor());
   Folder F{h.get()};
-  FLGP_TRY(F.begin(st.s, model, K, B, 1, FLGP_PREDICTOR_LOGIT));
+  FLGP_TRY(begin(F, st.s));
   const std::vector<double> cg((size_t)B, sigma22);
   FLGP_TRY(h2d(h->cg.p, cg.data(), sizeof(double) * (size_t)B, st.s));
   h->iters.assign((size_t)B, 0);
@@ -212,11 +254,64 @@ extern "C" int flgp_predictor_logit_create(const flgp_spectrum_model *model, con
   return FLGP_OK;
 }
 
+}  // namespace
+
+extern "C" int flgp_predictor_regression_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0,
+                                                int m, const double *Y, int q, double t, const double *noise, int n_noise,
+                                                double sigma, flgp_predictor **out) {
+  const char *who = "predictor_regression";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(model, "%s: null model", who);
+  return create_regression(who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma, out, [&] { return check_model(who, model, ep); },
+                           [&](Folder &F, hipStream_t st) { return F.begin(st, model, K, 1, q, FLGP_PREDICTOR_REGRESSION); });
+}
+
+extern "C" int flgp_predictor_logit_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0, int m,
+                                           const double *Y, int ncol, const int *col, const double *ts, int B, double sigma11,
+                                           double sigma22, double tol, int max_iter, int max_parallel, int *iters,
+                                           flgp_predictor **out) {
+  const char *who = "predictor_logit";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(model, "%s: null model", who);
+  return create_logit(who, ep, K, idx0, m, Y, ncol, col, ts, B, sigma11, sigma22, tol, max_iter, max_parallel, iters, out,
+                      [&] { return check_model(who, model, ep); },
+                      [&](Folder &F, hipStream_t st) { return F.begin(st, model, K, B, 1, FLGP_PREDICTOR_LOGIT); });
+}
+
+// the Nystrom creates: a null out, a null grid and the bandwidth index come before the mirrored entry's refusals
+extern "C" int flgp_predictor_nystrom_regression_create(const flgp_nystrom_grid *grid, int i, const flgp_eigenpair *ep, int K,
+                                                        const int *idx0, int m, const double *Y, int q, double t,
+                                                        const double *noise, int n_noise, double sigma, flgp_predictor **out) {
+  const char *who = "predictor_nystrom_regression";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(grid, "%s: null grid", who);
+  FLGP_REQUIRE(i >= 0 && i < grid->l, "%s: bandwidth %d outside 0..%d", who, i, grid->l - 1);
+  return create_regression(who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma, out, [&] { return check_grid(who, grid, i, ep); },
+                           [&](Folder &F, hipStream_t st) { return F.begin(st, grid, i, K, 1, q, FLGP_PREDICTOR_REGRESSION); });
+}
+
+extern "C" int flgp_predictor_nystrom_logit_create(const flgp_nystrom_grid *grid, int i, const flgp_eigenpair *ep, int K,
+                                                   const int *idx0, int m, const double *Y, int ncol, const int *col,
+                                                   const double *ts, int B, double sigma11, double sigma22, double tol, int max_iter,
+                                                   int max_parallel, int *iters, flgp_predictor **out) {
+  const char *who = "predictor_nystrom_logit";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(grid, "%s: null grid", who);
+  FLGP_REQUIRE(i >= 0 && i < grid->l, "%s: bandwidth %d outside 0..%d", who, i, grid->l - 1);
+  return create_logit(who, ep, K, idx0, m, Y, ncol, col, ts, B, sigma11, sigma22, tol, max_iter, max_parallel, iters, out,
+                      [&] { return check_grid(who, grid, i, ep); },
+                      [&](Folder &F, hipStream_t st) { return F.begin(st, grid, i, K, B, 1, FLGP_PREDICTOR_LOGIT); });
+}
+
 extern "C" int flgp_predictor_dims(const flgp_predictor *h, int *d, int *s, int *r, int *K, int *groups, int *q, int *kind, long *ldp) {
   FLGP_REQUIRE(h, "predictor_dims: null handle");
-  if (d) *d = h->model->d;
-  if (s) *s = h->model->s;
-  if (r) *r = h->model->r;
+  if (d) *d = h->d;
+  if (s) *s = h->s;
+  if (r) *r = h->model ? h->model->r : 0;     // a Nystrom handle's weights are dense
   if (K) *K = h->K;
   if (groups) *groups = h->groups;
   if (q) *q = h->q;
@@ -230,7 +325,7 @@ extern "C" int flgp_predictor_to_host(const flgp_predictor *h, double *P, double
   FLGP_TRY(on_handle_device(h, "predictor_to_host"));
   Stream st;
   FLGP_TRY(st.create());
-  if (P) FLGP_TRY(d2h(P, h->P.p, sizeof(double) * (size_t)h->model->s * h->ldp, st.s));
+  if (P) FLGP_TRY(d2h(P, h->P.p, sizeof(double) * (size_t)h->s * h->ldp, st.s));
   if (cg) FLGP_TRY(d2h(cg, h->cg.p, sizeof(double) * (size_t)h->groups, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));
   return FLGP_OK;
@@ -246,6 +341,15 @@ extern "C" int flgp_dev_predictor_apply(void *stream, const flgp_predictor *h, c
                n_new);
   FLGP_REQUIRE(h, "%s: null handle", who);
   FLGP_TRY(on_handle_device(h, who));
+  if (h->grid) {
+    NystromRowWork W;
+    FLGP_TRY(W.alloc(h, n_new, d_var != nullptr));
+    for (long i0 = 0; i0 < n_new; i0 += W.B)
+      FLGP_TRY(nystrom_apply_block(st, h, W, dX + i0, (int)std::min<long>(W.B, n_new - i0), ldx, d_mean ? d_mean + i0 : nullptr, ldm,
+                                   d_var ? d_var + i0 : nullptr, ldv));
+    FLGP_HIP(hipStreamSynchronize(st));
+    return FLGP_OK;
+  }
   const int B = std::min(model_block_rows(), n_new);
   ModelRowWork W;
   FLGP_TRY(W.alloc(h->model, B));
@@ -263,12 +367,15 @@ extern "C" int flgp_predictor_apply(const flgp_predictor *h, const double *X, in
   FLGP_REQUIRE(h, "%s: null handle", who);
   FLGP_TRY(on_handle_device(h, who));
   const flgp_spectrum_model *m = h->model;
-  const int B = std::min(model_block_rows(), n_new), d = m->d, gq = h->groups * h->q;
+  const int d = h->d, gq = h->groups * h->q;
   Stream st;
   FLGP_TRY(st.create());
   ModelRowWork W;
+  NystromRowWork NW;
   DevBuf dX, dmean, dvar;
-  FLGP_TRY(W.alloc(m, B));
+  if (h->grid) FLGP_TRY(NW.alloc(h, n_new, var != nullptr));
+  const int B = h->grid ? NW.B : std::min(model_block_rows(), n_new);
+  if (m) FLGP_TRY(W.alloc(m, B));
   FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
   if (mean) FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)n_new * gq));
   if (var) FLGP_TRY(dvar.alloc(sizeof(double) * (size_t)n_new * h->groups));
@@ -277,8 +384,12 @@ extern "C" int flgp_predictor_apply(const flgp_predictor *h, const double *X, in
     FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_new, sizeof(double) * (size_t)nb, d,
                               hipMemcpyHostToDevice, st.s));
     FLGP_TRY(check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points"));
-    FLGP_TRY(apply_block(st.s, h, W, dX.as<double>(), nb, nb, mean ? dmean.as<double>() + i0 : nullptr, n_new,
-                         var ? dvar.as<double>() + i0 : nullptr, n_new));
+    if (h->grid)
+      FLGP_TRY(nystrom_apply_block(st.s, h, NW, dX.as<double>(), nb, nb, mean ? dmean.as<double>() + i0 : nullptr, n_new,
+                                   var ? dvar.as<double>() + i0 : nullptr, n_new));
+    else
+      FLGP_TRY(apply_block(st.s, h, W, dX.as<double>(), nb, nb, mean ? dmean.as<double>() + i0 : nullptr, n_new,
+                           var ? dvar.as<double>() + i0 : nullptr, n_new));
   }
   if (mean) FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)n_new * gq, st.s));
   if (var) FLGP_TRY(d2h(var, dvar.p, sizeof(double) * (size_t)n_new * h->groups, st.s));
