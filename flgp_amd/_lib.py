@@ -239,6 +239,7 @@ _SIGNATURES = {
     "flgp_comm_abort": (None, [P]),
     "flgp_comm_agree": (c_int, [P, c_int, P]),
     "flgp_dev_hk_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "flgp_dev_hk_route": (c_int, [c_int, c_int, c_int, c_long]),
 }
 
 

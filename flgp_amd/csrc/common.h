@@ -234,7 +234,9 @@ struct GemmFusedReduce {
 
 // heat-kernel contraction on LDS-resident panels of V (hk.hip); d_vw holds hk_panel_vw_elems(n1, K) doubles
 bool hk_panel_applicable(int n0, int n1, int K, long ldh);
-bool hk_panel2_applicable(int n0, int n1, int K, long ldh);    // hk2.hip: the same with the k loop unrolled (K in 97..112, 193..208)
+bool hk_panel2_applicable(int n0, int n1, int K, long ldh);    // hk2.hip: the same with the k loop unrolled (K in 89..112, 185..208)
+int hk2_nks(int K);                                            // hk2.hip: the k steps of its instance for K (it pads K to 4 of them each), 0: none
+// the larger of the two layouts for every K: n1 padded to 32 rows x max(K padded to 16, hk2.hip's 4 hk2_nks(K)) columns
 size_t hk_panel_vw_elems(int n1, int K);
 // Vw(b, k) = exp(-t (1 - values_k)) V1(row(b), k), b-contiguous: d_vw[b + k n1] (gemm.hip; row(b) = d_idx1[b] or row0_1 + b)
 int hk_scale_launch(hipStream_t st, const double *d_values, int K, double t, const double *dV1, int ld1, const int *d_idx1,

@@ -824,8 +824,15 @@ int gather_rows_ld(hipStream_t st, const double *dV, int ld, const int *d_idx, i
 }  // namespace flgp
 
 extern "C" size_t flgp_dev_hk_workspace(int n0, int n1, int K, int gather0) {
-  // (the padded operand of the panel kernel, hk.hip, is the larger of the two layouts of Vw)
+  // (hk_panel_vw_elems covers the padded operand of either panel kernel, and so the plain n1 x K one of the GEMM route)
   return sizeof(double) * (hk_panel_vw_elems(n1, K) + (gather0 ? (size_t)n0 * K : 0)) + 256;
+}
+
+// which route flgp_dev_hk takes with the tuning as it stands: 2 = hk_panel2_kernel (hk2.hip), 1 = hk_panel_kernel (hk.hip),
+// 0 = the tiled GEMM (test / diagnostic entry point; launches nothing)
+extern "C" int flgp_dev_hk_route(int n0, int n1, int K, long ldh) {
+  if (hk_panel2_applicable(n0, n1, K, ldh)) return 2;
+  return hk_panel_applicable(n0, n1, K, ldh) ? 1 : 0;
 }
 
 extern "C" int flgp_dev_hk(void *stream, const double *d_values, int K, double t, const double *dV0, int ld0,

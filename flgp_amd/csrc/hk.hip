@@ -211,10 +211,12 @@ bool hk_panel_applicable(int n0, int n1, int K, long ldh) {
          (size_t)lds_max >= sizeof(double) * (size_t)nst * 16 * HP;      // (the panel in LDS)
 }
 
-// doubles of the small operand's buffer: the larger of the two layouts (hk.hip: rows padded to 16; hk2.hip: to tile pairs)
+// doubles of the small operand's buffer: the larger of the two layouts (hk.hip: rows padded to 16, K to 16; hk2.hip: rows
+// to tile pairs, K to the 4 hk2_nks(K) columns of its instance -- 104 for K = 89..96 and 208 for K = 185..192, more than
+// K padded to 16)
 size_t hk_panel_vw_elems(int n1, int K) {
-  const size_t n1p = (size_t)(n1 + 31) / 32 * 32, Kp = (size_t)(K + 15) / 16 * 16;
-  return n1p * Kp;
+  const size_t n1p = (size_t)(n1 + 31) / 32 * 32, Kp = (size_t)(K + 15) / 16 * 16, Kp2 = (size_t)4 * hk2_nks(K);
+  return n1p * (Kp > Kp2 ? Kp : Kp2);
 }
 
 // H(a, b) = sum_k V0(a, k) Vw(b, k) with Vw built from (values, V1[rows]) into d_vw (hk_panel_vw_elems doubles)
@@ -233,6 +235,8 @@ int hk_panel_launch(hipStream_t st, const double *d_values, int K, double t, con
   g.nblocks = ceil_div(n0, HP);
   const int cus = device_figures().cus;
   int grid = (cus > 0 ? cus : 256) * tuning("hk_panel_wg_per_cu", 1);
+  const int grid_cap = tuning("hk_panel_grid", 0);     // tests: a workgroup walks several panels at a small n0
+  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
   if (grid > g.nblocks) grid = g.nblocks;
   const size_t lds = sizeof(double) * (size_t)nst * 16 * HP;
   const double fl = 2.0 * (double)n0 * (double)n1 * (double)K;

@@ -292,7 +292,7 @@ __global__ void hk2_scale_kernel(const double *__restrict__ values, int K, int n
 }
 
 // K -> the instantiated number of k steps (0: none); the kernel pads K up to 4 NKS with zeros
-static int hk2_nks(int K) {
+int hk2_nks(int K) {
   const int ks = (K + 3) / 4;
   if (ks > 52 || ks < 23) return 0;
   // 47..52 steps run in the 52-step instance: it needs no scratch (an exact 50-step one kept 68 B per lane, 1 GB of HBM
@@ -329,6 +329,8 @@ int hk_panel2_launch(hipStream_t st, const double *d_values, int K, double t, co
   g.nblocks = ceil_div(n0, HP2);
   const int cus = device_figures().cus;
   int grid = cus > 0 ? cus : 256;
+  const int grid_cap = tuning("hk_panel_grid", 0);     // tests: a workgroup walks several panels at a small n0
+  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
   if (grid > g.nblocks) grid = g.nblocks;
   const size_t lds = sizeof(double) * (size_t)(2 * na + (nks - na)) * HP2 * 4;
   const double fl = 2.0 * (double)n0 * (double)n1 * (double)K;
