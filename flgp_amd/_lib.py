@@ -133,6 +133,10 @@ _SIGNATURES = {
     "flgp_predictor_nystrom_regression_create": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_double, P, c_int, c_double, P]),
     "flgp_predictor_nystrom_logit_create": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, P, c_int, c_double, c_double, c_double,
                                                     c_int, c_int, P, P]),
+    "flgp_predictor_pg_create": (c_int, [P, P, c_int, P, c_int, P, c_int, P, P, P, c_int, c_double, c_int, c_int, P, P, P]),
+    "flgp_predictor_nystrom_pg_create": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, P, P, c_int, c_double, c_int, c_int, P, P,
+                                                 P]),
+    "flgp_predictor_pg_apply": (c_int, [P, P, c_int, P, P, P, P]),
     "flgp_se_spectrum_grid": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P, c_int]),
     "flgp_lae_eigenmap": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, P, P]),
     "flgp_dev_se_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P,
@@ -168,6 +172,9 @@ _SIGNATURES = {
     "flgp_dev_spectrum_model_extend": (c_int, [P, P, P, c_int, c_int, P, c_int]),
     "flgp_dev_predictor_rows": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, c_int, c_int, P, P, c_long, P, c_long]),
     "flgp_dev_predictor_apply": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_long]),
+    "flgp_dev_predictor_pg_rows": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, P, c_long, P, c_long, P, c_long, P]),
+    "flgp_dev_pg_link": (c_int, [P, P, c_long, c_int, c_int, P, c_long, P, c_long, P]),
+    "flgp_dev_predictor_pg_apply": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_long, P, c_long, P]),
     "flgp_dev_nystrom_predictor_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "flgp_dev_nystrom_predictor_rows": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_double, P, P, c_long, c_int, c_int,
                                                 c_int, P, P, c_long, P, c_long, P, c_size_t]),

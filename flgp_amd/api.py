@@ -1160,9 +1160,12 @@ class Predictor:
     :meth:`regression` or :meth:`logit` with the arguments of ``ResidentEigenPair.regression_posterior`` /
     ``logit_posterior_batch`` that define the trained state.  The model is borrowed and must outlive the predictor.
     :meth:`nystrom_regression` and :meth:`nystrom_logit` make the same handle over one bandwidth of a
-    :class:`NystromGrid`: dense weights, the mean alone without the similarity ever going to memory."""
+    :class:`NystromGrid`: dense weights, the mean alone without the similarity ever going to memory.
+    :meth:`pg` / :meth:`pg_for_classes` (and :meth:`nystrom_pg` / :meth:`nystrom_pg_for_classes`) fold the Polya-Gamma chains
+    of ``ResidentEigenPair.test_pgbinary_batch`` instead ("Polya-Gamma predictor"): :meth:`predict` then gives the
+    probabilities and labels of unseen rows; such a handle has no variance."""
 
-    _KIND = ("regression", "logit")
+    _KIND = ("regression", "logit", "pg")
 
     def __init__(self, handle, model, iters=None):
         self._h = handle
@@ -1275,6 +1278,80 @@ class Predictor:
                                                              int(max_parallel), _ptr(its), ctypes.byref(out)))
         return cls(out, grid, its[:B].copy())
 
+    @staticmethod
+    def _chains(who, Y, ts, col, seeds, seed):
+        """ts, col, seeds of B chains with the conventions (and refusals) of ``test_pgbinary_batch``"""
+        ncol = Y.shape[1]
+        ts = np.ascontiguousarray(np.asarray(ts, dtype=np.float64).reshape(-1))
+        B = ts.size
+        if col is None and ncol != B:
+            raise FlgpError(-1, f"{who}: col may be NULL only if ncol == B (ncol={ncol}, B={B})")
+        cols = None if col is None else np.ascontiguousarray(np.asarray(col, dtype=np.int32).reshape(-1))
+        if cols is not None and cols.size != B:
+            raise ValueError("col must have one entry per value of t")
+        if seeds is None:
+            s0 = _seed(seed)
+            seeds = [(s0 + b) & 0xFFFFFFFFFFFFFFFF for b in range(B)]
+        seeds = np.ascontiguousarray(np.asarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in np.asarray(seeds, dtype=object).reshape(-1)],
+                                                dtype=np.uint64))
+        if seeds.size != B:
+            raise ValueError("seeds must have one entry per value of t")
+        return ts, cols, seeds, B
+
+    @classmethod
+    def _pg(cls, create, who, head, owner, pair, idx0, m, Y, K, ts, sigma, col, seeds, seed, N_sample, max_parallel, return_state):
+        ts, cols, seeds, B = cls._chains(who, Y, ts, col, seeds, seed)
+        om = np.zeros((m, max(B, 1)), order="F") if return_state else None
+        f = np.zeros((m, max(B, 1)), order="F") if return_state else None
+        out = ctypes.c_void_p()
+        check(create(*head, pair._h, int(K), _ptr(idx0), m, _ptr(Y), Y.shape[1], _ptr(cols), _ptr(ts), _ptr(seeds), B, float(sigma),
+                     int(N_sample), int(max_parallel), _ptr(om), _ptr(f), ctypes.byref(out)))
+        pred = cls(out, owner)
+        return (pred, {"omega": om, "f": f}) if return_state else pred
+
+    @classmethod
+    def pg(cls, model, pair, idx0, K, ts, Y, sigma, col=None, seeds=None, seed=None, N_sample=100, max_parallel=0,
+           return_state=False):
+        """The Polya-Gamma chains of ``test_pgbinary_batch`` on the training rows ``idx0`` of ``pair``, folded into the model:
+        chain b is column ``col[b]`` of ``Y`` at ``ts[b]`` with ``seeds[b]`` (default ``seed + b``).  With
+        ``return_state`` returns ``(predictor, {"omega", "f"})``, the chains' final state (m x B), the batch entry's bits."""
+        hm, idx0, m, Y = cls._trained(model, pair, idx0, Y)
+        return cls._pg(_lib.lib().flgp_predictor_pg_create, "predictor_pg", (hm,), model, pair, idx0, m, Y, K, ts, sigma, col, seeds,
+                       seed, N_sample, max_parallel, return_state)
+
+    @staticmethod
+    def _indicators(who, labels, m, J):
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.float64).reshape(-1))
+        if lab.size != m:
+            raise ValueError("labels must have one entry per row of idx0")
+        for a in range(lab.size):
+            if not (0.0 <= lab[a] < J and lab[a] == np.floor(lab[a])):
+                raise FlgpError(-1, "%s: Y[%d]=%g is not a class label in 0 .. %d" % (who, a, lab[a], J - 1))
+        return (lab[:, None] == np.arange(J)[None, :]).astype(np.float64)
+
+    @classmethod
+    def pg_for_classes(cls, model, pair, idx0, K, ts, labels, sigma, N_sample=100, seed=None):
+        """The J = ``len(ts)`` one-vs-rest chains of ``predict_logit_mult_gp_batch``: chain j is the indicator ``labels == j``
+        at ``ts[j]`` with seed + j; ``predict(X)["label"]`` is then the class of a row."""
+        J = np.asarray(ts).size
+        aug = cls._indicators("predictor_pg", labels, np.asarray(idx0).size, J)
+        return cls.pg(model, pair, idx0, K, ts, aug, sigma, seed=_seed(seed), N_sample=N_sample)
+
+    @classmethod
+    def nystrom_pg(cls, grid, i, pair, idx0, K, ts, Y, sigma, col=None, seeds=None, seed=None, N_sample=100, max_parallel=0,
+                   return_state=False):
+        """:meth:`pg` over bandwidth ``i`` of a :class:`NystromGrid`; ``pair`` and ``idx0`` as in :meth:`nystrom_regression`."""
+        hg, i, idx0, m, Y = cls._trained_nystrom(grid, i, pair, idx0, Y)
+        return cls._pg(_lib.lib().flgp_predictor_nystrom_pg_create, "predictor_nystrom_pg", (hg, i), grid, pair, idx0, m, Y, K, ts,
+                       sigma, col, seeds, seed, N_sample, max_parallel, return_state)
+
+    @classmethod
+    def nystrom_pg_for_classes(cls, grid, i, pair, idx0, K, ts, labels, sigma, N_sample=100, seed=None):
+        """:meth:`pg_for_classes` over bandwidth ``i`` of a :class:`NystromGrid`."""
+        J = np.asarray(ts).size
+        aug = cls._indicators("predictor_nystrom_pg", labels, np.asarray(idx0).size, J)
+        return cls.nystrom_pg(grid, i, pair, idx0, K, ts, aug, sigma, seed=_seed(seed), N_sample=N_sample)
+
     @property
     def dims(self):
         return {"d": self.d, "s": self.s, "r": self.r, "K": self.K, "groups": self.groups, "q": self.q, "kind": self.kind,
@@ -1287,7 +1364,8 @@ class Predictor:
         return self._h
 
     def to_host(self):
-        """``{"P": s x ldp (row-major; group g in columns g (K + q) .., its last q the mean's), "cg": groups}``."""
+        """``{"P": s x ldp (row-major; group g in columns g (K + q) .., its last q the mean's), "cg": groups}``.  A "pg"
+        handle's P holds its q columns alone (column b chain b) and its cg is 0."""
         h = self._handle()
         out = {"P": np.zeros((self.s, self.ldp)), "cg": np.zeros(self.groups)}
         check(_lib.lib().flgp_predictor_to_host(h, _ptr(out["P"]), _ptr(out["cg"])))
@@ -1307,6 +1385,24 @@ class Predictor:
         v = np.zeros((n, self.groups), order="F") if var else None
         check(_lib.lib().flgp_predictor_apply(h, _ptr(X), n, _ptr(mean), _ptr(v)))
         return {"mean": mean, "var": v}
+
+    def predict(self, X, latent=False):
+        """A "pg" handle's answer for the rows ``X`` (n_new x d): ``{"pi": n_new x B, "y": n_new x B (pi > 0.5),
+        "label": n_new (the first chain of maximal pi)}`` and, with ``latent``, ``"f"`` (pi = 1 / (1 + exp(-f)))."""
+        h = self._handle()
+        if self.kind != "pg":
+            raise FlgpError(-1, f"predictor_pg_apply: the handle is not a Polya-Gamma one (kind {self._KIND.index(self.kind)})")
+        X = _f64(X, "X")
+        if X.shape[1] != self.d:
+            raise ValueError(f"X has {X.shape[1]} columns but the model was fitted on {self.d}")
+        n = X.shape[0]
+        if n < 1:
+            raise ValueError("X must have at least one row")
+        out = {"pi": np.zeros((n, self.q), order="F"), "y": np.zeros((n, self.q), order="F"), "label": np.zeros(n)}
+        if latent:
+            out["f"] = np.zeros((n, self.q), order="F")
+        check(_lib.lib().flgp_predictor_pg_apply(h, _ptr(X), n, _ptr(out.get("f")), _ptr(out["pi"]), _ptr(out["y"]), _ptr(out["label"])))
+        return out
 
     def free(self):
         if self._h is not None:

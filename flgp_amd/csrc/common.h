@@ -543,6 +543,26 @@ int logit_operands_check(const char *who, const flgp_eigenpair *ep, int K, const
 int logit_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
                    int ncol, const int *col, const double *ts, int B, double sigma11, double tol, int max_iter, int max_parallel,
                    int *its, const OperandSink &sink);
+// The trained state of B Polya-Gamma chains (f-22): flgp_eigenpair_pg_predict_batch's chains on its own launches, both
+// sides of m = K.  pg_operands_check: that entry's refusals that concern the chains alone, in its order and wording;
+// `also`: a further variance screened with sigma (the entry's sigma_nv).  The sink receives u = L (V1^T w) (K doubles) of
+// chain p0 + a at U + a su while it is valid -- the latent mean of a row with eigenvector entries v is v . u -- and queues
+// its work on the stream it is handed: `st`, or for m <= K the stream of the pool worker that ran the chain (from that
+// worker's thread, one chain per call).  omega_out / f_out (m x B or NULL): the chains' final state, the entry's bits.
+// Synchronises `st`; a pivot <= 0 gives FLGP_ERR_NOCONV under the entry's "chain b (t=.., seed=..): .." message.
+using PgSink = std::function<int(hipStream_t st, int p0, int S, const double *U, long su)>;
+int pg_operands_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                      const int *col, const double *ts, const unsigned long long *seeds, int B, double sigma, int n_sample,
+                      double also = 0.0);
+int pg_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                const int *col, const double *ts, const unsigned long long *seeds, int B, double sigma, int n_sample,
+                int max_parallel, double *omega_out, double *f_out, const PgSink &sink);
+// The Nystrom predictor's mean-only route on a P of q columns alone (nystrom_predictor.hip; f-22): flgp_dev_nystrom_predictor_rows
+// with groups = 1 and no K columns, unchanged in its arithmetic.  The workspace is that entry's, sized by the first.
+size_t nystrom_mean_workspace(int n, int s, int q);
+int nystrom_mean_rows(hipStream_t st, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu, const double *dU,
+                      int ldu, int s, double inv_c, const double *d_w, const double *d_P, long ldp, int q, double *d_mean, long ldm,
+                      void *d_work, size_t work_bytes);
 }  // namespace flgp
 
 struct flgp_nystrom_grid;

@@ -554,9 +554,13 @@ struct LowRankB {
   }
   // out = Vl L V1^T x for any Vl (rows x K at ldl): V1 itself in C x, the new rows' V2 in a predicted mean
   int cmul(hipStream_t st, const double *Vl, long ldl, int rows, const double *x, double *out) {
-    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, x, m, u.as<double>(), work.as<double>(), we));
-    FLGP_TRY(pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>()));
+    FLGP_TRY(lvt(st, x));
     return gemm_nn(st, rows, 1, K, Vl, ldl, u.as<double>(), K, out, nullptr, 0);
+  }
+  // u = L (V1^T x): the first half of cmul
+  int lvt(hipStream_t st, const double *x) {
+    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, x, m, u.as<double>(), work.as<double>(), we));
+    return pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>());
   }
 };
 
@@ -1689,12 +1693,13 @@ int pg_eigen_binary(hipStream_t st, const flgp_eigenpair *ep, int K, double t, d
 struct PgBatch {
   PgChunk P;
   LrChunk C;
-  DevBuf vec, zb, kv, X, Q, part, flag, act, mean;
-  int planQ = 1, planU = 1, mnew = 0;
+  DevBuf vec, zb, kv, X, Q, part, flag, act;
+  int planQ = 1, planU = 1;
   size_t pe = 0;
-  long sp = 0, sm = 0;           // doubles between two slots' planes and predicted means
+  long sp = 0;                   // doubles between two slots' planes
 
-  // device bytes of one chain: X, Q, eleven m-vectors, z, u, l, ls, its planes, its mean over the new rows, flag and list entry
+  // device bytes of one chain: X, Q, eleven m-vectors, z, u, l, ls, its planes, the mnew doubles of the caller's own for it (the
+  // batch entry's mean over the new rows), flag and list entry
   static double bytes(int m, int K, int mnew) {
     int a, b;
     size_t pe;
@@ -1702,20 +1707,19 @@ struct PgBatch {
     return 8.0 * ((double)pad32((long)m * K) + pad32((long)K * K) + 11.0 * pad32(m) + pad32(2L * m + K) + 3.0 * pad32(K) +
                   pad32((long)pe) + pad32(mnew)) + 8.0;
   }
-  int alloc(hipStream_t st, int m, int K, int mnew_, int slots) {
-    mnew = mnew_;
+  int alloc(hipStream_t st, int m, int K, int slots) {
     C = LrChunk{};
     C.m = m; C.K = K; C.slots = slots;
     C.sv = pad32(m); C.sk = pad32(K); C.sx = pad32((long)m * K); C.sq = pad32((long)K * K);
     P = PgChunk{};
     P.m = m; P.K = K; P.slots = slots; P.sv = C.sv; P.sz = pad32(2L * m + K); P.ldy = m;
     LrBatch::plans(m, K, &planQ, &planU, &pe);
-    sp = pad32((long)pe); sm = pad32(mnew);
+    sp = pad32((long)pe);
     const size_t S = (size_t)slots;
     FLGP_TRY(vec.alloc(sizeof(double) * 11 * S * P.sv)); FLGP_TRY(zb.alloc(sizeof(double) * S * P.sz));
     FLGP_TRY(kv.alloc(sizeof(double) * 3 * S * C.sk));
     FLGP_TRY(X.alloc(sizeof(double) * S * C.sx)); FLGP_TRY(Q.alloc(sizeof(double) * S * C.sq));
-    FLGP_TRY(part.alloc(sizeof(double) * S * sp)); FLGP_TRY(mean.alloc(sizeof(double) * S * sm));
+    FLGP_TRY(part.alloc(sizeof(double) * S * sp));
     FLGP_TRY(flag.alloc(sizeof(int) * S)); FLGP_TRY(act.alloc(sizeof(int) * S));
     double *v = vec.as<double>(), *k = kv.as<double>();
     const size_t vs = S * P.sv, ks = S * C.sk;
@@ -1771,10 +1775,9 @@ struct PgBatch {
     FLGP_TRY(nn(st, C.m, C.V1, C.ld1, 0, C.u, P.t2, P.sv));
     return pgb_axpy3(st, P, add, P.t2, P.sigma, xin, out);
   }
-  // the chains of the chunk [p0, p0 + S): weights, the n_sample sweeps, the collapsed w (in x) and pi / y of the new rows
-  // into columns p0 .. of d_pi / d_y (d_y may be nullptr)
-  int run(hipStream_t st, const flgp_eigenpair *ep, const double *d_ts, int S, int n_sample, const Rows &r1, double sigma_nv,
-          PgMatch *match, double *d_pi, double *d_y) {
+  // the chains of the chunk [p0, p0 + S): weights, the n_sample sweeps, the collapsed w (in x) and u = L V1^T w (in C.u): the
+  // latent mean of a row with eigenvector entries v is v . u
+  int run(hipStream_t st, const flgp_eigenpair *ep, const double *d_ts, int S, int n_sample) {
     P.slots = C.slots = S;
     const int *a = act.as<int>();
     FLGP_TRY(lrb_weights(st, (const double *)ep->values.p, nullptr, C.K, d_ts, S, C.sk, C.ls, C.l));
@@ -1797,23 +1800,19 @@ struct PgBatch {
     FLGP_TRY(lrb_mul(st, C.m, P.sw, P.sv, P.r, P.sv, P.r, P.sv, a, S));
     FLGP_TRY(solve(st, P.r, P.f0));
     FLGP_TRY(pgb_axpy3(st, P, P.kappa, nullptr, -1.0, P.f0, P.x));
-    FLGP_TRY(lvt(st, P.x));                                                                    // mean = V2 L V1^T w
-    FLGP_TRY(nn(st, mnew, r1.V, r1.ld, 0, C.u, mean.as<double>(), sm));
-    return pgb_pi(st, mnew, S, mean.as<double>(), sm, sigma_nv, match ? match->ptr.as<long>() : nullptr,
-                  match ? match->list.as<int>() : nullptr, P.x, P.sv, d_pi, d_y, mnew);
+    return lvt(st, P.x);
   }
 };
 
 // what a worker of the m x m route (m <= K) owns and reuses across its chains: C, the contraction's workspace, the
-// spectrum weights, the chain's state and the mean over the new rows
+// spectrum weights and the chain's state
 struct PgDirectWorker {
-  DevBuf C, work, ls, l, mean;
+  DevBuf C, work, ls, l;
   PgChain P;
-  int alloc(int m, int K, int mnew, const Rows &r0, double sigma) {
+  int alloc(int m, int K, const Rows &r0, double sigma) {
     FLGP_TRY(C.alloc(sizeof(double) * (size_t)m * m));
     FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
     FLGP_TRY(ls.alloc(sizeof(double) * (size_t)K)); FLGP_TRY(l.alloc(sizeof(double) * (size_t)K));
-    FLGP_TRY(mean.alloc(sizeof(double) * (size_t)mnew));
     P.route = PG_DIRECT; P.C = C.as<double>();
     P.L.sigma = sigma; P.L.V1 = r0.V; P.L.ld1 = r0.ld; P.L.l = l.as<double>(); P.L.ls = ls.as<double>();
     return P.alloc(m, K);
@@ -1954,70 +1953,49 @@ extern "C" int flgp_eigenpair_pg_predict_multiclass(const flgp_eigenpair *ep, in
   return pg_verdict(st.s, flag.p, who);
 }
 
-// B chains in one call: chain b is column col[b] of Y at ts[b] with seeds[b], and its columns of the
-// outputs are flgp_eigenpair_pg_predict's, bit for bit, whatever shares the call.  m > K: chunks of chains in the same
-// launches (PgBatch); m <= K: the chains dealt to pool workers, each with a PgChain of its own on the m x m route.
-extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
-                                               const int *col, const double *ts, const unsigned long long *seeds, int B,
-                                               double sigma, double sigma_nv, const int *idx1, int mnew, int n_sample,
-                                               int max_parallel, double *pi_pred, double *y_pred, double *argmax_out,
-                                               double *omega_out, double *f_out) {
-  const char *who = "eigenpair_pg_predict_batch";
-  FLGP_REQUIRE(idx0 && Y && ts && seeds && idx1 && pi_pred, "%s: null pointer", who);
-  FLGP_REQUIRE(B >= 1 && m >= 1 && mnew >= 1 && ncol >= 1, "%s: bad shape (B=%d, m=%d, m_new=%d, ncol=%d)", who, B, m, mnew, ncol);
-  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
-  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
-  std::vector<int> cols((size_t)B);
-  for (int b = 0; b < B; ++b) {
-    const int c = cols[(size_t)b] = col ? col[b] : b;
-    FLGP_REQUIRE(c >= 0 && c < ncol, "chain %d (t=%g, seed=%llu): %s: col=%d is outside [0, ncol=%d)", b, ts[b], seeds[b], who, c, ncol);
-    FLGP_REQUIRE(std::isfinite(ts[b]), "chain %d (t=%g, seed=%llu): %s: t must be finite", b, ts[b], seeds[b], who);
-  }
-  for (int c = 0; c < ncol; ++c)
-    for (int a = 0; a < m; ++a) {
-      const double y = Y[(size_t)c * m + a];
-      FLGP_REQUIRE(y >= 0.0 && y <= 1.0, "%s: Y[%d, %d]=%g is outside [0, 1]", who, a, c, y);
-    }
-  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(sigma_nv), "%s: sigma must be finite and >= 0", who);
-  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
-  Rows r0, r1;
-  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
-  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+// ---- B chains in one call and their trained state for the predictor (f-22) ----------------------------------
+// The chains of flgp_eigenpair_pg_predict_batch up to u = L (V1^T w) at the final omega: m > K in chunks of chains sharing
+// every launch (PgBatch), m <= K dealt to pool workers, each with a PgChain of its own on the m x m route.  What follows u
+// is the caller's: the batch entry multiplies the new rows' V2 onto it, the predictor folds it into its anchor side.
+namespace {
+// what a sink sees of the chains [p0, p0 + S) while it is valid: u of chain p0 + a at U + a su and its collapsed w at w + a sw.
+// `act` is the slot list of the batched launches (m > K); it is nullptr on the pool route, where S = 1 and `st` is the
+// worker's stream
+struct PgChunkOut {
+  hipStream_t st;
+  int p0, S;
+  const double *U; long su;
+  const double *w; long sw;
+  const int *act;
+};
+using PgChunkSink = std::function<int(const PgChunkOut &)>;
 
-  Stream st;
-  FLGP_TRY(st.create());
-  const size_t vb = sizeof(double) * (size_t)m, nb = sizeof(double) * (size_t)mnew;
-  DevBuf dY, dpi, dy, dlab, dflag;
-  FLGP_TRY(upload(dY, Y, vb * ncol, st.s));
-  FLGP_TRY(dpi.alloc(nb * B));
-  if (y_pred) FLGP_TRY(dy.alloc(nb * B));
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  FLGP_TRY(r1.gather(st.s, ep, K));
-  PgMatch match;
-  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, idx0, m, idx1, mnew));
-  PgMatch *mt = sigma_nv != 0.0 ? &match : nullptr;
-  std::vector<int> flags((size_t)B, 0);       // one pivot flag per chain, read after the chain's sweeps
+// r0 gathered, dY on the device, cols resolved.  sink_doubles: the doubles per chain of the caller's own buffers, for the
+// planning of the chunk / the workers alone.  flags: one pivot flag per chain, valid once `st` is synchronised (the caller's
+// verdict: pg_flags_verdict).  A worker's failure comes back worded "chain b (t=.., seed=..): ..".
+int pg_chains(hipStream_t st, const flgp_eigenpair *ep, int K, const Rows &r0, const double *dY, const int *cols, const double *ts,
+              const unsigned long long *seeds, int B, double sigma, int n_sample, int max_parallel, int sink_doubles,
+              double *omega_out, double *f_out, int *flags, DevBuf &dflag, const PgChunkSink &sink) {
+  const int m = r0.m;
+  const size_t vb = sizeof(double) * (size_t)m;
   if (m <= K) {
     FLGP_TRY(dflag.alloc(sizeof(int) * (size_t)B));
-    FLGP_HIP(hipMemsetAsync(dflag.p, 0, sizeof(int) * (size_t)B, st.s));
-    FLGP_HIP(hipStreamSynchronize(st.s));      // the workers' streams start from the gathered rows and the cleared flags
+    FLGP_HIP(hipMemsetAsync(dflag.p, 0, sizeof(int) * (size_t)B, st));
+    FLGP_HIP(hipStreamSynchronize(st));        // the workers' streams start from the gathered rows and the cleared flags
     DevicePool pool;
-    FLGP_TRY(pool.plan(max_parallel > 0 ? max_parallel : std::min(B, 4), B, PgDirectWorker::bytes(m, K, mnew)));
+    FLGP_TRY(pool.plan(max_parallel > 0 ? max_parallel : std::min(B, 4), B, PgDirectWorker::bytes(m, K, sink_doubles)));
     const PoolFailure bad = pool.run<PgDirectWorker>(
-        st.s, B, [&](PgDirectWorker &W) { return W.alloc(m, K, mnew, r0, sigma); },
+        st, B, [&](PgDirectWorker &W) { return W.alloc(m, K, r0, sigma); },
         [&](hipStream_t ws, PgDirectWorker &W, int b) -> int {
           PgChain &P = W.P;
           P.flag = P.L.flag = dflag.as<int>() + b;
           FLGP_TRY(gpr_weights(ws, (const double *)ep->values.p, K, ts[b], W.ls.as<double>(), W.l.as<double>()));
           FLGP_TRY(hk(ws, ep, K, ts[b], r0, r0, W.C.as<double>(), W.work.as<double>()));
           if (sigma != 0.0) FLGP_TRY(gpr_add_diag(ws, W.C.as<double>(), m, sigma));
-          FLGP_TRY(P.run(ws, dY.as<double>() + (size_t)cols[(size_t)b] * m, n_sample, seeds[b]));
+          FLGP_TRY(P.run(ws, dY + (size_t)cols[b] * m, n_sample, seeds[b]));
           FLGP_TRY(P.collapsed_w(ws));
-          FLGP_TRY(P.L.cmul(ws, r1.V, r1.ld, mnew, P.x.as<double>(), W.mean.as<double>()));
-          FLGP_TRY(pg_pi(ws, mnew, W.mean.as<double>(), sigma_nv, mt ? mt->ptr.as<long>() : nullptr,
-                         mt ? mt->list.as<int>() : nullptr, P.x.as<double>(), dpi.as<double>() + (size_t)b * mnew, 1,
-                         y_pred ? dy.as<double>() + (size_t)b * mnew : nullptr));
+          FLGP_TRY(P.L.lvt(ws, P.x.as<double>()));
+          FLGP_TRY(sink(PgChunkOut{ws, b, 1, P.L.u.as<double>(), K, P.x.as<double>(), m, nullptr}));
           if (omega_out) FLGP_TRY(d2h(omega_out + (size_t)b * m, P.omega.p, vb, ws));
           if (f_out) FLGP_TRY(d2h(f_out + (size_t)b * m, P.f.p, vb, ws));
           FLGP_HIP(hipStreamSynchronize(ws));    // the worker's buffers take the next chain
@@ -2027,37 +2005,142 @@ extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, 
       set_error("chain %d (t=%g, seed=%llu): %s", bad.item, ts[bad.item], seeds[bad.item], bad.message.c_str());
       return bad.status;
     }
-    FLGP_TRY(d2h(flags.data(), dflag.p, sizeof(int) * (size_t)B, st.s));
-  } else {
-    DevBuf dcol, dts, dseed;
-    FLGP_TRY(upload(dcol, cols.data(), sizeof(int) * (size_t)B, st.s));
-    FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st.s));
-    FLGP_TRY(upload(dseed, seeds, sizeof(unsigned long long) * (size_t)B, st.s));
-    // the chunk: max_parallel chains, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of the
-    // free memory
-    const int want = max_parallel > 0 ? max_parallel : B;
-    size_t free_b = 0, total_b = 0;
-    if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
-    const int chunk = std::min(plan_workers(want, B, (double)free_b, PgBatch::bytes(m, K, mnew)), GEMM_BATCH_MAX);
-    PgBatch L;
-    FLGP_TRY(L.alloc(st.s, m, K, mnew, chunk));
-    L.P.Y = dY.as<double>(); L.P.sigma = sigma;
-    L.C.V1 = r0.V; L.C.ld1 = r0.ld; L.C.sigma = sigma;
-    for (int p0 = 0; p0 < B; p0 += chunk) {
-      const int S = std::min(chunk, B - p0);
-      L.P.ycol = dcol.as<int>() + p0; L.P.seed = dseed.as<unsigned long long>() + p0;
-      FLGP_TRY(L.run(st.s, ep, dts.as<double>() + p0, S, n_sample, r1, sigma_nv, mt, dpi.as<double>() + (size_t)p0 * mnew,
-                     y_pred ? dy.as<double>() + (size_t)p0 * mnew : nullptr));
-      // the slots' omega and f, packed: m x S from rows sv apart
-      if (omega_out)
-        FLGP_HIP(hipMemcpy2DAsync(omega_out + (size_t)p0 * m, vb, L.P.omega, sizeof(double) * (size_t)L.P.sv, vb, (size_t)S,
-                                  hipMemcpyDeviceToHost, st.s));
-      if (f_out)
-        FLGP_HIP(hipMemcpy2DAsync(f_out + (size_t)p0 * m, vb, L.P.f, sizeof(double) * (size_t)L.P.sv, vb, (size_t)S,
-                                  hipMemcpyDeviceToHost, st.s));
-      FLGP_TRY(d2h(flags.data() + p0, L.C.flag, sizeof(int) * (size_t)S, st.s));
-    }
+    return d2h(flags, dflag.p, sizeof(int) * (size_t)B, st);
   }
+  DevBuf dcol, dts, dseed;
+  FLGP_TRY(upload(dcol, cols, sizeof(int) * (size_t)B, st));
+  FLGP_TRY(upload(dts, ts, sizeof(double) * (size_t)B, st));
+  FLGP_TRY(upload(dseed, seeds, sizeof(unsigned long long) * (size_t)B, st));
+  // the chunk: max_parallel chains, or (<= 0) all of them; where that is more than one, no more than fit into 90 % of the
+  // free memory
+  const int want = max_parallel > 0 ? max_parallel : B;
+  size_t free_b = 0, total_b = 0;
+  if (plan_workers(want, B, 0.0, 0.0) > 1) FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  const int chunk = std::min(plan_workers(want, B, (double)free_b, PgBatch::bytes(m, K, sink_doubles)), GEMM_BATCH_MAX);
+  PgBatch L;
+  FLGP_TRY(L.alloc(st, m, K, chunk));
+  L.P.Y = dY; L.P.sigma = sigma;
+  L.C.V1 = r0.V; L.C.ld1 = r0.ld; L.C.sigma = sigma;
+  for (int p0 = 0; p0 < B; p0 += chunk) {
+    const int S = std::min(chunk, B - p0);
+    L.P.ycol = dcol.as<int>() + p0; L.P.seed = dseed.as<unsigned long long>() + p0;
+    FLGP_TRY(L.run(st, ep, dts.as<double>() + p0, S, n_sample));
+    FLGP_TRY(sink(PgChunkOut{st, p0, S, L.C.u, L.C.sk, L.P.x, L.P.sv, L.act.as<int>()}));
+    // the slots' omega and f, packed: m x S from rows sv apart
+    if (omega_out)
+      FLGP_HIP(hipMemcpy2DAsync(omega_out + (size_t)p0 * m, vb, L.P.omega, sizeof(double) * (size_t)L.P.sv, vb, (size_t)S,
+                                hipMemcpyDeviceToHost, st));
+    if (f_out)
+      FLGP_HIP(hipMemcpy2DAsync(f_out + (size_t)p0 * m, vb, L.P.f, sizeof(double) * (size_t)L.P.sv, vb, (size_t)S,
+                                hipMemcpyDeviceToHost, st));
+    FLGP_TRY(d2h(flags + p0, L.C.flag, sizeof(int) * (size_t)S, st));
+  }
+  return FLGP_OK;
+}
+
+int pg_flags_verdict(const char *who, const int *flags, const double *ts, const unsigned long long *seeds, int B) {
+  for (int b = 0; b < B; ++b)
+    if (flags[b]) {
+      const int rc = pg_pivot_error(flags[b], who);
+      const std::string msg(flgp_last_error());
+      set_error("chain %d (t=%g, seed=%llu): %s", b, ts[b], seeds[b], msg.c_str());
+      return rc;
+    }
+  return FLGP_OK;
+}
+}  // namespace
+
+// the batch entry's refusals that concern the trained state alone, in its order and wording; `also` is a further variance
+// screened with sigma (the batch entry's sigma_nv)
+int flgp::pg_operands_check(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                            const int *col, const double *ts, const unsigned long long *seeds, int B, double sigma, int n_sample,
+                            double also) {
+  FLGP_REQUIRE(idx0 && Y && ts && seeds, "%s: null pointer", who);
+  FLGP_REQUIRE(B >= 1 && m >= 1 && ncol >= 1, "%s: bad shape (B=%d, m=%d, ncol=%d)", who, B, m, ncol);
+  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
+  FLGP_REQUIRE(col || ncol == B, "%s: col may be NULL only if ncol == B (ncol=%d, B=%d)", who, ncol, B);
+  for (int b = 0; b < B; ++b) {
+    const int c = col ? col[b] : b;
+    FLGP_REQUIRE(c >= 0 && c < ncol, "chain %d (t=%g, seed=%llu): %s: col=%d is outside [0, ncol=%d)", b, ts[b], seeds[b], who, c, ncol);
+    FLGP_REQUIRE(std::isfinite(ts[b]), "chain %d (t=%g, seed=%llu): %s: t must be finite", b, ts[b], seeds[b], who);
+  }
+  for (int c = 0; c < ncol; ++c)
+    for (int a = 0; a < m; ++a) {
+      const double y = Y[(size_t)c * m + a];
+      FLGP_REQUIRE(y >= 0.0 && y <= 1.0, "%s: Y[%d, %d]=%g is outside [0, 1]", who, a, c, y);
+    }
+  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(also), "%s: sigma must be finite and >= 0", who);
+  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
+  Rows r0;
+  return r0.check(ep, idx0, m, who, "idx0");
+}
+
+int flgp::pg_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y,
+                      int ncol, const int *col, const double *ts, const unsigned long long *seeds, int B, double sigma,
+                      int n_sample, int max_parallel, double *omega_out, double *f_out, const PgSink &sink) {
+  Rows r0;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  std::vector<int> cols((size_t)B), flags((size_t)B, 0);
+  for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
+  DevBuf dY, dflag;
+  FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * ncol, st));
+  FLGP_TRY(r0.gather(st, ep, K));
+  FLGP_TRY(pg_chains(st, ep, K, r0, dY.as<double>(), cols.data(), ts, seeds, B, sigma, n_sample, max_parallel, 0, omega_out, f_out,
+                     flags.data(), dflag, [&](const PgChunkOut &o) { return sink(o.st, o.p0, o.S, o.U, o.su); }));
+  FLGP_HIP(hipStreamSynchronize(st));
+  return pg_flags_verdict(who, flags.data(), ts, seeds, B);
+}
+
+// Chain b is column col[b] of Y at ts[b] with seeds[b], and its columns of the outputs are flgp_eigenpair_pg_predict's, bit
+// for bit, whatever shares the call.
+extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
+                                               const int *col, const double *ts, const unsigned long long *seeds, int B,
+                                               double sigma, double sigma_nv, const int *idx1, int mnew, int n_sample,
+                                               int max_parallel, double *pi_pred, double *y_pred, double *argmax_out,
+                                               double *omega_out, double *f_out) {
+  const char *who = "eigenpair_pg_predict_batch";
+  // what concerns idx1, m_new and pi_pred stands where it stood among the refusals: the null pointers and the shape come first
+  FLGP_REQUIRE(idx0 && Y && ts && seeds && idx1 && pi_pred, "%s: null pointer", who);
+  FLGP_REQUIRE(B >= 1 && m >= 1 && mnew >= 1 && ncol >= 1, "%s: bad shape (B=%d, m=%d, m_new=%d, ncol=%d)", who, B, m, mnew, ncol);
+  FLGP_TRY(pg_operands_check(who, ep, K, idx0, m, Y, ncol, col, ts, seeds, B, sigma, n_sample, sigma_nv));
+  std::vector<int> cols((size_t)B);
+  for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+
+  Stream st;
+  FLGP_TRY(st.create());
+  const size_t vb = sizeof(double) * (size_t)m, nb = sizeof(double) * (size_t)mnew;
+  const long sm = pad32(mnew);                 // doubles between two chains' means over the new rows
+  DevBuf dY, dpi, dy, dlab, dflag, dmean;
+  FLGP_TRY(upload(dY, Y, vb * ncol, st.s));
+  FLGP_TRY(dpi.alloc(nb * B));
+  if (y_pred) FLGP_TRY(dy.alloc(nb * B));
+  FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)sm * B));
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  PgMatch match;
+  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, idx0, m, idx1, mnew));
+  const long *mptr = sigma_nv != 0.0 ? match.ptr.as<long>() : nullptr;
+  const int *mlist = sigma_nv != 0.0 ? match.list.as<int>() : nullptr;
+  std::vector<int> flags((size_t)B, 0);       // one pivot flag per chain, read after the chain's sweeps
+  // mean = V2 u, then pi = logistic(mean + sigma_nv sum_{idx0_j = idx1_i} w_j) into the chains' columns
+  FLGP_TRY(pg_chains(st.s, ep, K, r0, dY.as<double>(), cols.data(), ts, seeds, B, sigma, n_sample, max_parallel, mnew, omega_out,
+                     f_out, flags.data(), dflag, [&](const PgChunkOut &o) -> int {
+                       double *mean = dmean.as<double>() + (size_t)o.p0 * sm;
+                       double *pi = dpi.as<double>() + (size_t)o.p0 * mnew;
+                       double *y = y_pred ? dy.as<double>() + (size_t)o.p0 * mnew : nullptr;
+                       if (!o.act) {
+                         FLGP_TRY(gemm_nn(o.st, mnew, 1, K, r1.V, r1.ld, o.U, K, mean, nullptr, 0));
+                         return pg_pi(o.st, mnew, mean, sigma_nv, mptr, mlist, o.w, pi, 1, y);
+                       }
+                       const GemmBatch gb{o.S, o.act, 0, o.su, sm, 0, 0};
+                       FLGP_TRY(gemm_launch(o.st, mnew, 1, K, 1.0, r1.V, 1, r1.ld, o.U, 1, K, 0.0, nullptr, 0, 0, mean, 1, mnew,
+                                            nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0, nullptr, &gb));
+                       return pgb_pi(o.st, mnew, o.S, mean, sm, sigma_nv, mptr, mlist, o.w, o.sw, pi, y, mnew);
+                     }));
   if (argmax_out) {
     FLGP_TRY(dlab.alloc(nb));
     FLGP_TRY(pg_argmax(st.s, mnew, B, dpi.as<double>(), dlab.as<double>()));
@@ -2066,14 +2149,7 @@ extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, 
   FLGP_TRY(d2h(pi_pred, dpi.p, nb * B, st.s));
   if (y_pred) FLGP_TRY(d2h(y_pred, dy.p, nb * B, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));
-  for (int b = 0; b < B; ++b)
-    if (flags[(size_t)b]) {
-      const int rc = pg_pivot_error(flags[(size_t)b], who);
-      const std::string msg(flgp_last_error());
-      set_error("chain %d (t=%g, seed=%llu): %s", b, ts[b], seeds[b], msg.c_str());
-      return rc;
-    }
-  return FLGP_OK;
+  return pg_flags_verdict(who, flags.data(), ts, seeds, B);
 }
 
 // ---- regression training objective for B (pair, x) problems in one call -------------------------------

@@ -210,6 +210,11 @@ struct NpLayout {
 
 }  // namespace flgp
 
+static int np_rows_body(const char *who, hipStream_t st, const double *dX, int n, int ldx, int d, int dpad, const double *dUt,
+                        const double *duu, const double *dU, int ldu, int s, double inv_c, const double *d_w, const double *d_P,
+                        long ldp, int groups, int K, int q, const double *d_cg, double *d_mean, long ldm, double *d_var, long ldv,
+                        void *d_work, size_t work_bytes);
+
 extern "C" size_t flgp_dev_nystrom_predictor_workspace(int n, int s, int groups, int K, int q, int want_var) {
   if (n < 1 || s < 1 || groups < 1 || K < 1 || q < 0) return 0;
   return sizeof(double) * NpLayout(n, s, groups, K, q, want_var).total;
@@ -234,10 +239,18 @@ extern "C" int flgp_dev_nystrom_predictor_rows(void *stream, const double *dX, i
   FLGP_REQUIRE(ldx >= n && ldu >= s && (!d_mean || ldm >= n) && (!d_var || ldv >= n),
                "%s: a leading dimension is too small (n=%d, s=%d)", who, n, s);
   FLGP_REQUIRE((long)groups * ((long)K + q) < (1L << 31) && (long)n * s < (1L << 40), "%s: the operand is too wide", who);
+  return np_rows_body(who, (hipStream_t)stream, dX, n, ldx, d, dpad, dUt, duu, dU, ldu, s, inv_c, d_w, d_P, ldp, groups, K, q, d_cg, d_mean,
+                      ldm, d_var, ldv, d_work, work_bytes);
+}
+
+// what follows the refusals; K = 0 is a P of mean columns alone (nystrom_mean_rows)
+static int np_rows_body(const char *who, hipStream_t st, const double *dX, int n, int ldx, int d, int dpad, const double *dUt,
+                        const double *duu, const double *dU, int ldu, int s, double inv_c, const double *d_w, const double *d_P,
+                        long ldp, int groups, int K, int q, const double *d_cg, double *d_mean, long ldm, double *d_var, long ldv,
+                        void *d_work, size_t work_bytes) {
   const NpLayout L(n, s, groups, K, q, d_var != nullptr);
   FLGP_REQUIRE(work_bytes >= sizeof(double) * L.total, "%s: the workspace holds %zu bytes, %zu are needed", who, work_bytes,
                sizeof(double) * L.total);
-  hipStream_t st = (hipStream_t)stream;
   double *W = (double *)d_work;
   double *Z = W + L.Z, *p1 = W + L.p1, *p2 = W + L.p2, *pm = W + L.pm, *fac = W + L.fac, *xx = W + L.xx, *Pm = W + L.Pm, *T = W + L.T;
   const int gq = d_mean ? groups * q : 0, npass = d_mean ? L.npass : 0, nchunk = L.nchunk, w = K + q;
@@ -291,4 +304,22 @@ extern "C" int flgp_dev_nystrom_predictor_rows(void *stream, const double *dX, i
     }
   }
   return FLGP_OK;
+}
+
+size_t flgp::nystrom_mean_workspace(int n, int s, int q) {
+  if (n < 1 || s < 1 || q < 1) return 0;
+  return sizeof(double) * NpLayout(n, s, 1, 0, q, 0).total;
+}
+
+int flgp::nystrom_mean_rows(hipStream_t st, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu,
+                            const double *dU, int ldu, int s, double inv_c, const double *d_w, const double *d_P, long ldp, int q,
+                            double *d_mean, long ldm, void *d_work, size_t work_bytes) {
+  const char *who = "nystrom_mean_rows";
+  FLGP_REQUIRE(dX && dUt && duu && dU && d_w && d_P && d_mean && d_work, "%s: null pointer", who);
+  const int dpad = flgp_dev_anchor_dpad(d);
+  FLGP_REQUIRE(dpad > 0 && d >= 1, "%s: kernels are built for 1 <= d <= %d (got %d)", who, FLGP_DMAX, d);
+  FLGP_REQUIRE(n >= 1 && s >= 1 && q >= 1 && ldp >= q && ldx >= n && ldu >= s && ldm >= n && (long)n * s < (1L << 40),
+               "%s: bad shape (n=%d, s=%d, q=%d)", who, n, s, q);
+  return np_rows_body(who, st, dX, n, ldx, d, dpad, dUt, duu, dU, ldu, s, inv_c, d_w, d_P, ldp, 1, 0, q, nullptr, d_mean, ldm, nullptr, 0,
+                      d_work, work_bytes);
 }

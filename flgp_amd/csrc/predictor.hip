@@ -7,6 +7,8 @@
 // to the weights is the model's (model.hip: model_rows).
 // The same handle over one bandwidth of a Nystrom grid (f-21): the anchor side is the grid's pre-scaled eigenvectors V', the
 // weights are dense and the row path is nystrom_predictor.hip's.
+// A Polya-Gamma handle (f-22) keeps the B mean columns alone, P(:, b) = B u_b with u_b = L (V1^T w_b) of chain b (eigenpair.hip:
+// pg_operands): a served row's latent is a_i P, its pi, y and label the link's (predictor_pg_rows_kernel, pg_link_kernel).
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -75,7 +77,107 @@ __global__ __launch_bounds__(PRED_WAVES * 64) void predictor_rows_kernel(const i
   }
 }
 
+// The Polya-Gamma handle's rows (f-22): P holds the B mean columns alone, column b chain b.  One wave per row; lane l of
+// chunk c owns chain b = 64 c + l: f is the chain over a ascending, multiply then add, from 0.0 (predictor_rows_kernel's
+// mean column), pi = 1 / (1 + exp(-f)) and y = (pi > 0.5) are pg_pi_kernel's expressions.  label: every lane keeps the
+// (largest pi, its first chain) of its own chunks -- a later chunk replaces only on a strictly larger value -- and six
+// butterfly steps combine (value, chain) pairs: the larger value wins, at equal values the lower chain, so every lane ends
+// with the first chain of maximal pi, pg_argmax_kernel's answer (a NaN is never larger; a NaN in chain 0 gives 0 as there).
+// Any output may be nullptr; the exponential is skipped where f alone is wanted.
+__global__ __launch_bounds__(PRED_WAVES * 64) void predictor_pg_rows_kernel(const int *__restrict__ ell_idx,
+                                                                             const double *__restrict__ ell_val, int n, int r,
+                                                                             const double *__restrict__ P, long ldp, int B,
+                                                                             double *__restrict__ f, long ldf,
+                                                                             double *__restrict__ pi, long ldpi,
+                                                                             double *__restrict__ y, long ldy,
+                                                                             double *__restrict__ label) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c_hi = (B + 63) / 64;
+  const bool link = pi || y || label;
+  for (long i = (long)blockIdx.x * PRED_WAVES + wave; i < n; i += (long)gridDim.x * PRED_WAVES) {
+    int my_idx = 0;
+    double my_val = 0.0;
+    if (lane < r) { my_idx = ell_idx[i * r + lane]; my_val = ell_val[i * r + lane]; }
+    double best = -1.0, first = 0.0;            // pi >= 0: any chain beats a lane without one
+    int loc = 0x7fffffff;
+    for (int c = 0; c < c_hi; ++c) {
+      const int b = c * 64 + lane;
+      const bool on = b < B;
+      double z = 0.0;
+      for (int a = 0; a < r; ++a) {
+        const long ja = __builtin_amdgcn_readlane(my_idx, a);
+        const double va = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_val), a),
+                                           __builtin_amdgcn_readlane(__double2loint(my_val), a));
+        if (on) z = z + va * P[ja * ldp + b];
+      }
+      if (on) {
+        if (f) f[(long)b * ldf + i] = z;
+        if (link) {
+          const double v = 1.0 / (1.0 + exp(-z));
+          if (pi) pi[(long)b * ldpi + i] = v;
+          if (y) y[(long)b * ldy + i] = v > 0.5 ? 1.0 : 0.0;
+          if (c == 0) first = v;
+          if (v > best) { best = v; loc = b; }
+        }
+      }
+    }
+    if (label) {
+      for (int o = 32; o >= 1; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int ol = __shfl_xor(loc, o);
+        if (ob > best || (ob == best && ol < loc)) { best = ob; loc = ol; }
+      }
+      if (lane == 0) label[i] = (first != first || loc == 0x7fffffff) ? 0.0 : (double)loc;
+    }
+  }
+}
+
+// the same three expressions on a latent that exists: a thread per row, the chains ascending (pg_argmax_kernel's loop)
+__global__ void pg_link_kernel(long n, int B, const double *__restrict__ f, long ldf, double *__restrict__ pi, long ldpi,
+                               double *__restrict__ y, long ldy, double *__restrict__ label) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double best = 0.0;
+  int loc = 0;
+  for (int b = 0; b < B; ++b) {
+    const double v = 1.0 / (1.0 + exp(-f[(long)b * ldf + i]));
+    if (pi) pi[(long)b * ldpi + i] = v;
+    if (y) y[(long)b * ldy + i] = v > 0.5 ? 1.0 : 0.0;
+    if (b == 0) best = v;
+    else if (v > best) { best = v; loc = b; }
+  }
+  if (label) label[i] = (double)loc;
+}
+
 }  // namespace flgp
+
+extern "C" int flgp_dev_predictor_pg_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *d_P,
+                                          long ldp, int s, int B, double *d_f, long ldf, double *d_pi, long ldpi, double *d_y, long ldy,
+                                          double *d_label) {
+  const char *who = "predictor_pg_rows";
+  FLGP_REQUIRE(d_ell_idx && d_ell_val && d_P, "%s: null pointer", who);
+  FLGP_REQUIRE(d_f || d_pi || d_y || d_label, "%s: null pointer (no output is wanted)", who);
+  FLGP_REQUIRE(n >= 1 && r >= 1 && r <= FLGP_RMAX && s >= 1 && B >= 1, "%s: bad shape (n=%d, r=%d, s=%d, B=%d)", who, n, r, s, B);
+  FLGP_REQUIRE(ldp >= B, "%s: ldp=%ld is below B = %d", who, ldp, B);
+  FLGP_REQUIRE((!d_f || ldf >= n) && (!d_pi || ldpi >= n) && (!d_y || ldy >= n), "%s: a leading dimension is below n = %d", who, n);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("predictor_pg_rows", st, 2.0 * (double)n * r * B);
+  hipLaunchKernelGGL(predictor_pg_rows_kernel, dim3(std::min(ceil_div(n, PRED_WAVES), 1 << 20)), dim3(PRED_WAVES * 64), 0, st, d_ell_idx,
+                     d_ell_val, n, r, d_P, ldp, B, d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
+  return check_launch("predictor_pg_rows_kernel");
+}
+
+extern "C" int flgp_dev_pg_link(void *stream, const double *d_f, long ldf, int n, int B, double *d_pi, long ldpi, double *d_y, long ldy,
+                                double *d_label) {
+  const char *who = "pg_link";
+  FLGP_REQUIRE(d_f, "%s: null pointer", who);
+  FLGP_REQUIRE(d_pi || d_y || d_label, "%s: null pointer (no output is wanted)", who);
+  FLGP_REQUIRE(n >= 1 && B >= 1, "%s: bad shape (n=%d, B=%d)", who, n, B);
+  FLGP_REQUIRE(ldf >= n && (!d_pi || ldpi >= n) && (!d_y || ldy >= n), "%s: a leading dimension is below n = %d", who, n);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(pg_link_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (long)n, B, d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
+  return check_launch("pg_link_kernel");
+}
 
 extern "C" int flgp_dev_predictor_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r,
                                        const double *d_P, long ldp, int s, int groups, int K, int q, const double *d_cg,
@@ -124,9 +226,11 @@ struct Folder {
   const double *B = nullptr;
   int shape(hipStream_t st, int s, int d, int device, int K, int groups, int q, int kind) {
     h->s = s; h->d = d; h->K = K; h->groups = groups; h->q = q; h->kind = kind; h->device = device;
-    h->ldp = ((long)groups * (K + q) + 15) / 16 * 16;
+    // a Polya-Gamma handle's P holds the q mean columns alone
+    h->ldp = ((kind == FLGP_PREDICTOR_PG ? (long)q : (long)groups * (K + q)) + 15) / 16 * 16;
     FLGP_TRY(h->P.alloc(sizeof(double) * (size_t)s * h->ldp));
     FLGP_TRY(h->cg.alloc(sizeof(double) * (size_t)groups));
+    FLGP_HIP(hipMemsetAsync(h->cg.p, 0, sizeof(double) * (size_t)groups, st));
     FLGP_HIP(hipMemsetAsync(h->P.p, 0, sizeof(double) * (size_t)s * h->ldp, st));
     return FLGP_OK;
   }
@@ -152,6 +256,13 @@ struct Folder {
       FLGP_TRY(flgp_dev_gemm(st, s, K, K, 1.0, B, 1, s, G + a * sg, K, 1, 0.0, nullptr, 0, 0, Pg, h->ldp, 1, nullptr, 0));
       FLGP_TRY(flgp_dev_gemm(st, s, q, K, 1.0, B, 1, s, U + a * su, 1, K, 0.0, nullptr, 0, 0, Pg + K, h->ldp, 1, nullptr, 0));
     }
+    return FLGP_OK;
+  }
+  // Polya-Gamma chains [p0, p0 + S): P(:, b) = sum_k B(:, k) u_b(k), a column per N = 1 product whatever shares the call
+  int fold_pg(hipStream_t st, int p0, int S, const double *U, long su) {
+    for (int a = 0; a < S; ++a)
+      FLGP_TRY(flgp_dev_gemm(st, h->s, 1, h->K, 1.0, B, 1, h->s, U + a * su, 1, h->K, 0.0, nullptr, 0, 0, h->P.as<double>() + p0 + a,
+                             h->ldp, 1, nullptr, 0));
     return FLGP_OK;
   }
 };
@@ -254,7 +365,160 @@ int create_logit(const char *who, const flgp_eigenpair *ep, int K, const int *id
   return FLGP_OK;
 }
 
+template <class Check, class Begin>
+int create_pg(const char *who, const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol, const int *col,
+              const double *ts, const unsigned long long *seeds, int B, double sigma, int n_sample, int max_parallel, double *omega_out,
+              double *f_out, flgp_predictor **out, Check check, Begin begin) {
+  FLGP_TRY(pg_operands_check(who, ep, K, idx0, m, Y, ncol, col, ts, seeds, B, sigma, n_sample));
+  FLGP_TRY(check());
+  Stream st;
+  FLGP_TRY(st.create());
+  std::unique_ptr<flgp_predictor> h(new flgp_predictor());
+  Folder F{h.get()};
+  FLGP_TRY(begin(F, st.s));
+  const int rc = pg_operands(st.s, who, ep, K, idx0, m, Y, ncol, col, ts, seeds, B, sigma, n_sample, max_parallel, omega_out, f_out,
+                             [&](hipStream_t ws, int p0, int S, const double *U, long su) { return F.fold_pg(ws, p0, S, U, su); });
+  if (rc != FLGP_OK) { (void)hipStreamSynchronize(st.s); return rc; }
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  *out = h.release();
+  return FLGP_OK;
+}
+
+// ---- apply on a Polya-Gamma handle: the latent of a block, then the link
+int pg_apply_block(hipStream_t st, const flgp_predictor *h, ModelRowWork &W, const double *dX, int nb, int ldx, double *d_f, long ldf,
+                   double *d_pi, long ldpi, double *d_y, long ldy, double *d_label) {
+  const flgp_spectrum_model *m = h->model;
+  FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
+  return flgp_dev_predictor_pg_rows(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, m->s, h->q,
+                                    d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
+}
+// a Nystrom handle: the mean-only route writes the block's latent (the caller's f, or `lat`: nb x q at ld nb), then the link
+struct NystromPgWork {
+  DevBuf work, lat;
+  size_t bytes = 0;
+  int B = 0;
+  int alloc(const flgp_predictor *h, int n_new, bool own_latent) {
+    B = std::min(nys_row_block(h->s, h->K, n_new), std::min(model_block_rows(), n_new));
+    bytes = nystrom_mean_workspace(B, h->s, h->q);
+    FLGP_TRY(work.alloc(bytes));
+    return own_latent ? lat.alloc(sizeof(double) * (size_t)B * h->q) : FLGP_OK;
+  }
+};
+int nystrom_pg_apply_block(hipStream_t st, const flgp_predictor *h, NystromPgWork &W, const double *dX, int nb, int ldx, double *d_f,
+                           long ldf, double *d_pi, long ldpi, double *d_y, long ldy, double *d_label) {
+  const flgp_nystrom_grid *G = h->grid;
+  double *lat = d_f ? d_f : W.lat.as<double>();
+  const long ldl = d_f ? ldf : nb;
+  FLGP_TRY(nystrom_mean_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
+                             G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, h->q, lat, ldl, W.work.p, W.bytes));
+  if (!(d_pi || d_y || d_label)) return FLGP_OK;
+  return flgp_dev_pg_link(st, lat, ldl, nb, h->q, d_pi, ldpi, d_y, ldy, d_label);
+}
+
 }  // namespace
+
+extern "C" int flgp_predictor_pg_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0, int m,
+                                        const double *Y, int ncol, const int *col, const double *ts, const unsigned long long *seeds,
+                                        int B, double sigma, int n_sample, int max_parallel, double *omega_out, double *f_out,
+                                        flgp_predictor **out) {
+  const char *who = "predictor_pg";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(model, "%s: null model", who);
+  return create_pg(who, ep, K, idx0, m, Y, ncol, col, ts, seeds, B, sigma, n_sample, max_parallel, omega_out, f_out, out,
+                   [&] { return check_model(who, model, ep); },
+                   [&](Folder &F, hipStream_t st) { return F.begin(st, model, K, 1, B, FLGP_PREDICTOR_PG); });
+}
+
+extern "C" int flgp_predictor_nystrom_pg_create(const flgp_nystrom_grid *grid, int i, const flgp_eigenpair *ep, int K, const int *idx0,
+                                                int m, const double *Y, int ncol, const int *col, const double *ts,
+                                                const unsigned long long *seeds, int B, double sigma, int n_sample, int max_parallel,
+                                                double *omega_out, double *f_out, flgp_predictor **out) {
+  const char *who = "predictor_nystrom_pg";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(grid, "%s: null grid", who);
+  FLGP_REQUIRE(i >= 0 && i < grid->l, "%s: bandwidth %d outside 0..%d", who, i, grid->l - 1);
+  return create_pg(who, ep, K, idx0, m, Y, ncol, col, ts, seeds, B, sigma, n_sample, max_parallel, omega_out, f_out, out,
+                   [&] { return check_grid(who, grid, i, ep); },
+                   [&](Folder &F, hipStream_t st) { return F.begin(st, grid, i, K, 1, B, FLGP_PREDICTOR_PG); });
+}
+
+extern "C" int flgp_dev_predictor_pg_apply(void *stream, const flgp_predictor *h, const double *dX, int n_new, int ldx, double *d_f,
+                                           long ldf, double *d_pi, long ldpi, double *d_y, long ldy, double *d_label) {
+  const char *who = "predictor_pg_apply";
+  hipStream_t st = (hipStream_t)stream;
+  FLGP_REQUIRE(dX && (d_f || d_pi || d_y || d_label), "%s: null pointer", who);
+  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
+  FLGP_REQUIRE(ldx >= n_new && (!d_f || ldf >= n_new) && (!d_pi || ldpi >= n_new) && (!d_y || ldy >= n_new),
+               "%s: a leading dimension is below n_new = %d", who, n_new);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_PG, "%s: the handle is not a Polya-Gamma one (kind %d)", who, h->kind);
+  FLGP_TRY(on_handle_device(h, who));
+  auto at = [](double *p, long i0) { return p ? p + i0 : nullptr; };
+  if (h->grid) {
+    NystromPgWork W;
+    FLGP_TRY(W.alloc(h, n_new, d_f == nullptr));
+    for (long i0 = 0; i0 < n_new; i0 += W.B)
+      FLGP_TRY(nystrom_pg_apply_block(st, h, W, dX + i0, (int)std::min<long>(W.B, n_new - i0), ldx, at(d_f, i0), ldf, at(d_pi, i0), ldpi,
+                                      at(d_y, i0), ldy, at(d_label, i0)));
+    FLGP_HIP(hipStreamSynchronize(st));
+    return FLGP_OK;
+  }
+  const int B = std::min(model_block_rows(), n_new);
+  ModelRowWork W;
+  FLGP_TRY(W.alloc(h->model, B));
+  for (long i0 = 0; i0 < n_new; i0 += B)
+    FLGP_TRY(pg_apply_block(st, h, W, dX + i0, (int)std::min<long>(B, n_new - i0), ldx, at(d_f, i0), ldf, at(d_pi, i0), ldpi, at(d_y, i0),
+                            ldy, at(d_label, i0)));
+  FLGP_HIP(hipStreamSynchronize(st));     // (the workspaces die here)
+  return FLGP_OK;
+}
+
+extern "C" int flgp_predictor_pg_apply(const flgp_predictor *h, const double *X, int n_new, double *f, double *pi, double *y,
+                                       double *label) {
+  const char *who = "predictor_pg_apply";
+  FLGP_REQUIRE(X && (f || pi || y || label), "%s: null pointer", who);
+  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_PG, "%s: the handle is not a Polya-Gamma one (kind %d)", who, h->kind);
+  FLGP_TRY(on_handle_device(h, who));
+  const flgp_spectrum_model *m = h->model;
+  const int d = h->d, q = h->q;
+  Stream st;
+  FLGP_TRY(st.create());
+  ModelRowWork W;
+  NystromPgWork NW;
+  DevBuf dX, df, dpi, dy, dlab;
+  if (h->grid) FLGP_TRY(NW.alloc(h, n_new, f == nullptr));
+  const int B = h->grid ? NW.B : std::min(model_block_rows(), n_new);
+  if (m) FLGP_TRY(W.alloc(m, B));
+  const size_t nq = sizeof(double) * (size_t)n_new * q;
+  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
+  if (f) FLGP_TRY(df.alloc(nq));
+  if (pi) FLGP_TRY(dpi.alloc(nq));
+  if (y) FLGP_TRY(dy.alloc(nq));
+  if (label) FLGP_TRY(dlab.alloc(sizeof(double) * (size_t)n_new));
+  auto at = [](DevBuf &b, bool want, long i0) { return want ? b.as<double>() + i0 : nullptr; };
+  for (long i0 = 0; i0 < n_new; i0 += B) {
+    const int nb = (int)std::min<long>(B, n_new - i0);
+    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_new, sizeof(double) * (size_t)nb, d,
+                              hipMemcpyHostToDevice, st.s));
+    FLGP_TRY(check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points"));
+    if (h->grid)
+      FLGP_TRY(nystrom_pg_apply_block(st.s, h, NW, dX.as<double>(), nb, nb, at(df, f, i0), n_new, at(dpi, pi, i0), n_new, at(dy, y, i0),
+                                      n_new, at(dlab, label, i0)));
+    else
+      FLGP_TRY(pg_apply_block(st.s, h, W, dX.as<double>(), nb, nb, at(df, f, i0), n_new, at(dpi, pi, i0), n_new, at(dy, y, i0), n_new,
+                              at(dlab, label, i0)));
+  }
+  if (f) FLGP_TRY(d2h(f, df.p, nq, st.s));
+  if (pi) FLGP_TRY(d2h(pi, dpi.p, nq, st.s));
+  if (y) FLGP_TRY(d2h(y, dy.p, nq, st.s));
+  if (label) FLGP_TRY(d2h(label, dlab.p, sizeof(double) * (size_t)n_new, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
 
 extern "C" int flgp_predictor_regression_create(const flgp_spectrum_model *model, const flgp_eigenpair *ep, int K, const int *idx0,
                                                 int m, const double *Y, int q, double t, const double *noise, int n_noise,
@@ -340,6 +604,10 @@ extern "C" int flgp_dev_predictor_apply(void *stream, const flgp_predictor *h, c
   FLGP_REQUIRE(ldx >= n_new && (!d_mean || ldm >= n_new) && (!d_var || ldv >= n_new), "%s: a leading dimension is below n_new = %d", who,
                n_new);
   FLGP_REQUIRE(h, "%s: null handle", who);
+  if (h->kind == FLGP_PREDICTOR_PG) {
+    FLGP_REQUIRE(!d_var, "%s: a Polya-Gamma handle has no variance", who);
+    return flgp_dev_predictor_pg_apply(stream, h, dX, n_new, ldx, d_mean, ldm, nullptr, 0, nullptr, 0, nullptr);
+  }
   FLGP_TRY(on_handle_device(h, who));
   if (h->grid) {
     NystromRowWork W;
@@ -365,6 +633,10 @@ extern "C" int flgp_predictor_apply(const flgp_predictor *h, const double *X, in
   FLGP_REQUIRE(X && (mean || var), "%s: null pointer", who);
   FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
   FLGP_REQUIRE(h, "%s: null handle", who);
+  if (h->kind == FLGP_PREDICTOR_PG) {
+    FLGP_REQUIRE(!var, "%s: a Polya-Gamma handle has no variance", who);
+    return flgp_predictor_pg_apply(h, X, n_new, mean, nullptr, nullptr, nullptr);
+  }
   FLGP_TRY(on_handle_device(h, who));
   const flgp_spectrum_model *m = h->model;
   const int d = h->d, gq = h->groups * h->q;
