@@ -1163,9 +1163,12 @@ class Predictor:
     :class:`NystromGrid`: dense weights, the mean alone without the similarity ever going to memory.
     :meth:`pg` / :meth:`pg_for_classes` (and :meth:`nystrom_pg` / :meth:`nystrom_pg_for_classes`) fold the Polya-Gamma chains
     of ``ResidentEigenPair.test_pgbinary_batch`` instead ("Polya-Gamma predictor"): :meth:`predict` then gives the
-    probabilities and labels of unseen rows; such a handle has no variance."""
+    probabilities and labels of unseen rows; such a handle has no variance.
+    A "regression" or "logit" handle also serves the joint posterior of the latent function ("joint posterior of served
+    rows"): :meth:`features` and :meth:`covariance` give z_i and z_i . z_j, :meth:`draws` a handle of S seeded function draws
+    per output whose :meth:`apply` returns the same functions on every call."""
 
-    _KIND = ("regression", "logit", "pg")
+    _KIND = ("regression", "logit", "pg", "draws")
 
     def __init__(self, handle, model, iters=None):
         self._h = handle
@@ -1177,6 +1180,7 @@ class Predictor:
         self.d, self.s, self.r, self.K, self.groups, self.q, kind = (int(x.value) for x in v)
         self.kind = self._KIND[kind]
         self.ldp = int(ldp.value)
+        self.draw_shape = (1, self.q, 1) if self.kind == "draws" else None     # (groups, q, S) of the source: set by draws()
 
     @staticmethod
     def _trained(model, pair, idx0, Y):
@@ -1373,7 +1377,8 @@ class Predictor:
 
     def apply(self, X, var=True):
         """The posterior of the rows ``X`` (n_new x d): ``{"mean": n_new x (groups q), "var": n_new x groups}``
-        Fortran-ordered; ``var=False`` skips the variance ("var" is None) and leaves the mean's bits unchanged."""
+        Fortran-ordered; ``var=False`` skips the variance ("var" is None) and leaves the mean's bits unchanged.  A "draws"
+        handle (:meth:`draws`) returns its draws instead, one array ``n_new x groups x q x S``."""
         h = self._handle()
         X = _f64(X, "X")
         if X.shape[1] != self.d:
@@ -1381,10 +1386,87 @@ class Predictor:
         n = X.shape[0]
         if n < 1:
             raise ValueError("X must have at least one row")
+        if self.kind == "draws":
+            f = np.zeros((n, self.q), order="F")
+            check(_lib.lib().flgp_predictor_apply(h, _ptr(X), n, _ptr(f), None))
+            return f.reshape((n,) + tuple(self.draw_shape))
         mean = np.zeros((n, self.groups * self.q), order="F")
         v = np.zeros((n, self.groups), order="F") if var else None
         check(_lib.lib().flgp_predictor_apply(h, _ptr(X), n, _ptr(mean), _ptr(v)))
         return {"mean": mean, "var": v}
+
+    def _rows(self, X, name="X"):
+        X = _f64(X, name)
+        if X.shape[1] != self.d:
+            raise ValueError(f"{name} has {X.shape[1]} columns but the model was fitted on {self.d}")
+        if X.shape[0] < 1:
+            raise ValueError(f"{name} must have at least one row")
+        return X
+
+    def _joint(self, who, group):
+        """the handle of a kind that has a covariance operand, and the group index, checked before the library is touched"""
+        h = self._handle()
+        if self.kind not in ("regression", "logit"):
+            raise FlgpError(-1, f"{who}: a handle of kind {self._KIND.index(self.kind)} has no covariance operand")
+        group = int(group)
+        if not 0 <= group < self.groups:
+            raise IndexError(f"group {group} outside 0..{self.groups - 1}")
+        return h, group
+
+    def draws(self, S, seed):
+        """A "draws" predictor of ``S`` posterior function draws per (group, output) of this "regression" or "logit" handle:
+        its ``apply(X)`` returns ``n x groups x q x S`` values f(x_i) = mean_i + z_i . xi_t of the LATENT function (the diagonal
+        term ``cg`` is independent noise and is left to the caller).  Draw t depends on (this handle, seed, group, output, t)
+        alone -- not on S -- and a row gets the same values whenever and with whatever other rows it is served.  The new
+        handle borrows the model or grid, not this predictor."""
+        h, _ = self._joint("predictor_draws", 0)
+        S = int(S)
+        if S < 1:
+            raise ValueError("S must be at least 1")
+        if self.groups * self.q * S > 2 ** 31 - 16:
+            raise ValueError("groups * q * S overflows an int")
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_predictor_draws_create(h, S, int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(out)))
+        d = type(self)(out, self._model)
+        d.draw_shape = (self.groups, self.q, S)
+        return d
+
+    def normals(self):
+        """A "draws" handle's standard normals, ``K x ncol``: column ``(g q + c) S + t`` is ``synth.normal(seed, (g q + c) 2^32
+        + t, K)``."""
+        h = self._handle()
+        if self.kind != "draws":
+            raise FlgpError(-1, f"predictor_draws_normals: the handle is not a draws one (kind {self._KIND.index(self.kind)})")
+        xi = np.zeros((self.K, self.q), order="F")
+        check(_lib.lib().flgp_predictor_draws_normals(h, _ptr(xi)))
+        return xi
+
+    def features(self, X, group=0):
+        """``Z`` (n x K, Fortran-ordered) with ``Z[i] = z_i`` of ``group``: the latent covariance of two rows is ``Z[i] . Z[j]``
+        and ``apply``'s ``var[i, group] - cg[group]`` is ``|Z[i]|^2``."""
+        h, group = self._joint("predictor_features", group)
+        X = self._rows(X)
+        Z = np.zeros((X.shape[0], self.K), order="F")
+        check(_lib.lib().flgp_predictor_features(h, group, _ptr(X), X.shape[0], _ptr(Z)))
+        return Z
+
+    def covariance(self, Xa, Xb=None, group=0, diag_term=False):
+        """The latent posterior covariance block of the rows ``Xa`` against ``Xb`` (``na x nb``, Fortran-ordered); ``Xb=None``
+        means ``Xb = Xa`` and the block is exactly symmetric.  ``diag_term`` adds ``cg[group]`` on the diagonal (on the host),
+        which makes the block the covariance of noisy observations; it needs ``Xb=None``."""
+        h, group = self._joint("predictor_covariance", group)
+        if diag_term and Xb is not None:
+            raise ValueError("diag_term needs Xb=None: the diagonal term belongs to a row's covariance with itself")
+        Xa = self._rows(Xa, "Xa")
+        Xb = None if Xb is None else self._rows(Xb, "Xb")
+        na, nb = Xa.shape[0], Xa.shape[0] if Xb is None else Xb.shape[0]
+        C = np.zeros((na, nb), order="F")
+        check(_lib.lib().flgp_predictor_covariance(h, group, _ptr(Xa), na, _ptr(Xb), nb, _ptr(C)))
+        if diag_term:
+            cg = np.zeros(self.groups)
+            check(_lib.lib().flgp_predictor_to_host(h, None, _ptr(cg)))
+            C[np.arange(na), np.arange(na)] += cg[group]
+        return C
 
     def predict(self, X, latent=False):
         """A "pg" handle's answer for the rows ``X`` (n_new x d): ``{"pi": n_new x B, "y": n_new x B (pi > 0.5),

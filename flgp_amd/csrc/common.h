@@ -563,6 +563,20 @@ size_t nystrom_mean_workspace(int n, int s, int q);
 int nystrom_mean_rows(hipStream_t st, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu, const double *dU,
                       int ldu, int s, double inv_c, const double *d_w, const double *d_P, long ldp, int q, double *d_mean, long ldm,
                       void *d_work, size_t work_bytes);
+// The Nystrom predictor's columns-out route (nystrom_predictor.hip; f-23): out(i, c) = f_i sum_j Z(i, j) P(j, c0 + c), c < nc, with
+// Z and f made and stored as the variance route makes them, T = Z P(:, a chunk of columns) one j-ascending chain per element
+// (gemm_launch without a workspace; chunks under nystrom_predictor_t_mb) and out = f T.  out n x nc column-major (ldo).
+size_t nystrom_cols_workspace(int n, int s, int nc);
+int nystrom_cols_rows(hipStream_t st, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu, const double *dU,
+                      int ldu, int s, double inv_c, const double *d_w, const double *d_P, long ldp, int c0, int nc, double *d_out,
+                      long ldo, void *d_work, size_t work_bytes);
+// The draws handle's kernels (predictor_cols.hip; f-23).  draws_normals_fill: xi(k, col) at d_xi[k ncol + col], normal p = k of
+// stream (col / S) 2^32 + col % S under seed.  draws_fold: P_draw(j, (g q + c) S + t) = P(j, g (K + q) + K + c) + the k-ascending
+// chain of P(j, g (K + q) + k) xi(k, col).  sym_mirror: the strict upper triangle of C (n x n, ldc) takes the lower one's bits.
+int draws_normals_fill(hipStream_t st, unsigned long long seed, int K, int S, long ncol, double *d_xi);
+int draws_fold(hipStream_t st, const double *d_P, long ldp, int s, int groups, int K, int q, int S, const double *d_xi, double *d_Pd,
+               long ldd);
+int sym_mirror(hipStream_t st, double *d_C, int n, long ldc);
 }  // namespace flgp
 
 struct flgp_nystrom_grid;

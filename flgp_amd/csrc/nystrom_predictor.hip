@@ -175,6 +175,15 @@ __global__ __launch_bounds__(256) void np_var_kernel(const double *__restrict__ 
   }
 }
 
+// out(x, c) = f_x T(x, c) for the nc columns of a chunk: the product np_var_kernel squares (T nb x nc, ld nb)
+__global__ __launch_bounds__(256) void np_scale_kernel(const double *__restrict__ T, int nb, int nc, const double *__restrict__ fac,
+                                                       double *__restrict__ out, long ldo) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= nb) return;
+  const double f = fac[x];
+  for (int c = blockIdx.y; c < nc; c += gridDim.y) out[(long)c * ldo + x] = f * T[(size_t)c * nb + x];
+}
+
 template <int NC, int STORE>
 static int np_launch_sim(hipStream_t st, int dpad, const double *X, int nb, int ldx, int d, const double *Ut, const double *uu, int s,
                          double inv_c, const double *w, const double *Pm, double *Z, int sums, double *p1, double *p2, double *pm) {
@@ -322,4 +331,67 @@ int flgp::nystrom_mean_rows(hipStream_t st, const double *dX, int n, int ldx, in
                "%s: bad shape (n=%d, s=%d, q=%d)", who, n, s, q);
   return np_rows_body(who, st, dX, n, ldx, d, dpad, dUt, duu, dU, ldu, s, inv_c, d_w, d_P, ldp, 1, 0, q, nullptr, d_mean, ldm, nullptr, 0,
                       d_work, work_bytes);
+}
+
+// ---- the columns-out route (f-23).  The workspace: the pieces of the variance route without a mean (NpLayout of one mean
+// column, which is never packed), then T for a chunk of columns
+namespace {
+struct NpColsLayout {
+  NpLayout L;
+  size_t T, total;
+  int cc;                                               // columns of T held at once
+  NpColsLayout(int n, int s, int nc) : L(n, s, 1, 0, 1, 0) {
+    const size_t cap = np_t_cap() / sizeof(double);
+    cc = (int)std::max<size_t>(1, std::min<size_t>((size_t)nc, cap / (size_t)n));
+    T = L.total;
+    // cc n <= min(nc n, max(n, cap)), which grows with n: the workspace of a block holds every shorter block
+    total = T + (std::min((size_t)nc * n, std::max((size_t)n, cap)) + 31) / 32 * 32;
+  }
+};
+}  // namespace
+
+size_t flgp::nystrom_cols_workspace(int n, int s, int nc) {
+  if (n < 1 || s < 1 || nc < 1) return 0;
+  return sizeof(double) * NpColsLayout(n, s, nc).total;
+}
+
+int flgp::nystrom_cols_rows(hipStream_t st, const double *dX, int n, int ldx, int d, const double *dUt, const double *duu,
+                            const double *dU, int ldu, int s, double inv_c, const double *d_w, const double *d_P, long ldp, int c0,
+                            int nc, double *d_out, long ldo, void *d_work, size_t work_bytes) {
+  const char *who = "nystrom_cols_rows";
+  FLGP_REQUIRE(dX && dUt && duu && dU && d_w && d_P && d_out && d_work, "%s: null pointer", who);
+  const int dpad = flgp_dev_anchor_dpad(d);
+  FLGP_REQUIRE(dpad > 0 && d >= 1, "%s: kernels are built for 1 <= d <= %d (got %d)", who, FLGP_DMAX, d);
+  FLGP_REQUIRE(n >= 1 && s >= 1 && nc >= 1 && c0 >= 0 && (long)c0 + nc <= ldp && ldx >= n && ldu >= s && ldo >= n &&
+                   (long)n * s < (1L << 40),
+               "%s: bad shape (n=%d, s=%d, c0=%d, nc=%d)", who, n, s, c0, nc);
+  const NpColsLayout C(n, s, nc);
+  FLGP_REQUIRE(work_bytes >= sizeof(double) * C.total, "%s: the workspace holds %zu bytes, %zu are needed", who, work_bytes,
+               sizeof(double) * C.total);
+  const NpLayout &L = C.L;
+  double *W = (double *)d_work;
+  double *Z = W + L.Z, *p1 = W + L.p1, *p2 = W + L.p2, *pm = W + L.pm, *fac = W + L.fac, *xx = W + L.xx, *Pm = W + L.Pm, *T = W + C.T;
+  ProfScope ps("nystrom_cols_rows", st, (double)n * s * (2.0 * dpad + 4.0 + 2.0 * nc));
+  // Z and the row factor: the launches of the variance route where no mean is asked for
+  if (nys_dots_via_gemm(dpad)) {
+    hipLaunchKernelGGL(np_sqnorm_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, dX, n, ldx, d, xx);
+    FLGP_TRY(check_launch("np_sqnorm_kernel"));
+    FLGP_TRY(gemm_launch(st, n, s, d, 1.0, dX, 1, ldx, dU, ldu, 1, 0.0, nullptr, 0, 0, Z, 1, n, nullptr, 0, 0.0, nullptr));
+    hipLaunchKernelGGL((np_exp_rows_kernel<0, 1>), dim3(ceil_div(n, 256), L.nchunk), dim3(256), 0, st, Z, n, s, xx, duu, inv_c, d_w, Pm, p1,
+                       p2, pm);
+    FLGP_TRY(check_launch("np_exp_rows_kernel"));
+  } else {
+    FLGP_TRY((np_launch_sim<0, 1>(st, dpad, dX, n, ldx, d, dUt, duu, s, inv_c, d_w, Pm, Z, 1, p1, p2, pm)));
+  }
+  hipLaunchKernelGGL(np_finish_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, st, p1, p2, pm, L.nchunk, n, 0, 1, fac, (double *)nullptr,
+                     (long)0);
+  FLGP_TRY(check_launch("np_finish_kernel"));
+  for (int b0 = 0; b0 < nc; b0 += C.cc) {
+    const int bc = std::min(C.cc, nc - b0);
+    FLGP_TRY(gemm_launch(st, n, bc, s, 1.0, Z, 1, n, d_P + c0 + b0, ldp, 1, 0.0, nullptr, 0, 0, T, 1, n, nullptr, 0, 0.0, nullptr));
+    hipLaunchKernelGGL(np_scale_kernel, dim3(ceil_div(n, 256), std::min(bc, 65535)), dim3(256), 0, st, T, n, bc, fac,
+                       d_out + (long)b0 * ldo, ldo);
+    FLGP_TRY(check_launch("np_scale_kernel"));
+  }
+  return FLGP_OK;
 }

@@ -9,6 +9,9 @@
 // weights are dense and the row path is nystrom_predictor.hip's.
 // A Polya-Gamma handle (f-22) keeps the B mean columns alone, P(:, b) = B u_b with u_b = L (V1^T w_b) of chain b (eigenpair.hip:
 // pg_operands): a served row's latent is a_i P, its pi, y and label the link's (predictor_pg_rows_kernel, pg_link_kernel).
+// The joint posterior of served rows (f-23): the K columns of a group are the features z_i, z_i . z_j the latent covariance of
+// two rows, and a draws handle keeps P_draw(:, col) = P_mean(:, c) + P_K xi_col, mean columns alone, served like any mean
+// (predictor_cols.hip: the wide row kernel, the normals and the fold; nystrom_predictor.hip: the columns-out route).
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -21,6 +24,7 @@ struct flgp_predictor {
   const flgp_nystrom_grid *grid = nullptr;      // bandwidth gi of a Nystrom grid (f-21: dense weights, nystrom_predictor.hip)
   int gi = 0, s = 0, d = 0;
   DevBuf P, cg;                                 // s x ldp row-major, groups
+  DevBuf xi;                                    // a draws handle (f-23): the normals, xi(k, col) at k q + col
   std::vector<int> iters;                       // logit: one count per group
   int K = 0, groups = 0, q = 0, kind = 0, device = 0;
   long ldp = 0;
@@ -226,8 +230,9 @@ struct Folder {
   const double *B = nullptr;
   int shape(hipStream_t st, int s, int d, int device, int K, int groups, int q, int kind) {
     h->s = s; h->d = d; h->K = K; h->groups = groups; h->q = q; h->kind = kind; h->device = device;
-    // a Polya-Gamma handle's P holds the q mean columns alone
-    h->ldp = ((kind == FLGP_PREDICTOR_PG ? (long)q : (long)groups * (K + q)) + 15) / 16 * 16;
+    // a Polya-Gamma handle's P holds the q mean columns alone, and so does a draws handle's (f-23)
+    const bool mean_only = kind == FLGP_PREDICTOR_PG || kind == FLGP_PREDICTOR_DRAWS;
+    h->ldp = ((mean_only ? (long)q : (long)groups * (K + q)) + 15) / 16 * 16;
     FLGP_TRY(h->P.alloc(sizeof(double) * (size_t)s * h->ldp));
     FLGP_TRY(h->cg.alloc(sizeof(double) * (size_t)groups));
     FLGP_HIP(hipMemsetAsync(h->cg.p, 0, sizeof(double) * (size_t)groups, st));
@@ -571,6 +576,215 @@ extern "C" int flgp_predictor_nystrom_logit_create(const flgp_nystrom_grid *grid
                       [&](Folder &F, hipStream_t st) { return F.begin(st, grid, i, K, B, 1, FLGP_PREDICTOR_LOGIT); });
 }
 
+// ---- f-23: columns [c0, c0 + nc) of z_i = a_i P (model) or f_i sum_j Z_ij P_j (Nystrom) for the rows of a block, as they are:
+// the features of a regression / logit handle (the K columns of a group) and the draws of a draws handle (all of P_draw).
+namespace {
+
+bool has_covariance_operand(const flgp_predictor *h) {
+  return h->kind == FLGP_PREDICTOR_REGRESSION || h->kind == FLGP_PREDICTOR_LOGIT;
+}
+
+// "<who>: <what> of <bytes> bytes does not fit 90 % of the <free> bytes free" (the memory query is the first device call)
+int fits_free_memory(const char *who, const char *what, double bytes) {
+  size_t free_b = 0, total_b = 0;
+  FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+  FLGP_REQUIRE(bytes <= 0.9 * (double)free_b, "%s: %s of %.0f bytes does not fit 90 %% of the %zu bytes free", who, what, bytes, free_b);
+  return FLGP_OK;
+}
+
+// the rows per block and the workspaces of one block.  `mean_route`: a Nystrom draws handle of at most 8 columns takes the
+// mean-only route (nystrom_mean_rows); every other Nystrom call the columns-out route
+struct ColsWork {
+  ModelRowWork M;
+  DevBuf nys;
+  size_t nys_bytes = 0;
+  int B = 0;
+  bool mean_route = false;
+  static int rows(const flgp_predictor *h, int n) {
+    const int B = std::min(model_block_rows(), n);
+    return h->grid ? std::min(nys_row_block(h->s, h->K, n), B) : B;
+  }
+  static size_t bytes(const flgp_predictor *h, int B, int nc, bool mean_route) {
+    if (!h->grid) return (sizeof(int) + sizeof(double)) * (size_t)B * (size_t)(2 * h->model->r);
+    return mean_route ? nystrom_mean_workspace(B, h->s, nc) : nystrom_cols_workspace(B, h->s, nc);
+  }
+  int alloc(const flgp_predictor *h, int n, int nc, bool mean) {
+    B = rows(h, n);
+    mean_route = mean;
+    if (!h->grid) return M.alloc(h->model, B);
+    nys_bytes = bytes(h, B, nc, mean);
+    return nys.alloc(nys_bytes);
+  }
+};
+
+int cols_block(hipStream_t st, const flgp_predictor *h, ColsWork &W, const double *dX, int nb, int ldx, int c0, int nc, double *d_out,
+               long ldo) {
+  if (!h->grid) {
+    const flgp_spectrum_model *m = h->model;
+    FLGP_TRY(model_rows(st, m, W.M, dX, nb, ldx));
+    return flgp_dev_predictor_cols(st, W.M.ell_idx.as<int>(), W.M.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, m->s, c0,
+                                   nc, d_out, ldo);
+  }
+  const flgp_nystrom_grid *G = h->grid;
+  if (W.mean_route) {      // a draws handle's whole P_draw: the mean-only route takes its columns from 0
+    FLGP_REQUIRE(c0 == 0, "predictor: the mean-only route serves columns from 0 (c0=%d)", c0);
+    return nystrom_mean_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
+                             G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, nc, d_out, ldo, W.nys.p, W.nys_bytes);
+  }
+  return nystrom_cols_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
+                           G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, c0, nc, d_out, ldo, W.nys.p, W.nys_bytes);
+}
+
+bool draws_mean_route(const flgp_predictor *h) { return h->grid && h->kind == FLGP_PREDICTOR_DRAWS && h->q <= 8; }
+
+// device rows: block by block on `st`, which is synchronised before the workspaces die
+int cols_from_device(const char *who, hipStream_t st, const flgp_predictor *h, const double *dX, int n, int ldx, int c0, int nc,
+                     double *d_out, long ldo) {
+  const bool mean = draws_mean_route(h);
+  const int B = ColsWork::rows(h, n);
+  FLGP_TRY(fits_free_memory(who, "the workspace of a row block", (double)ColsWork::bytes(h, B, nc, mean)));
+  ColsWork W;
+  FLGP_TRY(W.alloc(h, n, nc, mean));
+  for (long i0 = 0; i0 < n; i0 += W.B)
+    FLGP_TRY(cols_block(st, h, W, dX + i0, (int)std::min<long>(W.B, n - i0), ldx, c0, nc, d_out + i0, ldo));
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
+}
+
+// host rows: uploaded and screened block by block; the result stays on the device (d_out n x nc, ldo)
+int cols_from_host(const char *who, hipStream_t st, const flgp_predictor *h, const double *X, int n, int c0, int nc, double *d_out,
+                   long ldo) {
+  const bool mean = draws_mean_route(h);
+  const int B = ColsWork::rows(h, n), d = h->d;
+  FLGP_TRY(fits_free_memory(who, "a row block and its workspace",
+                            (double)ColsWork::bytes(h, B, nc, mean) + sizeof(double) * (double)B * d));
+  ColsWork W;
+  DevBuf dX;
+  FLGP_TRY(W.alloc(h, n, nc, mean));
+  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)W.B * d));
+  for (long i0 = 0; i0 < n; i0 += W.B) {
+    const int nb = (int)std::min<long>(W.B, n - i0);
+    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb, d,
+                              hipMemcpyHostToDevice, st));
+    FLGP_TRY(check_finite_on_device(st, dX.as<double>(), (long)nb * d, "points"));
+    FLGP_TRY(cols_block(st, h, W, dX.as<double>(), nb, nb, c0, nc, d_out + i0, ldo));
+  }
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
+}
+
+// the same, down to the host (out n x nc column-major)
+int cols_to_host(const char *who, const flgp_predictor *h, const double *X, int n, int c0, int nc, double *out) {
+  const double bytes = sizeof(double) * (double)n * nc;
+  FLGP_TRY(fits_free_memory(who, "the n x nc result", bytes));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf d_out;
+  FLGP_TRY(d_out.alloc((size_t)bytes));
+  FLGP_TRY(cols_from_host(who, st.s, h, X, n, c0, nc, d_out.as<double>(), n));
+  FLGP_TRY(d2h(out, d_out.p, (size_t)bytes, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
+// what features and covariance refuse about the handle, after their own pointers and shapes
+int check_features(const char *who, const flgp_predictor *h, int g) {
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(has_covariance_operand(h), "%s: a handle of kind %d has no covariance operand", who, h->kind);
+  FLGP_REQUIRE(g >= 0 && g < h->groups, "%s: group %d outside 0..%d", who, g, h->groups - 1);
+  return on_handle_device(h, who);
+}
+
+}  // namespace
+
+extern "C" int flgp_predictor_draws_create(const flgp_predictor *h, int S, unsigned long long seed, flgp_predictor **out) {
+  const char *who = "predictor_draws";
+  FLGP_REQUIRE(out, "%s: null pointer", who);
+  *out = nullptr;
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(has_covariance_operand(h), "%s: a handle of kind %d has no covariance operand", who, h->kind);
+  FLGP_REQUIRE(S >= 1, "%s: need S >= 1 (S=%d)", who, S);
+  const long ncol = (long)h->groups * h->q * S;
+  FLGP_REQUIRE(ncol <= 0x7fffffffL - 15, "%s: groups q S = %ld columns overflow an int", who, ncol);
+  FLGP_TRY(on_handle_device(h, who));
+  const long ldd = (ncol + 15) / 16 * 16;
+  FLGP_TRY(fits_free_memory(who, "P_draw and the normals", sizeof(double) * ((double)h->s * ldd + (double)h->K * ncol)));
+  Stream st;
+  FLGP_TRY(st.create());
+  std::unique_ptr<flgp_predictor> o(new flgp_predictor());
+  o->model = h->model; o->grid = h->grid; o->gi = h->gi;       // what h borrows, not h
+  Folder F{o.get()};
+  FLGP_TRY(F.shape(st.s, h->s, h->d, h->device, h->K, 1, (int)ncol, FLGP_PREDICTOR_DRAWS));
+  FLGP_TRY(o->xi.alloc(sizeof(double) * (size_t)h->K * (size_t)ncol));
+  FLGP_TRY(flgp_dev_predictor_draws_fold(st.s, (const double *)h->P.p, h->ldp, h->s, h->groups, h->K, h->q, S, seed, o->xi.as<double>(),
+                                         o->P.as<double>(), o->ldp));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  *out = o.release();
+  return FLGP_OK;
+}
+
+extern "C" int flgp_predictor_draws_normals(const flgp_predictor *h, double *xi) {
+  const char *who = "predictor_draws_normals";
+  FLGP_REQUIRE(xi, "%s: null pointer", who);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_DRAWS, "%s: the handle is not a draws one (kind %d)", who, h->kind);
+  FLGP_TRY(on_handle_device(h, who));
+  const size_t K = (size_t)h->K, ncol = (size_t)h->q;
+  std::vector<double> rows(K * ncol);
+  Stream st;
+  FLGP_TRY(st.create());
+  FLGP_TRY(d2h(rows.data(), h->xi.p, sizeof(double) * rows.size(), st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  for (size_t k = 0; k < K; ++k)
+    for (size_t c = 0; c < ncol; ++c) xi[c * K + k] = rows[k * ncol + c];
+  return FLGP_OK;
+}
+
+extern "C" int flgp_dev_predictor_features(void *stream, const flgp_predictor *h, int g, const double *dX, int n, int ldx, double *dZ,
+                                           long ldz) {
+  const char *who = "predictor_features";
+  FLGP_REQUIRE(dX && dZ, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
+  FLGP_REQUIRE(ldx >= n && ldz >= n, "%s: a leading dimension is below n = %d", who, n);
+  FLGP_TRY(check_features(who, h, g));
+  return cols_from_device(who, (hipStream_t)stream, h, dX, n, ldx, g * (h->K + h->q), h->K, dZ, ldz);
+}
+
+extern "C" int flgp_predictor_features(const flgp_predictor *h, int g, const double *X, int n, double *Z) {
+  const char *who = "predictor_features";
+  FLGP_REQUIRE(X && Z, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
+  FLGP_TRY(check_features(who, h, g));
+  return cols_to_host(who, h, X, n, g * (h->K + h->q), h->K, Z);
+}
+
+extern "C" int flgp_predictor_covariance(const flgp_predictor *h, int g, const double *Xa, int na, const double *Xb, int nb, double *C) {
+  const char *who = "predictor_covariance";
+  FLGP_REQUIRE(Xa && C, "%s: null pointer", who);
+  FLGP_REQUIRE(na >= 1 && (!Xb || nb >= 1), "%s: need na >= 1 and nb >= 1 (na=%d, nb=%d)", who, na, nb);
+  FLGP_TRY(check_features(who, h, g));
+  if (!Xb) nb = na;
+  const int K = h->K, c0 = g * (h->K + h->q);
+  const double bytes = sizeof(double) * ((double)na * K + (Xb ? (double)nb * K : 0.0) + (double)na * nb);
+  FLGP_TRY(fits_free_memory(who, "the features and the na x nb block", bytes));
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf Za, Zb, dC;
+  FLGP_TRY(Za.alloc(sizeof(double) * (size_t)na * K));
+  FLGP_TRY(dC.alloc(sizeof(double) * (size_t)na * nb));
+  FLGP_TRY(cols_from_host(who, st.s, h, Xa, na, c0, K, Za.as<double>(), na));
+  if (Xb) {
+    FLGP_TRY(Zb.alloc(sizeof(double) * (size_t)nb * K));
+    FLGP_TRY(cols_from_host(who, st.s, h, Xb, nb, c0, K, Zb.as<double>(), nb));
+  }
+  const double *B = Xb ? Zb.as<double>() : Za.as<double>();
+  FLGP_TRY(flgp_dev_gemm(st.s, na, nb, K, 1.0, Za.as<double>(), 1, na, B, nb, 1, 0.0, nullptr, 0, 0, dC.as<double>(), 1, na, nullptr, 0));
+  if (!Xb) FLGP_TRY(sym_mirror(st.s, dC.as<double>(), na, na));
+  FLGP_TRY(d2h(C, dC.p, sizeof(double) * (size_t)na * nb, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return FLGP_OK;
+}
+
 extern "C" int flgp_predictor_dims(const flgp_predictor *h, int *d, int *s, int *r, int *K, int *groups, int *q, int *kind, long *ldp) {
   FLGP_REQUIRE(h, "predictor_dims: null handle");
   if (d) *d = h->d;
@@ -608,6 +822,11 @@ extern "C" int flgp_dev_predictor_apply(void *stream, const flgp_predictor *h, c
     FLGP_REQUIRE(!d_var, "%s: a Polya-Gamma handle has no variance", who);
     return flgp_dev_predictor_pg_apply(stream, h, dX, n_new, ldx, d_mean, ldm, nullptr, 0, nullptr, 0, nullptr);
   }
+  if (h->kind == FLGP_PREDICTOR_DRAWS) {
+    FLGP_REQUIRE(!d_var, "%s: a draws handle has no variance", who);
+    FLGP_TRY(on_handle_device(h, who));
+    return cols_from_device(who, st, h, dX, n_new, ldx, 0, h->q, d_mean, ldm);
+  }
   FLGP_TRY(on_handle_device(h, who));
   if (h->grid) {
     NystromRowWork W;
@@ -636,6 +855,11 @@ extern "C" int flgp_predictor_apply(const flgp_predictor *h, const double *X, in
   if (h->kind == FLGP_PREDICTOR_PG) {
     FLGP_REQUIRE(!var, "%s: a Polya-Gamma handle has no variance", who);
     return flgp_predictor_pg_apply(h, X, n_new, mean, nullptr, nullptr, nullptr);
+  }
+  if (h->kind == FLGP_PREDICTOR_DRAWS) {
+    FLGP_REQUIRE(!var, "%s: a draws handle has no variance", who);
+    FLGP_TRY(on_handle_device(h, who));
+    return cols_to_host(who, h, X, n_new, 0, h->q, mean);
   }
   FLGP_TRY(on_handle_device(h, who));
   const flgp_spectrum_model *m = h->model;
