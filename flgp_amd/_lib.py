@@ -141,6 +141,7 @@ _SIGNATURES = {
     "flgp_predictor_draws_normals": (c_int, [P, P]),
     "flgp_predictor_features": (c_int, [P, c_int, P, c_int, P]),
     "flgp_predictor_covariance": (c_int, [P, c_int, P, c_int, P, c_int, P]),
+    "flgp_predictor_update": (c_int, [P, P, c_int, P, P, c_int, P]),
     "flgp_se_spectrum_grid": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P, c_int]),
     "flgp_lae_eigenmap": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, P, P]),
     "flgp_dev_se_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P,
@@ -180,6 +181,9 @@ _SIGNATURES = {
     "flgp_dev_predictor_cols": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, c_int, P, c_long]),
     "flgp_dev_predictor_draws_fold": (c_int, [P, P, c_long, c_int, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, P, P, c_long]),
     "flgp_dev_predictor_features": (c_int, [P, P, c_int, P, c_int, c_int, P, c_long]),
+    "flgp_dev_predictor_gram_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "flgp_dev_predictor_gram": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, c_int, P, P, c_long, P, c_long, P, c_size_t]),
+    "flgp_dev_predictor_update": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_int, P]),
     "flgp_dev_pg_link": (c_int, [P, P, c_long, c_int, c_int, P, c_long, P, c_long, P]),
     "flgp_dev_predictor_pg_apply": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_long, P, c_long, P]),
     "flgp_dev_nystrom_predictor_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -1468,6 +1468,28 @@ class Predictor:
             C[np.arange(na), np.arange(na)] += cg[group]
         return C
 
+    def update(self, X, Y, noise=None):
+        """A new "regression" predictor: this one conditioned on the newly labelled rows ``X`` (n_b x d) with responses ``Y``
+        (n_b x q) -- exactly the posterior of the old and the new labels together, at the cost of the new rows alone.  ``noise``:
+        None (the noise this handle was created with), one variance, or one per row.  This predictor is not modified, and the
+        new one borrows the model, not this predictor.  Refused on a "logit", "pg" or "draws" handle, on a Nystrom handle and on a
+        handle created with ``noisepar="different"``; a handle returned by ``update`` can always be updated again."""
+        h = self._handle()
+        X = self._rows(X)
+        n = X.shape[0]
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim > 2 or (Y.ndim == 2 and Y.shape != (n, self.q)) or (Y.ndim < 2 and (self.q != 1 or Y.size != n)):
+            raise ValueError(f"Y must have one row per row of X and q = {self.q} columns")
+        Y = np.asfortranarray(Y.reshape(n, -1))
+        nz = None
+        if noise is not None:
+            nz = np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1))
+            if nz.size not in (1, n):
+                raise FlgpError(-1, f"predictor_update: n_noise={nz.size} must be 0 with a NULL noise, 1 or n_b={n}")
+        out = ctypes.c_void_p()
+        check(_lib.lib().flgp_predictor_update(h, _ptr(X), n, _ptr(Y), _ptr(nz), 0 if nz is None else nz.size, ctypes.byref(out)))
+        return type(self)(out, self._model)
+
     def predict(self, X, latent=False):
         """A "pg" handle's answer for the rows ``X`` (n_new x d): ``{"pi": n_new x B, "y": n_new x B (pi > 0.5),
         "label": n_new (the first chain of maximal pi)}`` and, with ``latent``, ``"f"`` (pi = 1 / (1 + exp(-f)))."""

@@ -526,6 +526,15 @@ struct ModelRowWork {
 };
 int model_block_rows();
 int model_rows(hipStream_t st, const flgp_spectrum_model *m, ModelRowWork &W, const double *dX, int nb, int ldx);
+// The update of a regression handle (predictor_update.hip).  predictor_gram: flgp_dev_predictor_gram's two
+// launches on d_part (predictor_gram_bytes(n, K, q) bytes); `first` starts every element from 0.0, otherwise from S as it stands,
+// so the chunk partials of successive row blocks -- each a multiple of predictor_gram_chunk() rows -- form one ascending chain.
+// predictor_update_system: M = I + S[:K, :K] (ld K) and R = S[:K, K:] (ld K) of S at ld K + q.
+size_t predictor_gram_bytes(long n, int K, int q);
+int predictor_gram_chunk();
+int predictor_gram(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *d_P, long ldp, int K,
+                   int q, const double *d_w, const double *d_Y, long ldy, double *d_S, long lds, double *d_part, bool first);
+int predictor_update_system(hipStream_t st, const double *d_S, int K, int q, double *d_M, double *d_R);
 // B(j, k) = Vs(j, k) q_k, q_k = scale / sigma_k (0 where sigma_k = 0): the anchor side of flgp_dev_hk_rows (sparse.hip)
 int hk_rows_b(hipStream_t st, const double *dVs, int ldv, int s, const double *d_eig, int K, double scale, double *dB);
 // The trained operands of the posteriors for the predictor (predictor.hip), by the weight-space route whatever m is, on

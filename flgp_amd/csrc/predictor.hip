@@ -28,6 +28,10 @@ struct flgp_predictor {
   std::vector<int> iters;                       // logit: one count per group
   int K = 0, groups = 0, q = 0, kind = 0, device = 0;
   long ldp = 0;
+  // a regression handle (f-24): the nugget and noise[0] it was created with, and whether its K columns are the covariance of
+  // its mean ("same" noise, or the result of an update) -- what flgp_predictor_update conditions on
+  double sigma = 0.0, noise0 = 0.0;
+  bool consistent = false;
 };
 
 namespace flgp {
@@ -335,6 +339,7 @@ int create_regression(const char *who, const flgp_eigenpair *ep, int K, const in
   Folder F{h.get()};
   FLGP_TRY(begin(F, st.s));
   const double c = noise[0] + sigma;
+  h->sigma = sigma; h->noise0 = noise[0]; h->consistent = n_noise == 1;
   FLGP_TRY(h2d(h->cg.p, &c, sizeof(double), st.s));
   FLGP_TRY(regression_operands(st.s, who, ep, K, idx0, m, Y, q, t, noise, n_noise, sigma,
                                [&](int p0, int S, const double *G, long sg, const double *U, long su) {
@@ -783,6 +788,175 @@ extern "C" int flgp_predictor_covariance(const flgp_predictor *h, int g, const d
   FLGP_TRY(d2h(C, dC.p, sizeof(double) * (size_t)na * nb, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));
   return FLGP_OK;
+}
+
+// ---- f-24: a regression handle conditioned on newly labelled rows.  With f_i = mean_i + z_i . xi, xi ~ N(0, I_K), observing
+// y_i = f_i + N(0, d_i) on n_b rows is a K x K problem in xi: M = I + sum_i z_i z_i^T / d_i = L L^T, xi* = M^-1 sum_i z_i
+// (y_i - mean_i)^T / d_i, and the new handle is P_mean' = P_mean + P_K xi*, P_K' = P_K L^-T.  S = sum_i e_i e_i^T / d_i with
+// e_i = [z_i ; y_i - mean_i] comes from predictor_update.hip; the fold is the pieces the creates run on.
+namespace {
+
+// refusals 1 to 3 of the update entries come before these; then the handle (4 to 7)
+int update_check_handle(const char *who, const flgp_predictor *h) {
+  FLGP_REQUIRE(h->kind != FLGP_PREDICTOR_LOGIT,
+               "%s: a logit handle cannot be updated (a Laplace posterior is not closed under conditioning)", who);
+  FLGP_REQUIRE(h->kind != FLGP_PREDICTOR_PG, "%s: a Polya-Gamma handle cannot be updated (it holds the chains' mean columns alone)", who);
+  FLGP_REQUIRE(h->kind != FLGP_PREDICTOR_DRAWS,
+               "%s: a draws handle cannot be updated (update the regression handle it was made from and make the draws again)", who);
+  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_REGRESSION, "%s: the handle is not a regression one (kind %d)", who, h->kind);
+  FLGP_REQUIRE(!h->grid, "%s: a Nystrom handle cannot be updated (only a handle over a spectrum model)", who);
+  FLGP_REQUIRE(h->consistent,
+               "%s: the handle was created with per-row noise: its variance operand is built at noise[0] and is not the covariance "
+               "of its mean, so conditioning it is not a posterior of anything",
+               who);
+  return on_handle_device(h, who);
+}
+
+// w_i = 1 / (noise_i + sigma) on the host; noise NULL: the create's noise[0]
+int update_weights(const char *who, const flgp_predictor *h, const double *noise, int n_noise, int n_b, std::vector<double> &w) {
+  for (int a = 0; a < n_noise; ++a) {
+    FLGP_REQUIRE(std::isfinite(noise[a]), "%s: noise[%d] must be finite", who, a);
+    FLGP_REQUIRE(noise[a] + h->sigma > 0.0, "%s: noise[%d] + sigma must be positive", who, a);
+  }
+  w.resize((size_t)n_b);
+  for (int i = 0; i < n_b; ++i) w[(size_t)i] = 1.0 / ((n_noise == 0 ? h->noise0 : noise[n_noise == 1 ? 0 : i]) + h->sigma);
+  return FLGP_OK;
+}
+
+struct UpdateRun {
+  const flgp_predictor *h;
+  ModelRowWork M;
+  DevBuf S, dW, part;
+  int B = 0;                                    // rows per block: a multiple of the Gram kernel's chunk
+  // the block: model_extend_block rounded down to a multiple of the chunk, at least one chunk -- any multiple gives the same chain
+  static int rows(const flgp_predictor *) {
+    const int gc = predictor_gram_chunk();
+    return std::max(gc, model_block_rows() / gc * gc);
+  }
+  int begin(hipStream_t st, int n_b, const std::vector<double> &w) {
+    const int Wd = h->K + h->q;
+    B = rows(h);
+    FLGP_TRY(M.alloc(h->model, std::min(B, n_b)));
+    FLGP_TRY(S.alloc(sizeof(double) * (size_t)Wd * Wd));
+    FLGP_TRY(part.alloc(predictor_gram_bytes(std::min(B, n_b), h->K, h->q)));
+    FLGP_TRY(dW.alloc(sizeof(double) * (size_t)n_b));
+    return h2d(dW.p, w.data(), sizeof(double) * (size_t)n_b, st);
+  }
+  // rows [i0, i0 + nb) of the call: dX their points (ldx), dY their responses (ldy)
+  int block(hipStream_t st, long i0, const double *dX, int nb, int ldx, const double *dY, long ldy) {
+    const flgp_spectrum_model *m = h->model;
+    FLGP_TRY(model_rows(st, m, M, dX, nb, ldx));
+    return predictor_gram(st, M.ell_idx.as<int>(), M.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, h->K, h->q,
+                          dW.as<double>() + i0, dY, ldy, S.as<double>(), h->K + h->q, part.as<double>(), i0 == 0);
+  }
+  // the fold; synchronises `st`
+  int finish(hipStream_t st, const char *who, flgp_predictor **out) {
+    const int K = h->K, q = h->q, s = h->s;
+    const size_t wi = (size_t)32 * 64 * K;
+    DevBuf Mk, R, Li, Tb, wt, flag;
+    FLGP_TRY(Mk.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(R.alloc(sizeof(double) * (size_t)K * q));
+    FLGP_TRY(Li.alloc(sizeof(double) * (size_t)K * K)); FLGP_TRY(Tb.alloc(sizeof(double) * (size_t)64 * K));
+    FLGP_TRY(wt.alloc(sizeof(double) * wi)); FLGP_TRY(flag.alloc(sizeof(int)));
+    FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    std::unique_ptr<flgp_predictor> o(new flgp_predictor());
+    o->model = h->model;                        // what h borrows, not h
+    Folder F{o.get()};
+    FLGP_TRY(F.shape(st, s, h->d, h->device, K, 1, q, FLGP_PREDICTOR_REGRESSION));
+    o->sigma = h->sigma; o->noise0 = h->noise0; o->consistent = true;
+    FLGP_HIP(hipMemcpyAsync(o->cg.p, h->cg.p, sizeof(double), hipMemcpyDeviceToDevice, st));
+    FLGP_TRY(predictor_update_system(st, S.as<double>(), K, q, Mk.as<double>(), R.as<double>()));
+    FLGP_TRY(chol_blocked(st, Mk.as<double>(), K, K, flag.as<int>()));
+    FLGP_TRY(chol_trsv(st, Mk.as<double>(), K, K, R.as<double>(), K, q, 3, flag.as<int>()));              // xi*
+    FLGP_TRY(tri_inverse(st, Mk.as<double>(), K, K, Li.as<double>(), K, Tb.as<double>(), wt.as<double>(), wi, flag.as<int>()));
+    const double *Ph = (const double *)h->P.p;
+    double *Po = o->P.as<double>();
+    // P_K'(j, k') = sum_k P_K(j, k) Linv(k', k);  P_mean' = P_mean + P_K xi*: no workspace, each element one k-ascending chain
+    FLGP_TRY(flgp_dev_gemm(st, s, K, K, 1.0, Ph, h->ldp, 1, Li.as<double>(), K, 1, 0.0, nullptr, 0, 0, Po, o->ldp, 1, nullptr, 0));
+    FLGP_TRY(flgp_dev_gemm(st, s, q, K, 1.0, Ph, h->ldp, 1, R.as<double>(), 1, K, 1.0, Ph + K, h->ldp, 1, Po + K, o->ldp, 1, nullptr, 0));
+    int bad = 0;
+    FLGP_TRY(read_flag(st, flag.p, &bad));
+    if (bad) {
+      set_error("%s: I + Z^T D^-1 Z is not positive definite (pivot %d <= 0)", who, bad - 1);
+      return FLGP_ERR_NOCONV;
+    }
+    *out = o.release();
+    return FLGP_OK;
+  }
+};
+
+// a non-finite response: the q columns of dY (ldy) on the device
+int update_check_responses(hipStream_t st, const double *dY, long ldy, int n_b, int q) {
+  for (int c = 0; c < q; ++c) FLGP_TRY(check_finite_on_device(st, dY + (long)c * ldy, n_b, "predictor_update: the responses Y"));
+  return FLGP_OK;
+}
+
+}  // namespace
+
+extern "C" int flgp_dev_predictor_update(void *stream, const flgp_predictor *h, const double *dX, int n_b, int ldx, const double *dY,
+                                         long ldy, const double *d_noise, int n_noise, flgp_predictor **out) {
+  const char *who = "predictor_update";
+  hipStream_t st = (hipStream_t)stream;
+  FLGP_REQUIRE(out, "%s: null pointer (out)", who);
+  *out = nullptr;
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(dX && dY, "%s: null pointer", who);
+  FLGP_REQUIRE(n_b >= 1, "%s: need n_b >= 1 (n_b=%d)", who, n_b);
+  FLGP_REQUIRE(d_noise ? (n_noise == 1 || n_noise == n_b) : n_noise == 0,
+               "%s: n_noise=%d must be 0 with a NULL noise, 1 or n_b=%d", who, n_noise, n_b);
+  FLGP_REQUIRE(ldx >= n_b && ldy >= n_b, "%s: a leading dimension is below n_b = %d", who, n_b);
+  FLGP_TRY(update_check_handle(who, h));
+  std::vector<double> noise((size_t)n_noise), w;
+  if (n_noise) {
+    FLGP_TRY(d2h(noise.data(), d_noise, sizeof(double) * (size_t)n_noise, st));
+    FLGP_HIP(hipStreamSynchronize(st));
+  }
+  FLGP_TRY(update_check_responses(st, dY, ldy, n_b, h->q));
+  FLGP_TRY(update_weights(who, h, noise.data(), n_noise, n_b, w));
+  UpdateRun U{h};
+  FLGP_TRY(U.begin(st, n_b, w));
+  int rc = FLGP_OK;
+  for (long i0 = 0; i0 < n_b && rc == FLGP_OK; i0 += U.B)
+    rc = U.block(st, i0, dX + i0, (int)std::min<long>(U.B, n_b - i0), ldx, dY + i0, ldy);
+  if (rc == FLGP_OK) rc = U.finish(st, who, out);
+  (void)hipStreamSynchronize(st);               // (the workspaces die here)
+  return rc;
+}
+
+extern "C" int flgp_predictor_update(const flgp_predictor *h, const double *X, int n_b, const double *Y, const double *noise,
+                                     int n_noise, flgp_predictor **out) {
+  const char *who = "predictor_update";
+  FLGP_REQUIRE(out, "%s: null pointer (out)", who);
+  *out = nullptr;
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(X && Y, "%s: null pointer", who);
+  FLGP_REQUIRE(n_b >= 1, "%s: need n_b >= 1 (n_b=%d)", who, n_b);
+  FLGP_REQUIRE(noise ? (n_noise == 1 || n_noise == n_b) : n_noise == 0, "%s: n_noise=%d must be 0 with a NULL noise, 1 or n_b=%d", who,
+               n_noise, n_b);
+  FLGP_TRY(update_check_handle(who, h));
+  const int d = h->d, q = h->q;
+  Stream st;
+  FLGP_TRY(st.create());
+  DevBuf dX, dY;
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)n_b * q));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)n_b * q, st.s));
+  FLGP_TRY(update_check_responses(st.s, dY.as<double>(), n_b, n_b, q));
+  std::vector<double> w;
+  FLGP_TRY(update_weights(who, h, noise, n_noise, n_b, w));
+  UpdateRun U{h};
+  FLGP_TRY(U.begin(st.s, n_b, w));
+  const int B = std::min(U.B, n_b);
+  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
+  int rc = FLGP_OK;
+  for (long i0 = 0; i0 < n_b && rc == FLGP_OK; i0 += B) {
+    const int nb = (int)std::min<long>(B, n_b - i0);
+    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_b, sizeof(double) * (size_t)nb, d,
+                              hipMemcpyHostToDevice, st.s));
+    rc = check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points");
+    if (rc == FLGP_OK) rc = U.block(st.s, i0, dX.as<double>(), nb, nb, dY.as<double>() + i0, n_b);
+  }
+  if (rc == FLGP_OK) rc = U.finish(st.s, who, out);
+  (void)hipStreamSynchronize(st.s);
+  return rc;
 }
 
 extern "C" int flgp_predictor_dims(const flgp_predictor *h, int *d, int *s, int *r, int *K, int *groups, int *q, int *kind, long *ldp) {
