@@ -142,6 +142,7 @@ _SIGNATURES = {
     "flgp_predictor_features": (c_int, [P, c_int, P, c_int, P]),
     "flgp_predictor_covariance": (c_int, [P, c_int, P, c_int, P, c_int, P]),
     "flgp_predictor_update": (c_int, [P, P, c_int, P, P, c_int, P]),
+    "flgp_predictor_design": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "flgp_se_spectrum_grid": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P, c_int]),
     "flgp_lae_eigenmap": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_char_p, P, P]),
     "flgp_dev_se_spectrum_grid": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_char_p, c_int, P, P, P,
@@ -184,6 +185,9 @@ _SIGNATURES = {
     "flgp_dev_predictor_gram_workspace": (c_size_t, [c_int, c_int, c_int]),
     "flgp_dev_predictor_gram": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, c_int, P, P, c_long, P, c_long, P, c_size_t]),
     "flgp_dev_predictor_update": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_int, P]),
+    "flgp_dev_predictor_design_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "flgp_dev_predictor_design_rows": (c_int, [P, P, P, c_int, c_int, P, c_long, c_int, c_int, c_double, c_int, P, P, P, P, c_size_t]),
+    "flgp_dev_predictor_design": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P]),
     "flgp_dev_pg_link": (c_int, [P, P, c_long, c_int, c_int, P, c_long, P, c_long, P]),
     "flgp_dev_predictor_pg_apply": (c_int, [P, P, P, c_int, c_int, P, c_long, P, c_long, P, c_long, P]),
     "flgp_dev_nystrom_predictor_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -1490,6 +1490,29 @@ class Predictor:
         check(_lib.lib().flgp_predictor_update(h, _ptr(X), n, _ptr(Y), _ptr(nz), 0 if nz is None else nz.size, ctypes.byref(out)))
         return type(self)(out, self._model)
 
+    def design(self, X, B, noise=None):
+        """Which ``B`` of the candidate rows ``X`` (n x d) to label next: greedy maximum-variance design.  Each step takes the
+        untaken row of largest latent posterior variance given the picks so far (at equal variances the lowest row number)
+        and conditions on it with observation variance ``noise + sigma``; ``noise``: None (the noise this handle was created
+        with) or one variance.  Returns ``{"picks": int array (B), "gain": (B), "var": (n)}``: the 0-based rows, the latent
+        variance of each at the moment it was taken, and the latent variance of every candidate after all B picks -- what
+        ``update(X[picks], .)`` then serves as ``apply``'s variance minus ``cg``, whatever the labels are.  The loop this closes
+        is design -> label -> ``update`` -> design again; this predictor is not modified.  Refused on the handles ``update``
+        refuses."""
+        h = self._handle()
+        X = self._rows(X)
+        n, B = X.shape[0], int(B)
+        if not 1 <= B <= n:
+            raise ValueError(f"B must be between 1 and the {n} rows of X")
+        nz = None
+        if noise is not None:
+            nz = np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1))
+            if nz.size != 1:
+                raise ValueError("noise must be None or one variance")
+        out = {"picks": np.zeros(B, dtype=np.int32), "gain": np.zeros(B), "var": np.zeros(n)}
+        check(_lib.lib().flgp_predictor_design(h, _ptr(X), n, B, _ptr(nz), _ptr(out["picks"]), _ptr(out["gain"]), _ptr(out["var"])))
+        return out
+
     def predict(self, X, latent=False):
         """A "pg" handle's answer for the rows ``X`` (n_new x d): ``{"pi": n_new x B, "y": n_new x B (pi > 0.5),
         "label": n_new (the first chain of maximal pi)}`` and, with ``latent``, ``"f"`` (pi = 1 / (1 + exp(-f)))."""

@@ -535,6 +535,11 @@ int predictor_gram_chunk();
 int predictor_gram(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *d_P, long ldp, int K,
                    int q, const double *d_w, const double *d_Y, long ldy, double *d_S, long lds, double *d_part, bool first);
 int predictor_update_system(hipStream_t st, const double *d_S, int K, int q, double *d_M, double *d_R);
+// The greedy design loop (predictor_design.hip): flgp_dev_predictor_design_rows' launches on d_work
+// (predictor_design_bytes(n, r, s, K, B) bytes), shapes already checked; asynchronous on `st`.
+size_t predictor_design_bytes(int n, int r, int s, int K, int B);
+int predictor_design_rows(hipStream_t st, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *d_P, long ldp,
+                          int s, int K, double d, int B, int *d_picks, double *d_gain, double *d_score, void *d_work);
 // B(j, k) = Vs(j, k) q_k, q_k = scale / sigma_k (0 where sigma_k = 0): the anchor side of flgp_dev_hk_rows (sparse.hip)
 int hk_rows_b(hipStream_t st, const double *dVs, int ldv, int s, const double *d_eig, int K, double scale, double *dB);
 // The trained operands of the posteriors for the predictor (predictor.hip), by the weight-space route whatever m is, on

@@ -959,6 +959,135 @@ extern "C" int flgp_predictor_update(const flgp_predictor *h, const double *X, i
   return rc;
 }
 
+// ---- f-25: which rows to label next.  The pool's rows go through the model's row chain block by block into n x r arrays; the
+// greedy loop (predictor_design.hip) runs once on them.
+namespace {
+
+// refusals 1 to 3 of the design entries come before these; then the handle (4 to 7), in update's words
+int design_check_handle(const char *who, const flgp_predictor *h) {
+  FLGP_REQUIRE(h->kind != FLGP_PREDICTOR_LOGIT,
+               "%s: a logit handle has no design (the observation variance of a new label is not a constant)", who);
+  FLGP_REQUIRE(h->kind != FLGP_PREDICTOR_PG, "%s: a Polya-Gamma handle has no design (it holds the chains' mean columns alone)", who);
+  FLGP_REQUIRE(h->kind != FLGP_PREDICTOR_DRAWS, "%s: a draws handle has no design (design on the regression handle it was made from)", who);
+  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_REGRESSION, "%s: the handle is not a regression one (kind %d)", who, h->kind);
+  FLGP_REQUIRE(!h->grid, "%s: a Nystrom handle has no design (only a handle over a spectrum model)", who);
+  FLGP_REQUIRE(h->consistent,
+               "%s: the handle was created with per-row noise: its variance operand is built at noise[0] and is not the covariance "
+               "of its mean, so the variance a design would reduce is not a posterior's",
+               who);
+  return on_handle_device(h, who);
+}
+
+// refusal 8: d = noise + sigma, noise NULL = the create's noise[0]
+int design_variance(const char *who, const flgp_predictor *h, const double *noise, double *d) {
+  const double nz = noise ? noise[0] : h->noise0;
+  FLGP_REQUIRE(std::isfinite(nz), "%s: the noise must be finite", who);
+  FLGP_REQUIRE(nz + h->sigma > 0.0, "%s: noise + sigma must be positive", who);
+  *d = nz + h->sigma;
+  return FLGP_OK;
+}
+
+struct DesignRun {
+  const flgp_predictor *h;
+  ModelRowWork M;
+  DevBuf idx, val, work;
+  int n = 0, Bd = 0, blk = 0;
+  size_t work_bytes = 0;
+  // the pool's rows, the workspace and the row chain's block, against the free memory; `extra`: what the entry holds besides
+  int begin(const char *who, int n_, int B, double extra) {
+    const flgp_spectrum_model *m = h->model;
+    n = n_; Bd = B;
+    blk = std::min(model_block_rows(), n);
+    work_bytes = predictor_design_bytes(n, m->r, h->s, h->K, B);
+    FLGP_REQUIRE(work_bytes > 0, "%s: bad shape (n=%d, r=%d, s=%d, K=%d, B=%d)", who, n, m->r, h->s, h->K, B);
+    const double rows = (sizeof(int) + sizeof(double)) * (double)n * m->r;
+    const double chain = (sizeof(int) + sizeof(double)) * (double)blk * (2.0 * m->r);
+    size_t free_b = 0, total_b = 0;
+    FLGP_HIP(hipMemGetInfo(&free_b, &total_b));
+    FLGP_REQUIRE(rows + (double)work_bytes + chain + extra <= 0.9 * (double)free_b,
+                 "%s: the pool's rows of %.0f bytes and the workspace of %zu bytes (n=%d, B=%d) do not fit 90 %% of the %zu bytes free", who,
+                 rows + chain + extra, work_bytes, n, B, free_b);
+    FLGP_TRY(M.alloc(m, blk));
+    FLGP_TRY(idx.alloc(sizeof(int) * (size_t)n * m->r));
+    FLGP_TRY(val.alloc(sizeof(double) * (size_t)n * m->r));
+    return work.alloc(work_bytes);
+  }
+  // rows [i0, i0 + nb) of the call: dX their points (ldx)
+  int block(hipStream_t st, long i0, const double *dX, int nb, int ldx) {
+    const flgp_spectrum_model *m = h->model;
+    FLGP_TRY(model_rows(st, m, M, dX, nb, ldx));
+    FLGP_HIP(hipMemcpyAsync(idx.as<int>() + i0 * m->r, M.ell_idx.p, sizeof(int) * (size_t)nb * m->r, hipMemcpyDeviceToDevice, st));
+    FLGP_HIP(hipMemcpyAsync(val.as<double>() + i0 * m->r, M.ell_val.p, sizeof(double) * (size_t)nb * m->r, hipMemcpyDeviceToDevice, st));
+    return FLGP_OK;
+  }
+  int loop(hipStream_t st, double d, int *d_picks, double *d_gain, double *d_score) {
+    return predictor_design_rows(st, idx.as<int>(), val.as<double>(), n, h->model->r, (const double *)h->P.p, h->ldp, h->s, h->K, d, Bd,
+                                 d_picks, d_gain, d_score, work.p);
+  }
+};
+
+}  // namespace
+
+extern "C" int flgp_dev_predictor_design(void *stream, const flgp_predictor *h, const double *dX, int n, int ldx, int B,
+                                         const double *noise, int *d_picks, double *d_gain, double *d_score) {
+  const char *who = "predictor_design";
+  hipStream_t st = (hipStream_t)stream;
+  FLGP_REQUIRE(d_picks, "%s: null pointer (picks)", who);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(dX, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
+  FLGP_REQUIRE(B >= 1 && B <= n, "%s: need 1 <= B <= n (B=%d, n=%d)", who, B, n);
+  FLGP_REQUIRE(ldx >= n, "%s: a leading dimension is below n = %d", who, n);
+  FLGP_TRY(design_check_handle(who, h));
+  double d = 0.0;
+  FLGP_TRY(design_variance(who, h, noise, &d));
+  DesignRun R{h};
+  FLGP_TRY(R.begin(who, n, B, 0.0));
+  int rc = FLGP_OK;
+  for (long i0 = 0; i0 < n && rc == FLGP_OK; i0 += R.blk) rc = R.block(st, i0, dX + i0, (int)std::min<long>(R.blk, n - i0), ldx);
+  if (rc == FLGP_OK) rc = R.loop(st, d, d_picks, d_gain, d_score);
+  (void)hipStreamSynchronize(st);               // (the workspaces die here)
+  return rc;
+}
+
+extern "C" int flgp_predictor_design(const flgp_predictor *h, const double *X, int n, int B, const double *noise, int *picks,
+                                     double *gain, double *score) {
+  const char *who = "predictor_design";
+  FLGP_REQUIRE(picks, "%s: null pointer (picks)", who);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(X, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
+  FLGP_REQUIRE(B >= 1 && B <= n, "%s: need 1 <= B <= n (B=%d, n=%d)", who, B, n);
+  FLGP_TRY(design_check_handle(who, h));
+  double d = 0.0;
+  FLGP_TRY(design_variance(who, h, noise, &d));
+  const int dim = h->d;
+  Stream st;
+  FLGP_TRY(st.create());
+  DesignRun R{h};
+  const double out_bytes = sizeof(int) * (double)B + sizeof(double) * ((double)B + n);
+  FLGP_TRY(R.begin(who, n, B, out_bytes + sizeof(double) * (double)std::min(model_block_rows(), n) * dim));
+  DevBuf dX, d_picks, d_gain, d_score;
+  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)R.blk * dim));
+  FLGP_TRY(d_picks.alloc(sizeof(int) * (size_t)B));
+  if (gain) FLGP_TRY(d_gain.alloc(sizeof(double) * (size_t)B));
+  if (score) FLGP_TRY(d_score.alloc(sizeof(double) * (size_t)n));
+  int rc = FLGP_OK;
+  for (long i0 = 0; i0 < n && rc == FLGP_OK; i0 += R.blk) {
+    const int nb = (int)std::min<long>(R.blk, n - i0);
+    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb, dim,
+                              hipMemcpyHostToDevice, st.s));
+    rc = check_finite_on_device(st.s, dX.as<double>(), (long)nb * dim, "points");
+    if (rc == FLGP_OK) rc = R.block(st.s, i0, dX.as<double>(), nb, nb);
+  }
+  if (rc == FLGP_OK) rc = R.loop(st.s, d, d_picks.as<int>(), gain ? d_gain.as<double>() : nullptr, score ? d_score.as<double>() : nullptr);
+  if (rc == FLGP_OK) rc = d2h(picks, d_picks.p, sizeof(int) * (size_t)B, st.s);
+  if (rc == FLGP_OK && gain) rc = d2h(gain, d_gain.p, sizeof(double) * (size_t)B, st.s);
+  if (rc == FLGP_OK && score) rc = d2h(score, d_score.p, sizeof(double) * (size_t)n, st.s);
+  (void)hipStreamSynchronize(st.s);
+  return rc;
+}
+
 extern "C" int flgp_predictor_dims(const flgp_predictor *h, int *d, int *s, int *r, int *K, int *groups, int *q, int *kind, long *ldp) {
   FLGP_REQUIRE(h, "predictor_dims: null handle");
   if (d) *d = h->d;
