@@ -1,6 +1,7 @@
 // Shared host-side helpers for libflgp_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -526,6 +527,40 @@ struct ModelRowWork {
 };
 int model_block_rows();
 int model_rows(hipStream_t st, const flgp_spectrum_model *m, ModelRowWork &W, const double *dX, int nb, int ldx);
+// The rows an entry serves: the caller's device rows (dX, ldx), or host rows X (column-major, ld n) with the block they are
+// staged in, which lives as long as the entry's other workspaces do.
+struct RowPoints {
+  const double *dX = nullptr;
+  int ldx = 0;
+  const double *X = nullptr;
+  DevBuf staged;
+};
+// Rows [0, n) of `points` (d columns) in blocks of B: block(i0, rows, nb, ld) on the nb device rows from i0, asynchronous on
+// `st`.  Host rows are uploaded and screened ("points") block by block.  Stops at the first failure and returns its code; the
+// final synchronise and the copies down are the caller's.
+template <class Block>
+int for_row_blocks(hipStream_t st, RowPoints &points, int n, int d, int B, Block block) {
+  if (points.X) FLGP_TRY(points.staged.alloc(sizeof(double) * (size_t)std::min(B, n) * d));
+  for (long i0 = 0; i0 < n; i0 += B) {
+    const int nb = (int)std::min<long>(B, n - i0);
+    if (!points.X) {
+      FLGP_TRY(block(i0, points.dX + i0, nb, points.ldx));
+      continue;
+    }
+    double *rows = points.staged.as<double>();
+    FLGP_HIP(hipMemcpy2DAsync(rows, sizeof(double) * (size_t)nb, points.X + i0, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb, d,
+                              hipMemcpyHostToDevice, st));
+    FLGP_TRY(check_finite_on_device(st, rows, (long)nb * d, "points"));
+    FLGP_TRY(block(i0, rows, nb, nb));
+  }
+  return FLGP_OK;
+}
+// The way out of an entry that queued row blocks: `st` is idle before the workspaces die, whether rc is a failure or not
+inline int settle(hipStream_t st, int rc) {
+  if (rc != FLGP_OK) { (void)hipStreamSynchronize(st); return rc; }
+  FLGP_HIP(hipStreamSynchronize(st));
+  return FLGP_OK;
+}
 // The update of a regression handle (predictor_update.hip).  predictor_gram: flgp_dev_predictor_gram's two
 // launches on d_part (predictor_gram_bytes(n, K, q) bytes); `first` starts every element from 0.0, otherwise from S as it stands,
 // so the chunk partials of successive row blocks -- each a multiple of predictor_gram_chunk() rows -- form one ascending chain.

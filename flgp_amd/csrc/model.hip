@@ -2,7 +2,8 @@
 //   k-NN -> LAE / SE weights -> the three scalings under the fit's column sums -> u = a V / sigma * sqrt(n_fit)
 // for rows that were not in the fit, on the stage entries the fit itself runs (knn.hip, lae.hip, sparse.hip).  The fit
 // that makes the handle is capi.hip's flgp_heat_kernel_spectrum_model.  The chain up to the weights (model_rows) is shared
-// with the fitted predictor (predictor.hip, f-20), which puts its row kernel in the place of U-recovery.
+// with the fitted predictor (predictor.hip, f-20), which puts its row kernel (predictor_rows.hip) in the place of U-recovery.
+// Both walk their rows through common.h's for_row_blocks.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -58,32 +59,19 @@ struct ExtendWork : ModelRowWork {
   }
 };
 
-// rows [0, nb) of dX (ldx) into rows [0, nb) of d_out (ldo): asynchronous on `st`
-int extend_block(hipStream_t st, const flgp_spectrum_model *m, ExtendWork &W, const double *dX, int nb, int ldx, double *d_out,
-                 int ldo) {
-  FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
-  // sqrt(n_fit): the scale of the fit's rows, whatever the number of new ones
-  return flgp_dev_u_recover(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)m->V.p, m->s, m->s,
-                            (const double *)m->eig.p, m->K, std::sqrt((double)m->n_fit), m->root, d_out, ldo, nullptr,
-                            W.uwork.as<double>());
-}
-
-// host rows X (n_new x d, ld n_new) block by block into d_out (+ row offset already applied, ldo): synchronises `st`
-int extend_from_host(hipStream_t st, const flgp_spectrum_model *m, const double *X, int n_new, double *d_out, int ldo) {
-  const int B = std::min(model_block_rows(), n_new), d = m->d;
+// the n_new rows of `points` block by block into d_out (+ row offset already applied, ldo): synchronises `st`
+int extend_rows(hipStream_t st, const flgp_spectrum_model *m, RowPoints &points, int n_new, double *d_out, int ldo) {
+  const int B = std::min(model_block_rows(), n_new);
   ExtendWork W;
-  DevBuf dX;
   FLGP_TRY(W.alloc(m, B));
-  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
-  for (long i0 = 0; i0 < n_new; i0 += B) {
-    const int nb = (int)std::min<long>(B, n_new - i0);
-    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_new, sizeof(double) * (size_t)nb, d,
-                              hipMemcpyHostToDevice, st));
-    FLGP_TRY(check_finite_on_device(st, dX.as<double>(), (long)nb * d, "points"));
-    FLGP_TRY(extend_block(st, m, W, dX.as<double>(), nb, nb, d_out + i0, ldo));
-  }
-  FLGP_HIP(hipStreamSynchronize(st));
-  return FLGP_OK;
+  const int rc = for_row_blocks(st, points, n_new, m->d, B, [&](long i0, const double *dX, int nb, int ldx) -> int {
+    FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
+    // sqrt(n_fit): the scale of the fit's rows, whatever the number of new ones
+    return flgp_dev_u_recover(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)m->V.p, m->s, m->s,
+                              (const double *)m->eig.p, m->K, std::sqrt((double)m->n_fit), m->root, d_out + i0, ldo, nullptr,
+                              W.uwork.as<double>());
+  });
+  return settle(st, rc);                  // (the workspaces die here)
 }
 
 }  // namespace
@@ -96,13 +84,8 @@ extern "C" int flgp_dev_spectrum_model_extend(void *stream, const flgp_spectrum_
   FLGP_REQUIRE(ldx >= n_new && ldv >= n_new, "spectrum_model_extend: a leading dimension is below n_new = %d", n_new);
   FLGP_REQUIRE(m, "spectrum_model_extend: null handle");
   FLGP_TRY(on_model_device(m, "spectrum_model_extend"));
-  const int B = std::min(model_block_rows(), n_new);
-  ExtendWork W;
-  FLGP_TRY(W.alloc(m, B));
-  for (long i0 = 0; i0 < n_new; i0 += B)
-    FLGP_TRY(extend_block(st, m, W, dX + i0, (int)std::min<long>(B, n_new - i0), ldx, d_vectors + i0, ldv));
-  FLGP_HIP(hipStreamSynchronize(st));     // (the workspaces die here)
-  return FLGP_OK;
+  RowPoints points{dX, ldx};
+  return extend_rows(st, m, points, n_new, d_vectors, ldv);
 }
 
 extern "C" int flgp_spectrum_model_dims(const flgp_spectrum_model *m, int *n_fit, int *d, int *s, int *r, int *K, int *kernel_se,
@@ -150,8 +133,9 @@ extern "C" int flgp_spectrum_model_extend(const flgp_spectrum_model *m, const do
   Stream st;
   FLGP_TRY(st.create());
   DevBuf dvec;
+  RowPoints points{nullptr, 0, X};
   FLGP_TRY(dvec.alloc(sizeof(double) * (size_t)n_new * m->K));
-  FLGP_TRY(extend_from_host(st.s, m, X, n_new, dvec.as<double>(), n_new));
+  FLGP_TRY(extend_rows(st.s, m, points, n_new, dvec.as<double>(), n_new));
   FLGP_TRY(d2h(vectors, dvec.p, sizeof(double) * (size_t)n_new * m->K, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));
   return FLGP_OK;
@@ -191,7 +175,8 @@ extern "C" int flgp_spectrum_model_extend_resident(const flgp_spectrum_model *m,
     FLGP_TRY(h2d(drows.p, head_rows, sizeof(int) * (size_t)n_head, st.s));
     FLGP_TRY(gather_rows_ld(st.s, (const double *)head->vectors.p, head->n, drows.as<int>(), n_head, K, ep->vectors.as<double>(), n));
   }
-  FLGP_TRY(extend_from_host(st.s, m, X, n_new, ep->vectors.as<double>() + n_head, n));
+  RowPoints points{nullptr, 0, X};
+  FLGP_TRY(extend_rows(st.s, m, points, n_new, ep->vectors.as<double>() + n_head, n));
   *out = ep.release();
   return FLGP_OK;
 }

@@ -4,14 +4,17 @@
 // so that the posterior of a row that arrives later is z_i = a_i P on the row's r scaled anchor weights: its last q entries
 // the mean, c plus the squares of its first K entries the variance.  No n_new x K array exists.  The trained operands come
 // from the bodies of the entries the handle mirrors (eigenpair.hip: regression_operands, logit_operands); the row chain up
-// to the weights is the model's (model.hip: model_rows).
+// to the weights is the model's (model.hip: model_rows); the row kernels are predictor_rows.hip's.
 // The same handle over one bandwidth of a Nystrom grid (f-21): the anchor side is the grid's pre-scaled eigenvectors V', the
 // weights are dense and the row path is nystrom_predictor.hip's.
 // A Polya-Gamma handle (f-22) keeps the B mean columns alone, P(:, b) = B u_b with u_b = L (V1^T w_b) of chain b (eigenpair.hip:
-// pg_operands): a served row's latent is a_i P, its pi, y and label the link's (predictor_pg_rows_kernel, pg_link_kernel).
+// pg_operands): a served row's latent is a_i P, its pi, y and label the link's (predictor_rows.hip: predictor_pg_rows_kernel,
+// pg_link_kernel).
 // The joint posterior of served rows (f-23): the K columns of a group are the features z_i, z_i . z_j the latent covariance of
 // two rows, and a draws handle keeps P_draw(:, col) = P_mean(:, c) + P_K xi_col, mean columns alone, served like any mean
 // (predictor_cols.hip: the wide row kernel, the normals and the fold; nystrom_predictor.hip: the columns-out route).
+// This file holds the handle and the host routes.  Every entry over served rows is one walk of common.h's for_row_blocks with
+// its block body over a RowWork; its host and its device entry share that walk and one argument check.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -34,195 +37,40 @@ struct flgp_predictor {
   bool consistent = false;
 };
 
-namespace flgp {
-
-// One wave per (row, group).  Lane l of column chunk c holds column j = 64 c + l of the group's K + q: z is the chain over
-// a ascending, multiply then add, from 0.0.  A column j >= K is the mean's entry j - K.  For j < K the lane adds z^2 to its
-// own sum, so lane l holds S_l = the squares of k = l, l + 64, l + 128, .. added in that order from 0.0 (0.0 where K <= l);
-// then six butterfly steps S_l <- S_l + S_(l xor o), o = 32, 16, 8, 4, 2, 1, leave the same total in every lane and
-// var = cg + S_0.  The order is a function of (K, k) alone, every term is a square, and nothing depends on the grid.
-// The row's r (index, value) pairs sit in lanes 0 .. r-1 and are broadcast from there: they are wave-uniform, so a row of P
-// is one coalesced load per chunk.
-constexpr int PRED_WAVES = 4;
-__global__ __launch_bounds__(PRED_WAVES * 64) void predictor_rows_kernel(const int *__restrict__ ell_idx,
-                                                                          const double *__restrict__ ell_val, int n, int r,
-                                                                          const double *__restrict__ P, long ldp, int groups,
-                                                                          int K, int q, const double *__restrict__ cg,
-                                                                          double *__restrict__ mean, long ldm,
-                                                                          double *__restrict__ var, long ldv) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int w = K + q;
-  // the columns a call needs: the mean's alone where var is skipped, the squares' alone where the mean is
-  const int j_lo = var ? 0 : K, j_hi = mean ? w : K;
-  const int c_lo = j_lo / 64, c_hi = (j_hi + 63) / 64;
-  for (long i = (long)blockIdx.x * PRED_WAVES + wave; i < n; i += (long)gridDim.x * PRED_WAVES) {
-    int my_idx = 0;
-    double my_val = 0.0;
-    if (lane < r) { my_idx = ell_idx[i * r + lane]; my_val = ell_val[i * r + lane]; }
-    for (int g = blockIdx.y; g < groups; g += gridDim.y) {
-      const double *__restrict__ Pg = P + (long)g * w;
-      double sq = 0.0;
-      for (int c = c_lo; c < c_hi; ++c) {
-        const int j = c * 64 + lane;
-        const bool on = j >= j_lo && j < j_hi;
-        double z = 0.0;
-        for (int a = 0; a < r; ++a) {           // every lane takes the broadcast; a lane past the columns loads nothing
-          const long ja = __builtin_amdgcn_readlane(my_idx, a);
-          const double va = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_val), a),
-                                             __builtin_amdgcn_readlane(__double2loint(my_val), a));
-          if (on) z = z + va * Pg[ja * ldp + j];
-        }
-        if (on) {
-          if (j < K) sq = sq + z * z;
-          else mean[((long)g * q + (j - K)) * ldm + i] = z;
-        }
-      }
-      if (var) {
-        for (int o = 32; o >= 1; o >>= 1) sq = sq + __shfl_xor(sq, o);
-        if (lane == 0) var[(long)g * ldv + i] = cg[g] + sq;
-      }
-    }
-  }
-}
-
-// The Polya-Gamma handle's rows (f-22): P holds the B mean columns alone, column b chain b.  One wave per row; lane l of
-// chunk c owns chain b = 64 c + l: f is the chain over a ascending, multiply then add, from 0.0 (predictor_rows_kernel's
-// mean column), pi = 1 / (1 + exp(-f)) and y = (pi > 0.5) are pg_pi_kernel's expressions.  label: every lane keeps the
-// (largest pi, its first chain) of its own chunks -- a later chunk replaces only on a strictly larger value -- and six
-// butterfly steps combine (value, chain) pairs: the larger value wins, at equal values the lower chain, so every lane ends
-// with the first chain of maximal pi, pg_argmax_kernel's answer (a NaN is never larger; a NaN in chain 0 gives 0 as there).
-// Any output may be nullptr; the exponential is skipped where f alone is wanted.
-__global__ __launch_bounds__(PRED_WAVES * 64) void predictor_pg_rows_kernel(const int *__restrict__ ell_idx,
-                                                                             const double *__restrict__ ell_val, int n, int r,
-                                                                             const double *__restrict__ P, long ldp, int B,
-                                                                             double *__restrict__ f, long ldf,
-                                                                             double *__restrict__ pi, long ldpi,
-                                                                             double *__restrict__ y, long ldy,
-                                                                             double *__restrict__ label) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c_hi = (B + 63) / 64;
-  const bool link = pi || y || label;
-  for (long i = (long)blockIdx.x * PRED_WAVES + wave; i < n; i += (long)gridDim.x * PRED_WAVES) {
-    int my_idx = 0;
-    double my_val = 0.0;
-    if (lane < r) { my_idx = ell_idx[i * r + lane]; my_val = ell_val[i * r + lane]; }
-    double best = -1.0, first = 0.0;            // pi >= 0: any chain beats a lane without one
-    int loc = 0x7fffffff;
-    for (int c = 0; c < c_hi; ++c) {
-      const int b = c * 64 + lane;
-      const bool on = b < B;
-      double z = 0.0;
-      for (int a = 0; a < r; ++a) {
-        const long ja = __builtin_amdgcn_readlane(my_idx, a);
-        const double va = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_val), a),
-                                           __builtin_amdgcn_readlane(__double2loint(my_val), a));
-        if (on) z = z + va * P[ja * ldp + b];
-      }
-      if (on) {
-        if (f) f[(long)b * ldf + i] = z;
-        if (link) {
-          const double v = 1.0 / (1.0 + exp(-z));
-          if (pi) pi[(long)b * ldpi + i] = v;
-          if (y) y[(long)b * ldy + i] = v > 0.5 ? 1.0 : 0.0;
-          if (c == 0) first = v;
-          if (v > best) { best = v; loc = b; }
-        }
-      }
-    }
-    if (label) {
-      for (int o = 32; o >= 1; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int ol = __shfl_xor(loc, o);
-        if (ob > best || (ob == best && ol < loc)) { best = ob; loc = ol; }
-      }
-      if (lane == 0) label[i] = (first != first || loc == 0x7fffffff) ? 0.0 : (double)loc;
-    }
-  }
-}
-
-// the same three expressions on a latent that exists: a thread per row, the chains ascending (pg_argmax_kernel's loop)
-__global__ void pg_link_kernel(long n, int B, const double *__restrict__ f, long ldf, double *__restrict__ pi, long ldpi,
-                               double *__restrict__ y, long ldy, double *__restrict__ label) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double best = 0.0;
-  int loc = 0;
-  for (int b = 0; b < B; ++b) {
-    const double v = 1.0 / (1.0 + exp(-f[(long)b * ldf + i]));
-    if (pi) pi[(long)b * ldpi + i] = v;
-    if (y) y[(long)b * ldy + i] = v > 0.5 ? 1.0 : 0.0;
-    if (b == 0) best = v;
-    else if (v > best) { best = v; loc = b; }
-  }
-  if (label) label[i] = (double)loc;
-}
-
-}  // namespace flgp
-
-extern "C" int flgp_dev_predictor_pg_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r, const double *d_P,
-                                          long ldp, int s, int B, double *d_f, long ldf, double *d_pi, long ldpi, double *d_y, long ldy,
-                                          double *d_label) {
-  const char *who = "predictor_pg_rows";
-  FLGP_REQUIRE(d_ell_idx && d_ell_val && d_P, "%s: null pointer", who);
-  FLGP_REQUIRE(d_f || d_pi || d_y || d_label, "%s: null pointer (no output is wanted)", who);
-  FLGP_REQUIRE(n >= 1 && r >= 1 && r <= FLGP_RMAX && s >= 1 && B >= 1, "%s: bad shape (n=%d, r=%d, s=%d, B=%d)", who, n, r, s, B);
-  FLGP_REQUIRE(ldp >= B, "%s: ldp=%ld is below B = %d", who, ldp, B);
-  FLGP_REQUIRE((!d_f || ldf >= n) && (!d_pi || ldpi >= n) && (!d_y || ldy >= n), "%s: a leading dimension is below n = %d", who, n);
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("predictor_pg_rows", st, 2.0 * (double)n * r * B);
-  hipLaunchKernelGGL(predictor_pg_rows_kernel, dim3(std::min(ceil_div(n, PRED_WAVES), 1 << 20)), dim3(PRED_WAVES * 64), 0, st, d_ell_idx,
-                     d_ell_val, n, r, d_P, ldp, B, d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
-  return check_launch("predictor_pg_rows_kernel");
-}
-
-extern "C" int flgp_dev_pg_link(void *stream, const double *d_f, long ldf, int n, int B, double *d_pi, long ldpi, double *d_y, long ldy,
-                                double *d_label) {
-  const char *who = "pg_link";
-  FLGP_REQUIRE(d_f, "%s: null pointer", who);
-  FLGP_REQUIRE(d_pi || d_y || d_label, "%s: null pointer (no output is wanted)", who);
-  FLGP_REQUIRE(n >= 1 && B >= 1, "%s: bad shape (n=%d, B=%d)", who, n, B);
-  FLGP_REQUIRE(ldf >= n && (!d_pi || ldpi >= n) && (!d_y || ldy >= n), "%s: a leading dimension is below n = %d", who, n);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(pg_link_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (long)n, B, d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
-  return check_launch("pg_link_kernel");
-}
-
-extern "C" int flgp_dev_predictor_rows(void *stream, const int *d_ell_idx, const double *d_ell_val, int n, int r,
-                                       const double *d_P, long ldp, int s, int groups, int K, int q, const double *d_cg,
-                                       double *d_mean, long ldm, double *d_var, long ldv) {
-  const char *who = "predictor_rows";
-  FLGP_REQUIRE(d_ell_idx && d_ell_val && d_P, "%s: null pointer", who);
-  FLGP_REQUIRE(d_mean || d_var, "%s: null pointer (no output is wanted)", who);
-  FLGP_REQUIRE(!d_var || d_cg, "%s: null pointer (the variance needs cg)", who);
-  FLGP_REQUIRE(n >= 1 && r >= 1 && r <= FLGP_RMAX && s >= 1 && groups >= 1 && K >= 1 && q >= 0,
-               "%s: bad shape (n=%d, r=%d, s=%d, groups=%d, K=%d, q=%d)", who, n, r, s, groups, K, q);
-  FLGP_REQUIRE(!d_mean || q >= 1, "%s: a mean needs q >= 1 (q=%d)", who, q);
-  FLGP_REQUIRE(ldp >= (long)groups * ((long)K + q), "%s: ldp=%ld is below groups (K + q) = %ld", who, ldp,
-               (long)groups * ((long)K + q));
-  FLGP_REQUIRE((!d_mean || ldm >= n) && (!d_var || ldv >= n), "%s: a leading dimension is below n = %d", who, n);
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("predictor_rows", st, 2.0 * (double)n * r * groups * ((double)K + q));
-  const dim3 grid(std::min(ceil_div(n, PRED_WAVES), 1 << 20), std::min(groups, 65535));
-  hipLaunchKernelGGL(predictor_rows_kernel, grid, dim3(PRED_WAVES * 64), 0, st, d_ell_idx, d_ell_val, n, r, d_P, ldp, groups, K, q,
-                     d_cg, d_mean, ldm, d_var, ldv);
-  return check_launch("predictor_rows_kernel");
-}
-
 namespace {
 
-// what a create entry checks about the model (not null: looked at first) and the pair after its mirrored entry's checks; the
-// comparison of the values is the first device work
+// whether the pair's K values are the K device values at d_values, bit for bit: the first device work of a create
+int same_values(const flgp_eigenpair *ep, const double *d_values, bool &same) {
+  std::vector<double> a((size_t)ep->K), b((size_t)ep->K);
+  FLGP_HIP(hipMemcpy(a.data(), ep->values.p, sizeof(double) * a.size(), hipMemcpyDeviceToHost));
+  FLGP_HIP(hipMemcpy(b.data(), d_values, sizeof(double) * b.size(), hipMemcpyDeviceToHost));
+  same = std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0;
+  return FLGP_OK;
+}
+
+// what a create entry checks about the model (not null: looked at first) and the pair after its mirrored entry's checks
 int check_model(const char *who, const flgp_spectrum_model *model, const flgp_eigenpair *ep) {
   FLGP_REQUIRE(ep->K == model->K, "%s: the pair has K = %d, the model K = %d", who, ep->K, model->K);
   int dev = -1;
   FLGP_HIP(hipGetDevice(&dev));
   FLGP_REQUIRE(dev == model->device && dev == ep->device, "%s: the model lives on device %d, the pair on device %d, the current device is %d",
                who, model->device, ep->device, dev);
-  std::vector<double> a((size_t)ep->K), b((size_t)ep->K);
-  FLGP_HIP(hipMemcpy(a.data(), ep->values.p, sizeof(double) * a.size(), hipMemcpyDeviceToHost));
-  FLGP_HIP(hipMemcpy(b.data(), model->values.p, sizeof(double) * b.size(), hipMemcpyDeviceToHost));
-  FLGP_REQUIRE(std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0,
-               "%s: the pair's values are not the model's (a pair from another fit)", who);
+  bool same = false;
+  FLGP_TRY(same_values(ep, (const double *)model->values.p, same));
+  FLGP_REQUIRE(same, "%s: the pair's values are not the model's (a pair from another fit)", who);
+  return FLGP_OK;
+}
+
+// the same about bandwidth i of a Nystrom grid (f-21)
+int check_grid(const char *who, const flgp_nystrom_grid *grid, int i, const flgp_eigenpair *ep) {
+  FLGP_REQUIRE(ep->K == grid->K, "%s: the pair has K = %d, the grid K = %d", who, ep->K, grid->K);
+  int dev = -1;
+  FLGP_HIP(hipGetDevice(&dev));
+  FLGP_REQUIRE(dev == grid->device && dev == ep->device, "%s: the grid lives on device %d, the pair on device %d, the current device is %d",
+               who, grid->device, ep->device, dev);
+  bool same = false;
+  FLGP_TRY(same_values(ep, grid->values_of(i), same));
+  FLGP_REQUIRE(same, "%s: the pair's values are not those of bandwidth %d (a pair from another bandwidth or grid)", who, i);
   return FLGP_OK;
 }
 
@@ -283,48 +131,58 @@ int on_handle_device(const flgp_predictor *h, const char *who) {
   return FLGP_OK;
 }
 
-// rows [0, nb) of dX (ldx): the model's row chain up to the weights, then the row kernel; asynchronous on `st`
-int apply_block(hipStream_t st, const flgp_predictor *h, ModelRowWork &W, const double *dX, int nb, int ldx, double *d_mean, long ldm,
-                double *d_var, long ldv) {
-  const flgp_spectrum_model *m = h->model;
-  FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
-  return flgp_dev_predictor_rows(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, m->s, h->groups,
-                                 h->K, h->q, (const double *)h->cg.p, d_mean, ldm, d_var, ldv);
-}
-
-// ---- a Nystrom handle (f-21): what create checks after the mirrored entry's checks, and the row blocks of apply
-int check_grid(const char *who, const flgp_nystrom_grid *grid, int i, const flgp_eigenpair *ep) {
-  FLGP_REQUIRE(ep->K == grid->K, "%s: the pair has K = %d, the grid K = %d", who, ep->K, grid->K);
-  int dev = -1;
-  FLGP_HIP(hipGetDevice(&dev));
-  FLGP_REQUIRE(dev == grid->device && dev == ep->device, "%s: the grid lives on device %d, the pair on device %d, the current device is %d",
-               who, grid->device, ep->device, dev);
-  std::vector<double> a((size_t)ep->K), b((size_t)ep->K);
-  FLGP_HIP(hipMemcpy(a.data(), ep->values.p, sizeof(double) * a.size(), hipMemcpyDeviceToHost));
-  FLGP_HIP(hipMemcpy(b.data(), grid->values_of(i), sizeof(double) * b.size(), hipMemcpyDeviceToHost));
-  FLGP_REQUIRE(std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0,
-               "%s: the pair's values are not those of bandwidth %d (a pair from another bandwidth or grid)", who, i);
-  return FLGP_OK;
-}
-
-// rows per block: min(R(1) of the extension, model_extend_block), and the workspace of one block
-struct NystromRowWork {
-  DevBuf work;
-  size_t bytes = 0;
-  int B = 0;
-  int alloc(const flgp_predictor *h, int n_new, bool want_var) {
-    B = std::min(nys_row_block(h->s, h->K, n_new), std::min(model_block_rows(), n_new));
-    bytes = flgp_dev_nystrom_predictor_workspace(B, h->s, h->groups, h->K, h->q, want_var ? 1 : 0);
-    return work.alloc(bytes);
+// What serving a block of rows takes from a handle: the rows per block, the block's workspaces and the way from a block's
+// points to the operands of its row kernel -- for a model handle the row chain up to the weights (ell), for a Nystrom handle
+// the grid's anchor side in front of the three row routes of nystrom_predictor.hip.
+struct RowWork {
+  const flgp_predictor *h;
+  ModelRowWork M;
+  DevBuf nys, lat;                              // a Nystrom block's workspace; the PG route's own latent (nb x q at ld nb)
+  size_t nys_bytes = 0;
+  // rows per block: model_extend_block, and for a Nystrom handle R(1) of the extension where that is smaller
+  int rows(int n) const {
+    const int B = std::min(model_block_rows(), n);
+    return h->grid ? std::min(nys_row_block(h->s, h->K, n), B) : B;
+  }
+  // update's block: model_extend_block rounded down to a multiple of the Gram kernel's chunk, at least one chunk -- any
+  // multiple gives the same chain
+  static int update_rows() {
+    const int gc = predictor_gram_chunk();
+    return std::max(gc, model_block_rows() / gc * gc);
+  }
+  // a block of at most B rows: the row chain's workspaces of a model handle; `bytes` for the route a Nystrom handle is served by
+  int alloc(int B, size_t bytes = 0, bool own_latent = false) {
+    if (!h->grid) return M.alloc(h->model, B);
+    nys_bytes = bytes;
+    FLGP_TRY(nys.alloc(bytes));
+    return own_latent ? lat.alloc(sizeof(double) * (size_t)B * h->q) : FLGP_OK;
+  }
+  // rows [0, nb) of dX (ldx) through the model's row chain: their weights (nb x r); asynchronous on `st`
+  int ell(hipStream_t st, const double *dX, int nb, int ldx, const int *&idx, const double *&val) {
+    FLGP_TRY(model_rows(st, h->model, M, dX, nb, ldx));
+    idx = M.ell_idx.as<int>();
+    val = M.ell_val.as<double>();
+    return FLGP_OK;
+  }
+  int nystrom_rows(hipStream_t st, const double *dX, int nb, int ldx, double *d_mean, long ldm, double *d_var, long ldv) {
+    const flgp_nystrom_grid *G = h->grid;
+    return flgp_dev_nystrom_predictor_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p,
+                                           G->s, G->s, G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, h->groups, h->K,
+                                           h->q, (const double *)h->cg.p, d_mean, ldm, d_var, ldv, nys.p, nys_bytes);
+  }
+  int nystrom_mean(hipStream_t st, const double *dX, int nb, int ldx, int nc, double *d_out, long ldo) {
+    const flgp_nystrom_grid *G = h->grid;
+    return nystrom_mean_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
+                             G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, nc, d_out, ldo, nys.p, nys_bytes);
+  }
+  int nystrom_cols(hipStream_t st, const double *dX, int nb, int ldx, int c0, int nc, double *d_out, long ldo) {
+    const flgp_nystrom_grid *G = h->grid;
+    return nystrom_cols_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
+                             G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, c0, nc, d_out, ldo, nys.p, nys_bytes);
   }
 };
-int nystrom_apply_block(hipStream_t st, const flgp_predictor *h, NystromRowWork &W, const double *dX, int nb, int ldx, double *d_mean,
-                        long ldm, double *d_var, long ldv) {
-  const flgp_nystrom_grid *G = h->grid;
-  return flgp_dev_nystrom_predictor_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p,
-                                         G->s, G->s, G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, h->groups, h->K,
-                                         h->q, (const double *)h->cg.p, d_mean, ldm, d_var, ldv, W.work.p, W.bytes);
-}
+
+double *at(double *p, long i0) { return p ? p + i0 : nullptr; }
 
 // The create entries: one body per kind of posterior, shared by the two kinds of handle.  `check` is what the handle refuses
 // after the mirrored entry's checks (its last part the first device work), `begin` its Folder::begin.
@@ -394,35 +252,40 @@ int create_pg(const char *who, const flgp_eigenpair *ep, int K, const int *idx0,
   return FLGP_OK;
 }
 
-// ---- apply on a Polya-Gamma handle: the latent of a block, then the link
-int pg_apply_block(hipStream_t st, const flgp_predictor *h, ModelRowWork &W, const double *dX, int nb, int ldx, double *d_f, long ldf,
-                   double *d_pi, long ldpi, double *d_y, long ldy, double *d_label) {
-  const flgp_spectrum_model *m = h->model;
-  FLGP_TRY(model_rows(st, m, W, dX, nb, ldx));
-  return flgp_dev_predictor_pg_rows(st, W.ell_idx.as<int>(), W.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, m->s, h->q,
-                                    d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
+// ---- apply on a Polya-Gamma handle (f-22): the latent of a block, then the link.  What both entries refuse; `ld_ok`: the
+// device entry's leading dimensions, refused before the handle is looked at
+int pg_apply_check(const char *who, const flgp_predictor *h, const double *X, bool any_output, int n_new, bool ld_ok) {
+  FLGP_REQUIRE(X && any_output, "%s: null pointer", who);
+  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
+  FLGP_REQUIRE(ld_ok, "%s: a leading dimension is below n_new = %d", who, n_new);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_PG, "%s: the handle is not a Polya-Gamma one (kind %d)", who, h->kind);
+  return on_handle_device(h, who);
 }
-// a Nystrom handle: the mean-only route writes the block's latent (the caller's f, or `lat`: nb x q at ld nb), then the link
-struct NystromPgWork {
-  DevBuf work, lat;
-  size_t bytes = 0;
-  int B = 0;
-  int alloc(const flgp_predictor *h, int n_new, bool own_latent) {
-    B = std::min(nys_row_block(h->s, h->K, n_new), std::min(model_block_rows(), n_new));
-    bytes = nystrom_mean_workspace(B, h->s, h->q);
-    FLGP_TRY(work.alloc(bytes));
-    return own_latent ? lat.alloc(sizeof(double) * (size_t)B * h->q) : FLGP_OK;
-  }
-};
-int nystrom_pg_apply_block(hipStream_t st, const flgp_predictor *h, NystromPgWork &W, const double *dX, int nb, int ldx, double *d_f,
-                           long ldf, double *d_pi, long ldpi, double *d_y, long ldy, double *d_label) {
-  const flgp_nystrom_grid *G = h->grid;
-  double *lat = d_f ? d_f : W.lat.as<double>();
-  const long ldl = d_f ? ldf : nb;
-  FLGP_TRY(nystrom_mean_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
-                             G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, h->q, lat, ldl, W.work.p, W.bytes));
-  if (!(d_pi || d_y || d_label)) return FLGP_OK;
-  return flgp_dev_pg_link(st, lat, ldl, nb, h->q, d_pi, ldpi, d_y, ldy, d_label);
+
+// the n rows of `points` into the device outputs that are wanted; synchronises `st`.  A Nystrom handle: the mean-only route
+// writes the block's latent (the caller's f, or W.lat), then the link
+int pg_apply_rows(hipStream_t st, const flgp_predictor *h, RowPoints &points, int n, double *d_f, long ldf, double *d_pi, long ldpi,
+                  double *d_y, long ldy, double *d_label) {
+  RowWork W{h};
+  const int B = W.rows(n);
+  FLGP_TRY(W.alloc(B, h->grid ? nystrom_mean_workspace(B, h->s, h->q) : 0, d_f == nullptr));
+  const int rc = for_row_blocks(st, points, n, h->d, B, [&](long i0, const double *dX, int nb, int ldx) -> int {
+    double *f = at(d_f, i0), *pi = at(d_pi, i0), *y = at(d_y, i0), *label = at(d_label, i0);
+    if (!h->grid) {
+      const int *idx;
+      const double *val;
+      FLGP_TRY(W.ell(st, dX, nb, ldx, idx, val));
+      return flgp_dev_predictor_pg_rows(st, idx, val, nb, h->model->r, (const double *)h->P.p, h->ldp, h->s, h->q, f, ldf, pi, ldpi, y, ldy,
+                                        label);
+    }
+    double *lat = f ? f : W.lat.as<double>();
+    const long ldl = f ? ldf : nb;
+    FLGP_TRY(W.nystrom_mean(st, dX, nb, ldx, h->q, lat, ldl));
+    if (!(pi || y || label)) return FLGP_OK;
+    return flgp_dev_pg_link(st, lat, ldl, nb, h->q, pi, ldpi, y, ldy, label);
+  });
+  return settle(st, rc);                        // (the workspaces die here)
 }
 
 }  // namespace
@@ -456,72 +319,26 @@ extern "C" int flgp_predictor_nystrom_pg_create(const flgp_nystrom_grid *grid, i
 
 extern "C" int flgp_dev_predictor_pg_apply(void *stream, const flgp_predictor *h, const double *dX, int n_new, int ldx, double *d_f,
                                            long ldf, double *d_pi, long ldpi, double *d_y, long ldy, double *d_label) {
-  const char *who = "predictor_pg_apply";
-  hipStream_t st = (hipStream_t)stream;
-  FLGP_REQUIRE(dX && (d_f || d_pi || d_y || d_label), "%s: null pointer", who);
-  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
-  FLGP_REQUIRE(ldx >= n_new && (!d_f || ldf >= n_new) && (!d_pi || ldpi >= n_new) && (!d_y || ldy >= n_new),
-               "%s: a leading dimension is below n_new = %d", who, n_new);
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_PG, "%s: the handle is not a Polya-Gamma one (kind %d)", who, h->kind);
-  FLGP_TRY(on_handle_device(h, who));
-  auto at = [](double *p, long i0) { return p ? p + i0 : nullptr; };
-  if (h->grid) {
-    NystromPgWork W;
-    FLGP_TRY(W.alloc(h, n_new, d_f == nullptr));
-    for (long i0 = 0; i0 < n_new; i0 += W.B)
-      FLGP_TRY(nystrom_pg_apply_block(st, h, W, dX + i0, (int)std::min<long>(W.B, n_new - i0), ldx, at(d_f, i0), ldf, at(d_pi, i0), ldpi,
-                                      at(d_y, i0), ldy, at(d_label, i0)));
-    FLGP_HIP(hipStreamSynchronize(st));
-    return FLGP_OK;
-  }
-  const int B = std::min(model_block_rows(), n_new);
-  ModelRowWork W;
-  FLGP_TRY(W.alloc(h->model, B));
-  for (long i0 = 0; i0 < n_new; i0 += B)
-    FLGP_TRY(pg_apply_block(st, h, W, dX + i0, (int)std::min<long>(B, n_new - i0), ldx, at(d_f, i0), ldf, at(d_pi, i0), ldpi, at(d_y, i0),
-                            ldy, at(d_label, i0)));
-  FLGP_HIP(hipStreamSynchronize(st));     // (the workspaces die here)
-  return FLGP_OK;
+  FLGP_TRY(pg_apply_check("predictor_pg_apply", h, dX, d_f || d_pi || d_y || d_label, n_new,
+                          ldx >= n_new && (!d_f || ldf >= n_new) && (!d_pi || ldpi >= n_new) && (!d_y || ldy >= n_new)));
+  RowPoints points{dX, ldx};
+  return pg_apply_rows((hipStream_t)stream, h, points, n_new, d_f, ldf, d_pi, ldpi, d_y, ldy, d_label);
 }
 
 extern "C" int flgp_predictor_pg_apply(const flgp_predictor *h, const double *X, int n_new, double *f, double *pi, double *y,
                                        double *label) {
-  const char *who = "predictor_pg_apply";
-  FLGP_REQUIRE(X && (f || pi || y || label), "%s: null pointer", who);
-  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  FLGP_REQUIRE(h->kind == FLGP_PREDICTOR_PG, "%s: the handle is not a Polya-Gamma one (kind %d)", who, h->kind);
-  FLGP_TRY(on_handle_device(h, who));
-  const flgp_spectrum_model *m = h->model;
-  const int d = h->d, q = h->q;
+  FLGP_TRY(pg_apply_check("predictor_pg_apply", h, X, f || pi || y || label, n_new, true));
   Stream st;
   FLGP_TRY(st.create());
-  ModelRowWork W;
-  NystromPgWork NW;
-  DevBuf dX, df, dpi, dy, dlab;
-  if (h->grid) FLGP_TRY(NW.alloc(h, n_new, f == nullptr));
-  const int B = h->grid ? NW.B : std::min(model_block_rows(), n_new);
-  if (m) FLGP_TRY(W.alloc(m, B));
-  const size_t nq = sizeof(double) * (size_t)n_new * q;
-  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
+  DevBuf df, dpi, dy, dlab;
+  RowPoints points{nullptr, 0, X};
+  const size_t nq = sizeof(double) * (size_t)n_new * h->q;
   if (f) FLGP_TRY(df.alloc(nq));
   if (pi) FLGP_TRY(dpi.alloc(nq));
   if (y) FLGP_TRY(dy.alloc(nq));
   if (label) FLGP_TRY(dlab.alloc(sizeof(double) * (size_t)n_new));
-  auto at = [](DevBuf &b, bool want, long i0) { return want ? b.as<double>() + i0 : nullptr; };
-  for (long i0 = 0; i0 < n_new; i0 += B) {
-    const int nb = (int)std::min<long>(B, n_new - i0);
-    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_new, sizeof(double) * (size_t)nb, d,
-                              hipMemcpyHostToDevice, st.s));
-    FLGP_TRY(check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points"));
-    if (h->grid)
-      FLGP_TRY(nystrom_pg_apply_block(st.s, h, NW, dX.as<double>(), nb, nb, at(df, f, i0), n_new, at(dpi, pi, i0), n_new, at(dy, y, i0),
-                                      n_new, at(dlab, label, i0)));
-    else
-      FLGP_TRY(pg_apply_block(st.s, h, W, dX.as<double>(), nb, nb, at(df, f, i0), n_new, at(dpi, pi, i0), n_new, at(dy, y, i0), n_new,
-                              at(dlab, label, i0)));
-  }
+  FLGP_TRY(pg_apply_rows(st.s, h, points, n_new, f ? df.as<double>() : nullptr, n_new, pi ? dpi.as<double>() : nullptr, n_new,
+                         y ? dy.as<double>() : nullptr, n_new, label ? dlab.as<double>() : nullptr));
   if (f) FLGP_TRY(d2h(f, df.p, nq, st.s));
   if (pi) FLGP_TRY(d2h(pi, dpi.p, nq, st.s));
   if (y) FLGP_TRY(d2h(y, dy.p, nq, st.s));
@@ -597,96 +414,46 @@ int fits_free_memory(const char *who, const char *what, double bytes) {
   return FLGP_OK;
 }
 
-// the rows per block and the workspaces of one block.  `mean_route`: a Nystrom draws handle of at most 8 columns takes the
-// mean-only route (nystrom_mean_rows); every other Nystrom call the columns-out route
-struct ColsWork {
-  ModelRowWork M;
-  DevBuf nys;
-  size_t nys_bytes = 0;
-  int B = 0;
-  bool mean_route = false;
-  static int rows(const flgp_predictor *h, int n) {
-    const int B = std::min(model_block_rows(), n);
-    return h->grid ? std::min(nys_row_block(h->s, h->K, n), B) : B;
-  }
-  static size_t bytes(const flgp_predictor *h, int B, int nc, bool mean_route) {
-    if (!h->grid) return (sizeof(int) + sizeof(double)) * (size_t)B * (size_t)(2 * h->model->r);
-    return mean_route ? nystrom_mean_workspace(B, h->s, nc) : nystrom_cols_workspace(B, h->s, nc);
-  }
-  int alloc(const flgp_predictor *h, int n, int nc, bool mean) {
-    B = rows(h, n);
-    mean_route = mean;
-    if (!h->grid) return M.alloc(h->model, B);
-    nys_bytes = bytes(h, B, nc, mean);
-    return nys.alloc(nys_bytes);
-  }
-};
-
-int cols_block(hipStream_t st, const flgp_predictor *h, ColsWork &W, const double *dX, int nb, int ldx, int c0, int nc, double *d_out,
-               long ldo) {
-  if (!h->grid) {
-    const flgp_spectrum_model *m = h->model;
-    FLGP_TRY(model_rows(st, m, W.M, dX, nb, ldx));
-    return flgp_dev_predictor_cols(st, W.M.ell_idx.as<int>(), W.M.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, m->s, c0,
-                                   nc, d_out, ldo);
-  }
-  const flgp_nystrom_grid *G = h->grid;
-  if (W.mean_route) {      // a draws handle's whole P_draw: the mean-only route takes its columns from 0
+// the n rows of `points` into d_out (n x nc, ldo), which stays on the device; synchronises `st`.  A Nystrom draws handle of at
+// most 8 columns takes the mean-only route (nystrom_mean_rows); every other Nystrom call the columns-out route
+int cols_rows(const char *who, hipStream_t st, const flgp_predictor *h, RowPoints &points, int n, int c0, int nc, double *d_out,
+              long ldo) {
+  const bool mean_route = h->grid && h->kind == FLGP_PREDICTOR_DRAWS && h->q <= 8;
+  RowWork W{h};
+  const int B = W.rows(n);
+  const size_t bytes = !h->grid      ? (sizeof(int) + sizeof(double)) * (size_t)B * (size_t)(2 * h->model->r)
+                       : mean_route ? nystrom_mean_workspace(B, h->s, nc)
+                                    : nystrom_cols_workspace(B, h->s, nc);
+  if (points.X)
+    FLGP_TRY(fits_free_memory(who, "a row block and its workspace", (double)bytes + sizeof(double) * (double)B * h->d));
+  else
+    FLGP_TRY(fits_free_memory(who, "the workspace of a row block", (double)bytes));
+  FLGP_TRY(W.alloc(B, bytes));
+  const int rc = for_row_blocks(st, points, n, h->d, B, [&](long i0, const double *dX, int nb, int ldx) -> int {
+    if (!h->grid) {
+      const int *idx;
+      const double *val;
+      FLGP_TRY(W.ell(st, dX, nb, ldx, idx, val));
+      return flgp_dev_predictor_cols(st, idx, val, nb, h->model->r, (const double *)h->P.p, h->ldp, h->s, c0, nc, d_out + i0, ldo);
+    }
+    if (!mean_route) return W.nystrom_cols(st, dX, nb, ldx, c0, nc, d_out + i0, ldo);
+    // a draws handle's whole P_draw: the mean-only route takes its columns from 0
     FLGP_REQUIRE(c0 == 0, "predictor: the mean-only route serves columns from 0 (c0=%d)", c0);
-    return nystrom_mean_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
-                             G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, nc, d_out, ldo, W.nys.p, W.nys_bytes);
-  }
-  return nystrom_cols_rows(st, dX, nb, ldx, G->d, (const double *)G->Ut.p, (const double *)G->uu.p, (const double *)G->U.p, G->s, G->s,
-                           G->inv_c[h->gi], G->rsu_of(h->gi), (const double *)h->P.p, h->ldp, c0, nc, d_out, ldo, W.nys.p, W.nys_bytes);
+    return W.nystrom_mean(st, dX, nb, ldx, nc, d_out + i0, ldo);
+  });
+  return settle(st, rc);                        // (the workspaces die here)
 }
 
-bool draws_mean_route(const flgp_predictor *h) { return h->grid && h->kind == FLGP_PREDICTOR_DRAWS && h->q <= 8; }
-
-// device rows: block by block on `st`, which is synchronised before the workspaces die
-int cols_from_device(const char *who, hipStream_t st, const flgp_predictor *h, const double *dX, int n, int ldx, int c0, int nc,
-                     double *d_out, long ldo) {
-  const bool mean = draws_mean_route(h);
-  const int B = ColsWork::rows(h, n);
-  FLGP_TRY(fits_free_memory(who, "the workspace of a row block", (double)ColsWork::bytes(h, B, nc, mean)));
-  ColsWork W;
-  FLGP_TRY(W.alloc(h, n, nc, mean));
-  for (long i0 = 0; i0 < n; i0 += W.B)
-    FLGP_TRY(cols_block(st, h, W, dX + i0, (int)std::min<long>(W.B, n - i0), ldx, c0, nc, d_out + i0, ldo));
-  FLGP_HIP(hipStreamSynchronize(st));
-  return FLGP_OK;
-}
-
-// host rows: uploaded and screened block by block; the result stays on the device (d_out n x nc, ldo)
-int cols_from_host(const char *who, hipStream_t st, const flgp_predictor *h, const double *X, int n, int c0, int nc, double *d_out,
-                   long ldo) {
-  const bool mean = draws_mean_route(h);
-  const int B = ColsWork::rows(h, n), d = h->d;
-  FLGP_TRY(fits_free_memory(who, "a row block and its workspace",
-                            (double)ColsWork::bytes(h, B, nc, mean) + sizeof(double) * (double)B * d));
-  ColsWork W;
-  DevBuf dX;
-  FLGP_TRY(W.alloc(h, n, nc, mean));
-  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)W.B * d));
-  for (long i0 = 0; i0 < n; i0 += W.B) {
-    const int nb = (int)std::min<long>(W.B, n - i0);
-    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb, d,
-                              hipMemcpyHostToDevice, st));
-    FLGP_TRY(check_finite_on_device(st, dX.as<double>(), (long)nb * d, "points"));
-    FLGP_TRY(cols_block(st, h, W, dX.as<double>(), nb, nb, c0, nc, d_out + i0, ldo));
-  }
-  FLGP_HIP(hipStreamSynchronize(st));
-  return FLGP_OK;
-}
-
-// the same, down to the host (out n x nc column-major)
+// host rows, down to the host (out n x nc column-major)
 int cols_to_host(const char *who, const flgp_predictor *h, const double *X, int n, int c0, int nc, double *out) {
   const double bytes = sizeof(double) * (double)n * nc;
   FLGP_TRY(fits_free_memory(who, "the n x nc result", bytes));
   Stream st;
   FLGP_TRY(st.create());
   DevBuf d_out;
+  RowPoints points{nullptr, 0, X};
   FLGP_TRY(d_out.alloc((size_t)bytes));
-  FLGP_TRY(cols_from_host(who, st.s, h, X, n, c0, nc, d_out.as<double>(), n));
+  FLGP_TRY(cols_rows(who, st.s, h, points, n, c0, nc, d_out.as<double>(), n));
   FLGP_TRY(d2h(out, d_out.p, (size_t)bytes, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));
   return FLGP_OK;
@@ -698,6 +465,14 @@ int check_features(const char *who, const flgp_predictor *h, int g) {
   FLGP_REQUIRE(has_covariance_operand(h), "%s: a handle of kind %d has no covariance operand", who, h->kind);
   FLGP_REQUIRE(g >= 0 && g < h->groups, "%s: group %d outside 0..%d", who, g, h->groups - 1);
   return on_handle_device(h, who);
+}
+
+// what both features entries refuse; `ld_ok`: the device entry's leading dimensions
+int features_check(const char *who, const flgp_predictor *h, int g, const double *X, const double *Z, int n, bool ld_ok) {
+  FLGP_REQUIRE(X && Z, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
+  FLGP_REQUIRE(ld_ok, "%s: a leading dimension is below n = %d", who, n);
+  return check_features(who, h, g);
 }
 
 }  // namespace
@@ -748,18 +523,14 @@ extern "C" int flgp_predictor_draws_normals(const flgp_predictor *h, double *xi)
 extern "C" int flgp_dev_predictor_features(void *stream, const flgp_predictor *h, int g, const double *dX, int n, int ldx, double *dZ,
                                            long ldz) {
   const char *who = "predictor_features";
-  FLGP_REQUIRE(dX && dZ, "%s: null pointer", who);
-  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
-  FLGP_REQUIRE(ldx >= n && ldz >= n, "%s: a leading dimension is below n = %d", who, n);
-  FLGP_TRY(check_features(who, h, g));
-  return cols_from_device(who, (hipStream_t)stream, h, dX, n, ldx, g * (h->K + h->q), h->K, dZ, ldz);
+  FLGP_TRY(features_check(who, h, g, dX, dZ, n, ldx >= n && ldz >= n));
+  RowPoints points{dX, ldx};
+  return cols_rows(who, (hipStream_t)stream, h, points, n, g * (h->K + h->q), h->K, dZ, ldz);
 }
 
 extern "C" int flgp_predictor_features(const flgp_predictor *h, int g, const double *X, int n, double *Z) {
   const char *who = "predictor_features";
-  FLGP_REQUIRE(X && Z, "%s: null pointer", who);
-  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
-  FLGP_TRY(check_features(who, h, g));
+  FLGP_TRY(features_check(who, h, g, X, Z, n, true));
   return cols_to_host(who, h, X, n, g * (h->K + h->q), h->K, Z);
 }
 
@@ -775,12 +546,13 @@ extern "C" int flgp_predictor_covariance(const flgp_predictor *h, int g, const d
   Stream st;
   FLGP_TRY(st.create());
   DevBuf Za, Zb, dC;
+  RowPoints rows_a{nullptr, 0, Xa}, rows_b{nullptr, 0, Xb};
   FLGP_TRY(Za.alloc(sizeof(double) * (size_t)na * K));
   FLGP_TRY(dC.alloc(sizeof(double) * (size_t)na * nb));
-  FLGP_TRY(cols_from_host(who, st.s, h, Xa, na, c0, K, Za.as<double>(), na));
+  FLGP_TRY(cols_rows(who, st.s, h, rows_a, na, c0, K, Za.as<double>(), na));
   if (Xb) {
     FLGP_TRY(Zb.alloc(sizeof(double) * (size_t)nb * K));
-    FLGP_TRY(cols_from_host(who, st.s, h, Xb, nb, c0, K, Zb.as<double>(), nb));
+    FLGP_TRY(cols_rows(who, st.s, h, rows_b, nb, c0, K, Zb.as<double>(), nb));
   }
   const double *B = Xb ? Zb.as<double>() : Za.as<double>();
   FLGP_TRY(flgp_dev_gemm(st.s, na, nb, K, 1.0, Za.as<double>(), 1, na, B, nb, 1, 0.0, nullptr, 0, 0, dC.as<double>(), 1, na, nullptr, 0));
@@ -812,6 +584,20 @@ int update_check_handle(const char *who, const flgp_predictor *h) {
   return on_handle_device(h, who);
 }
 
+// what both update entries refuse before any device work, in the header's order; `ld_ok`: the device entry's leading dimensions
+int update_check(const char *who, const flgp_predictor *h, const double *X, const double *Y, int n_b, const double *noise, int n_noise,
+                 flgp_predictor **out, bool ld_ok) {
+  FLGP_REQUIRE(out, "%s: null pointer (out)", who);
+  *out = nullptr;
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(X && Y, "%s: null pointer", who);
+  FLGP_REQUIRE(n_b >= 1, "%s: need n_b >= 1 (n_b=%d)", who, n_b);
+  FLGP_REQUIRE(noise ? (n_noise == 1 || n_noise == n_b) : n_noise == 0, "%s: n_noise=%d must be 0 with a NULL noise, 1 or n_b=%d", who,
+               n_noise, n_b);
+  FLGP_REQUIRE(ld_ok, "%s: a leading dimension is below n_b = %d", who, n_b);
+  return update_check_handle(who, h);
+}
+
 // w_i = 1 / (noise_i + sigma) on the host; noise NULL: the create's noise[0]
 int update_weights(const char *who, const flgp_predictor *h, const double *noise, int n_noise, int n_b, std::vector<double> &w) {
   for (int a = 0; a < n_noise; ++a) {
@@ -824,19 +610,14 @@ int update_weights(const char *who, const flgp_predictor *h, const double *noise
 }
 
 struct UpdateRun {
-  const flgp_predictor *h;
-  ModelRowWork M;
+  RowWork W;
   DevBuf S, dW, part;
   int B = 0;                                    // rows per block: a multiple of the Gram kernel's chunk
-  // the block: model_extend_block rounded down to a multiple of the chunk, at least one chunk -- any multiple gives the same chain
-  static int rows(const flgp_predictor *) {
-    const int gc = predictor_gram_chunk();
-    return std::max(gc, model_block_rows() / gc * gc);
-  }
   int begin(hipStream_t st, int n_b, const std::vector<double> &w) {
+    const flgp_predictor *h = W.h;
     const int Wd = h->K + h->q;
-    B = rows(h);
-    FLGP_TRY(M.alloc(h->model, std::min(B, n_b)));
+    B = RowWork::update_rows();
+    FLGP_TRY(W.alloc(std::min(B, n_b)));
     FLGP_TRY(S.alloc(sizeof(double) * (size_t)Wd * Wd));
     FLGP_TRY(part.alloc(predictor_gram_bytes(std::min(B, n_b), h->K, h->q)));
     FLGP_TRY(dW.alloc(sizeof(double) * (size_t)n_b));
@@ -844,13 +625,16 @@ struct UpdateRun {
   }
   // rows [i0, i0 + nb) of the call: dX their points (ldx), dY their responses (ldy)
   int block(hipStream_t st, long i0, const double *dX, int nb, int ldx, const double *dY, long ldy) {
-    const flgp_spectrum_model *m = h->model;
-    FLGP_TRY(model_rows(st, m, M, dX, nb, ldx));
-    return predictor_gram(st, M.ell_idx.as<int>(), M.ell_val.as<double>(), nb, m->r, (const double *)h->P.p, h->ldp, h->K, h->q,
-                          dW.as<double>() + i0, dY, ldy, S.as<double>(), h->K + h->q, part.as<double>(), i0 == 0);
+    const flgp_predictor *h = W.h;
+    const int *idx;
+    const double *val;
+    FLGP_TRY(W.ell(st, dX, nb, ldx, idx, val));
+    return predictor_gram(st, idx, val, nb, h->model->r, (const double *)h->P.p, h->ldp, h->K, h->q, dW.as<double>() + i0, dY, ldy,
+                          S.as<double>(), h->K + h->q, part.as<double>(), i0 == 0);
   }
   // the fold; synchronises `st`
   int finish(hipStream_t st, const char *who, flgp_predictor **out) {
+    const flgp_predictor *h = W.h;
     const int K = h->K, q = h->q, s = h->s;
     const size_t wi = (size_t)32 * 64 * K;
     DevBuf Mk, R, Li, Tb, wt, flag;
@@ -884,10 +668,20 @@ struct UpdateRun {
   }
 };
 
-// a non-finite response: the q columns of dY (ldy) on the device
-int update_check_responses(hipStream_t st, const double *dY, long ldy, int n_b, int q) {
-  for (int c = 0; c < q; ++c) FLGP_TRY(check_finite_on_device(st, dY + (long)c * ldy, n_b, "predictor_update: the responses Y"));
-  return FLGP_OK;
+// The checked call once its responses dY (ldy) are on the device and its noise on the host: the responses' screen, the weights,
+// the row blocks and the fold; synchronises `st`
+int update_run(const char *who, hipStream_t st, const flgp_predictor *h, RowPoints &points, int n_b, const double *dY, long ldy,
+               const double *noise, int n_noise, flgp_predictor **out) {
+  for (int c = 0; c < h->q; ++c) FLGP_TRY(check_finite_on_device(st, dY + (long)c * ldy, n_b, "predictor_update: the responses Y"));
+  std::vector<double> w;
+  FLGP_TRY(update_weights(who, h, noise, n_noise, n_b, w));
+  UpdateRun U{{h}};
+  FLGP_TRY(U.begin(st, n_b, w));
+  int rc = for_row_blocks(st, points, n_b, h->d, U.B, [&](long i0, const double *dX, int nb, int ldx) -> int {
+    return U.block(st, i0, dX, nb, ldx, dY + i0, ldy);
+  });
+  if (rc == FLGP_OK) rc = U.finish(st, who, out);
+  return settle(st, rc);                        // (the workspaces die here)
 }
 
 }  // namespace
@@ -896,67 +690,27 @@ extern "C" int flgp_dev_predictor_update(void *stream, const flgp_predictor *h, 
                                          long ldy, const double *d_noise, int n_noise, flgp_predictor **out) {
   const char *who = "predictor_update";
   hipStream_t st = (hipStream_t)stream;
-  FLGP_REQUIRE(out, "%s: null pointer (out)", who);
-  *out = nullptr;
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  FLGP_REQUIRE(dX && dY, "%s: null pointer", who);
-  FLGP_REQUIRE(n_b >= 1, "%s: need n_b >= 1 (n_b=%d)", who, n_b);
-  FLGP_REQUIRE(d_noise ? (n_noise == 1 || n_noise == n_b) : n_noise == 0,
-               "%s: n_noise=%d must be 0 with a NULL noise, 1 or n_b=%d", who, n_noise, n_b);
-  FLGP_REQUIRE(ldx >= n_b && ldy >= n_b, "%s: a leading dimension is below n_b = %d", who, n_b);
-  FLGP_TRY(update_check_handle(who, h));
-  std::vector<double> noise((size_t)n_noise), w;
+  FLGP_TRY(update_check(who, h, dX, dY, n_b, d_noise, n_noise, out, ldx >= n_b && ldy >= n_b));
+  std::vector<double> noise((size_t)n_noise);
   if (n_noise) {
     FLGP_TRY(d2h(noise.data(), d_noise, sizeof(double) * (size_t)n_noise, st));
     FLGP_HIP(hipStreamSynchronize(st));
   }
-  FLGP_TRY(update_check_responses(st, dY, ldy, n_b, h->q));
-  FLGP_TRY(update_weights(who, h, noise.data(), n_noise, n_b, w));
-  UpdateRun U{h};
-  FLGP_TRY(U.begin(st, n_b, w));
-  int rc = FLGP_OK;
-  for (long i0 = 0; i0 < n_b && rc == FLGP_OK; i0 += U.B)
-    rc = U.block(st, i0, dX + i0, (int)std::min<long>(U.B, n_b - i0), ldx, dY + i0, ldy);
-  if (rc == FLGP_OK) rc = U.finish(st, who, out);
-  (void)hipStreamSynchronize(st);               // (the workspaces die here)
-  return rc;
+  RowPoints points{dX, ldx};
+  return update_run(who, st, h, points, n_b, dY, ldy, noise.data(), n_noise, out);
 }
 
 extern "C" int flgp_predictor_update(const flgp_predictor *h, const double *X, int n_b, const double *Y, const double *noise,
                                      int n_noise, flgp_predictor **out) {
   const char *who = "predictor_update";
-  FLGP_REQUIRE(out, "%s: null pointer (out)", who);
-  *out = nullptr;
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  FLGP_REQUIRE(X && Y, "%s: null pointer", who);
-  FLGP_REQUIRE(n_b >= 1, "%s: need n_b >= 1 (n_b=%d)", who, n_b);
-  FLGP_REQUIRE(noise ? (n_noise == 1 || n_noise == n_b) : n_noise == 0, "%s: n_noise=%d must be 0 with a NULL noise, 1 or n_b=%d", who,
-               n_noise, n_b);
-  FLGP_TRY(update_check_handle(who, h));
-  const int d = h->d, q = h->q;
+  FLGP_TRY(update_check(who, h, X, Y, n_b, noise, n_noise, out, true));
   Stream st;
   FLGP_TRY(st.create());
-  DevBuf dX, dY;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)n_b * q));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)n_b * q, st.s));
-  FLGP_TRY(update_check_responses(st.s, dY.as<double>(), n_b, n_b, q));
-  std::vector<double> w;
-  FLGP_TRY(update_weights(who, h, noise, n_noise, n_b, w));
-  UpdateRun U{h};
-  FLGP_TRY(U.begin(st.s, n_b, w));
-  const int B = std::min(U.B, n_b);
-  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
-  int rc = FLGP_OK;
-  for (long i0 = 0; i0 < n_b && rc == FLGP_OK; i0 += B) {
-    const int nb = (int)std::min<long>(B, n_b - i0);
-    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_b, sizeof(double) * (size_t)nb, d,
-                              hipMemcpyHostToDevice, st.s));
-    rc = check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points");
-    if (rc == FLGP_OK) rc = U.block(st.s, i0, dX.as<double>(), nb, nb, dY.as<double>() + i0, n_b);
-  }
-  if (rc == FLGP_OK) rc = U.finish(st.s, who, out);
-  (void)hipStreamSynchronize(st.s);
-  return rc;
+  DevBuf dY;
+  RowPoints points{nullptr, 0, X};
+  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)n_b * h->q));
+  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)n_b * h->q, st.s));
+  return update_run(who, st.s, h, points, n_b, dY.as<double>(), n_b, noise, n_noise, out);
 }
 
 // ---- f-25: which rows to label next.  The pool's rows go through the model's row chain block by block into n x r arrays; the
@@ -978,8 +732,17 @@ int design_check_handle(const char *who, const flgp_predictor *h) {
   return on_handle_device(h, who);
 }
 
-// refusal 8: d = noise + sigma, noise NULL = the create's noise[0]
-int design_variance(const char *who, const flgp_predictor *h, const double *noise, double *d) {
+// What both design entries refuse before any device work, in the header's order; `ld_ok`: the device entry's leading dimension.
+// Refusal 8 last: *d = noise + sigma, noise NULL = the create's noise[0]
+int design_check(const char *who, const flgp_predictor *h, const double *X, int n, int B, const double *noise, const int *picks, bool ld_ok,
+                 double *d) {
+  FLGP_REQUIRE(picks, "%s: null pointer (picks)", who);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  FLGP_REQUIRE(X, "%s: null pointer", who);
+  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
+  FLGP_REQUIRE(B >= 1 && B <= n, "%s: need 1 <= B <= n (B=%d, n=%d)", who, B, n);
+  FLGP_REQUIRE(ld_ok, "%s: a leading dimension is below n = %d", who, n);
+  FLGP_TRY(design_check_handle(who, h));
   const double nz = noise ? noise[0] : h->noise0;
   FLGP_REQUIRE(std::isfinite(nz), "%s: the noise must be finite", who);
   FLGP_REQUIRE(nz + h->sigma > 0.0, "%s: noise + sigma must be positive", who);
@@ -988,16 +751,16 @@ int design_variance(const char *who, const flgp_predictor *h, const double *nois
 }
 
 struct DesignRun {
-  const flgp_predictor *h;
-  ModelRowWork M;
+  RowWork W;
   DevBuf idx, val, work;
   int n = 0, Bd = 0, blk = 0;
   size_t work_bytes = 0;
   // the pool's rows, the workspace and the row chain's block, against the free memory; `extra`: what the entry holds besides
   int begin(const char *who, int n_, int B, double extra) {
+    const flgp_predictor *h = W.h;
     const flgp_spectrum_model *m = h->model;
     n = n_; Bd = B;
-    blk = std::min(model_block_rows(), n);
+    blk = W.rows(n);
     work_bytes = predictor_design_bytes(n, m->r, h->s, h->K, B);
     FLGP_REQUIRE(work_bytes > 0, "%s: bad shape (n=%d, r=%d, s=%d, K=%d, B=%d)", who, n, m->r, h->s, h->K, B);
     const double rows = (sizeof(int) + sizeof(double)) * (double)n * m->r;
@@ -1007,20 +770,26 @@ struct DesignRun {
     FLGP_REQUIRE(rows + (double)work_bytes + chain + extra <= 0.9 * (double)free_b,
                  "%s: the pool's rows of %.0f bytes and the workspace of %zu bytes (n=%d, B=%d) do not fit 90 %% of the %zu bytes free", who,
                  rows + chain + extra, work_bytes, n, B, free_b);
-    FLGP_TRY(M.alloc(m, blk));
+    FLGP_TRY(W.alloc(blk));
     FLGP_TRY(idx.alloc(sizeof(int) * (size_t)n * m->r));
     FLGP_TRY(val.alloc(sizeof(double) * (size_t)n * m->r));
     return work.alloc(work_bytes);
   }
   // rows [i0, i0 + nb) of the call: dX their points (ldx)
   int block(hipStream_t st, long i0, const double *dX, int nb, int ldx) {
-    const flgp_spectrum_model *m = h->model;
-    FLGP_TRY(model_rows(st, m, M, dX, nb, ldx));
-    FLGP_HIP(hipMemcpyAsync(idx.as<int>() + i0 * m->r, M.ell_idx.p, sizeof(int) * (size_t)nb * m->r, hipMemcpyDeviceToDevice, st));
-    FLGP_HIP(hipMemcpyAsync(val.as<double>() + i0 * m->r, M.ell_val.p, sizeof(double) * (size_t)nb * m->r, hipMemcpyDeviceToDevice, st));
+    const int r = W.h->model->r;
+    const int *bi;
+    const double *bv;
+    FLGP_TRY(W.ell(st, dX, nb, ldx, bi, bv));
+    FLGP_HIP(hipMemcpyAsync(idx.as<int>() + i0 * r, bi, sizeof(int) * (size_t)nb * r, hipMemcpyDeviceToDevice, st));
+    FLGP_HIP(hipMemcpyAsync(val.as<double>() + i0 * r, bv, sizeof(double) * (size_t)nb * r, hipMemcpyDeviceToDevice, st));
     return FLGP_OK;
   }
-  int loop(hipStream_t st, double d, int *d_picks, double *d_gain, double *d_score) {
+  // every block of `points`, then the greedy loop on the pool's rows; asynchronous on `st` but for the screen of host rows
+  int loop(hipStream_t st, RowPoints &points, double d, int *d_picks, double *d_gain, double *d_score) {
+    const flgp_predictor *h = W.h;
+    FLGP_TRY(for_row_blocks(st, points, n, h->d, blk,
+                            [&](long i0, const double *dX, int nb, int ldx) -> int { return block(st, i0, dX, nb, ldx); }));
     return predictor_design_rows(st, idx.as<int>(), val.as<double>(), n, h->model->r, (const double *)h->P.p, h->ldp, h->s, h->K, d, Bd,
                                  d_picks, d_gain, d_score, work.p);
   }
@@ -1032,60 +801,34 @@ extern "C" int flgp_dev_predictor_design(void *stream, const flgp_predictor *h, 
                                          const double *noise, int *d_picks, double *d_gain, double *d_score) {
   const char *who = "predictor_design";
   hipStream_t st = (hipStream_t)stream;
-  FLGP_REQUIRE(d_picks, "%s: null pointer (picks)", who);
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  FLGP_REQUIRE(dX, "%s: null pointer", who);
-  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
-  FLGP_REQUIRE(B >= 1 && B <= n, "%s: need 1 <= B <= n (B=%d, n=%d)", who, B, n);
-  FLGP_REQUIRE(ldx >= n, "%s: a leading dimension is below n = %d", who, n);
-  FLGP_TRY(design_check_handle(who, h));
   double d = 0.0;
-  FLGP_TRY(design_variance(who, h, noise, &d));
-  DesignRun R{h};
+  FLGP_TRY(design_check(who, h, dX, n, B, noise, d_picks, ldx >= n, &d));
+  DesignRun R{{h}};
+  RowPoints points{dX, ldx};
   FLGP_TRY(R.begin(who, n, B, 0.0));
-  int rc = FLGP_OK;
-  for (long i0 = 0; i0 < n && rc == FLGP_OK; i0 += R.blk) rc = R.block(st, i0, dX + i0, (int)std::min<long>(R.blk, n - i0), ldx);
-  if (rc == FLGP_OK) rc = R.loop(st, d, d_picks, d_gain, d_score);
-  (void)hipStreamSynchronize(st);               // (the workspaces die here)
-  return rc;
+  return settle(st, R.loop(st, points, d, d_picks, d_gain, d_score));     // (the workspaces die here)
 }
 
 extern "C" int flgp_predictor_design(const flgp_predictor *h, const double *X, int n, int B, const double *noise, int *picks,
                                      double *gain, double *score) {
   const char *who = "predictor_design";
-  FLGP_REQUIRE(picks, "%s: null pointer (picks)", who);
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  FLGP_REQUIRE(X, "%s: null pointer", who);
-  FLGP_REQUIRE(n >= 1, "%s: need n >= 1 (n=%d)", who, n);
-  FLGP_REQUIRE(B >= 1 && B <= n, "%s: need 1 <= B <= n (B=%d, n=%d)", who, B, n);
-  FLGP_TRY(design_check_handle(who, h));
   double d = 0.0;
-  FLGP_TRY(design_variance(who, h, noise, &d));
-  const int dim = h->d;
+  FLGP_TRY(design_check(who, h, X, n, B, noise, picks, true, &d));
   Stream st;
   FLGP_TRY(st.create());
-  DesignRun R{h};
+  DesignRun R{{h}};
+  RowPoints points{nullptr, 0, X};
   const double out_bytes = sizeof(int) * (double)B + sizeof(double) * ((double)B + n);
-  FLGP_TRY(R.begin(who, n, B, out_bytes + sizeof(double) * (double)std::min(model_block_rows(), n) * dim));
-  DevBuf dX, d_picks, d_gain, d_score;
-  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)R.blk * dim));
+  FLGP_TRY(R.begin(who, n, B, out_bytes + sizeof(double) * (double)R.W.rows(n) * h->d));
+  DevBuf d_picks, d_gain, d_score;
   FLGP_TRY(d_picks.alloc(sizeof(int) * (size_t)B));
   if (gain) FLGP_TRY(d_gain.alloc(sizeof(double) * (size_t)B));
   if (score) FLGP_TRY(d_score.alloc(sizeof(double) * (size_t)n));
-  int rc = FLGP_OK;
-  for (long i0 = 0; i0 < n && rc == FLGP_OK; i0 += R.blk) {
-    const int nb = (int)std::min<long>(R.blk, n - i0);
-    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb, dim,
-                              hipMemcpyHostToDevice, st.s));
-    rc = check_finite_on_device(st.s, dX.as<double>(), (long)nb * dim, "points");
-    if (rc == FLGP_OK) rc = R.block(st.s, i0, dX.as<double>(), nb, nb);
-  }
-  if (rc == FLGP_OK) rc = R.loop(st.s, d, d_picks.as<int>(), gain ? d_gain.as<double>() : nullptr, score ? d_score.as<double>() : nullptr);
+  int rc = R.loop(st.s, points, d, d_picks.as<int>(), gain ? d_gain.as<double>() : nullptr, score ? d_score.as<double>() : nullptr);
   if (rc == FLGP_OK) rc = d2h(picks, d_picks.p, sizeof(int) * (size_t)B, st.s);
   if (rc == FLGP_OK && gain) rc = d2h(gain, d_gain.p, sizeof(double) * (size_t)B, st.s);
   if (rc == FLGP_OK && score) rc = d2h(score, d_score.p, sizeof(double) * (size_t)n, st.s);
-  (void)hipStreamSynchronize(st.s);
-  return rc;
+  return settle(st.s, rc);
 }
 
 extern "C" int flgp_predictor_dims(const flgp_predictor *h, int *d, int *s, int *r, int *K, int *groups, int *q, int *kind, long *ldp) {
@@ -1112,84 +855,68 @@ extern "C" int flgp_predictor_to_host(const flgp_predictor *h, double *P, double
   return FLGP_OK;
 }
 
+// ---- apply (f-20, f-21): mean and variance of served rows; a Polya-Gamma handle goes to pg_apply, a draws handle to the columns
+namespace {
+
+// what both apply entries refuse; `ld_ok`: the device entry's leading dimensions, refused before the handle is looked at.  A
+// Polya-Gamma handle's device is pg_apply's to check, under its own name
+int apply_check(const char *who, const flgp_predictor *h, const double *X, const double *mean, const double *var, int n_new, bool ld_ok) {
+  FLGP_REQUIRE(X && (mean || var), "%s: null pointer", who);
+  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
+  FLGP_REQUIRE(ld_ok, "%s: a leading dimension is below n_new = %d", who, n_new);
+  FLGP_REQUIRE(h, "%s: null handle", who);
+  if (h->kind == FLGP_PREDICTOR_PG) {
+    FLGP_REQUIRE(!var, "%s: a Polya-Gamma handle has no variance", who);
+    return FLGP_OK;
+  }
+  if (h->kind == FLGP_PREDICTOR_DRAWS) FLGP_REQUIRE(!var, "%s: a draws handle has no variance", who);
+  return on_handle_device(h, who);
+}
+
+// the n rows of `points` of a regression or logit handle into the device outputs that are wanted; synchronises `st`
+int apply_rows(hipStream_t st, const flgp_predictor *h, RowPoints &points, int n, double *d_mean, long ldm, double *d_var, long ldv) {
+  RowWork W{h};
+  const int B = W.rows(n);
+  FLGP_TRY(W.alloc(B, h->grid ? flgp_dev_nystrom_predictor_workspace(B, h->s, h->groups, h->K, h->q, d_var ? 1 : 0) : 0));
+  const int rc = for_row_blocks(st, points, n, h->d, B, [&](long i0, const double *dX, int nb, int ldx) -> int {
+    double *mean = at(d_mean, i0), *var = at(d_var, i0);
+    if (h->grid) return W.nystrom_rows(st, dX, nb, ldx, mean, ldm, var, ldv);
+    const int *idx;
+    const double *val;
+    FLGP_TRY(W.ell(st, dX, nb, ldx, idx, val));
+    return flgp_dev_predictor_rows(st, idx, val, nb, h->model->r, (const double *)h->P.p, h->ldp, h->s, h->groups, h->K, h->q,
+                                   (const double *)h->cg.p, mean, ldm, var, ldv);
+  });
+  return settle(st, rc);                        // (the workspaces die here)
+}
+
+}  // namespace
+
 extern "C" int flgp_dev_predictor_apply(void *stream, const flgp_predictor *h, const double *dX, int n_new, int ldx, double *d_mean,
                                         long ldm, double *d_var, long ldv) {
   const char *who = "predictor_apply";
   hipStream_t st = (hipStream_t)stream;
-  FLGP_REQUIRE(dX && (d_mean || d_var), "%s: null pointer", who);
-  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
-  FLGP_REQUIRE(ldx >= n_new && (!d_mean || ldm >= n_new) && (!d_var || ldv >= n_new), "%s: a leading dimension is below n_new = %d", who,
-               n_new);
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  if (h->kind == FLGP_PREDICTOR_PG) {
-    FLGP_REQUIRE(!d_var, "%s: a Polya-Gamma handle has no variance", who);
+  FLGP_TRY(apply_check(who, h, dX, d_mean, d_var, n_new, ldx >= n_new && (!d_mean || ldm >= n_new) && (!d_var || ldv >= n_new)));
+  if (h->kind == FLGP_PREDICTOR_PG)
     return flgp_dev_predictor_pg_apply(stream, h, dX, n_new, ldx, d_mean, ldm, nullptr, 0, nullptr, 0, nullptr);
-  }
-  if (h->kind == FLGP_PREDICTOR_DRAWS) {
-    FLGP_REQUIRE(!d_var, "%s: a draws handle has no variance", who);
-    FLGP_TRY(on_handle_device(h, who));
-    return cols_from_device(who, st, h, dX, n_new, ldx, 0, h->q, d_mean, ldm);
-  }
-  FLGP_TRY(on_handle_device(h, who));
-  if (h->grid) {
-    NystromRowWork W;
-    FLGP_TRY(W.alloc(h, n_new, d_var != nullptr));
-    for (long i0 = 0; i0 < n_new; i0 += W.B)
-      FLGP_TRY(nystrom_apply_block(st, h, W, dX + i0, (int)std::min<long>(W.B, n_new - i0), ldx, d_mean ? d_mean + i0 : nullptr, ldm,
-                                   d_var ? d_var + i0 : nullptr, ldv));
-    FLGP_HIP(hipStreamSynchronize(st));
-    return FLGP_OK;
-  }
-  const int B = std::min(model_block_rows(), n_new);
-  ModelRowWork W;
-  FLGP_TRY(W.alloc(h->model, B));
-  for (long i0 = 0; i0 < n_new; i0 += B)
-    FLGP_TRY(apply_block(st, h, W, dX + i0, (int)std::min<long>(B, n_new - i0), ldx, d_mean ? d_mean + i0 : nullptr, ldm,
-                         d_var ? d_var + i0 : nullptr, ldv));
-  FLGP_HIP(hipStreamSynchronize(st));     // (the workspaces die here)
-  return FLGP_OK;
+  RowPoints points{dX, ldx};
+  if (h->kind == FLGP_PREDICTOR_DRAWS) return cols_rows(who, st, h, points, n_new, 0, h->q, d_mean, ldm);
+  return apply_rows(st, h, points, n_new, d_mean, ldm, d_var, ldv);
 }
 
 extern "C" int flgp_predictor_apply(const flgp_predictor *h, const double *X, int n_new, double *mean, double *var) {
   const char *who = "predictor_apply";
-  FLGP_REQUIRE(X && (mean || var), "%s: null pointer", who);
-  FLGP_REQUIRE(n_new >= 1, "%s: need n_new >= 1 (n_new=%d)", who, n_new);
-  FLGP_REQUIRE(h, "%s: null handle", who);
-  if (h->kind == FLGP_PREDICTOR_PG) {
-    FLGP_REQUIRE(!var, "%s: a Polya-Gamma handle has no variance", who);
-    return flgp_predictor_pg_apply(h, X, n_new, mean, nullptr, nullptr, nullptr);
-  }
-  if (h->kind == FLGP_PREDICTOR_DRAWS) {
-    FLGP_REQUIRE(!var, "%s: a draws handle has no variance", who);
-    FLGP_TRY(on_handle_device(h, who));
-    return cols_to_host(who, h, X, n_new, 0, h->q, mean);
-  }
-  FLGP_TRY(on_handle_device(h, who));
-  const flgp_spectrum_model *m = h->model;
-  const int d = h->d, gq = h->groups * h->q;
+  FLGP_TRY(apply_check(who, h, X, mean, var, n_new, true));
+  if (h->kind == FLGP_PREDICTOR_PG) return flgp_predictor_pg_apply(h, X, n_new, mean, nullptr, nullptr, nullptr);
+  if (h->kind == FLGP_PREDICTOR_DRAWS) return cols_to_host(who, h, X, n_new, 0, h->q, mean);
+  const size_t gq = (size_t)h->groups * h->q;
   Stream st;
   FLGP_TRY(st.create());
-  ModelRowWork W;
-  NystromRowWork NW;
-  DevBuf dX, dmean, dvar;
-  if (h->grid) FLGP_TRY(NW.alloc(h, n_new, var != nullptr));
-  const int B = h->grid ? NW.B : std::min(model_block_rows(), n_new);
-  if (m) FLGP_TRY(W.alloc(m, B));
-  FLGP_TRY(dX.alloc(sizeof(double) * (size_t)B * d));
+  DevBuf dmean, dvar;
+  RowPoints points{nullptr, 0, X};
   if (mean) FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)n_new * gq));
   if (var) FLGP_TRY(dvar.alloc(sizeof(double) * (size_t)n_new * h->groups));
-  for (long i0 = 0; i0 < n_new; i0 += B) {
-    const int nb = (int)std::min<long>(B, n_new - i0);
-    FLGP_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)nb, X + i0, sizeof(double) * (size_t)n_new, sizeof(double) * (size_t)nb, d,
-                              hipMemcpyHostToDevice, st.s));
-    FLGP_TRY(check_finite_on_device(st.s, dX.as<double>(), (long)nb * d, "points"));
-    if (h->grid)
-      FLGP_TRY(nystrom_apply_block(st.s, h, NW, dX.as<double>(), nb, nb, mean ? dmean.as<double>() + i0 : nullptr, n_new,
-                                   var ? dvar.as<double>() + i0 : nullptr, n_new));
-    else
-      FLGP_TRY(apply_block(st.s, h, W, dX.as<double>(), nb, nb, mean ? dmean.as<double>() + i0 : nullptr, n_new,
-                           var ? dvar.as<double>() + i0 : nullptr, n_new));
-  }
+  FLGP_TRY(apply_rows(st.s, h, points, n_new, mean ? dmean.as<double>() : nullptr, n_new, var ? dvar.as<double>() : nullptr, n_new));
   if (mean) FLGP_TRY(d2h(mean, dmean.p, sizeof(double) * (size_t)n_new * gq, st.s));
   if (var) FLGP_TRY(d2h(var, dvar.p, sizeof(double) * (size_t)n_new * h->groups, st.s));
   FLGP_HIP(hipStreamSynchronize(st.s));

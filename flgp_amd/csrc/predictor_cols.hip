@@ -1,7 +1,7 @@
 // The wide row kernel of the fitted predictor and the kernels of the draws handle (include/flgp_hip.h).
 //   out(i, c) = sum_a A(i, a) P(idx(i, a), c0 + c),   c < nc
-// is the chain of predictor_rows_kernel / predictor_pg_rows_kernel (predictor.hip) -- a ascending, multiply then add, from 0.0 --
-// for hundreds of columns: those kernels give lane l column 64 c + l and store it at once, 64 addresses ldo doubles apart.
+// is the chain of predictor_rows_kernel / predictor_pg_rows_kernel (predictor_rows.hip) -- a ascending, multiply then add, from
+// 0.0 -- for hundreds of columns: those kernels give lane l column 64 c + l and store it at once, 64 addresses ldo doubles apart.
 // Here a workgroup owns 64 rows x 64 columns, passes the tile through LDS and stores column segments of 64 consecutive rows.
 // The draws handle: xi(k, col) from the project's counter RNG (rng.h) and P_draw(:, col) = P_mean(:, c) + P_K xi(:, col).
 #include "common.h"

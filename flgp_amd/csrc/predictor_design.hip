@@ -19,7 +19,8 @@
 //   c_i       a ascending, multiply then add, from 0.0; score_i - c_i c_i is one multiplication and one subtraction, unclamped.
 // The argmax is a reduction under a total order -- the larger score, a NaN below every number, at equal scores (or two NaNs) the
 // lower index -- so its result does not depend on how the candidates are split over lanes, waves, workgroups and partials.
-// predictor.hip holds the handle entries (flgp_predictor_design / flgp_dev_predictor_design).
+// predictor.hip holds the handle entries (flgp_predictor_design / flgp_dev_predictor_design), predictor_rows.hip the
+// predictor_rows_kernel named above.
 #include "common.h"
 #include <algorithm>
 #include <cmath>

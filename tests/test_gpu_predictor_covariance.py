@@ -13,6 +13,9 @@ m = 60 > K.
 * diag(covariance) + cg against apply's var: |d| <= (K + 8) 2^-53 sum_k z_k^2 -- the same squares, another order.
 * features: on a model handle the cols restatement on the model's ELL rows, bit for bit; on the Nystrom handle the long-double
   restatement within f-21's b_ik = (3 eta_i + (3 s + 12) u) M_ik, M_ik = f_i sum_j Z_ij |P(j, k)|.
+* 513 rows across the block seam (model_extend_block = 256 against the default): features from host and device rows and a
+  513 x 300 covariance block bit for bit, on a model and a Nystrom handle; a NaN behind the first block is refused and the
+  handle stays usable.
 * the refusals that need live handles."""
 import numpy as np
 import pytest
@@ -177,6 +180,85 @@ def test_nystrom_features_against_the_long_double_restatement():
     assert np.abs(ref).max() > 0 and ratio <= 1.0
     np.testing.assert_array_equal(pred.features(Xn[100:101])[0], Z[100])
     pred.free()
+
+
+SEAM = 513                                                                      # two blocks of 256 rows and a block of one
+
+
+def seam_handle(which):
+    """(a regression handle, 513 unseen rows): over the "lae" model of shape A, or over bandwidth 1 of the Nystrom grid"""
+    if which == "model":
+        X = pf.case("A")[0]
+        model, pair, host = pf.fitted("A")
+        idx0, Y = pf.training(X, 60, 3, seed=7)
+        return api.Predictor.regression(model, pair, Y, idx0, K12, (pf.T, pf.NOISE), pf.SIGMA), pf.new_rows("A", SEAM)
+    X, Ua, X2 = pf.ny_cloud()
+    grid, pairs = pf.ny_fitted()
+    idx0, Y = pf.training(X, 60, 3, seed=7)
+    return api.Predictor.nystrom_regression(grid, 1, pairs[1], Y, idx0, pf.NY[3], (pf.T, pf.NOISE), pf.SIGMA), np.asfortranarray(X2[:SEAM])
+
+
+def dev_features(pred, Xn, ldx, ldz):
+    """flgp_dev_predictor_features on padded, NaN-filled buffers with a spare output column: the (K + 1) x ldz buffer as it is left"""
+    import torch
+    n, d = Xn.shape
+    dX = torch.full((d, ldx), float("nan"), dtype=torch.float64, device=pf.DEV)
+    dX[:, :n] = torch.from_numpy(np.ascontiguousarray(Xn.T)).to(pf.DEV)
+    dZ = torch.full((pred.K + 1, ldz), float("nan"), dtype=torch.float64, device=pf.DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().flgp_dev_predictor_features(st, pred._h, 0, dX.data_ptr(), n, ldx, dZ.data_ptr(), ldz))
+    torch.cuda.synchronize()
+    return dZ.cpu().numpy()
+
+
+@pytest.mark.parametrize("which", ["model", "nystrom"])
+def test_features_and_covariance_bits_across_a_block_seam(which):
+    """513 rows at model_extend_block = 256 are three blocks, at the default one: features (host rows and device rows) and a
+    513 x 300 covariance block give the same bits either way.  On the model handle each element is one chain over a row's own
+    weights; on the Nystrom handle a row's Z, f and T chains do not see the block either (apply's are asserted equal at the
+    two block sizes in tests/test_gpu_nystrom_predictor.py)."""
+    pred, Xn = seam_handle(which)
+    K = pred.K
+    Xb = np.asfortranarray(Xn[200:500])
+    L = _lib.lib()
+    want = {"Z": pred.features(Xn), "dev": dev_features(pred, Xn, 516, 518), "C": pred.covariance(Xn, Xb)}
+    L.flgp_set_tuning(b"model_extend_block", 256)
+    try:
+        got = {"Z": pred.features(Xn), "dev": dev_features(pred, Xn, 516, 518), "C": pred.covariance(Xn, Xb)}
+    finally:
+        L.flgp_set_tuning(b"model_extend_block", 1 << 20)
+    assert want["Z"].shape == (SEAM, K) and want["C"].shape == (SEAM, 300) and np.isfinite(want["Z"]).all() and np.abs(want["Z"]).max() > 0
+    for key in ("Z", "C"):
+        np.testing.assert_array_equal(got[key], want[key], err_msg=f"{which} {key}")
+    for dZ in (want["dev"], got["dev"]):
+        np.testing.assert_array_equal(dZ[:K, :SEAM].T, want["Z"], err_msg=f"{which} device entry")
+        assert np.isnan(dZ[K]).all() and np.isnan(dZ[:, SEAM:]).all()           # the spare column and the padding rows
+    pred.free()
+
+
+def test_a_non_finite_point_behind_the_first_block_is_refused():
+    """a NaN in row 300 of 513 at model_extend_block = 256: the second block is the one that is refused, after the first one's
+    work was queued; the handle gives its unchanged bits on clean rows straight after"""
+    L = _lib.lib()
+    for which in ("model", "nystrom"):
+        pred, Xn = seam_handle(which)
+        bad = np.array(Xn, order="F"); bad[300, 1] = np.nan
+        want = pred.apply(Xn)
+        Z = pred.features(Xn) if which == "model" else None
+        L.flgp_set_tuning(b"model_extend_block", 256)
+        try:
+            with pytest.raises(api.FlgpError, match="points"):
+                pred.apply(bad)
+            got = pred.apply(Xn)
+            if which == "model":
+                with pytest.raises(api.FlgpError, match="points"):
+                    pred.features(bad)
+                np.testing.assert_array_equal(pred.features(Xn), Z)
+        finally:
+            L.flgp_set_tuning(b"model_extend_block", 1 << 20)
+        for key in ("mean", "var"):
+            np.testing.assert_array_equal(got[key], want[key], err_msg=f"{which} {key}")
+        pred.free()
 
 
 def test_refusals_that_need_live_handles():
