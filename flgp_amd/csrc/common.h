@@ -448,7 +448,6 @@ int pg_f0r(hipStream_t st, int m, const double *Vz, const double *z2, double ss,
            const double *omega, double *f0, double *r, double *sw);
 int pg_dvec(hipStream_t st, int m, const double *omega, double sigma, double *sw, double *dh, double *a);
 int pg_mul(hipStream_t st, int m, const double *a, const double *x, const double *b, double *out);
-int pg_wb_out(hipStream_t st, int m, const double *sw, const double *dh, const double *g, const double *Xv, double *out);
 int pg_axpy3(hipStream_t st, int m, const double *x, const double *y, double c, const double *z, double *out);
 int pg_trmv(hipStream_t st, const double *dL, long lda, int m, const double *z, double *y, const int *d_flag);
 int pg_pi(hipStream_t st, long n, const double *mean, double sigma_nv, const long *ptr, const int *list, const double *w,

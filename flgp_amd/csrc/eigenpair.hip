@@ -6,9 +6,10 @@
 // batch of one, the J one-vs-rest posteriors its batch of J: f-12; any response matrix in one call: f-17; the
 // training objective for B problems in one call: f-15; the regression objective for B (pair, x) problems through a training
 // context: f-18; the trained operands of both posteriors for the fitted predictor of predictor.hip: f-20);
-// Polya-Gamma Gibbs prediction (pg.hip; B chains in one call: DESIGN 8 f-16).  The algebra they share is written once:
-// woodbury_step (regression, m > K) and LowRankB (the K x K solve against B = sW C sW + I and C x, for the Gibbs
-// sweep).  Each entry checks its arguments on the host, then runs on one stream of its own.
+// Polya-Gamma Gibbs prediction (pg.hip; B chains in one call, the binary entry its batch of one and the
+// one-vs-rest entry its batch of J: DESIGN 8 f-16).  The algebra they share is written once: woodbury_step (regression,
+// m > K) and LrBatch (the K x K solve against B = sW C sW + I, for the Newton loop and, through PgBatch, the Gibbs sweep).
+// Each entry checks its arguments on the host, then runs on one stream of its own.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -517,57 +518,11 @@ struct RgDirect {
 // ---- logit training objective: what train_lae_logit_gp_cpp's COBYLA minimises, on the
 // resident pair, for B problems (labels, t) in one call; the single entry is the batch of one ------------------------------
 namespace {
-// The low-rank pieces of C = V1 L V1^T + sigma I (V1 m x K at ld1, L = exp(-t (1 - values)), ls = L^1/2) that the
-// Polya-Gamma sweep (PgChain) works on.  With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with
-// X = diag(xs) V1 L^1/2 (xs = D^-1/2 sW) and Q = I + X^T X (K x K):
-//   B^-1 y = D^-1 y - D^-1/2 X Q^-1 X^T D^-1/2 y,   det B = det D det Q.
-// The callers' elementwise kernels make xs and use the result; the sigma x term of C x is theirs too.
-struct LowRankB {
-  int m = 0, K = 0;
-  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;
-  long ld1 = 0;
-  double sigma = 0.0;          // C's: the callers' kernels use it, nothing below does
-  int *flag = nullptr;
-  DevBuf X, Q, u, work;        // Q holds its factor L_Q after factor(); u (K) and work (we) are scratch
-  size_t we = 0;
-
-  int alloc(int m_, int K_, bool factored, int *flag_) {     // !factored: cmul only (no X, no Q)
-    m = m_; K = K_; flag = flag_;
-    we = vt_work_elems(K, 1);
-    FLGP_TRY(u.alloc(sizeof(double) * (size_t)std::max(K, 1))); FLGP_TRY(work.alloc(sizeof(double) * we));
-    if (!factored) return FLGP_OK;
-    FLGP_TRY(X.alloc(sizeof(double) * (size_t)m * K));
-    return Q.alloc(sizeof(double) * (size_t)K * K);
-  }
-  // X = diag(xs) V1 L^1/2, Q = I + X^T X = L_Q L_Q^T
-  int factor(hipStream_t st, const double *xs) {
-    FLGP_TRY(gpc_scale2(st, V1, ld1, xs, ls, m, K, X.as<double>()));
-    FLGP_TRY(gemm_tn(st, K, K, m, X.as<double>(), m, X.as<double>(), m, Q.as<double>(), work.as<double>(), we));
-    FLGP_TRY(gpr_add_diag(st, Q.as<double>(), K, 1.0));
-    return chol_blocked(st, Q.as<double>(), K, K, flag);
-  }
-  // Xv = X Q^-1 X^T g with the factor of the last factor()
-  int apply(hipStream_t st, const double *g, double *Xv) {
-    FLGP_TRY(gemm_tn(st, K, 1, m, X.as<double>(), m, g, m, u.as<double>(), work.as<double>(), we));
-    FLGP_TRY(chol_trsv(st, Q.as<double>(), K, K, u.as<double>(), K, 1, 3, flag));
-    return gemm_nn(st, m, 1, K, X.as<double>(), m, u.as<double>(), K, Xv, nullptr, 0);
-  }
-  // out = Vl L V1^T x for any Vl (rows x K at ldl): V1 itself in C x, the new rows' V2 in a predicted mean
-  int cmul(hipStream_t st, const double *Vl, long ldl, int rows, const double *x, double *out) {
-    FLGP_TRY(lvt(st, x));
-    return gemm_nn(st, rows, 1, K, Vl, ldl, u.as<double>(), K, out, nullptr, 0);
-  }
-  // u = L (V1^T x): the first half of cmul
-  int lvt(hipStream_t st, const double *x) {
-    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, x, m, u.as<double>(), work.as<double>(), we));
-    return pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>());
-  }
-};
-
 inline long pad32(long n) { return (n + 31) / 32 * 32; }     // a slot starts 256-byte aligned, like an allocation of its own
 
 // Alg. 3.1 for m > K on C = V1 L V1^T + sigma I, O(m K^2) per iteration, never an m x m matrix, for a chunk of problems.
-// With D = 1 + sigma W, xs = D^-1/2 sW, X = diag(xs) V1 L^1/2 and Q = I + X^T X (LowRankB's identities), per iteration:
+// With D = 1 + sigma W and U = sW V1, B = sW C sW + I = D + U L U^T, so with xs = D^-1/2 sW, X = diag(xs) V1 L^1/2 and
+// Q = I + X^T X (K x K):  B^-1 y = D^-1 y - D^-1/2 X Q^-1 X^T D^-1/2 y,  det B = det D det Q.  Per iteration:
 // sW, b from f; D, X, Q factored (K x K); c = C b; g = xs c; r = B^-1 (sW c) = D^-1/2 (g - X Q^-1 X^T g); a = b - sW r;
 // f_new = C a.  As in GpcNewton, a, D and L_Q stay those of the LAST iteration and f is the final mode; everything is
 // fixed-order.  Slot s of every buffer belongs to problem p0 + s for the whole chunk, the device list `act` names the slots
@@ -1522,57 +1477,52 @@ int flgp::logit_operands(hipStream_t st, const char *who, const flgp_eigenpair *
 
 // ---- Polya-Gamma Gibbs prediction: test_pgbinary_cpp and predict_logit_mult_gp_cpp (pg.hip) ---------------
 namespace {
-// One chain of PGLogitModel (src/PGLogitModel.cpp) with C = V1 L V1^T + sigma I (eigen routes) or a dense C.  Each sweep
-// resamples f in Matheron's form, with the law of _resample_f (:25-39) and one solve against B = sW C sW + I:
+// One chain of PGLogitModel (src/PGLogitModel.cpp) on an m x m B, with a dense C (DENSE: flgp_pg_logit_predict's host
+// matrices) or C = V1 L V1^T + sigma I of the resident pair for m <= K (DIRECT: a pool worker of pg_chains; m > K runs in
+// PgBatch).  Each sweep resamples f in Matheron's form, with the law of _resample_f (:25-39) and one solve against
+// B = sW C sW + I, factored m x m:
 //   f0 = V1 L^1/2 z1 + sqrt(sigma) z2 (dense: L_C z2), r = kappa / sW - sW f0 - z3, f = f0 + C (sW B^-1 r),
-// then omega ~ PG(1, f).  B^-1: route DENSE / DIRECT factor the m x m B; WOODBURY (m > K) writes B = D + U L U^T with
-// D = 1 + sigma omega, U = sW V1 and factors the K x K Q = I + X^T X, X = D^-1/2 U L^1/2 (LowRankB):
-//   sW B^-1 r = sW D^-1/2 (g - X Q^-1 X^T g),  g = D^-1/2 r.
-// C x = V1 (L (V1^T x)) + sigma x in both eigen routes; C is formed only to build B in DIRECT.  The routes split along two
-// lines, the solve (m x m in DENSE and DIRECT) and C x (dense only in DENSE), so they stay branches, not two solver objects.
-enum PgRoute { PG_DENSE, PG_DIRECT, PG_WOODBURY };
+// then omega ~ PG(1, f).  C x = V1 (L (V1^T x)) + sigma x in DIRECT, where C is formed only to build B, and a dense product in
+// DENSE: the routes differ in f0 and C x alone, so they stay branches, not two solver objects.
+enum PgRoute { PG_DENSE, PG_DIRECT };
 struct PgChain {
   PgRoute route = PG_DENSE;
-  int m = 0;
-  LowRankB L;                                                // eigen routes: the caller sets V1, ld1, l, ls, sigma
-  const double *C = nullptr, *LC = nullptr;                  // DENSE / DIRECT: C (m x m); DENSE: its factor
+  int m = 0, K = 0;
+  const double *C = nullptr, *LC = nullptr;                  // C (m x m); DENSE: its factor
+  // DIRECT, set by the caller: V1 (m x K at ld1), l = exp(-t (1 - values)), ls = l^1/2 and C's sigma
+  const double *V1 = nullptr, *l = nullptr, *ls = nullptr;
+  long ld1 = 0;
+  double sigma = 0.0;
   int *flag = nullptr;
-  DevBuf kappa, omega, f, f0, r, sw, z, x, t1, t2, B, dh, a;
+  DevBuf kappa, omega, f, f0, r, sw, z, x, t1, t2, B, u, work;   // u (K) and work (we) are lvt's
+  size_t we = 0;
 
-  int alloc(int m_, int K) {
-    m = m_;
+  int alloc(int m_, int K_) {
+    m = m_; K = K_;
     const size_t v = sizeof(double) * (size_t)m;
     FLGP_TRY(kappa.alloc(v)); FLGP_TRY(omega.alloc(v)); FLGP_TRY(f.alloc(v)); FLGP_TRY(f0.alloc(v)); FLGP_TRY(r.alloc(v));
     FLGP_TRY(sw.alloc(v)); FLGP_TRY(x.alloc(v)); FLGP_TRY(t1.alloc(v)); FLGP_TRY(t2.alloc(v));
     FLGP_TRY(z.alloc(sizeof(double) * ((size_t)2 * m + K)));
-    FLGP_TRY(L.alloc(m, K, route == PG_WOODBURY, flag));
-    if (route == PG_WOODBURY) {
-      FLGP_TRY(dh.alloc(v)); FLGP_TRY(a.alloc(v));
-    } else {
-      FLGP_TRY(B.alloc(sizeof(double) * (size_t)m * m));
-    }
-    return FLGP_OK;
+    we = vt_work_elems(K, 1);
+    FLGP_TRY(u.alloc(sizeof(double) * (size_t)std::max(K, 1))); FLGP_TRY(work.alloc(sizeof(double) * we));
+    return B.alloc(sizeof(double) * (size_t)m * m);
   }
-  // sW (and the Woodbury pieces) from omega, B or Q factored in place
+  // sW from omega, B factored in place
   int factor(hipStream_t st) {
-    if (route != PG_WOODBURY) {
-      FLGP_TRY(pg_dvec(st, m, omega.as<double>(), 0.0, sw.as<double>(), t1.as<double>(), t2.as<double>()));
-      FLGP_TRY(gpc_bmat(st, C, sw.as<double>(), m, B.as<double>()));
-      return chol_blocked(st, B.as<double>(), m, m, flag);
-    }
-    FLGP_TRY(pg_dvec(st, m, omega.as<double>(), L.sigma, sw.as<double>(), dh.as<double>(), a.as<double>()));
-    return L.factor(st, a.as<double>());
+    FLGP_TRY(pg_dvec(st, m, omega.as<double>(), 0.0, sw.as<double>(), t1.as<double>(), t2.as<double>()));
+    FLGP_TRY(gpc_bmat(st, C, sw.as<double>(), m, B.as<double>()));
+    return chol_blocked(st, B.as<double>(), m, m, flag);
   }
   // out = sW .* B^-1 rin with the factor of the last factor()
   int solve(hipStream_t st, const double *rin, double *out) {
-    if (route != PG_WOODBURY) {
-      FLGP_HIP(hipMemcpyAsync(t1.p, rin, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
-      FLGP_TRY(chol_trsv(st, B.as<double>(), m, m, t1.as<double>(), m, 1, 3, flag));
-      return pg_mul(st, m, sw.as<double>(), t1.as<double>(), nullptr, out);
-    }
-    FLGP_TRY(pg_mul(st, m, dh.as<double>(), rin, nullptr, t1.as<double>()));                                       // g
-    FLGP_TRY(L.apply(st, t1.as<double>(), t2.as<double>()));
-    return pg_wb_out(st, m, sw.as<double>(), dh.as<double>(), t1.as<double>(), t2.as<double>(), out);
+    FLGP_HIP(hipMemcpyAsync(t1.p, rin, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    FLGP_TRY(chol_trsv(st, B.as<double>(), m, m, t1.as<double>(), m, 1, 3, flag));
+    return pg_mul(st, m, sw.as<double>(), t1.as<double>(), nullptr, out);
+  }
+  // u = L (V1^T x): the latent mean of a row with eigenvector entries v is then v . u
+  int lvt(hipStream_t st, const double *xin) {
+    FLGP_TRY(gemm_tn(st, K, 1, m, V1, ld1, xin, m, u.as<double>(), work.as<double>(), we));
+    return pg_mul(st, K, l, u.as<double>(), nullptr, u.as<double>());
   }
   // out = add + C xin (add may be nullptr)
   int cmul(hipStream_t st, const double *xin, const double *add, double *out) {
@@ -1580,23 +1530,23 @@ struct PgChain {
       FLGP_TRY(gpc_gemv(st, C, m, xin, nullptr, t2.as<double>()));
       return pg_axpy3(st, m, add, t2.as<double>(), 0.0, nullptr, out);
     }
-    FLGP_TRY(L.cmul(st, L.V1, L.ld1, m, xin, t2.as<double>()));
-    return pg_axpy3(st, m, add, t2.as<double>(), L.sigma, xin, out);
+    FLGP_TRY(lvt(st, xin));
+    FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, t2.as<double>(), nullptr, 0));
+    return pg_axpy3(st, m, add, t2.as<double>(), sigma, xin, out);
   }
   int run(hipStream_t st, const double *dY, int n_sample, unsigned long long seed) {
     FLGP_TRY(pg_init(st, m, dY, kappa.as<double>(), omega.as<double>(), f.as<double>()));
-    const int kz = route == PG_DENSE ? 0 : L.K;
-    double *z1 = z.as<double>(), *z2 = z1 + kz, *z3 = z2 + m;
+    double *z1 = z.as<double>(), *z2 = z1 + K, *z3 = z2 + m;      // DENSE: K = 0
     for (int s = 0; s < n_sample; ++s) {
       ProfScope ps("pg_sweep", st, 0.0);
-      FLGP_TRY(pg_normals(st, seed, s, kz, m, z1));
+      FLGP_TRY(pg_normals(st, seed, s, K, m, z1));
       if (route == PG_DENSE) {
         FLGP_TRY(pg_trmv(st, LC, m, m, z2, t2.as<double>(), flag));                                         // L_C z2
       } else {
-        FLGP_TRY(pg_mul(st, L.K, L.ls, z1, nullptr, L.u.as<double>()));
-        FLGP_TRY(gemm_nn(st, m, 1, L.K, L.V1, L.ld1, L.u.as<double>(), L.K, t2.as<double>(), nullptr, 0));  // V1 L^1/2 z1
+        FLGP_TRY(pg_mul(st, K, ls, z1, nullptr, u.as<double>()));
+        FLGP_TRY(gemm_nn(st, m, 1, K, V1, ld1, u.as<double>(), K, t2.as<double>(), nullptr, 0));            // V1 L^1/2 z1
       }
-      FLGP_TRY(pg_f0r(st, m, t2.as<double>(), z2, route == PG_DENSE ? 0.0 : std::sqrt(L.sigma), z3, kappa.as<double>(),
+      FLGP_TRY(pg_f0r(st, m, t2.as<double>(), z2, route == PG_DENSE ? 0.0 : std::sqrt(sigma), z3, kappa.as<double>(),
                       omega.as<double>(), f0.as<double>(), r.as<double>(), sw.as<double>()));
       FLGP_TRY(factor(st));
       FLGP_TRY(solve(st, r.as<double>(), x.as<double>()));
@@ -1656,40 +1606,15 @@ int check_pg_common(const double *Y, int m, int mnew, int n_sample, const char *
   return FLGP_OK;
 }
 
-// One binary chain on the resident pair (V1, V2 gathered by the caller) and its collapsed prediction of the new rows:
-// pi into d_pi[i * ld_pi] and labels into d_y (either may be nullptr); final omega and f stay in P.
-int pg_eigen_binary(hipStream_t st, const flgp_eigenpair *ep, int K, double t, double sigma, double sigma_nv, Rows &r0,
-                    const Rows &r1, const double *dY, int n_sample, unsigned long long seed, PgMatch *match,
-                    PgChain &P, DevBuf &flag, double *d_pi, long ld_pi, double *d_y) {
-  const int m = r0.m, mnew = r1.m;
-  GprCtx G;
-  FLGP_TRY(G.prepare(st, ep, K, t));          // ls = exp(-t (1 - values) / 2), l = exp(-t (1 - values))
-  DevBuf C, hw;
-  P.route = m <= K ? PG_DIRECT : PG_WOODBURY;
-  if (P.route == PG_DIRECT) {
-    FLGP_TRY(hk_c11(st, ep, K, t, r0, sigma, C, hw, flgp_dev_hk_workspace(m, m, K, 1)));
-    P.C = C.as<double>();
-  }
-  P.L.sigma = sigma; P.L.V1 = r0.V; P.L.ld1 = r0.ld; P.L.l = G.l.as<double>(); P.L.ls = G.ls.as<double>(); P.flag = flag.as<int>();
-  FLGP_TRY(P.alloc(m, K));
-  FLGP_TRY(P.run(st, dY, n_sample, seed));
-  FLGP_TRY(P.collapsed_w(st));
-  // mean = V2 L V1^T w, then pi = logistic(mean + sigma_nv sum_{idx0_j = idx1_i} w_j)
-  DevBuf mean;
-  FLGP_TRY(mean.alloc(sizeof(double) * (size_t)mnew));
-  FLGP_TRY(P.L.cmul(st, r1.V, r1.ld, mnew, P.x.as<double>(), mean.as<double>()));
-  FLGP_TRY(pg_pi(st, mnew, mean.as<double>(), sigma_nv, match ? match->ptr.as<long>() : nullptr,
-                 match ? match->list.as<int>() : nullptr, P.x.as<double>(), d_pi, ld_pi, d_y));
-  FLGP_HIP(hipStreamSynchronize(st));         // the chain's buffers are given back to the cache on the way out
-  return FLGP_OK;
-}
-
-// PgChain's Woodbury route (m > K) for a chunk of chains in the same launches.  Slot s of every buffer
-// belongs to chain p0 + s for the whole chunk; each step of run / factor / solve / cmul / collapsed_w is one launch over
-// the slots: the pgb_* kernels (pg.hip) for the chain's own elementwise steps, LrBatch's kernels (lrb_*, on the LrChunk
-// view C whose xs is the chain's a) for X, Q and its factor, and the batched GEMM with V1 / V2 at stride 0.  Every chain
-// runs all n_sample sweeps, so the slot list is the identity.  The split products take, per chain, LowRankB's plan (a
-// workspace of vt_work_elems(K, 1) doubles) on planes of the slot's own: LrBatch::plans.
+// PgChain's sweep for m > K, for a chunk of chains in the same launches: B is never formed.  With LrBatch's
+// identities (D = 1 + sigma omega, a = D^-1/2 sW its xs, dh = D^-1/2, X = diag(a) V1 L^1/2, Q = I + X^T X factored K x K):
+//   sW B^-1 r = sW D^-1/2 (g - X Q^-1 X^T g),  g = D^-1/2 r,
+// and C x = V1 (L (V1^T x)) + sigma x.  Slot s of every buffer belongs to chain p0 + s for the whole chunk; each step of
+// run / factor / solve / cmul is one launch over the slots: the pgb_* kernels (pg.hip) for the chain's own elementwise
+// steps, LrBatch's kernels (lrb_*, on the LrChunk view C) for X, Q and its factor, and the batched GEMM with V1 / V2 at
+// stride 0.  Every chain runs all n_sample sweeps, so the slot list is the identity.  The split products take, per chain,
+// the plan of an unbatched product with a workspace of vt_work_elems(K, 1) doubles, on planes of the slot's own:
+// LrBatch::plans.
 struct PgBatch {
   PgChunk P;
   LrChunk C;
@@ -1746,7 +1671,7 @@ struct PgBatch {
     return gemm_launch(st, rows, 1, C.K, 1.0, Am, 1, lda, u, 1, C.K, 0.0, nullptr, 0, 0, out, 1, rows, nullptr, 0, 0.0, nullptr,
                        nullptr, nullptr, 0, nullptr, &gb);
   }
-  // u = L (V1^T x) per slot: the first two steps of LowRankB::cmul
+  // u = L (V1^T x) per slot: PgChain::lvt
   int lvt(hipStream_t st, const double *x) {
     FLGP_TRY(tn(st, C.V1, C.ld1, 0, x, C.u));
     return lrb_mul(st, C.K, C.l, C.sk, C.u, C.sk, C.u, C.sk, act.as<int>(), P.slots);
@@ -1814,7 +1739,7 @@ struct PgDirectWorker {
     FLGP_TRY(work.alloc(flgp_dev_hk_workspace(m, m, K, 1)));
     FLGP_TRY(ls.alloc(sizeof(double) * (size_t)K)); FLGP_TRY(l.alloc(sizeof(double) * (size_t)K));
     P.route = PG_DIRECT; P.C = C.as<double>();
-    P.L.sigma = sigma; P.L.V1 = r0.V; P.L.ld1 = r0.ld; P.L.l = l.as<double>(); P.L.ls = ls.as<double>();
+    P.sigma = sigma; P.V1 = r0.V; P.ld1 = r0.ld; P.l = l.as<double>(); P.ls = ls.as<double>();
     return P.alloc(m, K);
   }
   static double bytes(int m, int K, int mnew) {
@@ -1876,87 +1801,10 @@ extern "C" int flgp_pg_logit_predict(const double *C, int m, const double *Y, co
   return pg_verdict(st.s, flag.p, who);
 }
 
-extern "C" int flgp_eigenpair_pg_predict(const flgp_eigenpair *ep, int K, double t, double sigma, double sigma_nv,
-                                         const int *idx0, int m, const double *Y, const int *idx1, int mnew, int n_sample,
-                                         unsigned long long seed, double *pi_pred, double *y_pred, double *omega_out,
-                                         double *f_out) {
-  const char *who = "eigenpair_pg_predict";
-  FLGP_REQUIRE(idx0 && Y && idx1 && pi_pred && y_pred, "%s: null pointer", who);
-  FLGP_REQUIRE(std::isfinite(t), "%s: t must be finite", who);
-  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(sigma_nv), "%s: sigma must be finite and >= 0", who);
-  FLGP_TRY(check_pg_common(Y, m, mnew, n_sample, who));
-  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
-  Rows r0, r1;
-  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
-  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
-  Stream st;
-  FLGP_TRY(st.create());
-  DevBuf dY, flag, dpi, dy;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m)); FLGP_TRY(flag.alloc(sizeof(int)));
-  FLGP_TRY(dpi.alloc(sizeof(double) * (size_t)mnew)); FLGP_TRY(dy.alloc(sizeof(double) * (size_t)mnew));
-  FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st.s));
-  FLGP_TRY(h2d(dY.p, Y, sizeof(double) * (size_t)m, st.s));
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  FLGP_TRY(r1.gather(st.s, ep, K));
-  PgMatch match;
-  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, idx0, m, idx1, mnew));
-  PgChain P;
-  FLGP_TRY(pg_eigen_binary(st.s, ep, K, t, sigma, sigma_nv, r0, r1, dY.as<double>(), n_sample, seed,
-                           sigma_nv != 0.0 ? &match : nullptr, P, flag, dpi.as<double>(), 1, dy.as<double>()));
-  FLGP_TRY(d2h(pi_pred, dpi.p, sizeof(double) * (size_t)mnew, st.s));
-  FLGP_TRY(d2h(y_pred, dy.p, sizeof(double) * (size_t)mnew, st.s));
-  if (omega_out) FLGP_TRY(d2h(omega_out, P.omega.p, sizeof(double) * (size_t)m, st.s));
-  if (f_out) FLGP_TRY(d2h(f_out, P.f.p, sizeof(double) * (size_t)m, st.s));
-  return pg_verdict(st.s, flag.p, who);
-}
-
-// predict_logit_mult_gp_cpp (src/MultiClassification.cpp:57-88): one-vs-rest over the J classes of multi_train_split(Y),
-// class j exactly flgp_eigenpair_pg_predict with t = ts[j], sigma_nv = 0 and seed + j; the chains run one after another
-// on one stream.  labels: the first arg-max of each row of probs (m_new x J).
-extern "C" int flgp_eigenpair_pg_predict_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma,
-                                                    const int *idx0, int m, const double *Y, const int *idx1, int mnew,
-                                                    int n_sample, unsigned long long seed, double *probs, double *labels) {
-  const char *who = "eigenpair_pg_predict_multiclass";
-  FLGP_REQUIRE(ts && idx0 && Y && idx1 && probs && labels, "%s: null pointer", who);
-  FLGP_REQUIRE(J >= 1 && m >= 1 && mnew >= 1, "%s: bad shape (J=%d, m=%d, m_new=%d)", who, J, m, mnew);
-  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
-  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0, "%s: sigma must be finite and >= 0", who);
-  for (int j = 0; j < J; ++j) FLGP_REQUIRE(std::isfinite(ts[j]), "%s: ts[%d] must be finite", who, j);
-  for (int a = 0; a < m; ++a)
-    FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] < J && Y[a] == std::floor(Y[a]), "%s: Y[%d]=%g is not a class label in 0 .. %d", who, a,
-                 Y[a], J - 1);
-  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
-  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
-  Rows r0, r1;
-  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
-  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
-  Stream st;
-  FLGP_TRY(st.create());
-  DevBuf dY, flag, dprobs, dlab;
-  FLGP_TRY(dY.alloc(sizeof(double) * (size_t)m * J)); FLGP_TRY(flag.alloc(sizeof(int)));
-  FLGP_TRY(dprobs.alloc(sizeof(double) * (size_t)mnew * J)); FLGP_TRY(dlab.alloc(sizeof(double) * (size_t)mnew));
-  std::vector<double> aug((size_t)m * J, 0.0);          // multi_train_split (src/MultiClassification.cpp:14-26)
-  for (int a = 0; a < m; ++a) aug[(size_t)Y[a] * m + a] = 1.0;
-  FLGP_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st.s));
-  FLGP_TRY(h2d(dY.p, aug.data(), sizeof(double) * aug.size(), st.s));
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  FLGP_TRY(r1.gather(st.s, ep, K));
-  for (int j = 0; j < J; ++j) {
-    PgChain P;
-    FLGP_TRY(pg_eigen_binary(st.s, ep, K, ts[j], sigma, 0.0, r0, r1, dY.as<double>() + (size_t)j * m, n_sample,
-                             seed + (unsigned long long)j, nullptr, P, flag, dprobs.as<double>() + (size_t)j * mnew, 1, nullptr));
-  }
-  FLGP_TRY(pg_argmax(st.s, mnew, J, dprobs.as<double>(), dlab.as<double>()));
-  FLGP_TRY(d2h(probs, dprobs.p, sizeof(double) * (size_t)mnew * J, st.s));
-  FLGP_TRY(d2h(labels, dlab.p, sizeof(double) * (size_t)mnew, st.s));
-  return pg_verdict(st.s, flag.p, who);
-}
-
-// ---- B chains in one call and their trained state for the predictor (f-22) ----------------------------------
-// The chains of flgp_eigenpair_pg_predict_batch up to u = L (V1^T w) at the final omega: m > K in chunks of chains sharing
-// every launch (PgBatch), m <= K dealt to pool workers, each with a PgChain of its own on the m x m route.  What follows u
-// is the caller's: the batch entry multiplies the new rows' V2 onto it, the predictor folds it into its anchor side.
+// ---- B chains in one call: the three resident-pair entries, and the chains' trained state for the predictor
+// (f-22).  The chains up to u = L (V1^T w) at the final omega: m > K in chunks of chains sharing every launch (PgBatch),
+// m <= K dealt to pool workers, each with a PgChain of its own on the m x m route.  What follows u is the caller's: the
+// entries multiply the new rows' V2 onto it (pg_predict_chains), the predictor folds it into its anchor side.
 namespace {
 // what a sink sees of the chains [p0, p0 + S) while it is valid: u of chain p0 + a at U + a su and its collapsed w at w + a sw.
 // `act` is the slot list of the batched launches (m > K); it is nullptr on the pool route, where S = 1 and `st` is the
@@ -1970,12 +1818,19 @@ struct PgChunkOut {
 };
 using PgChunkSink = std::function<int(const PgChunkOut &)>;
 
+// words the last error as chain b's
+void pg_name_chain(int b, const double *ts, const unsigned long long *seeds) {
+  const std::string msg(flgp_last_error());
+  set_error("chain %d (t=%g, seed=%llu): %s", b, ts[b], seeds[b], msg.c_str());
+}
+
 // r0 gathered, dY on the device, cols resolved.  sink_doubles: the doubles per chain of the caller's own buffers, for the
 // planning of the chunk / the workers alone.  flags: one pivot flag per chain, valid once `st` is synchronised (the caller's
-// verdict: pg_flags_verdict).  A worker's failure comes back worded "chain b (t=.., seed=..): ..".
+// verdict: pg_flags_verdict).  name_chains: a failure comes back worded "chain b (t=.., seed=..): .." (a caller whose
+// chains are the user's: the batch entry, the predictor); without, as the chain itself words it (the batch of one, of J classes).
 int pg_chains(hipStream_t st, const flgp_eigenpair *ep, int K, const Rows &r0, const double *dY, const int *cols, const double *ts,
               const unsigned long long *seeds, int B, double sigma, int n_sample, int max_parallel, int sink_doubles,
-              double *omega_out, double *f_out, int *flags, DevBuf &dflag, const PgChunkSink &sink) {
+              bool name_chains, double *omega_out, double *f_out, int *flags, DevBuf &dflag, const PgChunkSink &sink) {
   const int m = r0.m;
   const size_t vb = sizeof(double) * (size_t)m;
   if (m <= K) {
@@ -1988,21 +1843,22 @@ int pg_chains(hipStream_t st, const flgp_eigenpair *ep, int K, const Rows &r0, c
         st, B, [&](PgDirectWorker &W) { return W.alloc(m, K, r0, sigma); },
         [&](hipStream_t ws, PgDirectWorker &W, int b) -> int {
           PgChain &P = W.P;
-          P.flag = P.L.flag = dflag.as<int>() + b;
+          P.flag = dflag.as<int>() + b;
           FLGP_TRY(gpr_weights(ws, (const double *)ep->values.p, K, ts[b], W.ls.as<double>(), W.l.as<double>()));
           FLGP_TRY(hk(ws, ep, K, ts[b], r0, r0, W.C.as<double>(), W.work.as<double>()));
           if (sigma != 0.0) FLGP_TRY(gpr_add_diag(ws, W.C.as<double>(), m, sigma));
           FLGP_TRY(P.run(ws, dY + (size_t)cols[b] * m, n_sample, seeds[b]));
           FLGP_TRY(P.collapsed_w(ws));
-          FLGP_TRY(P.L.lvt(ws, P.x.as<double>()));
-          FLGP_TRY(sink(PgChunkOut{ws, b, 1, P.L.u.as<double>(), K, P.x.as<double>(), m, nullptr}));
+          FLGP_TRY(P.lvt(ws, P.x.as<double>()));
+          FLGP_TRY(sink(PgChunkOut{ws, b, 1, P.u.as<double>(), K, P.x.as<double>(), m, nullptr}));
           if (omega_out) FLGP_TRY(d2h(omega_out + (size_t)b * m, P.omega.p, vb, ws));
           if (f_out) FLGP_TRY(d2h(f_out + (size_t)b * m, P.f.p, vb, ws));
           FLGP_HIP(hipStreamSynchronize(ws));    // the worker's buffers take the next chain
           return FLGP_OK;
         });
     if (bad.item >= 0) {
-      set_error("chain %d (t=%g, seed=%llu): %s", bad.item, ts[bad.item], seeds[bad.item], bad.message.c_str());
+      set_error("%s", bad.message.c_str());
+      if (name_chains) pg_name_chain(bad.item, ts, seeds);
       return bad.status;
     }
     return d2h(flags, dflag.p, sizeof(int) * (size_t)B, st);
@@ -2038,15 +1894,67 @@ int pg_chains(hipStream_t st, const flgp_eigenpair *ep, int K, const Rows &r0, c
   return FLGP_OK;
 }
 
-int pg_flags_verdict(const char *who, const int *flags, const double *ts, const unsigned long long *seeds, int B) {
+// the lowest chain that met a pivot <= 0
+int pg_flags_verdict(const char *who, bool name_chains, const int *flags, const double *ts, const unsigned long long *seeds, int B) {
   for (int b = 0; b < B; ++b)
     if (flags[b]) {
       const int rc = pg_pivot_error(flags[b], who);
-      const std::string msg(flgp_last_error());
-      set_error("chain %d (t=%g, seed=%llu): %s", b, ts[b], seeds[b], msg.c_str());
+      if (name_chains) pg_name_chain(b, ts, seeds);
       return rc;
     }
   return FLGP_OK;
+}
+
+// The three resident-pair entries after their argument checks (r0, r1 checked): chain b is column col[b] (NULL: b) of Y
+// (m x ncol) at ts[b] with seeds[b]; its pi over the new rows into column b of pi_pred and, where asked for, its labels
+// into y_pred, the first arg-max over the chains into argmax_out and its final omega and f into omega_out, f_out.
+int pg_predict_chains(const char *who, bool name_chains, const flgp_eigenpair *ep, int K, Rows &r0, Rows &r1, const double *Y,
+                      int ncol, const int *col, const double *ts, const unsigned long long *seeds, int B, double sigma,
+                      double sigma_nv, int n_sample, int max_parallel, double *pi_pred, double *y_pred, double *argmax_out,
+                      double *omega_out, double *f_out) {
+  const int m = r0.m, mnew = r1.m;
+  std::vector<int> cols((size_t)B);
+  for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
+  Stream st;
+  FLGP_TRY(st.create());
+  const size_t vb = sizeof(double) * (size_t)m, nb = sizeof(double) * (size_t)mnew;
+  const long sm = pad32(mnew);                 // doubles between two chains' means over the new rows
+  DevBuf dY, dpi, dy, dlab, dflag, dmean;
+  FLGP_TRY(upload(dY, Y, vb * ncol, st.s));
+  FLGP_TRY(dpi.alloc(nb * B));
+  if (y_pred) FLGP_TRY(dy.alloc(nb * B));
+  FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)sm * B));
+  FLGP_TRY(r0.gather(st.s, ep, K));
+  FLGP_TRY(r1.gather(st.s, ep, K));
+  PgMatch match;
+  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, r0.idx, m, r1.idx, mnew));
+  const long *mptr = sigma_nv != 0.0 ? match.ptr.as<long>() : nullptr;
+  const int *mlist = sigma_nv != 0.0 ? match.list.as<int>() : nullptr;
+  std::vector<int> flags((size_t)B, 0);       // one pivot flag per chain, read after the chain's sweeps
+  // mean = V2 u, then pi = logistic(mean + sigma_nv sum_{idx0_j = idx1_i} w_j) into the chains' columns
+  FLGP_TRY(pg_chains(st.s, ep, K, r0, dY.as<double>(), cols.data(), ts, seeds, B, sigma, n_sample, max_parallel, mnew, name_chains,
+                     omega_out, f_out, flags.data(), dflag, [&](const PgChunkOut &o) -> int {
+                       double *mean = dmean.as<double>() + (size_t)o.p0 * sm;
+                       double *pi = dpi.as<double>() + (size_t)o.p0 * mnew;
+                       double *y = y_pred ? dy.as<double>() + (size_t)o.p0 * mnew : nullptr;
+                       if (!o.act) {
+                         FLGP_TRY(gemm_nn(o.st, mnew, 1, K, r1.V, r1.ld, o.U, K, mean, nullptr, 0));
+                         return pg_pi(o.st, mnew, mean, sigma_nv, mptr, mlist, o.w, pi, 1, y);
+                       }
+                       const GemmBatch gb{o.S, o.act, 0, o.su, sm, 0, 0};
+                       FLGP_TRY(gemm_launch(o.st, mnew, 1, K, 1.0, r1.V, 1, r1.ld, o.U, 1, K, 0.0, nullptr, 0, 0, mean, 1, mnew,
+                                            nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0, nullptr, &gb));
+                       return pgb_pi(o.st, mnew, o.S, mean, sm, sigma_nv, mptr, mlist, o.w, o.sw, pi, y, mnew);
+                     }));
+  if (argmax_out) {
+    FLGP_TRY(dlab.alloc(nb));
+    FLGP_TRY(pg_argmax(st.s, mnew, B, dpi.as<double>(), dlab.as<double>()));
+    FLGP_TRY(d2h(argmax_out, dlab.p, nb, st.s));
+  }
+  FLGP_TRY(d2h(pi_pred, dpi.p, nb * B, st.s));
+  if (y_pred) FLGP_TRY(d2h(y_pred, dy.p, nb * B, st.s));
+  FLGP_HIP(hipStreamSynchronize(st.s));
+  return pg_flags_verdict(who, name_chains, flags.data(), ts, seeds, B);
 }
 }  // namespace
 
@@ -2086,14 +1994,14 @@ int flgp::pg_operands(hipStream_t st, const char *who, const flgp_eigenpair *ep,
   DevBuf dY, dflag;
   FLGP_TRY(upload(dY, Y, sizeof(double) * (size_t)m * ncol, st));
   FLGP_TRY(r0.gather(st, ep, K));
-  FLGP_TRY(pg_chains(st, ep, K, r0, dY.as<double>(), cols.data(), ts, seeds, B, sigma, n_sample, max_parallel, 0, omega_out, f_out,
-                     flags.data(), dflag, [&](const PgChunkOut &o) { return sink(o.st, o.p0, o.S, o.U, o.su); }));
+  FLGP_TRY(pg_chains(st, ep, K, r0, dY.as<double>(), cols.data(), ts, seeds, B, sigma, n_sample, max_parallel, 0, true, omega_out,
+                     f_out, flags.data(), dflag, [&](const PgChunkOut &o) { return sink(o.st, o.p0, o.S, o.U, o.su); }));
   FLGP_HIP(hipStreamSynchronize(st));
-  return pg_flags_verdict(who, flags.data(), ts, seeds, B);
+  return pg_flags_verdict(who, true, flags.data(), ts, seeds, B);
 }
 
-// Chain b is column col[b] of Y at ts[b] with seeds[b], and its columns of the outputs are flgp_eigenpair_pg_predict's, bit
-// for bit, whatever shares the call.
+// Chain b is column col[b] of Y at ts[b] with seeds[b], and its columns of the outputs are the same bits whatever shares
+// the call: the two entries below are this one with B = 1 and with B = J.
 extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, const int *idx0, int m, const double *Y, int ncol,
                                                const int *col, const double *ts, const unsigned long long *seeds, int B,
                                                double sigma, double sigma_nv, const int *idx1, int mnew, int n_sample,
@@ -2104,52 +2012,60 @@ extern "C" int flgp_eigenpair_pg_predict_batch(const flgp_eigenpair *ep, int K, 
   FLGP_REQUIRE(idx0 && Y && ts && seeds && idx1 && pi_pred, "%s: null pointer", who);
   FLGP_REQUIRE(B >= 1 && m >= 1 && mnew >= 1 && ncol >= 1, "%s: bad shape (B=%d, m=%d, m_new=%d, ncol=%d)", who, B, m, mnew, ncol);
   FLGP_TRY(pg_operands_check(who, ep, K, idx0, m, Y, ncol, col, ts, seeds, B, sigma, n_sample, sigma_nv));
-  std::vector<int> cols((size_t)B);
-  for (int b = 0; b < B; ++b) cols[(size_t)b] = col ? col[b] : b;
   Rows r0, r1;
   FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
   FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  return pg_predict_chains(who, true, ep, K, r0, r1, Y, ncol, col, ts, seeds, B, sigma, sigma_nv, n_sample, max_parallel, pi_pred,
+                           y_pred, argmax_out, omega_out, f_out);
+}
 
-  Stream st;
-  FLGP_TRY(st.create());
-  const size_t vb = sizeof(double) * (size_t)m, nb = sizeof(double) * (size_t)mnew;
-  const long sm = pad32(mnew);                 // doubles between two chains' means over the new rows
-  DevBuf dY, dpi, dy, dlab, dflag, dmean;
-  FLGP_TRY(upload(dY, Y, vb * ncol, st.s));
-  FLGP_TRY(dpi.alloc(nb * B));
-  if (y_pred) FLGP_TRY(dy.alloc(nb * B));
-  FLGP_TRY(dmean.alloc(sizeof(double) * (size_t)sm * B));
-  FLGP_TRY(r0.gather(st.s, ep, K));
-  FLGP_TRY(r1.gather(st.s, ep, K));
-  PgMatch match;
-  if (sigma_nv != 0.0) FLGP_TRY(match.build(st.s, idx0, m, idx1, mnew));
-  const long *mptr = sigma_nv != 0.0 ? match.ptr.as<long>() : nullptr;
-  const int *mlist = sigma_nv != 0.0 ? match.list.as<int>() : nullptr;
-  std::vector<int> flags((size_t)B, 0);       // one pivot flag per chain, read after the chain's sweeps
-  // mean = V2 u, then pi = logistic(mean + sigma_nv sum_{idx0_j = idx1_i} w_j) into the chains' columns
-  FLGP_TRY(pg_chains(st.s, ep, K, r0, dY.as<double>(), cols.data(), ts, seeds, B, sigma, n_sample, max_parallel, mnew, omega_out,
-                     f_out, flags.data(), dflag, [&](const PgChunkOut &o) -> int {
-                       double *mean = dmean.as<double>() + (size_t)o.p0 * sm;
-                       double *pi = dpi.as<double>() + (size_t)o.p0 * mnew;
-                       double *y = y_pred ? dy.as<double>() + (size_t)o.p0 * mnew : nullptr;
-                       if (!o.act) {
-                         FLGP_TRY(gemm_nn(o.st, mnew, 1, K, r1.V, r1.ld, o.U, K, mean, nullptr, 0));
-                         return pg_pi(o.st, mnew, mean, sigma_nv, mptr, mlist, o.w, pi, 1, y);
-                       }
-                       const GemmBatch gb{o.S, o.act, 0, o.su, sm, 0, 0};
-                       FLGP_TRY(gemm_launch(o.st, mnew, 1, K, 1.0, r1.V, 1, r1.ld, o.U, 1, K, 0.0, nullptr, 0, 0, mean, 1, mnew,
-                                            nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0, nullptr, &gb));
-                       return pgb_pi(o.st, mnew, o.S, mean, sm, sigma_nv, mptr, mlist, o.w, o.sw, pi, y, mnew);
-                     }));
-  if (argmax_out) {
-    FLGP_TRY(dlab.alloc(nb));
-    FLGP_TRY(pg_argmax(st.s, mnew, B, dpi.as<double>(), dlab.as<double>()));
-    FLGP_TRY(d2h(argmax_out, dlab.p, nb, st.s));
-  }
-  FLGP_TRY(d2h(pi_pred, dpi.p, nb * B, st.s));
-  if (y_pred) FLGP_TRY(d2h(y_pred, dy.p, nb * B, st.s));
-  FLGP_HIP(hipStreamSynchronize(st.s));
-  return pg_flags_verdict(who, flags.data(), ts, seeds, B);
+// test_pgbinary_cpp on the resident pair: the batch of one
+extern "C" int flgp_eigenpair_pg_predict(const flgp_eigenpair *ep, int K, double t, double sigma, double sigma_nv,
+                                         const int *idx0, int m, const double *Y, const int *idx1, int mnew, int n_sample,
+                                         unsigned long long seed, double *pi_pred, double *y_pred, double *omega_out,
+                                         double *f_out) {
+  const char *who = "eigenpair_pg_predict";
+  FLGP_REQUIRE(idx0 && Y && idx1 && pi_pred && y_pred, "%s: null pointer", who);
+  FLGP_REQUIRE(std::isfinite(t), "%s: t must be finite", who);
+  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(sigma_nv), "%s: sigma must be finite and >= 0", who);
+  FLGP_TRY(check_pg_common(Y, m, mnew, n_sample, who));
+  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  return pg_predict_chains(who, false, ep, K, r0, r1, Y, 1, nullptr, &t, &seed, 1, sigma, sigma_nv, n_sample, 0, pi_pred, y_pred,
+                           nullptr, omega_out, f_out);
+}
+
+// predict_logit_mult_gp_cpp (src/MultiClassification.cpp:57-88): one-vs-rest over the J classes of multi_train_split(Y), the
+// batch of J on the indicator matrix: class j is flgp_eigenpair_pg_predict with t = ts[j], sigma_nv = 0 and seed + j, bit for
+// bit.  The J chains run together: for m > K one chunk of up to J chains sharing every launch, as many as fit
+// into 90 % of the free device memory (a chain's state is PgBatch::bytes: X alone 8 m K bytes, 16 MB at m = 1e4, K = 200);
+// for m <= K min(J, 4) pool workers.  labels: the first arg-max of each row of probs (m_new x J).
+extern "C" int flgp_eigenpair_pg_predict_multiclass(const flgp_eigenpair *ep, int K, const double *ts, int J, double sigma,
+                                                    const int *idx0, int m, const double *Y, const int *idx1, int mnew,
+                                                    int n_sample, unsigned long long seed, double *probs, double *labels) {
+  const char *who = "eigenpair_pg_predict_multiclass";
+  FLGP_REQUIRE(ts && idx0 && Y && idx1 && probs && labels, "%s: null pointer", who);
+  FLGP_REQUIRE(J >= 1 && m >= 1 && mnew >= 1, "%s: bad shape (J=%d, m=%d, m_new=%d)", who, J, m, mnew);
+  FLGP_REQUIRE(n_sample >= 1, "%s: N_sample=%d must be at least 1", who, n_sample);
+  FLGP_REQUIRE(std::isfinite(sigma) && sigma >= 0.0, "%s: sigma must be finite and >= 0", who);
+  for (int j = 0; j < J; ++j) FLGP_REQUIRE(std::isfinite(ts[j]), "%s: ts[%d] must be finite", who, j);
+  for (int a = 0; a < m; ++a)
+    FLGP_REQUIRE(Y[a] >= 0.0 && Y[a] < J && Y[a] == std::floor(Y[a]), "%s: Y[%d]=%g is not a class label in 0 .. %d", who, a,
+                 Y[a], J - 1);
+  FLGP_REQUIRE(ep, "%s: null eigenpair", who);
+  FLGP_REQUIRE(K >= 1 && K <= ep->K, "%s: need 1 <= K <= %d (K=%d)", who, ep->K, K);
+  Rows r0, r1;
+  FLGP_TRY(r0.check(ep, idx0, m, who, "idx0"));
+  FLGP_TRY(r1.check(ep, idx1, mnew, who, "idx1"));
+  std::vector<double> aug((size_t)m * J, 0.0);          // multi_train_split (src/MultiClassification.cpp:14-26)
+  for (int a = 0; a < m; ++a) aug[(size_t)Y[a] * m + a] = 1.0;
+  std::vector<unsigned long long> seeds((size_t)J);
+  for (int j = 0; j < J; ++j) seeds[(size_t)j] = seed + (unsigned long long)j;
+  return pg_predict_chains(who, false, ep, K, r0, r1, aug.data(), J, nullptr, ts, seeds.data(), J, sigma, 0.0, n_sample, 0, probs,
+                           nullptr, labels, nullptr, nullptr);
 }
 
 // ---- regression training objective for B (pair, x) problems in one call -------------------------------

@@ -11,8 +11,9 @@
 // uniforms 2i, 2i + 1, sqrt(-2 log u_2i) cos(2 pi u_2i+1); an exponential is -log u.  Nothing depends on the launch
 // geometry.
 //
-// Layout of one chain (flgp_eigenpair_pg_predict, flgp_pg_logit_predict, and every chain of
-// flgp_eigenpair_pg_predict_batch under its own seed), sweep s = 0 .. n_sample - 1:
+// Layout of one chain under its own seed (flgp_pg_logit_predict's, and every chain of flgp_eigenpair_pg_predict_batch:
+// flgp_eigenpair_pg_predict is its batch of one, flgp_eigenpair_pg_predict_multiclass its batch of J with seed + j),
+// sweep s = 0 .. n_sample - 1:
 //   stream 4s     normal k (k < K): z1 of f0 = V1 L^1/2 z1 + sqrt(sigma) z2 (unused by the dense entry);
 //   stream 4s + 1 normal a (a < m): z2 (the dense entry: f0 = L_C z2);
 //   stream 4s + 2 normal a: z3 of r = kappa / sqrt(omega) - sqrt(omega) f0 - z3;
@@ -201,19 +202,6 @@ __global__ void pg_mul_kernel(int m, const double *__restrict__ a, const double 
 int pg_mul(hipStream_t st, int m, const double *a, const double *x, const double *b, double *out) {
   hipLaunchKernelGGL(pg_mul_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, m, a, x, b, out);
   return check_launch("pg_mul_kernel");
-}
-
-// out = sw .* dh .* (g - Xv)
-__global__ void pg_wb_out_kernel(int m, const double *__restrict__ sw, const double *__restrict__ dh,
-                                 const double *__restrict__ g, const double *__restrict__ Xv, double *__restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  out[i] = sw[i] * (dh[i] * (g[i] - Xv[i]));
-}
-
-int pg_wb_out(hipStream_t st, int m, const double *sw, const double *dh, const double *g, const double *Xv, double *out) {
-  hipLaunchKernelGGL(pg_wb_out_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, m, sw, dh, g, Xv, out);
-  return check_launch("pg_wb_out_kernel");
 }
 
 // out = x + y + c z   (x, y, z each optional: a missing term is left out, not added as 0)

@@ -1,8 +1,9 @@
 """Timing of the batched Polya-Gamma prediction (flgp_eigenpair_pg_predict_batch) against the routes it
 stands beside, on a synthetic resident pair with n = 1e6, K = 200, m_new = n - m new rows, N_sample = 100 and ten classes:
 
-  * route A: flgp_eigenpair_pg_predict_multiclass for B = 10 (the ten chains one after another on one stream), B calls of
-    flgp_eigenpair_pg_predict otherwise;
+  * route A: flgp_eigenpair_pg_predict_multiclass for B = 10 (when profiles/pg_predict_batch_timing.json was taken: the ten
+    chains one after another on one stream; it is the batch of J now), B calls of flgp_eigenpair_pg_predict
+    otherwise;
   * route under test: one batch call (max_parallel = 0);
   * m = 1000 and 1e4 with B = 1, 10, 40 (the Woodbury sweep), and m = 200 = K with B = 10 (the m x m route's workers).
 

@@ -1,8 +1,10 @@
 """GPU: B Polya-Gamma chains in one call (flgp_eigenpair_pg_predict_batch).  The contract is bits: column b
 of every output equals what the single entry returns for chain b's (column, t, seed), whatever B, the order, the chunk size
-or the other chains are -- every comparison with the single entry is np.array_equal.  One test holds the batch to the
-numpy restatement (tests/np_pg.py) instead, at the bound the single entry is held to, so that the suite does not rest on
-one implementation alone."""
+or the other chains are -- every comparison with the single entry is np.array_equal.  The single and the one-vs-rest entry
+are the batch of one and of J, so these comparisons show that a chain's bits do not depend on its company; what the two
+returned while they ran a sweep of their own is pinned in tests/golden/pg_predict_bits.npz (test_gpu_pg_bits.py).  One test
+holds the batch to the numpy restatement (tests/np_pg.py) instead, at the bound the single entry is held to, so that the
+suite does not rest on one implementation alone."""
 import os
 import re
 import sys
