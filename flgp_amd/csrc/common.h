@@ -294,7 +294,7 @@ struct GpcNewton {
   static int pivot_error(int bad, const char *who, int iter);   // iter 0: the factorisation at the final f
 };
 // The low-rank Newton loop of the logit training objective (m > K) for a chunk of independent problems in the same
-// launches (gpc.hip, the loop itself in eigenpair.hip: LrBatch).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
+// launches (gpc.hip, the loop itself in eigenpair_internal.h: LrBatch).  A problem owns one slot of every buffer below for the whole call; the kernels take a device list `act`
 // of A slot numbers (the problems still iterating) and carry its index in the grid, so a step is one launch whatever A is
 // and a slot that left the list is not written again.  The strides are doubles between two slots; Y, N, V1 are shared.
 // `pair` (nullptr: one pair, V1 shared): a device list with the pair of every SLOT, for a chunk whose problems
@@ -336,7 +336,7 @@ int lrb_trsv(hipStream_t st, const LrChunk &c, const int *act, int A);
 // lrb_trsv's q-column form: the q columns of R (K x q per slot at stride sr) <- Q^-1 (.), a workgroup per column
 int lrb_trsv_cols(hipStream_t st, const LrChunk &c, const int *act, int A, double *R, long sr, int q);
 int lrb_amll(hipStream_t st, const LrChunk &c);
-// The predictive rows of the logit posterior for m > K (gpc.hip; the loop is in eigenpair.hip: WsBatch).
+// The predictive rows of the logit posterior for m > K (gpc.hip; the loop is in eigenpair_logit.hip: WsBatch).
 // gpc_predict_rows_multi: mean_i = u^T v_i and cov_i = c + |G v_i|^2 for the mnew rows v_i = V(rows_i, 0:K) of the pair, read
 // in place (d_idx, or row0 + i when it is nullptr), against J operands [G ; u^T] (G K x K lower triangular, u K) stored
 // back to back in d_Gf, gpc_predict_operand_elems(K) doubles each as wsb_predict_prep writes them: the rows are staged once
@@ -351,7 +351,7 @@ int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int 
                            const double *d_Gf, double c, double *d_mean, double *d_cov, long ldo);
 int gpc_rowsumsq_add(hipStream_t st, const double *dZ, long ldz, int rows, int cols, double c, double *d_out);
 // The weight-space loop and the predictive operands for a chunk of problems in the same launches (gpc.hip,
-// the loop in eigenpair.hip: WsBatch), on LrChunk's slots and lists, beside the lrb_* steps it shares.  On the listed
+// the loop in eigenpair_logit.hip: WsBatch), on LrChunk's slots and lists, beside the lrb_* steps it shares.  On the listed
 // slots: wsb_w: sW and b from f and Y with N = 1 (gpc_w_kernel's form without N); wsb_bd: c = b / D; wsb_fnew:
 // f_new = g + sigma (b - sW^2 g) / D; wsb_scale_cols: M(i, j) *= ls(j) on the K x K matrix at Q's stride;
 // wsb_predict_prep: the operand [G ; u^T] of (dG at Q's stride, u) into operand s of d_Gf.  wsb_tri_inverse: tri_inverse of the
@@ -400,7 +400,7 @@ struct RgTerms {
 };
 int rg_assemble(hipStream_t st, const RgTerms &T);
 // The Woodbury route (m > K) of the same objective for a chunk of problems in the same launches (the steps in
-// eigenpair.hip: RgBatch).  Problem s of the chunk owns slot s of every buffer below and the kernels carry the slot in
+// eigenpair_regression.hip: RgBatch).  Problem s of the chunk owns slot s of every buffer below and the kernels carry the slot in
 // gridDim.y (rgb_assemble: one workgroup per slot), so a step is one launch whatever the chunk holds.  The strides are
 // doubles between two slots.  What belongs to a pair and not to a problem (its eigenvalues, its gathered rows V and, for
 // "same", M0 = V^T V) is stored once per distinct pair and found through pair[s] (on the device).  Y is shared.
@@ -455,7 +455,7 @@ int pg_pi(hipStream_t st, long n, const double *mean, double sigma_nv, const lon
 int pg_argmax(hipStream_t st, long n, int J, const double *probs, double *labels);
 int pg_init(hipStream_t st, int m, const double *Y, double *kappa, double *omega, double *f);
 // The Woodbury sweep (m > K) for a chunk of chains in the same launches (pg.hip, the sweep itself in
-// eigenpair.hip: PgBatch).  A chain owns slot s of every buffer below for the whole chunk and the kernels carry the slot in
+// eigenpair_pg.hip: PgBatch).  A chain owns slot s of every buffer below for the whole chunk and the kernels carry the slot in
 // gridDim.y, so a step is one launch whatever the chunk holds.  sv and sz are the doubles between two slots of an
 // m-vector and of z; Y is shared, chain s reading column ycol[s] and drawing from seed[s] (both on the device).  The K x K
 // pieces (X, Q, u, l, ls, the pivot flags) are LrChunk's, on the lrb_* kernels.
@@ -498,7 +498,7 @@ int launch_lae_reg(hipStream_t st, const double *dX, int n, int ldx, int d, cons
 
 }  // namespace flgp
 
-// device-resident EigenPair (include/flgp_hip.h): made in capi.hip, consumed there (H, copied out by hostcopy.hip) and in eigenpair.hip
+// device-resident EigenPair (include/flgp_hip.h): made in capi.hip, consumed there (H, copied out by hostcopy.hip) and in eigenpair*.hip
 struct flgp_eigenpair {
   flgp::DevBuf values, vectors;   // K, n x K column-major
   int n = 0, K = 0, device = 0;
@@ -577,7 +577,7 @@ int predictor_design_rows(hipStream_t st, const int *d_ell_idx, const double *d_
 // B(j, k) = Vs(j, k) q_k, q_k = scale / sigma_k (0 where sigma_k = 0): the anchor side of flgp_dev_hk_rows (sparse.hip)
 int hk_rows_b(hipStream_t st, const double *dVs, int ldv, int s, const double *d_eig, int K, double scale, double *dB);
 // The trained operands of the posteriors for the predictor (predictor.hip), by the weight-space route whatever m is, on
-// the launches of the m > K bodies of the entries they mirror (eigenpair.hip).  *_check: that entry's refusals under `who`,
+// the launches of the m > K bodies of the entries they mirror (eigenpair_regression.hip, eigenpair_logit.hip).  *_check: that entry's refusals under `who`,
 // before any device work.  The sink receives the operands of problems [p0, p0 + S) while they are valid: G (K x K, ld K)
 // of problem p0 + a at G + a sg and U (K x q, ld K) at U + a su, with var_i = c + |G u_i|^2 and mean_i = U^T u_i; it queues
 // its work on `st`.  Both synchronise `st` and return the mirrored entry's verdict.

@@ -412,9 +412,9 @@ int GpcNewton::amll(hipStream_t st, const double *dY, const double *dN, double *
   return FLGP_OK;
 }
 
-// ---- the low-rank Newton loop for a chunk of independent problems (the loop is in eigenpair.hip) --------
+// ---- the low-rank Newton loop for a chunk of independent problems (the loop is in eigenpair_internal.h)
 // The elementwise steps, the K x K factorisation and the final sums of Alg. 3.1 on C = V1 L V1^T + sigma I (LrBatch,
-// eigenpair.hip), with the problem in the grid (blockIdx.y, or blockIdx.x where a workgroup takes a whole problem): entry q
+// eigenpair_internal.h), with the problem in the grid (blockIdx.y, or blockIdx.x where a workgroup takes a whole problem): entry q
 // of the device list `act` names the slot whose buffers the workgroups of row q use (LrChunk, common.h).  A workgroup reads
 // and writes its own slot only and every sum is in a fixed order, so a slot's bits do not depend on the list.
 
@@ -852,7 +852,7 @@ int gpc_predict_rows_multi(hipStream_t st, const double *dV, long ld, const int 
   return launch(gpc_predict_rows_multi_kernel<1>);
 }
 
-// ---- the weight-space Newton loop and the predictive operands for a chunk of problems (WsBatch, eigenpair.hip)
+// ---- the weight-space Newton loop and the predictive operands for a chunk of problems (WsBatch, eigenpair_logit.hip)
 // The steps of the weight-space loop that the lrb_* kernels above do not already have, in their form: the slot in
 // blockIdx.y through the device list, a workgroup on its own slot only.  Each keeps the expression tree of the unbatched
 // kernel it stands beside where there is one (gpc_w_kernel without N, tri_inv_diag_kernel, gpr_scale_kernel's column

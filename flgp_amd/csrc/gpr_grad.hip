@@ -286,7 +286,7 @@ int rgb_assemble(hipStream_t st, const RgbChunk &c, int slots) {
 
 using namespace flgp;
 
-// T (64 x m) and the k-split planes, sized as the direct branch of the regression objective sizes them (eigenpair.hip)
+// T (64 x m) and the k-split planes, sized as the direct branch of the regression objective sizes them (eigenpair_regression.hip)
 extern "C" size_t flgp_dev_tri_inverse_workspace(int m) {
   return m < 1 ? 0 : sizeof(double) * ((size_t)TNB * m + (size_t)32 * TNB * m);
 }

@@ -295,7 +295,7 @@ int pg_init(hipStream_t st, int m, const double *Y, double *kappa, double *omega
   return check_launch("pg_init_kernel");
 }
 
-// ---- the Woodbury sweep for a chunk of chains (PgChunk, common.h; the sweep is in eigenpair.hip) ----------
+// ---- the Woodbury sweep for a chunk of chains (PgChunk, common.h; the sweep is in eigenpair_pg.hip) -------
 // The kernels above with the chain's slot in blockIdx.y.  A thread reads and writes its own slot only, every expression is
 // its namesake's and every random number is a function of (seed[slot], sweep, stream, entry, draw), so a chain's bits are
 // those of the single entry whatever shares its chunk.

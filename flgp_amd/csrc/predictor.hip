@@ -3,11 +3,11 @@
 //   P = Bq Gp^T   (s x (K + q) per group),   Bq(j, k) = Vs(j, k) sqrt(n_fit) / sigma_k,   Gp = [G ; U^T],
 // so that the posterior of a row that arrives later is z_i = a_i P on the row's r scaled anchor weights: its last q entries
 // the mean, c plus the squares of its first K entries the variance.  No n_new x K array exists.  The trained operands come
-// from the bodies of the entries the handle mirrors (eigenpair.hip: regression_operands, logit_operands); the row chain up
+// from the bodies of the entries the handle mirrors (eigenpair_regression.hip: regression_operands; eigenpair_logit.hip: logit_operands); the row chain up
 // to the weights is the model's (model.hip: model_rows); the row kernels are predictor_rows.hip's.
 // The same handle over one bandwidth of a Nystrom grid (f-21): the anchor side is the grid's pre-scaled eigenvectors V', the
 // weights are dense and the row path is nystrom_predictor.hip's.
-// A Polya-Gamma handle (f-22) keeps the B mean columns alone, P(:, b) = B u_b with u_b = L (V1^T w_b) of chain b (eigenpair.hip:
+// A Polya-Gamma handle (f-22) keeps the B mean columns alone, P(:, b) = B u_b with u_b = L (V1^T w_b) of chain b (eigenpair_pg.hip:
 // pg_operands): a served row's latent is a_i P, its pi, y and label the link's (predictor_rows.hip: predictor_pg_rows_kernel,
 // pg_link_kernel).
 // The joint posterior of served rows (f-23): the K columns of a group are the features z_i, z_i . z_j the latent covariance of

@@ -1,4 +1,5 @@
-"""SHA-256 of what the host and sharded entry points of capi.hip return at small fixed inputs, one line per output.
+"""SHA-256 of what the host and sharded entry points of capi.hip and the resident-pair consumers of eigenpair*.hip that
+no bit fixture pins return at small fixed inputs, one line per output.
 Two builds that issue the same kernels give the same listing on the same GPU: run it on each and diff.
     python scripts/entry_hashes.py [--lib path/to/libflgp_hip.so]"""
 import argparse, ctypes, hashlib, os, sys
@@ -71,6 +72,21 @@ show("hk_from_spectrum ranges", api.HK_from_spectrum_cpp(ep, K, t, *ranges))
 show("hk_from_spectrum gathered", api.HK_from_spectrum_cpp(ep, K, t, gathered0, gathered1))
 res = api.ResidentEigenPair.from_host(ep)
 show("eigenpair_from_host -> hk_from_eigenpair", res.HK_from_spectrum_cpp(K, t, *ranges))
+# the resident-pair consumers that no bit fixture pins (csrc/eigenpair*.hip): m <= K and m > K, rows in place and gathered
+Yr, Yt, Yb = rng.standard_normal((100, 2)), rng.standard_normal(n), (rng.random(100) < 0.5).astype(float)
+for rows, tr, new in (("ranges", ranges[1], ranges[0]), ("gathered", gathered0, gathered1)):
+    for mm in (20, 100):
+        i0, y, yb, tag = tr[:mm], Yr[:mm], Yb[:mm], f"{rows} m={mm}"
+        noises = 0.1 + 0.05 * np.arange(mm) / mm
+        show(f"VtV VtY VC {tag}", res.VtV(K, i0), res.VtY(K, i0, y), res.VC(K, i0, Yr[:K]))
+        show(f"predict_regression same different {tag}", res.predict_regression_cpp(y, i0, new, K, (t, 0.1), 1e-3),
+             res.predict_regression_cpp(y, i0, new, K, (t, *noises), 1e-3, "different"))
+        show(f"posterior_covariance_regression {tag}", res.posterior_covariance_regression(i0, new, K, (t, 0.1), 1e-3))
+        rp = res.regression_posterior(y[:, 0], i0, new, K, (t, 0.1), 1e-3, target=Yt[:new.size])
+        show(f"regression_posterior {tag}", rp["Y_pred"]["train"], rp["Y_pred"]["test"], rp["posterior"]["cov"], np.array([rp["nll"]]))
+        show(f"marginal_log_likelihood_logit_la {tag}", np.array(res.marginal_log_likelihood_logit_la(K, t, i0, yb, return_iters=True)))
+        pc = res.posterior_distribution_classification(i0, new, K, t, yb, 1e-3, 1e-3)
+        show(f"posterior_distribution_classification {tag}", pc["mean"], pc["cov"])
 res.free()
 em = api.lae_eigenmap(X, s, r, 4, U=U)
 show("lae_eigenmap", em["eigenvalues"], em["eigenvectors"])
